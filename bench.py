@@ -7,11 +7,16 @@ A step = ONE TrackFeatures pass over the batch: one kernel launch on device-resi
 (pyramids, ref_uv, predicted cur_uv, status already in HBM) writing (u, v) + status, and for
 N > 1 the RCCL all-gather of every rank's packed result shard.
 
-    python bench.py --gpus 1 --steps 200 --warmup 20
+    python bench.py --gpus 1 --steps 200 --warmup 20 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints one JSON line (contract in the task statement) with these extra objects:
+A plain run sets up, runs W warmup steps, times the K steps and prints one JSON line from rank 0:
+metric, value, unit, higher_is_better, dtype, ms_per_step (wall time of one timed step), the
+workload and the build.  --dump-outputs DIR writes what the last timed step returned, (u, v) and
+status of every feature, as DIR/cur_uv.npy and DIR/status.npy (float32); the inputs are seeded, so
+two builds can be compared output for output.  Everything else is measured only with --full, whose
+line also carries these objects:
   roofline      : algorithmic bytes of the tracker kernel / its average launch duration against the
                   8 TB/s HBM peak (the bound north_star names); traffic = PMC-derived HBM bytes per
                   launch from the committed counter summary under profiles/, else null.
@@ -22,6 +27,7 @@ Rank 0 prints one JSON line (contract in the task statement) with these extra ob
                   device path against the oracle on the same inputs.
   cpu_baseline  : the oracle (CPU restatement, single thread) timed on a bounded sample of the same
                   workload on this host.
+  and throughput_mode, with_pyramid_upload, configs, host_call, real_images, config5_sharded (N > 1).
 The timed region contains ONLY the K steps (no event records); the kernel duration for the roofline
 objects comes from a separate pass of the same launches bracketed by HIP events on the launch stream.
 """
@@ -84,6 +90,26 @@ def pmc_profile(workload: str, source_hash: str):
     if recorded != source_hash:
         return None, f"the committed counters ({w.get('source')}) were taken on build {recorded}; this library is build {source_hash}"
     return w, None
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """--dump-outputs: one DIR/<name>.npy per array, in float32 (float64 stays float64), so that two builds can be compared output
+    for output.  All arrays have one row per feature; if together they exceed 64 MB, the same fixed, seeded sample of rows is written
+    from every array, with the sampled row indices as sample_rows.npy."""
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    arrays = {k: v.astype(np.float64 if v.dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    if sum(a.nbytes for a in arrays.values()) > DUMP_LIMIT_BYTES:
+        rows = min(a.shape[0] for a in arrays.values())
+        row_bytes = sum(a.nbytes // max(1, a.shape[0]) for a in arrays.values()) + 8
+        idx = np.sort(np.random.RandomState(0).choice(rows, min(rows, DUMP_LIMIT_BYTES // row_bytes), replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["sample_rows"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 def parity_report(gpu_uv, gpu_st, cpu_uv, cpu_st) -> dict:
@@ -745,6 +771,9 @@ def run_sharded(args, cfg, world, rank, local_rank, dev, use_dist):
         elapsed = time.perf_counter() - t0
         guv, gst = FD.unpack_gathered(sharded.gathered, n, world)
         tracked = float((gst == 1).float().mean().item())
+        if args.dump_outputs and rank == 0:  # the last step's gathered result, in global feature order
+            last_uv, last_st = FD.unpack_gathered(slots[(args.steps - 1) & 1].gathered, n, world)
+            dump_outputs(args.dump_outputs, {"cur_uv": last_uv.cpu().numpy(), "status": last_st.cpu().numpy()})
         # result check: the gathered result must equal ONE unsharded launch over all n features on this rank, bit for bit
         d_all, d_all_st = torch.empty_like(d_ref), torch.empty_like(d_st)
         klt.track(d_ref, d_in, d_st, d_all, d_all_st, None)
@@ -816,6 +845,8 @@ def run_native_comm(args, cfg, world, rank, local_rank, dev):
         if world > 1:
             dist.barrier()
         elapsed = time.perf_counter() - t0
+        if args.dump_outputs and rank == 0:  # every step writes the whole gathered result into the same buffers
+            dump_outputs(args.dump_outputs, {"cur_uv": d_out.cpu().numpy(), "status": d_sto.cpu().numpy()})
         # result check: this rank's block of the gathered result == its own unsharded launch on that block
         b, e = D.shard_bounds(n, world, rank)
         d_chk, d_chk_st = torch.empty(e - b, 2, dtype=torch.float32, device=dev), torch.empty(e - b, dtype=torch.uint8, device=dev)
@@ -842,7 +873,7 @@ def run_native_comm(args, cfg, world, rank, local_rank, dev):
                        "parallelism": f"features sharded x{world}, pyramids replicated, one ncclAllGather of packed (uv,status) per step issued by "
                                       "libftk_hip.so (ftk_klt_track_sharded_device) + scatter kernel; plain per-step loop",
                        "tracked_fraction": tracked, "gathered_block_equals_local_launch": ok}}
-    if dist.is_initialized() and not args.no_config5_leg:
+    if args.full and dist.is_initialized() and not args.no_config5_leg:
         leg = run_config5_leg(args, world, rank, local_rank, dev, ctx, stream, out)
         if out is not None:
             out["config5_sharded"] = leg
@@ -1017,9 +1048,16 @@ def main():
     ap.add_argument("--dry-launch", action="store_true",
                     help="rank plumbing only: gloo on the CPU, no device work (CPU test of the N-rank launch)")
     ap.add_argument("--launch-timeout", type=float, default=1500.0, help="self-launched N > 1 runs: seconds before the ranks are ended")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: roofline passes, parity against the CPU oracle, cpu_baseline, throughput_mode, "
+                         "with_pyramid_upload, configs, host_call, real_images and (N > 1) config5_sharded; off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the arrays the timed path returned in its last step to DIR/<name>.npy (float32)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
 
     # Who starts the ranks.  Under a launcher (torchrun: WORLD_SIZE is set) this process IS one rank.  Without one,
     # `--gpus N > 1` starts its own N ranks as children BEFORE anything touches torch or HIP, so that the plain
@@ -1114,14 +1152,9 @@ def main():
             step()
         stream.synchronize()
 
-        first_uv, first_st = d_cur_out.cpu().numpy().copy(), status.copy()  # the first step's result, for the parity object
+        if args.full:
+            first_uv, first_st = d_cur_out.cpu().numpy().copy(), status.copy()  # the first step's result, for the parity object
         launches = [klt.bind(d_ref, d_cur_in, d_st_in, views2[slot][0], views2[slot][1], None) for slot in range(2)]
-        # kernel-only duration (roofline objects): HIP events on the launch stream around the same launches on the same
-        # data in a SEPARATE pass after the timed region — an event pair costs about a tenth of this kernel in queue
-        # time, so none is recorded between the K timed steps at any step count.
-        n_ev = max(10, min(args.steps, 50))
-        ev0 = {k: torch.cuda.Event(enable_timing=True) for k in range(n_ev)}
-        ev1 = {k: torch.cuda.Event(enable_timing=True) for k in range(n_ev)}
 
         # N > 1: every step is the tracker kernel followed by the RCCL all-gather of its packed result shard.  The
         # K steps are captured ONCE into a HIP graph in which the gather of step k runs on a side stream beside the
@@ -1199,28 +1232,45 @@ def main():
         if use_dist:
             dist.barrier()
         elapsed = time.perf_counter() - t0
-        # kernel duration for the roofline objects: a short eager pass right after the timed region (same launches, same data)
-        for k in ev0:
-            ev0[k].record(stream)
-            launches[k & 1]()
-            ev1[k].record(stream)
-        torch.cuda.synchronize()
-        # The kernel's average launch duration for the roofline objects: ONE event pair around a batch of back-to-back launches
-        # (no event between them), divided by the batch size.  It contains the inter-launch gap, so it can only OVERSTATE the
-        # kernel time (an event pair around a single launch adds ~5 us of marker cost: that figure is given beside it, and
-        # subtracting a separately measured "empty pair" over-corrects — it came out 10 % BELOW the rocprofv3 trace average).
-        batch0, batch1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        batch_n = max(20, min(args.steps, 200))
-        batch0.record(stream)
-        for k in range(batch_n):
-            launches[k & 1]()
-        batch1.record(stream)
-        torch.cuda.synchronize()
-        kernel_ms_batch = batch0.elapsed_time(batch1) / batch_n
+        if args.dump_outputs and rank == 0:
+            # what a caller of the timed path receives from its last step: (u, v) and status of every feature; with N > 1 the
+            # gathered result of all ranks, in rank order
+            last = (args.steps - 1) & 1
+            if use_dist:
+                per = FD.packed_bytes(n)
+                shards = [FD.pack_views(gathered2[last][r * per:(r + 1) * per], n) for r in range(world)]
+                out_uv, out_st = torch.cat([v[0] for v in shards]), torch.cat([v[1] for v in shards])
+            else:
+                out_uv, out_st = views2[last]
+            dump_outputs(args.dump_outputs, {"cur_uv": out_uv.cpu().numpy(), "status": out_st.cpu().numpy()})
+        if args.full:
+            # kernel-only duration (roofline objects): HIP events on the launch stream around the same launches on the same
+            # data in a SEPARATE pass after the timed region — an event pair costs about a tenth of this kernel in queue
+            # time, so none is recorded between the K timed steps at any step count.
+            n_ev = max(10, min(args.steps, 50))
+            ev0 = {k: torch.cuda.Event(enable_timing=True) for k in range(n_ev)}
+            ev1 = {k: torch.cuda.Event(enable_timing=True) for k in range(n_ev)}
+            for k in ev0:
+                ev0[k].record(stream)
+                launches[k & 1]()
+                ev1[k].record(stream)
+            torch.cuda.synchronize()
+            # The kernel's average launch duration for the roofline objects: ONE event pair around a batch of back-to-back launches
+            # (no event between them), divided by the batch size.  It contains the inter-launch gap, so it can only OVERSTATE the
+            # kernel time (an event pair around a single launch adds ~5 us of marker cost: that figure is given beside it, and
+            # subtracting a separately measured "empty pair" over-corrects — it came out 10 % BELOW the rocprofv3 trace average).
+            batch0, batch1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            batch_n = max(20, min(args.steps, 200))
+            batch0.record(stream)
+            for k in range(batch_n):
+                launches[k & 1]()
+            batch1.record(stream)
+            torch.cuda.synchronize()
+            kernel_ms_batch = batch0.elapsed_time(batch1) / batch_n
         # Throughput mode (ftk_set_reduction_mode(TREE)): the same launches with butterfly sums instead of the exact-order chains.
         # Reported beside the contract path — what bit-exactness costs — never asserted and never the headline.
         tree = None
-        if world == 1 and not args.no_tree_leg:
+        if args.full and world == 1 and not args.no_tree_leg:
             ctx.set_reduction("tree")
             try:
                 tree_out = (torch.empty_like(views2[1][0]), torch.empty_like(views2[1][1]))
@@ -1237,10 +1287,10 @@ def main():
             finally:
                 ctx.set_reduction("exact")
         upload = None
-        if world == 1 and args.features == 0 and not args.no_upload_leg:
+        if args.full and world == 1 and args.features == 0 and not args.no_upload_leg:
             upload = with_pyramid_upload(args, cfg, ctx, klt, opt, ref_img, cur_img, d_ref, d_cur_in, d_st_in, n, levels, stream, views2[1])
         configs_leg, host_call = None, None
-        if world == 1 and args.features == 0 and not args.no_configs_leg:
+        if args.full and world == 1 and args.features == 0 and not args.no_configs_leg:
             from feature_tracker_amd import _native as NL0
             src_hash = NL0.build_info().get("source_hash")
             k_cfg = max(20, min(args.steps, 100))
@@ -1256,15 +1306,15 @@ def main():
             # the reference's default method (kFast) of the other two trackers, at sizes their one-wave kernels serve
             configs_leg["affine_fast_5000_13x13"] = tracker_config_leg("affine_fast", dict(synth.CONFIGS["config3"], width=640, height=480, levels=4, method="fast"), k_cfg, ctx, dev, stream, src_hash)
             configs_leg["seconds_spent"] = time.perf_counter() - t_cfg
-        if world == 1 and args.features == 0 and not args.no_host_call_leg:
+        if args.full and world == 1 and args.features == 0 and not args.no_host_call_leg:
             host_call = host_call_leg(cfg, ref_levels, cur_levels, uv, first_uv, first_st)
         real_images = None
-        if world == 1 and args.features == 0 and not args.no_real_images_leg:
+        if args.full and world == 1 and args.features == 0 and not args.no_real_images_leg:
             try:
                 real_images = real_images_leg(max(20, min(args.steps, 100)), ctx, dev, stream)
             except (ImportError, FileNotFoundError) as exc:  # no PIL / no data files on this machine: say so in the line
                 real_images = {"skipped": f"{type(exc).__name__}: {exc}"}
-        if use_dist:
+        if args.full and use_dist:
             # every rank must now hold every rank's result shard: spot-check the own shard inside the gathered buffer
             per = FD.packed_bytes(n)
             for slot in range(min(2, args.steps)):
@@ -1276,22 +1326,10 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    kernel_ms_bracketed = float(np.mean([ev0[k].elapsed_time(ev1[k]) for k in ev0]))
-    kernel_ms = float(kernel_ms_batch)  # the ONE kernel time both roofline objects use
-    # the LAST launch's result as well: calls of >= 4096 features go through the longest-first launch order from the third call on
-    # (ftk_klt_track_device), so the first step alone would not show that the ordered launches return the same bits
-    last_uv, last_st = views2[0][0].cpu().numpy().copy(), views2[0][1].cpu().numpy().copy()
     if rank == 0:
-        total_features = n * world * args.steps
-        value = total_features / elapsed
-        algo = algorithmic_bytes(iters, levels, half, cfg["method"])
-        achieved = algo / (kernel_ms * 1e-3) / 1e9
+        value = n * world * args.steps / elapsed
         from feature_tracker_amd import _native as NL
         build = NL.build_info()
-        pmc, pmc_refused = pmc_profile(args.workload, build.get("source_hash")) if args.features == 0 else (None, "--features overrides the workload")
-        pmc = pmc or {}
-        kernel_name = "klt_basic_inverse_pipelined_kernel" if (cfg["model"], cfg["method"]) == ("basic", "inverse") else f"klt_track_kernel<{cfg['model']}, {cfg['method']}>"
-        cpu_uv, cpu_st, cpu_it, _ = oracle_once(cfg, ref_levels, cur_levels, uv)
         out = {
             "metric": "tracked features/sec (2000 pts, 640x480, 4-lvl pyr)", "value": value, "unit": "tracked features/s",
             "n_gpus": world, "rccl_ranks": rccl_ranks, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
@@ -1301,6 +1339,24 @@ def main():
                                        + (", steps captured in one HIP graph (gather k overlaps kernel k+1)" if graph is not None else ""))
                        if use_dist else "single GPU",
                        "tracked_fraction": float((status == 1).mean()), "mean_iterations_per_feature": float(iters.mean())},
+            "build": build,
+        }
+    else:
+        out = None
+    if args.full:
+        kernel_ms_bracketed = float(np.mean([ev0[k].elapsed_time(ev1[k]) for k in ev0]))
+        kernel_ms = float(kernel_ms_batch)  # the ONE kernel time both roofline objects use
+        # the LAST launch's result as well: calls of >= 4096 features go through the longest-first launch order from the third call on
+        # (ftk_klt_track_device), so the first step alone would not show that the ordered launches return the same bits
+        last_uv, last_st = views2[0][0].cpu().numpy().copy(), views2[0][1].cpu().numpy().copy()
+    if args.full and rank == 0:
+        algo = algorithmic_bytes(iters, levels, half, cfg["method"])
+        achieved = algo / (kernel_ms * 1e-3) / 1e9
+        pmc, pmc_refused = pmc_profile(args.workload, build.get("source_hash")) if args.features == 0 else (None, "--features overrides the workload")
+        pmc = pmc or {}
+        kernel_name = "klt_basic_inverse_pipelined_kernel" if (cfg["model"], cfg["method"]) == ("basic", "inverse") else f"klt_track_kernel<{cfg['model']}, {cfg['method']}>"
+        cpu_uv, cpu_st, cpu_it, _ = oracle_once(cfg, ref_levels, cur_levels, uv)
+        out.update({
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
                          "traffic": pmc.get("bytes_per_launch"), "traffic_source": pmc.get("source"), "traffic_refused": pmc_refused,
                          "kernel": kernel_name, "kernel_ms": kernel_ms, "kernel_launches_timed": len(ev0),
@@ -1309,10 +1365,9 @@ def main():
                          "kernel_ms_single_launch_event_pair": kernel_ms_bracketed,
                          "kernel_ms_rocprofv3_trace_this_build": (pmc.get("trace_average_ns") or 0) * 1e-6 or None,
                          "algorithmic_bytes_per_launch": algo},
-            "build": build,
             "parity": dict(parity_report(first_uv, first_st, cpu_uv, cpu_st), iteration_counts_equal=bool(np.array_equal(iters, cpu_it)),
                            last_launch_bit_identical=bool(np.array_equal(last_uv.view(np.uint32), cpu_uv.view(np.uint32)) and np.array_equal(last_st, cpu_st))),
-        }
+        })
         if pmc.get("valu_insts_per_launch"):
             valu = pmc["valu_insts_per_launch"] / (kernel_ms * 1e-3)
             out["roofline_valu"] = {"bound": "valu_issue", "achieved": valu, "peak": VALU_PEAK_DATASHEET, "unit": "wave64 VALU instructions/s",
@@ -1353,10 +1408,8 @@ def main():
             out["configs"] = configs_leg
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg, ref_levels, cur_levels, uv)
-    else:
-        out = None
-    if use_dist and not args.no_config5_leg:
-        # BASELINE.json configs[4] (200 000 features sharded over the ranks): measured by every N > 1 run, after the weak-scaling region
+    if args.full and use_dist and not args.no_config5_leg:
+        # BASELINE.json configs[4] (200 000 features sharded over the ranks): measured by every N > 1 --full run, after the weak-scaling region
         leg = run_config5_leg(args, world, rank, local_rank, dev, ctx, stream, out)
         if out is not None:
             out["config5_sharded"] = leg

@@ -1,5 +1,5 @@
 #!/bin/bash
-# GPU box: runs the reference's own test programs (compiled unchanged by scripts/check_dropin.sh) on the reference's example
+# GPU box: runs the reference's own test programs (compiled unchanged by oracle/check_dropin.sh) on the reference's example
 # images and prints the times THEY report; FTK_HOST_PYRAMID=1 shows the same with the host-side pyramid loop for comparison.
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 T=$(mktemp -d); mkdir -p $T/example $T/build
@@ -10,11 +10,11 @@ for mode in device host; do
   [ $mode = host ] && export FTK_HOST_PYRAMID=1 || unset FTK_HOST_PYRAMID
   echo "=== pyramids built on the $mode"
   for p in test_optical_flow test_descriptor_matcher_brief test_descriptor_matcher_superpoint test_direct_method; do
-    echo "--- $p"; $ROOT/feature_tracker_amd/host/build/dropin/$p 2>&1 | grep -a -i "cost time\|track\|match" | sed 's/\x1b\[[0-9;]*m//g' | head -8
+    echo "--- $p"; $ROOT/oracle/_ref/dropin/$p 2>&1 | grep -a -i "cost time\|track\|match" | sed 's/\x1b\[[0-9;]*m//g' | head -8
   done
   # the tracker program's spans are a few hundred microseconds of host + device work: three more runs show the spread
   for i in 2 3 4; do
-    echo "--- test_optical_flow, run $i"; $ROOT/feature_tracker_amd/host/build/dropin/test_optical_flow 2>&1 | grep -a -i "cost time" | sed 's/\x1b\[[0-9;]*m//g'
+    echo "--- test_optical_flow, run $i"; $ROOT/oracle/_ref/dropin/test_optical_flow 2>&1 | grep -a -i "cost time" | sed 's/\x1b\[[0-9;]*m//g'
   done
 done
 echo "=== bench_cli n=300 / n=2000"

@@ -5,7 +5,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 for w in ${*:-config3 config4 config5_shard config2}; do
   for s in 1 0; do
     echo "== $w FTK_KLT_SCHED=$s"
-    FTK_KLT_SCHED=$s python3 $ROOT/bench.py --workload $w --steps 50 --warmup 5 --no-cpu-baseline 2>/dev/null | python3 -c "
+    FTK_KLT_SCHED=$s python3 $ROOT/bench.py --full --workload $w --steps 50 --warmup 5 --no-cpu-baseline 2>/dev/null | python3 -c "
 import sys, json
 for l in sys.stdin:
     try: d = json.loads(l)

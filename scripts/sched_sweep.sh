@@ -1,7 +1,7 @@
 #!/bin/bash
 # Experiment (GPU box): with the longest-first launch order in place, do more resident waves pay?  (packing / waves per feature)
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
-run() { w=$1; shift; echo "== $w $*"; env "$@" python3 $ROOT/bench.py --workload $w --steps 40 --warmup 5 --no-cpu-baseline 2>/dev/null | python3 -c "
+run() { w=$1; shift; echo "== $w $*"; env "$@" python3 $ROOT/bench.py --full --workload $w --steps 40 --warmup 5 --no-cpu-baseline 2>/dev/null | python3 -c "
 import sys, json
 for l in sys.stdin:
     try: d = json.loads(l)

@@ -7,7 +7,7 @@ for w in ${*:-config3 config4}; do
   for t in default $TAGS; do
     echo "== $w $t"
     if [ $t = default ]; then unset FTK_LIB_PATH; else export FTK_LIB_PATH=$ROOT/feature_tracker_amd/csrc/diag/libftk_hip_$t.so; fi
-    python3 $ROOT/bench.py --workload $w --steps 40 --warmup 5 --no-cpu-baseline 2>/dev/null | python3 -c "
+    python3 $ROOT/bench.py --full --workload $w --steps 40 --warmup 5 --no-cpu-baseline 2>/dev/null | python3 -c "
 import sys, json
 for l in sys.stdin:
     try: d = json.loads(l)

@@ -95,8 +95,8 @@ CONFIG5_TORCH_KEYS = {"ms_per_step", "features_per_s", "ms_per_step_plain_loop",
 
 
 def test_two_ranks_produce_the_config5_sharded_object_without_extra_flags():
-    # `bench.py --gpus N` (N > 1) with the DRIVER's arguments must carry BASELINE configs[4] — 200 000 features sharded
-    # over the ranks, one all-gather per step — in its one line.  The dry launch runs the same config5_sharded_leg() the GPU run calls
+    # `bench.py --gpus N --full` (N > 1) must carry BASELINE configs[4] — 200 000 features sharded over the ranks, one
+    # all-gather per step — in its one line; the dry launch rehearses that object on every call.  The dry launch runs the same config5_sharded_leg() the GPU run calls
     # (step loop, slots, timing reductions, gathered == unsharded), over gloo around a stand-in tracker: schema and bookkeeping at 2 ranks.
     res = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "20", "--warmup", "5", "--dry-launch"], env=_env(), capture_output=True, text=True, timeout=300)
     assert res.returncode == 0, res.stderr[-2000:]
@@ -106,3 +106,30 @@ def test_two_ranks_produce_the_config5_sharded_object_without_extra_flags():
     assert c5["torch"]["gathered_equals_unsharded_bitwise"] is True
     assert c5["torch"]["ms_per_step"] > 0 and c5["torch"]["kernel_us"] > 0 and c5["torch"]["all_gather_us"] > 0
     assert abs(c5["torch"]["features_per_s"] - 200000 / (c5["torch"]["ms_per_step"] * 1e-3)) < 1e-3 * c5["torch"]["features_per_s"]
+
+
+def test_dump_outputs_writes_float32_and_a_fixed_sample_past_the_limit(tmp_path, monkeypatch):
+    import numpy as np
+
+    import bench
+
+    uv = np.arange(20, dtype=np.float32).reshape(10, 2)
+    st = (np.arange(10) % 3).astype(np.uint8)
+    bench.dump_outputs(str(tmp_path / "small"), {"cur_uv": uv, "status": st})
+    got_uv, got_st = np.load(tmp_path / "small" / "cur_uv.npy"), np.load(tmp_path / "small" / "status.npy")
+    assert got_uv.dtype == np.float32 and np.array_equal(got_uv, uv)
+    assert got_st.dtype == np.float32 and np.array_equal(got_st, st.astype(np.float32))
+    assert sorted(os.listdir(tmp_path / "small")) == ["cur_uv.npy", "status.npy"]
+    # past the size limit: the same seeded rows of every array, their indices beside them, within the limit
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4000)
+    uv = np.arange(2000, dtype=np.float32).reshape(1000, 2)
+    st = (np.arange(1000) % 3).astype(np.uint8)
+    for d in ("big1", "big2"):
+        bench.dump_outputs(str(tmp_path / d), {"cur_uv": uv, "status": st})
+    rows = np.load(tmp_path / "big1" / "sample_rows.npy")
+    assert np.array_equal(rows, np.load(tmp_path / "big2" / "sample_rows.npy"))
+    assert 0 < rows.size < 1000 and np.all(np.diff(rows) > 0)
+    idx = rows.astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "big1" / "cur_uv.npy"), uv[idx])
+    assert np.array_equal(np.load(tmp_path / "big1" / "status.npy"), st[idx].astype(np.float32))
+    assert sum(os.path.getsize(tmp_path / "big1" / f) for f in os.listdir(tmp_path / "big1")) <= 4000 + 3 * 128  # + .npy headers

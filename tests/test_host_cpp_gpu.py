@@ -149,8 +149,9 @@ def test_cpp_float_matcher_matches_oracle(tmp_path, oracle, mode, dim):
     assert np.array_equal(got[ost == 1], omatched[ost == 1])
 
 
-MISSING_DROPIN = ("feature_tracker_amd/host/build/dropin/ is missing: the reference's own caller programs are compiled unchanged by build() "
-                  "(scripts/check_dropin.sh) in the container where /root/reference is mounted and travel to the GPU box as build artefacts.  A box "
+DROPIN = os.path.join(ROOT, "oracle", "_ref", "dropin")
+MISSING_DROPIN = ("oracle/_ref/dropin/ is missing: the reference's own caller programs are compiled unchanged by build() "
+                  "(oracle/check_dropin.sh) where the reference checkout is present and travel with the tree as build artefacts.  A machine "
                   "without them has NOT exercised the drop-in boundary, so this is a failure, not a skip (VERDICT r4 item 9).")
 
 
@@ -159,10 +160,10 @@ MISSING_DROPIN = ("feature_tracker_amd/host/build/dropin/ is missing: the refere
                                          ("test_descriptor_matcher_disk", r"tracked features (\d+) / (\d+)")])
 def test_reference_callers_run_unchanged(tmp_path, prog, expect):
     """The reference's own test programs, compiled UNCHANGED against this repo's headers / libraries by
-    scripts/check_dropin.sh (only possible where the reference is mounted; the binaries travel as build artefacts),
+    oracle/check_dropin.sh (only possible where the reference is present; the binaries travel as build artefacts),
     run headless on the GPU with the reference's example images at the relative path they hard-code."""
     import re
-    exe = os.path.join(BUILD, "dropin", prog)
+    exe = os.path.join(DROPIN, prog)
     if not os.path.exists(exe):
         pytest.fail(MISSING_DROPIN)
     os.makedirs(tmp_path / "example", exist_ok=True)
@@ -178,13 +179,13 @@ def test_reference_callers_run_unchanged(tmp_path, prog, expect):
 
 
 def test_reference_direct_method_program_matches_oracle(tmp_path, oracle):
-    """The reference's own test_direct_method.cpp, compiled unchanged (scripts/check_dropin.sh), on its own example
+    """The reference's own test_direct_method.cpp, compiled unchanged (oracle/check_dropin.sh), on its own example
     frames: 300 std::rand() points with stereo depth, 5 frames, 5-level pyramids.  The poses it prints must be the
     oracle's for the same inputs (the program prints ~6 significant digits; the ABI-level tests compare bit for bit)."""
     import ctypes
     import re
     from PIL import Image
-    exe = os.path.join(BUILD, "dropin", "test_direct_method")
+    exe = os.path.join(DROPIN, "test_direct_method")
     if not os.path.exists(exe):
         pytest.fail(MISSING_DROPIN)
     data = os.path.join(ROOT, "tests", "data", "direct_method")
