@@ -31,6 +31,7 @@ EXPORTS = [
     "ftk_brief_compute", "ftk_brief_compute_device", "ftk_harris_detect", "ftk_harris_response",
     "ftk_shard_bounds", "ftk_klt_shard_bytes", "ftk_comm_unique_id", "ftk_comm_create", "ftk_comm_destroy", "ftk_comm_rank", "ftk_comm_world",
     "ftk_klt_track_sharded_device", "ftk_klt_track_sharded", "ftk_klt_track_shard_device", "ftk_klt_unpack_shards_device", "ftk_hamming_match_sharded_device",
+    "ftk_default_dense_flow_options", "ftk_dense_flow_gaussian", "ftk_dense_flow", "ftk_dense_flow_device", "ftk_dense_flow_level",
 ]
 UNIQUE_ID_BYTES = 128
 
@@ -58,6 +59,14 @@ class DirectOptions(C.Structure):
     _fields_ = [
         ("max_track_points", C.c_uint32), ("max_iteration", C.c_uint32), ("half_rows", C.c_int32), ("half_cols", C.c_int32),
         ("max_converge_step", C.c_float), ("max_converge_residual", C.c_float), ("method", C.c_int32),
+    ]
+
+
+class DenseFlowOptions(C.Structure):
+    """DenseOpticalFlow::Options (dense_optical_flow.h:15-20) + the object's {k2, k4, k22} for half patch 0."""
+    _fields_ = [
+        ("max_iteration", C.c_int32), ("half_patch", C.c_int32), ("max_converge_step", C.c_float), ("max_delta_flow_step", C.c_float),
+        ("k_moments", C.c_float * 3),
     ]
 
 
@@ -164,6 +173,12 @@ def lib() -> C.CDLL:
     l.ftk_klt_track_shard_device.argtypes = [vp, i32, i32, C.c_int, C.POINTER(KltOptions), vp, vp, vp, vp, vp, i32, vp, C.c_int, C.c_int, vp, vp]
     l.ftk_klt_unpack_shards_device.argtypes = [vp, vp, i32, i32, vp, vp]
     l.ftk_hamming_match_sharded_device.argtypes = [vp, vp, vp, i32, vp, i32, i32, i32, C.c_float, vp, vp, i32, i32, vp]
+    l.ftk_default_dense_flow_options.argtypes = [C.POINTER(DenseFlowOptions)]
+    l.ftk_default_dense_flow_options.restype = None
+    l.ftk_dense_flow_gaussian.argtypes = [i32, vp, vp]
+    l.ftk_dense_flow.argtypes = [vp, C.POINTER(DenseFlowOptions), vp, vp, vp, vp]
+    l.ftk_dense_flow_device.argtypes = [vp, C.POINTER(DenseFlowOptions), vp, vp, vp, vp]
+    l.ftk_dense_flow_level.argtypes = [vp, C.POINTER(DenseFlowOptions), vp, vp, i32, vp, vp, i32]
     _lib = l
     return l
 

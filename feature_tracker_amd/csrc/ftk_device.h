@@ -294,6 +294,42 @@ struct HarrisParams {
 };
 hipError_t harris_launch(const HarrisParams &p, hipStream_t stream);
 
+// Dense optical flow (dense_flow_kernels.hip, DenseOpticalFlow).  Moments: two float4 per pixel, {S0, Sr, Sc, Src} then {Srr, Scc, 0, 0},
+// row-major at the image's own size; flow planes row-major at the ref level's size.
+struct DenseMomentsParams {
+    DevImage img[2];       // ref, cur of one level
+    float4 *mom[2];        // their moment images
+    const float *weights;  // (2 half + 1)^2 normalised Gaussian weights, row-major (ftk_dense_flow_gaussian)
+    int32_t half;
+};
+struct DenseFlowParams {
+    const float4 *mom_ref;
+    const float4 *mom_cur;
+    int32_t ref_rows, ref_cols, cur_rows, cur_cols;
+    float k2, k4, k22;
+    int32_t max_iteration;
+    float converge;  // kMaxConvergeStep
+    float max_step;  // kMaxDeltaFlowStep
+    int32_t init;    // 0: zero flow; 1: init_r / init_c at ref size where flow_valid's bit is set (may alias out_*); 2: upsample init_* (init_rows x init_cols)
+    int32_t flow_valid;
+    const float *init_r;
+    const float *init_c;
+    int32_t init_rows, init_cols;
+    float *out_r;
+    float *out_c;
+};
+struct DenseMedianParams {
+    const float *in_r;
+    const float *in_c;
+    float *out_r;
+    float *out_c;
+    int32_t rows, cols;
+};
+int dense_lds_half();  // largest half patch the moments kernel stages in LDS (above: global reads, same arithmetic)
+hipError_t dense_moments_launch(const DenseMomentsParams &p, hipStream_t stream);
+hipError_t dense_flow_launch(const DenseFlowParams &p, hipStream_t stream);
+hipError_t dense_median_launch(const DenseMedianParams &p, hipStream_t stream);
+
 // Scatter of the all-gathered packed tracker shards into (cur_uv, status) in global feature order (ftk_comm.cpp).
 hipError_t unpack_klt_shards_launch(const uint8_t *d_gathered, int32_t n, int32_t world, int32_t cap, int64_t shard_bytes, float *d_uv_out,
                                     uint8_t *d_status_out, hipStream_t stream);
@@ -320,5 +356,6 @@ hipError_t cosine_warm(hipStream_t stream);
 hipError_t direct_warm(hipStream_t stream);
 hipError_t pyramid_warm(hipStream_t stream);
 hipError_t feature_warm(hipStream_t stream);
+hipError_t dense_warm(hipStream_t stream);
 
 }  // namespace ftk

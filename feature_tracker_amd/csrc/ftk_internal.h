@@ -124,6 +124,11 @@ struct ftk_context {
     // pinned host staging for the host-buffer entry points (one H2D + one D2H per call)
     void *pinned = nullptr;
     size_t pinned_bytes = 0;
+    // dense optical flow: moment images + flow planes (grown only outside a stream capture) and the Gaussian table of dense_half
+    void *dense_ws = nullptr;
+    size_t dense_ws_bytes = 0;
+    float *dense_weights = nullptr;
+    int32_t dense_half = -1;
     // BRIEF sampling pattern resident on the device, cached per (n_bits, half)
     int8_t *brief_pattern = nullptr;
     int32_t brief_bits = 0, brief_half = 0;

@@ -256,3 +256,20 @@ class DeviceDirectBatch:
 
     def track(self):
         N.check(N.lib().ftk_direct_track_batch_device(self.ctx.handle, C.byref(self.opt), self.table, self.n), self.ctx.handle)
+
+
+def dense_flow_device(ctx: Context, options, ref_pyr: ImagePyramid, cur_pyr: ImagePyramid, flow_r, flow_c, k_moments=(0.0, 0.0, 0.0)) -> None:
+    """ftk_dense_flow_device: Farneback dense flow of the two pyramids into ``flow_r`` / ``flow_c`` (contiguous float32 CUDA tensors of
+    level 0's ref shape), enqueued on the context's stream; no synchronisation, capturable once an uncaptured call of the same shape
+    and half patch has made the workspace resident.  ``options``: a DenseOpticalFlowOptions or a native DenseFlowOptions;
+    ``k_moments`` are the k2 / k4 / k22 a half patch of 0 uses."""
+    from .tracker import DenseOpticalFlowOptions
+
+    opt = options.to_native(k_moments) if isinstance(options, DenseOpticalFlowOptions) else options
+    _, rows, cols = ref_pyr.level_desc(0)
+    for t in (flow_r, flow_c):
+        if str(t.dtype) != "torch.float32" or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != (rows, cols):
+            raise ValueError(f"flow planes must be contiguous float32 CUDA tensors of shape ({rows}, {cols})")
+    rc = N.lib().ftk_dense_flow_device(ctx.handle, C.byref(opt), ref_pyr.handle, cur_pyr.handle, C.c_void_p(flow_r.data_ptr()),
+                                       C.c_void_p(flow_c.data_ptr()))
+    N.check(rc, ctx.handle)

@@ -5,12 +5,14 @@
 #ifndef _SLAM_UTILITY_BASIC_TYPE_H_
 #define _SLAM_UTILITY_BASIC_TYPE_H_
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <initializer_list>
 #include <limits>
 #include <string>
+#include <utility>
 #include <vector>
 
 template <int R, int C>
@@ -218,6 +220,53 @@ public:
 
 private:
     float x_, y_, z_, w_;  // Eigen's coefficient order
+};
+
+// Dynamic float matrix (Eigen::MatrixXf's role in the reference: the dense flow planes, dense_optical_flow.h:27,45-64), column-major
+// like Eigen's default.  Only what the reference's DenseOpticalFlow, its header and its demo use.
+class Mat {
+public:
+    Mat() = default;
+    Mat(int32_t rows, int32_t cols) { resize(rows, cols); }
+    Mat(const Mat &) = default;
+    Mat &operator=(const Mat &) = default;
+    Mat(Mat &&o) noexcept : d_(std::move(o.d_)), rows_(o.rows_), cols_(o.cols_) {
+        o.rows_ = 0;
+        o.cols_ = 0;
+    }
+    Mat &operator=(Mat &&o) noexcept {
+        if (this != &o) {
+            d_ = std::move(o.d_);
+            rows_ = o.rows_;
+            cols_ = o.cols_;
+            o.d_.clear();
+            o.rows_ = 0;
+            o.cols_ = 0;
+        }
+        return *this;
+    }
+
+    void resize(int32_t rows, int32_t cols) {
+        rows_ = rows > 0 ? rows : 0;
+        cols_ = cols > 0 ? cols : 0;
+        d_.resize(static_cast<size_t>(rows_) * cols_);
+    }
+    void setZero() { std::fill(d_.begin(), d_.end(), 0.0f); }
+    void setZero(int32_t rows, int32_t cols) {
+        resize(rows, cols);
+        setZero();
+    }
+    int32_t rows() const { return rows_; }
+    int32_t cols() const { return cols_; }
+    float &operator()(int32_t r, int32_t c) { return d_[static_cast<size_t>(c) * rows_ + r]; }
+    const float &operator()(int32_t r, int32_t c) const { return d_[static_cast<size_t>(c) * rows_ + r]; }
+    float *data() { return d_.data(); }
+    const float *data() const { return d_.data(); }
+
+private:
+    std::vector<float> d_;
+    int32_t rows_ = 0;
+    int32_t cols_ = 0;
 };
 
 constexpr int32_t kMaxInt32 = std::numeric_limits<int32_t>::max();

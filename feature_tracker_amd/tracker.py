@@ -653,3 +653,92 @@ class DirectMethod:
         out_q = _quat_mul(ref_q_wc, q_rc)
         out_p = (_quat_rotate(ref_q_wc, p_rc) + ref_p_wc).astype(np.float32)
         return True, cur_uv, out_q, out_p, st
+
+
+class DenseOpticalFlowOptions:
+    """DenseOpticalFlow::Options (dense_optical_flow.h:15-20) — same field names and defaults."""
+
+    def __init__(self):
+        self.kMaxIteration = 10
+        self.kHalfPatchSize = 2
+        self.kMaxConvergeStep = 1e-6
+        self.kMaxDeltaFlowStep = 1.0
+
+    def to_native(self, k_moments=(0.0, 0.0, 0.0)) -> N.DenseFlowOptions:
+        o = N.DenseFlowOptions()
+        o.max_iteration = int(self.kMaxIteration)
+        o.half_patch = int(self.kHalfPatchSize)
+        o.max_converge_step = float(self.kMaxConvergeStep)
+        o.max_delta_flow_step = float(self.kMaxDeltaFlowStep)
+        for i in range(3):
+            o.k_moments[i] = float(k_moments[i])
+        return o
+
+
+def dense_flow_gaussian(half_patch: int, k=(0.0, 0.0, 0.0)):
+    """ftk_dense_flow_gaussian (host only, no device): (weights [(2h+1), (2h+1)], k = [k2, k4, k22]); for half patch 0 the table is
+    [1] and k is returned as passed (dense_optical_flow.cpp:95-98)."""
+    size = 2 * int(half_patch) + 1
+    w = np.zeros((max(size, 1), max(size, 1)), np.float32)
+    kk = np.array(k, dtype=np.float32)
+    N.check(N.lib().ftk_dense_flow_gaussian(int(half_patch), _ptr(w), _ptr(kk)), None)
+    return w, kk
+
+
+class DenseOpticalFlow:
+    """feature_tracker::DenseOpticalFlow (dense_optical_flow.h:12-65): Farneback dense flow, every pixel on the device.
+
+    ``Track(ref, cur, flow_rc=None)`` takes two ImagePyramid objects (pyramid overload, dense_optical_flow.cpp:35-85) or two 2-D uint8
+    images (image overload, :7-33) and returns ``(ok, [flow_r, flow_c])``; in the image overload a plane of ref's shape in
+    ``flow_rc`` is the initial guess, any other is reset to zero.  The object keeps the Gaussian kernel's k2 / k4 / k22 between calls as
+    the reference's does: a half patch of 0 reuses the previous call's values (0 for a fresh object)."""
+
+    def __init__(self, ctx: Optional[Context] = None):
+        self._ctx = ctx
+        self._options = DenseOpticalFlowOptions()
+        self._k = np.zeros(3, np.float32)
+
+    def OpticalFlowMethodName(self) -> str:
+        return "Gunnar Farneback"
+
+    def options(self) -> DenseOpticalFlowOptions:
+        return self._options
+
+    def _remember_k(self):
+        h = int(self._options.kHalfPatchSize)
+        if 0 < h <= 255:
+            _, self._k = dense_flow_gaussian(h, self._k)
+
+    def Track(self, ref, cur, flow_rc=None):
+        flow_rc = [None, None] if flow_rc is None else list(flow_rc)
+        if ref is None or cur is None:
+            return False, flow_rc
+        ctx = self._ctx or default_context()
+        opt = self._options.to_native(self._k)
+        if isinstance(ref, ImagePyramid) and isinstance(cur, ImagePyramid):
+            if ref.level() != cur.level() or ref.level() < 1:  # :37-39
+                return False, flow_rc
+            _, rows, cols = ref.level_desc(0)
+            fr = np.empty((rows, cols), np.float32)
+            fc = np.empty((rows, cols), np.float32)
+            N.check(N.lib().ftk_dense_flow(ctx.handle, C.byref(opt), ref.handle, cur.handle, _ptr(fr), _ptr(fc)), ctx.handle)
+            self._remember_k()
+            return True, [fr, fc]
+        ref_img = np.ascontiguousarray(ref, dtype=np.uint8)
+        cur_img = np.ascontiguousarray(cur, dtype=np.uint8)
+        if ref_img.ndim != 2 or cur_img.ndim != 2 or ref_img.size == 0 or cur_img.size == 0:
+            return False, flow_rc
+        if int(self._options.kHalfPatchSize) < 0:  # :12, the flow untouched
+            return False, flow_rc
+        planes, valid = [], 0
+        for bit, f in ((1, flow_rc[0]), (2, flow_rc[1])):
+            if f is not None and np.shape(f) == ref_img.shape:
+                valid |= bit
+                planes.append(np.array(f, dtype=np.float32, copy=True, order="C"))
+            else:
+                planes.append(np.zeros(ref_img.shape, np.float32))
+        rp = ImagePyramid.from_host_levels([ref_img], ctx)
+        cp = ImagePyramid.from_host_levels([cur_img], ctx)
+        N.check(N.lib().ftk_dense_flow_level(ctx.handle, C.byref(opt), rp.handle, cp.handle, 0, _ptr(planes[0]), _ptr(planes[1]), valid), ctx.handle)
+        self._remember_k()
+        return True, planes

@@ -294,6 +294,51 @@ typedef struct ftk_direct_problem {
 } ftk_direct_problem;
 int ftk_direct_track_batch_device(ftk_context *ctx, const ftk_direct_options *opt, const ftk_direct_problem *problems, int32_t n_problems);
 
+/* ---- dense optical flow (Farneback) ------------------------------------------------------------ */
+
+/* DenseOpticalFlow::Options, src/dense_optical_flow_tracker/dense_optical_flow.h:15-20 (same defaults).  k_moments = {k2, k4, k22}
+ * of the Gaussian kernel, read ONLY when half_patch == 0: the reference then keeps the object's previous values
+ * (dense_optical_flow.cpp:95-98 returns before :119-131), which are 0 for a fresh object; the classes above pass what their
+ * object holds.  Larger half patches recompute them.  half_patch may be at most 255 here (the reference has no bound). */
+typedef struct ftk_dense_flow_options {
+    int32_t max_iteration;     /* kMaxIteration     (10)   */
+    int32_t half_patch;        /* kHalfPatchSize    (2)    */
+    float max_converge_step;   /* kMaxConvergeStep  (1e-6) */
+    float max_delta_flow_step; /* kMaxDeltaFlowStep (1.0)  */
+    float k_moments[3];        /* k2, k4, k22 for half_patch == 0 (0, 0, 0) */
+} ftk_dense_flow_options;
+#define FTK_DENSE_MAX_HALF_PATCH 255
+void ftk_default_dense_flow_options(ftk_dense_flow_options *opt);
+
+/* InitializeGaussianKernel (dense_optical_flow.cpp:87-134) on the host, no device needed: the library's single definition of the
+ * table.  weights_out (optional): (2 half_patch + 1)^2 floats, row-major; k_out (optional): {k2, k4, k22}, left as passed for
+ * half_patch == 0 (the reference's quirk).  FTK_E_INVALID_ARGUMENT for half_patch < 0 (the reference's `return false`) or above
+ * FTK_DENSE_MAX_HALF_PATCH. */
+int ftk_dense_flow_gaussian(int32_t half_patch, float *weights_out, float *k_out);
+
+/*
+ * Replaces DenseOpticalFlow::Track(ImagePyramid, ImagePyramid, flow_rc) (dense_optical_flow.cpp:35-85): coarse to fine from zero
+ * flow at the coarsest level; per level the moment images of both images (:136-189), the per-pixel Gauss-Newton refinement
+ * (:191-245) and the 3x3 median (:334-371), then the smoothed flow upsampled to the next level (:66-77).  flow_r / flow_c receive
+ * level 0's ref size (rows x cols, row-major: row and column components of the flow).  Both pyramids need the same level count
+ * (>= 1; the reference returns false otherwise — the classes above check).  half_patch < 0 gives zero flow and FTK_OK (the
+ * reference ignores the per-level `false`).  Host buffers, synchronous.
+ */
+int ftk_dense_flow(ftk_context *ctx, const ftk_dense_flow_options *opt, const ftk_pyramid *ref_pyr, const ftk_pyramid *cur_pyr, float *flow_r,
+                   float *flow_c);
+/* The same on device buffers (d_flow_r / d_flow_c: level 0's ref size), stream-ordered on the context's stream, no host
+ * synchronisation, capturable.  Workspace (moment images, flow planes, the Gaussian table) belongs to the context and grows only on
+ * calls outside a stream capture: a captured call whose shape or half patch needs more fails with FTK_E_UNSUPPORTED — make one
+ * uncaptured call of the same shape first. */
+int ftk_dense_flow_device(ftk_context *ctx, const ftk_dense_flow_options *opt, const ftk_pyramid *ref_pyr, const ftk_pyramid *cur_pyr, float *d_flow_r,
+                          float *d_flow_c);
+/* Replaces DenseOpticalFlow::Track(GrayImage, GrayImage, flow_rc) (:7-33) on level `level` of both pyramids (ref and cur may differ in
+ * size).  flow_r / flow_c: host buffers of the ref level's size, in/out; flow_valid bit 0: flow_r holds a ref-sized initial guess
+ * (otherwise it is reset to zero, :18-20), bit 1 the same for flow_c (:21-23).  half_patch < 0 fails with FTK_E_INVALID_ARGUMENT
+ * and leaves the flow untouched (the reference's `return false`). */
+int ftk_dense_flow_level(ftk_context *ctx, const ftk_dense_flow_options *opt, const ftk_pyramid *ref_pyr, const ftk_pyramid *cur_pyr, int32_t level,
+                         float *flow_r, float *flow_c, int32_t flow_valid);
+
 /* ---- features sharded over the GPUs of one node ------------------------ */
 
 /*

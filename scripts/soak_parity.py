@@ -7,6 +7,8 @@ time budget — every tracker variant, both descriptor matchers, the direct meth
                                                               | direct (batches of 1 .. 80 pose problems through the device
                                                                 batch entry: the spread kernel with 32 .. 2 producer workgroups
                                                                 per problem, and one workgroup per problem beyond what fits)
+                                                              | dense (DenseOpticalFlow: random sizes, levels, options and
+                                                                initial flows, both overloads, against tests/dense_flow_ref.c)
                                                               | tree (REPORTING mode: the trackers in the throughput mode,
                                                                 ftk_set_reduction_mode(TREE) — per-variant px-error statistics
                                                                 against the oracle, nothing asserted, exit code 0)
@@ -245,6 +247,48 @@ def direct_batch_round():
     note(f"direct batch of {count:2d}", same, f"{w}x{h} L{levels} h{half}")
 
 
+def dense_flow_round():
+    """DenseOpticalFlow against the scalar restatement: pyramid overload on a random scene, or the single-level overload with a
+    random (partly hostile) initial flow and a cur image of another size; random half patch, iterations, step cap and threshold."""
+    from tests import dense_flow_ref as DR
+
+    w, h = int(rs.randint(1, 260)), int(rs.randint(1, 200))
+    t = (float(rs.uniform(-6, 6)), float(rs.uniform(-6, 6)))
+    ref, cur = synth.make_image_pair(max(w, 8), max(h, 8), t, rotation_deg=float(rs.uniform(-2, 2)), scale=float(rs.uniform(0.98, 1.02)))
+    ref, cur = np.ascontiguousarray(ref[:h, :w]), np.ascontiguousarray(cur[:h, :w])
+    d = F.DenseOpticalFlow(F.default_context())
+    o = d.options()
+    o.kHalfPatchSize = int(rs.choice([-1, 0, 1, 2, 2, 2, 3, 4, 7, 17]))
+    o.kMaxIteration = int(rs.choice([0, 1, 5, 10, 20]))
+    o.kMaxDeltaFlowStep = float(rs.choice([0.25, 1.0, 3.0]))
+    o.kMaxConvergeStep = float(rs.choice([1e-6, 1e-4, 1e-3]))
+    k = np.float32(rs.uniform(0.5, 3.0, 3)) if rs.rand() < 0.3 else np.zeros(3, np.float32)
+    d._k = k.copy()
+    opt = DR.options(o.kMaxIteration, o.kHalfPatchSize, o.kMaxConvergeStep, o.kMaxDeltaFlowStep)
+    with np.errstate(all="ignore"):
+        if rs.rand() < 0.5:
+            levels = int(rs.randint(1, 6))
+            while levels > 1 and (min(w, h) >> (levels - 1)) < 1:
+                levels -= 1
+            rl, cl = synth.build_pyramid(ref, levels), synth.build_pyramid(cur, levels)
+            ok, (fr, fc) = d.Track(F.ImagePyramid.from_host_levels(rl), F.ImagePyramid.from_host_levels(cl))
+            ok_c, fr_c, fc_c, _ = DR.track_pyramid(rl, cl, opt, k)
+            same = ok == ok_c and DR.same(fr, fr_c) and DR.same(fc, fc_c)
+            note("dense pyramid", same, f"{w}x{h} L{levels} h{o.kHalfPatchSize} it{o.kMaxIteration}")
+        else:
+            if rs.rand() < 0.4:
+                _, cur = synth.make_image_pair(int(rs.randint(8, 260)), int(rs.randint(8, 200)), t)
+            init = [rs.uniform(-5, 5, (h, w)).astype(np.float32) if rs.rand() < 0.7 else None for _ in range(2)]
+            for f in init:
+                if f is not None and rs.rand() < 0.3:
+                    m = rs.rand(h, w) < 0.05
+                    f[m] = rs.choice(np.float32([np.nan, np.inf, -np.inf, -0.0, 1e30, 3e9]), m.sum())
+            ok, (fr, fc) = d.Track(ref, cur, list(init))
+            ok_c, fr_c, fc_c, _ = DR.track_image(ref, cur, opt, k, init[0], init[1])
+            same = ok == ok_c and (not ok or (DR.same(fr, fr_c) and DR.same(fc, fc_c)))
+            note("dense single level", same, f"{w}x{h} cur {cur.shape} h{o.kHalfPatchSize} it{o.kMaxIteration}")
+
+
 t_end = time.time() + budget
 rounds = 0
 t_report = time.time() + 60.0
@@ -253,6 +297,8 @@ while time.time() < t_end:
         matcher_round()
     elif ONLY == "direct":
         direct_batch_round()
+    elif ONLY == "dense":
+        dense_flow_round()
     elif ONLY == "tree":
         klt_round()
         direct_round()
