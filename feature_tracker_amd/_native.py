@@ -16,6 +16,8 @@ LIB_PATH = os.path.join(CSRC_DIR, "libftk_hip.so")
 
 FTK_OK = 0
 FTK_MAX_LEVELS = 12
+FTK_CORR_MAX_LEVELS = 16
+FTK_CORR_MAX_RADIUS = 64
 ERROR_NAMES = {0: "FTK_OK", -1: "FTK_E_INVALID_ARGUMENT", -2: "FTK_E_NO_DEVICE", -3: "FTK_E_HIP", -4: "FTK_E_UNSUPPORTED",
                -5: "FTK_E_OUT_OF_MEMORY"}
 
@@ -32,6 +34,7 @@ EXPORTS = [
     "ftk_shard_bounds", "ftk_klt_shard_bytes", "ftk_comm_unique_id", "ftk_comm_create", "ftk_comm_destroy", "ftk_comm_rank", "ftk_comm_world",
     "ftk_klt_track_sharded_device", "ftk_klt_track_sharded", "ftk_klt_track_shard_device", "ftk_klt_unpack_shards_device", "ftk_hamming_match_sharded_device",
     "ftk_default_dense_flow_options", "ftk_dense_flow_gaussian", "ftk_dense_flow", "ftk_dense_flow_device", "ftk_dense_flow_level",
+    "ftk_corr_pyramid_layout", "ftk_corr_pyramid_build_device", "ftk_corr_pyramid_lookup_device",
 ]
 UNIQUE_ID_BYTES = 128
 
@@ -179,6 +182,10 @@ def lib() -> C.CDLL:
     l.ftk_dense_flow.argtypes = [vp, C.POINTER(DenseFlowOptions), vp, vp, vp, vp]
     l.ftk_dense_flow_device.argtypes = [vp, C.POINTER(DenseFlowOptions), vp, vp, vp, vp]
     l.ftk_dense_flow_level.argtypes = [vp, C.POINTER(DenseFlowOptions), vp, vp, i32, vp, vp, i32]
+    i64p = C.POINTER(C.c_int64)
+    l.ftk_corr_pyramid_layout.argtypes = [i32, i32, i32, i32, i64p, i64p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    l.ftk_corr_pyramid_build_device.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
+    l.ftk_corr_pyramid_lookup_device.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, i32]
     _lib = l
     return l
 
@@ -193,3 +200,15 @@ def check(rc: int, ctx_handle=None) -> None:
     if rc != FTK_OK:
         msg = lib().ftk_last_error(ctx_handle)
         raise FtkError(rc, msg.decode() if msg else "")
+
+
+def corr_pyramid_layout(B: int, H: int, W: int, levels: int):
+    """ftk_corr_pyramid_layout (host only): (elements, [offset_l], [(H_l, W_l)]) of a correlation volume; FtkError when a level would be
+    empty or the sizes are out of range."""
+    n = max(int(levels), 0)
+    elements = C.c_int64()
+    off = (C.c_int64 * max(n, 1))()
+    lh = (C.c_int32 * max(n, 1))()
+    lw = (C.c_int32 * max(n, 1))()
+    check(lib().ftk_corr_pyramid_layout(int(B), int(H), int(W), int(levels), C.byref(elements), off, lh, lw), None)
+    return elements.value, [off[i] for i in range(n)], [(lh[i], lw[i]) for i in range(n)]

@@ -330,6 +330,32 @@ hipError_t dense_moments_launch(const DenseMomentsParams &p, hipStream_t stream)
 hipError_t dense_flow_launch(const DenseFlowParams &p, hipStream_t stream);
 hipError_t dense_median_launch(const DenseMedianParams &p, hipStream_t stream);
 
+// RAFT correlation pyramid (raft_corr_kernels.hip, CorrelationPyramid).  One volume buffer: level l at element level_offset[l], laid out
+// [B * H * W][level_h[l]][level_w[l]] (ftk_corr_pyramid_layout).
+constexpr int kCorrMaxLevels = 16;
+struct CorrBuildParams {
+    const float *f0;  // [B][C][H][W]
+    const float *f1;
+    float *volume;
+    int32_t B, C, H, W;
+    float divisor;  // (float)sqrt((double)C)
+    int32_t fused;  // pooled levels the build's epilogue writes (0 .. corr_fused_levels())
+    int64_t level_offset[4];
+    int32_t level_h[4], level_w[4];
+};
+struct CorrLookupParams {
+    const float *volume;
+    const float *coords;  // [B][2][H][W]: x, y
+    float *out;           // [B][levels * K][H][W], or per_level: levels blocks of [B][H][W][K]
+    int32_t B, H, W, levels, radius, per_level;
+    int64_t level_offset[kCorrMaxLevels];
+    int32_t level_h[kCorrMaxLevels], level_w[kCorrMaxLevels];
+};
+int corr_fused_levels();
+hipError_t corr_build_launch(const CorrBuildParams &p, hipStream_t stream);
+hipError_t corr_pool_launch(const float *src, float *dst, int64_t slabs, int hin, int win, int hout, int wout, hipStream_t stream);
+hipError_t corr_lookup_launch(const CorrLookupParams &p, hipStream_t stream);
+
 // Scatter of the all-gathered packed tracker shards into (cur_uv, status) in global feature order (ftk_comm.cpp).
 hipError_t unpack_klt_shards_launch(const uint8_t *d_gathered, int32_t n, int32_t world, int32_t cap, int64_t shard_bytes, float *d_uv_out,
                                     uint8_t *d_status_out, hipStream_t stream);

@@ -273,3 +273,50 @@ def dense_flow_device(ctx: Context, options, ref_pyr: ImagePyramid, cur_pyr: Ima
     rc = N.lib().ftk_dense_flow_device(ctx.handle, C.byref(opt), ref_pyr.handle, cur_pyr.handle, C.c_void_p(flow_r.data_ptr()),
                                        C.c_void_p(flow_c.data_ptr()))
     N.check(rc, ctx.handle)
+
+
+def _corr_check(name, t, dim):
+    if str(t.dtype) != "torch.float32" or not t.is_cuda or not t.is_contiguous() or t.dim() != dim:
+        raise ValueError(f"{name} must be a contiguous {dim}-D float32 CUDA tensor (got {tuple(t.shape)}, {t.dtype}, {t.device})")
+
+
+def corr_pyramid_build_device(ctx: Context, fmap0, fmap1, levels: int, volume, stream=None) -> None:
+    """ftk_corr_pyramid_build_device: the correlation pyramid of ``fmap0`` / ``fmap1`` (contiguous float32 CUDA [B, C, H, W]) into
+    ``volume`` (contiguous float32 CUDA, ftk_corr_pyramid_layout's element count), enqueued on ``stream`` (a torch.cuda.Stream; default:
+    torch's current stream).  No synchronisation, no allocation: capturable."""
+    torch = _torch()
+    _corr_check("fmap0", fmap0, 4)
+    _corr_check("fmap1", fmap1, 4)
+    if tuple(fmap0.shape) != tuple(fmap1.shape) or fmap0.device != fmap1.device:
+        raise ValueError(f"fmap0 and fmap1 differ: {tuple(fmap0.shape)} on {fmap0.device} vs {tuple(fmap1.shape)} on {fmap1.device}")
+    B, Cc, H, W = fmap0.shape
+    elements, _, _ = N.corr_pyramid_layout(B, H, W, levels)
+    _corr_check("volume", volume, volume.dim())
+    if volume.numel() != elements or volume.device != fmap0.device:
+        raise ValueError(f"volume must hold {elements} floats on {fmap0.device} (got {volume.numel()} on {volume.device})")
+    s = torch.cuda.current_stream(fmap0.device) if stream is None else stream
+    rc = N.lib().ftk_corr_pyramid_build_device(ctx.handle, C.c_void_p(s.cuda_stream), C.c_void_p(fmap0.data_ptr()), C.c_void_p(fmap1.data_ptr()),
+                                               B, Cc, H, W, int(levels), C.c_void_p(volume.data_ptr()))
+    N.check(rc, ctx.handle)
+
+
+def corr_pyramid_lookup_device(ctx: Context, volume, levels: int, radius: int, coords, out, per_level: bool = False, stream=None) -> None:
+    """ftk_corr_pyramid_lookup_device: the (2r+1)^2 windows of every level around ``coords`` (contiguous float32 CUDA [B, 2, H, W], x then y)
+    into ``out``: [B, levels * K, H, W], or with ``per_level`` ``levels`` consecutive [B, H, W, K] blocks (K = (2r+1)^2)."""
+    torch = _torch()
+    _corr_check("coords", coords, 4)
+    B, two, H, W = coords.shape
+    if two != 2:
+        raise ValueError(f"coords must be [B, 2, H, W] (got {tuple(coords.shape)})")
+    elements, _, _ = N.corr_pyramid_layout(B, H, W, levels)
+    _corr_check("volume", volume, volume.dim())
+    if volume.numel() != elements or volume.device != coords.device:
+        raise ValueError(f"volume must hold {elements} floats on {coords.device} (got {volume.numel()} on {volume.device})")
+    K = (2 * int(radius) + 1) ** 2
+    _corr_check("out", out, out.dim())
+    if out.numel() != B * levels * K * H * W or out.device != coords.device:
+        raise ValueError(f"out must hold {B * levels * K * H * W} floats on {coords.device}")
+    s = torch.cuda.current_stream(coords.device) if stream is None else stream
+    rc = N.lib().ftk_corr_pyramid_lookup_device(ctx.handle, C.c_void_p(s.cuda_stream), C.c_void_p(volume.data_ptr()), B, H, W, int(levels),
+                                                int(radius), C.c_void_p(coords.data_ptr()), C.c_void_p(out.data_ptr()), int(bool(per_level)))
+    N.check(rc, ctx.handle)

@@ -339,6 +339,33 @@ int ftk_dense_flow_device(ftk_context *ctx, const ftk_dense_flow_options *opt, c
 int ftk_dense_flow_level(ftk_context *ctx, const ftk_dense_flow_options *opt, const ftk_pyramid *ref_pyr, const ftk_pyramid *cur_pyr, int32_t level,
                          float *flow_r, float *flow_c, int32_t flow_valid);
 
+/* ---- RAFT correlation pyramid (src/nn_optical_flow_tracker/raft/correlation_volumes.py) ------------------------ */
+
+/*
+ * CorrelationPyramid (correlation_volumes.py:19-83) on caller-provided memory: the library holds no workspace, so both device entries
+ * are stream-ordered, never synchronise and can be captured in a graph at any time.  Feature maps are contiguous float32 [B][C][H][W];
+ * the volume is ONE buffer of ftk_corr_pyramid_layout's size, level l at element level_offsets[l], laid out [B*H*W][level_h[l]][level_w[l]]
+ * (the reference's [B*H*W, 1, H_l, W_l] tensors).  Both device entries enqueue on `stream` (a hipStream_t; NULL is the null stream),
+ * not on the context's own stream, so a caller's current stream orders them; the context selects the device and records errors.
+ */
+#define FTK_CORR_MAX_LEVELS 16
+#define FTK_CORR_MAX_RADIUS 64
+/* Host only, no device needed.  *elements: floats of the whole volume, 4 * B * H * W * sum_l H_l * W_l bytes; level_offsets (elements),
+ * level_h, level_w (each optional, `levels` entries).  H_l = H_{l-1} / 2 and W_l = W_{l-1} / 2 rounded down (avg_pool2d, :27-34).
+ * FTK_E_INVALID_ARGUMENT for non-positive sizes, levels outside 1 .. FTK_CORR_MAX_LEVELS, a level with H_l or W_l == 0 (the reference
+ * raises in avg_pool2d) or a size that overflows int64. */
+int ftk_corr_pyramid_layout(int32_t B, int32_t H, int32_t W, int32_t levels, int64_t *elements, int64_t *level_offsets, int32_t *level_h,
+                            int32_t *level_w);
+/* __init__ (:20-34) and ComputeCorrelation (:36-46): level 0 = f0^T f1 / sqrt(C) per batch item (an fmaf chain over the channels in
+ * ascending order from +0, divided by (float)sqrt((double)C)), then levels - 1 2x2 average pools.  d_volume: the layout's size. */
+int ftk_corr_pyramid_build_device(ftk_context *ctx, void *stream, const float *d_fmap0, const float *d_fmap1, int32_t B, int32_t C, int32_t H,
+                                  int32_t W, int32_t levels, float *d_volume);
+/* __call__ (:48-77) and the model's concatenation (model.py:87-88): for every pixel and level the (2r+1)^2 bilinear window around
+ * d_coords / 2^l (d_coords: [B][2][H][W], x then y).  per_level == 0: d_out is [B][levels * (2r+1)^2][H][W], the tensor model.py:88
+ * builds; per_level != 0: d_out holds `levels` consecutive blocks [B][H][W][(2r+1)^2], the list __call__ returns.  radius 0 .. FTK_CORR_MAX_RADIUS. */
+int ftk_corr_pyramid_lookup_device(ftk_context *ctx, void *stream, const float *d_volume, int32_t B, int32_t H, int32_t W, int32_t levels,
+                                   int32_t radius, const float *d_coords, float *d_out, int32_t per_level);
+
 /* ---- features sharded over the GPUs of one node ------------------------ */
 
 /*
