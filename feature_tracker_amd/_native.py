@@ -113,7 +113,7 @@ def lib() -> C.CDLL:
             import torch  # noqa: F401
         except Exception:
             pass
-    path = os.environ.get("FTK_LIB_PATH", LIB_PATH)  # e.g. a diagnostic (-DFTK_STAMPS) build
+    path = os.environ.get("FTK_LIB_PATH", LIB_PATH)  # e.g. a library built with other compiler flags
     if not os.path.exists(path):
         raise ImportError(
             f"{path} is missing: the HIP extension must be built first "

@@ -24,24 +24,18 @@
 // and is kept in LDS for the producers; the Jacobian of the pixel w.r.t. the pose (:145-148) depends
 // on the reference-frame point only and is recomputed per lane (12 products).
 // fp32 throughout, no contraction; quaternion arithmetic as defined in oracle/oracle_direct_method.c.
-#ifndef FTK_DM_CHAIN_ROUND
-#define FTK_DM_CHAIN_ROUND 8  // 32 terms per prefetch round (four: +2 % on the spread kernel, whose consumer does nothing but chain; the one-workgroup kernel does not care)
-#endif
-#define FTK_CHAIN_ROUND FTK_DM_CHAIN_ROUND
+#define FTK_CHAIN_ROUND 8  // 32 terms per prefetch round (four: +2 % on the spread kernel, whose consumer does nothing but chain; the one-workgroup kernel does not care)
 #include "klt_common.h"
 
 namespace ftk {
 namespace {
 
-// Experiment switches (scripts/build_variant.sh).  In the ONE-workgroup kernel ten waves (nine producers), chain rounds of eight reads and
-// a raised priority for the chain wave change nothing (3.56 / 3.49 / 3.47 ms against 3.49 for the 300-point problem): that kernel is
-// bound by what one compute unit can issue per iteration (793 chunks x ~390 producer instructions + 50 700 x 1.4 chain instructions),
-// not by the split of that work over its waves — which is why a single problem is SPREAD over the chip (direct_track_spread_kernel
-// below: 2.53 ms); there the consumer only chains, and both switches pay (docs/LAB_NOTES.md).
-#ifndef FTK_DM_WAVES
-#define FTK_DM_WAVES 8
-#endif
-constexpr int kDmWaves = FTK_DM_WAVES;
+// In the ONE-workgroup kernel ten waves (nine producers), chain rounds of eight reads and a raised priority for the chain wave change
+// nothing (3.56 / 3.49 / 3.47 ms against 3.49 for the 300-point problem): that kernel is bound by what one compute unit can issue per
+// iteration (793 chunks x ~390 producer instructions + 50 700 x 1.4 chain instructions), not by the split of that work over its waves —
+// which is why a single problem is SPREAD over the chip (direct_track_spread_kernel below: 2.53 ms); there the consumer only chains,
+// and longer chain rounds and the raised priority pay (docs/LAB_NOTES.md).
+constexpr int kDmWaves = 8;
 constexpr int kDmProducers = kDmWaves - 1;
 constexpr int kDmChunk = 64;
 constexpr int kDmRow = kDmChunk + 4;  // row pitch in floats: keeps the consumer's b128 reads on distinct banks
@@ -557,29 +551,18 @@ __device__ __forceinline__ void spread_stores_done() { asm volatile("s_waitcnt v
 // acknowledged by the memory side before the flag store is issued), and in the polling wave the guarded sc1 loads behind the branch
 // on the polled value — MI355X_MICROARCH.md's second valid form for handed-off bytes that are ONLY ever touched by sc1 accesses: no
 // cache holds a copy that could be stale, a wave issues its memory instructions in order and nothing is issued past an unresolved
-// branch, and a compiler barrier on either side keeps the compiler from moving the accesses.  -DFTK_SPREAD_FENCES=1 makes
-// the flag store an agent-scope RELEASE and puts an agent-scope ACQUIRE fence behind the poll.  Same results, but on gfx950 these are
+// branch, and a compiler barrier on either side keeps the compiler from moving the accesses.  The alternative, an
+// agent-scope RELEASE flag store and an agent-scope ACQUIRE fence behind the poll, gives the same results, but on gfx950 these are
 // `buffer_wbl2 sc1` (a write-back of the XCD's L2) per produced chunk and `buffer_inv sc1` (an invalidate of it) per fetched chunk —
 // 800 of each per iteration: the loader's seven loads then take 800 - 900 ns instead of 320, the consumer waits for its loaders,
-// 1.32 -> 1.48 ms for one 300-point problem and 1.33 -> 1.72 ms for six side by side (profiles/r5_direct_spread_consumer.txt).  That
-// form stays a build switch; tests/test_direct_method_gpu.py and the soak compare the default build with the one-workgroup kernel.
-#ifndef FTK_SPREAD_FENCES
-#define FTK_SPREAD_FENCES 0
-#endif
+// 1.32 -> 1.48 ms for one 300-point problem and 1.33 -> 1.72 ms for six side by side (profiles/r5_direct_spread_consumer.txt).
+// tests/test_direct_method_gpu.py and the soak compare the spread kernel with the one-workgroup kernel.
 __device__ __forceinline__ void spread_publish(uint32_t *p, uint32_t v) {
-#if FTK_SPREAD_FENCES
-    __hip_atomic_store(p, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-#else
     __atomic_signal_fence(__ATOMIC_SEQ_CST);
     spread_store(p, v);
-#endif
 }
 __device__ __forceinline__ void spread_acquired() {
-#if FTK_SPREAD_FENCES
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-#else
     __atomic_signal_fence(__ATOMIC_SEQ_CST);
-#endif
 }
 
 // Polls *flag until it equals `want` (or `also`); false when the wait ran out.  Whole wave, uniform address.

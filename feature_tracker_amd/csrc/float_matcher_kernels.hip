@@ -31,8 +31,7 @@
 // row whose candidate list overflowed, or more irregular cur rows than the side list holds sends
 // that row through the exact scan over every j in step 4 (same code, longer list).
 //
-// For dim <= 256 steps 2 and 3 are ONE walk over the candidates (cosine_gemm_rr_kernel, default, and
-// cosine_gemm_rs_kernel<2>): a running row maximum replaces the known one, which only makes the list a
+// For dim <= 256 steps 2 and 3 are ONE walk over the candidates (cosine_gemm_rr_kernel): a running row maximum replaces the known one, which only makes the list a
 // superset; entries carry their approximate score and step 4 keeps those within 2 * margin of the final
 // maximum.  The rr kernel also writes the accumulator element's index into the 5 low mantissa bits of the
 // score (so a maximum names its own element): a perturbation of at most 31 ulp < 2e-6 of the cosine, i.e.
@@ -55,7 +54,7 @@ constexpr float kMargin = 1.5e-3f;
 constexpr float kNormLo = 9.094947017729282e-13f;  // 2^-40
 constexpr float kNormHi = 1.099511627776e12f;      // 2^40
 // Candidates per row up to which a call runs as ONE exact launch (cosine_match_small_kernel: a wave walks its row's candidates
-// alone, so its time grows with n_cur); measured, scripts/cosine_small_ab.py
+// alone, so its time grows with n_cur); measured against the multi-launch pipeline per shape
 constexpr int kCosineSmallCurNearby = 2048;  // 300 x 300 x 256 NearbyMatch 48.7 -> 10.7 us, 1 000 x 1 000 47.4 -> 21.3, 2 000 x 2 000 54.6 -> 40.3 (3 000 candidates: even)
 constexpr int kCosineSmallCurForce = 384;    // ForceMatch computes every pair exactly: 100 x 100 x 256 35.4 -> 14.8 us, 300 x 300 40.3 -> 32.1, 600 x 600 41.6 -> 59.2 (not taken)
 constexpr int kCosineSmallRefMax = 4096;
@@ -449,342 +448,11 @@ __global__ void __launch_bounds__(256) cosine_gemm_kernel(const CosineParams p) 
 
 #undef FTK_LOAD_CHUNK
 
-// ---- 2 / 3 (dim_pad <= 256): ref-stationary contraction ----------------------------------------
-// rocprofv3 on the kernel above (10 000^2 x 256): MFMA busy 25 %, 41 % of the wave time waiting on
-// memory, a third of the L2 lookups missing — each workgroup re-fetches its ref chunk for every cur
-// tile and has a prefetch distance of one 64-wide chunk (~500 cycles) against L2-miss latency.
-// Here a workgroup of 8 waves keeps its 128 ref rows for the WHOLE K in LDS (loaded once), streams
-// cur chunks of 256 rows x 64 K through a double-buffered LDS tile with the global loads issued
-// TWO chunks ahead (two named register sets), and pays one barrier per chunk.  Wave (wm, wn) of
-// the 4 x 2 grid computes 64 cur x 64 ref = 2 x 2 MFMA tiles; the epilogue is unchanged.
-//
-// kMode 0 / 1 are steps 2 / 3 of the header (row maximum, then collection against it).  kMode 2 does
-// both in ONE walk: the workgroup keeps a running maximum per ref row in LDS (sMax) and collects every
-// pair within 2 * margin of the maximum seen SO FAR — a superset of the final list, because the running
-// maximum never exceeds the final one.  The first cur tile only feeds sMax and is walked a second time at
-// the end, so collection never starts from an empty bound; after that a row adds entries only when a
-// tile raises (or comes within the margin of) its maximum, ~ln(tiles) times per workgroup for any
-// exchangeable order of the cur rows.  Each entry carries its approximate score; the recheck kernel
-// drops those below the final row maximum - 2 * margin, so the exact work is that of the two-pass path.
-// A row whose list overflows takes the exact scan, as before.
-// Entries are staged in LDS (sStage: one ds_add for the slot, ~100 cycles) and appended to the per-row global lists
-// after the walk, all at once: a returning global atomic per entry, waited for inside the epilogue, costs ~1.5 us each
-// and a wave meets ~50 entries per walk — measured, that alone made the single walk slower than the two launches.
-constexpr int kCurTile = 256;
-constexpr int kStageCap = 1024;  // entries {ref row in the tile, cur row, score}; beyond it an entry goes to global directly
-
-template <int kMode, bool kNearby>
-__global__ void __launch_bounds__(512) cosine_gemm_rs_kernel(const CosineParams p) {
-    constexpr bool kCollect = kMode == 1, kSingle = kMode == 2;
-    extern __shared__ __attribute__((aligned(16))) unsigned char rs_lds[];
-    const int pitch_y = p.dim_pad + 8;                                         // halfs
-    _Float16 *const sY = reinterpret_cast<_Float16 *>(rs_lds);                 // [128][pitch_y]
-    _Float16 *const sX = sY + kTile * pitch_y;                                 // [2][256][kPitch]
-    float4 *const sInfo = reinterpret_cast<float4 *>(sX + 2 * kCurTile * kPitch);  // [2][256]: {bias, u, v, -}
-    uint32_t *const sMax = reinterpret_cast<uint32_t *>(sInfo + 2 * kCurTile);     // [128] running row maxima (kMode 2)
-    uint32_t *const sStageCount = sMax + kTile;                                    // [4], first word used
-    uint32_t *const sStage = sStageCount + 4;                                      // [kStageCap][3]
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
-    const int i0 = blockIdx.x * kTile;
-    const int tiles_total = p.n_cur_pad / kCurTile;
-    const int jt_begin = blockIdx.y * p.tiles_per_split;
-    const int jt_end = min(jt_begin + p.tiles_per_split, tiles_total);
-    if (jt_begin >= jt_end) {
-        return;
-    }
-    const int n_chunks = p.dim_pad / kChunkK;
-    const int n_tiles = jt_end - jt_begin;
-    const int n_steps = kSingle ? n_tiles + 1 : n_tiles;  // kMode 2: tile 0 once more at the end
-    const int total_chunks = n_steps * n_chunks;
-    if (kSingle && tid < kTile) {
-        sMax[tid] = 0u;  // key 0 = nothing seen (visible after the first barrier of the walk)
-        if (tid == 0) {
-            sStageCount[0] = 0u;
-        }
-    }
-    const float pos_inf = __uint_as_float(0x7F800000u), neg_inf = __uint_as_float(0xFF800000u);
-
-    int row_i[2];
-    bool live[2];
-    float pu[2], pv[2], thr[2], best[2];
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt) {
-        const int i = i0 + wn * 64 + nt * 32 + (lane & 31);
-        row_i[nt] = i;
-        live[nt] = i < p.n_ref && p.ref_irregular[i] == 0;
-        pu[nt] = (kNearby && i < p.n_ref) ? p.pred_uv[2 * i] : 0.0f;
-        pv[nt] = (kNearby && i < p.n_ref) ? p.pred_uv[2 * i + 1] : 0.0f;
-        best[nt] = neg_inf;
-        thr[nt] = pos_inf;
-        if (kCollect && live[nt]) {
-            const uint32_t key = p.row_max[i];
-            thr[nt] = (key == 0u) ? pos_inf : order_value(key) - 2.0f * kMargin;
-        }
-    }
-
-    // ref rows, whole K, once: thread t copies dim_pad / 4 halfs of row t / 4
-    {
-        const int r = tid >> 2, part = tid & 3, span = p.dim_pad / 4;  // span is a multiple of 16 halfs (dim_pad % 64 == 0)
-        const uint4 *src = reinterpret_cast<const uint4 *>(p.ref_h + (size_t)(i0 + r) * p.dim_pad + part * span);
-        uint4 *dst = reinterpret_cast<uint4 *>(sY + r * pitch_y + part * span);
-        for (int k = 0; k < span / 8; ++k) {
-            dst[k] = src[k];
-        }
-    }
-
-    // cur chunk staging: thread t carries 64 B (32 halfs) of row t / 2
-    const int srow = tid >> 1, scol = (tid & 1) * 32;
-    const _Float16 *const gx_base = p.cur_h + (size_t)srow * p.dim_pad + scol;
-    // chunk index -> (tile, K chunk) without a runtime division (n_chunks = dim_pad / 64 <= 4; c < 2^16):
-    // ceil(2^16 / d) is exact for these ranges
-    const unsigned div_magic = (65536u + (unsigned)n_chunks - 1u) / (unsigned)n_chunks;
-    auto tile_of = [&](int c) { return (int)(((unsigned)c * div_magic) >> 16); };
-    auto chunk_src = [&](int c) {
-        const int t_ = tile_of(c);
-        const int jt = jt_begin + ((kSingle && t_ == n_tiles) ? 0 : t_), kc = c - t_ * n_chunks;
-        return reinterpret_cast<const uint4 *>(gx_base + (size_t)jt * kCurTile * p.dim_pad + kc * kChunkK);
-    };
-    // two named register sets (an aggregate passed by reference into a lambda ends up in scratch memory)
-    uint4 s0a, s0b, s0c, s0d, s1a, s1b, s1c, s1d;
-#define FTK_RS_LOAD(A, B, C, D, c_)          \
-    do {                                     \
-        const uint4 *g_ = chunk_src(c_);     \
-        A = g_[0];                           \
-        B = g_[1];                           \
-        C = g_[2];                           \
-        D = g_[3];                           \
-    } while (0)
-#define FTK_RS_STORE(A, B, C, D, buf_)                                                                       \
-    do {                                                                                                     \
-        uint4 *d_ = reinterpret_cast<uint4 *>(sX + ((buf_) * kCurTile + srow) * kPitch + scol);              \
-        d_[0] = A;                                                                                           \
-        d_[1] = B;                                                                                           \
-        d_[2] = C;                                                                                           \
-        d_[3] = D;                                                                                           \
-    } while (0)
-    auto write_info = [&](int tile_index) {  // per-candidate data of the cur tile walked at step tile_index
-        if (tid < kCurTile) {
-            const int j = (jt_begin + ((kSingle && tile_index == n_tiles) ? 0 : tile_index)) * kCurTile + tid;
-            float4 info = make_float4(p.cur_bias[j], 0.0f, 0.0f, 0.0f);
-            if (kNearby && j < p.n_cur) {
-                info.y = p.cur_uv[2 * j];
-                info.z = p.cur_uv[2 * j + 1];
-            }
-            sInfo[(tile_index & 1) * kCurTile + tid] = info;
-        }
-    };
-
-    // set (c & 1) carries chunk c between its load and its LDS store
-    FTK_RS_LOAD(s0a, s0b, s0c, s0d, 0);
-    FTK_RS_STORE(s0a, s0b, s0c, s0d, 0);
-    write_info(0);
-    if (total_chunks > 1) {
-        FTK_RS_LOAD(s1a, s1b, s1c, s1d, 1);
-    }
-    if (total_chunks > 2) {
-        FTK_RS_LOAD(s0a, s0b, s0c, s0d, 2);
-    }
-
-    float16v acc[2][2];
-    auto zero_acc = [&]() {
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt) {
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    acc[mt][nt][r] = 0.0f;
-                }
-            }
-        }
-    };
-    zero_acc();
-
-    // one pipeline step: chunk c is in LDS buffer c & 1; the set named at the call site holds chunk c + 1 and is
-    // refilled with chunk c + 3 (FTK_RS_STEP below); `compute` is the part that touches no staging register
-    auto compute = [&](int c) {
-        const int tile_index = tile_of(c), kc = c - tile_index * n_chunks;
-        if (kc == 0 && tile_index + 1 < n_steps) {
-            write_info(tile_index + 1);
-        }
-        const _Float16 *bx = sX + ((c & 1) * kCurTile) * kPitch;
-        // fragments of K-step kk + 1 are read while the four MFMAs of step kk run (two register sets; the compiler
-        // otherwise re-reads into the same registers right before each use and exposes the LDS latency four times a chunk)
-        const _Float16 *ax0 = &bx[(wm * 64 + (lane & 31)) * kPitch + 8 * (lane >> 5)];
-        const _Float16 *by0 = &sY[(wn * 64 + (lane & 31)) * pitch_y + kc * kChunkK + 8 * (lane >> 5)];
-        half8 fa[2][2], fb[2][2];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            fa[0][t] = *reinterpret_cast<const half8 *>(ax0 + t * 32 * kPitch);
-            fb[0][t] = *reinterpret_cast<const half8 *>(by0 + t * 32 * pitch_y);
-        }
-#pragma unroll
-        for (int kk = 0; kk < kChunkK / 16; ++kk) {
-            const int cur_set = kk & 1, nxt_set = cur_set ^ 1;
-            if (kk + 1 < kChunkK / 16) {
-#pragma unroll
-                for (int t = 0; t < 2; ++t) {
-                    fa[nxt_set][t] = *reinterpret_cast<const half8 *>(ax0 + t * 32 * kPitch + (kk + 1) * 16);
-                    fb[nxt_set][t] = *reinterpret_cast<const half8 *>(by0 + t * 32 * pitch_y + (kk + 1) * 16);
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);  // keep the reads above the MFMAs: the scheduler sinks them otherwise
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt) {
-#pragma unroll
-                for (int nt = 0; nt < 2; ++nt) {
-                    acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[cur_set][mt], fb[cur_set][nt], acc[mt][nt], 0, 0, 0);
-                }
-            }
-        }
-        if (kc == n_chunks - 1) {
-            // epilogue of this cur tile: C/D map of the 32x32 MFMA — col = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
-            const int j0 = (jt_begin + ((kSingle && tile_index == n_tiles) ? 0 : tile_index)) * kCurTile;
-            const float4 *info_tile = sInfo + (tile_index & 1) * kCurTile;
-            // straight-line pass: bias, window, running maximum (per tile in collect mode, per launch otherwise)
-            float tile_best[2] = {neg_inf, neg_inf};
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int jl = wm * 64 + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                    const float4 info = info_tile[jl];
-#pragma unroll
-                    for (int nt = 0; nt < 2; ++nt) {
-                        float v = acc[mt][nt][r] + info.x;
-                        if (kNearby) {
-                            const bool out = (int)(fabsf(pu[nt] - info.y) > p.max_col) | (int)(fabsf(pv[nt] - info.z) > p.max_row);
-                            v = out ? neg_inf : v;
-                        }
-                        if (kCollect || kSingle) {
-                            acc[mt][nt][r] = v;  // kept for the (rare) second look below
-                        }
-                        tile_best[nt] = fmaxf(tile_best[nt], v);
-                    }
-                }
-            }
-            if (kSingle) {
-#pragma unroll
-                for (int nt = 0; nt < 2; ++nt) {
-                    const int slot_row = wn * 64 + nt * 32 + (lane & 31);
-                    const float mine = live[nt] ? tile_best[nt] : neg_inf;  // padding / irregular rows collect nothing
-                    if (tile_index > 0 && mine > neg_inf) {
-                        // bound = maximum over the tiles before this one (all waves, published before the last barrier)
-                        // joined with this lane's share of the current tile
-                        const uint32_t seen = sMax[slot_row];
-                        const float bound = fmaxf(seen ? order_value(seen) : neg_inf, mine) - 2.0f * kMargin;
-                        if (mine >= bound) {
-#pragma unroll
-                            for (int mt = 0; mt < 2; ++mt) {
-#pragma unroll
-                                for (int r = 0; r < 16; ++r) {
-                                    if (acc[mt][nt][r] >= bound) {
-                                        const int jl = wm * 64 + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                                        const uint32_t at = atomicAdd(&sStageCount[0], 1u);
-                                        if (at < (uint32_t)kStageCap) {
-                                            sStage[3 * at] = (uint32_t)slot_row;
-                                            sStage[3 * at + 1] = (uint32_t)(j0 + jl);
-                                            sStage[3 * at + 2] = __float_as_uint(acc[mt][nt][r]);
-                                        } else {
-                                            const uint32_t slot = atomicAdd(&p.cand_count[row_i[nt]], 1u);
-                                            if (slot < (uint32_t)kCosineCandCap) {
-                                                p.cand[(size_t)row_i[nt] * kCosineCandCap + slot] = j0 + jl;
-                                                p.cand_score[(size_t)row_i[nt] * kCosineCandCap + slot] = acc[mt][nt][r];
-                                            }
-                                        }
-                                    }
-                                }
-                            }
-                        }
-                    }
-                    if (tile_index < n_tiles && mine > neg_inf) {
-                        atomicMax(&sMax[slot_row], order_key(mine));
-                    }
-                }
-            } else if (!kCollect) {
-                best[0] = fmaxf(best[0], tile_best[0]);
-                best[1] = fmaxf(best[1], tile_best[1]);
-            } else {
-                // a tile holds a candidate for very few rows: one test per (lane, nt) instead of one branch per element
-#pragma unroll
-                for (int nt = 0; nt < 2; ++nt) {
-                    if (tile_best[nt] >= thr[nt]) {
-#pragma unroll
-                        for (int mt = 0; mt < 2; ++mt) {
-#pragma unroll
-                            for (int r = 0; r < 16; ++r) {
-                                if (acc[mt][nt][r] >= thr[nt]) {
-                                    const int jl = wm * 64 + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                                    const uint32_t slot = atomicAdd(&p.cand_count[row_i[nt]], 1u);
-                                    if (slot < (uint32_t)kCosineCandCap) {
-                                        p.cand[(size_t)row_i[nt] * kCosineCandCap + slot] = j0 + jl;
-                                    }
-                                }
-                            }
-                        }
-                    }
-                }
-            }
-            zero_acc();
-        }
-    };
-
-#define FTK_RS_STEP(c_, A, B, C, D)                                                                                       \
-    do {                                                                                                                  \
-        __syncthreads(); /* chunk c visible; everyone is done with chunk c - 1 (its buffer, the older sInfo half) */      \
-        if ((c_) + 1 < total_chunks) {                                                                                    \
-            FTK_RS_STORE(A, B, C, D, ((c_) + 1) & 1);                                                                     \
-        }                                                                                                                 \
-        if ((c_) + 3 < total_chunks) {                                                                                    \
-            FTK_RS_LOAD(A, B, C, D, (c_) + 3);                                                                            \
-        }                                                                                                                 \
-        compute(c_);                                                                                                      \
-    } while (0)
-    for (int c = 0; c < total_chunks; c += 2) {
-        FTK_RS_STEP(c, s1a, s1b, s1c, s1d);  // chunk c + 1 lives in set 1 (odd), refilled with chunk c + 3
-        if (c + 1 < total_chunks) {
-            FTK_RS_STEP(c + 1, s0a, s0b, s0c, s0d);  // chunk c + 2 lives in set 0 (even), refilled with chunk c + 4
-        }
-    }
-#undef FTK_RS_STEP
-#undef FTK_RS_LOAD
-#undef FTK_RS_STORE
-    if (kSingle) {
-        __syncthreads();
-        if (tid < kTile) {
-            const int i = i0 + tid;
-            const uint32_t key = sMax[tid];
-            if (key != 0u && i < p.n_ref) {
-                atomicMax(&p.row_max[i], key);
-            }
-        }
-        const uint32_t staged = min(sStageCount[0], (uint32_t)kStageCap);
-        for (uint32_t e = (uint32_t)tid; e < staged; e += 512u) {
-            const int i = i0 + (int)sStage[3 * e];
-            const uint32_t slot = atomicAdd(&p.cand_count[i], 1u);
-            if (slot < (uint32_t)kCosineCandCap) {
-                p.cand[(size_t)i * kCosineCandCap + slot] = (int32_t)sStage[3 * e + 1];
-                p.cand_score[(size_t)i * kCosineCandCap + slot] = __uint_as_float(sStage[3 * e + 2]);
-            }
-        }
-    } else if (!kCollect) {
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt) {
-            const float other = __shfl_xor(best[nt], 32);
-            const float m = fmaxf(best[nt], other);
-            if (lane < 32 && live[nt] && m > neg_inf) {
-                atomicMax(&p.row_max[row_i[nt]], order_key(m));
-            }
-        }
-    }
-}
-
 // ---- 2 + 3 (dim_pad <= 256), register-stationary: the ref fragments never leave the register file ----------
-// rocprofv3 on the LDS-stationary kernel above (10 000^2 x 256, single walk): ~93 us, MFMA busy ~30 %.  Every wave
-// reads one 1 KB fragment from LDS per MFMA (2 cur + 2 ref fragments for 2 x 2 tiles), which alone fills the LDS
-// pipe at the MFMA peak rate, and every workgroup streams the whole cur slice through L2 -> LDS for only 128 ref rows.
+// rocprofv3 on an LDS-stationary form (128 ref rows per workgroup in LDS, 10 000^2 x 256, single walk): ~93 us, MFMA
+// busy ~30 %.  Every wave read one 1 KB fragment from LDS per MFMA (2 cur + 2 ref fragments for 2 x 2 tiles), which
+// alone fills the LDS pipe at the MFMA peak rate, and every workgroup streamed the whole cur slice through L2 -> LDS
+// for only 128 ref rows.
 // Here each of the 8 waves keeps ITS 64 ref rows for the whole K as MFMA B operands in registers (2 x dim_pad / 16
 // fragments = 128 VGPRs at dim 256, loaded once), so a workgroup covers 512 ref rows; cur tiles of 64 rows x whole K
 // stream through a double-buffered LDS tile that ALL waves read (2 fragment reads per 4 MFMAs — half the LDS traffic
@@ -792,9 +460,6 @@ __global__ void __launch_bounds__(512) cosine_gemm_rs_kernel(const CosineParams 
 // maximum of the single walk is a register (exact, no cross-wave staleness).  Scored entries are staged in LDS and
 // appended after the walk if they lie within the margin of the workgroup's own final maximum; the recheck kernel cuts
 // against the global one.
-#ifndef FTK_RR_DEBUG
-#define FTK_RR_DEBUG 0  // timing experiments only (scripts/build_variant.sh): 1 no collection, 2 one epilogue row, 4 one MFMA step
-#endif
 constexpr int kRrTile = 64;        // cur rows per step
 constexpr int kRrRows = 512;       // ref rows per workgroup
 constexpr int kRrListCap = 1024;   // tiles of one workgroup's slice that the NearbyMatch tile list can hold (longer slices: no list)
@@ -1008,10 +673,10 @@ __global__ void __launch_bounds__(512) cosine_gemm_rr_kernel(const CosineParams 
         if (kStageVecs > 3) soff3 = source_of(3);
     }
     auto rr_tile_of = [&](int idx) { return (kNearby && use_list) ? sTiles[list_lo + idx] : jt_begin + idx; };
-#define FTK_RR_TILE(step_) rr_tile_of(step_)
-#define FTK_RR_FETCH(step_, SX, SINFO)                                                                                        \
+#define FTK_WALK_TILE(step_) rr_tile_of(step_)
+#define FTK_WALK_FETCH(step_, SX, SINFO)                                                                                      \
     do {                                                                                                                      \
-        const int jt_ = FTK_RR_TILE(step_);                                                                                   \
+        const int jt_ = FTK_WALK_TILE(step_);                                                                                 \
         const _Float16 *g_ = p.cur_h + (size_t)jt_ * kRrTile * kDimPad;                                                       \
         _Float16 *d_ = SX + (wave * kStageVecs) * 64 * 8;                                                                     \
         __builtin_amdgcn_global_load_lds(g_ + soff0, (lds_ptr)(d_), 16, 0, 0);                                                \
@@ -1114,9 +779,6 @@ __global__ void __launch_bounds__(512) cosine_gemm_rr_kernel(const CosineParams 
             for (int mt = 0; mt < 2; ++mt) {
 #pragma unroll
                 for (int nt = 0; nt < 2; ++nt) {
-#if FTK_RR_DEBUG & 4
-                    if (kk == 0)
-#endif
                     acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[cur_set][mt], bfrag[nt][kk], acc[mt][nt], 0, 0, 0);
                 }
             }
@@ -1124,7 +786,7 @@ __global__ void __launch_bounds__(512) cosine_gemm_rr_kernel(const CosineParams 
     };
     // epilogue: C/D map of the 32x32 MFMA — col (ref) = lane & 31, row (cur) = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
     auto rr_epilogue = [&](int s, const float4 *info_tile) {
-        const int j0 = FTK_RR_TILE(s) * kRrTile;
+        const int j0 = FTK_WALK_TILE(s) * kRrTile;
         // Pass 1, branch-free: score = accumulator + bias (window applied), with the element's index e = 16 * mt + r written
         // into the five low mantissa bits (a perturbation below 2e-6, see the margin budget in the header), and the two
         // largest of the lane's 32 scores: m1 (which then names its own element) and m2.
@@ -1133,9 +795,6 @@ __global__ void __launch_bounds__(512) cosine_gemm_rr_kernel(const CosineParams 
         for (int mt = 0; mt < 2; ++mt) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-#if FTK_RR_DEBUG & 2
-                if (r != 5) continue;
-#endif
                 const int jl = mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
                 const float4 info = info_tile[jl];
 #pragma unroll
@@ -1173,11 +832,10 @@ __global__ void __launch_bounds__(512) cosine_gemm_rr_kernel(const CosineParams 
                 const auto halves = __builtin_amdgcn_permlane32_swap(__float_as_uint(mine), __float_as_uint(mine), false, false);
                 mine = fmaxf(__uint_as_float(halves[0]), __uint_as_float(halves[1]));
             }
-#if !(FTK_RR_DEBUG & 1)
             {
                 // the row's maximum over this tile is exact here (one wave owns the row; both halves were just joined), so the
-                // first tile collects against its own maximum and needs no second visit (the LDS-stationary kernel above,
-                // whose waves share a row through a stale LDS word, does need one)
+                // first tile collects against its own maximum and needs no second visit (a kernel whose waves share a row
+                // through a stale LDS word would need one)
                 const float bound = fmaxf(run[nt], mine) - 2.0f * kMargin;
                 const bool hit1 = has && m1[nt] >= bound;
                 const bool hit2 = has && m2[nt] >= bound && m2[nt] > kRrNone;
@@ -1219,7 +877,6 @@ __global__ void __launch_bounds__(512) cosine_gemm_rr_kernel(const CosineParams 
                     append(above > 2, slot_row | 0x80000000u, share_first, m1[nt]);
                 }
             }
-#endif
             run[nt] = fmaxf(run[nt], mine);
         }
         if (wcount > (uint32_t)(kRrWaveStageCap - kRrStepEntriesMax)) {  // wave-uniform, rare
@@ -1235,49 +892,37 @@ __global__ void __launch_bounds__(512) cosine_gemm_rr_kernel(const CosineParams 
     // per-candidate data of step s - 1 then, hence four rotating buffers for it and the walk unrolled by four (the buffers
     // are distinct static arrays so that the compiler waits for a transfer only where its target is read).
     const bool late = __builtin_amdgcn_readfirstlane(wave) >= 4;
-#ifdef FTK_RR_STAMPS  // timing build only: cycles per phase of one early and one late wave of one workgroup, printed at the end
-    unsigned long long st_wait = 0, st_fetch = 0, st_mfma = 0, st_epi = 0, st_t = __builtin_amdgcn_s_memtime();
-    const unsigned long long st_begin = st_t;
-#define FTK_RR_LAP(acc_) do { const unsigned long long n_ = __builtin_amdgcn_s_memtime(); acc_ += n_ - st_t; st_t = n_; } while (0)
-#else
-#define FTK_RR_LAP(acc_) do { } while (0)
-#endif
-#define FTK_RR_STEP(s_, SX, SINFO, SXN, SINFON, SINFOP)                                                                     \
+#define FTK_WALK_STEP(s_, SX, SINFO, SXN, SINFON, SINFOP)                                                                   \
     {                                                                                                                         \
         if ((s_) >= n_steps) {                                                                                                \
             break; /* leaving (not skipping) keeps the accumulators out of a merge: a skipped MFMA block costs 64 copies */    \
         }                                                                                                                     \
         __syncthreads();                                                                                                      \
-        FTK_RR_LAP(st_wait);                                                                                                  \
         if ((s_) + 1 < n_steps) {                                                                                             \
-            FTK_RR_FETCH((s_) + 1, SXN, SINFON);                                                                              \
+            FTK_WALK_FETCH((s_) + 1, SXN, SINFON);                                                                            \
         }                                                                                                                     \
-        FTK_RR_LAP(st_fetch);                                                                                                 \
         if (late && (s_) >= 1) {                                                                                              \
             rr_epilogue((s_) - 1, SINFOP);                                                                                    \
         }                                                                                                                     \
-        FTK_RR_LAP(st_epi);                                                                                                   \
         rr_mfma(reinterpret_cast<const unsigned char *>(SX) + frag_row_bytes);                                               \
-        FTK_RR_LAP(st_mfma);                                                                                                  \
         if (!late) {                                                                                                          \
             rr_epilogue(s_, SINFO);                                                                                           \
         }                                                                                                                     \
-        FTK_RR_LAP(st_epi);                                                                                                   \
     }
-    FTK_RR_FETCH(0, sXa, sInfo0);
+    FTK_WALK_FETCH(0, sXa, sInfo0);
     for (int s = 0;; s += 4) {
-        FTK_RR_STEP(s, sXa, sInfo0, sXb, sInfo1, sInfo3)
-        FTK_RR_STEP(s + 1, sXb, sInfo1, sXa, sInfo2, sInfo0)
-        FTK_RR_STEP(s + 2, sXa, sInfo2, sXb, sInfo3, sInfo1)
-        FTK_RR_STEP(s + 3, sXb, sInfo3, sXa, sInfo0, sInfo2)
+        FTK_WALK_STEP(s, sXa, sInfo0, sXb, sInfo1, sInfo3)
+        FTK_WALK_STEP(s + 1, sXb, sInfo1, sXa, sInfo2, sInfo0)
+        FTK_WALK_STEP(s + 2, sXa, sInfo2, sXb, sInfo3, sInfo1)
+        FTK_WALK_STEP(s + 3, sXb, sInfo3, sXa, sInfo0, sInfo2)
     }
     if (late) {  // the last step's epilogue of the late waves (its per-candidate data landed before that step's barrier)
         const int last = n_steps - 1, slot = last & 3;
         rr_epilogue(last, slot == 0 ? sInfo0 : slot == 1 ? sInfo1 : slot == 2 ? sInfo2 : sInfo3);
     }
-#undef FTK_RR_STEP
-#undef FTK_RR_FETCH
-#undef FTK_RR_TILE
+#undef FTK_WALK_STEP
+#undef FTK_WALK_FETCH
+#undef FTK_WALK_TILE
     if (lane < 32) {
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt) {
@@ -1287,13 +932,6 @@ __global__ void __launch_bounds__(512) cosine_gemm_rr_kernel(const CosineParams 
         }
     }
     flush_stage();
-#ifdef FTK_RR_STAMPS
-    if (blockIdx.x == 100 && lane == 0 && (wave == 0 || wave == 4)) {
-        const unsigned long long total = __builtin_amdgcn_s_memtime() - st_begin;
-        printf("rr stamps wave %d steps %d: wait %llu fetch %llu mfma %llu epilogue %llu (in loop) total %llu cycles (s_memtime ticks)\n", wave, n_steps,
-               st_wait, st_fetch, st_mfma, st_epi, total);
-    }
-#endif
 }
 
 // ---- 4. exact decision -------------------------------------------------------------------------
@@ -1520,18 +1158,12 @@ hipError_t cosine_launch_small(const CosineParams &p, hipStream_t stream) {
 
 }  // namespace
 
-bool cosine_small_form(int n_ref, int n_cur, int dim, bool nearby, bool small_off, bool small_any) {
+bool cosine_small_form(int n_ref, int n_cur, int dim, bool nearby, bool small_off) {
     if (small_off) {  // FTK_COSINE_SMALL=0 (experiment switch of the context)
         return false;
     }
-    // small_any: FTK_COSINE_SMALL_ANY=1, no size limit (scripts/cosine_small_ab.py)
-    const bool fits = small_any || (n_ref <= kCosineSmallRefMax && n_cur <= (nearby ? kCosineSmallCurNearby : kCosineSmallCurForce));
+    const bool fits = n_ref <= kCosineSmallRefMax && n_cur <= (nearby ? kCosineSmallCurNearby : kCosineSmallCurForce);
     return (dim == 64 || dim == 128 || dim == 256) && fits;
-}
-
-size_t cosine_rs_lds_bytes(int dim_pad) {
-    return sizeof(_Float16) * ((size_t)kTile * (dim_pad + 8) + (size_t)2 * kCurTile * kPitch) + sizeof(float4) * 2 * kCurTile +
-           sizeof(uint32_t) * (kTile + 4 + 3 * kStageCap);
 }
 
 size_t cosine_rr_lds_bytes(int dim_pad) {
@@ -1543,7 +1175,7 @@ hipError_t cosine_match_launch(const CosineParams &p, hipStream_t stream) {
     if (p.n_ref <= 0 || p.n_cur <= 0) {
         return hipSuccess;
     }
-    if (cosine_small_form(p.n_ref, p.n_cur, p.dim, p.pred_uv != nullptr, p.small_off != 0, p.small_any != 0)) {
+    if (cosine_small_form(p.n_ref, p.n_cur, p.dim, p.pred_uv != nullptr, p.small_off != 0)) {
         switch (p.dim) {
             case 64: return cosine_launch_small<8>(p, stream);
             case 128: return cosine_launch_small<16>(p, stream);
@@ -1564,14 +1196,13 @@ hipError_t cosine_match_launch(const CosineParams &p, hipStream_t stream) {
             hipLaunchKernelGGL(cosine_prep_kernel, dim3((unsigned)((rows * 8 + 255) / 256), 2u), dim3(256), 0, stream, p);
         }
     }
-    const int row_tiles = p.n_ref_pad / kTile;
-    if (p.ref_stationary == 2) {
+    if (p.ref_stationary) {
         if (p.pred_uv && p.tile_box && !packets) {  // the packet-wide prep kernel has written the boxes itself
             hipLaunchKernelGGL(cosine_tile_box_kernel, dim3((unsigned)(p.n_cur_pad / kRrTile)), dim3(64), 0, stream, p);
         }
         const dim3 grid((unsigned)((p.n_ref_pad / kRrRows) * p.splits));
         const size_t lds = cosine_rr_lds_bytes(p.dim_pad);
-#define FTK_RR_LAUNCH(KSTEPS, NEARBY)                                                                                             \
+#define FTK_GEMM_LAUNCH(KSTEPS, NEARBY)                                                                                           \
     do {                                                                                                                            \
         auto kern = cosine_gemm_rr_kernel<KSTEPS, NEARBY>;                                                                          \
         e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);        \
@@ -1580,55 +1211,27 @@ hipError_t cosine_match_launch(const CosineParams &p, hipStream_t stream) {
         }                                                                                                                           \
         hipLaunchKernelGGL(kern, grid, dim3(512), lds, stream, p);                                                                  \
     } while (0)
-#define FTK_RR_DISPATCH(KSTEPS)            \
-    do {                                   \
-        if (p.pred_uv) {                   \
-            FTK_RR_LAUNCH(KSTEPS, true);   \
-        } else {                           \
-            FTK_RR_LAUNCH(KSTEPS, false);  \
-        }                                  \
+#define FTK_GEMM_DISPATCH(KSTEPS)           \
+    do {                                    \
+        if (p.pred_uv) {                    \
+            FTK_GEMM_LAUNCH(KSTEPS, true);  \
+        } else {                            \
+            FTK_GEMM_LAUNCH(KSTEPS, false); \
+        }                                   \
     } while (0)
         switch (p.dim_pad / 16) {
-            case 4: FTK_RR_DISPATCH(4); break;
-            case 8: FTK_RR_DISPATCH(8); break;
-            case 12: FTK_RR_DISPATCH(12); break;
-            case 16: FTK_RR_DISPATCH(16); break;
+            case 4: FTK_GEMM_DISPATCH(4); break;
+            case 8: FTK_GEMM_DISPATCH(8); break;
+            case 12: FTK_GEMM_DISPATCH(12); break;
+            case 16: FTK_GEMM_DISPATCH(16); break;
             default: return hipErrorInvalidValue;
         }
-#undef FTK_RR_DISPATCH
-#undef FTK_RR_LAUNCH
-    } else if (p.ref_stationary) {
-        const int tiles_total = p.n_cur_pad / kCurTile;
-        const int splits = (tiles_total + p.tiles_per_split - 1) / p.tiles_per_split;
-        const dim3 grid((unsigned)row_tiles, (unsigned)splits);
-        const size_t lds = cosine_rs_lds_bytes(p.dim_pad);
-#define FTK_RS_LAUNCH(MODE, NEARBY)                                                                                               \
-    do {                                                                                                                            \
-        auto kern = cosine_gemm_rs_kernel<MODE, NEARBY>;                                                                            \
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);        \
-        if (e != hipSuccess) {                                                                                                      \
-            return e;                                                                                                               \
-        }                                                                                                                           \
-        hipLaunchKernelGGL(kern, grid, dim3(512), lds, stream, p);                                                                  \
-    } while (0)
-        if (p.cand_score) {  // single walk
-            if (p.pred_uv) {
-                FTK_RS_LAUNCH(2, true);
-            } else {
-                FTK_RS_LAUNCH(2, false);
-            }
-        } else if (p.pred_uv) {
-            FTK_RS_LAUNCH(0, true);
-            FTK_RS_LAUNCH(1, true);
-        } else {
-            FTK_RS_LAUNCH(0, false);
-            FTK_RS_LAUNCH(1, false);
-        }
-#undef FTK_RS_LAUNCH
+#undef FTK_GEMM_DISPATCH
+#undef FTK_GEMM_LAUNCH
     } else {
         const int tiles_total = p.n_cur_pad / kTile;
         const int splits = (tiles_total + p.tiles_per_split - 1) / p.tiles_per_split;
-        const dim3 grid((unsigned)row_tiles, (unsigned)splits);
+        const dim3 grid((unsigned)(p.n_ref_pad / kTile), (unsigned)splits);
         if (p.pred_uv) {
             hipLaunchKernelGGL((cosine_gemm_kernel<false, true>), grid, dim3(256), 0, stream, p);
             hipLaunchKernelGGL((cosine_gemm_kernel<true, true>), grid, dim3(256), 0, stream, p);

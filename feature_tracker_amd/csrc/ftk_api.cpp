@@ -68,9 +68,8 @@ int ensure_pinned(ftk_context *ctx, size_t bytes) {
     // host-buffer entry points need (the host writes the block before the launch and reads it after the synchronisation).  The 2 000
     // workgroups of a zero-copy tracker call then share 64-byte lines instead of each crossing PCIe for its own 17 bytes, and their
     // results leave the chip as whole lines when the kernel ends: same box, 2 000-feature call 68.1 / 71.2 -> 66.2 / 65.6 us, small
-    // calls unchanged (round 5).  FTK_PINNED_NONCOHERENT=0: fine-grained memory as before.
-    const unsigned flags = ftk_env::off(FTK_ENV(ctx, pinned_noncoherent)) ? hipHostMallocDefault : hipHostMallocNonCoherent;
-    FTK_HIP(ctx, hipHostMalloc(&ctx->pinned, want, flags));
+    // calls unchanged (round 5).
+    FTK_HIP(ctx, hipHostMalloc(&ctx->pinned, want, hipHostMallocNonCoherent));
     ctx->pinned_bytes = want;
     return FTK_OK;
 }
@@ -219,7 +218,7 @@ namespace {
 
 // Direct method: a batch is spread over the chip (1 + NP workgroups per problem) while at least two producer workgroups per problem
 // fit beside the others (NP = 32 for up to six problems, then what the 224 usable workgroups of a whole MI355X allow).  Round 5, same box,
-// scripts/direct_batch_time.py (300 points x 13 x 13 x 4 levels), spread / one workgroup per problem, ms: 1 problem 1.01 / 1.81,
+// batches of 300 points x 13 x 13 x 4 levels, spread / one workgroup per problem, ms: 1 problem 1.01 / 1.81,
 // 6: 1.05 / 1.85, 12: 1.11 / 1.85, 24 (NP 8): 1.16 / 1.86, 32 (6): 1.21 / 1.86, 44 (4): 1.30 / 1.87, 56 (3): 1.41 / 1.89, 64 (2): 1.39 /
 // 1.89, 74 (2): 1.54 / 1.88, 100 (1): 2.03 / 1.93 — one producer workgroup does not keep up with its consumer's chain, two do
 // (profiles/r5_direct_spread_consumer.txt).  Beyond that one workgroup per problem IS the fast form, and its time is one problem's.
@@ -298,7 +297,7 @@ int fill_klt_params(ftk_context *ctx, int model, const ftk_klt_options *opt, con
     // lasts as long as its slowest one.  The kernels report each call's longest feature (klt_common.h tail_report); a variant whose
     // recent calls had one of kTailLongFrom iterations or more is looked up in the long-tail half of the table.
     p.long_tail = 0;
-    if (ctx && ctx->tail_host && !ftk_env::off(FTK_ENV(ctx, klt_tail)) && model >= 0 && model < 3) {
+    if (ctx && ctx->tail_host && model >= 0 && model < 3) {
         const int mi = opt->method == FTK_METHOD_INVERSE ? 0 : (opt->method == FTK_METHOD_DIRECT ? 1 : 2);
         ftk_context::TailState &ts = ctx->tail[model][mi];
         // this variant's own word: {call number << 8 | iterations} of the longest feature of its most recent launch that has got that
@@ -311,10 +310,6 @@ int fill_klt_params(ftk_context *ctx, int model, const ftk_klt_options *opt, con
             ts.longest = seen & 0xFFu;
         }
         p.long_tail = ts.launches < ts.long_until ? 1 : 0;
-        if (FTK_ENV(ctx, klt_tail) && atoi(FTK_ENV(ctx, klt_tail)) == 2 && ts.launches < 12) {  // diagnostic
-            fprintf(stderr, "[ftk tail] model %d method %d launch %u (context launch %u): host word call %u iterations %u, long_until %u -> long_tail %d\n", model, mi,
-                    ts.launches, ctx->tail_call, seen >> 8, seen & 0xFFu, ts.long_until, p.long_tail);
-        }
     }
     if (const char *env = FTK_ENV(ctx, klt_tail_class)) {
         p.long_tail = atoi(env) != 0 ? 1 : 0;  // experiment override (the sweep and the policy test pin the class)
@@ -350,8 +345,7 @@ int fill_klt_params(ftk_context *ctx, int model, const ftk_klt_options *opt, con
         for (int i = 0; i < p.n_levels; ++i) {
             small = small && p.ref[i].rows < (1 << 23) && p.ref[i].cols < (1 << 23) && p.cur[i].rows < (1 << 23) && p.cur[i].cols < (1 << 23);
         }
-        const char *env = FTK_ENV(ctx, klt_pipelined);
-        p.pb_enabled = (small && !(env && atoi(env) == 0)) ? 1 : 0;
+        p.pb_enabled = small ? 1 : 0;
     }
     // The `fast` method (the reference's default) of Basic KLT runs the one-wave kernel of klt_fast_kernels.hip at every feature
     // count: with 1 - 2 iterations per level a feature's life is its level entries, which that kernel walks without a barrier and with
@@ -359,9 +353,6 @@ int fill_klt_params(ftk_context *ctx, int model, const ftk_klt_options *opt, con
     // generic kernel's instantiations serve it), not for patches whose per-pixel records would crowd the LDS.
     // (the chunked one-wave LSSD levels choose their chain form at run time: quads while every feature of the call is resident at once)
     p.quad_chain = n <= 4096 ? 1 : 0;
-    if (const char *env = FTK_ENV(ctx, klt_quad)) {
-        p.quad_chain = atoi(env) != 0 ? 1 : 0;  // experiment override
-    }
     p.fk_enabled = 0;
     // One wave walks all P pixels of every pass: up to 15 x 15 that beats the generic kernel's 2 - 4 waves at every feature count
     // (2 000 x 13 x 13: 22.6 vs 27.5 us; 10 000: 58.6 vs 82.9 us); larger patches only where the call is throughput-bound anyway
@@ -376,10 +367,9 @@ int fill_klt_params(ftk_context *ctx, int model, const ftk_klt_options *opt, con
         for (int i = 0; i < p.n_levels; ++i) {
             small = small && p.ref[i].rows < (1 << 23) && p.ref[i].cols < (1 << 23) && p.cur[i].rows < (1 << 23) && p.cur[i].cols < (1 << 23);
         }
-        const char *env = FTK_ENV(ctx, klt_fast_kernel);
         ftk::KltParams one = p;
         one.features_per_group = 1;
-        if (small && !(env && atoi(env) == 0) && ftk::klt_fast_lds_bytes(model, one) <= 40 * 1024) {
+        if (small && ftk::klt_fast_lds_bytes(model, one) <= 40 * 1024) {
             p.fk_enabled = 1;
             p.waves_per_feature = 1;
         }
@@ -432,10 +422,6 @@ int fill_klt_params(ftk_context *ctx, int model, const ftk_klt_options *opt, con
             p.features_per_group = group < 1 ? 1 : (group > 4 ? 4 : group);
         }
     }
-#ifdef FTK_PB_EXTRAS_TIMING_ONLY  // diagnostic builds only (scripts/build_variant.sh): a capacity below the provable maximum gives wrong results
-    p.pb_cap_r = p.patch_rows + 2 + (FTK_PB_EXTRAS_TIMING_ONLY);
-    p.pb_cap_c = p.patch_cols + 2 + (FTK_PB_EXTRAS_TIMING_ONLY);
-#endif
     size_t lds = ftk::klt_lds_bytes(model, opt->method, p);
     if (lds == 0) {
         return fail(ctx, FTK_E_UNSUPPORTED, "klt: unknown variant (model %d, method %d)", model, opt->method);
@@ -958,10 +944,9 @@ int ftk_pyramid_build(ftk_context *ctx, const uint8_t *image, int32_t rows, int3
     // A host image goes through a pinned staging slot: the CPU copies it there (the caller's buffer is free on return), the
     // pyramid launch reads the slot over PCIe and keeps level 0 — no staged hipMemcpy of pageable memory, no stream
     // synchronisation (CreateImagePyramid x 2 sits inside the reference's timed region, test_optical_flow.cpp:69-73: 57 us per
-    // build before).  One-level pyramids and FTK_PYRAMID_ZEROCOPY=0 / FTK_PYRAMID_FUSED=0 keep the copy.
+    // build before).  One-level pyramids keep the copy.
     ftk_context::ImageStage *stage = nullptr;
-    const bool stage_allowed = !(FTK_ENV(ctx, pyramid_zerocopy) && atoi(FTK_ENV(ctx, pyramid_zerocopy)) == 0);
-    if (!image_on_device && stage_allowed && n_levels >= 2 && ftk::pyramid_fused_enabled()) {
+    if (!image_on_device && n_levels >= 2) {
         rc = acquire_image_stage(ctx, (size_t)rows * cols, &stage);
         if (rc != FTK_OK) {
             ftk_pyramid_destroy(pyr);
@@ -1036,10 +1021,9 @@ int ftk_pyramid_update(ftk_context *ctx, ftk_pyramid *pyr, const uint8_t *image,
     }
     // A frame in PINNED host memory (FTK_IMAGE_HOST_ASYNC) is read by the pyramid launch itself when the device can address it:
     // the copy engine takes ~20 us per 300 KB frame, the kernel's own PCIe read a third of that, and a launch gap goes with it.
-    // FTK_PYRAMID_ZEROCOPY=0 keeps the copy (experiment switch); pageable or unmapped memory takes it anyway.
+    // Pageable or unmapped memory takes the copy.
     const uint8_t *direct_src = nullptr;
-    const bool zero_copy_allowed = !(FTK_ENV(ctx, pyramid_zerocopy) && atoi(FTK_ENV(ctx, pyramid_zerocopy)) == 0);
-    if (image_location == FTK_IMAGE_HOST_ASYNC && zero_copy_allowed && pyr->n_levels >= 2 && ftk::pyramid_fused_enabled()) {
+    if (image_location == FTK_IMAGE_HOST_ASYNC && pyr->n_levels >= 2) {
         hipPointerAttribute_t attr;
         if (hipPointerGetAttributes(&attr, image) == hipSuccess && attr.type == hipMemoryTypeHost && attr.devicePointer != nullptr) {
             direct_src = static_cast<const uint8_t *>(attr.devicePointer);
@@ -1048,7 +1032,7 @@ int ftk_pyramid_update(ftk_context *ctx, ftk_pyramid *pyr, const uint8_t *image,
         }
     }
     ftk_context::ImageStage *stage = nullptr;
-    if (image_location == FTK_IMAGE_HOST && zero_copy_allowed && pyr->n_levels >= 2 && ftk::pyramid_fused_enabled()) {
+    if (image_location == FTK_IMAGE_HOST && pyr->n_levels >= 2) {
         // a pageable frame: CPU copy into a pinned slot (the caller's buffer is free on return), read by the launch; no synchronisation
         const int rc = acquire_image_stage(ctx, (size_t)pyr->levels[0].rows * pyr->levels[0].cols, &stage);
         if (rc != FTK_OK) {
@@ -1287,10 +1271,9 @@ int ftk_klt_track_device(ftk_context *ctx, int model, const ftk_klt_options *opt
                 ctx->sched_calls = 0;
             }
             const uint32_t k = ctx->sched_calls++;
-            // Position-keyed swaps ride on every such call, whatever the list did since the last one (FTK_KLT_SWAP=0: off).  Call
-            // numbers start at 4 (an all-zero grid / claim word is never "recent") and tag 23 bits of a claim word: the claims are
-            // wiped before a tag could repeat.
-            const bool swap_allowed = !(FTK_ENV(ctx, klt_swap) && atoi(FTK_ENV(ctx, klt_swap)) == 0);
+            // Position-keyed swaps ride on every such call, whatever the list did since the last one.  Call numbers start at 4 (an
+            // all-zero grid / claim word is never "recent") and tag 23 bits of a claim word: the claims are wiped before a tag could
+            // repeat.
             // (never inside a stream capture: a replayed launch would carry this call's number again and read its own old claims)
             hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
             if (hipStreamIsCapturing(ctx->stream, &capture) != hipSuccess) {
@@ -1325,7 +1308,7 @@ int ftk_klt_track_device(ftk_context *ctx, int model, const ftk_klt_options *opt
                 last_recorded = ctx->sched_recorded;
                 ctx->sched_recorded = ctx->sched_call;
             }
-            if (recording && swap_allowed && p.waves_per_feature >= 2 && ref_untouched && n > 1024 + 512) {
+            if (recording && p.waves_per_feature >= 2 && ref_untouched && n > 1024 + 512) {
                 p.sched_flags = ctx->sched_grid + (2u << 16);
                 p.sched_claim = ctx->sched_claim;
             }
@@ -1339,26 +1322,21 @@ int ftk_klt_track_device(ftk_context *ctx, int model, const ftk_klt_options *opt
                 // stale entries, a write past order[n - 1].  Such a call gets the iteration-count / identity order instead.
                 p.sort_ref_uv = ref_untouched ? p.ref_uv : nullptr;
             }
-            const int order_mode = FTK_ENV(ctx, klt_order) ? atoi(FTK_ENV(ctx, klt_order)) : -1;  // experiment: 0 = never, 1 = always
-            const bool use_order = order_mode >= 0 ? order_mode != 0 : true;
-            if (k >= 2 && use_order) {                        // made during the previous call from the counts before it
+            if (k >= 2) {                                     // made during the previous call from the counts before it
                 p.order = ctx->sched_order[k & 1];
-            } else if (use_order && recording && last_recorded != 0u && last_recorded + 1u == ctx->sched_call && ctx->sched_pred && model != FTK_MODEL_BASIC &&
+            } else if (recording && last_recorded != 0u && last_recorded + 1u == ctx->sched_call && ctx->sched_pred && model != FTK_MODEL_BASIC &&
                        p.sched_claim == nullptr) {
                 // (LSSD and affine KLT: their iteration counts have tails — config 4 without history 206 -> 183 us, with luminance
                 // 357 -> 315; Basic KLT's are flat on most scenes and the ~10 us of the two launches would buy nothing — config 5 shard
                 // 181 -> 190; the multi-wave kernels trade slots by position inside the launch instead)
                 // No index-keyed order (the feature count has just changed, or these are the first calls): order THIS call by what the
                 // last call left at its features' positions — two small launches in front of the tracker's (klt_kernels.hip
-                // klt_position_order_launch; FTK_KLT_POSITION_ORDER=0: list order as before).  The buffer is the one an index-keyed
-                // order of this call would have used: nobody else writes it during this call.
-                const bool position_order = !(FTK_ENV(ctx, klt_position_order) && atoi(FTK_ENV(ctx, klt_position_order)) == 0);
-                if (position_order) {
-                    const uint32_t *last_table = ctx->sched_grid + (((ctx->sched_call - 1u) & 1u) << 16);
-                    FTK_HIP(ctx, ftk::klt_position_order_launch(p.ref_uv, n, last_table, ctx->sched_call - 1u, ctx->sched_pred, ctx->sched_grid + kSchedTableWords,
-                                                                ctx->sched_order[k & 1], ctx->stream));
-                    p.order = ctx->sched_order[k & 1];
-                }
+                // klt_position_order_launch).  The buffer is the one an index-keyed order of this call would have used: nobody else
+                // writes it during this call.
+                const uint32_t *last_table = ctx->sched_grid + (((ctx->sched_call - 1u) & 1u) << 16);
+                FTK_HIP(ctx, ftk::klt_position_order_launch(p.ref_uv, n, last_table, ctx->sched_call - 1u, ctx->sched_pred, ctx->sched_grid + kSchedTableWords,
+                                                            ctx->sched_order[k & 1], ctx->stream));
+                p.order = ctx->sched_order[k & 1];
             }
             if (const char *dump = FTK_ENV(ctx, klt_swap_dump)) {  // diagnostic: how many trades the PREVIOUS launch of this context made
                 if (p.sched_claim != nullptr && ctx->sched_call > 5u) {
@@ -1392,55 +1370,6 @@ int ftk_klt_track_device(ftk_context *ctx, int model, const ftk_klt_options *opt
             }
         }
     }
-#ifdef FTK_STAMPS
-    // diagnostic build: per-phase cycle totals (s_memtime ticks at 100 MHz) averaged over features, to stderr
-    unsigned long long *d_stamps = nullptr;
-    FTK_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&d_stamps), sizeof(unsigned long long) * 8 * (size_t)n));
-    FTK_HIP(ctx, hipMemsetAsync(d_stamps, 0, sizeof(unsigned long long) * 8 * (size_t)n, ctx->stream));
-    p.stamps = d_stamps;
-    FTK_HIP(ctx, ftk::klt_launch(model, opt->method, p, ctx->stream));
-    {
-        std::vector<unsigned long long> h(8 * (size_t)n);
-        FTK_HIP(ctx, hipMemcpyAsync(h.data(), d_stamps, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost, ctx->stream));
-        FTK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        double avg[8] = {0};
-        for (int i = 0; i < n; ++i)
-            for (int k = 0; k < 8; ++k) avg[k] += (double)h[(size_t)i * 8 + k];
-        static int printed = 0;
-        if (printed++ < 3) {
-            fprintf(stderr, "[ftk stamps] memtime ticks/feature: ref_stage %.0f setup %.0f cur_stage %.0f phaseA %.0f count %.0f chain %.0f solve %.0f total %.0f\n",
-                    avg[0] / n, avg[1] / n, avg[2] / n, avg[3] / n, avg[4] / n, avg[5] / n, avg[6] / n, avg[7] / n);
-        }
-        if (const char *dump = FTK_ENV(ctx, stamps_dump)) {
-            if (FILE *f = fopen(dump, "wb")) {
-                fwrite(h.data(), sizeof(unsigned long long), h.size(), f);
-                fclose(f);
-            }
-        }
-        if (p.pb_enabled && printed <= 3) {
-            // pipelined kernel: slots 6 / 4 hold s_memrealtime (100 MHz) at workgroup start / end
-            unsigned long long t_min = ~0ull, t_max = 0, life = 0;
-            for (int i = 0; i < n; ++i) {
-                const unsigned long long t0 = h[(size_t)i * 8 + 6], t1 = h[(size_t)i * 8 + 4];
-                if (t0 == 0) continue;
-                t_min = t0 < t_min ? t0 : t_min;
-                t_max = t1 > t_max ? t1 : t_max;
-                life += t1 - t0;
-            }
-            unsigned long long last_start = 0, first_end = ~0ull;
-            for (int i = 0; i < n; ++i) {
-                const unsigned long long t0 = h[(size_t)i * 8 + 6], t1 = h[(size_t)i * 8 + 4];
-                if (t0 == 0) continue;
-                last_start = t0 > last_start ? t0 : last_start;
-                first_end = t1 < first_end ? t1 : first_end;
-            }
-            fprintf(stderr, "[ftk stamps] realtime: span %.2f us, mean workgroup life %.2f us, last start +%.2f us, first end +%.2f us\n",
-                    (double)(t_max - t_min) * 0.01, (double)life * 0.01 / n, (double)(last_start - t_min) * 0.01, (double)(first_end - t_min) * 0.01);
-        }
-        (void)hipFree(d_stamps);
-    }
-    return FTK_OK;
-#else
     const hipError_t launch_rc = ftk::klt_launch(model, opt->method, p, ctx->stream);
     if (launch_rc != hipSuccess) {
         // The launch-order state advanced above assumed this launch would write its iteration counts and (from the second call
@@ -1450,7 +1379,6 @@ int ftk_klt_track_device(ftk_context *ctx, int model, const ftk_klt_options *opt
         return fail(ctx, launch_rc == hipErrorOutOfMemory ? FTK_E_OUT_OF_MEMORY : FTK_E_HIP, "klt launch failed: %s", hipGetErrorString(launch_rc));
     }
     return FTK_OK;
-#endif
 }
 
 int ftk_klt_track(ftk_context *ctx, int model, const ftk_klt_options *opt, const ftk_pyramid *ref, const ftk_pyramid *cur, const float *ref_uv,
@@ -1496,10 +1424,9 @@ int ftk_klt_track(ftk_context *ctx, int model, const ftk_klt_options *opt, const
     // Small calls (the reference's callers track a few hundred features) are dominated by the two staging copies and
     // their queue latency, not by bytes: the kernel then reads (ref_uv, cur_uv, status) from and writes its 9 B per
     // feature straight into the pinned host block over PCIe — no H2D / D2H at all (2 000 features: 89 -> ~60 us per
-    // call).  Larger calls keep the bulk copies.  FTK_KLT_ZEROCOPY=0 disables it.
-    const bool zero_copy_allowed = !(FTK_ENV(ctx, klt_zerocopy) && atoi(FTK_ENV(ctx, klt_zerocopy)) == 0);
+    // call).  Larger calls keep the bulk copies.
     void *mapped = nullptr;
-    if (zero_copy_allowed && n <= 16384 && hipHostGetDevicePointer(&mapped, ctx->pinned, 0) == hipSuccess && mapped != nullptr) {
+    if (n <= 16384 && hipHostGetDevicePointer(&mapped, ctx->pinned, 0) == hipSuccess && mapped != nullptr) {
         uint8_t *mbase = static_cast<uint8_t *>(mapped);
         float *m_ref = reinterpret_cast<float *>(mbase);
         float *m_cur = reinterpret_cast<float *>(mbase + uv_bytes);
@@ -1867,12 +1794,6 @@ int ftk_hamming_match_device(ftk_context *ctx, const uint32_t *d_ref_words, int3
     // splits take 85 / 74 / 69 us; the scan is pure VALU work and small workgroups even out the tail.
     const int row_blocks = (n_ref + ftk::kMatchRowsPerBlock - 1) / ftk::kMatchRowsPerBlock;
     int splits = (4096 + row_blocks - 1) / row_blocks;
-    if (const char *env = FTK_ENV(ctx, match_wgs)) {
-        splits = (atoi(env) + row_blocks - 1) / row_blocks;  // experiment: target number of workgroups
-    }
-    if (const char *env = FTK_ENV(ctx, match_splits)) {
-        splits = atoi(env);  // experiment override
-    }
     const int max_splits = (n_cur + 63) / 64;
     if (splits > max_splits) {
         splits = max_splits;
@@ -1881,16 +1802,13 @@ int ftk_hamming_match_device(ftk_context *ctx, const uint32_t *d_ref_words, int3
         splits = 1;
     }
     int per = (n_cur + splits - 1) / splits;
-    if (!(FTK_ENV(ctx, match_any_per) && atoi(FTK_ENV(ctx, match_any_per)) == 1)) {
-        per = (per + 63) / 64 * 64;
-    }
+    per = (per + 63) / 64 * 64;
     p.matrix_cores = 0;
     {
         // Which scan: 256- and 512-bit descriptors go to the matrix cores (matcher_kernels.hip, hamming_match_mfma_kernel:
-        // faster at every size measured, 300 x 300 to 10 000 x 10 000, scripts/match_shapes.py); other widths to the popcount
-        // scan with the candidates on the scalar path.  FTK_MATCH_KERNEL=mfma|scalar|lds forces one (experiment switch).
+        // faster at every size measured, 300 x 300 to 10 000 x 10 000); other widths to the popcount
+        // scan with the candidates on the scalar path.  FTK_MATCH_KERNEL=mfma|scalar forces one (experiment switch).
         const char *env = FTK_ENV(ctx, match_kernel);
-        p.lds_tiles = (env && !strcmp(env, "lds")) ? 1 : 0;
         // (the matrix-core scan addresses the candidates with 32-bit byte offsets)
         bool mfma = n_bits > 0 && (n_words == 8 || n_words == 16) && (long long)n_cur * n_words * 4 < (1ll << 31);
         if (env) {
@@ -1901,11 +1819,7 @@ int ftk_hamming_match_device(ftk_context *ctx, const uint32_t *d_ref_words, int3
             // One wave per workgroup: 64 rows and one split of the candidates, in 32-candidate tiles.  Two waves fit a SIMD
             // (registers): one round of at most 2048 waves, the splits whole tiles and as even as the tile count allows.
             const int mfma_row_blocks = (n_ref + 63) / 64;
-            int target = 2048;
-            if (const char *wgs = FTK_ENV(ctx, match_wgs)) {
-                target = atoi(wgs);
-            }
-            int mfma_splits = target / mfma_row_blocks;
+            int mfma_splits = 2048 / mfma_row_blocks;
             mfma_splits = mfma_splits < 1 ? 1 : mfma_splits;
             const int n_tiles = (n_cur + 31) / 32;
             int tiles_per_split = (n_tiles + mfma_splits - 1) / mfma_splits;
@@ -1919,8 +1833,7 @@ int ftk_hamming_match_device(ftk_context *ctx, const uint32_t *d_ref_words, int3
     // NearbyMatch from a few thousand candidates on: bounding boxes for the early exit of workgroups whose candidates
     // cannot reach any window of their rows (matcher_kernels.hip)
     p.boxes = nullptr;
-    const bool boxes_off = FTK_ENV(ctx, match_boxes) && atoi(FTK_ENV(ctx, match_boxes)) == 0;  // experiment switch
-    if (d_pred_uv && n_bits > 0 && n_cur >= 2048 && !boxes_off) {
+    if (d_pred_uv && n_bits > 0 && n_cur >= 2048) {
         const size_t n_boxes = (size_t)row_blocks + (size_t)((n_cur + per - 1) / per);
         const int rc = ensure_match_boxes(ctx, n_boxes);
         if (rc != FTK_OK) {
@@ -1928,34 +1841,8 @@ int ftk_hamming_match_device(ftk_context *ctx, const uint32_t *d_ref_words, int3
         }
         p.boxes = reinterpret_cast<float4 *>(ctx->match_boxes);
     }
-#ifdef FTK_MATCH_STAMPS
-    {
-        // diagnostic build: per-workgroup {start, loaded, end} (s_memrealtime, 100 MHz) + HW_ID, dumped to $FTK_MATCH_STAMPS_DUMP
-        const int n_splits = (n_cur + per - 1) / per;
-        // (the matrix-core scan has 64-row workgroups and writes 8 words per workgroup)
-        const size_t n_wg = p.matrix_cores ? (size_t)((n_ref + 63) / 64) * n_splits * 2 : (size_t)row_blocks * n_splits;
-        unsigned long long *d_st = nullptr;
-        FTK_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&d_st), sizeof(unsigned long long) * 4 * n_wg));
-        FTK_HIP(ctx, hipMemsetAsync(d_st, 0, sizeof(unsigned long long) * 4 * n_wg, ctx->stream));
-        p.stamps = d_st;
-        FTK_HIP(ctx, ftk::match_launch(p, ctx->stream));
-        std::vector<unsigned long long> h(4 * n_wg);
-        FTK_HIP(ctx, hipMemcpyAsync(h.data(), d_st, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost, ctx->stream));
-        FTK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (const char *dump = FTK_ENV(ctx, match_stamps_dump)) {
-            if (FILE *f = fopen(dump, "wb")) {
-                fwrite(h.data(), sizeof(unsigned long long), h.size(), f);
-                fclose(f);
-            }
-        }
-        (void)hipFree(d_st);
-        return FTK_OK;
-    }
-#else
-    p.stamps = nullptr;
     FTK_HIP(ctx, ftk::match_launch(p, ctx->stream));
     return FTK_OK;
-#endif
 }
 
 int ftk_hamming_match(ftk_context *ctx, const uint32_t *ref_words, int32_t n_ref, const uint32_t *cur_words, int32_t n_cur, int32_t n_words,
@@ -2205,11 +2092,7 @@ int ftk_direct_track_batch_device(ftk_context *ctx, const ftk_direct_options *op
         if (const char *min_env = FTK_ENV(ctx, direct_spread_min_terms)) {
             min_terms = atoll(min_env);  // tests: spread even tiny problems (producers whose waves own no chunk)
         }
-        int max_problems = kDirectSpreadMaxProblems;
-        if (const char *max_env = FTK_ENV(ctx, direct_spread_max_problems)) {
-            max_problems = atoi(max_env);  // experiments: scripts/direct_batch_time.py
-        }
-        bool spread = producers > 0 && !ctx->direct_spread_off && n_problems <= max_problems && !p.tree && opt->method == FTK_METHOD_DIRECT && !feat_in_global &&
+        bool spread = producers > 0 && !ctx->direct_spread_off && n_problems <= kDirectSpreadMaxProblems && !p.tree && opt->method == FTK_METHOD_DIRECT && !feat_in_global &&
                       max_features > 0 && terms >= min_terms && terms < (1ll << 31);
         if (spread) {
             // Every workgroup of the launch must be resident at once (consumer and producers wait for each other): size the producers from
@@ -2396,7 +2279,6 @@ int ftk_cosine_match_device(ftk_context *ctx, const float *d_ref_desc, int32_t n
     FTK_HIP(ctx, hipSetDevice(ctx->device));
     ftk::CosineParams p;
     p.small_off = ftk_env::off(FTK_ENV(ctx, cosine_small)) ? 1 : 0;
-    p.small_any = ftk_env::on(FTK_ENV(ctx, cosine_small_any)) ? 1 : 0;
     p.ref = d_ref_desc;
     p.cur = d_cur_desc;
     p.pred_uv = d_pred_uv;
@@ -2406,16 +2288,12 @@ int ftk_cosine_match_device(ftk_context *ctx, const float *d_ref_desc, int32_t n
     p.n_cur = n_cur;
     p.dim = dim;
     p.dim_pad = (int32_t)align_up((size_t)dim, 64);
-    // dim <= 256 (SuperPoint, DISK): the ref-stationary contraction — 128 ref rows for the whole K resident in LDS,
-    // cur streamed in 256-row tiles, one 8-wave workgroup per CU.  Longer descriptors use the chunked kernel.
-    // dim <= 256 (SuperPoint, DISK): the ref fragments stay on chip for the whole walk over cur — in registers
-    // (cosine_gemm_rr_kernel, 512 ref rows per workgroup; the default) or in LDS (cosine_gemm_rs_kernel, 128 rows;
-    // FTK_COSINE_KERNEL=rs).  Longer descriptors, or FTK_COSINE_KERNEL=chunked, use the chunked kernel.
-    const char *kernel_env = FTK_ENV(ctx, cosine_kernel);
-    const bool want_chunked = (kernel_env && !strcmp(kernel_env, "chunked")) || (FTK_ENV(ctx, cosine_chunked) && atoi(FTK_ENV(ctx, cosine_chunked)) == 1);
-    p.ref_stationary = (p.dim_pad <= 256 && !want_chunked) ? ((kernel_env && !strcmp(kernel_env, "rs")) ? 1 : 2) : 0;
-    const int cur_tile = p.ref_stationary == 2 ? 64 : (p.ref_stationary == 1 ? 256 : 128);
-    const int row_group = p.ref_stationary == 2 ? 512 : 128;
+    // dim <= 256 (SuperPoint, DISK): the ref fragments stay in registers for the whole walk over cur (cosine_gemm_rr_kernel,
+    // 512 ref rows per workgroup).  Longer descriptors, or FTK_COSINE_CHUNKED=1, use the chunked kernel.
+    const bool want_chunked = FTK_ENV(ctx, cosine_chunked) && atoi(FTK_ENV(ctx, cosine_chunked)) == 1;
+    p.ref_stationary = (p.dim_pad <= 256 && !want_chunked) ? 1 : 0;
+    const int cur_tile = p.ref_stationary ? 64 : 128;
+    const int row_group = p.ref_stationary ? 512 : 128;
     p.n_ref_pad = (int32_t)align_up((size_t)n_ref, (size_t)row_group);
     p.n_cur_pad = (int32_t)align_up((size_t)n_cur, (size_t)cur_tile);
     p.max_distance = max_distance;
@@ -2430,11 +2308,11 @@ int ftk_cosine_match_device(ftk_context *ctx, const float *d_ref_desc, int32_t n
         splits = atoi(env);  // experiment override
     }
     splits = std::max(1, std::min(splits, tiles_total));
-    if (p.ref_stationary == 2 && !FTK_ENV(ctx, cosine_splits)) {
+    if (p.ref_stationary && !FTK_ENV(ctx, cosine_splits)) {
         // At least TWO tiles per split: a walk's first step has no running maximum to cut against yet, so it lists its whole share
         // of every row; with one-tile splits that is all there is, the rows' lists overflow (kCosineCandCap) and the recheck falls
         // back to the exact scan of every pair — 2 000 x 2 000 x 256: 32 splits 17.6 + 3 591 us (contraction + recheck), 16 splits
-        // 20.2 + 11.8 us; 1 000 x 1 000 x 128: 16 splits 11.4 + 1 099 us, 8 splits 14.1 + 7.6 us (scripts/trace_cosine_shape.sh).
+        // 20.2 + 11.8 us; 1 000 x 1 000 x 128: 16 splits 11.4 + 1 099 us, 8 splits 14.1 + 7.6 us (rocprofv3 kernel trace).
         splits = std::max(1, std::min(splits, tiles_total / 2));
     }
     p.splits = splits;
@@ -2460,10 +2338,9 @@ int ftk_cosine_match_device(ftk_context *ctx, const float *d_ref_desc, int32_t n
     const size_t o_irr_cnt = carve(sizeof(uint32_t));
     const size_t o_clear_end = off;
     const size_t o_cand = carve(sizeof(int32_t) * (size_t)p.n_ref_pad * ftk::kCosineCandCap);
-    // the on-chip-ref kernels walk cur ONCE (running row maximum + scored candidate lists); FTK_COSINE_TWO_PASS=1 with
-    // FTK_COSINE_KERNEL=rs keeps the maximum-then-collect pair of launches for comparison
-    const bool single_walk =
-        p.ref_stationary == 2 || (p.ref_stationary == 1 && !(FTK_ENV(ctx, cosine_two_pass) && atoi(FTK_ENV(ctx, cosine_two_pass)) == 1));
+    // the register-stationary kernel walks cur ONCE (running row maximum + scored candidate lists); the chunked kernel runs the
+    // maximum-then-collect pair of launches
+    const bool single_walk = p.ref_stationary != 0;
     const size_t o_cand_score = single_walk ? carve(sizeof(float) * (size_t)p.n_ref_pad * ftk::kCosineCandCap) : 0;
     const size_t o_irr_list = carve(sizeof(int32_t) * ftk::kCosineIrregularCap);
     const int rc = ensure_cosine_ws(ctx, off);

@@ -94,7 +94,6 @@ struct KltParams {
     uint32_t spill_stride_floats;
     int32_t tree;                        // 0: sums in the reference's order (the contract); 1: throughput mode — the same per-pixel products, summed
                                          // by per-lane partials + a cross-lane butterfly (ftk_set_reduction_mode; reported, never the default)
-    unsigned long long *stamps; // diagnostic build (-DFTK_STAMPS) only: 8 cycle totals per feature; else null
 };
 
 // ceil(2^32 / d): row = umulhi(index, magic)
@@ -120,10 +119,7 @@ __host__ __device__ constexpr void klt_fill_geometry(KltParams &p) {
     p.magic_exc = klt_div_magic(p.ex_cols);
     p.rwin_rows = p.patch_rows + 3;
     p.rwin_cols = (p.patch_cols + 3 + 3) & ~3;  // pixel-pair columns, rounded up to a multiple of 4 (8-byte LDS stores)
-#ifndef FTK_CWIN_MARGIN
-#define FTK_CWIN_MARGIN 2
-#endif
-    p.cwin_margin = FTK_CWIN_MARGIN;
+    p.cwin_margin = 2;
     p.cwin_rows = p.rwin_rows + 2 * p.cwin_margin;
     p.cwin_cols = (p.patch_cols + 3 + 2 * p.cwin_margin + 3) & ~3;
     p.magic_rwc = klt_div_magic(p.rwin_cols);
@@ -164,10 +160,7 @@ hipError_t klt_basic_pipelined_launch(const KltParams &p, hipStream_t stream);
 
 // Reference descriptors a thread of the register-tiled Hamming scan keeps in registers (a 256-thread workgroup covers
 // 256 * kMatchRefs reference rows); the host sizes its grid and its NearbyMatch boxes with the same number.
-#ifndef FTK_MATCH_REFS
-#define FTK_MATCH_REFS 2
-#endif
-constexpr int kMatchRefs = FTK_MATCH_REFS;
+constexpr int kMatchRefs = 2;
 constexpr int kMatchRowsPerBlock = 256 * kMatchRefs;
 
 struct MatchParams {
@@ -182,9 +175,7 @@ struct MatchParams {
     float max_col, max_row;
     int32_t cur_per_block;  // candidates scanned by one workgroup
     int32_t keys_clean;     // keys already hold "no match" (context-owned workspace: the epilogue leaves it that way)
-    unsigned long long *stamps;  // diagnostic build (-DFTK_MATCH_STAMPS) only: {start, end} s_memrealtime + HW_ID per workgroup; else null
     int32_t matrix_cores;   // 1: the scan on the matrix cores (hamming_match_mfma_kernel; n_words 8 / 16)
-    int32_t lds_tiles;      // experiment (FTK_MATCH_KERNEL=lds): candidates staged through LDS tiles instead of the scalar path
     float4 *boxes;          // NearbyMatch, optional: ceil(n_ref / 512) prediction boxes, then one candidate box per split
                             // ({u min, u max, v min, v max}; hamming_box_kernel fills them, the scan leaves early on them)
     int32_t small_off;      // experiment (FTK_MATCH_SMALL=0, read once per context): never the one-launch form
@@ -215,19 +206,17 @@ struct CosineParams {
     void *clear_begin;        // row_max | cand_count | irregular_count, contiguous: zeroed by one memset per call
     size_t clear_bytes;
     int32_t n_ref, n_cur, dim, n_ref_pad, n_cur_pad, dim_pad;
-    int32_t tiles_per_split;  // cur tiles (128 rows; 256 in ref-stationary mode) walked by one workgroup
-    int32_t ref_stationary;   // dim_pad <= 256.  2: cosine_gemm_rr_kernel (ref fragments in registers; n_ref_pad % 512 == 0,
-                              // n_cur_pad % 64 == 0, `splits` workgroups share the cur tiles evenly);
-                              // 1: cosine_gemm_rs_kernel (ref rows in LDS; n_cur_pad % 256 == 0, tiles_per_split)
+    int32_t tiles_per_split;  // cur tiles (128 rows) walked by one workgroup of the chunked kernel
+    int32_t ref_stationary;   // dim_pad <= 256: cosine_gemm_rr_kernel (ref fragments in registers; n_ref_pad % 512 == 0,
+                              // n_cur_pad % 64 == 0, `splits` workgroups share the cur tiles evenly); 0: the chunked kernel
     int32_t splits;
     float max_distance, max_col, max_row;
-    int32_t small_off, small_any;  // experiments (FTK_COSINE_SMALL=0 / FTK_COSINE_SMALL_ANY=1, read once per context)
+    int32_t small_off;        // experiment (FTK_COSINE_SMALL=0, read once per context): never the one-launch form
 };
-size_t cosine_rs_lds_bytes(int dim_pad);
 size_t cosine_rr_lds_bytes(int dim_pad);
 hipError_t cosine_match_launch(const CosineParams &p, hipStream_t stream);
 // Whether cosine_match_launch runs a call of this shape as one exact launch without the workspace (small calls).
-bool cosine_small_form(int n_ref, int n_cur, int dim, bool nearby, bool small_off, bool small_any);
+bool cosine_small_form(int n_ref, int n_cur, int dim, bool nearby, bool small_off);
 
 // DirectMethod (direct_kernels.hip): one workgroup per pose problem; all problems of a launch share
 // the pyramid depth and the options.
@@ -245,11 +234,7 @@ struct DirectProblem {
     int32_t status_valid;   // 0: reset every status to kTracked first (direct_method_tracker.cpp:73-75)
     float4 *feat;           // null: the per-feature projection table lives in LDS; else n_track entries of device memory (large problems)
 };
-#if defined(FTK_DM_WAVES) && FTK_DM_WAVES > 8
-constexpr uint32_t kDirectLdsFeatures = 384;  // (experiment builds with more producer waves: a larger ring)
-#else
 constexpr uint32_t kDirectLdsFeatures = 768;  // tracked features whose per-feature table (64 B each) still fits in LDS beside the ring
-#endif
 struct DirectParams {
     const DirectProblem *problems;  // device memory, one per workgroup
     int32_t tree;                   // throughput mode (ftk_set_reduction_mode): butterfly sums instead of the scalar loop's order
@@ -361,11 +346,10 @@ hipError_t unpack_klt_shards_launch(const uint8_t *d_gathered, int32_t n, int32_
                                     uint8_t *d_status_out, hipStream_t stream);
 hipError_t pyramid_downsample_launch(const uint8_t *src, int32_t src_rows, int32_t src_cols, uint8_t *dst, hipStream_t stream);
 // Levels 1 .. n_levels - 1 from level 0 (dst[l] = level l, l >= 1): one fused launch (pyramid_fused_kernel), deeper levels one by one.
-// level0_keep (needs pyramid_fused_enabled() and n_levels >= 2): `level0` is a device-visible source outside the pyramid (pinned host
-// memory) and the same launch stores it as the pyramid's level 0.
+// level0_keep (n_levels >= 2): `level0` is a device-visible source outside the pyramid (pinned host memory) and the same launch
+// stores it as the pyramid's level 0.
 hipError_t pyramid_build_levels_launch(const uint8_t *level0, int32_t rows, int32_t cols, uint8_t *const *dst, int32_t n_levels, hipStream_t stream,
                                        uint8_t *level0_keep = nullptr);
-bool pyramid_fused_enabled();
 hipError_t extract_patch_launch(DevImage ref, float u, float v, int32_t ex_rows, int32_t ex_cols, float *d_patch, uint8_t *d_valid,
                                 uint32_t *d_count, hipStream_t stream);
 

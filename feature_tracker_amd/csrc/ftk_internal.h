@@ -14,17 +14,18 @@
 using ftk::DevImage;
 
 // The FTK_* experiment switches of the library, read ONCE per context (ftk_context_create; ftk_context_refresh_env re-reads them for
-// a test or a sweep that flips one): no getenv on any call path.  None of them changes a result — they pick launch shapes and kernels.
+// a test or a sweep that flips one): no getenv on any call path.  Most pick launch shapes and kernels and leave every result as it is.
+// Two do not: FTK_REDUCTION=tree starts the context in the throughput mode (not the reference's summation order), and
+// FTK_DIRECT_SPREAD_POISON=1 makes the spread direct-method kernel act as if its waits had run out (tests only).
 #define FTK_ENV_SWITCHES(X)                                                                                                        \
-    X(klt_waves, "FTK_KLT_WAVES") X(klt_group, "FTK_KLT_GROUP") X(klt_pipelined, "FTK_KLT_PIPELINED") X(klt_fast_kernel, "FTK_KLT_FAST_KERNEL") \
-    X(lssd_chunked, "FTK_LSSD_CHUNKED") X(klt_spill, "FTK_KLT_SPILL") X(klt_spill_budget_mb, "FTK_KLT_SPILL_BUDGET_MB") X(klt_sched, "FTK_KLT_SCHED") \
-    X(klt_swap, "FTK_KLT_SWAP") X(klt_order, "FTK_KLT_ORDER") X(klt_position_order, "FTK_KLT_POSITION_ORDER") X(klt_swap_dump, "FTK_KLT_SWAP_DUMP") \
-    X(klt_sched_dump, "FTK_KLT_SCHED_DUMP") X(stamps_dump, "FTK_STAMPS_DUMP") X(klt_zerocopy, "FTK_KLT_ZEROCOPY") X(pyramid_zerocopy, "FTK_PYRAMID_ZEROCOPY") \
-    X(match_wgs, "FTK_MATCH_WGS") X(match_splits, "FTK_MATCH_SPLITS") X(match_any_per, "FTK_MATCH_ANY_PER") X(match_kernel, "FTK_MATCH_KERNEL") \
-    X(match_boxes, "FTK_MATCH_BOXES") X(match_stamps_dump, "FTK_MATCH_STAMPS_DUMP") X(match_small, "FTK_MATCH_SMALL") \
-    X(direct_spread, "FTK_DIRECT_SPREAD") X(direct_spread_min_terms, "FTK_DIRECT_SPREAD_MIN_TERMS") X(direct_spread_resident, "FTK_DIRECT_SPREAD_RESIDENT") X(direct_spread_poison, "FTK_DIRECT_SPREAD_POISON") X(direct_spread_max_problems, "FTK_DIRECT_SPREAD_MAX_PROBLEMS") \
-    X(cosine_kernel, "FTK_COSINE_KERNEL") X(cosine_chunked, "FTK_COSINE_CHUNKED") X(cosine_splits, "FTK_COSINE_SPLITS") X(cosine_two_pass, "FTK_COSINE_TWO_PASS") \
-    X(cosine_small, "FTK_COSINE_SMALL") X(cosine_small_any, "FTK_COSINE_SMALL_ANY") X(reduction, "FTK_REDUCTION") X(klt_policy, "FTK_KLT_POLICY") X(klt_quad, "FTK_KLT_QUAD") X(klt_tail, "FTK_KLT_TAIL") X(klt_sched_min, "FTK_KLT_SCHED_MIN") X(klt_tail_class, "FTK_KLT_TAIL_CLASS") X(pinned_noncoherent, "FTK_PINNED_NONCOHERENT")
+    X(klt_waves, "FTK_KLT_WAVES") X(klt_group, "FTK_KLT_GROUP") X(lssd_chunked, "FTK_LSSD_CHUNKED") X(klt_spill, "FTK_KLT_SPILL")              \
+    X(klt_spill_budget_mb, "FTK_KLT_SPILL_BUDGET_MB") X(klt_sched, "FTK_KLT_SCHED") X(klt_sched_min, "FTK_KLT_SCHED_MIN")                     \
+    X(klt_sched_dump, "FTK_KLT_SCHED_DUMP") X(klt_swap_dump, "FTK_KLT_SWAP_DUMP") X(klt_tail_class, "FTK_KLT_TAIL_CLASS")                     \
+    X(match_small, "FTK_MATCH_SMALL") X(match_kernel, "FTK_MATCH_KERNEL")                                                                  \
+    X(direct_spread, "FTK_DIRECT_SPREAD") X(direct_spread_min_terms, "FTK_DIRECT_SPREAD_MIN_TERMS")                                        \
+    X(direct_spread_resident, "FTK_DIRECT_SPREAD_RESIDENT") X(direct_spread_poison, "FTK_DIRECT_SPREAD_POISON")                            \
+    X(cosine_small, "FTK_COSINE_SMALL") X(cosine_chunked, "FTK_COSINE_CHUNKED") X(cosine_splits, "FTK_COSINE_SPLITS")                      \
+    X(reduction, "FTK_REDUCTION")
 
 struct ftk_env {
 #define X(field, name) const char *field = nullptr;

@@ -32,15 +32,7 @@
 //
 // Arithmetic contract as in klt_kernels.hip: IEEE fp32, no contraction, correctly rounded division.
 #define FTK_CHAIN_ROUND 4  // 16 terms per round: the consumer wave holds 32 VGPRs of prefetched terms
-#ifndef FTK_PB_QUAD_CHAIN
-#define FTK_PB_QUAD_CHAIN 1  // the exact-order chain through the DPP network (klt_common.h chain_quads_left); 0: one lane per sum (round 4)
-#endif
-#ifndef FTK_PB_CHAIN_AHEAD
-#define FTK_PB_CHAIN_AHEAD 1  // the consumer reads chunk q + 1 of a step under the adds of chunk q (klt_common.h chain_quads_chunks); 0: chunk by chunk
-#endif
 #include "klt_common.h"
-
-#include <stdlib.h>
 
 namespace ftk {
 namespace {
@@ -48,12 +40,9 @@ namespace {
 constexpr int kChunk = 64;  // pixels per chunk = one producer wave round
 // Ring rows are kChunk + 4 floats apart: the consumer's lanes read 16 bytes each from DIFFERENT rows
 // at the same column, and a row pitch of 256 B would put all of them on the same four banks.
-#ifndef FTK_PB_RING_PAD
-#define FTK_PB_RING_PAD 16
-#endif
 // (round 5: the quad chain reads 16 bytes per lane, the four lanes of a quad 64 consecutive bytes of ONE row; a pitch of 80 floats puts
 // the rows of the two quads of an 8-lane group on the two halves of the banks.  Its quads follow klt_common.h chain_quads_left.)
-constexpr int kRingRow = kChunk + FTK_PB_RING_PAD;
+constexpr int kRingRow = kChunk + 16;
 constexpr int kTerms = 5;   // 0 H00, 1 H11, 2 H01, 3 -fx*ft, 4 -fy*ft (basic_klt.cpp:139-144)
 constexpr int kCurQuads = 4;  // 8-byte window loads a thread may hold in flight (current window)
 constexpr int kRefQuads = 3;  // ... (next level's reference window)
@@ -298,9 +287,7 @@ __device__ __forceinline__ uint32_t magic20(int d) {
     return m;
 }
 
-#ifndef FTK_WAVES_PER_EU
-#define FTK_WAVES_PER_EU 4
-#endif
+constexpr int kWavesPerEu = 4;
 
 // Workgroup barrier — or, for one-wave features packed several to a workgroup (solo), only a compiler fence: LDS operations of
 // one wave execute in program order, and the other waves of the group work on other features.
@@ -323,7 +310,7 @@ __device__ __forceinline__ void pb_sync(bool solo) {
 // products, different summation order: NOT bit-identical to the reference; a separate instantiation so that the contract path's
 // code is untouched by it.
 template <bool SOLO, int HR, int HC, bool TREE>
-__global__ void __attribute__((amdgpu_waves_per_eu(FTK_WAVES_PER_EU))) __launch_bounds__(256) klt_basic_inverse_pipelined_kernel(const KltParams p_arg) {
+__global__ void __attribute__((amdgpu_waves_per_eu(kWavesPerEu))) __launch_bounds__(256) klt_basic_inverse_pipelined_kernel(const KltParams p_arg) {
     // `p` carries everything but the level tables, which stay in the kernel argument (p_arg.ref / p_arg.cur): a local copy whose
     // arrays are indexed with a run-time level would be placed in scratch memory (measured: the kernel twice as slow).
     klt_touch_kernarg<sizeof(KltParams)>();  // every line of the argument block requested up front (klt_common.h)
@@ -415,10 +402,6 @@ __global__ void __attribute__((amdgpu_waves_per_eu(FTK_WAVES_PER_EU))) __launch_
         }
         return;
     }
-#ifdef FTK_STAMPS
-    const unsigned long long stamp_kernel_t0 = __builtin_amdgcn_s_memtime();
-    const unsigned long long stamp_real_t0 = __builtin_amdgcn_s_memrealtime();  // 100 MHz, common to all CUs
-#endif
     const PbLds c = pb_carve(lds_mine, p, b.nwaves);
     const int np = pb_producers(b.nwaves);
     const bool producer = (b.nwaves == 1) || b.wave > 0;
@@ -428,10 +411,8 @@ __global__ void __attribute__((amdgpu_waves_per_eu(FTK_WAVES_PER_EU))) __launch_
     const int n_chunks = (p.P + kChunk - 1) / kChunk;
     const int n_steps = (n_chunks + np - 1) / np;
     const int ring_mask = pb_ring_slots(b.nwaves) - 1;
-#if FTK_PB_QUAD_CHAIN && FTK_PB_CHAIN_AHEAD
     const bool last_chunk_short = p.P - (n_chunks - 1) * kChunk <= 48;  // (a last chunk of 49 .. 64 terms is a full one: its row is zero beyond P)
     const float *const quad_rows = c.ring + min(b.lane >> 2, kTerms - 1) * kRingRow + 4 * (b.lane & 3);  // this lane's quad's sum, its 4 of every 16 terms
-#endif
 
     // basic_klt.cpp:10,18-19 (pyramid) / :59-86 (single level)
     const float full_ref_u = full_ref.x, full_ref_v = full_ref.y;
@@ -445,7 +426,6 @@ __global__ void __attribute__((amdgpu_waves_per_eu(FTK_WAVES_PER_EU))) __launch_
     const int ref_quads_total = rrows * (rcols >> 2), cur_quads_total = p.cwin_rows * (p.cwin_cols >> 2);
     const bool ref_fits = ref_quads_total <= kRefQuads * b.nt, cur_fits = cur_quads_total <= kCurQuads * b.nt;
 
-    FTK_STAMP_BEGIN(b);
     int buf = 0;
     {
         // the coarsest level's reference window: nothing to overlap it with yet
@@ -454,29 +434,12 @@ __global__ void __attribute__((amdgpu_waves_per_eu(FTK_WAVES_PER_EU))) __launch_
         footprint_origin(p, ref_u, ref_v, r_lo, c_lo);
         stage_any(opaque_blk(b), ref, c.ref_win, r_lo, c_lo, rrows, rcols, p.pb_magic_rwc, p.pb_magic_rwq);
     }
-#ifdef FTK_STAMPS_FINE2
-    FTK_STAMP_END(b, 2);  // fine2: the prologue's reference window (reported in the "count" column together with the B1 waits)
-#endif
     uint32_t iters = 0;
     float out_u = in_u, out_v = in_v;
     for (int level = p.n_levels - 1; level > -1; --level) {
         const DevImage ref = p_arg.ref[level];
         const DevImage cur = p_arg.cur[level];
         set_level_priority(level, younger);
-#ifdef FTK_PB_CHAIN_PRIO
-        if (b.nwaves > 1) {
-            // the exact-order chain is the feature's critical path: its wave outranks the producers sharing the SIMD
-            if (consumer) {
-                __builtin_amdgcn_s_setprio(3);
-            } else if (level >= 2) {
-                __builtin_amdgcn_s_setprio(2);
-            } else if (level == 1) {
-                __builtin_amdgcn_s_setprio(1);
-            } else {
-                __builtin_amdgcn_s_setprio(0);
-            }
-        }
-#endif
         // ---- level entry: issue the window loads, build the node tables meanwhile ----
         Win rw, cw;
         rw.data = c.ref_win + buf * c.ref_win_stride;
@@ -501,20 +464,12 @@ __global__ void __attribute__((amdgpu_waves_per_eu(FTK_WAVES_PER_EU))) __launch_
         // the lattice are built: at one wave per feature the level entry is a chain of dependent latencies
         RawQuads<kCurQuads> qc;
         RawQuads<kRefQuads> qn;
-#ifdef FTK_STAMPS_FINE2
-        FTK_STAMP_END(b, 0);  // fine2: footprints, window tests, level priority, DevImage fetches
-#endif
         if (cur_async) {
             issue_quads(qc, b, cur, cw.r_lo, cw.c_lo, cw.rows, cw.cols, p.magic_cwq);
         }
         if (next_async) {
             issue_quads(qn, b, p_arg.ref[level - 1], nr_lo, nc_lo, rrows, rcols, p.pb_magic_rwq);
         }
-#ifdef FTK_STAMPS_FINE2
-        FTK_STAMP_END(b, 1);  // fine2: issuing the window loads
-#elif defined(FTK_STAMPS_FINE)
-        FTK_STAMP_END(b, 0);  // fine: footprints + issuing the window loads
-#endif
         if (b.wave == 0) {
             // both axes' node tables in one pass of wave 0 (two passes when the patch has more than 64 rows + columns)
             AxisSpec ar = {p.patch_rows, p.half_rows, ref.rows - 1, rw.r_lo, rw.rows - 1, rw.cols, p.pb_cap_r, ref_v, c.rnodes, c.ridx, &c.slots[0]};
@@ -529,18 +484,7 @@ __global__ void __attribute__((amdgpu_waves_per_eu(FTK_WAVES_PER_EU))) __launch_
                 build_nodes_pass(lane, ac, none);
             }
         }
-#ifdef FTK_STAMPS_FINE2
-        FTK_STAMP_END(b, 3);  // fine2: node tables (wave 0) land in the lattice column
-        pb_sync(solo);
-        FTK_STAMP_END(b, 2);
-#elif defined(FTK_STAMPS_FINE)
-        FTK_STAMP_END(b, 1);  // fine: node tables (wave 0)
-        pb_sync(solo);
-        FTK_STAMP_END(b, 2);  // fine: wait at B1
-#else
         pb_sync(solo);  // B1: node tables (and this level's reference window) visible
-        FTK_STAMP_END(b, 0);
-#endif
         // ---- lattice: one bilinear per node pair ----
         const int n_r = (int)c.slots[0], n_c = (int)c.slots[1];
         {
@@ -552,9 +496,6 @@ __global__ void __attribute__((amdgpu_waves_per_eu(FTK_WAVES_PER_EU))) __launch_
                 c.lattice[idx] = node_tap(rw.data, rw.cols, c.rnodes[r], c.cnodes[cc]);
             }
         }
-#ifdef FTK_STAMPS_FINE
-        FTK_STAMP_END(b, 3);  // fine: lattice
-#endif
         // ---- consume the prefetched loads ----
         if (cur_async) {
             store_quads(qc, b, c.cur_win, cw.rows, cw.cols, p.magic_cwq);
@@ -568,19 +509,11 @@ __global__ void __attribute__((amdgpu_waves_per_eu(FTK_WAVES_PER_EU))) __launch_
                 stage_any(opaque_blk(b), p_arg.ref[level - 1], c.ref_win + (buf ^ 1) * c.ref_win_stride, nr_lo, nc_lo, rrows, rcols, p.pb_magic_rwc, p.pb_magic_rwq);
             }
         }
-#ifdef FTK_STAMPS_FINE
-        FTK_STAMP_END(b, 5);  // fine: window stores (waits for the global loads)
-        pb_sync(solo);
-        b.stamp_t0 = __builtin_amdgcn_s_memtime();
-#else
         pb_sync(solo);  // B2: lattice and windows visible
-        FTK_STAMP_END(b, 1);
-#endif
 
         // ---- Gauss-Newton iterations (TrackOneFeature, basic_klt.cpp:88-116) ----
         for (uint32_t iter = 0; iter < p.max_iteration; ++iter) {
             ++iters;
-            FTK_STAMP_BEGIN(b);
             if (iter > 0 && !win_covers(cw, cur_u, cur_v)) {  // four float compares in the usual case (klt_common.h win_set_cover)
                 // restage the current window when the patch has left it (wave-uniform)
                 footprint_origin(p, cur_u, cur_v, need_r, need_c);
@@ -595,9 +528,6 @@ __global__ void __attribute__((amdgpu_waves_per_eu(FTK_WAVES_PER_EU))) __launch_
                     pb_sync(solo);
                 }
             }
-#ifndef FTK_STAMPS_FINE
-            FTK_STAMP_END(b, 2);
-#endif
             uint32_t wave_valid = 0;
             float acc = 0.0f;
             if constexpr (TREE) {
@@ -663,11 +593,9 @@ __global__ void __attribute__((amdgpu_waves_per_eu(FTK_WAVES_PER_EU))) __launch_
                         }
                     }
                     pb_sync(solo);
-#if FTK_PB_QUAD_CHAIN
                     if (consumer) {
                         // the whole wave: quad k = lanes 4 k .. 4 k + 3 carries sum k (klt_common.h, "quad chain"); the quads behind the
                         // fifth follow its rows and are ignored
-#if FTK_PB_CHAIN_AHEAD
                         // the step's chunks are all in the ring: the full ones in one go (the next chunk's reads under this one's adds),
                         // then the patch's last chunk if it has fewer than 49 terms
                         const int first = s * np, count = min(np, n_chunks - first);
@@ -679,32 +607,12 @@ __global__ void __attribute__((amdgpu_waves_per_eu(FTK_WAVES_PER_EU))) __launch_
                         if (full < count) {
                             acc = chain_quads_left(acc, row + full * (kTerms * kRingRow), p.P - (n_chunks - 1) * kChunk);
                         }
-#else
-                        const int sum = min(b.lane >> 2, kTerms - 1);
-                        for (int q = 0; q < np; ++q) {
-                            if (s * np + q < n_chunks) {
-                                acc = chain_quads_left(acc, c.ring + (((s & ring_mask) * np + q) * kTerms + sum) * kRingRow + 4 * (b.lane & 3), p.P - (s * np + q) * kChunk);
-                            }
-                        }
-#endif
                     }
-#else
-                    if (consumer && b.lane < kTerms) {
-                        for (int q = 0; q < np; ++q) {
-                            if (s * np + q < n_chunks) {
-                                acc = chain_chunk_left(acc, c.ring + (((s & ring_mask) * np + q) * kTerms + b.lane) * kRingRow, p.P - (s * np + q) * kChunk);
-                            }
-                        }
-                    }
-#endif
                 }
-    #ifndef FTK_STAMPS_FINE
-                FTK_STAMP_END(b, 3);
-    #endif
                 if (consumer) {
                     float m[2][2], bb[2], sol[2];
                     const int acc_bits = __float_as_int(acc);
-                    constexpr int kSumLanes = FTK_PB_QUAD_CHAIN ? 4 : 1;  // sum k ends in lane 4 k (every lane of its quad) / in lane k
+                    constexpr int kSumLanes = 4;  // sum k ends in lane 4 k (every lane of its quad)
                     m[0][0] = __int_as_float(__builtin_amdgcn_readlane(acc_bits, 0));
                     m[1][1] = __int_as_float(__builtin_amdgcn_readlane(acc_bits, 1 * kSumLanes));
                     m[0][1] = m[1][0] = __int_as_float(__builtin_amdgcn_readlane(acc_bits, 2 * kSumLanes));
@@ -717,9 +625,6 @@ __global__ void __attribute__((amdgpu_waves_per_eu(FTK_WAVES_PER_EU))) __launch_
                     }
                 }
                 pb_sync(solo);  // B3: solution and valid counts visible
-    #ifndef FTK_STAMPS_FINE
-                FTK_STAMP_END(b, 5);
-    #endif
             }
             const float v0 = c.sol[0], v1 = c.sol[1];  // read together with the counts: one LDS round trip, not two
             uint32_t n_valid = 0;
@@ -755,7 +660,6 @@ __global__ void __attribute__((amdgpu_waves_per_eu(FTK_WAVES_PER_EU))) __launch_
         cur_u *= 2.0f;
         cur_v *= 2.0f;
         buf ^= 1;
-        FTK_STAMP_BEGIN(b);
     }
 
     if (uv_outside(out_u, out_v, p_arg.cur[0])) {
@@ -774,23 +678,6 @@ __global__ void __attribute__((amdgpu_waves_per_eu(FTK_WAVES_PER_EU))) __launch_
             p.sched_iters[id] = iters;  // the next call's launch order (ftk_api.cpp: longest first)
         }
     }
-#ifdef FTK_STAMPS
-    if (b.tid == 0 && p.stamps) {
-        b.stamp_acc[7] = __builtin_amdgcn_s_memtime() - stamp_kernel_t0;
-        b.stamp_acc[6] = stamp_real_t0;
-#ifdef FTK_STAMPS_FINE
-        b.stamp_acc[4] = b.stamp_acc[2];  // fine: the B1 wait is reported in the "count" column
-#endif
-        b.stamp_acc[2] = ((unsigned long long)__builtin_amdgcn_s_getreg((20 << 11) | 20) << 32) |  // XCC_ID (hwreg 20), all bits
-                         (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4);            // HW_ID (hwreg 4): wave, simd, cu, sh, se
-#ifndef FTK_STAMPS_FINE
-        b.stamp_acc[4] = __builtin_amdgcn_s_memrealtime();
-#endif
-        for (int k = 0; k < 8; ++k) {
-            p.stamps[(size_t)id * 8 + k] = b.stamp_acc[k];
-        }
-    }
-#endif
 }
 
 
@@ -833,10 +720,9 @@ hipError_t klt_basic_pipelined_launch(const KltParams &p_in, hipStream_t stream)
     // compile-time geometry for the patch sizes of the BASELINE configurations and the reference's default (11x11, 13x13, 21x21);
     // the throughput mode (p.tree: reported, never the contract) has its own instantiations of the same set
     void (*kernel)(const KltParams) = pick_kernel<0, 0>(solo, p.tree != 0);
-    static const bool specialise = !(getenv("FTK_PB_SPECIALISE") && atoi(getenv("FTK_PB_SPECIALISE")) == 0);  // experiment switch
-    if (specialise && p.half_rows == p.half_cols) {
+    if (p.half_rows == p.half_cols) {
         KltParams check = p;
-        klt_fill_geometry(check);  // the specialised kernels recompute exactly this: refuse them if the caller's geometry differs (diagnostic builds)
+        klt_fill_geometry(check);  // the specialised kernels recompute exactly this: refuse them if the caller's geometry differs
         const bool same = check.pb_cap_r == p.pb_cap_r && check.pb_cap_c == p.pb_cap_c && check.cwin_rows == p.cwin_rows && check.cwin_cols == p.cwin_cols;
         if (same) {
             switch (p.half_rows) {

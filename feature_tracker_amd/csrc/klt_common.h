@@ -17,21 +17,6 @@ namespace {
 
 constexpr int kWave = 64;
 
-// Diagnostic build only (-DFTK_STAMPS): per-phase cycle totals of every workgroup, written to a
-// side buffer that no other code reads.  The production build contains none of this.
-#ifdef FTK_STAMPS
-#define FTK_STAMP_BEGIN(b) (b).stamp_t0 = __builtin_amdgcn_s_memtime()
-#define FTK_STAMP_END(b, k)                                           \
-    do {                                                              \
-        const unsigned long long now_ = __builtin_amdgcn_s_memtime(); \
-        (b).stamp_acc[k] += now_ - (b).stamp_t0;                      \
-        (b).stamp_t0 = now_;                                          \
-    } while (0)
-#else
-#define FTK_STAMP_BEGIN(b)
-#define FTK_STAMP_END(b, k)
-#endif
-
 // ---------------------------------------------------------------------------------------------
 // scalar helpers
 // ---------------------------------------------------------------------------------------------
@@ -58,10 +43,6 @@ struct Blk {
     int tid, nt, lane, wave, nwaves;
     bool solo = false;  // compile-time true in the one-wave instantiations: no workgroup barrier anywhere, cross-wave exchanges fold away
     bool tree = false;  // throughput mode (KltParams::tree): sums by per-lane partials + a butterfly instead of the exact-order chain
-#ifdef FTK_STAMPS
-    mutable unsigned long long stamp_t0 = 0;
-    mutable unsigned long long stamp_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#endif
 };
 
 // Workgroup barrier; for a one-wave feature only a compiler fence (LDS operations of one wave execute in program order).
@@ -109,15 +90,10 @@ __device__ __forceinline__ void klt_touch_kernarg() {
 // evenly and the last one finishes ~10 % earlier (measured: 53.9 -> 49.3 us span at 2000 features).
 // `younger`: the workgroup sits in the later-dispatched half of the launch.  With 2 000 identical features the finishing time
 // still correlates 0.87 with the launch slot (31 us for the first 250 workgroups, 36 for the last 250, all started within
-// 0.4 us: scripts/stamps_placement.py), so the younger half runs one step above the older half of the same level:
+// 0.4 us: per-workgroup timestamps), so the younger half runs one step above the older half of the same level:
 // config 2 40.4 -> 39.0 us per step, 300 / 1 000-feature launches -3.5 %, config 5 shard -1.7 %, config 1 +-0.  (Rotating or
 // purely age-based priorities, and a finer split, all lose: docs/LAB_NOTES.md.)
 __device__ __forceinline__ void set_level_priority(int level, bool younger = false) {
-#ifdef FTK_NO_LEVEL_PRIO
-    (void)level;
-    (void)younger;
-    return;
-#endif
     const int pr = (level >= 3 ? 3 : level) + (younger ? 1 : 0);
     if (pr >= 3) {
         __builtin_amdgcn_s_setprio(3);
@@ -808,15 +784,10 @@ constexpr int kChainRound = FTK_CHAIN_ROUND;
 // add (its float4 was issued last) covers the whole round — one s_waitcnt per round instead of one per float4.  A lone wave issues
 // one instruction of ANY kind per 4 cycles (scripts/microbench/dep_add_latency.hip: a dependent v_add_f32 costs 4, an s_nop or
 // s_waitcnt in between 4 more), so the waits were a ninth of the chain loop's instructions.
-#ifdef FTK_CHAIN_FORWARD_ISSUE
-constexpr bool kChainReversedIssue = false;
-#else
-constexpr bool kChainReversedIssue = true;
-#endif
 __device__ __forceinline__ void chain_load(float4 (&q)[kChainRound], const float4 *t) {
 #pragma unroll
     for (int d = 0; d < kChainRound; ++d) {
-        const int e = kChainReversedIssue ? kChainRound - 1 - d : d;
+        const int e = kChainRound - 1 - d;
         q[e] = t[e];
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -905,7 +876,7 @@ template <int kStride4>
 __device__ __forceinline__ void chain_load_groups(float4 (&q)[kChainRound], const float4 *t) {
 #pragma unroll
     for (int d = 0; d < kChainRound; ++d) {
-        const int e = kChainReversedIssue ? kChainRound - 1 - d : d;
+        const int e = kChainRound - 1 - d;
         q[e] = t[e * kStride4];
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -1007,20 +978,11 @@ __device__ __forceinline__ float chain_chunk_left(float acc, const float *row, i
 // front of this block, the two wait states a DPP operand needs after a VALU write are there (it cannot see the DPP in the asm).
 __device__ __forceinline__ float chain_quad_step16(float acc, const float4 q) {
     asm volatile("s_nop 1\n" FTK_QADD4(0) FTK_QADD4(1) FTK_QADD4(2) FTK_QADD4(3) : "+v"(acc) : "v"(q.x), "v"(q.y), "v"(q.z), "v"(q.w));
-#ifdef FTK_QUAD_EXTRA_ZERO_ADDS  // experiment: what do 16 more adds per 16 terms cost (acc + 0 == acc)?
-    {
-        const float z = 0.0f;
-        asm volatile("s_nop 1\n" FTK_QADD4(0) FTK_QADD4(1) FTK_QADD4(2) FTK_QADD4(3) : "+v"(acc) : "v"(z), "v"(z), "v"(z), "v"(z));
-    }
-#endif
     return acc;
 }
 
 // 64 terms (four reads) in one block: one `s_nop` and one wait for the reads per 64 adds instead of per 16 — a lone wave issues an
 // instruction of any kind every 4 - 5 cycles, so each instruction that is not an add costs as much as a term.
-#ifndef FTK_QUAD_STEP64
-#define FTK_QUAD_STEP64 1  // 0: 16-add blocks everywhere (A / B, scripts/build_variant.sh)
-#endif
 #define FTK_QADD4R(i, a, b, c, d) FTK_QADD(i, a) FTK_QADD(i, b) FTK_QADD(i, c) FTK_QADD(i, d)
 #define FTK_QADD16R(a, b, c, d) FTK_QADD4R(0, a, b, c, d) FTK_QADD4R(1, a, b, c, d) FTK_QADD4R(2, a, b, c, d) FTK_QADD4R(3, a, b, c, d)
 __device__ __forceinline__ float chain_quad_step64(float acc, const float4 q0, const float4 q1, const float4 q2, const float4 q3) {
@@ -1094,7 +1056,7 @@ __device__ __forceinline__ float chain_quads_chunks(float acc, const float4 *t, 
 // affine fast on the real pair -4 .. -5 %): 64-add blocks; otherwise (the multi-wave kernels: no consistent difference) 16-add blocks.
 template <bool kBlocks64 = false>
 __device__ __forceinline__ float chain_quads_strided(float acc, const float4 *t, int n16, int step4) {
-    if constexpr (kBlocks64 && FTK_QUAD_STEP64) {
+    if constexpr (kBlocks64) {
         // blocks of four steps (64 adds in one asm block), the reads of the next block issued before the adds of this one; the up to
         // three steps behind the last block are read up front and kept in registers (no LDS latency at the end of the chain)
         const int rem = n16 & 3, tail = n16 - rem;
@@ -1590,10 +1552,7 @@ constexpr int kOrderLdsBytes = (4 * 256 + 4) * 4;  // two histograms (iteration 
 // of the image per XCD fetch least — 5.5 MB instead of 32.8 MB per 25 000-feature launch at 1080p — but run 6 % SLOWER than list
 // order; runs of 4 / 16 / 32 / 64 / 128 / 256 workgroups: +2.5 / +1.3 / -0.9 / -1.6 / -1.6 / -1.3 % with 21.8 / 15.8 / - / 9.8 MB
 // fetched).  Only whole blocks of 8 runs take part; the ranks behind them stay put.
-#ifndef FTK_ORDER_RUN_GROUPS
-#define FTK_ORDER_RUN_GROUPS 64
-#endif
-constexpr int kOrderRunGroups = FTK_ORDER_RUN_GROUPS;
+constexpr int kOrderRunGroups = 64;
 
 __device__ __forceinline__ int xcd_major_slot(int rank, int n, int group) {
     const int whole = n / group;  // workgroups with `group` features

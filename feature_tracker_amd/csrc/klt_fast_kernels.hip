@@ -26,12 +26,7 @@
 // Arithmetic contract as in klt_kernels.hip: IEEE fp32, no contraction, correctly rounded division, every sum strictly in
 // row-major pixel order on one lane.  Results are bit-identical to the generic kernel and to the oracle (tests/test_klt_gpu.py).
 #define FTK_CHAIN_ROUND 4
-#ifndef FTK_FK_QUAD_CHAIN
-#define FTK_FK_QUAD_CHAIN 1  // the whole-row exact-order chains through the DPP network (klt_common.h "quad chain"); 0: one lane per sum (round 4)
-#endif
 #include "klt_common.h"
-
-#include <stdlib.h>
 
 namespace ftk {
 namespace {
@@ -47,11 +42,7 @@ __host__ __device__ inline int fk_pad4(int x) { return (x + 3) & ~3; }
 // (round 5, quad chains: the four lanes of a quad read 64 consecutive bytes of ONE row and the two quads of an 8-lane group two
 // different rows — a pitch congruent 16 mod 32 floats puts those on the two halves of the banks)
 __host__ __device__ inline int fk_term_pitch(const KltParams &p) {
-#if FTK_FK_QUAD_CHAIN
     return (p.Ppad & 31) == 16 ? p.Ppad : p.Ppad + 16;
-#else
-    return (p.Ppad & 7) == 4 ? p.Ppad : p.Ppad + 4;
-#endif
 }
 
 constexpr int kAfRows = 24;     // rows of the affine ring: 0 - 5 the bias products (every iteration), 6 + A_* the 18 Hessian products (first iteration)
@@ -220,17 +211,12 @@ __device__ __forceinline__ void ldlt2_apply(const Ldlt2 &f, float b0, float b1, 
     x1 = f.swapped ? y0 : y1;
 }
 
-#ifndef FTK_WAVES_PER_EU
-#define FTK_WAVES_PER_EU 4
-#endif
+constexpr int kWavesPerEu = 4;
 
 // MODEL: FTK_MODEL_BASIC or FTK_MODEL_AFFINE.
 // HR / HC: the half patch sizes as compile-time constants (the geometry folds into immediates), or 0 / 0 for "as passed".
 template <int MODEL, int HR, int HC>
-__global__ void __attribute__((amdgpu_waves_per_eu(FTK_WAVES_PER_EU))) __launch_bounds__(256) klt_fast_kernel(const KltParams p_arg) {
-#ifdef FTK_STAMPS
-    const unsigned long long stamp_kernel_t0 = __builtin_amdgcn_s_memtime();
-#endif
+__global__ void __attribute__((amdgpu_waves_per_eu(kWavesPerEu))) __launch_bounds__(256) klt_fast_kernel(const KltParams p_arg) {
     klt_touch_kernarg<sizeof(KltParams)>();
     KltParams p = p_arg;  // everything but the level tables (a run-time level index into a local copy would put it in scratch)
     if constexpr (HR > 0 && HC > 0) {
@@ -304,9 +290,6 @@ __global__ void __attribute__((amdgpu_waves_per_eu(FTK_WAVES_PER_EU))) __launch_
     const int rrows = p.rwin_rows, rcols = p.rwin_cols;
     const bool cur_fits = p.cwin_rows * (p.cwin_cols >> 2) <= kFkCurQuads * kWave;
 
-#ifdef FTK_STAMPS
-    b.stamp_t0 = stamp_kernel_t0;
-#endif
     // ---- the coarsest level's inputs: the reference rows into registers, the current window into LDS ----
     Win cw;
     cw.data = c.cur_win;
@@ -351,7 +334,6 @@ __global__ void __attribute__((amdgpu_waves_per_eu(FTK_WAVES_PER_EU))) __launch_
         }
     }
     fk_fence();
-    FTK_STAMP_END(b, 0);
 
     uint32_t iters = 0;
     float out_u = in_u, out_v = in_v;
@@ -360,7 +342,6 @@ __global__ void __attribute__((amdgpu_waves_per_eu(FTK_WAVES_PER_EU))) __launch_
         const DevImage ref = p_arg.ref[level];
         const DevImage cur = p_arg.cur[level];
         set_level_priority(level, younger);
-        FTK_STAMP_BEGIN(b);
         // ---- ExtractExtendPatchInReferenceImage (optical_flow.cpp:49-102): ONE weight set, integer lattice floor(ref) - ex / 2 ----
         uint32_t ref_valid = 0;
         {
@@ -399,7 +380,6 @@ __global__ void __attribute__((amdgpu_waves_per_eu(FTK_WAVES_PER_EU))) __launch_
         }
         const bool all_ref_valid = ref_interior;
         fk_fence();
-        FTK_STAMP_END(b, 1);
         // ---- the next level's inputs are requested now and arrive while this level runs ----
         RawQuads<kFkCurQuads> qcn;
         int nr_lo = 0, nc_lo = 0, ncr_lo = 0, ncc_lo = 0;
@@ -420,7 +400,6 @@ __global__ void __attribute__((amdgpu_waves_per_eu(FTK_WAVES_PER_EU))) __launch_
                 issue_quads(qcn, b, ncur, ncr_lo, ncc_lo, cw.rows, cw.cols, p.magic_cwq);
             }
         }
-        FTK_STAMP_END(b, 4);
         bool level_runs = true;
         if (ref_valid == 0) {
             status = FTK_OUTSIDE;  // basic_klt_fast.cpp:12-16
@@ -453,14 +432,12 @@ __global__ void __attribute__((amdgpu_waves_per_eu(FTK_WAVES_PER_EU))) __launch_
                     }
                 }
                 fk_fence();
-                FTK_STAMP_END(b, 2);
                 status = FTK_LARGE_RESIDUAL;  // basic_klt_fast.cpp:29
                 float last_squared_step = INFINITY;
                 uint32_t large_step_cnt = 0;
                 Ldlt2 fac = {0.0f, 0.0f, 0.0f, false};
                 for (uint32_t iter = 0; iter < p.max_iteration; ++iter) {
                     ++iters;
-                    FTK_STAMP_BEGIN(b);
                     if (!win_covers(cw, cur_u, cur_v)) {
                         // the patch has left the window (or the integer test has to decide): restage around the present position
                         int need_r, need_c;
@@ -530,25 +507,16 @@ __global__ void __attribute__((amdgpu_waves_per_eu(FTK_WAVES_PER_EU))) __launch_
                         }
                     }
                     fk_fence();
-                    FTK_STAMP_END(b, 3);
                     if (n_valid == 0) {
                         break;  // basic_klt_fast.cpp:40-42
                     }
                     // the exact-order sums: lanes 0 / 1 the bias, and in the level's first iteration lanes 2 - 4 the Hessian
                     const int chains = iter == 0 ? kFkTerms : 2;
                     float acc = 0.0f;
-#if FTK_FK_QUAD_CHAIN
                     // every lane: quad q carries sum q (klt_common.h "quad chain"); the quads behind the last sum follow its row, ignored
                     constexpr int kSumLanes = 4;
                     acc = chain_quads_row<true>(0.0f, c.terms + min(lane >> 2, chains - 1) * pitch + 4 * (lane & 3), p.Ppad >> 4);
-#else
-                    constexpr int kSumLanes = 1;
-                    if (lane < chains) {
-                        acc = chain_lane(c.terms + lane * pitch, p.Ppad);
-                    }
-#endif
                     const int acc_bits = __float_as_int(acc);
-                    FTK_STAMP_END(b, 5);
                     if (iter == 0) {
                         fac = ldlt2_factor(__int_as_float(__builtin_amdgcn_readlane(acc_bits, 2 * kSumLanes)), __int_as_float(__builtin_amdgcn_readlane(acc_bits, 3 * kSumLanes)),
                                            __int_as_float(__builtin_amdgcn_readlane(acc_bits, 4 * kSumLanes)));
@@ -561,7 +529,6 @@ __global__ void __attribute__((amdgpu_waves_per_eu(FTK_WAVES_PER_EU))) __launch_
                     }
                     cur_u += v0;
                     cur_v += v1;
-                    FTK_STAMP_END(b, 6);
                     if (fast_step_logic(p, v0 * v0 + v1 * v1, last_squared_step, large_step_cnt, status)) {
                         break;
                     }
@@ -588,7 +555,6 @@ __global__ void __attribute__((amdgpu_waves_per_eu(FTK_WAVES_PER_EU))) __launch_
                     }
                 }
                 fk_fence();
-                FTK_STAMP_END(b, 2);
                 status = FTK_LARGE_RESIDUAL;  // affine_klt_fast.cpp:29
                 float last_squared_step = INFINITY;
                 uint32_t large_step_cnt = 0;
@@ -622,10 +588,6 @@ __global__ void __attribute__((amdgpu_waves_per_eu(FTK_WAVES_PER_EU))) __launch_
                     if (valid && !hit) {
                         sample(cur, cw, row_c, col_c, i_cur);  // a warped tap outside the window: global memory, same arithmetic
                     }
-#ifdef FTK_STAMPS_MISSES
-                    b.stamp_acc[2] += 100ull * (unsigned long long)__popcll(wave_ballot(in_patch && valid && !hit));  // diagnostic: taps that left the window
-                    b.stamp_acc[0] += 100ull * (unsigned long long)__popcll(wave_ballot(in_patch && !valid));        // ... and taps outside the image
-#endif
                     const bool ok = in_patch && valid && (__float_as_int(rec.w) & 1) != 0;
                     dt = ok ? i_cur - rec.z : 0.0f;
                     bx = ok ? col_c : 0.0f;
@@ -636,7 +598,6 @@ __global__ void __attribute__((amdgpu_waves_per_eu(FTK_WAVES_PER_EU))) __launch_
                 };
                 for (uint32_t iter = 0; iter < p.max_iteration; ++iter) {
                     ++iters;
-                    FTK_STAMP_BEGIN(b);
                     if (!win_covers(cw, cur_u, cur_v)) {
                         // the (unwarped) patch has left the window: restage around the present position; warped taps outside the window
                         // are sampled from global memory with the same arithmetic
@@ -727,17 +688,9 @@ __global__ void __attribute__((amdgpu_waves_per_eu(FTK_WAVES_PER_EU))) __launch_
                             n_valid += (uint32_t)__popcll(wave_ballot(ok));  // (every lane counts every pass: the total stays wave-uniform)
                         }
                         fk_fence();
-                        FTK_STAMP_END(b, 3);
-#if FTK_FK_QUAD_CHAIN
                         acc = chain_quads_row<true>(0.0f, c.terms + imul(min(lane >> 2, 5), pitch) + 4 * (lane & 3), p.Ppad >> 4);  // quad q carries bias sum q
-#else
-                        if (lane < 6) {
-                            acc = chain_lane(c.terms + imul(lane, pitch), p.Ppad);
-                        }
-#endif
                         fk_fence();
                     }
-                    FTK_STAMP_END(b, 5);
                     if (n_valid == 0) {
                         break;  // affine_klt_fast.cpp:38-40
                     }
@@ -769,15 +722,9 @@ __global__ void __attribute__((amdgpu_waves_per_eu(FTK_WAVES_PER_EU))) __launch_
                     }
                     // (the substitutions with L broadcast into wave-uniform registers — ~130 straight-line instructions instead of ~290
                     // with a cross-lane broadcast per term — were built and measured: 0.08 us per iteration SLOWER; docs/LAB_NOTES.md)
-#if FTK_FK_QUAD_CHAIN
                     if (first ? lane < 6 : ((lane & 3) == 0 && lane < 24)) {  // the ring's chain lanes / the quads' first lanes hold the six bias sums
                         c.sums[40 + (first ? lane : lane >> 2)] = acc;
                     }
-#else
-                    if (lane < 6) {
-                        c.sums[40 + lane] = acc;
-                    }
-#endif
                     fk_fence();
                     ldlt6_solve(fac, c.sums + 40, c.sums + 48, lane);  // affine_klt_fast.cpp:42
                     fk_fence();
@@ -798,7 +745,6 @@ __global__ void __attribute__((amdgpu_waves_per_eu(FTK_WAVES_PER_EU))) __launch_
                     a10 += z[1];
                     a01 += z[2];
                     a11 += z[3];
-                    FTK_STAMP_END(b, 6);
                     if (fast_step_logic(p, v0 * v0 + v1 * v1, last_squared_step, large_step_cnt, status)) {
                         break;
                     }
@@ -816,7 +762,6 @@ __global__ void __attribute__((amdgpu_waves_per_eu(FTK_WAVES_PER_EU))) __launch_
         cur_u *= 2.0f;
         cur_v *= 2.0f;
         // ---- the next level's inputs: what was requested at this level's entry, where it fits what is needed now ----
-        FTK_STAMP_BEGIN(b);
         r_lo = nr_lo;
         c_lo = nc_lo;
         ref_interior = next_interior;
@@ -842,7 +787,6 @@ __global__ void __attribute__((amdgpu_waves_per_eu(FTK_WAVES_PER_EU))) __launch_
             stage_any(opaque_blk(b), p_arg.cur[level - 1], c.cur_win, cw.r_lo, cw.c_lo, cw.rows, cw.cols, p.magic_cwc, p.magic_cwq);
         }
         fk_fence();
-        FTK_STAMP_END(b, 4);
     }
 
     if (uv_outside(out_u, out_v, p_arg.cur[0])) {
@@ -861,14 +805,6 @@ __global__ void __attribute__((amdgpu_waves_per_eu(FTK_WAVES_PER_EU))) __launch_
             p.sched_iters[id] = iters;
         }
     }
-#ifdef FTK_STAMPS
-    if (lane == 0 && p.stamps) {
-        b.stamp_acc[7] = __builtin_amdgcn_s_memtime() - stamp_kernel_t0;
-        for (int k = 0; k < 8; ++k) {
-            p.stamps[(size_t)id * 8 + k] = b.stamp_acc[k];
-        }
-    }
-#endif
 }
 
 template <int MODEL, int HR, int HC>
@@ -909,8 +845,7 @@ hipError_t klt_fast_launch(int model, const KltParams &p_in, hipStream_t stream)
     if (p.sort_iters && lds < (size_t)kOrderLdsBytes) {
         lds = kOrderLdsBytes;
     }
-    static const bool specialise = !(getenv("FTK_FK_SPECIALISE") && atoi(getenv("FTK_FK_SPECIALISE")) == 0);  // experiment switch
-    if (specialise && p.half_rows == p.half_cols) {
+    if (p.half_rows == p.half_cols) {
         KltParams check = p;
         klt_fill_geometry(check);  // what the specialised kernels recompute: it must be what the caller passed
         if (check.cwin_rows == p.cwin_rows && check.cwin_cols == p.cwin_cols && check.rwin_cols == p.rwin_cols && check.Ppad == p.Ppad) {

@@ -38,8 +38,6 @@
 #define FTK_CHAIN_ROUND 4
 #include "klt_common.h"
 
-#include <stdlib.h>
-
 namespace ftk {
 namespace {
 
@@ -180,12 +178,8 @@ __device__ __forceinline__ uint32_t collect_count(const Blk &b, const uint32_t *
     return total;
 }
 
-#ifndef FTK_KLT_QUAD_CHAIN
-#define FTK_KLT_QUAD_CHAIN 1  // sums of up to 16 term rows through the DPP network (klt_common.h "quad chain"); 0: one lane per sum (round 4)
-#endif
-
 // The chunked LSSD levels leave sum k in lane 4 k when they ran the quad chains (KltParams::quad_chain), in lane k otherwise.
-__device__ __forceinline__ int sum_lanes(const KltParams &p) { return (FTK_KLT_QUAD_CHAIN && p.quad_chain) ? 4 : 1; }
+__device__ __forceinline__ int sum_lanes(const KltParams &p) { return p.quad_chain ? 4 : 1; }
 
 // The K <= 16 sums of `terms[K][Ppad]` by ALL lanes of one wave: quad q = lanes 4 q .. 4 q + 3 carries sum q (the quads behind the last
 // sum follow its row and are ignored), Ppad / 16 steps of 16 ordered adds each; lane 4 q publishes sum q.  Same adds, same order as
@@ -205,7 +199,7 @@ __device__ __forceinline__ void chain_sums(const Blk &b, const float *terms, int
     if (b.wave == 0) {
         if (b.tree) {
             tree_sums(terms, K, Ppad, sums, b.lane);  // throughput mode: not the reference's order
-        } else if (FTK_KLT_QUAD_CHAIN && K <= 16) {
+        } else if (K <= 16) {
             chain_rows_quads(terms, K, Ppad, sums, b.lane);
         } else if (b.lane < K) {
             sums[b.lane] = chain_lane(terms + b.lane * Ppad, Ppad);
@@ -227,7 +221,7 @@ __device__ __forceinline__ void chain_then(const Blk &b, const float *terms, int
         if (b.tree) {
             tree_sums(terms, K, Ppad, sums, b.lane);  // throughput mode: not the reference's order
             __builtin_amdgcn_wave_barrier();
-        } else if (FTK_KLT_QUAD_CHAIN && K <= 16) {
+        } else if (K <= 16) {
             chain_rows_quads(terms, K, Ppad, sums, b.lane);
         } else if (b.lane < K) {
             sums[b.lane] = chain_lane(terms + b.lane * Ppad, Ppad);
@@ -474,11 +468,6 @@ __device__ __forceinline__ bool nonfast_gather(const DevImage &cur, const Win &c
     if (MODE == kGatherHoisted) {
         miss = miss || (valid && !hit);
     }
-#ifdef FTK_STAMPS
-    if (MODE == kGatherInline) {
-        miss = miss || (valid && !hit);  // diagnostic: the affine levels count the passes that left the window (stamp slot 2)
-    }
-#endif
     return ok && valid;
 }
 
@@ -551,18 +540,13 @@ struct BasicState {
 template <int METHOD>
 __device__ __forceinline__ void basic_level(const Blk &b, const KltParams &p, const DevImage &ref, const DevImage &cur, float ref_u, float ref_v,
                                             BasicState &s, uint8_t &status, uint32_t &iters, Carve &c) {
-    FTK_STAMP_BEGIN(b);
     Win rw, cw;
     stage_level_windows(b, p, ref, cur, ref_u, ref_v, s.cur_u, s.cur_v, c, rw, cw, (METHOD == FTK_METHOD_INVERSE) ? 3 : 1);
     bool cw_staged = true;
-    FTK_STAMP_END(b, 0);
     nonfast_level_setup<METHOD>(b, p, ref, rw, ref_u, ref_v, c);
-    FTK_STAMP_END(b, 1);
     for (uint32_t iter = 0; iter < p.max_iteration; ++iter) {
         ++iters;
-        FTK_STAMP_BEGIN(b);
         ensure_cur_window(b, p, cur, s.cur_u, s.cur_v, c, cw, cw_staged);
-        FTK_STAMP_END(b, 2);
         // phase A; slow == true_type redoes it through the general sampler when a tap left the window
         auto phase_a = [&](auto slow, bool &miss) -> uint32_t {
             constexpr bool kSlow = decltype(slow)::value;
@@ -590,14 +574,12 @@ __device__ __forceinline__ void basic_level(const Blk &b, const KltParams &p, co
         };
         bool miss = false;
         uint32_t n_valid = phase_a(std::false_type{}, miss);
-        FTK_STAMP_END(b, 3);
         publish_count(b, n_valid, c.wave_cnt, iter);
         if (block_any(b, miss, c.wave_cnt, iter & 1u)) {
             n_valid = phase_a(std::true_type{}, miss);
             publish_count(b, n_valid, c.wave_cnt, iter);
             blk_sync(b);
         }
-        FTK_STAMP_END(b, 4);
         chain_then(b, c.terms, 5, p.Ppad, c.sums, false, [&]() {
             float m[2][2];
             float bb[2], sol[2];
@@ -611,7 +593,6 @@ __device__ __forceinline__ void basic_level(const Blk &b, const KltParams &p, co
             c.sums[17] = sol[1];
             reinterpret_cast<uint32_t *>(c.sums)[18] = collect_count(b, c.wave_cnt, iter);  // travels with the solution: one LDS round trip after the barrier
         });
-        FTK_STAMP_END(b, 5);
         n_valid = reinterpret_cast<const uint32_t *>(c.sums)[18];
         const float v[2] = {c.sums[16], c.sums[17]};
         if (n_valid == 0) {
@@ -623,7 +604,6 @@ __device__ __forceinline__ void basic_level(const Blk &b, const KltParams &p, co
         }
         s.cur_u += v[0];
         s.cur_v += v[1];
-        FTK_STAMP_END(b, 6);
         if (uv_outside(s.cur_u, s.cur_v, cur)) {
             status = FTK_OUTSIDE;
             break;
@@ -863,17 +843,13 @@ template <int METHOD>
 __device__ __forceinline__ void affine_level(const Blk &b, const KltParams &p, const DevImage &ref, const DevImage &cur, float ref_u, float ref_v,
                                              AffineState &s, uint8_t &status, uint32_t &iters, Carve &c) {
     Win rw, cw;
-    FTK_STAMP_BEGIN(b);
     stage_level_windows(b, p, ref, cur, ref_u, ref_v, s.cur_u, s.cur_v, c, rw, cw, (METHOD == FTK_METHOD_INVERSE) ? 3 : 1);
     bool cw_staged = true;
-    FTK_STAMP_END(b, 0);
     nonfast_level_setup<METHOD, true>(b, p, ref, rw, ref_u, ref_v, c);
-    FTK_STAMP_END(b, 1);
     const bool staged = !b.solo && b.nwaves > 1 && p.P > b.nt;
     const uint32_t dense_slots = affine_dense_slots(b.lane);  // chain lane -> its entries of the dense Hessian (wave 0)
     for (uint32_t iter = 0; iter < p.max_iteration; ++iter) {
         ++iters;
-        FTK_STAMP_BEGIN(b);
         ensure_cur_window(b, p, cur, s.cur_u, s.cur_v, c, cw, cw_staged);
         bool miss_unused = false;
         // the 24 products of one patch pixel -> terms[k][pxi]; returns whether the pixel is used
@@ -902,7 +878,6 @@ __device__ __forceinline__ void affine_level(const Blk &b, const KltParams &p, c
             }
             publish_count(b, n_valid, c.wave_cnt, iter);
             blk_sync(b);  // the terms (and the published counts) are visible
-            FTK_STAMP_END(b, 3);
             // (The 24 sums as quad chains on TWO waves side by side — 16 + 8 quads, published through LDS, one more barrier — were built
             // and measured in round 5: slower, config 3 139.8 -> 149.1 us, real pair 300 features 89.1 -> 91.1; docs/LAB_NOTES.md.)
             if (b.wave == 0 && b.lane < A_COUNT) {
@@ -913,11 +888,7 @@ __device__ __forceinline__ void affine_level(const Blk &b, const KltParams &p, c
                 const bool ok = produce(b.tid);  // P > nt: every lane has a pixel
                 n_valid += (uint32_t)__popcll(wave_ballot(ok));
             }
-#ifdef FTK_STAMPS
-            b.stamp_acc[2] += (unsigned long long)__popcll(wave_ballot(miss_unused));  // lanes of wave 0's pass that sampled global memory
-#endif
             blk_sync(b);  // the products of pixels [0, nt) are visible
-            FTK_STAMP_END(b, 3);
             if (b.wave == 0) {
                 if (b.lane < A_COUNT) {
                     acc = chain_groups<kAffineGroup / 4>(reinterpret_cast<const float4 *>(c.terms) + b.lane, b.nt / (4 * kChainRound), 0.0f);
@@ -949,7 +920,6 @@ __device__ __forceinline__ void affine_level(const Blk &b, const KltParams &p, c
             } else if (b.lane < A_COUNT) {
                 c.sums[b.lane] = acc;
             }
-            FTK_STAMP_END(b, 4);
             float ad_all[6];
 #pragma unroll
             for (int j = 0; j < 6; ++j) {
@@ -968,10 +938,8 @@ __device__ __forceinline__ void affine_level(const Blk &b, const KltParams &p, c
             if (b.lane == 0) {
                 reinterpret_cast<uint32_t *>(c.sums)[A_COUNT + 6] = collect_count(b, c.wave_cnt, iter);
             }
-            FTK_STAMP_END(b, 5);
         }
         blk_sync(b);  // the solution is visible
-        FTK_STAMP_END(b, 6);
         n_valid = reinterpret_cast<const uint32_t *>(c.sums)[A_COUNT + 6];
         const float z[6] = {c.sums[A_COUNT], c.sums[A_COUNT + 1], c.sums[A_COUNT + 2], c.sums[A_COUNT + 3], c.sums[A_COUNT + 4], c.sums[A_COUNT + 5]};
         if (n_valid == 0) {
@@ -1194,11 +1162,9 @@ __device__ __forceinline__ void lssd_level(const Blk &b, const KltParams &p, con
     float *icur = c.a0;
     for (uint32_t iter = 0; iter < p.max_iteration; ++iter) {
         ++iters;
-        FTK_STAMP_BEGIN(b);
         float centre_u, centre_v;
         se2_apply(s, ref_u, ref_v, centre_u, centre_v);
         ensure_cur_window(b, p, cur, centre_u, centre_v, c, cw, cw_staged);
-        FTK_STAMP_END(b, 2);
         // pass 1 (:140-184): validity mask and the two patch means (sequential sums)
         uint32_t n_valid = 0;
         bool miss_unused = false;
@@ -1225,10 +1191,8 @@ __device__ __forceinline__ void lssd_level(const Blk &b, const KltParams &p, con
             }
             n_valid += (uint32_t)__popcll(wave_ballot(ok));
         }
-        FTK_STAMP_END(b, 3);  // pass 1: sampling, the two mean terms
         n_valid = block_total(b, n_valid, c.wave_cnt);
         chain_sums(b, c.terms, 2, p.Ppad, c.sums);
-        FTK_STAMP_END(b, 4);  // count exchange + the two mean chains
         const float ref_average = c.sums[0] / (float)n_valid;
         const float cur_average = c.sums[1] / (float)n_valid;
         const float grad_average = (METHOD == FTK_METHOD_INVERSE) ? ref_average : cur_average;
@@ -1252,12 +1216,10 @@ __device__ __forceinline__ void lssd_level(const Blk &b, const KltParams &p, con
             lssd_terms(p, c.terms, pxi, ok, j0, j1, j2, residual);
         }
         blk_sync(b);
-        FTK_STAMP_END(b, 5);  // pass 2: divisions by the means, nine products
         if (n_valid == 0) {
             break;
         }
         chain_then(b, c.terms, 9, p.Ppad, c.sums, false, [&]() { lssd_solve(c.sums, b.lane); });
-        FTK_STAMP_END(b, 6);  // nine chains + the 3 x 3 solve
         float v[3];
         const bool solved = lssd_solve_and_update(c.sums, s, v, status, b.lane);
         blk_sync(b);  // sums[] is rewritten by the first chain of the next iteration
@@ -1479,10 +1441,8 @@ __device__ __forceinline__ void lssd_level_fast_chunked(const Blk &b, const KltP
     Win rw, cw;
     float level_centre_u, level_centre_v;
     se2_apply(s, ref_u, ref_v, level_centre_u, level_centre_v);
-    FTK_STAMP_BEGIN(b);
     stage_level_windows(b, p, ref, cur, ref_u, ref_v, level_centre_u, level_centre_v, c, rw, cw);
     bool cw_staged = true;
-    FTK_STAMP_END(b, 0);  // diagnostic build: level windows
     const uint32_t ref_valid_num = extract_extended_patch(b, p, ref, rw, ref_u, ref_v, c);
     if (ref_valid_num == 0) {
         status = FTK_OUTSIDE;
@@ -1498,7 +1458,6 @@ __device__ __forceinline__ void lssd_level_fast_chunked(const Blk &b, const KltP
         rc[pxi] = make_float2((float)(prow - p.half_rows) + ref_v, (float)(pcol - p.half_cols) + ref_u);
     }
     blk_sync(b);
-    FTK_STAMP_END(b, 1);  // extended patch + gradients
 
     status = FTK_LARGE_RESIDUAL;
     float last_squared_step = INFINITY;
@@ -1506,7 +1465,6 @@ __device__ __forceinline__ void lssd_level_fast_chunked(const Blk &b, const KltP
     const int n_chunks = (p.P + kChunkPixels - 1) / kChunkPixels;
     for (uint32_t iter = 0; iter < p.max_iteration; ++iter) {
         ++iters;
-        FTK_STAMP_BEGIN(b);
         float centre_u, centre_v;
         se2_apply(s, ref_u, ref_v, centre_u, centre_v);
         ensure_cur_window(b, p, cur, centre_u, centre_v, c, cw, cw_staged);
@@ -1579,7 +1537,7 @@ __device__ __forceinline__ void lssd_level_fast_chunked(const Blk &b, const KltP
                 for (int k = 0; k < 9; ++k) {
                     part[k] += ring[k * kChunkRow + b.lane];
                 }
-            } else if (FTK_KLT_QUAD_CHAIN && p.quad_chain) {
+            } else if (p.quad_chain) {
                 // every lane: quad q carries sum q (klt_common.h "quad chain"); the quads behind the ninth follow its row and are ignored.
                 // A launch that oversubscribes the chip keeps one lane per sum (KltParams::quad_chain): there the instruction COUNT decides.
                 acc = chain_quads_left(acc, ring + min(b.lane >> 2, 8) * kChunkRow + 4 * (b.lane & 3), p.P - chunk * kChunkPixels);
@@ -1601,7 +1559,6 @@ __device__ __forceinline__ void lssd_level_fast_chunked(const Blk &b, const KltP
                 acc = (b.lane == k * sum_lanes(p)) ? part[k] : acc;  // the sums where the exact path leaves them: lanes 0..8 (quad chains: 0, 4 .. 32)
             }
         }
-        FTK_STAMP_END(b, 3);  // window check + the chunks (sampling, products, chains)
         if (wave_ballot(seen_cur) == 0ull || wave_ballot(seen_valid) == 0ull) {
             break;  // lssd_klt_fast.cpp:60-63 / :80-83
         }
@@ -1620,7 +1577,6 @@ __device__ __forceinline__ void lssd_level_fast_chunked(const Blk &b, const KltP
             break;
         }
         se2_update<true>(s, v, b.lane);
-        FTK_STAMP_END(b, 5);  // solve + update
         if (fast_step_logic(p, vec3_squared_norm(v), last_squared_step, large_step_cnt, status)) {
             break;
         }
@@ -1737,7 +1693,7 @@ __device__ __forceinline__ void lssd_level_fast_chunked_lum(const Blk &b, const 
                 cur_valid_num += (uint32_t)__popcll(wave_ballot(ok_cur));
                 ring[b.lane] = interior ? value : 0.0f;
                 blk_sync(b);
-                if (FTK_KLT_QUAD_CHAIN && p.quad_chain) {
+                if (p.quad_chain) {
                     mean_acc = chain_quads_left(mean_acc, ring + 4 * (b.lane & 3), p.P - chunk * kChunkPixels);  // every quad carries the one sum
                 } else if (b.lane == 0) {
                     mean_acc = chain_chunk_left(mean_acc, ring, p.P - chunk * kChunkPixels);
@@ -1779,7 +1735,7 @@ __device__ __forceinline__ void lssd_level_fast_chunked_lum(const Blk &b, const 
                 ring[8 * kChunkRow + b.lane] = -(dy * residual);
                 seen_valid = seen_valid || ok;
                 blk_sync(b);
-                if (FTK_KLT_QUAD_CHAIN && p.quad_chain) {
+                if (p.quad_chain) {
                     acc = chain_quads_left(acc, ring + min(b.lane >> 2, 8) * kChunkRow + 4 * (b.lane & 3), p.P - chunk * kChunkPixels);
                 } else if (b.lane < 9) {
                     acc = chain_chunk_left(acc, ring + b.lane * kChunkRow, p.P - chunk * kChunkPixels);
@@ -1830,17 +1786,12 @@ struct ChainCount<FTK_MODEL_LSSD> {
 };
 
 constexpr int kMaxWaves = 4;
-#ifndef FTK_LONG_SLOTS
-#define FTK_LONG_SLOTS 128
-#endif
-constexpr int kLongFeatureSlots = FTK_LONG_SLOTS;  // launch slots (longest first) that keep the top issue priority
+constexpr int kLongFeatureSlots = 128;  // launch slots (longest first) that keep the top issue priority
 
-// Register cap: the compiler is asked to fit FTK_WAVES_PER_EU waves per SIMD so that enough feature
+// Register cap: the compiler is asked to fit kWavesPerEu waves per SIMD so that enough feature
 // workgroups are co-resident per CU (the kernel is issue / latency bound, not register bound).
-#ifndef FTK_WAVES_PER_EU
-#define FTK_WAVES_PER_EU 4  // <= 128 VGPRs: 8 two-wave (or 4 four-wave) feature workgroups per CU
-#endif
-#define FTK_EU_ATTR __attribute__((amdgpu_waves_per_eu(FTK_WAVES_PER_EU)))
+constexpr int kWavesPerEu = 4;  // <= 128 VGPRs: 8 two-wave (or 4 four-wave) feature workgroups per CU
+#define FTK_EU_ATTR __attribute__((amdgpu_waves_per_eu(kWavesPerEu)))
 
 // (The non-fast affine variants used to need a cap of 3 — 168 VGPRs, 24 of them row pointers of the product stores; with the
 // grouped product layout, affine_all_terms, they fit 128 like the rest.)
@@ -1939,9 +1890,6 @@ __global__ void FTK_EU_ATTR __launch_bounds__(kWave *kMaxWaves) klt_track_kernel
         return;
     }
 
-#ifdef FTK_STAMPS
-    const unsigned long long stamp_kernel_t0 = __builtin_amdgcn_s_memtime();
-#endif
     constexpr int K = ChainCount<MODEL>::value;
     float *lds_mine = reinterpret_cast<float *>(lds_raw);
     if (SOLO && p.features_per_group > 1) {
@@ -2025,11 +1973,6 @@ __global__ void FTK_EU_ATTR __launch_bounds__(kWave *kMaxWaves) klt_track_kernel
             }
         }
 
-#ifdef FTK_STAMPS
-        for (int k = 0; k < 8; ++k) {
-            b0.stamp_acc[k] = b.stamp_acc[k];  // `b` is this level's copy (opaque_blk): carry its totals over
-        }
-#endif
         if (level == 0) {
             if (MODEL == FTK_MODEL_BASIC) {
                 out_u = bs.cur_u;
@@ -2075,14 +2018,6 @@ __global__ void FTK_EU_ATTR __launch_bounds__(kWave *kMaxWaves) klt_track_kernel
             p.sched_iters[id] = iters;  // the next call's launch order (ftk_api.cpp: longest first)
         }
     }
-#ifdef FTK_STAMPS
-    if (b.tid == 0 && p.stamps) {
-        b.stamp_acc[7] = __builtin_amdgcn_s_memtime() - stamp_kernel_t0;
-        for (int k = 0; k < 8; ++k) {
-            p.stamps[(size_t)id * 8 + k] = b.stamp_acc[k];
-        }
-    }
-#endif
 }
 
 template <int MODEL, int METHOD>
@@ -2096,18 +2031,14 @@ hipError_t launch_variant(const KltParams &p, size_t lds_bytes, hipStream_t stre
     } else if (p.tree) {  // throughput mode (reported, never the contract): its own instantiations, run-time geometry
         kernel = p.waves_per_feature == 1 ? klt_track_kernel<MODEL, METHOD, true, 0, true> : klt_track_kernel<MODEL, METHOD, false, 0, true>;
     }
-    static const bool specialise = !(getenv("FTK_KLT_SPECIALISE") && atoi(getenv("FTK_KLT_SPECIALISE")) == 0);  // experiment switch
     // (measured per variant, 13 x 13: Basic -6...-14 %, LSSD -16...-21 %, affine fast -16 %, affine inverse / direct -8...-9 % — the
     // latter only once chain_groups' loop is kept rolled: with a compile-time round count the compiler unrolled it fully and the
     // kernel went from 81 to 128 VGPRs and 9...18 % SLOWER)
-    constexpr bool gains = true;
-    if constexpr (gains) {
-        if (!p.tree && !p.spill && specialise && p.half_rows == 6 && p.half_cols == 6) {
-            KltParams check = p;
-            klt_fill_geometry(check);  // what the specialised kernel recomputes: it must be what the caller passed
-            if (check.cwin_rows == p.cwin_rows && check.cwin_cols == p.cwin_cols && check.Ppad == p.Ppad && check.rwin_cols == p.rwin_cols) {
-                kernel = p.waves_per_feature == 1 ? klt_track_kernel<MODEL, METHOD, true, 6> : klt_track_kernel<MODEL, METHOD, false, 6>;
-            }
+    if (!p.tree && !p.spill && p.half_rows == 6 && p.half_cols == 6) {
+        KltParams check = p;
+        klt_fill_geometry(check);  // what the specialised kernel recomputes: it must be what the caller passed
+        if (check.cwin_rows == p.cwin_rows && check.cwin_cols == p.cwin_cols && check.Ppad == p.Ppad && check.rwin_cols == p.rwin_cols) {
+            kernel = p.waves_per_feature == 1 ? klt_track_kernel<MODEL, METHOD, true, 6> : klt_track_kernel<MODEL, METHOD, false, 6>;
         }
     }
     if constexpr (MODEL == FTK_MODEL_LSSD && METHOD == FTK_METHOD_FAST) {

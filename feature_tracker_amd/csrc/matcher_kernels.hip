@@ -188,12 +188,11 @@ __global__ void __launch_bounds__(kBlock) hamming_box_kernel(const MatchParams p
 }
 
 // Register-tiled scan (n_bits > 0): thread i keeps kRefs reference descriptors in registers, so one
-// broadcast LDS read of a candidate feeds kRefs popcount chains, and the running best is a packed
-// integer key (distance << 16 | position in the tile) maintained with one v_lshl_or + one v_min_u32
-// per pair — the minimum of that key is the smallest distance and, among equals, the lowest j, which
-// is what the reference's strict '<' scan returns.  Tiles are visited in ascending j and a later tile
-// replaces the best only with a strictly smaller distance.  18 VALU per pair (8 xor, 8 bcnt, 2 key) on the full path,
-// 13 (6 xor, 6 bcnt, 1 compare) on the early-exit path described in the kernel.
+// fetch of a candidate feeds kRefs popcount chains, and the running best is a packed integer key
+// (distance << 16 | position in the chunk) maintained with one v_lshl_or + one v_min_u32 per pair —
+// the minimum of that key is the smallest distance and, among equals, the lowest j, which is what the
+// reference's strict '<' scan returns.  Chunks are visited in ascending j and a later chunk replaces
+// the best only with a strictly smaller distance.
 constexpr int kRefs = kMatchRefs;
 
 // popcount(x) + acc in ONE instruction (v_bcnt_u32_b32 adds its second operand).  Written out because the compiler, left to
@@ -210,35 +209,33 @@ static __device__ __forceinline__ uint32_t popc_first(uint32_t x) {
     return r;
 }
 
-template <int NW, bool kNearby>
-__global__ void __launch_bounds__(kBlock) hamming_match_tiled_kernel(const MatchParams p) {
-    __shared__ __attribute__((aligned(16))) uint32_t tile_words[kTile * NW];
-    __shared__ float2 tile_uv[kTile];
+// The candidates travel on the SCALAR path: every lane of a wave compares its own reference rows with the same candidate, so
+// the candidate's words are wave-uniform — they are fetched with s_load_dwordx8 through the scalar cache into SGPRs (constant
+// address space) and feed v_xor_b32 as its scalar operand.  No LDS tile, no staging pass, no barrier, no LDS address
+// arithmetic on the VALU: what is left per pair is 6 xor + 6 bcnt + 1 compare on the early-exit path.
+// The waves of a workgroup never synchronise; a candidate pair's 64 bytes are requested one step ahead of their use.
+typedef const __attribute__((address_space(4))) uint32_t *scalar_words;
+typedef const __attribute__((address_space(4))) float *scalar_floats;
+constexpr int kChunk = 32768;  // candidates per packed-key epoch (position in 16 bits)
 
-#ifdef FTK_MATCH_STAMPS
-    const unsigned long long stamp_t0 = __builtin_amdgcn_s_memrealtime();
-    const unsigned long long stamp_c0 = __builtin_amdgcn_s_memtime();
-#endif
+template <int NW, bool kNearby>
+__global__ void __launch_bounds__(kBlock) hamming_match_scalar_kernel(const MatchParams p) {
     // A workgroup that starts while older ones are in their popcount loops is the youngest on its SIMDs and gets only the
-    // issue slots the others leave (oldest first): its descriptor loads went out 10 us late (stamps build).  Raised priority
-    // until the descriptors are in registers lets it get its memory requests in flight at once.
+    // issue slots the others leave (oldest first): its descriptor loads went out 10 us late (measured with per-workgroup
+    // timestamps).  Raised priority until the descriptors are in registers lets it get its memory requests in flight at once.
     __builtin_amdgcn_s_setprio(3);
     // thread t owns rows t, t + 256, ... of the workgroup's block: a wave's 16-byte loads of one row segment then walk the
     // descriptors with a 32-byte stride (half of every fetched line is used by this load, the other half by the next one),
-    // where rows 2t, 2t + 1 would stride 64 bytes — measured with the stamps build: the descriptor load of a workgroup
-    // took 8 us (median) of its 30 us that way
+    // where rows 2t, 2t + 1 would stride 64 bytes — measured with per-workgroup timestamps: the descriptor load of a
+    // workgroup took 8 us (median) of its 30 us that way
     const int i_base = blockIdx.x * kBlock * kRefs + threadIdx.x;
     const int j_begin = blockIdx.y * p.cur_per_block;
-#ifdef FTK_MATCH_STAMPS
-    asm volatile("" ::"s"(j_begin));
-    const unsigned long long stamp_args = __builtin_amdgcn_s_memrealtime();  // kernel arguments have arrived
-#endif
     const int j_end = min(j_begin + p.cur_per_block, p.n_cur);
     if (kNearby && p.boxes != nullptr) {
         // NearbyMatch: when the bounding box of this workgroup's 512 predictions and the bounding box of its candidates
         // (hamming_box_kernel) are more than window + 1 px apart on an axis, no pair passes
         // fabs(du) <= max_col && fabs(dv) <= max_row (the pixel covers the rounding of the fp32 difference) and the
-        // workgroup is done before it stages a candidate.  A NaN coordinate passes every window test
+        // workgroup is done before it fetches a candidate.  A NaN coordinate passes every window test
         // (descriptor_matcher.h:108-111), so it makes its box the whole plane.  Exact for any input; it pays when the
         // features come in spatial order (a detector scanning the image), where most workgroups leave here.
         const float4 pb = p.boxes[blockIdx.x], cb = p.boxes[gridDim.x + blockIdx.y];
@@ -254,7 +251,7 @@ __global__ void __launch_bounds__(kBlock) hamming_match_tiled_kernel(const Match
         const int i = i_base + r * kBlock;
         const bool active = i < p.n_ref;
         // unconditional wide loads from a clamped row (a per-word `active ? load : 0` compiles to one exec-masked 4-byte load per
-        // word: 16 scattered dword loads per thread — the stamps build showed the descriptor load at 8 us of a 30-us workgroup)
+        // word: 16 scattered dword loads per thread, 8 us of a 30-us workgroup)
         const uint32_t *row = p.ref_words + (long long)(active ? i : p.n_ref - 1) * NW;
         if (NW % 4 == 0) {
 #pragma unroll
@@ -280,14 +277,8 @@ __global__ void __launch_bounds__(kBlock) hamming_match_tiled_kernel(const Match
         pred_u[r] = (kNearby && active) ? p.pred_uv[2 * i] : 0.0f;
         pred_v[r] = (kNearby && active) ? p.pred_uv[2 * i + 1] : 0.0f;
     }
-
-#ifdef FTK_MATCH_STAMPS
-    asm volatile("" ::"v"(ref[0][0]));
-    const unsigned long long stamp_after_load = __builtin_amdgcn_s_memrealtime();
-#endif
     __builtin_amdgcn_s_setprio(0);
-    uint32_t best_d[kRefs];
-    int best_j[kRefs];
+
     // A pair matters only when its distance is below BOTH the row's running minimum (strict '<': ties keep the earlier j)
     // and the threshold (descriptor_matcher.h:68-71, :106-114: min_distance starts AT kMaxValidDescriptorDistance), and a
     // Hamming distance only grows word by word.  So after kEarly of the NW words, a candidate whose partial count has
@@ -297,182 +288,6 @@ __global__ void __launch_bounds__(kBlock) hamming_match_tiled_kernel(const Match
     // Exact for any input (the branch only skips work that cannot change the result); `limit` is kept conservative
     // (>= the true bound), the final comparison against max_distance below is the authoritative one.
     constexpr int kEarly = NW >= 8 ? (NW * 3) / 4 : NW;
-    uint32_t limit[kRefs];
-    const uint32_t limit0 = (p.max_distance >= 0.0f && p.max_distance < 65000.0f) ? (uint32_t)p.max_distance + 1u : (p.max_distance < 0.0f ? 0u : 0xFFFFu);
-#pragma unroll
-    for (int r = 0; r < kRefs; ++r) {
-        best_d[r] = 0xFFFFu;  // above any real distance (<= 512)
-        best_j[r] = -1;
-        limit[r] = limit0;
-    }
-    for (int tile_begin = j_begin; tile_begin < j_end; tile_begin += kTile) {
-        const int tile_n = min(kTile, j_end - tile_begin);
-        __syncthreads();
-        for (int idx = (int)threadIdx.x; idx < tile_n * NW; idx += kBlock) {
-            tile_words[idx] = p.cur_words[(long long)tile_begin * NW + idx];
-        }
-        if (kNearby && (int)threadIdx.x < tile_n) {
-            tile_uv[threadIdx.x] = make_float2(p.cur_uv[2 * (tile_begin + threadIdx.x)], p.cur_uv[2 * (tile_begin + threadIdx.x) + 1]);
-        }
-        __syncthreads();
-        uint32_t key[kRefs];
-#pragma unroll
-        for (int r = 0; r < kRefs; ++r) {
-            key[r] = 0xFFFFFFFFu;
-        }
-        // two candidates per step (indices clamped to the tile's last: seeing a candidate twice changes nothing), their first
-        // kEarly words fetched one step ahead into the other register set so that the LDS latency sits under the previous
-        // pair's popcounts; two steps per trip so that the two sets swap roles without register moves
-        uint32_t cw[2][2][NW];
-        auto fetch = [&](int set, int t) {
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                const int tc = min(t + c, tile_n - 1);
-#pragma unroll
-                for (int w = 0; w < kEarly; ++w) {
-                    cw[set][c][w] = tile_words[tc * NW + w];
-                }
-            }
-        };
-        auto step = [&](int set, int t) {
-            uint32_t d[2][kRefs];
-            bool alive = false;
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-#pragma unroll
-                for (int r = 0; r < kRefs; ++r) {
-                    d[c][r] = popc_first(ref[r][0] ^ cw[set][c][0]);
-#pragma unroll
-                    for (int w = 1; w < kEarly; ++w) {
-                        d[c][r] = popc_add(ref[r][w] ^ cw[set][c][w], d[c][r]);
-                    }
-                    alive = alive | (d[c][r] < limit[r]);
-                }
-            }
-            if (kEarly == NW || __builtin_expect(__ballot(alive) != 0ull, 0)) {  // wave-uniform
-#pragma unroll
-                for (int c = 0; c < 2; ++c) {
-                    const int tc = min(t + c, tile_n - 1);
-#pragma unroll
-                    for (int w = kEarly; w < NW; ++w) {
-                        cw[set][c][w] = tile_words[tc * NW + w];
-                    }
-                    float2 cuv = make_float2(0.0f, 0.0f);
-                    if (kNearby) {
-                        cuv = tile_uv[tc];
-                    }
-#pragma unroll
-                    for (int r = 0; r < kRefs; ++r) {
-#pragma unroll
-                        for (int w = kEarly; w < NW; ++w) {
-                            d[c][r] = popc_add(ref[r][w] ^ cw[set][c][w], d[c][r]);
-                        }
-                        uint32_t k = (d[c][r] << 16) | (uint32_t)tc;
-                        if (kNearby) {
-                            // descriptor_matcher.h:108-111: outside the window -> not a candidate
-                            const bool out = (int)(fabsf(pred_u[r] - cuv.x) > p.max_col) | (int)(fabsf(pred_v[r] - cuv.y) > p.max_row);
-                            k = out ? 0xFFFFFFFFu : k;
-                        }
-                        key[r] = min(key[r], k);
-                        limit[r] = min(limit[r], key[r] >> 16);
-                    }
-                }
-            }
-        };
-        fetch(0, 0);
-        for (int t = 0; t < tile_n; t += 4) {
-            fetch(1, t + 2);
-            step(0, t);
-            fetch(0, t + 4);
-            step(1, t + 2);
-        }
-#pragma unroll
-        for (int r = 0; r < kRefs; ++r) {
-            const uint32_t dist = key[r] >> 16;
-            if (dist < best_d[r]) {  // strict: an earlier tile keeps ties
-                best_d[r] = dist;
-                best_j[r] = tile_begin + (int)(key[r] & 0xFFFFu);
-            }
-        }
-    }
-#ifdef FTK_MATCH_STAMPS
-    if (threadIdx.x == 0 && p.stamps) {
-        unsigned long long *st = p.stamps + 4 * ((size_t)blockIdx.y * gridDim.x + blockIdx.x);
-        st[0] = stamp_t0;
-        st[1] = __builtin_amdgcn_s_memtime() - stamp_c0;  // shader-clock ticks over the workgroup's life
-        (void)stamp_after_load;
-        st[2] = __builtin_amdgcn_s_memrealtime();
-        st[3] = ((stamp_args - stamp_t0) << 40) | ((unsigned long long)(__builtin_amdgcn_s_getreg((20 << 11) | 20) & 0xF) << 32) |
-                (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4);
-    }
-#endif
-#pragma unroll
-    for (int r = 0; r < kRefs; ++r) {
-        const int i = i_base + r * kBlock;
-        // `distance < min_distance && distance < threshold` with min_distance starting at the threshold
-        if (i < p.n_ref && best_j[r] >= 0 && (float)best_d[r] < p.max_distance) {
-            const unsigned long long packed = ((unsigned long long)best_d[r] << 32) | (unsigned)best_j[r];
-            atomicMin(&p.keys[i], packed);
-        }
-    }
-}
-
-// The same scan with the candidates on the SCALAR path: every lane of a wave compares its own reference rows with the same
-// candidate, so the candidate's words are wave-uniform — they are fetched with s_load_dwordx8 through the scalar cache
-// into SGPRs (constant address space) and feed v_xor_b32 as its scalar operand.  No LDS tile, no staging pass, no barrier,
-// no LDS address arithmetic on the VALU: what is left per pair is 6 xor + 6 bcnt + 1 compare on the early-exit path.
-// The waves of a workgroup never synchronise; a candidate pair's 64 bytes are requested one step ahead of their use.
-typedef const __attribute__((address_space(4))) uint32_t *scalar_words;
-typedef const __attribute__((address_space(4))) float *scalar_floats;
-constexpr int kChunk = 32768;  // candidates per packed-key epoch (position in 16 bits)
-
-template <int NW, bool kNearby>
-__global__ void __launch_bounds__(kBlock) hamming_match_scalar_kernel(const MatchParams p) {
-    __builtin_amdgcn_s_setprio(3);  // see hamming_match_tiled_kernel: get the descriptor loads out at once
-    const int i_base = blockIdx.x * kBlock * kRefs + threadIdx.x;
-    const int j_begin = blockIdx.y * p.cur_per_block;
-    const int j_end = min(j_begin + p.cur_per_block, p.n_cur);
-    if (kNearby && p.boxes != nullptr) {
-        const float4 pb = p.boxes[blockIdx.x], cb = p.boxes[gridDim.x + blockIdx.y];
-        const float reach_u = p.max_col + 1.0f, reach_v = p.max_row + 1.0f;
-        if (cb.x - pb.y > reach_u || pb.x - cb.y > reach_u || cb.z - pb.w > reach_v || pb.z - cb.w > reach_v) {
-            return;  // block-uniform (hamming_match_tiled_kernel explains the box test)
-        }
-    }
-    uint32_t ref[kRefs][NW];
-    float pred_u[kRefs], pred_v[kRefs];
-#pragma unroll
-    for (int r = 0; r < kRefs; ++r) {
-        const int i = i_base + r * kBlock;
-        const bool active = i < p.n_ref;
-        const uint32_t *row = p.ref_words + (long long)(active ? i : p.n_ref - 1) * NW;
-        if (NW % 4 == 0) {
-#pragma unroll
-            for (int w = 0; w < NW; w += 4) {
-                const uint4 q = *reinterpret_cast<const uint4 *>(row + w);
-                ref[r][w] = q.x;
-                ref[r][w + 1] = q.y;
-                ref[r][w + 2] = q.z;
-                ref[r][w + 3] = q.w;
-            }
-        } else {
-#pragma unroll
-            for (int w = 0; w < NW; ++w) {
-                ref[r][w] = row[w];
-            }
-        }
-        if (!active) {
-#pragma unroll
-            for (int w = 0; w < NW; ++w) {
-                ref[r][w] = 0u;
-            }
-        }
-        pred_u[r] = (kNearby && active) ? p.pred_uv[2 * i] : 0.0f;
-        pred_v[r] = (kNearby && active) ? p.pred_uv[2 * i + 1] : 0.0f;
-    }
-    __builtin_amdgcn_s_setprio(0);
-
-    constexpr int kEarly = NW >= 8 ? (NW * 3) / 4 : NW;  // see hamming_match_tiled_kernel
     uint32_t best_d[kRefs], limit[kRefs];
     int best_j[kRefs];
     const uint32_t limit0 = (p.max_distance >= 0.0f && p.max_distance < 65000.0f) ? (uint32_t)p.max_distance + 1u : (p.max_distance < 0.0f ? 0u : 0xFFFFu);
@@ -672,11 +487,6 @@ static __device__ __forceinline__ void mfma_update_keys(const MatchParams &p, co
 template <int NW, bool kNearby>
 static __device__ __forceinline__ void mfma_scan(const MatchParams &p, int lane, int c, int h, int row0, int j_begin, int j_end) {
     const int last = j_end - 1;
-#ifdef FTK_MATCH_STAMPS
-    const unsigned long long st_rt0 = __builtin_amdgcn_s_memrealtime();
-    const unsigned long long st_c0 = __builtin_amdgcn_s_memtime();
-    unsigned long long st_slow = 0, st_slow_n = 0;
-#endif
     // ---- candidate words: two register sets, the tile after the current one always in flight ----
     v4i words[2][NW / 4];
 #define FTK_FETCH_WORDS(set_, tile_begin_)                                                                     \
@@ -759,16 +569,6 @@ static __device__ __forceinline__ void mfma_scan(const MatchParams &p, int lane,
     int at_lowest = 32;        // how many of the 32 sit on it
     const int shift = 4 * h;
 
-#ifdef FTK_MATCH_STAMPS
-#define FTK_SLOW_BEGIN const unsigned long long slow0_ = __builtin_amdgcn_s_memtime();
-#define FTK_SLOW_END                                                \
-    asm volatile("" ::"v"(lowest));                                 \
-    st_slow += __builtin_amdgcn_s_memtime() - slow0_;               \
-    ++st_slow_n;
-#else
-#define FTK_SLOW_BEGIN
-#define FTK_SLOW_END
-#endif
 #define FTK_EXPAND_WORD(set_, m_)                                                         \
     const uint32_t half_ = (uint32_t)words[set_][(m_) / 4][(m_) % 4] >> shift;           \
     v4i b_;                                                                              \
@@ -793,7 +593,6 @@ static __device__ __forceinline__ void mfma_scan(const MatchParams &p, int lane,
         }                                                                                                                      \
         const int top_ = max(max(gtop_[0], gtop_[1]), max(gtop_[2], gtop_[3]));                                                \
         if (__builtin_expect(__ballot(top_ > lowest) != 0ull, 0)) { /* wave-uniform */                                          \
-            FTK_SLOW_BEGIN                                                                                                     \
             /* complete the distances: the remaining words' popcounts and products (group maxima of the partial results */     \
             /* stay valid as a filter: a completed result is never larger) */                                                  \
             _Pragma("unroll") for (int i_ = 0; i_ < 16; ++i_) {                                                                \
@@ -806,12 +605,8 @@ static __device__ __forceinline__ void mfma_scan(const MatchParams &p, int lane,
                 acc1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[1][m_], b_, acc1, 0, 0, 0);                                      \
             }                                                                                                                  \
             mfma_update_keys<kNearby>(p, acc0, acc1, gtop_, key, pred_rows, lowest, at_lowest, h, min((tile_begin_) + c, last), j_begin); \
-            FTK_SLOW_END                                                                                                       \
         }                                                                                                                      \
     }
-#ifdef FTK_MATCH_STAMPS
-    const unsigned long long st_prologue = __builtin_amdgcn_s_memtime() - st_c0;
-#endif
     for (int tile_begin = j_begin; tile_begin < j_end; tile_begin += 64) {
         FTK_FETCH_WORDS(1, tile_begin + 32)
         __builtin_amdgcn_sched_barrier(0);  // the loads go out BEFORE the products of the tile in hand (the scheduler sinks them otherwise)
@@ -822,9 +617,6 @@ static __device__ __forceinline__ void mfma_scan(const MatchParams &p, int lane,
             FTK_MFMA_TILE(1, tile_begin + 32)
         }
     }
-#ifdef FTK_MATCH_STAMPS
-    const unsigned long long st_loop_end = __builtin_amdgcn_s_memtime();
-#endif
     // ---- the best candidate of every row: maximum over the 32 lanes of the half, then one lane per row merges across splits ----
     // A register in which no lane of the wave found anything — nearly all of them under a real threshold — is skipped; with up
     // to eight finders per register every one of them merges its own key (atomicMin takes the smallest distance, then the
@@ -857,26 +649,11 @@ static __device__ __forceinline__ void mfma_scan(const MatchParams &p, int lane,
             atomicMin(&p.keys[row], packed);
         }
     }
-#ifdef FTK_MATCH_STAMPS
-    if (threadIdx.x == 0 && p.stamps) {
-        unsigned long long *st = p.stamps + 8 * ((size_t)blockIdx.y * gridDim.x + blockIdx.x);
-        st[0] = st_rt0;
-        st[1] = __builtin_amdgcn_s_memrealtime();
-        st[2] = st_prologue;
-        st[3] = st_loop_end - st_c0 - st_prologue;  // the tile loop
-        st[4] = st_slow;
-        st[5] = st_slow_n;
-        st[6] = __builtin_amdgcn_s_memtime() - st_loop_end;  // the final reduction
-        st[7] = __builtin_amdgcn_s_memtime() - st_c0;
-    }
-#endif
 }
 
 #undef FTK_FETCH_WORDS
 #undef FTK_EXPAND_WORD
 #undef FTK_MFMA_TILE
-#undef FTK_SLOW_BEGIN
-#undef FTK_SLOW_END
 
 template <int NW, bool kNearby>
 __global__ void __launch_bounds__(64) hamming_match_mfma_kernel(const MatchParams p) {
@@ -888,7 +665,7 @@ __global__ void __launch_bounds__(64) hamming_match_mfma_kernel(const MatchParam
     const int j_end = min(j_begin + p.cur_per_block, p.n_cur);
     bool out_of_reach = false;
     if (kNearby && p.boxes != nullptr) {
-        // wave-uniform early exit on the bounding boxes (hamming_match_tiled_kernel); row boxes cover 256 * kMatchRefs rows
+        // wave-uniform early exit on the bounding boxes (hamming_match_scalar_kernel); row boxes cover 256 * kMatchRefs rows
         const int n_row_boxes = (p.n_ref + kBlock * kMatchRefs - 1) / (kBlock * kMatchRefs);
         const float4 pb = p.boxes[((int)blockIdx.x * kMfmaRows) / (kBlock * kMatchRefs)], cb = p.boxes[n_row_boxes + blockIdx.y];
         const float reach_u = p.max_col + 1.0f, reach_v = p.max_row + 1.0f;
@@ -907,7 +684,7 @@ __global__ void __launch_bounds__(64) hamming_match_mfma_kernel(const MatchParam
 // then lowest j: the reference's strict '<' scan (descriptor_matcher.h:68-75) — the wave reduces the 64 keys and lane 0 writes
 // index_pairs[row] if a match exists (untouched otherwise, :60-62).  NearbyMatch applies the window per pair (:108-111).
 // ---------------------------------------------------------------------------------------------------------------------------
-// Where the one-launch form wins (scripts/match_small_ab.py, event-bracketed calls, launches / one launch): 300 x 300 x 256 bits
+// Where the one-launch form wins (event-bracketed calls, launches / one launch): 300 x 300 x 256 bits
 // 10.4 / 6.3 us, 1000 x 1000 10.2 / 7.0, 2000 x 2000 11.7 / 9.7, 3000 x 300 11.0 / 6.9, 300 x 3000 10.0 / 8.9 — and where it does not:
 // 2000 x 2000 x 512 15.9 / 20.4, 300 x 3000 x 512 10.6 / 15.2, 64 x 60 000 10.3 / 73 (a wave walks its row's candidates alone).
 constexpr long long kSmallMatchWork = 32ll << 20;  // n_ref * n_cur * n_words up to which the one-launch form is used ...
@@ -1027,13 +804,7 @@ hipError_t launch_nw(const MatchParams &p, hipStream_t stream) {
         if (p.boxes) {
             hipLaunchKernelGGL(hamming_box_kernel, dim3((unsigned)(row_blocks + splits)), dim3(kBlock), 0, stream, p, row_blocks);
         }
-        if (p.lds_tiles) {
-            hipLaunchKernelGGL((hamming_match_tiled_kernel<NW, true>), dim3(row_blocks, splits), dim3(kBlock), 0, stream, p);
-        } else {
-            hipLaunchKernelGGL((hamming_match_scalar_kernel<NW, true>), dim3(row_blocks, splits), dim3(kBlock), 0, stream, p);
-        }
-    } else if (p.lds_tiles) {
-        hipLaunchKernelGGL((hamming_match_tiled_kernel<NW, false>), dim3(row_blocks, splits), dim3(kBlock), 0, stream, p);
+        hipLaunchKernelGGL((hamming_match_scalar_kernel<NW, true>), dim3(row_blocks, splits), dim3(kBlock), 0, stream, p);
     } else {
         hipLaunchKernelGGL((hamming_match_scalar_kernel<NW, false>), dim3(row_blocks, splits), dim3(kBlock), 0, stream, p);
     }
@@ -1043,7 +814,7 @@ hipError_t launch_nw(const MatchParams &p, hipStream_t stream) {
 }  // namespace
 
 bool match_small_form(int n_ref, int n_cur, int n_words, int n_bits, bool small_off) {
-    const bool allowed = !small_off;  // FTK_MATCH_SMALL=0 (experiment switch of the context; scripts/match_small_ab.py flips it)
+    const bool allowed = !small_off;  // FTK_MATCH_SMALL=0 (experiment switch of the context)
     const bool width = n_words == 1 || n_words == 2 || n_words == 4 || n_words == 8 || n_words == 16;
     return allowed && width && n_bits > 0 && n_cur < kSmallNoIndex && (long long)n_cur * n_words <= kSmallMatchRowWork &&
            (long long)n_ref * n_cur * n_words <= kSmallMatchWork;

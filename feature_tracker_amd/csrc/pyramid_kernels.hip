@@ -8,11 +8,8 @@
 //    exposed because the reference makes it a public method; one wave per call.
 #include "ftk_device.h"
 
-#include <string.h>
-
 #include <limits.h>
 #include <math.h>
-#include <stdlib.h>
 
 namespace ftk {
 namespace {
@@ -242,50 +239,33 @@ hipError_t pyramid_downsample_launch(const uint8_t *src, int32_t src_rows, int32
 
 // Levels 1 .. n_levels - 1 of a pyramid whose level 0 is `level0` (rows x cols): one fused launch for the first six, the
 // per-level kernel for anything deeper.  dst[l] / out_rows / out_cols describe level l (entries >= 1 are used).
-bool pyramid_fused_enabled() {
-    static const bool fused = !(getenv("FTK_PYRAMID_FUSED") && atoi(getenv("FTK_PYRAMID_FUSED")) == 0);  // experiment switch
-    return fused;
-}
-
-// `level0_keep` (optional, fused launch only — pyramid_fused_enabled() and n_levels >= 2): `level0` is a source OUTSIDE the pyramid
-// (device-visible pinned host memory) and the launch also writes it to level0_keep, the pyramid's own level 0.
+// `level0_keep` (optional): `level0` is a source OUTSIDE the pyramid (device-visible pinned host memory) and the launch also writes
+// it to level0_keep, the pyramid's own level 0.
 hipError_t pyramid_build_levels_launch(const uint8_t *level0, int32_t rows, int32_t cols, uint8_t *const *dst, int32_t n_levels, hipStream_t stream,
                                        uint8_t *level0_keep) {
     if (n_levels <= 1) {
         return hipSuccess;
     }
-    const bool fused = pyramid_fused_enabled();
-    if (level0_keep != nullptr && !fused) {
-        return hipErrorInvalidValue;
+    PyramidLevels lv;
+    lv.n_levels = n_levels < kFusedMaxLevels ? n_levels : kFusedMaxLevels;
+    for (int l = 0; l < kFusedMaxLevels; ++l) {
+        lv.dst[l] = (l >= 1 && l < lv.n_levels) ? dst[l] : nullptr;
     }
-    int done = 1;  // levels that exist so far
-    if (fused) {
-        PyramidLevels lv;
-        lv.n_levels = n_levels < kFusedMaxLevels ? n_levels : kFusedMaxLevels;
-        for (int l = 0; l < kFusedMaxLevels; ++l) {
-            lv.dst[l] = (l >= 1 && l < lv.n_levels) ? dst[l] : nullptr;
-        }
-        lv.dst[0] = level0_keep;
-        // wide tiles (256-byte row pieces) for a source in host memory, when five levels are enough for them (16 rows = 2^4);
-        // FTK_PYRAMID_TILE=wide|square forces one (experiment switch)
-        static const char *tile_env = getenv("FTK_PYRAMID_TILE");
-        const bool wide_ok = lv.n_levels <= 5;
-        const bool wide = wide_ok && (tile_env ? !strcmp(tile_env, "wide") : level0_keep != nullptr);
-        if (wide) {
-            const dim3 grid((unsigned)((cols + 255) / 256), (unsigned)((rows + 15) / 16));
-            hipLaunchKernelGGL((pyramid_fused_kernel<256, 16>), grid, dim3(kBlock), 0, stream, level0, rows, cols, lv);
-        } else {
-            const dim3 grid((unsigned)((cols + kTile - 1) / kTile), (unsigned)((rows + kTile - 1) / kTile));
-            hipLaunchKernelGGL((pyramid_fused_kernel<kTile, kTile>), grid, dim3(kBlock), 0, stream, level0, rows, cols, lv);
-        }
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) {
-            return e;
-        }
-        done = lv.n_levels;
+    lv.dst[0] = level0_keep;
+    // wide tiles (256-byte row pieces) for a source in host memory, when five levels are enough for them (16 rows = 2^4)
+    if (level0_keep != nullptr && lv.n_levels <= 5) {
+        const dim3 grid((unsigned)((cols + 255) / 256), (unsigned)((rows + 15) / 16));
+        hipLaunchKernelGGL((pyramid_fused_kernel<256, 16>), grid, dim3(kBlock), 0, stream, level0, rows, cols, lv);
+    } else {
+        const dim3 grid((unsigned)((cols + kTile - 1) / kTile), (unsigned)((rows + kTile - 1) / kTile));
+        hipLaunchKernelGGL((pyramid_fused_kernel<kTile, kTile>), grid, dim3(kBlock), 0, stream, level0, rows, cols, lv);
     }
-    for (int l = done; l < n_levels; ++l) {
-        const hipError_t e = pyramid_downsample_launch(l == 1 ? (level0_keep ? level0_keep : level0) : dst[l - 1], rows >> (l - 1), cols >> (l - 1), dst[l], stream);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        return e;
+    }
+    for (int l = lv.n_levels; l < n_levels; ++l) {  // (lv.n_levels >= 2: level 1 always comes from the fused launch)
+        e = pyramid_downsample_launch(dst[l - 1], rows >> (l - 1), cols >> (l - 1), dst[l], stream);
         if (e != hipSuccess) {
             return e;
         }

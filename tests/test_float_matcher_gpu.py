@@ -162,11 +162,12 @@ def test_full_size_properties(ftk):
     assert np.array_equal(shuffle[idx2[idx2 >= 0]], idx[idx >= 0])
 
 
-@pytest.mark.parametrize("env", [{}, {"FTK_COSINE_TWO_PASS": "1"}, {"FTK_COSINE_CHUNKED": "1"}, {"FTK_COSINE_SPLITS": "1"}, {"FTK_COSINE_SPLITS": "5"}])
+@pytest.mark.parametrize("env", [{}, {"FTK_COSINE_CHUNKED": "1"}, {"FTK_COSINE_SPLITS": "1"}, {"FTK_COSINE_SPLITS": "5"}])
 def test_contraction_variants_agree_with_oracle(ftk, oracle, switch, env):
-    """The shortlist has three implementations behind one decision rule (single walk with a running row maximum,
-    maximum-then-collect, chunked for long descriptors) and a split count chosen from the grid size: each of them,
-    at forced split counts, must give the oracle's indices — force and nearby, ragged sizes."""
+    """The shortlist has two implementations behind one decision rule (the register-stationary single walk with a running
+    row maximum for descriptors up to 256 wide, the chunked maximum-then-collect pair above that; FTK_COSINE_CHUNKED=1 forces
+    the pair on these shapes) and a split count chosen from the grid size: each of them, at forced split counts, must give
+    the oracle's indices — force and nearby, ragged sizes."""
     for k, v in env.items():
         switch(k, v)
     rs = np.random.RandomState(21)

@@ -169,10 +169,10 @@ def test_nearby_match_in_spatial_order(ftk, oracle, n, n_bits, window):
         assert np.array_equal(g, c), (col, row, np.flatnonzero(g != c)[:10])
 
 
-@pytest.mark.parametrize("kernel", ["mfma", "scalar", "lds"])
+@pytest.mark.parametrize("kernel", ["mfma", "scalar"])
 def test_every_scan_kernel_gives_the_oracle_indices(ftk, oracle, kernel, switch):
-    """The three Hamming scans behind ftk_hamming_match (matrix cores for 256 / 512 bits, popcount with the candidates on the
-    scalar path, popcount with LDS tiles; FTK_MATCH_KERNEL picks one, read per call) on the same inputs: thresholds below,
+    """The two Hamming scans behind ftk_hamming_match (matrix cores for 256 / 512 bits, popcount with the candidates on the
+    scalar path; FTK_MATCH_KERNEL picks one, read per call) on the same inputs: thresholds below,
     at and far above the distances that occur (the early exits key on the threshold), duplicates (lowest j wins), a
     candidate count that is not a multiple of any tile, reference counts around the 64-row and 512-row blocks, NearbyMatch
     windows with NaN coordinates, and stale indices that must survive."""
