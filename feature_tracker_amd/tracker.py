@@ -65,7 +65,9 @@ class Context:
 
     def set_reduction(self, mode: str = "exact"):
         """ftk_set_reduction_mode: "exact" (default, the contract: sums in the reference's order, bit-identical results) or "tree"
-        (throughput mode: same products, butterfly sums; reported next to the exact mode, never asserted)."""
+        (throughput mode: same products, butterfly sums; not bit-identical to the CPU path in general.  Asserted by
+        tests/test_reduction_tree_gpu.py: bit-identical on integer-exact scenes, one step within the exact chain's rounding error
+        of exactly summed products elsewhere, deterministic, and exact for affine inverse / direct and the large-patch form)."""
         N.check(N.lib().ftk_set_reduction_mode(self._h, {"exact": 0, "tree": 1}[mode]), self._h)
 
     def close(self):

@@ -112,14 +112,17 @@ void ftk_default_klt_options(ftk_klt_options *opt);
  * How the trackers sum their normal equations.
  *   FTK_REDUCTION_EXACT (default, the contract): every sum in the reference's row-major pixel order, one dependent add per
  *     term (basic_klt.cpp:139-144, affine_klt.cpp:229-256, lssd_klt.cpp:214-215) — results bit-identical to the CPU path.
- *   FTK_REDUCTION_TREE (throughput mode; measured and reported, never asserted, never the default): the SAME per-pixel products,
+ *   FTK_REDUCTION_TREE (throughput mode; measured and reported, never the default): the SAME per-pixel products,
  *     summed as per-lane partials combined by a cross-lane butterfly.  The sums then differ from the reference's in the last
  *     bits, and because the convergence test |v|^2 < kMaxConvergeStep turns such differences into an extra or a missing
  *     iteration, a small fraction of the features moves by more than the 1e-3 px the contract allows (bench.py reports max /
  *     p99 / fraction > 1e-3 px and status mismatches next to the speed).  It exists to show what bit-exactness costs.
  *     Implemented for every tracker variant except the two non-fast affine ones (24 sums of a 13 x 13 patch already run as 24
  *     parallel chains; they ignore the setting and stay exact) and for the direct method (ftk_direct_track*), whose 50 700-term
- *     chains per iteration are where the summation order costs most.
+ *     chains per iteration are where the summation order costs most.  Asserted (tests/test_reduction_tree_gpu.py): bit-identical
+ *     to the exact mode where every partial sum is an exact float (integer-valued terms, sums below 2^24); elsewhere one step is
+ *     at least roughly as close to exactly summed products as the exact chain is (max error <= 4 x the chain's + 2 ulp, median
+ *     <= the chain's + 1 ulp); repeated calls are bit-identical; affine inverse / direct and the large-patch form stay exact.
  */
 enum { FTK_REDUCTION_EXACT = 0, FTK_REDUCTION_TREE = 1 };
 int ftk_set_reduction_mode(ftk_context *ctx, int mode);

@@ -13,14 +13,14 @@ enum {
     H00, H01, H02, H03, H04, H05, H11, H12, H13, H14, H15, H22, H23, H24, H25, H33, H34, H35, H44, H45, H55, H_COUNT
 };
 
-static void affine_expand(const float *u, float *m /* 6x6 row-major */) {
+static void affine_expand(const orc_sum *u, float *m /* 6x6 row-major */) {
     static const int idx[6][6] = {
         {H00, H01, H02, H03, H04, H05}, {H01, H11, H12, H13, H14, H15}, {H02, H12, H22, H23, H24, H25},
         {H03, H13, H23, H33, H34, H35}, {H04, H14, H24, H34, H44, H45}, {H05, H15, H25, H35, H45, H55},
     };
     for (int i = 0; i < 6; ++i) {
         for (int j = 0; j < 6; ++j) {
-            m[i * 6 + j] = u[idx[i][j]];
+            m[i * 6 + j] = (float)u[idx[i][j]];
         }
     }
 }
@@ -28,11 +28,14 @@ static void affine_expand(const float *u, float *m /* 6x6 row-major */) {
 /* ConstructIncrementalFunction, affine_klt.cpp:131-273.  The Jacobian uses the ABSOLUTE
  * warped coordinates x = col_j, y = row_j (:219-220).  H(3,4) accumulates yy*dxdy (:245, sic). */
 static int32_t affine_build_normal_equations(const orc_klt_options *opt, const orc_image *ref, const orc_image *cur, float ref_u, float ref_v,
-                                             float cur_u, float cur_v, const float *affine, float *m, float *b) {
+                                             float cur_u, float cur_v, const float *affine, float *m, float *bf) {
     const int direct = (opt->method == ORC_DIRECT);
     const orc_image *grad_img = direct ? cur : ref;
-    float u[H_COUNT];
-    memset(u, 0, sizeof(u));
+    orc_sum u[H_COUNT];
+    orc_sum b[6];
+    for (int i = 0; i < H_COUNT; ++i) {
+        u[i] = 0.0f;
+    }
     for (int i = 0; i < 6; ++i) {
         b[i] = 0.0f;
     }
@@ -58,6 +61,10 @@ static int32_t affine_build_normal_equations(const orc_klt_options *opt, const o
                 const float x = col_j, y = row_j;
                 const float xx = x * x, yy = y * y, xy = x * y;
                 const float dxdx = dx * dx, dydy = dy * dy, dxdy = dx * dy;
+                ++n_valid;
+                if (!ORC_SUM_KEEP((drow + opt->half_rows) * (2 * opt->half_cols + 1) + dcol + opt->half_cols)) {
+                    continue;
+                }
                 u[H00] += xx * dxdx;
                 u[H01] += xx * dxdy;
                 u[H02] += xy * dxdx;
@@ -85,11 +92,13 @@ static int32_t affine_build_normal_equations(const orc_klt_options *opt, const o
                 b[3] -= dt * y * dy;
                 b[4] -= dt * dx;
                 b[5] -= dt * dy;
-                ++n_valid;
             }
         }
     }
     affine_expand(u, m);
+    for (int i = 0; i < 6; ++i) {
+        bf[i] = (float)b[i];
+    }
     return n_valid;
 }
 
@@ -139,9 +148,10 @@ void orc_affine_track_one(const orc_klt_options *opt, const orc_image *ref, cons
 /* ComputeBias, affine_klt_fast.cpp:140-188: one checked bilinear fetch of cur per patch pixel
  * at the affine-warped position; weights by the current absolute coordinates (:174-179). */
 static int32_t affine_fast_bias(const orc_klt_options *opt, const orc_image *cur, float cur_u, float cur_v, const float *ex_patch,
-                                const uint8_t *ex_valid, int32_t ex_cols, const float *dxs, const float *dys, const float *affine, float *b) {
+                                const uint8_t *ex_valid, int32_t ex_cols, const float *dxs, const float *dys, const float *affine, float *bf) {
     const int32_t patch_cols = ex_cols - 2;
     int32_t n_valid = 0;
+    orc_sum b[6];
     for (int i = 0; i < 6; ++i) {
         b[i] = 0.0f;
     }
@@ -164,14 +174,20 @@ static int32_t affine_fast_bias(const orc_klt_options *opt, const orc_image *cur
             const float dt = i_cur - ex_patch[ex_index];
             const int32_t index = (row_in_ex - 1) * patch_cols + (col_in_ex - 1);
             const float dx = dxs[index], dy = dys[index];
+            ++n_valid;
+            if (!ORC_SUM_KEEP(index)) {
+                continue;
+            }
             b[0] -= dt * col_c * dx;
             b[1] -= dt * col_c * dy;
             b[2] -= dt * row_c * dx;
             b[3] -= dt * row_c * dy;
             b[4] -= dt * dx;
             b[5] -= dt * dy;
-            ++n_valid;
         }
+    }
+    for (int i = 0; i < 6; ++i) {
+        bf[i] = (float)b[i];
     }
     return n_valid;
 }
@@ -185,11 +201,13 @@ void orc_affine_track_one_fast(const orc_klt_options *opt, const orc_image *ref,
     uint8_t *ex_valid = (uint8_t *)malloc((size_t)ex_rows * ex_cols);
     float *dxs = (float *)malloc(sizeof(float) * patch_rows * patch_cols);
     float *dys = (float *)malloc(sizeof(float) * patch_rows * patch_cols);
-    float u[H_COUNT];
+    orc_sum u[H_COUNT];
     float m[36];
     float last_squared_step = INFINITY;
     uint32_t large_step_cnt = 0;
-    memset(u, 0, sizeof(u));
+    for (int i = 0; i < H_COUNT; ++i) {
+        u[i] = 0.0f;
+    }
 
     if (orc_extract_extend_patch(ref, ref_u, ref_v, ex_rows, ex_cols, ex_patch, ex_valid) == 0) {
         *status = ORC_OUTSIDE;
@@ -211,6 +229,9 @@ void orc_affine_track_one_fast(const orc_klt_options *opt, const orc_image *ref,
                 const float y = (float)(row - opt->half_rows) + cur_uv[1];
                 const float xx = x * x, yy = y * y, xy = x * y;
                 const float dxdx = dx * dx, dydy = dy * dy, dxdy = dx * dy;
+                if (!ORC_SUM_KEEP(index)) {
+                    continue;
+                }
                 u[H00] += xx * dxdx;
                 u[H01] += xx * dxdy;
                 u[H02] += xy * dxdx;

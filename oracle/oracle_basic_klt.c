@@ -9,7 +9,7 @@
 
 /* ConstructIncrementalFunction, basic_klt.cpp:118-181.  h = [h00, h01, h11], b = [b0, b1]. */
 static int32_t basic_build_normal_equations(const orc_klt_options *opt, const orc_image *ref, const orc_image *cur, float ref_u, float ref_v,
-                                            float cur_u, float cur_v, float *h, float *b) {
+                                            float cur_u, float cur_v, orc_sum *h, orc_sum *b) {
     const int direct = (opt->method != ORC_INVERSE);
     /* gradient image: ref for inverse (:132-134), cur for direct (:159-161) */
     const orc_image *grad_img = direct ? cur : ref;
@@ -31,11 +31,13 @@ static int32_t basic_build_normal_equations(const orc_klt_options *opt, const or
                 const float fx = right - left;
                 const float fy = bottom - top;
                 const float ft = i_cur - i_ref;
-                h[0] += fx * fx;
-                h[2] += fy * fy;
-                h[1] += fx * fy;
-                b[0] -= fx * ft;
-                b[1] -= fy * ft;
+                if (ORC_SUM_KEEP((drow + opt->half_rows) * (2 * opt->half_cols + 1) + dcol + opt->half_cols)) {
+                    h[0] += fx * fx;
+                    h[2] += fy * fy;
+                    h[1] += fx * fy;
+                    b[0] -= fx * ft;
+                    b[1] -= fy * ft;
+                }
                 ++n_valid;
             }
         }
@@ -48,15 +50,16 @@ static int32_t basic_build_normal_equations(const orc_klt_options *opt, const or
 void orc_basic_track_one(const orc_klt_options *opt, const orc_image *ref, const orc_image *cur, float ref_u, float ref_v, float *cur_uv,
                          uint8_t *status, uint32_t *iters) {
     for (uint32_t iter = 0; iter < opt->max_iteration; ++iter) {
-        float h[3] = {0.0f, 0.0f, 0.0f};
-        float b[2] = {0.0f, 0.0f};
+        orc_sum h[3] = {0.0f, 0.0f, 0.0f};
+        orc_sum b[2] = {0.0f, 0.0f};
         ++*iters;
         if (basic_build_normal_equations(opt, ref, cur, ref_u, ref_v, cur_uv[0], cur_uv[1], h, b) == 0) {
             break;
         }
-        const float hm[4] = {h[0], h[1], h[1], h[2]};
+        const float hm[4] = {(float)h[0], (float)h[1], (float)h[1], (float)h[2]};
+        const float bf[2] = {(float)b[0], (float)b[1]};
         float v[2];
-        orc_ldlt_solve(2, hm, b, v);
+        orc_ldlt_solve(2, hm, bf, v);
         if (isnan(v[0]) || isnan(v[1])) {
             *status = ORC_NUMERIC_ERROR;
             break;
@@ -78,11 +81,10 @@ void orc_basic_track_one(const orc_klt_options *opt, const orc_image *ref, const
  * lattice floor(cur) - patch/2; pixels invalid in cur (:132) or in the extended ref patch
  * (:138,171) are skipped. */
 static uint32_t basic_fast_bias(const orc_image *cur, float cur_u, float cur_v, const float *ex_patch, const uint8_t *ex_valid, int32_t ex_rows,
-                                int32_t ex_cols, const float *dx, const float *dy, float *b) {
+                                int32_t ex_cols, const float *dx, const float *dy, float *bf) {
     const int32_t patch_rows = ex_rows - 2;
     const int32_t patch_cols = ex_cols - 2;
-    b[0] = 0.0f;
-    b[1] = 0.0f;
+    orc_sum b[2] = {0.0f, 0.0f};
 
     const float int_row = floorf(cur_v);
     const float int_col = floorf(cur_u);
@@ -114,11 +116,15 @@ static uint32_t basic_fast_bias(const orc_image *cur, float cur_u, float cur_v, 
                                 w_bl * (float)orc_px(cur, row + 1, col) + w_br * (float)orc_px(cur, row + 1, col + 1);
             const float dt = i_cur - ex_patch[ex_index];
             const int32_t index = row_in_patch * patch_cols + col_in_patch;
-            b[0] -= dx[index] * dt;
-            b[1] -= dy[index] * dt;
+            if (ORC_SUM_KEEP(index)) {
+                b[0] -= dx[index] * dt;
+                b[1] -= dy[index] * dt;
+            }
             ++n_valid;
         }
     }
+    bf[0] = (float)b[0];
+    bf[1] = (float)b[1];
     return n_valid;
 }
 
@@ -131,7 +137,7 @@ void orc_basic_track_one_fast(const orc_klt_options *opt, const orc_image *ref, 
     uint8_t *ex_valid = (uint8_t *)malloc((size_t)ex_rows * ex_cols);
     float *dx = (float *)malloc(sizeof(float) * patch_rows * patch_cols);
     float *dy = (float *)malloc(sizeof(float) * patch_rows * patch_cols);
-    float h[3] = {0.0f, 0.0f, 0.0f};
+    orc_sum h[3] = {0.0f, 0.0f, 0.0f};
     float hm[4];
     float last_squared_step = INFINITY;
     uint32_t large_step_cnt = 0;
@@ -151,19 +157,21 @@ void orc_basic_track_one_fast(const orc_klt_options *opt, const orc_image *ref, 
                 const float gy = ex_patch[ex_index + ex_cols] - ex_patch[ex_index - ex_cols];
                 dx[index] = gx;
                 dy[index] = gy;
-                h[0] += gx * gx;
-                h[1] += gx * gy;
-                h[2] += gy * gy;
+                if (ORC_SUM_KEEP(index)) {
+                    h[0] += gx * gx;
+                    h[1] += gx * gy;
+                    h[2] += gy * gy;
+                }
             } else {
                 dx[index] = 0.0f;
                 dy[index] = 0.0f;
             }
         }
     }
-    hm[0] = h[0];
-    hm[1] = h[1];
-    hm[2] = h[1];
-    hm[3] = h[2];
+    hm[0] = (float)h[0];
+    hm[1] = (float)h[1];
+    hm[2] = (float)h[1];
+    hm[3] = (float)h[2];
 
     *status = ORC_LARGE_RESIDUAL; /* :29 */
     for (uint32_t iter = 0; iter < opt->max_iteration; ++iter) {

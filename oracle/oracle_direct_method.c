@@ -104,10 +104,14 @@ static void track_all_features_direct(const orc_direct_options *opt, const orc_i
     const float fx = K[0], fy = K[1], cx = K[2], cy = K[3];
     const uint32_t max_feature_id = ((uint32_t)n < opt->max_track_points) ? (uint32_t)n : opt->max_track_points;
     for (uint32_t iter = 0; iter < opt->max_iteration; ++iter) {
-        float H[6][6];
-        float b[6];
-        memset(H, 0, sizeof(H));
-        memset(b, 0, sizeof(b));
+        orc_sum H[6][6];
+        orc_sum b[6];
+        for (int r = 0; r < 6; ++r) {
+            for (int c = 0; c < 6; ++c) {
+                H[r][c] = 0.0f;
+            }
+            b[r] = 0.0f;
+        }
         if (iterations) {
             ++*iterations;
         }
@@ -155,6 +159,9 @@ static void track_all_features_direct(const orc_direct_options *opt, const orc_i
                     if (orc_get_pixel_value(cur_image, row_j, col_j - 1.0f, &t[0]) && orc_get_pixel_value(cur_image, row_j, col_j + 1.0f, &t[1]) &&
                         orc_get_pixel_value(cur_image, row_j - 1.0f, col_j, &t[2]) && orc_get_pixel_value(cur_image, row_j + 1.0f, col_j, &t[3]) &&
                         orc_get_pixel_value(ref_image, row_i, col_i, &t[4]) && orc_get_pixel_value(cur_image, row_j, col_j, &t[5])) {
+                        if (!ORC_SUM_KEEP((drow + opt->half_rows) * (2 * opt->half_cols + 1) + dcol + opt->half_cols)) {
+                            continue;
+                        }
                         const float gx = (t[1] - t[0]) * 0.5f, gy = (t[3] - t[2]) * 0.5f;
                         const float residual = t[5] - t[4];
                         float jac[6];
@@ -171,8 +178,14 @@ static void track_all_features_direct(const orc_direct_options *opt, const orc_i
                 }
             }
         }
-        float dx[6];
-        orc_ldlt_solve(6, &H[0][0], b, dx);
+        float Hf[36], bf[6], dx[6];
+        for (int r = 0; r < 6; ++r) {
+            for (int c = 0; c < 6; ++c) {
+                Hf[r * 6 + c] = (float)H[r][c];
+            }
+            bf[r] = (float)b[r];
+        }
+        orc_ldlt_solve(6, Hf, bf, dx);
         int has_nan = 0;
         for (int k = 0; k < 6; ++k) {
             has_nan |= isnan(dx[k]);

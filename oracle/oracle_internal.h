@@ -9,6 +9,25 @@
 
 #include "ftk_oracle.h"
 
+/* Accumulator of the sums the trackers' throughput mode (ftk_set_reduction_mode TREE) re-orders: the normal-equation H / b
+ * of every model and method, the LSSD patch means and the direct method's 27 sums.  The default build keeps them in float
+ * (the reference's order and rounding: bit-identical to it); liboracle_sum64.so builds with -DORC_SUM_T=double, which keeps
+ * the same f32 products and rounds each sum to float once, where the f32 code consumes it — what an exact reduction of
+ * those products gives, whatever its order. */
+#ifndef ORC_SUM_T
+#define ORC_SUM_T float
+#endif
+typedef ORC_SUM_T orc_sum;
+
+/* Negative control of the wide build only (orc_sum_drop_stride): ORC_SUM_KEEP(i) is false for every k-th pixel i of a
+ * patch (i % k == k - 1), whose terms then never reach the sums — what a reduction that loses one lane's partial does. */
+#ifdef ORC_SUM_DROP
+extern int32_t orc_sum_drop_k;
+#define ORC_SUM_KEEP(i) (orc_sum_drop_k <= 0 || ((i) % orc_sum_drop_k) != orc_sum_drop_k - 1)
+#else
+#define ORC_SUM_KEEP(i) 1
+#endif
+
 /* float -> int32 with the x86-64 cvttss2si result the reference gets from static_cast<int32_t>
  * (out of range / NaN -> INT32_MIN); in-range values truncate toward zero. */
 static inline int32_t orc_f2i(float x) {

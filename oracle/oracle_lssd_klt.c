@@ -37,7 +37,7 @@ static void se2_update(float *r, float *t, const float *v) {
 }
 
 /* hessian += j^T j ; bias -= j^T residual  (lssd_klt.cpp:214-215, lssd_klt_fast.cpp:220-221) */
-static inline void accumulate3(float *h, float *b, const float *j, float residual) {
+static inline void accumulate3(orc_sum *h, orc_sum *b, const float *j, float residual) {
     for (int i = 0; i < 3; ++i) {
         for (int k = 0; k < 3; ++k) {
             h[i * 3 + k] += j[i] * j[k];
@@ -50,14 +50,14 @@ static inline void accumulate3(float *h, float *b, const float *j, float residua
  * (:140-184), pass 2 = mean-normalised Jacobian and residual (:186-247).  Always
  * mean-normalises (consider_patch_luminance_ is not consulted here). */
 static int32_t lssd_build_normal_equations(const orc_klt_options *opt, const orc_image *ref, const orc_image *cur, float ref_u, float ref_v,
-                                           const float *r, const float *t, float *h, float *b) {
+                                           const float *r, const float *t, orc_sum *h, orc_sum *b) {
     const int direct = (opt->method != ORC_INVERSE);
     const orc_image *grad_img = direct ? cur : ref;
     const int32_t patch_cols = 2 * opt->half_cols + 1;
     const int32_t patch_size = (2 * opt->half_rows + 1) * patch_cols;
     uint8_t *pixel_valid = (uint8_t *)malloc((size_t)patch_size);
     int32_t n_valid = 0;
-    float ref_average = 0.0f, cur_average = 0.0f;
+    orc_sum ref_sum = 0.0f, cur_sum = 0.0f;
 
     for (int32_t drow = -opt->half_rows; drow <= opt->half_rows; ++drow) {
         for (int32_t dcol = -opt->half_cols; dcol <= opt->half_cols; ++dcol) {
@@ -72,8 +72,8 @@ static int32_t lssd_build_normal_equations(const orc_klt_options *opt, const orc
             if (orc_sample(grad_img, grow, gcol - 1.0f, &left) && orc_sample(grad_img, grow, gcol + 1.0f, &right) &&
                 orc_sample(grad_img, grow - 1.0f, gcol, &top) && orc_sample(grad_img, grow + 1.0f, gcol, &bottom) &&
                 orc_sample(ref, row_i, col_i, &i_ref) && orc_sample(cur, row_j, col_j, &i_cur)) {
-                ref_average += i_ref;
-                cur_average += i_cur;
+                ref_sum += i_ref;
+                cur_sum += i_cur;
                 ++n_valid;
                 pixel_valid[index] = 1;
             } else {
@@ -81,8 +81,8 @@ static int32_t lssd_build_normal_equations(const orc_klt_options *opt, const orc
             }
         }
     }
-    ref_average /= (float)n_valid;
-    cur_average /= (float)n_valid;
+    const float ref_average = (float)ref_sum / (float)n_valid;
+    const float cur_average = (float)cur_sum / (float)n_valid;
     const float grad_average = direct ? cur_average : ref_average; /* :209 vs :237 */
 
     for (int32_t drow = -opt->half_rows; drow <= opt->half_rows; ++drow) {
@@ -114,7 +114,9 @@ static int32_t lssd_build_normal_equations(const orc_klt_options *opt, const orc
             j[1] = jp0 * 1.0f + jp1 * 0.0f;
             j[2] = jp0 * 0.0f + jp1 * 1.0f;
             const float residual = i_cur / cur_average - i_ref / ref_average;
-            accumulate3(h, b, j, residual);
+            if (ORC_SUM_KEEP(index)) {
+                accumulate3(h, b, j, residual);
+            }
         }
     }
     free(pixel_valid);
@@ -125,12 +127,19 @@ static int32_t lssd_build_normal_equations(const orc_klt_options *opt, const orc
 void orc_lssd_track_one(const orc_klt_options *opt, const orc_image *ref, const orc_image *cur, float ref_u, float ref_v, float *r, float *t,
                         uint8_t *status, uint32_t *iters) {
     for (uint32_t iter = 0; iter < opt->max_iteration; ++iter) {
-        float h[9] = {0}, b[3] = {0}, v[3];
+        orc_sum h[9] = {0}, b[3] = {0};
+        float hf[9], bf[3], v[3];
         ++*iters;
         if (lssd_build_normal_equations(opt, ref, cur, ref_u, ref_v, r, t, h, b) == 0) {
             break;
         }
-        orc_ldlt_solve(3, h, b, v);
+        for (int i = 0; i < 9; ++i) {
+            hf[i] = (float)h[i];
+        }
+        for (int i = 0; i < 3; ++i) {
+            bf[i] = (float)b[i];
+        }
+        orc_ldlt_solve(3, hf, bf, v);
         if (isnan(v[0]) || isnan(v[1]) || isnan(v[2])) {
             *status = ORC_NUMERIC_ERROR;
             break;
@@ -223,13 +232,13 @@ void orc_lssd_track_one_fast(const orc_klt_options *opt, const orc_image *ref, c
     /* Luminance scaling of the reference patch (:27-46): numerator = interior of the extended
      * patch, denominator = valid count of the WHOLE extended patch (sic). */
     if (consider_luminance) {
-        float ref_average = 0.0f;
+        orc_sum ref_sum = 0.0f;
         for (int32_t row = 1; row < ex_rows - 1; ++row) {
             for (int32_t col = 1; col < ex_cols - 1; ++col) {
-                ref_average += ex_patch[row * ex_cols + col];
+                ref_sum += ex_patch[row * ex_cols + col];
             }
         }
-        ref_average /= (float)ref_valid_num;
+        const float ref_average = (float)ref_sum / (float)ref_valid_num;
         for (int32_t i = 0; i < patch_size; ++i) {
             dxs[i] /= ref_average;
         }
@@ -252,19 +261,20 @@ void orc_lssd_track_one_fast(const orc_klt_options *opt, const orc_image *ref, c
         /* Luminance scaling of the current patch (:65-78): numerator = rows/cols 1..P-2 only,
          * denominator = full valid count (sic). */
         if (consider_luminance) {
-            float cur_average = 0.0f;
+            orc_sum cur_sum = 0.0f;
             for (int32_t row = 1; row < patch_rows - 1; ++row) {
                 for (int32_t col = 1; col < patch_cols - 1; ++col) {
-                    cur_average += cur_patch[row * patch_cols + col];
+                    cur_sum += cur_patch[row * patch_cols + col];
                 }
             }
-            cur_average /= (float)cur_valid_num;
+            const float cur_average = (float)cur_sum / (float)cur_valid_num;
             for (int32_t i = 0; i < patch_size; ++i) {
                 cur_patch[i] /= cur_average;
             }
         }
 
-        float h[9] = {0}, b[3] = {0}, v[3];
+        orc_sum h[9] = {0}, b[3] = {0};
+        float hf[9], bf[3], v[3];
         int32_t n_valid = 0;
         for (int32_t drow = -opt->half_rows; drow <= opt->half_rows; ++drow) {
             for (int32_t dcol = -opt->half_cols; dcol <= opt->half_cols; ++dcol) {
@@ -280,7 +290,9 @@ void orc_lssd_track_one_fast(const orc_klt_options *opt, const orc_image *ref, c
                     j[1] = dxs[index];
                     j[2] = dys[index];
                     const float residual = cur_patch[index] - ex_patch[ex_index];
-                    accumulate3(h, b, j, residual);
+                    if (ORC_SUM_KEEP(index)) {
+                        accumulate3(h, b, j, residual);
+                    }
                     ++n_valid;
                 }
             }
@@ -288,8 +300,14 @@ void orc_lssd_track_one_fast(const orc_klt_options *opt, const orc_image *ref, c
         if (n_valid == 0) {
             break;
         }
+        for (int i = 0; i < 9; ++i) {
+            hf[i] = (float)h[i];
+        }
+        for (int i = 0; i < 3; ++i) {
+            bf[i] = (float)b[i];
+        }
 
-        orc_ldlt_solve(3, h, b, v);
+        orc_ldlt_solve(3, hf, bf, v);
         if (isnan(v[0]) || isnan(v[1]) || isnan(v[2])) {
             *status = ORC_NUMERIC_ERROR;
             break;

@@ -11,6 +11,11 @@
 /* exported wrappers of the inlined samplers (oracle_internal.h) */
 float orc_get_pixel_value_nocheck(const orc_image *img, float row, float col) { return orc_bilinear(img, row, col); }
 
+#ifdef ORC_SUM_DROP
+int32_t orc_sum_drop_k = 0;
+void orc_sum_drop_stride(int32_t k) { orc_sum_drop_k = k; }
+#endif
+
 int orc_get_pixel_value(const orc_image *img, float row, float col, float *value) { return orc_sample(img, row, col, value); }
 
 /* ImagePyramid::CreateImagePyramid (call sites test/test_optical_flow.cpp:70-71):

@@ -1,11 +1,16 @@
 """ctypes binding of oracle/liboracle.so — the CPU restatement of the reference path.
 
+wide() returns the same binding over oracle/liboracle_sum64.so, the build whose re-ordered sums (normal equations, LSSD
+patch means, the direct method's 27 sums) accumulate in double and round to float where the f32 path consumes them: what a
+perfect reduction of the oracle's own f32 products gives.  The reference for the throughput (tree) reduction mode.
+
 TEST INFRASTRUCTURE ONLY: imported by tests/, __graft_entry__.smoke() and bench.py's
 cpu_baseline leg.  Nothing under feature_tracker_amd/ may import this module.
 """
 from __future__ import annotations
 
 import ctypes as C
+import importlib.util
 import os
 import subprocess
 
@@ -13,6 +18,7 @@ import numpy as np
 
 _ORACLE_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle")
 _LIB_PATH = os.path.join(_ORACLE_DIR, "liboracle.so")
+_WIDE_PATH = os.path.join(_ORACLE_DIR, "liboracle_sum64.so")
 
 MODELS = {"basic": 0, "affine": 1, "lssd": 2}
 METHODS = {"inverse": 0, "direct": 1, "fast": 2}
@@ -39,11 +45,13 @@ class _Options(C.Structure):
 
 
 def build(force: bool = False) -> str:
-    """Compile the oracle with the committed Makefile (gcc -O3 -ffp-contract=off)."""
-    srcs = [os.path.join(_ORACLE_DIR, f) for f in os.listdir(_ORACLE_DIR) if f.endswith((".c", ".h"))]
-    stale = (not os.path.exists(_LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(_LIB_PATH) for s in srcs)
-    if force or stale:
-        subprocess.run(["make", "-C", _ORACLE_DIR, "-B", "liboracle.so"], check=True, capture_output=True)
+    """Compile both oracle libraries (liboracle.so and the wide-sum liboracle_sum64.so) with the committed Makefile
+    (gcc -O3 -ffp-contract=off); returns the path of the one this binding loads."""
+    srcs = [os.path.join(_ORACLE_DIR, f) for f in os.listdir(_ORACLE_DIR) if f.endswith((".c", ".h"))] + [os.path.join(_ORACLE_DIR, "Makefile")]
+    for path in (os.path.join(_ORACLE_DIR, "liboracle.so"), _WIDE_PATH):
+        stale = (not os.path.exists(path)) or any(os.path.getmtime(s) > os.path.getmtime(path) for s in srcs)
+        if force or stale:
+            subprocess.run(["make", "-C", _ORACLE_DIR, "-B", os.path.basename(path)], check=True, capture_output=True)
     return _LIB_PATH
 
 
@@ -60,6 +68,29 @@ def lib():
         for name in ("orc_eigen_dot", "orc_eigen_norm", "orc_cosine_distance"):
             getattr(_lib, name).restype = C.c_float
     return _lib
+
+
+_wide = None
+
+
+def wide():
+    """This binding over liboracle_sum64.so: the same functions and signatures, plus drop_stride()."""
+    global _wide
+    if _wide is None:
+        spec = importlib.util.spec_from_file_location(__name__ + "_sum64", os.path.abspath(__file__))
+        mod = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(mod)
+        mod._LIB_PATH = _WIDE_PATH
+        mod._wide = mod
+        _wide = mod
+    return _wide
+
+
+def drop_stride(k):
+    """Negative control of the wide build only: omit the terms of every k-th patch pixel from the sums (0: none)."""
+    if _LIB_PATH != _WIDE_PATH:
+        raise RuntimeError("drop_stride exists in the wide-sum build only (oracle_lib.wide())")
+    lib().orc_sum_drop_stride(C.c_int32(int(k)))
 
 
 def _images(levels):
