@@ -1,4 +1,4 @@
-// ftk_api.cpp — the C ABI of libftk_hip.so (declared in include/ftk.h).
+// ftk_api.cpp — the C ABI of libftk_hip.so (declared in include/ftk.h), except the trackers' entry points (ftk_klt.cpp).
 //
 // Host-side plumbing only: argument validation, device buffers, stream ordering, launches.
 // All numerics live in the kernels.  There is deliberately no CPU fallback: if HIP is not
@@ -35,11 +35,7 @@ int ftk_fail(ftk_context *ctx, int code, const char *fmt, ...) {
     return code;
 }
 
-namespace {
-
-size_t align_up(size_t x, size_t a) { return ftk_align_up(x, a); }
-
-int ensure_scratch(ftk_context *ctx, size_t bytes) {
+int ftk_ensure_scratch(ftk_context *ctx, size_t bytes) {
     if (bytes <= ctx->scratch_bytes) {
         return FTK_OK;
     }
@@ -48,13 +44,13 @@ int ensure_scratch(ftk_context *ctx, size_t bytes) {
         ctx->scratch = nullptr;
         ctx->scratch_bytes = 0;
     }
-    const size_t want = align_up(bytes + bytes / 2, 4096);
+    const size_t want = ftk_align_up(bytes + bytes / 2, 4096);
     FTK_HIP(ctx, hipMalloc(&ctx->scratch, want));
     ctx->scratch_bytes = want;
     return FTK_OK;
 }
 
-int ensure_pinned(ftk_context *ctx, size_t bytes) {
+int ftk_ensure_pinned(ftk_context *ctx, size_t bytes) {
     if (bytes <= ctx->pinned_bytes) {
         return FTK_OK;
     }
@@ -63,7 +59,7 @@ int ensure_pinned(ftk_context *ctx, size_t bytes) {
         ctx->pinned = nullptr;
         ctx->pinned_bytes = 0;
     }
-    const size_t want = align_up(bytes + bytes / 2, 4096);
+    const size_t want = ftk_align_up(bytes + bytes / 2, 4096);
     // Coarse-grained (non-coherent) host memory: cacheable in the device's L2, coherent at kernel boundaries — which is all the
     // host-buffer entry points need (the host writes the block before the launch and reads it after the synchronisation).  The 2 000
     // workgroups of a zero-copy tracker call then share 64-byte lines instead of each crossing PCIe for its own 17 bytes, and their
@@ -73,6 +69,10 @@ int ensure_pinned(ftk_context *ctx, size_t bytes) {
     ctx->pinned_bytes = want;
     return FTK_OK;
 }
+
+namespace {
+
+size_t align_up(size_t x, size_t a) { return ftk_align_up(x, a); }
 
 // The next image-staging slot, free and at least `bytes` large (ftk_internal.h ImageStage); *out stays null when the device cannot
 // address pinned host memory (the callers then take their copy paths).
@@ -125,12 +125,6 @@ int ensure_match_keys(ftk_context *ctx, size_t count) {
     return FTK_OK;
 }
 
-constexpr uint32_t kSchedMinFeatures = 4096;  // below this (nearly) every feature is resident from the start: nothing to order ...
-constexpr uint32_t kSchedMinLongTail = 1024;  // ... unless the calls have a long tail (see ftk_klt_track_device)
-constexpr size_t kSchedTableWords = (2u << 16) + 2;  // two position tables of 2^16 entries (klt_common.h kSchedTableSize) + the two "no tail" flags behind them
-constexpr size_t kSchedOrderWords = 512;             // behind them: histogram + cursors of the position-keyed launch order (klt_position_order_launch)
-constexpr int32_t kSchedMaxFeatures = 1 << 18;  // the sort block walks the list alone; beyond this it could outlast the launch
-
 int ensure_match_boxes(ftk_context *ctx, size_t count) {
     if (count <= ctx->match_boxes_count) {
         return FTK_OK;
@@ -181,39 +175,6 @@ int ftk_ensure_device_buffer(ftk_context *ctx, void **buf, size_t *have, size_t 
     return FTK_OK;
 }
 
-namespace ftk {
-namespace {
-#include "klt_wave_policy.inc"
-
-// nearest bucket centre on a log scale (the centres ascend)
-int policy_bucket(const int *centres, int count, int x) {
-    int best = 0;
-    for (int i = 1; i < count; ++i) {
-        // x is nearer to centres[i] than to centres[i - 1] when x * x > centres[i - 1] * centres[i]
-        if ((long long)x * x > (long long)centres[i - 1] * centres[i]) {
-            best = i;
-        }
-    }
-    return best;
-}
-}  // namespace
-
-// Waves per feature for one call (klt_wave_policy.inc: measured, generated): method_class 0 inverse, 1 direct, 2 fast-like.
-// Patches beyond the table's largest bucket by more than a factor of two (from about 30 x 30) are outside what was swept: the
-// lanes-per-pixel rule serves them (they run four waves: the pixel loops dominate).
-int klt_policy_waves(int model, int method_class, int consider_luminance, int long_tail, int pixels, int n) {
-    if (pixels > 2 * kPolicyPixels[kPolicyPixelBuckets - 1]) {
-        return std::min(4, std::max(1, (pixels + 63) / 64));
-    }
-    int variant = model * 3 + method_class;
-    if (model == FTK_MODEL_LSSD && method_class == 2 && consider_luminance) {
-        variant = 9;
-    }
-    const int w = kWavePolicy[variant][long_tail ? 1 : 0][policy_bucket(kPolicyPixels, kPolicyPixelBuckets, pixels)][policy_bucket(kPolicyFeatures, kPolicyFeatureBuckets, n)];
-    return w < 1 ? 1 : (w > 4 ? 4 : w);
-}
-}  // namespace ftk
-
 namespace {
 
 // Direct method: a batch is spread over the chip (1 + NP workgroups per problem) while at least two producer workgroups per problem
@@ -224,247 +185,8 @@ namespace {
 // (profiles/r5_direct_spread_consumer.txt).  Beyond that one workgroup per problem IS the fast form, and its time is one problem's.
 constexpr int kDirectSpreadMaxProblems = 112;  // (two producers each no longer fit from 75 problems on a whole device: the fit decides)
 constexpr int kDirectSpreadMinProducers = 2;
-constexpr uint32_t kTailLongFrom = 24;  // iterations of a call's longest feature from which the call counts as tail-bound
-constexpr uint32_t kTailHold = 8;       // launches of the variant for which one such report holds
-constexpr uint32_t kTailFresh = 256;    // launches of the context a report may lag behind (the host enqueues far ahead of the device)
 
 int ensure_device_buffer(ftk_context *ctx, void **buf, size_t *have, size_t bytes) { return ftk_ensure_device_buffer(ctx, buf, have, bytes); }
-
-int fill_klt_params(ftk_context *ctx, int model, const ftk_klt_options *opt, const ftk_pyramid *ref, const ftk_pyramid *cur, int32_t n,
-                    const float *prior, int consider_luminance, int single_level, ftk::KltParams *out) {
-    if (!opt || !ref || !cur) {
-        return fail(ctx, FTK_E_INVALID_ARGUMENT, "klt: null options or pyramid");
-    }
-    if (model < FTK_MODEL_BASIC || model > FTK_MODEL_LSSD) {
-        return fail(ctx, FTK_E_INVALID_ARGUMENT, "klt: unknown model %d", model);
-    }
-    if (opt->method < FTK_METHOD_INVERSE || opt->method > FTK_METHOD_NEON) {
-        return fail(ctx, FTK_E_INVALID_ARGUMENT, "klt: unknown method %d", opt->method);
-    }
-    if (ref->n_levels != cur->n_levels) {
-        // OpticalFlow::TrackFeatures returns false here (optical_flow.cpp:9); callers above the ABI handle it
-        return fail(ctx, FTK_E_INVALID_ARGUMENT, "klt: pyramid level mismatch (%d vs %d)", ref->n_levels, cur->n_levels);
-    }
-    if (ref->n_levels < 1) {
-        return fail(ctx, FTK_E_INVALID_ARGUMENT, "klt: empty pyramid");
-    }
-    if (ref->device != ctx->device || cur->device != ctx->device) {
-        return fail(ctx, FTK_E_INVALID_ARGUMENT, "klt: pyramid lives on another device");
-    }
-    // The reference takes any int32 half size (optical_flow.h:24-25).  Here: up to 1023 (a 2047 x 2047 patch; pixel indices stay
-    // below 2^23 for the 24-bit multiplier); patches beyond a workgroup's LDS run the large-patch form below.
-    if (opt->half_rows < 0 || opt->half_cols < 0 || opt->half_rows > 1023 || opt->half_cols > 1023) {
-        return fail(ctx, FTK_E_UNSUPPORTED, "klt: half patch size (%d, %d) outside [0, 1023]", opt->half_rows, opt->half_cols);
-    }
-    ftk::KltParams &p = *out;
-    memset(&p, 0, sizeof(p));
-    p.tree = (ctx && ctx->reduction == FTK_REDUCTION_TREE) ? 1 : 0;  // before the LDS size is computed: the throughput mode of the pipelined kernel keeps one table per wave
-    p.n_levels = single_level ? 1 : ref->n_levels;
-    p.single_level = single_level ? 1 : 0;
-    for (int i = 0; i < p.n_levels; ++i) {
-        p.ref[i] = ref->levels[i];
-        p.cur[i] = cur->levels[i];
-    }
-    p.n = n;
-    p.order = nullptr;        // list order unless the caller of this function installs a permutation
-    p.sched_iters = nullptr;
-    p.sort_iters = nullptr;
-    p.sort_order_out = nullptr;
-    p.n_track = ((uint32_t)n < opt->max_track_points) ? (uint32_t)n : opt->max_track_points;
-    p.max_iteration = opt->max_iteration;
-    p.max_large_step = opt->max_tolerance_large_step;
-    p.half_rows = opt->half_rows;
-    p.half_cols = opt->half_cols;
-    p.converge = opt->max_converge_step;
-    static const float identity[4] = {1.0f, 0.0f, 0.0f, 1.0f};
-    const float *pr = prior ? prior : identity;
-    for (int i = 0; i < 4; ++i) {
-        p.prior[i] = pr[i];
-    }
-    p.consider_luminance = consider_luminance ? 1 : 0;
-    ftk::klt_fill_geometry(p);  // patch / window / lattice geometry: everything that follows from the half sizes alone (ftk_device.h)
-    // Wavefronts per feature: DATA, not rules (round 5).  csrc/klt_wave_policy.inc is generated by
-    // scripts/make_wave_policy.py from one committed sweep (scripts/wave_policy_sweep.py -> profiles/r5_wave_policy_sweep.jsonl:
-    // every variant x 9 x 9 ... 21 x 21 x 300 ... 16 000 features x one to four waves, on the synthetic scene and on the reference's
-    // example pair) and holds, per (variant, tail class, pixel bucket, feature bucket), the wave count that measured fastest.  The
-    // kernel forms follow from the count (below): one wave = the one-wave kernels (klt_fast_kernels.hip, the chunked LSSD levels, the
-    // pipelined Basic kernel's solo form), more = the multi-wave forms.  tests/test_wave_policy_gpu.py times cells of every variant
-    // and fails when the table's column is more than 10 % off the best.  Whatever is chosen changes the launch shape only, never a
-    // result.
-    //
-    // Tail class: the table was swept on two kinds of scene — every feature done after a handful of iterations, and real frames in
-    // which a few features never converge and run kMaxIteration iterations on every level, so that a call of a few thousand features
-    // lasts as long as its slowest one.  The kernels report each call's longest feature (klt_common.h tail_report); a variant whose
-    // recent calls had one of kTailLongFrom iterations or more is looked up in the long-tail half of the table.
-    p.long_tail = 0;
-    if (ctx && ctx->tail_host && model >= 0 && model < 3) {
-        const int mi = opt->method == FTK_METHOD_INVERSE ? 0 : (opt->method == FTK_METHOD_DIRECT ? 1 : 2);
-        ftk_context::TailState &ts = ctx->tail[model][mi];
-        // this variant's own word: {call number << 8 | iterations} of the longest feature of its most recent launch that has got that
-        // far.  The host may be many launches ahead of the device (back-to-back calls), so a report counts while it is at most
-        // kTailFresh launches of the context old, and one long report holds for kTailHold launches of the variant.
-        const uint32_t seen = reinterpret_cast<volatile uint32_t *>(ctx->tail_host)[model * 3 + mi];
-        const uint32_t age = (ctx->tail_call - (seen >> 8)) & 0xFFFFFFu;
-        if (seen != 0 && age <= kTailFresh && (seen & 0xFFu) >= kTailLongFrom) {
-            ts.long_until = ts.launches + kTailHold;
-            ts.longest = seen & 0xFFu;
-        }
-        p.long_tail = ts.launches < ts.long_until ? 1 : 0;
-    }
-    if (const char *env = FTK_ENV(ctx, klt_tail_class)) {
-        p.long_tail = atoi(env) != 0 ? 1 : 0;  // experiment override (the sweep and the policy test pin the class)
-    }
-    const bool fast_like = opt->method != FTK_METHOD_INVERSE && opt->method != FTK_METHOD_DIRECT;
-    int waves = ftk::klt_policy_waves(model, fast_like ? 2 : (opt->method == FTK_METHOD_DIRECT ? 1 : 0), p.consider_luminance, p.long_tail, p.P, n);
-    if (p.tree && waves == 1 && fast_like && model != FTK_MODEL_LSSD) {
-        waves = std::min(4, std::max(2, (p.P + 63) / 64));  // the throughput mode has no one-wave fast kernel: the generic kernel's waves
-    }
-    if (const char *env = FTK_ENV(ctx, klt_waves)) {
-        waves = atoi(env);  // experiment override
-    }
-    p.waves_per_feature = waves < 1 ? 1 : (waves > 4 ? 4 : waves);
-    // One-wave features are packed several to a workgroup (no barrier between them): the 16 workgroups a CU admits would
-    // otherwise cap it at 16 resident features = 4 waves per SIMD, below what the registers allow.
-    p.features_per_group = 1;
-    const bool pipelined_candidate = model == FTK_MODEL_BASIC && opt->method == FTK_METHOD_INVERSE && p.patch_rows <= 64 && p.patch_cols <= 64;
-    if (p.waves_per_feature == 1 && pipelined_candidate) {
-        // measured (config 5 shard, 25 000 features): 1 / 2 / 3 / 4 per workgroup = 191 / 175 / 180 / 172 us.  (Round 2 measured no gain:
-        // that was before the compile-time geometry removed the SGPR spill traffic — the one-wave kernel is bound by how many
-        // features are in flight, not by vector issue: the throughput mode, which drops 20 % of its VALU work, runs no faster.)
-        int group = 4;
-        if (const char *env = FTK_ENV(ctx, klt_group)) {
-            group = atoi(env);  // experiment override
-        }
-        p.features_per_group = group < 1 ? 1 : (group > 4 ? 4 : group);
-    }
-    // Basic KLT inverse runs the pipelined kernel (klt_basic_kernels.hip) when its single-wave table
-    // builders can hold the patch (<= 64 rows / columns) and coordinates stay exact integers in fp32.
-    p.pb_enabled = 0;
-    if (model == FTK_MODEL_BASIC && opt->method == FTK_METHOD_INVERSE && p.patch_rows <= 64 && p.patch_cols <= 64) {
-        bool small = true;
-        for (int i = 0; i < p.n_levels; ++i) {
-            small = small && p.ref[i].rows < (1 << 23) && p.ref[i].cols < (1 << 23) && p.cur[i].rows < (1 << 23) && p.cur[i].cols < (1 << 23);
-        }
-        p.pb_enabled = small ? 1 : 0;
-    }
-    // The `fast` method (the reference's default) of Basic KLT runs the one-wave kernel of klt_fast_kernels.hip at every feature
-    // count: with 1 - 2 iterations per level a feature's life is its level entries, which that kernel walks without a barrier and with
-    // the next level's windows in flight (2 000 x 13 x 13: 28.8 us on the generic two-wave kernel).  Not in the throughput mode (the
-    // generic kernel's instantiations serve it), not for patches whose per-pixel records would crowd the LDS.
-    // (the chunked one-wave LSSD levels choose their chain form at run time: quads while every feature of the call is resident at once)
-    p.quad_chain = n <= 4096 ? 1 : 0;
-    p.fk_enabled = 0;
-    // One wave walks all P pixels of every pass: up to 15 x 15 that beats the generic kernel's 2 - 4 waves at every feature count
-    // (2 000 x 13 x 13: 22.6 vs 27.5 us; 10 000: 58.6 vs 82.9 us); larger patches only where the call is throughput-bound anyway
-    // (2 000 x 21 x 21: 77.8 vs 54.4 us on two waves).
-    // The affine tracker's fast method runs on the same skeleton (the first iteration of a level sweeps and chains 64-pixel chunks
-    // through a ring, the later ones six whole rows) from 512 features on: 13 x 13, same box, one wave / generic kernel: 1 000
-    // features 34.7 / 36.9 us, 2 000: 77.0 / 83.6, 3 000: 66.0 / 108.3, 5 000: 80.5 / 128.9 — and 100: 83.8 / 75.0, 300: 56.9 / 53.4:
-    // a small call IS its slowest feature (31 iterations here), and that one runs 10 % faster on the generic kernel's three waves.
-    const bool fk_model = model == FTK_MODEL_BASIC || model == FTK_MODEL_AFFINE;
-    if (fk_model && fast_like && !p.tree && p.waves_per_feature == 1 && p.P <= 1024) {  // (the policy table chose ONE wave: the one-wave kernel)
-        bool small = true;
-        for (int i = 0; i < p.n_levels; ++i) {
-            small = small && p.ref[i].rows < (1 << 23) && p.ref[i].cols < (1 << 23) && p.cur[i].rows < (1 << 23) && p.cur[i].cols < (1 << 23);
-        }
-        ftk::KltParams one = p;
-        one.features_per_group = 1;
-        if (small && ftk::klt_fast_lds_bytes(model, one) <= 40 * 1024) {
-            p.fk_enabled = 1;
-            p.waves_per_feature = 1;
-        }
-    }
-    // LSSD fast, one wave per feature, no luminance scaling: the chunked sweep / chain variant (a 64-pixel ring instead of all
-    // P products of all nine chains in LDS; config 4: 304 -> 242 us)
-    p.terms_floats = 0;
-    p.px_floats = 3;
-    p.lssd_chunked = 0;
-    if (model == FTK_MODEL_AFFINE && (opt->method == FTK_METHOD_INVERSE || opt->method == FTK_METHOD_DIRECT)) {
-        p.px_floats = 4;
-        p.terms_floats = ((p.Ppad / 4 + ftk::kAffineTermsRoundGroups - 1) / ftk::kAffineTermsRoundGroups) * ftk::kAffineTermsRoundGroups * ftk::kAffineTermsGroupFloats;  // products grouped by four pixels (klt_kernels.hip affine_all_terms)
-        // The axis tables of the level setup are dead once the iterations start, and the head of the product groups is rewritten
-        // by every iteration before it is read: the tables live THERE.  1.2 KB less per feature at 13 x 13 — 22.5 instead of
-        // 23.8 KB, i.e. seven instead of six features per CU.  Not for patches of fewer than four pixels (1x1, 1x3, 3x1): their
-        // FIRST group holds zero padding (written once per launch) that the tables would overwrite; from 1x5 / 3x3 on the first
-        // group with padding starts behind the tables (group g at 100 g floats, tables 12 (rows + cols) floats).
-        if (p.P >= 4) {
-            p.a0_floats = 0;
-        }
-    }
-    const char *chunk_env = FTK_ENV(ctx, lssd_chunked);
-    // (with consider_patch_luminance: the variant that keeps the sampled values in registers — patches up to 512 pixels, klt_kernels.hip kLumChunks)
-    if (model == FTK_MODEL_LSSD && fast_like && p.waves_per_feature == 1 && (!p.consider_luminance || (p.P <= 512 && !p.tree)) && !(chunk_env && atoi(chunk_env) == 0)) {
-        p.lssd_chunked = 1;
-        p.px_floats = 6;
-        const int32_t epad = (p.E + 3) & ~3;
-        p.terms_floats = epad > 9 * 68 ? epad : 9 * 68;  // the ring, or the extended patch that shares its space at level entry
-        p.a0_floats = 0;                                  // (klt_kernels.hip lssd_level_fast_chunked)
-    }
-    if (p.fk_enabled) {
-        int group = 4;  // one-wave features that never meet, several to a workgroup (the 16-workgroups-per-CU cap)
-        if (const char *env = FTK_ENV(ctx, klt_group)) {
-            group = atoi(env);  // experiment override
-        }
-        p.features_per_group = group < 1 ? 1 : (group > 4 ? 4 : group);
-        ftk::KltParams one = p;
-        one.features_per_group = 1;
-        const int fit = (int)((size_t)(64 * 1024) / ftk::klt_fast_lds_bytes(model, one));  // a workgroup's LDS stays below 64 KB
-        if (p.features_per_group > fit) {
-            p.features_per_group = fit < 1 ? 1 : fit;
-        }
-    } else if (!p.pb_enabled) {
-        p.features_per_group = 1;  // the generic kernel's workgroup is one feature ...
-        if (p.waves_per_feature == 1) {
-            int group = 2;  // ... or, one-wave variants, a few features that never meet (config 4, 10 000 features: 153 / 140.5 / 141 us at 1 / 2 / 4)
-            if (const char *env = FTK_ENV(ctx, klt_group)) {
-                group = atoi(env);  // experiment override
-            }
-            p.features_per_group = group < 1 ? 1 : (group > 4 ? 4 : group);
-        }
-    }
-    size_t lds = ftk::klt_lds_bytes(model, opt->method, p);
-    if (lds == 0) {
-        return fail(ctx, FTK_E_UNSUPPORTED, "klt: unknown variant (model %d, method %d)", model, opt->method);
-    }
-    // The large-patch form: a patch whose per-pixel arrays exceed a workgroup's 160 KB of LDS (from 41 x 41 for Basic KLT, 37 x 37
-    // for the non-fast affine variants) runs the generic multi-wave kernel with those arrays in a per-workgroup slice of device
-    // memory (ftk_device.h KltParams::spill) — same code, same sums.  Exact mode only.  FTK_KLT_SPILL=1 forces the form for any
-    // patch, 2 also drops the LDS image windows (what happens by itself from about 280 x 280): the tests walk every variant through both.
-    const char *spill_env = FTK_ENV(ctx, klt_spill);
-    const int spill_force = spill_env ? atoi(spill_env) : 0;
-    if (lds > 160 * 1024 || spill_force > 0) {
-        p.spill = 1;
-        p.tree = 0;
-        p.pb_enabled = p.fk_enabled = p.lssd_chunked = 0;
-        p.features_per_group = 1;
-        int w = (p.P + 63) / 64;
-        p.waves_per_feature = w < 2 ? 2 : (w > 4 ? 4 : w);
-        ftk::KltParams geometry = p;
-        ftk::klt_fill_geometry(geometry);
-        p.a0_floats = geometry.a0_floats;
-        p.px_floats = 3;
-        p.terms_floats = 0;
-        if (model == FTK_MODEL_AFFINE && (opt->method == FTK_METHOD_INVERSE || opt->method == FTK_METHOD_DIRECT)) {
-            p.px_floats = 4;
-            p.terms_floats = ((p.Ppad / 4 + ftk::kAffineTermsRoundGroups - 1) / ftk::kAffineTermsRoundGroups) * ftk::kAffineTermsRoundGroups * ftk::kAffineTermsGroupFloats;
-        }
-        lds = ftk::klt_lds_bytes(model, opt->method, p);
-        if (lds > 150 * 1024 || spill_force > 1) {
-            // not even the windows fit: every tap takes the samplers' global-memory path (same arithmetic); a disabled window has one
-            // row and no column, which every covered-by-the-window test refuses
-            p.rwin_rows = p.cwin_rows = 1;
-            p.rwin_cols = p.cwin_cols = 0;
-            p.magic_rwc = p.magic_cwc = p.magic_rwq = p.magic_cwq = 0;
-            lds = ftk::klt_lds_bytes(model, opt->method, p);
-        }
-        const size_t floats = ftk::klt_spill_floats(model, p);
-        if (floats == 0 || floats > 0xFFFFFFFFull) {
-            return fail(ctx, FTK_E_UNSUPPORTED, "klt: patch %dx%d needs %zu floats of device memory per feature", p.patch_rows, p.patch_cols, floats);
-        }
-        p.spill_stride_floats = (uint32_t)floats;
-    }
-    return FTK_OK;
-}
 
 int make_pyramid(ftk_context *ctx, ftk_pyramid **out) {
     if (!ctx || !out) {
@@ -509,19 +231,6 @@ int ftk_device_count(void) {
         return 0;
     }
     return n;
-}
-
-void ftk_default_klt_options(ftk_klt_options *opt) {
-    if (!opt) {
-        return;
-    }
-    opt->max_track_points = 500;
-    opt->max_iteration = 15;
-    opt->max_tolerance_large_step = 3;
-    opt->half_rows = 6;
-    opt->half_cols = 6;
-    opt->max_converge_step = 4e-2f;
-    opt->method = FTK_METHOD_FAST;
 }
 
 int ftk_context_create(int device, void *stream, ftk_context **out) {
@@ -695,9 +404,9 @@ int ftk_warmup(ftk_context *ctx, unsigned what) {
         FTK_HIP(ctx, ftk::pyramid_warm(ctx->stream));
         // the staging blocks of the host-buffer entry points, at the size a few thousand features need ...
         // ... and what the upload of one 1080p pyramid stages (ftk_pyramid_upload gathers the levels in the pinned block)
-        int rc = ensure_scratch(ctx, 4u << 20);
+        int rc = ftk_ensure_scratch(ctx, 4u << 20);
         if (rc == FTK_OK) {
-            rc = ensure_pinned(ctx, 4u << 20);
+            rc = ftk_ensure_pinned(ctx, 4u << 20);
         }
         // ... and the two pinned slots host images pass through on their way into a pyramid (1 MB each: up to 1024 x 1024)
         for (int k = 0; k < 2 && rc == FTK_OK; ++k) {
@@ -713,10 +422,10 @@ int ftk_warmup(ftk_context *ctx, unsigned what) {
         FTK_HIP(ctx, ftk::feature_warm(ctx->stream));  // BRIEF descriptors sit in front of the matcher
         int rc = ensure_match_keys(ctx, 4096);
         if (rc == FTK_OK) {
-            rc = ensure_scratch(ctx, 4u << 20);
+            rc = ftk_ensure_scratch(ctx, 4u << 20);
         }
         if (rc == FTK_OK) {
-            rc = ensure_pinned(ctx, 4u << 20);
+            rc = ftk_ensure_pinned(ctx, 4u << 20);
         }
         if (rc == FTK_OK) {
             rc = ensure_brief_pattern(ctx, 256, 8);  // kLength / kHalfPatchSize of the reference's caller (test_descriptor_matcher_brief.cpp:71-72)
@@ -847,7 +556,7 @@ int ftk_pyramid_upload(ftk_context *ctx, const ftk_image *host_levels, int32_t n
     }
     pyr->n_levels = n_levels;
     // gather the levels in pinned staging, then ONE H2D copy of the whole pyramid
-    if (ensure_pinned(ctx, total) != FTK_OK) {
+    if (ftk_ensure_pinned(ctx, total) != FTK_OK) {
         ftk_pyramid_destroy(pyr);
         return FTK_E_OUT_OF_MEMORY;
     }
@@ -1099,401 +808,6 @@ void ftk_pyramid_destroy(ftk_pyramid *pyr) {
     delete pyr;
 }
 
-/* ---- KLT ----------------------------------------------------------------------------------- */
-
-int ftk_klt_track_device(ftk_context *ctx, int model, const ftk_klt_options *opt, const ftk_pyramid *ref, const ftk_pyramid *cur,
-                         const float *d_ref_uv, const float *d_cur_uv_in, float *d_cur_uv_out, const uint8_t *d_status_in,
-                         uint8_t *d_status_out, int32_t n, const float *prior, int consider_luminance, int single_level, uint32_t *d_iters) {
-    if (!ctx) {
-        return fail(nullptr, FTK_E_INVALID_ARGUMENT, "klt_track_device: null context");
-    }
-    FTK_LOCK(ctx);
-    if (n < 0) {
-        return fail(ctx, FTK_E_INVALID_ARGUMENT, "klt_track_device: negative feature count");
-    }
-    if (n == 0) {
-        return FTK_OK;
-    }
-    if (!d_ref_uv || !d_cur_uv_in || !d_cur_uv_out || !d_status_in || !d_status_out) {
-        return fail(ctx, FTK_E_INVALID_ARGUMENT, "klt_track_device: null buffer");
-    }
-    // The kernels read and write a feature's (u, v) as ONE 8-byte access (include/ftk.h: "8-byte aligned"): a pair array at an odd
-    // float offset — legal through round 3 — is refused here instead of becoming misaligned 64-bit accesses on the device.
-    if (((reinterpret_cast<uintptr_t>(d_ref_uv) | reinterpret_cast<uintptr_t>(d_cur_uv_in) | reinterpret_cast<uintptr_t>(d_cur_uv_out)) & 7u) != 0) {
-        return fail(ctx, FTK_E_INVALID_ARGUMENT, "klt_track_device: the (u, v) arrays must be 8-byte aligned (ref %p, in %p, out %p)", (const void *)d_ref_uv,
-                    (const void *)d_cur_uv_in, (const void *)d_cur_uv_out);
-    }
-    ftk::KltParams p;
-    const int rc = fill_klt_params(ctx, model, opt, ref, cur, n, prior, consider_luminance, single_level, &p);
-    if (rc != FTK_OK) {
-        return rc;
-    }
-    p.tree = (ctx->reduction == FTK_REDUCTION_TREE && !p.spill) ? 1 : 0;
-    {
-        // this launch's number, for the report of its longest feature (tail-aware wave policy, fill_klt_params)
-        if (!ctx->tail_host) {
-            void *host = nullptr;
-            if (hipHostMalloc(&host, 64, hipHostMallocDefault) == hipSuccess && hipMalloc(reinterpret_cast<void **>(&ctx->tail_dev), 64) == hipSuccess) {
-                memset(host, 0, 64);
-                ctx->tail_host = static_cast<uint32_t *>(host);
-                (void)hipMemsetAsync(ctx->tail_dev, 0, 64, ctx->stream);
-            } else {
-                (void)hipGetLastError();
-                if (host) {
-                    (void)hipHostFree(host);
-                }
-            }
-        }
-        if (ctx->tail_host && ctx->tail_dev) {
-            ctx->tail_call = (ctx->tail_call + 1u) & 0xFFFFFFu;
-            if (ctx->tail_call == 0u) {
-                ctx->tail_call = 1u;  // (after 16 M launches the device word's running maximum starts over with the host's)
-                (void)hipMemsetAsync(ctx->tail_dev, 0, 64, ctx->stream);
-            }
-            const int mi = opt->method == FTK_METHOD_INVERSE ? 0 : (opt->method == FTK_METHOD_DIRECT ? 1 : 2);
-            ++ctx->tail[model][mi].launches;
-            p.tail_dev = ctx->tail_dev + (model * 3 + mi);    // a word per variant
-            p.tail_host = ctx->tail_host + (model * 3 + mi);  // (hipHostMalloc'ed memory is device-visible under the same address)
-            p.tail_call = ctx->tail_call;
-        }
-    }
-    p.ref_uv = d_ref_uv;
-    p.cur_uv_in = d_cur_uv_in;
-    p.cur_uv_out = d_cur_uv_out;
-    p.status_in = d_status_in;
-    p.status_out = d_status_out;
-    p.iters = d_iters;
-    FTK_HIP(ctx, hipSetDevice(ctx->device));
-    if (p.spill) {
-        // Large patches: a slice of device memory per launch slot.  All features at once while that stays within a budget (4 GB;
-        // FTK_KLT_SPILL_BUDGET_MB), otherwise in batches of consecutive features — a feature's result does not depend on the others.
-        const size_t per = sizeof(float) * (size_t)p.spill_stride_floats;
-        size_t budget = (size_t)4096 << 20;
-        if (const char *env = FTK_ENV(ctx, klt_spill_budget_mb)) {
-            budget = (size_t)(atoll(env) > 0 ? atoll(env) : 1) << 20;
-        }
-        size_t batch = budget / per;
-        batch = batch < 1 ? 1 : (batch > (size_t)n ? (size_t)n : batch);
-        if (batch * per > ctx->klt_spill_bytes) {
-            // the slices would have to grow: a hipFree / hipMalloc (and a synchronisation) that a stream capture cannot contain
-            hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-            if (hipStreamIsCapturing(ctx->stream, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) {
-                return fail(ctx, FTK_E_UNSUPPORTED, "klt_track_device: a %d x %d patch needs %zu MB of device memory for its per-feature slices, which cannot be "
-                            "allocated while the stream is being captured: make one such call before the capture (the buffer is kept)", p.patch_rows, p.patch_cols,
-                            (batch * per) >> 20);
-            }
-        }
-        const int rc_buf = ftk_ensure_device_buffer(ctx, &ctx->klt_spill, &ctx->klt_spill_bytes, batch * per);
-        if (rc_buf != FTK_OK) {
-            return rc_buf;
-        }
-        p.spill_base = static_cast<float *>(ctx->klt_spill);
-        ctx->sched_calls = 0;  // no launch order for these calls; a later ordinary call starts its history over
-        ctx->sched_n = 0;
-        for (size_t b0 = 0; b0 < (size_t)n; b0 += batch) {
-            const size_t nb = (size_t)n - b0 < batch ? (size_t)n - b0 : batch;
-            ftk::KltParams q = p;
-            q.n = (int32_t)nb;
-            q.ref_uv = p.ref_uv + 2 * b0;
-            q.cur_uv_in = p.cur_uv_in + 2 * b0;
-            q.cur_uv_out = p.cur_uv_out + 2 * b0;
-            q.status_in = p.status_in + b0;
-            q.status_out = p.status_out + b0;
-            q.iters = p.iters ? p.iters + b0 : nullptr;
-            q.n_track = (size_t)p.n_track > b0 ? (uint32_t)((size_t)p.n_track - b0 < nb ? (size_t)p.n_track - b0 : nb) : 0u;  // kMaxTrackPointsNumber is a cap on the whole list
-            const hipError_t e = ftk::klt_launch(model, opt->method, q, ctx->stream);
-            if (e != hipSuccess) {
-                return fail(ctx, e == hipErrorOutOfMemory ? FTK_E_OUT_OF_MEMORY : FTK_E_HIP, "klt launch (large patch) failed: %s", hipGetErrorString(e));
-            }
-        }
-        return FTK_OK;
-    }
-    {
-        // Launch order.  A call's time is bulk + tail: features run a data-dependent number of Gauss-Newton iterations
-        // (config 3: mean 6.7, one feature 52), a launch in list order starts the long ones wherever they happen to sit,
-        // and the grid drains while they finish.  Trackers are called frame after frame on (nearly) the same feature list
-        // and a feature that needed many iterations tends to need many again, so the launch slots go through a permutation:
-        // longest first by an EARLIER call's iteration counts.  No launch of its own: call k's tracker launch carries one
-        // extra workgroup (block 0, klt_common.h klt_order_block) that sorts call k - 1's counts while the features of call k
-        // run, and call k + 1 uses the result — so from the third call with the same feature count on, with a predictor two
-        // calls old.  Which slot runs a feature changes nothing in its arithmetic.  Only for calls with more features than
-        // fit the chip at once; FTK_KLT_SCHED=0 keeps list order.
-        const bool sched_allowed = !(FTK_ENV(ctx, klt_sched) && atoi(FTK_ENV(ctx, klt_sched)) == 0);
-        // From kSchedMinFeatures on — or, when this variant's recent calls had a long feature (p.long_tail: the kernels report it,
-        // fill_klt_params), already from kSchedMinLongTail: multi-wave features of a few thousand do NOT all fit the chip at once, and
-        // a 50-iteration feature that starts in the second round ends the launch that much later (the reference's example pair, same
-        // box, order from 4 096 / from 1 024: affine inverse 2 000 features 165.9 / 138.8 us, affine direct 3 000: 174.7 / 136.0, LSSD
-        // fast 3 000: 143.2 / 113.2, Basic fast 3 000: 60.9 / 52.3; the synthetic scene's LSSD / affine variants -4 ... -15 %).  Calls
-        // without a tail keep list order there: the order costs every feature one more dependent load (Basic variants +3 ... 4 %).
-        const uint32_t sched_min = FTK_ENV(ctx, klt_sched_min) ? (uint32_t)atoi(FTK_ENV(ctx, klt_sched_min))  // (experiment override)
-                                                               : (p.long_tail ? kSchedMinLongTail : kSchedMinFeatures);
-        if (sched_allowed && p.n_track >= sched_min && n <= kSchedMaxFeatures) {
-            if ((size_t)n > ctx->sched_capacity) {
-                FTK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-                for (int k = 0; k < 2; ++k) {
-                    if (ctx->sched_iters[k]) {
-                        (void)hipFree(ctx->sched_iters[k]);
-                        (void)hipFree(ctx->sched_order[k]);
-                        ctx->sched_iters[k] = nullptr;
-                        ctx->sched_order[k] = nullptr;
-                    }
-                }
-                if (ctx->sched_claim) {
-                    (void)hipFree(ctx->sched_claim);
-                    ctx->sched_claim = nullptr;
-                }
-                if (ctx->sched_pred) {
-                    (void)hipFree(ctx->sched_pred);
-                    ctx->sched_pred = nullptr;
-                }
-                ctx->sched_capacity = 0;
-                ctx->sched_n = 0;
-                const size_t cap = ((size_t)n + 4095) / 4096 * 4096;
-                // position-keyed slot swaps: a claim word per launch slot, and (once) the two tables of iteration counts by position
-                FTK_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->sched_claim), sizeof(uint32_t) * cap));
-                FTK_HIP(ctx, hipMemsetAsync(ctx->sched_claim, 0, sizeof(uint32_t) * cap, ctx->stream));
-                FTK_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->sched_pred), cap));
-                if (!ctx->sched_grid) {
-                    FTK_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->sched_grid), sizeof(uint32_t) * (kSchedTableWords + kSchedOrderWords)));
-                    FTK_HIP(ctx, hipMemsetAsync(ctx->sched_grid, 0, sizeof(uint32_t) * kSchedTableWords, ctx->stream));
-                }
-                for (int k = 0; k < 2; ++k) {
-                    FTK_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->sched_iters[k]), sizeof(uint32_t) * cap));
-                    FTK_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->sched_order[k]), sizeof(int32_t) * cap));
-                    // never-written entries must still be valid feature ids (0) and valid counts, whatever happens to a launch
-                    FTK_HIP(ctx, hipMemsetAsync(ctx->sched_iters[k], 0, sizeof(uint32_t) * cap, ctx->stream));
-                    FTK_HIP(ctx, hipMemsetAsync(ctx->sched_order[k], 0, sizeof(int32_t) * cap, ctx->stream));
-                }
-                ctx->sched_capacity = cap;
-            }
-            if (ctx->sched_n != n) {
-                ctx->sched_n = n;
-                ctx->sched_calls = 0;
-            }
-            const uint32_t k = ctx->sched_calls++;
-            // Position-keyed swaps ride on every such call, whatever the list did since the last one.  Call numbers start at 4 (an
-            // all-zero grid / claim word is never "recent") and tag 23 bits of a claim word: the claims are wiped before a tag could
-            // repeat.
-            // (never inside a stream capture: a replayed launch would carry this call's number again and read its own old claims)
-            hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
-            if (hipStreamIsCapturing(ctx->stream, &capture) != hipSuccess) {
-                (void)hipGetLastError();
-                capture = hipStreamCaptureStatusActive;  // unknown: be safe
-            }
-            // (nor when the results overwrite the reference positions: both sides of a trade must read the same positions)
-            const char *ref_lo = reinterpret_cast<const char *>(p.ref_uv), *out_lo = reinterpret_cast<const char *>(p.cur_uv_out);
-            const size_t uv_span = sizeof(float) * 2 * (size_t)n;
-            const bool ref_untouched = ref_lo + uv_span <= out_lo || out_lo + uv_span <= ref_lo;
-            // Multi-wave features only: there a feature is tens of microseconds long and iteration counts have heavy tails
-            // (config 3: 192 / 207 -> 149 / 166 us with no / a stale launch order, +0.5 % with a fitting one); the one-wave kernels
-            // run 10 000 - 25 000 cheap features, every late one of which would pay a table look-up for a 3 % gain at best
-            // (config 4: +2.9 % with a fitting order, -3 % without; config 5: +1 %).
-            // EVERY such call (outside a capture) leaves its iteration counts in the position table — one or two atomics per feature —
-            // so that the next one can order or trade by position whatever kernel either of them runs.
-            const bool recording = capture == hipStreamCaptureStatusNone && ctx->sched_grid && ctx->sched_claim;
-            uint32_t last_recorded = 0;
-            if (recording) {
-                if (ctx->sched_call < 4u) {
-                    ctx->sched_call = 4u;
-                }
-                ++ctx->sched_call;
-                if ((ctx->sched_call & 0x7FFFFFu) < 4u) {
-                    FTK_HIP(ctx, hipMemsetAsync(ctx->sched_claim, 0, sizeof(uint32_t) * ctx->sched_capacity, ctx->stream));
-                    FTK_HIP(ctx, hipMemsetAsync(ctx->sched_grid, 0, sizeof(uint32_t) * kSchedTableWords, ctx->stream));
-                    ctx->sched_call += 4u;
-                    ctx->sched_recorded = 0;
-                }
-                p.sched_grid = ctx->sched_grid;
-                p.sched_call = ctx->sched_call;
-                last_recorded = ctx->sched_recorded;
-                ctx->sched_recorded = ctx->sched_call;
-            }
-            if (recording && p.waves_per_feature >= 2 && ref_untouched && n > 1024 + 512) {
-                p.sched_flags = ctx->sched_grid + (2u << 16);
-                p.sched_claim = ctx->sched_claim;
-            }
-            p.sched_iters = ctx->sched_iters[k & 1];          // this call's counts
-            if (k >= 1) {                                     // sort the previous call's counts beside this call's features
-                p.sort_iters = ctx->sched_iters[(k - 1) & 1];
-                p.sort_order_out = ctx->sched_order[(k - 1) & 1];
-                // The spatial (tile) order reads the reference positions in two passes while the feature workgroups of the same
-                // launch write cur_uv_out: with one position buffer updated in place (ref == out, allowed by include/ftk.h) a
-                // feature crossing a tile boundary in between would make the histogram and the scatter disagree — duplicates,
-                // stale entries, a write past order[n - 1].  Such a call gets the iteration-count / identity order instead.
-                p.sort_ref_uv = ref_untouched ? p.ref_uv : nullptr;
-            }
-            if (k >= 2) {                                     // made during the previous call from the counts before it
-                p.order = ctx->sched_order[k & 1];
-            } else if (recording && last_recorded != 0u && last_recorded + 1u == ctx->sched_call && ctx->sched_pred && model != FTK_MODEL_BASIC &&
-                       p.sched_claim == nullptr) {
-                // (LSSD and affine KLT: their iteration counts have tails — config 4 without history 206 -> 183 us, with luminance
-                // 357 -> 315; Basic KLT's are flat on most scenes and the ~10 us of the two launches would buy nothing — config 5 shard
-                // 181 -> 190; the multi-wave kernels trade slots by position inside the launch instead)
-                // No index-keyed order (the feature count has just changed, or these are the first calls): order THIS call by what the
-                // last call left at its features' positions — two small launches in front of the tracker's (klt_kernels.hip
-                // klt_position_order_launch).  The buffer is the one an index-keyed order of this call would have used: nobody else
-                // writes it during this call.
-                const uint32_t *last_table = ctx->sched_grid + (((ctx->sched_call - 1u) & 1u) << 16);
-                FTK_HIP(ctx, ftk::klt_position_order_launch(p.ref_uv, n, last_table, ctx->sched_call - 1u, ctx->sched_pred, ctx->sched_grid + kSchedTableWords,
-                                                            ctx->sched_order[k & 1], ctx->stream));
-                p.order = ctx->sched_order[k & 1];
-            }
-            if (const char *dump = FTK_ENV(ctx, klt_swap_dump)) {  // diagnostic: how many trades the PREVIOUS launch of this context made
-                if (p.sched_claim != nullptr && ctx->sched_call > 5u) {
-                    std::vector<uint32_t> h((size_t)n);
-                    FTK_HIP(ctx, hipMemcpyAsync(h.data(), ctx->sched_claim, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-                    FTK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-                    const uint32_t last = (ctx->sched_call - 1u) & 0x7FFFFFu;
-                    size_t trades = 0, own = 0;
-                    for (uint32_t w : h) {
-                        if ((w >> 9) == last) {
-                            ((w & 0x1FFu) == 0x1FFu ? own : trades) += 1;
-                        }
-                    }
-                    if (FILE *f = fopen(dump, "w")) {
-                        fprintf(f, "%zu %zu\n", trades, own);
-                        fclose(f);
-                    }
-                }
-            }
-            if (const char *dump = FTK_ENV(ctx, klt_sched_dump)) {  // diagnostic: the permutation in use and the counts it came from
-                if (k >= 2) {
-                    std::vector<int32_t> h((size_t)n * 2);
-                    FTK_HIP(ctx, hipMemcpyAsync(h.data(), ctx->sched_order[k & 1], sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-                    FTK_HIP(ctx, hipMemcpyAsync(h.data() + n, ctx->sched_iters[k & 1], sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-                    FTK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-                    if (FILE *f = fopen(dump, "wb")) {
-                        fwrite(h.data(), sizeof(int32_t), h.size(), f);
-                        fclose(f);
-                    }
-                }
-            }
-        }
-    }
-    const hipError_t launch_rc = ftk::klt_launch(model, opt->method, p, ctx->stream);
-    if (launch_rc != hipSuccess) {
-        // The launch-order state advanced above assumed this launch would write its iteration counts and (from the second call
-        // on) a permutation: it did neither, so the history starts over — the next call must not install an order nobody wrote.
-        ctx->sched_calls = 0;
-        ctx->sched_n = 0;
-        return fail(ctx, launch_rc == hipErrorOutOfMemory ? FTK_E_OUT_OF_MEMORY : FTK_E_HIP, "klt launch failed: %s", hipGetErrorString(launch_rc));
-    }
-    return FTK_OK;
-}
-
-int ftk_klt_track(ftk_context *ctx, int model, const ftk_klt_options *opt, const ftk_pyramid *ref, const ftk_pyramid *cur, const float *ref_uv,
-                  float *cur_uv, uint8_t *status, int32_t n, const float *prior, int consider_luminance, int single_level, uint32_t *iters) {
-    FTK_TRACE_SCOPE("ftk_klt_track");
-    if (!ctx) {
-        return fail(nullptr, FTK_E_INVALID_ARGUMENT, "klt_track: null context");
-    }
-    FTK_LOCK(ctx);
-    if (n < 0) {
-        return fail(ctx, FTK_E_INVALID_ARGUMENT, "klt_track: negative feature count");
-    }
-    if (n == 0) {
-        return FTK_OK;
-    }
-    if (!ref_uv || !cur_uv || !status) {
-        return fail(ctx, FTK_E_INVALID_ARGUMENT, "klt_track: null buffer");
-    }
-    FTK_HIP(ctx, hipSetDevice(ctx->device));
-    // One contiguous block [ref_uv | cur_uv | status | iters], mirrored in pinned host memory:
-    // a single H2D of (ref_uv, cur_uv, status) and a single D2H of (cur_uv, status, iters) per call.
-    const size_t uv_bytes = align_up(sizeof(float) * 2 * (size_t)n, 256);
-    const size_t st_bytes = align_up((size_t)n, 256);
-    const size_t it_bytes = align_up(sizeof(uint32_t) * (size_t)n, 256);
-    const size_t total = 2 * uv_bytes + st_bytes + it_bytes;
-    int rc = ensure_scratch(ctx, total);
-    if (rc != FTK_OK) {
-        return rc;
-    }
-    rc = ensure_pinned(ctx, total);
-    if (rc != FTK_OK) {
-        return rc;
-    }
-    uint8_t *dbase = static_cast<uint8_t *>(ctx->scratch);
-    uint8_t *hbase = static_cast<uint8_t *>(ctx->pinned);
-    float *d_ref = reinterpret_cast<float *>(dbase);
-    float *d_cur = reinterpret_cast<float *>(dbase + uv_bytes);
-    uint8_t *d_st = dbase + 2 * uv_bytes;
-    uint32_t *d_it = reinterpret_cast<uint32_t *>(dbase + 2 * uv_bytes + st_bytes);
-    memcpy(hbase, ref_uv, sizeof(float) * 2 * (size_t)n);
-    memcpy(hbase + uv_bytes, cur_uv, sizeof(float) * 2 * (size_t)n);
-    memcpy(hbase + 2 * uv_bytes, status, (size_t)n);
-    // Small calls (the reference's callers track a few hundred features) are dominated by the two staging copies and
-    // their queue latency, not by bytes: the kernel then reads (ref_uv, cur_uv, status) from and writes its 9 B per
-    // feature straight into the pinned host block over PCIe — no H2D / D2H at all (2 000 features: 89 -> ~60 us per
-    // call).  Larger calls keep the bulk copies.
-    void *mapped = nullptr;
-    if (n <= 16384 && hipHostGetDevicePointer(&mapped, ctx->pinned, 0) == hipSuccess && mapped != nullptr) {
-        uint8_t *mbase = static_cast<uint8_t *>(mapped);
-        float *m_ref = reinterpret_cast<float *>(mbase);
-        float *m_cur = reinterpret_cast<float *>(mbase + uv_bytes);
-        uint8_t *m_st = mbase + 2 * uv_bytes;
-        uint32_t *m_it = reinterpret_cast<uint32_t *>(mbase + 2 * uv_bytes + st_bytes);
-        rc = ftk_klt_track_device(ctx, model, opt, ref, cur, m_ref, m_cur, m_cur, m_st, m_st, n, prior, consider_luminance, single_level,
-                                  iters ? m_it : nullptr);
-        if (rc != FTK_OK) {
-            (void)hipStreamSynchronize(ctx->stream);
-            return rc;
-        }
-        FTK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        memcpy(cur_uv, hbase + uv_bytes, sizeof(float) * 2 * (size_t)n);
-        memcpy(status, hbase + 2 * uv_bytes, (size_t)n);
-        if (iters) {
-            memcpy(iters, hbase + 2 * uv_bytes + st_bytes, sizeof(uint32_t) * (size_t)n);
-        }
-        return FTK_OK;
-    }
-    FTK_HIP(ctx, hipMemcpyAsync(dbase, hbase, 2 * uv_bytes + st_bytes, hipMemcpyHostToDevice, ctx->stream));
-    rc = ftk_klt_track_device(ctx, model, opt, ref, cur, d_ref, d_cur, d_cur, d_st, d_st, n, prior, consider_luminance, single_level,
-                              iters ? d_it : nullptr);
-    if (rc != FTK_OK) {
-        (void)hipStreamSynchronize(ctx->stream);
-        return rc;
-    }
-    const size_t back = uv_bytes + st_bytes + (iters ? it_bytes : 0);
-    FTK_HIP(ctx, hipMemcpyAsync(hbase + uv_bytes, dbase + uv_bytes, back, hipMemcpyDeviceToHost, ctx->stream));
-    FTK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    memcpy(cur_uv, hbase + uv_bytes, sizeof(float) * 2 * (size_t)n);
-    memcpy(status, hbase + 2 * uv_bytes, (size_t)n);
-    if (iters) {
-        memcpy(iters, hbase + 2 * uv_bytes + st_bytes, sizeof(uint32_t) * (size_t)n);
-    }
-    return FTK_OK;
-}
-
-int ftk_extract_extend_patch(ftk_context *ctx, const ftk_pyramid *ref, int32_t level, float u, float v, int32_t ex_rows, int32_t ex_cols,
-                             float *ex_patch, uint8_t *valid, uint32_t *valid_count) {
-    FTK_TRACE_SCOPE("ftk_extract_extend_patch");
-    if (!ctx) {
-        return fail(nullptr, FTK_E_INVALID_ARGUMENT, "extract_extend_patch: null context");
-    }
-    FTK_LOCK(ctx);
-    if (!ref || level < 0 || level >= ref->n_levels || ex_rows <= 0 || ex_cols <= 0 || !ex_patch || !valid || !valid_count) {
-        return fail(ctx, FTK_E_INVALID_ARGUMENT, "extract_extend_patch: bad arguments");
-    }
-    FTK_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t n = (size_t)ex_rows * ex_cols;
-    const size_t patch_bytes = align_up(sizeof(float) * n, 256);
-    const size_t valid_bytes = align_up(n, 256);
-    int rc = ensure_scratch(ctx, patch_bytes + valid_bytes + 256);
-    if (rc != FTK_OK) {
-        return rc;
-    }
-    uint8_t *base = static_cast<uint8_t *>(ctx->scratch);
-    float *d_patch = reinterpret_cast<float *>(base);
-    uint8_t *d_valid = base + patch_bytes;
-    uint32_t *d_count = reinterpret_cast<uint32_t *>(base + patch_bytes + valid_bytes);
-    FTK_HIP(ctx, ftk::extract_patch_launch(ref->levels[level], u, v, ex_rows, ex_cols, d_patch, d_valid, d_count, ctx->stream));
-    FTK_HIP(ctx, hipMemcpyAsync(ex_patch, d_patch, sizeof(float) * n, hipMemcpyDeviceToHost, ctx->stream));
-    FTK_HIP(ctx, hipMemcpyAsync(valid, d_valid, n, hipMemcpyDeviceToHost, ctx->stream));
-    FTK_HIP(ctx, hipMemcpyAsync(valid_count, d_count, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    FTK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return FTK_OK;
-}
-
 /* ---- BRIEF descriptors (producer of the matcher's input) ----------------------------------- */
 
 static int ensure_brief_pattern(ftk_context *ctx, int32_t n_bits, int32_t half) {
@@ -1514,7 +828,7 @@ static int ensure_brief_pattern(ftk_context *ctx, int32_t n_bits, int32_t half) 
     }
     FTK_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->brief_pattern), pattern.size()));
     // through the pinned block on the context's stream: a pageable hipMemcpy on the null stream costs milliseconds the first time
-    const int prc = ensure_pinned(ctx, pattern.size());
+    const int prc = ftk_ensure_pinned(ctx, pattern.size());
     if (prc != FTK_OK) {
         return prc;
     }
@@ -1579,7 +893,7 @@ int ftk_brief_compute(ftk_context *ctx, const ftk_pyramid *image, int32_t level,
     const size_t n_words = (size_t)(n_bits + 31) / 32;
     const size_t uv_bytes = align_up(sizeof(float) * 2 * (size_t)n, 256);
     const size_t w_bytes = align_up(sizeof(uint32_t) * n_words * (size_t)n, 256);
-    int rc = ensure_scratch(ctx, uv_bytes + w_bytes);
+    int rc = ftk_ensure_scratch(ctx, uv_bytes + w_bytes);
     if (rc != FTK_OK) {
         return rc;
     }
@@ -1588,7 +902,7 @@ int ftk_brief_compute(ftk_context *ctx, const ftk_pyramid *image, int32_t level,
     }
     rc = ensure_brief_pattern(ctx, n_bits, half_patch);  // before the pinned block is filled: it stages the pattern there
     if (rc == FTK_OK) {
-        rc = ensure_pinned(ctx, uv_bytes + w_bytes);
+        rc = ftk_ensure_pinned(ctx, uv_bytes + w_bytes);
     }
     if (rc != FTK_OK) {
         return rc;
@@ -1622,7 +936,7 @@ static int harris_run(ftk_context *ctx, const ftk_pyramid *image, int32_t level,
     const size_t capacity = px;  // worst case (min_distance 1): every candidate is its own window maximum
     const size_t g_bytes = align_up(sizeof(short) * px, 256), f_bytes = align_up(sizeof(float) * px, 256);
     const size_t k_bytes = align_up(sizeof(unsigned long long) * px, 256), l_bytes = align_up(sizeof(unsigned long long) * capacity, 256);
-    const int rc = ensure_scratch(ctx, 2 * g_bytes + f_bytes + 3 * k_bytes + l_bytes + 256);
+    const int rc = ftk_ensure_scratch(ctx, 2 * g_bytes + f_bytes + 3 * k_bytes + l_bytes + 256);
     if (rc != FTK_OK) {
         return rc;
     }
@@ -1884,7 +1198,7 @@ int ftk_hamming_match(ftk_context *ctx, const uint32_t *ref_words, int32_t n_ref
     const size_t pred_bytes = pred_uv ? align_up(sizeof(float) * 2 * (size_t)n_ref, 256) : 0;
     const size_t cuv_bytes = pred_uv ? align_up(sizeof(float) * 2 * (size_t)n_cur, 256) : 0;
     const size_t idx_bytes = align_up(sizeof(int32_t) * (size_t)n_ref, 256);
-    int rc = ensure_scratch(ctx, ref_bytes + cur_bytes + pred_bytes + cuv_bytes + idx_bytes);
+    int rc = ftk_ensure_scratch(ctx, ref_bytes + cur_bytes + pred_bytes + cuv_bytes + idx_bytes);
     if (rc != FTK_OK) {
         return rc;
     }
@@ -1897,7 +1211,7 @@ int ftk_hamming_match(ftk_context *ctx, const uint32_t *ref_words, int32_t n_ref
     // One H2D per call: the inputs are gathered in the context's pinned block, laid out like the device scratch (pageable
     // hipMemcpyAsync calls are staged one by one by the runtime, ~10 us each; the reference's callers time this call).
     const size_t in_bytes = ref_bytes + cur_bytes + pred_bytes + cuv_bytes + idx_bytes;
-    rc = ensure_pinned(ctx, in_bytes);
+    rc = ftk_ensure_pinned(ctx, in_bytes);
     if (rc != FTK_OK) {
         return rc;
     }
@@ -1950,7 +1264,7 @@ int ftk_ldlt6_solve(ftk_context *ctx, const float *a, const float *b, float *x, 
     }
     FTK_HIP(ctx, hipSetDevice(ctx->device));
     const size_t a_bytes = align_up(sizeof(float) * 36 * (size_t)n, 256), b_bytes = align_up(sizeof(float) * 6 * (size_t)n, 256);
-    const int rc = ensure_scratch(ctx, a_bytes + 2 * b_bytes);
+    const int rc = ftk_ensure_scratch(ctx, a_bytes + 2 * b_bytes);
     if (rc != FTK_OK) {
         return rc;
     }
@@ -2170,7 +1484,7 @@ int ftk_direct_track(ftk_context *ctx, const ftk_direct_options *opt, const ftk_
     const size_t uv_bytes = align_up(sizeof(float) * 2 * (size_t)n, 256);
     const size_t st_bytes = align_up((size_t)n, 256);
     const size_t total = pts_bytes + 2 * uv_bytes + st_bytes + 256 + 256;
-    int rc = ensure_scratch(ctx, total);
+    int rc = ftk_ensure_scratch(ctx, total);
     if (rc != FTK_OK) {
         return rc;
     }
@@ -2401,7 +1715,7 @@ int ftk_cosine_match(ftk_context *ctx, const float *ref_desc, int32_t n_ref, con
     const size_t pred_bytes = pred_uv ? align_up(sizeof(float) * 2 * (size_t)n_ref, 256) : 0;
     const size_t cuv_bytes = pred_uv ? align_up(sizeof(float) * 2 * (size_t)n_cur, 256) : 0;
     const size_t idx_bytes = align_up(sizeof(int32_t) * (size_t)n_ref, 256);
-    int rc = ensure_scratch(ctx, ref_bytes + cur_bytes + pred_bytes + cuv_bytes + idx_bytes);
+    int rc = ftk_ensure_scratch(ctx, ref_bytes + cur_bytes + pred_bytes + cuv_bytes + idx_bytes);
     if (rc != FTK_OK) {
         return rc;
     }
@@ -2413,7 +1727,7 @@ int ftk_cosine_match(ftk_context *ctx, const float *ref_desc, int32_t n_ref, con
     int32_t *d_idx = reinterpret_cast<int32_t *>(base + ref_bytes + cur_bytes + pred_bytes + cuv_bytes);
     // one H2D per call through the pinned block (see ftk_hamming_match)
     const size_t in_bytes = ref_bytes + cur_bytes + pred_bytes + cuv_bytes + idx_bytes;
-    rc = ensure_pinned(ctx, in_bytes);
+    rc = ftk_ensure_pinned(ctx, in_bytes);
     if (rc != FTK_OK) {
         return rc;
     }
@@ -2552,7 +1866,7 @@ int dense_setup(ftk_context *ctx, const char *who, const ftk_dense_flow_options 
         }
         const size_t bytes = sizeof(float) * w.size();
         FTK_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->dense_weights), bytes));
-        rc = ensure_pinned(ctx, bytes);
+        rc = ftk_ensure_pinned(ctx, bytes);
         if (rc != FTK_OK) {
             return rc;
         }
@@ -2678,7 +1992,7 @@ int ftk_dense_flow(ftk_context *ctx, const ftk_dense_flow_options *opt, const ft
     FTK_HIP(ctx, hipSetDevice(ctx->device));
     const size_t px = (size_t)ref_pyr->levels[0].rows * ref_pyr->levels[0].cols;
     const size_t plane = align_up(sizeof(float) * px, 256);
-    int rc = ensure_scratch(ctx, 2 * plane);
+    int rc = ftk_ensure_scratch(ctx, 2 * plane);
     if (rc != FTK_OK) {
         return rc;
     }
@@ -2689,7 +2003,7 @@ int ftk_dense_flow(ftk_context *ctx, const ftk_dense_flow_options *opt, const ft
         (void)hipStreamSynchronize(ctx->stream);
         return rc;
     }
-    rc = ensure_pinned(ctx, 2 * plane);
+    rc = ftk_ensure_pinned(ctx, 2 * plane);
     if (rc != FTK_OK) {
         return rc;
     }
@@ -2723,7 +2037,7 @@ int ftk_dense_flow_level(ftk_context *ctx, const ftk_dense_flow_options *opt, co
     }
     const DevImage ref = ref_pyr->levels[level];
     const size_t px = (size_t)ref.rows * ref.cols, plane = align_up(sizeof(float) * px, 256);
-    rc = ensure_pinned(ctx, 2 * plane);
+    rc = ftk_ensure_pinned(ctx, 2 * plane);
     if (rc != FTK_OK) {
         return rc;
     }

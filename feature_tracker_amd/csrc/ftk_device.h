@@ -1,4 +1,4 @@
-// ftk_device.h — structures shared between the host-side C ABI (ftk_api.cpp) and the gfx950
+// ftk_device.h — structures shared between the host-side C ABI (ftk_api.cpp, ftk_klt.cpp) and the gfx950
 // kernels (klt_kernels.hip, matcher_kernels.hip, pyramid_kernels.hip).
 #pragma once
 
@@ -44,7 +44,7 @@ struct KltParams {
     uint32_t *tail_dev;
     uint32_t *tail_host;
     uint32_t tail_call;
-    int32_t long_tail;          // host-side note: this variant's recent calls had a feature of many iterations (ftk_api.cpp, tail-aware policy)
+    int32_t long_tail;          // host-side note: this variant's recent calls had a feature of many iterations (klt_plan.cpp; nothing reads it back)
     const uint32_t *sort_iters;  // may be null: the previous call's counts; one extra workgroup (block 0) sorts them ...
     int32_t *sort_order_out;     // ... into this permutation, longest first (klt_common.h, klt_order_block)
     const float *sort_ref_uv;    // reference positions the sort block may use for the spatial (tile) order: ref_uv, or null when this
@@ -78,7 +78,7 @@ struct KltParams {
     int32_t lssd_chunked;       // LSSD fast, one wave per feature, no luminance scaling: chunked sweep / chain (klt_kernels.hip)
     int32_t features_per_group; // > 1 (only with waves_per_feature == 1): that many one-wave features share a workgroup, without
                                 // meeting at a barrier (lifts the 16-workgroups-per-CU cap on resident one-wave features)
-    int32_t group_lds_stride;   // bytes between the LDS carves of the features of a group (filled by the launcher)
+    int32_t group_lds_stride;   // bytes between the LDS carves of the features of a group (klt_plan)
     // pipelined Basic-KLT inverse kernel (klt_basic_kernels.hip); pb_enabled = 0 selects the generic kernel
     int32_t pb_enabled;
     int32_t pb_rwin_rows, pb_rwin_cols;  // reference window incl. the rounding row / column: 2h+5 (cols padded to 4)
@@ -99,7 +99,7 @@ struct KltParams {
 // ceil(2^32 / d): row = umulhi(index, magic)
 __host__ __device__ constexpr uint32_t klt_div_magic(int32_t d) { return d <= 1 ? 0u : (uint32_t)(((1ull << 32) + (uint64_t)d - 1) / (uint64_t)d); }
 
-// Everything in KltParams that follows from (half_rows, half_cols) ALONE.  One definition for the host (fill_klt_params) and
+// Everything in KltParams that follows from (half_rows, half_cols) ALONE.  One definition for the host (klt_plan) and
 // for the kernels' compile-time specialisations (klt_basic_kernels.hip instantiates the pipelined kernel for the common patch
 // sizes: the geometry then folds into immediates instead of living in ~40 SGPRs, most of them spilled to vector lanes).
 __host__ __device__ constexpr void klt_fill_geometry(KltParams &p) {
@@ -142,21 +142,13 @@ __host__ __device__ constexpr void klt_fill_geometry(KltParams &p) {
     p.pb_cap_c = p.patch_cols + 2 + 2 * (bits_c + 3);
 }
 
-// LDS bytes a (model, method) variant needs for the given geometry; 0 if the variant is unknown.
-size_t klt_lds_bytes(int model, int method, const KltParams &p);
-// Floats of device memory one workgroup of the large-patch (p.spill) form needs; 0 if the variant is unknown.
-size_t klt_spill_floats(int model, const KltParams &p);
-// Launches the tracker kernel for (model, method) on `stream`; one workgroup of waves_per_feature wavefronts per feature.
-hipError_t klt_launch(int model, int method, const KltParams &p, hipStream_t stream);
+// (the trackers' launch plan, per-form LDS sizes, kernel pickers and klt_launch: klt_plan.h)
 // Launch order of THIS call from the position table the last call wrote (klt_kernels.hip): order[slot] = feature, predicted-longest
 // first.  last_table: 2^16 words; pred: n bytes; hist_and_cursor: 512 words (zeroed here).
 hipError_t klt_position_order_launch(const float *ref_uv, int32_t n, const uint32_t *last_table, uint32_t last_call, uint8_t *pred, uint32_t *hist_and_cursor,
                                      int32_t *order, hipStream_t stream);
 // Lane-parallel 6x6 LDLT (klt_common.h) on n systems, one wave each: the test hook behind ftk_ldlt6_solve.
 hipError_t ldlt6_launch(const float *d_a, const float *d_b, float *d_x, int n, hipStream_t stream);
-// Pipelined kernel for (FTK_MODEL_BASIC, FTK_METHOD_INVERSE); klt_launch dispatches to it when p.pb_enabled.
-size_t klt_basic_pipelined_lds_bytes(const KltParams &p);
-hipError_t klt_basic_pipelined_launch(const KltParams &p, hipStream_t stream);
 
 // Reference descriptors a thread of the register-tiled Hamming scan keeps in registers (a 256-thread workgroup covers
 // 256 * kMatchRefs reference rows); the host sizes its grid and its NearbyMatch boxes with the same number.
@@ -353,9 +345,6 @@ hipError_t pyramid_build_levels_launch(const uint8_t *level0, int32_t rows, int3
 hipError_t extract_patch_launch(DevImage ref, float u, float v, int32_t ex_rows, int32_t ex_cols, float *d_patch, uint8_t *d_valid,
                                 uint32_t *d_count, hipStream_t stream);
 
-// One-wave kernels of the `fast` method (klt_fast_kernels.hip); klt_launch dispatches to them when p.fk_enabled.
-size_t klt_fast_lds_bytes(int model, const KltParams &p);
-hipError_t klt_fast_launch(int model, const KltParams &p, hipStream_t stream);
 hipError_t klt_fast_warm(hipStream_t stream);
 
 // One empty launch per translation unit: loads its code object (ftk_warmup).

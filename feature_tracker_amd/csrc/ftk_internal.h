@@ -1,4 +1,4 @@
-// ftk_internal.h — definitions shared by the translation units behind the C ABI (ftk_api.cpp, ftk_comm.cpp).
+// ftk_internal.h — definitions shared by the translation units behind the C ABI (ftk_api.cpp, ftk_klt.cpp, ftk_comm.cpp).
 // Not installed, not part of the boundary: include/ftk.h is.
 #pragma once
 
@@ -196,3 +196,6 @@ struct ftk_trace_scope {
 #define FTK_TRACE_SCOPE(name) ftk_trace_scope ftk_trace_scope_(name)
 // Grows a context-owned device buffer (stream-synchronising first: earlier launches may still read the old one).
 int ftk_ensure_device_buffer(ftk_context *ctx, void **buf, size_t *have, size_t bytes);
+// The context's device scratch / pinned host staging block of the host-buffer entry points, at least `bytes` large (ftk_api.cpp).
+int ftk_ensure_scratch(ftk_context *ctx, size_t bytes);
+int ftk_ensure_pinned(ftk_context *ctx, size_t bytes);

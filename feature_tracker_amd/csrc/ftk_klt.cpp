@@ -1,0 +1,561 @@
+// ftk_klt.cpp — the trackers' entry points of the C ABI (include/ftk.h): ftk_klt_track_device and its host-buffer wrapper.
+//
+// One call, in the order it runs: argument checks -> tail class (klt_tail_class) -> launch plan (klt_plan.h: a pure function) ->
+// this launch's number for the tail report -> the large-patch batches (klt_launch_spilled) OR the launch order (klt_sched_prepare)
+// -> launch.  Reading the world — the context, the FTK_KLT_* switches, the device's tail words — happens here, never in the plan.
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "ftk_device.h"
+#include "ftk_internal.h"
+#include "klt_plan.h"
+
+namespace {
+
+size_t align_up(size_t x, size_t a) { return ftk_align_up(x, a); }
+
+constexpr uint32_t kSchedMinFeatures = 4096;  // below this (nearly) every feature is resident from the start: nothing to order ...
+constexpr uint32_t kSchedMinLongTail = 1024;  // ... unless the calls have a long tail (see ftk_klt_track_device)
+constexpr size_t kSchedTableWords = (2u << 16) + 2;  // two position tables of 2^16 entries (klt_common.h kSchedTableSize) + the two "no tail" flags behind them
+constexpr size_t kSchedOrderWords = 512;             // behind them: histogram + cursors of the position-keyed launch order (klt_position_order_launch)
+constexpr int32_t kSchedMaxFeatures = 1 << 18;  // the sort block walks the list alone; beyond this it could outlast the launch
+constexpr uint32_t kTailLongFrom = 24;  // iterations of a call's longest feature from which the call counts as tail-bound
+constexpr uint32_t kTailHold = 8;       // launches of the variant for which one such report holds
+constexpr uint32_t kTailFresh = 256;    // launches of the context a report may lag behind (the host enqueues far ahead of the device)
+
+int klt_check_call(ftk_context *ctx, int model, const ftk_klt_options *opt, const ftk_pyramid *ref, const ftk_pyramid *cur) {
+    if (!opt || !ref || !cur) {
+        return fail(ctx, FTK_E_INVALID_ARGUMENT, "klt: null options or pyramid");
+    }
+    if (model < FTK_MODEL_BASIC || model > FTK_MODEL_LSSD) {
+        return fail(ctx, FTK_E_INVALID_ARGUMENT, "klt: unknown model %d", model);
+    }
+    if (opt->method < FTK_METHOD_INVERSE || opt->method > FTK_METHOD_NEON) {
+        return fail(ctx, FTK_E_INVALID_ARGUMENT, "klt: unknown method %d", opt->method);
+    }
+    if (ref->n_levels != cur->n_levels) {
+        // OpticalFlow::TrackFeatures returns false here (optical_flow.cpp:9); callers above the ABI handle it
+        return fail(ctx, FTK_E_INVALID_ARGUMENT, "klt: pyramid level mismatch (%d vs %d)", ref->n_levels, cur->n_levels);
+    }
+    if (ref->n_levels < 1) {
+        return fail(ctx, FTK_E_INVALID_ARGUMENT, "klt: empty pyramid");
+    }
+    if (ref->device != ctx->device || cur->device != ctx->device) {
+        return fail(ctx, FTK_E_INVALID_ARGUMENT, "klt: pyramid lives on another device");
+    }
+    // The reference takes any int32 half size (optical_flow.h:24-25).  Here: up to 1023 (a 2047 x 2047 patch; pixel indices stay
+    // below 2^23 for the 24-bit multiplier); patches beyond a workgroup's LDS run the large-patch form below.
+    if (opt->half_rows < 0 || opt->half_cols < 0 || opt->half_rows > 1023 || opt->half_cols > 1023) {
+        return fail(ctx, FTK_E_UNSUPPORTED, "klt: half patch size (%d, %d) outside [0, 1023]", opt->half_rows, opt->half_cols);
+    }
+    return FTK_OK;
+}
+
+// An FTK_KLT_* count override: "atoi, clamp 1..4", or kKltNotSet.
+int klt_count_override(const char *env) {
+    if (!env) {
+        return ftk::kKltNotSet;
+    }
+    const int v = atoi(env);
+    return v < 1 ? 1 : (v > 4 ? 4 : v);
+}
+
+// Tail class of this variant's next launch (the wave policy's second axis, klt_plan.cpp), from the word its kernels report into;
+// the one place that updates ctx->tail[..].long_until.  FTK_KLT_TAIL_CLASS pins the class (the sweep and the policy test).
+int klt_tail_class(ftk_context *ctx, int model, int method) {
+    int long_tail = 0;
+    if (ctx->tail_host) {
+        const int mi = method == FTK_METHOD_INVERSE ? 0 : (method == FTK_METHOD_DIRECT ? 1 : 2);
+        ftk_context::TailState &ts = ctx->tail[model][mi];
+        // this variant's own word: {call number << 8 | iterations} of the longest feature of its most recent launch that has got that
+        // far.  The host may be many launches ahead of the device (back-to-back calls), so a report counts while it is at most
+        // kTailFresh launches of the context old, and one long report holds for kTailHold launches of the variant.
+        const uint32_t seen = reinterpret_cast<volatile uint32_t *>(ctx->tail_host)[model * 3 + mi];
+        const uint32_t age = (ctx->tail_call - (seen >> 8)) & 0xFFFFFFu;
+        if (seen != 0 && age <= kTailFresh && (seen & 0xFFu) >= kTailLongFrom) {
+            ts.long_until = ts.launches + kTailHold;
+            ts.longest = seen & 0xFFu;
+        }
+        long_tail = ts.launches < ts.long_until ? 1 : 0;
+    }
+    if (const char *env = FTK_ENV(ctx, klt_tail_class)) {
+        long_tail = atoi(env) != 0 ? 1 : 0;  // experiment override
+    }
+    return long_tail;
+}
+
+// The call's own fields of the argument block, then the plan (geometry and launch shape).
+int klt_plan_call(ftk_context *ctx, int model, const ftk_klt_options *opt, const ftk_pyramid *ref, const ftk_pyramid *cur, int32_t n, const float *prior,
+                  int consider_luminance, int single_level, int long_tail, ftk::KltParams *out, ftk::KltPlan *plan) {
+    ftk::KltParams &p = *out;
+    memset(&p, 0, sizeof(p));  // (every pointer null: list order, nothing recorded, unless a later step installs it)
+    ftk::KltPlanInput in = {};
+    p.n_levels = single_level ? 1 : ref->n_levels;
+    p.single_level = single_level ? 1 : 0;
+    for (int i = 0; i < p.n_levels; ++i) {
+        p.ref[i] = ref->levels[i];
+        p.cur[i] = cur->levels[i];
+        in.max_extent = std::max({in.max_extent, p.ref[i].rows, p.ref[i].cols, p.cur[i].rows, p.cur[i].cols});
+    }
+    p.n = n;
+    p.n_track = ((uint32_t)n < opt->max_track_points) ? (uint32_t)n : opt->max_track_points;
+    p.max_iteration = opt->max_iteration;
+    p.max_large_step = opt->max_tolerance_large_step;
+    p.converge = opt->max_converge_step;
+    static const float identity[4] = {1.0f, 0.0f, 0.0f, 1.0f};
+    const float *pr = prior ? prior : identity;
+    for (int i = 0; i < 4; ++i) {
+        p.prior[i] = pr[i];
+    }
+    p.consider_luminance = consider_luminance ? 1 : 0;
+    in.model = model;
+    in.method = opt->method;
+    in.half_rows = opt->half_rows;
+    in.half_cols = opt->half_cols;
+    in.n = n;
+    in.consider_luminance = p.consider_luminance;
+    in.tree = ctx->reduction == FTK_REDUCTION_TREE ? 1 : 0;
+    in.long_tail = long_tail;
+    in.waves = klt_count_override(FTK_ENV(ctx, klt_waves));
+    in.group = klt_count_override(FTK_ENV(ctx, klt_group));
+    in.lssd_chunked = FTK_ENV(ctx, lssd_chunked) ? atoi(FTK_ENV(ctx, lssd_chunked)) : ftk::kKltNotSet;
+    in.spill = FTK_ENV(ctx, klt_spill) ? atoi(FTK_ENV(ctx, klt_spill)) : ftk::kKltNotSet;
+    size_t spill_floats = 0;
+    switch (ftk::klt_plan(in, &p, plan, &spill_floats)) {
+        case ftk::kKltPlanUnknownVariant: return fail(ctx, FTK_E_UNSUPPORTED, "klt: unknown variant (model %d, method %d)", model, opt->method);
+        case ftk::kKltPlanSpillTooLarge:
+            return fail(ctx, FTK_E_UNSUPPORTED, "klt: patch %dx%d needs %zu floats of device memory per feature", p.patch_rows, p.patch_cols, spill_floats);
+        default: return FTK_OK;
+    }
+}
+
+// This launch's number, for the report of its longest feature (the tail words are allocated on a context's first tracker call).
+void klt_tail_number(ftk_context *ctx, int model, int method, ftk::KltParams &p) {
+    if (!ctx->tail_host) {
+        void *host = nullptr;
+        if (hipHostMalloc(&host, 64, hipHostMallocDefault) == hipSuccess && hipMalloc(reinterpret_cast<void **>(&ctx->tail_dev), 64) == hipSuccess) {
+            memset(host, 0, 64);
+            ctx->tail_host = static_cast<uint32_t *>(host);
+            (void)hipMemsetAsync(ctx->tail_dev, 0, 64, ctx->stream);
+        } else {
+            (void)hipGetLastError();
+            if (host) {
+                (void)hipHostFree(host);
+            }
+        }
+    }
+    if (ctx->tail_host && ctx->tail_dev) {
+        ctx->tail_call = (ctx->tail_call + 1u) & 0xFFFFFFu;
+        if (ctx->tail_call == 0u) {
+            ctx->tail_call = 1u;  // (after 16 M launches the device word's running maximum starts over with the host's)
+            (void)hipMemsetAsync(ctx->tail_dev, 0, 64, ctx->stream);
+        }
+        const int mi = method == FTK_METHOD_INVERSE ? 0 : (method == FTK_METHOD_DIRECT ? 1 : 2);
+        ++ctx->tail[model][mi].launches;
+        p.tail_dev = ctx->tail_dev + (model * 3 + mi);    // a word per variant
+        p.tail_host = ctx->tail_host + (model * 3 + mi);  // (hipHostMalloc'ed memory is device-visible under the same address)
+        p.tail_call = ctx->tail_call;
+    }
+}
+
+// Large patches: a slice of device memory per launch slot.  All features at once while that stays within a budget (4 GB;
+// FTK_KLT_SPILL_BUDGET_MB), otherwise in batches of consecutive features — a feature's result does not depend on the others.
+int klt_launch_spilled(ftk_context *ctx, int model, int method, ftk::KltParams &p, const ftk::KltPlan &plan) {
+    const int32_t n = p.n;
+    const size_t per = sizeof(float) * (size_t)p.spill_stride_floats;
+    size_t budget = (size_t)4096 << 20;
+    if (const char *env = FTK_ENV(ctx, klt_spill_budget_mb)) {
+        budget = (size_t)(atoll(env) > 0 ? atoll(env) : 1) << 20;
+    }
+    size_t batch = budget / per;
+    batch = batch < 1 ? 1 : (batch > (size_t)n ? (size_t)n : batch);
+    if (batch * per > ctx->klt_spill_bytes) {
+        // the slices would have to grow: a hipFree / hipMalloc (and a synchronisation) that a stream capture cannot contain
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(ctx->stream, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) {
+            return fail(ctx, FTK_E_UNSUPPORTED, "klt_track_device: a %d x %d patch needs %zu MB of device memory for its per-feature slices, which cannot be "
+                        "allocated while the stream is being captured: make one such call before the capture (the buffer is kept)", p.patch_rows, p.patch_cols,
+                        (batch * per) >> 20);
+        }
+    }
+    const int rc_buf = ftk_ensure_device_buffer(ctx, &ctx->klt_spill, &ctx->klt_spill_bytes, batch * per);
+    if (rc_buf != FTK_OK) {
+        return rc_buf;
+    }
+    p.spill_base = static_cast<float *>(ctx->klt_spill);
+    ctx->sched_calls = 0;  // no launch order for these calls; a later ordinary call starts its history over
+    ctx->sched_n = 0;
+    for (size_t b0 = 0; b0 < (size_t)n; b0 += batch) {
+        const size_t nb = (size_t)n - b0 < batch ? (size_t)n - b0 : batch;
+        ftk::KltParams q = p;
+        q.n = (int32_t)nb;
+        q.ref_uv = p.ref_uv + 2 * b0;
+        q.cur_uv_in = p.cur_uv_in + 2 * b0;
+        q.cur_uv_out = p.cur_uv_out + 2 * b0;
+        q.status_in = p.status_in + b0;
+        q.status_out = p.status_out + b0;
+        q.iters = p.iters ? p.iters + b0 : nullptr;
+        q.n_track = (size_t)p.n_track > b0 ? (uint32_t)((size_t)p.n_track - b0 < nb ? (size_t)p.n_track - b0 : nb) : 0u;  // kMaxTrackPointsNumber is a cap on the whole list
+        ftk::KltPlan batch_plan = plan;
+        batch_plan.grid = (unsigned)nb;  // one workgroup per feature in this form
+        const hipError_t e = ftk::klt_launch(batch_plan, model, method, q, ctx->stream);
+        if (e != hipSuccess) {
+            return fail(ctx, e == hipErrorOutOfMemory ? FTK_E_OUT_OF_MEMORY : FTK_E_HIP, "klt launch (large patch) failed: %s", hipGetErrorString(e));
+        }
+    }
+    return FTK_OK;
+}
+
+// Launch order.  A call's time is bulk + tail: features run a data-dependent number of Gauss-Newton iterations
+// (config 3: mean 6.7, one feature 52), a launch in list order starts the long ones wherever they happen to sit,
+// and the grid drains while they finish.  Trackers are called frame after frame on (nearly) the same feature list
+// and a feature that needed many iterations tends to need many again, so the launch slots go through a permutation:
+// longest first by an EARLIER call's iteration counts.  No launch of its own: call k's tracker launch carries one
+// extra workgroup (block 0, klt_common.h klt_order_block) that sorts call k - 1's counts while the features of call k
+// run, and call k + 1 uses the result — so from the third call with the same feature count on, with a predictor two
+// calls old.  Which slot runs a feature changes nothing in its arithmetic.  Only for calls with more features than
+// fit the chip at once; FTK_KLT_SCHED=0 keeps list order.
+int klt_sched_prepare(ftk_context *ctx, int model, int32_t n, int long_tail, ftk::KltParams &p) {
+    const bool sched_allowed = !(FTK_ENV(ctx, klt_sched) && atoi(FTK_ENV(ctx, klt_sched)) == 0);
+    // From kSchedMinFeatures on — or, when this variant's recent calls had a long feature (long_tail: the kernels report it,
+    // klt_tail_class), already from kSchedMinLongTail: multi-wave features of a few thousand do NOT all fit the chip at once, and
+    // a 50-iteration feature that starts in the second round ends the launch that much later (the reference's example pair, same
+    // box, order from 4 096 / from 1 024: affine inverse 2 000 features 165.9 / 138.8 us, affine direct 3 000: 174.7 / 136.0, LSSD
+    // fast 3 000: 143.2 / 113.2, Basic fast 3 000: 60.9 / 52.3; the synthetic scene's LSSD / affine variants -4 ... -15 %).  Calls
+    // without a tail keep list order there: the order costs every feature one more dependent load (Basic variants +3 ... 4 %).
+    const uint32_t sched_min = FTK_ENV(ctx, klt_sched_min) ? (uint32_t)atoi(FTK_ENV(ctx, klt_sched_min))  // (experiment override)
+                                                           : (long_tail ? kSchedMinLongTail : kSchedMinFeatures);
+    if (sched_allowed && p.n_track >= sched_min && n <= kSchedMaxFeatures) {
+        if ((size_t)n > ctx->sched_capacity) {
+            FTK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            for (int k = 0; k < 2; ++k) {
+                if (ctx->sched_iters[k]) {
+                    (void)hipFree(ctx->sched_iters[k]);
+                    (void)hipFree(ctx->sched_order[k]);
+                    ctx->sched_iters[k] = nullptr;
+                    ctx->sched_order[k] = nullptr;
+                }
+            }
+            if (ctx->sched_claim) {
+                (void)hipFree(ctx->sched_claim);
+                ctx->sched_claim = nullptr;
+            }
+            if (ctx->sched_pred) {
+                (void)hipFree(ctx->sched_pred);
+                ctx->sched_pred = nullptr;
+            }
+            ctx->sched_capacity = 0;
+            ctx->sched_n = 0;
+            const size_t cap = ((size_t)n + 4095) / 4096 * 4096;
+            // position-keyed slot swaps: a claim word per launch slot, and (once) the two tables of iteration counts by position
+            FTK_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->sched_claim), sizeof(uint32_t) * cap));
+            FTK_HIP(ctx, hipMemsetAsync(ctx->sched_claim, 0, sizeof(uint32_t) * cap, ctx->stream));
+            FTK_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->sched_pred), cap));
+            if (!ctx->sched_grid) {
+                FTK_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->sched_grid), sizeof(uint32_t) * (kSchedTableWords + kSchedOrderWords)));
+                FTK_HIP(ctx, hipMemsetAsync(ctx->sched_grid, 0, sizeof(uint32_t) * kSchedTableWords, ctx->stream));
+            }
+            for (int k = 0; k < 2; ++k) {
+                FTK_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->sched_iters[k]), sizeof(uint32_t) * cap));
+                FTK_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->sched_order[k]), sizeof(int32_t) * cap));
+                // never-written entries must still be valid feature ids (0) and valid counts, whatever happens to a launch
+                FTK_HIP(ctx, hipMemsetAsync(ctx->sched_iters[k], 0, sizeof(uint32_t) * cap, ctx->stream));
+                FTK_HIP(ctx, hipMemsetAsync(ctx->sched_order[k], 0, sizeof(int32_t) * cap, ctx->stream));
+            }
+            ctx->sched_capacity = cap;
+        }
+        if (ctx->sched_n != n) {
+            ctx->sched_n = n;
+            ctx->sched_calls = 0;
+        }
+        const uint32_t k = ctx->sched_calls++;
+        // Position-keyed swaps ride on every such call, whatever the list did since the last one.  Call numbers start at 4 (an
+        // all-zero grid / claim word is never "recent") and tag 23 bits of a claim word: the claims are wiped before a tag could
+        // repeat.
+        // (never inside a stream capture: a replayed launch would carry this call's number again and read its own old claims)
+        hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(ctx->stream, &capture) != hipSuccess) {
+            (void)hipGetLastError();
+            capture = hipStreamCaptureStatusActive;  // unknown: be safe
+        }
+        // (nor when the results overwrite the reference positions: both sides of a trade must read the same positions)
+        const char *ref_lo = reinterpret_cast<const char *>(p.ref_uv), *out_lo = reinterpret_cast<const char *>(p.cur_uv_out);
+        const size_t uv_span = sizeof(float) * 2 * (size_t)n;
+        const bool ref_untouched = ref_lo + uv_span <= out_lo || out_lo + uv_span <= ref_lo;
+        // Multi-wave features only: there a feature is tens of microseconds long and iteration counts have heavy tails
+        // (config 3: 192 / 207 -> 149 / 166 us with no / a stale launch order, +0.5 % with a fitting one); the one-wave kernels
+        // run 10 000 - 25 000 cheap features, every late one of which would pay a table look-up for a 3 % gain at best
+        // (config 4: +2.9 % with a fitting order, -3 % without; config 5: +1 %).
+        // EVERY such call (outside a capture) leaves its iteration counts in the position table — one or two atomics per feature —
+        // so that the next one can order or trade by position whatever kernel either of them runs.
+        const bool recording = capture == hipStreamCaptureStatusNone && ctx->sched_grid && ctx->sched_claim;
+        uint32_t last_recorded = 0;
+        if (recording) {
+            if (ctx->sched_call < 4u) {
+                ctx->sched_call = 4u;
+            }
+            ++ctx->sched_call;
+            if ((ctx->sched_call & 0x7FFFFFu) < 4u) {
+                FTK_HIP(ctx, hipMemsetAsync(ctx->sched_claim, 0, sizeof(uint32_t) * ctx->sched_capacity, ctx->stream));
+                FTK_HIP(ctx, hipMemsetAsync(ctx->sched_grid, 0, sizeof(uint32_t) * kSchedTableWords, ctx->stream));
+                ctx->sched_call += 4u;
+                ctx->sched_recorded = 0;
+            }
+            p.sched_grid = ctx->sched_grid;
+            p.sched_call = ctx->sched_call;
+            last_recorded = ctx->sched_recorded;
+            ctx->sched_recorded = ctx->sched_call;
+        }
+        if (recording && p.waves_per_feature >= 2 && ref_untouched && n > 1024 + 512) {
+            p.sched_flags = ctx->sched_grid + (2u << 16);
+            p.sched_claim = ctx->sched_claim;
+        }
+        p.sched_iters = ctx->sched_iters[k & 1];          // this call's counts
+        if (k >= 1) {                                     // sort the previous call's counts beside this call's features
+            p.sort_iters = ctx->sched_iters[(k - 1) & 1];
+            p.sort_order_out = ctx->sched_order[(k - 1) & 1];
+            // The spatial (tile) order reads the reference positions in two passes while the feature workgroups of the same
+            // launch write cur_uv_out: with one position buffer updated in place (ref == out, allowed by include/ftk.h) a
+            // feature crossing a tile boundary in between would make the histogram and the scatter disagree — duplicates,
+            // stale entries, a write past order[n - 1].  Such a call gets the iteration-count / identity order instead.
+            p.sort_ref_uv = ref_untouched ? p.ref_uv : nullptr;
+        }
+        if (k >= 2) {                                     // made during the previous call from the counts before it
+            p.order = ctx->sched_order[k & 1];
+        } else if (recording && last_recorded != 0u && last_recorded + 1u == ctx->sched_call && ctx->sched_pred && model != FTK_MODEL_BASIC &&
+                   p.sched_claim == nullptr) {
+            // (LSSD and affine KLT: their iteration counts have tails — config 4 without history 206 -> 183 us, with luminance
+            // 357 -> 315; Basic KLT's are flat on most scenes and the ~10 us of the two launches would buy nothing — config 5 shard
+            // 181 -> 190; the multi-wave kernels trade slots by position inside the launch instead)
+            // No index-keyed order (the feature count has just changed, or these are the first calls): order THIS call by what the
+            // last call left at its features' positions — two small launches in front of the tracker's (klt_kernels.hip
+            // klt_position_order_launch).  The buffer is the one an index-keyed order of this call would have used: nobody else
+            // writes it during this call.
+            const uint32_t *last_table = ctx->sched_grid + (((ctx->sched_call - 1u) & 1u) << 16);
+            FTK_HIP(ctx, ftk::klt_position_order_launch(p.ref_uv, n, last_table, ctx->sched_call - 1u, ctx->sched_pred, ctx->sched_grid + kSchedTableWords,
+                                                        ctx->sched_order[k & 1], ctx->stream));
+            p.order = ctx->sched_order[k & 1];
+        }
+        if (const char *dump = FTK_ENV(ctx, klt_swap_dump)) {  // diagnostic: how many trades the PREVIOUS launch of this context made
+            if (p.sched_claim != nullptr && ctx->sched_call > 5u) {
+                std::vector<uint32_t> h((size_t)n);
+                FTK_HIP(ctx, hipMemcpyAsync(h.data(), ctx->sched_claim, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+                FTK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+                const uint32_t last = (ctx->sched_call - 1u) & 0x7FFFFFu;
+                size_t trades = 0, own = 0;
+                for (uint32_t w : h) {
+                    if ((w >> 9) == last) {
+                        ((w & 0x1FFu) == 0x1FFu ? own : trades) += 1;
+                    }
+                }
+                if (FILE *f = fopen(dump, "w")) {
+                    fprintf(f, "%zu %zu\n", trades, own);
+                    fclose(f);
+                }
+            }
+        }
+        if (const char *dump = FTK_ENV(ctx, klt_sched_dump)) {  // diagnostic: the permutation in use and the counts it came from
+            if (k >= 2) {
+                std::vector<int32_t> h((size_t)n * 2);
+                FTK_HIP(ctx, hipMemcpyAsync(h.data(), ctx->sched_order[k & 1], sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+                FTK_HIP(ctx, hipMemcpyAsync(h.data() + n, ctx->sched_iters[k & 1], sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+                FTK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+                if (FILE *f = fopen(dump, "wb")) {
+                    fwrite(h.data(), sizeof(int32_t), h.size(), f);
+                    fclose(f);
+                }
+            }
+        }
+    }
+    return FTK_OK;
+}
+
+}  // namespace
+
+void ftk_default_klt_options(ftk_klt_options *opt) {
+    if (!opt) {
+        return;
+    }
+    opt->max_track_points = 500;
+    opt->max_iteration = 15;
+    opt->max_tolerance_large_step = 3;
+    opt->half_rows = 6;
+    opt->half_cols = 6;
+    opt->max_converge_step = 4e-2f;
+    opt->method = FTK_METHOD_FAST;
+}
+
+int ftk_klt_track_device(ftk_context *ctx, int model, const ftk_klt_options *opt, const ftk_pyramid *ref, const ftk_pyramid *cur,
+                         const float *d_ref_uv, const float *d_cur_uv_in, float *d_cur_uv_out, const uint8_t *d_status_in,
+                         uint8_t *d_status_out, int32_t n, const float *prior, int consider_luminance, int single_level, uint32_t *d_iters) {
+    if (!ctx) {
+        return fail(nullptr, FTK_E_INVALID_ARGUMENT, "klt_track_device: null context");
+    }
+    FTK_LOCK(ctx);
+    if (n < 0) {
+        return fail(ctx, FTK_E_INVALID_ARGUMENT, "klt_track_device: negative feature count");
+    }
+    if (n == 0) {
+        return FTK_OK;
+    }
+    if (!d_ref_uv || !d_cur_uv_in || !d_cur_uv_out || !d_status_in || !d_status_out) {
+        return fail(ctx, FTK_E_INVALID_ARGUMENT, "klt_track_device: null buffer");
+    }
+    // The kernels read and write a feature's (u, v) as ONE 8-byte access (include/ftk.h: "8-byte aligned"): a pair array at an odd
+    // float offset — legal through round 3 — is refused here instead of becoming misaligned 64-bit accesses on the device.
+    if (((reinterpret_cast<uintptr_t>(d_ref_uv) | reinterpret_cast<uintptr_t>(d_cur_uv_in) | reinterpret_cast<uintptr_t>(d_cur_uv_out)) & 7u) != 0) {
+        return fail(ctx, FTK_E_INVALID_ARGUMENT, "klt_track_device: the (u, v) arrays must be 8-byte aligned (ref %p, in %p, out %p)", (const void *)d_ref_uv,
+                    (const void *)d_cur_uv_in, (const void *)d_cur_uv_out);
+    }
+    int rc = klt_check_call(ctx, model, opt, ref, cur);
+    if (rc != FTK_OK) {
+        return rc;
+    }
+    const int long_tail = klt_tail_class(ctx, model, opt->method);
+    ftk::KltParams p;
+    ftk::KltPlan plan;
+    rc = klt_plan_call(ctx, model, opt, ref, cur, n, prior, consider_luminance, single_level, long_tail, &p, &plan);
+    if (rc != FTK_OK) {
+        return rc;
+    }
+    klt_tail_number(ctx, model, opt->method, p);
+    p.ref_uv = d_ref_uv;
+    p.cur_uv_in = d_cur_uv_in;
+    p.cur_uv_out = d_cur_uv_out;
+    p.status_in = d_status_in;
+    p.status_out = d_status_out;
+    p.iters = d_iters;
+    FTK_HIP(ctx, hipSetDevice(ctx->device));
+    if (plan.form == ftk::KltForm::GenericSpill) {
+        return klt_launch_spilled(ctx, model, opt->method, p, plan);
+    }
+    rc = klt_sched_prepare(ctx, model, n, long_tail, p);
+    if (rc != FTK_OK) {
+        return rc;
+    }
+    const hipError_t launch_rc = ftk::klt_launch(plan, model, opt->method, p, ctx->stream);
+    if (launch_rc != hipSuccess) {
+        // The launch-order state advanced above assumed this launch would write its iteration counts and (from the second call
+        // on) a permutation: it did neither, so the history starts over — the next call must not install an order nobody wrote.
+        ctx->sched_calls = 0;
+        ctx->sched_n = 0;
+        return fail(ctx, launch_rc == hipErrorOutOfMemory ? FTK_E_OUT_OF_MEMORY : FTK_E_HIP, "klt launch failed: %s", hipGetErrorString(launch_rc));
+    }
+    return FTK_OK;
+}
+
+int ftk_klt_track(ftk_context *ctx, int model, const ftk_klt_options *opt, const ftk_pyramid *ref, const ftk_pyramid *cur, const float *ref_uv,
+                  float *cur_uv, uint8_t *status, int32_t n, const float *prior, int consider_luminance, int single_level, uint32_t *iters) {
+    FTK_TRACE_SCOPE("ftk_klt_track");
+    if (!ctx) {
+        return fail(nullptr, FTK_E_INVALID_ARGUMENT, "klt_track: null context");
+    }
+    FTK_LOCK(ctx);
+    if (n < 0) {
+        return fail(ctx, FTK_E_INVALID_ARGUMENT, "klt_track: negative feature count");
+    }
+    if (n == 0) {
+        return FTK_OK;
+    }
+    if (!ref_uv || !cur_uv || !status) {
+        return fail(ctx, FTK_E_INVALID_ARGUMENT, "klt_track: null buffer");
+    }
+    FTK_HIP(ctx, hipSetDevice(ctx->device));
+    // One contiguous block [ref_uv | cur_uv | status | iters], mirrored in pinned host memory:
+    // a single H2D of (ref_uv, cur_uv, status) and a single D2H of (cur_uv, status, iters) per call.
+    const size_t uv_bytes = align_up(sizeof(float) * 2 * (size_t)n, 256);
+    const size_t st_bytes = align_up((size_t)n, 256);
+    const size_t it_bytes = align_up(sizeof(uint32_t) * (size_t)n, 256);
+    const size_t total = 2 * uv_bytes + st_bytes + it_bytes;
+    int rc = ftk_ensure_scratch(ctx, total);
+    if (rc != FTK_OK) {
+        return rc;
+    }
+    rc = ftk_ensure_pinned(ctx, total);
+    if (rc != FTK_OK) {
+        return rc;
+    }
+    uint8_t *dbase = static_cast<uint8_t *>(ctx->scratch);
+    uint8_t *hbase = static_cast<uint8_t *>(ctx->pinned);
+    float *d_ref = reinterpret_cast<float *>(dbase);
+    float *d_cur = reinterpret_cast<float *>(dbase + uv_bytes);
+    uint8_t *d_st = dbase + 2 * uv_bytes;
+    uint32_t *d_it = reinterpret_cast<uint32_t *>(dbase + 2 * uv_bytes + st_bytes);
+    memcpy(hbase, ref_uv, sizeof(float) * 2 * (size_t)n);
+    memcpy(hbase + uv_bytes, cur_uv, sizeof(float) * 2 * (size_t)n);
+    memcpy(hbase + 2 * uv_bytes, status, (size_t)n);
+    // Small calls (the reference's callers track a few hundred features) are dominated by the two staging copies and
+    // their queue latency, not by bytes: the kernel then reads (ref_uv, cur_uv, status) from and writes its 9 B per
+    // feature straight into the pinned host block over PCIe — no H2D / D2H at all (2 000 features: 89 -> ~60 us per
+    // call).  Larger calls keep the bulk copies.
+    void *mapped = nullptr;
+    if (n <= 16384 && hipHostGetDevicePointer(&mapped, ctx->pinned, 0) == hipSuccess && mapped != nullptr) {
+        uint8_t *mbase = static_cast<uint8_t *>(mapped);
+        float *m_ref = reinterpret_cast<float *>(mbase);
+        float *m_cur = reinterpret_cast<float *>(mbase + uv_bytes);
+        uint8_t *m_st = mbase + 2 * uv_bytes;
+        uint32_t *m_it = reinterpret_cast<uint32_t *>(mbase + 2 * uv_bytes + st_bytes);
+        rc = ftk_klt_track_device(ctx, model, opt, ref, cur, m_ref, m_cur, m_cur, m_st, m_st, n, prior, consider_luminance, single_level,
+                                  iters ? m_it : nullptr);
+        if (rc != FTK_OK) {
+            (void)hipStreamSynchronize(ctx->stream);
+            return rc;
+        }
+        FTK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        memcpy(cur_uv, hbase + uv_bytes, sizeof(float) * 2 * (size_t)n);
+        memcpy(status, hbase + 2 * uv_bytes, (size_t)n);
+        if (iters) {
+            memcpy(iters, hbase + 2 * uv_bytes + st_bytes, sizeof(uint32_t) * (size_t)n);
+        }
+        return FTK_OK;
+    }
+    FTK_HIP(ctx, hipMemcpyAsync(dbase, hbase, 2 * uv_bytes + st_bytes, hipMemcpyHostToDevice, ctx->stream));
+    rc = ftk_klt_track_device(ctx, model, opt, ref, cur, d_ref, d_cur, d_cur, d_st, d_st, n, prior, consider_luminance, single_level,
+                              iters ? d_it : nullptr);
+    if (rc != FTK_OK) {
+        (void)hipStreamSynchronize(ctx->stream);
+        return rc;
+    }
+    const size_t back = uv_bytes + st_bytes + (iters ? it_bytes : 0);
+    FTK_HIP(ctx, hipMemcpyAsync(hbase + uv_bytes, dbase + uv_bytes, back, hipMemcpyDeviceToHost, ctx->stream));
+    FTK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    memcpy(cur_uv, hbase + uv_bytes, sizeof(float) * 2 * (size_t)n);
+    memcpy(status, hbase + 2 * uv_bytes, (size_t)n);
+    if (iters) {
+        memcpy(iters, hbase + 2 * uv_bytes + st_bytes, sizeof(uint32_t) * (size_t)n);
+    }
+    return FTK_OK;
+}
+
+int ftk_extract_extend_patch(ftk_context *ctx, const ftk_pyramid *ref, int32_t level, float u, float v, int32_t ex_rows, int32_t ex_cols,
+                             float *ex_patch, uint8_t *valid, uint32_t *valid_count) {
+    FTK_TRACE_SCOPE("ftk_extract_extend_patch");
+    if (!ctx) {
+        return fail(nullptr, FTK_E_INVALID_ARGUMENT, "extract_extend_patch: null context");
+    }
+    FTK_LOCK(ctx);
+    if (!ref || level < 0 || level >= ref->n_levels || ex_rows <= 0 || ex_cols <= 0 || !ex_patch || !valid || !valid_count) {
+        return fail(ctx, FTK_E_INVALID_ARGUMENT, "extract_extend_patch: bad arguments");
+    }
+    FTK_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t n = (size_t)ex_rows * ex_cols;
+    const size_t patch_bytes = align_up(sizeof(float) * n, 256);
+    const size_t valid_bytes = align_up(n, 256);
+    int rc = ftk_ensure_scratch(ctx, patch_bytes + valid_bytes + 256);
+    if (rc != FTK_OK) {
+        return rc;
+    }
+    uint8_t *base = static_cast<uint8_t *>(ctx->scratch);
+    float *d_patch = reinterpret_cast<float *>(base);
+    uint8_t *d_valid = base + patch_bytes;
+    uint32_t *d_count = reinterpret_cast<uint32_t *>(base + patch_bytes + valid_bytes);
+    FTK_HIP(ctx, ftk::extract_patch_launch(ref->levels[level], u, v, ex_rows, ex_cols, d_patch, d_valid, d_count, ctx->stream));
+    FTK_HIP(ctx, hipMemcpyAsync(ex_patch, d_patch, sizeof(float) * n, hipMemcpyDeviceToHost, ctx->stream));
+    FTK_HIP(ctx, hipMemcpyAsync(valid, d_valid, n, hipMemcpyDeviceToHost, ctx->stream));
+    FTK_HIP(ctx, hipMemcpyAsync(valid_count, d_count, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    FTK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return FTK_OK;
+}

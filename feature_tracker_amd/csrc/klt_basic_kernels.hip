@@ -33,6 +33,7 @@
 // Arithmetic contract as in klt_kernels.hip: IEEE fp32, no contraction, correctly rounded division.
 #define FTK_CHAIN_ROUND 4  // 16 terms per round: the consumer wave holds 32 VGPRs of prefetched terms
 #include "klt_common.h"
+#include "klt_plan.h"
 
 namespace ftk {
 namespace {
@@ -675,7 +676,7 @@ __global__ void __attribute__((amdgpu_waves_per_eu(kWavesPerEu))) __launch_bound
         tail_report(p, iters, id);  // the longest feature of the call, for the next call's wave policy
         sched_grid_record(p, full_ref_u, full_ref_v, out_u, out_v, iters);  // ... and by position
         if (p.sched_iters) {
-            p.sched_iters[id] = iters;  // the next call's launch order (ftk_api.cpp: longest first)
+            p.sched_iters[id] = iters;  // the next call's launch order (ftk_klt.cpp: longest first)
         }
     }
 }
@@ -685,67 +686,37 @@ __global__ void __attribute__((amdgpu_waves_per_eu(kWavesPerEu))) __launch_bound
 
 namespace {
 template <int HR, int HC>
-void (*pick_kernel(bool solo, bool tree))(const KltParams) {
+KltKernel pick_kernel(bool solo, bool tree) {
+    void (*entry)(const KltParams);
     if (tree) {
-        return solo ? klt_basic_inverse_pipelined_kernel<true, HR, HC, true> : klt_basic_inverse_pipelined_kernel<false, HR, HC, true>;
+        entry = solo ? klt_basic_inverse_pipelined_kernel<true, HR, HC, true> : klt_basic_inverse_pipelined_kernel<false, HR, HC, true>;
+    } else {
+        entry = solo ? klt_basic_inverse_pipelined_kernel<true, HR, HC, false> : klt_basic_inverse_pipelined_kernel<false, HR, HC, false>;
     }
-    return solo ? klt_basic_inverse_pipelined_kernel<true, HR, HC, false> : klt_basic_inverse_pipelined_kernel<false, HR, HC, false>;
+    return {entry, "pipelined", HR, solo, tree, false, false};
 }
 }  // namespace
 
-size_t klt_basic_pipelined_lds_bytes(const KltParams &p) {
-    const size_t one = pb_lds_bytes(p, p.waves_per_feature);
-    return p.features_per_group > 1 ? one * (size_t)p.features_per_group : one;
-}
+size_t klt_pipelined_feature_lds_bytes(const KltParams &p) { return pb_lds_bytes(p, p.waves_per_feature); }
 
-hipError_t klt_basic_pipelined_launch(const KltParams &p_in, hipStream_t stream) {
-    KltParams p = p_in;
-    if (p.waves_per_feature == 1) {
-        if (p.features_per_group < 1) {
-            p.features_per_group = 1;
-        }
-        p.group_lds_stride = (int32_t)pb_lds_bytes(p, 1);  // a multiple of 16
-    } else {
-        p.features_per_group = 1;
-    }
-    size_t lds = klt_basic_pipelined_lds_bytes(p);
-    const unsigned sort_block = p.sort_iters ? 1u : 0u;  // one more workgroup: the sort of a later call's launch order
-    if (sort_block && lds < (size_t)kOrderLdsBytes) {
-        lds = kOrderLdsBytes;
-    }
-    const bool solo = p.features_per_group > 1 || p.waves_per_feature == 1;
-    if (solo && p.features_per_group < 1) {
-        p.features_per_group = 1;
-    }
+KltKernel klt_pipelined_pick(const KltParams &p) {
+    const bool solo = p.waves_per_feature == 1;
     // compile-time geometry for the patch sizes of the BASELINE configurations and the reference's default (11x11, 13x13, 21x21);
     // the throughput mode (p.tree: reported, never the contract) has its own instantiations of the same set
-    void (*kernel)(const KltParams) = pick_kernel<0, 0>(solo, p.tree != 0);
     if (p.half_rows == p.half_cols) {
         KltParams check = p;
         klt_fill_geometry(check);  // the specialised kernels recompute exactly this: refuse them if the caller's geometry differs
         const bool same = check.pb_cap_r == p.pb_cap_r && check.pb_cap_c == p.pb_cap_c && check.cwin_rows == p.cwin_rows && check.cwin_cols == p.cwin_cols;
         if (same) {
             switch (p.half_rows) {
-                case 5: kernel = pick_kernel<5, 5>(solo, p.tree != 0); break;
-                case 6: kernel = pick_kernel<6, 6>(solo, p.tree != 0); break;
-                case 10: kernel = pick_kernel<10, 10>(solo, p.tree != 0); break;
+                case 5: return pick_kernel<5, 5>(solo, p.tree != 0);
+                case 6: return pick_kernel<6, 6>(solo, p.tree != 0);
+                case 10: return pick_kernel<10, 10>(solo, p.tree != 0);
                 default: break;
             }
         }
     }
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) {
-            return e;
-        }
-    }
-    if (solo) {
-        const unsigned groups = (unsigned)((p.n + p.features_per_group - 1) / p.features_per_group);
-        hipLaunchKernelGGL(kernel, dim3(groups + sort_block), dim3(kWave * p.features_per_group), lds, stream, p);
-    } else {
-        hipLaunchKernelGGL(kernel, dim3((unsigned)p.n + sort_block), dim3(kWave * p.waves_per_feature), lds, stream, p);
-    }
-    return hipGetLastError();
+    return pick_kernel<0, 0>(solo, p.tree != 0);
 }
 
 // First-use cost out of the callers' timed regions (ftk_warmup): launching this empty kernel makes the runtime load this

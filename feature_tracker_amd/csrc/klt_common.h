@@ -1395,7 +1395,7 @@ __device__ __forceinline__ void sched_grid_record(const KltParams &p, float ref_
     }
 }
 
-// The iteration count of a call's longest feature, for the NEXT call's wave policy (ftk_api.cpp "tail-aware"): features that ran at
+// The iteration count of a call's longest feature, for the NEXT call's wave policy (ftk_klt.cpp klt_tail_class): features that ran at
 // least kTailReportFrom iterations raise a device word with atomicMax — an L2 load for most, an atomic for the few that raise it —
 // and whoever raised it forwards the new value to a device-visible host word with one system-scope store.  A lower value may land
 // after a higher one (two raisers racing over PCIe): the host treats the word as a hint.  One lane per feature calls this.

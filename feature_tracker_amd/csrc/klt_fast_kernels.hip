@@ -27,6 +27,7 @@
 // row-major pixel order on one lane.  Results are bit-identical to the generic kernel and to the oracle (tests/test_klt_gpu.py).
 #define FTK_CHAIN_ROUND 4
 #include "klt_common.h"
+#include "klt_plan.h"
 
 namespace ftk {
 namespace {
@@ -807,43 +808,15 @@ __global__ void __attribute__((amdgpu_waves_per_eu(kWavesPerEu))) __launch_bound
     }
 }
 
-template <int MODEL, int HR, int HC>
-hipError_t fk_launch(const KltParams &p, size_t lds, hipStream_t stream) {
-    void (*kernel)(const KltParams) = klt_fast_kernel<MODEL, HR, HC>;
-    if (lds > 48 * 1024) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) {
-            return e;
-        }
-    }
-    const unsigned sort_block = p.sort_iters ? 1u : 0u;
-    const unsigned groups = (unsigned)((p.n + p.features_per_group - 1) / p.features_per_group);
-    hipLaunchKernelGGL(kernel, dim3(groups + sort_block), dim3(kWave * p.features_per_group), lds, stream, p);
-    return hipGetLastError();
-}
-
 }  // namespace
 
-size_t klt_fast_lds_bytes(int model, const KltParams &p) {
-    if (model != FTK_MODEL_BASIC && model != FTK_MODEL_AFFINE) {
-        return 0;
-    }
-    const size_t one = fk_lds_bytes(model, p);
-    return one * (size_t)(p.features_per_group > 1 ? p.features_per_group : 1);
+size_t klt_fast_feature_lds_bytes(int model, const KltParams &p) {
+    return (model == FTK_MODEL_BASIC || model == FTK_MODEL_AFFINE) ? fk_lds_bytes(model, p) : 0;
 }
 
-hipError_t klt_fast_launch(int model, const KltParams &p_in, hipStream_t stream) {
+KltKernel klt_fast_pick(int model, const KltParams &p) {
     if (model != FTK_MODEL_BASIC && model != FTK_MODEL_AFFINE) {
-        return hipErrorInvalidValue;
-    }
-    KltParams p = p_in;
-    if (p.features_per_group < 1) {
-        p.features_per_group = 1;
-    }
-    p.group_lds_stride = (int32_t)fk_lds_bytes(model, p);  // a multiple of 16
-    size_t lds = klt_fast_lds_bytes(model, p);
-    if (p.sort_iters && lds < (size_t)kOrderLdsBytes) {
-        lds = kOrderLdsBytes;
+        return KltKernel{};
     }
     if (p.half_rows == p.half_cols) {
         KltParams check = p;
@@ -851,17 +824,18 @@ hipError_t klt_fast_launch(int model, const KltParams &p_in, hipStream_t stream)
         if (check.cwin_rows == p.cwin_rows && check.cwin_cols == p.cwin_cols && check.rwin_cols == p.rwin_cols && check.Ppad == p.Ppad) {
             if (model == FTK_MODEL_BASIC) {
                 switch (p.half_rows) {
-                    case 5: return fk_launch<FTK_MODEL_BASIC, 5, 5>(p, lds, stream);
-                    case 6: return fk_launch<FTK_MODEL_BASIC, 6, 6>(p, lds, stream);
-                    case 10: return fk_launch<FTK_MODEL_BASIC, 10, 10>(p, lds, stream);
+                    case 5: return {klt_fast_kernel<FTK_MODEL_BASIC, 5, 5>, "fast", 5, true, false, false, false};
+                    case 6: return {klt_fast_kernel<FTK_MODEL_BASIC, 6, 6>, "fast", 6, true, false, false, false};
+                    case 10: return {klt_fast_kernel<FTK_MODEL_BASIC, 10, 10>, "fast", 10, true, false, false, false};
                     default: break;
                 }
             } else if (p.half_rows == 6) {
-                return fk_launch<FTK_MODEL_AFFINE, 6, 6>(p, lds, stream);
+                return {klt_fast_kernel<FTK_MODEL_AFFINE, 6, 6>, "fast", 6, true, false, false, false};
             }
         }
     }
-    return model == FTK_MODEL_BASIC ? fk_launch<FTK_MODEL_BASIC, 0, 0>(p, lds, stream) : fk_launch<FTK_MODEL_AFFINE, 0, 0>(p, lds, stream);
+    return model == FTK_MODEL_BASIC ? KltKernel{klt_fast_kernel<FTK_MODEL_BASIC, 0, 0>, "fast", 0, true, false, false, false}
+                                    : KltKernel{klt_fast_kernel<FTK_MODEL_AFFINE, 0, 0>, "fast", 0, true, false, false, false};
 }
 
 __global__ void klt_fast_warm_kernel() {}

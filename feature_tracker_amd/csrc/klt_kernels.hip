@@ -37,6 +37,7 @@
 // inverse 134 -> 122, which then fits 4 waves per SIMD instead of 3).
 #define FTK_CHAIN_ROUND 4
 #include "klt_common.h"
+#include "klt_plan.h"
 
 namespace ftk {
 namespace {
@@ -99,7 +100,7 @@ __host__ __device__ inline size_t spill_floats(int K, const KltParams &p) {
 }
 
 __host__ __device__ inline size_t spill_lds_bytes(const KltParams &p) {
-    // a disabled window (rows 1, cols 0: klt_api's choice when the windows do not fit either) still owns eight shorts: the
+    // a disabled window (rows 1, cols 0: klt_plan.cpp's choice when the windows do not fit either) still owns eight shorts: the
     // branch-free taps read element 0 before they discard the value
     const size_t shorts = (size_t)pad4(p.rwin_rows * p.rwin_cols) + (size_t)pad4(p.cwin_rows * p.cwin_cols) + 16;
     return sizeof(float) * (72 + 24) + sizeof(uint16_t) * shorts;
@@ -1591,7 +1592,7 @@ __device__ __forceinline__ void lssd_level_fast_chunked(const Blk &b, const KltP
 // the reference mean's numerator covers the interior of the EXTENDED patch (= the patch) and its denominator the valid count of the
 // whole extended patch; the current mean's numerator covers patch rows / columns 1 .. size - 2 only and its denominator every valid
 // pixel.  Same expressions, same order of every sum as lssd_level_fast: bit-identical.
-constexpr int kLumChunks = 8;  // 64-pixel chunks a lane can keep values for: patches up to 512 pixels (ftk_api.cpp gates on it)
+constexpr int kLumChunks = 8;  // 64-pixel chunks a lane can keep values for: patches up to 512 pixels (klt_plan.cpp gates on it)
 
 __device__ __forceinline__ void lssd_level_fast_chunked_lum(const Blk &b, const KltParams &p, const DevImage &ref, const DevImage &cur, float ref_u,
                                                             float ref_v, LssdState &s, uint8_t &status, uint32_t &iters, Carve &c) {
@@ -1898,7 +1899,7 @@ __global__ void FTK_EU_ATTR __launch_bounds__(kWave *kMaxWaves) klt_track_kernel
     Carve c = SPILL ? carve_spill(lds_mine, p.spill_base + (size_t)block * p.spill_stride_floats, K, p) : carve_lds(lds_mine, K, p);
     if (MODEL == FTK_MODEL_AFFINE && METHOD != FTK_METHOD_FAST) {
         if (p.a0_floats == 0) {
-            c.a0 = c.terms;  // the level setup's axis tables share the head of the product groups (a0_floats == 0: ftk_api.cpp)
+            c.a0 = c.terms;  // the level setup's axis tables share the head of the product groups (a0_floats == 0: klt_plan.cpp)
         }
         // grouped layout (affine_all_terms): the pixels behind the patch up to the end of the last round of groups, all 24 sums
         const int first = p.P, end = affine_group_rounds(p.Ppad) * (4 * kChainRound);
@@ -2015,55 +2016,43 @@ __global__ void FTK_EU_ATTR __launch_bounds__(kWave *kMaxWaves) klt_track_kernel
         tail_report(p, iters, id);  // the longest feature of the call, for the next call's wave policy
         sched_grid_record(p, full_ref_u, full_ref_v, out_u, out_v, iters);  // ... and by position
         if (p.sched_iters) {
-            p.sched_iters[id] = iters;  // the next call's launch order (ftk_api.cpp: longest first)
+            p.sched_iters[id] = iters;  // the next call's launch order (ftk_klt.cpp: longest first)
         }
     }
 }
 
+// The generic kernel's instantiation for a plan.
 template <int MODEL, int METHOD>
-hipError_t launch_variant(const KltParams &p, size_t lds_bytes, hipStream_t stream) {
-    void (*kernel)(const KltParams) = p.waves_per_feature == 1 ? klt_track_kernel<MODEL, METHOD, true, 0> : klt_track_kernel<MODEL, METHOD, false, 0>;
-    if (p.spill) {
-        if (p.waves_per_feature < 2 || !p.spill_base) {
-            return hipErrorInvalidValue;
-        }
-        kernel = klt_track_kernel<MODEL, METHOD, false, 0, false, false, true>;
-    } else if (p.tree) {  // throughput mode (reported, never the contract): its own instantiations, run-time geometry
-        kernel = p.waves_per_feature == 1 ? klt_track_kernel<MODEL, METHOD, true, 0, true> : klt_track_kernel<MODEL, METHOD, false, 0, true>;
+KltKernel pick_variant(const KltPlan &plan, const KltParams &p) {
+    const bool solo = p.waves_per_feature == 1;
+    if (plan.form == KltForm::GenericSpill) {
+        return {klt_track_kernel<MODEL, METHOD, false, 0, false, false, true>, "generic", 0, false, false, false, true};
+    }
+    if (p.tree) {  // throughput mode (reported, never the contract): its own instantiations, run-time geometry
+        return solo ? KltKernel{klt_track_kernel<MODEL, METHOD, true, 0, true>, "generic", 0, true, true, false, false}
+                    : KltKernel{klt_track_kernel<MODEL, METHOD, false, 0, true>, "generic", 0, false, true, false, false};
     }
     // (measured per variant, 13 x 13: Basic -6...-14 %, LSSD -16...-21 %, affine fast -16 %, affine inverse / direct -8...-9 % — the
     // latter only once chain_groups' loop is kept rolled: with a compile-time round count the compiler unrolled it fully and the
     // kernel went from 81 to 128 VGPRs and 9...18 % SLOWER)
-    if (!p.tree && !p.spill && p.half_rows == 6 && p.half_cols == 6) {
+    bool h6 = p.half_rows == 6 && p.half_cols == 6;
+    if (h6) {
         KltParams check = p;
         klt_fill_geometry(check);  // what the specialised kernel recomputes: it must be what the caller passed
-        if (check.cwin_rows == p.cwin_rows && check.cwin_cols == p.cwin_cols && check.Ppad == p.Ppad && check.rwin_cols == p.rwin_cols) {
-            kernel = p.waves_per_feature == 1 ? klt_track_kernel<MODEL, METHOD, true, 6> : klt_track_kernel<MODEL, METHOD, false, 6>;
-        }
+        h6 = check.cwin_rows == p.cwin_rows && check.cwin_cols == p.cwin_cols && check.Ppad == p.Ppad && check.rwin_cols == p.rwin_cols;
     }
     if constexpr (MODEL == FTK_MODEL_LSSD && METHOD == FTK_METHOD_FAST) {
-        if (p.waves_per_feature == 1 && p.lssd_chunked && p.consider_luminance && !p.tree && !p.spill) {
-            const bool h6 = kernel == klt_track_kernel<MODEL, METHOD, true, 6>;
-            kernel = h6 ? klt_track_kernel<MODEL, METHOD, true, 6, false, true> : klt_track_kernel<MODEL, METHOD, true, 0, false, true>;
+        if (solo && p.lssd_chunked && p.consider_luminance) {
+            return h6 ? KltKernel{klt_track_kernel<MODEL, METHOD, true, 6, false, true>, "generic", 6, true, false, true, false}
+                      : KltKernel{klt_track_kernel<MODEL, METHOD, true, 0, false, true>, "generic", 0, true, false, true, false};
         }
     }
-    const unsigned sort_block = p.sort_iters ? 1u : 0u;  // one more workgroup: the sort of a later call's launch order
-    if (sort_block && lds_bytes < (size_t)kOrderLdsBytes) {
-        lds_bytes = kOrderLdsBytes;
+    if (h6) {
+        return solo ? KltKernel{klt_track_kernel<MODEL, METHOD, true, 6>, "generic", 6, true, false, false, false}
+                    : KltKernel{klt_track_kernel<MODEL, METHOD, false, 6>, "generic", 6, false, false, false, false};
     }
-    if (lds_bytes > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e != hipSuccess) {
-            return e;
-        }
-    }
-    if (p.waves_per_feature == 1) {
-        const int group = p.features_per_group < 1 ? 1 : p.features_per_group;
-        hipLaunchKernelGGL(kernel, dim3((unsigned)((p.n + group - 1) / group) + sort_block), dim3(kWave * group), lds_bytes, stream, p);
-    } else {
-        hipLaunchKernelGGL(kernel, dim3((unsigned)p.n + sort_block), dim3(kWave * p.waves_per_feature), lds_bytes, stream, p);
-    }
-    return hipGetLastError();
+    return solo ? KltKernel{klt_track_kernel<MODEL, METHOD, true, 0>, "generic", 0, true, false, false, false}
+                : KltKernel{klt_track_kernel<MODEL, METHOD, false, 0>, "generic", 0, false, false, false, false};
 }
 
 int chain_count(int model) {
@@ -2077,23 +2066,12 @@ int chain_count(int model) {
 
 }  // namespace
 
-size_t klt_lds_bytes(int model, int method, const KltParams &p) {
-    if (p.pb_enabled && model == FTK_MODEL_BASIC && method == FTK_METHOD_INVERSE) {
-        return klt_basic_pipelined_lds_bytes(p);
-    }
-    if (p.fk_enabled && method != FTK_METHOD_INVERSE && method != FTK_METHOD_DIRECT) {
-        return klt_fast_lds_bytes(model, p);
-    }
+size_t klt_generic_feature_lds_bytes(int model, const KltParams &p) {
     const int k = chain_count(model);
-    if (k == 0) {
-        return 0;
-    }
-    if (p.spill) {
-        return (spill_lds_bytes(p) + 15) & ~(size_t)15;
-    }
-    const size_t one = (carve_bytes(k, p) + 15) & ~(size_t)15;
-    return (p.waves_per_feature == 1 && p.features_per_group > 1) ? one * (size_t)p.features_per_group : one;
+    return k == 0 ? 0 : (carve_bytes(k, p) + 15) & ~(size_t)15;
 }
+
+size_t klt_spill_lds_bytes(int model, const KltParams &p) { return chain_count(model) == 0 ? 0 : (spill_lds_bytes(p) + 15) & ~(size_t)15; }
 
 size_t klt_spill_floats(int model, const KltParams &p) {
     const int k = chain_count(model);
@@ -2236,38 +2214,49 @@ hipError_t klt_position_order_launch(const float *ref_uv, int32_t n, const uint3
     return hipGetLastError();
 }
 
-hipError_t klt_launch(int model, int method, const KltParams &p, hipStream_t stream) {
-    if (p.waves_per_feature < 1 || p.waves_per_feature > kMaxWaves) {
-        return hipErrorInvalidValue;
+KltKernel klt_pick(const KltPlan &plan, int model, int method, const KltParams &p) {
+    if (plan.form == KltForm::Pipelined) {
+        return klt_pipelined_pick(p);
     }
-    if (p.pb_enabled && model == FTK_MODEL_BASIC && method == FTK_METHOD_INVERSE) {
-        return klt_basic_pipelined_launch(p, stream);
-    }
-    if (p.fk_enabled && method != FTK_METHOD_INVERSE && method != FTK_METHOD_DIRECT) {
-        return klt_fast_launch(model, p, stream);
-    }
-    const size_t lds = klt_lds_bytes(model, method, p);
-    KltParams pg = p;
-    if (pg.waves_per_feature == 1) {
-        if (pg.features_per_group < 1) {
-            pg.features_per_group = 1;
-        }
-        pg.group_lds_stride = (int32_t)(lds / (size_t)pg.features_per_group);  // a multiple of 16
+    if (plan.form == KltForm::OneWaveFast) {
+        return klt_fast_pick(model, p);
     }
     const int m = (method == FTK_METHOD_INVERSE || method == FTK_METHOD_DIRECT) ? method : FTK_METHOD_FAST;
-#define FTK_DISPATCH(MODEL)                                                               \
-    switch (m) {                                                                          \
-        case FTK_METHOD_INVERSE: return launch_variant<MODEL, FTK_METHOD_INVERSE>(pg, lds, stream); \
-        case FTK_METHOD_DIRECT: return launch_variant<MODEL, FTK_METHOD_DIRECT>(pg, lds, stream);   \
-        default: return launch_variant<MODEL, FTK_METHOD_FAST>(pg, lds, stream);                    \
+#define FTK_DISPATCH(MODEL)                                                             \
+    switch (m) {                                                                        \
+        case FTK_METHOD_INVERSE: return pick_variant<MODEL, FTK_METHOD_INVERSE>(plan, p); \
+        case FTK_METHOD_DIRECT: return pick_variant<MODEL, FTK_METHOD_DIRECT>(plan, p);   \
+        default: return pick_variant<MODEL, FTK_METHOD_FAST>(plan, p);                    \
     }
     switch (model) {
         case FTK_MODEL_BASIC: FTK_DISPATCH(FTK_MODEL_BASIC)
         case FTK_MODEL_AFFINE: FTK_DISPATCH(FTK_MODEL_AFFINE)
         case FTK_MODEL_LSSD: FTK_DISPATCH(FTK_MODEL_LSSD)
-        default: return hipErrorInvalidValue;
+        default: return KltKernel{};
     }
 #undef FTK_DISPATCH
+}
+
+// The one launch path of the trackers: every form's kernel leaves through here.
+hipError_t klt_launch(const KltPlan &plan, int model, int method, const KltParams &p, hipStream_t stream) {
+    const KltKernel kernel = klt_pick(plan, model, method, p);
+    // an inconsistent plan is refused, not repaired (klt_plan sets these fields)
+    if (!kernel.entry || p.waves_per_feature < 1 || p.waves_per_feature > kMaxWaves || p.features_per_group < 1 ||
+        (p.waves_per_feature > 1 && p.features_per_group != 1) || plan.block != (unsigned)(kWave * p.waves_per_feature * p.features_per_group) ||
+        plan.grid != (unsigned)((p.n + p.features_per_group - 1) / p.features_per_group) ||
+        (plan.form == KltForm::GenericSpill && (p.waves_per_feature < 2 || !p.spill_base))) {
+        return hipErrorInvalidValue;
+    }
+    const unsigned sort_block = p.sort_iters ? 1u : 0u;  // one more workgroup: the sort of a later call's launch order
+    const size_t lds = sort_block && plan.lds_bytes < (size_t)kOrderLdsBytes ? (size_t)kOrderLdsBytes : plan.lds_bytes;
+    if (lds > 48 * 1024) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel.entry), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) {
+            return e;
+        }
+    }
+    hipLaunchKernelGGL(kernel.entry, dim3(plan.grid + sort_block), dim3(plan.block), lds, stream, p);
+    return hipGetLastError();
 }
 
 // First-use cost out of the callers' timed regions (ftk_warmup): launching this empty kernel makes the runtime load this

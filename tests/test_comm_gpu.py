@@ -138,7 +138,7 @@ def test_a_failed_local_launch_poisons_its_shard_instead_of_leaving_the_collecti
         klt.track_sharded(comm, d_ref, d_ref.clone(), torch.zeros(n, dtype=torch.uint8, device=dev), d_out, d_st)  # sizes the exchange buffers
         stream.synchronize()
         try:  # (a communicator left open by a failed assertion keeps the interpreter from exiting)
-            klt.opt.half_rows = 1024  # outside [0, 1023]: fill_klt_params refuses it
+            klt.opt.half_rows = 1024  # outside [0, 1023]: klt_check_call (ftk_klt.cpp) refuses it
             with pytest.raises(_native.FtkError) as e:
                 klt.track_sharded(comm, d_ref, d_ref.clone(), torch.zeros(n, dtype=torch.uint8, device=dev), d_out, d_st)
             assert e.value.code == -4 and "half patch" in str(e.value)

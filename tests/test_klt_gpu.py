@@ -488,7 +488,7 @@ def test_one_wave_features_packed_into_workgroups(ftk, oracle, switch, group):
 @pytest.mark.parametrize("group", [None, 1, 3])
 def test_affine_fast_one_wave_kernel_on_the_edge_cases(ftk, oracle, switch, group):
     """The affine tracker's `fast` method runs klt_fast_kernel<affine> only from 513 features on (a smaller call is its slowest
-    feature, and that one is faster on the generic kernel's three waves: ftk_api.cpp fk_model), so the edge-case tests above — all
+    feature, and that one is faster on the generic kernel's three waves: klt_plan.cpp pick_form), so the edge-case tests above — all
     of 64 - 400 features — reach it on the generic kernel.  The same cases at 520 - 700 features: border and outside features (clamped
     reference rows instead of the register-fed interior form, zero valid pixels), predictions, incoming failures and a cap that cuts
     a workgroup's group of features, a rectangular patch with tight options, pyramid levels smaller than the patch, the single-level
@@ -561,7 +561,7 @@ def test_lssd_fast_chunked_equals_the_unchunked_level(ftk, oracle, switch):
 @pytest.mark.parametrize("model,method", [("affine", "inverse"), ("lssd", "fast"), ("basic", "inverse")])
 def test_launch_order_from_the_previous_call_changes_nothing(ftk, oracle, model, method, switch):
     """From the third call with the same feature count on, the device entry launches the features longest-first by an earlier
-    call's iteration counts (ftk_api.cpp; the sort runs in an extra workgroup of the launch in between, klt_common.h
+    call's iteration counts (ftk_klt.cpp; the sort runs in an extra workgroup of the launch in between, klt_common.h
     klt_order_block; calls of >= 4096 features).  Every call must return what the first one did — the oracle's answer — also
     when the history comes from DIFFERENT inputs (a stale predictor) and when some features are passed through (incoming
     status, kMaxTrackPointsNumber)."""
@@ -679,7 +679,7 @@ def test_flat_iteration_counts_give_a_spatial_xcd_major_launch_order(ftk, oracle
     assert np.array_equal(np.sort(order), np.arange(n)), "not a permutation"
     if np.array_equal(order, np.arange(n)):
         pytest.skip("the iteration counts of this scene have a tail: the order is by count, not by region")
-    group, run = 4, 64  # one-wave features, four per workgroup (ftk_api.cpp default); kOrderRunGroups workgroups per run
+    group, run = 4, 64  # one-wave features, four per workgroup (klt_plan.cpp default); kOrderRunGroups workgroups per run
     dealt = (n // group) // (8 * run) * (8 * run)
     assert dealt > 0
     w = np.arange(dealt)                    # workgroup index -> (XCD, position among that XCD's workgroups)

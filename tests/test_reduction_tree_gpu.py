@@ -279,7 +279,7 @@ def test_affine_inverse_and_direct_stay_exact_under_tree_mode(ftk, contexts, swi
                                                      ("basic", "fast", 6, "1"), ("basic", "inverse", 6, "1"), ("lssd", "inverse", 6, "1"),
                                                      ("affine", "fast", 6, "2"), ("lssd", "fast", 6, "1"), ("basic", "direct", 6, "2")])
 def test_large_patch_form_stays_exact_under_tree_mode(ftk, contexts, switch, model, method, half, force):
-    """The large-patch (spill) form forces p.tree = 0 (ftk_api.cpp): by itself from beyond a workgroup's LDS, and forced with
+    """The large-patch (spill) form forces p.tree = 0 (klt_plan.cpp): by itself from beyond a workgroup's LDS, and forced with
     FTK_KLT_SPILL on an ordinary patch.  Full multi-level tracking, bit for bit."""
     switch("FTK_KLT_SPILL", force)
     ref_levels, cur_levels = scenes.scene(640, 480, 2, "easy", "similarity")
