@@ -26,6 +26,7 @@
 // fp32 throughout, no contraction; quaternion arithmetic as defined in oracle/oracle_direct_method.c.
 #define FTK_CHAIN_ROUND 8  // 32 terms per prefetch round (four: +2 % on the spread kernel, whose consumer does nothing but chain; the one-workgroup kernel does not care)
 #include "klt_common.h"
+#include "match_plan.h"
 
 namespace ftk {
 namespace {
@@ -35,7 +36,6 @@ namespace {
 // iteration (793 chunks x ~390 producer instructions + 50 700 x 1.4 chain instructions), not by the split of that work over its waves —
 // which is why a single problem is SPREAD over the chip (direct_track_spread_kernel below: 2.53 ms); there the consumer only chains,
 // and longer chain rounds and the raised priority pay (docs/LAB_NOTES.md).
-constexpr int kDmWaves = 8;
 constexpr int kDmProducers = kDmWaves - 1;
 constexpr int kDmChunk = 64;
 constexpr int kDmRow = kDmChunk + 4;  // row pitch in floats: keeps the consumer's b128 reads on distinct banks
@@ -856,25 +856,21 @@ int direct_spread_resident_groups(uint32_t max_features, int device) {
     return per_cu * cus;
 }
 
-hipError_t direct_track_launch(const DirectParams &p, int n_problems, uint32_t max_features, hipStream_t stream) {
-    if (n_problems <= 0) {
-        return hipSuccess;
-    }
-    const size_t lds = direct_lds_bytes(max_features);
+hipError_t direct_track_launch(const DirectPlan &plan, const DirectParams &p, hipStream_t stream) {
     void (*kernel)(const DirectParams) = p.tree ? direct_track_kernel<true> : direct_track_kernel<false>;
-    if (p.spread > 0) {
+    if (plan.producers > 0) {
         if (p.tree || !p.spread_ws || p.spread_ws_words == 0) {
             return hipErrorInvalidValue;
         }
         kernel = direct_track_spread_kernel;
     }
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (plan.lds > 48 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds);
         if (e != hipSuccess) {
             return e;
         }
     }
-    hipLaunchKernelGGL(kernel, dim3((unsigned)(p.spread > 0 ? n_problems * (1 + p.spread) : n_problems)), dim3(kDmWaves * kWave), lds, stream, p);
+    hipLaunchKernelGGL(kernel, plan.grid, plan.block, plan.lds, stream, p);
     return hipGetLastError();
 }
 

@@ -39,7 +39,7 @@
 #include <limits.h>
 #include <stdlib.h>
 
-#include "ftk_device.h"
+#include "match_plan.h"
 
 namespace ftk {
 namespace {
@@ -47,17 +47,12 @@ namespace {
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef float float16v __attribute__((ext_vector_type(16)));
 
-constexpr int kTile = 128;     // rows of one operand tile (cur: MFMA rows, ref: MFMA columns)
+constexpr int kTile = kCosineTile;
 constexpr int kChunkK = 64;    // K staged per LDS chunk
 constexpr int kPitch = kChunkK + 8;  // halfs; +16 B keeps the 128-bit fragment reads off one bank group
 constexpr float kMargin = 1.5e-3f;
 constexpr float kNormLo = 9.094947017729282e-13f;  // 2^-40
 constexpr float kNormHi = 1.099511627776e12f;      // 2^40
-// Candidates per row up to which a call runs as ONE exact launch (cosine_match_small_kernel: a wave walks its row's candidates
-// alone, so its time grows with n_cur); measured against the multi-launch pipeline per shape
-constexpr int kCosineSmallCurNearby = 2048;  // 300 x 300 x 256 NearbyMatch 48.7 -> 10.7 us, 1 000 x 1 000 47.4 -> 21.3, 2 000 x 2 000 54.6 -> 40.3 (3 000 candidates: even)
-constexpr int kCosineSmallCurForce = 384;    // ForceMatch computes every pair exactly: 100 x 100 x 256 35.4 -> 14.8 us, 300 x 300 40.3 -> 32.1, 600 x 600 41.6 -> 59.2 (not taken)
-constexpr int kCosineSmallRefMax = 4096;
 
 __device__ __forceinline__ uint32_t order_key(float f) {
     const uint32_t b = __float_as_uint(f);
@@ -460,8 +455,6 @@ __global__ void __launch_bounds__(256) cosine_gemm_kernel(const CosineParams p) 
 // maximum of the single walk is a register (exact, no cross-wave staleness).  Scored entries are staged in LDS and
 // appended after the walk if they lie within the margin of the workgroup's own final maximum; the recheck kernel cuts
 // against the global one.
-constexpr int kRrTile = 64;        // cur rows per step
-constexpr int kRrRows = 512;       // ref rows per workgroup
 constexpr int kRrListCap = 1024;   // tiles of one workgroup's slice that the NearbyMatch tile list can hold (longer slices: no list)
 constexpr int kRrStepEntriesMax = 384;  // most a wave can stage in one step: best, second best and a whole-share entry per lane and nt (64 x 2 x 3)
 constexpr int kRrWaveStageCap = 768;  // staged entries per wave (64 rows; measured need ~3.3 per row)
@@ -1145,102 +1138,72 @@ __global__ void __launch_bounds__(256) cosine_match_small_kernel(const CosinePar
     }
 }
 
-template <int kSteps>
-hipError_t cosine_launch_small(const CosineParams &p, hipStream_t stream) {
-    const dim3 grid((unsigned)((p.n_ref + 3) / 4));
-    if (p.pred_uv) {
-        hipLaunchKernelGGL((cosine_match_small_kernel<kSteps, true>), grid, dim3(256), 0, stream, p);
-    } else {
-        hipLaunchKernelGGL((cosine_match_small_kernel<kSteps, false>), grid, dim3(256), 0, stream, p);
+template <int kKSteps>
+hipError_t launch_rr(const CosinePlan &plan, const CosineParams &p, hipStream_t stream) {
+    void (*kern)(const CosineParams) = p.pred_uv ? cosine_gemm_rr_kernel<kKSteps, true> : cosine_gemm_rr_kernel<kKSteps, false>;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds);
+    if (e != hipSuccess) {
+        return e;
     }
+    hipLaunchKernelGGL(kern, plan.grid, plan.block, plan.lds, stream, p);
     return hipGetLastError();
 }
 
 }  // namespace
-
-bool cosine_small_form(int n_ref, int n_cur, int dim, bool nearby, bool small_off) {
-    if (small_off) {  // FTK_COSINE_SMALL=0 (experiment switch of the context)
-        return false;
-    }
-    const bool fits = n_ref <= kCosineSmallRefMax && n_cur <= (nearby ? kCosineSmallCurNearby : kCosineSmallCurForce);
-    return (dim == 64 || dim == 128 || dim == 256) && fits;
-}
 
 size_t cosine_rr_lds_bytes(int dim_pad) {
     (void)dim_pad;  // the tile buffers are static arrays of the kernel instance
     return sizeof(uint32_t) * (kRrRows + 3 * kRrStageCap + kRrListCap + 40);
 }
 
-hipError_t cosine_match_launch(const CosineParams &p, hipStream_t stream) {
-    if (p.n_ref <= 0 || p.n_cur <= 0) {
-        return hipSuccess;
-    }
-    if (cosine_small_form(p.n_ref, p.n_cur, p.dim, p.pred_uv != nullptr, p.small_off != 0)) {
+hipError_t cosine_match_launch(const CosinePlan &plan, const CosineParams &p, hipStream_t stream) {
+    const bool nearby = p.pred_uv != nullptr;
+#define FTK_NEARBY_LAUNCH(KERNEL, ...)                                                              \
+    do {                                                                                            \
+        if (nearby) {                                                                               \
+            hipLaunchKernelGGL((KERNEL<__VA_ARGS__, true>), plan.grid, plan.block, plan.lds, stream, p);  \
+        } else {                                                                                    \
+            hipLaunchKernelGGL((KERNEL<__VA_ARGS__, false>), plan.grid, plan.block, plan.lds, stream, p); \
+        }                                                                                           \
+    } while (0)
+    if (plan.form == CosineForm::Small) {
         switch (p.dim) {
-            case 64: return cosine_launch_small<8>(p, stream);
-            case 128: return cosine_launch_small<16>(p, stream);
-            default: return cosine_launch_small<32>(p, stream);
+            case 64: FTK_NEARBY_LAUNCH(cosine_match_small_kernel, 8); break;
+            case 128: FTK_NEARBY_LAUNCH(cosine_match_small_kernel, 16); break;
+            default: FTK_NEARBY_LAUNCH(cosine_match_small_kernel, 32); break;
         }
+        return hipGetLastError();
     }
     hipError_t e = hipMemsetAsync(p.clear_begin, 0, p.clear_bytes, stream);  // key 0 = "no candidate yet", counts 0
     if (e != hipSuccess) {
         return e;
     }
     // both operands in one launch: blockIdx.y selects ref / cur
-    const bool packets = (p.dim % 8) == 0 && ((reinterpret_cast<uintptr_t>(p.ref) | reinterpret_cast<uintptr_t>(p.cur)) & 15u) == 0;
-    {
-        const int rows = p.n_ref_pad > p.n_cur_pad ? p.n_ref_pad : p.n_cur_pad;
-        if (packets) {
-            hipLaunchKernelGGL(cosine_prep_pair_kernel, dim3((unsigned)((rows * 2 + 255) / 256), 2u), dim3(256), 0, stream, p);
-        } else {
-            hipLaunchKernelGGL(cosine_prep_kernel, dim3((unsigned)((rows * 8 + 255) / 256), 2u), dim3(256), 0, stream, p);
-        }
+    if (plan.packet_prep) {
+        hipLaunchKernelGGL(cosine_prep_pair_kernel, plan.prep_grid, dim3(256), 0, stream, p);
+    } else {
+        hipLaunchKernelGGL(cosine_prep_kernel, plan.prep_grid, dim3(256), 0, stream, p);
     }
-    if (p.ref_stationary) {
-        if (p.pred_uv && p.tile_box && !packets) {  // the packet-wide prep kernel has written the boxes itself
-            hipLaunchKernelGGL(cosine_tile_box_kernel, dim3((unsigned)(p.n_cur_pad / kRrTile)), dim3(64), 0, stream, p);
-        }
-        const dim3 grid((unsigned)((p.n_ref_pad / kRrRows) * p.splits));
-        const size_t lds = cosine_rr_lds_bytes(p.dim_pad);
-#define FTK_GEMM_LAUNCH(KSTEPS, NEARBY)                                                                                           \
-    do {                                                                                                                            \
-        auto kern = cosine_gemm_rr_kernel<KSTEPS, NEARBY>;                                                                          \
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);        \
-        if (e != hipSuccess) {                                                                                                      \
-            return e;                                                                                                               \
-        }                                                                                                                           \
-        hipLaunchKernelGGL(kern, grid, dim3(512), lds, stream, p);                                                                  \
-    } while (0)
-#define FTK_GEMM_DISPATCH(KSTEPS)           \
-    do {                                    \
-        if (p.pred_uv) {                    \
-            FTK_GEMM_LAUNCH(KSTEPS, true);  \
-        } else {                            \
-            FTK_GEMM_LAUNCH(KSTEPS, false); \
-        }                                   \
-    } while (0)
+    if (plan.box_grid.x > 0) {  // (the packet-wide prep kernel writes the boxes itself)
+        hipLaunchKernelGGL(cosine_tile_box_kernel, plan.box_grid, dim3(64), 0, stream, p);
+    }
+    if (plan.form == CosineForm::RegisterStationary) {
         switch (p.dim_pad / 16) {
-            case 4: FTK_GEMM_DISPATCH(4); break;
-            case 8: FTK_GEMM_DISPATCH(8); break;
-            case 12: FTK_GEMM_DISPATCH(12); break;
-            case 16: FTK_GEMM_DISPATCH(16); break;
+            case 4: e = launch_rr<4>(plan, p, stream); break;
+            case 8: e = launch_rr<8>(plan, p, stream); break;
+            case 12: e = launch_rr<12>(plan, p, stream); break;
+            case 16: e = launch_rr<16>(plan, p, stream); break;
             default: return hipErrorInvalidValue;
         }
-#undef FTK_GEMM_DISPATCH
-#undef FTK_GEMM_LAUNCH
-    } else {
-        const int tiles_total = p.n_cur_pad / kTile;
-        const int splits = (tiles_total + p.tiles_per_split - 1) / p.tiles_per_split;
-        const dim3 grid((unsigned)(p.n_ref_pad / kTile), (unsigned)splits);
-        if (p.pred_uv) {
-            hipLaunchKernelGGL((cosine_gemm_kernel<false, true>), grid, dim3(256), 0, stream, p);
-            hipLaunchKernelGGL((cosine_gemm_kernel<true, true>), grid, dim3(256), 0, stream, p);
-        } else {
-            hipLaunchKernelGGL((cosine_gemm_kernel<false, false>), grid, dim3(256), 0, stream, p);
-            hipLaunchKernelGGL((cosine_gemm_kernel<true, false>), grid, dim3(256), 0, stream, p);
+        if (e != hipSuccess) {
+            return e;
         }
+    } else {  // the maximum-then-collect pair of launches
+        FTK_NEARBY_LAUNCH(cosine_gemm_kernel, false);
+        FTK_NEARBY_LAUNCH(cosine_gemm_kernel, true);
     }
-    hipLaunchKernelGGL(cosine_recheck_kernel, dim3((unsigned)((p.n_ref * 8 + 255) / 256)), dim3(256), 0, stream, p);
+#undef FTK_NEARBY_LAUNCH
+    hipLaunchKernelGGL(cosine_recheck_kernel, plan.recheck_grid, dim3(256), 0, stream, p);
     return hipGetLastError();
 }
 

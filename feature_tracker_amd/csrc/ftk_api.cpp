@@ -16,6 +16,7 @@
 
 #include "ftk_device.h"
 #include "ftk_internal.h"
+#include "match_plan.h"
 
 using ftk::DevImage;
 
@@ -140,22 +141,6 @@ int ensure_match_boxes(ftk_context *ctx, size_t count) {
     return FTK_OK;
 }
 
-int ensure_cosine_ws(ftk_context *ctx, size_t bytes) {
-    if (bytes <= ctx->cosine_ws_bytes) {
-        return FTK_OK;
-    }
-    if (ctx->cosine_ws) {
-        FTK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        FTK_HIP(ctx, hipFree(ctx->cosine_ws));
-        ctx->cosine_ws = nullptr;
-        ctx->cosine_ws_bytes = 0;
-    }
-    const size_t want = align_up(bytes + bytes / 4, 4096);
-    FTK_HIP(ctx, hipMalloc(&ctx->cosine_ws, want));
-    ctx->cosine_ws_bytes = want;
-    return FTK_OK;
-}
-
 }  // namespace
 
 // Grows a context-owned device buffer (stream-synchronising first: earlier launches may still read the old one).
@@ -176,15 +161,6 @@ int ftk_ensure_device_buffer(ftk_context *ctx, void **buf, size_t *have, size_t 
 }
 
 namespace {
-
-// Direct method: a batch is spread over the chip (1 + NP workgroups per problem) while at least two producer workgroups per problem
-// fit beside the others (NP = 32 for up to six problems, then what the 224 usable workgroups of a whole MI355X allow).  Round 5, same box,
-// batches of 300 points x 13 x 13 x 4 levels, spread / one workgroup per problem, ms: 1 problem 1.01 / 1.81,
-// 6: 1.05 / 1.85, 12: 1.11 / 1.85, 24 (NP 8): 1.16 / 1.86, 32 (6): 1.21 / 1.86, 44 (4): 1.30 / 1.87, 56 (3): 1.41 / 1.89, 64 (2): 1.39 /
-// 1.89, 74 (2): 1.54 / 1.88, 100 (1): 2.03 / 1.93 — one producer workgroup does not keep up with its consumer's chain, two do
-// (profiles/r5_direct_spread_consumer.txt).  Beyond that one workgroup per problem IS the fast form, and its time is one problem's.
-constexpr int kDirectSpreadMaxProblems = 112;  // (two producers each no longer fit from 75 problems on a whole device: the fit decides)
-constexpr int kDirectSpreadMinProducers = 2;
 
 int ensure_device_buffer(ftk_context *ctx, void **buf, size_t *have, size_t bytes) { return ftk_ensure_device_buffer(ctx, buf, have, bytes); }
 
@@ -1026,7 +1002,83 @@ int ftk_harris_detect(ftk_context *ctx, const ftk_pyramid *image, int32_t level,
 
 /* ---- matcher ------------------------------------------------------------------------------- */
 
-static bool supported_words(int32_t n_words) { return n_words == 1 || n_words == 2 || n_words == 4 || n_words == 8 || n_words == 16; }
+extern "C++" {
+namespace {
+
+int env_int(const char *v) { return v ? atoi(v) : ftk::kPlanNotSet; }
+
+// Zero-pads the n_words-wide descriptors to `dev_words` words in a context-owned copy (equal pad bits in both sets: same distances).
+int pad_descriptors(ftk_context *ctx, const uint32_t **ref, int32_t n_ref, const uint32_t **cur, int32_t n_cur, int32_t n_words, int32_t dev_words) {
+    const size_t ref_bytes = align_up(sizeof(uint32_t) * (size_t)n_ref * dev_words, 256);
+    const size_t cur_bytes = align_up(sizeof(uint32_t) * (size_t)n_cur * dev_words, 256);
+    const int rc = ensure_device_buffer(ctx, &ctx->match_pad, &ctx->match_pad_bytes, ref_bytes + cur_bytes);
+    if (rc != FTK_OK) {
+        return rc;
+    }
+    uint32_t *pad_ref = static_cast<uint32_t *>(ctx->match_pad);
+    uint32_t *pad_cur = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(ctx->match_pad) + ref_bytes);
+    FTK_HIP(ctx, hipMemsetAsync(ctx->match_pad, 0, ref_bytes + cur_bytes, ctx->stream));
+    FTK_HIP(ctx, hipMemcpy2DAsync(pad_ref, sizeof(uint32_t) * dev_words, *ref, sizeof(uint32_t) * n_words, sizeof(uint32_t) * n_words, (size_t)n_ref,
+                                  hipMemcpyDeviceToDevice, ctx->stream));
+    FTK_HIP(ctx, hipMemcpy2DAsync(pad_cur, sizeof(uint32_t) * dev_words, *cur, sizeof(uint32_t) * n_words, sizeof(uint32_t) * n_words, (size_t)n_cur,
+                                  hipMemcpyDeviceToDevice, ctx->stream));
+    *ref = pad_ref;
+    *cur = pad_cur;
+    return FTK_OK;
+}
+
+// The host-buffer matchers: [ref | cur | pred | cur_uv | index] gathered in the context's pinned block, laid out like the device
+// scratch, and sent with ONE H2D (pageable hipMemcpyAsync calls are staged one by one by the runtime, ~10 us each; the reference's
+// callers time these calls); `run` launches the device entry on the scratch copies, then the indices come back.  Descriptor rows of
+// `row_bytes` are zero-padded to `dev_row_bytes` (pad bits equal in both sets: distance unchanged).
+template <class Run>
+int run_staged_match(ftk_context *ctx, const void *ref, int32_t n_ref, const void *cur, int32_t n_cur, size_t row_bytes, size_t dev_row_bytes,
+                     const float *pred_uv, const float *cur_uv, int32_t *index_pairs, Run run) {
+    FTK_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t ref_bytes = align_up(dev_row_bytes * (size_t)n_ref, 256);
+    const size_t cur_bytes = align_up(dev_row_bytes * (size_t)n_cur, 256);
+    const size_t pred_bytes = pred_uv ? align_up(sizeof(float) * 2 * (size_t)n_ref, 256) : 0;
+    const size_t cuv_bytes = pred_uv ? align_up(sizeof(float) * 2 * (size_t)n_cur, 256) : 0;
+    const size_t idx_at = ref_bytes + cur_bytes + pred_bytes + cuv_bytes, in_bytes = idx_at + align_up(sizeof(int32_t) * (size_t)n_ref, 256);
+    int rc = ftk_ensure_scratch(ctx, in_bytes);
+    rc = rc == FTK_OK ? ftk_ensure_pinned(ctx, in_bytes) : rc;
+    if (rc != FTK_OK) {
+        return rc;
+    }
+    uint8_t *base = static_cast<uint8_t *>(ctx->scratch), *hbase = static_cast<uint8_t *>(ctx->pinned);
+    if (dev_row_bytes == row_bytes) {
+        memcpy(hbase, ref, row_bytes * (size_t)n_ref);
+        memcpy(hbase + ref_bytes, cur, row_bytes * (size_t)n_cur);
+    } else {
+        memset(hbase, 0, ref_bytes + cur_bytes);
+        for (int32_t i = 0; i < n_ref; ++i) {
+            memcpy(hbase + dev_row_bytes * (size_t)i, static_cast<const uint8_t *>(ref) + row_bytes * (size_t)i, row_bytes);
+        }
+        for (int32_t i = 0; i < n_cur; ++i) {
+            memcpy(hbase + ref_bytes + dev_row_bytes * (size_t)i, static_cast<const uint8_t *>(cur) + row_bytes * (size_t)i, row_bytes);
+        }
+    }
+    if (pred_uv) {
+        memcpy(hbase + ref_bytes + cur_bytes, pred_uv, sizeof(float) * 2 * (size_t)n_ref);
+        memcpy(hbase + ref_bytes + cur_bytes + pred_bytes, cur_uv, sizeof(float) * 2 * (size_t)n_cur);
+    }
+    memcpy(hbase + idx_at, index_pairs, sizeof(int32_t) * (size_t)n_ref);
+    FTK_HIP(ctx, hipMemcpyAsync(base, hbase, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    int32_t *d_idx = reinterpret_cast<int32_t *>(base + idx_at);
+    rc = run(base, base + ref_bytes, pred_uv ? reinterpret_cast<float *>(base + ref_bytes + cur_bytes) : nullptr,
+             pred_uv ? reinterpret_cast<float *>(base + ref_bytes + cur_bytes + pred_bytes) : nullptr, d_idx);
+    if (rc != FTK_OK) {
+        (void)hipStreamSynchronize(ctx->stream);
+        return rc;
+    }
+    FTK_HIP(ctx, hipMemcpyAsync(hbase + idx_at, d_idx, sizeof(int32_t) * (size_t)n_ref, hipMemcpyDeviceToHost, ctx->stream));
+    FTK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    memcpy(index_pairs, hbase + idx_at, sizeof(int32_t) * (size_t)n_ref);
+    return FTK_OK;
+}
+
+}  // namespace
+}  // extern "C++"
 
 int ftk_hamming_match_device(ftk_context *ctx, const uint32_t *d_ref_words, int32_t n_ref, const uint32_t *d_cur_words, int32_t n_cur,
                              int32_t n_words, int32_t n_bits, float max_distance, const float *d_pred_uv, const float *d_cur_uv,
@@ -1051,111 +1103,20 @@ int ftk_hamming_match_device(ftk_context *ctx, const uint32_t *d_ref_words, int3
         return fail(ctx, FTK_E_INVALID_ARGUMENT, "hamming_match_device: null buffer");
     }
     FTK_HIP(ctx, hipSetDevice(ctx->device));
-    // The register-tiled scan exists for 1, 2, 4, 8 and 16 words per descriptor.  Other widths up to 16 words are
-    // zero-padded on the device into a context-owned copy (equal pad bits in both sets: same distances); wider
-    // descriptors take the generic scan (matcher_kernels.hip), which reads any width.  Same indices either way.
-    if (!supported_words(n_words) && n_words < 16) {
-        int dev_words = 1;
-        while (dev_words < n_words) {
-            dev_words *= 2;
-        }
-        const size_t ref_bytes = align_up(sizeof(uint32_t) * (size_t)n_ref * dev_words, 256);
-        const size_t cur_bytes = align_up(sizeof(uint32_t) * (size_t)n_cur * dev_words, 256);
-        const int rc = ensure_device_buffer(ctx, &ctx->match_pad, &ctx->match_pad_bytes, ref_bytes + cur_bytes);
-        if (rc != FTK_OK) {
-            return rc;
-        }
-        uint32_t *pad_ref = static_cast<uint32_t *>(ctx->match_pad);
-        uint32_t *pad_cur = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(ctx->match_pad) + ref_bytes);
-        FTK_HIP(ctx, hipMemsetAsync(ctx->match_pad, 0, ref_bytes + cur_bytes, ctx->stream));
-        FTK_HIP(ctx, hipMemcpy2DAsync(pad_ref, sizeof(uint32_t) * dev_words, d_ref_words, sizeof(uint32_t) * n_words, sizeof(uint32_t) * n_words,
-                                      (size_t)n_ref, hipMemcpyDeviceToDevice, ctx->stream));
-        FTK_HIP(ctx, hipMemcpy2DAsync(pad_cur, sizeof(uint32_t) * dev_words, d_cur_words, sizeof(uint32_t) * n_words, sizeof(uint32_t) * n_words,
-                                      (size_t)n_cur, hipMemcpyDeviceToDevice, ctx->stream));
-        d_ref_words = pad_ref;
-        d_cur_words = pad_cur;
-        n_words = dev_words;
+    const char *kernel = FTK_ENV(ctx, match_kernel);
+    const ftk::HammingPlan plan = ftk::hamming_plan({n_ref, n_cur, n_words, n_bits, d_pred_uv != nullptr, d_workspace != nullptr, env_int(FTK_ENV(ctx, match_small)),
+                                                     kernel ? (strcmp(kernel, "mfma") == 0 ? 1 : 0) : ftk::kPlanNotSet});
+    int rc = plan.dev_words != n_words ? pad_descriptors(ctx, &d_ref_words, n_ref, &d_cur_words, n_cur, n_words, plan.dev_words) : FTK_OK;
+    rc = rc == FTK_OK && plan.keys_clean ? ensure_match_keys(ctx, (size_t)n_ref) : rc;  // (the context's keys hold "no match")
+    rc = rc == FTK_OK && plan.n_boxes > 0 ? ensure_match_boxes(ctx, plan.n_boxes) : rc;
+    if (rc != FTK_OK) {
+        return rc;
     }
-    int p_keys_clean = 0;
-    unsigned long long *keys = reinterpret_cast<unsigned long long *>(d_workspace);
-    p_keys_clean = 0;
-    if (!keys) {
-        p_keys_clean = 1;
-        const int rc = ensure_match_keys(ctx, (size_t)n_ref);
-        if (rc != FTK_OK) {
-            return rc;
-        }
-        keys = ctx->match_keys;
-    }
-    ftk::MatchParams p;
-    p.keys_clean = p_keys_clean;
-    p.small_off = ftk_env::off(FTK_ENV(ctx, match_small)) ? 1 : 0;
-    p.ref_words = d_ref_words;
-    p.cur_words = d_cur_words;
-    p.pred_uv = d_pred_uv;
-    p.cur_uv = d_cur_uv;
-    p.index_pairs = d_index_pairs;
-    p.keys = keys;
-    p.n_ref = n_ref;
-    p.n_cur = n_cur;
-    p.n_words = n_words;
-    p.n_bits = n_bits;
-    p.max_distance = max_distance;
-    p.max_col = (float)max_col_distance;
-    p.max_row = (float)max_row_distance;
-    // Split the candidate range finely (a workgroup covers 512 reference descriptors — two per thread,
-    // matcher_kernels.hip — and as few as 64 candidates): measured at 10 000 x 10 000, 40 / 80 / 160
-    // splits take 85 / 74 / 69 us; the scan is pure VALU work and small workgroups even out the tail.
-    const int row_blocks = (n_ref + ftk::kMatchRowsPerBlock - 1) / ftk::kMatchRowsPerBlock;
-    int splits = (4096 + row_blocks - 1) / row_blocks;
-    const int max_splits = (n_cur + 63) / 64;
-    if (splits > max_splits) {
-        splits = max_splits;
-    }
-    if (splits < 1) {
-        splits = 1;
-    }
-    int per = (n_cur + splits - 1) / splits;
-    per = (per + 63) / 64 * 64;
-    p.matrix_cores = 0;
-    {
-        // Which scan: 256- and 512-bit descriptors go to the matrix cores (matcher_kernels.hip, hamming_match_mfma_kernel:
-        // faster at every size measured, 300 x 300 to 10 000 x 10 000); other widths to the popcount
-        // scan with the candidates on the scalar path.  FTK_MATCH_KERNEL=mfma|scalar forces one (experiment switch).
-        const char *env = FTK_ENV(ctx, match_kernel);
-        // (the matrix-core scan addresses the candidates with 32-bit byte offsets)
-        bool mfma = n_bits > 0 && (n_words == 8 || n_words == 16) && (long long)n_cur * n_words * 4 < (1ll << 31);
-        if (env) {
-            mfma = mfma && !strcmp(env, "mfma");
-        }
-        if (mfma) {
-            p.matrix_cores = 1;
-            // One wave per workgroup: 64 rows and one split of the candidates, in 32-candidate tiles.  Two waves fit a SIMD
-            // (registers): one round of at most 2048 waves, the splits whole tiles and as even as the tile count allows.
-            const int mfma_row_blocks = (n_ref + 63) / 64;
-            int mfma_splits = 2048 / mfma_row_blocks;
-            mfma_splits = mfma_splits < 1 ? 1 : mfma_splits;
-            const int n_tiles = (n_cur + 31) / 32;
-            int tiles_per_split = (n_tiles + mfma_splits - 1) / mfma_splits;
-            if (tiles_per_split > 1024) {
-                tiles_per_split = 1024;  // the position field of the running keys
-            }
-            per = tiles_per_split * 32;
-        }
-    }
-    p.cur_per_block = per;
-    // NearbyMatch from a few thousand candidates on: bounding boxes for the early exit of workgroups whose candidates
-    // cannot reach any window of their rows (matcher_kernels.hip)
-    p.boxes = nullptr;
-    if (d_pred_uv && n_bits > 0 && n_cur >= 2048) {
-        const size_t n_boxes = (size_t)row_blocks + (size_t)((n_cur + per - 1) / per);
-        const int rc = ensure_match_boxes(ctx, n_boxes);
-        if (rc != FTK_OK) {
-            return rc;
-        }
-        p.boxes = reinterpret_cast<float4 *>(ctx->match_boxes);
-    }
-    FTK_HIP(ctx, ftk::match_launch(p, ctx->stream));
+    unsigned long long *keys = plan.keys_clean ? ctx->match_keys : reinterpret_cast<unsigned long long *>(d_workspace);
+    const ftk::MatchParams p = {d_ref_words, d_cur_words, d_pred_uv, d_cur_uv, d_index_pairs, keys, n_ref, n_cur, plan.dev_words, n_bits, max_distance,
+                                (float)max_col_distance, (float)max_row_distance, plan.cur_per_block, plan.keys_clean, plan.matrix_cores,
+                                plan.n_boxes > 0 ? reinterpret_cast<float4 *>(ctx->match_boxes) : nullptr};
+    FTK_HIP(ctx, ftk::match_launch(plan, p, ctx->stream));
     return FTK_OK;
 }
 
@@ -1185,67 +1146,12 @@ int ftk_hamming_match(ftk_context *ctx, const uint32_t *ref_words, int32_t n_ref
     if (!ref_words || !cur_words || !index_pairs || (pred_uv && !cur_uv)) {
         return fail(ctx, FTK_E_INVALID_ARGUMENT, "hamming_match: null buffer");
     }
-    FTK_HIP(ctx, hipSetDevice(ctx->device));
-    int dev_words = 1;
-    while (dev_words < n_words && dev_words < 16) {
-        dev_words *= 2;
-    }
-    if (n_words > 16) {
-        dev_words = n_words;  // wider than any register-tiled instantiation: the generic scan reads the width as it is
-    }
-    const size_t ref_bytes = align_up(sizeof(uint32_t) * (size_t)n_ref * dev_words, 256);
-    const size_t cur_bytes = align_up(sizeof(uint32_t) * (size_t)n_cur * dev_words, 256);
-    const size_t pred_bytes = pred_uv ? align_up(sizeof(float) * 2 * (size_t)n_ref, 256) : 0;
-    const size_t cuv_bytes = pred_uv ? align_up(sizeof(float) * 2 * (size_t)n_cur, 256) : 0;
-    const size_t idx_bytes = align_up(sizeof(int32_t) * (size_t)n_ref, 256);
-    int rc = ftk_ensure_scratch(ctx, ref_bytes + cur_bytes + pred_bytes + cuv_bytes + idx_bytes);
-    if (rc != FTK_OK) {
-        return rc;
-    }
-    uint8_t *base = static_cast<uint8_t *>(ctx->scratch);
-    uint32_t *d_ref = reinterpret_cast<uint32_t *>(base);
-    uint32_t *d_cur = reinterpret_cast<uint32_t *>(base + ref_bytes);
-    float *d_pred = pred_uv ? reinterpret_cast<float *>(base + ref_bytes + cur_bytes) : nullptr;
-    float *d_cuv = pred_uv ? reinterpret_cast<float *>(base + ref_bytes + cur_bytes + pred_bytes) : nullptr;
-    int32_t *d_idx = reinterpret_cast<int32_t *>(base + ref_bytes + cur_bytes + pred_bytes + cuv_bytes);
-    // One H2D per call: the inputs are gathered in the context's pinned block, laid out like the device scratch (pageable
-    // hipMemcpyAsync calls are staged one by one by the runtime, ~10 us each; the reference's callers time this call).
-    const size_t in_bytes = ref_bytes + cur_bytes + pred_bytes + cuv_bytes + idx_bytes;
-    rc = ftk_ensure_pinned(ctx, in_bytes);
-    if (rc != FTK_OK) {
-        return rc;
-    }
-    uint8_t *hbase = static_cast<uint8_t *>(ctx->pinned);
-    if (dev_words == n_words) {
-        memcpy(hbase, ref_words, sizeof(uint32_t) * (size_t)n_ref * n_words);
-        memcpy(hbase + ref_bytes, cur_words, sizeof(uint32_t) * (size_t)n_cur * n_words);
-    } else {
-        // zero-pad each descriptor to the next supported width (pad bits are equal in both sets -> distance unchanged)
-        memset(hbase, 0, ref_bytes + cur_bytes);
-        for (int32_t i = 0; i < n_ref; ++i) {
-            memcpy(hbase + sizeof(uint32_t) * (size_t)i * dev_words, ref_words + (size_t)i * n_words, sizeof(uint32_t) * n_words);
-        }
-        for (int32_t i = 0; i < n_cur; ++i) {
-            memcpy(hbase + ref_bytes + sizeof(uint32_t) * (size_t)i * dev_words, cur_words + (size_t)i * n_words, sizeof(uint32_t) * n_words);
-        }
-    }
-    if (pred_uv) {
-        memcpy(hbase + ref_bytes + cur_bytes, pred_uv, sizeof(float) * 2 * (size_t)n_ref);
-        memcpy(hbase + ref_bytes + cur_bytes + pred_bytes, cur_uv, sizeof(float) * 2 * (size_t)n_cur);
-    }
-    uint8_t *h_idx = hbase + ref_bytes + cur_bytes + pred_bytes + cuv_bytes;
-    memcpy(h_idx, index_pairs, sizeof(int32_t) * (size_t)n_ref);
-    FTK_HIP(ctx, hipMemcpyAsync(base, hbase, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-    rc = ftk_hamming_match_device(ctx, d_ref, n_ref, d_cur, n_cur, dev_words, n_bits, max_distance, d_pred, d_cuv, max_col_distance,
-                                  max_row_distance, d_idx, nullptr);
-    if (rc != FTK_OK) {
-        (void)hipStreamSynchronize(ctx->stream);
-        return rc;
-    }
-    FTK_HIP(ctx, hipMemcpyAsync(h_idx, d_idx, sizeof(int32_t) * (size_t)n_ref, hipMemcpyDeviceToHost, ctx->stream));
-    FTK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    memcpy(index_pairs, h_idx, sizeof(int32_t) * (size_t)n_ref);
-    return FTK_OK;
+    const int32_t dev_words = ftk::hamming_device_words(n_words);  // padded on the host, during the gather
+    return run_staged_match(ctx, ref_words, n_ref, cur_words, n_cur, sizeof(uint32_t) * n_words, sizeof(uint32_t) * dev_words, pred_uv, cur_uv, index_pairs,
+                            [&](uint8_t *d_ref, uint8_t *d_cur, float *d_pred, float *d_cuv, int32_t *d_idx) {
+                                return ftk_hamming_match_device(ctx, reinterpret_cast<uint32_t *>(d_ref), n_ref, reinterpret_cast<uint32_t *>(d_cur), n_cur,
+                                                                dev_words, n_bits, max_distance, d_pred, d_cuv, max_col_distance, max_row_distance, d_idx, nullptr);
+                            });
 }
 
 /* ---- diagnostics ---------------------------------------------------------------------------- */
@@ -1293,23 +1199,12 @@ void ftk_default_direct_options(ftk_direct_options *opt) {
     opt->method = FTK_METHOD_DIRECT;
 }
 
-int ftk_direct_track_batch_device(ftk_context *ctx, const ftk_direct_options *opt, const ftk_direct_problem *problems, int32_t n_problems) {
-    if (!ctx) {
-        return fail(nullptr, FTK_E_INVALID_ARGUMENT, "direct_track: null context");
-    }
-    FTK_LOCK(ctx);
-    if (!opt || n_problems < 0 || (n_problems > 0 && !problems)) {
-        return fail(ctx, FTK_E_INVALID_ARGUMENT, "direct_track: null options / problems");
-    }
-    if (n_problems == 0) {
-        return FTK_OK;
-    }
-    if (opt->half_rows < 0 || opt->half_cols < 0 || opt->half_rows > 63 || opt->half_cols > 63) {
-        return fail(ctx, FTK_E_UNSUPPORTED, "direct_track: half patch size (%d, %d) outside [0, 63]", opt->half_rows, opt->half_cols);
-    }
-    std::vector<ftk::DirectProblem> host((size_t)n_problems);
-    uint32_t max_features = 0;
-    int32_t n_levels = 0;
+namespace {
+
+// The kernels' problem table from the caller's problems (checked here); *max_features: tracked features of the largest problem.
+int direct_problem_table(ftk_context *ctx, const ftk_direct_options *opt, const ftk_direct_problem *problems, int32_t n_problems,
+                         std::vector<ftk::DirectProblem> *table, uint32_t *max_features, int32_t *n_levels) {
+    table->resize((size_t)n_problems);
     for (int32_t k = 0; k < n_problems; ++k) {
         const ftk_direct_problem &in = problems[k];
         if (!in.ref || !in.cur || in.n < 0 || (in.n > 0 && (!in.d_p_c_in_ref || !in.d_ref_uv || !in.d_cur_uv || !in.d_status)) || !in.d_pose) {
@@ -1319,22 +1214,18 @@ int ftk_direct_track_batch_device(ftk_context *ctx, const ftk_direct_options *op
             return fail(ctx, FTK_E_INVALID_ARGUMENT, "direct_track: problem %d pyramid level mismatch (%d vs %d)", k, in.ref->n_levels, in.cur->n_levels);
         }
         if (k == 0) {
-            n_levels = in.ref->n_levels;
-        } else if (in.ref->n_levels != n_levels) {
+            *n_levels = in.ref->n_levels;
+        } else if (in.ref->n_levels != *n_levels) {
             return fail(ctx, FTK_E_UNSUPPORTED, "direct_track: all problems of a batch must share the pyramid depth");
         }
         if (in.ref->device != ctx->device || in.cur->device != ctx->device) {
             return fail(ctx, FTK_E_INVALID_ARGUMENT, "direct_track: pyramid lives on another device");
         }
-        ftk::DirectProblem &out = host[(size_t)k];
+        ftk::DirectProblem &out = (*table)[(size_t)k];
         memset(&out, 0, sizeof(out));
-        for (int i = 0; i < n_levels; ++i) {
-            out.ref[i] = in.ref->levels[i];
-            out.cur[i] = in.cur->levels[i];
-        }
-        for (int i = 0; i < 4; ++i) {
-            out.K[i] = in.K[i];
-        }
+        memcpy(out.ref, in.ref->levels, sizeof(DevImage) * (size_t)*n_levels);
+        memcpy(out.cur, in.cur->levels, sizeof(DevImage) * (size_t)*n_levels);
+        memcpy(out.K, in.K, sizeof(out.K));
         out.p_ref = in.d_p_c_in_ref;
         out.ref_uv = in.d_ref_uv;
         out.cur_uv = in.d_cur_uv;
@@ -1344,25 +1235,25 @@ int ftk_direct_track_batch_device(ftk_context *ctx, const ftk_direct_options *op
         out.n = in.n;
         out.status_valid = in.status_valid ? 1 : 0;
         const uint32_t tracked = ((uint32_t)in.n < opt->max_track_points) ? (uint32_t)in.n : opt->max_track_points;
-        max_features = std::max(max_features, tracked);
+        *max_features = std::max(*max_features, tracked);
     }
-    FTK_HIP(ctx, hipSetDevice(ctx->device));
-    // The per-feature table (an iteration's projections, a level's reference positions and Jacobians) lives in LDS while it fits
-    // beside the product ring (64 B per tracked feature, up to kDirectLdsFeatures); larger problems keep that table in a context-owned device buffer instead —
-    // same kernel, same arithmetic, same order of the sums.
-    const bool feat_in_global = max_features > ftk::kDirectLdsFeatures;
-    if (feat_in_global) {
-        const size_t per = align_up(sizeof(float) * 16 * (size_t)max_features, 256);
-        const int rc = ensure_device_buffer(ctx, &ctx->direct_feat, &ctx->direct_feat_bytes, per * (size_t)n_problems);
+    return FTK_OK;
+}
+
+// The problem table travels through a context-owned device buffer (separate from the scratch the host-buffer wrapper uses); with the
+// feature tables in device memory each problem gets its slice first.
+int upload_direct_table(ftk_context *ctx, const ftk::DirectPlan &plan, std::vector<ftk::DirectProblem> &table) {
+    const size_t n_problems = table.size();
+    if (plan.feat_in_global) {
+        const int rc = ensure_device_buffer(ctx, &ctx->direct_feat, &ctx->direct_feat_bytes, plan.feat_bytes * n_problems);
         if (rc != FTK_OK) {
             return rc;
         }
-        for (int32_t k = 0; k < n_problems; ++k) {
-            host[(size_t)k].feat = reinterpret_cast<float4 *>(static_cast<uint8_t *>(ctx->direct_feat) + per * (size_t)k);
+        for (size_t k = 0; k < n_problems; ++k) {
+            table[k].feat = reinterpret_cast<float4 *>(static_cast<uint8_t *>(ctx->direct_feat) + plan.feat_bytes * k);
         }
     }
-    // the problem table travels through a context-owned device buffer (separate from the scratch the host-buffer wrapper uses)
-    const size_t table_bytes = sizeof(ftk::DirectProblem) * (size_t)n_problems;
+    const size_t table_bytes = sizeof(ftk::DirectProblem) * n_problems;
     if (table_bytes > ctx->direct_table_bytes) {
         if (ctx->direct_table) {
             FTK_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1373,93 +1264,79 @@ int ftk_direct_track_batch_device(ftk_context *ctx, const ftk_direct_options *op
         FTK_HIP(ctx, hipMalloc(&ctx->direct_table, align_up(table_bytes, 4096)));
         ctx->direct_table_bytes = align_up(table_bytes, 4096);
     }
-    // pageable host -> device copy: synchronous with respect to the host buffer, so `host` may go out of scope
-    FTK_HIP(ctx, hipMemcpyAsync(ctx->direct_table, host.data(), table_bytes, hipMemcpyHostToDevice, ctx->stream));
+    // pageable host -> device copy: synchronous with respect to the host buffer, so `table` may go out of scope
+    FTK_HIP(ctx, hipMemcpyAsync(ctx->direct_table, table.data(), table_bytes, hipMemcpyHostToDevice, ctx->stream));
     FTK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ftk::DirectParams p;
-    p.problems = static_cast<const ftk::DirectProblem *>(ctx->direct_table);
-    p.tree = ctx->reduction == FTK_REDUCTION_TREE ? 1 : 0;
-    p.n_levels = n_levels;
-    p.max_track_points = opt->max_track_points;
-    p.max_iteration = opt->max_iteration;
-    p.half_rows = opt->half_rows;
-    p.half_cols = opt->half_cols;
-    p.patch_rows = 2 * opt->half_rows + 1;
-    p.patch_cols = 2 * opt->half_cols + 1;
-    p.converge = opt->max_converge_step;
-    p.method = opt->method;
-    // ONE problem (or a handful: a stereo pair, a small rig) with enough terms: spread over the chip (direct_track_spread_kernel) — the
-    // one-workgroup kernel is bound by what a single compute unit can issue per iteration.  Exact sums only; FTK_DIRECT_SPREAD=0 keeps
-    // the one-workgroup kernel, =n sets the number of producer workgroups per problem (default 32).  Larger batches fill the chip with
-    // one workgroup per problem.
-    p.spread = 0;
-    p.spread_ws = nullptr;
-    p.spread_ws_words = 0;
-    p.spread_poison = ftk_env::on(FTK_ENV(ctx, direct_spread_poison)) ? 1 : 0;
-    ctx->direct_spread_launched = 0;
-    {
-        const char *env = FTK_ENV(ctx, direct_spread);
-        int producers = env ? atoi(env) : 32;
-        producers = producers < 0 ? 0 : (producers > 200 ? 200 : producers);
-        const long long terms = (long long)max_features * p.patch_rows * p.patch_cols;
-        long long min_terms = 64ll * 256;  // below about 256 chunks the producers of one compute unit keep up with the chain
-        if (const char *min_env = FTK_ENV(ctx, direct_spread_min_terms)) {
-            min_terms = atoll(min_env);  // tests: spread even tiny problems (producers whose waves own no chunk)
-        }
-        bool spread = producers > 0 && !ctx->direct_spread_off && n_problems <= kDirectSpreadMaxProblems && !p.tree && opt->method == FTK_METHOD_DIRECT && !feat_in_global &&
-                      max_features > 0 && terms >= min_terms && terms < (1ll << 31);
-        if (spread) {
-            // Every workgroup of the launch must be resident at once (consumer and producers wait for each other): size the producers from
-            // what THIS device holds — occupancy of the kernel as launched x its compute units (256 on a whole MI355X, 32 on a CPX partition),
-            // an eighth left free for whatever else runs — and keep the one-workgroup kernel when fewer than 1 + 2 fit per problem.
-            if (ctx->direct_spread_resident < 0 || ctx->direct_spread_resident_features != max_features) {
-                ctx->direct_spread_resident = ftk::direct_spread_resident_groups(max_features, ctx->device);
-                ctx->direct_spread_resident_features = max_features;
-            }
-            int resident = ctx->direct_spread_resident;
-            if (const char *cap_env = FTK_ENV(ctx, direct_spread_resident)) {
-                resident = std::min(resident, atoi(cap_env));  // tests: pretend to be a small partition
-            }
-            const int usable = resident - resident / 8;
-            const int fit = usable / n_problems - 1;
-            producers = std::min(producers, fit);
-            spread = producers >= kDirectSpreadMinProducers || (env && producers >= 1 && producers == std::min(atoi(env), fit));  // (an explicit FTK_DIRECT_SPREAD=n that fits is honoured: tests)
-        }
-        size_t ws = 0;
-        if (spread) {
-            // Workspace: [chunk][7][64] values per problem (the Jacobian row and the residual of every term).  Not beyond 512 MB in total
-            // (127 x 127 patches x 768 features would be 347 MB per problem: two such problems keep the one-workgroup kernel), word
-            // offsets must fit 32 bits, and a buffer that would have
-            // to GROW while the stream is being captured is an error the caller can act on, not a hipMalloc inside the capture.
-            ws = align_up(ftk::direct_spread_ws_bytes(max_features, p.patch_rows, p.patch_cols), 256);
-            if (ws / sizeof(uint32_t) > 0xFFFFFFFFull || ws * (size_t)n_problems > (512ull << 20)) {
-                spread = false;
-            }
-        }
-        if (spread && ws * (size_t)n_problems > ctx->direct_spread_bytes) {
-            hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-            if (hipStreamIsCapturing(ctx->stream, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) {
-                spread = false;  // the one-workgroup kernel needs no workspace: same result, capturable
-            }
-        }
-        if (spread) {
-            const int rc = ensure_device_buffer(ctx, &ctx->direct_spread, &ctx->direct_spread_bytes, ws * (size_t)n_problems);
-            if (rc != FTK_OK) {
-                return rc;
-            }
-            for (int32_t k = 0; k < n_problems; ++k) {  // header + chunk flags of every problem: zero before the launch
-                FTK_HIP(ctx, hipMemsetAsync(static_cast<uint8_t *>(ctx->direct_spread) + ws * (size_t)k, 0,
-                                            ftk::direct_spread_clear_bytes(max_features, p.patch_rows, p.patch_cols), ctx->stream));
-            }
-            p.spread = producers;
-            p.spread_ws = static_cast<uint32_t *>(ctx->direct_spread);
-            p.spread_ws_words = (uint32_t)(ws / sizeof(uint32_t));
-            ctx->direct_spread_launched = n_problems;
-            ctx->direct_spread_stride = ws;
-        }
-    }
-    FTK_HIP(ctx, ftk::direct_track_launch(p, n_problems, feat_in_global ? 0u : max_features, ctx->stream));
     return FTK_OK;
+}
+
+// ftk_direct_track_batch_device; spread_allowed = false: the re-run of a poisoned spread launch on one workgroup per problem.
+int direct_track_batch(ftk_context *ctx, const ftk_direct_options *opt, const ftk_direct_problem *problems, int32_t n_problems, bool spread_allowed) {
+    if (!opt || n_problems < 0 || (n_problems > 0 && !problems)) {
+        return fail(ctx, FTK_E_INVALID_ARGUMENT, "direct_track: null options / problems");
+    }
+    if (n_problems == 0) {
+        return FTK_OK;
+    }
+    if (opt->half_rows < 0 || opt->half_cols < 0 || opt->half_rows > 63 || opt->half_cols > 63) {
+        return fail(ctx, FTK_E_UNSUPPORTED, "direct_track: half patch size (%d, %d) outside [0, 63]", opt->half_rows, opt->half_cols);
+    }
+    std::vector<ftk::DirectProblem> table;
+    uint32_t max_features = 0;
+    int32_t n_levels = 0;
+    int rc = direct_problem_table(ctx, opt, problems, n_problems, &table, &max_features, &n_levels);
+    if (rc != FTK_OK) {
+        return rc;
+    }
+    FTK_HIP(ctx, hipSetDevice(ctx->device));
+    const bool resident_known = ctx->direct_spread_resident >= 0 && ctx->direct_spread_resident_features == max_features;
+    ftk::DirectPlanInput in = {n_problems, max_features, 2 * opt->half_rows + 1, 2 * opt->half_cols + 1, opt->method, ctx->reduction == FTK_REDUCTION_TREE,
+                               spread_allowed, resident_known ? ctx->direct_spread_resident : ftk::kPlanNotSet, ftk::kPlanNotSet, ctx->direct_spread_bytes,
+                               env_int(FTK_ENV(ctx, direct_spread)), env_int(FTK_ENV(ctx, direct_spread_resident)), env_int(FTK_ENV(ctx, direct_spread_poison)),
+                               FTK_ENV(ctx, direct_spread_min_terms) ? atoll(FTK_ENV(ctx, direct_spread_min_terms)) : ftk::kPlanNotSet};
+    ftk::DirectPlan plan = ftk::direct_plan(in);
+    rc = upload_direct_table(ctx, plan, table);
+    if (rc != FTK_OK) {
+        return rc;
+    }
+    if (plan.ask_resident) {  // the occupancy query, cached per feature count
+        ctx->direct_spread_resident = ftk::direct_spread_resident_groups(max_features, ctx->device);
+        ctx->direct_spread_resident_features = max_features;
+        in.resident = ctx->direct_spread_resident;
+        plan = ftk::direct_plan(in);
+    }
+    if (plan.ask_capturing) {  // the spread workspace would grow: not inside a stream capture
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        in.capturing = hipStreamIsCapturing(ctx->stream, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
+        plan = ftk::direct_plan(in);
+    }
+    ctx->direct_spread_launched = 0;
+    if (plan.producers > 0) {
+        rc = ensure_device_buffer(ctx, &ctx->direct_spread, &ctx->direct_spread_bytes, plan.ws_stride * (size_t)n_problems);
+        if (rc != FTK_OK) {
+            return rc;
+        }
+        for (int32_t k = 0; k < n_problems; ++k) {  // header + chunk flags of every problem: zero before the launch
+            FTK_HIP(ctx, hipMemsetAsync(static_cast<uint8_t *>(ctx->direct_spread) + plan.ws_stride * (size_t)k, 0, plan.clear_bytes, ctx->stream));
+        }
+        ctx->direct_spread_launched = n_problems;
+    }
+    const ftk::DirectParams p = {static_cast<const ftk::DirectProblem *>(ctx->direct_table), in.tree, n_levels, opt->max_track_points, opt->max_iteration,
+                                 opt->half_rows, opt->half_cols, in.patch_rows, in.patch_cols, opt->max_converge_step, opt->method, plan.producers,
+                                 plan.producers > 0 ? static_cast<uint32_t *>(ctx->direct_spread) : nullptr, (uint32_t)(plan.ws_stride / sizeof(uint32_t)),
+                                 plan.poison};
+    FTK_HIP(ctx, ftk::direct_track_launch(plan, p, ctx->stream));
+    return FTK_OK;
+}
+
+}  // namespace
+
+int ftk_direct_track_batch_device(ftk_context *ctx, const ftk_direct_options *opt, const ftk_direct_problem *problems, int32_t n_problems) {
+    if (!ctx) {
+        return fail(nullptr, FTK_E_INVALID_ARGUMENT, "direct_track: null context");
+    }
+    FTK_LOCK(ctx);
+    return direct_track_batch(ctx, opt, problems, n_problems, true);
 }
 
 int ftk_direct_track(ftk_context *ctx, const ftk_direct_options *opt, const ftk_pyramid *ref, const ftk_pyramid *cur, const float *K,
@@ -1495,28 +1372,24 @@ int ftk_direct_track(ftk_context *ctx, const ftk_direct_options *opt, const ftk_
     uint8_t *d_st = base + pts_bytes + 2 * uv_bytes;
     float *d_pose = reinterpret_cast<float *>(base + pts_bytes + 2 * uv_bytes + st_bytes);
     uint32_t *d_it = reinterpret_cast<uint32_t *>(base + pts_bytes + 2 * uv_bytes + st_bytes + 256);
-    float pose[7] = {q_rc_wxyz[0], q_rc_wxyz[1], q_rc_wxyz[2], q_rc_wxyz[3], p_rc[0], p_rc[1], p_rc[2]};
+    float pose[7];
+    auto upload_state = [&]() -> int {  // the in/out buffers: positions, statuses and the pose (`pose` is a stack buffer: synchronised)
+        memcpy(pose, q_rc_wxyz, sizeof(float) * 4);
+        memcpy(pose + 4, p_rc, sizeof(float) * 3);
+        FTK_HIP(ctx, hipMemcpyAsync(d_cur, cur_uv, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+        FTK_HIP(ctx, hipMemcpyAsync(d_st, status, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+        FTK_HIP(ctx, hipMemcpyAsync(d_pose, pose, sizeof(pose), hipMemcpyHostToDevice, ctx->stream));
+        FTK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return FTK_OK;
+    };
     FTK_HIP(ctx, hipMemcpyAsync(d_pts, p_c_in_ref, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
     FTK_HIP(ctx, hipMemcpyAsync(d_ref, ref_uv, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    FTK_HIP(ctx, hipMemcpyAsync(d_cur, cur_uv, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    FTK_HIP(ctx, hipMemcpyAsync(d_st, status, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    FTK_HIP(ctx, hipMemcpyAsync(d_pose, pose, sizeof(pose), hipMemcpyHostToDevice, ctx->stream));
-    FTK_HIP(ctx, hipStreamSynchronize(ctx->stream));  // `pose` is a stack buffer
-    ftk_direct_problem prob;
-    prob.ref = ref;
-    prob.cur = cur;
-    for (int i = 0; i < 4; ++i) {
-        prob.K[i] = K[i];
+    rc = upload_state();
+    if (rc != FTK_OK) {
+        return rc;
     }
-    prob.d_p_c_in_ref = d_pts;
-    prob.d_ref_uv = d_ref;
-    prob.d_cur_uv = d_cur;
-    prob.n = n;
-    prob.d_pose = d_pose;
-    prob.d_status = d_st;
-    prob.status_valid = status_valid;
-    prob.d_iterations = d_it;
-    rc = ftk_direct_track_batch_device(ctx, opt, &prob, 1);
+    const ftk_direct_problem prob = {ref, cur, {K[0], K[1], K[2], K[3]}, d_pts, d_ref, d_cur, n, d_pose, d_st, status_valid, d_it};
+    rc = direct_track_batch(ctx, opt, &prob, 1, true);
     if (rc != FTK_OK) {
         (void)hipStreamSynchronize(ctx->stream);
         return rc;
@@ -1529,19 +1402,8 @@ int ftk_direct_track(ftk_context *ctx, const ftk_direct_options *opt, const ftk_
         FTK_HIP(ctx, hipMemcpyAsync(&poisoned, static_cast<uint32_t *>(ctx->direct_spread) + 1, sizeof(poisoned), hipMemcpyDeviceToHost, ctx->stream));
         FTK_HIP(ctx, hipStreamSynchronize(ctx->stream));
         if (poisoned != 0) {
-            FTK_HIP(ctx, hipMemcpyAsync(d_cur, cur_uv, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-            FTK_HIP(ctx, hipMemcpyAsync(d_st, status, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-            for (int i = 0; i < 4; ++i) {
-                pose[i] = q_rc_wxyz[i];
-            }
-            for (int i = 0; i < 3; ++i) {
-                pose[4 + i] = p_rc[i];
-            }
-            FTK_HIP(ctx, hipMemcpyAsync(d_pose, pose, sizeof(pose), hipMemcpyHostToDevice, ctx->stream));
-            FTK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            ctx->direct_spread_off = true;
-            rc = ftk_direct_track_batch_device(ctx, opt, &prob, 1);
-            ctx->direct_spread_off = false;
+            rc = upload_state();
+            rc = rc == FTK_OK ? direct_track_batch(ctx, opt, &prob, 1, false) : rc;
             if (rc != FTK_OK) {
                 (void)hipStreamSynchronize(ctx->stream);
                 return rc;
@@ -1557,12 +1419,8 @@ int ftk_direct_track(ftk_context *ctx, const ftk_direct_options *opt, const ftk_
     FTK_HIP(ctx, hipMemcpyAsync(pose, d_pose, sizeof(pose), hipMemcpyDeviceToHost, ctx->stream));
     FTK_HIP(ctx, hipMemcpyAsync(&it, d_it, sizeof(it), hipMemcpyDeviceToHost, ctx->stream));
     FTK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (int i = 0; i < 4; ++i) {
-        q_rc_wxyz[i] = pose[i];
-    }
-    for (int i = 0; i < 3; ++i) {
-        p_rc[i] = pose[4 + i];
-    }
+    memcpy(q_rc_wxyz, pose, sizeof(float) * 4);
+    memcpy(p_rc, pose + 4, sizeof(float) * 3);
     if (iterations) {
         *iterations = it;
     }
@@ -1591,95 +1449,23 @@ int ftk_cosine_match_device(ftk_context *ctx, const float *d_ref_desc, int32_t n
         return fail(ctx, FTK_E_INVALID_ARGUMENT, "cosine_match_device: null buffer");
     }
     FTK_HIP(ctx, hipSetDevice(ctx->device));
-    ftk::CosineParams p;
-    p.small_off = ftk_env::off(FTK_ENV(ctx, cosine_small)) ? 1 : 0;
-    p.ref = d_ref_desc;
-    p.cur = d_cur_desc;
-    p.pred_uv = d_pred_uv;
-    p.cur_uv = d_cur_uv;
-    p.index_pairs = d_index_pairs;
-    p.n_ref = n_ref;
-    p.n_cur = n_cur;
-    p.dim = dim;
-    p.dim_pad = (int32_t)align_up((size_t)dim, 64);
-    // dim <= 256 (SuperPoint, DISK): the ref fragments stay in registers for the whole walk over cur (cosine_gemm_rr_kernel,
-    // 512 ref rows per workgroup).  Longer descriptors, or FTK_COSINE_CHUNKED=1, use the chunked kernel.
-    const bool want_chunked = FTK_ENV(ctx, cosine_chunked) && atoi(FTK_ENV(ctx, cosine_chunked)) == 1;
-    p.ref_stationary = (p.dim_pad <= 256 && !want_chunked) ? 1 : 0;
-    const int cur_tile = p.ref_stationary ? 64 : 128;
-    const int row_group = p.ref_stationary ? 512 : 128;
-    p.n_ref_pad = (int32_t)align_up((size_t)n_ref, (size_t)row_group);
-    p.n_cur_pad = (int32_t)align_up((size_t)n_cur, (size_t)cur_tile);
-    p.max_distance = max_distance;
-    p.max_col = (float)max_col_distance;
-    p.max_row = (float)max_row_distance;
-    // Keep the whole grid co-resident in ONE round (on-chip ref: one workgroup per CU -> <= 256; chunked: two per
-    // CU -> <= 512), each workgroup walking a contiguous run of cur tiles: a second, partly filled round costs more
-    // than slightly longer runs.
-    const int row_tiles = p.n_ref_pad / row_group, tiles_total = p.n_cur_pad / cur_tile;
-    int splits = (p.ref_stationary ? 256 : 512) / row_tiles;
-    if (const char *env = FTK_ENV(ctx, cosine_splits)) {
-        splits = atoi(env);  // experiment override
-    }
-    splits = std::max(1, std::min(splits, tiles_total));
-    if (p.ref_stationary && !FTK_ENV(ctx, cosine_splits)) {
-        // At least TWO tiles per split: a walk's first step has no running maximum to cut against yet, so it lists its whole share
-        // of every row; with one-tile splits that is all there is, the rows' lists overflow (kCosineCandCap) and the recheck falls
-        // back to the exact scan of every pair — 2 000 x 2 000 x 256: 32 splits 17.6 + 3 591 us (contraction + recheck), 16 splits
-        // 20.2 + 11.8 us; 1 000 x 1 000 x 128: 16 splits 11.4 + 1 099 us, 8 splits 14.1 + 7.6 us (rocprofv3 kernel trace).
-        splits = std::max(1, std::min(splits, tiles_total / 2));
-    }
-    p.splits = splits;
-    p.tiles_per_split = (tiles_total + splits - 1) / splits;
-    // workspace carve-up (every region 256-byte aligned)
-    size_t off = 0;
-    auto carve = [&off](size_t bytes) {
-        const size_t at = off;
-        off += align_up(bytes, 256);
-        return at;
-    };
-    const size_t o_ref_h = carve(sizeof(uint16_t) * (size_t)p.n_ref_pad * p.dim_pad);
-    const size_t o_cur_h = carve(sizeof(uint16_t) * (size_t)p.n_cur_pad * p.dim_pad);
-    const size_t o_ref_norm = carve(sizeof(float) * (size_t)p.n_ref_pad);
-    const size_t o_cur_norm = carve(sizeof(float) * (size_t)p.n_cur_pad);
-    const size_t o_cur_bias = carve(sizeof(float) * (size_t)p.n_cur_pad);
-    const size_t o_cur_info = carve(sizeof(float) * 4 * (size_t)p.n_cur_pad);
-    const size_t o_tile_box = carve(sizeof(float) * 4 * ((size_t)p.n_cur_pad / 64 + 1));
-    const size_t o_ref_irr = carve((size_t)p.n_ref_pad);
-    // row_max | cand_count | irregular_count are adjacent: ONE memset clears them (key 0 = "no candidate yet")
-    const size_t o_row_max = carve(sizeof(uint32_t) * (size_t)p.n_ref_pad);
-    const size_t o_cnt = carve(sizeof(uint32_t) * (size_t)p.n_ref_pad);
-    const size_t o_irr_cnt = carve(sizeof(uint32_t));
-    const size_t o_clear_end = off;
-    const size_t o_cand = carve(sizeof(int32_t) * (size_t)p.n_ref_pad * ftk::kCosineCandCap);
-    // the register-stationary kernel walks cur ONCE (running row maximum + scored candidate lists); the chunked kernel runs the
-    // maximum-then-collect pair of launches
-    const bool single_walk = p.ref_stationary != 0;
-    const size_t o_cand_score = single_walk ? carve(sizeof(float) * (size_t)p.n_ref_pad * ftk::kCosineCandCap) : 0;
-    const size_t o_irr_list = carve(sizeof(int32_t) * ftk::kCosineIrregularCap);
-    const int rc = ensure_cosine_ws(ctx, off);
+    const ftk::CosinePlanInput in = {n_ref, n_cur, dim, d_pred_uv != nullptr, ((reinterpret_cast<uintptr_t>(d_ref_desc) | reinterpret_cast<uintptr_t>(d_cur_desc)) & 15u) == 0,
+                                     env_int(FTK_ENV(ctx, cosine_small)), env_int(FTK_ENV(ctx, cosine_chunked)), env_int(FTK_ENV(ctx, cosine_splits))};
+    const ftk::CosinePlan plan = ftk::cosine_plan(in);
+    const int rc = ensure_device_buffer(ctx, &ctx->cosine_ws, &ctx->cosine_ws_bytes, plan.ws_bytes);
     if (rc != FTK_OK) {
         return rc;
     }
     uint8_t *ws = static_cast<uint8_t *>(ctx->cosine_ws);
-    p.ref_h = reinterpret_cast<_Float16 *>(ws + o_ref_h);
-    p.cur_h = reinterpret_cast<_Float16 *>(ws + o_cur_h);
-    p.ref_norm = reinterpret_cast<float *>(ws + o_ref_norm);
-    p.cur_norm = reinterpret_cast<float *>(ws + o_cur_norm);
-    p.cur_bias = reinterpret_cast<float *>(ws + o_cur_bias);
-    p.cur_info = reinterpret_cast<float4 *>(ws + o_cur_info);
-    // NearbyMatch tile lists (float_matcher_kernels.hip): worth their extra launch from a few thousand candidates on
-    p.tile_box = (d_pred_uv && p.n_cur_pad / 64 >= 32) ? reinterpret_cast<float4 *>(ws + o_tile_box) : nullptr;
-    p.ref_irregular = ws + o_ref_irr;
-    p.row_max = reinterpret_cast<uint32_t *>(ws + o_row_max);
-    p.cand_count = reinterpret_cast<uint32_t *>(ws + o_cnt);
-    p.cand = reinterpret_cast<int32_t *>(ws + o_cand);
-    p.cand_score = single_walk ? reinterpret_cast<float *>(ws + o_cand_score) : nullptr;
-    p.irregular_count = reinterpret_cast<uint32_t *>(ws + o_irr_cnt);
-    p.irregular_list = reinterpret_cast<int32_t *>(ws + o_irr_list);
-    p.clear_begin = ws + o_row_max;
-    p.clear_bytes = o_clear_end - o_row_max;
-    FTK_HIP(ctx, ftk::cosine_match_launch(p, ctx->stream));
+    auto at = [ws](size_t offset) { return reinterpret_cast<void *>(ws + offset); };
+    const ftk::CosineParams p = {d_ref_desc, d_cur_desc, d_pred_uv, d_cur_uv, d_index_pairs, (_Float16 *)at(plan.ref_h), (_Float16 *)at(plan.cur_h),
+                                 (float *)at(plan.ref_norm), (float *)at(plan.cur_norm), (float *)at(plan.cur_bias), (float4 *)at(plan.cur_info),
+                                 plan.use_tile_box ? (float4 *)at(plan.tile_box) : nullptr, ws + plan.ref_irregular, (uint32_t *)at(plan.row_max),
+                                 (uint32_t *)at(plan.cand_count), (int32_t *)at(plan.cand), plan.ref_stationary ? (float *)at(plan.cand_score) : nullptr,
+                                 (uint32_t *)at(plan.irregular_count), (int32_t *)at(plan.irregular_list), at(plan.row_max), plan.clear_end - plan.row_max,
+                                 n_ref, n_cur, dim, plan.n_ref_pad, plan.n_cur_pad, plan.dim_pad, plan.tiles_per_split, plan.ref_stationary, plan.splits,
+                                 max_distance, (float)max_col_distance, (float)max_row_distance};
+    FTK_HIP(ctx, ftk::cosine_match_launch(plan, p, ctx->stream));
     return FTK_OK;
 }
 
@@ -1709,47 +1495,11 @@ int ftk_cosine_match(ftk_context *ctx, const float *ref_desc, int32_t n_ref, con
     if (!ref_desc || !cur_desc || !index_pairs || (pred_uv && !cur_uv)) {
         return fail(ctx, FTK_E_INVALID_ARGUMENT, "cosine_match: null buffer");
     }
-    FTK_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t ref_bytes = align_up(sizeof(float) * (size_t)n_ref * dim, 256);
-    const size_t cur_bytes = align_up(sizeof(float) * (size_t)n_cur * dim, 256);
-    const size_t pred_bytes = pred_uv ? align_up(sizeof(float) * 2 * (size_t)n_ref, 256) : 0;
-    const size_t cuv_bytes = pred_uv ? align_up(sizeof(float) * 2 * (size_t)n_cur, 256) : 0;
-    const size_t idx_bytes = align_up(sizeof(int32_t) * (size_t)n_ref, 256);
-    int rc = ftk_ensure_scratch(ctx, ref_bytes + cur_bytes + pred_bytes + cuv_bytes + idx_bytes);
-    if (rc != FTK_OK) {
-        return rc;
-    }
-    uint8_t *base = static_cast<uint8_t *>(ctx->scratch);
-    float *d_ref = reinterpret_cast<float *>(base);
-    float *d_cur = reinterpret_cast<float *>(base + ref_bytes);
-    float *d_pred = pred_uv ? reinterpret_cast<float *>(base + ref_bytes + cur_bytes) : nullptr;
-    float *d_cuv = pred_uv ? reinterpret_cast<float *>(base + ref_bytes + cur_bytes + pred_bytes) : nullptr;
-    int32_t *d_idx = reinterpret_cast<int32_t *>(base + ref_bytes + cur_bytes + pred_bytes + cuv_bytes);
-    // one H2D per call through the pinned block (see ftk_hamming_match)
-    const size_t in_bytes = ref_bytes + cur_bytes + pred_bytes + cuv_bytes + idx_bytes;
-    rc = ftk_ensure_pinned(ctx, in_bytes);
-    if (rc != FTK_OK) {
-        return rc;
-    }
-    uint8_t *hbase = static_cast<uint8_t *>(ctx->pinned);
-    memcpy(hbase, ref_desc, sizeof(float) * (size_t)n_ref * dim);
-    memcpy(hbase + ref_bytes, cur_desc, sizeof(float) * (size_t)n_cur * dim);
-    if (pred_uv) {
-        memcpy(hbase + ref_bytes + cur_bytes, pred_uv, sizeof(float) * 2 * (size_t)n_ref);
-        memcpy(hbase + ref_bytes + cur_bytes + pred_bytes, cur_uv, sizeof(float) * 2 * (size_t)n_cur);
-    }
-    uint8_t *h_idx = hbase + ref_bytes + cur_bytes + pred_bytes + cuv_bytes;
-    memcpy(h_idx, index_pairs, sizeof(int32_t) * (size_t)n_ref);
-    FTK_HIP(ctx, hipMemcpyAsync(base, hbase, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-    rc = ftk_cosine_match_device(ctx, d_ref, n_ref, d_cur, n_cur, dim, max_distance, d_pred, d_cuv, max_col_distance, max_row_distance, d_idx);
-    if (rc != FTK_OK) {
-        (void)hipStreamSynchronize(ctx->stream);
-        return rc;
-    }
-    FTK_HIP(ctx, hipMemcpyAsync(h_idx, d_idx, sizeof(int32_t) * (size_t)n_ref, hipMemcpyDeviceToHost, ctx->stream));
-    FTK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    memcpy(index_pairs, h_idx, sizeof(int32_t) * (size_t)n_ref);
-    return FTK_OK;
+    return run_staged_match(ctx, ref_desc, n_ref, cur_desc, n_cur, sizeof(float) * dim, sizeof(float) * dim, pred_uv, cur_uv, index_pairs,
+                            [&](uint8_t *d_ref, uint8_t *d_cur, float *d_pred, float *d_cuv, int32_t *d_idx) {
+                                return ftk_cosine_match_device(ctx, reinterpret_cast<float *>(d_ref), n_ref, reinterpret_cast<float *>(d_cur), n_cur, dim,
+                                                               max_distance, d_pred, d_cuv, max_col_distance, max_row_distance, d_idx);
+                            });
 }
 
 /* ---- dense optical flow (Farneback) ------------------------------------------------------------ */

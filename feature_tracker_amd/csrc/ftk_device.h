@@ -9,6 +9,8 @@
 
 namespace ftk {
 
+constexpr int kWave = 64;  // lanes of a wavefront
+
 // Floats per pixel group (4 pixels x 24 sums + one float4 of padding) of the non-fast affine variants' product layout
 // (klt_kernels.hip affine_all_terms); the host sizes KltParams::terms_floats with it.
 constexpr int kAffineTermsGroupFloats = 4 * 24 + 4;
@@ -152,8 +154,18 @@ hipError_t ldlt6_launch(const float *d_a, const float *d_b, float *d_x, int n, h
 
 // Reference descriptors a thread of the register-tiled Hamming scan keeps in registers (a 256-thread workgroup covers
 // 256 * kMatchRefs reference rows); the host sizes its grid and its NearbyMatch boxes with the same number.
+constexpr int kMatchBlock = 256;  // threads of every Hamming-matcher workgroup except the matrix-core scan's one wave
 constexpr int kMatchRefs = 2;
-constexpr int kMatchRowsPerBlock = 256 * kMatchRefs;
+constexpr int kMatchRowsPerBlock = kMatchBlock * kMatchRefs;
+constexpr int kMfmaRows = 64;  // reference rows per workgroup of the matrix-core scan: ONE wave (nothing is shared, so nothing is
+                               // gained by larger groups, and single waves pack the SIMDs' two slots evenly)
+constexpr int kMfmaTile = 32;  // candidates per tile of the matrix-core scan (one v_mfma_i32_32x32x32_i8)
+constexpr int kMfmaMaxTilesPerSplit = 1024;  // the position field of the matrix-core scan's running keys
+// The one-launch form (hamming_match_small_kernel) up to n_ref * n_cur * n_words = kSmallMatchWork while a row's walk stays at or below
+// n_cur * n_words = kSmallMatchRowWork; the packed key holds the candidate in 20 bits, kSmallNoIndex = "none"
+constexpr long long kSmallMatchWork = 32ll << 20;
+constexpr int kSmallMatchRowWork = 24576;
+constexpr int kSmallNoIndex = 0xFFFFF;
 
 struct MatchParams {
     const uint32_t *ref_words;
@@ -170,15 +182,21 @@ struct MatchParams {
     int32_t matrix_cores;   // 1: the scan on the matrix cores (hamming_match_mfma_kernel; n_words 8 / 16)
     float4 *boxes;          // NearbyMatch, optional: ceil(n_ref / 512) prediction boxes, then one candidate box per split
                             // ({u min, u max, v min, v max}; hamming_box_kernel fills them, the scan leaves early on them)
-    int32_t small_off;      // experiment (FTK_MATCH_SMALL=0, read once per context): never the one-launch form
 };
-hipError_t match_launch(const MatchParams &p, hipStream_t stream);
-// Whether match_launch runs a call of this shape as ONE launch without the keys workspace or the NearbyMatch boxes (small calls).
-bool match_small_form(int n_ref, int n_cur, int n_words, int n_bits, bool small_off);
+struct HammingPlan;
+hipError_t match_launch(const HammingPlan &plan, const MatchParams &p, hipStream_t stream);
 
 // Float-descriptor (cosine distance) matcher: float_matcher_kernels.hip.
 constexpr int kCosineCandCap = 64;       // candidates kept per ref row before the row falls back to the exact scan
 constexpr int kCosineIrregularCap = 64;  // cur rows with a zero / non-finite / extreme norm kept in the side list
+constexpr int kCosineTile = 128;  // rows of one operand tile of the chunked kernel (cur: MFMA rows, ref: MFMA columns)
+constexpr int kRrTile = 64;       // cur rows per step of the register-stationary kernel (and per NearbyMatch tile box)
+constexpr int kRrRows = 512;      // ref rows per workgroup of the register-stationary kernel
+// Candidates per row up to which a call runs as ONE exact launch (cosine_match_small_kernel: a wave walks its row's candidates
+// alone, so its time grows with n_cur); measured against the multi-launch pipeline per shape
+constexpr int kCosineSmallCurNearby = 2048;  // 300 x 300 x 256 NearbyMatch 48.7 -> 10.7 us, 1 000 x 1 000 47.4 -> 21.3, 2 000 x 2 000 54.6 -> 40.3 (3 000 candidates: even)
+constexpr int kCosineSmallCurForce = 384;    // ForceMatch computes every pair exactly: 100 x 100 x 256 35.4 -> 14.8 us, 300 x 300 40.3 -> 32.1, 600 x 600 41.6 -> 59.2 (not taken)
+constexpr int kCosineSmallRefMax = 4096;
 struct CosineParams {
     const float *ref, *cur;   // [n][dim] fp32 descriptors, row-major
     const float *pred_uv;     // null => ForceMatch
@@ -203,12 +221,10 @@ struct CosineParams {
                               // n_cur_pad % 64 == 0, `splits` workgroups share the cur tiles evenly); 0: the chunked kernel
     int32_t splits;
     float max_distance, max_col, max_row;
-    int32_t small_off;        // experiment (FTK_COSINE_SMALL=0, read once per context): never the one-launch form
 };
 size_t cosine_rr_lds_bytes(int dim_pad);
-hipError_t cosine_match_launch(const CosineParams &p, hipStream_t stream);
-// Whether cosine_match_launch runs a call of this shape as one exact launch without the workspace (small calls).
-bool cosine_small_form(int n_ref, int n_cur, int dim, bool nearby, bool small_off);
+struct CosinePlan;
+hipError_t cosine_match_launch(const CosinePlan &plan, const CosineParams &p, hipStream_t stream);
 
 // DirectMethod (direct_kernels.hip): one workgroup per pose problem; all problems of a launch share
 // the pyramid depth and the options.
@@ -227,6 +243,7 @@ struct DirectProblem {
     float4 *feat;           // null: the per-feature projection table lives in LDS; else n_track entries of device memory (large problems)
 };
 constexpr uint32_t kDirectLdsFeatures = 768;  // tracked features whose per-feature table (64 B each) still fits in LDS beside the ring
+constexpr int kDmWaves = 8;                   // waves of a direct-method workgroup
 struct DirectParams {
     const DirectProblem *problems;  // device memory, one per workgroup
     int32_t tree;                   // throughput mode (ftk_set_reduction_mode): butterfly sums instead of the scalar loop's order
@@ -247,7 +264,8 @@ size_t direct_lds_bytes(uint32_t max_features);
 size_t direct_spread_ws_bytes(uint32_t n_track, int32_t patch_rows, int32_t patch_cols);
 size_t direct_spread_clear_bytes(uint32_t n_track, int32_t patch_rows, int32_t patch_cols);
 int direct_spread_resident_groups(uint32_t max_features, int device);  // workgroups of the spread kernel the device holds at once (0: unknown)
-hipError_t direct_track_launch(const DirectParams &p, int n_problems, uint32_t max_features, hipStream_t stream);
+struct DirectPlan;
+hipError_t direct_track_launch(const DirectPlan &plan, const DirectParams &p, hipStream_t stream);
 
 struct BriefParams {
     DevImage img;

@@ -118,9 +118,7 @@ struct ftk_context {
     size_t direct_spread_bytes = 0;
     int direct_spread_resident = -1;            // workgroups of the spread kernel this device holds at once (-1: not asked yet)
     uint32_t direct_spread_resident_features = 0;
-    int direct_spread_launched = 0;             // problems the LAST ftk_direct_track_batch_device call spread over the chip (0: one workgroup each)
-    size_t direct_spread_stride = 0;            // bytes of workspace per problem of that launch (header word 1 != 0: its waits ran out)
-    bool direct_spread_off = false;             // set around the re-run of a poisoned spread launch
+    int direct_spread_launched = 0;             // problems the LAST ftk_direct_track_batch_device call spread over the chip (0: one workgroup each; header word 1 != 0: its waits ran out)
     uint32_t direct_spread_reruns = 0;          // such re-runs so far (tests)
     // pinned host staging for the host-buffer entry points (one H2D + one D2H per call)
     void *pinned = nullptr;

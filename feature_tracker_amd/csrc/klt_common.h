@@ -15,7 +15,6 @@
 namespace ftk {
 namespace {
 
-constexpr int kWave = 64;
 
 // ---------------------------------------------------------------------------------------------
 // scalar helpers

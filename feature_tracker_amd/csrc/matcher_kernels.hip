@@ -14,14 +14,14 @@
 // order, and a tiny epilogue kernel writes index_pairs[i] only where a match exists (the
 // reference leaves the entry untouched otherwise).  Integer / popcount VALU work: v_xor_b32 +
 // v_bcnt_u32_b32 (popcount-accumulate) — no MFMA, the data are bits.
-#include "ftk_device.h"
+#include "match_plan.h"
 
 #include <stdlib.h>
 
 namespace ftk {
 namespace {
 
-constexpr int kBlock = 256;
+constexpr int kBlock = kMatchBlock;
 constexpr int kTile = 256;  // candidates staged per LDS tile
 constexpr unsigned long long kNoMatch = ~0ull;
 
@@ -417,8 +417,6 @@ __global__ void __launch_bounds__(kBlock) hamming_match_scalar_kernel(const Matc
 //     64-bit atomicMin as the other scans; match_epilogue_kernel turns them into indices.
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
-constexpr int kMfmaRows = 64;  // reference rows per workgroup: ONE wave (nothing is shared, so nothing is gained by larger groups,
-                               // and single waves pack the SIMDs' two slots evenly)
 
 // The rare path of the matrix-core scan: some lane of the wave holds a result above its lowest limit.  The caller folded the 32
 // results into four group maxima (8 registers each); only groups, and in them only registers, in which SOME lane beats its key
@@ -607,14 +605,15 @@ static __device__ __forceinline__ void mfma_scan(const MatchParams &p, int lane,
             mfma_update_keys<kNearby>(p, acc0, acc1, gtop_, key, pred_rows, lowest, at_lowest, h, min((tile_begin_) + c, last), j_begin); \
         }                                                                                                                      \
     }
-    for (int tile_begin = j_begin; tile_begin < j_end; tile_begin += 64) {
-        FTK_FETCH_WORDS(1, tile_begin + 32)
+    static_assert(kMfmaMaxTilesPerSplit * kMfmaTile < 0xFFFF, "a split's candidate positions fit the 16-bit position field of the keys");
+    for (int tile_begin = j_begin; tile_begin < j_end; tile_begin += 2 * kMfmaTile) {
+        FTK_FETCH_WORDS(1, tile_begin + kMfmaTile)
         __builtin_amdgcn_sched_barrier(0);  // the loads go out BEFORE the products of the tile in hand (the scheduler sinks them otherwise)
         FTK_MFMA_TILE(0, tile_begin)
-        if (tile_begin + 32 < j_end) {
-            FTK_FETCH_WORDS(0, tile_begin + 64)
+        if (tile_begin + kMfmaTile < j_end) {
+            FTK_FETCH_WORDS(0, tile_begin + 2 * kMfmaTile)
             __builtin_amdgcn_sched_barrier(0);
-            FTK_MFMA_TILE(1, tile_begin + 32)
+            FTK_MFMA_TILE(1, tile_begin + kMfmaTile)
         }
     }
     // ---- the best candidate of every row: maximum over the 32 lanes of the half, then one lane per row merges across splits ----
@@ -687,9 +686,7 @@ __global__ void __launch_bounds__(64) hamming_match_mfma_kernel(const MatchParam
 // Where the one-launch form wins (event-bracketed calls, launches / one launch): 300 x 300 x 256 bits
 // 10.4 / 6.3 us, 1000 x 1000 10.2 / 7.0, 2000 x 2000 11.7 / 9.7, 3000 x 300 11.0 / 6.9, 300 x 3000 10.0 / 8.9 — and where it does not:
 // 2000 x 2000 x 512 15.9 / 20.4, 300 x 3000 x 512 10.6 / 15.2, 64 x 60 000 10.3 / 73 (a wave walks its row's candidates alone).
-constexpr long long kSmallMatchWork = 32ll << 20;  // n_ref * n_cur * n_words up to which the one-launch form is used ...
-constexpr int kSmallMatchRowWork = 24576;          // ... while a row's walk stays below n_cur * n_words = this
-constexpr int kSmallNoIndex = 0xFFFFF;
+// (the shape rule: kSmallMatchWork, kSmallMatchRowWork, ftk_device.h; match_plan.cpp applies it)
 
 template <int NW, bool kNearby>
 __global__ void __launch_bounds__(kBlock) hamming_match_small_kernel(const MatchParams p) {
@@ -754,17 +751,6 @@ __global__ void __launch_bounds__(kBlock) hamming_match_small_kernel(const Match
     }
 }
 
-template <int NW>
-hipError_t launch_small(const MatchParams &p, hipStream_t stream) {
-    const dim3 grid((unsigned)((p.n_ref + kBlock / 64 - 1) / (kBlock / 64)));
-    if (p.pred_uv) {
-        hipLaunchKernelGGL((hamming_match_small_kernel<NW, true>), grid, dim3(kBlock), 0, stream, p);
-    } else {
-        hipLaunchKernelGGL((hamming_match_small_kernel<NW, false>), grid, dim3(kBlock), 0, stream, p);
-    }
-    return hipGetLastError();
-}
-
 __global__ void __launch_bounds__(kBlock) match_epilogue_kernel(unsigned long long *keys, int32_t *index_pairs, int n_ref) {
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i < n_ref) {
@@ -776,87 +762,62 @@ __global__ void __launch_bounds__(kBlock) match_epilogue_kernel(unsigned long lo
     }
 }
 
+// The scan of the plan's form on NW-word descriptors.
 template <int NW>
-hipError_t launch_nw(const MatchParams &p, hipStream_t stream) {
-    const int splits = (p.n_cur + p.cur_per_block - 1) / p.cur_per_block;
-    if (p.n_bits == 0) {
-        // ComputeDistance's "empty descriptor" answer (kMaxInt32) does not fit the packed key: plain scan
-        const int row_blocks = (p.n_ref + kBlock - 1) / kBlock;
-        hipLaunchKernelGGL(hamming_match_kernel<NW>, dim3(row_blocks, splits), dim3(kBlock), 0, stream, p);
-        return hipGetLastError();
-    }
-    const int row_blocks = (p.n_ref + kBlock * kRefs - 1) / (kBlock * kRefs);
-    if (p.matrix_cores) {
-        if constexpr (NW >= 8) {
-            if (p.pred_uv && p.boxes) {
-                hipLaunchKernelGGL(hamming_box_kernel, dim3((unsigned)(row_blocks + splits)), dim3(kBlock), 0, stream, p, row_blocks);
-            }
-            const dim3 grid((unsigned)((p.n_ref + kMfmaRows - 1) / kMfmaRows), (unsigned)splits);
-            if (p.pred_uv) {
-                hipLaunchKernelGGL((hamming_match_mfma_kernel<NW, true>), grid, dim3(64), 0, stream, p);
+void launch_scan(const HammingPlan &plan, const MatchParams &p, hipStream_t stream) {
+    const bool nearby = p.pred_uv != nullptr;
+    const dim3 grid = plan.scan_grid, block = plan.scan_block;
+    switch (plan.form) {
+        case HammingForm::Small:
+            if (nearby) {
+                hipLaunchKernelGGL((hamming_match_small_kernel<NW, true>), grid, block, 0, stream, p);
             } else {
-                hipLaunchKernelGGL((hamming_match_mfma_kernel<NW, false>), grid, dim3(64), 0, stream, p);
+                hipLaunchKernelGGL((hamming_match_small_kernel<NW, false>), grid, block, 0, stream, p);
             }
-            return hipGetLastError();
-        }
+            break;
+        case HammingForm::Plain: hipLaunchKernelGGL(hamming_match_kernel<NW>, grid, block, 0, stream, p); break;
+        case HammingForm::MatrixCores:
+            if constexpr (NW >= 8) {
+                if (nearby) {
+                    hipLaunchKernelGGL((hamming_match_mfma_kernel<NW, true>), grid, block, 0, stream, p);
+                } else {
+                    hipLaunchKernelGGL((hamming_match_mfma_kernel<NW, false>), grid, block, 0, stream, p);
+                }
+            }
+            break;
+        default:
+            if (nearby) {
+                hipLaunchKernelGGL((hamming_match_scalar_kernel<NW, true>), grid, block, 0, stream, p);
+            } else {
+                hipLaunchKernelGGL((hamming_match_scalar_kernel<NW, false>), grid, block, 0, stream, p);
+            }
+            break;
     }
-    if (p.pred_uv) {
-        if (p.boxes) {
-            hipLaunchKernelGGL(hamming_box_kernel, dim3((unsigned)(row_blocks + splits)), dim3(kBlock), 0, stream, p, row_blocks);
-        }
-        hipLaunchKernelGGL((hamming_match_scalar_kernel<NW, true>), dim3(row_blocks, splits), dim3(kBlock), 0, stream, p);
-    } else {
-        hipLaunchKernelGGL((hamming_match_scalar_kernel<NW, false>), dim3(row_blocks, splits), dim3(kBlock), 0, stream, p);
-    }
-    return hipGetLastError();
 }
 
 }  // namespace
 
-bool match_small_form(int n_ref, int n_cur, int n_words, int n_bits, bool small_off) {
-    const bool allowed = !small_off;  // FTK_MATCH_SMALL=0 (experiment switch of the context)
-    const bool width = n_words == 1 || n_words == 2 || n_words == 4 || n_words == 8 || n_words == 16;
-    return allowed && width && n_bits > 0 && n_cur < kSmallNoIndex && (long long)n_cur * n_words <= kSmallMatchRowWork &&
-           (long long)n_ref * n_cur * n_words <= kSmallMatchWork;
-}
-
-hipError_t match_launch(const MatchParams &p, hipStream_t stream) {
-    if (p.n_ref <= 0 || p.n_cur <= 0) {
-        return hipSuccess;
-    }
-    hipError_t e = hipSuccess;
-    if (match_small_form(p.n_ref, p.n_cur, p.n_words, p.n_bits, p.small_off != 0)) {
-        switch (p.n_words) {
-            case 1: return launch_small<1>(p, stream);
-            case 2: return launch_small<2>(p, stream);
-            case 4: return launch_small<4>(p, stream);
-            case 8: return launch_small<8>(p, stream);
-            default: return launch_small<16>(p, stream);
-        }
-    }
-    if (!p.keys_clean) {
-        e = hipMemsetAsync(p.keys, 0xFF, sizeof(unsigned long long) * (size_t)p.n_ref, stream);
+hipError_t match_launch(const HammingPlan &plan, const MatchParams &p, hipStream_t stream) {
+    if (plan.form != HammingForm::Small && !p.keys_clean) {
+        const hipError_t e = hipMemsetAsync(p.keys, 0xFF, sizeof(unsigned long long) * (size_t)p.n_ref, stream);
         if (e != hipSuccess) {
             return e;
         }
     }
+    if (plan.box_grid.x > 0) {  // the row boxes, then one per split
+        hipLaunchKernelGGL(hamming_box_kernel, plan.box_grid, dim3(kBlock), 0, stream, p, (int)(plan.box_grid.x - plan.scan_grid.y));
+    }
     switch (p.n_words) {
-        case 1: e = launch_nw<1>(p, stream); break;
-        case 2: e = launch_nw<2>(p, stream); break;
-        case 4: e = launch_nw<4>(p, stream); break;
-        case 8: e = launch_nw<8>(p, stream); break;
-        case 16: e = launch_nw<16>(p, stream); break;
-        default: {
-            const int splits = (p.n_cur + p.cur_per_block - 1) / p.cur_per_block;
-            hipLaunchKernelGGL(hamming_match_generic_kernel, dim3((p.n_ref + kBlock - 1) / kBlock, splits), dim3(kBlock), 0, stream, p);
-            e = hipGetLastError();
-            break;
-        }
+        case 1: launch_scan<1>(plan, p, stream); break;
+        case 2: launch_scan<2>(plan, p, stream); break;
+        case 4: launch_scan<4>(plan, p, stream); break;
+        case 8: launch_scan<8>(plan, p, stream); break;
+        case 16: launch_scan<16>(plan, p, stream); break;
+        default: hipLaunchKernelGGL(hamming_match_generic_kernel, plan.scan_grid, plan.scan_block, 0, stream, p); break;
     }
-    if (e != hipSuccess) {
-        return e;
+    if (plan.epilogue_grid.x > 0) {
+        hipLaunchKernelGGL(match_epilogue_kernel, plan.epilogue_grid, dim3(kBlock), 0, stream, p.keys, p.index_pairs, p.n_ref);
     }
-    hipLaunchKernelGGL(match_epilogue_kernel, dim3((p.n_ref + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, p.keys, p.index_pairs, p.n_ref);
     return hipGetLastError();
 }
 
