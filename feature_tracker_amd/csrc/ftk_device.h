@@ -351,6 +351,33 @@ hipError_t corr_build_launch(const CorrBuildParams &p, hipStream_t stream);
 hipError_t corr_pool_launch(const float *src, float *dst, int64_t slabs, int hin, int win, int hout, int wout, hipStream_t stream);
 hipError_t corr_lookup_launch(const CorrLookupParams &p, hipStream_t stream);
 
+// NNFeatureMatcher's post-processing (nn_match_kernels.hip): mutual-best matching of a score matrix, or a match list.
+// Keys (unsigned 64-bit, merged with atomicMax, 0 = empty): score mode (order-preserving map of the score << 32 | ~index), so the
+// greatest score wins and, among equal scores, the lowest index; list mode ((k + 1) << 32 | idx_cur), so the last row wins.
+constexpr int kNnBlock = 256;     // threads of every workgroup of this file
+constexpr int kNnTileCols = 256;  // columns of a tile: one 16-byte load per lane of a wave covers a 1 KB row segment
+constexpr int kNnTileRowsMin = 16, kNnTileRowsMax = 128;  // rows of a tile (a multiple of 16: four waves x four loads in flight each)
+constexpr int kNnMaxBatch = 65535;                        // grid.y
+struct NnMatchParams {
+    const float *scores;              // [B][n_ref][n_cur] through row_stride / batch_stride (elements), unit column stride
+    int64_t row_stride, batch_stride;
+    int32_t batch, n_ref, n_cur;
+    int32_t tile_rows, col_tiles;
+    float min_score;
+    unsigned long long *row_key;      // [B][n_ref]
+    unsigned long long *col_key;      // [B][n_cur]
+    unsigned int *done;               // workgroups of the epilogue that have finished (the last one empties col_key)
+    int32_t *match_index;             // [B][n_ref]
+    uint8_t *status;                  // [B][n_ref]
+};
+struct NnMatchPlan;
+hipError_t nn_match_scores_launch(const NnMatchPlan &plan, const NnMatchParams &p, hipStream_t stream);
+// List mode: row_key holds n_ref entries (empty before and after).
+hipError_t nn_match_list_launch(const long long *matches, int32_t n_matches, int32_t n_ref, int32_t n_cur, unsigned long long *row_key,
+                                int32_t *match_index, uint8_t *status, hipStream_t stream);
+hipError_t nn_fill_pixels_launch(const int32_t *match_index, int32_t n_ref, const float *cur_uv, int32_t n_cur, float *matched_uv, hipStream_t stream);
+hipError_t nn_match_warm(hipStream_t stream);
+
 // Scatter of the all-gathered packed tracker shards into (cur_uv, status) in global feature order (ftk_comm.cpp).
 hipError_t unpack_klt_shards_launch(const uint8_t *d_gathered, int32_t n, int32_t world, int32_t cap, int64_t shard_bytes, float *d_uv_out,
                                     uint8_t *d_status_out, hipStream_t stream);

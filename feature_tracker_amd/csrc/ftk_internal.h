@@ -72,6 +72,9 @@ struct ftk_context {
     size_t scratch_bytes = 0;
     unsigned long long *match_keys = nullptr;
     size_t match_keys_count = 0;
+    // keys of NNFeatureMatcher's post-processing (ftk_nn_match_*_device): all 0 = empty between calls; grown only outside a stream capture
+    unsigned long long *nn_keys = nullptr;
+    size_t nn_keys_count = 0;
     float *match_boxes = nullptr;  // NearbyMatch bounding boxes (4 floats each)
     size_t match_boxes_count = 0;
     // workspace of the float-descriptor matcher (fp16 copies, norms, candidate lists)

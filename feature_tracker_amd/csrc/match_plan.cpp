@@ -231,4 +231,34 @@ DirectPlan direct_plan(const DirectPlanInput &in) {
     return pl;
 }
 
+// One pass over the matrix, a workgroup per tile of tile_rows x kNnTileCols scores.  The tile is 1 KB wide (a wave's 16-byte loads
+// cover a row segment in one instruction) and as tall as leaves about four workgroups for each of the 256 CUs: the pass is a stream
+// from HBM / the Infinity Cache, which wants ~32 KB of loads in flight per CU (16 waves x four 1 KB loads), while every tile ends
+// with kNnTileCols + tile_rows 8-byte atomics whose number falls with the tile's height.
+NnMatchPlan nn_match_plan(const NnMatchPlanInput &in) {
+    NnMatchPlan pl = {};
+    const long long keys = (long long)in.batch * ((long long)in.n_ref + in.n_cur);
+    if (in.batch < 1 || in.n_ref < 1 || in.n_cur < 1 || in.batch > kNnMaxBatch || keys >= (1ll << 31)) {
+        return pl;
+    }
+    pl.vec4 = in.aligned16 && in.row_stride % 4 == 0 && in.batch_stride % 4 == 0;
+    pl.col_tiles = ceil_div(in.n_cur, kNnTileCols);
+    int rows = kNnTileRowsMax;
+    while (rows > kNnTileRowsMin && (long long)in.batch * pl.col_tiles * ceil_div(in.n_ref, rows) < 1024) {
+        rows /= 2;
+    }
+    pl.tile_rows = rows;
+    pl.row_tiles = ceil_div(in.n_ref, rows);
+    const long long tiles = (long long)pl.row_tiles * pl.col_tiles;
+    if (tiles >= (1ll << 31)) {
+        return pl;
+    }
+    pl.ok = true;
+    pl.key_count = (size_t)keys + 1;
+    pl.grid = dim3((unsigned)tiles, (unsigned)in.batch);
+    pl.block = dim3(kNnBlock);
+    pl.epilogue_grid = dim3(ceil_div((long long)in.batch * in.n_ref, kNnBlock));
+    return pl;
+}
+
 }  // namespace ftk

@@ -82,4 +82,21 @@ struct DirectPlan {
 };
 DirectPlan direct_plan(const DirectPlanInput &in);
 
+// ---- NNFeatureMatcher post-processing (nn_match_kernels.hip) ----
+struct NnMatchPlanInput {
+    int32_t batch, n_ref, n_cur;        // all >= 1
+    long long row_stride, batch_stride;  // elements
+    int aligned16;                       // the base pointer is 16-byte aligned
+};
+struct NnMatchPlan {
+    bool ok;             // false: the problem does not fit a launch (batch > kNnMaxBatch, or 2^31 tiles / key indices); nothing else is set
+    int32_t vec4;        // 16-byte loads (aligned base, row and batch strides multiples of 4 elements), else 4-byte loads
+    int32_t tile_rows;   // a multiple of kNnTileRowsMin up to kNnTileRowsMax; tile columns are kNnTileCols
+    int32_t row_tiles, col_tiles;
+    size_t key_count;    // workspace, in 8-byte words: batch * n_ref row keys, batch * n_cur column keys, one counter word
+    dim3 grid, block;    // the pass: x = row_tiles * col_tiles (column tile fastest), y = batch
+    dim3 epilogue_grid;  // block kNnBlock, one thread per (batch item, reference row)
+};
+NnMatchPlan nn_match_plan(const NnMatchPlanInput &in);
+
 }  // namespace ftk

@@ -320,3 +320,60 @@ def corr_pyramid_lookup_device(ctx: Context, volume, levels: int, radius: int, c
     rc = N.lib().ftk_corr_pyramid_lookup_device(ctx.handle, C.c_void_p(s.cuda_stream), C.c_void_p(volume.data_ptr()), B, H, W, int(levels),
                                                 int(radius), C.c_void_p(coords.data_ptr()), C.c_void_p(out.data_ptr()), int(bool(per_level)))
     N.check(rc, ctx.handle)
+
+
+def _nn_stream(torch, device, stream):
+    s = torch.cuda.current_stream(device) if stream is None else stream
+    return C.c_void_p(s.cuda_stream)
+
+
+def nn_match_scores_device(ctx: Context, scores, min_score: float, match_index, status, stream=None) -> None:
+    """ftk_nn_match_scores_device: mutual-best matching of ``scores`` (float32 CUDA [B, n_ref, n_cur], any row / batch stride, unit column
+    stride) into ``match_index`` (contiguous int32 [B, n_ref]) and ``status`` (contiguous uint8 [B, n_ref]), enqueued on ``stream``
+    (default: torch's current stream).  No synchronisation; no allocation once the context's key workspace holds the size: capturable."""
+    torch = _torch()
+    if not isinstance(scores, torch.Tensor) or scores.dtype != torch.float32 or not scores.is_cuda or scores.dim() != 3:
+        raise ValueError("scores must be a 3-D float32 CUDA tensor [B, n_ref, n_cur] (no CPU fallback, no other dtype)")
+    B, n_ref, n_cur = scores.shape
+    if n_cur > 1 and scores.stride(2) != 1:
+        raise ValueError(f"scores must have unit column stride (got strides {tuple(scores.stride())}): pass a row / batch slice, or .contiguous()")
+    for name, t, dt in (("match_index", match_index, torch.int32), ("status", status, torch.uint8)):
+        if t.dtype != dt or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != (B, n_ref) or t.device != scores.device:
+            raise ValueError(f"{name} must be a contiguous {dt} tensor of shape ({B}, {n_ref}) on {scores.device}")
+    # a size-1 dimension's stride is arbitrary in torch: give the extent the library validates against
+    row_stride = scores.stride(1) if n_ref > 1 else max(n_cur, 1)
+    batch_stride = scores.stride(0) if B > 1 else 0
+    rc = N.lib().ftk_nn_match_scores_device(ctx.handle, _nn_stream(torch, scores.device, stream), C.c_void_p(scores.data_ptr()), B, n_ref, n_cur,
+                                            row_stride, batch_stride, float(min_score), C.c_void_p(match_index.data_ptr()),
+                                            C.c_void_p(status.data_ptr()))
+    N.check(rc, ctx.handle)
+
+
+def nn_match_list_device(ctx: Context, matches, n_ref: int, n_cur: int, match_index, status, stream=None) -> None:
+    """ftk_nn_match_list_device: ``matches`` (contiguous int64 CUDA [K, 2] rows of (idx_ref, idx_cur)) into ``match_index`` (int32 [n_ref])
+    and ``status`` (uint8 [n_ref]); the last applied row of an idx_ref wins."""
+    torch = _torch()
+    if not isinstance(matches, torch.Tensor) or matches.dtype != torch.int64 or not matches.is_cuda or matches.dim() != 2 or matches.size(1) != 2 \
+            or not matches.is_contiguous():
+        raise ValueError("matches must be a contiguous int64 CUDA tensor [K, 2]")
+    for name, t, dt in (("match_index", match_index, torch.int32), ("status", status, torch.uint8)):
+        if t.dtype != dt or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != (int(n_ref),) or t.device != matches.device:
+            raise ValueError(f"{name} must be a contiguous {dt} tensor of shape ({n_ref},) on {matches.device}")
+    rc = N.lib().ftk_nn_match_list_device(ctx.handle, _nn_stream(torch, matches.device, stream), C.c_void_p(matches.data_ptr()), matches.size(0),
+                                          int(n_ref), int(n_cur), C.c_void_p(match_index.data_ptr()), C.c_void_p(status.data_ptr()))
+    N.check(rc, ctx.handle)
+
+
+def nn_fill_pixels_device(ctx: Context, match_index, cur_uv, matched_uv, stream=None) -> None:
+    """ftk_nn_fill_pixels_device: ``matched_uv`` (float32 [n_cur, 2]) = ``cur_uv`` with entry t < n_ref replaced by cur_uv[match_index[t]]
+    where that index is valid (``match_index``: int32 [n_ref])."""
+    torch = _torch()
+    n_ref, n_cur = match_index.numel(), cur_uv.size(0)
+    if match_index.dtype != torch.int32 or not match_index.is_cuda or not match_index.is_contiguous() or match_index.dim() != 1:
+        raise ValueError("match_index must be a contiguous 1-D int32 CUDA tensor")
+    for name, t in (("cur_uv", cur_uv), ("matched_uv", matched_uv)):
+        if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != (n_cur, 2) or t.device != match_index.device:
+            raise ValueError(f"{name} must be a contiguous float32 tensor of shape ({n_cur}, 2) on {match_index.device}")
+    rc = N.lib().ftk_nn_fill_pixels_device(ctx.handle, _nn_stream(torch, match_index.device, stream), C.c_void_p(match_index.data_ptr()), n_ref,
+                                           C.c_void_p(cur_uv.data_ptr()), n_cur, C.c_void_p(matched_uv.data_ptr()))
+    N.check(rc, ctx.handle)

@@ -3,6 +3,7 @@
 //   hamming n_ref n_cur n_words n_bits nearby keys_given small kernel
 //   cosine  n_ref n_cur dim nearby aligned16 small chunked splits
 //   direct  n_problems max_features patch_rows patch_cols method tree spread_allowed resident capturing held spread resident_cap poison min_terms
+//   nn      batch n_ref n_cur row_stride batch_stride aligned16
 // one line of key=value pairs per case on stdout.  tests/test_match_plan_cpu.py drives it.
 #include <cstdio>
 #include <cstdlib>
@@ -59,6 +60,14 @@ int main() {
             printf("ask_resident=%d ask_capturing=%d feat_in_global=%d feat_bytes=%zu producers=%d ws_stride=%zu clear_bytes=%zu poison=%d lds=%zu", p.ask_resident,
                    p.ask_capturing, p.feat_in_global, p.feat_bytes, p.producers, p.ws_stride, p.clear_bytes, p.poison, p.lds);
             grid("grid", p.grid), grid("block", p.block);
+        } else if (kind == "nn") {
+            ftk::NnMatchPlanInput in;
+            in.batch = (int32_t)field(line), in.n_ref = (int32_t)field(line), in.n_cur = (int32_t)field(line);
+            in.row_stride = field(line), in.batch_stride = field(line), in.aligned16 = (int)field(line);
+            const ftk::NnMatchPlan p = ftk::nn_match_plan(in);
+            printf("ok=%d vec4=%d tile_rows=%d tile_cols=%d row_tiles=%d col_tiles=%d key_count=%zu", p.ok, p.vec4, p.tile_rows, ftk::kNnTileCols, p.row_tiles,
+                   p.col_tiles, p.key_count);
+            grid("grid", p.grid), grid("block", p.block), grid("epilogue_grid", p.epilogue_grid);
         } else {
             printf("error=unknown_kind");
         }

@@ -486,6 +486,58 @@ int ftk_cosine_match_device(ftk_context *ctx, const float *d_ref_desc, int32_t n
  * Pure index -> pixel gather on host buffers (O(n_ref), not worth a launch); status is in/out. */
 int ftk_fill_matched_pixels(const int32_t *index_pairs, int32_t n_ref, const float *cur_uv, int32_t n_cur, float *matched_uv, uint8_t *status);
 
+/* ---- NNFeatureMatcher: what Match does after the network ----------------------------------- */
+
+/*
+ * Replaces the score-matrix branch of NNFeatureMatcher::Match (nn_feature_matcher.cpp:177-215: kLightglueFor*ScoreMat) — not the
+ * network in front of it.  scores: float32, logically [batch][n_ref][n_cur], element (b, i, j) at
+ * scores[b * batch_stride + i * row_stride + j] (strides in elements; column stride 1; row_stride >= n_cur; pass the
+ * [:, :-1, :-1] view of LightGlue's log-assignment tensor to leave its dustbin row and column out).  Per batch item:
+ *   col_best[j] = first argmax over i of column j and row_best[i] = first argmax over j of row i, both by the reference's loop
+ *   (:188-199, :201-210: start at index 0, replace on a strict >) — so ties go to the lowest index, -0 and +0 tie, a NaN at index 0
+ *   keeps its column / row, a NaN elsewhere never wins, all -inf gives 0;
+ *   row i is matched iff NOT (row maximum < min_score) (:211: a NaN maximum or a NaN min_score passes) and
+ *   col_best[row_best[i]] == i (:212);
+ *   match_index[b * n_ref + i] = row_best[i] if matched, else -1; status[...] = FTK_TRACKED if matched, else FTK_LARGE_RESIDUAL
+ *   (:156, :214).
+ * Bit-identical to the scalar loops for every input: only comparisons are involved.  The matrix is read once.
+ * Device entry: asynchronous on `stream` (a hipStream_t; NULL = the legacy default stream), 16-byte loads when d_scores is 16-byte
+ * aligned and both strides are multiples of 4, 4-byte loads otherwise (same results).  The context keeps
+ * batch * (n_ref + n_cur) + 1 8-byte words of key workspace, left empty by every call; it grows only outside a stream capture
+ * (FTK_E_UNSUPPORTED inside one: make one call of the size, or larger, on this context before capturing).  Calls on one context
+ * share that workspace: issue them on one stream at a time.  Limits: batch <= 65535, batch * (n_ref + n_cur) < 2^31.
+ * n_ref == 0 (or batch == 0) writes nothing and returns FTK_OK — the host entry with *matched_ok = 0, the reference's `return false`
+ * (:92).  n_cur == 0 with n_ref > 0 is FTK_E_INVALID_ARGUMENT: the reference would read scores(0) of an empty row (a departure
+ * from undefined behaviour).
+ */
+int ftk_nn_match_scores_device(ftk_context *ctx, void *stream, const float *d_scores, int32_t batch, int32_t n_ref, int32_t n_cur, int64_t row_stride,
+                               int64_t batch_stride, float min_score, int32_t *d_match_index, uint8_t *d_status);
+/* Host arrays in and out, synchronous; *matched_ok as in ftk_hamming_match. */
+int ftk_nn_match_scores(ftk_context *ctx, const float *scores, int32_t batch, int32_t n_ref, int32_t n_cur, int64_t row_stride, int64_t batch_stride,
+                        float min_score, int32_t *match_index, uint8_t *status, int *matched_ok);
+
+/*
+ * Replaces the match-list branch (nn_feature_matcher.cpp:158-174: kLightglueFor*Matches).  matches: int64 [n_matches][2] rows of
+ * (idx_ref, idx_cur).  Row k is applied iff 0 <= idx_ref < min(n_ref, n_cur) and 0 <= idx_cur < n_cur: the reference bounds idx_ref
+ * by the size of matched_pixel_uv_cur (n_cur entries, :169) and then writes status[idx_ref] (n_ref entries, :172), so the
+ * intersection is the largest range in which it is defined (a departure from undefined behaviour).  Of several applied rows with
+ * one idx_ref the one with the largest k wins, as in the sequential loop.  Outputs as above (one batch item).  n_matches < 2^31 - 1.
+ */
+int ftk_nn_match_list_device(ftk_context *ctx, void *stream, const int64_t *d_matches, int32_t n_matches, int32_t n_ref, int32_t n_cur,
+                             int32_t *d_match_index, uint8_t *d_status);
+int ftk_nn_match_list(ftk_context *ctx, const int64_t *matches, int32_t n_matches, int32_t n_ref, int32_t n_cur, int32_t *match_index, uint8_t *status,
+                      int *matched_ok);
+
+/*
+ * The pixel fill of both branches on the device (:157, :171, :213).  matched_uv has n_CUR entries of (u, v), as the reference's
+ * `matched_pixel_uv_cur = pixel_uv_cur`: entry t becomes cur_uv[match_index[t]] where t < n_ref and 0 <= match_index[t] < n_cur,
+ * and cur_uv[t] otherwise.  In score mode the reference writes matched_pixel_uv_cur[idx_ref] without a bounds test, which is
+ * undefined for idx_ref >= n_cur: here such a row keeps its match_index and status and its pixel is not written (a departure from
+ * undefined behaviour).  d_matched_uv must not alias d_cur_uv.
+ */
+int ftk_nn_fill_pixels_device(ftk_context *ctx, void *stream, const int32_t *d_match_index, int32_t n_ref, const float *d_cur_uv, int32_t n_cur,
+                              float *d_matched_uv);
+
 #ifdef __cplusplus
 }
 #endif
