@@ -1,5 +1,7 @@
 /*
- * oracle_direct_method.c — TEST INFRASTRUCTURE (see ftk_oracle.h).  PARITY UNPINNED.
+ * oracle_direct_method.c — TEST INFRASTRUCTURE (see ftk_oracle.h).  Parity pinned by tests/test_direct_ref64_cpu.py: this file
+ * against tests/direct_ref64.py, a float64 restatement written independently from the same source (1e-3 px on pixels and on the
+ * pixels the pose induces, statuses and iteration counts equal, mutants detected); the reference ships no golden vectors.
  *
  * DirectMethod, restated from
  * src/direct_method_tracker/direct_method_tracker.cpp: the pyramid driver TrackFeatures (:35-86)

@@ -44,7 +44,7 @@ def run_both(ftk, oracle, rl, cl, uv, pts, cur_uv=None, q=(1, 0, 0, 0), p=(0, 0,
     o.kPatchColHalfSize = opt.get("half_cols", opt.get("half", 6))
     o.kMaxConvergeStep = opt.get("converge", 1e-6)
     o.kMethod = opt.get("method", "direct")
-    K = [FX, FY, CX, CY]
+    K = [float(k) for k in opt.get("K", (FX, FY, CX, CY))]
     ok_g, c_g, q_g, p_g, s_g = dm.TrackFeatures(ftk.ImagePyramid.from_host_levels(rl), ftk.ImagePyramid.from_host_levels(cl), K, pts, uv, cur_uv, q, p, status)
     ok_c, c_c, q_c, p_c, s_c, it_c = oracle.direct_track(rl, cl, K, pts, uv, cur_uv, q, p, status, method=o.kMethod, half=o.kPatchRowHalfSize,
                                                           half_cols=o.kPatchColHalfSize, max_points=o.kMaxTrackPointsNumber,
@@ -83,6 +83,46 @@ def test_varied_depths_levels_and_patches(ftk, oracle, levels, half, n):
     g, c = run_both(ftk, oracle, rl, cl, uv, pts, half=half, max_points=n)
     assert_identical(g, c)
     assert g[4] >= levels
+
+
+@pytest.mark.parametrize("half,half_cols", [(3, 7), (7, 2), (0, 0), (0, 5), (4, 0)])
+def test_rectangular_patches_and_half_zero(ftk, oracle, half, half_cols):
+    """kPatchRowHalfSize and kPatchColHalfSize differ; a half of 0 is accepted (a one-pixel row, column or patch)."""
+    rl, cl, uv, pts = scene(levels=3, n=200, half=max(half, half_cols), rotation_deg=0.4, scale=1.004)
+    g, c = run_both(ftk, oracle, rl, cl, uv, pts, half=half, half_cols=half_cols, max_points=200)
+    assert_identical(g, c)
+    assert g[4] >= 3
+
+
+def test_odd_image_size_whose_pyramid_drops_a_row_or_column_at_every_level(ftk, oracle):
+    from tests.test_direct_ref64_cpu import K333, planar
+    rl, cl, uv, pts = planar(333, 251, 3, 180, K333, half=5, rotation_deg=0.3, scale=1.003, seed=7)
+    assert [l.shape for l in rl] == [(251, 333), (125, 166), (62, 83)]
+    g, c = run_both(ftk, oracle, rl, cl, uv, pts, half=5, max_points=180, K=K333)
+    assert_identical(g, c)
+    assert g[4] >= 3
+
+
+@pytest.mark.parametrize("n,half", [(64, 1), (57, 1), (512, 3), (337, 3)])
+def test_term_counts_at_and_one_past_a_multiple_of_the_wave_size(ftk, oracle, n, half):
+    """n x patch terms: 576 = 64 x 9 and 25 088 = 64 x 392 fill their last chunk of 64 exactly, 513 and 16 513 leave one term in it
+    (the two larger ones are spread over the chip by the default dispatch)."""
+    terms = n * (2 * half + 1) ** 2
+    assert terms % 64 == (0 if n in (64, 512) else 1)
+    rl, cl, uv, pts = scene(levels=2, n=n, half=half, rotation_deg=0.4, scale=1.004)
+    g, c = run_both(ftk, oracle, rl, cl, uv, pts, half=half, max_points=n)
+    assert_identical(g, c)
+
+
+@pytest.mark.parametrize("start", ["identity", "nearby"])
+@pytest.mark.parametrize("pose", ["rot-x", "rot-y", "trans-z", "general"])
+def test_tilted_plane_seen_from_a_known_pose(ftk, oracle, pose, start):
+    """The 3-D scenes of tests/test_direct_ref64_cpu.py (rotation about x and y, translation along z, a general motion)."""
+    from tests.test_direct_ref64_cpu import K320, full_cases
+    c3 = next(c for c in full_cases() if c["name"] == f"plane-{pose}/{start}-start")
+    g, c = run_both(ftk, oracle, c3["rl"], c3["cl"], c3["uv"], c3["pts"], None, c3["q"], c3["p"], K=K320, **c3["opt"])
+    assert_identical(g, c)
+    assert (g[3] == 1).sum() >= 140  # (a border feature or two leave the image)
 
 
 def test_prediction_initial_pose_status_and_cap(ftk, oracle):
