@@ -66,13 +66,8 @@ struct ftk_comm {
     ncclComm_t comm = nullptr;
     int32_t rank = 0, world = 1;
     // this rank's packed result shard and the gathered buffer (world shards), grown on demand
-    void *packed = nullptr;
-    size_t packed_bytes = 0;
-    void *gathered = nullptr;
-    size_t gathered_bytes = 0;
-    // device staging of the host-buffer entry point (ref_uv | cur_uv | status | iters for all n features)
-    void *stage = nullptr;
-    size_t stage_bytes = 0;
+    ftk_buffer packed, gathered;
+    ftk_buffer stage;  // device staging of the host-buffer entry point (ref_uv | cur_uv | status | iters for all n features)
 };
 
 namespace {
@@ -90,19 +85,19 @@ void shard_range(int32_t n, int32_t world, int32_t rank, int32_t *begin, int32_t
 }
 
 int ensure_comm_buffers(ftk_comm *c, size_t shard_bytes) {
-    int rc = ftk_ensure_device_buffer(c->ctx, &c->packed, &c->packed_bytes, shard_bytes);
+    int rc = ftk_ensure_device_buffer(c->ctx, c->packed, shard_bytes);
     if (rc != FTK_OK) {
         return rc;
     }
-    return ftk_ensure_device_buffer(c->ctx, &c->gathered, &c->gathered_bytes, shard_bytes * (size_t)c->world);
+    return ftk_ensure_device_buffer(c->ctx, c->gathered, shard_bytes * (size_t)c->world);
 }
 
 int all_gather(ftk_comm *c, size_t shard_bytes) {
     if (c->comm == nullptr) {  // world == 1 made without an RCCL id: nothing to exchange, the "gathered" buffer is the shard
-        FTK_HIP(c->ctx, hipMemcpyAsync(c->gathered, c->packed, shard_bytes, hipMemcpyDeviceToDevice, c->ctx->stream));
+        FTK_HIP(c->ctx, hipMemcpyAsync(c->gathered.get(), c->packed.get(), shard_bytes, hipMemcpyDeviceToDevice, c->ctx->stream));
         return FTK_OK;
     }
-    const ncclResult_t r = rccl().AllGather(c->packed, c->gathered, shard_bytes, ncclUint8, c->comm, c->ctx->stream);
+    const ncclResult_t r = rccl().AllGather(c->packed.get(), c->gathered.get(), shard_bytes, ncclUint8, c->comm, c->ctx->stream);
     if (r != ncclSuccess) {
         return ftk_fail(c->ctx, FTK_E_HIP, "ncclAllGather failed: %s", rccl().GetErrorString(r));
     }
@@ -189,24 +184,14 @@ void ftk_comm_destroy(ftk_comm *c) {
     if (!c) {
         return;
     }
-    {
-        FTK_LOCK(c->ctx);
-        (void)hipSetDevice(c->ctx->device);
-        (void)hipStreamSynchronize(c->ctx->stream);
-        if (c->comm) {
-            (void)rccl().CommDestroy(c->comm);
-        }
-        if (c->packed) {
-            (void)hipFree(c->packed);
-        }
-        if (c->gathered) {
-            (void)hipFree(c->gathered);
-        }
-        if (c->stage) {
-            (void)hipFree(c->stage);
-        }
+    ftk_context *ctx = c->ctx;
+    FTK_LOCK(ctx);
+    (void)hipSetDevice(ctx->device);
+    (void)hipStreamSynchronize(ctx->stream);
+    if (c->comm) {
+        (void)rccl().CommDestroy(c->comm);
     }
-    delete c;
+    delete c;  // and its buffers
 }
 
 int ftk_comm_rank(const ftk_comm *c) { return c ? c->rank : -1; }
@@ -292,14 +277,14 @@ int ftk_klt_track_sharded_device(ftk_context *ctx, ftk_comm *comm, int model, co
         return rc;
     }
     rc = ftk_klt_track_shard_device(ctx, comm->rank, comm->world, model, opt, ref, cur, d_ref_uv, d_cur_uv_in, d_status_in, n, prior,
-                                    consider_luminance, single_level, comm->packed, d_iters);
+                                    consider_luminance, single_level, comm->packed.get(), d_iters);
     if (rc != FTK_OK) {
         // The peers are (or will be) inside the collective: leaving without it would block them for ever.  Contribute a POISONED
         // shard instead — every byte 0xFF: status 255 is no TrackStatus and (u, v) are NaNs — so that every rank, this one
         // included, sees the failure in the data (the host-buffer entry turns it into an error code), and report the local error.
         const std::string local_error = ctx->error;
-        if (hipMemsetAsync(comm->packed, 0xFF, shard, ctx->stream) == hipSuccess && all_gather(comm, shard) == FTK_OK) {
-            (void)ftk_klt_unpack_shards_device(ctx, comm->gathered, n, comm->world, d_cur_uv_out, d_status_out);
+        if (hipMemsetAsync(comm->packed.get(), 0xFF, shard, ctx->stream) == hipSuccess && all_gather(comm, shard) == FTK_OK) {
+            (void)ftk_klt_unpack_shards_device(ctx, comm->gathered.get(), n, comm->world, d_cur_uv_out, d_status_out);
         }
         ctx->error = local_error;
         return rc;
@@ -308,7 +293,7 @@ int ftk_klt_track_sharded_device(ftk_context *ctx, ftk_comm *comm, int model, co
     if (rc != FTK_OK) {
         return rc;
     }
-    return ftk_klt_unpack_shards_device(ctx, comm->gathered, n, comm->world, d_cur_uv_out, d_status_out);
+    return ftk_klt_unpack_shards_device(ctx, comm->gathered.get(), n, comm->world, d_cur_uv_out, d_status_out);
 }
 
 int ftk_klt_track_sharded(ftk_context *ctx, ftk_comm *comm, int model, const ftk_klt_options *opt, const ftk_pyramid *ref, const ftk_pyramid *cur,
@@ -333,11 +318,11 @@ int ftk_klt_track_sharded(ftk_context *ctx, ftk_comm *comm, int model, const ftk
     FTK_HIP(ctx, hipSetDevice(ctx->device));
     const size_t uv_bytes = ftk_align_up(sizeof(float) * 2 * (size_t)n, 256), st_bytes = ftk_align_up((size_t)n, 256);
     const size_t it_bytes = ftk_align_up(sizeof(uint32_t) * (size_t)n, 256);
-    int rc = ftk_ensure_device_buffer(ctx, &comm->stage, &comm->stage_bytes, 2 * uv_bytes + st_bytes + it_bytes);
+    int rc = ftk_ensure_device_buffer(ctx, comm->stage, 2 * uv_bytes + st_bytes + it_bytes);
     if (rc != FTK_OK) {
         return rc;
     }
-    uint8_t *base = static_cast<uint8_t *>(comm->stage);
+    uint8_t *base = comm->stage.as<uint8_t>();
     float *d_ref = reinterpret_cast<float *>(base), *d_cur = reinterpret_cast<float *>(base + uv_bytes);
     uint8_t *d_st = base + 2 * uv_bytes;
     uint32_t *d_it = reinterpret_cast<uint32_t *>(base + 2 * uv_bytes + st_bytes);
@@ -407,7 +392,7 @@ int ftk_hamming_match_sharded_device(ftk_context *ctx, ftk_comm *comm, const uin
     if (rc != FTK_OK) {
         return rc;
     }
-    int32_t *local = static_cast<int32_t *>(comm->packed);
+    int32_t *local = comm->packed.as<int32_t>();
     if (m > 0) {
         FTK_HIP(ctx, hipMemcpyAsync(local, d_index_pairs + begin, sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToDevice, ctx->stream));
         rc = ftk_hamming_match_device(ctx, d_ref_words + (size_t)begin * n_words, m, d_cur_words, n_cur, n_words, n_bits, max_distance,
@@ -424,7 +409,7 @@ int ftk_hamming_match_sharded_device(ftk_context *ctx, ftk_comm *comm, const uin
         int32_t b = 0, e = 0;
         shard_range(n_ref, comm->world, r, &b, &e);
         if (e > b) {
-            FTK_HIP(ctx, hipMemcpyAsync(d_index_pairs + b, static_cast<const uint8_t *>(comm->gathered) + shard * (size_t)r, sizeof(int32_t) * (size_t)(e - b),
+            FTK_HIP(ctx, hipMemcpyAsync(d_index_pairs + b, comm->gathered.as<const uint8_t>() + shard * (size_t)r, sizeof(int32_t) * (size_t)(e - b),
                                         hipMemcpyDeviceToDevice, ctx->stream));
         }
     }

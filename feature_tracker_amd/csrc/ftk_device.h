@@ -1,4 +1,4 @@
-// ftk_device.h — structures shared between the host-side C ABI (ftk_api.cpp, ftk_klt.cpp) and the gfx950
+// ftk_device.h — structures shared between the host-side C ABI (the ftk_*.cpp files) and the gfx950
 // kernels (klt_kernels.hip, matcher_kernels.hip, pyramid_kernels.hip).
 #pragma once
 

@@ -1,4 +1,4 @@
-// ftk_internal.h — definitions shared by the translation units behind the C ABI (ftk_api.cpp, ftk_klt.cpp, ftk_comm.cpp).
+// ftk_internal.h — definitions shared by the translation units behind the C ABI (ftk_context.cpp and one ftk_*.cpp per family of entry points).
 // Not installed, not part of the boundary: include/ftk.h is.
 #pragma once
 
@@ -9,6 +9,7 @@
 #include <mutex>
 #include <string>
 
+#include "ftk_buffer.h"
 #include "ftk_device.h"
 
 using ftk::DevImage;
@@ -67,34 +68,21 @@ struct ftk_context {
     bool owns_stream = false;
     std::string error;
     ftk_env env;  // the experiment switches as they were when the context was made (or last refreshed)
-    // cached device scratch for the host-buffer entry points
-    void *scratch = nullptr;
-    size_t scratch_bytes = 0;
-    unsigned long long *match_keys = nullptr;
-    size_t match_keys_count = 0;
-    // keys of NNFeatureMatcher's post-processing (ftk_nn_match_*_device): all 0 = empty between calls; grown only outside a stream capture
-    unsigned long long *nn_keys = nullptr;
-    size_t nn_keys_count = 0;
-    float *match_boxes = nullptr;  // NearbyMatch bounding boxes (4 floats each)
-    size_t match_boxes_count = 0;
-    // workspace of the float-descriptor matcher (fp16 copies, norms, candidate lists)
-    void *cosine_ws = nullptr;
-    size_t cosine_ws_bytes = 0;
-    // problem table of the direct-method launches
-    void *direct_table = nullptr;
-    size_t direct_table_bytes = 0;
-    // per-feature projection tables of direct-method problems too large for LDS (16 B per tracked feature)
-    void *direct_feat = nullptr;
-    size_t direct_feat_bytes = 0;
-    // zero-padded copies of descriptors whose width is not a power of two (device-resident matcher entry)
+    // Every block below is an ftk_buffer: it grows where it is used and goes with the context (ftk_context_destroy frees none by name).
+    ftk_buffer scratch;      // cached device scratch for the host-buffer entry points
+    ftk_buffer match_keys;   // 8-byte keys of the Hamming matcher: all ones = "no match yet" between calls
+    ftk_buffer nn_keys;      // 8-byte keys of NNFeatureMatcher's post-processing (ftk_nn_match_*_device): all 0 = empty between calls; grown only outside a stream capture
+    ftk_buffer match_boxes;  // NearbyMatch bounding boxes (4 floats each)
+    ftk_buffer cosine_ws;    // workspace of the float-descriptor matcher (fp16 copies, norms, candidate lists)
+    ftk_buffer direct_table; // problem table of the direct-method launches
+    ftk_buffer direct_feat;  // per-feature projection tables of direct-method problems too large for LDS (16 B per tracked feature)
     // launch order of the trackers (ftk_klt_track_device): iteration counts of the last two calls and the permutations the
     // sort block of the tracker launches makes from them, double-buffered
-    uint32_t *sched_iters[2] = {nullptr, nullptr};
-    int32_t *sched_order[2] = {nullptr, nullptr};
+    ftk_buffer sched_iters[2];  // uint32_t
+    ftk_buffer sched_order[2];  // int32_t
     // position-keyed slot swaps (klt_common.h sched_resolve_slot): iteration counts by position (two hash tables), one claim word per launch slot
-    uint32_t *sched_grid = nullptr;
-    uint32_t *sched_claim = nullptr;
-    uint8_t *sched_pred = nullptr;    // predicted iteration count of every feature of the call in hand (position-keyed launch order)
+    ftk_buffer sched_grid, sched_claim;  // uint32_t
+    ftk_buffer sched_pred;            // uint8_t: predicted iteration count of every feature of the call in hand (position-keyed launch order)
     uint32_t sched_recorded = 0;      // sched_call of the last call that left its counts in the position table (0: none yet)
     uint32_t sched_call = 0;     // calls that used the grid so far (tags its entries and the claims)
     size_t sched_capacity = 0;   // features each buffer holds
@@ -103,36 +91,27 @@ struct ftk_context {
     // Tail-aware wave policy (round 5): the trackers' kernels report the iteration count of a call's LONGEST feature (features below
     // kTailReportFrom stay silent) into a device word per variant (atomicMax) whose raisers forward it to `tail_host`, device-visible host words
     // a later call's policy reads without any synchronisation: {call number << 8 | iterations}; feature 0 always reports, so every launch refreshes its word.  A heuristic input, never a result.
-    uint32_t *tail_host = nullptr;
-    uint32_t *tail_dev = nullptr;
+    ftk_buffer tail_host{ftk_buffer::kPinned}, tail_dev;  // 16 uint32_t each; allocated by a context's first tracker call outside a stream capture
     uint32_t tail_call = 0;                 // tracker launches of this context so far (tags the reports)
     struct TailState {
         uint32_t launches = 0;              // launches of this variant so far
         uint32_t long_until = 0;            // "this variant's calls have a long tail" while launches < long_until
         uint32_t longest = 0;               // the last long report's iteration count
     } tail[3][3];                           // [model][inverse, direct, fast]
-    void *match_pad = nullptr;
-    size_t match_pad_bytes = 0;
-    // per-workgroup slices of the trackers' large-patch form (ftk_device.h KltParams::spill)
-    void *klt_spill = nullptr;
-    size_t klt_spill_bytes = 0;
-    // hand-off workspace of the spread direct-method kernel (header, chunk flags, products)
-    void *direct_spread = nullptr;
-    size_t direct_spread_bytes = 0;
+    ftk_buffer match_pad;      // zero-padded copies of descriptors whose width is not a power of two (device-resident matcher entry)
+    ftk_buffer klt_spill;      // per-workgroup slices of the trackers' large-patch form (ftk_device.h KltParams::spill)
+    ftk_buffer direct_spread;  // hand-off workspace of the spread direct-method kernel (header, chunk flags, products)
     int direct_spread_resident = -1;            // workgroups of the spread kernel this device holds at once (-1: not asked yet)
     uint32_t direct_spread_resident_features = 0;
     int direct_spread_launched = 0;             // problems the LAST ftk_direct_track_batch_device call spread over the chip (0: one workgroup each; header word 1 != 0: its waits ran out)
     uint32_t direct_spread_reruns = 0;          // such re-runs so far (tests)
     // pinned host staging for the host-buffer entry points (one H2D + one D2H per call)
-    void *pinned = nullptr;
-    size_t pinned_bytes = 0;
-    // dense optical flow: moment images + flow planes (grown only outside a stream capture) and the Gaussian table of dense_half
-    void *dense_ws = nullptr;
-    size_t dense_ws_bytes = 0;
-    float *dense_weights = nullptr;
+    ftk_buffer pinned{ftk_buffer::kPinnedNonCoherent};
+    // dense optical flow: moment images + flow planes (grown only outside a stream capture) and the Gaussian table (floats) of dense_half
+    ftk_buffer dense_ws, dense_weights;
     int32_t dense_half = -1;
-    // BRIEF sampling pattern resident on the device, cached per (n_bits, half)
-    int8_t *brief_pattern = nullptr;
+    // BRIEF sampling pattern (int8_t) resident on the device, cached per (n_bits, half)
+    ftk_buffer brief_pattern;
     int32_t brief_bits = 0, brief_half = 0;
     // FTK_REDUCTION_EXACT (default) or FTK_REDUCTION_TREE: how the trackers' normal-equation sums are formed (ftk_set_reduction_mode)
     int32_t reduction = 0;
@@ -140,11 +119,15 @@ struct ftk_context {
     // pageable image: a CPU copy into the slot, then the launch reads the slot over PCIe — no staged hipMemcpy, no stream
     // synchronisation; a slot is reused only after the event recorded behind its last reader has passed)
     struct ImageStage {
-        uint8_t *host = nullptr;
+        ftk_buffer host{ftk_buffer::kPinned};
         const uint8_t *device_view = nullptr;
-        size_t bytes = 0;
         hipEvent_t done = nullptr;
         bool busy = false;
+        ~ImageStage() {
+            if (done) {
+                (void)hipEventDestroy(done);
+            }
+        }
     } image_stage[2];
     int image_stage_next = 0;
 };
@@ -153,13 +136,12 @@ struct ftk_pyramid {
     int device = 0;
     int32_t n_levels = 0;
     DevImage levels[FTK_MAX_LEVELS];
-    uint8_t *owned = nullptr;  // single allocation holding every owned level
+    ftk_buffer owned;  // single allocation holding every owned level
 };
 
 
 // Records the message on the context (or, with ctx == nullptr, for ftk_last_error(NULL)) and returns `code`.
 int ftk_fail(ftk_context *ctx, int code, const char *fmt, ...);
-#define fail ftk_fail
 
 #define FTK_HIP(ctx, expr)                                                                                   \
     do {                                                                                                     \
@@ -195,8 +177,41 @@ struct ftk_trace_scope {
     }
 };
 #define FTK_TRACE_SCOPE(name) ftk_trace_scope ftk_trace_scope_(name)
-// Grows a context-owned device buffer (stream-synchronising first: earlier launches may still read the old one).
-int ftk_ensure_device_buffer(ftk_context *ctx, void **buf, size_t *have, size_t bytes);
-// The context's device scratch / pinned host staging block of the host-buffer entry points, at least `bytes` large (ftk_api.cpp).
-int ftk_ensure_scratch(ftk_context *ctx, size_t bytes);
-int ftk_ensure_pinned(ftk_context *ctx, size_t bytes);
+
+// Is `stream` being captured into a graph?  The one place that asks; a query that fails counts as capturing (allocating,
+// synchronising or numbering a launch inside a capture is the mistake to avoid, refusing outside one merely costs a retry).
+inline bool ftk_stream_capturing(hipStream_t stream) {
+    hipStreamCaptureStatus status = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &status) != hipSuccess) {
+        (void)hipGetLastError();
+        return true;
+    }
+    return status != hipStreamCaptureStatusNone;
+}
+
+// Growth policies of the context's blocks (they decide when a call reallocates, and so first-call times).  The device scratch /
+// pinned host staging block of the host-buffer entry points: + 50 %, whole pages.
+inline int ftk_ensure_scratch(ftk_context *ctx, size_t bytes) {
+    FTK_HIP(ctx, ctx->scratch.reserve(ctx->stream, bytes, bytes / 2, 4096));
+    return FTK_OK;
+}
+// (Coarse-grained, non-coherent host memory: cacheable in the device's L2, coherent at kernel boundaries — which is all the
+// host-buffer entry points need: the host writes the block before the launch and reads it after the synchronisation.  The 2 000
+// workgroups of a zero-copy tracker call then share 64-byte lines instead of each crossing PCIe for its own 17 bytes, and their
+// results leave the chip as whole lines when the kernel ends: 2 000-feature call 68.1 / 71.2 -> 66.2 / 65.6 us, small calls unchanged.)
+inline int ftk_ensure_pinned(ftk_context *ctx, size_t bytes) {
+    FTK_HIP(ctx, ctx->pinned.reserve(ctx->stream, bytes, bytes / 2, 4096));
+    return FTK_OK;
+}
+// Every other workspace that grows with the call: + 25 %, whole pages.
+inline int ftk_ensure_device_buffer(ftk_context *ctx, ftk_buffer &buf, size_t bytes) {
+    FTK_HIP(ctx, buf.reserve(ctx->stream, bytes, bytes / 4, 4096));
+    return FTK_OK;
+}
+
+// Helpers of one family that ftk_warmup uses too.
+// The next image-staging slot, free and at least `bytes` large (ImageStage above); *out stays null when the device cannot address
+// pinned host memory (the callers then take their copy paths).  ftk_pyramid.cpp
+int ftk_acquire_image_stage(ftk_context *ctx, size_t bytes, ftk_context::ImageStage **out);
+int ftk_ensure_match_keys(ftk_context *ctx, size_t count);                      // ftk_match.cpp
+int ftk_ensure_brief_pattern(ftk_context *ctx, int32_t n_bits, int32_t half);   // ftk_features.cpp

@@ -15,8 +15,6 @@
 
 namespace {
 
-size_t align_up(size_t x, size_t a) { return ftk_align_up(x, a); }
-
 constexpr uint32_t kSchedMinFeatures = 4096;  // below this (nearly) every feature is resident from the start: nothing to order ...
 constexpr uint32_t kSchedMinLongTail = 1024;  // ... unless the calls have a long tail (see ftk_klt_track_device)
 constexpr size_t kSchedTableWords = (2u << 16) + 2;  // two position tables of 2^16 entries (klt_common.h kSchedTableSize) + the two "no tail" flags behind them
@@ -28,28 +26,28 @@ constexpr uint32_t kTailFresh = 256;    // launches of the context a report may 
 
 int klt_check_call(ftk_context *ctx, int model, const ftk_klt_options *opt, const ftk_pyramid *ref, const ftk_pyramid *cur) {
     if (!opt || !ref || !cur) {
-        return fail(ctx, FTK_E_INVALID_ARGUMENT, "klt: null options or pyramid");
+        return ftk_fail(ctx, FTK_E_INVALID_ARGUMENT, "klt: null options or pyramid");
     }
     if (model < FTK_MODEL_BASIC || model > FTK_MODEL_LSSD) {
-        return fail(ctx, FTK_E_INVALID_ARGUMENT, "klt: unknown model %d", model);
+        return ftk_fail(ctx, FTK_E_INVALID_ARGUMENT, "klt: unknown model %d", model);
     }
     if (opt->method < FTK_METHOD_INVERSE || opt->method > FTK_METHOD_NEON) {
-        return fail(ctx, FTK_E_INVALID_ARGUMENT, "klt: unknown method %d", opt->method);
+        return ftk_fail(ctx, FTK_E_INVALID_ARGUMENT, "klt: unknown method %d", opt->method);
     }
     if (ref->n_levels != cur->n_levels) {
         // OpticalFlow::TrackFeatures returns false here (optical_flow.cpp:9); callers above the ABI handle it
-        return fail(ctx, FTK_E_INVALID_ARGUMENT, "klt: pyramid level mismatch (%d vs %d)", ref->n_levels, cur->n_levels);
+        return ftk_fail(ctx, FTK_E_INVALID_ARGUMENT, "klt: pyramid level mismatch (%d vs %d)", ref->n_levels, cur->n_levels);
     }
     if (ref->n_levels < 1) {
-        return fail(ctx, FTK_E_INVALID_ARGUMENT, "klt: empty pyramid");
+        return ftk_fail(ctx, FTK_E_INVALID_ARGUMENT, "klt: empty pyramid");
     }
     if (ref->device != ctx->device || cur->device != ctx->device) {
-        return fail(ctx, FTK_E_INVALID_ARGUMENT, "klt: pyramid lives on another device");
+        return ftk_fail(ctx, FTK_E_INVALID_ARGUMENT, "klt: pyramid lives on another device");
     }
     // The reference takes any int32 half size (optical_flow.h:24-25).  Here: up to 1023 (a 2047 x 2047 patch; pixel indices stay
     // below 2^23 for the 24-bit multiplier); patches beyond a workgroup's LDS run the large-patch form below.
     if (opt->half_rows < 0 || opt->half_cols < 0 || opt->half_rows > 1023 || opt->half_cols > 1023) {
-        return fail(ctx, FTK_E_UNSUPPORTED, "klt: half patch size (%d, %d) outside [0, 1023]", opt->half_rows, opt->half_cols);
+        return ftk_fail(ctx, FTK_E_UNSUPPORTED, "klt: half patch size (%d, %d) outside [0, 1023]", opt->half_rows, opt->half_cols);
     }
     return FTK_OK;
 }
@@ -73,7 +71,7 @@ int klt_tail_class(ftk_context *ctx, int model, int method) {
         // this variant's own word: {call number << 8 | iterations} of the longest feature of its most recent launch that has got that
         // far.  The host may be many launches ahead of the device (back-to-back calls), so a report counts while it is at most
         // kTailFresh launches of the context old, and one long report holds for kTailHold launches of the variant.
-        const uint32_t seen = reinterpret_cast<volatile uint32_t *>(ctx->tail_host)[model * 3 + mi];
+        const uint32_t seen = ctx->tail_host.as<volatile uint32_t>()[model * 3 + mi];
         const uint32_t age = (ctx->tail_call - (seen >> 8)) & 0xFFFFFFu;
         if (seen != 0 && age <= kTailFresh && (seen & 0xFFu) >= kTailLongFrom) {
             ts.long_until = ts.launches + kTailHold;
@@ -125,38 +123,36 @@ int klt_plan_call(ftk_context *ctx, int model, const ftk_klt_options *opt, const
     in.spill = FTK_ENV(ctx, klt_spill) ? atoi(FTK_ENV(ctx, klt_spill)) : ftk::kKltNotSet;
     size_t spill_floats = 0;
     switch (ftk::klt_plan(in, &p, plan, &spill_floats)) {
-        case ftk::kKltPlanUnknownVariant: return fail(ctx, FTK_E_UNSUPPORTED, "klt: unknown variant (model %d, method %d)", model, opt->method);
+        case ftk::kKltPlanUnknownVariant: return ftk_fail(ctx, FTK_E_UNSUPPORTED, "klt: unknown variant (model %d, method %d)", model, opt->method);
         case ftk::kKltPlanSpillTooLarge:
-            return fail(ctx, FTK_E_UNSUPPORTED, "klt: patch %dx%d needs %zu floats of device memory per feature", p.patch_rows, p.patch_cols, spill_floats);
+            return ftk_fail(ctx, FTK_E_UNSUPPORTED, "klt: patch %dx%d needs %zu floats of device memory per feature", p.patch_rows, p.patch_cols, spill_floats);
         default: return FTK_OK;
     }
 }
 
-// This launch's number, for the report of its longest feature (the tail words are allocated on a context's first tracker call).
+// This launch's number, for the report of its longest feature (the tail words are allocated on a context's first tracker call
+// outside a stream capture; until then, and when that fails, the launches carry no tail words).
 void klt_tail_number(ftk_context *ctx, int model, int method, ftk::KltParams &p) {
-    if (!ctx->tail_host) {
-        void *host = nullptr;
-        if (hipHostMalloc(&host, 64, hipHostMallocDefault) == hipSuccess && hipMalloc(reinterpret_cast<void **>(&ctx->tail_dev), 64) == hipSuccess) {
-            memset(host, 0, 64);
-            ctx->tail_host = static_cast<uint32_t *>(host);
-            (void)hipMemsetAsync(ctx->tail_dev, 0, 64, ctx->stream);
+    if (!ctx->tail_host && !ftk_stream_capturing(ctx->stream)) {
+        if (ctx->tail_host.reserve(ctx->stream, 64, 0, 1) == hipSuccess && ctx->tail_dev.reserve(ctx->stream, 64, 0, 1) == hipSuccess) {
+            memset(ctx->tail_host.get(), 0, 64);
+            (void)hipMemsetAsync(ctx->tail_dev.get(), 0, 64, ctx->stream);
         } else {
             (void)hipGetLastError();
-            if (host) {
-                (void)hipHostFree(host);
-            }
+            ctx->tail_host.release();
+            ctx->tail_dev.release();
         }
     }
     if (ctx->tail_host && ctx->tail_dev) {
         ctx->tail_call = (ctx->tail_call + 1u) & 0xFFFFFFu;
         if (ctx->tail_call == 0u) {
             ctx->tail_call = 1u;  // (after 16 M launches the device word's running maximum starts over with the host's)
-            (void)hipMemsetAsync(ctx->tail_dev, 0, 64, ctx->stream);
+            (void)hipMemsetAsync(ctx->tail_dev.get(), 0, 64, ctx->stream);
         }
         const int mi = method == FTK_METHOD_INVERSE ? 0 : (method == FTK_METHOD_DIRECT ? 1 : 2);
         ++ctx->tail[model][mi].launches;
-        p.tail_dev = ctx->tail_dev + (model * 3 + mi);    // a word per variant
-        p.tail_host = ctx->tail_host + (model * 3 + mi);  // (hipHostMalloc'ed memory is device-visible under the same address)
+        p.tail_dev = ctx->tail_dev.as<uint32_t>() + (model * 3 + mi);    // a word per variant
+        p.tail_host = ctx->tail_host.as<uint32_t>() + (model * 3 + mi);  // (pinned host memory is device-visible under the same address)
         p.tail_call = ctx->tail_call;
     }
 }
@@ -172,20 +168,17 @@ int klt_launch_spilled(ftk_context *ctx, int model, int method, ftk::KltParams &
     }
     size_t batch = budget / per;
     batch = batch < 1 ? 1 : (batch > (size_t)n ? (size_t)n : batch);
-    if (batch * per > ctx->klt_spill_bytes) {
-        // the slices would have to grow: a hipFree / hipMalloc (and a synchronisation) that a stream capture cannot contain
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(ctx->stream, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) {
-            return fail(ctx, FTK_E_UNSUPPORTED, "klt_track_device: a %d x %d patch needs %zu MB of device memory for its per-feature slices, which cannot be "
+    // the slices would have to grow: a release, an allocation (and a synchronisation) that a stream capture cannot contain
+    if (batch * per > ctx->klt_spill.bytes() && ftk_stream_capturing(ctx->stream)) {
+        return ftk_fail(ctx, FTK_E_UNSUPPORTED, "klt_track_device: a %d x %d patch needs %zu MB of device memory for its per-feature slices, which cannot be "
                         "allocated while the stream is being captured: make one such call before the capture (the buffer is kept)", p.patch_rows, p.patch_cols,
                         (batch * per) >> 20);
-        }
     }
-    const int rc_buf = ftk_ensure_device_buffer(ctx, &ctx->klt_spill, &ctx->klt_spill_bytes, batch * per);
+    const int rc_buf = ftk_ensure_device_buffer(ctx, ctx->klt_spill, batch * per);
     if (rc_buf != FTK_OK) {
         return rc_buf;
     }
-    p.spill_base = static_cast<float *>(ctx->klt_spill);
+    p.spill_base = ctx->klt_spill.as<float>();
     ctx->sched_calls = 0;  // no launch order for these calls; a later ordinary call starts its history over
     ctx->sched_n = 0;
     for (size_t b0 = 0; b0 < (size_t)n; b0 += batch) {
@@ -203,7 +196,7 @@ int klt_launch_spilled(ftk_context *ctx, int model, int method, ftk::KltParams &
         batch_plan.grid = (unsigned)nb;  // one workgroup per feature in this form
         const hipError_t e = ftk::klt_launch(batch_plan, model, method, q, ctx->stream);
         if (e != hipSuccess) {
-            return fail(ctx, e == hipErrorOutOfMemory ? FTK_E_OUT_OF_MEMORY : FTK_E_HIP, "klt launch (large patch) failed: %s", hipGetErrorString(e));
+            return ftk_fail(ctx, e == hipErrorOutOfMemory ? FTK_E_OUT_OF_MEMORY : FTK_E_HIP, "klt launch (large patch) failed: %s", hipGetErrorString(e));
         }
     }
     return FTK_OK;
@@ -230,40 +223,24 @@ int klt_sched_prepare(ftk_context *ctx, int model, int32_t n, int long_tail, ftk
                                                            : (long_tail ? kSchedMinLongTail : kSchedMinFeatures);
     if (sched_allowed && p.n_track >= sched_min && n <= kSchedMaxFeatures) {
         if ((size_t)n > ctx->sched_capacity) {
-            FTK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            for (int k = 0; k < 2; ++k) {
-                if (ctx->sched_iters[k]) {
-                    (void)hipFree(ctx->sched_iters[k]);
-                    (void)hipFree(ctx->sched_order[k]);
-                    ctx->sched_iters[k] = nullptr;
-                    ctx->sched_order[k] = nullptr;
-                }
-            }
-            if (ctx->sched_claim) {
-                (void)hipFree(ctx->sched_claim);
-                ctx->sched_claim = nullptr;
-            }
-            if (ctx->sched_pred) {
-                (void)hipFree(ctx->sched_pred);
-                ctx->sched_pred = nullptr;
-            }
             ctx->sched_capacity = 0;
             ctx->sched_n = 0;
             const size_t cap = ((size_t)n + 4095) / 4096 * 4096;
             // position-keyed slot swaps: a claim word per launch slot, and (once) the two tables of iteration counts by position
-            FTK_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->sched_claim), sizeof(uint32_t) * cap));
-            FTK_HIP(ctx, hipMemsetAsync(ctx->sched_claim, 0, sizeof(uint32_t) * cap, ctx->stream));
-            FTK_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->sched_pred), cap));
-            if (!ctx->sched_grid) {
-                FTK_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->sched_grid), sizeof(uint32_t) * (kSchedTableWords + kSchedOrderWords)));
-                FTK_HIP(ctx, hipMemsetAsync(ctx->sched_grid, 0, sizeof(uint32_t) * kSchedTableWords, ctx->stream));
+            FTK_HIP(ctx, ctx->sched_claim.reserve(ctx->stream, sizeof(uint32_t) * cap, 0, 1));
+            FTK_HIP(ctx, hipMemsetAsync(ctx->sched_claim.get(), 0, sizeof(uint32_t) * cap, ctx->stream));
+            FTK_HIP(ctx, ctx->sched_pred.reserve(ctx->stream, cap, 0, 1));
+            bool new_grid = false;
+            FTK_HIP(ctx, ctx->sched_grid.reserve(ctx->stream, sizeof(uint32_t) * (kSchedTableWords + kSchedOrderWords), 0, 1, &new_grid));
+            if (new_grid) {
+                FTK_HIP(ctx, hipMemsetAsync(ctx->sched_grid.get(), 0, sizeof(uint32_t) * kSchedTableWords, ctx->stream));
             }
             for (int k = 0; k < 2; ++k) {
-                FTK_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->sched_iters[k]), sizeof(uint32_t) * cap));
-                FTK_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->sched_order[k]), sizeof(int32_t) * cap));
+                FTK_HIP(ctx, ctx->sched_iters[k].reserve(ctx->stream, sizeof(uint32_t) * cap, 0, 1));
+                FTK_HIP(ctx, ctx->sched_order[k].reserve(ctx->stream, sizeof(int32_t) * cap, 0, 1));
                 // never-written entries must still be valid feature ids (0) and valid counts, whatever happens to a launch
-                FTK_HIP(ctx, hipMemsetAsync(ctx->sched_iters[k], 0, sizeof(uint32_t) * cap, ctx->stream));
-                FTK_HIP(ctx, hipMemsetAsync(ctx->sched_order[k], 0, sizeof(int32_t) * cap, ctx->stream));
+                FTK_HIP(ctx, hipMemsetAsync(ctx->sched_iters[k].get(), 0, sizeof(uint32_t) * cap, ctx->stream));
+                FTK_HIP(ctx, hipMemsetAsync(ctx->sched_order[k].get(), 0, sizeof(int32_t) * cap, ctx->stream));
             }
             ctx->sched_capacity = cap;
         }
@@ -276,11 +253,7 @@ int klt_sched_prepare(ftk_context *ctx, int model, int32_t n, int long_tail, ftk
         // all-zero grid / claim word is never "recent") and tag 23 bits of a claim word: the claims are wiped before a tag could
         // repeat.
         // (never inside a stream capture: a replayed launch would carry this call's number again and read its own old claims)
-        hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(ctx->stream, &capture) != hipSuccess) {
-            (void)hipGetLastError();
-            capture = hipStreamCaptureStatusActive;  // unknown: be safe
-        }
+        const bool capturing = ftk_stream_capturing(ctx->stream);
         // (nor when the results overwrite the reference positions: both sides of a trade must read the same positions)
         const char *ref_lo = reinterpret_cast<const char *>(p.ref_uv), *out_lo = reinterpret_cast<const char *>(p.cur_uv_out);
         const size_t uv_span = sizeof(float) * 2 * (size_t)n;
@@ -291,7 +264,7 @@ int klt_sched_prepare(ftk_context *ctx, int model, int32_t n, int long_tail, ftk
         // (config 4: +2.9 % with a fitting order, -3 % without; config 5: +1 %).
         // EVERY such call (outside a capture) leaves its iteration counts in the position table — one or two atomics per feature —
         // so that the next one can order or trade by position whatever kernel either of them runs.
-        const bool recording = capture == hipStreamCaptureStatusNone && ctx->sched_grid && ctx->sched_claim;
+        const bool recording = !capturing && ctx->sched_grid && ctx->sched_claim;
         uint32_t last_recorded = 0;
         if (recording) {
             if (ctx->sched_call < 4u) {
@@ -299,24 +272,24 @@ int klt_sched_prepare(ftk_context *ctx, int model, int32_t n, int long_tail, ftk
             }
             ++ctx->sched_call;
             if ((ctx->sched_call & 0x7FFFFFu) < 4u) {
-                FTK_HIP(ctx, hipMemsetAsync(ctx->sched_claim, 0, sizeof(uint32_t) * ctx->sched_capacity, ctx->stream));
-                FTK_HIP(ctx, hipMemsetAsync(ctx->sched_grid, 0, sizeof(uint32_t) * kSchedTableWords, ctx->stream));
+                FTK_HIP(ctx, hipMemsetAsync(ctx->sched_claim.get(), 0, sizeof(uint32_t) * ctx->sched_capacity, ctx->stream));
+                FTK_HIP(ctx, hipMemsetAsync(ctx->sched_grid.get(), 0, sizeof(uint32_t) * kSchedTableWords, ctx->stream));
                 ctx->sched_call += 4u;
                 ctx->sched_recorded = 0;
             }
-            p.sched_grid = ctx->sched_grid;
+            p.sched_grid = ctx->sched_grid.as<uint32_t>();
             p.sched_call = ctx->sched_call;
             last_recorded = ctx->sched_recorded;
             ctx->sched_recorded = ctx->sched_call;
         }
         if (recording && p.waves_per_feature >= 2 && ref_untouched && n > 1024 + 512) {
-            p.sched_flags = ctx->sched_grid + (2u << 16);
-            p.sched_claim = ctx->sched_claim;
+            p.sched_flags = ctx->sched_grid.as<uint32_t>() + (2u << 16);
+            p.sched_claim = ctx->sched_claim.as<uint32_t>();
         }
-        p.sched_iters = ctx->sched_iters[k & 1];          // this call's counts
+        p.sched_iters = ctx->sched_iters[k & 1].as<uint32_t>();          // this call's counts
         if (k >= 1) {                                     // sort the previous call's counts beside this call's features
-            p.sort_iters = ctx->sched_iters[(k - 1) & 1];
-            p.sort_order_out = ctx->sched_order[(k - 1) & 1];
+            p.sort_iters = ctx->sched_iters[(k - 1) & 1].as<uint32_t>();
+            p.sort_order_out = ctx->sched_order[(k - 1) & 1].as<int32_t>();
             // The spatial (tile) order reads the reference positions in two passes while the feature workgroups of the same
             // launch write cur_uv_out: with one position buffer updated in place (ref == out, allowed by include/ftk.h) a
             // feature crossing a tile boundary in between would make the histogram and the scatter disagree — duplicates,
@@ -324,7 +297,7 @@ int klt_sched_prepare(ftk_context *ctx, int model, int32_t n, int long_tail, ftk
             p.sort_ref_uv = ref_untouched ? p.ref_uv : nullptr;
         }
         if (k >= 2) {                                     // made during the previous call from the counts before it
-            p.order = ctx->sched_order[k & 1];
+            p.order = ctx->sched_order[k & 1].as<int32_t>();
         } else if (recording && last_recorded != 0u && last_recorded + 1u == ctx->sched_call && ctx->sched_pred && model != FTK_MODEL_BASIC &&
                    p.sched_claim == nullptr) {
             // (LSSD and affine KLT: their iteration counts have tails — config 4 without history 206 -> 183 us, with luminance
@@ -334,15 +307,15 @@ int klt_sched_prepare(ftk_context *ctx, int model, int32_t n, int long_tail, ftk
             // last call left at its features' positions — two small launches in front of the tracker's (klt_kernels.hip
             // klt_position_order_launch).  The buffer is the one an index-keyed order of this call would have used: nobody else
             // writes it during this call.
-            const uint32_t *last_table = ctx->sched_grid + (((ctx->sched_call - 1u) & 1u) << 16);
-            FTK_HIP(ctx, ftk::klt_position_order_launch(p.ref_uv, n, last_table, ctx->sched_call - 1u, ctx->sched_pred, ctx->sched_grid + kSchedTableWords,
-                                                        ctx->sched_order[k & 1], ctx->stream));
-            p.order = ctx->sched_order[k & 1];
+            const uint32_t *last_table = ctx->sched_grid.as<uint32_t>() + (((ctx->sched_call - 1u) & 1u) << 16);
+            FTK_HIP(ctx, ftk::klt_position_order_launch(p.ref_uv, n, last_table, ctx->sched_call - 1u, ctx->sched_pred.as<uint8_t>(),
+                                                        ctx->sched_grid.as<uint32_t>() + kSchedTableWords, ctx->sched_order[k & 1].as<int32_t>(), ctx->stream));
+            p.order = ctx->sched_order[k & 1].as<int32_t>();
         }
         if (const char *dump = FTK_ENV(ctx, klt_swap_dump)) {  // diagnostic: how many trades the PREVIOUS launch of this context made
             if (p.sched_claim != nullptr && ctx->sched_call > 5u) {
                 std::vector<uint32_t> h((size_t)n);
-                FTK_HIP(ctx, hipMemcpyAsync(h.data(), ctx->sched_claim, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+                FTK_HIP(ctx, hipMemcpyAsync(h.data(), ctx->sched_claim.as<uint32_t>(), sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
                 FTK_HIP(ctx, hipStreamSynchronize(ctx->stream));
                 const uint32_t last = (ctx->sched_call - 1u) & 0x7FFFFFu;
                 size_t trades = 0, own = 0;
@@ -360,8 +333,8 @@ int klt_sched_prepare(ftk_context *ctx, int model, int32_t n, int long_tail, ftk
         if (const char *dump = FTK_ENV(ctx, klt_sched_dump)) {  // diagnostic: the permutation in use and the counts it came from
             if (k >= 2) {
                 std::vector<int32_t> h((size_t)n * 2);
-                FTK_HIP(ctx, hipMemcpyAsync(h.data(), ctx->sched_order[k & 1], sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-                FTK_HIP(ctx, hipMemcpyAsync(h.data() + n, ctx->sched_iters[k & 1], sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+                FTK_HIP(ctx, hipMemcpyAsync(h.data(), ctx->sched_order[k & 1].as<int32_t>(), sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+                FTK_HIP(ctx, hipMemcpyAsync(h.data() + n, ctx->sched_iters[k & 1].as<uint32_t>(), sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
                 FTK_HIP(ctx, hipStreamSynchronize(ctx->stream));
                 if (FILE *f = fopen(dump, "wb")) {
                     fwrite(h.data(), sizeof(int32_t), h.size(), f);
@@ -392,23 +365,23 @@ int ftk_klt_track_device(ftk_context *ctx, int model, const ftk_klt_options *opt
                          const float *d_ref_uv, const float *d_cur_uv_in, float *d_cur_uv_out, const uint8_t *d_status_in,
                          uint8_t *d_status_out, int32_t n, const float *prior, int consider_luminance, int single_level, uint32_t *d_iters) {
     if (!ctx) {
-        return fail(nullptr, FTK_E_INVALID_ARGUMENT, "klt_track_device: null context");
+        return ftk_fail(nullptr, FTK_E_INVALID_ARGUMENT, "klt_track_device: null context");
     }
     FTK_LOCK(ctx);
     if (n < 0) {
-        return fail(ctx, FTK_E_INVALID_ARGUMENT, "klt_track_device: negative feature count");
+        return ftk_fail(ctx, FTK_E_INVALID_ARGUMENT, "klt_track_device: negative feature count");
     }
     if (n == 0) {
         return FTK_OK;
     }
     if (!d_ref_uv || !d_cur_uv_in || !d_cur_uv_out || !d_status_in || !d_status_out) {
-        return fail(ctx, FTK_E_INVALID_ARGUMENT, "klt_track_device: null buffer");
+        return ftk_fail(ctx, FTK_E_INVALID_ARGUMENT, "klt_track_device: null buffer");
     }
     // The kernels read and write a feature's (u, v) as ONE 8-byte access (include/ftk.h: "8-byte aligned"): a pair array at an odd
     // float offset — legal through round 3 — is refused here instead of becoming misaligned 64-bit accesses on the device.
     if (((reinterpret_cast<uintptr_t>(d_ref_uv) | reinterpret_cast<uintptr_t>(d_cur_uv_in) | reinterpret_cast<uintptr_t>(d_cur_uv_out)) & 7u) != 0) {
-        return fail(ctx, FTK_E_INVALID_ARGUMENT, "klt_track_device: the (u, v) arrays must be 8-byte aligned (ref %p, in %p, out %p)", (const void *)d_ref_uv,
-                    (const void *)d_cur_uv_in, (const void *)d_cur_uv_out);
+        return ftk_fail(ctx, FTK_E_INVALID_ARGUMENT, "klt_track_device: the (u, v) arrays must be 8-byte aligned (ref %p, in %p, out %p)", (const void *)d_ref_uv,
+                        (const void *)d_cur_uv_in, (const void *)d_cur_uv_out);
     }
     int rc = klt_check_call(ctx, model, opt, ref, cur);
     if (rc != FTK_OK) {
@@ -442,7 +415,7 @@ int ftk_klt_track_device(ftk_context *ctx, int model, const ftk_klt_options *opt
         // on) a permutation: it did neither, so the history starts over — the next call must not install an order nobody wrote.
         ctx->sched_calls = 0;
         ctx->sched_n = 0;
-        return fail(ctx, launch_rc == hipErrorOutOfMemory ? FTK_E_OUT_OF_MEMORY : FTK_E_HIP, "klt launch failed: %s", hipGetErrorString(launch_rc));
+        return ftk_fail(ctx, launch_rc == hipErrorOutOfMemory ? FTK_E_OUT_OF_MEMORY : FTK_E_HIP, "klt launch failed: %s", hipGetErrorString(launch_rc));
     }
     return FTK_OK;
 }
@@ -451,24 +424,24 @@ int ftk_klt_track(ftk_context *ctx, int model, const ftk_klt_options *opt, const
                   float *cur_uv, uint8_t *status, int32_t n, const float *prior, int consider_luminance, int single_level, uint32_t *iters) {
     FTK_TRACE_SCOPE("ftk_klt_track");
     if (!ctx) {
-        return fail(nullptr, FTK_E_INVALID_ARGUMENT, "klt_track: null context");
+        return ftk_fail(nullptr, FTK_E_INVALID_ARGUMENT, "klt_track: null context");
     }
     FTK_LOCK(ctx);
     if (n < 0) {
-        return fail(ctx, FTK_E_INVALID_ARGUMENT, "klt_track: negative feature count");
+        return ftk_fail(ctx, FTK_E_INVALID_ARGUMENT, "klt_track: negative feature count");
     }
     if (n == 0) {
         return FTK_OK;
     }
     if (!ref_uv || !cur_uv || !status) {
-        return fail(ctx, FTK_E_INVALID_ARGUMENT, "klt_track: null buffer");
+        return ftk_fail(ctx, FTK_E_INVALID_ARGUMENT, "klt_track: null buffer");
     }
     FTK_HIP(ctx, hipSetDevice(ctx->device));
     // One contiguous block [ref_uv | cur_uv | status | iters], mirrored in pinned host memory:
     // a single H2D of (ref_uv, cur_uv, status) and a single D2H of (cur_uv, status, iters) per call.
-    const size_t uv_bytes = align_up(sizeof(float) * 2 * (size_t)n, 256);
-    const size_t st_bytes = align_up((size_t)n, 256);
-    const size_t it_bytes = align_up(sizeof(uint32_t) * (size_t)n, 256);
+    const size_t uv_bytes = ftk_align_up(sizeof(float) * 2 * (size_t)n, 256);
+    const size_t st_bytes = ftk_align_up((size_t)n, 256);
+    const size_t it_bytes = ftk_align_up(sizeof(uint32_t) * (size_t)n, 256);
     const size_t total = 2 * uv_bytes + st_bytes + it_bytes;
     int rc = ftk_ensure_scratch(ctx, total);
     if (rc != FTK_OK) {
@@ -478,8 +451,8 @@ int ftk_klt_track(ftk_context *ctx, int model, const ftk_klt_options *opt, const
     if (rc != FTK_OK) {
         return rc;
     }
-    uint8_t *dbase = static_cast<uint8_t *>(ctx->scratch);
-    uint8_t *hbase = static_cast<uint8_t *>(ctx->pinned);
+    uint8_t *dbase = ctx->scratch.as<uint8_t>();
+    uint8_t *hbase = ctx->pinned.as<uint8_t>();
     float *d_ref = reinterpret_cast<float *>(dbase);
     float *d_cur = reinterpret_cast<float *>(dbase + uv_bytes);
     uint8_t *d_st = dbase + 2 * uv_bytes;
@@ -492,7 +465,7 @@ int ftk_klt_track(ftk_context *ctx, int model, const ftk_klt_options *opt, const
     // feature straight into the pinned host block over PCIe — no H2D / D2H at all (2 000 features: 89 -> ~60 us per
     // call).  Larger calls keep the bulk copies.
     void *mapped = nullptr;
-    if (n <= 16384 && hipHostGetDevicePointer(&mapped, ctx->pinned, 0) == hipSuccess && mapped != nullptr) {
+    if (n <= 16384 && hipHostGetDevicePointer(&mapped, ctx->pinned.get(), 0) == hipSuccess && mapped != nullptr) {
         uint8_t *mbase = static_cast<uint8_t *>(mapped);
         float *m_ref = reinterpret_cast<float *>(mbase);
         float *m_cur = reinterpret_cast<float *>(mbase + uv_bytes);
@@ -534,21 +507,21 @@ int ftk_extract_extend_patch(ftk_context *ctx, const ftk_pyramid *ref, int32_t l
                              float *ex_patch, uint8_t *valid, uint32_t *valid_count) {
     FTK_TRACE_SCOPE("ftk_extract_extend_patch");
     if (!ctx) {
-        return fail(nullptr, FTK_E_INVALID_ARGUMENT, "extract_extend_patch: null context");
+        return ftk_fail(nullptr, FTK_E_INVALID_ARGUMENT, "extract_extend_patch: null context");
     }
     FTK_LOCK(ctx);
     if (!ref || level < 0 || level >= ref->n_levels || ex_rows <= 0 || ex_cols <= 0 || !ex_patch || !valid || !valid_count) {
-        return fail(ctx, FTK_E_INVALID_ARGUMENT, "extract_extend_patch: bad arguments");
+        return ftk_fail(ctx, FTK_E_INVALID_ARGUMENT, "extract_extend_patch: bad arguments");
     }
     FTK_HIP(ctx, hipSetDevice(ctx->device));
     const size_t n = (size_t)ex_rows * ex_cols;
-    const size_t patch_bytes = align_up(sizeof(float) * n, 256);
-    const size_t valid_bytes = align_up(n, 256);
+    const size_t patch_bytes = ftk_align_up(sizeof(float) * n, 256);
+    const size_t valid_bytes = ftk_align_up(n, 256);
     int rc = ftk_ensure_scratch(ctx, patch_bytes + valid_bytes + 256);
     if (rc != FTK_OK) {
         return rc;
     }
-    uint8_t *base = static_cast<uint8_t *>(ctx->scratch);
+    uint8_t *base = ctx->scratch.as<uint8_t>();
     float *d_patch = reinterpret_cast<float *>(base);
     uint8_t *d_valid = base + patch_bytes;
     uint32_t *d_count = reinterpret_cast<uint32_t *>(base + patch_bytes + valid_bytes);

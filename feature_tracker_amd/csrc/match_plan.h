@@ -1,6 +1,6 @@
 // match_plan.h — the launch plans of the Hamming matcher, the cosine matcher and the direct method, as klt_plan.h is the trackers':
 // pure functions of values (no context, no environment, no HIP call; tests/test_match_plan_cpu.py walks them without a device).
-// The entry points (ftk_api.cpp) parse the FTK_* overrides, plan, hold the buffers the plan asks for; the launchers carry it out.
+// The entry points (ftk_match.cpp, ftk_direct.cpp, ftk_nn.cpp) parse the FTK_* overrides, plan, hold the buffers the plan asks for; the launchers carry it out.
 #pragma once
 
 #include <limits.h>
