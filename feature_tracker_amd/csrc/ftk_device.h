@@ -146,7 +146,7 @@ __host__ __device__ constexpr void klt_fill_geometry(KltParams &p) {
 
 // (the trackers' launch plan, per-form LDS sizes, kernel pickers and klt_launch: klt_plan.h)
 // Launch order of THIS call from the position table the last call wrote (klt_kernels.hip): order[slot] = feature, predicted-longest
-// first.  last_table: 2^16 words; pred: n bytes; hist_and_cursor: 512 words (zeroed here).
+// first.  last_table: 2^16 words; pred: n bytes; hist_and_cursor: kSchedOrderWords (klt_sched.h) words (zeroed here).
 hipError_t klt_position_order_launch(const float *ref_uv, int32_t n, const uint32_t *last_table, uint32_t last_call, uint8_t *pred, uint32_t *hist_and_cursor,
                                      int32_t *order, hipStream_t stream);
 // Lane-parallel 6x6 LDLT (klt_common.h) on n systems, one wave each: the test hook behind ftk_ldlt6_solve.

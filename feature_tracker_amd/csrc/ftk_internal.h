@@ -11,6 +11,7 @@
 
 #include "ftk_buffer.h"
 #include "ftk_device.h"
+#include "klt_sched.h"
 
 using ftk::DevImage;
 
@@ -83,21 +84,12 @@ struct ftk_context {
     // position-keyed slot swaps (klt_common.h sched_resolve_slot): iteration counts by position (two hash tables), one claim word per launch slot
     ftk_buffer sched_grid, sched_claim;  // uint32_t
     ftk_buffer sched_pred;            // uint8_t: predicted iteration count of every feature of the call in hand (position-keyed launch order)
-    uint32_t sched_recorded = 0;      // sched_call of the last call that left its counts in the position table (0: none yet)
-    uint32_t sched_call = 0;     // calls that used the grid so far (tags its entries and the claims)
-    size_t sched_capacity = 0;   // features each buffer holds
-    int32_t sched_n = 0;         // feature count of the calls counted in sched_calls
-    uint32_t sched_calls = 0;    // consecutive calls with that feature count so far
+    ftk::KltSchedState sched;         // which order the next call gets (klt_sched.h klt_sched_step)
     // Tail-aware wave policy (round 5): the trackers' kernels report the iteration count of a call's LONGEST feature (features below
     // kTailReportFrom stay silent) into a device word per variant (atomicMax) whose raisers forward it to `tail_host`, device-visible host words
     // a later call's policy reads without any synchronisation: {call number << 8 | iterations}; feature 0 always reports, so every launch refreshes its word.  A heuristic input, never a result.
     ftk_buffer tail_host{ftk_buffer::kPinned}, tail_dev;  // 16 uint32_t each; allocated by a context's first tracker call outside a stream capture
-    uint32_t tail_call = 0;                 // tracker launches of this context so far (tags the reports)
-    struct TailState {
-        uint32_t launches = 0;              // launches of this variant so far
-        uint32_t long_until = 0;            // "this variant's calls have a long tail" while launches < long_until
-        uint32_t longest = 0;               // the last long report's iteration count
-    } tail[3][3];                           // [model][inverse, direct, fast]
+    ftk::KltTailState tail;                 // launch numbers and the variants' tail classes (klt_sched.h klt_tail_class_step)
     ftk_buffer match_pad;      // zero-padded copies of descriptors whose width is not a power of two (device-resident matcher entry)
     ftk_buffer klt_spill;      // per-workgroup slices of the trackers' large-patch form (ftk_device.h KltParams::spill)
     ftk_buffer direct_spread;  // hand-off workspace of the spread direct-method kernel (header, chunk flags, products)

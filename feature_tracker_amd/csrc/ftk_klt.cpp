@@ -2,7 +2,9 @@
 //
 // One call, in the order it runs: argument checks -> tail class (klt_tail_class) -> launch plan (klt_plan.h: a pure function) ->
 // this launch's number for the tail report -> the large-patch batches (klt_launch_spilled) OR the launch order (klt_sched_prepare)
-// -> launch.  Reading the world — the context, the FTK_KLT_* switches, the device's tail words — happens here, never in the plan.
+// -> launch.  Reading the world — the context, the FTK_KLT_* switches, the device's tail words — happens here, never in the plan
+// nor in the two state machines that decide tail class and launch order (klt_sched.h: pure step functions).
+#include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -14,15 +16,6 @@
 #include "klt_plan.h"
 
 namespace {
-
-constexpr uint32_t kSchedMinFeatures = 4096;  // below this (nearly) every feature is resident from the start: nothing to order ...
-constexpr uint32_t kSchedMinLongTail = 1024;  // ... unless the calls have a long tail (see ftk_klt_track_device)
-constexpr size_t kSchedTableWords = (2u << 16) + 2;  // two position tables of 2^16 entries (klt_common.h kSchedTableSize) + the two "no tail" flags behind them
-constexpr size_t kSchedOrderWords = 512;             // behind them: histogram + cursors of the position-keyed launch order (klt_position_order_launch)
-constexpr int32_t kSchedMaxFeatures = 1 << 18;  // the sort block walks the list alone; beyond this it could outlast the launch
-constexpr uint32_t kTailLongFrom = 24;  // iterations of a call's longest feature from which the call counts as tail-bound
-constexpr uint32_t kTailHold = 8;       // launches of the variant for which one such report holds
-constexpr uint32_t kTailFresh = 256;    // launches of the context a report may lag behind (the host enqueues far ahead of the device)
 
 int klt_check_call(ftk_context *ctx, int model, const ftk_klt_options *opt, const ftk_pyramid *ref, const ftk_pyramid *cur) {
     if (!opt || !ref || !cur) {
@@ -61,23 +54,12 @@ int klt_count_override(const char *env) {
     return v < 1 ? 1 : (v > 4 ? 4 : v);
 }
 
-// Tail class of this variant's next launch (the wave policy's second axis, klt_plan.cpp), from the word its kernels report into;
-// the one place that updates ctx->tail[..].long_until.  FTK_KLT_TAIL_CLASS pins the class (the sweep and the policy test).
+// Tail class of this variant's next launch (the wave policy's second axis, klt_plan.cpp), from the word its kernels report into
+// (klt_sched.h klt_tail_class_step).  FTK_KLT_TAIL_CLASS pins the class (the sweep and the policy test).
 int klt_tail_class(ftk_context *ctx, int model, int method) {
     int long_tail = 0;
     if (ctx->tail_host) {
-        const int mi = method == FTK_METHOD_INVERSE ? 0 : (method == FTK_METHOD_DIRECT ? 1 : 2);
-        ftk_context::TailState &ts = ctx->tail[model][mi];
-        // this variant's own word: {call number << 8 | iterations} of the longest feature of its most recent launch that has got that
-        // far.  The host may be many launches ahead of the device (back-to-back calls), so a report counts while it is at most
-        // kTailFresh launches of the context old, and one long report holds for kTailHold launches of the variant.
-        const uint32_t seen = ctx->tail_host.as<volatile uint32_t>()[model * 3 + mi];
-        const uint32_t age = (ctx->tail_call - (seen >> 8)) & 0xFFFFFFu;
-        if (seen != 0 && age <= kTailFresh && (seen & 0xFFu) >= kTailLongFrom) {
-            ts.long_until = ts.launches + kTailHold;
-            ts.longest = seen & 0xFFu;
-        }
-        long_tail = ts.launches < ts.long_until ? 1 : 0;
+        long_tail = ftk::klt_tail_class_step(ctx->tail, model, method, ctx->tail_host.as<volatile uint32_t>()[model * 3 + ftk::klt_method_class(method)]);
     }
     if (const char *env = FTK_ENV(ctx, klt_tail_class)) {
         long_tail = atoi(env) != 0 ? 1 : 0;  // experiment override
@@ -144,16 +126,14 @@ void klt_tail_number(ftk_context *ctx, int model, int method, ftk::KltParams &p)
         }
     }
     if (ctx->tail_host && ctx->tail_dev) {
-        ctx->tail_call = (ctx->tail_call + 1u) & 0xFFFFFFu;
-        if (ctx->tail_call == 0u) {
-            ctx->tail_call = 1u;  // (after 16 M launches the device word's running maximum starts over with the host's)
+        bool wipe_device_word = false;
+        p.tail_call = ftk::klt_tail_next_call(ctx->tail, model, method, &wipe_device_word);
+        if (wipe_device_word) {
             (void)hipMemsetAsync(ctx->tail_dev.get(), 0, 64, ctx->stream);
         }
-        const int mi = method == FTK_METHOD_INVERSE ? 0 : (method == FTK_METHOD_DIRECT ? 1 : 2);
-        ++ctx->tail[model][mi].launches;
-        p.tail_dev = ctx->tail_dev.as<uint32_t>() + (model * 3 + mi);    // a word per variant
-        p.tail_host = ctx->tail_host.as<uint32_t>() + (model * 3 + mi);  // (pinned host memory is device-visible under the same address)
-        p.tail_call = ctx->tail_call;
+        const int word = model * 3 + ftk::klt_method_class(method);
+        p.tail_dev = ctx->tail_dev.as<uint32_t>() + word;    // a word per variant
+        p.tail_host = ctx->tail_host.as<uint32_t>() + word;  // (pinned host memory is device-visible under the same address)
     }
 }
 
@@ -179,8 +159,7 @@ int klt_launch_spilled(ftk_context *ctx, int model, int method, ftk::KltParams &
         return rc_buf;
     }
     p.spill_base = ctx->klt_spill.as<float>();
-    ctx->sched_calls = 0;  // no launch order for these calls; a later ordinary call starts its history over
-    ctx->sched_n = 0;
+    ftk::klt_sched_reset(ctx->sched);  // no launch order for these calls; a later ordinary call starts its history over
     for (size_t b0 = 0; b0 < (size_t)n; b0 += batch) {
         const size_t nb = (size_t)n - b0 < batch ? (size_t)n - b0 : batch;
         ftk::KltParams q = p;
@@ -202,148 +181,121 @@ int klt_launch_spilled(ftk_context *ctx, int model, int method, ftk::KltParams &
     return FTK_OK;
 }
 
-// Launch order.  A call's time is bulk + tail: features run a data-dependent number of Gauss-Newton iterations
-// (config 3: mean 6.7, one feature 52), a launch in list order starts the long ones wherever they happen to sit,
-// and the grid drains while they finish.  Trackers are called frame after frame on (nearly) the same feature list
-// and a feature that needed many iterations tends to need many again, so the launch slots go through a permutation:
-// longest first by an EARLIER call's iteration counts.  No launch of its own: call k's tracker launch carries one
-// extra workgroup (block 0, klt_common.h klt_order_block) that sorts call k - 1's counts while the features of call k
-// run, and call k + 1 uses the result — so from the third call with the same feature count on, with a predictor two
-// calls old.  Which slot runs a feature changes nothing in its arithmetic.  Only for calls with more features than
-// fit the chip at once; FTK_KLT_SCHED=0 keeps list order.
-int klt_sched_prepare(ftk_context *ctx, int model, int32_t n, int long_tail, ftk::KltParams &p) {
-    const bool sched_allowed = !(FTK_ENV(ctx, klt_sched) && atoi(FTK_ENV(ctx, klt_sched)) == 0);
-    // From kSchedMinFeatures on — or, when this variant's recent calls had a long feature (long_tail: the kernels report it,
-    // klt_tail_class), already from kSchedMinLongTail: multi-wave features of a few thousand do NOT all fit the chip at once, and
-    // a 50-iteration feature that starts in the second round ends the launch that much later (the reference's example pair, same
-    // box, order from 4 096 / from 1 024: affine inverse 2 000 features 165.9 / 138.8 us, affine direct 3 000: 174.7 / 136.0, LSSD
-    // fast 3 000: 143.2 / 113.2, Basic fast 3 000: 60.9 / 52.3; the synthetic scene's LSSD / affine variants -4 ... -15 %).  Calls
-    // without a tail keep list order there: the order costs every feature one more dependent load (Basic variants +3 ... 4 %).
-    const uint32_t sched_min = FTK_ENV(ctx, klt_sched_min) ? (uint32_t)atoi(FTK_ENV(ctx, klt_sched_min))  // (experiment override)
-                                                           : (long_tail ? kSchedMinLongTail : kSchedMinFeatures);
-    if (sched_allowed && p.n_track >= sched_min && n <= kSchedMaxFeatures) {
-        if ((size_t)n > ctx->sched_capacity) {
-            ctx->sched_capacity = 0;
-            ctx->sched_n = 0;
-            const size_t cap = ((size_t)n + 4095) / 4096 * 4096;
-            // position-keyed slot swaps: a claim word per launch slot, and (once) the two tables of iteration counts by position
-            FTK_HIP(ctx, ctx->sched_claim.reserve(ctx->stream, sizeof(uint32_t) * cap, 0, 1));
-            FTK_HIP(ctx, hipMemsetAsync(ctx->sched_claim.get(), 0, sizeof(uint32_t) * cap, ctx->stream));
-            FTK_HIP(ctx, ctx->sched_pred.reserve(ctx->stream, cap, 0, 1));
-            bool new_grid = false;
-            FTK_HIP(ctx, ctx->sched_grid.reserve(ctx->stream, sizeof(uint32_t) * (kSchedTableWords + kSchedOrderWords), 0, 1, &new_grid));
-            if (new_grid) {
-                FTK_HIP(ctx, hipMemsetAsync(ctx->sched_grid.get(), 0, sizeof(uint32_t) * kSchedTableWords, ctx->stream));
-            }
-            for (int k = 0; k < 2; ++k) {
-                FTK_HIP(ctx, ctx->sched_iters[k].reserve(ctx->stream, sizeof(uint32_t) * cap, 0, 1));
-                FTK_HIP(ctx, ctx->sched_order[k].reserve(ctx->stream, sizeof(int32_t) * cap, 0, 1));
-                // never-written entries must still be valid feature ids (0) and valid counts, whatever happens to a launch
-                FTK_HIP(ctx, hipMemsetAsync(ctx->sched_iters[k].get(), 0, sizeof(uint32_t) * cap, ctx->stream));
-                FTK_HIP(ctx, hipMemsetAsync(ctx->sched_order[k].get(), 0, sizeof(int32_t) * cap, ctx->stream));
-            }
-            ctx->sched_capacity = cap;
-        }
-        if (ctx->sched_n != n) {
-            ctx->sched_n = n;
-            ctx->sched_calls = 0;
-        }
-        const uint32_t k = ctx->sched_calls++;
-        // Position-keyed swaps ride on every such call, whatever the list did since the last one.  Call numbers start at 4 (an
-        // all-zero grid / claim word is never "recent") and tag 23 bits of a claim word: the claims are wiped before a tag could
-        // repeat.
-        // (never inside a stream capture: a replayed launch would carry this call's number again and read its own old claims)
-        const bool capturing = ftk_stream_capturing(ctx->stream);
-        // (nor when the results overwrite the reference positions: both sides of a trade must read the same positions)
-        const char *ref_lo = reinterpret_cast<const char *>(p.ref_uv), *out_lo = reinterpret_cast<const char *>(p.cur_uv_out);
-        const size_t uv_span = sizeof(float) * 2 * (size_t)n;
-        const bool ref_untouched = ref_lo + uv_span <= out_lo || out_lo + uv_span <= ref_lo;
-        // Multi-wave features only: there a feature is tens of microseconds long and iteration counts have heavy tails
-        // (config 3: 192 / 207 -> 149 / 166 us with no / a stale launch order, +0.5 % with a fitting one); the one-wave kernels
-        // run 10 000 - 25 000 cheap features, every late one of which would pay a table look-up for a 3 % gain at best
-        // (config 4: +2.9 % with a fitting order, -3 % without; config 5: +1 %).
-        // EVERY such call (outside a capture) leaves its iteration counts in the position table — one or two atomics per feature —
-        // so that the next one can order or trade by position whatever kernel either of them runs.
-        const bool recording = !capturing && ctx->sched_grid && ctx->sched_claim;
-        uint32_t last_recorded = 0;
-        if (recording) {
-            if (ctx->sched_call < 4u) {
-                ctx->sched_call = 4u;
-            }
-            ++ctx->sched_call;
-            if ((ctx->sched_call & 0x7FFFFFu) < 4u) {
-                FTK_HIP(ctx, hipMemsetAsync(ctx->sched_claim.get(), 0, sizeof(uint32_t) * ctx->sched_capacity, ctx->stream));
-                FTK_HIP(ctx, hipMemsetAsync(ctx->sched_grid.get(), 0, sizeof(uint32_t) * kSchedTableWords, ctx->stream));
-                ctx->sched_call += 4u;
-                ctx->sched_recorded = 0;
-            }
-            p.sched_grid = ctx->sched_grid.as<uint32_t>();
-            p.sched_call = ctx->sched_call;
-            last_recorded = ctx->sched_recorded;
-            ctx->sched_recorded = ctx->sched_call;
-        }
-        if (recording && p.waves_per_feature >= 2 && ref_untouched && n > 1024 + 512) {
-            p.sched_flags = ctx->sched_grid.as<uint32_t>() + (2u << 16);
-            p.sched_claim = ctx->sched_claim.as<uint32_t>();
-        }
-        p.sched_iters = ctx->sched_iters[k & 1].as<uint32_t>();          // this call's counts
-        if (k >= 1) {                                     // sort the previous call's counts beside this call's features
-            p.sort_iters = ctx->sched_iters[(k - 1) & 1].as<uint32_t>();
-            p.sort_order_out = ctx->sched_order[(k - 1) & 1].as<int32_t>();
-            // The spatial (tile) order reads the reference positions in two passes while the feature workgroups of the same
-            // launch write cur_uv_out: with one position buffer updated in place (ref == out, allowed by include/ftk.h) a
-            // feature crossing a tile boundary in between would make the histogram and the scatter disagree — duplicates,
-            // stale entries, a write past order[n - 1].  Such a call gets the iteration-count / identity order instead.
-            p.sort_ref_uv = ref_untouched ? p.ref_uv : nullptr;
-        }
-        if (k >= 2) {                                     // made during the previous call from the counts before it
-            p.order = ctx->sched_order[k & 1].as<int32_t>();
-        } else if (recording && last_recorded != 0u && last_recorded + 1u == ctx->sched_call && ctx->sched_pred && model != FTK_MODEL_BASIC &&
-                   p.sched_claim == nullptr) {
-            // (LSSD and affine KLT: their iteration counts have tails — config 4 without history 206 -> 183 us, with luminance
-            // 357 -> 315; Basic KLT's are flat on most scenes and the ~10 us of the two launches would buy nothing — config 5 shard
-            // 181 -> 190; the multi-wave kernels trade slots by position inside the launch instead)
-            // No index-keyed order (the feature count has just changed, or these are the first calls): order THIS call by what the
-            // last call left at its features' positions — two small launches in front of the tracker's (klt_kernels.hip
-            // klt_position_order_launch).  The buffer is the one an index-keyed order of this call would have used: nobody else
-            // writes it during this call.
-            const uint32_t *last_table = ctx->sched_grid.as<uint32_t>() + (((ctx->sched_call - 1u) & 1u) << 16);
-            FTK_HIP(ctx, ftk::klt_position_order_launch(p.ref_uv, n, last_table, ctx->sched_call - 1u, ctx->sched_pred.as<uint8_t>(),
-                                                        ctx->sched_grid.as<uint32_t>() + kSchedTableWords, ctx->sched_order[k & 1].as<int32_t>(), ctx->stream));
-            p.order = ctx->sched_order[k & 1].as<int32_t>();
-        }
-        if (const char *dump = FTK_ENV(ctx, klt_swap_dump)) {  // diagnostic: how many trades the PREVIOUS launch of this context made
-            if (p.sched_claim != nullptr && ctx->sched_call > 5u) {
-                std::vector<uint32_t> h((size_t)n);
-                FTK_HIP(ctx, hipMemcpyAsync(h.data(), ctx->sched_claim.as<uint32_t>(), sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-                FTK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-                const uint32_t last = (ctx->sched_call - 1u) & 0x7FFFFFu;
-                size_t trades = 0, own = 0;
-                for (uint32_t w : h) {
-                    if ((w >> 9) == last) {
-                        ((w & 0x1FFu) == 0x1FFu ? own : trades) += 1;
-                    }
-                }
-                if (FILE *f = fopen(dump, "w")) {
-                    fprintf(f, "%zu %zu\n", trades, own);
-                    fclose(f);
-                }
+// Every buffer of the launch order for `cap` features: the double-buffered counts and orders, a claim word per launch slot, a
+// predicted count per feature and (once) the grid buffer (klt_sched.h: two position tables, flags, order workspace).
+int klt_sched_grow(ftk_context *ctx, size_t cap) {
+    FTK_HIP(ctx, ctx->sched_claim.reserve(ctx->stream, sizeof(uint32_t) * cap, 0, 1));
+    FTK_HIP(ctx, hipMemsetAsync(ctx->sched_claim.get(), 0, sizeof(uint32_t) * cap, ctx->stream));
+    FTK_HIP(ctx, ctx->sched_pred.reserve(ctx->stream, cap, 0, 1));
+    bool new_grid = false;
+    FTK_HIP(ctx, ctx->sched_grid.reserve(ctx->stream, sizeof(uint32_t) * ftk::kSchedGridWords, 0, 1, &new_grid));
+    if (new_grid) {
+        FTK_HIP(ctx, hipMemsetAsync(ctx->sched_grid.get(), 0, sizeof(uint32_t) * ftk::kSchedTableWords, ctx->stream));
+    }
+    for (int k = 0; k < 2; ++k) {
+        FTK_HIP(ctx, ctx->sched_iters[k].reserve(ctx->stream, sizeof(uint32_t) * cap, 0, 1));
+        FTK_HIP(ctx, ctx->sched_order[k].reserve(ctx->stream, sizeof(int32_t) * cap, 0, 1));
+        // never-written entries must still be valid feature ids (0) and valid counts, whatever happens to a launch
+        FTK_HIP(ctx, hipMemsetAsync(ctx->sched_iters[k].get(), 0, sizeof(uint32_t) * cap, ctx->stream));
+        FTK_HIP(ctx, hipMemsetAsync(ctx->sched_order[k].get(), 0, sizeof(int32_t) * cap, ctx->stream));
+    }
+    return FTK_OK;
+}
+
+// The two diagnostics of the launch order, each into the file its switch names (they synchronise the stream).
+int klt_sched_dump(ftk_context *ctx, const ftk::KltSchedStep &step, int32_t n) {
+    const char *dump = FTK_ENV(ctx, klt_swap_dump);  // how many trades the PREVIOUS launch of this context made
+    if (dump && step.trades && step.sched_call > 5u) {
+        std::vector<uint32_t> h((size_t)n);
+        FTK_HIP(ctx, hipMemcpyAsync(h.data(), ctx->sched_claim.as<uint32_t>(), sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+        FTK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        size_t trades = 0, own = 0;
+        for (uint32_t w : h) {
+            if (ftk::sched_claim_call(w) == ftk::sched_claim_tag(step.sched_call - 1u)) {
+                (ftk::sched_claim_code(w) == ftk::kSchedSelf ? own : trades) += 1;
             }
         }
-        if (const char *dump = FTK_ENV(ctx, klt_sched_dump)) {  // diagnostic: the permutation in use and the counts it came from
-            if (k >= 2) {
-                std::vector<int32_t> h((size_t)n * 2);
-                FTK_HIP(ctx, hipMemcpyAsync(h.data(), ctx->sched_order[k & 1].as<int32_t>(), sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-                FTK_HIP(ctx, hipMemcpyAsync(h.data() + n, ctx->sched_iters[k & 1].as<uint32_t>(), sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-                FTK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-                if (FILE *f = fopen(dump, "wb")) {
-                    fwrite(h.data(), sizeof(int32_t), h.size(), f);
-                    fclose(f);
-                }
-            }
+        if (FILE *f = fopen(dump, "w")) {
+            fprintf(f, "%zu %zu\n", trades, own);
+            fclose(f);
+        }
+    }
+    dump = FTK_ENV(ctx, klt_sched_dump);  // the index-keyed permutation in use and the counts it came from (still in the buffer this call will overwrite)
+    if (dump && step.order == ftk::KltOrder::Index) {
+        std::vector<int32_t> h((size_t)n * 2);
+        FTK_HIP(ctx, hipMemcpyAsync(h.data(), ctx->sched_order[step.order_buf].as<int32_t>(), sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+        FTK_HIP(ctx, hipMemcpyAsync(h.data() + n, ctx->sched_iters[step.iters_buf].as<uint32_t>(), sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+        FTK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (FILE *f = fopen(dump, "wb")) {
+            fwrite(h.data(), sizeof(int32_t), h.size(), f);
+            fclose(f);
         }
     }
     return FTK_OK;
+}
+
+// Launch order of this call (klt_sched.h klt_sched_step decides): inputs, step, act.
+int klt_sched_prepare(ftk_context *ctx, int model, int32_t n, int long_tail, ftk::KltParams &p) {
+    ftk::KltSchedInput in = {};
+    in.n = n;
+    in.n_track = p.n_track;
+    in.model = model;
+    in.waves_per_feature = p.waves_per_feature;
+    in.long_tail = long_tail;
+    in.sched = FTK_ENV(ctx, klt_sched) ? atoi(FTK_ENV(ctx, klt_sched)) : ftk::kKltNotSet;
+    // (a negative threshold was always read as an unsigned one: above every feature count)
+    in.sched_min = FTK_ENV(ctx, klt_sched_min) ? (atoi(FTK_ENV(ctx, klt_sched_min)) < 0 ? INT32_MAX : atoi(FTK_ENV(ctx, klt_sched_min))) : ftk::kKltNotSet;
+    if (!ftk::klt_sched_applies(in)) {
+        return FTK_OK;  // list order, and nothing else to ask
+    }
+    in.capturing = ftk_stream_capturing(ctx->stream);
+    const char *ref_lo = reinterpret_cast<const char *>(p.ref_uv), *out_lo = reinterpret_cast<const char *>(p.cur_uv_out);
+    const size_t uv_span = sizeof(float) * 2 * (size_t)n;
+    in.ref_untouched = ref_lo + uv_span <= out_lo || out_lo + uv_span <= ref_lo;
+    in.have_grid = (bool)ctx->sched_grid;
+    in.have_claim = (bool)ctx->sched_claim;
+    in.have_pred = (bool)ctx->sched_pred;
+
+    ftk::KltSchedState next = ctx->sched;  // (installed once the buffers it counts on exist)
+    const ftk::KltSchedStep step = ftk::klt_sched_step(next, in);
+
+    if (step.grow_to != 0) {
+        const int rc = klt_sched_grow(ctx, step.grow_to);
+        if (rc != FTK_OK) {
+            ctx->sched.capacity = 0;
+            ftk::klt_sched_reset(ctx->sched);
+            return rc;
+        }
+    }
+    if (step.wipe_claims_and_grid) {
+        FTK_HIP(ctx, hipMemsetAsync(ctx->sched_claim.get(), 0, sizeof(uint32_t) * next.capacity, ctx->stream));
+        FTK_HIP(ctx, hipMemsetAsync(ctx->sched_grid.get(), 0, sizeof(uint32_t) * ftk::kSchedTableWords, ctx->stream));
+    }
+    ctx->sched = next;
+    uint32_t *grid = ctx->sched_grid.as<uint32_t>();
+    if (step.recording) {
+        p.sched_grid = grid;
+        p.sched_call = step.sched_call;
+    }
+    if (step.trades) {
+        p.sched_flags = grid + ftk::kSchedFlagsAt;
+        p.sched_claim = ctx->sched_claim.as<uint32_t>();
+    }
+    p.sched_iters = ctx->sched_iters[step.iters_buf].as<uint32_t>();
+    if (step.sort_from >= 0) {
+        p.sort_iters = ctx->sched_iters[step.sort_from].as<uint32_t>();
+        p.sort_order_out = ctx->sched_order[step.sort_from].as<int32_t>();
+        p.sort_ref_uv = step.sort_reads_ref_uv ? p.ref_uv : nullptr;
+    }
+    if (step.order != ftk::KltOrder::None) {
+        int32_t *order = ctx->sched_order[step.order_buf].as<int32_t>();
+        if (step.order == ftk::KltOrder::Position) {
+            FTK_HIP(ctx, ftk::klt_position_order_launch(p.ref_uv, n, grid + ftk::sched_table_at(step.sched_call - 1u), step.sched_call - 1u,
+                                                        ctx->sched_pred.as<uint8_t>(), grid + ftk::kSchedTableWords, order, ctx->stream));
+        }
+        p.order = order;
+    }
+    return klt_sched_dump(ctx, step, n);
 }
 
 }  // namespace
@@ -413,8 +365,7 @@ int ftk_klt_track_device(ftk_context *ctx, int model, const ftk_klt_options *opt
     if (launch_rc != hipSuccess) {
         // The launch-order state advanced above assumed this launch would write its iteration counts and (from the second call
         // on) a permutation: it did neither, so the history starts over — the next call must not install an order nobody wrote.
-        ctx->sched_calls = 0;
-        ctx->sched_n = 0;
+        ftk::klt_sched_reset(ctx->sched);
         return ftk_fail(ctx, launch_rc == hipErrorOutOfMemory ? FTK_E_OUT_OF_MEMORY : FTK_E_HIP, "klt launch failed: %s", hipGetErrorString(launch_rc));
     }
     return FTK_OK;
@@ -453,10 +404,6 @@ int ftk_klt_track(ftk_context *ctx, int model, const ftk_klt_options *opt, const
     }
     uint8_t *dbase = ctx->scratch.as<uint8_t>();
     uint8_t *hbase = ctx->pinned.as<uint8_t>();
-    float *d_ref = reinterpret_cast<float *>(dbase);
-    float *d_cur = reinterpret_cast<float *>(dbase + uv_bytes);
-    uint8_t *d_st = dbase + 2 * uv_bytes;
-    uint32_t *d_it = reinterpret_cast<uint32_t *>(dbase + 2 * uv_bytes + st_bytes);
     memcpy(hbase, ref_uv, sizeof(float) * 2 * (size_t)n);
     memcpy(hbase + uv_bytes, cur_uv, sizeof(float) * 2 * (size_t)n);
     memcpy(hbase + 2 * uv_bytes, status, (size_t)n);
@@ -465,35 +412,22 @@ int ftk_klt_track(ftk_context *ctx, int model, const ftk_klt_options *opt, const
     // feature straight into the pinned host block over PCIe — no H2D / D2H at all (2 000 features: 89 -> ~60 us per
     // call).  Larger calls keep the bulk copies.
     void *mapped = nullptr;
-    if (n <= 16384 && hipHostGetDevicePointer(&mapped, ctx->pinned.get(), 0) == hipSuccess && mapped != nullptr) {
-        uint8_t *mbase = static_cast<uint8_t *>(mapped);
-        float *m_ref = reinterpret_cast<float *>(mbase);
-        float *m_cur = reinterpret_cast<float *>(mbase + uv_bytes);
-        uint8_t *m_st = mbase + 2 * uv_bytes;
-        uint32_t *m_it = reinterpret_cast<uint32_t *>(mbase + 2 * uv_bytes + st_bytes);
-        rc = ftk_klt_track_device(ctx, model, opt, ref, cur, m_ref, m_cur, m_cur, m_st, m_st, n, prior, consider_luminance, single_level,
-                                  iters ? m_it : nullptr);
-        if (rc != FTK_OK) {
-            (void)hipStreamSynchronize(ctx->stream);
-            return rc;
-        }
-        FTK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        memcpy(cur_uv, hbase + uv_bytes, sizeof(float) * 2 * (size_t)n);
-        memcpy(status, hbase + 2 * uv_bytes, (size_t)n);
-        if (iters) {
-            memcpy(iters, hbase + 2 * uv_bytes + st_bytes, sizeof(uint32_t) * (size_t)n);
-        }
-        return FTK_OK;
+    const bool zero_copy = n <= 16384 && hipHostGetDevicePointer(&mapped, ctx->pinned.get(), 0) == hipSuccess && mapped != nullptr;
+    uint8_t *base = zero_copy ? static_cast<uint8_t *>(mapped) : dbase;  // what the device entry works on
+    float *b_cur = reinterpret_cast<float *>(base + uv_bytes);
+    uint8_t *b_st = base + 2 * uv_bytes;
+    if (!zero_copy) {
+        FTK_HIP(ctx, hipMemcpyAsync(dbase, hbase, 2 * uv_bytes + st_bytes, hipMemcpyHostToDevice, ctx->stream));
     }
-    FTK_HIP(ctx, hipMemcpyAsync(dbase, hbase, 2 * uv_bytes + st_bytes, hipMemcpyHostToDevice, ctx->stream));
-    rc = ftk_klt_track_device(ctx, model, opt, ref, cur, d_ref, d_cur, d_cur, d_st, d_st, n, prior, consider_luminance, single_level,
-                              iters ? d_it : nullptr);
+    rc = ftk_klt_track_device(ctx, model, opt, ref, cur, reinterpret_cast<float *>(base), b_cur, b_cur, b_st, b_st, n, prior, consider_luminance, single_level,
+                              iters ? reinterpret_cast<uint32_t *>(base + 2 * uv_bytes + st_bytes) : nullptr);
     if (rc != FTK_OK) {
         (void)hipStreamSynchronize(ctx->stream);
         return rc;
     }
-    const size_t back = uv_bytes + st_bytes + (iters ? it_bytes : 0);
-    FTK_HIP(ctx, hipMemcpyAsync(hbase + uv_bytes, dbase + uv_bytes, back, hipMemcpyDeviceToHost, ctx->stream));
+    if (!zero_copy) {
+        FTK_HIP(ctx, hipMemcpyAsync(hbase + uv_bytes, dbase + uv_bytes, uv_bytes + st_bytes + (iters ? it_bytes : 0), hipMemcpyDeviceToHost, ctx->stream));
+    }
     FTK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     memcpy(cur_uv, hbase + uv_bytes, sizeof(float) * 2 * (size_t)n);
     memcpy(status, hbase + 2 * uv_bytes, (size_t)n);

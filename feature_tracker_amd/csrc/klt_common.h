@@ -5,6 +5,7 @@
 #pragma once
 
 #include "ftk_device.h"
+#include "klt_sched.h"
 
 #include <limits.h>
 #include <math.h>
@@ -1359,14 +1360,7 @@ __device__ __forceinline__ void store_quads(const RawQuads<N> &q, const Blk &b, 
 // slot, taken with a compare-and-swap by whichever of the two gets there first, guarantees that every feature is processed
 // exactly once whatever the timing; nobody waits for anybody.  Which slot runs a feature changes nothing in its arithmetic.
 // ---------------------------------------------------------------------------------------------
-constexpr int kSchedTableBits = 16;
-constexpr int kSchedTableSize = 1 << kSchedTableBits;  // entries per table; two tables (written by this call / read from the last)
-constexpr int kSchedHeadFirst = 256;   // the heads are the slots [kSchedHeadFirst, kSchedHeadFirst + kSchedHeadSlots): resident from the
-constexpr int kSchedHeadSlots = 256;   // first microsecond, but NOT the very first ones — with a fitting launch order those hold the
-constexpr int kSchedLateSlot = 1024;   // longest features, which must not start a scan's 2 - 3 us later
-constexpr uint32_t kSchedLongCount = 12;   // a late slot is a candidate from this predicted count on ...
-constexpr uint32_t kSchedSwapMargin = 8;   // ... and a head trades with it if that is this much above its own feature's prediction
-constexpr uint32_t kSchedSelf = 0x1FFu;    // claim code "the slot runs its own feature"; 0 .. kSchedHeadSlots - 1: the head (by number) it trades with
+// (the slot classes, the table geometry and the formats of the words: klt_sched.h, shared with the host)
 
 // positions are remembered at 4-pixel resolution (a feature that crosses such a boundary between two frames is simply not predicted)
 __device__ __forceinline__ uint32_t sched_table_slot(float u, float v) {
@@ -1376,16 +1370,17 @@ __device__ __forceinline__ uint32_t sched_table_slot(float u, float v) {
 
 // What the LAST call left at this position (the table this call only reads: every wave of a launch sees the same predictions)
 __device__ __forceinline__ uint32_t sched_prediction(const KltParams &p, float u, float v) {
+    // (sched_table_at(p.sched_call - 1u), spelled out: through the helper the compiler forms this address with other instructions)
     const uint32_t word = p.sched_grid[(((p.sched_call - 1u) & 1u) << kSchedTableBits) + sched_table_slot(u, v)];
-    return (word >> 8) == ((p.sched_call - 1u) & 0xFFFFFFu) ? (word & 0xFFu) : 0u;
+    return sched_grid_call(word) == sched_grid_tag(p.sched_call - 1u) ? sched_grid_iters(word) : 0u;
 }
 
 // ... at the feature's reference position (a caller that tracks the same list again asks there) AND at the position it was tracked to
 // (a caller that tracks frame after frame asks there: the next call's reference positions are this call's results)
 __device__ __forceinline__ void sched_grid_record(const KltParams &p, float ref_u, float ref_v, float out_u, float out_v, uint32_t iters) {
     if (p.sched_grid != nullptr) {
-        const uint32_t word = ((p.sched_call & 0xFFFFFFu) << 8) | (iters < 255u ? iters : 255u);
-        uint32_t *table = p.sched_grid + ((p.sched_call & 1u) << kSchedTableBits);
+        const uint32_t word = sched_grid_pack(p.sched_call, iters);
+        uint32_t *table = p.sched_grid + sched_table_at(p.sched_call);
         const uint32_t at_ref = sched_table_slot(ref_u, ref_v), at_out = sched_table_slot(out_u, out_v);
         atomicMax(&table[at_ref], word);
         if (at_out != at_ref) {
@@ -1398,10 +1393,9 @@ __device__ __forceinline__ void sched_grid_record(const KltParams &p, float ref_
 // least kTailReportFrom iterations raise a device word with atomicMax — an L2 load for most, an atomic for the few that raise it —
 // and whoever raised it forwards the new value to a device-visible host word with one system-scope store.  A lower value may land
 // after a higher one (two raisers racing over PCIe): the host treats the word as a hint.  One lane per feature calls this.
-constexpr uint32_t kTailReportFrom = 12;
 __device__ __forceinline__ void tail_report(const KltParams &p, uint32_t iters, uint32_t id) {
     if (p.tail_dev != nullptr && (iters >= kTailReportFrom || id == 0u)) {  // (feature 0 always: every launch refreshes the variant's word)
-        const uint32_t word = (p.tail_call << 8) | (iters < 255u ? iters : 255u);
+        const uint32_t word = tail_word_pack(p.tail_call, iters);
         if (word > __hip_atomic_load(p.tail_dev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
             if (atomicMax(p.tail_dev, word) < word) {
                 __hip_atomic_store(p.tail_host, word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -1414,11 +1408,11 @@ __device__ __forceinline__ void tail_report(const KltParams &p, uint32_t iters, 
 // slot runs — `slot` itself, or the slot it traded places with.  `swapped_in` tells a head that it now runs a predicted-long feature.
 __device__ __forceinline__ uint32_t sched_resolve_slot(const KltParams &p, uint32_t slot, bool &swapped_in) {
     swapped_in = false;
-    const uint32_t n = (uint32_t)p.n, call = p.sched_call & 0x7FFFFFu;
+    const uint32_t n = (uint32_t)p.n, call = sched_claim_tag(p.sched_call);
     const int lane = (int)(threadIdx.x & 63);
     // The sort block of the LAST launch found no tail in the counts it sorted: nobody trades, and nobody pays for looking (one
     // word, the same for every slot of this launch: this launch's own sort block writes the other one).
-    if (p.sched_flags[(p.sched_call - 1u) & 1u] == ((((p.sched_call - 1u) & 0x7FFFFFFFu) << 1) | 1u)) {
+    if (p.sched_flags[(p.sched_call - 1u) & 1u] == sched_flag_pack(p.sched_call - 1u, 1u)) {
         return slot;
     }
     if (slot >= (uint32_t)kSchedLateSlot) {
@@ -1431,16 +1425,16 @@ __device__ __forceinline__ uint32_t sched_resolve_slot(const KltParams &p, uint3
         uint32_t word = 0;
         if (lane == 0) {
             uint32_t seen = __hip_atomic_load(&p.sched_claim[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if ((seen >> 9) != call) {
-                const uint32_t mine = (call << 9) | kSchedSelf;
+            if (sched_claim_call(seen) != call) {
+                const uint32_t mine = sched_claim_pack(call, kSchedSelf);
                 const uint32_t prev = atomicCAS(&p.sched_claim[slot], seen, mine);
                 seen = prev == seen ? mine : prev;  // lost the race: only a head of THIS call writes here
             }
             word = seen;
         }
         word = (uint32_t)__builtin_amdgcn_readfirstlane((int)word);
-        const uint32_t code = word & 0x1FFu;
-        return ((word >> 9) == call && code != kSchedSelf) ? (uint32_t)kSchedHeadFirst + code : slot;
+        const uint32_t code = sched_claim_code(word);
+        return (sched_claim_call(word) == call && code != kSchedSelf) ? (uint32_t)kSchedHeadFirst + code : slot;
     }
     if (slot < (uint32_t)kSchedHeadFirst || slot >= (uint32_t)(kSchedHeadFirst + kSchedHeadSlots) || n <= (uint32_t)kSchedLateSlot) {
         return slot;
@@ -1467,8 +1461,8 @@ __device__ __forceinline__ uint32_t sched_resolve_slot(const KltParams &p, uint3
     uint32_t won = 0;
     if (lane == 0) {
         const uint32_t seen = __hip_atomic_load(&p.sched_claim[target], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if ((seen >> 9) != call) {
-            won = atomicCAS(&p.sched_claim[target], seen, (call << 9) | head) == seen ? 1u : 0u;
+        if (sched_claim_call(seen) != call) {
+            won = atomicCAS(&p.sched_claim[target], seen, sched_claim_pack(call, head)) == seen ? 1u : 0u;
         }
     }
     won = (uint32_t)__builtin_amdgcn_readfirstlane((int)won);
@@ -1655,7 +1649,7 @@ __device__ __forceinline__ void klt_order_block(const uint32_t *iters, int32_t *
     }
     __syncthreads();
     if (tid == 0 && sched_flags != nullptr) {
-        sched_flags[sched_call & 1u] = ((sched_call & 0x7FFFFFFFu) << 1) | (*flat != 0 ? 1u : 0u);  // for the NEXT launch's slots (sched_resolve_slot)
+        sched_flags[sched_call & 1u] = sched_flag_pack(sched_call, 0u) | (*flat != 0 ? 1u : 0u);  // for the NEXT launch's slots (sched_resolve_slot)
     }
     const bool by_tile = *flat != 0 && spatial;
     if (*flat != 0 && !spatial) {

@@ -2204,7 +2204,7 @@ __global__ void __launch_bounds__(256) klt_predict_scatter_kernel(const uint8_t 
 
 hipError_t klt_position_order_launch(const float *ref_uv, int32_t n, const uint32_t *last_table, uint32_t last_call, uint8_t *pred, uint32_t *hist_and_cursor,
                                      int32_t *order, hipStream_t stream) {
-    hipError_t e = hipMemsetAsync(hist_and_cursor, 0, sizeof(uint32_t) * 512, stream);
+    hipError_t e = hipMemsetAsync(hist_and_cursor, 0, sizeof(uint32_t) * kSchedOrderWords, stream);
     if (e != hipSuccess) {
         return e;
     }

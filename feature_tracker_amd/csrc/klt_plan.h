@@ -4,10 +4,9 @@
 #pragma once
 
 #include "ftk_device.h"
+#include "klt_sched.h"
 
 namespace ftk {
-
-constexpr int kKltNotSet = -1;  // an FTK_KLT_* override that is not in the environment
 
 // Everything the decision depends on, as values.
 struct KltPlanInput {
@@ -41,7 +40,7 @@ enum KltPlanError { kKltPlanOk = 0, kKltPlanUnknownVariant, kKltPlanSpillTooLarg
 // `plan`.  On kKltPlanSpillTooLarge `spill_floats` holds the floats of device memory per feature that were asked for.
 KltPlanError klt_plan(const KltPlanInput &in, KltParams *p, KltPlan *plan, size_t *spill_floats);
 
-// Waves per feature of one call from the measured table (klt_wave_policy.inc): method_class 0 inverse, 1 direct, 2 fast-like.
+// Waves per feature of one call from the measured table (klt_wave_policy.inc): method_class as klt_method_class (klt_sched.h).
 int klt_policy_waves(int model, int method_class, int consider_luminance, int long_tail, int pixels, int n);
 
 // LDS bytes ONE feature needs in each form (a multiple of 16), from the geometry, waves_per_feature, tree and the carve fields of

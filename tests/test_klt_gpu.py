@@ -693,6 +693,51 @@ def test_flat_iteration_counts_give_a_spatial_xcd_major_launch_order(ftk, oracle
     assert np.median(areas) < 0.25 * area_all, (np.median(areas), area_all)
 
 
+def test_index_keyed_order_is_installed_from_the_call_the_cpu_model_says(ftk, oracle, switch, tmp_path):
+    """Ties the CPU model of the launch-order ladder (tests/klt_sched_ref.py, which tests/test_klt_sched_cpu.py holds against
+    klt_sched_step) to the running library: on one fresh context, FTK_KLT_SCHED_DUMP writes its file exactly on the calls for which
+    the model says an index-keyed order is installed (the third call with one feature count on; a changed count starts over), every
+    dumped order is a permutation, and every call returns the oracle's answer."""
+    import torch
+    from feature_tracker_amd import device as D
+    from tests import klt_sched_ref
+    ref_levels, cur_levels = scenes.scene(320, 240, 3, "easy", "translation")
+    n, fewer = 4603, 4400
+    uv = synth.make_features(n, 320, 240, margin=24.0, border_fraction=0.0, half=5)
+    dump = tmp_path / "order.bin"
+    switch("FTK_KLT_SCHED_DUMP", str(dump))
+    dev = torch.device("cuda", 0)
+    stream = torch.cuda.Stream(device=dev)
+    ctx = D.context_on_stream(stream, 0)
+    opt = ftk.OpticalFlowOptions()
+    opt.kMethod, opt.kPatchRowHalfSize, opt.kPatchColHalfSize, opt.kMaxTrackPointsNumber = "fast", 5, 5, n
+    model = klt_sched_ref.Sched()
+    counts = [n] * 6 + [fewer] * 2
+    got, dumped, expected = [], [], []
+    with torch.cuda.stream(stream):
+        klt = D.DeviceKlt("lssd", opt, D.upload_pyramid(ref_levels, ctx, dev), D.upload_pyramid(cur_levels, ctx, dev), ctx)
+        for m in counts:
+            expected.append(model.call(m, m, 2, 1, 0, 0, 1)["order"] == "index")
+            if dump.exists():
+                dump.unlink()
+            d_ref = torch.from_numpy(np.ascontiguousarray(uv[:m])).to(dev)
+            d_out, d_so = torch.empty_like(d_ref), torch.empty(m, dtype=torch.uint8, device=dev)
+            klt.track(d_ref, d_ref.clone(), torch.zeros(m, dtype=torch.uint8, device=dev), d_out, d_so)
+            stream.synchronize()
+            got.append((d_out.cpu().numpy(), d_so.cpu().numpy()))
+            dumped.append(np.fromfile(dump, dtype=np.int32) if dump.exists() else None)
+    assert expected == [False, False, True, True, True, True, False, False]
+    assert [d is not None for d in dumped] == expected
+    for m, d in zip(counts, dumped):
+        if d is not None:
+            assert d.size == 2 * m and np.array_equal(np.sort(d[:m]), np.arange(m)), "not a permutation"
+    answers = {m: oracle.klt_track_pyramid("lssd", ref_levels, cur_levels, uv[:m], uv[:m], np.zeros(m, np.uint8), method="fast", half=5, max_points=n) for m in (n, fewer)}
+    for m, (g_uv, g_st) in zip(counts, got):
+        ok, c, s, _ = answers[m]
+        assert np.array_equal(g_st, s)
+        assert np.array_equal(g_uv.view(np.uint32), c.view(np.uint32))
+
+
 @pytest.mark.parametrize("n", [4603, 8192])
 def test_one_position_buffer_updated_in_place_over_many_calls(ftk, oracle, n):
     """ref_uv == cur_uv_in == cur_uv_out (one position buffer updated in place: include/ftk.h allows the out tensors to alias the in
