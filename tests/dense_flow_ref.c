@@ -5,6 +5,8 @@
  *   - Utility::Interpolate(Mat, r, c): clamp-to-edge bilinear (dfr_interpolate);
  *   - the 3x3 median of SmoothFlow: the 5th smallest value under a total order (-0 < +0, every NaN above +inf) (dfr_median9).
  * Built by tests/dense_flow_ref.py with the oracle's flags (gcc -O3 -ffp-contract=off); the product never loads it.
+ * Pinned independently by ref64 (tests/dense_ref64.py, a float64 numpy restatement written from the reference's source alone):
+ * tests/test_dense_ref64_cpu.py holds this file to it stage by stage and end to end, tests/test_dense_ref64_gpu.py the kernels.
  * Mat planes are row-major float arrays here (the layout does not enter any arithmetic). */
 #include <math.h>
 #include <stdint.h>

@@ -2,6 +2,9 @@
 
 TEST INFRASTRUCTURE ONLY: compiled on first use with the oracle's flags (gcc -O3 -ffp-contract=off) into a temporary
 directory; nothing under feature_tracker_amd/ may import it.
+
+The restatement is pinned independently by ref64 (tests/dense_ref64.py): tests/test_dense_ref64_cpu.py compares it with that float64
+restatement stage by stage and end to end; tests/test_dense_ref64_gpu.py compares the kernels with ref64 directly.
 """
 from __future__ import annotations
 
