@@ -23,6 +23,77 @@ def _torch():
     return torch
 
 
+_F32, _U8, _I32 = ("float32",), ("uint8",), ("int32",)
+_WORDS = ("int32", "uint32")   # bit patterns: the kernels read uint32, torch callers usually hold int32
+_COUNTS = ("int32", "uint32")  # the ABI writes uint32 iteration counts
+_KEYS = ("int64", "uint64")
+
+
+def _tensor_complaint(name, t, dtypes, shape, min_numel=None):
+    """The dtype / rank / shape / stride half of an argument check: what is wrong with ``t`` as argument ``name``, or None.  A pure
+    function of tensor metadata (dtype, shape, strides), so a CPU tensor answers like a CUDA one.  ``dtypes``: allowed torch dtype
+    names; ``shape``: one entry per dimension, an extent or None for any; ``min_numel``: least element count (flat buffers the ABI
+    sizes in bytes or words).  Dense row-major only: the C ABI sees a pointer and counts, never a stride."""
+    if not hasattr(t, "data_ptr") or not hasattr(t, "stride"):
+        return f"{name} must be a torch tensor (got {type(t).__name__})"
+    want = "[" + ", ".join("*" if e is None else str(int(e)) for e in shape) + "]" + ("" if min_numel is None else f" with at least {int(min_numel)} elements")
+    expected = f"{name} must be a contiguous {' or '.join(dtypes)} tensor of shape {want}"
+    got_shape, got_stride = tuple(int(e) for e in t.shape), tuple(int(e) for e in t.stride())
+    got = f"got {t.dtype} {list(got_shape)} with strides {list(got_stride)}"
+    if str(t.dtype) not in tuple("torch." + d for d in dtypes):
+        return f"{expected}: wrong dtype ({got}); there is no conversion here, the kernels read the bytes as they are"
+    if len(got_shape) != len(shape):
+        return f"{expected}: {len(got_shape)} dimensions instead of {len(shape)} ({got})"
+    for axis, (have, need) in enumerate(zip(got_shape, shape)):
+        if need is not None and have != int(need):
+            return f"{expected}: dimension {axis} is {have}, not {int(need)} ({got})"
+    numel = 1
+    for e in got_shape:
+        numel *= e
+    if min_numel is not None and numel < int(min_numel):
+        return f"{expected}: {numel} elements are too few ({got})"
+    dense = 1
+    for extent, stride in zip(reversed(got_shape), reversed(got_stride)):
+        if numel and extent > 1 and stride != dense:  # (the stride of an extent-1 dimension is arbitrary in torch)
+            return f"{expected}: it is a strided view ({got}) and nothing is copied here, the results are written in place; pass {name}.contiguous()"
+        dense *= extent
+    return None
+
+
+def _device_complaint(name, t, device_index):
+    """The other half: ``t`` lives in the memory of the context's HIP device (``device_index`` None: of any one HIP device)."""
+    if not t.is_cuda:
+        return f"{name} must be a CUDA tensor (got one on {t.device}): the kernels take its pointer, there is no host path and no copy here"
+    if device_index is not None and t.device.index != device_index:
+        return f"{name} must be on cuda:{device_index}, the device of the context and of the call's other tensors (got one on {t.device})"
+    return None
+
+
+def _check(name, t, dtypes, shape, device_index, min_numel=None):
+    """Refuses (ValueError) a tensor argument the C ABI would misread; never copies or converts.  Every ``data_ptr()`` of this module
+    is taken from a tensor that passed here (tests/test_device_args_cpu.py walks the entries and holds that)."""
+    complaint = _tensor_complaint(name, t, dtypes, shape, min_numel) or _device_complaint(name, t, device_index)
+    if complaint:
+        raise ValueError(complaint)
+
+
+def _call_device(ctx, first):
+    """The device index a call's tensors must share: the context's where it is known (context_on_stream), else the first tensor's."""
+    index = getattr(ctx, "device_index", None)
+    if index is None and getattr(first, "is_cuda", False):
+        index = first.device.index
+    return index
+
+
+def _check_pairs(n_ref, pred_uv, cur_uv, n_cur, device_index):
+    """NearbyMatch's pixel arrays: float32 [n_ref, 2] and [n_cur, 2], both or neither."""
+    if (pred_uv is None) != (cur_uv is None):
+        raise ValueError(f"pred_uv and cur_uv go together: NearbyMatch needs both, ForceMatch neither (got {'pred_uv' if cur_uv is None else 'cur_uv'} alone)")
+    if pred_uv is not None:
+        _check("pred_uv", pred_uv, _F32, (n_ref, 2), device_index)
+        _check("cur_uv", cur_uv, _F32, (n_cur, 2), device_index)
+
+
 def context_on_stream(stream, device_index: Optional[int] = None) -> Context:
     """A context that launches on the given ``torch.cuda.Stream`` (not the legacy null stream), so
     torch events, collectives and allocations made under ``with torch.cuda.stream(stream)`` order
@@ -33,15 +104,16 @@ def context_on_stream(stream, device_index: Optional[int] = None) -> Context:
     handle = stream.cuda_stream
     if not handle:
         raise ValueError("pass a non-default torch.cuda.Stream (the null stream has no handle to borrow)")
-    return Context(device_index, handle)
+    ctx = Context(device_index, handle)
+    ctx.device_index = int(device_index)  # what the entries below hold their tensors to
+    return ctx
 
 
 def pyramid_from_tensors(levels: Sequence, ctx: Context) -> ImagePyramid:
     """levels: uint8 CUDA tensors [rows, cols], contiguous.  Borrowed, not copied."""
     desc = []
-    for t in levels:
-        if t.dtype.__str__() != "torch.uint8" or not t.is_cuda or not t.is_contiguous() or t.dim() != 2:
-            raise ValueError("pyramid levels must be contiguous 2-D uint8 CUDA tensors")
+    for k, t in enumerate(levels):
+        _check(f"levels[{k}]", t, _U8, (None, None), _call_device(ctx, t))
         desc.append((t.data_ptr(), t.shape[0], t.shape[1]))
     return ImagePyramid.from_device_levels(desc, ctx, keepalive=list(levels))
 
@@ -68,14 +140,37 @@ class DeviceKlt:
         self.lum = int(bool(consider_luminance))
         self.single = int(bool(single_level))
 
+    def _check_in(self, ref_uv, cur_uv_in, status_in, iters=None):
+        """ref_uv and cur_uv_in: float32 [n, 2]; status_in: uint8 [n]; iters: int32 [n] or None; all contiguous, on the context's device.
+        Returns (n, that device's index)."""
+        dev = _call_device(self.ctx, ref_uv)
+        _check("ref_uv", ref_uv, _F32, (None, 2), dev)
+        n = int(ref_uv.shape[0])
+        _check("cur_uv_in", cur_uv_in, _F32, (n, 2), dev)
+        _check("status_in", status_in, _U8, (n,), dev)
+        if iters is not None:
+            _check("iters", iters, _COUNTS, (n,), dev)
+        return n, dev
+
+    @staticmethod
+    def _check_out(n, dev, cur_uv_out, status_out):
+        """cur_uv_out: float32 [n, 2]; status_out: uint8 [n]; contiguous, on the device of the inputs (which they may alias)."""
+        _check("cur_uv_out", cur_uv_out, _F32, (n, 2), dev)
+        _check("status_out", status_out, _U8, (n,), dev)
+
+    def _prior(self):
+        return None if self.prior is None else self.prior.ctypes.data_as(C.c_void_p)
+
     def bind(self, ref_uv, cur_uv_in, status_in, cur_uv_out, status_out, iters=None):
         """Pre-marshals one launch on fixed buffers; the returned callable enqueues it with minimal
-        host work (for launch-rate-sensitive loops).  The tensors must outlive the callable."""
+        host work (for launch-rate-sensitive loops).  The tensors must outlive the callable.
+        Tensors: contiguous float32 [n, 2] pairs, uint8 [n] status, int32 [n] iters, as ``track``; checked here once, not per launch."""
+        n, dev = self._check_in(ref_uv, cur_uv_in, status_in, iters)
+        self._check_out(n, dev, cur_uv_out, status_out)
         fn = N.lib().ftk_klt_track_device
         args = (self.ctx.handle, self.model, C.byref(self.opt), self.ref_pyr.handle, self.cur_pyr.handle, C.c_void_p(ref_uv.data_ptr()),
                 C.c_void_p(cur_uv_in.data_ptr()), C.c_void_p(cur_uv_out.data_ptr()), C.c_void_p(status_in.data_ptr()),
-                C.c_void_p(status_out.data_ptr()), ref_uv.shape[0], None if self.prior is None else self.prior.ctypes.data_as(C.c_void_p),
-                self.lum, self.single, None if iters is None else C.c_void_p(iters.data_ptr()))
+                C.c_void_p(status_out.data_ptr()), n, self._prior(), self.lum, self.single, None if iters is None else C.c_void_p(iters.data_ptr()))
         keep = (ref_uv, cur_uv_in, status_in, cur_uv_out, status_out, iters)
         handle = self.ctx.handle
 
@@ -91,25 +186,27 @@ class DeviceKlt:
         """kMaxTrackPointsNumber of this tracker's options (the GLOBAL cap when the feature list is sharded)."""
         return int(self.opt.max_track_points)
 
-    def _args(self, ref_uv, cur_uv_in, status_in):
-        return (C.c_void_p(ref_uv.data_ptr()), C.c_void_p(cur_uv_in.data_ptr()), C.c_void_p(status_in.data_ptr()))
-
     def track_sharded(self, comm: "Comm", ref_uv, cur_uv_in, status_in, cur_uv_out, status_out, iters=None):
         """ftk_klt_track_sharded_device: this rank's block of the (full-length) buffers, RCCL all-gather, scatter — every rank's
-        out tensors hold all n results afterwards (stream-ordered)."""
-        r, c, s = self._args(ref_uv, cur_uv_in, status_in)
+        out tensors hold all n results afterwards (stream-ordered).
+        Tensors: contiguous float32 [n, 2] pairs, uint8 [n] status, int32 [n] iters (only this rank's block is written), as ``track``."""
+        n, dev = self._check_in(ref_uv, cur_uv_in, status_in, iters)
+        self._check_out(n, dev, cur_uv_out, status_out)
         rc = N.lib().ftk_klt_track_sharded_device(
-            self.ctx.handle, comm.handle, self.model, C.byref(self.opt), self.ref_pyr.handle, self.cur_pyr.handle, r, c, C.c_void_p(cur_uv_out.data_ptr()),
-            s, C.c_void_p(status_out.data_ptr()), ref_uv.shape[0], None if self.prior is None else self.prior.ctypes.data_as(C.c_void_p), self.lum, self.single,
-            None if iters is None else C.c_void_p(iters.data_ptr()))
+            self.ctx.handle, comm.handle, self.model, C.byref(self.opt), self.ref_pyr.handle, self.cur_pyr.handle, C.c_void_p(ref_uv.data_ptr()),
+            C.c_void_p(cur_uv_in.data_ptr()), C.c_void_p(cur_uv_out.data_ptr()), C.c_void_p(status_in.data_ptr()), C.c_void_p(status_out.data_ptr()), n,
+            self._prior(), self.lum, self.single, None if iters is None else C.c_void_p(iters.data_ptr()))
         N.check(rc, self.ctx.handle)
 
     def bind_sharded(self, comm: "Comm", ref_uv, cur_uv_in, status_in, cur_uv_out, status_out):
-        """Pre-marshalled track_sharded on fixed buffers (launch-rate-sensitive loops, HIP-graph capture)."""
-        r, c, s = self._args(ref_uv, cur_uv_in, status_in)
+        """Pre-marshalled track_sharded on fixed buffers (launch-rate-sensitive loops, HIP-graph capture).
+        Tensors: contiguous float32 [n, 2] pairs and uint8 [n] status, as ``track``; checked here once, not per launch."""
+        n, dev = self._check_in(ref_uv, cur_uv_in, status_in)
+        self._check_out(n, dev, cur_uv_out, status_out)
         fn = N.lib().ftk_klt_track_sharded_device
-        args = (self.ctx.handle, comm.handle, self.model, C.byref(self.opt), self.ref_pyr.handle, self.cur_pyr.handle, r, c, C.c_void_p(cur_uv_out.data_ptr()), s,
-                C.c_void_p(status_out.data_ptr()), ref_uv.shape[0], None if self.prior is None else self.prior.ctypes.data_as(C.c_void_p), self.lum, self.single, None)
+        args = (self.ctx.handle, comm.handle, self.model, C.byref(self.opt), self.ref_pyr.handle, self.cur_pyr.handle, C.c_void_p(ref_uv.data_ptr()),
+                C.c_void_p(cur_uv_in.data_ptr()), C.c_void_p(cur_uv_out.data_ptr()), C.c_void_p(status_in.data_ptr()), C.c_void_p(status_out.data_ptr()), n,
+                self._prior(), self.lum, self.single, None)
         keep = (comm, ref_uv, cur_uv_in, status_in, cur_uv_out, status_out)
         handle = self.ctx.handle
 
@@ -121,21 +218,32 @@ class DeviceKlt:
         return launch
 
     def track_shard(self, rank: int, world: int, ref_uv, cur_uv_in, status_in, packed_shard, iters=None):
-        """ftk_klt_track_shard_device: rank's block tracked into its packed shard (for callers with their own collective)."""
-        r, c, s = self._args(ref_uv, cur_uv_in, status_in)
+        """ftk_klt_track_shard_device: rank's block tracked into its packed shard (for callers with their own collective).
+        Tensors: inputs as ``track`` (full length n); packed_shard: contiguous uint8, at least ftk_klt_shard_bytes(n, world) bytes."""
+        n, dev = self._check_in(ref_uv, cur_uv_in, status_in, iters)
+        _check("packed_shard", packed_shard, _U8, (None,), dev, min_numel=N.lib().ftk_klt_shard_bytes(n, int(world)))
         rc = N.lib().ftk_klt_track_shard_device(
-            self.ctx.handle, int(rank), int(world), self.model, C.byref(self.opt), self.ref_pyr.handle, self.cur_pyr.handle, r, c, s, ref_uv.shape[0],
-            None if self.prior is None else self.prior.ctypes.data_as(C.c_void_p), self.lum, self.single, C.c_void_p(packed_shard.data_ptr()),
+            self.ctx.handle, int(rank), int(world), self.model, C.byref(self.opt), self.ref_pyr.handle, self.cur_pyr.handle, C.c_void_p(ref_uv.data_ptr()),
+            C.c_void_p(cur_uv_in.data_ptr()), C.c_void_p(status_in.data_ptr()), n, self._prior(), self.lum, self.single, C.c_void_p(packed_shard.data_ptr()),
             None if iters is None else C.c_void_p(iters.data_ptr()))
         N.check(rc, self.ctx.handle)
 
     def unpack_shards(self, gathered, n: int, world: int, cur_uv_out, status_out):
-        N.check(N.lib().ftk_klt_unpack_shards_device(self.ctx.handle, C.c_void_p(gathered.data_ptr()), int(n), int(world), C.c_void_p(cur_uv_out.data_ptr()),
+        """ftk_klt_unpack_shards_device: the scatter of ``world`` gathered shards into the n results.
+        Tensors: gathered: contiguous uint8, at least world * ftk_klt_shard_bytes(n, world) bytes; cur_uv_out: float32 [n, 2]; status_out: uint8 [n]."""
+        n, world = int(n), int(world)
+        dev = _call_device(self.ctx, gathered)
+        _check("gathered", gathered, _U8, (None,), dev, min_numel=max(world, 0) * N.lib().ftk_klt_shard_bytes(n, world))
+        self._check_out(n, dev, cur_uv_out, status_out)
+        N.check(N.lib().ftk_klt_unpack_shards_device(self.ctx.handle, C.c_void_p(gathered.data_ptr()), n, world, C.c_void_p(cur_uv_out.data_ptr()),
                                                      C.c_void_p(status_out.data_ptr())), self.ctx.handle)
 
     def track(self, ref_uv, cur_uv_in, status_in, cur_uv_out, status_out, iters=None, max_track_points=None):
-        """``max_track_points`` overrides the options' cap for this launch (a shard's share of the global cap)."""
-        n = ref_uv.shape[0]
+        """``max_track_points`` overrides the options' cap for this launch (a shard's share of the global cap).
+        Tensors: ref_uv, cur_uv_in, cur_uv_out: contiguous float32 [n, 2]; status_in, status_out: uint8 [n]; iters: int32 [n] or None; the
+        out tensors may alias the in tensors.  A strided view, another dtype or a short buffer is a ValueError, never a copy."""
+        n, dev = self._check_in(ref_uv, cur_uv_in, status_in, iters)
+        self._check_out(n, dev, cur_uv_out, status_out)
         opt = self.opt
         if max_track_points is not None and int(max_track_points) != int(opt.max_track_points):
             opt = N.KltOptions.from_buffer_copy(self.opt)
@@ -143,8 +251,7 @@ class DeviceKlt:
         rc = N.lib().ftk_klt_track_device(
             self.ctx.handle, self.model, C.byref(opt), self.ref_pyr.handle, self.cur_pyr.handle, C.c_void_p(ref_uv.data_ptr()),
             C.c_void_p(cur_uv_in.data_ptr()), C.c_void_p(cur_uv_out.data_ptr()), C.c_void_p(status_in.data_ptr()),
-            C.c_void_p(status_out.data_ptr()), n, None if self.prior is None else self.prior.ctypes.data_as(C.c_void_p), self.lum, self.single,
-            None if iters is None else C.c_void_p(iters.data_ptr()))
+            C.c_void_p(status_out.data_ptr()), n, self._prior(), self.lum, self.single, None if iters is None else C.c_void_p(iters.data_ptr()))
         N.check(rc, self.ctx.handle)
 
 
@@ -189,22 +296,43 @@ def shard_bounds(n: int, world: int, rank: int):
     return b.value, e.value
 
 
+def _check_words(ctx, ref_words, cur_words, n_bits, index_pairs, pred_uv, cur_uv):
+    """Packed descriptors: int32 / uint32 [n_ref, words] and [n_cur, words], n_bits <= 32 * words; index_pairs: int32 [n_ref]."""
+    dev = _call_device(ctx, ref_words)
+    _check("ref_words", ref_words, _WORDS, (None, None), dev)
+    n_ref, words = int(ref_words.shape[0]), int(ref_words.shape[1])
+    _check("cur_words", cur_words, _WORDS, (None, words), dev)
+    n_cur = int(cur_words.shape[0])
+    if int(n_bits) > 32 * words:
+        raise ValueError(f"n_bits {int(n_bits)} exceeds the {words} words (= {32 * words} bits) of a row of ref_words / cur_words")
+    _check("index_pairs", index_pairs, _I32, (n_ref,), dev)
+    _check_pairs(n_ref, pred_uv, cur_uv, n_cur, dev)
+    return n_ref, n_cur, words, dev
+
+
 def hamming_match_sharded_device(ctx: Context, comm: Comm, ref_words, cur_words, n_bits: int, max_distance: float, index_pairs, pred_uv=None,
                                  cur_uv=None, max_col: int = 40, max_row: int = 40):
-    """ftk_hamming_match_sharded_device on torch tensors: every rank passes ALL reference rows; index_pairs is complete everywhere."""
+    """ftk_hamming_match_sharded_device on torch tensors: every rank passes ALL reference rows; index_pairs is complete everywhere.
+    Tensors, all contiguous: words int32 / uint32 [n_ref, words] and [n_cur, words]; index_pairs int32 [n_ref]; pred_uv / cur_uv float32 [n_ref, 2] / [n_cur, 2]."""
+    n_ref, n_cur, words, _ = _check_words(ctx, ref_words, cur_words, n_bits, index_pairs, pred_uv, cur_uv)
     rc = N.lib().ftk_hamming_match_sharded_device(
-        ctx.handle, comm.handle, C.c_void_p(ref_words.data_ptr()), ref_words.shape[0], C.c_void_p(cur_words.data_ptr()), cur_words.shape[0],
-        ref_words.shape[1], int(n_bits), float(max_distance), None if pred_uv is None else C.c_void_p(pred_uv.data_ptr()),
+        ctx.handle, comm.handle, C.c_void_p(ref_words.data_ptr()), n_ref, C.c_void_p(cur_words.data_ptr()), n_cur,
+        words, int(n_bits), float(max_distance), None if pred_uv is None else C.c_void_p(pred_uv.data_ptr()),
         None if cur_uv is None else C.c_void_p(cur_uv.data_ptr()), int(max_col), int(max_row), C.c_void_p(index_pairs.data_ptr()))
     N.check(rc, ctx.handle)
 
 
 def hamming_match_device(ctx: Context, ref_words, cur_words, n_bits: int, max_distance: float, index_pairs, pred_uv=None, cur_uv=None,
                          max_col: int = 40, max_row: int = 40, workspace=None):
-    """ForceMatch (pred_uv None) / NearbyMatch on packed descriptors held in CUDA tensors ([n, words] int32/uint32)."""
+    """ForceMatch (pred_uv None) / NearbyMatch on packed descriptors held in CUDA tensors.
+    Tensors, all contiguous: words int32 / uint32 [n_ref, words] and [n_cur, words] (same words, n_bits <= 32 * words); index_pairs int32
+    [n_ref] (in/out); pred_uv / cur_uv float32 [n_ref, 2] / [n_cur, 2], both or neither; workspace int64 / uint64, at least n_ref elements, or None."""
+    n_ref, n_cur, words, dev = _check_words(ctx, ref_words, cur_words, n_bits, index_pairs, pred_uv, cur_uv)
+    if workspace is not None:
+        _check("workspace", workspace, _KEYS, (None,), dev, min_numel=n_ref)
     rc = N.lib().ftk_hamming_match_device(
-        ctx.handle, C.c_void_p(ref_words.data_ptr()), ref_words.shape[0], C.c_void_p(cur_words.data_ptr()), cur_words.shape[0],
-        ref_words.shape[1], int(n_bits), float(max_distance), None if pred_uv is None else C.c_void_p(pred_uv.data_ptr()),
+        ctx.handle, C.c_void_p(ref_words.data_ptr()), n_ref, C.c_void_p(cur_words.data_ptr()), n_cur,
+        words, int(n_bits), float(max_distance), None if pred_uv is None else C.c_void_p(pred_uv.data_ptr()),
         None if cur_uv is None else C.c_void_p(cur_uv.data_ptr()), int(max_col), int(max_row), C.c_void_p(index_pairs.data_ptr()),
         None if workspace is None else C.c_void_p(workspace.data_ptr()))
     N.check(rc, ctx.handle)
@@ -212,17 +340,31 @@ def hamming_match_device(ctx: Context, ref_words, cur_words, n_bits: int, max_di
 
 def cosine_match_device(ctx: Context, ref_desc, cur_desc, max_distance: float, index_pairs, pred_uv=None, cur_uv=None, max_col: int = 40,
                         max_row: int = 40):
-    """ForceMatch (pred_uv None) / NearbyMatch on float descriptors held in CUDA tensors ([n, dim] float32, contiguous)."""
+    """ForceMatch (pred_uv None) / NearbyMatch on float descriptors held in CUDA tensors.
+    Tensors, all contiguous: descriptors float32 [n_ref, dim] and [n_cur, dim], one row per feature (a [dim, n] network output: pass
+    ``desc.t().contiguous()``); index_pairs int32 [n_ref] (in/out); pred_uv / cur_uv float32 [n_ref, 2] / [n_cur, 2], both or neither."""
+    dev = _call_device(ctx, ref_desc)
+    _check("ref_desc", ref_desc, _F32, (None, None), dev)
+    n_ref, dim = int(ref_desc.shape[0]), int(ref_desc.shape[1])
+    _check("cur_desc", cur_desc, _F32, (None, dim), dev)
+    n_cur = int(cur_desc.shape[0])
+    _check("index_pairs", index_pairs, _I32, (n_ref,), dev)
+    _check_pairs(n_ref, pred_uv, cur_uv, n_cur, dev)
     rc = N.lib().ftk_cosine_match_device(
-        ctx.handle, C.c_void_p(ref_desc.data_ptr()), ref_desc.shape[0], C.c_void_p(cur_desc.data_ptr()), cur_desc.shape[0],
-        cur_desc.shape[1], float(max_distance), None if pred_uv is None else C.c_void_p(pred_uv.data_ptr()),
+        ctx.handle, C.c_void_p(ref_desc.data_ptr()), n_ref, C.c_void_p(cur_desc.data_ptr()), n_cur,
+        dim, float(max_distance), None if pred_uv is None else C.c_void_p(pred_uv.data_ptr()),
         None if cur_uv is None else C.c_void_p(cur_uv.data_ptr()), int(max_col), int(max_row), C.c_void_p(index_pairs.data_ptr()))
     N.check(rc, ctx.handle)
 
 
 def brief_compute_device(ctx: Context, image_pyr: ImagePyramid, uv, n_bits: int, half_patch: int, words_out, level: int = 0):
-    """BRIEF descriptors of CUDA-resident features straight into packed CUDA words ([n, ceil(n_bits/32)] int32)."""
-    rc = N.lib().ftk_brief_compute_device(ctx.handle, image_pyr.handle, int(level), C.c_void_p(uv.data_ptr()), uv.shape[0], int(n_bits),
+    """BRIEF descriptors of CUDA-resident features straight into packed CUDA words.
+    Tensors, contiguous: uv float32 [n, 2]; words_out int32 / uint32 [n, ceil(n_bits / 32)]."""
+    dev = _call_device(ctx, uv)
+    _check("uv", uv, _F32, (None, 2), dev)
+    n = int(uv.shape[0])
+    _check("words_out", words_out, _WORDS, (n, (max(int(n_bits), 0) + 31) // 32), dev)
+    rc = N.lib().ftk_brief_compute_device(ctx.handle, image_pyr.handle, int(level), C.c_void_p(uv.data_ptr()), n, int(n_bits),
                                           int(half_patch), C.c_void_p(words_out.data_ptr()))
     N.check(rc, ctx.handle)
 
@@ -231,7 +373,8 @@ class DeviceDirectBatch:
     """A batch of DirectMethod pose problems (ftk_direct_track_batch_device): one workgroup per problem, ONE launch.
     Every tensor stays in HBM; ``problems`` is a list of dicts with keys ref, cur (ImagePyramid), K (4 floats),
     p_c_in_ref [n, 3], ref_uv [n, 2], cur_uv [n, 2] (in/out), pose [7] (q w,x,y,z then p; in/out), status [n] uint8,
-    status_valid (bool) and optionally iterations (int32 [1])."""
+    status_valid (bool) and optionally iterations (int32 [1]).
+    Tensors: contiguous, float32 but for status and iterations, on the context's device; checked once, here, where their pointers are taken."""
 
     def __init__(self, options, problems, ctx: Context):
         self.ctx = ctx
@@ -241,17 +384,27 @@ class DeviceDirectBatch:
         self.table = (N.DirectProblem * self.n)()
         for k, pr in enumerate(problems):
             t = self.table[k]
+            where = f"problems[{k}]"
+            dev = _call_device(ctx, pr["ref_uv"])
+            _check(f"{where}['ref_uv']", pr["ref_uv"], _F32, (None, 2), dev)
+            n = int(pr["ref_uv"].shape[0])
+            _check(f"{where}['p_c_in_ref']", pr["p_c_in_ref"], _F32, (n, 3), dev)
+            _check(f"{where}['cur_uv']", pr["cur_uv"], _F32, (n, 2), dev)
+            _check(f"{where}['pose']", pr["pose"], _F32, (7,), dev)
+            _check(f"{where}['status']", pr["status"], _U8, (n,), dev)
+            it = pr.get("iterations")
+            if it is not None:
+                _check(f"{where}['iterations']", it, _COUNTS, (1,), dev)
             t.ref, t.cur = pr["ref"].handle, pr["cur"].handle
             for i in range(4):
                 t.K[i] = float(pr["K"][i])
             t.d_p_c_in_ref = pr["p_c_in_ref"].data_ptr()
             t.d_ref_uv = pr["ref_uv"].data_ptr()
             t.d_cur_uv = pr["cur_uv"].data_ptr()
-            t.n = int(pr["ref_uv"].shape[0])
+            t.n = n
             t.d_pose = pr["pose"].data_ptr()
             t.d_status = pr["status"].data_ptr()
             t.status_valid = int(bool(pr.get("status_valid", False)))
-            it = pr.get("iterations")
             t.d_iterations = None if it is None else it.data_ptr()
 
     def track(self):
@@ -267,17 +420,17 @@ def dense_flow_device(ctx: Context, options, ref_pyr: ImagePyramid, cur_pyr: Ima
 
     opt = options.to_native(k_moments) if isinstance(options, DenseOpticalFlowOptions) else options
     _, rows, cols = ref_pyr.level_desc(0)
-    for t in (flow_r, flow_c):
-        if str(t.dtype) != "torch.float32" or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != (rows, cols):
-            raise ValueError(f"flow planes must be contiguous float32 CUDA tensors of shape ({rows}, {cols})")
+    dev = _call_device(ctx, flow_r)
+    _check("flow_r", flow_r, _F32, (rows, cols), dev)
+    _check("flow_c", flow_c, _F32, (rows, cols), dev)
     rc = N.lib().ftk_dense_flow_device(ctx.handle, C.byref(opt), ref_pyr.handle, cur_pyr.handle, C.c_void_p(flow_r.data_ptr()),
                                        C.c_void_p(flow_c.data_ptr()))
     N.check(rc, ctx.handle)
 
 
 def _corr_check(name, t, dim):
-    if str(t.dtype) != "torch.float32" or not t.is_cuda or not t.is_contiguous() or t.dim() != dim:
-        raise ValueError(f"{name} must be a contiguous {dim}-D float32 CUDA tensor (got {tuple(t.shape)}, {t.dtype}, {t.device})")
+    """A contiguous float32 CUDA tensor of ``dim`` dimensions (the correlation entries take their stream, hence their device, from torch)."""
+    _check(name, t, _F32, (None,) * dim, None)
 
 
 def corr_pyramid_build_device(ctx: Context, fmap0, fmap1, levels: int, volume, stream=None) -> None:
