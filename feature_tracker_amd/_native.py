@@ -18,6 +18,7 @@ FTK_OK = 0
 FTK_MAX_LEVELS = 12
 FTK_CORR_MAX_LEVELS = 16
 FTK_CORR_MAX_RADIUS = 64
+FTK_FLOW_UPSAMPLE_TILE = 32
 ERROR_NAMES = {0: "FTK_OK", -1: "FTK_E_INVALID_ARGUMENT", -2: "FTK_E_NO_DEVICE", -3: "FTK_E_HIP", -4: "FTK_E_UNSUPPORTED",
                -5: "FTK_E_OUT_OF_MEMORY"}
 
@@ -34,7 +35,7 @@ EXPORTS = [
     "ftk_shard_bounds", "ftk_klt_shard_bytes", "ftk_comm_unique_id", "ftk_comm_create", "ftk_comm_destroy", "ftk_comm_rank", "ftk_comm_world",
     "ftk_klt_track_sharded_device", "ftk_klt_track_sharded", "ftk_klt_track_shard_device", "ftk_klt_unpack_shards_device", "ftk_hamming_match_sharded_device",
     "ftk_default_dense_flow_options", "ftk_dense_flow_gaussian", "ftk_dense_flow", "ftk_dense_flow_device", "ftk_dense_flow_level",
-    "ftk_corr_pyramid_layout", "ftk_corr_pyramid_build_device", "ftk_corr_pyramid_lookup_device",
+    "ftk_corr_pyramid_layout", "ftk_corr_pyramid_build_device", "ftk_corr_pyramid_lookup_device", "ftk_flow_upsample_device",
     "ftk_nn_match_scores_device", "ftk_nn_match_scores", "ftk_nn_match_list_device", "ftk_nn_match_list", "ftk_nn_fill_pixels_device",
 ]
 UNIQUE_ID_BYTES = 128
@@ -187,6 +188,7 @@ def lib() -> C.CDLL:
     l.ftk_corr_pyramid_layout.argtypes = [i32, i32, i32, i32, i64p, i64p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     l.ftk_corr_pyramid_build_device.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
     l.ftk_corr_pyramid_lookup_device.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, i32]
+    l.ftk_flow_upsample_device.argtypes = [vp, vp, vp, vp, i32, i32, i32, C.c_float, vp]
     i64, f32 = C.c_int64, C.c_float
     l.ftk_nn_match_scores_device.argtypes = [vp, vp, vp, i32, i32, i32, i64, i64, f32, vp, vp]
     l.ftk_nn_match_scores.argtypes = [vp, vp, i32, i32, i32, i64, i64, f32, vp, vp, C.POINTER(C.c_int)]

@@ -351,6 +351,18 @@ hipError_t corr_build_launch(const CorrBuildParams &p, hipStream_t stream);
 hipError_t corr_pool_launch(const float *src, float *dst, int64_t slabs, int hin, int win, int hout, int wout, hipStream_t stream);
 hipError_t corr_lookup_launch(const CorrLookupParams &p, hipStream_t stream);
 
+// RAFT's convex flow upsampling (raft_upsample_kernels.hip, Raft.UpsampleFlow): one launch.
+constexpr int kFlowUpsampleTile = 32;  // coarse pixels per workgroup along x (FTK_FLOW_UPSAMPLE_TILE)
+struct FlowUpsampleParams {
+    const float *flow;  // [B][2][H][W]
+    const float *mask;  // [B][576][H][W]
+    float *out;         // [B][2][8H][8W]
+    int32_t B, H, W;
+    float mask_scale;
+};
+// hipErrorInvalidValue when the grid would not fit in 2^31 - 1 workgroups
+hipError_t flow_upsample_launch(const FlowUpsampleParams &p, hipStream_t stream);
+
 // NNFeatureMatcher's post-processing (nn_match_kernels.hip): mutual-best matching of a score matrix, or a match list.
 // Keys (unsigned 64-bit, merged with atomicMax, 0 = empty): score mode (order-preserving map of the score << 32 | ~index), so the
 // greatest score wins and, among equal scores, the lowest index; list mode ((k + 1) << 32 | idx_cur), so the last row wins.

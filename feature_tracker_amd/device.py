@@ -475,6 +475,9 @@ def corr_pyramid_lookup_device(ctx: Context, volume, levels: int, radius: int, c
     N.check(rc, ctx.handle)
 
 
+from ._device_flow_upsample import flow_upsample_device  # noqa: E402,F401  (RAFT's UpsampleFlow; its own file, see there)
+
+
 def _nn_stream(torch, device, stream):
     s = torch.cuda.current_stream(device) if stream is None else stream
     return C.c_void_p(s.cuda_stream)

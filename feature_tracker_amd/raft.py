@@ -1,13 +1,16 @@
-"""RAFT's correlation pyramid (src/nn_optical_flow_tracker/raft/correlation_volumes.py:19-83) as a drop-in class.
+"""RAFT's two operators that are not stock torch layers: the correlation pyramid (src/nn_optical_flow_tracker/raft/
+correlation_volumes.py:19-83) as a drop-in class, and the convex flow upsampling (Raft.UpsampleFlow, model.py:48-64) as a function.
 
 ``CorrelationPyramid(fmap0, fmap1, num_levels, radius)`` keeps the reference's attributes (``num_levels``, ``radius``,
 ``correlation_pyramid``) and ``__call__``; ``lookup`` returns the fused ``[B, L*K, H, W]`` tensor that model.py:87-88 builds with
 ``cat`` / ``permute`` / ``contiguous``.  torch owns every buffer (one volume tensor, the levels are views into it) and the kernels
 launch on ``torch.cuda.current_stream()`` at each call, so construction and lookups can be captured in ``torch.cuda.graph``.
+``upsample_flow(flow, mask, mask_scale)`` is ``Raft.UpsampleFlow(flow, mask_scale * mask)`` in one launch.
 Inference only, float32 only, and no CPU fallback.
 """
 from __future__ import annotations
 
+import math
 from typing import Dict, List
 
 from . import _native as N
@@ -25,9 +28,9 @@ def _context(index: int) -> Context:
     return ctx
 
 
-def _check_no_grad(torch, *tensors) -> None:
+def _check_no_grad(torch, *tensors, what: str = "CorrelationPyramid") -> None:
     if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
-        raise RuntimeError("CorrelationPyramid is inference only (no backward): run it under torch.no_grad() or pass tensors that do not "
+        raise RuntimeError(f"{what} is inference only (no backward): run it under torch.no_grad() or pass tensors that do not "
                            "require grad")
 
 
@@ -94,3 +97,33 @@ class CorrelationPyramid:
         out = torch.empty((B, self.num_levels * K, H, W), dtype=torch.float32, device=self._device)
         D.corr_pyramid_lookup_device(self._ctx, self._volume, self.num_levels, self.radius, coords, out, per_level=False)
         return out
+
+
+def upsample_flow(flow, mask, mask_scale: float = 1.0):
+    """``Raft.UpsampleFlow(flow, mask_scale * mask)`` (model.py:48-64; update_block.py:66 is the 0.25 that ``mask_scale`` folds in):
+    ``flow`` [B, 2, H, W] and ``mask`` [B, 576, H, W], float32 CUDA tensors, give a new [B, 2, 8H, 8W] tensor — per fine pixel the
+    softmax of its 9 logits applied to 8 * flow of the zero-padded 3 x 3 coarse neighbourhood, by one HIP kernel
+    (raft_upsample_kernels.hip) on torch's current stream.  ``B`` is just the leading dimension: the flows and masks of T iterations
+    stacked as [T * B, ...] take one call.  Arguments are checked before any device is touched."""
+    import torch
+
+    for name, t, channels in (("flow", flow, 2), ("mask", mask, 576)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 4 or t.size(1) != channels:
+            got = f"{t.dtype} {list(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
+            raise ValueError(f"{name} must be a 4-D float32 CUDA tensor [B, {channels}, H, W] (no CPU fallback, no other dtype): got {got}")
+    B, _, H, W = flow.shape
+    if tuple(mask.shape) != (B, 576, H, W) or flow.device != mask.device:
+        raise ValueError(f"flow and mask must agree in B, H, W and device: {tuple(flow.shape)} on {flow.device} vs {tuple(mask.shape)} on "
+                         f"{mask.device}")
+    if B < 1 or H < 1 or W < 1:
+        raise ValueError(f"flow must not be empty (got {tuple(flow.shape)})")
+    if not math.isfinite(float(mask_scale)):
+        raise ValueError(f"mask_scale must be finite (got {mask_scale})")
+    if not flow.is_cuda:
+        raise ValueError(f"flow and mask must be CUDA tensors (got them on {flow.device}): there is no CPU fallback")
+    _check_no_grad(torch, flow, mask, what="upsample_flow")
+    torch = D._torch()
+    ctx = _context(flow.device.index if flow.device.index is not None else torch.cuda.current_device())
+    out = torch.empty((B, 2, 8 * H, 8 * W), dtype=torch.float32, device=flow.device)
+    D.flow_upsample_device(ctx, flow.contiguous(), mask.contiguous(), out, mask_scale)
+    return out

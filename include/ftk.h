@@ -369,6 +369,20 @@ int ftk_corr_pyramid_build_device(ftk_context *ctx, void *stream, const float *d
 int ftk_corr_pyramid_lookup_device(ftk_context *ctx, void *stream, const float *d_volume, int32_t B, int32_t H, int32_t W, int32_t levels,
                                    int32_t radius, const float *d_coords, float *d_out, int32_t per_level);
 
+/* ---- RAFT convex flow upsampling (src/nn_optical_flow_tracker/raft/model.py) ------------------------ */
+
+/* Coarse pixels along x that one workgroup of the kernel owns: shapes just below, at and above a multiple of it are the ones a test
+ * of the entry below should cover. */
+#define FTK_FLOW_UPSAMPLE_TILE 32
+/* Replaces Raft.UpsampleFlow(flow, mask_scale * mask) (model.py:48-64, the scaling is update_block.py:66): per fine pixel (8y + i, 8x + j)
+ * the softmax over the 9 logits mask[b][k * 64 + i * 8 + j][y][x] * mask_scale, k = 0 .. 8, applied to 8 * flow of the zero-padded
+ * 3 x 3 neighbourhood of coarse pixel (y, x), in the operation order DESIGN.md 5.12 fixes.  d_flow: [B][2][H][W], d_mask: [B][576][H][W],
+ * d_out: [B][2][8H][8W], all contiguous float32 on the context's device.  One launch on `stream` (a hipStream_t; NULL is the null
+ * stream), no allocation, no synchronisation: capturable at any time.  FTK_E_INVALID_ARGUMENT, before any launch, for a null pointer,
+ * a non-positive size, a non-finite mask_scale or a mask whose byte count overflows int64. */
+int ftk_flow_upsample_device(ftk_context *ctx, void *stream, const float *d_flow, const float *d_mask, int32_t B, int32_t H, int32_t W,
+                             float mask_scale, float *d_out);
+
 /* ---- features sharded over the GPUs of one node ------------------------ */
 
 /*

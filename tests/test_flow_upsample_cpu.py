@@ -1,0 +1,342 @@
+"""RAFT's convex flow upsampling without a device: the scalar restatement (tests/flow_upsample_ref.c) pinned against
+the reference's own arithmetic (the torch composition of Raft.UpsampleFlow, model.py:48-64, written out below and evaluated in float64
+and in float32), known answers that separate the index mapping from the softmax, hostile logits, the accuracy of exp_c against float64
+exp, two mutants of the restatement that the float64 comparison must reject, and the loud failures of the Python entries.
+
+Measured on the cases below (printed by the tests, -s shows them), in units of 2^-24 * max|8 flow|:
+restatement against float64 3.31 (the bound is 32), torch's float32 composition against float64 3.31 as well (at the worst output
+both round to the same float32), restatement against torch's float32 1.48 (the bound is 64); exp_c against float64 exp over
+10 258 303 arguments: 0.937 ulp."""
+import functools
+import math
+import types
+
+import numpy as np
+import pytest
+
+from tests import flow_upsample_ref as R
+
+torch = pytest.importorskip("torch")
+
+# |out - ref64| <= UNITS * u, u = 2^-24 * max|8 flow| (one rounding is at most 1 u relative).  Derived, not tuned, every
+# error with the same sign and exp_c at 2 ulp = 4 u: the nine numerators carry exp_c's 4 u plus the rounded subtraction's
+# |x_k - m| e^(x_k - m) u, at most 0.75 u over the nine weights; the sum s inherits both (4.75 u) and adds 8 roundings; the division 1;
+# the product 1; the output's 8 additions 1 each: 4.75 + 12.75 + 1 + 1 + 8 = 27.5 u, and 32 is the next power of two.
+UNITS = 32
+EXP_C_ULP_BOUND = 1  # the measured 0.937 ulp rounded up to the next integer (the derivation above allows 2)
+
+CASES = [(2, 3, 5, 1.0), (1, 1, 1, 4.0), (1, 2, 7, 20.0), (1, 9, 33, 1.0)]  # (B, H, W, logit scale)
+
+
+def torch_upsample(flow, mask):
+    """model.py:48-64, line by line, in the dtype of its arguments."""
+    B, _, H, W = flow.size()
+    mask = mask.view(B, 1, 9, 8, 8, H, W)
+    mask = torch.softmax(mask, dim=2)
+    up = torch.nn.functional.unfold(8 * flow, [3, 3], padding=1)
+    up = up.view(B, 2, 9, 1, 1, H, W)
+    up = torch.sum(up * mask, dim=2)
+    up = up.permute(0, 1, 4, 2, 5, 3)
+    return up.reshape(B, 2, H * 8, W * 8)
+
+
+def inputs(seed, B, H, W, logit_scale, flow_scale=3.0):
+    g = torch.Generator().manual_seed(seed)
+    flow = (torch.randn(B, 2, H, W, generator=g) * flow_scale).float()
+    mask = (torch.randn(B, 576, H, W, generator=g) * logit_scale).float()
+    return flow, mask
+
+
+@functools.lru_cache(maxsize=None)
+def case(k):
+    """(flow, mask, ref64, ref32, unit) of CASES[k], computed once and shared; nobody writes to them."""
+    B, H, W, scale = CASES[k]
+    flow, mask = inputs(100 + k, B, H, W, scale)
+    ref64 = torch_upsample(flow.double(), mask.double()).numpy()
+    ref32 = torch_upsample(flow, mask).numpy()
+    unit = 2.0 ** -24 * float((8 * flow).abs().max())
+    return flow.numpy(), mask.numpy(), ref64, ref32, unit
+
+
+def units_off(out, ref, unit):
+    return float(np.abs(out.astype(np.float64) - ref.astype(np.float64)).max()) / unit
+
+
+@pytest.mark.parametrize("k", range(len(CASES)), ids=[str(c) for c in CASES])
+def test_restatement_against_float64(k):
+    flow, mask, ref64, ref32, unit = case(k)
+    got = units_off(R.upsample(flow, mask), ref64, unit)
+    print(f"case {CASES[k]}: restatement vs float64 {got:.2f} units, torch float32 vs float64 {units_off(ref32, ref64, unit):.2f} (bound {UNITS})")
+    assert got <= UNITS
+
+
+@pytest.mark.parametrize("k", range(len(CASES)), ids=[str(c) for c in CASES])
+def test_restatement_against_torch_float32(k):
+    """Not bit-identical: torch's vector exp and its summation order are its own.  The bound is the float64 one, doubled."""
+    flow, mask, _, ref32, unit = case(k)
+    got = units_off(R.upsample(flow, mask), ref32, unit)
+    print(f"case {CASES[k]}: restatement vs torch float32 {got:.2f} units (bound {2 * UNITS})")
+    assert got <= 2 * UNITS
+
+
+@pytest.mark.parametrize("variant", [R.MUTANT_TRANSPOSED_WINDOW, R.MUTANT_DEGREE_3], ids=["window transposed", "exp_c of degree 3"])
+def test_mutants_fail_the_float64_comparison(variant):
+    """The comparison above has teeth: a restatement with the 3 x 3 window transposed, and one whose exp_c stops at degree 3, miss the
+    bound (on every case with more than one pixel resp. on every case)."""
+    worst = []
+    for k in range(len(CASES)):
+        flow, mask, ref64, _, unit = case(k)
+        worst.append(units_off(R.upsample(flow, mask, variant=variant), ref64, unit))
+    print(f"mutant {variant}: {['%.3g' % w for w in worst]} units (bound {UNITS})")
+    assert max(worst) > UNITS
+    if variant == R.MUTANT_DEGREE_3:
+        assert min(worst) > UNITS
+
+
+# ---- known answers -------------------------------------------------------------------------------------------------------------
+
+
+def padded_eight_flow(flow):
+    return np.pad(np.float32(8) * flow, ((0, 0), (0, 0), (1, 1), (1, 1)))
+
+
+def test_equal_logits_give_the_sequential_mean():
+    """All nine logits equal: every e_k is exp_c(0) = 1, s = 9, and every fine pixel of a coarse pixel is the sum of f_k * (1 / 9) over
+    the padded neighbourhood in the contract's order, in float32, bit for bit."""
+    flow, _ = inputs(7, 2, 4, 6, 1.0)
+    flow = flow.numpy()
+    B, _, H, W = flow.shape
+    mask = np.full((B, 576, H, W), 0.7, np.float32)
+    pad = padded_eight_flow(flow)
+    w = np.float32(1) / np.float32(9)
+    acc = None
+    for k in range(9):
+        p = pad[:, :, k // 3:k // 3 + H, k % 3:k % 3 + W] * w
+        acc = p if acc is None else acc + p
+    assert acc.dtype == np.float32
+    want = np.repeat(np.repeat(acc, 8, axis=2), 8, axis=3)
+    assert R.same(R.upsample(flow, mask), want)
+
+
+@pytest.mark.parametrize("k", range(9))
+def test_one_dominant_logit_copies_that_neighbour(k):
+    """Logit k at +200 over the rest: weight exactly 1 on neighbour k and exactly 0 elsewhere, so the output is 8 * flow of that
+    neighbour; where it lies outside the image, exactly +0."""
+    flow, _ = inputs(8, 1, 3, 4, 1.0)
+    flow = flow.numpy()
+    B, _, H, W = flow.shape
+    mask = np.zeros((B, 576, H, W), np.float32)
+    mask[:, k * 64:(k + 1) * 64] = 200.0
+    out = R.upsample(flow, mask)
+    pad = padded_eight_flow(flow)
+    want = np.repeat(np.repeat(pad[:, :, k // 3:k // 3 + H, k % 3:k % 3 + W], 8, axis=2), 8, axis=3)
+    assert np.array_equal(out, want)
+    outside = np.ones((H + 2, W + 2), bool)
+    outside[1:-1, 1:-1] = False
+    border = np.repeat(np.repeat(outside[k // 3:k // 3 + H, k % 3:k % 3 + W], 8, axis=0), 8, axis=1)
+    assert not np.signbit(out[:, :, border]).any() and (out[:, :, border] == 0).all()
+
+
+def test_index_mapping_apart_from_the_softmax():
+    """A flow that is nonzero at ONE coarse pixel and a one-hot mask whose k depends on (i, j) asymmetrically (k = (j - i) mod 9):
+    fine pixel (8y + i, 8x + j) shows the value exactly where neighbour k of (y, x) is that pixel.  Swapping i and j, in the mask
+    channel k * 64 + i * 8 + j or in the output position, changes the picture."""
+    H, W, yc, xc = 4, 5, 2, 1
+    flow = np.zeros((1, 2, H, W), np.float32)
+    flow[0, :, yc, xc] = (1.5, -2.25)
+    mask = np.zeros((1, 576, H, W), np.float32)
+    want = np.zeros((1, 2, 8 * H, 8 * W), np.float32)
+    swapped = np.zeros_like(want)
+    for i in range(8):
+        for j in range(8):
+            k = (j - i) % 9
+            mask[0, k * 64 + i * 8 + j] = 200.0
+            for y in range(H):
+                for x in range(W):
+                    if (y + k // 3 - 1, x + k % 3 - 1) == (yc, xc):
+                        want[0, :, 8 * y + i, 8 * x + j] = (12.0, -18.0)
+                        swapped[0, :, 8 * y + j, 8 * x + i] = (12.0, -18.0)
+    out = R.upsample(flow, mask)
+    assert np.array_equal(out, want)
+    assert not np.array_equal(out, swapped)
+
+
+def test_mask_scale_is_one_rounded_multiply():
+    """0.25 on 4 m equals 1 on m bit for bit (both multiplies are exact); 1 is the identity; 0.3 rounds and still meets the bound."""
+    flow, mask, _, _, _ = case(0)
+    base = R.upsample(flow, mask, 1.0)
+    assert R.same(R.upsample(flow, np.float32(4) * mask, 0.25), base)
+    scaled = (mask * np.float32(0.3)).astype(np.float32)
+    assert R.same(R.upsample(flow, mask, 0.3), R.upsample(flow, scaled, 1.0))
+
+
+# ---- hostile logits ------------------------------------------------------------------------------------------------------------
+
+NAN, INF = float("nan"), float("inf")
+BELOW_CUTOFF = float(np.nextafter(np.float32(-87.0), np.float32(-INF)))
+# (what, the nine logits, whether every weight is NaN)
+HOSTILE = [
+    ("NaN at k = 0", [NAN, 0.5, -1, 2, 0, 1, -2, 0.25, 3], True),
+    ("NaN at k = 5", [0.5, -1, 2, 0, 1, NAN, -2, 0.25, 3], True),
+    ("+inf", [0.5, -1, INF, 0, 1, 2, -2, 0.25, 3], True),
+    ("nine -inf", [-INF] * 9, True),
+    ("one -inf", [0.5, -1, 2, -INF, 1, 0, -2, 0.25, 3], False),
+    ("x - m at the cutoff", [0.0, -87.0, -1, -2, -3, -4, -5, -6, -7], False),
+    ("x - m just below the cutoff", [0.0, BELOW_CUTOFF, -1, -2, -3, -4, -5, -6, -7], False),
+    ("all but one below the cutoff", [-90.0] * 4 + [0.0] + [-1000.0] * 4, False),
+]
+
+
+def hostile_inputs(H=3, W=len(HOSTILE) + 1):
+    """Random inputs whose middle row carries HOSTILE[q] at coarse pixel (1, q), every sub-pixel; column W - 1 stays ordinary."""
+    flow, mask = inputs(9, 1, H, W, 1.0)
+    flow, mask = flow.numpy().copy(), mask.numpy().copy()
+    for q, (_, logits, _) in enumerate(HOSTILE):
+        for k, v in enumerate(logits):
+            mask[0, k * 64:(k + 1) * 64, 1, q] = v
+    return flow, mask
+
+
+def test_hostile_logits():
+    """IEEE as the contract's steps say: NaN where torch gives NaN, weight 0 for a logit at -inf or below the cutoff, and every finite
+    output within the float64 bound."""
+    flow, mask = hostile_inputs()
+    out = R.upsample(flow, mask)
+    with np.errstate(all="ignore"):
+        ref64 = torch_upsample(torch.from_numpy(flow).double(), torch.from_numpy(mask).double()).numpy()
+    assert np.array_equal(np.isnan(out), np.isnan(ref64))
+    for q, (what, _, all_nan) in enumerate(HOSTILE):
+        block = out[0, :, 8:16, 8 * q:8 * q + 8]
+        assert np.isnan(block).all() == all_nan and np.isnan(block).any() == all_nan, what
+    assert not np.isnan(out[0, :, :8]).any() and not np.isnan(out[0, :, :, -8:]).any()
+    finite = ~np.isnan(out)
+    unit = 2.0 ** -24 * float(np.abs(8 * flow).max())
+    assert float(np.abs(out[finite] - ref64[finite]).max()) <= UNITS * unit
+    # a -inf logit is a weight of exactly 0: the same bits as any logit far below the cutoff
+    q = [h[0] for h in HOSTILE].index("one -inf")
+    far = mask.copy()
+    far[0, 3 * 64:4 * 64, 1, q] = -1000.0
+    assert R.same(R.upsample(flow, far), out)
+
+
+def test_cutoff_sides():
+    c = R.cutoff()
+    assert c == np.float32(-87.0)
+    at, below, nan, zero, ninf = R.exp_c(np.float32([c, BELOW_CUTOFF, NAN, 0.0, -INF]))
+    assert at > 0 and at >= np.finfo(np.float32).tiny and abs(float(at) / math.exp(-87.0) - 1) < 1e-6  # a normal number
+    assert below == 0 and not np.signbit(below) and ninf == 0
+    assert np.isnan(nan) and zero == 1
+
+
+# ---- exp_c against float64 exp -------------------------------------------------------------------------------------------------
+
+
+def sweep_arguments():
+    """10 M seeded arguments in [cutoff, 0] (uniform, and log-uniform towards 0), every float32 within 512 ulp of each reduction
+    boundary (n +- 1/2) ln 2, and the arguments 0 and the cutoff."""
+    rng = np.random.default_rng(12)
+    parts = [rng.uniform(-87.0, 0.0, 8_000_000).astype(np.float32), (-np.exp(rng.uniform(np.log(1e-30), np.log(87.0), 2_000_000))).astype(np.float32)]
+    steps = np.arange(-512, 513, dtype=np.int64)
+    for n in range(0, -127, -1):
+        for half in (-0.5, 0.5):
+            b = np.float32((n + half) * math.log(2.0))
+            if -87.0 <= b < 0:
+                parts.append((np.int64(b.view(np.int32)) + steps).astype(np.int32).view(np.float32))
+    parts.append(np.float32([0.0, -0.0, -87.0]))
+    t = np.concatenate(parts)
+    return t[(t >= np.float32(-87.0)) & (t <= 0)]
+
+
+def test_exp_c_against_float64_exp():
+    t = sweep_arguments()
+    assert t.size >= 10_000_000 and (t == 0).any() and (t == np.float32(-87.0)).any()
+    got = R.exp_c(t)
+    want = np.exp(t.astype(np.float64))
+    assert (got >= np.finfo(np.float32).tiny).all() and (got <= 1).all()  # normal numbers, never above exp(0)
+    _, exponent = np.frexp(want)  # want = f * 2^exponent, f in [0.5, 1): its float32 ulp is 2^(exponent - 24)
+    err = np.abs(got.astype(np.float64) - want) / np.ldexp(1.0, exponent - 24)
+    worst = int(err.argmax())
+    print(f"exp_c over {t.size} arguments: max error {err.max():.3f} ulp at t = {float(t[worst])!r} (bound {EXP_C_ULP_BOUND})")
+    assert err.max() <= EXP_C_ULP_BOUND
+
+
+# ---- loud failures, before any device is touched -------------------------------------------------------------------------------
+
+
+def test_wrapper_refuses_bad_arguments_without_a_device():
+    import feature_tracker_amd as F
+    flow, mask = torch.zeros(2, 2, 3, 5), torch.zeros(2, 576, 3, 5)
+    bad = [
+        ("flow must be", (flow.double(), mask)), ("mask must be", (flow, mask.half())),                       # dtype
+        ("flow must be", (flow[0], mask)), ("mask must be", (flow, mask[None])),                              # rank
+        ("flow must be", (torch.zeros(2, 3, 3, 5), mask)), ("mask must be", (flow, torch.zeros(2, 575, 3, 5))),  # channels
+        ("agree", (flow, torch.zeros(2, 576, 4, 5))), ("agree", (flow, torch.zeros(2, 576, 3, 6))), ("agree", (flow, torch.zeros(3, 576, 3, 5))),
+        ("flow must be", (flow.numpy(), mask)),
+    ]
+    for match, args in bad:
+        with pytest.raises(ValueError, match=match):
+            F.upsample_flow(*args)
+    for scale in (NAN, INF, -INF):
+        with pytest.raises(ValueError, match="mask_scale"):
+            F.upsample_flow(flow, mask, scale)
+    with pytest.raises(ValueError, match="no CPU fallback"):
+        F.upsample_flow(flow, mask)
+    with pytest.raises(ValueError, match="no CPU fallback"):
+        F.upsample_flow(flow, mask, 0.25)
+
+
+def test_device_entry_refuses_bad_arguments_without_a_device():
+    from feature_tracker_amd import device as D
+    ctx = types.SimpleNamespace(handle=None)
+    flow, mask, out = torch.zeros(1, 2, 3, 5), torch.zeros(1, 576, 3, 5), torch.zeros(1, 2, 24, 40)
+    with pytest.raises(ValueError, match="^flow must be a CUDA tensor"):
+        D.flow_upsample_device(ctx, flow, mask, out)
+    with pytest.raises(ValueError, match="^flow must be .*wrong dtype"):
+        D.flow_upsample_device(ctx, flow.double(), mask, out)
+    with pytest.raises(ValueError, match="mask_scale"):
+        D.flow_upsample_device(ctx, flow, mask, out, mask_scale=NAN)
+
+
+# the walk of tests/test_device_args_cpu.py (duck-typed tensors, a recording stand-in for the native library) over this entry
+def _walk_call(w):
+    from feature_tracker_amd import device as D
+    return D.flow_upsample_device(w.ctx, w.t("flow", "float32", 2, 2, 3, 5), w.t("mask", "float32", 2, 576, 3, 5), w.t("out", "float32", 2, 2, 24, 40), 0.25)
+
+
+def test_device_entry_takes_no_pointer_of_an_unchecked_argument(monkeypatch):
+    from tests.test_device_args_cpu import _Walk
+    w = _Walk(monkeypatch)
+    _walk_call(w)
+    assert w.unchecked_reads == [] and w.lib.calls == ["ftk_flow_upsample_device"]
+    assert [f.name for f in w.made if f.reads != 1] == []
+
+
+@pytest.mark.parametrize("which,change,match", [
+    (0, ("dtype", "float64"), "flow must be"), (1, ("dtype", "float64"), "mask must be"), (2, ("dtype", "float64"), "out must be"),
+    (1, ("shape", (2, 575, 3, 5)), "mask must be.*dimension 1 is 575, not 576"), (1, ("shape", (2, 576, 4, 5)), "mask must be.*dimension 2"),
+    (1, ("shape", (2, 576, 3, 6)), "mask must be.*dimension 3"), (1, ("shape", (3, 576, 3, 5)), "mask must be.*dimension 0"),
+    (2, ("shape", (2, 2, 3, 5)), "out must be.*dimension 2 is 3, not 24"), (0, ("shape", (2, 2, 15)), "flow must be.*3 dimensions instead of 4"),
+    (2, ("device", 1), "out must be on cuda:0"),
+])
+def test_device_entry_stops_before_the_library(monkeypatch, which, change, match):
+    from tests.test_device_args_cpu import _FakeDevice, _FakeDtype, _Walk
+    w = _Walk(monkeypatch)
+    real_t, count = w.t, [0]
+
+    def t(name, dtype, *shape):
+        fake = real_t(name, dtype, *shape)
+        if count[0] == which:
+            kind, value = change
+            if kind == "dtype":
+                fake.dtype = _FakeDtype(value)
+            elif kind == "shape":
+                fake.shape = tuple(value)
+            else:
+                fake.device = _FakeDevice(value)
+        count[0] += 1
+        return fake
+
+    w.t = t
+    with pytest.raises(ValueError, match=match):
+        _walk_call(w)
+    assert w.lib.calls == [] and w.unchecked_reads == []
