@@ -1112,16 +1112,23 @@ __device__ __forceinline__ void se2_update(LssdState &s, const float (&v)[3], in
 // Vec3::squaredNorm(): Eigen's unrolled reduction of a fixed 3-vector is a0 + (a1 + a2)
 __device__ __forceinline__ float vec3_squared_norm(const float (&v)[3]) { return v[0] * v[0] + (v[1] * v[1] + v[2] * v[2]); }
 
+// The nine products of a pixel, in the order of the chains (the header of this section) — the ONE place that states them: the
+// upper triangle of J^T J row by row for J = (j0, j1, j2), then -J^T r.  `put(k, product)` stores product k where its caller sums.
+template <typename Put>
+__device__ __forceinline__ void lssd_products(float j0, float j1, float j2, float residual, Put put) {
+    put(0, j0 * j0);
+    put(1, j0 * j1);
+    put(2, j0 * j2);
+    put(3, j1 * j1);
+    put(4, j1 * j2);
+    put(5, j2 * j2);
+    put(6, -(j0 * residual));
+    put(7, -(j1 * residual));
+    put(8, -(j2 * residual));
+}
+
 __device__ __forceinline__ void lssd_terms(const KltParams &p, float *terms, int pxi, bool ok, float j0, float j1, float j2, float residual) {
-    terms[0 * p.Ppad + pxi] = ok ? j0 * j0 : 0.0f;
-    terms[1 * p.Ppad + pxi] = ok ? j0 * j1 : 0.0f;
-    terms[2 * p.Ppad + pxi] = ok ? j0 * j2 : 0.0f;
-    terms[3 * p.Ppad + pxi] = ok ? j1 * j1 : 0.0f;
-    terms[4 * p.Ppad + pxi] = ok ? j1 * j2 : 0.0f;
-    terms[5 * p.Ppad + pxi] = ok ? j2 * j2 : 0.0f;
-    terms[6 * p.Ppad + pxi] = ok ? -(j0 * residual) : 0.0f;
-    terms[7 * p.Ppad + pxi] = ok ? -(j1 * residual) : 0.0f;
-    terms[8 * p.Ppad + pxi] = ok ? -(j2 * residual) : 0.0f;
+    lssd_products(j0, j1, j2, residual, [&](int k, float product) { terms[k * p.Ppad + pxi] = ok ? product : 0.0f; });
 }
 
 // Wave 0: solves the 3x3 system from the nine chain sums and publishes v in sums[16..18].
@@ -1146,6 +1153,191 @@ __device__ __forceinline__ bool lssd_solve_and_update(const float *sums, LssdSta
         return false;
     }
     se2_update<true>(s, v, lane);  // every wave in full, on the same published solution
+    return true;
+}
+
+// --- per-pixel helpers of the three LSSD-fast level forms (lssd_level_fast, lssd_level_fast_chunked, lssd_level_fast_chunked_lum) ---
+
+// ExtractPatchInCurrentImage's test (lssd_klt_fast.cpp:145-160): does the conservative bounding box of the patch around `centre`
+// leave the rectangle in which every bilinear tap is inside `cur`?  Wave-uniform: scalar from the readfirstlane on.
+__device__ __forceinline__ bool lssd_partly_outside(const KltParams &p, const DevImage &cur, float centre_u, float centre_v) {
+    const int min_row = wadd(__builtin_amdgcn_readfirstlane(f2i(centre_v)), -p.patch_rows);
+    const int min_col = wadd(__builtin_amdgcn_readfirstlane(f2i(centre_u)), -p.patch_cols);
+    const int max_row = wadd(min_row, p.patch_rows * 2);
+    const int max_col = wadd(min_col, p.patch_cols * 2);
+    return min_row < 0 || max_row > cur.rows - 2 || min_col < 0 || max_col > cur.cols - 2;
+}
+
+// One pixel of the current patch (lssd_klt_fast.cpp:162-193): the checked sample with a zeroed miss when the patch is partly
+// outside, the unchecked bilinear (:189) otherwise.
+// kRoomy (the one-wave chunked forms; every lane of the wave must be here): when every lane's sample lies inside the image with
+// room for its +1 neighbours (the normal case: a rotation moves a pixel less than the conservative box of lssd_partly_outside
+// allows for) the cheaper bilinear_inside gives the same values.
+template <bool kRoomy>
+__device__ __forceinline__ bool lssd_sample_cur(const DevImage &cur, const Win &cw, float row_j, float col_j, bool partly_outside, float &value) {
+    bool ok_cur;
+    value = 0.0f;
+    if (partly_outside) {
+        ok_cur = sample(cur, cw, row_j, col_j, value);
+        if (!ok_cur) {
+            value = 0.0f;
+        }
+    } else {
+        bool all_roomy = false;
+        if constexpr (kRoomy) {
+            // 0 <= x <= M as ONE unsigned compare of the bit patterns (M >= 0 here: !partly_outside): negative values, -0 and
+            // NaNs have larger patterns than any finite M and take the general form below, which returns the same values
+            const bool roomy = (unsigned)__float_as_int(row_j) <= (unsigned)__float_as_int((float)(cur.rows - 2)) &&
+                               (unsigned)__float_as_int(col_j) <= (unsigned)__float_as_int((float)(cur.cols - 2));
+            all_roomy = wave_ballot(!roomy) == 0ull;
+        }
+        if (all_roomy) {
+            value = bilinear_inside(cur, cw, row_j, col_j);
+        } else {
+            value = bilinear(cur, cw, row_j, col_j);
+        }
+        ok_cur = true;
+    }
+    return ok_cur;
+}
+
+// The Jacobian's rotation column of the pixel at (row_i, col_i) with gradient (dx, dy) (lssd_klt_fast.cpp:214-219); the other two
+// columns are dx and dy themselves.
+__device__ __forceinline__ float lssd_pixel_j0(const LssdState &s, float row_i, float col_i, float dx, float dy) {
+    const float s0 = s.r00 * (-row_i) + s.r01 * col_i;
+    const float s1 = s.r10 * (-row_i) + s.r11 * col_i;
+    return dx * s0 + dy * s1;
+}
+
+// A lane's pixel of a chunk into the ring ([9][kChunkRow]): its nine products (lssd_products), row k = product k.  `px` is the
+// pixel's record {dx, dy, reference value, valid} (lssd_chunked_entry), `value` its sample in the current image.
+// An unused pixel contributes exact zeros to every sum (lssd_terms): zeroing the four factors does it with four selects instead of
+// nine — the products are then +0 or -0, and x + (+-0) == x for every x a sum can hold (the sums start at +0 and +0 + (-0) == +0).
+__device__ __forceinline__ void lssd_ring_products(float *ring, int lane, bool ok, const LssdState &s, float row_i, float col_i, const float4 &px,
+                                                   float value) {
+    const float dx = ok ? px.x : 0.0f, dy = ok ? px.y : 0.0f;
+    const float j0 = ok ? lssd_pixel_j0(s, row_i, col_i, px.x, px.y) : 0.0f;
+    const float residual = ok ? value - px.z : 0.0f;
+    lssd_products(j0, dx, dy, residual, [&](int k, float product) { ring[k * kChunkRow + lane] = product; });
+}
+
+// Advances the kSums exact-order sums (9: the products; 1: the luminance form's mean, in ring row 0) over chunk `chunk` of the ring.
+// quad chain: every lane works, quad q carries sum q (klt_common.h "quad chain"); the quads behind the last sum follow its row and
+// are ignored.  A launch that oversubscribes the chip keeps one lane per sum (KltParams::quad_chain): there the instruction COUNT
+// decides.  Either way sum k ends in lane k * sum_lanes(p).
+template <int kSums>
+__device__ __forceinline__ float lssd_chain_ring(const Blk &b, const KltParams &p, const float *ring, int chunk, float acc) {
+    const int left = p.P - chunk * kChunkPixels;
+    if (p.quad_chain) {
+        return chain_quads_left(acc, ring + min(b.lane >> 2, kSums - 1) * kChunkRow + 4 * (b.lane & 3), left);
+    }
+    if (b.lane < kSums) {
+        return chain_chunk_left(acc, ring + b.lane * kChunkRow, left);
+    }
+    return acc;
+}
+
+// What a chunked level keeps from its entry (lssd_chunked_entry) to its iterations.
+struct LssdChunked {
+    float *ring;        // [9][kChunkRow]
+    const float4 *rec;  // per patch pixel: {dx, dy, reference value, valid}
+    const float2 *rc;   // per patch pixel: {row_i, col_i}
+    int n_chunks;
+    Win cw;
+    bool cw_staged;
+    float last_squared_step;
+    uint32_t large_step_cnt;
+};
+
+// The tail of a chunked iteration: the nine sums sit in `acc` of lanes k * sum_lanes(p) — broadcast (v_readlane, no round trip
+// through LDS), solve (lssd_solve on registers), update `s`.  Returns whether the level goes on; `status` is set when it does not.
+__device__ __forceinline__ bool lssd_chunked_step(const Blk &b, const KltParams &p, float acc, LssdState &s, LssdChunked &lv, uint8_t &status) {
+    const int acc_bits = __float_as_int(acc);
+    const int sl = __builtin_amdgcn_readfirstlane(sum_lanes(p));
+    float sum[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        sum[k] = __int_as_float(__builtin_amdgcn_readlane(acc_bits, k * sl));
+    }
+    const float bb[3] = {sum[6], sum[7], sum[8]};
+    float v[3];
+    ldlt3_solve<true>(sum[0], sum[1], sum[2], sum[3], sum[4], sum[5], bb, v, b.lane);
+    if (isnan(v[0]) || isnan(v[1]) || isnan(v[2])) {
+        status = FTK_NUMERIC_ERROR;
+        return false;
+    }
+    se2_update<true>(s, v, b.lane);
+    return !fast_step_logic(p, vec3_squared_norm(v), lv.last_squared_step, lv.large_step_cnt, status);
+}
+
+// The level entry of the two chunked forms (lssd_klt_fast.cpp:7-46).  Returns false (status = FTK_OUTSIDE) when no pixel of the
+// extended reference patch is inside the image.
+// The chunked variants have a0_floats == 0: the extended patch (level entry only) lives in the ring's space (iterations only).
+// What an iteration needs of a patch pixel is laid out by pixel: {dx, dy, reference value, valid} and {row_i, col_i} — one
+// 16-byte and one 8-byte conflict-free read per pixel instead of the row / column division, the index into the extended
+// patch and four scattered reads, every iteration.
+// LUM (consider_patch_luminance, :27-46): the gradients and the patch value are each divided by the reference mean (the gradients
+// are differences of UNSCALED values).  The reference's quirk is kept: the mean's numerator covers the interior of the EXTENDED
+// patch (= the patch) and its denominator the valid count of the whole extended patch.
+template <bool LUM>
+__device__ __forceinline__ bool lssd_chunked_entry(const Blk &b, const KltParams &p, const DevImage &ref, const DevImage &cur, float ref_u,
+                                                   float ref_v, const LssdState &s, uint8_t &status, Carve &c, LssdChunked &lv) {
+    c.a0 = c.terms;
+    const float *ex = c.a0;
+    const uint8_t *exv = c.flagsE;
+    float4 *rec = reinterpret_cast<float4 *>(c.a1);
+    float2 *rc = reinterpret_cast<float2 *>(c.a1 + 4 * p.Ppad);
+    lv.ring = c.terms;
+    lv.rec = rec;
+    lv.rc = rc;
+    lv.n_chunks = (p.P + kChunkPixels - 1) / kChunkPixels;
+    Win rw;
+    float level_centre_u, level_centre_v;
+    se2_apply(s, ref_u, ref_v, level_centre_u, level_centre_v);
+    stage_level_windows(b, p, ref, cur, ref_u, ref_v, level_centre_u, level_centre_v, c, rw, lv.cw);
+    lv.cw_staged = true;
+    const uint32_t ref_valid_num = extract_extended_patch(b, p, ref, rw, ref_u, ref_v, c);
+    if (ref_valid_num == 0) {
+        status = FTK_OUTSIDE;
+        return false;
+    }
+    float ref_average = 1.0f;
+    if constexpr (LUM) {
+        // :27-35 — the interior of the extended patch in row-major order (== the P patch pixels), summed by lane 0 from a
+        // contiguous row laid over the (not yet written) per-pixel records
+        float *row = c.a1;
+        for (int pxi = b.tid; pxi < p.Ppad; pxi += b.nt) {
+            int prow, pcol;
+            pixel_rc(p, pxi < p.P ? pxi : 0, prow, pcol);
+            row[pxi] = pxi < p.P ? ex[imul(prow + 1, p.ex_cols) + pcol + 1] : 0.0f;
+        }
+        blk_sync(b);
+        float ref_sum = 0.0f;
+        if (b.lane == 0) {
+            ref_sum = chain_lane(row, p.Ppad);
+        }
+        ref_average = uniform_lane(ref_sum, 0) / (float)ref_valid_num;
+        blk_sync(b);
+    }
+    for (int pxi = b.tid; pxi < p.P; pxi += b.nt) {
+        int prow, pcol;
+        pixel_rc(p, pxi, prow, pcol);
+        float dx, dy;
+        ex_gradient(p, ex, exv, prow, pcol, dx, dy);
+        const int ei = imul(prow, p.ex_cols) + pcol + (p.ex_cols + 1);
+        float value = ex[ei];
+        if constexpr (LUM) {
+            dx /= ref_average;
+            dy /= ref_average;
+            value /= ref_average;
+        }
+        rec[pxi] = make_float4(dx, dy, value, __int_as_float(exv[ei] != 0 ? -1 : 0));
+        rc[pxi] = make_float2((float)(prow - p.half_rows) + ref_v, (float)(pcol - p.half_cols) + ref_u);
+    }
+    blk_sync(b);
+    status = FTK_LARGE_RESIDUAL;
+    lv.last_squared_step = INFINITY;
+    lv.large_step_cnt = 0;
     return true;
 }
 
@@ -1283,11 +1475,7 @@ __device__ __forceinline__ void lssd_level_fast(const Blk &b, const KltParams &p
         float centre_u, centre_v;
         se2_apply(s, ref_u, ref_v, centre_u, centre_v);
         ensure_cur_window(b, p, cur, centre_u, centre_v, c, cw, cw_staged);
-        const int min_row = wadd(__builtin_amdgcn_readfirstlane(f2i(centre_v)), -p.patch_rows);  // wave-uniform: scalar from here on
-        const int min_col = wadd(__builtin_amdgcn_readfirstlane(f2i(centre_u)), -p.patch_cols);
-        const int max_row = wadd(min_row, p.patch_rows * 2);
-        const int max_col = wadd(min_col, p.patch_cols * 2);
-        const bool partly_outside = (min_row < 0 || max_row > cur.rows - 2 || min_col < 0 || max_col > cur.cols - 2);
+        const bool partly_outside = lssd_partly_outside(p, cur, centre_u, centre_v);
         uint32_t cur_valid_num = 0;
         if (!p.consider_luminance) {
             // Without the luminance scaling nothing separates ExtractPatchInCurrentImage from ComputeHessianAndBias but
@@ -1304,24 +1492,12 @@ __device__ __forceinline__ void lssd_level_fast(const Blk &b, const KltParams &p
                     const float col_i = (float)(pcol - p.half_cols) + ref_u;
                     float row_j, col_j;
                     se2_apply(s, col_i, row_i, col_j, row_j);
-                    float value = 0.0f;
-                    if (partly_outside) {
-                        ok_cur = sample(cur, cw, row_j, col_j, value);
-                        if (!ok_cur) {
-                            value = 0.0f;
-                        }
-                    } else {
-                        value = bilinear(cur, cw, row_j, col_j);
-                        ok_cur = true;
-                    }
+                    float value;
+                    ok_cur = lssd_sample_cur<false>(cur, cw, row_j, col_j, partly_outside, value);
                     const int ei = imul(prow + 1, p.ex_cols) + pcol + 1;
                     ok = exv[ei] != 0 && ok_cur;
-                    const float s0 = s.r00 * (-row_i) + s.r01 * col_i;
-                    const float s1 = s.r10 * (-row_i) + s.r11 * col_i;
                     const float dx = dxs[pxi], dy = dys[pxi];
-                    const float j0 = dx * s0 + dy * s1;
-                    const float residual = value - ex[ei];
-                    lssd_terms(p, c.terms, pxi, ok, j0, dx, dy, residual);
+                    lssd_terms(p, c.terms, pxi, ok, lssd_pixel_j0(s, row_i, col_i, dx, dy), dx, dy, value - ex[ei]);
                 }
                 cur_valid_num += (uint32_t)__popcll(wave_ballot(ok_cur));
                 n_valid += (uint32_t)__popcll(wave_ballot(ok));
@@ -1353,16 +1529,8 @@ __device__ __forceinline__ void lssd_level_fast(const Blk &b, const KltParams &p
                 const float col_i = (float)(pcol - p.half_cols) + ref_u;
                 float row_j, col_j;
                 se2_apply(s, col_i, row_i, col_j, row_j);
-                float value = 0.0f;
-                if (partly_outside) {
-                    ok = sample(cur, cw, row_j, col_j, value);
-                    if (!ok) {
-                        value = 0.0f;
-                    }
-                } else {
-                    value = bilinear(cur, cw, row_j, col_j);
-                    ok = true;
-                }
+                float value;
+                ok = lssd_sample_cur<false>(cur, cw, row_j, col_j, partly_outside, value);
                 curp[pxi] = value;
                 curv[pxi] = ok ? 1 : 0;
                 // :65-71 — the mean numerator only covers patch rows / cols 1 .. size-2
@@ -1396,12 +1564,8 @@ __device__ __forceinline__ void lssd_level_fast(const Blk &b, const KltParams &p
                 const float col_i = (float)(pcol - p.half_cols) + ref_u;
                 const int ei = imul(prow + 1, p.ex_cols) + pcol + 1;
                 ok = exv[ei] != 0 && curv[pxi] != 0;
-                const float s0 = s.r00 * (-row_i) + s.r01 * col_i;
-                const float s1 = s.r10 * (-row_i) + s.r11 * col_i;
                 const float dx = dxs[pxi], dy = dys[pxi];
-                const float j0 = dx * s0 + dy * s1;
-                const float residual = curp[pxi] - ex[ei];
-                lssd_terms(p, c.terms, pxi, ok, j0, dx, dy, residual);
+                lssd_terms(p, c.terms, pxi, ok, lssd_pixel_j0(s, row_i, col_i, dx, dy), dx, dy, curp[pxi] - ex[ei]);
             }
             n_valid += (uint32_t)__popcll(wave_ballot(ok));
         }
@@ -1425,110 +1589,38 @@ __device__ __forceinline__ void lssd_level_fast(const Blk &b, const KltParams &p
 // TrackOneFeatureFast (lssd_klt_fast.cpp:7-229) for a ONE-WAVE feature without the luminance scaling: the sweep and the chain
 // alternate over 64-pixel chunks through a one-slot ring in LDS (9 rows x 64 products) instead of laying all P products of all
 // nine chains out first — 2.4 KB of LDS instead of 6.2 KB at 13 x 13, which is what caps the resident features per CU for this
-// variant — and the nine sums stay in the chain lanes' registers (broadcast by v_readlane, no round trip through LDS).  Same
-// per-pixel expressions, same row-major order of every sum as lssd_level_fast: bit-identical.
+// variant — and the nine sums stay in the chain lanes' registers (lssd_chunked_step).  Same per-pixel expressions, same row-major
+// order of every sum as lssd_level_fast: bit-identical.
 __device__ __forceinline__ void lssd_level_fast_chunked(const Blk &b, const KltParams &p, const DevImage &ref, const DevImage &cur, float ref_u,
                                                         float ref_v, LssdState &s, uint8_t &status, uint32_t &iters, Carve &c) {
-    // the chunked variant has a0_floats == 0: the extended patch (level entry only) lives in the ring's space (iterations only)
-    c.a0 = c.terms;
-    float *ex = c.a0;
-    uint8_t *exv = c.flagsE;
-    float *ring = c.terms;  // [9][kChunkRow]
-    // what an iteration needs of a patch pixel, laid out by pixel: {dx, dy, reference value, valid} and {row_i, col_i} — one
-    // 16-byte and one 8-byte conflict-free read per pixel instead of the row / column division, the index into the extended
-    // patch and four scattered reads, every iteration
-    float4 *rec = reinterpret_cast<float4 *>(c.a1);
-    float2 *rc = reinterpret_cast<float2 *>(c.a1 + 4 * p.Ppad);
-    Win rw, cw;
-    float level_centre_u, level_centre_v;
-    se2_apply(s, ref_u, ref_v, level_centre_u, level_centre_v);
-    stage_level_windows(b, p, ref, cur, ref_u, ref_v, level_centre_u, level_centre_v, c, rw, cw);
-    bool cw_staged = true;
-    const uint32_t ref_valid_num = extract_extended_patch(b, p, ref, rw, ref_u, ref_v, c);
-    if (ref_valid_num == 0) {
-        status = FTK_OUTSIDE;
+    LssdChunked lv;
+    if (!lssd_chunked_entry<false>(b, p, ref, cur, ref_u, ref_v, s, status, c, lv)) {
         return;
     }
-    for (int pxi = b.tid; pxi < p.P; pxi += b.nt) {
-        int prow, pcol;
-        pixel_rc(p, pxi, prow, pcol);
-        float dx, dy;
-        ex_gradient(p, ex, exv, prow, pcol, dx, dy);
-        const int ei = imul(prow, p.ex_cols) + pcol + (p.ex_cols + 1);
-        rec[pxi] = make_float4(dx, dy, ex[ei], __int_as_float(exv[ei] != 0 ? -1 : 0));
-        rc[pxi] = make_float2((float)(prow - p.half_rows) + ref_v, (float)(pcol - p.half_cols) + ref_u);
-    }
-    blk_sync(b);
-
-    status = FTK_LARGE_RESIDUAL;
-    float last_squared_step = INFINITY;
-    uint32_t large_step_cnt = 0;
-    const int n_chunks = (p.P + kChunkPixels - 1) / kChunkPixels;
     for (uint32_t iter = 0; iter < p.max_iteration; ++iter) {
         ++iters;
         float centre_u, centre_v;
         se2_apply(s, ref_u, ref_v, centre_u, centre_v);
-        ensure_cur_window(b, p, cur, centre_u, centre_v, c, cw, cw_staged);
-        const int min_row = wadd(__builtin_amdgcn_readfirstlane(f2i(centre_v)), -p.patch_rows);  // wave-uniform: scalar from here on
-        const int min_col = wadd(__builtin_amdgcn_readfirstlane(f2i(centre_u)), -p.patch_cols);
-        const int max_row = wadd(min_row, p.patch_rows * 2);
-        const int max_col = wadd(min_col, p.patch_cols * 2);
-        const bool partly_outside = (min_row < 0 || max_row > cur.rows - 2 || min_col < 0 || max_col > cur.cols - 2);
+        ensure_cur_window(b, p, cur, centre_u, centre_v, c, lv.cw, lv.cw_staged);
+        const bool partly_outside = lssd_partly_outside(p, cur, centre_u, centre_v);
         // lssd_klt_fast.cpp:60-63 / :80-83 only ask whether the two counts are zero (their values feed the luminance scaling,
         // which this variant does not serve): one flag per lane and one ballot per iteration instead of two per chunk
         bool seen_cur = false, seen_valid = false;
         float acc = 0.0f;
         float part[9] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};  // throughput mode only (b.tree is a compile-time constant)
-        for (int chunk = 0; chunk < n_chunks; ++chunk) {
+        for (int chunk = 0; chunk < lv.n_chunks; ++chunk) {
             const int pxi = chunk * kChunkPixels + b.lane;
             const bool in = pxi < p.P;
             const int pp = in ? pxi : 0;
-            const float2 rci = rc[pp];
-            const float4 px4 = rec[pp];
+            const float2 rci = lv.rc[pp];
+            const float4 px4 = lv.rec[pp];
             const float row_i = rci.x, col_i = rci.y;
             float row_j, col_j;
             se2_apply(s, col_i, row_i, col_j, row_j);
-            float value = 0.0f;
-            bool ok_cur;
-            if (partly_outside) {
-                ok_cur = sample(cur, cw, row_j, col_j, value);
-                if (!ok_cur) {
-                    value = 0.0f;
-                }
-            } else {
-                // the unchecked bilinear (lssd_klt_fast.cpp:189); when every lane's sample lies inside the image with room for
-                // its +1 neighbours (the normal case: a rotation moves a pixel less than the conservative window above allows
-                // for) the cheaper form gives the same values
-                // 0 <= x <= M as ONE unsigned compare of the bit patterns (M >= 0 here: !partly_outside): negative values, -0 and
-                // NaNs have larger patterns than any finite M and take the general form below, which returns the same values
-                const bool roomy = (unsigned)__float_as_int(row_j) <= (unsigned)__float_as_int((float)(cur.rows - 2)) &&
-                                   (unsigned)__float_as_int(col_j) <= (unsigned)__float_as_int((float)(cur.cols - 2));
-                if (wave_ballot(!roomy) == 0ull) {
-                    value = bilinear_inside(cur, cw, row_j, col_j);
-                } else {
-                    value = bilinear(cur, cw, row_j, col_j);
-                }
-                ok_cur = true;
-            }
-            ok_cur = ok_cur && in;
+            float value;
+            const bool ok_cur = lssd_sample_cur<true>(cur, lv.cw, row_j, col_j, partly_outside, value) && in;
             const bool ok = __float_as_int(px4.w) != 0 && ok_cur;
-            const float s0 = s.r00 * (-row_i) + s.r01 * col_i;
-            const float s1 = s.r10 * (-row_i) + s.r11 * col_i;
-            // An unused pixel contributes exact zeros to every sum (lssd_terms): zeroing the four factors does it with four
-            // selects instead of nine — the products are then +0 or -0, and x + (+-0) == x for every x a sum can hold (the
-            // sums start at +0 and +0 + (-0) == +0).
-            const float dx = ok ? px4.x : 0.0f, dy = ok ? px4.y : 0.0f;
-            const float j0 = ok ? px4.x * s0 + px4.y * s1 : 0.0f;
-            const float residual = ok ? value - px4.z : 0.0f;
-            ring[0 * kChunkRow + b.lane] = j0 * j0;
-            ring[1 * kChunkRow + b.lane] = j0 * dx;
-            ring[2 * kChunkRow + b.lane] = j0 * dy;
-            ring[3 * kChunkRow + b.lane] = dx * dx;
-            ring[4 * kChunkRow + b.lane] = dx * dy;
-            ring[5 * kChunkRow + b.lane] = dy * dy;
-            ring[6 * kChunkRow + b.lane] = -(j0 * residual);
-            ring[7 * kChunkRow + b.lane] = -(dx * residual);
-            ring[8 * kChunkRow + b.lane] = -(dy * residual);
+            lssd_ring_products(lv.ring, b.lane, ok, s, row_i, col_i, px4, value);
             seen_cur = seen_cur || ok_cur;
             seen_valid = seen_valid || ok;
             blk_sync(b);  // one wave: LDS operations run in program order; this keeps the compiler from reordering across
@@ -1536,14 +1628,10 @@ __device__ __forceinline__ void lssd_level_fast_chunked(const Blk &b, const KltP
                 // throughput mode: every lane adds ITS pixel's nine products to nine partial sums (combined by a butterfly below)
 #pragma unroll
                 for (int k = 0; k < 9; ++k) {
-                    part[k] += ring[k * kChunkRow + b.lane];
+                    part[k] += lv.ring[k * kChunkRow + b.lane];
                 }
-            } else if (p.quad_chain) {
-                // every lane: quad q carries sum q (klt_common.h "quad chain"); the quads behind the ninth follow its row and are ignored.
-                // A launch that oversubscribes the chip keeps one lane per sum (KltParams::quad_chain): there the instruction COUNT decides.
-                acc = chain_quads_left(acc, ring + min(b.lane >> 2, 8) * kChunkRow + 4 * (b.lane & 3), p.P - chunk * kChunkPixels);
-            } else if (b.lane < 9) {
-                acc = chain_chunk_left(acc, ring + b.lane * kChunkRow, p.P - chunk * kChunkPixels);
+            } else {
+                acc = lssd_chain_ring<9>(b, p, lv.ring, chunk, acc);
             }
             blk_sync(b);
         }
@@ -1563,96 +1651,33 @@ __device__ __forceinline__ void lssd_level_fast_chunked(const Blk &b, const KltP
         if (wave_ballot(seen_cur) == 0ull || wave_ballot(seen_valid) == 0ull) {
             break;  // lssd_klt_fast.cpp:60-63 / :80-83
         }
-        // the nine sums sit in lanes 0..8: broadcast and solve (lssd_solve on registers)
-        const int acc_bits = __float_as_int(acc);
-        const int sl = __builtin_amdgcn_readfirstlane(sum_lanes(p));
-        const float h00 = __int_as_float(__builtin_amdgcn_readlane(acc_bits, 0)), h01 = __int_as_float(__builtin_amdgcn_readlane(acc_bits, 1 * sl));
-        const float h02 = __int_as_float(__builtin_amdgcn_readlane(acc_bits, 2 * sl)), h11 = __int_as_float(__builtin_amdgcn_readlane(acc_bits, 3 * sl));
-        const float h12 = __int_as_float(__builtin_amdgcn_readlane(acc_bits, 4 * sl)), h22 = __int_as_float(__builtin_amdgcn_readlane(acc_bits, 5 * sl));
-        const float bb[3] = {__int_as_float(__builtin_amdgcn_readlane(acc_bits, 6 * sl)), __int_as_float(__builtin_amdgcn_readlane(acc_bits, 7 * sl)),
-                             __int_as_float(__builtin_amdgcn_readlane(acc_bits, 8 * sl))};
-        float v[3];
-        ldlt3_solve<true>(h00, h01, h02, h11, h12, h22, bb, v, b.lane);
-        if (isnan(v[0]) || isnan(v[1]) || isnan(v[2])) {
-            status = FTK_NUMERIC_ERROR;
-            break;
-        }
-        se2_update<true>(s, v, b.lane);
-        if (fast_step_logic(p, vec3_squared_norm(v), last_squared_step, large_step_cnt, status)) {
+        if (!lssd_chunked_step(b, p, acc, s, lv, status)) {
             break;
         }
     }
 }
 
 // The same level with consider_patch_luminance (lssd_klt_fast.cpp:27-46, 65-78): the reference patch and its gradients are divided by
-// the reference mean once per level, the current patch by its mean in every iteration — a SECOND exact-order sum per iteration (one
-// lane: the interior of the sampled patch, row-major) in front of the nine.  Chunked like the level above: pass 1 samples chunk by
-// chunk, keeps each lane's values in REGISTERS (a lane owns the pixels lane, lane + 64, ...: at most kLumChunks of them) and chains
-// the mean through ring row 0; pass 2 divides, forms the nine products and chains them.  The quirks of the reference are kept:
-// the reference mean's numerator covers the interior of the EXTENDED patch (= the patch) and its denominator the valid count of the
-// whole extended patch; the current mean's numerator covers patch rows / columns 1 .. size - 2 only and its denominator every valid
-// pixel.  Same expressions, same order of every sum as lssd_level_fast: bit-identical.
+// the reference mean once per level (lssd_chunked_entry<true>), the current patch by its mean in every iteration — a SECOND
+// exact-order sum per iteration (the interior of the sampled patch, row-major) in front of the nine.  Chunked like the level above:
+// pass 1 samples chunk by chunk, keeps each lane's values in REGISTERS (a lane owns the pixels lane, lane + 64, ...: at most
+// kLumChunks of them) and chains the mean through ring row 0; pass 2 divides, forms the nine products and chains them.  The quirk
+// of the reference is kept: the current mean's numerator covers patch rows / columns 1 .. size - 2 only and its denominator every
+// valid pixel.  Same expressions, same order of every sum as lssd_level_fast: bit-identical.
 constexpr int kLumChunks = 8;  // 64-pixel chunks a lane can keep values for: patches up to 512 pixels (klt_plan.cpp gates on it)
 
 __device__ __forceinline__ void lssd_level_fast_chunked_lum(const Blk &b, const KltParams &p, const DevImage &ref, const DevImage &cur, float ref_u,
                                                             float ref_v, LssdState &s, uint8_t &status, uint32_t &iters, Carve &c) {
-    c.a0 = c.terms;
-    float *ex = c.a0;
-    uint8_t *exv = c.flagsE;
-    float *ring = c.terms;  // [9][kChunkRow]
-    float4 *rec = reinterpret_cast<float4 *>(c.a1);
-    float2 *rc = reinterpret_cast<float2 *>(c.a1 + 4 * p.Ppad);
-    Win rw, cw;
-    float level_centre_u, level_centre_v;
-    se2_apply(s, ref_u, ref_v, level_centre_u, level_centre_v);
-    stage_level_windows(b, p, ref, cur, ref_u, ref_v, level_centre_u, level_centre_v, c, rw, cw);
-    bool cw_staged = true;
-    const uint32_t ref_valid_num = extract_extended_patch(b, p, ref, rw, ref_u, ref_v, c);
-    if (ref_valid_num == 0) {
-        status = FTK_OUTSIDE;
+    LssdChunked lv;
+    if (!lssd_chunked_entry<true>(b, p, ref, cur, ref_u, ref_v, s, status, c, lv)) {
         return;
     }
-    // :27-35 — the reference mean: the interior of the extended patch in row-major order (== the P patch pixels), summed by lane 0
-    // from a contiguous row laid over the (not yet written) per-pixel records
-    float *row = c.a1;
-    for (int pxi = b.tid; pxi < p.Ppad; pxi += b.nt) {
-        int prow, pcol;
-        pixel_rc(p, pxi < p.P ? pxi : 0, prow, pcol);
-        row[pxi] = pxi < p.P ? ex[imul(prow + 1, p.ex_cols) + pcol + 1] : 0.0f;
-    }
-    blk_sync(b);
-    float ref_sum = 0.0f;
-    if (b.lane == 0) {
-        ref_sum = chain_lane(row, p.Ppad);
-    }
-    const float ref_average = uniform_lane(ref_sum, 0) / (float)ref_valid_num;
-    blk_sync(b);
-    for (int pxi = b.tid; pxi < p.P; pxi += b.nt) {
-        int prow, pcol;
-        pixel_rc(p, pxi, prow, pcol);
-        float dx, dy;
-        ex_gradient(p, ex, exv, prow, pcol, dx, dy);
-        const int ei = imul(prow, p.ex_cols) + pcol + (p.ex_cols + 1);
-        // :37-46 — dx, dy and the patch value are each divided by the mean (the gradients are differences of UNSCALED values)
-        rec[pxi] = make_float4(dx / ref_average, dy / ref_average, ex[ei] / ref_average, __int_as_float(exv[ei] != 0 ? -1 : 0));
-        rc[pxi] = make_float2((float)(prow - p.half_rows) + ref_v, (float)(pcol - p.half_cols) + ref_u);
-    }
-    blk_sync(b);
-
-    status = FTK_LARGE_RESIDUAL;
-    float last_squared_step = INFINITY;
-    uint32_t large_step_cnt = 0;
-    const int n_chunks = (p.P + kChunkPixels - 1) / kChunkPixels;
     for (uint32_t iter = 0; iter < p.max_iteration; ++iter) {
         ++iters;
         float centre_u, centre_v;
         se2_apply(s, ref_u, ref_v, centre_u, centre_v);
-        ensure_cur_window(b, p, cur, centre_u, centre_v, c, cw, cw_staged);
-        const int min_row = wadd(__builtin_amdgcn_readfirstlane(f2i(centre_v)), -p.patch_rows);
-        const int min_col = wadd(__builtin_amdgcn_readfirstlane(f2i(centre_u)), -p.patch_cols);
-        const int max_row = wadd(min_row, p.patch_rows * 2);
-        const int max_col = wadd(min_col, p.patch_cols * 2);
-        const bool partly_outside = (min_row < 0 || max_row > cur.rows - 2 || min_col < 0 || max_col > cur.cols - 2);
+        ensure_cur_window(b, p, cur, centre_u, centre_v, c, lv.cw, lv.cw_staged);
+        const bool partly_outside = lssd_partly_outside(p, cur, centre_u, centre_v);
         // ---- pass 1: ExtractPatchInCurrentImage (:145-195) + the mean's numerator (:65-71) ----
         float val[kLumChunks];
         uint32_t ok_mask = 0;  // bit k: this lane's pixel of chunk k was sampled inside the image
@@ -1661,44 +1686,24 @@ __device__ __forceinline__ void lssd_level_fast_chunked_lum(const Blk &b, const 
 #pragma unroll
         for (int chunk = 0; chunk < kLumChunks; ++chunk) {
             val[chunk] = 0.0f;
-            if (chunk < n_chunks) {
+            if (chunk < lv.n_chunks) {
                 const int pxi = chunk * kChunkPixels + b.lane;
                 const bool in = pxi < p.P;
                 const int pp = in ? pxi : 0;
-                const float2 rci = rc[pp];
+                const float2 rci = lv.rc[pp];
                 float row_j, col_j;
                 se2_apply(s, rci.y, rci.x, col_j, row_j);
-                float value = 0.0f;
-                bool ok_cur;
-                if (partly_outside) {
-                    ok_cur = sample(cur, cw, row_j, col_j, value);
-                    if (!ok_cur) {
-                        value = 0.0f;
-                    }
-                } else {
-                    const bool roomy = (unsigned)__float_as_int(row_j) <= (unsigned)__float_as_int((float)(cur.rows - 2)) &&
-                                       (unsigned)__float_as_int(col_j) <= (unsigned)__float_as_int((float)(cur.cols - 2));
-                    if (wave_ballot(!roomy) == 0ull) {
-                        value = bilinear_inside(cur, cw, row_j, col_j);
-                    } else {
-                        value = bilinear(cur, cw, row_j, col_j);
-                    }
-                    ok_cur = true;
-                }
-                ok_cur = ok_cur && in;
+                float value;
+                const bool ok_cur = lssd_sample_cur<true>(cur, lv.cw, row_j, col_j, partly_outside, value) && in;
                 int prow, pcol;
                 pixel_rc(p, pp, prow, pcol);
                 const bool interior = in && prow >= 1 && prow < p.patch_rows - 1 && pcol >= 1 && pcol < p.patch_cols - 1;
                 val[chunk] = value;
                 ok_mask |= ok_cur ? (1u << chunk) : 0u;
                 cur_valid_num += (uint32_t)__popcll(wave_ballot(ok_cur));
-                ring[b.lane] = interior ? value : 0.0f;
+                lv.ring[b.lane] = interior ? value : 0.0f;
                 blk_sync(b);
-                if (p.quad_chain) {
-                    mean_acc = chain_quads_left(mean_acc, ring + 4 * (b.lane & 3), p.P - chunk * kChunkPixels);  // every quad carries the one sum
-                } else if (b.lane == 0) {
-                    mean_acc = chain_chunk_left(mean_acc, ring, p.P - chunk * kChunkPixels);
-                }
+                mean_acc = lssd_chain_ring<1>(b, p, lv.ring, chunk, mean_acc);  // quad chain: every quad carries the one sum
                 blk_sync(b);
             }
         }
@@ -1711,57 +1716,23 @@ __device__ __forceinline__ void lssd_level_fast_chunked_lum(const Blk &b, const 
         float acc = 0.0f;
 #pragma unroll
         for (int chunk = 0; chunk < kLumChunks; ++chunk) {
-            if (chunk < n_chunks) {
+            if (chunk < lv.n_chunks) {
                 const int pxi = chunk * kChunkPixels + b.lane;
                 const int pp = pxi < p.P ? pxi : 0;
-                const float2 rci = rc[pp];
-                const float4 px4 = rec[pp];
-                const float row_i = rci.x, col_i = rci.y;
+                const float2 rci = lv.rc[pp];
+                const float4 px4 = lv.rec[pp];
                 const bool ok = __float_as_int(px4.w) != 0 && ((ok_mask >> chunk) & 1u) != 0u;
-                const float scaled = val[chunk] / cur_average;
-                const float s0 = s.r00 * (-row_i) + s.r01 * col_i;
-                const float s1 = s.r10 * (-row_i) + s.r11 * col_i;
-                // an unused pixel contributes exact zeros to every sum: its factors are zeroed (lssd_level_fast_chunked)
-                const float dx = ok ? px4.x : 0.0f, dy = ok ? px4.y : 0.0f;
-                const float j0 = ok ? px4.x * s0 + px4.y * s1 : 0.0f;
-                const float residual = ok ? scaled - px4.z : 0.0f;
-                ring[0 * kChunkRow + b.lane] = j0 * j0;
-                ring[1 * kChunkRow + b.lane] = j0 * dx;
-                ring[2 * kChunkRow + b.lane] = j0 * dy;
-                ring[3 * kChunkRow + b.lane] = dx * dx;
-                ring[4 * kChunkRow + b.lane] = dx * dy;
-                ring[5 * kChunkRow + b.lane] = dy * dy;
-                ring[6 * kChunkRow + b.lane] = -(j0 * residual);
-                ring[7 * kChunkRow + b.lane] = -(dx * residual);
-                ring[8 * kChunkRow + b.lane] = -(dy * residual);
+                lssd_ring_products(lv.ring, b.lane, ok, s, rci.x, rci.y, px4, val[chunk] / cur_average);
                 seen_valid = seen_valid || ok;
                 blk_sync(b);
-                if (p.quad_chain) {
-                    acc = chain_quads_left(acc, ring + min(b.lane >> 2, 8) * kChunkRow + 4 * (b.lane & 3), p.P - chunk * kChunkPixels);
-                } else if (b.lane < 9) {
-                    acc = chain_chunk_left(acc, ring + b.lane * kChunkRow, p.P - chunk * kChunkPixels);
-                }
+                acc = lssd_chain_ring<9>(b, p, lv.ring, chunk, acc);
                 blk_sync(b);
             }
         }
         if (wave_ballot(seen_valid) == 0ull) {
             break;  // :80-83
         }
-        const int acc_bits = __float_as_int(acc);
-        const int sl = __builtin_amdgcn_readfirstlane(sum_lanes(p));
-        const float h00 = __int_as_float(__builtin_amdgcn_readlane(acc_bits, 0)), h01 = __int_as_float(__builtin_amdgcn_readlane(acc_bits, 1 * sl));
-        const float h02 = __int_as_float(__builtin_amdgcn_readlane(acc_bits, 2 * sl)), h11 = __int_as_float(__builtin_amdgcn_readlane(acc_bits, 3 * sl));
-        const float h12 = __int_as_float(__builtin_amdgcn_readlane(acc_bits, 4 * sl)), h22 = __int_as_float(__builtin_amdgcn_readlane(acc_bits, 5 * sl));
-        const float bb[3] = {__int_as_float(__builtin_amdgcn_readlane(acc_bits, 6 * sl)), __int_as_float(__builtin_amdgcn_readlane(acc_bits, 7 * sl)),
-                             __int_as_float(__builtin_amdgcn_readlane(acc_bits, 8 * sl))};
-        float v[3];
-        ldlt3_solve<true>(h00, h01, h02, h11, h12, h22, bb, v, b.lane);
-        if (isnan(v[0]) || isnan(v[1]) || isnan(v[2])) {
-            status = FTK_NUMERIC_ERROR;
-            break;
-        }
-        se2_update<true>(s, v, b.lane);
-        if (fast_step_logic(p, vec3_squared_norm(v), last_squared_step, large_step_cnt, status)) {
+        if (!lssd_chunked_step(b, p, acc, s, lv, status)) {
             break;
         }
     }

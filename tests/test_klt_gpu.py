@@ -556,6 +556,27 @@ def test_lssd_fast_chunked_equals_the_unchunked_level(ftk, oracle, switch):
             assert_parity(gpu, cpu, f"chunked={chunked} half={half}x{half_cols}")
             results.append(gpu)
         assert np.array_equal(results[0][1].view(np.uint32), results[1][1].view(np.uint32))
+    # The three level forms share their per-pixel helpers (klt_kernels.hip lssd_sample_cur ... lssd_chunked_entry): every form on
+    # every path of them, at the smallest shapes that reach it.  A 64 x 48 two-level pyramid with border features has patches
+    # partly outside the image and patches inside it; 3 x 3 is one ragged chunk, 9 x 9 two chunks with a ragged last one, and
+    # 23 x 23 with luminance (529 > 512 pixels) runs the plain level at one wave whatever FTK_LSSD_CHUNKED says.  Under the wide
+    # prior (a rotation by 10 degrees with columns of length 3) the first iteration's samples leave the conservative bounding box
+    # of a patch that lies inside the image near its edge — the chunked forms' all-lanes-inside shortcut must not be taken there.
+    ref, cur = synth.make_image_pair(64, 48, (1.3, -0.8))
+    small_ref, small_cur = synth.build_pyramid(ref, 2), synth.build_pyramid(cur, 2)
+    small_uv = scenes.features(50, 64, 48, half=4, border_fraction=0.2)
+    th = np.deg2rad(10.0)
+    wide = np.float32([[np.cos(th), -np.sin(th)], [np.sin(th), np.cos(th)]]) * np.float32(3.0)
+    for half, luminances in ((1, (False, True)), (4, (False, True)), (11, (True,))):
+        for lum in luminances:
+            for small_prior in (None, wide):
+                results = []
+                for chunked in ("1", "0"):
+                    switch("FTK_LSSD_CHUNKED", chunked)
+                    gpu, cpu = run_pyramid(ftk, oracle, "lssd", "fast", small_ref, small_cur, small_uv, half=half, prior=small_prior, luminance=lum)
+                    assert_parity(gpu, cpu, f"small: chunked={chunked} half={half} luminance={lum} prior={'wide' if small_prior is not None else 'none'}")
+                    results.append(gpu)
+                assert np.array_equal(results[0][1].view(np.uint32), results[1][1].view(np.uint32))
 
 
 @pytest.mark.parametrize("model,method", [("affine", "inverse"), ("lssd", "fast"), ("basic", "inverse")])
