@@ -316,21 +316,23 @@ int ftk_klt_track_sharded(ftk_context *ctx, ftk_comm *comm, int model, const ftk
         return ftk_fail(ctx, FTK_E_INVALID_ARGUMENT, "klt_track_sharded: null buffer");
     }
     FTK_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t uv_bytes = ftk_align_up(sizeof(float) * 2 * (size_t)n, 256), st_bytes = ftk_align_up((size_t)n, 256);
-    const size_t it_bytes = ftk_align_up(sizeof(uint32_t) * (size_t)n, 256);
-    int rc = ftk_ensure_device_buffer(ctx, comm->stage, 2 * uv_bytes + st_bytes + it_bytes);
+    ftk_layout L;
+    const auto s_ref = L.take<float>(2 * (size_t)n), s_cur = L.take<float>(2 * (size_t)n);
+    const auto s_st = L.take<uint8_t>((size_t)n);
+    const auto s_it = L.take<uint32_t>((size_t)n);
+    int rc = ftk_ensure_device_buffer(ctx, comm->stage, L);
     if (rc != FTK_OK) {
         return rc;
     }
-    uint8_t *base = comm->stage.as<uint8_t>();
-    float *d_ref = reinterpret_cast<float *>(base), *d_cur = reinterpret_cast<float *>(base + uv_bytes);
-    uint8_t *d_st = base + 2 * uv_bytes;
-    uint32_t *d_it = reinterpret_cast<uint32_t *>(base + 2 * uv_bytes + st_bytes);
-    FTK_HIP(ctx, hipMemcpyAsync(d_ref, ref_uv, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    FTK_HIP(ctx, hipMemcpyAsync(d_cur, cur_uv, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    FTK_HIP(ctx, hipMemcpyAsync(d_st, status, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    void *base = comm->stage.get();
+    float *d_ref = s_ref.in(base), *d_cur = s_cur.in(base);
+    uint8_t *d_st = s_st.in(base);
+    uint32_t *d_it = s_it.in(base);
+    FTK_HIP(ctx, hipMemcpyAsync(d_ref, ref_uv, s_ref.size_bytes(), hipMemcpyHostToDevice, ctx->stream));
+    FTK_HIP(ctx, hipMemcpyAsync(d_cur, cur_uv, s_cur.size_bytes(), hipMemcpyHostToDevice, ctx->stream));
+    FTK_HIP(ctx, hipMemcpyAsync(d_st, status, s_st.size_bytes(), hipMemcpyHostToDevice, ctx->stream));
     if (iters) {
-        FTK_HIP(ctx, hipMemsetAsync(d_it, 0, sizeof(uint32_t) * (size_t)n, ctx->stream));
+        FTK_HIP(ctx, hipMemsetAsync(d_it, 0, s_it.size_bytes(), ctx->stream));
     }
     rc = ftk_klt_track_sharded_device(ctx, comm, model, opt, ref, cur, d_ref, d_cur, d_cur, d_st, d_st, n, prior, consider_luminance, single_level,
                                       iters ? d_it : nullptr);
@@ -338,10 +340,10 @@ int ftk_klt_track_sharded(ftk_context *ctx, ftk_comm *comm, int model, const ftk
         (void)hipStreamSynchronize(ctx->stream);
         return rc;
     }
-    FTK_HIP(ctx, hipMemcpyAsync(cur_uv, d_cur, sizeof(float) * 2 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    FTK_HIP(ctx, hipMemcpyAsync(status, d_st, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    FTK_HIP(ctx, hipMemcpyAsync(cur_uv, d_cur, s_cur.size_bytes(), hipMemcpyDeviceToHost, ctx->stream));
+    FTK_HIP(ctx, hipMemcpyAsync(status, d_st, s_st.size_bytes(), hipMemcpyDeviceToHost, ctx->stream));
     if (iters) {
-        FTK_HIP(ctx, hipMemcpyAsync(iters, d_it, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+        FTK_HIP(ctx, hipMemcpyAsync(iters, d_it, s_it.size_bytes(), hipMemcpyDeviceToHost, ctx->stream));
     }
     FTK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     // A rank whose tracker launch failed contributes a poisoned shard (every byte 0xFF) instead of leaving its peers blocked in

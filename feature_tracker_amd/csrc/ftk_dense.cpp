@@ -29,9 +29,10 @@ int dense_setup(ftk_context *ctx, const char *who, const ftk_dense_flow_options 
         ref_px = std::max(ref_px, (size_t)a.rows * a.cols);
         cur_px = std::max(cur_px, (size_t)b.rows * b.cols);
     }
-    const size_t mom_ref_bytes = ftk_align_up(2 * sizeof(float4) * ref_px, 256), mom_cur_bytes = ftk_align_up(2 * sizeof(float4) * cur_px, 256);
-    const size_t plane_bytes = ftk_align_up(sizeof(float) * ref_px, 256);
-    const size_t need = mom_ref_bytes + mom_cur_bytes + 4 * plane_bytes;
+    ftk_layout ws;
+    const auto s_mom_ref = ws.take<float4>(2 * ref_px), s_mom_cur = ws.take<float4>(2 * cur_px);
+    const auto s_raw_r = ws.take<float>(ref_px), s_raw_c = ws.take<float>(ref_px), s_smooth_r = ws.take<float>(ref_px), s_smooth_c = ws.take<float>(ref_px);
+    const size_t need = ws.bytes();
     if (need > ctx->dense_ws.bytes() || ctx->dense_half != half) {
         if (ftk_stream_capturing(ctx->stream)) {
             return ftk_fail(ctx, FTK_E_UNSUPPORTED, "%s: the workspace (%zu bytes) or the Gaussian table of half patch %d is not resident yet and "
@@ -60,19 +61,17 @@ int dense_setup(ftk_context *ctx, const char *who, const ftk_dense_flow_options 
         FTK_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the pinned block is reused by the caller right away
         ctx->dense_half = half;
     }
-    rc = ftk_ensure_device_buffer(ctx, ctx->dense_ws, need);
+    rc = ftk_ensure_device_buffer(ctx, ctx->dense_ws, ws);
     if (rc != FTK_OK) {
         return rc;
     }
-    uint8_t *base = ctx->dense_ws.as<uint8_t>();
-    L->mom_ref = reinterpret_cast<float4 *>(base);
-    L->mom_cur = reinterpret_cast<float4 *>(base + mom_ref_bytes);
-    float *planes = reinterpret_cast<float *>(base + mom_ref_bytes + mom_cur_bytes);
-    const size_t pf = plane_bytes / sizeof(float);
-    L->raw_r = planes;
-    L->raw_c = planes + pf;
-    L->smooth_r = planes + 2 * pf;
-    L->smooth_c = planes + 3 * pf;
+    void *base = ctx->dense_ws.get();
+    L->mom_ref = s_mom_ref.in(base);
+    L->mom_cur = s_mom_cur.in(base);
+    L->raw_r = s_raw_r.in(base);
+    L->raw_c = s_raw_c.in(base);
+    L->smooth_r = s_smooth_r.in(base);
+    L->smooth_c = s_smooth_c.in(base);
     return FTK_OK;
 }
 
@@ -230,28 +229,28 @@ int ftk_dense_flow(ftk_context *ctx, const ftk_dense_flow_options *opt, const ft
     }
     FTK_HIP(ctx, hipSetDevice(ctx->device));
     const size_t px = (size_t)ref_pyr->levels[0].rows * ref_pyr->levels[0].cols;
-    const size_t plane = ftk_align_up(sizeof(float) * px, 256);
-    int rc = ftk_ensure_scratch(ctx, 2 * plane);
+    ftk_layout L;
+    const auto s_r = L.take<float>(px), s_c = L.take<float>(px);
+    int rc = ftk_ensure_scratch(ctx, L);
     if (rc != FTK_OK) {
         return rc;
     }
-    float *d_r = ctx->scratch.as<float>();
-    float *d_c = reinterpret_cast<float *>(ctx->scratch.as<uint8_t>() + plane);
+    float *d_r = s_r.in(ctx->scratch.get()), *d_c = s_c.in(ctx->scratch.get());
     rc = ftk_dense_flow_device(ctx, opt, ref_pyr, cur_pyr, d_r, d_c);
     if (rc != FTK_OK) {
         (void)hipStreamSynchronize(ctx->stream);
         return rc;
     }
-    rc = ftk_ensure_pinned(ctx, 2 * plane);
+    rc = ftk_ensure_pinned(ctx, L);  // after the device entry: it stages the Gaussian table through this block
     if (rc != FTK_OK) {
         return rc;
     }
-    uint8_t *h = ctx->pinned.as<uint8_t>();
-    FTK_HIP(ctx, hipMemcpyAsync(h, d_r, sizeof(float) * px, hipMemcpyDeviceToHost, ctx->stream));
-    FTK_HIP(ctx, hipMemcpyAsync(h + plane, d_c, sizeof(float) * px, hipMemcpyDeviceToHost, ctx->stream));
+    void *h = ctx->pinned.get();
+    FTK_HIP(ctx, hipMemcpyAsync(s_r.in(h), d_r, s_r.size_bytes(), hipMemcpyDeviceToHost, ctx->stream));
+    FTK_HIP(ctx, hipMemcpyAsync(s_c.in(h), d_c, s_c.size_bytes(), hipMemcpyDeviceToHost, ctx->stream));
     FTK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    memcpy(flow_r, h, sizeof(float) * px);
-    memcpy(flow_c, h + plane, sizeof(float) * px);
+    memcpy(flow_r, s_r.in(h), s_r.size_bytes());
+    memcpy(flow_c, s_c.in(h), s_c.size_bytes());
     return FTK_OK;
 }
 
@@ -275,30 +274,31 @@ int ftk_dense_flow_level(ftk_context *ctx, const ftk_dense_flow_options *opt, co
         return rc;
     }
     const DevImage ref = ref_pyr->levels[level];
-    const size_t px = (size_t)ref.rows * ref.cols, plane = ftk_align_up(sizeof(float) * px, 256);
-    rc = ftk_ensure_pinned(ctx, 2 * plane);
+    ftk_layout H;  // the pinned block: [flow_r | flow_c]
+    const auto s_r = H.take<float>((size_t)ref.rows * ref.cols), s_c = H.take<float>((size_t)ref.rows * ref.cols);
+    rc = ftk_ensure_pinned(ctx, H);
     if (rc != FTK_OK) {
         return rc;
     }
-    uint8_t *h = ctx->pinned.as<uint8_t>();
+    void *h = ctx->pinned.get();
     if (flow_valid & 1) {
-        memcpy(h, flow_r, sizeof(float) * px);
-        FTK_HIP(ctx, hipMemcpyAsync(L.raw_r, h, sizeof(float) * px, hipMemcpyHostToDevice, ctx->stream));
+        memcpy(s_r.in(h), flow_r, s_r.size_bytes());
+        FTK_HIP(ctx, hipMemcpyAsync(L.raw_r, s_r.in(h), s_r.size_bytes(), hipMemcpyHostToDevice, ctx->stream));
     }
     if (flow_valid & 2) {
-        memcpy(h + plane, flow_c, sizeof(float) * px);
-        FTK_HIP(ctx, hipMemcpyAsync(L.raw_c, h + plane, sizeof(float) * px, hipMemcpyHostToDevice, ctx->stream));
+        memcpy(s_c.in(h), flow_c, s_c.size_bytes());
+        FTK_HIP(ctx, hipMemcpyAsync(L.raw_c, s_c.in(h), s_c.size_bytes(), hipMemcpyHostToDevice, ctx->stream));
     }
     rc = dense_level(ctx, opt, L, ref, cur_pyr->levels[level], 1, flow_valid & 3, L.raw_r, L.raw_c, ref.rows, ref.cols, L.smooth_r, L.smooth_c);
     if (rc != FTK_OK) {
         (void)hipStreamSynchronize(ctx->stream);
         return rc;
     }
-    FTK_HIP(ctx, hipMemcpyAsync(h, L.smooth_r, sizeof(float) * px, hipMemcpyDeviceToHost, ctx->stream));
-    FTK_HIP(ctx, hipMemcpyAsync(h + plane, L.smooth_c, sizeof(float) * px, hipMemcpyDeviceToHost, ctx->stream));
+    FTK_HIP(ctx, hipMemcpyAsync(s_r.in(h), L.smooth_r, s_r.size_bytes(), hipMemcpyDeviceToHost, ctx->stream));
+    FTK_HIP(ctx, hipMemcpyAsync(s_c.in(h), L.smooth_c, s_c.size_bytes(), hipMemcpyDeviceToHost, ctx->stream));
     FTK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    memcpy(flow_r, h, sizeof(float) * px);
-    memcpy(flow_c, h + plane, sizeof(float) * px);
+    memcpy(flow_r, s_r.in(h), s_r.size_bytes());
+    memcpy(flow_c, s_c.in(h), s_c.size_bytes());
     return FTK_OK;
 }
 

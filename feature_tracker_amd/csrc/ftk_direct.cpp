@@ -172,21 +172,20 @@ int ftk_direct_track(ftk_context *ctx, const ftk_direct_options *opt, const ftk_
         return ftk_fail(ctx, FTK_E_INVALID_ARGUMENT, "direct_track: null argument");
     }
     FTK_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t pts_bytes = ftk_align_up(sizeof(float) * 3 * (size_t)n, 256);
-    const size_t uv_bytes = ftk_align_up(sizeof(float) * 2 * (size_t)n, 256);
-    const size_t st_bytes = ftk_align_up((size_t)n, 256);
-    const size_t total = pts_bytes + 2 * uv_bytes + st_bytes + 256 + 256;
-    int rc = ftk_ensure_scratch(ctx, total);
+    ftk_layout L;
+    const auto s_pts = L.take<float>(3 * (size_t)n);
+    const auto s_ref = L.take<float>(2 * (size_t)n), s_cur = L.take<float>(2 * (size_t)n);
+    const auto s_st = L.take<uint8_t>((size_t)n);
+    const auto s_pose = L.take<float>(7);
+    const auto s_it = L.take<uint32_t>(1);
+    int rc = ftk_ensure_scratch(ctx, L);
     if (rc != FTK_OK) {
         return rc;
     }
-    uint8_t *base = ctx->scratch.as<uint8_t>();
-    float *d_pts = reinterpret_cast<float *>(base);
-    float *d_ref = reinterpret_cast<float *>(base + pts_bytes);
-    float *d_cur = reinterpret_cast<float *>(base + pts_bytes + uv_bytes);
-    uint8_t *d_st = base + pts_bytes + 2 * uv_bytes;
-    float *d_pose = reinterpret_cast<float *>(base + pts_bytes + 2 * uv_bytes + st_bytes);
-    uint32_t *d_it = reinterpret_cast<uint32_t *>(base + pts_bytes + 2 * uv_bytes + st_bytes + 256);
+    void *base = ctx->scratch.get();
+    float *d_pts = s_pts.in(base), *d_ref = s_ref.in(base), *d_cur = s_cur.in(base), *d_pose = s_pose.in(base);
+    uint8_t *d_st = s_st.in(base);
+    uint32_t *d_it = s_it.in(base);
     float pose[7];
     auto upload_state = [&]() -> int {  // the in/out buffers: positions, statuses and the pose (`pose` is a stack buffer: synchronised)
         memcpy(pose, q_rc_wxyz, sizeof(float) * 4);

@@ -18,23 +18,27 @@ int harris_run(ftk_context *ctx, const ftk_pyramid *image, int32_t level, int32_
     const DevImage img = image->levels[level];
     const size_t px = (size_t)img.rows * img.cols;
     const size_t capacity = px;  // worst case (min_distance 1): every candidate is its own window maximum
-    const size_t g_bytes = ftk_align_up(sizeof(short) * px, 256), f_bytes = ftk_align_up(sizeof(float) * px, 256);
-    const size_t k_bytes = ftk_align_up(sizeof(unsigned long long) * px, 256), l_bytes = ftk_align_up(sizeof(unsigned long long) * capacity, 256);
-    const int rc = ftk_ensure_scratch(ctx, 2 * g_bytes + f_bytes + 3 * k_bytes + l_bytes + 256);
+    ftk_layout L;
+    const auto s_gx = L.take<short>(px), s_gy = L.take<short>(px);
+    const auto s_response = L.take<float>(px);
+    const auto s_key = L.take<unsigned long long>(px), s_tmp = L.take<unsigned long long>(px), s_wmax = L.take<unsigned long long>(px);
+    const auto s_list = L.take<unsigned long long>(capacity);
+    const auto s_count = L.take<unsigned>(1);
+    const int rc = ftk_ensure_scratch(ctx, L);
     if (rc != FTK_OK) {
         return rc;
     }
-    uint8_t *base = ctx->scratch.as<uint8_t>();
+    void *base = ctx->scratch.get();
     ftk::HarrisParams p;
     p.img = img;
-    p.gx = reinterpret_cast<short *>(base);
-    p.gy = reinterpret_cast<short *>(base + g_bytes);
-    p.response = response_out ? reinterpret_cast<float *>(base + 2 * g_bytes) : nullptr;
-    p.key = reinterpret_cast<unsigned long long *>(base + 2 * g_bytes + f_bytes);
-    p.tmp = p.key + k_bytes / sizeof(unsigned long long);
-    p.wmax = p.tmp + k_bytes / sizeof(unsigned long long);
-    p.list = survivors ? p.wmax + k_bytes / sizeof(unsigned long long) : nullptr;
-    p.count = reinterpret_cast<unsigned *>(base + 2 * g_bytes + f_bytes + 3 * k_bytes + l_bytes);
+    p.gx = s_gx.in(base);
+    p.gy = s_gy.in(base);
+    p.response = response_out ? s_response.in(base) : nullptr;
+    p.key = s_key.in(base);
+    p.tmp = s_tmp.in(base);
+    p.wmax = s_wmax.in(base);
+    p.list = survivors ? s_list.in(base) : nullptr;
+    p.count = s_count.in(base);
     p.capacity = (unsigned)capacity;
     p.min_distance = min_distance;
     p.min_response = min_response;
@@ -143,35 +147,31 @@ int ftk_brief_compute(ftk_context *ctx, const ftk_pyramid *image, int32_t level,
     }
     FTK_HIP(ctx, hipSetDevice(ctx->device));
     const size_t n_words = (size_t)(n_bits + 31) / 32;
-    const size_t uv_bytes = ftk_align_up(sizeof(float) * 2 * (size_t)n, 256);
-    const size_t w_bytes = ftk_align_up(sizeof(uint32_t) * n_words * (size_t)n, 256);
-    int rc = ftk_ensure_scratch(ctx, uv_bytes + w_bytes);
-    if (rc != FTK_OK) {
-        return rc;
-    }
     if (n_bits <= 0 || half_patch <= 0 || half_patch > 63) {
         return ftk_fail(ctx, FTK_E_INVALID_ARGUMENT, "brief_compute: bad arguments (bits %d, half %d)", n_bits, half_patch);
     }
-    rc = ftk_ensure_brief_pattern(ctx, n_bits, half_patch);  // before the pinned block is filled: it stages the pattern there
-    if (rc == FTK_OK) {
-        rc = ftk_ensure_pinned(ctx, uv_bytes + w_bytes);
-    }
+    ftk_layout L;
+    const auto s_uv = L.take<float>(2 * (size_t)n);
+    const auto s_words = L.take<uint32_t>(n_words * (size_t)n);
+    int rc = ftk_ensure_brief_pattern(ctx, n_bits, half_patch);  // before the pinned block is filled: it stages the pattern there
     if (rc != FTK_OK) {
         return rc;
     }
-    uint8_t *base = ctx->scratch.as<uint8_t>(), *hbase = ctx->pinned.as<uint8_t>();
-    float *d_uv = reinterpret_cast<float *>(base);
-    uint32_t *d_words = reinterpret_cast<uint32_t *>(base + uv_bytes);
-    memcpy(hbase, uv, sizeof(float) * 2 * (size_t)n);
-    FTK_HIP(ctx, hipMemcpyAsync(d_uv, hbase, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    rc = ftk_brief_compute_device(ctx, image, level, d_uv, n, n_bits, half_patch, d_words);
+    uint8_t *base = nullptr, *hbase = nullptr;
+    rc = ftk_ensure_mirror(ctx, L, &base, &hbase);
+    if (rc != FTK_OK) {
+        return rc;
+    }
+    memcpy(s_uv.in(hbase), uv, s_uv.size_bytes());
+    FTK_HIP(ctx, hipMemcpyAsync(s_uv.in(base), s_uv.in(hbase), s_uv.size_bytes(), hipMemcpyHostToDevice, ctx->stream));
+    rc = ftk_brief_compute_device(ctx, image, level, s_uv.in(base), n, n_bits, half_patch, s_words.in(base));
     if (rc != FTK_OK) {
         (void)hipStreamSynchronize(ctx->stream);
         return rc;
     }
-    FTK_HIP(ctx, hipMemcpyAsync(hbase + uv_bytes, d_words, sizeof(uint32_t) * n_words * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    FTK_HIP(ctx, hipMemcpyAsync(s_words.in(hbase), s_words.in(base), s_words.size_bytes(), hipMemcpyDeviceToHost, ctx->stream));
     FTK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    memcpy(words, hbase + uv_bytes, sizeof(uint32_t) * n_words * (size_t)n);
+    memcpy(words, s_words.in(hbase), s_words.size_bytes());
     return FTK_OK;
 }
 
@@ -236,17 +236,18 @@ int ftk_ldlt6_solve(ftk_context *ctx, const float *a, const float *b, float *x, 
         return FTK_OK;
     }
     FTK_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t a_bytes = ftk_align_up(sizeof(float) * 36 * (size_t)n, 256), b_bytes = ftk_align_up(sizeof(float) * 6 * (size_t)n, 256);
-    const int rc = ftk_ensure_scratch(ctx, a_bytes + 2 * b_bytes);
+    ftk_layout L;
+    const auto s_a = L.take<float>(36 * (size_t)n), s_b = L.take<float>(6 * (size_t)n), s_x = L.take<float>(6 * (size_t)n);
+    const int rc = ftk_ensure_scratch(ctx, L);
     if (rc != FTK_OK) {
         return rc;
     }
-    uint8_t *base = ctx->scratch.as<uint8_t>();
-    float *d_a = reinterpret_cast<float *>(base), *d_b = reinterpret_cast<float *>(base + a_bytes), *d_x = reinterpret_cast<float *>(base + a_bytes + b_bytes);
-    FTK_HIP(ctx, hipMemcpyAsync(d_a, a, sizeof(float) * 36 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    FTK_HIP(ctx, hipMemcpyAsync(d_b, b, sizeof(float) * 6 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    void *base = ctx->scratch.get();
+    float *d_a = s_a.in(base), *d_b = s_b.in(base), *d_x = s_x.in(base);
+    FTK_HIP(ctx, hipMemcpyAsync(d_a, a, s_a.size_bytes(), hipMemcpyHostToDevice, ctx->stream));
+    FTK_HIP(ctx, hipMemcpyAsync(d_b, b, s_b.size_bytes(), hipMemcpyHostToDevice, ctx->stream));
     FTK_HIP(ctx, ftk::ldlt6_launch(d_a, d_b, d_x, n, ctx->stream));
-    FTK_HIP(ctx, hipMemcpyAsync(x, d_x, sizeof(float) * 6 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    FTK_HIP(ctx, hipMemcpyAsync(x, d_x, s_x.size_bytes(), hipMemcpyDeviceToHost, ctx->stream));
     FTK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return FTK_OK;
 }

@@ -11,6 +11,7 @@
 
 #include "ftk_buffer.h"
 #include "ftk_device.h"
+#include "ftk_layout.h"
 #include "klt_sched.h"
 
 using ftk::DevImage;
@@ -145,8 +146,6 @@ int ftk_fail(ftk_context *ctx, int code, const char *fmt, ...);
 
 #define FTK_LOCK(ctx) std::lock_guard<std::recursive_mutex> ftk_lock_guard_((ctx)->lock)
 
-inline size_t ftk_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
 // FTK_TRACE=1 in the environment: every host-buffer entry point of the C ABI prints its wall time to stderr when it returns
 // ("[ftk trace] ftk_klt_track 83.1 us") — for finding out where a caller's timed region goes; costs one getenv per process.
 struct ftk_trace_scope {
@@ -199,6 +198,22 @@ inline int ftk_ensure_pinned(ftk_context *ctx, size_t bytes) {
 inline int ftk_ensure_device_buffer(ftk_context *ctx, ftk_buffer &buf, size_t bytes) {
     FTK_HIP(ctx, buf.reserve(ctx->stream, bytes, bytes / 4, 4096));
     return FTK_OK;
+}
+
+// The same three for a block carved by a staging layout (ftk_layout.h).  A layout whose sizes wrapped is refused here, before anything is sized by it.
+inline int ftk_layout_refused(ftk_context *ctx) { return ftk_fail(ctx, FTK_E_INVALID_ARGUMENT, "the array sizes of this call overflow its staging block"); }
+inline int ftk_ensure_scratch(ftk_context *ctx, const ftk_layout &L) { return L.ok() ? ftk_ensure_scratch(ctx, L.bytes()) : ftk_layout_refused(ctx); }
+inline int ftk_ensure_pinned(ftk_context *ctx, const ftk_layout &L) { return L.ok() ? ftk_ensure_pinned(ctx, L.bytes()) : ftk_layout_refused(ctx); }
+inline int ftk_ensure_device_buffer(ftk_context *ctx, ftk_buffer &buf, const ftk_layout &L) {
+    return L.ok() ? ftk_ensure_device_buffer(ctx, buf, L.bytes()) : ftk_layout_refused(ctx);
+}
+// The device scratch block and its pinned mirror, both laid out by `L` (the tracker, the matchers, BRIEF, dense flow).
+inline int ftk_ensure_mirror(ftk_context *ctx, const ftk_layout &L, uint8_t **dbase, uint8_t **hbase) {
+    int rc = ftk_ensure_scratch(ctx, L);
+    rc = rc == FTK_OK ? ftk_ensure_pinned(ctx, L) : rc;
+    *dbase = ctx->scratch.as<uint8_t>();
+    *hbase = ctx->pinned.as<uint8_t>();
+    return rc;
 }
 
 // Helpers of one family that ftk_warmup uses too.

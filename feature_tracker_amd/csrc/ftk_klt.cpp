@@ -390,23 +390,18 @@ int ftk_klt_track(ftk_context *ctx, int model, const ftk_klt_options *opt, const
     FTK_HIP(ctx, hipSetDevice(ctx->device));
     // One contiguous block [ref_uv | cur_uv | status | iters], mirrored in pinned host memory:
     // a single H2D of (ref_uv, cur_uv, status) and a single D2H of (cur_uv, status, iters) per call.
-    const size_t uv_bytes = ftk_align_up(sizeof(float) * 2 * (size_t)n, 256);
-    const size_t st_bytes = ftk_align_up((size_t)n, 256);
-    const size_t it_bytes = ftk_align_up(sizeof(uint32_t) * (size_t)n, 256);
-    const size_t total = 2 * uv_bytes + st_bytes + it_bytes;
-    int rc = ftk_ensure_scratch(ctx, total);
+    ftk_layout L;
+    const auto s_ref = L.take<float>(2 * (size_t)n), s_cur = L.take<float>(2 * (size_t)n);
+    const auto s_st = L.take<uint8_t>((size_t)n);
+    const auto s_it = L.take<uint32_t>((size_t)n);
+    uint8_t *dbase = nullptr, *hbase = nullptr;
+    int rc = ftk_ensure_mirror(ctx, L, &dbase, &hbase);
     if (rc != FTK_OK) {
         return rc;
     }
-    rc = ftk_ensure_pinned(ctx, total);
-    if (rc != FTK_OK) {
-        return rc;
-    }
-    uint8_t *dbase = ctx->scratch.as<uint8_t>();
-    uint8_t *hbase = ctx->pinned.as<uint8_t>();
-    memcpy(hbase, ref_uv, sizeof(float) * 2 * (size_t)n);
-    memcpy(hbase + uv_bytes, cur_uv, sizeof(float) * 2 * (size_t)n);
-    memcpy(hbase + 2 * uv_bytes, status, (size_t)n);
+    memcpy(s_ref.in(hbase), ref_uv, s_ref.size_bytes());
+    memcpy(s_cur.in(hbase), cur_uv, s_cur.size_bytes());
+    memcpy(s_st.in(hbase), status, s_st.size_bytes());
     // Small calls (the reference's callers track a few hundred features) are dominated by the two staging copies and
     // their queue latency, not by bytes: the kernel then reads (ref_uv, cur_uv, status) from and writes its 9 B per
     // feature straight into the pinned host block over PCIe — no H2D / D2H at all (2 000 features: 89 -> ~60 us per
@@ -414,25 +409,23 @@ int ftk_klt_track(ftk_context *ctx, int model, const ftk_klt_options *opt, const
     void *mapped = nullptr;
     const bool zero_copy = n <= 16384 && hipHostGetDevicePointer(&mapped, ctx->pinned.get(), 0) == hipSuccess && mapped != nullptr;
     uint8_t *base = zero_copy ? static_cast<uint8_t *>(mapped) : dbase;  // what the device entry works on
-    float *b_cur = reinterpret_cast<float *>(base + uv_bytes);
-    uint8_t *b_st = base + 2 * uv_bytes;
     if (!zero_copy) {
-        FTK_HIP(ctx, hipMemcpyAsync(dbase, hbase, 2 * uv_bytes + st_bytes, hipMemcpyHostToDevice, ctx->stream));
+        FTK_HIP(ctx, hipMemcpyAsync(s_ref.in(dbase), s_ref.in(hbase), L.span_bytes(s_ref, s_st), hipMemcpyHostToDevice, ctx->stream));
     }
-    rc = ftk_klt_track_device(ctx, model, opt, ref, cur, reinterpret_cast<float *>(base), b_cur, b_cur, b_st, b_st, n, prior, consider_luminance, single_level,
-                              iters ? reinterpret_cast<uint32_t *>(base + 2 * uv_bytes + st_bytes) : nullptr);
+    rc = ftk_klt_track_device(ctx, model, opt, ref, cur, s_ref.in(base), s_cur.in(base), s_cur.in(base), s_st.in(base), s_st.in(base), n, prior, consider_luminance,
+                              single_level, iters ? s_it.in(base) : nullptr);
     if (rc != FTK_OK) {
         (void)hipStreamSynchronize(ctx->stream);
         return rc;
     }
     if (!zero_copy) {
-        FTK_HIP(ctx, hipMemcpyAsync(hbase + uv_bytes, dbase + uv_bytes, uv_bytes + st_bytes + (iters ? it_bytes : 0), hipMemcpyDeviceToHost, ctx->stream));
+        FTK_HIP(ctx, hipMemcpyAsync(s_cur.in(hbase), s_cur.in(dbase), iters ? L.span_bytes(s_cur, s_it) : L.span_bytes(s_cur, s_st), hipMemcpyDeviceToHost, ctx->stream));
     }
     FTK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    memcpy(cur_uv, hbase + uv_bytes, sizeof(float) * 2 * (size_t)n);
-    memcpy(status, hbase + 2 * uv_bytes, (size_t)n);
+    memcpy(cur_uv, s_cur.in(hbase), s_cur.size_bytes());
+    memcpy(status, s_st.in(hbase), s_st.size_bytes());
     if (iters) {
-        memcpy(iters, hbase + 2 * uv_bytes + st_bytes, sizeof(uint32_t) * (size_t)n);
+        memcpy(iters, s_it.in(hbase), s_it.size_bytes());
     }
     return FTK_OK;
 }
@@ -449,16 +442,18 @@ int ftk_extract_extend_patch(ftk_context *ctx, const ftk_pyramid *ref, int32_t l
     }
     FTK_HIP(ctx, hipSetDevice(ctx->device));
     const size_t n = (size_t)ex_rows * ex_cols;
-    const size_t patch_bytes = ftk_align_up(sizeof(float) * n, 256);
-    const size_t valid_bytes = ftk_align_up(n, 256);
-    int rc = ftk_ensure_scratch(ctx, patch_bytes + valid_bytes + 256);
+    ftk_layout L;
+    const auto s_patch = L.take<float>(n);
+    const auto s_valid = L.take<uint8_t>(n);
+    const auto s_count = L.take<uint32_t>(1);
+    int rc = ftk_ensure_scratch(ctx, L);
     if (rc != FTK_OK) {
         return rc;
     }
-    uint8_t *base = ctx->scratch.as<uint8_t>();
-    float *d_patch = reinterpret_cast<float *>(base);
-    uint8_t *d_valid = base + patch_bytes;
-    uint32_t *d_count = reinterpret_cast<uint32_t *>(base + patch_bytes + valid_bytes);
+    void *base = ctx->scratch.get();
+    float *d_patch = s_patch.in(base);
+    uint8_t *d_valid = s_valid.in(base);
+    uint32_t *d_count = s_count.in(base);
     FTK_HIP(ctx, ftk::extract_patch_launch(ref->levels[level], u, v, ex_rows, ex_cols, d_patch, d_valid, d_count, ctx->stream));
     FTK_HIP(ctx, hipMemcpyAsync(ex_patch, d_patch, sizeof(float) * n, hipMemcpyDeviceToHost, ctx->stream));
     FTK_HIP(ctx, hipMemcpyAsync(valid, d_valid, n, hipMemcpyDeviceToHost, ctx->stream));

@@ -16,15 +16,14 @@ int ensure_match_boxes(ftk_context *ctx, size_t count) {
 
 // Zero-pads the n_words-wide descriptors to `dev_words` words in a context-owned copy (equal pad bits in both sets: same distances).
 int pad_descriptors(ftk_context *ctx, const uint32_t **ref, int32_t n_ref, const uint32_t **cur, int32_t n_cur, int32_t n_words, int32_t dev_words) {
-    const size_t ref_bytes = ftk_align_up(sizeof(uint32_t) * (size_t)n_ref * dev_words, 256);
-    const size_t cur_bytes = ftk_align_up(sizeof(uint32_t) * (size_t)n_cur * dev_words, 256);
-    const int rc = ftk_ensure_device_buffer(ctx, ctx->match_pad, ref_bytes + cur_bytes);
+    ftk_layout L;
+    const auto s_ref = L.take<uint32_t>((size_t)n_ref * dev_words), s_cur = L.take<uint32_t>((size_t)n_cur * dev_words);
+    const int rc = ftk_ensure_device_buffer(ctx, ctx->match_pad, L);
     if (rc != FTK_OK) {
         return rc;
     }
-    uint32_t *pad_ref = ctx->match_pad.as<uint32_t>();
-    uint32_t *pad_cur = reinterpret_cast<uint32_t *>(ctx->match_pad.as<uint8_t>() + ref_bytes);
-    FTK_HIP(ctx, hipMemsetAsync(pad_ref, 0, ref_bytes + cur_bytes, ctx->stream));
+    uint32_t *pad_ref = s_ref.in(ctx->match_pad.get()), *pad_cur = s_cur.in(ctx->match_pad.get());
+    FTK_HIP(ctx, hipMemsetAsync(pad_ref, 0, L.bytes(), ctx->stream));
     FTK_HIP(ctx, hipMemcpy2DAsync(pad_ref, sizeof(uint32_t) * dev_words, *ref, sizeof(uint32_t) * n_words, sizeof(uint32_t) * n_words, (size_t)n_ref,
                                   hipMemcpyDeviceToDevice, ctx->stream));
     FTK_HIP(ctx, hipMemcpy2DAsync(pad_cur, sizeof(uint32_t) * dev_words, *cur, sizeof(uint32_t) * n_words, sizeof(uint32_t) * n_words, (size_t)n_cur,
@@ -42,45 +41,41 @@ template <class Run>
 int run_staged_match(ftk_context *ctx, const void *ref, int32_t n_ref, const void *cur, int32_t n_cur, size_t row_bytes, size_t dev_row_bytes,
                      const float *pred_uv, const float *cur_uv, int32_t *index_pairs, Run run) {
     FTK_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t ref_bytes = ftk_align_up(dev_row_bytes * (size_t)n_ref, 256);
-    const size_t cur_bytes = ftk_align_up(dev_row_bytes * (size_t)n_cur, 256);
-    const size_t pred_bytes = pred_uv ? ftk_align_up(sizeof(float) * 2 * (size_t)n_ref, 256) : 0;
-    const size_t cuv_bytes = pred_uv ? ftk_align_up(sizeof(float) * 2 * (size_t)n_cur, 256) : 0;
-    const size_t idx_at = ref_bytes + cur_bytes + pred_bytes + cuv_bytes, in_bytes = idx_at + ftk_align_up(sizeof(int32_t) * (size_t)n_ref, 256);
-    int rc = ftk_ensure_scratch(ctx, in_bytes);
-    rc = rc == FTK_OK ? ftk_ensure_pinned(ctx, in_bytes) : rc;
+    ftk_layout L;
+    const auto s_ref = L.take<uint8_t>(dev_row_bytes * (size_t)n_ref), s_cur = L.take<uint8_t>(dev_row_bytes * (size_t)n_cur);
+    const auto s_pred = L.take<float>(pred_uv ? 2 * (size_t)n_ref : 0), s_cuv = L.take<float>(pred_uv ? 2 * (size_t)n_cur : 0);  // (nothing without pred_uv)
+    const auto s_idx = L.take<int32_t>((size_t)n_ref);
+    uint8_t *base = nullptr, *hbase = nullptr;
+    int rc = ftk_ensure_mirror(ctx, L, &base, &hbase);
     if (rc != FTK_OK) {
         return rc;
     }
-    uint8_t *base = ctx->scratch.as<uint8_t>(), *hbase = ctx->pinned.as<uint8_t>();
     if (dev_row_bytes == row_bytes) {
-        memcpy(hbase, ref, row_bytes * (size_t)n_ref);
-        memcpy(hbase + ref_bytes, cur, row_bytes * (size_t)n_cur);
+        memcpy(s_ref.in(hbase), ref, s_ref.size_bytes());
+        memcpy(s_cur.in(hbase), cur, s_cur.size_bytes());
     } else {
-        memset(hbase, 0, ref_bytes + cur_bytes);
+        memset(s_ref.in(hbase), 0, L.span_bytes(s_ref, s_cur));
         for (int32_t i = 0; i < n_ref; ++i) {
-            memcpy(hbase + dev_row_bytes * (size_t)i, static_cast<const uint8_t *>(ref) + row_bytes * (size_t)i, row_bytes);
+            memcpy(s_ref.in(hbase) + dev_row_bytes * (size_t)i, static_cast<const uint8_t *>(ref) + row_bytes * (size_t)i, row_bytes);
         }
         for (int32_t i = 0; i < n_cur; ++i) {
-            memcpy(hbase + ref_bytes + dev_row_bytes * (size_t)i, static_cast<const uint8_t *>(cur) + row_bytes * (size_t)i, row_bytes);
+            memcpy(s_cur.in(hbase) + dev_row_bytes * (size_t)i, static_cast<const uint8_t *>(cur) + row_bytes * (size_t)i, row_bytes);
         }
     }
     if (pred_uv) {
-        memcpy(hbase + ref_bytes + cur_bytes, pred_uv, sizeof(float) * 2 * (size_t)n_ref);
-        memcpy(hbase + ref_bytes + cur_bytes + pred_bytes, cur_uv, sizeof(float) * 2 * (size_t)n_cur);
+        memcpy(s_pred.in(hbase), pred_uv, s_pred.size_bytes());
+        memcpy(s_cuv.in(hbase), cur_uv, s_cuv.size_bytes());
     }
-    memcpy(hbase + idx_at, index_pairs, sizeof(int32_t) * (size_t)n_ref);
-    FTK_HIP(ctx, hipMemcpyAsync(base, hbase, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-    int32_t *d_idx = reinterpret_cast<int32_t *>(base + idx_at);
-    rc = run(base, base + ref_bytes, pred_uv ? reinterpret_cast<float *>(base + ref_bytes + cur_bytes) : nullptr,
-             pred_uv ? reinterpret_cast<float *>(base + ref_bytes + cur_bytes + pred_bytes) : nullptr, d_idx);
+    memcpy(s_idx.in(hbase), index_pairs, s_idx.size_bytes());
+    FTK_HIP(ctx, hipMemcpyAsync(base, hbase, L.bytes(), hipMemcpyHostToDevice, ctx->stream));
+    rc = run(s_ref.in(base), s_cur.in(base), pred_uv ? s_pred.in(base) : nullptr, pred_uv ? s_cuv.in(base) : nullptr, s_idx.in(base));
     if (rc != FTK_OK) {
         (void)hipStreamSynchronize(ctx->stream);
         return rc;
     }
-    FTK_HIP(ctx, hipMemcpyAsync(hbase + idx_at, d_idx, sizeof(int32_t) * (size_t)n_ref, hipMemcpyDeviceToHost, ctx->stream));
+    FTK_HIP(ctx, hipMemcpyAsync(s_idx.in(hbase), s_idx.in(base), s_idx.size_bytes(), hipMemcpyDeviceToHost, ctx->stream));
     FTK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    memcpy(index_pairs, hbase + idx_at, sizeof(int32_t) * (size_t)n_ref);
+    memcpy(index_pairs, s_idx.in(hbase), s_idx.size_bytes());
     return FTK_OK;
 }
 

@@ -27,24 +27,27 @@ int ensure_nn_keys(ftk_context *ctx, const char *who, hipStream_t stream, size_t
 template <class Launch>
 int run_nn_host(ftk_context *ctx, const void *in, size_t in_bytes, int64_t n_out, int32_t *match_index, uint8_t *status, Launch launch) {
     FTK_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t in_pad = ftk_align_up(in_bytes, 256), idx_pad = ftk_align_up(sizeof(int32_t) * (size_t)n_out, 256);
-    const int rc = ftk_ensure_scratch(ctx, in_pad + idx_pad + (size_t)n_out);
+    ftk_layout L;
+    const auto s_in = L.take<uint8_t>(in_bytes);
+    const auto s_idx = L.take<int32_t>((size_t)n_out);
+    const auto s_st = L.take<uint8_t>((size_t)n_out);
+    const int rc = ftk_ensure_scratch(ctx, L);
     if (rc != FTK_OK) {
         return rc;
     }
-    uint8_t *base = ctx->scratch.as<uint8_t>();
+    uint8_t *base = s_in.in(ctx->scratch.get());
     if (in_bytes > 0) {
         FTK_HIP(ctx, hipMemcpyAsync(base, in, in_bytes, hipMemcpyHostToDevice, ctx->stream));
     }
-    int32_t *d_idx = reinterpret_cast<int32_t *>(base + in_pad);
-    uint8_t *d_st = base + in_pad + idx_pad;
+    int32_t *d_idx = s_idx.in(ctx->scratch.get());
+    uint8_t *d_st = s_st.in(ctx->scratch.get());
     const int lrc = launch(base, d_idx, d_st);
     if (lrc != FTK_OK) {
         (void)hipStreamSynchronize(ctx->stream);
         return lrc;
     }
-    FTK_HIP(ctx, hipMemcpyAsync(match_index, d_idx, sizeof(int32_t) * (size_t)n_out, hipMemcpyDeviceToHost, ctx->stream));
-    FTK_HIP(ctx, hipMemcpyAsync(status, d_st, (size_t)n_out, hipMemcpyDeviceToHost, ctx->stream));
+    FTK_HIP(ctx, hipMemcpyAsync(match_index, d_idx, s_idx.size_bytes(), hipMemcpyDeviceToHost, ctx->stream));
+    FTK_HIP(ctx, hipMemcpyAsync(status, d_st, s_st.size_bytes(), hipMemcpyDeviceToHost, ctx->stream));
     FTK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return FTK_OK;
 }

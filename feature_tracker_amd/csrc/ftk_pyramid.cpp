@@ -79,12 +79,15 @@ int ftk_pyramid_upload(ftk_context *ctx, const ftk_image *host_levels, int32_t n
         return rc;
     }
     FTK_HIP(ctx, hipSetDevice(ctx->device));
-    size_t offsets[FTK_MAX_LEVELS];
-    size_t total = 0;
+    ftk_layout L;  // of the pyramid's own block and of its image in the pinned block
+    ftk_slot<uint8_t> slots[FTK_MAX_LEVELS];
     for (int i = 0; i < n_levels; ++i) {
-        offsets[i] = total;
-        total += ftk_align_up((size_t)host_levels[i].rows * host_levels[i].cols, 256);
+        slots[i] = L.take<uint8_t>((size_t)host_levels[i].rows * host_levels[i].cols);
     }
+    if (!L.ok()) {
+        return ftk_layout_refused(ctx);
+    }
+    const size_t total = L.bytes();
     ftk_pyramid *pyr = nullptr;
     rc = make_pyramid(ctx, &pyr);
     if (rc != FTK_OK) {
@@ -103,9 +106,8 @@ int ftk_pyramid_upload(ftk_context *ctx, const ftk_image *host_levels, int32_t n
     }
     uint8_t *staging = ctx->pinned.as<uint8_t>(), *owned = pyr->owned.as<uint8_t>();
     for (int i = 0; i < n_levels; ++i) {
-        const size_t bytes = (size_t)host_levels[i].rows * host_levels[i].cols;
-        memcpy(staging + offsets[i], host_levels[i].data, bytes);
-        pyr->levels[i].data = owned + offsets[i];
+        memcpy(slots[i].in(staging), host_levels[i].data, slots[i].size_bytes());
+        pyr->levels[i].data = slots[i].in(owned);
         pyr->levels[i].rows = host_levels[i].rows;
         pyr->levels[i].cols = host_levels[i].cols;
     }
@@ -160,8 +162,8 @@ int ftk_pyramid_build(ftk_context *ctx, const uint8_t *image, int32_t rows, int3
     }
     FTK_HIP(ctx, hipSetDevice(ctx->device));
     int32_t lrows[FTK_MAX_LEVELS], lcols[FTK_MAX_LEVELS];
-    size_t offsets[FTK_MAX_LEVELS];
-    size_t total = 0;
+    ftk_layout L;
+    ftk_slot<uint8_t> slots[FTK_MAX_LEVELS];
     lrows[0] = rows;
     lcols[0] = cols;
     for (int i = 0; i < n_levels; ++i) {
@@ -172,11 +174,12 @@ int ftk_pyramid_build(ftk_context *ctx, const uint8_t *image, int32_t rows, int3
                 return ftk_fail(ctx, FTK_E_INVALID_ARGUMENT, "pyramid_build: level %d would be empty", i);
             }
         }
-        offsets[i] = total;
-        if (i > 0 || !image_on_device) {
-            total += ftk_align_up((size_t)lrows[i] * lcols[i], 256);
-        }
+        slots[i] = L.take<uint8_t>(i > 0 || !image_on_device ? (size_t)lrows[i] * lcols[i] : 0);  // (level 0 of a device image stays the caller's)
     }
+    if (!L.ok()) {
+        return ftk_layout_refused(ctx);
+    }
+    const size_t total = L.bytes();
     ftk_pyramid *pyr = nullptr;
     int rc = make_pyramid(ctx, &pyr);
     if (rc != FTK_OK) {
@@ -215,7 +218,7 @@ int ftk_pyramid_build(ftk_context *ctx, const uint8_t *image, int32_t rows, int3
     pyr->levels[0].cols = cols;
     uint8_t *level_ptr[FTK_MAX_LEVELS] = {nullptr};
     for (int i = 1; i < n_levels; ++i) {
-        level_ptr[i] = owned + offsets[i];
+        level_ptr[i] = slots[i].in(owned);
         pyr->levels[i].data = level_ptr[i];
         pyr->levels[i].rows = lrows[i];
         pyr->levels[i].cols = lcols[i];
