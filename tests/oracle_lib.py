@@ -214,9 +214,9 @@ def force_match(ref_bits, cur_bits, max_distance, index_pairs=None):
     n_ref = ref_bits.shape[0]
     n_cur = cur_bits.shape[0]
     n_bits = ref_bits.shape[1] if ref_bits.ndim == 2 else 0
+    if n_cur == 0:  # descriptor_matcher.h:58 comes before the size check of :60: index_pairs as it was
+        return False, (np.zeros(0, np.int32) if index_pairs is None else np.array(index_pairs, np.int32))
     idx = _prep_index(index_pairs, n_ref)
-    if n_cur == 0:
-        return False, idx if index_pairs is not None else np.zeros(0, np.int32)
     ok = lib().orc_force_match_bits(ref_bits.ctypes.data_as(C.c_void_p), n_ref, cur_bits.ctypes.data_as(C.c_void_p), n_cur, n_bits,
                                     C.c_float(max_distance), idx.ctypes.data_as(C.c_void_p))
     return bool(ok), idx

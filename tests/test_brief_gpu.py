@@ -12,12 +12,21 @@ pytestmark = pytest.mark.gpu
 DATA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data", "optical_flow")
 
 
-@pytest.mark.parametrize("n_bits,half", [(256, 8), (128, 4), (200, 12), (512, 15), (32, 1)])
+def image_size(half):
+    """320 x 240 up to half 15; above, 6 half more each way, so that as large a share of the features stays interior (>= 2 half + 40)."""
+    return (320, 240) if half <= 15 else (320 + 6 * half, 240 + 6 * half)
+
+
+@pytest.mark.parametrize("n_bits,half", [(256, 8), (128, 4), (200, 12), (512, 15), (32, 1), (256, 16), (256, 31), (100, 62), (256, 63)])
 def test_brief_bits_match_oracle(ftk, oracle, n_bits, half):
-    img, _ = synth.make_image_pair(320, 240)
+    """Every accepted half patch, up to 63: the kernel asks for 2 ((2h+3)^2 + (2h+1)^2) bytes of dynamic LDS, 65 540 at h = 63, which a
+    gfx950 launch takes as it is (the device reports 163 840 bytes of LDS per workgroup)."""
+    width, height = image_size(half)
+    assert min(width, height) >= 2 * half + 40
+    img, _ = synth.make_image_pair(width, height)
     rs = np.random.RandomState(n_bits)
-    uv = np.stack([rs.uniform(-5, 325, 400), rs.uniform(-5, 245, 400)], axis=1).astype(np.float32)
-    uv[:6] = [[half + 1, half + 1], [half + 0.49, half + 1], [319 - half - 1, 239 - half - 1], [319 - half - 0.5, 100], [np.nan, 5], [1e20, 5]]
+    uv = np.stack([rs.uniform(-5, width + 5, 400), rs.uniform(-5, height + 5, 400)], axis=1).astype(np.float32)
+    uv[:6] = [[half + 1, half + 1], [half + 0.49, half + 1], [width - 1 - half - 1, height - 1 - half - 1], [width - 1 - half - 0.5, 100], [np.nan, 5], [1e20, 5]]
     d = ftk.BriefDescriptor()
     d.options().kLength, d.options().kHalfPatchSize = n_bits, half
     ok, bits = d.Compute(img, uv)
@@ -25,9 +34,37 @@ def test_brief_bits_match_oracle(ftk, oracle, n_bits, half):
     assert ok and ok_c
     assert np.array_equal(bits, bits_c)
     assert bits_c.any(axis=1).sum() > 200  # interior features carry information
+    assert bits_c[0].any() and bits_c[2].any() and not bits_c[[1, 3, 4, 5]].any()  # the edge placements: the last interior pixel, one beyond it
     words = d.compute_packed(img, uv)
     assert np.array_equal(words, ftk.pack_brief(bits_c))
     assert np.array_equal(ftk.unpack_brief(words, n_bits), bits_c)
+
+
+def test_half_patch_beyond_63_is_refused_as_an_argument(ftk):
+    """half = 64 is refused by both entries with FTK_E_INVALID_ARGUMENT, before any launch (a launch error would be FTK_E_HIP)."""
+    import torch
+    from feature_tracker_amd import _native as N
+    from feature_tracker_amd import device as D
+    img, _ = synth.make_image_pair(640, 640)
+    uv = np.float32([[320, 320], [100, 200]])
+    d = ftk.BriefDescriptor()
+    d.options().kLength, d.options().kHalfPatchSize = 256, 64
+    with pytest.raises(N.FtkError) as e:
+        d.compute_packed(img, uv)
+    assert e.value.code == -1 and N.ERROR_NAMES[-1] == "FTK_E_INVALID_ARGUMENT"
+    dev = torch.device("cuda", 0)
+    stream = torch.cuda.Stream(device=dev)
+    with torch.cuda.stream(stream):
+        ctx = D.context_on_stream(stream, 0)
+        pyr = D.upload_pyramid([img], ctx, dev)
+        d_uv = torch.from_numpy(uv).to(dev)
+        d_words = torch.full((2, 8), 77, dtype=torch.int32, device=dev)
+        with pytest.raises(N.FtkError) as e:
+            D.brief_compute_device(ctx, pyr, d_uv, 256, 64, d_words)
+        assert e.value.code == -1
+        D.brief_compute_device(ctx, pyr, d_uv, 256, 63, d_words)  # the last accepted one, on the same context
+        stream.synchronize()
+        assert (d_words.cpu().numpy() != 77).any()
 
 
 def test_descriptor_to_matcher_pipeline_on_device(ftk, oracle):
