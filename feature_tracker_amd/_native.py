@@ -19,6 +19,12 @@ FTK_MAX_LEVELS = 12
 FTK_CORR_MAX_LEVELS = 16
 FTK_CORR_MAX_RADIUS = 64
 FTK_FLOW_UPSAMPLE_TILE = 32
+# SepConvGru (include/ftk.h): the supported sizes and the packed weight layout
+FTK_SEP_CONV_GRU_MAX_PARTS = 3
+FTK_SEP_CONV_GRU_MAX_H_CHANNELS = 1024
+FTK_SEP_CONV_GRU_MAX_IN_CHANNELS = 4096
+FTK_SEP_CONV_GRU_CHUNK = 16
+FTK_SEP_CONV_GRU_KERNEL_SIZES = (3, 5)
 ERROR_NAMES = {0: "FTK_OK", -1: "FTK_E_INVALID_ARGUMENT", -2: "FTK_E_NO_DEVICE", -3: "FTK_E_HIP", -4: "FTK_E_UNSUPPORTED",
                -5: "FTK_E_OUT_OF_MEMORY"}
 
@@ -36,6 +42,7 @@ EXPORTS = [
     "ftk_klt_track_sharded_device", "ftk_klt_track_sharded", "ftk_klt_track_shard_device", "ftk_klt_unpack_shards_device", "ftk_hamming_match_sharded_device",
     "ftk_default_dense_flow_options", "ftk_dense_flow_gaussian", "ftk_dense_flow", "ftk_dense_flow_device", "ftk_dense_flow_level",
     "ftk_corr_pyramid_layout", "ftk_corr_pyramid_build_device", "ftk_corr_pyramid_lookup_device", "ftk_flow_upsample_device",
+    "ftk_sep_conv_gru_packed_elements", "ftk_sep_conv_gru_gates_device", "ftk_sep_conv_gru_blend_device",
     "ftk_nn_match_scores_device", "ftk_nn_match_scores", "ftk_nn_match_list_device", "ftk_nn_match_list", "ftk_nn_fill_pixels_device",
 ]
 UNIQUE_ID_BYTES = 128
@@ -82,6 +89,11 @@ class DirectProblem(C.Structure):
         ("d_cur_uv", C.c_void_p), ("n", C.c_int32), ("d_pose", C.c_void_p), ("d_status", C.c_void_p), ("status_valid", C.c_int32),
         ("d_iterations", C.c_void_p),
     ]
+
+
+class GruPart(C.Structure):
+    """ftk_gru_part: one tensor of SepConvGru's ``x`` (a device pointer and its channel count)."""
+    _fields_ = [("data", C.c_void_p), ("channels", C.c_int32)]
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
@@ -190,6 +202,10 @@ def lib() -> C.CDLL:
     l.ftk_corr_pyramid_lookup_device.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, i32]
     l.ftk_flow_upsample_device.argtypes = [vp, vp, vp, vp, i32, i32, i32, C.c_float, vp]
     i64, f32 = C.c_int64, C.c_float
+    parts = C.POINTER(GruPart)
+    l.ftk_sep_conv_gru_packed_elements.argtypes = [i32, i32, i32, i64p]
+    l.ftk_sep_conv_gru_gates_device.argtypes = [vp, vp, parts, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]
+    l.ftk_sep_conv_gru_blend_device.argtypes = [vp, vp, parts, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
     l.ftk_nn_match_scores_device.argtypes = [vp, vp, vp, i32, i32, i32, i64, i64, f32, vp, vp]
     l.ftk_nn_match_scores.argtypes = [vp, vp, i32, i32, i32, i64, i64, f32, vp, vp, C.POINTER(C.c_int)]
     l.ftk_nn_match_list_device.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
@@ -221,3 +237,14 @@ def corr_pyramid_layout(B: int, H: int, W: int, levels: int):
     lw = (C.c_int32 * max(n, 1))()
     check(lib().ftk_corr_pyramid_layout(int(B), int(H), int(W), int(levels), C.byref(elements), off, lh, lw), None)
     return elements.value, [off[i] for i in range(n)], [(lh[i], lw[i]) for i in range(n)]
+
+
+def sep_conv_gru_k_steps(in_channels: int, kernel_size: int) -> int:
+    """MFMA k-steps of a packed SepConvGru weight matrix (include/ftk.h): whole chunks of FTK_SEP_CONV_GRU_CHUNK input channels, two k per step."""
+    chunks = -(-int(in_channels) // FTK_SEP_CONV_GRU_CHUNK)
+    return chunks * (FTK_SEP_CONV_GRU_CHUNK * int(kernel_size) // 2)
+
+
+def sep_conv_gru_packed_elements(out_channels: int, in_channels: int, kernel_size: int) -> int:
+    """Floats of the packed matrix, the value ftk_sep_conv_gru_packed_elements returns (pure Python: argument checks need no library)."""
+    return -(-int(out_channels) // 32) * sep_conv_gru_k_steps(in_channels, kernel_size) * 64

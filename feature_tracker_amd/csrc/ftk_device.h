@@ -363,6 +363,26 @@ struct FlowUpsampleParams {
 // hipErrorInvalidValue when the grid would not fit in 2^31 - 1 workgroups
 hipError_t flow_upsample_launch(const FlowUpsampleParams &p, hipStream_t stream);
 
+// RAFT's separable ConvGRU (raft_gru_kernels.hip, SepConvGru.forward, gru.py:59-76): per pass a gates launch and a
+// candidate + blend launch, each an implicit GEMM on the f32-input matrix cores.
+struct GruSegment {
+    const float *data;  // [B][channels][H][W]
+    int32_t channels;
+};
+struct SepConvGruParams {
+    GruSegment seg[4];     // the input's channel segments in order: the x parts, then h (gates) or r * h (candidate)
+    int32_t n_seg;
+    const float *weights;  // packed [m_tiles][k_steps][64] (sep_conv_gru_plan.h)
+    const float *bias;     // [out_channels]
+    const float *h;        // [B][h_channels][H][W]
+    float *z;              // gates: written; candidate: read
+    float *rh;             // gates: written
+    float *out;            // candidate: the new hidden state
+    int32_t h_channels, in_channels, B, H, W;
+};
+struct SepConvGruPlan;
+hipError_t sep_conv_gru_launch(const SepConvGruPlan &plan, const SepConvGruParams &p, int kernel_size, int vertical, int gates, hipStream_t stream);
+
 // NNFeatureMatcher's post-processing (nn_match_kernels.hip): mutual-best matching of a score matrix, or a match list.
 // Keys (unsigned 64-bit, merged with atomicMax, 0 = empty): score mode (order-preserving map of the score << 32 | ~index), so the
 // greatest score wins and, among equal scores, the lowest index; list mode ((k + 1) << 32 | idx_cur), so the last row wins.

@@ -18,6 +18,7 @@
 #include <stdint.h>
 
 #include "ftk_device.h"
+#include "raft_math.h"
 
 namespace ftk {
 namespace {
@@ -29,33 +30,6 @@ constexpr int kPitch = 9;             // LDS floats per coarse pixel of one fine
 constexpr int kThreads = 256;
 static_assert(kTile == FTK_FLOW_UPSAMPLE_TILE, "include/ftk.h states the tile width");
 static_assert(kThreads == 8 * kTile, "one thread per (pixel of the tile, fine column)");
-
-constexpr float kCutoff = -87.0f;
-constexpr float kLog2e = 0x1.715476p+0f;
-constexpr float kLn2Hi = 0x1.62e4p-1f;
-constexpr float kLn2Lo = 0x1.7f7d1cp-20f;
-
-// exp_c of DESIGN.md 5.12, t <= 0 or NaN.
-__device__ __forceinline__ float exp_c(float t) {
-    if (t != t) {
-        return t;
-    }
-    if (t < kCutoff) {
-        return 0.0f;
-    }
-    const float n = rintf(t * kLog2e);
-    float r = fmaf(n, -kLn2Hi, t);
-    r = fmaf(n, -kLn2Lo, r);
-    float p = 0x1.a01a02p-13f;
-    p = fmaf(p, r, 0x1.6c16c2p-10f);
-    p = fmaf(p, r, 0x1.111112p-7f);
-    p = fmaf(p, r, 0x1.555556p-5f);
-    p = fmaf(p, r, 0x1.555556p-3f);
-    p = fmaf(p, r, 0x1p-1f);
-    p = fmaf(p, r, 1.0f);
-    p = fmaf(p, r, 1.0f);
-    return p * __uint_as_float((uint32_t)((int)n + 127) << 23);
-}
 
 __global__ __launch_bounds__(kThreads) void flow_upsample_kernel(FlowUpsampleParams prm, int tiles_x) {
     __shared__ float s_flow[2][3][kTile + 2];

@@ -1,17 +1,20 @@
-"""RAFT's two operators that are not stock torch layers: the correlation pyramid (src/nn_optical_flow_tracker/raft/
-correlation_volumes.py:19-83) as a drop-in class, and the convex flow upsampling (Raft.UpsampleFlow, model.py:48-64) as a function.
+"""RAFT's two operators that are not stock torch layers, the correlation pyramid (src/nn_optical_flow_tracker/raft/
+correlation_volumes.py:19-83) as a drop-in class and the convex flow upsampling (Raft.UpsampleFlow, model.py:48-64) as a function, and
+its recurrent unit, the separable ConvGRU (gru.py:46-76), as a class that runs one step in four fused launches.
 
 ``CorrelationPyramid(fmap0, fmap1, num_levels, radius)`` keeps the reference's attributes (``num_levels``, ``radius``,
 ``correlation_pyramid``) and ``__call__``; ``lookup`` returns the fused ``[B, L*K, H, W]`` tensor that model.py:87-88 builds with
 ``cat`` / ``permute`` / ``contiguous``.  torch owns every buffer (one volume tensor, the levels are views into it) and the kernels
 launch on ``torch.cuda.current_stream()`` at each call, so construction and lookups can be captured in ``torch.cuda.graph``.
 ``upsample_flow(flow, mask, mask_scale)`` is ``Raft.UpsampleFlow(flow, mask_scale * mask)`` in one launch.
+``SepConvGru(x_channels, h_channels, kernel_size)`` holds the reference module's twelve tensors; ``gru(x, h)`` is its ``forward`` with
+``x`` one tensor or up to three read in place of their ``cat``.
 Inference only, float32 only, and no CPU fallback.
 """
 from __future__ import annotations
 
 import math
-from typing import Dict, List
+from typing import Dict, List, Mapping
 
 from . import _native as N
 from . import device as D
@@ -127,3 +130,136 @@ def upsample_flow(flow, mask, mask_scale: float = 1.0):
     out = torch.empty((B, 2, 8 * H, 8 * W), dtype=torch.float32, device=flow.device)
     D.flow_upsample_device(ctx, flow.contiguous(), mask.contiguous(), out, mask_scale)
     return out
+
+
+class SepConvGru:
+    """gru.py:46-76 (built at update_block.py:53): the separable ConvGRU, a horizontal 1 x ks pass and then a vertical ks x 1 pass, each
+    z = sigmoid(conv_z([x, h])), r = sigmoid(conv_r([x, h])), q = tanh(conv_q([x, r * h])), h = (1 - z) * h + z * q.  A call is four
+    launches of raft_gru_kernels.hip (per pass: the stacked z | r convolution with its sigmoids and r * h; the q convolution with tanh
+    and the blend), in the arithmetic DESIGN.md 5.13 fixes.  Not an nn.Module (the package imports torch lazily): the weights live in
+    ``self.weights`` under the reference's names and are packed into the kernels' layout once, by ``load`` / ``from_state_dict``."""
+
+    GATES = ("z_horizontal", "r_horizontal", "q_horizontal", "z_vertical", "r_vertical", "q_vertical")
+
+    def __init__(self, x_channels: int, h_channels: int, kernel_size: int = 5):
+        if int(kernel_size) not in N.FTK_SEP_CONV_GRU_KERNEL_SIZES:
+            raise ValueError(f"kernel_size {kernel_size} is not supported: 3 and 5 are")
+        if int(x_channels) < 1 or not 1 <= int(h_channels) <= N.FTK_SEP_CONV_GRU_MAX_H_CHANNELS:
+            raise ValueError(f"x_channels {x_channels} must be >= 1 and h_channels {h_channels} in 1 .. {N.FTK_SEP_CONV_GRU_MAX_H_CHANNELS}")
+        if int(x_channels) + int(h_channels) > N.FTK_SEP_CONV_GRU_MAX_IN_CHANNELS:
+            raise ValueError(f"x_channels + h_channels = {int(x_channels) + int(h_channels)} above {N.FTK_SEP_CONV_GRU_MAX_IN_CHANNELS}")
+        self.x_channels, self.h_channels, self.kernel_size = int(x_channels), int(h_channels), int(kernel_size)
+        self.weights: Dict[str, object] = {}
+        self._packed: Dict[str, object] = {}
+
+    def parameter_shapes(self) -> Dict[str, tuple]:
+        """The twelve names of the reference module's state dict and their shapes."""
+        C, Ch, ks = self.x_channels + self.h_channels, self.h_channels, self.kernel_size
+        shapes = {}
+        for g in self.GATES:
+            shapes[f"conv_{g}.weight"] = (Ch, C, 1, ks) if g.endswith("horizontal") else (Ch, C, ks, 1)
+            shapes[f"conv_{g}.bias"] = (Ch,)
+        return shapes
+
+    @classmethod
+    def from_state_dict(cls, state: Mapping, prefix: str = "", kernel_size: int = None):
+        """From a state dict of the reference's module (``Raft(...).update_block.gru.state_dict()``, or a whole model's with
+        ``prefix="update_block.gru."``): the sizes are read off ``conv_z_horizontal.weight``."""
+        import torch
+
+        key = f"{prefix}conv_z_horizontal.weight"
+        w = state.get(key) if hasattr(state, "get") else None
+        if not isinstance(w, torch.Tensor) or w.dim() != 4 or w.size(2) != 1:
+            raise ValueError(f"{key} must be a 4-D tensor [h_channels, x_channels + h_channels, 1, kernel_size]"
+                             + (f" (got {list(w.shape)})" if isinstance(w, torch.Tensor) else " and is missing"))
+        Ch, C, _, ks = (int(e) for e in w.shape)
+        if kernel_size is not None and int(kernel_size) != ks:
+            raise ValueError(f"{key} has kernel_size {ks}, not {kernel_size}")
+        if C <= Ch:
+            raise ValueError(f"{key} has {C} input channels for {Ch} hidden ones: x_channels must be >= 1")
+        gru = cls(C - Ch, Ch, ks)
+        gru.load(state, prefix)
+        return gru
+
+    def load(self, state: Mapping, prefix: str = "") -> None:
+        """Takes the twelve tensors (float32, one device, the shapes of ``parameter_shapes``) and packs them; a ValueError names the key."""
+        import torch
+
+        taken, device = {}, None
+        for name, shape in self.parameter_shapes().items():
+            key = prefix + name
+            t = state.get(key) if hasattr(state, "get") else None
+            if t is None:
+                raise ValueError(f"{key} is missing from the state dict")
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != shape:
+                got = f"{t.dtype} {list(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
+                raise ValueError(f"{key} must be a float32 tensor of shape {list(shape)} (got {got})")
+            device = t.device if device is None else device
+            if t.device != device:
+                raise ValueError(f"{key} is on {t.device}, the other weights on {device}")
+            taken[name] = t.detach()
+        self.weights = taken
+        self._packed = self._pack(taken)
+
+    def _pack(self, w) -> Dict[str, object]:
+        """include/ftk.h's layout: [M, K] (torch's own k = c * ks + t) padded to whole tiles and k-steps (rows +0, columns -0), as
+        [tiles][k_steps][64] with lane = 32 (k % 2) + row % 32.  Construction time: torch ops."""
+        import torch
+
+        K = (self.x_channels + self.h_channels) * self.kernel_size
+        k_steps = N.sep_conv_gru_k_steps(self.x_channels + self.h_channels, self.kernel_size)
+
+        def pack(matrix):
+            M = matrix.size(0)
+            tiles = -(-M // 32)
+            full = torch.zeros((tiles * 32, 2 * k_steps), dtype=torch.float32, device=matrix.device)
+            full[:, K:] = -0.0
+            full[:M, :K] = matrix
+            return full.view(tiles, 32, k_steps, 2).permute(0, 2, 3, 1).contiguous().view(-1)
+
+        packed = {}
+        for d in ("horizontal", "vertical"):
+            flat = {g: w[f"conv_{g}_{d}.weight"].reshape(self.h_channels, K) for g in "zrq"}
+            packed["zr_" + d] = pack(torch.cat([flat["z"], flat["r"]], 0))
+            packed["zr_bias_" + d] = torch.cat([w[f"conv_z_{d}.bias"], w[f"conv_r_{d}.bias"]], 0).contiguous()
+            packed["q_" + d] = pack(flat["q"])
+            packed["q_bias_" + d] = w[f"conv_q_{d}.bias"].contiguous()
+        return packed
+
+    def __call__(self, x, h):
+        """``SepConvGru.forward(cat(x), h)``: ``x`` one float32 CUDA tensor [B, x_channels, H, W] or a sequence of up to three whose
+        channels sum to x_channels (a caller passes ``(inp, out, flow)``: neither update_block.py:41's nor :63's ``cat`` is needed);
+        ``h`` [B, h_channels, H, W].  Returns the new hidden state as a new tensor; nothing passed in is modified."""
+        import torch
+
+        parts = [x] if isinstance(x, torch.Tensor) else list(x) if isinstance(x, (list, tuple)) else None
+        if parts is None or not 1 <= len(parts) <= N.FTK_SEP_CONV_GRU_MAX_PARTS:
+            raise ValueError(f"x must be a tensor or a sequence of 1 .. {N.FTK_SEP_CONV_GRU_MAX_PARTS} tensors (got "
+                             f"{type(x).__name__}{'' if parts is None else ' of ' + str(len(parts))})")
+        named = [("h", h)] + [(f"x[{i}]" if len(parts) > 1 else "x", p) for i, p in enumerate(parts)]
+        for name, t in named:
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 4:
+                got = f"{t.dtype} {list(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
+                raise ValueError(f"{name} must be a 4-D float32 CUDA tensor [B, channels, H, W] (no CPU fallback, no other dtype): got {got}")
+        B, Ch, H, W = h.shape
+        if Ch != self.h_channels:
+            raise ValueError(f"h has {Ch} channels, this SepConvGru {self.h_channels}")
+        if min(B, H, W) < 1:
+            raise ValueError(f"h must not be empty (got {tuple(h.shape)})")
+        for name, t in named[1:]:
+            if (t.size(0), t.size(2), t.size(3)) != (B, H, W) or t.size(1) < 1 or t.device != h.device:
+                raise ValueError(f"{name} and h must agree in B, H, W and device: {tuple(t.shape)} on {t.device} vs {tuple(h.shape)} on {h.device}")
+        if sum(int(p.size(1)) for p in parts) != self.x_channels:
+            raise ValueError(f"the channels of x sum to {sum(int(p.size(1)) for p in parts)}, this SepConvGru has x_channels {self.x_channels}")
+        if not self._packed:
+            raise ValueError("this SepConvGru has no weights yet: load(state_dict) or SepConvGru.from_state_dict(state_dict)")
+        _check_no_grad(torch, h, *parts, what="SepConvGru")
+        if not h.is_cuda:
+            raise ValueError(f"x and h must be CUDA tensors (got them on {h.device}): there is no CPU fallback")
+        if self._packed["q_horizontal"].device != h.device:
+            raise ValueError(f"the weights are on {self._packed['q_horizontal'].device}, x and h on {h.device}")
+        torch = D._torch()
+        ctx = _context(h.device.index if h.device.index is not None else torch.cuda.current_device())
+        z, rh, mid, out = (torch.empty((B, Ch, H, W), dtype=torch.float32, device=h.device) for _ in range(4))
+        D.sep_conv_gru_device(ctx, [p.contiguous() for p in parts], h.contiguous(), self._packed, self.kernel_size, z, rh, mid, out)
+        return out

@@ -383,6 +383,43 @@ int ftk_corr_pyramid_lookup_device(ftk_context *ctx, void *stream, const float *
 int ftk_flow_upsample_device(ftk_context *ctx, void *stream, const float *d_flow, const float *d_mask, int32_t B, int32_t H, int32_t W,
                              float mask_scale, float *d_out);
 
+/* ---- RAFT separable ConvGRU (src/nn_optical_flow_tracker/raft/gru.py:46-76) ------------------------ */
+
+/*
+ * SepConvGru.forward (gru.py:59-76) as two kernels per pass, each a 1 x ks (horizontal) or ks x 1 (vertical) convolution as an
+ * implicit GEMM on the f32-input matrix cores with the activation and the element-wise tail in its epilogue.  The input of a
+ * convolution is the channel concatenation of 1 .. FTK_SEP_CONV_GRU_MAX_PARTS tensors of x, read in place, then h (gates) or r * h
+ * (blend): no concatenation is ever stored.  Everything is contiguous float32 [B][channels][H][W] on the context's device.
+ * Limits: kernel_size 3 or 5; 1 <= h_channels <= FTK_SEP_CONV_GRU_MAX_H_CHANNELS; x_channels >= 1 and x_channels + h_channels <=
+ * FTK_SEP_CONV_GRU_MAX_IN_CHANNELS; any B, H, W >= 1.  A size outside them is FTK_E_UNSUPPORTED and launches nothing.
+ *
+ * Packed weights: the weight matrix [M][K], K = kernel_size * C_in in torch's own order k = c * kernel_size + t (M = 2 h_channels for
+ * the gates: the rows of z, then those of r; M = h_channels for q), as [ceil(M / 32)][k_steps][64] floats: entry (tile, s, lane) is
+ * W[32 tile + lane % 32][2 s + lane / 32]; k_steps = ceil(C_in / FTK_SEP_CONV_GRU_CHUNK) * FTK_SEP_CONV_GRU_CHUNK * kernel_size / 2;
+ * a k >= K is packed as -0.0f, a row >= M as +0.0f.  The bias is [M].
+ */
+#define FTK_SEP_CONV_GRU_MAX_PARTS 3
+#define FTK_SEP_CONV_GRU_MAX_H_CHANNELS 1024
+#define FTK_SEP_CONV_GRU_MAX_IN_CHANNELS 4096
+#define FTK_SEP_CONV_GRU_CHUNK 16
+typedef struct ftk_gru_part {
+    const float *data; /* [B][channels][H][W] */
+    int32_t channels;
+} ftk_gru_part;
+/* Host only, no device needed: floats of the packed matrix of out_channels rows over in_channels = x_channels + h_channels. */
+int ftk_sep_conv_gru_packed_elements(int32_t out_channels, int32_t in_channels, int32_t kernel_size, int64_t *elements);
+/* gru.py:59-76, lines 63-66 (vertical == 0) / 70-73 (vertical != 0): d_z = sigmoid_c(conv_z(x | h)), d_rh = sigmoid_c(conv_r(x | h)) * h.
+ * d_weights: the packed stacked z | r matrix, d_bias: [2 h_channels].  One launch on `stream` (a hipStream_t), no allocation, no
+ * synchronisation: capturable. */
+int ftk_sep_conv_gru_gates_device(ftk_context *ctx, void *stream, const ftk_gru_part *x_parts, int32_t n_parts, const float *d_h, const float *d_weights,
+                                  const float *d_bias, int32_t h_channels, int32_t kernel_size, int32_t vertical, int32_t B, int32_t H, int32_t W, float *d_z,
+                                  float *d_rh);
+/* gru.py:59-76, lines 66-68 / 73-75: d_out = (1 - z) * h + z * tanh_c(conv_q(x | rh)), every operation one float32 rounding.
+ * d_weights: the packed q matrix, d_bias: [h_channels].  d_out must not alias d_h, d_z or d_rh.  One launch on `stream`. */
+int ftk_sep_conv_gru_blend_device(ftk_context *ctx, void *stream, const ftk_gru_part *x_parts, int32_t n_parts, const float *d_rh, const float *d_z,
+                                  const float *d_h, const float *d_weights, const float *d_bias, int32_t h_channels, int32_t kernel_size, int32_t vertical,
+                                  int32_t B, int32_t H, int32_t W, float *d_out);
+
 /* ---- features sharded over the GPUs of one node ------------------------ */
 
 /*
