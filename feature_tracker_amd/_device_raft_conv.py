@@ -1,0 +1,52 @@
+"""``device.conv2d_device``: the torch device entry of the stock layers of RAFT's UpdateBlock (ftk_conv2d_device).
+
+It is re-exported by device.py and held to that module's rule: no ``data_ptr()`` of a tensor that did not pass ``device._check``.
+It lives in a file of its own for the reason _device_sep_conv_gru.py gives; this entry's walk (the same recording stand-ins) and its
+refusals are tests/test_update_block_cpu.py.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+
+from . import _native as N
+
+
+def conv2d_device(ctx, parts, packed_weights, bias, kernel_size: int, relu: bool, out_scale: float, out, stream=None) -> None:
+    """One layer of update_block.py (a Conv2d of kernel size 1, 3 or 7, stride 1, zero padding ``kernel_size // 2``; with ``relu`` the
+    ReLU after it; then ``out_scale *``, 1.0 everywhere but the mask head's last layer) in one launch on ``stream`` (a torch.cuda.Stream;
+    default: torch's current stream).  ``parts``: 1 .. 3 contiguous float32 CUDA tensors [B, C_i, H, W] read in place as their channel
+    concatenation; ``out``: [B, out_channels, H, W]; ``bias``: [out_channels]; ``packed_weights``: the flat float32 tensor in the layout
+    of include/ftk.h.  No synchronisation, no allocation: capturable.  Every argument is checked before the device is touched."""
+    from . import device as D
+
+    ks = int(kernel_size)
+    if ks not in N.FTK_CONV2D_KERNEL_SIZES:
+        raise ValueError(f"kernel_size {kernel_size} is not supported: 1, 3 and 7 are")
+    if not math.isfinite(float(out_scale)):
+        raise ValueError(f"out_scale must be finite (got {out_scale})")
+    parts = list(parts)
+    if not 1 <= len(parts) <= N.FTK_CONV2D_MAX_PARTS:
+        raise ValueError(f"the input must be 1 .. {N.FTK_CONV2D_MAX_PARTS} tensors (got {len(parts)})")
+    dev = D._call_device(ctx, out)
+    D._check("out", out, D._F32, (None, None, None, None), dev)
+    B, Cout, H, W = (int(e) for e in out.shape)
+    if min(B, Cout, H, W) < 1:
+        raise ValueError(f"out must be a non-empty [B, out_channels, H, W] tensor (got {list(out.shape)})")
+    if Cout > N.FTK_CONV2D_MAX_OUT_CHANNELS:
+        raise ValueError(f"out_channels {Cout} above FTK_CONV2D_MAX_OUT_CHANNELS = {N.FTK_CONV2D_MAX_OUT_CHANNELS}")
+    Cin = 0
+    for i, part in enumerate(parts):
+        D._check(f"parts[{i}]", part, D._F32, (B, None, H, W), dev)
+        if int(part.shape[1]) < 1:
+            raise ValueError(f"parts[{i}] must have at least one channel (got {list(part.shape)})")
+        Cin += int(part.shape[1])
+    if Cin > N.FTK_CONV2D_MAX_IN_CHANNELS:
+        raise ValueError(f"in_channels {Cin} above FTK_CONV2D_MAX_IN_CHANNELS = {N.FTK_CONV2D_MAX_IN_CHANNELS}")
+    D._check("packed_weights", packed_weights, D._F32, (N.conv2d_packed_elements(Cout, Cin, ks),), dev)
+    D._check("bias", bias, D._F32, (Cout,), dev)
+    s = D._torch().cuda.current_stream(out.device) if stream is None else stream
+    segs = (N.GruPart * len(parts))(*[N.GruPart(C.c_void_p(p.data_ptr()), int(p.shape[1])) for p in parts])
+    rc = N.lib().ftk_conv2d_device(ctx.handle, C.c_void_p(s.cuda_stream), segs, len(parts), C.c_void_p(packed_weights.data_ptr()),
+                                   C.c_void_p(bias.data_ptr()), Cout, ks, 1 if relu else 0, float(out_scale), B, H, W, C.c_void_p(out.data_ptr()))
+    N.check(rc, ctx.handle)

@@ -25,6 +25,12 @@ FTK_SEP_CONV_GRU_MAX_H_CHANNELS = 1024
 FTK_SEP_CONV_GRU_MAX_IN_CHANNELS = 4096
 FTK_SEP_CONV_GRU_CHUNK = 16
 FTK_SEP_CONV_GRU_KERNEL_SIZES = (3, 5)
+# conv2d (UpdateBlock's stock layers; include/ftk.h): the supported sizes and, per kernel size, the chunk of input channels
+FTK_CONV2D_MAX_PARTS = 3
+FTK_CONV2D_MAX_OUT_CHANNELS = 1024
+FTK_CONV2D_MAX_IN_CHANNELS = 4096
+FTK_CONV2D_CHUNK = {1: 32, 3: 8, 7: 2}  # FTK_CONV2D_CHUNK_1 / _3 / _7
+FTK_CONV2D_KERNEL_SIZES = (1, 3, 7)
 ERROR_NAMES = {0: "FTK_OK", -1: "FTK_E_INVALID_ARGUMENT", -2: "FTK_E_NO_DEVICE", -3: "FTK_E_HIP", -4: "FTK_E_UNSUPPORTED",
                -5: "FTK_E_OUT_OF_MEMORY"}
 
@@ -43,6 +49,7 @@ EXPORTS = [
     "ftk_default_dense_flow_options", "ftk_dense_flow_gaussian", "ftk_dense_flow", "ftk_dense_flow_device", "ftk_dense_flow_level",
     "ftk_corr_pyramid_layout", "ftk_corr_pyramid_build_device", "ftk_corr_pyramid_lookup_device", "ftk_flow_upsample_device",
     "ftk_sep_conv_gru_packed_elements", "ftk_sep_conv_gru_gates_device", "ftk_sep_conv_gru_blend_device",
+    "ftk_conv2d_packed_elements", "ftk_conv2d_device",
     "ftk_nn_match_scores_device", "ftk_nn_match_scores", "ftk_nn_match_list_device", "ftk_nn_match_list", "ftk_nn_fill_pixels_device",
 ]
 UNIQUE_ID_BYTES = 128
@@ -206,6 +213,8 @@ def lib() -> C.CDLL:
     l.ftk_sep_conv_gru_packed_elements.argtypes = [i32, i32, i32, i64p]
     l.ftk_sep_conv_gru_gates_device.argtypes = [vp, vp, parts, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]
     l.ftk_sep_conv_gru_blend_device.argtypes = [vp, vp, parts, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
+    l.ftk_conv2d_packed_elements.argtypes = [i32, i32, i32, i64p]
+    l.ftk_conv2d_device.argtypes = [vp, vp, parts, i32, vp, vp, i32, i32, i32, f32, i32, i32, i32, vp]
     l.ftk_nn_match_scores_device.argtypes = [vp, vp, vp, i32, i32, i32, i64, i64, f32, vp, vp]
     l.ftk_nn_match_scores.argtypes = [vp, vp, i32, i32, i32, i64, i64, f32, vp, vp, C.POINTER(C.c_int)]
     l.ftk_nn_match_list_device.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
@@ -248,3 +257,14 @@ def sep_conv_gru_k_steps(in_channels: int, kernel_size: int) -> int:
 def sep_conv_gru_packed_elements(out_channels: int, in_channels: int, kernel_size: int) -> int:
     """Floats of the packed matrix, the value ftk_sep_conv_gru_packed_elements returns (pure Python: argument checks need no library)."""
     return -(-int(out_channels) // 32) * sep_conv_gru_k_steps(in_channels, kernel_size) * 64
+
+
+def conv2d_k_steps(in_channels: int, kernel_size: int) -> int:
+    """MFMA k-steps of a packed conv2d weight matrix (include/ftk.h): whole chunks of FTK_CONV2D_CHUNK[kernel_size] input channels, two k per step."""
+    chunk = FTK_CONV2D_CHUNK[int(kernel_size)]
+    return -(-int(in_channels) // chunk) * (chunk * int(kernel_size) ** 2 // 2)
+
+
+def conv2d_packed_elements(out_channels: int, in_channels: int, kernel_size: int) -> int:
+    """Floats of the packed matrix, the value ftk_conv2d_packed_elements returns (pure Python: argument checks need no library)."""
+    return -(-int(out_channels) // 32) * conv2d_k_steps(in_channels, kernel_size) * 64

@@ -365,12 +365,13 @@ hipError_t flow_upsample_launch(const FlowUpsampleParams &p, hipStream_t stream)
 
 // RAFT's separable ConvGRU (raft_gru_kernels.hip, SepConvGru.forward, gru.py:59-76): per pass a gates launch and a
 // candidate + blend launch, each an implicit GEMM on the f32-input matrix cores.
-struct GruSegment {
+// One tensor of an input that is a channel concatenation read in place (the GRU's and conv2d_kernel's segment lists).
+struct ChannelSegment {
     const float *data;  // [B][channels][H][W]
     int32_t channels;
 };
 struct SepConvGruParams {
-    GruSegment seg[4];     // the input's channel segments in order: the x parts, then h (gates) or r * h (candidate)
+    ChannelSegment seg[4];    // the input's channel segments in order: the x parts, then h (gates) or r * h (candidate)
     int32_t n_seg;
     const float *weights;  // packed [m_tiles][k_steps][64] (sep_conv_gru_plan.h)
     const float *bias;     // [out_channels]
@@ -382,6 +383,20 @@ struct SepConvGruParams {
 };
 struct SepConvGruPlan;
 hipError_t sep_conv_gru_launch(const SepConvGruPlan &plan, const SepConvGruParams &p, int kernel_size, int vertical, int gates, hipStream_t stream);
+
+// The stock layers of RAFT's UpdateBlock (raft_conv_kernels.hip, update_block.py:4-67): a stride-1, zero-padded square
+// convolution with bias, an optional ReLU and an output scale, as one implicit GEMM on the f32-input matrix cores.
+struct ConvParams {
+    ChannelSegment seg[3];  // the input's channel segments in order
+    int32_t n_seg;
+    const float *weights;   // packed [m_tiles][k_steps][64] (raft_conv_plan.h)
+    const float *bias;      // [out_channels]
+    float *out;             // [B][out_channels][H][W]
+    float out_scale;        // the epilogue's last multiply (1: none)
+    int32_t out_channels, in_channels, B, H, W;
+};
+struct ConvPlan;
+hipError_t raft_conv_launch(const ConvPlan &plan, const ConvParams &p, int kernel_size, int relu, hipStream_t stream);
 
 // NNFeatureMatcher's post-processing (nn_match_kernels.hip): mutual-best matching of a score matrix, or a match list.
 // Keys (unsigned 64-bit, merged with atomicMax, 0 = empty): score mode (order-preserving map of the score << 32 | ~index), so the

@@ -1,0 +1,47 @@
+// raft_conv_plan.h — the launch plan of conv2d_kernel (raft_conv_kernels.hip), as sep_conv_gru_plan.h is the GRU's: a
+// pure function of values (no context, no environment, no HIP call; tests/test_update_block_cpu.py walks it without a device through
+// host/build/raft_conv_plan_cli).  ftk_conv.cpp plans, the launcher carries the plan out.
+#pragma once
+
+#include "ftk_device.h"
+
+namespace ftk {
+
+constexpr int kConvMaxParts = 3;           // FTK_CONV2D_MAX_PARTS: tensors of the input
+constexpr int kConvMaxOutChannels = 1024;  // FTK_CONV2D_MAX_OUT_CHANNELS
+constexpr int kConvMaxInChannels = 4096;   // FTK_CONV2D_MAX_IN_CHANNELS: the channels of all parts
+constexpr int kConvWaves = 4;              // waves of a workgroup, arranged wm (output-channel tiles) x wn (rows of 32 pixels)
+constexpr int kConvTile = 32;              // the MFMA tile: 32 output channels x 32 pixels
+// Input channels staged in LDS at a time (FTK_CONV2D_CHUNK_1 / _3 / _7): chosen so that a chunk is whole k-steps, close to the GRU's 40
+// per chunk: 16, 36 and 49.  Each is a divisor or a multiple of kConvWaves (the staging splits a chunk over the waves).
+constexpr int conv_chunk(int kernel_size) { return kernel_size == 1 ? 32 : kernel_size == 3 ? 8 : 2; }
+constexpr int conv_steps(int kernel_size) { return conv_chunk(kernel_size) * kernel_size * kernel_size / 2; }
+// LDS floats per staged channel: (wn + 2 pad) rows of (32 + 2 pad); the static array of the kernel holds a chunk at wn = kConvWaves
+constexpr int conv_row(int kernel_size) { return kConvTile + 2 * (kernel_size / 2); }
+constexpr int conv_pitch(int kernel_size, int wn) { return (wn + 2 * (kernel_size / 2)) * conv_row(kernel_size); }
+constexpr int conv_lds_floats(int kernel_size) { return conv_chunk(kernel_size) * conv_pitch(kernel_size, kConvWaves); }
+
+struct ConvPlanInput {
+    int32_t out_channels, in_channels, kernel_size;
+    int32_t B, H, W;
+};
+enum class ConvRefusal { None, KernelSize, OutChannels, InChannels, Sizes, Grid };
+struct ConvPlan {
+    ConvRefusal refused;  // not None: nothing else is set
+    int32_t m_tiles;      // 32-row tiles of the weight matrix
+    int32_t wm, wn;       // wm * wn = kConvWaves; a workgroup owns wm tiles of output channels and wn rows of 32 pixels
+    int32_t m_groups;     // grid.y: ceil(m_tiles / wm)
+    int32_t tile_w, tile_h;    // pixels of a workgroup: 32 x wn
+    int32_t tiles_x, tiles_y;  // grid.x = tiles_x * tiles_y * B, x fastest
+    int32_t chunk, chunks, steps_per_chunk, k_steps;  // conv_chunk; ceil(in_channels / chunk); conv_steps; chunks * steps_per_chunk
+    int32_t pitch;        // LDS floats per staged channel: the strip and its halo on all four sides
+    size_t lds;           // bytes the kernel uses: chunk * pitch * 4 (its static array is conv_lds_floats)
+    dim3 grid, block;
+    const char *mfma;     // the MFMA form
+};
+const char *conv_refusal_name(ConvRefusal r);
+ConvPlan raft_conv_plan(const ConvPlanInput &in);
+// floats of the packed weight matrix: ceil(out_channels / 32) * k_steps * 64 (k_steps as the plan's); 0 for a kernel size the plan refuses
+int64_t raft_conv_packed_elements(int32_t out_channels, int32_t in_channels, int32_t kernel_size);
+
+}  // namespace ftk

@@ -1,0 +1,35 @@
+// raft_conv_plan_cli — prints the launch plan of conv2d_kernel (csrc/raft_conv_plan.h) without a device.  One case per line on stdin:
+//   out_channels in_channels kernel_size B H W
+// one line of key=value pairs per case on stdout.  tests/test_update_block_cpu.py drives it.
+#include <cstdio>
+#include <iostream>
+#include <sstream>
+#include <string>
+
+#include "raft_conv_plan.h"
+
+int main() {
+    std::string text;
+    while (std::getline(std::cin, text)) {
+        std::istringstream line(text);
+        long long v[6] = {0, 0, 0, 0, 0, 0};
+        for (long long &e : v) {
+            line >> e;
+        }
+        ftk::ConvPlanInput in{};
+        in.out_channels = (int32_t)v[0], in.in_channels = (int32_t)v[1], in.kernel_size = (int32_t)v[2];
+        in.B = (int32_t)v[3], in.H = (int32_t)v[4], in.W = (int32_t)v[5];
+        const ftk::ConvPlan p = ftk::raft_conv_plan(in);
+        printf("refused=%s", ftk::conv_refusal_name(p.refused));
+        if (p.refused == ftk::ConvRefusal::None) {
+            printf(" m_tiles=%d wm=%d wn=%d m_groups=%d tile_w=%d tile_h=%d tiles_x=%d tiles_y=%d chunk=%d chunks=%d steps_per_chunk=%d k_steps=%d"
+                   " pitch=%d lds=%zu lds_static=%zu packed=%lld grid=%ux%u block=%ux%u mfma=%s",
+                   p.m_tiles, p.wm, p.wn, p.m_groups, p.tile_w, p.tile_h, p.tiles_x, p.tiles_y, p.chunk, p.chunks, p.steps_per_chunk, p.k_steps, p.pitch, p.lds,
+                   sizeof(float) * (in.kernel_size == 1 ? ftk::conv_lds_floats(1) : in.kernel_size == 3 ? ftk::conv_lds_floats(3) : ftk::conv_lds_floats(7)),
+                   (long long)ftk::raft_conv_packed_elements(in.out_channels, in.in_channels, in.kernel_size), p.grid.x, p.grid.y, p.block.x, p.block.y,
+                   p.mfma);
+        }
+        printf("\n");
+    }
+    return 0;
+}

@@ -1,6 +1,7 @@
 """RAFT's two operators that are not stock torch layers, the correlation pyramid (src/nn_optical_flow_tracker/raft/
 correlation_volumes.py:19-83) as a drop-in class and the convex flow upsampling (Raft.UpsampleFlow, model.py:48-64) as a function, and
-its recurrent unit, the separable ConvGRU (gru.py:46-76), as a class that runs one step in four fused launches.
+its recurrent unit, the separable ConvGRU (gru.py:46-76), as a class that runs one step in four fused launches, and the update block
+around it (update_block.py:16-67) as ``MotionEncoder`` and ``UpdateBlock``, whose nine stock convolutions are one more kernel family.
 
 ``CorrelationPyramid(fmap0, fmap1, num_levels, radius)`` keeps the reference's attributes (``num_levels``, ``radius``,
 ``correlation_pyramid``) and ``__call__``; ``lookup`` returns the fused ``[B, L*K, H, W]`` tensor that model.py:87-88 builds with
@@ -9,6 +10,8 @@ launch on ``torch.cuda.current_stream()`` at each call, so construction and look
 ``upsample_flow(flow, mask, mask_scale)`` is ``Raft.UpsampleFlow(flow, mask_scale * mask)`` in one launch.
 ``SepConvGru(x_channels, h_channels, kernel_size)`` holds the reference module's twelve tensors; ``gru(x, h)`` is its ``forward`` with
 ``x`` one tensor or up to three read in place of their ``cat``.
+``UpdateBlock.from_state_dict(state, "update_block.")`` is called like the reference's module, ``(net, inp, correlation, flow) ->
+(new_net, mask, delta_flow)``, in 13 launches with no ``cat``.
 Inference only, float32 only, and no CPU fallback.
 """
 from __future__ import annotations
@@ -263,3 +266,217 @@ class SepConvGru:
         z, rh, mid, out = (torch.empty((B, Ch, H, W), dtype=torch.float32, device=h.device) for _ in range(4))
         D.sep_conv_gru_device(ctx, [p.contiguous() for p in parts], h.contiguous(), self._packed, self.kernel_size, z, rh, mid, out)
         return out
+
+
+# ---- the stock layers of UpdateBlock (update_block.py:4-67) -------------------------------------------------------
+
+
+def _state_tensor(state: Mapping, key: str, rank: int = None):
+    """``state[key]`` as a tensor, or a ValueError that names the key."""
+    import torch
+
+    t = state.get(key) if hasattr(state, "get") else None
+    if t is None:
+        raise ValueError(f"{key} is missing from the state dict")
+    if not isinstance(t, torch.Tensor) or (rank is not None and t.dim() != rank):
+        got = f"{t.dtype} {list(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
+        raise ValueError(f"{key} must be a {'' if rank is None else str(rank) + '-D '}tensor (got {got})")
+    return t
+
+
+def _pack_conv(weight):
+    """include/ftk.h's layout of a Conv2d weight [M, C_in, ks, ks]: torch's own [M, K] (k = (c * ks + ty) * ks + tx) padded to whole tiles
+    and k-steps (rows +0, columns -0), as [tiles][k_steps][64] with lane = 32 (k % 2) + row % 32.  Construction time: torch ops."""
+    import torch
+
+    M, Cin, ks, _ = (int(e) for e in weight.shape)
+    K, k_steps = Cin * ks * ks, N.conv2d_k_steps(Cin, ks)
+    tiles = -(-M // 32)
+    full = torch.zeros((tiles * 32, 2 * k_steps), dtype=torch.float32, device=weight.device)
+    full[:, K:] = -0.0
+    full[:M, :K] = weight.reshape(M, K)
+    return full.view(tiles, 32, k_steps, 2).permute(0, 2, 3, 1).contiguous().view(-1)
+
+
+def _load_convs(state: Mapping, prefix: str, shapes: Mapping):
+    """The Conv2d layers ``shapes`` names (layer -> (out_channels, in_channels, kernel_size)) from ``state``: float32, one device, those
+    shapes.  Returns the tensors under the reference's names and, per layer, (packed weights, bias, kernel_size, out_channels)."""
+    import torch
+
+    taken, packed, device = {}, {}, None
+    for layer, (M, Cin, ks) in shapes.items():
+        if ks not in N.FTK_CONV2D_KERNEL_SIZES or not 1 <= M <= N.FTK_CONV2D_MAX_OUT_CHANNELS or not 1 <= Cin <= N.FTK_CONV2D_MAX_IN_CHANNELS:
+            raise ValueError(f"{prefix}{layer}.weight: a {ks} x {ks} convolution of {Cin} -> {M} channels is outside the supported sizes (kernel size "
+                             f"1, 3 or 7, up to {N.FTK_CONV2D_MAX_IN_CHANNELS} -> {N.FTK_CONV2D_MAX_OUT_CHANNELS} channels)")
+        for kind, shape in (("weight", (M, Cin, ks, ks)), ("bias", (M,))):
+            key = f"{prefix}{layer}.{kind}"
+            t = _state_tensor(state, key)
+            if t.dtype != torch.float32 or tuple(t.shape) != shape:
+                raise ValueError(f"{key} must be a float32 tensor of shape {list(shape)} (got {t.dtype} {list(t.shape)})")
+            device = t.device if device is None else device
+            if t.device != device:
+                raise ValueError(f"{key} is on {t.device}, the other weights on {device}")
+            taken[f"{layer}.{kind}"] = t.detach()
+        packed[layer] = (_pack_conv(taken[f"{layer}.weight"]), taken[f"{layer}.bias"].contiguous(), ks, M)
+    return taken, packed
+
+
+def _check_maps(what: str, named, weights_device) -> tuple:
+    """The feature maps of a call, ``named`` = [(name, tensor, channels)]: 4-D float32 tensors of those channel counts that agree in B, H, W
+    and device, not empty, not requiring grad, on the device of the weights, which is a CUDA device.  Returns (B, H, W)."""
+    import torch
+
+    for name, t, channels in named:
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 4 or t.size(1) != channels:
+            got = f"{t.dtype} {list(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
+            raise ValueError(f"{name} must be a 4-D float32 CUDA tensor [B, {channels}, H, W] (no CPU fallback, no other dtype): got {got}")
+    first_name, first, _ = named[0]
+    B, _, H, W = first.shape
+    for name, t, _ in named[1:]:
+        if (t.size(0), t.size(2), t.size(3)) != (B, H, W) or t.device != first.device:
+            raise ValueError(f"{name} and {first_name} must agree in B, H, W and device: {tuple(t.shape)} on {t.device} vs {tuple(first.shape)} on "
+                             f"{first.device}")
+    if min(B, H, W) < 1:
+        raise ValueError(f"{first_name} must not be empty (got {tuple(first.shape)})")
+    if weights_device is None:
+        raise ValueError(f"this {what} has no weights yet: load(state_dict) or {what}.from_state_dict(state_dict)")
+    _check_no_grad(torch, *[t for _, t, _ in named], what=what)
+    if not first.is_cuda:
+        raise ValueError(f"the inputs must be CUDA tensors (got them on {first.device}): there is no CPU fallback")
+    if weights_device != first.device:
+        raise ValueError(f"the weights are on {weights_device}, the inputs on {first.device}")
+    return int(B), int(H), int(W)
+
+
+def _conv(ctx, parts, layer, relu: bool, out_scale: float = 1.0):
+    """One launch of conv2d_kernel over checked, contiguous ``parts``; ``layer`` as _load_convs makes it.  Returns a new tensor."""
+    torch = D._torch()
+    weights, bias, ks, M = layer
+    B, _, H, W = parts[0].shape
+    out = torch.empty((B, M, H, W), dtype=torch.float32, device=parts[0].device)
+    D.conv2d_device(ctx, parts, weights, bias, ks, relu, out_scale, out)
+    return out
+
+
+def _device_context(t):
+    return _context(t.device.index if t.device.index is not None else D._torch().cuda.current_device())
+
+
+class MotionEncoder:
+    """update_block.py:16-43: ``correlation_conv`` (1 x 1, ReLU, 3 x 3, ReLU) on the correlation features, ``flow_conv`` (7 x 7, ReLU, 3 x 3,
+    ReLU) on the flow, ``out_conv`` (3 x 3, ReLU) on their concatenation, which is read in place as two parts and never stored.  Five
+    launches of raft_conv_kernels.hip in the arithmetic DESIGN.md 5.14 fixes.  Not an nn.Module (the package imports torch lazily): the
+    weights live in ``self.weights`` under the reference's names and are packed into the kernels' layout once, by ``load`` /
+    ``from_state_dict``."""
+
+    def __init__(self, correlation_in: int, correlation_hidden: int, correlation_out: int, flow_hidden: int, flow_out: int, out_channels: int):
+        sizes = dict(correlation_in=correlation_in, correlation_hidden=correlation_hidden, correlation_out=correlation_out, flow_hidden=flow_hidden,
+                     flow_out=flow_out, out_channels=out_channels)
+        for name, v in sizes.items():
+            if int(v) < (3 if name == "out_channels" else 1):
+                raise ValueError(f"{name} {v} must be at least {3 if name == 'out_channels' else 1}")
+        self.correlation_in, self.correlation_hidden, self.correlation_out = int(correlation_in), int(correlation_hidden), int(correlation_out)
+        self.flow_hidden, self.flow_out, self.out_channels = int(flow_hidden), int(flow_out), int(out_channels)
+        for layer, (M, Cin, ks) in self.layer_shapes().items():
+            if M > N.FTK_CONV2D_MAX_OUT_CHANNELS or Cin > N.FTK_CONV2D_MAX_IN_CHANNELS:
+                raise ValueError(f"{layer}: {Cin} -> {M} channels above {N.FTK_CONV2D_MAX_IN_CHANNELS} -> {N.FTK_CONV2D_MAX_OUT_CHANNELS}")
+        self.weights: Dict[str, object] = {}
+        self._layers: Dict[str, tuple] = {}
+
+    def layer_shapes(self) -> Dict[str, tuple]:
+        """The five Conv2d layers under the reference's names: (out_channels, in_channels, kernel_size)."""
+        return {"correlation_conv.0": (self.correlation_hidden, self.correlation_in, 1),
+                "correlation_conv.2": (self.correlation_out, self.correlation_hidden, 3),
+                "flow_conv.0": (self.flow_hidden, 2, 7),
+                "flow_conv.2": (self.flow_out, self.flow_hidden, 3),
+                "out_conv.0": (self.out_channels - 2, self.correlation_out + self.flow_out, 3)}
+
+    @classmethod
+    def from_state_dict(cls, state: Mapping, prefix: str = ""):
+        """From a state dict of the reference's module (``Raft(...).update_block.motion_encoder.state_dict()``, or a whole model's with
+        ``prefix="update_block.motion_encoder."``): the sizes are read off the weights."""
+        w = {layer: _state_tensor(state, f"{prefix}{layer}.weight", 4) for layer in ("correlation_conv.0", "correlation_conv.2", "flow_conv.0", "flow_conv.2",
+                                                                                      "out_conv.0")}
+        enc = cls(w["correlation_conv.0"].size(1), w["correlation_conv.0"].size(0), w["correlation_conv.2"].size(0), w["flow_conv.0"].size(0),
+                  w["flow_conv.2"].size(0), w["out_conv.0"].size(0) + 2)
+        enc.load(state, prefix)
+        return enc
+
+    def load(self, state: Mapping, prefix: str = "") -> None:
+        """Takes the ten tensors (float32, one device, the shapes of ``layer_shapes``) and packs them; a ValueError names the key."""
+        self.weights, self._layers = _load_convs(state, prefix, self.layer_shapes())
+
+    def _weights_device(self):
+        return self._layers["out_conv.0"][0].device if self._layers else None
+
+    def _features(self, ctx, correlation, flow):
+        L = self._layers
+        temp_correlation = _conv(ctx, [_conv(ctx, [correlation], L["correlation_conv.0"], True)], L["correlation_conv.2"], True)
+        temp_flow = _conv(ctx, [_conv(ctx, [flow], L["flow_conv.0"], True)], L["flow_conv.2"], True)
+        return _conv(ctx, [temp_correlation, temp_flow], L["out_conv.0"], True)
+
+    def features(self, correlation, flow):
+        """update_block.py:37-40: ``out_conv(cat[correlation_conv(correlation), flow_conv(flow)])`` as a new [B, out_channels - 2, H, W]
+        tensor, in five launches on torch's current stream; ``correlation`` [B, correlation_in, H, W] and ``flow`` [B, 2, H, W] are float32
+        CUDA tensors.  Nothing passed in is modified."""
+        _check_maps("MotionEncoder", [("correlation", correlation, self.correlation_in), ("flow", flow, 2)], self._weights_device())
+        return self._features(_device_context(flow), correlation.contiguous(), flow.contiguous())
+
+    def __call__(self, correlation, flow):
+        """``MotionEncoder.forward`` (update_block.py:36-43): ``cat([features(correlation, flow), flow])``, [B, out_channels, H, W].  The cat is
+        torch's, and the only one; a caller that feeds SepConvGru passes ``(inp, features, flow)`` as parts instead and needs none."""
+        import torch
+
+        return torch.cat([self.features(correlation, flow), flow], dim=1)
+
+
+class UpdateBlock:
+    """update_block.py:45-67: one refinement iteration of RAFT, ``(net, inp, correlation, flow) -> (new_net, mask, delta_flow)``: the motion
+    encoder (5 launches), ``SepConvGru((inp, out, flow), net)`` (4), the flow head (2) and the mask head (2) whose last layer carries
+    :66's 0.25: 13 launches on torch's current stream, no ``cat`` and no element-wise pass.  Built from a state
+    dict of the reference's module; not an nn.Module.  ``self.weights`` holds every tensor under the reference's names."""
+
+    def __init__(self, motion_encoder: MotionEncoder, gru: SepConvGru, state: Mapping, prefix: str):
+        net = gru.h_channels
+        self.net_channels, self.inp_channels = net, gru.x_channels - motion_encoder.out_channels
+        self.motion_encoder, self.gru = motion_encoder, gru
+        hidden = _state_tensor(state, f"{prefix}flow_head.conv1.weight", 4).size(0)
+        mask_hidden = _state_tensor(state, f"{prefix}mask.0.weight", 4).size(0)
+        mask_out = _state_tensor(state, f"{prefix}mask.2.weight", 4).size(0)
+        self.mask_hidden_channels, self.mask_channels = int(mask_hidden), int(mask_out)
+        heads, self._layers = _load_convs(state, prefix, {"flow_head.conv1": (int(hidden), net, 3), "flow_head.conv2": (2, int(hidden), 3),
+                                                          "mask.0": (int(mask_hidden), net, 3), "mask.2": (int(mask_out), int(mask_hidden), 1)})
+        self.weights: Dict[str, object] = {"motion_encoder." + k: v for k, v in motion_encoder.weights.items()}
+        self.weights.update({"gru." + k: v for k, v in gru.weights.items()})
+        self.weights.update(heads)
+
+    @classmethod
+    def from_state_dict(cls, state: Mapping, prefix: str = "update_block."):
+        """From a state dict of the reference's ``Raft`` (the default prefix) or of its ``UpdateBlock`` alone (``prefix=""``).  All sizes are
+        read off the weights; a missing or mis-shaped tensor is a ValueError that names its key."""
+        encoder = MotionEncoder.from_state_dict(state, prefix + "motion_encoder.")
+        gru = SepConvGru.from_state_dict(state, prefix + "gru.")
+        if gru.x_channels <= encoder.out_channels:
+            raise ValueError(f"{prefix}gru.conv_z_horizontal.weight has {gru.x_channels} channels of x: fewer than inp (at least 1) and the motion "
+                             f"encoder's {encoder.out_channels}")
+        block = cls(encoder, gru, state, prefix)
+        devices = {str(t.device) for t in block.weights.values()}
+        if len(devices) != 1:
+            raise ValueError(f"the weights under {prefix!r} are on several devices: {sorted(devices)}")
+        return block
+
+    def __call__(self, net, inp, correlation, flow):
+        """``UpdateBlock.forward``: float32 CUDA tensors ``net`` [B, net, H, W], ``inp`` [B, inp, H, W], ``correlation`` [B, corr, H, W] and
+        ``flow`` [B, 2, H, W] give new tensors ``(new_net, mask, delta_flow)``; ``mask`` already carries the 0.25.  Every argument is
+        checked before the first launch; nothing passed in is modified."""
+        enc = self.motion_encoder
+        _check_maps("UpdateBlock", [("net", net, self.net_channels), ("inp", inp, self.inp_channels), ("correlation", correlation, enc.correlation_in),
+                                    ("flow", flow, 2)], enc._weights_device())
+        ctx = _device_context(net)
+        flow = flow.contiguous()
+        out = enc._features(ctx, correlation.contiguous(), flow)
+        new_net = self.gru((inp, out, flow), net)
+        L = self._layers
+        delta_flow = _conv(ctx, [_conv(ctx, [new_net], L["flow_head.conv1"], True)], L["flow_head.conv2"], False)
+        mask = _conv(ctx, [_conv(ctx, [new_net], L["mask.0"], True)], L["mask.2"], False, 0.25)
+        return new_net, mask, delta_flow

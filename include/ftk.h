@@ -420,6 +420,39 @@ int ftk_sep_conv_gru_blend_device(ftk_context *ctx, void *stream, const ftk_gru_
                                   const float *d_h, const float *d_weights, const float *d_bias, int32_t h_channels, int32_t kernel_size, int32_t vertical,
                                   int32_t B, int32_t H, int32_t W, float *d_out);
 
+/* ---- RAFT UpdateBlock's stock layers (src/nn_optical_flow_tracker/raft/update_block.py:4-67) ------------------------ */
+
+/*
+ * The nine convolutions around the GRU (MotionEncoder: update_block.py:20-35, FlowHead: :7-9, the mask head: :56-60) are one thing: a
+ * stride-1 square convolution of kernel_size 1, 3 or 7 with zero padding kernel_size / 2, a bias, an optional ReLU and an output scale,
+ * run as an implicit GEMM on the f32-input matrix cores.  The input is the channel concatenation of 1 .. FTK_CONV2D_MAX_PARTS tensors
+ * read in place (no concatenation is ever stored); everything is contiguous float32 [B][channels][H][W] on the context's device.
+ * Per output element: acc = bias[co]; for k = (c * kernel_size + ty) * kernel_size + tx ascending, acc = fmaf(W[co][k], in[c][y + ty -
+ * pad][x + tx - pad], acc), a tap outside the image being a multiplied +0; then v = (acc < 0) ? +0 : acc if relu; then out =
+ * out_scale * v, one rounded multiply.
+ * Limits: kernel_size 1, 3 or 7; 1 <= out_channels <= FTK_CONV2D_MAX_OUT_CHANNELS; 1 <= in_channels <= FTK_CONV2D_MAX_IN_CHANNELS; any
+ * B, H, W >= 1.  A size outside them is FTK_E_UNSUPPORTED and launches nothing.
+ *
+ * Packed weights: torch's own [M][K], K = C_in * kernel_size^2, as [ceil(M / 32)][k_steps][64] floats: entry (tile, s, lane) is
+ * W[32 tile + lane % 32][2 s + lane / 32]; k_steps = ceil(C_in / chunk) * chunk * kernel_size^2 / 2 with chunk = FTK_CONV2D_CHUNK_1, _3
+ * or _7 by kernel size; a k >= K is packed as -0.0f, a row >= M as +0.0f.  The bias is [M].
+ */
+#define FTK_CONV2D_MAX_PARTS 3
+#define FTK_CONV2D_MAX_OUT_CHANNELS 1024
+#define FTK_CONV2D_MAX_IN_CHANNELS 4096
+#define FTK_CONV2D_CHUNK_1 32
+#define FTK_CONV2D_CHUNK_3 8
+#define FTK_CONV2D_CHUNK_7 2
+/* Host only, no device needed: floats of the packed matrix of out_channels rows over in_channels. */
+int ftk_conv2d_packed_elements(int32_t out_channels, int32_t in_channels, int32_t kernel_size, int64_t *elements);
+/* One layer of update_block.py: a Conv2d and, with relu != 0, the ReLU after it: correlation_conv (:21-24, kernel sizes 1 and 3),
+ * flow_conv (:27-30, 7 and 3), out_conv (:33-34, whose input, :39's cat, is parts = {temp_correlation, temp_flow}), FlowHead (:7-9, :11-13)
+ * and the mask head (:57-59), whose last layer takes out_scale = 0.25f in place of :66's pass over the mask; out_scale is 1 elsewhere.
+ * parts: the input's tensors (ftk_gru_part: a device pointer and its channel count).  d_out: [B][out_channels][H][W], not aliasing an
+ * input.  One launch on `stream` (a hipStream_t), no allocation, no synchronisation: capturable. */
+int ftk_conv2d_device(ftk_context *ctx, void *stream, const ftk_gru_part *parts, int32_t n_parts, const float *d_weights, const float *d_bias,
+                      int32_t out_channels, int32_t kernel_size, int32_t relu, float out_scale, int32_t B, int32_t H, int32_t W, float *d_out);
+
 /* ---- features sharded over the GPUs of one node ------------------------ */
 
 /*
