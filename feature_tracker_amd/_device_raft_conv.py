@@ -1,4 +1,6 @@
-"""``device.conv2d_device``: the torch device entry of the stock layers of RAFT's UpdateBlock (ftk_conv2d_device).
+"""``device.conv2d_device``: the torch device entry of the stock layers of RAFT's UpdateBlock (ftk_conv2d_device), and
+``device.conv2d_strided_device``, the same layer with a stride, a residual and the image normalisation for RAFT's encoders
+(ftk_conv2d_strided_device; its walk and refusals are tests/test_raft_encoder_cpu.py).
 
 It is re-exported by device.py and held to that module's rule: no ``data_ptr()`` of a tensor that did not pass ``device._check``.
 It lives in a file of its own for the reason _device_sep_conv_gru.py gives; this entry's walk (the same recording stand-ins) and its
@@ -49,4 +51,56 @@ def conv2d_device(ctx, parts, packed_weights, bias, kernel_size: int, relu: bool
     segs = (N.GruPart * len(parts))(*[N.GruPart(C.c_void_p(p.data_ptr()), int(p.shape[1])) for p in parts])
     rc = N.lib().ftk_conv2d_device(ctx.handle, C.c_void_p(s.cuda_stream), segs, len(parts), C.c_void_p(packed_weights.data_ptr()),
                                    C.c_void_p(bias.data_ptr()), Cout, ks, 1 if relu else 0, float(out_scale), B, H, W, C.c_void_p(out.data_ptr()))
+    N.check(rc, ctx.handle)
+
+
+def conv2d_strided_device(ctx, parts, packed_weights, bias, kernel_size: int, stride: int, relu: bool, out_scale: float, residual, normalise: bool, out,
+                          stream=None) -> None:
+    """One layer of encoder.py: ``conv2d_device`` with a ``stride`` of 1 or 2 (2: kernel sizes 1 and 3), with ``residual`` (None or a
+    contiguous float32 CUDA tensor of ``out``'s shape) added before the ReLU, and with ``normalise`` model.py:70-71's ``2 * (x / 255) - 1``
+    applied to the in-image input values.  ``parts``: [B, C_i, H, W]; ``out``: [B, out_channels, ceil(H / stride), ceil(W / stride)].  The
+    weights are BatchNorm-folded by the caller and packed as for ``conv2d_device``.  One launch, no synchronisation, no allocation:
+    capturable.  Every argument is checked before the device is touched."""
+    from . import device as D
+
+    ks, st = int(kernel_size), int(stride)
+    if ks not in N.FTK_CONV2D_KERNEL_SIZES:
+        raise ValueError(f"kernel_size {kernel_size} is not supported: 1, 3 and 7 are")
+    if st not in N.FTK_CONV2D_STRIDES or ks not in N.FTK_CONV2D_STRIDES[st]:
+        raise ValueError(f"stride {stride} with kernel_size {ks} is not supported: stride 1, and stride 2 with kernel sizes 1 and 3, are")
+    if not math.isfinite(float(out_scale)):
+        raise ValueError(f"out_scale must be finite (got {out_scale})")
+    parts = list(parts)
+    if not 1 <= len(parts) <= N.FTK_CONV2D_MAX_PARTS:
+        raise ValueError(f"the input must be 1 .. {N.FTK_CONV2D_MAX_PARTS} tensors (got {len(parts)})")
+    dev = D._call_device(ctx, out)
+    D._check("out", out, D._F32, (None, None, None, None), dev)
+    B, Cout, OH, OW = (int(e) for e in out.shape)
+    if min(B, Cout, OH, OW) < 1:
+        raise ValueError(f"out must be a non-empty [B, out_channels, H, W] tensor (got {list(out.shape)})")
+    if Cout > N.FTK_CONV2D_MAX_OUT_CHANNELS:
+        raise ValueError(f"out_channels {Cout} above FTK_CONV2D_MAX_OUT_CHANNELS = {N.FTK_CONV2D_MAX_OUT_CHANNELS}")
+    D._check("parts[0]", parts[0], D._F32, (B, None, None, None), dev)
+    H, W = int(parts[0].shape[2]), int(parts[0].shape[3])
+    if (-(-H // st), -(-W // st)) != (OH, OW):
+        raise ValueError(f"out must be [B, out_channels, {-(-H // st)}, {-(-W // st)}] for parts[0] {list(parts[0].shape)} at stride {st} (got "
+                         f"{list(out.shape)})")
+    Cin = 0
+    for i, part in enumerate(parts):
+        D._check(f"parts[{i}]", part, D._F32, (B, None, H, W), dev)
+        if int(part.shape[1]) < 1:
+            raise ValueError(f"parts[{i}] must have at least one channel (got {list(part.shape)})")
+        Cin += int(part.shape[1])
+    if Cin > N.FTK_CONV2D_MAX_IN_CHANNELS:
+        raise ValueError(f"in_channels {Cin} above FTK_CONV2D_MAX_IN_CHANNELS = {N.FTK_CONV2D_MAX_IN_CHANNELS}")
+    D._check("packed_weights", packed_weights, D._F32, (N.conv2d_packed_elements(Cout, Cin, ks),), dev)
+    D._check("bias", bias, D._F32, (Cout,), dev)
+    if residual is not None:
+        D._check("residual", residual, D._F32, (B, Cout, OH, OW), dev)
+    s = D._torch().cuda.current_stream(out.device) if stream is None else stream
+    segs = (N.GruPart * len(parts))(*[N.GruPart(C.c_void_p(p.data_ptr()), int(p.shape[1])) for p in parts])
+    rc = N.lib().ftk_conv2d_strided_device(ctx.handle, C.c_void_p(s.cuda_stream), segs, len(parts), C.c_void_p(packed_weights.data_ptr()),
+                                           C.c_void_p(bias.data_ptr()), Cout, ks, st, 1 if relu else 0, float(out_scale),
+                                           None if residual is None else C.c_void_p(residual.data_ptr()), 1 if normalise else 0, B, H, W,
+                                           C.c_void_p(out.data_ptr()))
     N.check(rc, ctx.handle)

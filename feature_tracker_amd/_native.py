@@ -31,6 +31,7 @@ FTK_CONV2D_MAX_OUT_CHANNELS = 1024
 FTK_CONV2D_MAX_IN_CHANNELS = 4096
 FTK_CONV2D_CHUNK = {1: 32, 3: 8, 7: 2}  # FTK_CONV2D_CHUNK_1 / _3 / _7
 FTK_CONV2D_KERNEL_SIZES = (1, 3, 7)
+FTK_CONV2D_STRIDES = {1: (1, 3, 7), 2: (1, 3)}  # ftk_conv2d_strided_device: the kernel sizes of each stride
 ERROR_NAMES = {0: "FTK_OK", -1: "FTK_E_INVALID_ARGUMENT", -2: "FTK_E_NO_DEVICE", -3: "FTK_E_HIP", -4: "FTK_E_UNSUPPORTED",
                -5: "FTK_E_OUT_OF_MEMORY"}
 
@@ -49,7 +50,7 @@ EXPORTS = [
     "ftk_default_dense_flow_options", "ftk_dense_flow_gaussian", "ftk_dense_flow", "ftk_dense_flow_device", "ftk_dense_flow_level",
     "ftk_corr_pyramid_layout", "ftk_corr_pyramid_build_device", "ftk_corr_pyramid_lookup_device", "ftk_flow_upsample_device",
     "ftk_sep_conv_gru_packed_elements", "ftk_sep_conv_gru_gates_device", "ftk_sep_conv_gru_blend_device",
-    "ftk_conv2d_packed_elements", "ftk_conv2d_device",
+    "ftk_conv2d_packed_elements", "ftk_conv2d_device", "ftk_conv2d_strided_device",
     "ftk_nn_match_scores_device", "ftk_nn_match_scores", "ftk_nn_match_list_device", "ftk_nn_match_list", "ftk_nn_fill_pixels_device",
 ]
 UNIQUE_ID_BYTES = 128
@@ -215,6 +216,7 @@ def lib() -> C.CDLL:
     l.ftk_sep_conv_gru_blend_device.argtypes = [vp, vp, parts, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
     l.ftk_conv2d_packed_elements.argtypes = [i32, i32, i32, i64p]
     l.ftk_conv2d_device.argtypes = [vp, vp, parts, i32, vp, vp, i32, i32, i32, f32, i32, i32, i32, vp]
+    l.ftk_conv2d_strided_device.argtypes = [vp, vp, parts, i32, vp, vp, i32, i32, i32, i32, f32, vp, i32, i32, i32, i32, vp]
     l.ftk_nn_match_scores_device.argtypes = [vp, vp, vp, i32, i32, i32, i64, i64, f32, vp, vp]
     l.ftk_nn_match_scores.argtypes = [vp, vp, i32, i32, i32, i64, i64, f32, vp, vp, C.POINTER(C.c_int)]
     l.ftk_nn_match_list_device.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]

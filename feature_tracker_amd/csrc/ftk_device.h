@@ -397,6 +397,15 @@ struct ConvParams {
 };
 struct ConvPlan;
 hipError_t raft_conv_launch(const ConvPlan &plan, const ConvParams &p, int kernel_size, int relu, hipStream_t stream);
+// RAFT's encoders (encoder.py:4-68): the same layer with a stride of 1 or 2 (base.H, base.W the input's sizes), a residual
+// added before the ReLU and the image normalisation of model.py:70-71 at the fetch.  Stride 1 with neither is raft_conv_launch itself.
+struct ConvStridedParams {
+    ConvParams base;
+    const float *residual;  // [B][out_channels][OH][OW] or nullptr
+    int32_t OH, OW;         // ceil(H / stride) x ceil(W / stride): the plan's out_h, out_w
+    int32_t normalise;      // != 0: an in-image input value x is read as 2 (x / 255) - 1
+};
+hipError_t raft_conv_strided_launch(const ConvPlan &plan, const ConvStridedParams &p, int kernel_size, int relu, hipStream_t stream);
 
 // NNFeatureMatcher's post-processing (nn_match_kernels.hip): mutual-best matching of a score matrix, or a match list.
 // Keys (unsigned 64-bit, merged with atomicMax, 0 = empty): score mode (order-preserving map of the score << 32 | ~index), so the

@@ -17,6 +17,18 @@
 // channel (+0 outside the image: torch's zero padding), and every tap reads it at a shifted address: lanes 0-31 read 32 consecutive
 // floats, conflict-free.  The next chunk's strip and A operands are loaded into registers while this chunk's MFMAs run.
 // Every index is 64-bit; no address depends on the data.
+//
+// RAFT's encoders (encoder.py:4-68) add three things, all behind template parameters that default to the above, so the
+// UpdateBlock's six instantiations are the code they were: a stride S of 2 for KS 1 and 3, and, with EX, a residual added to the
+// accumulator before the ReLU (v = acc + res[co][y][x], one rounded add) and model.py:70-71's normalisation n = 2 (x / 255) - 1 of the
+// in-image values as they are fetched (the padding stays +0), both switched by the launch's arguments.
+// Stride 2: the workgroup owns 32 x wn OUTPUT pixels; output pixel (y, x) reads input (2 y + ty - PAD, 2 x + tx - PAD).  Lanes 0-31 of a
+// tap would read every second float of a linear row: ds_read_b32 serves a 32-lane half from banks (address / 4) % 32, so floats 2 j and
+// 2 j + 32 of lanes j and j + 16 would meet in one bank, a 2-way conflict on every B operand.  So a staged row holds its even columns
+// in one plane of 32 + PAD floats and its odd columns in a second plane behind it (raft_conv_plan.h): staged column sc = 2 j + tx is
+// float j + tx / 2 of plane tx % 2, lane j's bank is (base + j) % 32, 32 different banks.  Lanes 32-63 hold another tap and are
+// another half.  The strip of KS 3 is 2 (wn - 1) + 3 rows of 2 x 33 floats per channel (the 66th input column is never read); KS 1
+// reads even rows and columns only and stages just those, wn rows of 32.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -30,24 +42,38 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kThreads = 64 * kConvWaves;
 
-template <int KS, bool RELU>
-__global__ __launch_bounds__(kThreads) void conv2d_kernel(ConvParams prm, int wm, int tiles_x, int tiles_y, int chunks, int m_tiles) {
+inline __device__ const ConvParams &conv_base(const ConvParams &p) { return p; }
+inline __device__ const ConvParams &conv_base(const ConvStridedParams &p) { return p.base; }
+
+template <int KS, bool RELU, int S = 1, bool EX = false, typename P = ConvParams>
+__global__ __launch_bounds__(kThreads) void conv2d_kernel(P launch, int wm, int tiles_x, int tiles_y, int chunks, int m_tiles) {
+    static_assert(S == 1 || (S == 2 && KS != 7), "stride 2 is built for kernel sizes 1 and 3");
+    static_assert(EX || S == 1, "the strided forms take the extended parameters");
+    const ConvParams &prm = conv_base(launch);
     constexpr int PAD = KS / 2;
     constexpr int CC = conv_chunk(KS);     // input channels of a chunk
     constexpr int STEPS = conv_steps(KS);  // k-steps of a chunk
-    constexpr int ROW = conv_row(KS);      // LDS floats of a staged row
+    constexpr int ROW = S == 1 ? conv_row(KS) : conv_s2_row(KS);  // LDS floats of a staged row
+    constexpr int PLANE = conv_s2_plane(KS);                      // stride 2: floats of the even and of the odd plane of a row
+    constexpr int PITCH_MAX = S == 1 ? conv_pitch(KS, kConvWaves) : conv_s2_pitch(KS, kConvWaves);
     // Staging: a chunk of at least 4 channels gives each wave CC / 4 whole strips; a smaller one (KS 7: 2) gives each strip to 4 / CC waves.
     constexpr int WPC = CC < kConvWaves ? kConvWaves / CC : 1;  // waves of one strip
     constexpr int CPW = CC < kConvWaves ? 1 : CC / kConvWaves;  // strips of one wave
-    constexpr int ITERS = (conv_pitch(KS, kConvWaves) + 64 * WPC - 1) / (64 * WPC);
+    constexpr int ITERS = (PITCH_MAX + 64 * WPC - 1) / (64 * WPC);
     static_assert(2 * STEPS == CC * KS * KS, "a chunk is whole k-steps");
     static_assert(CC % kConvWaves == 0 || kConvWaves % CC == 0, "a chunk splits over the waves");
-    __shared__ float s_in[conv_lds_floats(KS)];
+    __shared__ float s_in[CC * PITCH_MAX];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wn = kConvWaves / wm;
     const int wmi = wave % wm, wni = wave / wm;
     const int H = prm.H, W = prm.W, Cin = prm.in_channels, Cout = prm.out_channels;
     const int64_t HW = (int64_t)H * W;
+    // the output's sizes: the input's at stride 1
+    int OH = H, OW = W;
+    if constexpr (EX) {
+        OH = launch.OH, OW = launch.OW;
+    }
+    const int64_t OHW = (int64_t)OH * OW;
     // blockIdx.x = tx + tiles_x * (ty + tiles_y * b)
     int64_t g = blockIdx.x;
     const int tx = (int)(g % tiles_x);
@@ -56,7 +82,7 @@ __global__ __launch_bounds__(kThreads) void conv2d_kernel(ConvParams prm, int wm
     const int64_t b = g / tiles_y;
     const int64_t x0 = (int64_t)tx * kConvTile;
     const int64_t y0 = (int64_t)ty * wn;
-    const int pitch = (wn + 2 * PAD) * ROW;
+    const int pitch = (S == 1 ? wn + 2 * PAD : conv_s2_rows(KS, wn)) * ROW;
     const int m_tile = blockIdx.y * wm + wmi;
     const bool active = m_tile < m_tiles;  // wave-uniform; an idle wave still stages and meets every barrier
     const int j = lane & 31, kh = lane >> 5;
@@ -69,8 +95,12 @@ __global__ __launch_bounds__(kThreads) void conv2d_kernel(ConvParams prm, int wm
 #pragma unroll
     for (int it = 0; it < ITERS; ++it) {
         const int pos = lane + 64 * (sub + WPC * it);
-        const int64_t yy = y0 - PAD + pos / ROW;
-        const int64_t xx = x0 - PAD + pos % ROW;
+        int64_t yy = y0 - PAD + pos / ROW;
+        int64_t xx = x0 - PAD + pos % ROW;
+        if constexpr (S == 2) {  // row r of a 3 x 3 strip is input row 2 y0 - 1 + r, of a 1 x 1 strip 2 (y0 + r); column: 2 (float of its plane) + plane
+            yy = KS == 1 ? 2 * (y0 + pos / ROW) : 2 * y0 - PAD + pos / ROW;
+            xx = 2 * x0 - PAD + 2 * ((pos % ROW) % PLANE) + (pos % ROW) / PLANE;
+        }
         soff[it] = (pos < pitch && yy >= 0 && yy < H && xx >= 0 && xx < W) ? yy * W + xx : -1;
     }
     float st[CPW][ITERS];
@@ -92,6 +122,11 @@ __global__ __launch_bounds__(kThreads) void conv2d_kernel(ConvParams prm, int wm
 #pragma unroll
             for (int it = 0; it < ITERS; ++it) {
                 st[i][it] = (plane != nullptr && soff[it] >= 0) ? plane[soff[it]] : 0.0f;
+                if constexpr (EX) {
+                    if (launch.normalise && plane != nullptr && soff[it] >= 0) {  // model.py:70-71, one rounding per operation; the padding stays +0
+                        st[i][it] = __fsub_rn(__fmul_rn(2.0f, __fdiv_rn(st[i][it], 255.0f)), 1.0f);
+                    }
+                }
             }
         }
     };
@@ -125,7 +160,7 @@ __global__ __launch_bounds__(kThreads) void conv2d_kernel(ConvParams prm, int wm
         const int co = m_tile * kConvTile + (r & 3) + 8 * (r >> 2) + 4 * kh;
         acc[r] = (active && co < Cout) ? prm.bias[co] : 0.0f;
     }
-    const int lane_base = wni * ROW + j;
+    const int lane_base = ((S == 2 && KS > 1) ? 2 * wni : wni) * ROW + j;
 
     fetch(0);
     if (active) {
@@ -146,8 +181,9 @@ __global__ __launch_bounds__(kThreads) void conv2d_kernel(ConvParams prm, int wm
             for (int s = 0; s < STEPS; ++s) {
                 // this lane's k of the step within the chunk: 2 s + kh = (cl * KS + ty) * KS + tx
                 constexpr int KK = KS * KS;
-                const int off0 = ((2 * s) / KK) * pitch + (((2 * s) / KS) % KS) * ROW + (2 * s) % KS;
-                const int off1 = ((2 * s + 1) / KK) * pitch + (((2 * s + 1) / KS) % KS) * ROW + (2 * s + 1) % KS;
+                const int tx0 = (2 * s) % KS, tx1 = (2 * s + 1) % KS;      // stride 2: float tx / 2 of plane tx % 2
+                const int off0 = ((2 * s) / KK) * pitch + (((2 * s) / KS) % KS) * ROW + (S == 1 ? tx0 : (tx0 & 1) * PLANE + tx0 / 2);
+                const int off1 = ((2 * s + 1) / KK) * pitch + (((2 * s + 1) / KS) % KS) * ROW + (S == 1 ? tx1 : (tx1 & 1) * PLANE + tx1 / 2);
                 const float bv = s_in[lane_base + (kh ? off1 : off0)];
                 acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a_cur[s], bv, acc, 0, 0, 0);
             }
@@ -164,10 +200,10 @@ __global__ __launch_bounds__(kThreads) void conv2d_kernel(ConvParams prm, int wm
     // epilogue
     const int64_t py = y0 + wni;
     const int64_t px = x0 + j;
-    if (!active || py >= H || px >= W) {
+    if (!active || py >= OH || px >= OW) {
         return;
     }
-    const int64_t pix = py * W + px;
+    const int64_t pix = py * OW + px;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int co = m_tile * kConvTile + (r & 3) + 8 * (r >> 2) + 4 * kh;
@@ -175,10 +211,15 @@ __global__ __launch_bounds__(kThreads) void conv2d_kernel(ConvParams prm, int wm
             continue;
         }
         float v = acc[r];
+        if constexpr (EX) {
+            if (launch.residual != nullptr) {
+                v = __fadd_rn(v, launch.residual[(b * Cout + co) * OHW + pix]);
+            }
+        }
         if (RELU) {
             v = (v < 0.0f) ? 0.0f : v;  // not fmaxf: a NaN stays a NaN and -0 stays -0
         }
-        prm.out[(b * Cout + co) * HW + pix] = __fmul_rn(prm.out_scale, v);
+        prm.out[(b * Cout + co) * OHW + pix] = __fmul_rn(prm.out_scale, v);
     }
 }
 
@@ -195,10 +236,44 @@ hipError_t launch_ks(const ConvPlan &plan, const ConvParams &p, int relu, hipStr
     return hipGetLastError();
 }
 
+template <int KS, int S>
+hipError_t launch_strided(const ConvPlan &plan, const ConvStridedParams &p, int relu, hipStream_t stream) {
+    constexpr int kLds = S == 1 ? conv_lds_floats(KS) : conv_s2_lds_floats(KS);
+    static_assert(kLds * sizeof(float) <= 64 * 1024, "the static LDS of a form stays inside 64 KiB");
+    if ((size_t)plan.chunk * plan.pitch > (size_t)kLds || plan.chunk != conv_chunk(KS) || plan.stride != S || p.OH != plan.out_h || p.OW != plan.out_w) {
+        return hipErrorInvalidValue;
+    }
+    if (relu) {
+        hipLaunchKernelGGL((conv2d_kernel<KS, true, S, true, ConvStridedParams>), plan.grid, plan.block, 0, stream, p, plan.wm, plan.tiles_x, plan.tiles_y,
+                           plan.chunks, plan.m_tiles);
+    } else {
+        hipLaunchKernelGGL((conv2d_kernel<KS, false, S, true, ConvStridedParams>), plan.grid, plan.block, 0, stream, p, plan.wm, plan.tiles_x, plan.tiles_y,
+                           plan.chunks, plan.m_tiles);
+    }
+    return hipGetLastError();
+}
+
 }  // namespace
 
-hipError_t raft_conv_launch(const ConvPlan &plan, const ConvParams &p, int kernel_size, int relu, hipStream_t stream) {
+hipError_t raft_conv_strided_launch(const ConvPlan &plan, const ConvStridedParams &p, int kernel_size, int relu, hipStream_t stream) {
     if (plan.refused != ConvRefusal::None || plan.block.x != (unsigned)kThreads || plan.wm * plan.wn != kConvWaves) {
+        return hipErrorInvalidValue;
+    }
+    if (plan.stride == 1 && p.residual == nullptr && !p.normalise) {
+        return raft_conv_launch(plan, p.base, kernel_size, relu, stream);  // nothing of the extension is asked for: the plain forms
+    }
+    switch (10 * plan.stride + kernel_size) {
+    case 11: return launch_strided<1, 1>(plan, p, relu, stream);
+    case 13: return launch_strided<3, 1>(plan, p, relu, stream);
+    case 17: return launch_strided<7, 1>(plan, p, relu, stream);
+    case 21: return launch_strided<1, 2>(plan, p, relu, stream);
+    case 23: return launch_strided<3, 2>(plan, p, relu, stream);
+    }
+    return hipErrorInvalidValue;
+}
+
+hipError_t raft_conv_launch(const ConvPlan &plan, const ConvParams &p, int kernel_size, int relu, hipStream_t stream) {
+    if (plan.refused != ConvRefusal::None || plan.block.x != (unsigned)kThreads || plan.wm * plan.wn != kConvWaves || plan.stride != 1) {
         return hipErrorInvalidValue;
     }
     switch (kernel_size) {

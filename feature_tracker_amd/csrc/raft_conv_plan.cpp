@@ -11,6 +11,7 @@ const char *conv_refusal_name(ConvRefusal r) {
     case ConvRefusal::InChannels: return "in_channels";
     case ConvRefusal::Sizes: return "sizes";
     case ConvRefusal::Grid: return "grid";
+    case ConvRefusal::Stride: return "stride";
     }
     return "?";
 }
@@ -29,6 +30,8 @@ ConvPlan raft_conv_plan(const ConvPlanInput &in) {
     p.refused = ConvRefusal::None;
     if (in.kernel_size != 1 && in.kernel_size != 3 && in.kernel_size != 7) {
         p.refused = ConvRefusal::KernelSize;
+    } else if ((in.stride != 1 && in.stride != 2) || (in.stride == 2 && in.kernel_size == 7)) {
+        p.refused = ConvRefusal::Stride;
     } else if (in.out_channels < 1 || in.out_channels > kConvMaxOutChannels) {
         p.refused = ConvRefusal::OutChannels;
     } else if (in.in_channels < 1 || in.in_channels > kConvMaxInChannels) {
@@ -47,13 +50,21 @@ ConvPlan raft_conv_plan(const ConvPlanInput &in) {
     p.m_groups = (p.m_tiles + p.wm - 1) / p.wm;
     p.tile_w = kConvTile;
     p.tile_h = p.wn;
-    p.tiles_x = (int32_t)(((int64_t)in.W + p.tile_w - 1) / p.tile_w);  // 64-bit: W + 31 may pass 2^31
-    p.tiles_y = (int32_t)(((int64_t)in.H + p.tile_h - 1) / p.tile_h);
+    p.stride = in.stride;
+    p.out_h = (int32_t)(((int64_t)in.H + in.stride - 1) / in.stride);
+    p.out_w = (int32_t)(((int64_t)in.W + in.stride - 1) / in.stride);
+    p.tiles_x = (int32_t)(((int64_t)p.out_w + p.tile_w - 1) / p.tile_w);  // 64-bit: W + 31 may pass 2^31
+    p.tiles_y = (int32_t)(((int64_t)p.out_h + p.tile_h - 1) / p.tile_h);
     p.chunk = conv_chunk(in.kernel_size);
     p.chunks = (in.in_channels + p.chunk - 1) / p.chunk;
     p.steps_per_chunk = conv_steps(in.kernel_size);
     p.k_steps = p.chunks * p.steps_per_chunk;
-    p.pitch = conv_pitch(in.kernel_size, p.wn);
+    const int32_t pad = in.kernel_size / 2;
+    p.rows = in.stride == 1 ? p.wn + 2 * pad : conv_s2_rows(in.kernel_size, p.wn);
+    p.row = in.stride == 1 ? conv_row(in.kernel_size) : conv_s2_row(in.kernel_size);
+    p.pitch = p.rows * p.row;  // stride 1: conv_pitch
+    p.strip_h = in.stride * (p.wn - 1) + in.kernel_size;
+    p.strip_w = in.stride == 1 ? conv_row(in.kernel_size) : 2 * (kConvTile - 1) + in.kernel_size + 1;
     p.lds = (size_t)p.chunk * p.pitch * sizeof(float);
     const int64_t tiles = (int64_t)p.tiles_x * p.tiles_y;  // below 2^57; times B only once it is known to be below 2^31
     const int64_t groups = tiles > 0x7fffffff ? tiles : tiles * in.B;

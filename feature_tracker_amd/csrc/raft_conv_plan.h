@@ -20,22 +20,36 @@ constexpr int conv_steps(int kernel_size) { return conv_chunk(kernel_size) * ker
 constexpr int conv_row(int kernel_size) { return kConvTile + 2 * (kernel_size / 2); }
 constexpr int conv_pitch(int kernel_size, int wn) { return (wn + 2 * (kernel_size / 2)) * conv_row(kernel_size); }
 constexpr int conv_lds_floats(int kernel_size) { return conv_chunk(kernel_size) * conv_pitch(kernel_size, kConvWaves); }
+// Stride 2 (kernel sizes 1 and 3): a workgroup still owns 32 output pixels x wn output rows and the chunk is the same, so
+// the packed weights are.  A 3 x 3 strip is 2 (wn - 1) + 3 input rows of 63 + 2 + 1 input columns, the even columns of a row in one plane
+// of 32 + pad floats and the odd ones in a second plane behind it: tap tx of output pixel j is staged column 2 j + tx, float j + tx / 2 of
+// plane tx % 2, so the 32 lanes of a tap read 32 consecutive floats.  A 1 x 1 reads even rows and even columns only: it keeps just those,
+// wn rows of one plane.
+constexpr int conv_s2_plane(int kernel_size) { return kConvTile + kernel_size / 2; }
+constexpr int conv_s2_row(int kernel_size) { return kernel_size == 1 ? kConvTile : 2 * conv_s2_plane(kernel_size); }
+constexpr int conv_s2_rows(int kernel_size, int wn) { return kernel_size == 1 ? wn : 2 * (wn - 1) + kernel_size; }
+constexpr int conv_s2_pitch(int kernel_size, int wn) { return conv_s2_rows(kernel_size, wn) * conv_s2_row(kernel_size); }
+constexpr int conv_s2_lds_floats(int kernel_size) { return conv_chunk(kernel_size) * conv_s2_pitch(kernel_size, kConvWaves); }
 
 struct ConvPlanInput {
     int32_t out_channels, in_channels, kernel_size;
-    int32_t B, H, W;
+    int32_t B, H, W;     // of the input
+    int32_t stride = 1;  // 1 or 2 (2: kernel sizes 1 and 3); the output is ceil(H / stride) x ceil(W / stride)
 };
-enum class ConvRefusal { None, KernelSize, OutChannels, InChannels, Sizes, Grid };
+enum class ConvRefusal { None, KernelSize, OutChannels, InChannels, Sizes, Grid, Stride };
 struct ConvPlan {
     ConvRefusal refused;  // not None: nothing else is set
     int32_t m_tiles;      // 32-row tiles of the weight matrix
     int32_t wm, wn;       // wm * wn = kConvWaves; a workgroup owns wm tiles of output channels and wn rows of 32 pixels
     int32_t m_groups;     // grid.y: ceil(m_tiles / wm)
-    int32_t tile_w, tile_h;    // pixels of a workgroup: 32 x wn
+    int32_t stride, out_h, out_w;  // the input's; the output's sizes, which the tiles partition
+    int32_t tile_w, tile_h;    // output pixels of a workgroup: 32 x wn
     int32_t tiles_x, tiles_y;  // grid.x = tiles_x * tiles_y * B, x fastest
     int32_t chunk, chunks, steps_per_chunk, k_steps;  // conv_chunk; ceil(in_channels / chunk); conv_steps; chunks * steps_per_chunk
-    int32_t pitch;        // LDS floats per staged channel: the strip and its halo on all four sides
-    size_t lds;           // bytes the kernel uses: chunk * pitch * 4 (its static array is conv_lds_floats)
+    int32_t pitch;        // LDS floats per staged channel: the strip and its halo on all four sides (rows * row)
+    int32_t rows, row;    // staged rows of a channel and LDS floats of one
+    int32_t strip_h, strip_w;  // input rows and columns a workgroup's taps span, from (stride * y0 - pad, stride * x0 - pad)
+    size_t lds;           // bytes the kernel uses: chunk * pitch * 4 (its static array is conv_lds_floats / conv_s2_lds_floats)
     dim3 grid, block;
     const char *mfma;     // the MFMA form
 };

@@ -12,6 +12,9 @@ launch on ``torch.cuda.current_stream()`` at each call, so construction and look
 ``x`` one tensor or up to three read in place of their ``cat``.
 ``UpdateBlock.from_state_dict(state, "update_block.")`` is called like the reference's module, ``(net, inp, correlation, flow) ->
 (new_net, mask, delta_flow)``, in 13 launches with no ``cat``.
+``FeatureEncoder`` / ``ContextEncoder`` (encoder.py:25-68) run their 17 / 18 layers on the same kernel family with a stride, a residual
+epilogue and BatchNorm folded into the weights once, and ``Raft.from_state_dict(state, levels, radius)(ref_image, cur_image)`` is
+model.py:66-97: the whole forward pass, the list of flow predictions, with every convolution on these kernels.
 Inference only, float32 only, and no CPU fallback.
 """
 from __future__ import annotations
@@ -480,3 +483,282 @@ class UpdateBlock:
         delta_flow = _conv(ctx, [_conv(ctx, [new_net], L["flow_head.conv1"], True)], L["flow_head.conv2"], False)
         mask = _conv(ctx, [_conv(ctx, [new_net], L["mask.0"], True)], L["mask.2"], False, 0.25)
         return new_net, mask, delta_flow
+
+
+# ---- the encoders and the whole model (encoder.py:4-68, model.py:6-97) --------------------------------------------
+
+BN_EPS = 1e-5  # nn.BatchNorm2d's default; the module stores none
+
+
+def _fold_batch_norm(state: Mapping, conv_key: str, bn_prefix: str, eps: float):
+    """``conv`` (no bias) followed by ``BatchNorm2d`` in eval mode as one layer: s = gamma / sqrt(var + eps), w' = w * s, b' = beta - mean * s,
+    on the host in numpy float32, every operation rounded once.  ``num_batches_tracked`` is read and ignored.  Returns
+    (w', b') on the weights' device."""
+    import numpy as np
+    import torch
+
+    w = _state_tensor(state, conv_key, 4)
+    if w.dtype != torch.float32:
+        raise ValueError(f"{conv_key} must be a float32 tensor (got {w.dtype} {list(w.shape)})")
+    M = int(w.size(0))
+    bn = {}
+    for kind in ("weight", "bias", "running_mean", "running_var"):
+        key = bn_prefix + kind
+        t = _state_tensor(state, key)
+        if t.dtype != torch.float32 or tuple(t.shape) != (M,):
+            raise ValueError(f"{key} must be a float32 tensor of shape {[M]} (got {t.dtype} {list(t.shape)})")
+        if t.device != w.device:
+            raise ValueError(f"{key} is on {t.device}, the other weights on {w.device}")
+        bn[kind] = t.detach().cpu().numpy()
+    _state_tensor(state, bn_prefix + "num_batches_tracked")
+    # numpy, not torch: its float32 division and square root are the correctly rounded scalar ones on every CPU, which torch's vectorised
+    # sqrt is not on every host (it has differed from sqrtf in the last bit)
+    with np.errstate(all="ignore"):
+        shifted = bn["running_var"] + np.float32(eps)
+        if not bool((shifted > 0).all()):
+            raise ValueError(f"{bn_prefix}running_var + eps must be positive (smallest: {float(shifted.min())})")
+        scale = bn["weight"] / np.sqrt(shifted)
+        if not bool(np.isfinite(scale).all()):
+            raise ValueError(f"{bn_prefix}weight / sqrt({bn_prefix}running_var + eps) is not finite")
+        folded_w = torch.from_numpy(w.detach().cpu().numpy() * scale.reshape(M, 1, 1, 1))
+        folded_b = torch.from_numpy(bn["bias"] - bn["running_mean"] * scale)
+    return folded_w.to(w.device), folded_b.to(w.device)
+
+
+def _strided_conv(ctx, x, layer, stride: int, relu: bool, residual=None, normalise: bool = False):
+    """One launch over a checked, contiguous ``x``; ``layer`` = (packed weights, bias, kernel_size, out_channels).  Returns a new tensor."""
+    torch = D._torch()
+    weights, bias, ks, M = layer
+    B, _, H, W = x.shape
+    out = torch.empty((B, M, -(-H // stride), -(-W // stride)), dtype=torch.float32, device=x.device)
+    D.conv2d_strided_device(ctx, [x], weights, bias, ks, stride, relu, 1.0, residual, normalise, out)
+    return out
+
+
+class FeatureEncoder:
+    """encoder.py:25-55: ``conv_in`` (7 x 7, bias, ReLU), three pairs of ``ResNetBlock`` (the second of each pair at stride 2 with a
+    projecting 1 x 1 shortcut) and ``conv_out`` (3 x 3, bias, ReLU): [B, in_channels, H, W] -> [B, out_channels, ~H/8, ~W/8] in 17 launches
+    of raft_conv_kernels.hip.  Every BatchNorm is folded into its convolution once, at construction; a block is ``relu(conv1')``, the
+    shortcut (``x`` itself, or ``shortcut'(x)``) and ``relu(conv2'(t) + shortcut)`` with the add in conv2's epilogue.  ``normalise=True``
+    applies model.py:70-71 to the image as conv_in fetches it.  Not an nn.Module; ``self.weights`` holds the state dict's tensors under the
+    reference's names."""
+
+    BLOCKS = tuple((f"resnet_{k}.{i}", 1 + i) for k in (1, 2, 3) for i in (0, 1))  # (name, stride): encoder.py:33-44
+
+    def __init__(self, state: Mapping, prefix: str = "", eps: float = BN_EPS, _split=None):
+        import torch
+
+        self.eps = float(eps)
+        if not 0 <= self.eps < float("inf"):
+            raise ValueError(f"eps must be a finite non-negative number (got {eps})")
+        names = set(state.keys()) if hasattr(state, "keys") else set()
+        taken: Dict[str, object] = {}
+        convs: Dict[str, tuple] = {}  # layer -> (w', b')
+
+        def take(key):
+            taken[key[len(prefix):]] = _state_tensor(state, key).detach()
+
+        def plain(layer, ks):
+            w = _state_tensor(state, f"{prefix}{layer}.weight", 4)
+            M, Cin = int(w.size(0)), int(w.size(1))
+            for kind, shape in (("weight", (M, Cin, ks, ks)), ("bias", (M,))):
+                key = f"{prefix}{layer}.{kind}"
+                t = _state_tensor(state, key)
+                if t.dtype != torch.float32 or tuple(t.shape) != shape:
+                    raise ValueError(f"{key} must be a float32 tensor of shape {list(shape)} (got {t.dtype} {list(t.shape)})")
+                take(key)
+            convs[layer] = (taken[f"{layer}.weight"], taken[f"{layer}.bias"])
+            return M, Cin
+
+        def folded(conv, bn, ks, Cin, M=None):
+            w = _state_tensor(state, f"{prefix}{conv}.weight", 4)
+            M = int(w.size(0)) if M is None else M
+            if tuple(w.shape) != (M, Cin, ks, ks):
+                raise ValueError(f"{prefix}{conv}.weight must be a float32 tensor of shape {[M, Cin, ks, ks]} (got {w.dtype} {list(w.shape)})")
+            convs[conv] = _fold_batch_norm(state, f"{prefix}{conv}.weight", f"{prefix}{bn}.", self.eps)
+            take(f"{prefix}{conv}.weight")
+            for kind in ("weight", "bias", "running_mean", "running_var", "num_batches_tracked"):
+                take(f"{prefix}{bn}.{kind}")
+            return M
+
+        width, self.in_channels = plain("conv_in.0", 7)
+        self.blocks = []  # (name, stride, has a shortcut)
+        for name, stride in self.BLOCKS:
+            M = folded(f"{name}.conv1", f"{name}.bn1", 3, width)
+            folded(f"{name}.conv2", f"{name}.bn2", 3, M, M)
+            shortcut = any(k.startswith(f"{prefix}{name}.shortcut.") for k in names) or stride != 1 or M != width
+            if shortcut:
+                folded(f"{name}.shortcut.0", f"{name}.shortcut.1", 1, width, M)
+            self.blocks.append((name, stride, shortcut))
+            width = M
+        self.out_channels, last_in = plain("conv_out.0", 3)
+        if last_in != width:
+            raise ValueError(f"{prefix}conv_out.0.weight must be a float32 tensor of shape {[self.out_channels, width, 3, 3]} (got "
+                             f"{list(taken['conv_out.0.weight'].shape)})")
+        devices = {str(t.device) for t in taken.values() if t.dtype == torch.float32}
+        if len(devices) != 1:
+            raise ValueError(f"the weights under {prefix!r} are on several devices: {sorted(devices)}")
+        for layer, (w, b) in convs.items():
+            M, Cin, ks = int(w.size(0)), int(w.size(1)), int(w.size(2))
+            if not 1 <= M <= N.FTK_CONV2D_MAX_OUT_CHANNELS or not 1 <= Cin <= N.FTK_CONV2D_MAX_IN_CHANNELS:
+                raise ValueError(f"{prefix}{layer}.weight: {Cin} -> {M} channels is outside 1 .. {N.FTK_CONV2D_MAX_IN_CHANNELS} -> 1 .. "
+                                 f"{N.FTK_CONV2D_MAX_OUT_CHANNELS}")
+        self.weights = taken
+        self.folded = convs
+        self._split = None
+        self._layers = {layer: (_pack_conv(w), b.contiguous(), int(w.size(2)), int(w.size(0))) for layer, (w, b) in convs.items()}
+        if _split is not None:  # ContextEncoder: conv_out as two launches over the two row ranges of its weight matrix
+            w, b = convs["conv_out.0"]
+            if not 0 < _split < self.out_channels:
+                raise ValueError(f"context_channels {_split} must be in 1 .. {self.out_channels - 1}: {prefix}conv_out.0.weight has {self.out_channels} "
+                                 "output channels for context and hidden together")
+            self._split = int(_split)
+            del self._layers["conv_out.0"]
+            self._layers["conv_out.0[context]"] = (_pack_conv(w[:_split]), b[:_split].contiguous(), 3, int(_split))
+            self._layers["conv_out.0[hidden]"] = (_pack_conv(w[_split:]), b[_split:].contiguous(), 3, self.out_channels - int(_split))
+
+    @classmethod
+    def from_state_dict(cls, state: Mapping, prefix: str = "", eps: float = BN_EPS):
+        """From a state dict of the reference's module, or a whole ``Raft``'s with ``prefix="feature_encoder."``.  All sizes are read off the
+        weights and whether a block has a shortcut off the keys; a missing, misshapen or mistyped tensor is a ValueError that names its key."""
+        return cls(state, prefix, eps)
+
+    def _weights_device(self):
+        return next(iter(self._layers.values()))[0].device
+
+    def _trunk(self, ctx, image, normalise: bool):
+        L = self._layers
+        x = _strided_conv(ctx, image, L["conv_in.0"], 1, True, normalise=normalise)
+        for name, stride, shortcut in self.blocks:
+            t = _strided_conv(ctx, x, L[f"{name}.conv1"], stride, True)
+            r = _strided_conv(ctx, x, L[f"{name}.shortcut.0"], stride, False) if shortcut else x
+            x = _strided_conv(ctx, t, L[f"{name}.conv2"], 1, True, residual=r)
+        return x
+
+    def _check(self, what, image):
+        _check_maps(what, [("image", image, self.in_channels)], self._weights_device())
+        return _device_context(image), image.contiguous()
+
+    def __call__(self, image, normalise: bool = False):
+        """``FeatureEncoder.forward``: a float32 CUDA tensor [B, in_channels, H, W] gives a new [B, out_channels, h, w] tensor, h = H halved
+        three times, each time rounded up.  Checked before the first launch; nothing passed in is modified."""
+        ctx, image = self._check("FeatureEncoder", image)
+        return _strided_conv(ctx, self._trunk(ctx, image, normalise), self._layers["conv_out.0"], 1, True)
+
+
+class ContextEncoder:
+    """encoder.py:57-68: a FeatureEncoder of ``context_channels + hidden_channels`` output channels whose result is split into ``(context,
+    hidden)`` = model.py:80's ``(inp, net)``.  Both come out dense with no copy pass: conv_out runs as two launches over the two row ranges
+    of its weight matrix (output channels are independent: bit-identical to the split), 18 launches in all.  The module's weights hold only
+    the sum of the two widths, so ``context_channels`` is an argument."""
+
+    def __init__(self, state: Mapping, prefix: str = "", context_channels: int = None, eps: float = BN_EPS):
+        if context_channels is None or int(context_channels) < 1:
+            raise ValueError(f"context_channels must be given and positive (got {context_channels}): the weights hold only context + hidden")
+        self.net = FeatureEncoder(state, prefix + "net.", eps, _split=int(context_channels))
+        self.context_channels = int(context_channels)
+        self.hidden_channels = self.net.out_channels - self.context_channels
+        self.weights = {"net." + k: v for k, v in self.net.weights.items()}
+
+    @classmethod
+    def from_state_dict(cls, state: Mapping, prefix: str = "", context_channels: int = None, eps: float = BN_EPS):
+        """From a state dict of the reference's module, or a whole ``Raft``'s with ``prefix="context_encoder."``."""
+        return cls(state, prefix, context_channels, eps)
+
+    def __call__(self, image, normalise: bool = False):
+        """``ContextEncoder.forward``: ``(context, hidden)``, new contiguous tensors [B, context_channels, h, w] and [B, hidden_channels, h, w]."""
+        ctx, image = self.net._check("ContextEncoder", image)
+        x = self.net._trunk(ctx, image, normalise)
+        L = self.net._layers
+        return _strided_conv(ctx, x, L["conv_out.0[context]"], 1, True), _strided_conv(ctx, x, L["conv_out.0[hidden]"], 1, True)
+
+
+class Raft:
+    """model.py:6-97: ``raft(ref_image, cur_image)`` returns the reference's list of flow predictions [B, 2, 8h, 8w], one per iteration.
+    The feature encoder runs once over the two images stacked along B (17 launches), the context encoder on the reference image (18), both
+    normalising the raw image at conv_in's fetch, and the correlation pyramid is built (1 launch up to four levels); then per iteration one lookup, UpdateBlock's 13 launches and one upsampling launch.
+    What stays torch: the stack of the two raw images, the meshgrid, and the three [B, 2, h, w] element-wise operations of model.py:90-94,
+    kept as written (``(cur + delta) - ref`` is not ``flow + delta`` in float32)."""
+
+    def __init__(self, feature_encoder: FeatureEncoder, context_encoder: ContextEncoder, update_block: UpdateBlock, correlation_pyramid_levels: int,
+                 correlation_radius: int, max_iterations: int = 12):
+        levels, radius = int(correlation_pyramid_levels), int(correlation_radius)
+        if not 1 <= levels <= N.FTK_CORR_MAX_LEVELS or not 0 <= radius <= N.FTK_CORR_MAX_RADIUS:
+            raise ValueError(f"correlation_pyramid_levels {correlation_pyramid_levels} outside 1 .. {N.FTK_CORR_MAX_LEVELS} or correlation_radius "
+                             f"{correlation_radius} outside 0 .. {N.FTK_CORR_MAX_RADIUS}")
+        width = levels * (2 * radius + 1) ** 2
+        if update_block.motion_encoder.correlation_in != width:
+            raise ValueError(f"the update block takes {update_block.motion_encoder.correlation_in} correlation channels, but {levels} levels of radius "
+                             f"{radius} give levels * (2 * radius + 1) ** 2 = {width}")
+        if int(max_iterations) < 1:
+            raise ValueError(f"max_iterations {max_iterations} must be at least 1")
+        if update_block.mask_channels != 576:
+            raise ValueError(f"the update block's mask has {update_block.mask_channels} channels: the upsampling takes 8 * 8 * 9 = 576")
+        if (context_encoder.context_channels, context_encoder.hidden_channels) != (update_block.inp_channels, update_block.net_channels):
+            raise ValueError(f"the context encoder gives {context_encoder.context_channels} + {context_encoder.hidden_channels} channels, the update "
+                             f"block takes inp {update_block.inp_channels} + net {update_block.net_channels}")
+        if feature_encoder.in_channels != context_encoder.net.in_channels:
+            raise ValueError(f"the feature encoder takes {feature_encoder.in_channels} image channels, the context encoder {context_encoder.net.in_channels}")
+        self.feature_encoder, self.context_encoder, self.update_block = feature_encoder, context_encoder, update_block
+        self.correlation_pyramid_levels, self.correlation_radius, self.max_iterations = levels, radius, int(max_iterations)
+        self.hidden_dim, self.context_dim = update_block.net_channels, update_block.inp_channels
+        self.weights: Dict[str, object] = {"feature_encoder." + k: v for k, v in feature_encoder.weights.items()}
+        self.weights.update({"context_encoder." + k: v for k, v in context_encoder.weights.items()})
+        self.weights.update({"update_block." + k: v for k, v in update_block.weights.items()})
+
+    @classmethod
+    def from_state_dict(cls, state: Mapping, correlation_pyramid_levels: int, correlation_radius: int, max_iterations: int = 12, eps: float = BN_EPS):
+        """From ``Raft(...).state_dict()`` of the reference.  All widths are read off the weights; the context encoder's split is the update
+        block's ``inp`` and ``net`` widths.  The two correlation arguments are not in the state dict: they must give the update block's
+        correlation width, levels * (2 * radius + 1) ** 2."""
+        block = UpdateBlock.from_state_dict(state, "update_block.")
+        features = FeatureEncoder.from_state_dict(state, "feature_encoder.", eps)
+        out = _state_tensor(state, "context_encoder.net.conv_out.0.weight", 4)
+        if int(out.size(0)) != block.inp_channels + block.net_channels:
+            raise ValueError(f"context_encoder.net.conv_out.0.weight has {int(out.size(0))} output channels, the update block takes inp "
+                             f"{block.inp_channels} + net {block.net_channels}")
+        context = ContextEncoder.from_state_dict(state, "context_encoder.", block.inp_channels, eps)
+        devices = {str(features._weights_device()), str(context.net._weights_device()), str(block.motion_encoder._weights_device())}
+        if len(devices) != 1:
+            raise ValueError(f"the weights are on several devices: {sorted(devices)}")
+        return cls(features, context, block, correlation_pyramid_levels, correlation_radius, max_iterations)
+
+    def __call__(self, ref_image, cur_image, iterations: int = None):
+        """``Raft.forward``: float32 CUDA images [B, in_channels, H, W] in 0 .. 255 give ``iterations`` (default ``max_iterations``) new
+        tensors [B, 2, 8h, 8w], h = H halved three times rounding up (a 60 x 60 image gives 64 x 64; nothing is cropped).  Every argument
+        is checked before the first launch; on torch's current stream, capturable at fixed shapes."""
+        import torch
+
+        n = self.max_iterations if iterations is None else int(iterations)
+        if n < 1:
+            raise ValueError(f"iterations {iterations} must be at least 1")
+        enc = self.feature_encoder
+        for name, t in (("ref_image", ref_image), ("cur_image", cur_image)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 4 or t.size(1) != enc.in_channels:
+                got = f"{t.dtype} {list(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
+                raise ValueError(f"{name} must be a 4-D float32 CUDA tensor [B, {enc.in_channels}, H, W] (no CPU fallback, no other dtype): got {got}")
+        if ref_image.size() != cur_image.size() or ref_image.device != cur_image.device:
+            raise ValueError(f"The size of the reference and current images should be the same: {tuple(ref_image.shape)} on {ref_image.device} vs "
+                             f"{tuple(cur_image.shape)} on {cur_image.device}")
+        B, _, H, W = (int(e) for e in ref_image.shape)
+        _check_maps("Raft", [("ref_image", ref_image, enc.in_channels), ("cur_image", cur_image, enc.in_channels)], enc._weights_device())
+        h, w = ((((e + 1) // 2 + 1) // 2 + 1) // 2 for e in (H, W))  # three stride-2 layers, each ceil(e / 2)
+        try:
+            N.corr_pyramid_layout(B, h, w, self.correlation_pyramid_levels)
+        except N.FtkError as e:
+            raise ValueError(f"images of {H} x {W} give {h} x {w} feature maps, too small for {self.correlation_pyramid_levels} correlation levels: "
+                             f"{e}") from None
+        features = enc(torch.cat([ref_image, cur_image], dim=0), normalise=True)
+        pyramid = CorrelationPyramid(features[:B], features[B:], self.correlation_pyramid_levels, self.correlation_radius)
+        inp, net = self.context_encoder(ref_image, normalise=True)
+        ys, xs = torch.meshgrid(torch.arange(h, device=ref_image.device), torch.arange(w, device=ref_image.device), indexing="ij")
+        ref = torch.stack([xs, ys], dim=0).float()[None].repeat(B, 1, 1, 1)  # InitializeFlow, model.py:34-45: x in channel 0
+        cur = ref
+        predictions = []
+        for _ in range(n):
+            correlation = pyramid.lookup(cur)
+            flow = cur - ref
+            net, mask, delta = self.update_block(net, inp, correlation, flow)
+            cur = cur + delta
+            predictions.append(upsample_flow(cur - ref, mask))
+        return predictions

@@ -453,6 +453,28 @@ int ftk_conv2d_packed_elements(int32_t out_channels, int32_t in_channels, int32_
 int ftk_conv2d_device(ftk_context *ctx, void *stream, const ftk_gru_part *parts, int32_t n_parts, const float *d_weights, const float *d_bias,
                       int32_t out_channels, int32_t kernel_size, int32_t relu, float out_scale, int32_t B, int32_t H, int32_t W, float *d_out);
 
+/* ---- RAFT's encoders (src/nn_optical_flow_tracker/raft/encoder.py:4-68) ------------------------------------------- */
+
+/*
+ * The layers of FeatureEncoder / ContextEncoder are the layer above with three additions.  BatchNorm (eval mode) is no addition: the
+ * caller folds it into the weights and the bias once (s = gamma / sqrtf(var + eps), w' = w * s, b' = beta - mean * s).
+ *  - stride 1 or 2 (2: kernel sizes 1 and 3 only): the input is [B][in_channels][H][W], the output [B][out_channels][ceil(H / stride)]
+ *    [ceil(W / stride)], the tap of output (y, x) is in[c][stride * y + ty - pad][stride * x + tx - pad], outside the image a multiplied +0.
+ *  - d_residual (may be NULL): a dense tensor of the output's shape; v = acc + residual[co][y][x], one rounded add, BEFORE the ReLU
+ *    (encoder.py:21-22); then ReLU and out_scale as above.
+ *  - normalise != 0: every in-image input value x is read as 2.0f * (x / 255.0f) - 1.0f (model.py:70-71: one rounded division, an exact
+ *    doubling, one rounded subtraction); the zero padding stays +0, which is why this is no change of the weights.
+ * Limits as ftk_conv2d_device; any other stride, or stride 2 with kernel_size 7, is FTK_E_UNSUPPORTED and launches nothing.  The packed
+ * weights are ftk_conv2d_device's (the stride changes neither the layout nor the chunk).  stride 1 with no residual and normalise == 0
+ * is ftk_conv2d_device itself.
+ * Replaces, per call: encoder.py:16-18 (conv1, bn1, ReLU: stride as the block's, relu); :21's shortcut (:12-13: 1 x 1, the block's
+ * stride, its BatchNorm, no ReLU); :19-22 (conv2, bn2, the add of the shortcut as d_residual, ReLU); :30-31 (conv_in, 7 x 7, normalise);
+ * :46-47 (conv_out).  d_out must not alias an input or the residual.  One launch on `stream`, no allocation, no synchronisation: capturable.
+ */
+int ftk_conv2d_strided_device(ftk_context *ctx, void *stream, const ftk_gru_part *parts, int32_t n_parts, const float *d_weights, const float *d_bias,
+                              int32_t out_channels, int32_t kernel_size, int32_t stride, int32_t relu, float out_scale, const float *d_residual,
+                              int32_t normalise, int32_t B, int32_t H, int32_t W, float *d_out);
+
 /* ---- features sharded over the GPUs of one node ------------------------ */
 
 /*

@@ -1,0 +1,605 @@
+"""RAFT's encoders and whole forward pass without a device: the scalar restatement (tests/raft_encoder_ref.c and the networks
+tests/raft_encoder_ref.py composes from it and the other restatements) pinned against an independent float64 composition
+of encoder.py and model.py (torch.nn.functional.conv2d / batch_norm / relu in float64, written out below), nine mutants of the
+restatement that the same bounds must reject, a golden fixture recorded from the reference's own ``Raft``, known answers that need no
+float64 side, the loud failures of the Python entries before any device is touched, and the strided launch plan through its
+command-line tool.
+
+Measured (printed by the tests, -s shows them), the largest absolute difference restatement - float64 over the cases x MEASURED_SEEDS:
+encoders 8.17e-07, whole model 1.07e-06 (predictions of up to 5 pixels); the bounds are 4 x these."""
+import functools
+import itertools
+import os
+import subprocess
+import types
+
+import numpy as np
+import pytest
+
+from tests import raft_encoder_ref as E
+
+torch = pytest.importorskip("torch")
+
+from tests.test_flow_upsample_cpu import torch_upsample  # noqa: E402
+from tests.test_raft_corr_cpu import torch_lookup, torch_pyramid  # noqa: E402
+from tests.test_update_block_cpu import layer_shapes as block_layer_shapes  # noqa: E402
+from tests.test_update_block_cpu import make_state as make_block_state  # noqa: E402
+from tests.test_update_block_cpu import torch_forward as block_torch_forward  # noqa: E402
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PLAN_CLI = os.path.join(ROOT, "feature_tracker_amd", "host", "build", "raft_conv_plan_cli")
+GOLDEN = os.path.join(ROOT, "tests", "golden", "raft", "raft_model_small.npz")
+
+# (out_channels, B, H, W): channel steps of 2, 3 (odd) and the reference's 32; even, odd and one-pixel images
+ENCODER_CASES = [(8, 2, 16, 24), (12, 1, 9, 13), (12, 2, 1, 1), (8, 1, 9, 13), (128, 1, 16, 24), (128, 1, 1, 1)]
+# (hidden, feature, context, levels, radius, corr_hidden, corr_out, flow_hidden, flow_out, motion_out, mask_hidden; B, H, W, iterations): tiny
+# widths twice, then model.py:105-117's.  One correlation level everywhere: a 2 x 3 or 3 x 3 feature map has no second one that is not a
+# single pixel, whose lookup is NaN in the reference (tests/test_raft_corr_cpu.py).
+RAFT_CASES = [(8, 12, 4, 1, 1, 8, 6, 8, 4, 10, 8, 1, 16, 24, 2), (5, 8, 7, 1, 2, 7, 5, 6, 3, 9, 5, 2, 17, 23, 3),
+              (64, 128, 128, 1, 3, 64, 32, 32, 16, 32, 64, 1, 24, 24, 2)]
+MEASURED_SEEDS = (1, 2, 3, 4)
+FIFTH_SEED = 5
+# The mutants are judged at these two of the measured seeds.  Not at seed 1: its 12-channel net on a one-pixel image and its tiny model
+# have dead border channels, where a padding of -1 moves the result by 3.9e-08 and 1.3e-06, less than the bounds: a net that cannot see
+# its padding cannot tell the mutant (seeds 2, 3 and 4 all can, on every case).
+MUTANT_SEEDS = (2, 3)
+# max |restatement - float64| over the cases x MEASURED_SEEDS, and the asserted bounds: 4 x them, for other seeds
+ENCODER_MEASURED_MAX_ABS = 8.17e-07
+RAFT_MEASURED_MAX_ABS = 1.07e-06
+ENCODER_BOUND = 4 * ENCODER_MEASURED_MAX_ABS
+RAFT_BOUND = 4 * RAFT_MEASURED_MAX_ABS
+
+
+def make_encoder_state(in_channels, out_channels, seed, prefix=""):
+    """The reference module's layers (encoder.py:4-48) at torch's default initialisation, seeded, with every BatchNorm's gamma, beta, running
+    mean and running variance randomised (the defaults 1, 0, 0, 1 would let a wrong fold pass).  The first variance of every BatchNorm is
+    near 0 (1e-6, with a small gamma so that the channel stays of ordinary size): there eps decides the scale."""
+    g = torch.Generator().manual_seed(3000 + seed)
+    torch.manual_seed(300 + seed)
+    step = out_channels // 4
+    state = {}
+
+    def conv(name, Cin, M, ks, bias):
+        c = torch.nn.Conv2d(Cin, M, ks, bias=bias)
+        state[f"{prefix}{name}.weight"] = c.weight.detach().clone()
+        if bias:
+            state[f"{prefix}{name}.bias"] = c.bias.detach().clone()
+
+    def bn(name, M):
+        state[f"{prefix}{name}.weight"] = 0.5 + torch.rand(M, generator=g)
+        state[f"{prefix}{name}.bias"] = 0.3 * torch.randn(M, generator=g)
+        state[f"{prefix}{name}.running_mean"] = 0.5 * torch.randn(M, generator=g)
+        state[f"{prefix}{name}.running_var"] = 0.5 + torch.rand(M, generator=g)
+        state[f"{prefix}{name}.num_batches_tracked"] = torch.tensor(7)
+
+    conv("conv_in.0", in_channels, step, 7, True)
+    width = step
+    for (name, stride), M in zip(E.BLOCKS, (step, 2 * step, 2 * step, 3 * step, 3 * step, out_channels)):
+        conv(f"{name}.conv1", width, M, 3, False)
+        bn(f"{name}.bn1", M)
+        conv(f"{name}.conv2", M, M, 3, False)
+        bn(f"{name}.bn2", M)
+        if stride != 1 or width != M:
+            conv(f"{name}.shortcut.0", width, M, 1, False)
+            bn(f"{name}.shortcut.1", M)
+        width = M
+    conv("conv_out.0", out_channels, out_channels, 3, True)
+    for key in [k for k in state if k.endswith("running_var")]:
+        state[key][0] = 1e-6
+        state[key[:-len("running_var")] + "weight"][0] = 0.004
+    return state
+
+
+def make_image(B, C, H, W, seed):
+    """Whole-number pixels in 0 .. 255."""
+    g = torch.Generator().manual_seed(4000 + seed)
+    return torch.floor(256.0 * torch.rand(B, C, H, W, generator=g)).clamp(0, 255)
+
+
+def torch_encoder(state, image, prefix="", dtype=torch.float64):
+    """encoder.py:15-23 and :49-55, line by line, in ``dtype``."""
+    F = torch.nn.functional
+    g = lambda k: state[prefix + k].to(dtype)  # noqa: E731
+
+    def bn(x, name):
+        return F.batch_norm(x, g(name + ".running_mean"), g(name + ".running_var"), g(name + ".weight"), g(name + ".bias"), training=False, eps=1e-5)
+
+    x = F.relu(F.conv2d(image.to(dtype), g("conv_in.0.weight"), g("conv_in.0.bias"), stride=1, padding=3))
+    for name, stride in E.BLOCKS:
+        out = F.relu(bn(F.conv2d(x, g(f"{name}.conv1.weight"), None, stride=stride, padding=1), f"{name}.bn1"))
+        out = bn(F.conv2d(out, g(f"{name}.conv2.weight"), None, stride=1, padding=1), f"{name}.bn2")
+        short = x
+        if f"{prefix}{name}.shortcut.0.weight" in state:
+            short = bn(F.conv2d(x, g(f"{name}.shortcut.0.weight"), None, stride=stride), f"{name}.shortcut.1")
+        x = F.relu(out + short)
+    return F.relu(F.conv2d(x, g("conv_out.0.weight"), g("conv_out.0.bias"), stride=1, padding=1))
+
+
+def block_widths(c):
+    """RAFT_CASES[k] as tests/test_update_block_cpu.py's nine widths (net, inp, corr, corr_hidden, corr_out, flow_hidden, flow_out, motion_out, mask_hidden)."""
+    hidden, _, context, levels, radius = c[:5]
+    return (hidden, context, levels * (2 * radius + 1) ** 2) + tuple(c[5:11])
+
+
+def make_raft_state(c, seed):
+    state = make_encoder_state(1, c[1], seed, "feature_encoder.")
+    state.update(make_encoder_state(1, c[0] + c[2], seed + 50, "context_encoder.net."))
+    state.update({"update_block." + k: v for k, v in make_block_state(block_widths(c), seed).items()})
+    return state
+
+
+def torch_raft(state, ref_image, cur_image, levels, radius, iterations, dtype=torch.float64):
+    """model.py:66-97, line by line, in ``dtype``; the two encoders' hidden width is the update block's."""
+    ref_image = 2.0 * (ref_image.to(dtype) / 255.0) - 1.0
+    cur_image = 2.0 * (cur_image.to(dtype) / 255.0) - 1.0
+    ref_feature = torch_encoder(state, ref_image, "feature_encoder.", dtype)
+    cur_feature = torch_encoder(state, cur_image, "feature_encoder.", dtype)
+    pyramid = torch_pyramid(ref_feature, cur_feature, levels)
+    block = {k[len("update_block."):]: v for k, v in state.items() if k.startswith("update_block.")}
+    hidden = block["flow_head.conv1.weight"].shape[1]
+    x = torch_encoder(state, ref_image, "context_encoder.net.", dtype)
+    inp, net = torch.split(x, [x.shape[1] - hidden, hidden], dim=-3)
+    B, _, h, w = ref_feature.shape
+    grid = torch.meshgrid([torch.arange(h, device=ref_image.device), torch.arange(w, device=ref_image.device)], indexing="ij")
+    ref = torch.stack(grid[::-1], dim=0).to(dtype)[None].repeat(B, 1, 1, 1)
+    cur = ref.clone()
+    predictions = []
+    for _ in range(iterations):
+        correlation = torch_lookup(pyramid, cur, radius).to(dtype)
+        flow = cur - ref
+        net, mask, delta = block_torch_forward(block, net, inp, correlation, flow, dtype)[:3]
+        cur = cur + delta
+        predictions.append(torch_upsample(cur - ref, mask))
+    return predictions
+
+
+@functools.lru_cache(maxsize=None)
+def encoder_case(k, seed):
+    """(state as numpy, image, the float64 reference) of ENCODER_CASES[k] with ``seed``: computed once and shared; nobody writes to them."""
+    M, B, H, W = ENCODER_CASES[k]
+    state = make_encoder_state(1, M, seed)
+    image = make_image(B, 1, H, W, seed)
+    normalised = 2.0 * (image.double() / 255.0) - 1.0
+    return {key: v.numpy() for key, v in state.items()}, image.numpy(), torch_encoder(state, normalised).numpy()
+
+
+@functools.lru_cache(maxsize=None)
+def raft_case(k, seed):
+    c = RAFT_CASES[k]
+    B, H, W, iterations = c[11:]
+    state = make_raft_state(c, seed)
+    ref_image, cur_image = make_image(B, 1, H, W, seed), make_image(B, 1, H, W, seed + 70)
+    ref64 = [p.numpy() for p in torch_raft(state, ref_image, cur_image, c[3], c[4], iterations)]
+    return {key: v.numpy() for key, v in state.items()}, ref_image.numpy(), cur_image.numpy(), ref64
+
+
+def max_abs(got, want):
+    """The largest absolute difference; a missing result or a shape that differs (a mutant's) is infinitely far."""
+    got, want = (list(t) if isinstance(t, (list, tuple)) else [t] for t in (got, want))
+    if len(got) != len(want) or any(g is None or g.shape != w.shape for g, w in zip(got, want)):
+        return float("inf")
+    return max(float(np.abs(g.astype(np.float64) - w.astype(np.float64)).max()) for g, w in zip(got, want))
+
+
+def encoder_restated(k, seed, variant=E.CONTRACT):
+    state, image, _ = encoder_case(k, seed)
+    return E.feature_encoder(image, state, "", True, variant)
+
+
+def raft_restated(k, seed, variant=E.CONTRACT):
+    c = RAFT_CASES[k]
+    state, ref_image, cur_image, _ = raft_case(k, seed)
+    return E.raft(ref_image, cur_image, state, c[3], c[4], c[14], variant)
+
+
+# ---- the restatement against float64, and its mutants ------------------------------------------------------------------------------
+
+
+@pytest.mark.parametrize("k", range(len(ENCODER_CASES)), ids=[str(c) for c in ENCODER_CASES])
+def test_encoder_restatement_against_float64(k):
+    worst = [max_abs(encoder_restated(k, seed), encoder_case(k, seed)[2]) for seed in MEASURED_SEEDS + (FIFTH_SEED,)]
+    print(f"case {ENCODER_CASES[k]}: max |restatement - float64| per seed {['%.3g' % w for w in worst]} (measured maximum {ENCODER_MEASURED_MAX_ABS:.3g}, "
+          f"bound {ENCODER_BOUND:.3g})")
+    assert max(worst[:-1]) <= ENCODER_MEASURED_MAX_ABS * 1.0001, "the recorded maximum is out of date"
+    assert max(worst) <= ENCODER_BOUND
+
+
+@pytest.mark.parametrize("k", range(len(RAFT_CASES)), ids=[str(c) for c in RAFT_CASES])
+def test_raft_restatement_against_float64(k):
+    worst = [max_abs(raft_restated(k, seed), raft_case(k, seed)[3]) for seed in MEASURED_SEEDS + (FIFTH_SEED,)]
+    print(f"case {RAFT_CASES[k]}: max |restatement - float64| per seed {['%.3g' % w for w in worst]} (measured maximum {RAFT_MEASURED_MAX_ABS:.3g}, bound "
+          f"{RAFT_BOUND:.3g})")
+    assert max(worst[:-1]) <= RAFT_MEASURED_MAX_ABS * 1.0001, "the recorded maximum is out of date"
+    assert max(worst) <= RAFT_BOUND
+
+
+def test_the_recorded_maxima_are_current():
+    enc = max(max_abs(encoder_restated(k, seed), encoder_case(k, seed)[2]) for k in range(len(ENCODER_CASES)) for seed in MEASURED_SEEDS)
+    whole = max(max_abs(raft_restated(k, seed), raft_case(k, seed)[3]) for k in range(len(RAFT_CASES)) for seed in MEASURED_SEEDS)
+    print(f"max |restatement - float64|: encoders {enc:.3g}, whole model {whole:.3g}")
+    assert 0.9 * ENCODER_MEASURED_MAX_ABS <= enc <= 1.0001 * ENCODER_MEASURED_MAX_ABS
+    assert 0.9 * RAFT_MEASURED_MAX_ABS <= whole <= 1.0001 * RAFT_MEASURED_MAX_ABS
+
+
+def mutant_applies(name, case, whole):
+    """Where a mutant is the contract itself it cannot be told apart: the floor of the output size on sizes that stay even through all three
+    halvings, and a tap or size rule of stride 2 ... never: every case has stride-2 layers.  ``ref + delta`` exists in the model alone."""
+    H, W = case[12:14] if whole else case[2:4]
+    if name == "output size floor(H / 2)":
+        return H % 8 != 0 or W % 8 != 0
+    if name == "ref + delta instead of cur + delta":
+        return whole
+    return True
+
+
+@pytest.mark.parametrize("name", sorted(E.MUTANTS))
+def test_mutants_fail_the_float64_bounds(name):
+    worst = []
+    for seed in MUTANT_SEEDS:
+        for k, c in enumerate(ENCODER_CASES):
+            if mutant_applies(name, c, False):
+                worst.append((max_abs(encoder_restated(k, seed, E.MUTANTS[name]), encoder_case(k, seed)[2]), ENCODER_BOUND))
+        for k, c in enumerate(RAFT_CASES):
+            if mutant_applies(name, c, True):
+                worst.append((max_abs(raft_restated(k, seed, E.MUTANTS[name]), raft_case(k, seed)[3]), RAFT_BOUND))
+    print(f"mutant {name}: {['%.3g' % w for w, _ in worst]} (bounds {ENCODER_BOUND:.3g}, {RAFT_BOUND:.3g})")
+    assert len(worst) >= 3 and all(w > bound for w, bound in worst)  # on every case where the mutant is not the contract itself
+
+
+# ---- the golden fixture: the reference's own Raft on torch CPU (tests/golden/make_raft_model.py) -----------------------------------
+
+
+def test_golden_fixture_of_the_reference_model():
+    import feature_tracker_amd as F
+    assert os.path.getsize(GOLDEN) < 100 * 1000
+    z = np.load(GOLDEN)
+    state = {k[len("state/"):]: z[k] for k in z.files if k.startswith("state/")}
+    sizes = [int(e) for e in z["sizes"]]
+    hidden, feature, context, levels, radius = sizes[1:6]
+    B, H, W = sizes[13:]
+    assert (B, H, W, sizes[12]) == (1, 16, 24, 2)
+    # exactly the module's key names: ours reads every one of them and asks for no other
+    block = block_layer_shapes(hidden, context, levels * (2 * radius + 1) ** 2, *sizes[6:12])
+    expect = set(E.encoder_keys("feature_encoder.")) | set(E.encoder_keys("context_encoder.net."))
+    expect |= {f"update_block.{k}.{kind}" for k in block for kind in ("weight", "bias")}
+    expect |= {f"update_block.gru.conv_{g}_{d}.{kind}" for g in "zrq" for d in ("horizontal", "vertical") for kind in ("weight", "bias")}
+    assert set(state) == expect
+    model = F.Raft.from_state_dict({k: torch.from_numpy(v) for k, v in state.items()}, levels, radius, max_iterations=2)
+    assert set(model.weights) == set(state)
+    assert (model.hidden_dim, model.context_dim, model.feature_encoder.out_channels) == (hidden, context, feature)
+    assert [b[2] for b in model.feature_encoder.blocks] == [False, True] * 3
+    for k in state:  # ... and no other: each one missing is refused by name
+        if k.startswith("update_block."):
+            continue
+        with pytest.raises(ValueError, match=k.replace(".", r"\.") + " is missing"):
+            F.Raft.from_state_dict({n: torch.from_numpy(v) for n, v in state.items() if n != k}, levels, radius)
+    got = E.raft(z["ref_image"], z["cur_image"], state, levels, radius, 2)
+    want = [z["prediction_0"], z["prediction_1"]]
+    assert all(w.dtype == np.float32 and w.shape == (B, 2, H, W) for w in want)
+    print(f"restatement against the reference model's recorded float32 predictions: {max_abs(got, want):.3g} (bound {RAFT_BOUND:.3g})")
+    assert max_abs(got, want) <= RAFT_BOUND
+
+
+# ---- known answers -----------------------------------------------------------------------------------------------------------------
+
+
+@pytest.mark.parametrize("ks", [1, 3])
+@pytest.mark.parametrize("H,W", list(itertools.product(range(1, 6), repeat=2)))
+def test_single_tap_of_stride_2_lands_where_the_contract_says(ks, H, W):
+    """A one-hot image through a one-tap stride-2 kernel: out[y][x] = in[2 y + ty - pad][2 x + tx - pad], exactly +0 elsewhere."""
+    pad = ks // 2
+    OH, OW = -(-H // 2), -(-W // 2)
+    for (ty, tx), (py, px) in itertools.product(itertools.product(range(ks), repeat=2), {(0, 0), (H - 1, W - 1), (H - 1, 0), (0, W - 1), (H // 2, W // 2)}):
+        image = np.zeros((1, 1, H, W), np.float32)
+        image[0, 0, py, px] = 3.0
+        weight = np.zeros((1, 1, ks, ks), np.float32)
+        weight[0, 0, ty, tx] = 1.0
+        want = np.zeros((1, 1, OH, OW), np.float32)
+        for y, x in itertools.product(range(OH), range(OW)):
+            if (2 * y + ty - pad, 2 * x + tx - pad) == (py, px):
+                want[0, 0, y, x] = 3.0
+        got = E.conv2d(image, weight, np.zeros(1, np.float32), 2)
+        assert E.same(got, want), (ty, tx, py, px)
+
+
+def test_output_sizes_are_torchs():
+    for n in range(1, 18):
+        x = torch.zeros(1, 1, n, 18 - n)
+        for ks in (1, 3):
+            want = torch.nn.functional.conv2d(x, torch.zeros(1, 1, ks, ks), stride=2, padding=ks // 2).shape
+            assert E.conv2d(x.numpy(), np.zeros((1, 1, ks, ks), np.float32), np.zeros(1, np.float32), 2).shape == tuple(want) == (1, 1, -(-n // 2), -(-(18 - n) // 2))
+
+
+def test_fold_in_numpy_is_the_fold_in_c_and_in_the_package():
+    import feature_tracker_amd as F
+    state = make_encoder_state(1, 12, 9)
+    enc = F.FeatureEncoder.from_state_dict(state)
+    n = 0
+    for name, _ in E.BLOCKS:
+        for conv, bn in (("conv1", "bn1"), ("conv2", "bn2"), ("shortcut.0", "shortcut.1")):
+            if f"{name}.{conv}.weight" not in state:
+                continue
+            args = [state[f"{name}.{conv}.weight"]] + [state[f"{name}.{bn}.{kind}"] for kind in ("weight", "bias", "running_mean", "running_var")]
+            w, b = E.fold(*args)
+            w_np, b_np = E.fold_numpy(*args)
+            assert E.same(w, w_np) and E.same(b, b_np)
+            ours = enc.folded[f"{name}.{conv}"]
+            assert E.same(ours[0].numpy(), w) and E.same(ours[1].numpy(), b)
+            n += 1
+    assert n == 15
+    assert E.same(E.normalise(np.arange(256, dtype=np.float32)), np.float32(2.0) * (np.arange(256, dtype=np.float32) / np.float32(255.0)) - np.float32(1.0))
+
+
+def test_residual_epilogue_keeps_nan_and_minus_zero():
+    """v = acc + res, then ReLU (not fmaxf), then the scale: a one-tap 1 x 1 layer whose accumulator is the input itself."""
+    x = np.float32([-0.0, np.nan, -3.0, 2.0, 5.0, 0.0]).reshape(1, 1, 1, 6)
+    res = np.float32([-0.0, 1.0, 1.0, -2.0, -7.0, -0.0]).reshape(1, 1, 1, 6)
+    one = np.ones((1, 1, 1, 1), np.float32)
+    out = E.conv2d(x, one, np.float32([-0.0]), 1, res, relu=True, scale=0.5)[0, 0, 0]
+    assert out[0] == 0 and np.signbit(out[0])            # -0 + -0 = -0, and ReLU keeps it
+    assert np.isnan(out[1])
+    assert out[2] == 0 and not np.signbit(out[2])        # relu(-3 + 1) = +0
+    assert out[3] == 0 and not np.signbit(out[3])        # 2 + -2 = +0
+    assert out[4] == 0 and not np.signbit(out[4])        # relu(5 - 7) = +0: the residual is added BEFORE the ReLU
+    assert out[5] == 0 and not np.signbit(out[5])        # fmaf(1, +0, -0) = +0, + -0 = +0
+    late = E.conv2d(x, one, np.float32([-0.0]), 1, res, relu=True, variant=E.MUTANT_RESIDUAL_AFTER_RELU)[0, 0, 0]
+    assert late[4] == -2.0
+    # stride 1 with nothing of the extension is the UpdateBlock's layer
+    from tests import raft_conv_ref
+    rng = np.random.default_rng(5)
+    x, w, b = rng.standard_normal((2, 5, 7, 9)).astype(np.float32), rng.standard_normal((6, 5, 3, 3)).astype(np.float32), rng.standard_normal(6).astype(np.float32)
+    assert E.same(E.conv2d(x, w, b, relu=True, scale=0.25), raft_conv_ref.conv2d(x, w, b, True, 0.25))
+    assert E.same(E.conv2d(x, w, b, residual=np.zeros((2, 6, 7, 9), np.float32) - 0.0, relu=False), raft_conv_ref.conv2d(x, w, b, False))
+
+
+# ---- loud failures, before any device is touched -----------------------------------------------------------------------------------
+
+
+def test_from_state_dict_refuses_by_key():
+    import feature_tracker_amd as F
+    state = make_encoder_state(1, 12, 1)
+    enc = F.FeatureEncoder.from_state_dict(state)
+    assert (enc.in_channels, enc.out_channels, [b[1:] for b in enc.blocks]) == (1, 12, [(1, False), (2, True)] * 3)
+    assert set(enc.weights) == set(state)
+    nested = {"net." + k: v for k, v in state.items()}
+    ctx_enc = F.ContextEncoder.from_state_dict(nested, context_channels=5)
+    assert (ctx_enc.context_channels, ctx_enc.hidden_channels) == (5, 7) and set(ctx_enc.weights) == set(nested)
+    for bad in (None, 0, 12, 13):
+        with pytest.raises(ValueError, match="context_channels"):
+            F.ContextEncoder.from_state_dict(nested, context_channels=bad)
+    zero_var = state["resnet_2.0.bn2.running_var"].clone()
+    zero_var[1] = -1e-5
+    inf_gamma = state["resnet_3.1.shortcut.1.weight"].clone()
+    inf_gamma[0] = float("inf")
+    for key, bad, match in (("conv_in.0.bias", None, r"conv_in\.0\.bias is missing"), ("resnet_1.1.shortcut.0.weight", None, r"resnet_1\.1\.shortcut\.0\.weight is missing"),
+                            ("resnet_2.0.bn1.running_mean", None, r"resnet_2\.0\.bn1\.running_mean is missing"),
+                            ("resnet_3.1.bn2.num_batches_tracked", None, r"resnet_3\.1\.bn2\.num_batches_tracked is missing"),
+                            ("resnet_1.0.conv2.weight", torch.zeros(3, 3, 3, 3).double(), r"resnet_1\.0\.conv2\.weight must be a float32"),
+                            ("resnet_1.0.conv2.weight", torch.zeros(3, 4, 3, 3), r"resnet_1\.0\.conv2\.weight must be .*\[3, 3, 3, 3\]"),
+                            ("conv_in.0.weight", torch.zeros(3, 1, 5, 5), r"conv_in\.0\.weight must be .*\[3, 1, 7, 7\]"),
+                            ("conv_out.0.weight", torch.zeros(12, 11, 3, 3), r"conv_out\.0\.weight must be .*\[12, 12, 3, 3\]"),
+                            ("resnet_2.1.bn1.bias", torch.zeros(8), r"resnet_2\.1\.bn1\.bias must be .*\[9\]"),
+                            ("resnet_2.0.bn2.running_var", zero_var, r"resnet_2\.0\.bn2\.running_var \+ eps must be positive"),
+                            ("resnet_3.1.shortcut.1.weight", inf_gamma, r"resnet_3\.1\.shortcut\.1\.weight / sqrt\(.* is not finite"),
+                            ("resnet_3.0.conv1.weight", torch.zeros(9, 9, 3), r"resnet_3\.0\.conv1\.weight must be a 4-D tensor")):
+        broken = dict(state)
+        if bad is None:
+            del broken[key]
+        else:
+            broken[key] = bad
+        with pytest.raises(ValueError, match=match):
+            F.FeatureEncoder.from_state_dict(broken)
+    # whether a block has a shortcut is read off the keys, under a prefix too: a stride-1 block of one width that carries the shortcut's
+    # keys gets its shortcut (the restatement applies it as well), and one of them missing is then refused by name
+    extra = dict(nested)
+    for kind, v in (("0.weight", 0.3 * torch.ones(3, 3, 1, 1)), ("1.weight", torch.ones(3)), ("1.bias", torch.zeros(3)), ("1.running_mean", torch.zeros(3)),
+                    ("1.running_var", torch.ones(3)), ("1.num_batches_tracked", torch.tensor(1))):
+        extra[f"net.resnet_1.0.shortcut.{kind}"] = v
+    with_shortcut = F.ContextEncoder.from_state_dict(extra, context_channels=5)
+    assert [b[1:] for b in with_shortcut.net.blocks] == [(1, True), (2, True), (1, False), (2, True), (1, False), (2, True)]
+    assert "resnet_1.0.shortcut.0" in with_shortcut.net.folded and set(with_shortcut.weights) == set(extra)
+    image = make_image(1, 1, 9, 13, 1).numpy()
+    plain_out = E.feature_encoder(image, {k: v.numpy() for k, v in nested.items()}, "net.", True)
+    extra_out = E.feature_encoder(image, {k: v.numpy() for k, v in extra.items()}, "net.", True)
+    assert not E.same(plain_out, extra_out)
+    del extra["net.resnet_1.0.shortcut.1.bias"]
+    with pytest.raises(ValueError, match=r"net\.resnet_1\.0\.shortcut\.1\.bias is missing"):
+        F.ContextEncoder.from_state_dict(extra, context_channels=5)
+    c = RAFT_CASES[0]
+    whole = make_raft_state(c, 1)
+    model = F.Raft.from_state_dict(whole, c[3], c[4])
+    assert (model.max_iterations, model.hidden_dim, model.context_dim) == (12, 8, 4) and set(model.weights) == set(whole)
+    with pytest.raises(ValueError, match=r"9 correlation channels, but 2 levels of radius 1 give levels \* \(2 \* radius \+ 1\) \*\* 2 = 18"):
+        F.Raft.from_state_dict(whole, 2, 1)
+    with pytest.raises(ValueError, match=r"context_encoder\.net\.conv_out\.0\.weight has 12 output channels"):
+        F.Raft.from_state_dict({**whole, **make_encoder_state(1, 12, 1, "context_encoder.net."),
+                                **{"update_block." + k: v for k, v in make_block_state((8, 5, 9) + tuple(c[5:11]), 1).items()}}, 1, 1)
+    with pytest.raises(ValueError, match="max_iterations 0"):
+        F.Raft.from_state_dict(whole, c[3], c[4], max_iterations=0)
+
+
+def test_wrappers_refuse_bad_arguments_without_a_device():
+    import feature_tracker_amd as F
+    c = RAFT_CASES[0]
+    model = F.Raft.from_state_dict(make_raft_state(c, 1), c[3], c[4], max_iterations=2)
+    ref, cur = make_image(1, 1, 16, 24, 1), make_image(1, 1, 16, 24, 2)
+    for match, args in (("ref_image must be", (ref.double(), cur)), ("cur_image must be", (ref, cur[0])), ("cur_image must be .*1, H, W", (ref, torch.zeros(1, 3, 16, 24))),
+                        ("ref_image must be", (ref.numpy(), cur)), ("The size of the reference and current images should be the same", (ref, cur[:, :, :15])),
+                        ("ref_image must not be empty", (ref[:, :, :0], cur[:, :, :0])), ("too small for 1 correlation levels|ref_image must not be empty", (ref[:0], cur[:0]))):
+        with pytest.raises(ValueError, match=match):
+            model(*args)
+    with pytest.raises(ValueError, match="iterations 0"):
+        model(ref, cur, iterations=0)
+    for k in range(2):
+        args = [ref, cur]
+        args[k] = args[k].clone().requires_grad_(True)
+        with pytest.raises(RuntimeError, match="Raft is inference only"):
+            model(*args)
+    with pytest.raises(ValueError, match="no CPU fallback"):
+        model(ref, cur)
+    for entry, what in ((model.feature_encoder, "FeatureEncoder"), (model.context_encoder, "ContextEncoder")):
+        with pytest.raises(ValueError, match="image must be .*1, H, W"):
+            entry(torch.zeros(1, 2, 16, 24))
+        with pytest.raises(RuntimeError, match=f"{what} is inference only"):
+            entry(ref.clone().requires_grad_(True))
+        with pytest.raises(ValueError, match="no CPU fallback"):
+            entry(ref)
+
+
+def test_device_entry_refuses_bad_arguments_without_a_device():
+    from feature_tracker_amd import _native as N
+    from feature_tracker_amd import device as D
+    ctx = types.SimpleNamespace(handle=None)
+    x, out = torch.zeros(1, 3, 5, 7), torch.zeros(1, 4, 3, 4)
+    w, b = torch.zeros(N.conv2d_packed_elements(4, 3, 3)), torch.zeros(4)
+    with pytest.raises(ValueError, match="^out must be a CUDA tensor"):
+        D.conv2d_strided_device(ctx, [x], w, b, 3, 2, True, 1.0, None, False, out)
+    for ks, stride, match in ((5, 1, "kernel_size 5"), (7, 2, "stride 2 with kernel_size 7"), (3, 3, "stride 3"), (3, 0, "stride 0")):
+        with pytest.raises(ValueError, match=match):
+            D.conv2d_strided_device(ctx, [x], w, b, ks, stride, True, 1.0, None, False, out)
+    with pytest.raises(ValueError, match="1 .. 3 tensors"):
+        D.conv2d_strided_device(ctx, [x] * 4, w, b, 3, 2, True, 1.0, None, False, out)
+    with pytest.raises(ValueError, match="out_scale must be finite"):
+        D.conv2d_strided_device(ctx, [x], w, b, 3, 2, True, float("inf"), None, False, out)
+
+
+# the walk of tests/test_device_args_cpu.py (duck-typed tensors, a recording stand-in for the native library) over this entry
+WALK_TENSORS = 1 + 2 + 2 + 1  # out, two parts, the packed weights and the bias, the residual
+
+
+def _walk_call(w):
+    from feature_tracker_amd import _native as N
+    from feature_tracker_amd import device as D
+    B, H, W, M, ks = 2, 5, 7, 40, 3
+    out = w.t("out", "float32", B, M, 3, 4)
+    parts = [w.t(f"parts[{i}]", "float32", B, c, H, W) for i, c in enumerate((3, 6))]
+    weights = w.t("packed_weights", "float32", N.conv2d_packed_elements(M, 9, ks))
+    bias = w.t("bias", "float32", M)
+    residual = w.t("residual", "float32", B, M, 3, 4)
+    return D.conv2d_strided_device(w.ctx, parts, weights, bias, ks, 2, True, 1.0, residual, False, out)
+
+
+def test_device_entry_takes_no_pointer_of_an_unchecked_argument(monkeypatch):
+    from tests.test_device_args_cpu import _Walk
+    w = _Walk(monkeypatch)
+    _walk_call(w)
+    assert w.unchecked_reads == []
+    assert w.lib.calls == ["ftk_conv2d_strided_device"]
+    assert len(w.made) == WALK_TENSORS and [f.name for f in w.made if f.reads != 1] == []
+
+
+@pytest.mark.parametrize("which", range(WALK_TENSORS))
+@pytest.mark.parametrize("kind", ["dtype", "shape", "device"])
+def test_device_entry_stops_before_the_library(monkeypatch, which, kind):
+    """Each tensor of the call in turn made float64, one element longer in its last dimension, or moved to another device."""
+    from tests.test_device_args_cpu import _FakeDevice, _FakeDtype, _Walk
+    w = _Walk(monkeypatch)
+    real_t, count, name = w.t, [0], [None]
+
+    def t(n, dtype, *shape):
+        fake = real_t(n, dtype, *shape)
+        if count[0] == which:
+            name[0] = n
+            if kind == "dtype":
+                fake.dtype = _FakeDtype("float64")
+            elif kind == "shape":
+                fake.shape = fake.shape[:-1] + (fake.shape[-1] + 1,)
+            else:
+                fake.device = _FakeDevice(1)
+        count[0] += 1
+        return fake
+
+    w.t = t
+    with pytest.raises(ValueError) as e:
+        _walk_call(w)
+    if not (kind == "shape" and name[0] in ("out", "parts[0]")):  # a wider out or first part is a legal one: the tensor that disagrees with it is refused
+        assert name[0] in str(e.value), (name[0], str(e.value))
+    assert w.lib.calls == [] and w.unchecked_reads == []
+
+
+# ---- the launch plan ---------------------------------------------------------------------------------------------------------------
+
+LDS_LIMIT = 64 * 1024
+PLAN_FIELDS = ("out_channels", "in_channels", "kernel_size", "B", "H", "W", "stride")
+
+
+def plan(cases):
+    assert os.path.exists(PLAN_CLI), "host layer not built (python -c 'import __graft_entry__ as g; g.build()')"
+    text = "\n".join(" ".join(str(c[f]) for f in PLAN_FIELDS if f in c) for c in cases) + "\n"
+    r = subprocess.run([PLAN_CLI], input=text, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    out = []
+    for line in r.stdout.splitlines():
+        d = {}
+        for kv in line.split():
+            k, v = kv.split("=")
+            d[k] = tuple(int(e) for e in v.split("x")) if k in ("grid", "block") else int(v) if v.lstrip("-").isdigit() else v
+        out.append(d)
+    assert len(out) == len(cases)
+    return out
+
+
+def cdiv(a, b):
+    return -(-a // b)
+
+
+def test_plan_properties_of_stride_2():
+    from feature_tracker_amd import _native as N
+    cases = []
+    for (M, Cin), ks, (B, H, W) in itertools.product(((1, 1), (2, 9), (33, 33), (64, 64), (96, 64), (128, 96), (1024, 4096)), (1, 3),
+                                                     ((1, 1, 1), (2, 6, 7), (1, 1, 7), (1, 7, 1), (1, 9, 129), (1, 440, 1024), (3, 33, 130), (1, 1, 100000), (1, 100001, 1))):
+        cases.append(dict(out_channels=M, in_channels=Cin, kernel_size=ks, B=B, H=H, W=W, stride=2))
+    seen_wm = set()
+    for c, p in zip(cases, plan(cases)):
+        what = f"{c} -> {p}"
+        assert p["refused"] == "none" and p["stride"] == 2, what
+        M, ks, H, W = c["out_channels"], c["kernel_size"], c["H"], c["W"]
+        pad = ks // 2
+        seen_wm.add(p["wm"])
+        # the output partition is exact: the tiles partition the OUTPUT image, the row tiles the output channels
+        assert (p["out_h"], p["out_w"]) == (cdiv(H, 2), cdiv(W, 2)), what
+        assert p["m_tiles"] == cdiv(M, 32) and p["wm"] * p["wn"] == 4 and p["wm"] in (1, 2, 4), what
+        assert p["m_groups"] == cdiv(p["m_tiles"], p["wm"]) and (p["m_groups"] - 1) * p["wm"] < p["m_tiles"], what
+        assert (p["tile_w"], p["tile_h"]) == (32, p["wn"]), what
+        assert p["tiles_x"] * 32 >= p["out_w"] > (p["tiles_x"] - 1) * 32 and p["tiles_y"] * p["wn"] >= p["out_h"] > (p["tiles_y"] - 1) * p["wn"], what
+        assert p["grid"] == (p["tiles_x"] * p["tiles_y"] * c["B"], p["m_groups"]) and p["block"] == (256, 1), what
+        # the chunk and the packed weights are stride 1's
+        chunk = N.FTK_CONV2D_CHUNK[ks]
+        assert p["chunk"] == chunk and p["steps_per_chunk"] * 2 == chunk * ks * ks and p["k_steps"] == N.conv2d_k_steps(c["in_channels"], ks), what
+        assert p["packed"] == N.conv2d_packed_elements(M, c["in_channels"], ks), what
+        # the staged strip covers every tap of every owned output pixel: rows 2 y0 - pad .. + strip_h, columns 2 x0 - pad .. + strip_w
+        assert p["strip_h"] == 2 * (p["wn"] - 1) + ks and p["strip_w"] == 63 + 2 * pad + 1, what
+        for y, ty in itertools.product(range(p["wn"]), range(ks)):
+            assert 0 <= 2 * y + ty < p["strip_h"], what
+        for x, tx in itertools.product(range(32), range(ks)):
+            assert 0 <= 2 * x + tx < p["strip_w"], what
+        # ... in even / odd planes: tap tx of pixel x is float x + tx // 2 of plane tx % 2, inside its plane and its row
+        plane = 32 + pad
+        assert p["row"] == (2 * plane if ks == 3 else 32) and p["rows"] == (p["strip_h"] if ks == 3 else p["wn"]) and p["pitch"] == p["rows"] * p["row"], what
+        for x, tx in itertools.product(range(32), range(ks)):
+            assert x + tx // 2 < plane and (tx % 2) * plane + x + tx // 2 < p["row"], what
+        banks = [{((tx % 2) * plane + x + tx // 2) % 32 for x in range(32)} for tx in range(ks)]
+        assert all(len(b) == 32 for b in banks), what  # a tap's 32 lanes: 32 different banks
+        assert p["lds"] == chunk * p["pitch"] * 4 <= p["lds_static_strided"] <= LDS_LIMIT, what
+    assert seen_wm == {1, 2, 4}
+
+
+def test_plan_refuses_strides_by_name_and_answers_six_fields_as_before():
+    base = dict(out_channels=16, in_channels=19, kernel_size=3, B=1, H=4, W=4)
+    cases = [dict(base, stride=0), dict(base, stride=3), dict(base, stride=-2), dict(base, kernel_size=7, stride=2), dict(base, kernel_size=5, stride=2),
+             dict(base, stride=2, out_channels=1025), dict(base, stride=2, H=0), dict(base, stride=1), dict(base, kernel_size=7, stride=1), dict(base, stride=2)]
+    got = [p["refused"] for p in plan(cases)]
+    assert got == ["stride", "stride", "stride", "stride", "kernel_size", "out_channels", "sizes", "none", "none", "none"]
+    # a line of six fields is answered as on the parent commit: these are that commit's answers, character for character
+    six = [dict(out_channels=96, in_channels=131, kernel_size=3, B=3, H=33, W=129), dict(out_channels=2, in_channels=2, kernel_size=7, B=1, H=5, W=6),
+           dict(base, kernel_size=5)]
+    text = "\n".join(" ".join(str(c[f]) for f in PLAN_FIELDS[:6]) for c in six) + "\n"
+    r = subprocess.run([PLAN_CLI], input=text, capture_output=True, text=True, timeout=120)
+    assert r.stdout.splitlines() == [
+        "refused=none m_tiles=3 wm=4 wn=1 m_groups=1 tile_w=32 tile_h=1 tiles_x=5 tiles_y=33 chunk=8 chunks=17 steps_per_chunk=36 k_steps=612 pitch=102 "
+        "lds=3264 lds_static=6528 packed=117504 grid=495x1 block=256x1 mfma=32x32x2_f32",
+        "refused=none m_tiles=1 wm=1 wn=4 m_groups=1 tile_w=32 tile_h=4 tiles_x=1 tiles_y=2 chunk=2 chunks=1 steps_per_chunk=49 k_steps=49 pitch=380 "
+        "lds=3040 lds_static=3040 packed=3136 grid=2x1 block=256x1 mfma=32x32x2_f32",
+        "refused=kernel_size"]
+    seven = plan([dict(six[0], stride=1)])[0]
+    assert (seven["stride"], seven["out_h"], seven["out_w"], seven["rows"], seven["row"], seven["pitch"]) == (1, 33, 129, 3, 34, 102)
