@@ -49,6 +49,7 @@ EXPORTS = [
     "ftk_klt_track_sharded_device", "ftk_klt_track_sharded", "ftk_klt_track_shard_device", "ftk_klt_unpack_shards_device", "ftk_hamming_match_sharded_device",
     "ftk_default_dense_flow_options", "ftk_dense_flow_gaussian", "ftk_dense_flow", "ftk_dense_flow_device", "ftk_dense_flow_level",
     "ftk_corr_pyramid_layout", "ftk_corr_pyramid_build_device", "ftk_corr_pyramid_lookup_device", "ftk_flow_upsample_device",
+    "ftk_corr_ondemand_layout", "ftk_corr_ondemand_prepare_device", "ftk_corr_ondemand_lookup_device",
     "ftk_sep_conv_gru_packed_elements", "ftk_sep_conv_gru_gates_device", "ftk_sep_conv_gru_blend_device",
     "ftk_conv2d_packed_elements", "ftk_conv2d_device", "ftk_conv2d_strided_device",
     "ftk_nn_match_scores_device", "ftk_nn_match_scores", "ftk_nn_match_list_device", "ftk_nn_match_list", "ftk_nn_fill_pixels_device",
@@ -208,6 +209,9 @@ def lib() -> C.CDLL:
     l.ftk_corr_pyramid_layout.argtypes = [i32, i32, i32, i32, i64p, i64p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     l.ftk_corr_pyramid_build_device.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
     l.ftk_corr_pyramid_lookup_device.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, i32]
+    l.ftk_corr_ondemand_layout.argtypes = [i32, i32, i32, i32, i32, i64p, i64p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    l.ftk_corr_ondemand_prepare_device.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
+    l.ftk_corr_ondemand_lookup_device.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32]
     l.ftk_flow_upsample_device.argtypes = [vp, vp, vp, vp, i32, i32, i32, C.c_float, vp]
     i64, f32 = C.c_int64, C.c_float
     parts = C.POINTER(GruPart)
@@ -247,6 +251,18 @@ def corr_pyramid_layout(B: int, H: int, W: int, levels: int):
     lh = (C.c_int32 * max(n, 1))()
     lw = (C.c_int32 * max(n, 1))()
     check(lib().ftk_corr_pyramid_layout(int(B), int(H), int(W), int(levels), C.byref(elements), off, lh, lw), None)
+    return elements.value, [off[i] for i in range(n)], [(lh[i], lw[i]) for i in range(n)]
+
+
+def corr_ondemand_layout(B: int, C_: int, H: int, W: int, levels: int):
+    """ftk_corr_ondemand_layout (host only): (elements, [offset_l], [(H_l, W_l)]) of an on-demand correlation workspace, fmap0 transposed at
+    element 0 and fmap1's level l channel-last at offset_l; elements = B * C * (H * W + sum_l H_l * W_l).  FtkError as corr_pyramid_layout."""
+    n = max(int(levels), 0)
+    elements = C.c_int64()
+    off = (C.c_int64 * max(n, 1))()
+    lh = (C.c_int32 * max(n, 1))()
+    lw = (C.c_int32 * max(n, 1))()
+    check(lib().ftk_corr_ondemand_layout(int(B), int(C_), int(H), int(W), int(levels), C.byref(elements), off, lh, lw), None)
     return elements.value, [off[i] for i in range(n)], [(lh[i], lw[i]) for i in range(n)]
 
 

@@ -351,6 +351,37 @@ hipError_t corr_build_launch(const CorrBuildParams &p, hipStream_t stream);
 hipError_t corr_pool_launch(const float *src, float *dst, int64_t slabs, int hin, int win, int hout, int wout, hipStream_t stream);
 hipError_t corr_lookup_launch(const CorrLookupParams &p, hipStream_t stream);
 
+// RAFT's on-demand correlation (raft_corr_ondemand_kernels.hip, OnDemandCorrelation): no volume.  One workspace: fmap0
+// transposed to [B][H * W][C] at element 0, fmap1's level l channel-last as [B][level_h[l]][level_w[l]][C] at level_offset[l]
+// (ftk_corr_ondemand_layout).  The grids are raft_corr_ondemand_plan's (raft_corr_ondemand_plan.h).
+struct CorrOdTransposeParams {
+    const float *f0;  // [B][C][H * W]
+    const float *f1;
+    float *out0;      // [B][H * W][C]
+    float *out1;
+    int32_t B, C;
+    int64_t HW;
+};
+struct CorrOdPoolParams {
+    const float *src;  // [B][hin][win][C]
+    float *dst;        // [B][hin / 2][win / 2][C]
+    int32_t B, C, hin, win;
+};
+struct CorrOdLookupParams {
+    const float *workspace;
+    const float *coords;  // [B][2][H][W]: x, y
+    float *out;           // [B][levels * K][H][W], or per_level: levels blocks of [B][H][W][K]
+    int32_t B, C, H, W, levels, radius, per_level;
+    int32_t lattice_side;  // 2r + 2, or 0: every corner directly
+    int32_t vector;        // 16-byte loads in the channel chain
+    float divisor;         // (float)sqrt((double)C)
+    int64_t level_offset[kCorrMaxLevels];
+    int32_t level_h[kCorrMaxLevels], level_w[kCorrMaxLevels];
+};
+hipError_t corr_od_transpose_launch(const CorrOdTransposeParams &p, dim3 grid, dim3 block, hipStream_t stream);
+hipError_t corr_od_pool_launch(const CorrOdPoolParams &p, int64_t blocks, hipStream_t stream);
+hipError_t corr_od_lookup_launch(const CorrOdLookupParams &p, dim3 grid, dim3 block, hipStream_t stream);
+
 // RAFT's convex flow upsampling (raft_upsample_kernels.hip, Raft.UpsampleFlow): one launch.
 constexpr int kFlowUpsampleTile = 32;  // coarse pixels per workgroup along x (FTK_FLOW_UPSAMPLE_TILE)
 struct FlowUpsampleParams {

@@ -15,6 +15,8 @@ launch on ``torch.cuda.current_stream()`` at each call, so construction and look
 ``FeatureEncoder`` / ``ContextEncoder`` (encoder.py:25-68) run their 17 / 18 layers on the same kernel family with a stride, a residual
 epilogue and BatchNorm folded into the weights once, and ``Raft.from_state_dict(state, levels, radius)(ref_image, cur_image)`` is
 model.py:66-97: the whole forward pass, the list of flow predictions, with every convolution on these kernels.
+``OnDemandCorrelation`` is ``CorrelationPyramid`` without the volume: it keeps the two feature maps channel-last and computes the
+correlation values a lookup reads when it reads them; ``Raft(..., correlation="on_demand")`` uses it.
 Inference only, float32 only, and no CPU fallback.
 """
 from __future__ import annotations
@@ -105,6 +107,73 @@ class CorrelationPyramid:
         K = (2 * self.radius + 1) ** 2
         out = torch.empty((B, self.num_levels * K, H, W), dtype=torch.float32, device=self._device)
         D.corr_pyramid_lookup_device(self._ctx, self._volume, self.num_levels, self.radius, coords, out, per_level=False)
+        return out
+
+
+class OnDemandCorrelation:
+    """``CorrelationPyramid``'s lookups without its volume (upstream RAFT's ``alternate_corr``): construction transposes the
+    two float32 CUDA feature maps [B, C, H, W] and pools ``fmap1`` through ``num_levels`` levels into one workspace of
+    4 * B * C * (H * W + sum_l H_l * W_l) bytes, and every lookup computes the correlation values its windows read, by the HIP kernels of
+    raft_corr_ondemand_kernels.hip.  Same arguments, checks, ``num_levels`` / ``radius`` attributes, ``__call__`` and ``lookup`` results as
+    ``CorrelationPyramid``; level 0 is bit-identical to it, levels >= 1 are the same quantity with other roundings.  There is no
+    ``correlation_pyramid`` attribute: no correlation value is ever stored."""
+
+    def __init__(self, fmap0, fmap1, num_levels: int, radius: int):
+        import torch  # not device._torch(): a CPU tensor is refused below, as a ValueError, on a machine without a device too
+
+        # CorrelationPyramid's checks and messages; where the tensor is comes last, so that every other complaint is also made without a device
+        for name, t in (("fmap0", fmap0), ("fmap1", fmap1)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 4:
+                raise ValueError(f"{name} must be a 4-D float32 CUDA tensor [B, C, H, W] (no CPU fallback, no other dtype)")
+        if fmap0.size() != fmap1.size() or fmap0.device != fmap1.device:
+            raise ValueError(f"fmap0 and fmap1 must have the same size and device: {tuple(fmap0.shape)} on {fmap0.device} vs "
+                             f"{tuple(fmap1.shape)} on {fmap1.device}")
+        for name, t in (("fmap0", fmap0), ("fmap1", fmap1)):
+            if not t.is_cuda:
+                raise ValueError(f"{name} must be a 4-D float32 CUDA tensor [B, C, H, W] (no CPU fallback, no other dtype)")
+        _check_no_grad(torch, fmap0, fmap1, what="OnDemandCorrelation")
+        if not 0 <= int(radius) <= N.FTK_CORR_MAX_RADIUS:
+            raise ValueError(f"radius {radius} outside 0 .. {N.FTK_CORR_MAX_RADIUS}")
+        B, C, H, W = fmap0.shape
+        try:
+            elements, _, _ = N.corr_ondemand_layout(B, C, H, W, int(num_levels))
+        except N.FtkError as e:
+            raise ValueError(f"OnDemandCorrelation of {H} x {W} feature maps with num_levels={num_levels}: {e}") from None
+        self.num_levels = int(num_levels)
+        self.radius = int(radius)
+        self._shape = (B, H, W)
+        self._channels = int(C)
+        self._device = fmap0.device
+        self._ctx = _context(fmap0.device.index if fmap0.device.index is not None else torch.cuda.current_device())
+        self._workspace = torch.empty(elements, dtype=torch.float32, device=fmap0.device)
+        D.corr_ondemand_prepare_device(self._ctx, fmap0.contiguous(), fmap1.contiguous(), self.num_levels, self._workspace)
+
+    @property
+    def workspace_bytes(self) -> int:
+        """Bytes of the one buffer this object holds: 4 * B * C * (H * W + sum_l H_l * W_l)."""
+        return 4 * int(self._workspace.numel())
+
+    _coords = CorrelationPyramid._coords
+
+    def __call__(self, pixel_locations):
+        """As ``CorrelationPyramid.__call__``: per level a contiguous [B, H, W, (2r+1)^2] tensor of the bilinear window samples."""
+        torch = D._torch()
+        coords = self._coords(pixel_locations)
+        B, H, W = self._shape
+        K = (2 * self.radius + 1) ** 2
+        block = B * H * W * K
+        out = torch.empty(self.num_levels * block, dtype=torch.float32, device=self._device)
+        D.corr_ondemand_lookup_device(self._ctx, self._workspace, self._channels, self.num_levels, self.radius, coords, out, per_level=True)
+        return [out[l * block:(l + 1) * block].view(B, H, W, K) for l in range(self.num_levels)]
+
+    def lookup(self, pixel_locations):
+        """As ``CorrelationPyramid.lookup``: [B, L*K, H, W] in one launch."""
+        torch = D._torch()
+        coords = self._coords(pixel_locations)
+        B, H, W = self._shape
+        K = (2 * self.radius + 1) ** 2
+        out = torch.empty((B, self.num_levels * K, H, W), dtype=torch.float32, device=self._device)
+        D.corr_ondemand_lookup_device(self._ctx, self._workspace, self._channels, self.num_levels, self.radius, coords, out, per_level=False)
         return out
 
 
@@ -488,6 +557,7 @@ class UpdateBlock:
 # ---- the encoders and the whole model (encoder.py:4-68, model.py:6-97) --------------------------------------------
 
 BN_EPS = 1e-5  # nn.BatchNorm2d's default; the module stores none
+CORRELATION_MODES = ("all_pairs", "on_demand")  # Raft(correlation=...): CorrelationPyramid (the reference's) or OnDemandCorrelation
 
 
 def _fold_batch_norm(state: Mapping, conv_key: str, bn_prefix: str, eps: float):
@@ -678,10 +748,14 @@ class Raft:
     The feature encoder runs once over the two images stacked along B (17 launches), the context encoder on the reference image (18), both
     normalising the raw image at conv_in's fetch, and the correlation pyramid is built (1 launch up to four levels); then per iteration one lookup, UpdateBlock's 13 launches and one upsampling launch.
     What stays torch: the stack of the two raw images, the meshgrid, and the three [B, 2, h, w] element-wise operations of model.py:90-94,
-    kept as written (``(cur + delta) - ref`` is not ``flow + delta`` in float32)."""
+    kept as written (``(cur + delta) - ref`` is not ``flow + delta`` in float32).  ``correlation="on_demand"`` replaces the pyramid by
+    ``OnDemandCorrelation`` (no volume; 1 + (levels - 1) launches to prepare); the default ``"all_pairs"`` is the reference's."""
 
     def __init__(self, feature_encoder: FeatureEncoder, context_encoder: ContextEncoder, update_block: UpdateBlock, correlation_pyramid_levels: int,
-                 correlation_radius: int, max_iterations: int = 12):
+                 correlation_radius: int, max_iterations: int = 12, correlation: str = "all_pairs"):
+        if correlation not in CORRELATION_MODES:
+            raise ValueError(f"correlation {correlation!r} is not one of {', '.join(repr(m) for m in CORRELATION_MODES)}")
+        self.correlation = correlation
         levels, radius = int(correlation_pyramid_levels), int(correlation_radius)
         if not 1 <= levels <= N.FTK_CORR_MAX_LEVELS or not 0 <= radius <= N.FTK_CORR_MAX_RADIUS:
             raise ValueError(f"correlation_pyramid_levels {correlation_pyramid_levels} outside 1 .. {N.FTK_CORR_MAX_LEVELS} or correlation_radius "
@@ -707,10 +781,13 @@ class Raft:
         self.weights.update({"update_block." + k: v for k, v in update_block.weights.items()})
 
     @classmethod
-    def from_state_dict(cls, state: Mapping, correlation_pyramid_levels: int, correlation_radius: int, max_iterations: int = 12, eps: float = BN_EPS):
+    def from_state_dict(cls, state: Mapping, correlation_pyramid_levels: int, correlation_radius: int, max_iterations: int = 12, eps: float = BN_EPS,
+                        correlation: str = "all_pairs"):
         """From ``Raft(...).state_dict()`` of the reference.  All widths are read off the weights; the context encoder's split is the update
         block's ``inp`` and ``net`` widths.  The two correlation arguments are not in the state dict: they must give the update block's
         correlation width, levels * (2 * radius + 1) ** 2."""
+        if correlation not in CORRELATION_MODES:
+            raise ValueError(f"correlation {correlation!r} is not one of {', '.join(repr(m) for m in CORRELATION_MODES)}")
         block = UpdateBlock.from_state_dict(state, "update_block.")
         features = FeatureEncoder.from_state_dict(state, "feature_encoder.", eps)
         out = _state_tensor(state, "context_encoder.net.conv_out.0.weight", 4)
@@ -721,7 +798,7 @@ class Raft:
         devices = {str(features._weights_device()), str(context.net._weights_device()), str(block.motion_encoder._weights_device())}
         if len(devices) != 1:
             raise ValueError(f"the weights are on several devices: {sorted(devices)}")
-        return cls(features, context, block, correlation_pyramid_levels, correlation_radius, max_iterations)
+        return cls(features, context, block, correlation_pyramid_levels, correlation_radius, max_iterations, correlation)
 
     def __call__(self, ref_image, cur_image, iterations: int = None):
         """``Raft.forward``: float32 CUDA images [B, in_channels, H, W] in 0 .. 255 give ``iterations`` (default ``max_iterations``) new
@@ -744,12 +821,16 @@ class Raft:
         _check_maps("Raft", [("ref_image", ref_image, enc.in_channels), ("cur_image", cur_image, enc.in_channels)], enc._weights_device())
         h, w = ((((e + 1) // 2 + 1) // 2 + 1) // 2 for e in (H, W))  # three stride-2 layers, each ceil(e / 2)
         try:
-            N.corr_pyramid_layout(B, h, w, self.correlation_pyramid_levels)
+            if self.correlation == "on_demand":  # the level rules alone: no volume is sized, none will exist
+                N.corr_ondemand_layout(B, enc.out_channels, h, w, self.correlation_pyramid_levels)
+            else:
+                N.corr_pyramid_layout(B, h, w, self.correlation_pyramid_levels)
         except N.FtkError as e:
             raise ValueError(f"images of {H} x {W} give {h} x {w} feature maps, too small for {self.correlation_pyramid_levels} correlation levels: "
                              f"{e}") from None
         features = enc(torch.cat([ref_image, cur_image], dim=0), normalise=True)
-        pyramid = CorrelationPyramid(features[:B], features[B:], self.correlation_pyramid_levels, self.correlation_radius)
+        correlation_class = OnDemandCorrelation if self.correlation == "on_demand" else CorrelationPyramid
+        pyramid = correlation_class(features[:B], features[B:], self.correlation_pyramid_levels, self.correlation_radius)
         inp, net = self.context_encoder(ref_image, normalise=True)
         ys, xs = torch.meshgrid(torch.arange(h, device=ref_image.device), torch.arange(w, device=ref_image.device), indexing="ij")
         ref = torch.stack([xs, ys], dim=0).float()[None].repeat(B, 1, 1, 1)  # InitializeFlow, model.py:34-45: x in channel 0

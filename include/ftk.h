@@ -369,6 +369,29 @@ int ftk_corr_pyramid_build_device(ftk_context *ctx, void *stream, const float *d
 int ftk_corr_pyramid_lookup_device(ftk_context *ctx, void *stream, const float *d_volume, int32_t B, int32_t H, int32_t W, int32_t levels,
                                    int32_t radius, const float *d_coords, float *d_out, int32_t per_level);
 
+/* ---- RAFT on-demand correlation: the lookups of the pyramid above without its volume ------------------------ */
+
+/*
+ * The same windows as ftk_corr_pyramid_lookup_device, with no correlation value ever stored: the workspace holds fmap0 transposed to
+ * [B][H*W][C] (element 0) and fmap1 pooled through the levels with the pyramid's pool formula, level l channel-last as
+ * [B][level_h[l]][level_w[l]][C] at element level_offsets[l]; a lookup evaluates the correlation of a query pixel with a level position
+ * as the fmaf chain over the channels (ascending, from +0) of fmap0[b, c, p] * fmap1_l[b, c, y2, x2], divided by (float)sqrt((double)C),
+ * zero outside the level, and samples it exactly as the pyramid's lookup does.  Level 0 is bit-identical to the pyramid's; levels >= 1
+ * are the same quantity with other roundings (the pool is linear).  Any C >= 1; limits FTK_CORR_MAX_LEVELS and FTK_CORR_MAX_RADIUS.
+ * The library holds no workspace and allocates nothing; both device entries enqueue on `stream` and can be captured in a graph.
+ */
+/* Host only.  *elements = B * C * (H * W + sum_l H_l * W_l) floats; level_offsets (elements), level_h, level_w as for
+ * ftk_corr_pyramid_layout (each optional, `levels` entries), and its level rules and errors. */
+int ftk_corr_ondemand_layout(int32_t B, int32_t C, int32_t H, int32_t W, int32_t levels, int64_t *elements, int64_t *level_offsets, int32_t *level_h,
+                             int32_t *level_w);
+/* Once per image pair: transposes d_fmap0 and d_fmap1 (contiguous float32 [B][C][H][W]) and pools d_fmap1 into d_workspace (the layout's
+ * size; a 16-byte aligned one with C % 4 == 0 lets the lookup load 16 bytes at a time).  1 + (levels - 1) launches. */
+int ftk_corr_ondemand_prepare_device(ftk_context *ctx, void *stream, const float *d_fmap0, const float *d_fmap1, int32_t B, int32_t C, int32_t H,
+                                     int32_t W, int32_t levels, float *d_workspace);
+/* d_coords and d_out as for ftk_corr_pyramid_lookup_device (both output forms), from the prepared workspace alone.  One launch. */
+int ftk_corr_ondemand_lookup_device(ftk_context *ctx, void *stream, const float *d_workspace, int32_t B, int32_t C, int32_t H, int32_t W,
+                                    int32_t levels, int32_t radius, const float *d_coords, float *d_out, int32_t per_level);
+
 /* ---- RAFT convex flow upsampling (src/nn_optical_flow_tracker/raft/model.py) ------------------------ */
 
 /* Coarse pixels along x that one workgroup of the kernel owns: shapes just below, at and above a multiple of it are the ones a test
