@@ -9,7 +9,7 @@ native library; the first compute call does, and fails loudly if it has not been
 """
 from . import synth  # noqa: F401
 from .nn_matcher import NNFeatureMatcher, NNFeatureMatcherOptions  # noqa: F401
-from .raft import ContextEncoder, CorrelationPyramid, FeatureEncoder, MotionEncoder, OnDemandCorrelation, Raft, SepConvGru, UpdateBlock, upsample_flow  # noqa: F401
+from .raft import ContextEncoder, CorrelationPyramid, FeatureEncoder, MotionEncoder, OnDemandCorrelation, Raft, SepConvGru, UpdateBlock, track_points_from_flow, upsample_flow  # noqa: F401
 from .tracker import (  # noqa: F401
     BriefDescriptor, BriefMatcher, CosineMatcher, DenseOpticalFlow, DenseOpticalFlowOptions, DirectMethod, DirectMethodOptions, DiskMatcher, SuperpointMatcher, Context, FeaturePointHarrisDetector, DescriptorMatcherOptions, ImagePyramid, OpticalFlow, OpticalFlowAffineKlt, OpticalFlowBasicKlt,
     OpticalFlowLssdKlt, OpticalFlowOptions, default_context, pack_brief, unpack_brief, refresh_env_switches,
@@ -17,7 +17,7 @@ from .tracker import (  # noqa: F401
 )
 
 __all__ = [
-    "CorrelationPyramid", "OnDemandCorrelation", "MotionEncoder", "SepConvGru", "UpdateBlock", "upsample_flow", "FeatureEncoder", "ContextEncoder", "Raft", "NNFeatureMatcher", "NNFeatureMatcherOptions", "BriefDescriptor", "BriefMatcher", "CosineMatcher", "DenseOpticalFlow", "DenseOpticalFlowOptions", "DirectMethod", "DirectMethodOptions", "DiskMatcher", "SuperpointMatcher", "Context", "FeaturePointHarrisDetector", "DescriptorMatcherOptions", "ImagePyramid", "OpticalFlow", "OpticalFlowAffineKlt", "OpticalFlowBasicKlt",
+    "CorrelationPyramid", "OnDemandCorrelation", "MotionEncoder", "SepConvGru", "UpdateBlock", "upsample_flow", "track_points_from_flow", "FeatureEncoder", "ContextEncoder", "Raft", "NNFeatureMatcher", "NNFeatureMatcherOptions", "BriefDescriptor", "BriefMatcher", "CosineMatcher", "DenseOpticalFlow", "DenseOpticalFlowOptions", "DirectMethod", "DirectMethodOptions", "DiskMatcher", "SuperpointMatcher", "Context", "FeaturePointHarrisDetector", "DescriptorMatcherOptions", "ImagePyramid", "OpticalFlow", "OpticalFlowAffineKlt", "OpticalFlowBasicKlt",
     "OpticalFlowLssdKlt", "OpticalFlowOptions", "default_context", "pack_brief", "unpack_brief", "refresh_env_switches", "synth",
     "NOT_TRACKED", "TRACKED", "LARGE_RESIDUAL", "OUTSIDE", "NUMERIC_ERROR",
 ]

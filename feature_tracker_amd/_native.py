@@ -19,6 +19,7 @@ FTK_MAX_LEVELS = 12
 FTK_CORR_MAX_LEVELS = 16
 FTK_CORR_MAX_RADIUS = 64
 FTK_FLOW_UPSAMPLE_TILE = 32
+FTK_FLOW_POINTS_TILE = 64
 # SepConvGru (include/ftk.h): the supported sizes and the packed weight layout
 FTK_SEP_CONV_GRU_MAX_PARTS = 3
 FTK_SEP_CONV_GRU_MAX_H_CHANNELS = 1024
@@ -48,7 +49,7 @@ EXPORTS = [
     "ftk_shard_bounds", "ftk_klt_shard_bytes", "ftk_comm_unique_id", "ftk_comm_create", "ftk_comm_destroy", "ftk_comm_rank", "ftk_comm_world",
     "ftk_klt_track_sharded_device", "ftk_klt_track_sharded", "ftk_klt_track_shard_device", "ftk_klt_unpack_shards_device", "ftk_hamming_match_sharded_device",
     "ftk_default_dense_flow_options", "ftk_dense_flow_gaussian", "ftk_dense_flow", "ftk_dense_flow_device", "ftk_dense_flow_level",
-    "ftk_corr_pyramid_layout", "ftk_corr_pyramid_build_device", "ftk_corr_pyramid_lookup_device", "ftk_flow_upsample_device",
+    "ftk_corr_pyramid_layout", "ftk_corr_pyramid_build_device", "ftk_corr_pyramid_lookup_device", "ftk_flow_upsample_device", "ftk_flow_track_points_device",
     "ftk_corr_ondemand_layout", "ftk_corr_ondemand_prepare_device", "ftk_corr_ondemand_lookup_device",
     "ftk_sep_conv_gru_packed_elements", "ftk_sep_conv_gru_gates_device", "ftk_sep_conv_gru_blend_device",
     "ftk_conv2d_packed_elements", "ftk_conv2d_device", "ftk_conv2d_strided_device",
@@ -213,6 +214,7 @@ def lib() -> C.CDLL:
     l.ftk_corr_ondemand_prepare_device.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
     l.ftk_corr_ondemand_lookup_device.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32]
     l.ftk_flow_upsample_device.argtypes = [vp, vp, vp, vp, i32, i32, i32, C.c_float, vp]
+    l.ftk_flow_track_points_device.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, C.c_float, C.c_float, vp, vp, vp, vp]
     i64, f32 = C.c_int64, C.c_float
     parts = C.POINTER(GruPart)
     l.ftk_sep_conv_gru_packed_elements.argtypes = [i32, i32, i32, i64p]

@@ -394,6 +394,23 @@ struct FlowUpsampleParams {
 // hipErrorInvalidValue when the grid would not fit in 2^31 - 1 workgroups
 hipError_t flow_upsample_launch(const FlowUpsampleParams &p, hipStream_t stream);
 
+// Sparse tracking from RAFT's coarse flow (raft_points_kernels.hip): one launch.
+constexpr int kFlowPointsTile = 64;  // points per workgroup (FTK_FLOW_POINTS_TILE)
+struct FlowPointsParams {
+    const float *flow;       // [B][2][H][W]
+    const float *mask;       // [B][576][H][W]
+    const float *flow_back;  // both or neither: the backward pair of the forward-backward check
+    const float *mask_back;
+    const float *points;     // [B][N][2] (u = x, v = y)
+    float *cur_points;       // [B][N][2]
+    uint8_t *status;         // [B][N]
+    float *fb_error2;        // [B][N] or null
+    int32_t B, H, W, N, image_rows, image_cols;
+    float mask_scale, fb_threshold;
+};
+// hipErrorInvalidValue when the grid would not fit in 2^31 - 1 workgroups
+hipError_t flow_track_points_launch(const FlowPointsParams &p, hipStream_t stream);
+
 // RAFT's separable ConvGRU (raft_gru_kernels.hip, SepConvGru.forward, gru.py:59-76): per pass a gates launch and a
 // candidate + blend launch, each an implicit GEMM on the f32-input matrix cores.
 // One tensor of an input that is a channel concatenation read in place (the GRU's and conv2d_kernel's segment lists).

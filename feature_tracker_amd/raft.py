@@ -17,6 +17,9 @@ epilogue and BatchNorm folded into the weights once, and ``Raft.from_state_dict(
 model.py:66-97: the whole forward pass, the list of flow predictions, with every convolution on these kernels.
 ``OnDemandCorrelation`` is ``CorrelationPyramid`` without the volume: it keeps the two feature maps channel-last and computes the
 correlation values a lookup reads when it reads them; ``Raft(..., correlation="on_demand")`` uses it.
+``track_points_from_flow`` moves feature points by the bilinear sample of the upsampled flow without storing it and gives them a
+TrackStatus, with an optional forward-backward check, in one launch; ``Raft.track_points`` is the model as a feature tracker on top of it
+(DESIGN.md 5.17).
 Inference only, float32 only, and no CPU fallback.
 """
 from __future__ import annotations
@@ -205,6 +208,72 @@ def upsample_flow(flow, mask, mask_scale: float = 1.0):
     out = torch.empty((B, 2, 8 * H, 8 * W), dtype=torch.float32, device=flow.device)
     D.flow_upsample_device(ctx, flow.contiguous(), mask.contiguous(), out, mask_scale)
     return out
+
+
+def _check_points(points, B: int, device) -> None:
+    """``points`` of a tracking call: a float32 tensor [B, N, 2] on ``device``; where it is comes last."""
+    import torch
+
+    if not isinstance(points, torch.Tensor) or points.dtype != torch.float32 or points.dim() != 3 or points.size(2) != 2 or points.size(0) != B:
+        got = f"{points.dtype} {list(points.shape)}" if isinstance(points, torch.Tensor) else type(points).__name__
+        raise ValueError(f"points must be a float32 CUDA tensor [{B}, N, 2] of (x, y) pixels (no CPU fallback, no other dtype): got {got}")
+    if points.device != device:
+        raise ValueError(f"points must be on {device}, with the other tensors of the call (got them on {points.device})")
+
+
+def track_points_from_flow(flow, mask, points, image_size, mask_scale: float = 1.0, backward=None, forward_backward: float = None):
+    """Feature points through RAFT's coarse flow, the sparse counterpart of ``upsample_flow``: ``points`` [B, N, 2]
+    (float32 CUDA, ``(x, y)`` in image pixels) are moved by the bilinear sample of ``upsample_flow(flow, mask, mask_scale)`` at each point,
+    computed where the point reads it; no [B, 2, 8H, 8W] tensor is written.  ``image_size = (rows, cols)``, at most ``(8H, 8W)``, is the image
+    the points live in.  Returns ``(cur_points [B, N, 2], status [B, N] uint8, fb_error2)``: ``TRACKED``, ``OUTSIDE`` (the reference or the
+    tracked point is not within ``0 .. cols - 1`` x ``0 .. rows - 1``; a reference point outside comes back as it is) or ``NUMERIC_ERROR``
+    (a non-finite result; the point comes back as it is).  ``backward=(flow_back, mask_back)`` with ``forward_backward=t`` pixels adds the
+    forward-backward check: a tracked point is sent back through the backward pair, ``fb_error2`` [B, N] is its squared distance to where
+    it started, and ``LARGE_RESIDUAL`` replaces ``TRACKED`` unless ``fb_error2 <= t * t``; without them ``fb_error2`` is ``None``.  One
+    launch of raft_points_kernels.hip on torch's current stream.  Arguments are checked before any device is touched."""
+    import torch
+
+    named = [("flow", flow, 2), ("mask", mask, 576)]
+    if (backward is None) != (forward_backward is None):
+        raise ValueError("backward and forward_backward go together: the backward (flow, mask) pair and the threshold in pixels, or neither")
+    if backward is not None:
+        if not isinstance(backward, (tuple, list)) or len(backward) != 2:
+            raise ValueError(f"backward must be a (flow_back, mask_back) pair (got {type(backward).__name__})")
+        named += [("backward[0]", backward[0], 2), ("backward[1]", backward[1], 576)]
+        if not float(forward_backward) >= 0 or not math.isfinite(float(forward_backward)):
+            raise ValueError(f"forward_backward must be a finite number of pixels >= 0 (got {forward_backward})")
+    for name, t, channels in named:
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 4 or t.size(1) != channels:
+            got = f"{t.dtype} {list(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
+            raise ValueError(f"{name} must be a 4-D float32 CUDA tensor [B, {channels}, H, W] (no CPU fallback, no other dtype): got {got}")
+    B, _, H, W = (int(e) for e in flow.shape)
+    for name, t, _ in named[1:]:
+        if (t.size(0), t.size(2), t.size(3)) != (B, H, W) or t.device != flow.device:
+            raise ValueError(f"flow and {name} must agree in B, H, W and device: {tuple(flow.shape)} on {flow.device} vs {tuple(t.shape)} on {t.device}")
+    if B < 1 or H < 1 or W < 1:
+        raise ValueError(f"flow must not be empty (got {tuple(flow.shape)})")
+    _check_points(points, B, flow.device)
+    try:
+        rows, cols = (int(e) for e in image_size)
+    except (TypeError, ValueError):
+        raise ValueError(f"image_size must be (rows, cols) (got {image_size!r})") from None
+    if not (1 <= rows <= 8 * H and 1 <= cols <= 8 * W):
+        raise ValueError(f"image_size {rows} x {cols} must be within 1 .. {8 * H} x 1 .. {8 * W}, the grid of the flow")
+    if not math.isfinite(float(mask_scale)):
+        raise ValueError(f"mask_scale must be finite (got {mask_scale})")
+    _check_no_grad(torch, points, *[t for _, t, _ in named], what="track_points_from_flow")
+    if not flow.is_cuda:
+        raise ValueError(f"flow, mask and points must be CUDA tensors (got them on {flow.device}): there is no CPU fallback")
+    torch = D._torch()
+    ctx = _device_context(flow)
+    n = int(points.size(1))
+    cur_points = torch.empty((B, n, 2), dtype=torch.float32, device=flow.device)
+    status = torch.empty((B, n), dtype=torch.uint8, device=flow.device)
+    fb_error2 = None if backward is None else torch.empty((B, n), dtype=torch.float32, device=flow.device)
+    flow_back, mask_back = (None, None) if backward is None else (backward[0].contiguous(), backward[1].contiguous())
+    D.flow_track_points_device(ctx, flow.contiguous(), mask.contiguous(), points.contiguous(), rows, cols, cur_points, status, fb_error2, mask_scale,
+                               flow_back, mask_back, 0.0 if backward is None else float(forward_backward))
+    return cur_points, status, fb_error2
 
 
 class SepConvGru:
@@ -537,10 +606,12 @@ class UpdateBlock:
             raise ValueError(f"the weights under {prefix!r} are on several devices: {sorted(devices)}")
         return block
 
-    def __call__(self, net, inp, correlation, flow):
+    def __call__(self, net, inp, correlation, flow, want_mask: bool = True):
         """``UpdateBlock.forward``: float32 CUDA tensors ``net`` [B, net, H, W], ``inp`` [B, inp, H, W], ``correlation`` [B, corr, H, W] and
         ``flow`` [B, 2, H, W] give new tensors ``(new_net, mask, delta_flow)``; ``mask`` already carries the 0.25.  Every argument is
-        checked before the first launch; nothing passed in is modified."""
+        checked before the first launch; nothing passed in is modified.  ``want_mask=False`` skips the mask head's two launches and returns
+        ``None`` for ``mask`` (a caller that uses only the last iteration's mask, ``Raft.track_points``); the other two results do not
+        depend on it."""
         enc = self.motion_encoder
         _check_maps("UpdateBlock", [("net", net, self.net_channels), ("inp", inp, self.inp_channels), ("correlation", correlation, enc.correlation_in),
                                     ("flow", flow, 2)], enc._weights_device())
@@ -550,7 +621,7 @@ class UpdateBlock:
         new_net = self.gru((inp, out, flow), net)
         L = self._layers
         delta_flow = _conv(ctx, [_conv(ctx, [new_net], L["flow_head.conv1"], True)], L["flow_head.conv2"], False)
-        mask = _conv(ctx, [_conv(ctx, [new_net], L["mask.0"], True)], L["mask.2"], False, 0.25)
+        mask = _conv(ctx, [_conv(ctx, [new_net], L["mask.0"], True)], L["mask.2"], False, 0.25) if want_mask else None
         return new_net, mask, delta_flow
 
 
@@ -843,3 +914,77 @@ class Raft:
             cur = cur + delta
             predictions.append(upsample_flow(cur - ref, mask))
         return predictions
+
+    def _check_pair(self, ref_image, cur_image, points, iterations, stacked: bool):
+        """The argument checks of ``__call__`` for ``track_points``, with those of ``points`` placed before the complaint about where the
+        tensors are, so that each is also made on a machine without a device; ``stacked``: the loop will run at batch 2B.  Returns
+        (n, B, H, W, h, w)."""
+        import torch
+
+        n = self.max_iterations if iterations is None else int(iterations)
+        if n < 1:
+            raise ValueError(f"iterations {iterations} must be at least 1")
+        enc = self.feature_encoder
+        for name, t in (("ref_image", ref_image), ("cur_image", cur_image)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 4 or t.size(1) != enc.in_channels:
+                got = f"{t.dtype} {list(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
+                raise ValueError(f"{name} must be a 4-D float32 CUDA tensor [B, {enc.in_channels}, H, W] (no CPU fallback, no other dtype): got {got}")
+        if ref_image.size() != cur_image.size() or ref_image.device != cur_image.device:
+            raise ValueError(f"The size of the reference and current images should be the same: {tuple(ref_image.shape)} on {ref_image.device} vs "
+                             f"{tuple(cur_image.shape)} on {cur_image.device}")
+        B, _, H, W = (int(e) for e in ref_image.shape)
+        _check_points(points, B, ref_image.device)
+        _check_no_grad(torch, points, what="Raft")
+        _check_maps("Raft", [("ref_image", ref_image, enc.in_channels), ("cur_image", cur_image, enc.in_channels)], enc._weights_device())
+        h, w = ((((e + 1) // 2 + 1) // 2 + 1) // 2 for e in (H, W))  # three stride-2 layers, each ceil(e / 2)
+        try:
+            if self.correlation == "on_demand":
+                N.corr_ondemand_layout(2 * B if stacked else B, enc.out_channels, h, w, self.correlation_pyramid_levels)
+            else:
+                N.corr_pyramid_layout(2 * B if stacked else B, h, w, self.correlation_pyramid_levels)
+        except N.FtkError as e:
+            raise ValueError(f"images of {H} x {W} give {h} x {w} feature maps, too small for {self.correlation_pyramid_levels} correlation levels: "
+                             f"{e}") from None
+        return n, B, H, W, h, w
+
+    def track_points(self, ref_image, cur_image, points, iterations: int = None, forward_backward: float = None, return_error: bool = False):
+        """RAFT as a feature tracker: ``points`` [B, N, 2] (float32 CUDA, ``(x, y)`` pixels of ``ref_image``) give
+        ``(cur_points [B, N, 2], status [B, N] uint8)``, the points in ``cur_image`` and their TrackStatus, as ``track_points_from_flow``
+        defines them on the last iteration's coarse flow and mask with the images' own ``(H, W)`` as ``image_size``: bit for bit what
+        sampling ``self(ref_image, cur_image)[-1]`` bilinearly at the points gives.  The loop is ``__call__``'s without the mask head in all
+        but the last iteration and without any ``upsample_flow``: 36 + 13 * iterations - 2 * (iterations - 1) + 1 launches.
+        ``forward_backward=t`` (pixels, finite, >= 0) adds the forward-backward check: the feature encoder still runs once, the loop runs
+        at batch 2B on the pair and the swapped pair, and the two halves of the last iteration are the forward and the backward flow of one
+        launch; a tracked point that does not come back within ``t`` pixels is ``LARGE_RESIDUAL``.  ``return_error=True`` appends
+        ``fb_error2`` [B, N] (``None`` without the check).  Every argument is checked before the first launch; on torch's current stream,
+        capturable at fixed shapes."""
+        import torch
+
+        check = forward_backward is not None
+        if check and (not float(forward_backward) >= 0 or not math.isfinite(float(forward_backward))):
+            raise ValueError(f"forward_backward must be a finite number of pixels >= 0 (got {forward_backward})")
+        n, B, H, W, h, w = self._check_pair(ref_image, cur_image, points, iterations, check)
+        both = torch.cat([ref_image, cur_image], dim=0)
+        features = self.feature_encoder(both, normalise=True)
+        correlation_class = OnDemandCorrelation if self.correlation == "on_demand" else CorrelationPyramid
+        if check:  # entries 0 .. B - 1: ref -> cur; B .. 2B - 1: cur -> ref
+            pyramid = correlation_class(features, torch.cat([features[B:], features[:B]], dim=0), self.correlation_pyramid_levels, self.correlation_radius)
+            inp, net = self.context_encoder(both, normalise=True)
+        else:
+            pyramid = correlation_class(features[:B], features[B:], self.correlation_pyramid_levels, self.correlation_radius)
+            inp, net = self.context_encoder(ref_image, normalise=True)
+        ys, xs = torch.meshgrid(torch.arange(h, device=ref_image.device), torch.arange(w, device=ref_image.device), indexing="ij")
+        ref = torch.stack([xs, ys], dim=0).float()[None].repeat(2 * B if check else B, 1, 1, 1)
+        cur = ref
+        mask = None
+        for i in range(n):
+            correlation = pyramid.lookup(cur)
+            flow = cur - ref
+            net, mask, delta = self.update_block(net, inp, correlation, flow, want_mask=i == n - 1)
+            cur = cur + delta
+        flow = cur - ref
+        if check:
+            result = track_points_from_flow(flow[:B], mask[:B], points, (H, W), backward=(flow[B:], mask[B:]), forward_backward=forward_backward)
+        else:
+            result = track_points_from_flow(flow, mask, points, (H, W))
+        return result if return_error else result[:2]

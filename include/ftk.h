@@ -406,6 +406,34 @@ int ftk_corr_ondemand_lookup_device(ftk_context *ctx, void *stream, const float 
 int ftk_flow_upsample_device(ftk_context *ctx, void *stream, const float *d_flow, const float *d_mask, int32_t B, int32_t H, int32_t W,
                              float mask_scale, float *d_out);
 
+/* ---- Sparse tracking from RAFT's coarse flow ------------------------ */
+
+/* Feature points that one workgroup of the kernel owns: point counts just below, at and above a multiple of it are the ones a test of
+ * the entry below should cover. */
+#define FTK_FLOW_POINTS_TILE 64
+/* Tracks N feature points per batch entry through the flow that Raft.UpsampleFlow(flow, mask_scale * mask) (model.py:48-64) would give,
+ * without storing it: d_points [B][N][2] (u = x, v = y, image pixels) -> d_cur_points [B][N][2], d_status [B][N] (uint8, TrackStatus) and,
+ * when it is not NULL, d_fb_error2 [B][N].  Per point, in the operation order DESIGN.md 5.17 fixes:
+ *   inside(p) is 0 <= p.u <= image_cols - 1 and 0 <= p.v <= image_rows - 1 in float32 (NaN fails); a reference point that is not inside
+ *   is FTK_OUTSIDE with cur = ref;
+ *   S(p) is the bilinear sample at p of the fine flow, whose four values are the floats ftk_flow_upsample_device writes, the right and
+ *   lower neighbours clamped to the grid's last column and row; cur = ref + S(ref): non-finite is FTK_NUMERIC_ERROR with cur = ref, not
+ *   inside is FTK_OUTSIDE with cur as computed;
+ *   with the backward pair (d_flow_back, d_mask_back: both or neither), a point that is still inside gets e2 = |cur + S_back(cur) - ref|^2,
+ *   and FTK_LARGE_RESIDUAL unless e2 <= fb_threshold^2 (a NaN e2 is a large residual); otherwise FTK_TRACKED.
+ * d_fb_error2 is e2 where the check ran and 0 elsewhere.  1 <= image_rows <= 8H and 1 <= image_cols <= 8W: the image may be smaller than
+ * the grid (RAFT's encoders round sizes up), and a pixel of the grid outside the image is outside.  d_flow, d_flow_back: [B][2][H][W];
+ * d_mask, d_mask_back: [B][576][H][W]; all contiguous float32 on the context's device.  One launch on `stream` (a hipStream_t; NULL is
+ * the null stream), no allocation, no synchronisation: capturable at any time.  N = 0 is FTK_OK with no launch, and the three point
+ * buffers may then be NULL.
+ * FTK_E_INVALID_ARGUMENT, before any launch, for a null required pointer, a non-positive B, H or W or a negative N, 8H or 8W above 2^24
+ * (float32 coordinates name every fine pixel up to there), image_rows or image_cols out of range, a non-finite mask_scale, a negative
+ * or NaN fb_threshold, half a backward pair, or a mask whose byte count overflows int64. */
+int ftk_flow_track_points_device(ftk_context *ctx, void *stream, const float *d_flow, const float *d_mask, const float *d_flow_back,
+                                 const float *d_mask_back, int32_t B, int32_t H, int32_t W, int32_t N, int32_t image_rows, int32_t image_cols,
+                                 float mask_scale, float fb_threshold, const float *d_points, float *d_cur_points, uint8_t *d_status,
+                                 float *d_fb_error2);
+
 /* ---- RAFT separable ConvGRU (src/nn_optical_flow_tracker/raft/gru.py:46-76) ------------------------ */
 
 /*
