@@ -20,6 +20,9 @@ FTK_CORR_MAX_LEVELS = 16
 FTK_CORR_MAX_RADIUS = 64
 FTK_FLOW_UPSAMPLE_TILE = 32
 FTK_FLOW_POINTS_TILE = 64
+FTK_FLOW_WARM_TILE = 256
+FTK_FLOW_WARM_MAX_PIXELS = 1 << 20
+FTK_FLOW_WARM_MAX_SPLITS = 32
 # SepConvGru (include/ftk.h): the supported sizes and the packed weight layout
 FTK_SEP_CONV_GRU_MAX_PARTS = 3
 FTK_SEP_CONV_GRU_MAX_H_CHANNELS = 1024
@@ -49,7 +52,7 @@ EXPORTS = [
     "ftk_shard_bounds", "ftk_klt_shard_bytes", "ftk_comm_unique_id", "ftk_comm_create", "ftk_comm_destroy", "ftk_comm_rank", "ftk_comm_world",
     "ftk_klt_track_sharded_device", "ftk_klt_track_sharded", "ftk_klt_track_shard_device", "ftk_klt_unpack_shards_device", "ftk_hamming_match_sharded_device",
     "ftk_default_dense_flow_options", "ftk_dense_flow_gaussian", "ftk_dense_flow", "ftk_dense_flow_device", "ftk_dense_flow_level",
-    "ftk_corr_pyramid_layout", "ftk_corr_pyramid_build_device", "ftk_corr_pyramid_lookup_device", "ftk_flow_upsample_device", "ftk_flow_track_points_device",
+    "ftk_corr_pyramid_layout", "ftk_corr_pyramid_build_device", "ftk_corr_pyramid_lookup_device", "ftk_flow_upsample_device", "ftk_flow_track_points_device", "ftk_flow_warm_splits", "ftk_flow_warm_device",
     "ftk_corr_ondemand_layout", "ftk_corr_ondemand_prepare_device", "ftk_corr_ondemand_lookup_device",
     "ftk_sep_conv_gru_packed_elements", "ftk_sep_conv_gru_gates_device", "ftk_sep_conv_gru_blend_device",
     "ftk_conv2d_packed_elements", "ftk_conv2d_device", "ftk_conv2d_strided_device",
@@ -215,6 +218,8 @@ def lib() -> C.CDLL:
     l.ftk_corr_ondemand_lookup_device.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32]
     l.ftk_flow_upsample_device.argtypes = [vp, vp, vp, vp, i32, i32, i32, C.c_float, vp]
     l.ftk_flow_track_points_device.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, C.c_float, C.c_float, vp, vp, vp, vp]
+    l.ftk_flow_warm_splits.argtypes = [i32, i32, i32, C.POINTER(C.c_int32)]
+    l.ftk_flow_warm_device.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp]
     i64, f32 = C.c_int64, C.c_float
     parts = C.POINTER(GruPart)
     l.ftk_sep_conv_gru_packed_elements.argtypes = [i32, i32, i32, i64p]
@@ -266,6 +271,14 @@ def corr_ondemand_layout(B: int, C_: int, H: int, W: int, levels: int):
     lw = (C.c_int32 * max(n, 1))()
     check(lib().ftk_corr_ondemand_layout(int(B), int(C_), int(H), int(W), int(levels), C.byref(elements), off, lh, lw), None)
     return elements.value, [off[i] for i in range(n)], [(lh[i], lw[i]) for i in range(n)]
+
+
+def flow_warm_splits(B: int, H: int, W: int) -> int:
+    """ftk_flow_warm_splits (host only): the number of source ranges ftk_flow_warm_device should scan at these sizes; FtkError for a
+    non-positive size or H * W above FTK_FLOW_WARM_MAX_PIXELS."""
+    splits = C.c_int32()
+    check(lib().ftk_flow_warm_splits(int(B), int(H), int(W), C.byref(splits)), None)
+    return splits.value
 
 
 def sep_conv_gru_k_steps(in_channels: int, kernel_size: int) -> int:

@@ -411,6 +411,24 @@ struct FlowPointsParams {
 // hipErrorInvalidValue when the grid would not fit in 2^31 - 1 workgroups
 hipError_t flow_track_points_launch(const FlowPointsParams &p, hipStream_t stream);
 
+// The warm start of RAFT on video (raft_warm_kernels.hip, upstream RAFT's forward_interpolate): a scan launch, and with
+// more than one split of the sources a gather launch.
+constexpr int kFlowWarmTile = 256;               // targets per workgroup and sources per LDS tile (FTK_FLOW_WARM_TILE)
+constexpr int kFlowWarmMaxSplits = 32;           // FTK_FLOW_WARM_MAX_SPLITS
+constexpr int kFlowWarmMaxPixels = 1 << 20;      // FTK_FLOW_WARM_MAX_PIXELS: the search is exhaustive
+constexpr int kFlowWarmFillGroups = 1024;        // the automatic split count aims at this many workgroups: four per compute unit
+struct FlowWarmParams {
+    const float *flow;              // [B][2][H][W]
+    unsigned long long *workspace;  // [splits][B][H * W] keys, or null with one split
+    float *out;                     // [B][2][H][W]
+    int32_t B, H, W, splits;
+    int32_t split_sources;          // sources per split, whole tiles: set by the launch function
+};
+// The split count ftk_flow_warm_splits reports: ceil(kFlowWarmFillGroups / (B * tiles)) held to 1 .. min(tiles, kFlowWarmMaxSplits).
+int flow_warm_auto_splits(int32_t B, int32_t H, int32_t W);
+// hipErrorInvalidValue when the grid would not fit in 2^31 - 1 workgroups
+hipError_t flow_warm_launch(const FlowWarmParams &p, hipStream_t stream);
+
 // RAFT's separable ConvGRU (raft_gru_kernels.hip, SepConvGru.forward, gru.py:59-76): per pass a gates launch and a
 // candidate + blend launch, each an implicit GEMM on the f32-input matrix cores.
 // One tensor of an input that is a channel concatenation read in place (the GRU's and conv2d_kernel's segment lists).

@@ -20,6 +20,9 @@ correlation values a lookup reads when it reads them; ``Raft(..., correlation="o
 ``track_points_from_flow`` moves feature points by the bilinear sample of the upsampled flow without storing it and gives them a
 TrackStatus, with an optional forward-backward check, in one launch; ``Raft.track_points`` is the model as a feature tracker on top of it
 (DESIGN.md 5.17).
+``warm_start_flow`` pushes a coarse flow forward along itself (upstream RAFT's ``forward_interpolate``, on the device), ``flow_init`` /
+``return_flow`` pass the state of the refinement loop into and out of ``Raft``, and ``RaftVideoTracker`` runs the model over a frame
+sequence with the previous frame's feature map kept and each pair started from the previous pair's flow.
 Inference only, float32 only, and no CPU fallback.
 """
 from __future__ import annotations
@@ -274,6 +277,39 @@ def track_points_from_flow(flow, mask, points, image_size, mask_scale: float = 1
     D.flow_track_points_device(ctx, flow.contiguous(), mask.contiguous(), points.contiguous(), rows, cols, cur_points, status, fb_error2, mask_scale,
                                flow_back, mask_back, 0.0 if backward is None else float(forward_backward))
     return cur_points, status, fb_error2
+
+
+def warm_start_flow(flow):
+    """The warm start of RAFT on video: ``flow`` [B, 2, H, W] (float32 CUDA, channel 0 = x), the coarse flow of one image
+    pair, pushed forward along itself as the start of the next pair, in place of upstream RAFT's ``forward_interpolate`` (scipy's
+    ``griddata(method="nearest")`` on the host).  Source pixel ``(x, y)`` lands at ``(x + flow_x, y + flow_y)`` and is valid strictly
+    inside ``(0, W) x (0, H)``; every pixel of the new [B, 2, H, W] tensor takes both components of the valid landing nearest to it
+    (``d2 = fmaf(ey, ey, ex * ex)`` in float32, the lowest source index among equal distances); an entry without a valid landing is all
+    +0.  ``H * W`` is at most ``FTK_FLOW_WARM_MAX_PIXELS`` = 2^20: the search is exhaustive.  One launch of raft_warm_kernels.hip on
+    torch's current stream, or two through a workspace that torch owns when the sources are split to fill the chip; no synchronisation,
+    capturable.  Arguments are checked before any device is touched."""
+    import torch
+
+    if not isinstance(flow, torch.Tensor) or flow.dtype != torch.float32 or flow.dim() != 4 or flow.size(1) != 2:
+        got = f"{flow.dtype} {list(flow.shape)}" if isinstance(flow, torch.Tensor) else type(flow).__name__
+        raise ValueError(f"flow must be a 4-D float32 CUDA tensor [B, 2, H, W] (no CPU fallback, no other dtype): got {got}")
+    B, _, H, W = (int(e) for e in flow.shape)
+    if B < 1 or H < 1 or W < 1:
+        raise ValueError(f"flow must not be empty (got {tuple(flow.shape)})")
+    if H * W > N.FTK_FLOW_WARM_MAX_PIXELS:
+        raise ValueError(f"flow of {H} x {W} pixels is above FTK_FLOW_WARM_MAX_PIXELS = {N.FTK_FLOW_WARM_MAX_PIXELS}: the search is exhaustive")
+    if not flow.is_contiguous():
+        raise ValueError(f"flow must be contiguous (got strides {list(flow.stride())}): pass flow.contiguous()")
+    _check_no_grad(torch, flow, what="warm_start_flow")
+    if not flow.is_cuda:
+        raise ValueError(f"flow must be a CUDA tensor (got it on {flow.device}): there is no CPU fallback")
+    torch = D._torch()
+    ctx = _device_context(flow)
+    splits = N.flow_warm_splits(B, H, W)
+    out = torch.empty_like(flow)
+    workspace = torch.empty(splits * B * H * W, dtype=torch.int64, device=flow.device) if splits > 1 else None
+    D.flow_warm_device(ctx, flow, out, splits, workspace)
+    return out
 
 
 class SepConvGru:
@@ -871,54 +907,73 @@ class Raft:
             raise ValueError(f"the weights are on several devices: {sorted(devices)}")
         return cls(features, context, block, correlation_pyramid_levels, correlation_radius, max_iterations, correlation)
 
-    def __call__(self, ref_image, cur_image, iterations: int = None):
-        """``Raft.forward``: float32 CUDA images [B, in_channels, H, W] in 0 .. 255 give ``iterations`` (default ``max_iterations``) new
-        tensors [B, 2, 8h, 8w], h = H halved three times rounding up (a 60 x 60 image gives 64 x 64; nothing is cropped).  Every argument
-        is checked before the first launch; on torch's current stream, capturable at fixed shapes."""
+    @staticmethod
+    def _check_flow_init(flow_init, pair: bool, B: int, h: int, w: int, device) -> None:
+        """``flow_init`` of a call: None, a float32 tensor [B, 2, h, w] on ``device``, the images', or, with the forward-backward check
+        (``pair``), a (forward, backward) pair of them."""
         import torch
 
-        n = self.max_iterations if iterations is None else int(iterations)
-        if n < 1:
-            raise ValueError(f"iterations {iterations} must be at least 1")
-        enc = self.feature_encoder
-        for name, t in (("ref_image", ref_image), ("cur_image", cur_image)):
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 4 or t.size(1) != enc.in_channels:
+        if flow_init is None:
+            return
+        if pair and (not isinstance(flow_init, (tuple, list)) or len(flow_init) != 2):
+            raise ValueError(f"flow_init must be a (forward_init, backward_init) pair with forward_backward (got {type(flow_init).__name__})")
+        named = [("flow_init[0]", flow_init[0]), ("flow_init[1]", flow_init[1])] if pair else [("flow_init", flow_init)]
+        for name, t in named:
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (B, 2, h, w):
                 got = f"{t.dtype} {list(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
-                raise ValueError(f"{name} must be a 4-D float32 CUDA tensor [B, {enc.in_channels}, H, W] (no CPU fallback, no other dtype): got {got}")
-        if ref_image.size() != cur_image.size() or ref_image.device != cur_image.device:
-            raise ValueError(f"The size of the reference and current images should be the same: {tuple(ref_image.shape)} on {ref_image.device} vs "
-                             f"{tuple(cur_image.shape)} on {cur_image.device}")
-        B, _, H, W = (int(e) for e in ref_image.shape)
-        _check_maps("Raft", [("ref_image", ref_image, enc.in_channels), ("cur_image", cur_image, enc.in_channels)], enc._weights_device())
-        h, w = ((((e + 1) // 2 + 1) // 2 + 1) // 2 for e in (H, W))  # three stride-2 layers, each ceil(e / 2)
-        try:
-            if self.correlation == "on_demand":  # the level rules alone: no volume is sized, none will exist
-                N.corr_ondemand_layout(B, enc.out_channels, h, w, self.correlation_pyramid_levels)
-            else:
-                N.corr_pyramid_layout(B, h, w, self.correlation_pyramid_levels)
-        except N.FtkError as e:
-            raise ValueError(f"images of {H} x {W} give {h} x {w} feature maps, too small for {self.correlation_pyramid_levels} correlation levels: "
-                             f"{e}") from None
-        features = enc(torch.cat([ref_image, cur_image], dim=0), normalise=True)
+                raise ValueError(f"{name} must be a float32 CUDA tensor [{B}, 2, {h}, {w}], the coarse flow of these images (no CPU fallback, no other "
+                                 f"dtype): got {got}")
+            if t.device != device:
+                raise ValueError(f"{name} must be on {device}, with the images (got it on {t.device})")
+        _check_no_grad(torch, *[t for _, t in named], what="Raft")
+
+    def _refine(self, fmap0, fmap1, inp, net, n: int, flow_init=None, want_mask: str = "every"):
+        """model.py:82-95, the refinement loop on its own: the correlation object of the feature maps ``fmap0`` and ``fmap1`` [B', C, h, w],
+        ``n`` iterations from ``cur = ref`` or, with ``flow_init`` [B', 2, h, w], from ``cur = ref + flow_init`` (upstream's ``coords1 =
+        coords1 + flow_init``), with ``inp`` and ``net`` of the context encoder.  ``want_mask``: "every" runs the mask head and
+        ``upsample_flow`` in every iteration (``__call__``), "last" the mask head in the last iteration alone (``track_points``), "never"
+        not at all.  Returns (the last ``cur - ref``, the last mask or None, the predictions of "every").  Everything was checked by the
+        caller."""
+        import torch
+
         correlation_class = OnDemandCorrelation if self.correlation == "on_demand" else CorrelationPyramid
-        pyramid = correlation_class(features[:B], features[B:], self.correlation_pyramid_levels, self.correlation_radius)
-        inp, net = self.context_encoder(ref_image, normalise=True)
-        ys, xs = torch.meshgrid(torch.arange(h, device=ref_image.device), torch.arange(w, device=ref_image.device), indexing="ij")
-        ref = torch.stack([xs, ys], dim=0).float()[None].repeat(B, 1, 1, 1)  # InitializeFlow, model.py:34-45: x in channel 0
-        cur = ref
-        predictions = []
-        for _ in range(n):
+        pyramid = correlation_class(fmap0, fmap1, self.correlation_pyramid_levels, self.correlation_radius)
+        batch, _, h, w = fmap0.shape
+        ys, xs = torch.meshgrid(torch.arange(h, device=fmap0.device), torch.arange(w, device=fmap0.device), indexing="ij")
+        ref = torch.stack([xs, ys], dim=0).float()[None].repeat(batch, 1, 1, 1)  # InitializeFlow, model.py:34-45: x in channel 0
+        cur = ref if flow_init is None else ref + flow_init
+        predictions, mask, flow = [], None, None
+        for i in range(n):
             correlation = pyramid.lookup(cur)
             flow = cur - ref
-            net, mask, delta = self.update_block(net, inp, correlation, flow)
+            net, mask, delta = self.update_block(net, inp, correlation, flow, want_mask=want_mask == "every" or (want_mask == "last" and i == n - 1))
             cur = cur + delta
-            predictions.append(upsample_flow(cur - ref, mask))
-        return predictions
+            if want_mask == "every":
+                flow = cur - ref
+                predictions.append(upsample_flow(flow, mask))
+        if want_mask != "every":
+            flow = cur - ref
+        return flow, mask, predictions
 
-    def _check_pair(self, ref_image, cur_image, points, iterations, stacked: bool):
-        """The argument checks of ``__call__`` for ``track_points``, with those of ``points`` placed before the complaint about where the
-        tensors are, so that each is also made on a machine without a device; ``stacked``: the loop will run at batch 2B.  Returns
-        (n, B, H, W, h, w)."""
+    def __call__(self, ref_image, cur_image, iterations: int = None, flow_init=None, return_flow: bool = False):
+        """``Raft.forward``: float32 CUDA images [B, in_channels, H, W] in 0 .. 255 give ``iterations`` (default ``max_iterations``) new
+        tensors [B, 2, 8h, 8w], h = H halved three times rounding up (a 60 x 60 image gives 64 x 64; nothing is cropped).  ``flow_init``
+        [B, 2, h, w] (float32, the images' device) starts the loop from ``ref + flow_init`` instead of ``ref``, as upstream's
+        ``flow_init`` does; ``return_flow=True`` returns ``(predictions, flow)`` with the last iteration's coarse ``cur - ref`` [B, 2, h, w],
+        what ``warm_start_flow`` takes.  Every argument is checked before the first launch; on torch's current stream, capturable at fixed
+        shapes."""
+        import torch
+
+        n, B, H, W, h, w = self._check_pair(ref_image, cur_image, None, iterations, False, flow_init)
+        features = self.feature_encoder(torch.cat([ref_image, cur_image], dim=0), normalise=True)
+        inp, net = self.context_encoder(ref_image, normalise=True)
+        flow, _, predictions = self._refine(features[:B], features[B:], inp, net, n, flow_init, "every")
+        return (predictions, flow) if return_flow else predictions
+
+    def _check_pair(self, ref_image, cur_image, points, iterations, stacked: bool, flow_init=None):
+        """The argument checks of a call on an image pair, with those of ``points`` (None: the call takes none) and of ``flow_init`` placed
+        before the complaint about where the tensors are, so that each is also made on a machine without a device; ``stacked``: the loop
+        will run at batch 2B and ``flow_init`` is a pair.  Returns (n, B, H, W, h, w)."""
         import torch
 
         n = self.max_iterations if iterations is None else int(iterations)
@@ -933,12 +988,14 @@ class Raft:
             raise ValueError(f"The size of the reference and current images should be the same: {tuple(ref_image.shape)} on {ref_image.device} vs "
                              f"{tuple(cur_image.shape)} on {cur_image.device}")
         B, _, H, W = (int(e) for e in ref_image.shape)
-        _check_points(points, B, ref_image.device)
-        _check_no_grad(torch, points, what="Raft")
-        _check_maps("Raft", [("ref_image", ref_image, enc.in_channels), ("cur_image", cur_image, enc.in_channels)], enc._weights_device())
+        if points is not None:
+            _check_points(points, B, ref_image.device)
+            _check_no_grad(torch, points, what="Raft")
         h, w = ((((e + 1) // 2 + 1) // 2 + 1) // 2 for e in (H, W))  # three stride-2 layers, each ceil(e / 2)
+        self._check_flow_init(flow_init, stacked, B, h, w, ref_image.device)
+        _check_maps("Raft", [("ref_image", ref_image, enc.in_channels), ("cur_image", cur_image, enc.in_channels)], enc._weights_device())
         try:
-            if self.correlation == "on_demand":
+            if self.correlation == "on_demand":  # the level rules alone: no volume is sized, none will exist
                 N.corr_ondemand_layout(2 * B if stacked else B, enc.out_channels, h, w, self.correlation_pyramid_levels)
             else:
                 N.corr_pyramid_layout(2 * B if stacked else B, h, w, self.correlation_pyramid_levels)
@@ -947,44 +1004,122 @@ class Raft:
                              f"{e}") from None
         return n, B, H, W, h, w
 
-    def track_points(self, ref_image, cur_image, points, iterations: int = None, forward_backward: float = None, return_error: bool = False):
+    def _track(self, flow, mask, points, size, B: int, forward_backward, return_error: bool, return_flow: bool):
+        """The end of a tracking call: the points launch on the loop's last flow and mask ([2B, ...] with the check: forward, then backward),
+        and the result tuple as ``track_points`` documents it."""
+        check = forward_backward is not None
+        if check:
+            result = track_points_from_flow(flow[:B], mask[:B], points, size, backward=(flow[B:], mask[B:]), forward_backward=forward_backward)
+        else:
+            result = track_points_from_flow(flow, mask, points, size)
+        result = result if return_error else result[:2]
+        return result + (((flow[:B], flow[B:]) if check else flow),) if return_flow else result
+
+    def track_points(self, ref_image, cur_image, points, iterations: int = None, forward_backward: float = None, return_error: bool = False,
+                     flow_init=None, return_flow: bool = False):
         """RAFT as a feature tracker: ``points`` [B, N, 2] (float32 CUDA, ``(x, y)`` pixels of ``ref_image``) give
         ``(cur_points [B, N, 2], status [B, N] uint8)``, the points in ``cur_image`` and their TrackStatus, as ``track_points_from_flow``
         defines them on the last iteration's coarse flow and mask with the images' own ``(H, W)`` as ``image_size``: bit for bit what
         sampling ``self(ref_image, cur_image)[-1]`` bilinearly at the points gives.  The loop is ``__call__``'s without the mask head in all
-        but the last iteration and without any ``upsample_flow``: 36 + 13 * iterations - 2 * (iterations - 1) + 1 launches.
+        but the last iteration and without any ``upsample_flow``: 36 + 14 * iterations - 2 * (iterations - 1) + 1 launches (a lookup and
+        UpdateBlock's 13 per iteration).
         ``forward_backward=t`` (pixels, finite, >= 0) adds the forward-backward check: the feature encoder still runs once, the loop runs
         at batch 2B on the pair and the swapped pair, and the two halves of the last iteration are the forward and the backward flow of one
         launch; a tracked point that does not come back within ``t`` pixels is ``LARGE_RESIDUAL``.  ``return_error=True`` appends
-        ``fb_error2`` [B, N] (``None`` without the check).  Every argument is checked before the first launch; on torch's current stream,
-        capturable at fixed shapes."""
+        ``fb_error2`` [B, N] (``None`` without the check).  ``flow_init`` [B, 2, h, w] starts the loop from ``ref + flow_init`` as in
+        ``__call__``; with the check it is a ``(forward_init, backward_init)`` pair.  ``return_flow=True`` appends the last iteration's
+        coarse ``cur - ref`` [B, 2, h, w], with the check the pair ``(forward, backward)``.  Every argument is checked before the first
+        launch; on torch's current stream, capturable at fixed shapes."""
         import torch
 
         check = forward_backward is not None
         if check and (not float(forward_backward) >= 0 or not math.isfinite(float(forward_backward))):
             raise ValueError(f"forward_backward must be a finite number of pixels >= 0 (got {forward_backward})")
-        n, B, H, W, h, w = self._check_pair(ref_image, cur_image, points, iterations, check)
+        n, B, H, W, h, w = self._check_pair(ref_image, cur_image, points, iterations, check, flow_init)
+        if check and flow_init is not None:
+            flow_init = torch.cat([flow_init[0], flow_init[1]], dim=0)
         both = torch.cat([ref_image, cur_image], dim=0)
         features = self.feature_encoder(both, normalise=True)
-        correlation_class = OnDemandCorrelation if self.correlation == "on_demand" else CorrelationPyramid
         if check:  # entries 0 .. B - 1: ref -> cur; B .. 2B - 1: cur -> ref
-            pyramid = correlation_class(features, torch.cat([features[B:], features[:B]], dim=0), self.correlation_pyramid_levels, self.correlation_radius)
+            fmap0, fmap1 = features, torch.cat([features[B:], features[:B]], dim=0)
             inp, net = self.context_encoder(both, normalise=True)
         else:
-            pyramid = correlation_class(features[:B], features[B:], self.correlation_pyramid_levels, self.correlation_radius)
+            fmap0, fmap1 = features[:B], features[B:]
             inp, net = self.context_encoder(ref_image, normalise=True)
-        ys, xs = torch.meshgrid(torch.arange(h, device=ref_image.device), torch.arange(w, device=ref_image.device), indexing="ij")
-        ref = torch.stack([xs, ys], dim=0).float()[None].repeat(2 * B if check else B, 1, 1, 1)
-        cur = ref
-        mask = None
-        for i in range(n):
-            correlation = pyramid.lookup(cur)
-            flow = cur - ref
-            net, mask, delta = self.update_block(net, inp, correlation, flow, want_mask=i == n - 1)
-            cur = cur + delta
-        flow = cur - ref
-        if check:
-            result = track_points_from_flow(flow[:B], mask[:B], points, (H, W), backward=(flow[B:], mask[B:]), forward_backward=forward_backward)
+        flow, mask, _ = self._refine(fmap0, fmap1, inp, net, n, flow_init, "last")
+        return self._track(flow, mask, points, (H, W), B, forward_backward, return_error, return_flow)
+
+
+class RaftVideoTracker:
+    """``Raft.track_points`` over a frame sequence.  ``track(image, points)`` treats the frame of the previous call as
+    ``ref_image`` and ``image`` as ``cur_image`` and returns what ``raft.track_points(previous, image, points, iterations,
+    forward_backward, return_error)`` returns, ``points`` in the previous frame's pixels; then ``image`` becomes the stored frame.
+    Two things carry over from pair to pair.  The feature map: the feature encoder runs once per frame, on the new image at batch B,
+    and the previous frame's map is kept (an output element of ``conv2d_kernel`` is one k-ordered ``fmaf`` chain whatever the batch, so
+    the kept map is bit for bit the half of the stacked call's).  The flow, with ``warm_start=True``: a pair's loop starts from
+    ``warm_start_flow`` of the previous pair's coarse flow, as upstream RAFT's video mode does, with the check each direction from its own;
+    the first pair after construction or ``reset()`` starts from zero.  With ``warm_start=False`` every pair starts from zero and the
+    results are ``track_points``' bit for bit.
+    Launches per frame, ``track_points``' count with the encoder's 17 at batch B instead of 2B: 36 + 14 * iterations - 2 * (iterations - 1)
+    + 1, plus ``warm_start_flow``'s one or two (one call over both directions of the check) from the second pair on; ``points=None``
+    saves the points launch and the mask head's two.  The context encoder is not cached: it runs on the previous image (on both with the
+    check), which is kept as a copy.  Not capturable as a whole: a call changes the state of the object."""
+
+    def __init__(self, raft: Raft, iterations: int = None, warm_start: bool = True, forward_backward: float = None):
+        if not isinstance(raft, Raft):
+            raise ValueError(f"raft must be a Raft (got {type(raft).__name__})")
+        n = raft.max_iterations if iterations is None else int(iterations)
+        if n < 1:
+            raise ValueError(f"iterations {iterations} must be at least 1")
+        if forward_backward is not None and (not float(forward_backward) >= 0 or not math.isfinite(float(forward_backward))):
+            raise ValueError(f"forward_backward must be a finite number of pixels >= 0 (got {forward_backward})")
+        self.raft, self.iterations, self.warm_start = raft, n, bool(warm_start)
+        self.forward_backward = None if forward_backward is None else float(forward_backward)
+        self.reset()
+
+    def reset(self) -> None:
+        """Drops the stored frame and flow: the next ``track`` is a first call."""
+        self._image, self._features, self._flow = None, None, None
+
+    @property
+    def last_flow(self):
+        """The last pair's coarse flow [B, 2, h, w], with the check the pair ``(forward, backward)``; None before the second frame."""
+        if self._flow is None or self.forward_backward is None:
+            return self._flow
+        B = self._flow.size(0) // 2
+        return self._flow[:B], self._flow[B:]
+
+    def track(self, image, points=None, return_error: bool = False):
+        """The first call after construction or ``reset()`` encodes and stores ``image`` [B, in_channels, H, W] (float32 CUDA, 0 .. 255)
+        and returns None.  Every later call returns ``(cur_points, status)``, with ``return_error=True`` and ``fb_error2``, of ``points``
+        [B, N, 2] (pixels of the previous frame) in ``image``, or None for ``points=None``, which only advances the state.  A frame whose
+        shape, dtype or device differs from the stored one is a ValueError.  Every argument is checked before the first launch."""
+        import torch
+
+        raft, check = self.raft, self.forward_backward is not None
+        first = self._image is None
+        channels = raft.feature_encoder.in_channels
+        if not isinstance(image, torch.Tensor) or image.dtype != torch.float32 or image.dim() != 4 or image.size(1) != channels:
+            got = f"{image.dtype} {list(image.shape)}" if isinstance(image, torch.Tensor) else type(image).__name__
+            raise ValueError(f"image must be a 4-D float32 CUDA tensor [B, {channels}, H, W] (no CPU fallback, no other dtype): got {got}")
+        if not first and (image.shape, image.device) != (self._image.shape, self._image.device):
+            raise ValueError(f"this frame is {image.dtype} {list(image.shape)} on {image.device}, the stored one {self._image.dtype} "
+                             f"{list(self._image.shape)} on {self._image.device}: call reset() before a sequence of another shape")
+        previous = image if first else self._image
+        _, B, H, W, _, _ = raft._check_pair(previous, image, None if first else points, self.iterations, check)
+        features = raft.feature_encoder(image, normalise=True)
+        if first:
+            self._image, self._features = image.clone(), features
+            return None
+        if check:  # entries 0 .. B - 1: previous -> image; B .. 2B - 1: image -> previous
+            fmap0, fmap1 = torch.cat([self._features, features], dim=0), torch.cat([features, self._features], dim=0)
+            inp, net = raft.context_encoder(torch.cat([previous, image], dim=0), normalise=True)
         else:
-            result = track_points_from_flow(flow, mask, points, (H, W))
-        return result if return_error else result[:2]
+            fmap0, fmap1 = self._features, features
+            inp, net = raft.context_encoder(previous, normalise=True)
+        flow_init = warm_start_flow(self._flow) if self.warm_start and self._flow is not None else None
+        flow, mask, _ = raft._refine(fmap0, fmap1, inp, net, self.iterations, flow_init, "never" if points is None else "last")
+        self._image, self._features, self._flow = image.clone(), features, flow
+        if points is None:
+            return None
+        return raft._track(flow, mask, points, (H, W), B, self.forward_backward, return_error, False)

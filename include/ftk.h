@@ -434,6 +434,33 @@ int ftk_flow_track_points_device(ftk_context *ctx, void *stream, const float *d_
                                  float mask_scale, float fb_threshold, const float *d_points, float *d_cur_points, uint8_t *d_status,
                                  float *d_fb_error2);
 
+/* ---- The warm start of RAFT on video ------------------------ */
+
+/* Targets that one workgroup of the kernel owns, and sources of one LDS tile: pixel counts just below, at and above a multiple of it
+ * are the ones a test of the entry below should cover. */
+#define FTK_FLOW_WARM_TILE 256
+/* The search is all targets against all sources: H * W is held to this. */
+#define FTK_FLOW_WARM_MAX_PIXELS (1 << 20)
+#define FTK_FLOW_WARM_MAX_SPLITS 32
+/* Host only: the number of source ranges ("splits") the entry below should be called with at these sizes, 1 .. FTK_FLOW_WARM_MAX_SPLITS,
+ * chosen so that the scan fills the chip; FTK_E_INVALID_ARGUMENT for a non-positive size or H * W above FTK_FLOW_WARM_MAX_PIXELS. */
+int ftk_flow_warm_splits(int32_t B, int32_t H, int32_t W, int32_t *splits);
+/* Replaces upstream RAFT's forward_interpolate (core/utils/utils.py: scipy.interpolate.griddata(method="nearest") on the host, per batch
+ * entry): the coarse flow d_flow [B][2][H][W] (channel 0 = x) pushed forward along itself into d_out [B][2][H][W], both contiguous float32
+ * on the context's device and distinct.  In float32, in the operation order DESIGN.md 5.18 fixes: source pixel s = y W + x lands at
+ * x1 = (float)x + flow[b][0][y][x], y1 = (float)y + flow[b][1][y][x] and is valid iff x1 > 0 && x1 < (float)W && y1 > 0 && y1 < (float)H
+ * (a NaN or infinite landing is not); target (tx, ty) takes both components of the valid source with the least
+ * d2 = fmaf(ey, ey, ex * ex), ex = (float)tx - x1, ey = (float)ty - y1, the least s among equal d2, as copies of its two input floats;
+ * a batch entry without a valid source is all +0.  Batch entries are independent.
+ * `splits` = 1: one launch, d_workspace may be NULL.  2 .. FTK_FLOW_WARM_MAX_SPLITS: the sources are scanned in that many ranges by as
+ * many times the workgroups, and a second launch combines them through d_workspace, splits * B * H * W 64-bit words that need no
+ * initialisation.  The result does not depend on `splits`.  On `stream` (a hipStream_t; NULL is the null stream), no allocation, no
+ * synchronisation: capturable at any time.
+ * FTK_E_INVALID_ARGUMENT, before any launch, for a null pointer (the workspace with splits > 1 too), d_out == d_flow, a non-positive
+ * size, H * W above FTK_FLOW_WARM_MAX_PIXELS or splits out of range; a grid beyond 2^31 - 1 workgroups is FTK_E_HIP. */
+int ftk_flow_warm_device(ftk_context *ctx, void *stream, const float *d_flow, int32_t B, int32_t H, int32_t W, int32_t splits,
+                         uint64_t *d_workspace, float *d_out);
+
 /* ---- RAFT separable ConvGRU (src/nn_optical_flow_tracker/raft/gru.py:46-76) ------------------------ */
 
 /*
