@@ -23,6 +23,11 @@ FTK_FLOW_POINTS_TILE = 64
 FTK_FLOW_WARM_TILE = 256
 FTK_FLOW_WARM_MAX_PIXELS = 1 << 20
 FTK_FLOW_WARM_MAX_SPLITS = 32
+# masked Harris detection and the track table (include/ftk.h)
+FTK_HARRIS_DEVICE_MAX_SURVIVORS = 65536
+FTK_HARRIS_RANK_TILE = 256
+FTK_TRACK_TABLE_MAX_SLOTS = 65536
+FTK_TRACK_TABLE_BLOCK = 1024
 # SepConvGru (include/ftk.h): the supported sizes and the packed weight layout
 FTK_SEP_CONV_GRU_MAX_PARTS = 3
 FTK_SEP_CONV_GRU_MAX_H_CHANNELS = 1024
@@ -57,6 +62,7 @@ EXPORTS = [
     "ftk_sep_conv_gru_packed_elements", "ftk_sep_conv_gru_gates_device", "ftk_sep_conv_gru_blend_device",
     "ftk_conv2d_packed_elements", "ftk_conv2d_device", "ftk_conv2d_strided_device",
     "ftk_nn_match_scores_device", "ftk_nn_match_scores", "ftk_nn_match_list_device", "ftk_nn_match_list", "ftk_nn_fill_pixels_device",
+    "ftk_harris_detect_device", "ftk_track_table_retire_device", "ftk_track_table_fill_device",
 ]
 UNIQUE_ID_BYTES = 128
 
@@ -233,6 +239,9 @@ def lib() -> C.CDLL:
     l.ftk_nn_match_list_device.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
     l.ftk_nn_match_list.argtypes = [vp, vp, i32, i32, i32, vp, vp, C.POINTER(C.c_int)]
     l.ftk_nn_fill_pixels_device.argtypes = [vp, vp, vp, i32, vp, i32, vp]
+    l.ftk_harris_detect_device.argtypes = [vp, vp, i32, i32, i32, f32, vp, vp, i32, vp, vp]
+    l.ftk_track_table_retire_device.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, f32, vp, vp]
+    l.ftk_track_table_fill_device.argtypes = [vp, vp, i32, i32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     _lib = l
     return l
 

@@ -180,6 +180,55 @@ __global__ void __launch_bounds__(256) harris_collect_kernel(long long total, co
     }
 }
 
+
+// ---------------------------------------------------------------------------------------------
+// Masked detection (ftk_harris_detect_device, the track table's fill): points that already exist stamp one pixel
+// each into a byte plane; a candidate with a stamp within `reach` (Chebyshev) loses its key BEFORE the window maximum, so it neither
+// survives nor suppresses anybody.  The plane is dilated along rows for every pixel, along columns only where a candidate sits.
+// ---------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) harris_stamp_kernel(int rows, int cols, const float *uv, const uint8_t *flags, const long long *ids, int n,
+                                                           uint8_t *plane) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n || (flags && flags[i] == 0) || (ids && ids[i] < 0)) {
+        return;
+    }
+    // clamp((int)floorf(x + 0.5f), 0, cols - 1), the clamp taken in float so that no value is out of int's range (NaN: pixel 0)
+    const float fx = fminf(fmaxf(floorf(uv[2 * i] + 0.5f), 0.0f), (float)(cols - 1));
+    const float fy = fminf(fmaxf(floorf(uv[2 * i + 1] + 0.5f), 0.0f), (float)(rows - 1));
+    plane[(long long)(int)fy * cols + (int)fx] = 1;
+}
+
+__global__ void __launch_bounds__(256) harris_dilate_rows_kernel(int rows, int cols, int reach, const uint8_t *plane, uint8_t *out) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)rows * cols) {
+        return;
+    }
+    const int r = (int)(i / cols), c = (int)(i - (long long)r * cols);
+    const int lo = max(c - reach, 0), hi = min(c + reach, cols - 1);
+    const uint8_t *row = plane + (long long)r * cols;
+    uint8_t m = 0;
+    for (int cc = lo; cc <= hi; ++cc) {
+        m |= row[cc];
+    }
+    out[i] = m;
+}
+
+__global__ void __launch_bounds__(256) harris_block_kernel(int rows, int cols, int reach, const uint8_t *dilated_rows, unsigned long long *key) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)rows * cols || key[i] == 0ull) {
+        return;
+    }
+    const int r = (int)(i / cols), c = (int)(i - (long long)r * cols);
+    const int lo = max(r - reach, 0), hi = min(r + reach, rows - 1);
+    uint8_t m = 0;
+    for (int rr = lo; rr <= hi; ++rr) {
+        m |= dilated_rows[(long long)rr * cols + c];
+    }
+    if (m) {
+        key[i] = 0ull;
+    }
+}
+
 }  // namespace
 
 hipError_t harris_launch(const HarrisParams &p, hipStream_t stream) {
@@ -198,6 +247,33 @@ hipError_t harris_launch(const HarrisParams &p, hipStream_t stream) {
         }
         hipLaunchKernelGGL(harris_collect_kernel, dim3(blocks), dim3(256), 0, stream, total, p.key, p.wmax, p.list, p.count, p.capacity);
     }
+    return hipGetLastError();
+}
+
+hipError_t harris_masked_launch(const HarrisParams &p, const HarrisOccupied &o, hipStream_t stream) {
+    const long long total = (long long)p.img.rows * p.img.cols;
+    const unsigned blocks = (unsigned)((total + 255) / 256);
+    const int reach = (p.min_distance > 1 ? p.min_distance : 1) - 1;
+    hipLaunchKernelGGL(harris_gradient_kernel, dim3(blocks), dim3(256), 0, stream, p.img, p.gx, p.gy);
+    hipLaunchKernelGGL(harris_response_kernel, dim3(blocks), dim3(256), 0, stream, p.img.rows, p.img.cols, p.gx, p.gy, p.min_response, p.response,
+                       p.key);
+    if (o.n > 0) {
+        hipError_t e = hipMemsetAsync(o.plane, 0, (size_t)total, stream);
+        if (e != hipSuccess) {
+            return e;
+        }
+        hipLaunchKernelGGL(harris_stamp_kernel, dim3((unsigned)((o.n + 255) / 256)), dim3(256), 0, stream, p.img.rows, p.img.cols, o.uv, o.flags, o.ids, o.n,
+                           o.plane);
+        hipLaunchKernelGGL(harris_dilate_rows_kernel, dim3(blocks), dim3(256), 0, stream, p.img.rows, p.img.cols, reach, o.plane, o.dilated);
+        hipLaunchKernelGGL(harris_block_kernel, dim3(blocks), dim3(256), 0, stream, p.img.rows, p.img.cols, reach, o.dilated, p.key);
+    }
+    hipLaunchKernelGGL(harris_window_max_kernel, dim3(blocks), dim3(256), 0, stream, p.img.rows, p.img.cols, reach, 1, p.key, p.tmp);
+    hipLaunchKernelGGL(harris_window_max_kernel, dim3(blocks), dim3(256), 0, stream, p.img.rows, p.img.cols, reach, 0, p.tmp, p.wmax);
+    hipError_t e = hipMemsetAsync(p.count, 0, sizeof(unsigned), stream);
+    if (e != hipSuccess) {
+        return e;
+    }
+    hipLaunchKernelGGL(harris_collect_kernel, dim3(blocks), dim3(256), 0, stream, total, p.key, p.wmax, p.list, p.count, p.capacity);
     return hipGetLastError();
 }
 

@@ -288,6 +288,58 @@ struct HarrisParams {
     float min_response;
 };
 hipError_t harris_launch(const HarrisParams &p, hipStream_t stream);
+// Points that already exist (masked detection): point i counts where flags[i] != 0 (flags null: everywhere) and
+// ids[i] >= 0 (ids null: everywhere); plane / dilated: rows*cols bytes each of workspace.  n == 0: no masking, no workspace.
+struct HarrisOccupied {
+    const float *uv;
+    const uint8_t *flags;
+    const long long *ids;
+    int32_t n;
+    uint8_t *plane, *dilated;
+};
+// harris_launch's passes with the occupied points' neighbourhoods taken out of the candidates first; p.list must be set, and
+// p.capacity entries suffice when it is the plan's bound (track_table_plan.h).
+hipError_t harris_masked_launch(const HarrisParams &p, const HarrisOccupied &o, hipStream_t stream);
+
+// The track table (track_table_kernels.hip, KltVideoTracker): fixed slots, torch-owned.
+struct TrackTable {
+    long long *ids;        // [n] -1 = empty
+    float *points;         // [n][2]
+    float *prev_points;    // [n][2]
+    uint8_t *status;       // [n]
+    int32_t *age;          // [n]
+    int32_t *n_live;       // [1]
+    long long *next_id;    // [1]
+    int32_t n;
+};
+struct TrackRetireParams {
+    TrackTable t;
+    const float *tracked_uv;        // [n][2] the forward call's results
+    const uint8_t *tracked_status;  // [n]
+    const float *back_uv;           // both or neither: the backward call's results
+    const uint8_t *back_status;
+    float fb_threshold;
+    int32_t *free_slots;            // [n] out: the empty slots in ascending order
+    int32_t *n_free;                // [1] out
+    int32_t per_thread;             // the plan's retire_per_thread
+};
+struct HarrisRankParams {
+    const unsigned long long *list;  // the survivors' keys in any order
+    const unsigned *count;           // how many (device word)
+    unsigned capacity;
+    int32_t cols;
+    float *uv_out;                   // detection: [max_count][2], zeroed before the launch; null: fill the table
+    int32_t *count_out;
+    int32_t max_count;
+    TrackTable t;                    // fill
+    const int32_t *free_slots;
+    const int32_t *n_free;
+};
+struct TrackTablePlan;
+hipError_t track_table_retire_launch(const TrackTablePlan &plan, const TrackRetireParams &p, hipStream_t stream);
+// Ranks the survivors (rank = survivors with a greater key) and writes rows (uv_out) or table slots; in fill mode a second, one-thread
+// launch advances next_id and n_live.
+hipError_t harris_rank_launch(const TrackTablePlan &plan, const HarrisRankParams &p, hipStream_t stream);
 
 // Dense optical flow (dense_flow_kernels.hip, DenseOpticalFlow).  Moments: two float4 per pixel, {S0, Sr, Sc, Src} then {Srr, Scc, 0, 0},
 // row-major at the image's own size; flow planes row-major at the ref level's size.

@@ -106,6 +106,7 @@ def context_on_stream(stream, device_index: Optional[int] = None) -> Context:
         raise ValueError("pass a non-default torch.cuda.Stream (the null stream has no handle to borrow)")
     ctx = Context(device_index, handle)
     ctx.device_index = int(device_index)  # what the entries below hold their tensors to
+    ctx.stream = stream  # KltVideoTracker orders torch's own work (allocations, the caller's stream) with the kernels through it
     return ctx
 
 
@@ -481,6 +482,7 @@ from ._device_flow_warm import flow_warm_device  # noqa: E402,F401  (the warm st
 from ._device_sep_conv_gru import sep_conv_gru_device  # noqa: E402,F401  (RAFT's SepConvGru; its own file, see there)
 from ._device_raft_conv import conv2d_device, conv2d_strided_device  # noqa: E402,F401  (the stock layers of RAFT's UpdateBlock; its own file, see there)
 from ._device_corr_ondemand import corr_ondemand_lookup_device, corr_ondemand_prepare_device  # noqa: E402,F401  (RAFT's on-demand correlation; its own file, see there)
+from ._device_klt_video import _check_bound, harris_detect_device, track_table_fill_device, track_table_retire_device  # noqa: E402,F401  (masked Harris detection and KltVideoTracker's table; its own file, see there)
 
 
 def _nn_stream(torch, device, stream):

@@ -367,6 +367,34 @@ class FeaturePointHarrisDetector:
                                           float(self._options.kMinValidResponse), _ptr(uv), C.byref(n)), ctx.handle)
         return True, uv[: n.value].copy()
 
+    def detect_device(self, pyramid: "ImagePyramid", max_count: int, occupied=None, occupied_mask=None, level: int = 0):
+        """DetectGoodFeatures without the host (device.harris_detect_device): the strongest ``max_count`` corners of level
+        ``level`` of ``pyramid`` that are not within kMinFeatureDistance - 1 pixels (Chebyshev) of a point of ``occupied`` (float32 CUDA
+        [n, 2], read where ``occupied_mask``, uint8 CUDA [n], is not 0; None: everywhere).  Returns (uv, count): float32 CUDA
+        [max_count, 2] with zeros behind the corners found, and int32 CUDA [1]; enqueued on the context's stream, nothing synchronises."""
+        import torch
+
+        from . import device as D
+
+        ctx = self._ctx or default_context()
+        if int(max_count) < 0:
+            raise ValueError(f"max_count must not be negative (got {max_count})")
+        # (the refusals that need no device come before the first allocation; the entry checks everything again)
+        if occupied is None and occupied_mask is not None:
+            raise ValueError("occupied_mask without occupied: the mask selects among the occupied points")
+        if occupied is not None:
+            D._check("occupied", occupied, D._F32, (None, 2), getattr(ctx, "device_index", None))
+            if occupied_mask is not None:
+                D._check("occupied_mask", occupied_mask, D._U8, (int(occupied.shape[0]),), occupied.device.index)
+        _, rows, cols = pyramid.level_desc(int(level))
+        D._check_bound(rows, cols, self._options.kMinFeatureDistance)
+        where = occupied.device if getattr(occupied, "is_cuda", False) else torch.device("cuda", getattr(ctx, "device_index", None) or torch.cuda.current_device())
+        uv = torch.empty((int(max_count), 2), dtype=torch.float32, device=where)
+        count = torch.empty((1,), dtype=torch.int32, device=where)
+        D.harris_detect_device(ctx, pyramid, int(max_count), int(self._options.kMinFeatureDistance), float(self._options.kMinValidResponse), uv, count,
+                               occupied, occupied_mask, level)
+        return uv, count
+
     def response(self, image) -> np.ndarray:
         ctx = self._ctx or default_context()
         pyr = image if isinstance(image, ImagePyramid) else ImagePyramid.from_host_levels([image], ctx)

@@ -238,6 +238,58 @@ int ftk_harris_detect(ftk_context *ctx, const ftk_pyramid *image, int32_t level,
 /* The response map alone (rows*cols floats, host memory; 0 outside the 11-pixel border). */
 int ftk_harris_response(ftk_context *ctx, const ftk_pyramid *image, int32_t level, float *response);
 
+/*
+ * ftk_harris_detect on the device, with a list of points that already exist: the same definition, and everything stays in
+ * device memory — no copy to the host, no host sort, no synchronisation; asynchronous on the context's stream.
+ *   Occupied points: point i of d_occupied_uv (n_occupied (x, y) pairs, float32) is read only where d_occupied_flags[i] != 0 (NULL flags:
+ *   every point counts; n_occupied 0: none, both pointers may be NULL).  It stamps the pixel (clamp((int)floorf(x + 0.5f), 0, W - 1),
+ *   clamp((int)floorf(y + 0.5f), 0, H - 1)), which may lie in the 11-pixel border band.  A candidate with a stamp within Chebyshev distance
+ *   reach = max(min_distance, 1) - 1 is BLOCKED: it does not survive and it does not compete, so it suppresses nobody.  The candidates that
+ *   are not blocked follow the window-maximum rule among themselves.
+ *   Output: d_uv_out, [max_count][2] float32, 8-byte aligned: the strongest min(S, max_count) of the S survivors as (col, row), by response
+ *   descending then pixel index ascending, and zeros behind them; d_count_out, one int32: min(S, max_count).  With no occupied point the rows
+ *   are ftk_harris_detect's.  The order in which the survivors were appended to the device's list does not reach the output: a survivor's row
+ *   is the number of survivors with a greater 64-bit key (keys carry the pixel index, so they are unique), counted on the device.
+ *   Survivors are pairwise at Chebyshev distance >= d = max(min_distance, 1), so S <= ceil(H / d) * ceil(W / d); the list is sized by that
+ *   bound and cannot overflow.  A call whose bound exceeds FTK_HARRIS_DEVICE_MAX_SURVIVORS is refused before any launch (FTK_E_UNSUPPORTED).
+ *   An image below 23 x 23 has no valid centre: count 0, rows zero.  Uses the context's scratch block (it may grow: not promised capturable).
+ */
+#define FTK_HARRIS_DEVICE_MAX_SURVIVORS 65536
+#define FTK_HARRIS_RANK_TILE 256
+int ftk_harris_detect_device(ftk_context *ctx, const ftk_pyramid *image, int32_t level, int32_t max_count, int32_t min_distance, float min_response,
+                             const float *d_occupied_uv, const uint8_t *d_occupied_flags, int32_t n_occupied, float *d_uv_out, int32_t *d_count_out);
+
+/* ---- the track table (KltVideoTracker) ------------------------------------------ */
+
+/*
+ * A fixed-capacity table of tracks in device memory, n_slots = 1 .. FTK_TRACK_TABLE_MAX_SLOTS slots that never move: d_ids int64 [n] (-1 =
+ * empty), d_points / d_prev_points float32 [n][2] (current / previous frame, 8-byte aligned), d_status uint8 [n] (TrackStatus; an empty slot
+ * has a status > FTK_TRACKED, so ftk_klt_track_device over all n slots skips it), d_age int32 [n] (frames tracked since detection),
+ * d_n_live int32 [1], d_next_id int64 [1].  Both entries are asynchronous on the context's stream and read nothing back.
+ *
+ * ftk_track_table_retire_device — after the frame's tracker call(s), one launch.  d_tracked_uv / d_tracked_status are the results of
+ * ftk_klt_track_device with ref_uv = cur_uv_in = d_points (separate buffers, not the table's).  A slot stays live iff its id >= 0 and its
+ * tracked status is FTK_TRACKED; with the forward-backward check (d_back_uv / d_back_status, both or neither: the results of a second call in
+ * the opposite direction started from the tracked points) it additionally needs a backward status FTK_TRACKED and
+ * fmaf(dy, dy, dx * dx) <= t * t in float32, d = backward result - the slot's point before the forward call, t = fb_threshold (>= 0) — else
+ * its status becomes FTK_LARGE_RESIDUAL.  A live slot gets prev_points <- its old point, points <- tracked, age += 1.  Any other slot that held
+ * a track gets id <- -1, the status and the point the tracker left; a slot that was empty is not touched.  d_free (int32 [n]) receives the
+ * indices of all empty slots in ASCENDING slot order (a scan, not an atomic append), d_n_free (int32 [1]) their number, d_n_live n - that.
+ *
+ * ftk_track_table_fill_device — masked detection on `image` (as ftk_harris_detect_device, the slots with id >= 0 as occupied points) fused
+ * with the fill: the survivor of rank r < n_free goes to slot d_free[r] with id = next_id + r, points = prev_points = (col, row), status
+ * FTK_NOT_TRACKED, age 0; then next_id and n_live grow by min(n_free, S).  d_free / d_n_free as retire wrote them (for an empty table:
+ * 0 .. n - 1 and n).  Refusals as ftk_harris_detect_device.
+ */
+#define FTK_TRACK_TABLE_MAX_SLOTS 65536
+#define FTK_TRACK_TABLE_BLOCK 1024
+int ftk_track_table_retire_device(ftk_context *ctx, int32_t n_slots, int64_t *d_ids, float *d_points, float *d_prev_points, uint8_t *d_status,
+                                  int32_t *d_age, int32_t *d_n_live, const float *d_tracked_uv, const uint8_t *d_tracked_status,
+                                  const float *d_back_uv, const uint8_t *d_back_status, float fb_threshold, int32_t *d_free, int32_t *d_n_free);
+int ftk_track_table_fill_device(ftk_context *ctx, const ftk_pyramid *image, int32_t level, int32_t min_distance, float min_response, int32_t n_slots,
+                                int64_t *d_ids, float *d_points, float *d_prev_points, uint8_t *d_status, int32_t *d_age, int32_t *d_n_live,
+                                int64_t *d_next_id, const int32_t *d_free, const int32_t *d_n_free);
+
 /* ---- diagnostics ---------------------------------------------------------------------------- */
 
 /*
