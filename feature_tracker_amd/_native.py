@@ -28,6 +28,11 @@ FTK_HARRIS_DEVICE_MAX_SURVIVORS = 65536
 FTK_HARRIS_RANK_TILE = 256
 FTK_TRACK_TABLE_MAX_SLOTS = 65536
 FTK_TRACK_TABLE_BLOCK = 1024
+# two-view outlier rejection (include/ftk.h)
+FTK_EPIPOLAR_MAX_HYPOTHESES = 4096
+FTK_EPIPOLAR_SAMPLE = 8
+FTK_EPIPOLAR_MAX_ATTEMPTS = 16
+FTK_EPIPOLAR_SCORE_TILE = 256
 # SepConvGru (include/ftk.h): the supported sizes and the packed weight layout
 FTK_SEP_CONV_GRU_MAX_PARTS = 3
 FTK_SEP_CONV_GRU_MAX_H_CHANNELS = 1024
@@ -63,6 +68,7 @@ EXPORTS = [
     "ftk_conv2d_packed_elements", "ftk_conv2d_device", "ftk_conv2d_strided_device",
     "ftk_nn_match_scores_device", "ftk_nn_match_scores", "ftk_nn_match_list_device", "ftk_nn_match_list", "ftk_nn_fill_pixels_device",
     "ftk_harris_detect_device", "ftk_track_table_retire_device", "ftk_track_table_fill_device",
+    "ftk_epipolar_workspace_bytes", "ftk_epipolar_ransac_device",
 ]
 UNIQUE_ID_BYTES = 128
 
@@ -242,6 +248,8 @@ def lib() -> C.CDLL:
     l.ftk_harris_detect_device.argtypes = [vp, vp, i32, i32, i32, f32, vp, vp, i32, vp, vp]
     l.ftk_track_table_retire_device.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, f32, vp, vp]
     l.ftk_track_table_fill_device.argtypes = [vp, vp, i32, i32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    l.ftk_epipolar_workspace_bytes.argtypes = [i32, i32, i64p]
+    l.ftk_epipolar_ransac_device.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, C.c_uint32, vp, vp, vp, vp, vp, vp]
     _lib = l
     return l
 
@@ -288,6 +296,15 @@ def flow_warm_splits(B: int, H: int, W: int) -> int:
     splits = C.c_int32()
     check(lib().ftk_flow_warm_splits(int(B), int(H), int(W), C.byref(splits)), None)
     return splits.value
+
+
+def epipolar_workspace_bytes(n: int, hypotheses: int) -> int:
+    """Bytes of workspace ftk_epipolar_ransac_device needs, the value ftk_epipolar_workspace_bytes returns (pure Python: argument checks
+    need no library; csrc/epipolar_plan.cpp): M, then the participants' normalised coordinates, their indices, counts, models and validity
+    flags, each block rounded up to 16 bytes."""
+    n, k = int(n), int(hypotheses)
+    up16 = lambda v: (v + 15) & ~15  # noqa: E731
+    return 16 + up16(16 * n) + up16(4 * n) + up16(4 * k) + up16(36 * k) + up16(k)
 
 
 def sep_conv_gru_k_steps(in_channels: int, kernel_size: int) -> int:

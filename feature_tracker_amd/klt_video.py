@@ -6,11 +6,13 @@ a handful of launches on one stream: no copy to the host, no count read back, no
 """
 from __future__ import annotations
 
+import ctypes as C
 from typing import Optional
 
 import numpy as np
 
 from . import _native as N
+from ._device_epipolar import SEED_ARG, check_sizes, epipolar_ransac_args
 from ._device_klt_video import harris_survivor_bound, track_table_fill_args, track_table_retire_args
 from .tracker import OUTSIDE, ImagePyramid, OpticalFlow
 
@@ -33,7 +35,12 @@ class KltVideoTracker:
     Slots never move: a slot index is stable for the life of a track, and every launch covers all ``N = max_features`` slots, so no
     count is ever read back.  ``flow`` is an OpticalFlowBasicKlt / OpticalFlowAffineKlt / OpticalFlowLssdKlt; its options, method, prior
     and luminance flag are used as they are at each call.  ``forward_backward=t`` adds a second tracker call in the opposite direction
-    and retires a track whose round trip ends more than ``t`` pixels from where it started.  ``ctx``: a context made by
+    and retires a track whose round trip ends more than ``t`` pixels from where it started.  ``epipolar_threshold=t`` adds two-view outlier
+    rejection (``EpipolarRansac``) on the forward results, before the backward call (which then skips the rejected slots)
+    and before retire: a track more than ``t`` pixels (Sampson) from the best of ``epipolar_hypotheses`` fundamental matrices retires with
+    LARGE_RESIDUAL.  The seed of frame f (counted from construction or ``reset()``, the first frame is 0) is ``epipolar_seed + f``, a host
+    integer; ``epipolar_F`` / ``epipolar_n_inliers`` / ``epipolar_best`` hold the last fit
+    (zeros, 0 and -1 before the first one and after ``reset()``).  None: no such launch.  ``ctx``: a context made by
     ``device.context_on_stream`` (torch must know the stream the kernels run on); None: the tracker makes a stream and a context of its own.
 
     Limits: uint8 images of at least 23 x 23 and of one shape (``reset()`` before another), float32 points, the context's stream (the
@@ -41,7 +48,8 @@ class KltVideoTracker:
     tracker entry may grow the context's scratch), no motion prediction (every track starts its search where it was)."""
 
     def __init__(self, flow, max_features: int, levels: int = 4, min_distance: int = 25, min_response: float = 40.0,
-                 forward_backward: Optional[float] = None, ctx=None):
+                 forward_backward: Optional[float] = None, ctx=None, epipolar_threshold: Optional[float] = None, epipolar_hypotheses: int = 512,
+                 epipolar_seed: int = 0):
         if not isinstance(flow, OpticalFlow) or flow._model is None:
             raise ValueError(f"flow must be an OpticalFlowBasicKlt, OpticalFlowAffineKlt or OpticalFlowLssdKlt (got {type(flow).__name__})")
         n = int(max_features)
@@ -56,6 +64,10 @@ class KltVideoTracker:
             raise ValueError(f"min_distance must be at least 1 (got {min_distance})")
         if forward_backward is not None and not float(forward_backward) >= 0.0:
             raise ValueError(f"forward_backward must be None or a threshold in pixels >= 0 (got {forward_backward})")
+        self.epipolar_threshold = None
+        if epipolar_threshold is not None:
+            _, _, self.epipolar_threshold, self.epipolar_hypotheses, self.epipolar_seed = check_sizes((1, 1), epipolar_threshold, epipolar_hypotheses,
+                                                                                                      epipolar_seed)
         if ctx is not None and getattr(ctx, "stream", None) is None:
             raise ValueError("ctx must come from device.context_on_stream(stream): the table's tensors are torch's, and torch must know the stream "
                              "the kernels run on (None: the tracker makes its own)")
@@ -69,6 +81,7 @@ class KltVideoTracker:
         self._spare = 0
         self._image = None
         self.ids = self.points = self.prev_points = self.status = self.age = self.n_live = self.next_id = None
+        self.epipolar_F = self.epipolar_n_inliers = self.epipolar_best = None
 
     # ---- the caller's side ------------------------------------------------------------------------------------------------------
 
@@ -184,6 +197,11 @@ class KltVideoTracker:
         # the tracker calls' results (forward, backward): separate from the table, which retire moves on
         self._uv = [torch.zeros((n, 2), dtype=torch.float32, device=device) for _ in range(2)]
         self._st = [torch.zeros(n, dtype=torch.uint8, device=device) for _ in range(2)]
+        if self.epipolar_threshold is not None:
+            self._epipolar_ws = torch.empty(-(-N.epipolar_workspace_bytes(n, self.epipolar_hypotheses) // 8), dtype=torch.int64, device=device)
+            self.epipolar_F = torch.zeros((3, 3), dtype=torch.float32, device=device)
+            self.epipolar_n_inliers = torch.zeros(1, dtype=torch.int32, device=device)
+            self.epipolar_best = torch.full((1,), -1, dtype=torch.int32, device=device)
         self._empty_table()
 
     def _empty_table(self):
@@ -195,12 +213,18 @@ class KltVideoTracker:
         self.age.zero_()
         self.n_live.zero_()
         self._free.copy_(torch.arange(n, dtype=torch.int32, device=self.ids.device))
+        if self.epipolar_F is not None:  # no fit yet: the first frame of a sequence runs no filter
+            self.epipolar_F.zero_()
+            self.epipolar_n_inliers.zero_()
+            self.epipolar_best.fill_(-1)
         self._n_free.fill_(n)
 
     def _track_and_retire(self, D, prev, cur):
         flow, ctx = self.flow, self._ctx
         prior, lum = flow._prior(), flow._luminance()
         D.DeviceKlt(_MODEL_NAMES[flow._model], flow.options(), prev, cur, ctx, prior, lum).track(self.points, self.points, self.status, self._uv[0], self._st[0])
+        if self.epipolar_threshold is not None:
+            self._reject_outliers()
         fb = self.forward_backward is not None
         if fb:
             D.DeviceKlt(_MODEL_NAMES[flow._model], flow.options(), cur, prev, ctx, prior, lum).track(self._uv[0], self._uv[0], self._st[0], self._uv[1], self._st[1])
@@ -210,6 +234,19 @@ class KltVideoTracker:
                 ctx, self.ids, self.points, self.prev_points, self.status, self.age, self.n_live, self._uv[0], self._st[0], self._free, self._n_free,
                 self._uv[1] if fb else None, self._st[1] if fb else None, self.forward_backward if fb else 0.0)
         rc = N.lib().ftk_track_table_retire_device(*retire)
+        if rc != 0:
+            N.check(rc, ctx.handle)
+
+    def _reject_outliers(self):
+        """The forward results against the best fundamental matrix: ``_st[0]`` of a tracked slot that disagrees becomes LARGE_RESIDUAL."""
+        ctx = self._ctx
+        args = self._bound.get("epipolar")
+        if args is None:
+            args = self._bound["epipolar"] = list(epipolar_ransac_args(
+                ctx, self.points, self._uv[0], self._st[0], self._shape, self.epipolar_threshold, self.epipolar_hypotheses, 0, self._epipolar_ws,
+                self.epipolar_best, self.epipolar_n_inliers, self.epipolar_F, stream=ctx.stream))
+        args[SEED_ARG] = C.c_uint32((self.epipolar_seed + self._frames) & 0xFFFFFFFF)
+        rc = N.lib().ftk_epipolar_ransac_device(*args)
         if rc != 0:
             N.check(rc, ctx.handle)
 

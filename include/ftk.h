@@ -290,6 +290,38 @@ int ftk_track_table_fill_device(ftk_context *ctx, const ftk_pyramid *image, int3
                                 int64_t *d_ids, float *d_points, float *d_prev_points, uint8_t *d_status, int32_t *d_age, int32_t *d_n_live,
                                 int64_t *d_next_id, const int32_t *d_free, const int32_t *d_n_free);
 
+/* ---- two-view outlier rejection (EpipolarRansac) -------------------------------- */
+
+/*
+ * RANSAC on the fundamental matrix over n correspondences d_ref_uv[i] -> d_cur_uv[i] (float32 [n][2], (u, v) pixels, 8-byte aligned), all on
+ * the device.  The PARTICIPANTS are the points with d_status[i] == FTK_TRACKED, in ascending index order (a scan, not an atomic append); M,
+ * their number, stays on the device.  DESIGN.md 5.20 states every float operation and its order; in short, all in float32 without contraction:
+ *   coordinates are normalised by the image alone: cx = 0.5f (W - 1), cy = 0.5f (H - 1), s = 2.0f / (float)(W + H), xn = (x - cx) s, and the
+ *   threshold (pixels, >= 0) becomes tn = threshold s;
+ *   hypothesis h = 0 .. hypotheses - 1 draws 8 distinct participants with a stated 32-bit integer mix of (seed, h, draw, attempt), at most 16
+ *   attempts per draw, else h is invalid; the 8 x 9 constraint matrix is reduced by Gaussian elimination with complete pivoting (largest |a|,
+ *   ties to the lowest row, then column), the null vector read off by back substitution and scaled to unit Frobenius norm; a zero or
+ *   non-finite pivot, or a non-finite F, makes h invalid.  No rank-2 projection, no refit on the inliers;
+ *   participant i is an inlier of h iff num^2 <= tn^2 den, den > 0, both sides finite (the Sampson test without the division); the score of h
+ *   is its inlier count, -1 when invalid.  The greatest count wins, the lowest h among equal counts.
+ * Outputs: d_best int32 [1] (-1: none), d_n_inliers int32 [1], d_F float32 [9] (row-major, pixel units, x_cur^T F x_ref = 0; zeros when there
+ * is none), and d_status rewritten in place: a participant that is not an inlier of the winner becomes FTK_LARGE_RESIDUAL, nothing else
+ * changes.  With M < 8 or every hypothesis invalid no status changes, best = -1, n_inliers = M, F = 0.  d_counts (int32 [hypotheses]) and
+ * d_models (float32 [hypotheses][9], the normalised F of every hypothesis, zeros when invalid) may be NULL.
+ * d_workspace: ftk_epipolar_workspace_bytes(n, hypotheses) bytes, 16-byte aligned, no initialisation needed.  n = 1 .. FTK_TRACK_TABLE_MAX_SLOTS
+ * and hypotheses = 1 .. FTK_EPIPOLAR_MAX_HYPOTHESES, anything beyond is FTK_E_UNSUPPORTED before any launch.  Four launches on `stream` (a
+ * hipStream_t; NULL is the null stream) of fixed shape; no host read, no synchronisation, no allocation: capturable at any time.  Integer
+ * counts and integer atomics only: the result does not depend on the schedule.
+ */
+#define FTK_EPIPOLAR_MAX_HYPOTHESES 4096
+#define FTK_EPIPOLAR_SAMPLE 8
+#define FTK_EPIPOLAR_MAX_ATTEMPTS 16
+#define FTK_EPIPOLAR_SCORE_TILE 256
+int ftk_epipolar_workspace_bytes(int32_t n, int32_t hypotheses, int64_t *bytes);
+int ftk_epipolar_ransac_device(ftk_context *ctx, void *stream, const float *d_ref_uv, const float *d_cur_uv, uint8_t *d_status, int32_t n,
+                               int32_t image_rows, int32_t image_cols, float threshold, int32_t hypotheses, uint32_t seed, void *d_workspace,
+                               int32_t *d_best, int32_t *d_n_inliers, float *d_F, int32_t *d_counts, float *d_models);
+
 /* ---- diagnostics ---------------------------------------------------------------------------- */
 
 /*
