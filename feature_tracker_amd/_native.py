@@ -33,6 +33,12 @@ FTK_EPIPOLAR_MAX_HYPOTHESES = 4096
 FTK_EPIPOLAR_SAMPLE = 8
 FTK_EPIPOLAR_MAX_ATTEMPTS = 16
 FTK_EPIPOLAR_SCORE_TILE = 256
+# the same with a choice of model (include/ftk.h)
+FTK_TWO_VIEW_FUNDAMENTAL = 0
+FTK_TWO_VIEW_HOMOGRAPHY = 1
+FTK_TWO_VIEW_AUTO = 2
+FTK_TWO_VIEW_HOMOGRAPHY_SAMPLE = 4
+TWO_VIEW_MODES = {"fundamental": 0, "homography": 1, "auto": 2}
 # SepConvGru (include/ftk.h): the supported sizes and the packed weight layout
 FTK_SEP_CONV_GRU_MAX_PARTS = 3
 FTK_SEP_CONV_GRU_MAX_H_CHANNELS = 1024
@@ -69,6 +75,7 @@ EXPORTS = [
     "ftk_nn_match_scores_device", "ftk_nn_match_scores", "ftk_nn_match_list_device", "ftk_nn_match_list", "ftk_nn_fill_pixels_device",
     "ftk_harris_detect_device", "ftk_track_table_retire_device", "ftk_track_table_fill_device",
     "ftk_epipolar_workspace_bytes", "ftk_epipolar_ransac_device",
+    "ftk_two_view_workspace_bytes", "ftk_two_view_ransac_device",
 ]
 UNIQUE_ID_BYTES = 128
 
@@ -250,6 +257,8 @@ def lib() -> C.CDLL:
     l.ftk_track_table_fill_device.argtypes = [vp, vp, i32, i32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     l.ftk_epipolar_workspace_bytes.argtypes = [i32, i32, i64p]
     l.ftk_epipolar_ransac_device.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, C.c_uint32, vp, vp, vp, vp, vp, vp]
+    l.ftk_two_view_workspace_bytes.argtypes = [i32, i32, i32, i64p]
+    l.ftk_two_view_ransac_device.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, C.c_uint32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     _lib = l
     return l
 
@@ -305,6 +314,14 @@ def epipolar_workspace_bytes(n: int, hypotheses: int) -> int:
     n, k = int(n), int(hypotheses)
     up16 = lambda v: (v + 15) & ~15  # noqa: E731
     return 16 + up16(16 * n) + up16(4 * n) + up16(4 * k) + up16(36 * k) + up16(k)
+
+
+def two_view_workspace_bytes(n: int, hypotheses: int, mode: int = FTK_TWO_VIEW_AUTO) -> int:
+    """Bytes of workspace ftk_two_view_ransac_device needs, the value ftk_two_view_workspace_bytes returns (pure Python;
+    csrc/two_view_plan.cpp): epipolar_workspace_bytes' layout with counts, models and validity flags of two models, the same for every mode."""
+    n, k = int(n), int(hypotheses)
+    up16 = lambda v: (v + 15) & ~15  # noqa: E731
+    return 16 + up16(16 * n) + up16(4 * n) + up16(8 * k) + up16(72 * k) + up16(2 * k)
 
 
 def sep_conv_gru_k_steps(in_channels: int, kernel_size: int) -> int:

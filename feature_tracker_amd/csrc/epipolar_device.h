@@ -1,0 +1,157 @@
+// epipolar_device.h — the device functions that the two-view kernels share (epipolar_kernels.hip, two_view_kernels.hip; DESIGN.md 5.20,
+// 5.21): "finite", the hash, the sampler, the Sampson test and the null vector of an 8 x 9 system by Gaussian elimination with complete
+// pivoting.  Every float operation is stated in DESIGN.md 5.20 and restated in tests/epipolar_ref.c and tests/two_view_ref.c; the build
+// has no contraction (-ffp-contract=off) and correctly rounded division and square root.
+#pragma once
+
+#include "epipolar_plan.h"
+
+namespace ftk {
+
+__device__ __forceinline__ bool ep_finite(float v) { return (__float_as_uint(v) & 0x7F800000u) != 0x7F800000u; }
+
+__device__ __forceinline__ uint32_t ep_fmix32(uint32_t x) {  // murmur3's finaliser
+    x ^= x >> 16;
+    x *= 0x85EBCA6Bu;
+    x ^= x >> 13;
+    x *= 0xC2B2AE35u;
+    x ^= x >> 16;
+    return x;
+}
+
+__device__ __forceinline__ uint32_t ep_mix32(uint32_t seed, uint32_t h, uint32_t k, uint32_t a) {
+    return ep_fmix32(ep_fmix32(seed + 0x9E3779B9u * (h + 1u)) ^ (0x85EBCA6Bu * (k * (uint32_t)kEpipolarMaxAttempts + a + 1u)));
+}
+
+// The sampler: S distinct positions of a list of m participants, kEpipolarMaxAttempts attempts per draw.  false: m < S or a draw ran out.
+template <int S>
+__device__ __forceinline__ bool ep_draw(uint32_t seed, uint32_t h, uint32_t m, uint32_t (&idx)[S]) {
+    bool ok = m >= (uint32_t)S;
+#pragma unroll
+    for (int k = 0; k < S; ++k) {
+        idx[k] = 0u;
+        bool found = false;
+        for (uint32_t t = 0; ok && !found && t < (uint32_t)kEpipolarMaxAttempts; ++t) {
+            const uint32_t j = (uint32_t)(((uint64_t)ep_mix32(seed, h, (uint32_t)k, t) * (uint64_t)m) >> 32);
+            bool dup = false;
+#pragma unroll
+            for (int q = 0; q < k; ++q) {
+                dup = dup || idx[q] == j;
+            }
+            if (!dup) {
+                idx[k] = j;
+                found = true;
+            }
+        }
+        ok = ok && found;
+    }
+    return ok;
+}
+
+// The Sampson test without the division, q = normalised (x1, y1, x2, y2), f = normalised F row-major.
+__device__ __forceinline__ bool ep_inlier(const float (&f)[9], const float4 q, float tn2) {
+    const float x1 = q.x, y1 = q.y, x2 = q.z, y2 = q.w;
+    if (!(ep_finite(x1) && ep_finite(y1) && ep_finite(x2) && ep_finite(y2))) {
+        return false;
+    }
+    const float a0 = (f[0] * x1 + f[1] * y1) + f[2];  // F x1
+    const float a1 = (f[3] * x1 + f[4] * y1) + f[5];
+    const float a2 = (f[6] * x1 + f[7] * y1) + f[8];
+    const float b0 = (f[0] * x2 + f[3] * y2) + f[6];  // F^T x2
+    const float b1 = (f[1] * x2 + f[4] * y2) + f[7];
+    const float num = (x2 * a0 + y2 * a1) + a2;
+    const float den = ((a0 * a0 + a1 * a1) + b0 * b0) + b1 * b1;
+    const float lhs = num * num, rhs = tn2 * den;
+    return den > 0.0f && ep_finite(lhs) && ep_finite(rhs) && lhs <= rhs;
+}
+
+// The unit null vector of the 8 x 9 matrix a (LDS, a[(r * 9 + c) * L] of this lane; destroyed), by Gaussian elimination with complete
+// pivoting, back substitution with the free unknown 1 and scaling to unit norm.  perm (9 ints) and fv (9 floats) are this lane's LDS
+// scratch, strided by L as a is.  `ok`: the matrix was filled from finite coordinates.  Returns the validity of f; f is zero when invalid.
+template <int L>
+__device__ __forceinline__ bool ep_null_vector(float *const a, int *const perm, float *const fv, bool ok, float (&f)[9]) {
+    for (int c = 0; c < 9; ++c) {
+        perm[c * L] = c;
+    }
+    for (int s = 0; ok && s < 8; ++s) {
+        float best = -1.0f;
+        int br = s, bc = s;
+        for (int r = s; r < 8; ++r) {
+            for (int c = s; c < 9; ++c) {
+                const float v = fabsf(a[(r * 9 + c) * L]);
+                if (v > best) {
+                    best = v;
+                    br = r;
+                    bc = c;
+                }
+            }
+        }
+        const float piv = a[(br * 9 + bc) * L];
+        if (!ep_finite(piv) || piv == 0.0f) {
+            ok = false;
+            break;
+        }
+        if (br != s) {
+            for (int c = s; c < 9; ++c) {
+                const float t = a[(s * 9 + c) * L];
+                a[(s * 9 + c) * L] = a[(br * 9 + c) * L];
+                a[(br * 9 + c) * L] = t;
+            }
+        }
+        if (bc != s) {
+            for (int r = 0; r < 8; ++r) {
+                const float t = a[(r * 9 + s) * L];
+                a[(r * 9 + s) * L] = a[(r * 9 + bc) * L];
+                a[(r * 9 + bc) * L] = t;
+            }
+            const int t = perm[s * L];
+            perm[s * L] = perm[bc * L];
+            perm[bc * L] = t;
+        }
+        for (int r = s + 1; r < 8; ++r) {
+            const float mult = a[(r * 9 + s) * L] / piv;
+            for (int c = s + 1; c < 9; ++c) {
+                a[(r * 9 + c) * L] = a[(r * 9 + c) * L] - mult * a[(s * 9 + c) * L];
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 9; ++i) {
+        f[i] = 0.0f;
+    }
+    if (ok) {
+        // the null vector: the free (ninth) column's unknown is 1, the others by back substitution
+        float z[9];
+        z[8] = 1.0f;
+#pragma unroll
+        for (int s = 7; s >= 0; --s) {
+            float acc = a[(s * 9 + 8) * L];
+#pragma unroll
+            for (int q = s + 1; q < 8; ++q) {
+                acc = acc + a[(s * 9 + q) * L] * z[q];
+            }
+            z[s] = -acc / a[(s * 9 + s) * L];
+        }
+#pragma unroll
+        for (int q = 0; q < 9; ++q) {
+            fv[perm[q * L] * L] = z[q];
+        }
+        float n2 = fv[0] * fv[0];
+#pragma unroll
+        for (int i = 1; i < 9; ++i) {
+            n2 = n2 + fv[i * L] * fv[i * L];
+        }
+        ok = ep_finite(n2) && n2 > 0.0f;
+        if (ok) {
+            const float inv = 1.0f / sqrtf(n2);
+#pragma unroll
+            for (int i = 0; i < 9; ++i) {
+                f[i] = fv[i * L] * inv;
+                ok = ok && ep_finite(f[i]);
+            }
+        }
+    }
+    return ok;
+}
+
+}  // namespace ftk

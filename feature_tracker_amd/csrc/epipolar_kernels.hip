@@ -12,42 +12,10 @@
 //    statuses of the participants that are not its inliers.
 // Every float operation below is stated in DESIGN.md 5.20 and restated in tests/epipolar_ref.c; the build has no contraction
 // (-ffp-contract=off) and correctly rounded division and square root.
-#include "epipolar_plan.h"
+#include "epipolar_device.h"
 
 namespace ftk {
 namespace {
-
-__device__ __forceinline__ bool ep_finite(float v) { return (__float_as_uint(v) & 0x7F800000u) != 0x7F800000u; }
-
-__device__ __forceinline__ uint32_t ep_fmix32(uint32_t x) {  // murmur3's finaliser
-    x ^= x >> 16;
-    x *= 0x85EBCA6Bu;
-    x ^= x >> 13;
-    x *= 0xC2B2AE35u;
-    x ^= x >> 16;
-    return x;
-}
-
-__device__ __forceinline__ uint32_t ep_mix32(uint32_t seed, uint32_t h, uint32_t k, uint32_t a) {
-    return ep_fmix32(ep_fmix32(seed + 0x9E3779B9u * (h + 1u)) ^ (0x85EBCA6Bu * (k * (uint32_t)kEpipolarMaxAttempts + a + 1u)));
-}
-
-// The Sampson test without the division, q = normalised (x1, y1, x2, y2), f = normalised F row-major.
-__device__ __forceinline__ bool ep_inlier(const float (&f)[9], const float4 q, float tn2) {
-    const float x1 = q.x, y1 = q.y, x2 = q.z, y2 = q.w;
-    if (!(ep_finite(x1) && ep_finite(y1) && ep_finite(x2) && ep_finite(y2))) {
-        return false;
-    }
-    const float a0 = (f[0] * x1 + f[1] * y1) + f[2];  // F x1
-    const float a1 = (f[3] * x1 + f[4] * y1) + f[5];
-    const float a2 = (f[6] * x1 + f[7] * y1) + f[8];
-    const float b0 = (f[0] * x2 + f[3] * y2) + f[6];  // F^T x2
-    const float b1 = (f[1] * x2 + f[4] * y2) + f[7];
-    const float num = (x2 * a0 + y2 * a1) + a2;
-    const float den = ((a0 * a0 + a1 * a1) + b0 * b0) + b1 * b1;
-    const float lhs = num * num, rhs = tn2 * den;
-    return den > 0.0f && ep_finite(lhs) && ep_finite(rhs) && lhs <= rhs;
-}
 
 __global__ void __launch_bounds__(kEpipolarScanBlock) epipolar_scan_kernel(const EpipolarParams p) {
     __shared__ int32_t scan[kEpipolarScanBlock];
@@ -97,27 +65,9 @@ __global__ void __launch_bounds__(kEpipolarHypBlock) epipolar_hypothesis_kernel(
     float *const fv = lds + 81 * kEpipolarHypBlock + lane;                                   // fv[c * 64]
     constexpr int L = kEpipolarHypBlock;
     const uint32_t m = (uint32_t)max(p.m[0], 0);
-    bool ok = m >= (uint32_t)kEpipolarSample;
     // the sampler: 8 distinct positions of the participants' list
     uint32_t idx[kEpipolarSample];
-#pragma unroll
-    for (int k = 0; k < kEpipolarSample; ++k) {
-        idx[k] = 0u;
-        bool found = false;
-        for (uint32_t t = 0; ok && !found && t < (uint32_t)kEpipolarMaxAttempts; ++t) {
-            const uint32_t j = (uint32_t)(((uint64_t)ep_mix32(p.seed, (uint32_t)h, (uint32_t)k, t) * (uint64_t)m) >> 32);
-            bool dup = false;
-#pragma unroll
-            for (int q = 0; q < k; ++q) {
-                dup = dup || idx[q] == j;
-            }
-            if (!dup) {
-                idx[k] = j;
-                found = true;
-            }
-        }
-        ok = ok && found;
-    }
+    bool ok = ep_draw<kEpipolarSample>(p.seed, (uint32_t)h, m, idx);
     if (ok) {
 #pragma unroll
         for (int k = 0; k < kEpipolarSample; ++k) {
@@ -135,89 +85,9 @@ __global__ void __launch_bounds__(kEpipolarHypBlock) epipolar_hypothesis_kernel(
             a[(k * 9 + 8) * L] = 1.0f;
         }
     }
-    for (int c = 0; c < 9; ++c) {
-        perm[c * L] = c;
-    }
-    // Gaussian elimination with complete pivoting
-    for (int s = 0; ok && s < 8; ++s) {
-        float best = -1.0f;
-        int br = s, bc = s;
-        for (int r = s; r < 8; ++r) {
-            for (int c = s; c < 9; ++c) {
-                const float v = fabsf(a[(r * 9 + c) * L]);
-                if (v > best) {
-                    best = v;
-                    br = r;
-                    bc = c;
-                }
-            }
-        }
-        const float piv = a[(br * 9 + bc) * L];
-        if (!ep_finite(piv) || piv == 0.0f) {
-            ok = false;
-            break;
-        }
-        if (br != s) {
-            for (int c = s; c < 9; ++c) {
-                const float t = a[(s * 9 + c) * L];
-                a[(s * 9 + c) * L] = a[(br * 9 + c) * L];
-                a[(br * 9 + c) * L] = t;
-            }
-        }
-        if (bc != s) {
-            for (int r = 0; r < 8; ++r) {
-                const float t = a[(r * 9 + s) * L];
-                a[(r * 9 + s) * L] = a[(r * 9 + bc) * L];
-                a[(r * 9 + bc) * L] = t;
-            }
-            const int t = perm[s * L];
-            perm[s * L] = perm[bc * L];
-            perm[bc * L] = t;
-        }
-        for (int r = s + 1; r < 8; ++r) {
-            const float mult = a[(r * 9 + s) * L] / piv;
-            for (int c = s + 1; c < 9; ++c) {
-                a[(r * 9 + c) * L] = a[(r * 9 + c) * L] - mult * a[(s * 9 + c) * L];
-            }
-        }
-    }
+    // Gaussian elimination with complete pivoting, the null vector, unit norm (epipolar_device.h)
     float f[9];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) {
-        f[i] = 0.0f;
-    }
-    if (ok) {
-        // the null vector: the free (ninth) column's unknown is 1, the others by back substitution
-        float z[9];
-        z[8] = 1.0f;
-#pragma unroll
-        for (int s = 7; s >= 0; --s) {
-            float acc = a[(s * 9 + 8) * L];
-#pragma unroll
-            for (int q = s + 1; q < 8; ++q) {
-                acc = acc + a[(s * 9 + q) * L] * z[q];
-            }
-            z[s] = -acc / a[(s * 9 + s) * L];
-        }
-#pragma unroll
-        for (int q = 0; q < 9; ++q) {
-            fv[perm[q * L] * L] = z[q];
-        }
-        float n2 = fv[0] * fv[0];
-#pragma unroll
-        for (int i = 1; i < 9; ++i) {
-            n2 = n2 + fv[i * L] * fv[i * L];
-        }
-        ok = ep_finite(n2) && n2 > 0.0f;
-        if (ok) {
-            const float inv = 1.0f / sqrtf(n2);
-#pragma unroll
-            for (int i = 0; i < 9; ++i) {
-                f[i] = fv[i * L] * inv;
-                ok = ok && ep_finite(f[i]);
-            }
-        }
-    }
+    ok = ep_null_vector<L>(a, perm, fv, ok, f);
 #pragma unroll
     for (int i = 0; i < 9; ++i) {
         p.models[(size_t)h * 9 + i] = ok ? f[i] : 0.0f;
@@ -335,13 +205,25 @@ __global__ void __launch_bounds__(kEpipolarScanBlock) epipolar_select_kernel(con
 
 }  // namespace
 
+void epipolar_launch_scan(const EpipolarParams &p, hipStream_t stream) {
+    hipLaunchKernelGGL(epipolar_scan_kernel, dim3(1), dim3(kEpipolarScanBlock), 0, stream, p);
+}
+
+void epipolar_launch_hypotheses(uint32_t hyp_blocks, const EpipolarParams &p, hipStream_t stream) {
+    hipLaunchKernelGGL(epipolar_hypothesis_kernel, dim3(hyp_blocks), dim3(kEpipolarHypBlock), 0, stream, p);
+}
+
+void epipolar_launch_score(uint32_t score_tiles, uint32_t score_groups, const EpipolarParams &p, hipStream_t stream) {
+    hipLaunchKernelGGL(epipolar_score_kernel, dim3(score_tiles, score_groups), dim3(kEpipolarScoreTile), 0, stream, p);
+}
+
 hipError_t epipolar_launch(const EpipolarPlan &plan, const EpipolarParams &p, hipStream_t stream) {
     EpipolarParams q = p;
     q.scan_per_thread = plan.scan_per_thread;
     q.select_per_thread = plan.select_per_thread;
-    hipLaunchKernelGGL(epipolar_scan_kernel, dim3(1), dim3(kEpipolarScanBlock), 0, stream, q);
-    hipLaunchKernelGGL(epipolar_hypothesis_kernel, dim3(plan.hyp_blocks), dim3(kEpipolarHypBlock), 0, stream, q);
-    hipLaunchKernelGGL(epipolar_score_kernel, dim3(plan.score_tiles, plan.score_groups), dim3(kEpipolarScoreTile), 0, stream, q);
+    epipolar_launch_scan(q, stream);
+    epipolar_launch_hypotheses(plan.hyp_blocks, q, stream);
+    epipolar_launch_score(plan.score_tiles, plan.score_groups, q, stream);
     hipLaunchKernelGGL(epipolar_select_kernel, dim3(1), dim3(kEpipolarScanBlock), 0, stream, q);
     return hipGetLastError();
 }

@@ -60,5 +60,10 @@ struct EpipolarParams {
     int32_t scan_per_thread, select_per_thread;
 };
 hipError_t epipolar_launch(const EpipolarPlan &plan, const EpipolarParams &p, hipStream_t stream);
+// The same kernels one at a time, for the two-view entry (two_view_kernels.hip), which shares the scan between two models and has a
+// select kernel of its own.  p carries scan_per_thread; best / n_inliers / F are not read.
+void epipolar_launch_scan(const EpipolarParams &p, hipStream_t stream);
+void epipolar_launch_hypotheses(uint32_t hyp_blocks, const EpipolarParams &p, hipStream_t stream);
+void epipolar_launch_score(uint32_t score_tiles, uint32_t score_groups, const EpipolarParams &p, hipStream_t stream);
 
 }  // namespace ftk

@@ -13,6 +13,7 @@ import numpy as np
 
 from . import _native as N
 from ._device_epipolar import SEED_ARG, check_sizes, epipolar_ransac_args
+from ._device_two_view import SEED_ARG as TWO_VIEW_SEED_ARG, check_mode, prefer_to_permille, two_view_ransac_args
 from ._device_klt_video import harris_survivor_bound, track_table_fill_args, track_table_retire_args
 from .tracker import OUTSIDE, ImagePyramid, OpticalFlow
 
@@ -40,7 +41,11 @@ class KltVideoTracker:
     and before retire: a track more than ``t`` pixels (Sampson) from the best of ``epipolar_hypotheses`` fundamental matrices retires with
     LARGE_RESIDUAL.  The seed of frame f (counted from construction or ``reset()``, the first frame is 0) is ``epipolar_seed + f``, a host
     integer; ``epipolar_F`` / ``epipolar_n_inliers`` / ``epipolar_best`` hold the last fit
-    (zeros, 0 and -1 before the first one and after ``reset()``).  None: no such launch.  ``ctx``: a context made by
+    (zeros, 0 and -1 before the first one and after ``reset()``).  None: no such launch.  ``epipolar_model="homography"`` or ``"auto"``
+    routes the same step through ``TwoViewRansac`` (``epipolar_prefer_homography`` is its ``prefer_homography``):
+    ``epipolar_F`` / ``epipolar_H`` float32 [3, 3], ``epipolar_n_inliers`` / ``epipolar_best`` int32 [2] (slot 0 the fundamental matrix,
+    slot 1 the homography) and ``epipolar_model_chosen`` int32 [1] (-1 before the first fit) then hold the last fit; with the default
+    ``"fundamental"`` the tracker launches what it launches without the argument and the two new attributes stay None.  ``ctx``: a context made by
     ``device.context_on_stream`` (torch must know the stream the kernels run on); None: the tracker makes a stream and a context of its own.
 
     Limits: uint8 images of at least 23 x 23 and of one shape (``reset()`` before another), float32 points, the context's stream (the
@@ -49,7 +54,7 @@ class KltVideoTracker:
 
     def __init__(self, flow, max_features: int, levels: int = 4, min_distance: int = 25, min_response: float = 40.0,
                  forward_backward: Optional[float] = None, ctx=None, epipolar_threshold: Optional[float] = None, epipolar_hypotheses: int = 512,
-                 epipolar_seed: int = 0):
+                 epipolar_seed: int = 0, epipolar_model: str = "fundamental", epipolar_prefer_homography: float = 0.75):
         if not isinstance(flow, OpticalFlow) or flow._model is None:
             raise ValueError(f"flow must be an OpticalFlowBasicKlt, OpticalFlowAffineKlt or OpticalFlowLssdKlt (got {type(flow).__name__})")
         n = int(max_features)
@@ -65,7 +70,15 @@ class KltVideoTracker:
         if forward_backward is not None and not float(forward_backward) >= 0.0:
             raise ValueError(f"forward_backward must be None or a threshold in pixels >= 0 (got {forward_backward})")
         self.epipolar_threshold = None
+        self.epipolar_model = "fundamental"
+        if epipolar_threshold is None and epipolar_model != "fundamental":
+            raise ValueError(f"epipolar_model={epipolar_model!r} needs epipolar_threshold: without a threshold no filter runs")
         if epipolar_threshold is not None:
+            if not isinstance(epipolar_model, str):
+                raise ValueError(f"epipolar_model must be 'fundamental', 'homography' or 'auto' (got {epipolar_model!r})")
+            self._epipolar_mode = check_mode(epipolar_model)
+            self.epipolar_model = epipolar_model
+            self._epipolar_permille = prefer_to_permille(epipolar_prefer_homography)
             _, _, self.epipolar_threshold, self.epipolar_hypotheses, self.epipolar_seed = check_sizes((1, 1), epipolar_threshold, epipolar_hypotheses,
                                                                                                       epipolar_seed)
         if ctx is not None and getattr(ctx, "stream", None) is None:
@@ -82,6 +95,7 @@ class KltVideoTracker:
         self._image = None
         self.ids = self.points = self.prev_points = self.status = self.age = self.n_live = self.next_id = None
         self.epipolar_F = self.epipolar_n_inliers = self.epipolar_best = None
+        self.epipolar_H = self.epipolar_model_chosen = None
 
     # ---- the caller's side ------------------------------------------------------------------------------------------------------
 
@@ -197,7 +211,15 @@ class KltVideoTracker:
         # the tracker calls' results (forward, backward): separate from the table, which retire moves on
         self._uv = [torch.zeros((n, 2), dtype=torch.float32, device=device) for _ in range(2)]
         self._st = [torch.zeros(n, dtype=torch.uint8, device=device) for _ in range(2)]
-        if self.epipolar_threshold is not None:
+        if self.epipolar_threshold is not None and self.epipolar_model != "fundamental":
+            self._epipolar_ws = torch.empty(-(-N.two_view_workspace_bytes(n, self.epipolar_hypotheses, self._epipolar_mode) // 8), dtype=torch.int64,
+                                            device=device)
+            self.epipolar_F = torch.zeros((3, 3), dtype=torch.float32, device=device)
+            self.epipolar_H = torch.zeros((3, 3), dtype=torch.float32, device=device)
+            self.epipolar_n_inliers = torch.zeros(2, dtype=torch.int32, device=device)
+            self.epipolar_best = torch.full((2,), -1, dtype=torch.int32, device=device)
+            self.epipolar_model_chosen = torch.full((1,), -1, dtype=torch.int32, device=device)
+        elif self.epipolar_threshold is not None:
             self._epipolar_ws = torch.empty(-(-N.epipolar_workspace_bytes(n, self.epipolar_hypotheses) // 8), dtype=torch.int64, device=device)
             self.epipolar_F = torch.zeros((3, 3), dtype=torch.float32, device=device)
             self.epipolar_n_inliers = torch.zeros(1, dtype=torch.int32, device=device)
@@ -217,6 +239,9 @@ class KltVideoTracker:
             self.epipolar_F.zero_()
             self.epipolar_n_inliers.zero_()
             self.epipolar_best.fill_(-1)
+        if self.epipolar_H is not None:
+            self.epipolar_H.zero_()
+            self.epipolar_model_chosen.fill_(-1)
         self._n_free.fill_(n)
 
     def _track_and_retire(self, D, prev, cur):
@@ -238,8 +263,20 @@ class KltVideoTracker:
             N.check(rc, ctx.handle)
 
     def _reject_outliers(self):
-        """The forward results against the best fundamental matrix: ``_st[0]`` of a tracked slot that disagrees becomes LARGE_RESIDUAL."""
+        """The forward results against the best fundamental matrix (or the chosen model): ``_st[0]`` of a tracked slot that disagrees becomes LARGE_RESIDUAL."""
         ctx = self._ctx
+        if self.epipolar_model != "fundamental":  # the homography, or the choice between the two (DESIGN.md 5.21)
+            args = self._bound.get("two_view")
+            if args is None:
+                args = self._bound["two_view"] = list(two_view_ransac_args(
+                    ctx, self.points, self._uv[0], self._st[0], self._shape, self.epipolar_threshold, self.epipolar_hypotheses, 0, self._epipolar_mode,
+                    self._epipolar_permille, self._epipolar_ws, self.epipolar_model_chosen, self.epipolar_best, self.epipolar_n_inliers, self.epipolar_F,
+                    self.epipolar_H, stream=ctx.stream))
+            args[TWO_VIEW_SEED_ARG] = C.c_uint32((self.epipolar_seed + self._frames) & 0xFFFFFFFF)
+            rc = N.lib().ftk_two_view_ransac_device(*args)
+            if rc != 0:
+                N.check(rc, ctx.handle)
+            return
         args = self._bound.get("epipolar")
         if args is None:
             args = self._bound["epipolar"] = list(epipolar_ransac_args(

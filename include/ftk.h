@@ -322,6 +322,34 @@ int ftk_epipolar_ransac_device(ftk_context *ctx, void *stream, const float *d_re
                                int32_t image_rows, int32_t image_cols, float threshold, int32_t hypotheses, uint32_t seed, void *d_workspace,
                                int32_t *d_best, int32_t *d_n_inliers, float *d_F, int32_t *d_counts, float *d_models);
 
+/*
+ * The same with a choice of model.  mode FTK_TWO_VIEW_FUNDAMENTAL is ftk_epipolar_ransac_device's computation, bit for bit.
+ * FTK_TWO_VIEW_HOMOGRAPHY fits x_cur ~ H x_ref instead: hypothesis h draws 4 distinct participants with the same sampler (M < 4: every h is
+ * invalid), each draw gives two rows of the 8 x 9 DLT system, [x1 y1 1 0 0 0 -(x2 x1) -(x2 y1) -x2] and [0 0 0 x1 y1 1 -(y2 x1) -(y2 y1) -y2],
+ * which the same elimination reduces; participant i is an inlier iff ex^2 + ey^2 <= tn^2 w^2 with w = (H6 x1 + H7 y1) + H8 != 0,
+ * ex = px - x2 w, ey = py - y2 w, both sides finite (the one-sided transfer error in the current image without the division; no symmetric
+ * error, no orientation test, no refit).  FTK_TWO_VIEW_AUTO runs both on the same participants and seed (one scan) and chooses the
+ * homography iff it has a winner and (the fundamental matrix has none, or 1000 n_H >= prefer_homography_permille n_F, in int64); otherwise
+ * the fundamental matrix if it has a winner; otherwise nothing changes and model = -1.  Only the chosen model's non-inliers become
+ * FTK_LARGE_RESIDUAL.
+ * Outputs: d_model int32 [1] (-1, 0 or 1), d_best / d_n_inliers int32 [2] (slot 0 the fundamental matrix, slot 1 the homography), d_F and
+ * d_H float32 [9] (row-major, pixel units, x_cur ~ H x_ref; zeros when there is none), d_counts int32 [2][hypotheses] and d_models float32
+ * [2][hypotheses][9] (may be NULL).  The slot of a model that did not run, or has no winner, holds best = -1, n_inliers = M and a zero
+ * matrix; every count of a model that did not run is -1 and its hypotheses are zeros.
+ * d_workspace: ftk_two_view_workspace_bytes(n, hypotheses, mode) bytes, 16-byte aligned, no initialisation needed.  The limits are the
+ * fundamental route's; a mode outside 0 .. 2 or prefer_homography_permille outside 0 .. 1000 is FTK_E_INVALID_ARGUMENT before any launch.
+ * Four launches (six with FTK_TWO_VIEW_AUTO) of fixed shape on `stream`; no host read, no synchronisation, no allocation: capturable.
+ */
+#define FTK_TWO_VIEW_FUNDAMENTAL 0
+#define FTK_TWO_VIEW_HOMOGRAPHY 1
+#define FTK_TWO_VIEW_AUTO 2
+#define FTK_TWO_VIEW_HOMOGRAPHY_SAMPLE 4
+int ftk_two_view_workspace_bytes(int32_t n, int32_t hypotheses, int32_t mode, int64_t *bytes);
+int ftk_two_view_ransac_device(ftk_context *ctx, void *stream, const float *d_ref_uv, const float *d_cur_uv, uint8_t *d_status, int32_t n,
+                               int32_t image_rows, int32_t image_cols, float threshold, int32_t hypotheses, uint32_t seed, int32_t mode,
+                               int32_t prefer_homography_permille, void *d_workspace, int32_t *d_model, int32_t *d_best, int32_t *d_n_inliers,
+                               float *d_F, float *d_H, int32_t *d_counts, float *d_models);
+
 /* ---- diagnostics ---------------------------------------------------------------------------- */
 
 /*
