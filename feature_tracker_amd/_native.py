@@ -39,6 +39,10 @@ FTK_TWO_VIEW_HOMOGRAPHY = 1
 FTK_TWO_VIEW_AUTO = 2
 FTK_TWO_VIEW_HOMOGRAPHY_SAMPLE = 4
 TWO_VIEW_MODES = {"fundamental": 0, "homography": 1, "auto": 2}
+# the keypoint decoder (include/ftk.h)
+FTK_KEYPOINT_DECODE_CELL = 8
+FTK_KEYPOINT_DECODE_MAX_KEYPOINTS = 65536
+FTK_KEYPOINT_DECODE_MAX_CHANNELS = 1024
 # SepConvGru (include/ftk.h): the supported sizes and the packed weight layout
 FTK_SEP_CONV_GRU_MAX_PARTS = 3
 FTK_SEP_CONV_GRU_MAX_H_CHANNELS = 1024
@@ -76,6 +80,7 @@ EXPORTS = [
     "ftk_harris_detect_device", "ftk_track_table_retire_device", "ftk_track_table_fill_device",
     "ftk_epipolar_workspace_bytes", "ftk_epipolar_ransac_device",
     "ftk_two_view_workspace_bytes", "ftk_two_view_ransac_device",
+    "ftk_keypoint_decode_workspace_bytes", "ftk_keypoint_decode_device",
 ]
 UNIQUE_ID_BYTES = 128
 
@@ -259,6 +264,8 @@ def lib() -> C.CDLL:
     l.ftk_epipolar_ransac_device.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, C.c_uint32, vp, vp, vp, vp, vp, vp]
     l.ftk_two_view_workspace_bytes.argtypes = [i32, i32, i32, i64p]
     l.ftk_two_view_ransac_device.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, C.c_uint32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    l.ftk_keypoint_decode_workspace_bytes.argtypes = [i32, i32, i32, i32, i64p]
+    l.ftk_keypoint_decode_device.argtypes = [vp, vp, vp, i32, i32, vp, i32, C.c_int64, C.c_int64, C.c_int64, i32, f32, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]
     _lib = l
     return l
 
@@ -322,6 +329,17 @@ def two_view_workspace_bytes(n: int, hypotheses: int, mode: int = FTK_TWO_VIEW_A
     n, k = int(n), int(hypotheses)
     up16 = lambda v: (v + 15) & ~15  # noqa: E731
     return 16 + up16(16 * n) + up16(4 * n) + up16(8 * k) + up16(72 * k) + up16(2 * k)
+
+
+def keypoint_decode_workspace_bytes(cell_rows: int, cell_cols: int, min_distance: int, n_occupied: int = 0) -> int:
+    """Bytes of workspace ftk_keypoint_decode_device needs, the value ftk_keypoint_decode_workspace_bytes returns (pure Python;
+    csrc/keypoint_decode_plan.cpp): three 64-bit planes of the 8 cell_rows x 8 cell_cols image, the survivor list and its count, and with
+    occupied points two byte planes."""
+    px = 64 * int(cell_rows) * int(cell_cols)
+    d = max(int(min_distance), 1)
+    capacity = -(-8 * int(cell_rows) // d) * -(-8 * int(cell_cols) // d)
+    up16 = lambda v: (v + 15) & ~15  # noqa: E731
+    return 3 * up16(8 * px) + up16(8 * capacity) + 16 + (2 * up16(px) if int(n_occupied) > 0 else 0)
 
 
 def sep_conv_gru_k_steps(in_channels: int, kernel_size: int) -> int:

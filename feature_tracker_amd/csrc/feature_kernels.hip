@@ -250,31 +250,45 @@ hipError_t harris_launch(const HarrisParams &p, hipStream_t stream) {
     return hipGetLastError();
 }
 
-hipError_t harris_masked_launch(const HarrisParams &p, const HarrisOccupied &o, hipStream_t stream) {
-    const long long total = (long long)p.img.rows * p.img.cols;
+hipError_t key_plane_select_launch(const KeyPlaneSelectParams &p, const HarrisOccupied &o, hipStream_t stream) {
+    const long long total = (long long)p.rows * p.cols;
     const unsigned blocks = (unsigned)((total + 255) / 256);
-    const int reach = (p.min_distance > 1 ? p.min_distance : 1) - 1;
-    hipLaunchKernelGGL(harris_gradient_kernel, dim3(blocks), dim3(256), 0, stream, p.img, p.gx, p.gy);
-    hipLaunchKernelGGL(harris_response_kernel, dim3(blocks), dim3(256), 0, stream, p.img.rows, p.img.cols, p.gx, p.gy, p.min_response, p.response,
-                       p.key);
     if (o.n > 0) {
         hipError_t e = hipMemsetAsync(o.plane, 0, (size_t)total, stream);
         if (e != hipSuccess) {
             return e;
         }
-        hipLaunchKernelGGL(harris_stamp_kernel, dim3((unsigned)((o.n + 255) / 256)), dim3(256), 0, stream, p.img.rows, p.img.cols, o.uv, o.flags, o.ids, o.n,
-                           o.plane);
-        hipLaunchKernelGGL(harris_dilate_rows_kernel, dim3(blocks), dim3(256), 0, stream, p.img.rows, p.img.cols, reach, o.plane, o.dilated);
-        hipLaunchKernelGGL(harris_block_kernel, dim3(blocks), dim3(256), 0, stream, p.img.rows, p.img.cols, reach, o.dilated, p.key);
+        hipLaunchKernelGGL(harris_stamp_kernel, dim3((unsigned)((o.n + 255) / 256)), dim3(256), 0, stream, p.rows, p.cols, o.uv, o.flags, o.ids, o.n, o.plane);
+        hipLaunchKernelGGL(harris_dilate_rows_kernel, dim3(blocks), dim3(256), 0, stream, p.rows, p.cols, p.reach, o.plane, o.dilated);
+        hipLaunchKernelGGL(harris_block_kernel, dim3(blocks), dim3(256), 0, stream, p.rows, p.cols, p.reach, o.dilated, p.key);
     }
-    hipLaunchKernelGGL(harris_window_max_kernel, dim3(blocks), dim3(256), 0, stream, p.img.rows, p.img.cols, reach, 1, p.key, p.tmp);
-    hipLaunchKernelGGL(harris_window_max_kernel, dim3(blocks), dim3(256), 0, stream, p.img.rows, p.img.cols, reach, 0, p.tmp, p.wmax);
+    hipLaunchKernelGGL(harris_window_max_kernel, dim3(blocks), dim3(256), 0, stream, p.rows, p.cols, p.reach, 1, p.key, p.tmp);
+    hipLaunchKernelGGL(harris_window_max_kernel, dim3(blocks), dim3(256), 0, stream, p.rows, p.cols, p.reach, 0, p.tmp, p.wmax);
     hipError_t e = hipMemsetAsync(p.count, 0, sizeof(unsigned), stream);
     if (e != hipSuccess) {
         return e;
     }
     hipLaunchKernelGGL(harris_collect_kernel, dim3(blocks), dim3(256), 0, stream, total, p.key, p.wmax, p.list, p.count, p.capacity);
     return hipGetLastError();
+}
+
+hipError_t harris_masked_launch(const HarrisParams &p, const HarrisOccupied &o, hipStream_t stream) {
+    const long long total = (long long)p.img.rows * p.img.cols;
+    const unsigned blocks = (unsigned)((total + 255) / 256);
+    hipLaunchKernelGGL(harris_gradient_kernel, dim3(blocks), dim3(256), 0, stream, p.img, p.gx, p.gy);
+    hipLaunchKernelGGL(harris_response_kernel, dim3(blocks), dim3(256), 0, stream, p.img.rows, p.img.cols, p.gx, p.gy, p.min_response, p.response,
+                       p.key);
+    KeyPlaneSelectParams s{};
+    s.rows = p.img.rows;
+    s.cols = p.img.cols;
+    s.reach = (p.min_distance > 1 ? p.min_distance : 1) - 1;
+    s.key = p.key;
+    s.tmp = p.tmp;
+    s.wmax = p.wmax;
+    s.list = p.list;
+    s.count = p.count;
+    s.capacity = p.capacity;
+    return key_plane_select_launch(s, o, stream);
 }
 
 hipError_t brief_launch(const BriefParams &p, hipStream_t stream) {

@@ -300,6 +300,16 @@ struct HarrisOccupied {
 // harris_launch's passes with the occupied points' neighbourhoods taken out of the candidates first; p.list must be set, and
 // p.capacity entries suffice when it is the plan's bound (track_table_plan.h).
 hipError_t harris_masked_launch(const HarrisParams &p, const HarrisOccupied &o, hipStream_t stream);
+// The passes of harris_masked_launch behind the response: any plane of sortable 64-bit keys (score bits << 32 | ~pixel index, 0: no
+// candidate) to the list of its survivors (DESIGN.md 5.19's rules).  The keypoint decoder's key plane goes through it too (5.22).
+struct KeyPlaneSelectParams {
+    int32_t rows, cols, reach;
+    unsigned long long *key, *tmp, *wmax;  // rows*cols each
+    unsigned long long *list;              // capacity entries
+    unsigned *count;
+    unsigned capacity;
+};
+hipError_t key_plane_select_launch(const KeyPlaneSelectParams &p, const HarrisOccupied &o, hipStream_t stream);
 
 // The track table (track_table_kernels.hip, KltVideoTracker): fixed slots, torch-owned.
 struct TrackTable {
@@ -331,6 +341,7 @@ struct HarrisRankParams {
     float *uv_out;                   // detection: [max_count][2], zeroed before the launch; null: fill the table
     int32_t *count_out;
     int32_t max_count;
+    float *score_out;                // detection: [max_count] the float the key's upper 32 bits carry, or null
     TrackTable t;                    // fill
     const int32_t *free_slots;
     const int32_t *n_free;
@@ -340,6 +351,7 @@ hipError_t track_table_retire_launch(const TrackTablePlan &plan, const TrackReti
 // Ranks the survivors (rank = survivors with a greater key) and writes rows (uv_out) or table slots; in fill mode a second, one-thread
 // launch advances next_id and n_live.
 hipError_t harris_rank_launch(const TrackTablePlan &plan, const HarrisRankParams &p, hipStream_t stream);
+hipError_t harris_rank_launch(uint32_t rank_blocks, const HarrisRankParams &p, hipStream_t stream);  // the same with the grid alone
 
 // Dense optical flow (dense_flow_kernels.hip, DenseOpticalFlow).  Moments: two float4 per pixel, {S0, Sr, Sc, Src} then {Srr, Scc, 0, 0},
 // row-major at the image's own size; flow planes row-major at the ref level's size.

@@ -101,6 +101,10 @@ __global__ void __launch_bounds__(kHarrisRankTile) harris_rank_kernel(const Harr
     if (p.uv_out) {
         if (rank < (unsigned)p.max_count) {
             reinterpret_cast<float2 *>(p.uv_out)[rank] = make_float2(u, v);
+            if (p.score_out) {  // sortable_bits (feature_kernels.hip) undone
+                const unsigned s = (unsigned)(mine >> 32);
+                p.score_out[rank] = __uint_as_float((s & 0x80000000u) ? (s ^ 0x80000000u) : ~s);
+            }
         }
         return;
     }
@@ -139,8 +143,12 @@ hipError_t track_table_retire_launch(const TrackTablePlan &plan, const TrackReti
 }
 
 hipError_t harris_rank_launch(const TrackTablePlan &plan, const HarrisRankParams &p, hipStream_t stream) {
+    return harris_rank_launch(plan.rank_blocks, p, stream);
+}
+
+hipError_t harris_rank_launch(uint32_t rank_blocks, const HarrisRankParams &p, hipStream_t stream) {
     // (one workgroup at least: with an empty list it still writes the count)
-    hipLaunchKernelGGL(harris_rank_kernel, dim3(plan.rank_blocks > 0 ? plan.rank_blocks : 1), dim3(kHarrisRankTile), 0, stream, p);
+    hipLaunchKernelGGL(harris_rank_kernel, dim3(rank_blocks > 0 ? rank_blocks : 1), dim3(kHarrisRankTile), 0, stream, p);
     if (!p.uv_out) {
         hipLaunchKernelGGL(track_advance_kernel, dim3(1), dim3(64), 0, stream, p);
     }

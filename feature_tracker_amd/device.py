@@ -485,6 +485,7 @@ from ._device_corr_ondemand import corr_ondemand_lookup_device, corr_ondemand_pr
 from ._device_klt_video import _check_bound, harris_detect_device, track_table_fill_device, track_table_retire_device  # noqa: E402,F401  (masked Harris detection and KltVideoTracker's table; its own file, see there)
 from ._device_epipolar import epipolar_ransac_device  # noqa: E402,F401  (two-view outlier rejection; its own file, see there)
 from ._device_two_view import two_view_ransac_device  # noqa: E402,F401  (the same with a choice of model)
+from ._device_keypoint_decode import keypoint_decode_device  # noqa: E402,F401  (the keypoint decoder; its own file, see there)
 
 
 def _nn_stream(torch, device, stream):

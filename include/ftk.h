@@ -350,6 +350,38 @@ int ftk_two_view_ransac_device(ftk_context *ctx, void *stream, const float *d_re
                                int32_t prefer_homography_permille, void *d_workspace, int32_t *d_model, int32_t *d_best, int32_t *d_n_inliers,
                                float *d_F, float *d_H, int32_t *d_counts, float *d_models);
 
+/*
+ * ftk_keypoint_decode_device — a SuperPoint-style network's head tensors to keypoints, scores and descriptors, all in device memory
+ * (KeypointDecoder).  The networks are not part of this library; this is the weight-free arithmetic behind them.
+ *   d_semi: float32 [65][cell_rows][cell_cols], the detector head's logits, channel 64 the dustbin.  The image is H = 8 cell_rows by
+ *   W = 8 cell_cols.  Per cell: m = the maximum (x_0, then `if (x_k > m) m = x_k` ascending), e_k = exp_c(x_k - m),
+ *   sum = e_0 + e_1 + ... + e_64 ascending, score_k = e_k / sum at pixel (8 cy + k / 8, 8 cx + k % 8) for k < 64.  A pixel is a candidate
+ *   iff score > min_score and it lies at least `border` pixels from every image edge; its key is sortable(score) << 32 | ~pixel index.
+ *   Suppression and selection are ftk_harris_detect_device's on that key plane (d_occupied_uv / d_occupied_flags / n_occupied as there):
+ *   row r < max_keypoints of d_uv receives (col, row) of the survivor of rank r, d_scores[r] its score, d_count[0] = min(S, max_keypoints);
+ *   rows behind the count are zeros.
+ *   d_desc: float32, `channels` channels over the cell grid, element (c, cy, cx) at d_desc[c desc_stride_c + cy desc_stride_y +
+ *   cx desc_stride_x] (strides in elements, >= 0).  Row r of d_descriptors [max_keypoints][channels] is the bilinear sample at
+ *   xc = min(max((x - 3.5) * 0.125, 0), cell_cols - 1), yc likewise, v_c = ((w00 d00 + w01 d01) + w10 d10) + w11 d11, divided by
+ *   max(sqrt(n2), 1e-12) where n2 sums v_c^2 per lane of 64 (fmaf, channels l, l + 64, ... ascending) and then over six rounds
+ *   p_l + p_(l xor off), off = 32 .. 1.  Non-finite values propagate.
+ *   d_heatmap: float32 [H][W] of every pixel's score, or NULL.
+ * d_workspace: ftk_keypoint_decode_workspace_bytes(cell_rows, cell_cols, min_distance, n_occupied) bytes, 16-byte aligned, no
+ * initialisation needed.  Limits: H, W <= 65 536; ceil(H / d) ceil(W / d) <= FTK_HARRIS_DEVICE_MAX_SURVIVORS with d = max(min_distance, 1)
+ * (FTK_E_UNSUPPORTED); 1 <= max_keypoints <= FTK_KEYPOINT_DECODE_MAX_KEYPOINTS; 1 <= channels <= FTK_KEYPOINT_DECODE_MAX_CHANNELS;
+ * min_score finite; border >= 0.  Everything is refused before any launch.  7 launches (10 with occupied points) of fixed shape on
+ * `stream`; no host read, no synchronisation, no allocation: capturable.
+ */
+#define FTK_KEYPOINT_DECODE_CELL 8
+#define FTK_KEYPOINT_DECODE_MAX_KEYPOINTS 65536
+#define FTK_KEYPOINT_DECODE_MAX_CHANNELS 1024
+int ftk_keypoint_decode_workspace_bytes(int32_t cell_rows, int32_t cell_cols, int32_t min_distance, int32_t n_occupied, int64_t *bytes);
+int ftk_keypoint_decode_device(ftk_context *ctx, void *stream, const float *d_semi, int32_t cell_rows, int32_t cell_cols, const float *d_desc,
+                               int32_t channels, int64_t desc_stride_c, int64_t desc_stride_y, int64_t desc_stride_x, int32_t max_keypoints,
+                               float min_score, int32_t min_distance, int32_t border, const float *d_occupied_uv, const uint8_t *d_occupied_flags,
+                               int32_t n_occupied, void *d_workspace, float *d_uv, float *d_scores, float *d_descriptors, int32_t *d_count,
+                               float *d_heatmap);
+
 /* ---- diagnostics ---------------------------------------------------------------------------- */
 
 /*
