@@ -43,6 +43,9 @@ TWO_VIEW_MODES = {"fundamental": 0, "homography": 1, "auto": 2}
 FTK_KEYPOINT_DECODE_CELL = 8
 FTK_KEYPOINT_DECODE_MAX_KEYPOINTS = 65536
 FTK_KEYPOINT_DECODE_MAX_CHANNELS = 1024
+# the assignment head (include/ftk.h)
+FTK_MATCH_ASSIGNMENT_MAX_ROWS = 4096
+FTK_MATCH_ASSIGNMENT_MAX_DIM = 1024
 # SepConvGru (include/ftk.h): the supported sizes and the packed weight layout
 FTK_SEP_CONV_GRU_MAX_PARTS = 3
 FTK_SEP_CONV_GRU_MAX_H_CHANNELS = 1024
@@ -81,6 +84,7 @@ EXPORTS = [
     "ftk_epipolar_workspace_bytes", "ftk_epipolar_ransac_device",
     "ftk_two_view_workspace_bytes", "ftk_two_view_ransac_device",
     "ftk_keypoint_decode_workspace_bytes", "ftk_keypoint_decode_device",
+    "ftk_match_assignment_workspace_bytes", "ftk_match_assignment_device",
 ]
 UNIQUE_ID_BYTES = 128
 
@@ -266,6 +270,8 @@ def lib() -> C.CDLL:
     l.ftk_two_view_ransac_device.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, C.c_uint32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     l.ftk_keypoint_decode_workspace_bytes.argtypes = [i32, i32, i32, i32, i64p]
     l.ftk_keypoint_decode_device.argtypes = [vp, vp, vp, i32, i32, vp, i32, C.c_int64, C.c_int64, C.c_int64, i32, f32, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]
+    l.ftk_match_assignment_workspace_bytes.argtypes = [i32, i32, i32, i32, i64p]
+    l.ftk_match_assignment_device.argtypes = [vp, vp, vp, i32, vp, i32, i32, vp, vp, f32, vp, vp, vp, vp, C.c_int64]
     _lib = l
     return l
 
@@ -340,6 +346,15 @@ def keypoint_decode_workspace_bytes(cell_rows: int, cell_cols: int, min_distance
     capacity = -(-8 * int(cell_rows) // d) * -(-8 * int(cell_cols) // d)
     up16 = lambda v: (v + 15) & ~15  # noqa: E731
     return 3 * up16(8 * px) + up16(8 * capacity) + 16 + (2 * up16(px) if int(n_occupied) > 0 else 0)
+
+
+def match_assignment_workspace_bytes(rows0: int, rows1: int, dim: int, with_weights: bool) -> int:
+    """Bytes of workspace ftk_match_assignment_device needs, the value ftk_match_assignment_workspace_bytes returns (pure Python;
+    csrc/match_assignment_plan.cpp): the two normalisers, and with weights the projected descriptors, z and ls(z), ls(-z) of both sides."""
+    m, n, d = int(rows0), int(rows1), int(dim)
+    up16 = lambda v: (v + 15) & ~15  # noqa: E731
+    own = up16(4 * m) + up16(4 * n)
+    return own + (up16(4 * (m + n) * d) + up16(4 * (m + n)) + up16(8 * m) + up16(8 * n) if with_weights else 0)
 
 
 def sep_conv_gru_k_steps(in_channels: int, kernel_size: int) -> int:

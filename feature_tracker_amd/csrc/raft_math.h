@@ -36,6 +36,37 @@ __device__ __forceinline__ float exp_c(float t) {
     return p * __uint_as_float((uint32_t)((int)n + 127) << 23);
 }
 
+constexpr uint32_t kLogSqrtHalfBits = 0x3f3504f3u;  // sqrt(1/2)
+constexpr float kLogLn2Hi = 0x1.62e3p-1f;           // 0x3f317180: 16 significant bits, so k * kLogLn2Hi is exact for |k| < 256
+constexpr float kLogLn2Lo = 0x1.2fefa2p-17f;        // 0x3717f7d1
+
+// log_c of DESIGN.md 5.23, x a positive normal number or NaN (here x in [1, 4096]): x = 2^k m with m in [sqrt(1/2), sqrt(2)) taken
+// off the bit pattern, f = m - 1 (exact), s = f / (2 + f), log m = 2 atanh(s) = f - f^2 / 2 + s (f^2 / 2 + R(s^2)) with R the four
+// minimax coefficients of fdlibm's logf.  log_c(1) = +0; NaN gives NaN.
+__device__ __forceinline__ float log_c(float x) {
+    if (x != x) {
+        return x;
+    }
+    const uint32_t ix = __float_as_uint(x) + (0x3f800000u - kLogSqrtHalfBits);
+    const float dk = (float)((int)(ix >> 23) - 127);
+    const float f = __fsub_rn(__uint_as_float((ix & 0x007fffffu) + kLogSqrtHalfBits), 1.0f);
+    const float s = __fdiv_rn(f, __fadd_rn(2.0f, f));
+    const float z = __fmul_rn(s, s);
+    const float w = __fmul_rn(z, z);
+    const float t1 = __fmul_rn(w, fmaf(w, 0x1.f13c4cp-3f, 0x1.999c26p-2f));
+    const float t2 = __fmul_rn(z, fmaf(w, 0x1.23d3dcp-2f, 0x1.555554p-1f));
+    const float R = __fadd_rn(t2, t1);
+    const float hfsq = __fmul_rn(__fmul_rn(0.5f, f), f);
+    float r = fmaf(s, __fadd_rn(hfsq, R), __fmul_rn(dk, kLogLn2Lo));
+    r = __fadd_rn(__fsub_rn(r, hfsq), f);
+    return fmaf(dk, kLogLn2Hi, r);
+}
+
+// ls of DESIGN.md 5.23 (log sigmoid): min(z, 0) - log_c(1 + exp_c(-|z|)); NaN gives NaN.
+__device__ __forceinline__ float log_sigmoid_c(float z) {
+    return __fsub_rn(fminf(z, 0.0f), log_c(__fadd_rn(1.0f, exp_c(-fabsf(z)))));
+}
+
 // sigmoid_c of DESIGN.md 5.13: 1 / (1 + e) for v >= 0 and e / (1 + e) otherwise, e = exp_c(-|v|); NaN gives NaN.
 __device__ __forceinline__ float sigmoid_c(float v) {
     const float e = exp_c(-fabsf(v));

@@ -382,6 +382,31 @@ int ftk_keypoint_decode_device(ftk_context *ctx, void *stream, const float *d_se
                                int32_t n_occupied, void *d_workspace, float *d_uv, float *d_scores, float *d_descriptors, int32_t *d_count,
                                float *d_heatmap);
 
+/*
+ * ftk_match_assignment_device — LightGlue's assignment head: two descriptor sets to the log-assignment tensor that
+ * ftk_nn_match_scores_device reads, all in device memory (MatchAssignment).  It replaces the tail of the network run at
+ * nn_feature_matcher.cpp:130-131 (session_.Run), which is upstream LightGlue's MatchAssignment.forward; the transformer layers before it
+ * are not part of this library.
+ *   d_desc0 [rows0][dim], d_desc1 [rows1][dim]: float32, dense rows.  d_weights: float32 [dim + 1][dim], rows 0 .. dim - 1 final_proj.weight
+ *   and row dim matchability.weight; d_bias: float32 [dim + 1] likewise; both NULL: no projection and no matchability, every descriptor
+ *   element is multiplied by `scale` (finite, > 0; ignored with weights).  d_count0 / d_count1: int32 [1] device words or NULL: rows
+ *   i < n0 = clamp(count0, 0, rows0) and columns j < n1 = clamp(count1, 0, rows1) are valid (NULL: all).
+ *   d_scores: [rows0 + 1] rows of row_stride floats (0: rows1 + 1), of which rows1 + 1 are written: entry (i, j) of the valid block is
+ *   ((sim - lse_row_i) + (sim - lse_col_j)) + (ls(z0_i) + ls(z1_j)), the dustbin column ls(-z0_i), the dustbin row ls(-z1_j), the
+ *   corner +0; without weights there is no ls term and the dustbins are -inf; every entry of an invalid row or column is -inf.  The
+ *   arithmetic is DESIGN.md 5.23's to the bit.  Non-finite values propagate; the inputs are never written.
+ * d_workspace: ftk_match_assignment_workspace_bytes(rows0, rows1, dim, with_weights) bytes, 16-byte aligned, no initialisation needed.
+ * Limits: 1 <= rows0, rows1 <= FTK_MATCH_ASSIGNMENT_MAX_ROWS; 1 <= dim <= FTK_MATCH_ASSIGNMENT_MAX_DIM; row_stride 0 or >= rows1 + 1.
+ * Everything is refused before any launch.  4 launches (3 without weights) of fixed shape on `stream`; no host read, no
+ * synchronisation, no allocation: capturable.
+ */
+#define FTK_MATCH_ASSIGNMENT_MAX_ROWS 4096
+#define FTK_MATCH_ASSIGNMENT_MAX_DIM 1024
+int ftk_match_assignment_workspace_bytes(int32_t rows0, int32_t rows1, int32_t dim, int32_t with_weights, int64_t *bytes);
+int ftk_match_assignment_device(ftk_context *ctx, void *stream, const float *d_desc0, int32_t rows0, const float *d_desc1, int32_t rows1, int32_t dim,
+                                const float *d_weights, const float *d_bias, float scale, const int32_t *d_count0, const int32_t *d_count1,
+                                void *d_workspace, float *d_scores, int64_t row_stride);
+
 /* ---- diagnostics ---------------------------------------------------------------------------- */
 
 /*
