@@ -18,6 +18,7 @@ CASES = {
     "lssd_direct": ("lssd", "direct", 64, (3.3, -2.1), 0.5, None, None),
     "one_slot": ("basic", "fast", 1, (3.3, -2.1), 0.0, None, None),
     "more_slots_than_corners": ("basic", "fast", 512, (3.3, -2.1), 0.0, None, None),
+    "more_slots_than_a_retire_block": ("basic", "fast", 1500, (3.3, -2.1), 0.0, None, None),
     "large_shift": ("basic", "fast", 64, (11.7, -8.4), 0.0, None, None),
     "forward_backward": ("basic", "fast", 64, (14.3, -10.2), 3.0, 1.0, None),
     "reset_mid_sequence": ("basic", "fast", 64, (3.3, -2.1), 0.0, None, 3),

@@ -57,7 +57,7 @@ def test_invariants_on_random_occupied_sets(distance, seed):
     assert {tuple(p) for p in far} <= {tuple(p) for p in got}
 
 
-@pytest.mark.parametrize("name", ["basic_fast", "more_slots_than_corners", "large_shift", "forward_backward", "reset_mid_sequence"])
+@pytest.mark.parametrize("name", ["basic_fast", "more_slots_than_corners", "more_slots_than_a_retire_block", "large_shift", "forward_backward", "reset_mid_sequence"])
 def test_table_invariants_over_a_sequence(name):
     states, _ = K.reference_run(name)
     seen, top = set(), -1
