@@ -32,12 +32,17 @@ def check_sizes(image_size, threshold, hypotheses, seed):
     return rows, cols, t, k, int(seed)
 
 
-def epipolar_ransac_args(ctx, ref_uv, cur_uv, status, image_size, threshold: float, hypotheses: int, seed: int, workspace, best, n_inliers, F,
-                         counts=None, models=None, stream=None):
-    """Checks one ftk_epipolar_ransac_device call and returns its marshalled arguments (KltVideoTracker keeps them: its tensors are fixed)."""
+def _ptr(x):
+    return None if x is None else C.c_void_p(x.data_ptr())
+
+
+def ransac_inputs(ctx, ref_uv, cur_uv, status, sizes, stream):
+    """What the checks of ftk_epipolar_ransac_device and ftk_two_view_ransac_device share after ``sizes = check_sizes(...)``: the three input
+    tensors, the limit of n and the choice of stream.  Returns (device.py, the device the other tensors must be on, n, hypotheses, the
+    marshalled arguments up to and including the seed); the caller checks its workspace and outputs against them and appends their pointers."""
     from . import device as D
 
-    rows, cols, t, k, seed = check_sizes(image_size, threshold, hypotheses, seed)
+    rows, cols, t, k, seed = sizes
     dev = D._call_device(ctx, ref_uv)
     D._check("ref_uv", ref_uv, D._F32, (None, 2), dev)
     n = int(ref_uv.shape[0])
@@ -45,6 +50,15 @@ def epipolar_ransac_args(ctx, ref_uv, cur_uv, status, image_size, threshold: flo
         raise ValueError(f"ref_uv must have 1 .. FTK_TRACK_TABLE_MAX_SLOTS = {N.FTK_TRACK_TABLE_MAX_SLOTS} points (got {n})")
     D._check("cur_uv", cur_uv, D._F32, (n, 2), dev)
     D._check("status", status, D._U8, (n,), dev)
+    s = D._torch().cuda.current_stream(ref_uv.device) if stream is None else stream
+    head = (ctx.handle, C.c_void_p(s.cuda_stream), _ptr(ref_uv), _ptr(cur_uv), _ptr(status), n, rows, cols, C.c_float(t), k, C.c_uint32(seed))
+    return D, dev, n, k, head
+
+
+def epipolar_ransac_args(ctx, ref_uv, cur_uv, status, image_size, threshold: float, hypotheses: int, seed: int, workspace, best, n_inliers, F,
+                         counts=None, models=None, stream=None):
+    """Checks one ftk_epipolar_ransac_device call and returns its marshalled arguments (KltVideoTracker keeps them: its tensors are fixed)."""
+    D, dev, n, k, head = ransac_inputs(ctx, ref_uv, cur_uv, status, check_sizes(image_size, threshold, hypotheses, seed), stream)
     D._check("workspace", workspace, D._KEYS, (None,), dev, min_numel=-(-N.epipolar_workspace_bytes(n, k) // 8))
     D._check("best", best, D._I32, (1,), dev)
     D._check("n_inliers", n_inliers, D._I32, (1,), dev)
@@ -53,10 +67,7 @@ def epipolar_ransac_args(ctx, ref_uv, cur_uv, status, image_size, threshold: flo
         D._check("counts", counts, D._I32, (k,), dev)
     if models is not None:
         D._check("models", models, D._F32, (k, 9), dev)
-    s = D._torch().cuda.current_stream(ref_uv.device) if stream is None else stream
-    p = lambda x: None if x is None else C.c_void_p(x.data_ptr())  # noqa: E731
-    return (ctx.handle, C.c_void_p(s.cuda_stream), p(ref_uv), p(cur_uv), p(status), n, rows, cols, C.c_float(t), k, C.c_uint32(seed), p(workspace),
-            p(best), p(n_inliers), p(F), p(counts), p(models))
+    return head + (_ptr(workspace), _ptr(best), _ptr(n_inliers), _ptr(F), _ptr(counts), _ptr(models))
 
 
 def epipolar_ransac_device(ctx, ref_uv, cur_uv, status, image_size, threshold: float, hypotheses: int, seed: int, workspace, best, n_inliers, F,

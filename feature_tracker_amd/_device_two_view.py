@@ -6,13 +6,10 @@ in a file of its own for _device_epipolar.py's reason; its walk and its refusals
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 
 from . import _native as N
-from ._device_epipolar import check_sizes
-
-SEED_ARG = 10  # where the seed sits in the marshalled arguments (KltVideoTracker replaces it per frame)
+from ._device_epipolar import SEED_ARG, _ptr, check_sizes, ransac_inputs  # noqa: F401  (SEED_ARG: both entries share the arguments up to the seed)
 
 
 def check_mode(model) -> int:
@@ -44,17 +41,9 @@ def prefer_to_permille(prefer_homography) -> int:
 def two_view_ransac_args(ctx, ref_uv, cur_uv, status, image_size, threshold: float, hypotheses: int, seed: int, model, prefer_homography_permille: int,
                          workspace, model_out, best, n_inliers, F, H, counts=None, models=None, stream=None):
     """Checks one ftk_two_view_ransac_device call and returns its marshalled arguments (KltVideoTracker keeps them: its tensors are fixed)."""
-    from . import device as D
-
-    rows, cols, t, k, seed = check_sizes(image_size, threshold, hypotheses, seed)
+    sizes = check_sizes(image_size, threshold, hypotheses, seed)
     mode, permille = check_mode(model), check_permille(prefer_homography_permille)
-    dev = D._call_device(ctx, ref_uv)
-    D._check("ref_uv", ref_uv, D._F32, (None, 2), dev)
-    n = int(ref_uv.shape[0])
-    if not 1 <= n <= N.FTK_TRACK_TABLE_MAX_SLOTS:
-        raise ValueError(f"ref_uv must have 1 .. FTK_TRACK_TABLE_MAX_SLOTS = {N.FTK_TRACK_TABLE_MAX_SLOTS} points (got {n})")
-    D._check("cur_uv", cur_uv, D._F32, (n, 2), dev)
-    D._check("status", status, D._U8, (n,), dev)
+    D, dev, n, k, head = ransac_inputs(ctx, ref_uv, cur_uv, status, sizes, stream)
     D._check("workspace", workspace, D._KEYS, (None,), dev, min_numel=-(-N.two_view_workspace_bytes(n, k, mode) // 8))
     D._check("model_out", model_out, D._I32, (1,), dev)
     D._check("best", best, D._I32, (2,), dev)
@@ -65,10 +54,7 @@ def two_view_ransac_args(ctx, ref_uv, cur_uv, status, image_size, threshold: flo
         D._check("counts", counts, D._I32, (2, k), dev)
     if models is not None:
         D._check("models", models, D._F32, (2, k, 9), dev)
-    s = D._torch().cuda.current_stream(ref_uv.device) if stream is None else stream
-    p = lambda x: None if x is None else C.c_void_p(x.data_ptr())  # noqa: E731
-    return (ctx.handle, C.c_void_p(s.cuda_stream), p(ref_uv), p(cur_uv), p(status), n, rows, cols, C.c_float(t), k, C.c_uint32(seed), mode, permille,
-            p(workspace), p(model_out), p(best), p(n_inliers), p(F), p(H), p(counts), p(models))
+    return head + (mode, permille, _ptr(workspace), _ptr(model_out), _ptr(best), _ptr(n_inliers), _ptr(F), _ptr(H), _ptr(counts), _ptr(models))
 
 
 def two_view_ransac_device(ctx, ref_uv, cur_uv, status, image_size, threshold: float, hypotheses: int, seed: int, model, prefer_homography_permille: int,

@@ -320,21 +320,24 @@ def flow_warm_splits(B: int, H: int, W: int) -> int:
     return splits.value
 
 
-def epipolar_workspace_bytes(n: int, hypotheses: int) -> int:
-    """Bytes of workspace ftk_epipolar_ransac_device needs, the value ftk_epipolar_workspace_bytes returns (pure Python: argument checks
-    need no library; csrc/epipolar_plan.cpp): M, then the participants' normalised coordinates, their indices, counts, models and validity
-    flags, each block rounded up to 16 bytes."""
-    n, k = int(n), int(hypotheses)
+def _ransac_workspace_bytes(n: int, hypotheses: int, slots: int) -> int:
+    """csrc/two_view_plan.cpp's workspace: M, then the participants' normalised coordinates, their indices, and per slot counts, models and
+    validity flags, each block rounded up to 16 bytes."""
+    n, k = int(n), slots * int(hypotheses)
     up16 = lambda v: (v + 15) & ~15  # noqa: E731
     return 16 + up16(16 * n) + up16(4 * n) + up16(4 * k) + up16(36 * k) + up16(k)
 
 
+def epipolar_workspace_bytes(n: int, hypotheses: int) -> int:
+    """Bytes of workspace ftk_epipolar_ransac_device needs, the value ftk_epipolar_workspace_bytes returns (pure Python: argument checks
+    need no library): the plan's layout with one slot."""
+    return _ransac_workspace_bytes(n, hypotheses, 1)
+
+
 def two_view_workspace_bytes(n: int, hypotheses: int, mode: int = FTK_TWO_VIEW_AUTO) -> int:
-    """Bytes of workspace ftk_two_view_ransac_device needs, the value ftk_two_view_workspace_bytes returns (pure Python;
-    csrc/two_view_plan.cpp): epipolar_workspace_bytes' layout with counts, models and validity flags of two models, the same for every mode."""
-    n, k = int(n), int(hypotheses)
-    up16 = lambda v: (v + 15) & ~15  # noqa: E731
-    return 16 + up16(16 * n) + up16(4 * n) + up16(8 * k) + up16(72 * k) + up16(2 * k)
+    """Bytes of workspace ftk_two_view_ransac_device needs, the value ftk_two_view_workspace_bytes returns (pure Python): the plan's layout
+    with the slots of two models, the same for every mode."""
+    return _ransac_workspace_bytes(n, hypotheses, 2)
 
 
 def keypoint_decode_workspace_bytes(cell_rows: int, cell_cols: int, min_distance: int, n_occupied: int = 0) -> int:

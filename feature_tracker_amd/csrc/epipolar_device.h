@@ -1,10 +1,11 @@
-// epipolar_device.h — the device functions that the two-view kernels share (epipolar_kernels.hip, two_view_kernels.hip; DESIGN.md 5.20,
-// 5.21): "finite", the hash, the sampler, the Sampson test and the null vector of an 8 x 9 system by Gaussian elimination with complete
-// pivoting.  Every float operation is stated in DESIGN.md 5.20 and restated in tests/epipolar_ref.c and tests/two_view_ref.c; the build
-// has no contraction (-ffp-contract=off) and correctly rounded division and square root.
+// epipolar_device.h — the device functions of the two-view kernels (two_view_kernels.hip): "finite", the hash, the
+// sampler, the null vector of an 8 x 9 system by Gaussian elimination with complete pivoting, the two inlier tests, and the two models
+// as compile-time traits of the hypothesis, score and select kernels.  Every float operation is stated in DESIGN.md 5.20 and 5.21 and
+// restated in tests/epipolar_ref.c and tests/two_view_ref.c; the build has no contraction (-ffp-contract=off) and correctly rounded
+// division and square root.
 #pragma once
 
-#include "epipolar_plan.h"
+#include "two_view_plan.h"
 
 namespace ftk {
 
@@ -64,6 +65,71 @@ __device__ __forceinline__ bool ep_inlier(const float (&f)[9], const float4 q, f
     const float lhs = num * num, rhs = tn2 * den;
     return den > 0.0f && ep_finite(lhs) && ep_finite(rhs) && lhs <= rhs;
 }
+
+// The one-sided transfer error in the current image without the division, q = normalised (x1, y1, x2, y2), g = normalised H row-major.
+__device__ __forceinline__ bool tv_inlier(const float (&g)[9], const float4 q, float tn2) {
+    const float x1 = q.x, y1 = q.y, x2 = q.z, y2 = q.w;
+    if (!(ep_finite(x1) && ep_finite(y1) && ep_finite(x2) && ep_finite(y2))) {
+        return false;
+    }
+    const float w = (g[6] * x1 + g[7] * y1) + g[8];
+    const float px = (g[0] * x1 + g[1] * y1) + g[2];
+    const float py = (g[3] * x1 + g[4] * y1) + g[5];
+    const float ex = px - x2 * w;
+    const float ey = py - y2 * w;
+    const float lhs = ex * ex + ey * ey, rhs = tn2 * (w * w);
+    return w != 0.0f && ep_finite(lhs) && ep_finite(rhs) && lhs <= rhs;
+}
+
+// The models.  kSample: correspondences of a hypothesis; kSlot: the model's slot of TwoViewParams; fill: the rows that the k-th drawn
+// correspondence q contributes to the 8 x 9 system a (LDS, a[(r * 9 + c) * L] of this lane); inlier: the test of a participant.
+struct FundamentalModel {
+    static constexpr int kSample = kEpipolarSample;
+    static constexpr int kSlot = kTwoViewFundamental;
+    template <int L>
+    static __device__ __forceinline__ void fill(float *const a, const int k, const float4 q) {  // one row: the epipolar constraint
+        const float x1 = q.x, y1 = q.y, x2 = q.z, y2 = q.w;
+        a[(k * 9 + 0) * L] = x2 * x1;
+        a[(k * 9 + 1) * L] = x2 * y1;
+        a[(k * 9 + 2) * L] = x2;
+        a[(k * 9 + 3) * L] = y2 * x1;
+        a[(k * 9 + 4) * L] = y2 * y1;
+        a[(k * 9 + 5) * L] = y2;
+        a[(k * 9 + 6) * L] = x1;
+        a[(k * 9 + 7) * L] = y1;
+        a[(k * 9 + 8) * L] = 1.0f;
+    }
+    static __device__ __forceinline__ bool inlier(const float (&f)[9], const float4 q, float tn2) { return ep_inlier(f, q, tn2); }
+};
+
+struct HomographyModel {
+    static constexpr int kSample = kTwoViewHomSample;
+    static constexpr int kSlot = kTwoViewHomography;
+    template <int L>
+    static __device__ __forceinline__ void fill(float *const a, const int k, const float4 q) {  // two rows: the DLT system
+        const float x1 = q.x, y1 = q.y, x2 = q.z, y2 = q.w;
+        const int r0 = 2 * k * 9, r1 = (2 * k + 1) * 9;
+        a[(r0 + 0) * L] = x1;
+        a[(r0 + 1) * L] = y1;
+        a[(r0 + 2) * L] = 1.0f;
+        a[(r0 + 3) * L] = 0.0f;
+        a[(r0 + 4) * L] = 0.0f;
+        a[(r0 + 5) * L] = 0.0f;
+        a[(r0 + 6) * L] = -(x2 * x1);
+        a[(r0 + 7) * L] = -(x2 * y1);
+        a[(r0 + 8) * L] = -x2;
+        a[(r1 + 0) * L] = 0.0f;
+        a[(r1 + 1) * L] = 0.0f;
+        a[(r1 + 2) * L] = 0.0f;
+        a[(r1 + 3) * L] = x1;
+        a[(r1 + 4) * L] = y1;
+        a[(r1 + 5) * L] = 1.0f;
+        a[(r1 + 6) * L] = -(y2 * x1);
+        a[(r1 + 7) * L] = -(y2 * y1);
+        a[(r1 + 8) * L] = -y2;
+    }
+    static __device__ __forceinline__ bool inlier(const float (&g)[9], const float4 q, float tn2) { return tv_inlier(g, q, tn2); }
+};
 
 // The unit null vector of the 8 x 9 matrix a (LDS, a[(r * 9 + c) * L] of this lane; destroyed), by Gaussian elimination with complete
 // pivoting, back substitution with the free unknown 1 and scaling to unit norm.  perm (9 ints) and fv (9 floats) are this lane's LDS

@@ -17,7 +17,7 @@ const char *two_view_refusal_name(TwoViewRefusal r) {
 
 TwoViewPlan two_view_plan(const TwoViewPlanInput &in) {
     TwoViewPlan p{};
-    if (in.mode < kTwoViewFundamental || in.mode > kTwoViewAuto) {
+    if (in.mode < kTwoViewFundamental || in.mode > (in.slots == 1 ? kTwoViewFundamental : kTwoViewAuto)) {
         p.refused = TwoViewRefusal::Mode;
         return p;
     }
@@ -25,36 +25,40 @@ TwoViewPlan two_view_plan(const TwoViewPlanInput &in) {
         p.refused = TwoViewRefusal::Prefer;
         return p;
     }
-    EpipolarPlanInput ein{};
-    ein.n = in.n;
-    ein.hypotheses = in.hypotheses;
-    ein.image_rows = in.image_rows;
-    ein.image_cols = in.image_cols;
-    const EpipolarPlan e = epipolar_plan(ein);  // the sizes' limits and the launch shapes are 5.20's
-    switch (e.refused) {
-        case EpipolarRefusal::None: break;
-        case EpipolarRefusal::Points: p.refused = TwoViewRefusal::Points; return p;
-        case EpipolarRefusal::Hypotheses: p.refused = TwoViewRefusal::Hypotheses; return p;
-        default: p.refused = TwoViewRefusal::Sizes; return p;
+    if (in.n < 1 || in.hypotheses < 1 || in.image_rows < 1 || in.image_cols < 1 || in.image_rows > kEpipolarMaxSide || in.image_cols > kEpipolarMaxSide ||
+        in.slots < 1 || in.slots > kTwoViewMaxSlots) {
+        p.refused = TwoViewRefusal::Sizes;
+        return p;
+    }
+    if (in.n > kEpipolarMaxPoints) {
+        p.refused = TwoViewRefusal::Points;
+        return p;
+    }
+    if (in.hypotheses > kEpipolarMaxHypotheses) {
+        p.refused = TwoViewRefusal::Hypotheses;
+        return p;
     }
     const auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t slots = (size_t)in.slots;
     p.refused = TwoViewRefusal::None;
+    p.slots = in.slots;
     p.run_fundamental = in.mode != kTwoViewHomography;
     p.run_homography = in.mode != kTwoViewFundamental;
     p.launches = 2 + 2 * (p.run_fundamental + p.run_homography);
-    p.scan_per_thread = e.scan_per_thread;
-    p.hyp_blocks = e.hyp_blocks;
-    p.hyp_lds = e.hyp_lds;
-    p.score_tiles = e.score_tiles;
-    p.score_groups = e.score_groups;
-    p.score_lds = e.score_lds;
-    p.select_per_thread = e.select_per_thread;
+    p.scan_per_thread = (in.n + kEpipolarScanBlock - 1) / kEpipolarScanBlock;
+    p.scan_lds = sizeof(int32_t) * kEpipolarScanBlock;
+    p.hyp_blocks = (uint32_t)((in.hypotheses + kEpipolarHypBlock - 1) / kEpipolarHypBlock);
+    p.hyp_lds = sizeof(float) * kEpipolarHypLdsFloats * kEpipolarHypBlock;
+    p.score_tiles = (uint32_t)((in.n + kEpipolarScoreTile - 1) / kEpipolarScoreTile);
+    p.score_groups = (uint32_t)((in.hypotheses + kEpipolarScoreGroup - 1) / kEpipolarScoreGroup);
+    p.score_lds = sizeof(float) * 4 * kEpipolarScoreTile;
+    p.select_per_thread = (in.hypotheses + kEpipolarScanBlock - 1) / kEpipolarScanBlock;
     p.off_points = 16;
     p.off_list = p.off_points + up16(sizeof(float) * 4 * (size_t)in.n);
     p.off_counts = p.off_list + up16(sizeof(int32_t) * (size_t)in.n);
-    p.off_models = p.off_counts + up16(sizeof(int32_t) * 2 * (size_t)in.hypotheses);
-    p.off_valid = p.off_models + up16(sizeof(float) * 18 * (size_t)in.hypotheses);
-    p.bytes = p.off_valid + up16(2 * (size_t)in.hypotheses);
+    p.off_models = p.off_counts + up16(sizeof(int32_t) * slots * (size_t)in.hypotheses);
+    p.off_valid = p.off_models + up16(sizeof(float) * 9 * slots * (size_t)in.hypotheses);
+    p.bytes = p.off_valid + up16(slots * (size_t)in.hypotheses);
     return p;
 }
 

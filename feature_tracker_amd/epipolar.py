@@ -1,7 +1,7 @@
 """``EpipolarRansac``: two-view outlier rejection on the device.
 
 Geometric verification is what every visual-odometry front end runs right after tracking or matching: fit a fundamental matrix by RANSAC
-and drop the correspondences that disagree with it.  Here that is four launches of epipolar_kernels.hip on one stream, on tensors that
+and drop the correspondences that disagree with it.  Here that is four launches of two_view_kernels.hip on one stream, on tensors that
 stay where they are: no copy to the host, no count read back, no synchronisation.
 """
 from __future__ import annotations
@@ -10,6 +10,49 @@ from typing import Optional
 
 from . import _native as N
 from ._device_epipolar import check_sizes, epipolar_ransac_args
+
+
+def ransac_filter(ransac, ref_uv, cur_uv, status, image_size, seed, return_hypotheses):
+    """``EpipolarRansac.filter`` and ``TwoViewRansac.filter``: the complaints about the tensors, the choice of context and stream, the one
+    workspace per device of ``ransac`` and the call.  ``ransac`` says what differs: ``_workspace_bytes(n, k)``, ``_result(torch, device, k,
+    return_hypotheses)`` (the result object with its tensors), ``_args(ctx, ..., workspace, out, stream)`` (the marshalled arguments) and
+    ``_entry`` (the native entry they are for)."""
+    rows, cols, _, k, seed = check_sizes(image_size, ransac.threshold, ransac.hypotheses, ransac.seed if seed is None else seed)
+    from . import device as D
+
+    tensors = (("ref_uv", ref_uv, D._F32, (None, 2)), ("cur_uv", cur_uv, D._F32, (None, 2)), ("status", status, D._U8, (None,)))
+    for name, t, dtypes, shape in tensors:
+        complaint = D._tensor_complaint(name, t, dtypes, shape)
+        if complaint:
+            raise ValueError(complaint)
+    for name, t, _, _ in tensors:
+        if not t.is_cuda:
+            raise ValueError(f"{name} must be a CUDA tensor (got one on {t.device}): there is no CPU fallback")
+    torch = D._torch()
+    ctx = ransac._ctx
+    if ctx is None:
+        from .raft import _device_context
+
+        ctx = _device_context(ref_uv)
+    device = ref_uv.device
+    caller = torch.cuda.current_stream(device)
+    stream = getattr(ctx, "stream", None) or caller
+    n = int(ref_uv.shape[0])
+    if stream != caller:
+        stream.wait_stream(caller)
+    with torch.cuda.stream(stream):
+        workspace = ransac._workspace.get(device)
+        if 1 <= n <= N.FTK_TRACK_TABLE_MAX_SLOTS:
+            words = -(-ransac._workspace_bytes(n, k) // 8)
+            if workspace is None or workspace.numel() < words:  # (the old block, if any, goes back to torch's allocator in stream order)
+                workspace = ransac._workspace[device] = torch.empty(words + words // 4, dtype=torch.int64, device=device)
+        out = ransac._result(torch, device, k, return_hypotheses)
+        rc = getattr(N.lib(), ransac._entry)(*ransac._args(ctx, ref_uv, cur_uv, status, (rows, cols), k, seed, workspace, out, stream))
+        if rc != 0:
+            N.check(rc, ctx.handle)
+    if stream != caller:
+        caller.wait_stream(stream)
+    return out
 
 
 class EpipolarResult:
@@ -53,45 +96,21 @@ class EpipolarRansac:
     def filter(self, ref_uv, cur_uv, status, image_size, seed: Optional[int] = None, return_hypotheses: bool = False) -> EpipolarResult:
         """One pass of outlier rejection; ``seed``: this call's seed instead of the object's; ``return_hypotheses``: also ``counts`` and
         ``models``.  Everything is enqueued; the returned tensors are valid in stream order."""
-        rows, cols, _, k, seed = check_sizes(image_size, self.threshold, self.hypotheses, self.seed if seed is None else seed)
-        from . import device as D
+        return ransac_filter(self, ref_uv, cur_uv, status, image_size, seed, return_hypotheses)
 
-        tensors = (("ref_uv", ref_uv, D._F32, (None, 2)), ("cur_uv", cur_uv, D._F32, (None, 2)), ("status", status, D._U8, (None,)))
-        for name, t, dtypes, shape in tensors:
-            complaint = D._tensor_complaint(name, t, dtypes, shape)
-            if complaint:
-                raise ValueError(complaint)
-        for name, t, _, _ in tensors:
-            if not t.is_cuda:
-                raise ValueError(f"{name} must be a CUDA tensor (got one on {t.device}): there is no CPU fallback")
-        torch = D._torch()
-        ctx = self._ctx
-        if ctx is None:
-            from .raft import _device_context
+    _entry = "ftk_epipolar_ransac_device"
 
-            ctx = _device_context(ref_uv)
-        device = ref_uv.device
-        caller = torch.cuda.current_stream(device)
-        stream = getattr(ctx, "stream", None) or caller
-        n = int(ref_uv.shape[0])
-        if stream != caller:
-            stream.wait_stream(caller)
-        with torch.cuda.stream(stream):
-            workspace = self._workspace.get(device)
-            if 1 <= n <= N.FTK_TRACK_TABLE_MAX_SLOTS:
-                words = -(-N.epipolar_workspace_bytes(n, k) // 8)
-                if workspace is None or workspace.numel() < words:  # (the old block, if any, goes back to torch's allocator in stream order)
-                    workspace = self._workspace[device] = torch.empty(words + words // 4, dtype=torch.int64, device=device)
-            out = EpipolarResult(torch.empty((3, 3), dtype=torch.float32, device=device), torch.empty(1, dtype=torch.int32, device=device),
-                                 torch.empty(1, dtype=torch.int32, device=device))
-            if return_hypotheses:
-                out.counts = torch.empty(k, dtype=torch.int32, device=device)
-                out.models = torch.empty((k, 9), dtype=torch.float32, device=device)
-            args = epipolar_ransac_args(ctx, ref_uv, cur_uv, status, (rows, cols), self.threshold, k, seed, workspace, out.best, out.n_inliers, out.F,
-                                        out.counts, out.models, stream)
-            rc = N.lib().ftk_epipolar_ransac_device(*args)
-            if rc != 0:
-                N.check(rc, ctx.handle)
-        if stream != caller:
-            caller.wait_stream(stream)
+    def _workspace_bytes(self, n, k):
+        return N.epipolar_workspace_bytes(n, k)
+
+    def _result(self, torch, device, k, return_hypotheses):
+        out = EpipolarResult(torch.empty((3, 3), dtype=torch.float32, device=device), torch.empty(1, dtype=torch.int32, device=device),
+                             torch.empty(1, dtype=torch.int32, device=device))
+        if return_hypotheses:
+            out.counts = torch.empty(k, dtype=torch.int32, device=device)
+            out.models = torch.empty((k, 9), dtype=torch.float32, device=device)
         return out
+
+    def _args(self, ctx, ref_uv, cur_uv, status, image_size, k, seed, workspace, out, stream):
+        return epipolar_ransac_args(ctx, ref_uv, cur_uv, status, image_size, self.threshold, k, seed, workspace, out.best, out.n_inliers, out.F,
+                                    out.counts, out.models, stream)

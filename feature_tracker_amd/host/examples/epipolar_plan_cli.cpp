@@ -1,4 +1,4 @@
-// epipolar_plan_cli — prints the launch plan and workspace layout of two-view outlier rejection (csrc/epipolar_plan.h) without a device.
+// epipolar_plan_cli — prints the launch plan and workspace layout of two-view outlier rejection (csrc/two_view_plan.h, with one slot) without a device.
 // One case per line on stdin:
 //   n hypotheses image_rows image_cols
 // one line of key=value pairs per case on stdout.  tests/test_epipolar_args_cpu.py drives it.
@@ -7,7 +7,7 @@
 #include <sstream>
 #include <string>
 
-#include "epipolar_plan.h"
+#include "two_view_plan.h"
 
 int main() {
     std::string text;
@@ -17,11 +17,12 @@ int main() {
         for (long long &e : v) {
             line >> e;
         }
-        ftk::EpipolarPlanInput in{};
+        ftk::TwoViewPlanInput in{};
         in.n = (int32_t)v[0], in.hypotheses = (int32_t)v[1], in.image_rows = (int32_t)v[2], in.image_cols = (int32_t)v[3];
-        const ftk::EpipolarPlan p = ftk::epipolar_plan(in);
-        printf("refused=%s", ftk::epipolar_refusal_name(p.refused));
-        if (p.refused == ftk::EpipolarRefusal::None) {
+        in.slots = 1, in.mode = ftk::kTwoViewFundamental;
+        const ftk::TwoViewPlan p = ftk::two_view_plan(in);
+        printf("refused=%s", ftk::two_view_refusal_name(p.refused));
+        if (p.refused == ftk::TwoViewRefusal::None) {
             printf(" scan_block=%d scan_per_thread=%d scan_lds=%zu hyp_block=%d hyp_blocks=%u hyp_lds=%zu score_tile=%d score_group=%d score_tiles=%u"
                    " score_groups=%u score_lds=%zu select_per_thread=%d off_points=%zu off_list=%zu off_counts=%zu off_models=%zu off_valid=%zu bytes=%zu",
                    ftk::kEpipolarScanBlock, p.scan_per_thread, p.scan_lds, ftk::kEpipolarHypBlock, p.hyp_blocks, p.hyp_lds, ftk::kEpipolarScoreTile,

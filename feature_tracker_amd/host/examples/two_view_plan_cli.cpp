@@ -1,5 +1,5 @@
 // two_view_plan_cli — prints the launch plan and workspace layout of two-view outlier rejection with a choice of model
-// (csrc/two_view_plan.h) without a device.  One case per line on stdin:
+// (csrc/two_view_plan.h, with two slots) without a device.  One case per line on stdin:
 //   n hypotheses image_rows image_cols mode prefer_permille
 // one line of key=value pairs per case on stdout.  tests/test_two_view_args_cpu.py drives it.
 #include <cstdio>
@@ -19,7 +19,7 @@ int main() {
         }
         ftk::TwoViewPlanInput in{};
         in.n = (int32_t)v[0], in.hypotheses = (int32_t)v[1], in.image_rows = (int32_t)v[2], in.image_cols = (int32_t)v[3];
-        in.mode = (int32_t)v[4], in.prefer_permille = (int32_t)v[5];
+        in.slots = 2, in.mode = (int32_t)v[4], in.prefer_permille = (int32_t)v[5];
         const ftk::TwoViewPlan p = ftk::two_view_plan(in);
         printf("refused=%s", ftk::two_view_refusal_name(p.refused));
         if (p.refused == ftk::TwoViewRefusal::None) {

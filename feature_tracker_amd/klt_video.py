@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _native as N
 from ._device_epipolar import SEED_ARG, check_sizes, epipolar_ransac_args
-from ._device_two_view import SEED_ARG as TWO_VIEW_SEED_ARG, check_mode, prefer_to_permille, two_view_ransac_args
+from ._device_two_view import check_mode, prefer_to_permille, two_view_ransac_args
 from ._device_klt_video import harris_survivor_bound, track_table_fill_args, track_table_retire_args
 from .tracker import OUTSIDE, ImagePyramid, OpticalFlow
 
@@ -211,19 +211,24 @@ class KltVideoTracker:
         # the tracker calls' results (forward, backward): separate from the table, which retire moves on
         self._uv = [torch.zeros((n, 2), dtype=torch.float32, device=device) for _ in range(2)]
         self._st = [torch.zeros(n, dtype=torch.uint8, device=device) for _ in range(2)]
-        if self.epipolar_threshold is not None and self.epipolar_model != "fundamental":
-            self._epipolar_ws = torch.empty(-(-N.two_view_workspace_bytes(n, self.epipolar_hypotheses, self._epipolar_mode) // 8), dtype=torch.int64,
-                                            device=device)
+        if self.epipolar_threshold is not None:
+            # the model decides, once: the number of slots of the outputs, the args builder, the entry, and what follows the seed in its arguments
+            two = self.epipolar_model != "fundamental"  # the homography, or the choice between the two
+            slots = 2 if two else 1
+            bytes_ = N.two_view_workspace_bytes(n, self.epipolar_hypotheses, self._epipolar_mode) if two else N.epipolar_workspace_bytes(n, self.epipolar_hypotheses)
+            self._epipolar_ws = torch.empty(-(-bytes_ // 8), dtype=torch.int64, device=device)
             self.epipolar_F = torch.zeros((3, 3), dtype=torch.float32, device=device)
-            self.epipolar_H = torch.zeros((3, 3), dtype=torch.float32, device=device)
-            self.epipolar_n_inliers = torch.zeros(2, dtype=torch.int32, device=device)
-            self.epipolar_best = torch.full((2,), -1, dtype=torch.int32, device=device)
-            self.epipolar_model_chosen = torch.full((1,), -1, dtype=torch.int32, device=device)
-        elif self.epipolar_threshold is not None:
-            self._epipolar_ws = torch.empty(-(-N.epipolar_workspace_bytes(n, self.epipolar_hypotheses) // 8), dtype=torch.int64, device=device)
-            self.epipolar_F = torch.zeros((3, 3), dtype=torch.float32, device=device)
-            self.epipolar_n_inliers = torch.zeros(1, dtype=torch.int32, device=device)
-            self.epipolar_best = torch.full((1,), -1, dtype=torch.int32, device=device)
+            self.epipolar_n_inliers = torch.zeros(slots, dtype=torch.int32, device=device)
+            self.epipolar_best = torch.full((slots,), -1, dtype=torch.int32, device=device)
+            if two:
+                self.epipolar_H = torch.zeros((3, 3), dtype=torch.float32, device=device)
+                self.epipolar_model_chosen = torch.full((1,), -1, dtype=torch.int32, device=device)
+                self._epipolar_call = ("two_view", two_view_ransac_args, "ftk_two_view_ransac_device", (
+                    self._epipolar_mode, self._epipolar_permille, self._epipolar_ws, self.epipolar_model_chosen, self.epipolar_best, self.epipolar_n_inliers,
+                    self.epipolar_F, self.epipolar_H))
+            else:
+                self._epipolar_call = ("epipolar", epipolar_ransac_args, "ftk_epipolar_ransac_device", (
+                    self._epipolar_ws, self.epipolar_best, self.epipolar_n_inliers, self.epipolar_F))
         self._empty_table()
 
     def _empty_table(self):
@@ -265,25 +270,13 @@ class KltVideoTracker:
     def _reject_outliers(self):
         """The forward results against the best fundamental matrix (or the chosen model): ``_st[0]`` of a tracked slot that disagrees becomes LARGE_RESIDUAL."""
         ctx = self._ctx
-        if self.epipolar_model != "fundamental":  # the homography, or the choice between the two (DESIGN.md 5.21)
-            args = self._bound.get("two_view")
-            if args is None:
-                args = self._bound["two_view"] = list(two_view_ransac_args(
-                    ctx, self.points, self._uv[0], self._st[0], self._shape, self.epipolar_threshold, self.epipolar_hypotheses, 0, self._epipolar_mode,
-                    self._epipolar_permille, self._epipolar_ws, self.epipolar_model_chosen, self.epipolar_best, self.epipolar_n_inliers, self.epipolar_F,
-                    self.epipolar_H, stream=ctx.stream))
-            args[TWO_VIEW_SEED_ARG] = C.c_uint32((self.epipolar_seed + self._frames) & 0xFFFFFFFF)
-            rc = N.lib().ftk_two_view_ransac_device(*args)
-            if rc != 0:
-                N.check(rc, ctx.handle)
-            return
-        args = self._bound.get("epipolar")
+        key, marshal, entry, rest = self._epipolar_call
+        args = self._bound.get(key)
         if args is None:
-            args = self._bound["epipolar"] = list(epipolar_ransac_args(
-                ctx, self.points, self._uv[0], self._st[0], self._shape, self.epipolar_threshold, self.epipolar_hypotheses, 0, self._epipolar_ws,
-                self.epipolar_best, self.epipolar_n_inliers, self.epipolar_F, stream=ctx.stream))
+            args = self._bound[key] = list(marshal(ctx, self.points, self._uv[0], self._st[0], self._shape, self.epipolar_threshold, self.epipolar_hypotheses, 0,
+                                                   *rest, stream=ctx.stream))
         args[SEED_ARG] = C.c_uint32((self.epipolar_seed + self._frames) & 0xFFFFFFFF)
-        rc = N.lib().ftk_epipolar_ransac_device(*args)
+        rc = getattr(N.lib(), entry)(*args)
         if rc != 0:
             N.check(rc, ctx.handle)
 

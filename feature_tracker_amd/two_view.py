@@ -12,6 +12,7 @@ from typing import Optional
 from . import _native as N
 from ._device_epipolar import check_sizes
 from ._device_two_view import check_mode, prefer_to_permille, two_view_ransac_args
+from .epipolar import ransac_filter
 
 
 class TwoViewResult:
@@ -56,46 +57,22 @@ class TwoViewRansac:
     def filter(self, ref_uv, cur_uv, status, image_size, seed: Optional[int] = None, return_hypotheses: bool = False) -> TwoViewResult:
         """One pass of outlier rejection; ``seed``: this call's seed instead of the object's; ``return_hypotheses``: also ``counts`` and
         ``models``.  Everything is enqueued; the returned tensors are valid in stream order."""
-        rows, cols, _, k, seed = check_sizes(image_size, self.threshold, self.hypotheses, self.seed if seed is None else seed)
-        from . import device as D
+        return ransac_filter(self, ref_uv, cur_uv, status, image_size, seed, return_hypotheses)
 
-        tensors = (("ref_uv", ref_uv, D._F32, (None, 2)), ("cur_uv", cur_uv, D._F32, (None, 2)), ("status", status, D._U8, (None,)))
-        for name, t, dtypes, shape in tensors:
-            complaint = D._tensor_complaint(name, t, dtypes, shape)
-            if complaint:
-                raise ValueError(complaint)
-        for name, t, _, _ in tensors:
-            if not t.is_cuda:
-                raise ValueError(f"{name} must be a CUDA tensor (got one on {t.device}): there is no CPU fallback")
-        torch = D._torch()
-        ctx = self._ctx
-        if ctx is None:
-            from .raft import _device_context
+    _entry = "ftk_two_view_ransac_device"
 
-            ctx = _device_context(ref_uv)
-        device = ref_uv.device
-        caller = torch.cuda.current_stream(device)
-        stream = getattr(ctx, "stream", None) or caller
-        n = int(ref_uv.shape[0])
-        if stream != caller:
-            stream.wait_stream(caller)
-        with torch.cuda.stream(stream):
-            workspace = self._workspace.get(device)
-            if 1 <= n <= N.FTK_TRACK_TABLE_MAX_SLOTS:
-                words = -(-N.two_view_workspace_bytes(n, k, self.mode) // 8)
-                if workspace is None or workspace.numel() < words:  # (the old block, if any, goes back to torch's allocator in stream order)
-                    workspace = self._workspace[device] = torch.empty(words + words // 4, dtype=torch.int64, device=device)
-            i32 = dict(dtype=torch.int32, device=device)
-            f32 = dict(dtype=torch.float32, device=device)
-            out = TwoViewResult(torch.empty(1, **i32), torch.empty((3, 3), **f32), torch.empty((3, 3), **f32), torch.empty(2, **i32), torch.empty(2, **i32))
-            if return_hypotheses:
-                out.counts = torch.empty((2, k), **i32)
-                out.models = torch.empty((2, k, 9), **f32)
-            args = two_view_ransac_args(ctx, ref_uv, cur_uv, status, (rows, cols), self.threshold, k, seed, self.mode, self.prefer_homography_permille,
-                                        workspace, out.model, out.best, out.n_inliers, out.F, out.H, out.counts, out.models, stream)
-            rc = N.lib().ftk_two_view_ransac_device(*args)
-            if rc != 0:
-                N.check(rc, ctx.handle)
-        if stream != caller:
-            caller.wait_stream(stream)
+    def _workspace_bytes(self, n, k):
+        return N.two_view_workspace_bytes(n, k, self.mode)
+
+    def _result(self, torch, device, k, return_hypotheses):
+        i32 = dict(dtype=torch.int32, device=device)
+        f32 = dict(dtype=torch.float32, device=device)
+        out = TwoViewResult(torch.empty(1, **i32), torch.empty((3, 3), **f32), torch.empty((3, 3), **f32), torch.empty(2, **i32), torch.empty(2, **i32))
+        if return_hypotheses:
+            out.counts = torch.empty((2, k), **i32)
+            out.models = torch.empty((2, k, 9), **f32)
         return out
+
+    def _args(self, ctx, ref_uv, cur_uv, status, image_size, k, seed, workspace, out, stream):
+        return two_view_ransac_args(ctx, ref_uv, cur_uv, status, image_size, self.threshold, k, seed, self.mode, self.prefer_homography_permille,
+                                    workspace, out.model, out.best, out.n_inliers, out.F, out.H, out.counts, out.models, stream)

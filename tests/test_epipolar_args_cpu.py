@@ -124,7 +124,7 @@ def test_nothing_in_the_package_imports_the_restatement():
 
 
 def _plan(n, k, rows, cols):
-    """The plan restated (csrc/epipolar_plan.cpp)."""
+    """The plan restated (csrc/two_view_plan.cpp with one slot)."""
     if n < 1 or k < 1 or not 1 <= rows <= 65536 or not 1 <= cols <= 65536:
         return {"refused": "sizes"}
     if n > 65536:
