@@ -14,44 +14,57 @@ import math
 from . import _native as N
 
 
+def _conv2d(ctx, parts, packed_weights, bias, kernel_size, relu, out_scale, out, stream, *, strided: bool, stride=1, residual=None, normalise=False) -> None:
+    """The checks and the marshalling of both entries; ``strided`` says which of them calls, and so which ABI entry is called."""
+    from . import device as D
+
+    ks, st = int(kernel_size), int(stride)
+    if ks not in N.FTK_CONV2D_KERNEL_SIZES:
+        raise ValueError(f"kernel_size {kernel_size} is not supported: 1, 3 and 7 are")
+    if strided and (st not in N.FTK_CONV2D_STRIDES or ks not in N.FTK_CONV2D_STRIDES[st]):
+        raise ValueError(f"stride {stride} with kernel_size {ks} is not supported: stride 1, and stride 2 with kernel sizes 1 and 3, are")
+    if not math.isfinite(float(out_scale)):
+        raise ValueError(f"out_scale must be finite (got {out_scale})")
+    parts = N.part_list(parts, "the input", N.FTK_CONV2D_MAX_PARTS)
+    dev = D._call_device(ctx, out)
+    D._check("out", out, D._F32, (None, None, None, None), dev)
+    B, Cout, OH, OW = (int(e) for e in out.shape)
+    if min(B, Cout, OH, OW) < 1:
+        raise ValueError(f"out must be a non-empty [B, out_channels, H, W] tensor (got {list(out.shape)})")
+    if Cout > N.FTK_CONV2D_MAX_OUT_CHANNELS:
+        raise ValueError(f"out_channels {Cout} above FTK_CONV2D_MAX_OUT_CHANNELS = {N.FTK_CONV2D_MAX_OUT_CHANNELS}")
+    H, W = OH, OW
+    if strided:  # the input's sizes are parts[0]'s
+        D._check("parts[0]", parts[0], D._F32, (B, None, None, None), dev)
+        H, W = int(parts[0].shape[2]), int(parts[0].shape[3])
+        if (-(-H // st), -(-W // st)) != (OH, OW):
+            raise ValueError(f"out must be [B, out_channels, {-(-H // st)}, {-(-W // st)}] for parts[0] {list(parts[0].shape)} at stride {st} (got "
+                             f"{list(out.shape)})")
+    Cin = N.checked_channels("parts", parts, B, H, W, dev)
+    if Cin > N.FTK_CONV2D_MAX_IN_CHANNELS:
+        raise ValueError(f"in_channels {Cin} above FTK_CONV2D_MAX_IN_CHANNELS = {N.FTK_CONV2D_MAX_IN_CHANNELS}")
+    D._check("packed_weights", packed_weights, D._F32, (N.conv2d_packed_elements(Cout, Cin, ks),), dev)
+    D._check("bias", bias, D._F32, (Cout,), dev)
+    if residual is not None:
+        D._check("residual", residual, D._F32, (B, Cout, OH, OW), dev)
+    s = D._torch().cuda.current_stream(out.device) if stream is None else stream
+    layer = (ctx.handle, C.c_void_p(s.cuda_stream), N.part_array(parts), len(parts), C.c_void_p(packed_weights.data_ptr()), C.c_void_p(bias.data_ptr()), Cout, ks)
+    sizes = (B, H, W, C.c_void_p(out.data_ptr()))
+    if strided:
+        rc = N.lib().ftk_conv2d_strided_device(*layer, st, 1 if relu else 0, float(out_scale), None if residual is None else C.c_void_p(residual.data_ptr()),
+                                               1 if normalise else 0, *sizes)
+    else:
+        rc = N.lib().ftk_conv2d_device(*layer, 1 if relu else 0, float(out_scale), *sizes)
+    N.check(rc, ctx.handle)
+
+
 def conv2d_device(ctx, parts, packed_weights, bias, kernel_size: int, relu: bool, out_scale: float, out, stream=None) -> None:
     """One layer of update_block.py (a Conv2d of kernel size 1, 3 or 7, stride 1, zero padding ``kernel_size // 2``; with ``relu`` the
     ReLU after it; then ``out_scale *``, 1.0 everywhere but the mask head's last layer) in one launch on ``stream`` (a torch.cuda.Stream;
     default: torch's current stream).  ``parts``: 1 .. 3 contiguous float32 CUDA tensors [B, C_i, H, W] read in place as their channel
     concatenation; ``out``: [B, out_channels, H, W]; ``bias``: [out_channels]; ``packed_weights``: the flat float32 tensor in the layout
     of include/ftk.h.  No synchronisation, no allocation: capturable.  Every argument is checked before the device is touched."""
-    from . import device as D
-
-    ks = int(kernel_size)
-    if ks not in N.FTK_CONV2D_KERNEL_SIZES:
-        raise ValueError(f"kernel_size {kernel_size} is not supported: 1, 3 and 7 are")
-    if not math.isfinite(float(out_scale)):
-        raise ValueError(f"out_scale must be finite (got {out_scale})")
-    parts = list(parts)
-    if not 1 <= len(parts) <= N.FTK_CONV2D_MAX_PARTS:
-        raise ValueError(f"the input must be 1 .. {N.FTK_CONV2D_MAX_PARTS} tensors (got {len(parts)})")
-    dev = D._call_device(ctx, out)
-    D._check("out", out, D._F32, (None, None, None, None), dev)
-    B, Cout, H, W = (int(e) for e in out.shape)
-    if min(B, Cout, H, W) < 1:
-        raise ValueError(f"out must be a non-empty [B, out_channels, H, W] tensor (got {list(out.shape)})")
-    if Cout > N.FTK_CONV2D_MAX_OUT_CHANNELS:
-        raise ValueError(f"out_channels {Cout} above FTK_CONV2D_MAX_OUT_CHANNELS = {N.FTK_CONV2D_MAX_OUT_CHANNELS}")
-    Cin = 0
-    for i, part in enumerate(parts):
-        D._check(f"parts[{i}]", part, D._F32, (B, None, H, W), dev)
-        if int(part.shape[1]) < 1:
-            raise ValueError(f"parts[{i}] must have at least one channel (got {list(part.shape)})")
-        Cin += int(part.shape[1])
-    if Cin > N.FTK_CONV2D_MAX_IN_CHANNELS:
-        raise ValueError(f"in_channels {Cin} above FTK_CONV2D_MAX_IN_CHANNELS = {N.FTK_CONV2D_MAX_IN_CHANNELS}")
-    D._check("packed_weights", packed_weights, D._F32, (N.conv2d_packed_elements(Cout, Cin, ks),), dev)
-    D._check("bias", bias, D._F32, (Cout,), dev)
-    s = D._torch().cuda.current_stream(out.device) if stream is None else stream
-    segs = (N.GruPart * len(parts))(*[N.GruPart(C.c_void_p(p.data_ptr()), int(p.shape[1])) for p in parts])
-    rc = N.lib().ftk_conv2d_device(ctx.handle, C.c_void_p(s.cuda_stream), segs, len(parts), C.c_void_p(packed_weights.data_ptr()),
-                                   C.c_void_p(bias.data_ptr()), Cout, ks, 1 if relu else 0, float(out_scale), B, H, W, C.c_void_p(out.data_ptr()))
-    N.check(rc, ctx.handle)
+    _conv2d(ctx, parts, packed_weights, bias, kernel_size, relu, out_scale, out, stream, strided=False)
 
 
 def conv2d_strided_device(ctx, parts, packed_weights, bias, kernel_size: int, stride: int, relu: bool, out_scale: float, residual, normalise: bool, out,
@@ -61,46 +74,4 @@ def conv2d_strided_device(ctx, parts, packed_weights, bias, kernel_size: int, st
     applied to the in-image input values.  ``parts``: [B, C_i, H, W]; ``out``: [B, out_channels, ceil(H / stride), ceil(W / stride)].  The
     weights are BatchNorm-folded by the caller and packed as for ``conv2d_device``.  One launch, no synchronisation, no allocation:
     capturable.  Every argument is checked before the device is touched."""
-    from . import device as D
-
-    ks, st = int(kernel_size), int(stride)
-    if ks not in N.FTK_CONV2D_KERNEL_SIZES:
-        raise ValueError(f"kernel_size {kernel_size} is not supported: 1, 3 and 7 are")
-    if st not in N.FTK_CONV2D_STRIDES or ks not in N.FTK_CONV2D_STRIDES[st]:
-        raise ValueError(f"stride {stride} with kernel_size {ks} is not supported: stride 1, and stride 2 with kernel sizes 1 and 3, are")
-    if not math.isfinite(float(out_scale)):
-        raise ValueError(f"out_scale must be finite (got {out_scale})")
-    parts = list(parts)
-    if not 1 <= len(parts) <= N.FTK_CONV2D_MAX_PARTS:
-        raise ValueError(f"the input must be 1 .. {N.FTK_CONV2D_MAX_PARTS} tensors (got {len(parts)})")
-    dev = D._call_device(ctx, out)
-    D._check("out", out, D._F32, (None, None, None, None), dev)
-    B, Cout, OH, OW = (int(e) for e in out.shape)
-    if min(B, Cout, OH, OW) < 1:
-        raise ValueError(f"out must be a non-empty [B, out_channels, H, W] tensor (got {list(out.shape)})")
-    if Cout > N.FTK_CONV2D_MAX_OUT_CHANNELS:
-        raise ValueError(f"out_channels {Cout} above FTK_CONV2D_MAX_OUT_CHANNELS = {N.FTK_CONV2D_MAX_OUT_CHANNELS}")
-    D._check("parts[0]", parts[0], D._F32, (B, None, None, None), dev)
-    H, W = int(parts[0].shape[2]), int(parts[0].shape[3])
-    if (-(-H // st), -(-W // st)) != (OH, OW):
-        raise ValueError(f"out must be [B, out_channels, {-(-H // st)}, {-(-W // st)}] for parts[0] {list(parts[0].shape)} at stride {st} (got "
-                         f"{list(out.shape)})")
-    Cin = 0
-    for i, part in enumerate(parts):
-        D._check(f"parts[{i}]", part, D._F32, (B, None, H, W), dev)
-        if int(part.shape[1]) < 1:
-            raise ValueError(f"parts[{i}] must have at least one channel (got {list(part.shape)})")
-        Cin += int(part.shape[1])
-    if Cin > N.FTK_CONV2D_MAX_IN_CHANNELS:
-        raise ValueError(f"in_channels {Cin} above FTK_CONV2D_MAX_IN_CHANNELS = {N.FTK_CONV2D_MAX_IN_CHANNELS}")
-    D._check("packed_weights", packed_weights, D._F32, (N.conv2d_packed_elements(Cout, Cin, ks),), dev)
-    D._check("bias", bias, D._F32, (Cout,), dev)
-    if residual is not None:
-        D._check("residual", residual, D._F32, (B, Cout, OH, OW), dev)
-    s = D._torch().cuda.current_stream(out.device) if stream is None else stream
-    segs = (N.GruPart * len(parts))(*[N.GruPart(C.c_void_p(p.data_ptr()), int(p.shape[1])) for p in parts])
-    rc = N.lib().ftk_conv2d_strided_device(ctx.handle, C.c_void_p(s.cuda_stream), segs, len(parts), C.c_void_p(packed_weights.data_ptr()),
-                                           C.c_void_p(bias.data_ptr()), Cout, ks, st, 1 if relu else 0, float(out_scale),
-                                           None if residual is None else C.c_void_p(residual.data_ptr()), 1 if normalise else 0, B, H, W,
-                                           C.c_void_p(out.data_ptr()))
-    N.check(rc, ctx.handle)
+    _conv2d(ctx, parts, packed_weights, bias, kernel_size, relu, out_scale, out, stream, strided=True, stride=stride, residual=residual, normalise=normalise)

@@ -26,9 +26,7 @@ def sep_conv_gru_device(ctx, x_parts, h, packed, kernel_size: int, z, rh, mid, o
     ks = int(kernel_size)
     if ks not in N.FTK_SEP_CONV_GRU_KERNEL_SIZES:
         raise ValueError(f"kernel_size {kernel_size} is not supported: 3 and 5 are")
-    x_parts = list(x_parts)
-    if not 1 <= len(x_parts) <= N.FTK_SEP_CONV_GRU_MAX_PARTS:
-        raise ValueError(f"x must be 1 .. {N.FTK_SEP_CONV_GRU_MAX_PARTS} tensors (got {len(x_parts)})")
+    x_parts = N.part_list(x_parts, "x", N.FTK_SEP_CONV_GRU_MAX_PARTS)
     dev = D._call_device(ctx, h)
     D._check("h", h, D._F32, (None, None, None, None), dev)
     B, Ch, H, W = (int(e) for e in h.shape)
@@ -36,13 +34,7 @@ def sep_conv_gru_device(ctx, x_parts, h, packed, kernel_size: int, z, rh, mid, o
         raise ValueError(f"h must be a non-empty [B, h_channels, H, W] tensor (got {list(h.shape)})")
     if Ch > N.FTK_SEP_CONV_GRU_MAX_H_CHANNELS:
         raise ValueError(f"h_channels {Ch} above FTK_SEP_CONV_GRU_MAX_H_CHANNELS = {N.FTK_SEP_CONV_GRU_MAX_H_CHANNELS}")
-    Cx = 0
-    for i, part in enumerate(x_parts):
-        D._check(f"x[{i}]", part, D._F32, (B, None, H, W), dev)
-        if int(part.shape[1]) < 1:
-            raise ValueError(f"x[{i}] must have at least one channel (got {list(part.shape)})")
-        Cx += int(part.shape[1])
-    Cin = Cx + Ch
+    Cin = N.checked_channels("x", x_parts, B, H, W, dev) + Ch
     if Cin > N.FTK_SEP_CONV_GRU_MAX_IN_CHANNELS:
         raise ValueError(f"x_channels + h_channels = {Cin} above FTK_SEP_CONV_GRU_MAX_IN_CHANNELS = {N.FTK_SEP_CONV_GRU_MAX_IN_CHANNELS}")
     for name, t in (("z", z), ("rh", rh), ("mid", mid), ("out", out)):
@@ -54,7 +46,7 @@ def sep_conv_gru_device(ctx, x_parts, h, packed, kernel_size: int, z, rh, mid, o
         want = rows if "bias" in key else N.sep_conv_gru_packed_elements(rows, Cin, ks)
         D._check(f"packed[{key!r}]", packed[key], D._F32, (want,), dev)
     s = D._torch().cuda.current_stream(h.device) if stream is None else stream
-    parts = (N.GruPart * len(x_parts))(*[N.GruPart(C.c_void_p(p.data_ptr()), int(p.shape[1])) for p in x_parts])
+    parts = N.part_array(x_parts)
     ptr = {key: C.c_void_p(packed[key].data_ptr()) for key in PACKED_KEYS}
     h_p, z_p, rh_p, mid_p, out_p = (C.c_void_p(t.data_ptr()) for t in (h, z, rh, mid, out))
     lib, sh = N.lib(), C.c_void_p(s.cuda_stream)

@@ -360,10 +360,14 @@ def match_assignment_workspace_bytes(rows0: int, rows1: int, dim: int, with_weig
     return own + (up16(4 * (m + n) * d) + up16(4 * (m + n)) + up16(8 * m) + up16(8 * n) if with_weights else 0)
 
 
+def _gemm_k_steps(in_channels: int, chunk: int, taps: int) -> int:
+    """MFMA k-steps of a packed weight matrix (include/ftk.h): whole chunks of ``chunk`` input channels of ``taps`` k each, two k per step."""
+    return -(-int(in_channels) // chunk) * (chunk * taps // 2)
+
+
 def sep_conv_gru_k_steps(in_channels: int, kernel_size: int) -> int:
-    """MFMA k-steps of a packed SepConvGru weight matrix (include/ftk.h): whole chunks of FTK_SEP_CONV_GRU_CHUNK input channels, two k per step."""
-    chunks = -(-int(in_channels) // FTK_SEP_CONV_GRU_CHUNK)
-    return chunks * (FTK_SEP_CONV_GRU_CHUNK * int(kernel_size) // 2)
+    """MFMA k-steps of a packed SepConvGru weight matrix: chunks of FTK_SEP_CONV_GRU_CHUNK input channels, ``kernel_size`` taps."""
+    return _gemm_k_steps(in_channels, FTK_SEP_CONV_GRU_CHUNK, int(kernel_size))
 
 
 def sep_conv_gru_packed_elements(out_channels: int, in_channels: int, kernel_size: int) -> int:
@@ -372,11 +376,36 @@ def sep_conv_gru_packed_elements(out_channels: int, in_channels: int, kernel_siz
 
 
 def conv2d_k_steps(in_channels: int, kernel_size: int) -> int:
-    """MFMA k-steps of a packed conv2d weight matrix (include/ftk.h): whole chunks of FTK_CONV2D_CHUNK[kernel_size] input channels, two k per step."""
-    chunk = FTK_CONV2D_CHUNK[int(kernel_size)]
-    return -(-int(in_channels) // chunk) * (chunk * int(kernel_size) ** 2 // 2)
+    """MFMA k-steps of a packed conv2d weight matrix: chunks of FTK_CONV2D_CHUNK[kernel_size] input channels, ``kernel_size`` squared taps."""
+    return _gemm_k_steps(in_channels, FTK_CONV2D_CHUNK[int(kernel_size)], int(kernel_size) ** 2)
 
 
 def conv2d_packed_elements(out_channels: int, in_channels: int, kernel_size: int) -> int:
     """Floats of the packed matrix, the value ftk_conv2d_packed_elements returns (pure Python: argument checks need no library)."""
     return -(-int(out_channels) // 32) * conv2d_k_steps(in_channels, kernel_size) * 64
+
+
+def part_list(parts, noun: str, limit: int) -> list:
+    """``parts`` as a list of 1 .. ``limit`` tensors; ``noun`` is what the refusal calls them.  Shared by _device_sep_conv_gru.py and _device_raft_conv.py."""
+    parts = list(parts)
+    if not 1 <= len(parts) <= limit:
+        raise ValueError(f"{noun} must be 1 .. {limit} tensors (got {len(parts)})")
+    return parts
+
+
+def checked_channels(label: str, parts, B: int, H: int, W: int, dev) -> int:
+    """``device._check`` of every part as a contiguous float32 [B, C_i >= 1, H, W] tensor on ``dev``; the sum of the C_i."""
+    from . import device as D
+
+    channels = 0
+    for i, part in enumerate(parts):
+        D._check(f"{label}[{i}]", part, D._F32, (B, None, H, W), dev)
+        if int(part.shape[1]) < 1:
+            raise ValueError(f"{label}[{i}] must have at least one channel (got {list(part.shape)})")
+        channels += int(part.shape[1])
+    return channels
+
+
+def part_array(parts):
+    """The ftk_gru_part array of parts that passed ``checked_channels``."""
+    return (GruPart * len(parts))(*[GruPart(C.c_void_p(p.data_ptr()), int(p.shape[1])) for p in parts])

@@ -1,7 +1,9 @@
 // raft_conv_kernels.hip — the stock layers of RAFT's UpdateBlock (src/nn_optical_flow_tracker/raft/update_block.py:4-67: the motion
 // encoder's five convolutions, the flow head's two, the mask head's two) on gfx950: one kernel family, conv2d_kernel<KS, RELU> for
-// KS in {1, 3, 7}, stride 1, zero padding KS / 2, in the style of raft_gru_kernels.hip: an implicit GEMM on the f32-input matrix cores
-// (v_mfma_f32_32x32x2_f32) with the bias in the accumulators and ReLU and an output scale in the epilogue.
+// KS in {1, 3, 7}, stride 1, zero padding KS / 2: an implicit GEMM on the f32-input matrix cores (v_mfma_f32_32x32x2_f32) with the
+// bias in the accumulators and ReLU and an output scale in the epilogue.  It is the algorithm of raft_gemm_core.h, which
+// states the numerical contract, written out in the kernel: with this body behind a device function the compiler's prologue changes and
+// the 256 -> 192 3 x 3 layer measured 2 % slower, so it stays here until that is solved.
 // No concatenation exists in memory: the input is a by-value list of {pointer, channels} segments read in place.
 //
 // The GEMM: D[co][p] = bias[co] + sum_k W[co][k] in[k][p], k = (c * KS + ty) * KS + tx (torch's own weight order, c over the
@@ -40,7 +42,7 @@ namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-constexpr int kThreads = 64 * kConvWaves;
+constexpr int kThreads = 64 * kGemmWaves;
 
 inline __device__ const ConvParams &conv_base(const ConvParams &p) { return p; }
 inline __device__ const ConvParams &conv_base(const ConvStridedParams &p) { return p.base; }
@@ -55,16 +57,16 @@ __global__ __launch_bounds__(kThreads) void conv2d_kernel(P launch, int wm, int 
     constexpr int STEPS = conv_steps(KS);  // k-steps of a chunk
     constexpr int ROW = S == 1 ? conv_row(KS) : conv_s2_row(KS);  // LDS floats of a staged row
     constexpr int PLANE = conv_s2_plane(KS);                      // stride 2: floats of the even and of the odd plane of a row
-    constexpr int PITCH_MAX = S == 1 ? conv_pitch(KS, kConvWaves) : conv_s2_pitch(KS, kConvWaves);
+    constexpr int PITCH_MAX = S == 1 ? conv_pitch(KS, kGemmWaves) : conv_s2_pitch(KS, kGemmWaves);
     // Staging: a chunk of at least 4 channels gives each wave CC / 4 whole strips; a smaller one (KS 7: 2) gives each strip to 4 / CC waves.
-    constexpr int WPC = CC < kConvWaves ? kConvWaves / CC : 1;  // waves of one strip
-    constexpr int CPW = CC < kConvWaves ? 1 : CC / kConvWaves;  // strips of one wave
+    constexpr int WPC = CC < kGemmWaves ? kGemmWaves / CC : 1;  // waves of one strip
+    constexpr int CPW = CC < kGemmWaves ? 1 : CC / kGemmWaves;  // strips of one wave
     constexpr int ITERS = (PITCH_MAX + 64 * WPC - 1) / (64 * WPC);
     static_assert(2 * STEPS == CC * KS * KS, "a chunk is whole k-steps");
-    static_assert(CC % kConvWaves == 0 || kConvWaves % CC == 0, "a chunk splits over the waves");
+    static_assert(CC % kGemmWaves == 0 || kGemmWaves % CC == 0, "a chunk splits over the waves");
     __shared__ float s_in[CC * PITCH_MAX];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wn = kConvWaves / wm;
+    const int wn = kGemmWaves / wm;
     const int wmi = wave % wm, wni = wave / wm;
     const int H = prm.H, W = prm.W, Cin = prm.in_channels, Cout = prm.out_channels;
     const int64_t HW = (int64_t)H * W;
@@ -80,7 +82,7 @@ __global__ __launch_bounds__(kThreads) void conv2d_kernel(P launch, int wm, int 
     g /= tiles_x;
     const int ty = (int)(g % tiles_y);
     const int64_t b = g / tiles_y;
-    const int64_t x0 = (int64_t)tx * kConvTile;
+    const int64_t x0 = (int64_t)tx * kGemmTile;
     const int64_t y0 = (int64_t)ty * wn;
     const int pitch = (S == 1 ? wn + 2 * PAD : conv_s2_rows(KS, wn)) * ROW;
     const int m_tile = blockIdx.y * wm + wmi;
@@ -88,8 +90,8 @@ __global__ __launch_bounds__(kThreads) void conv2d_kernel(P launch, int wm, int 
     const int j = lane & 31, kh = lane >> 5;
 
     // this wave's strips are those of channels sch + 4 i of the chunk, its positions in a strip lane + 64 (sub + WPC it)
-    const int sch = CC < kConvWaves ? wave % CC : wave;
-    const int sub = CC < kConvWaves ? wave / CC : 0;
+    const int sch = CC < kGemmWaves ? wave % CC : wave;
+    const int sub = CC < kGemmWaves ? wave / CC : 0;
     // where this lane's staged positions lie in a channel plane (-1: outside the image or the strip: +0)
     int64_t soff[ITERS];
 #pragma unroll
@@ -107,7 +109,7 @@ __global__ __launch_bounds__(kThreads) void conv2d_kernel(P launch, int wm, int 
     auto fetch = [&](int chunk) {
 #pragma unroll
         for (int i = 0; i < CPW; ++i) {
-            int c = chunk * CC + sch + kConvWaves * i;
+            int c = chunk * CC + sch + kGemmWaves * i;
             const float *plane = nullptr;
 #pragma unroll
             for (int s = 0; s < 3; ++s) {
@@ -137,7 +139,7 @@ __global__ __launch_bounds__(kThreads) void conv2d_kernel(P launch, int wm, int 
             for (int it = 0; it < ITERS; ++it) {
                 const int pos = lane + 64 * (sub + WPC * it);
                 if (pos < pitch) {
-                    s_in[(sch + kConvWaves * i) * pitch + pos] = st[i][it];
+                    s_in[(sch + kGemmWaves * i) * pitch + pos] = st[i][it];
                 }
             }
         }
@@ -157,7 +159,7 @@ __global__ __launch_bounds__(kThreads) void conv2d_kernel(P launch, int wm, int 
     f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int co = m_tile * kConvTile + (r & 3) + 8 * (r >> 2) + 4 * kh;
+        const int co = m_tile * kGemmTile + (r & 3) + 8 * (r >> 2) + 4 * kh;
         acc[r] = (active && co < Cout) ? prm.bias[co] : 0.0f;
     }
     const int lane_base = ((S == 2 && KS > 1) ? 2 * wni : wni) * ROW + j;
@@ -206,7 +208,7 @@ __global__ __launch_bounds__(kThreads) void conv2d_kernel(P launch, int wm, int 
     const int64_t pix = py * OW + px;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int co = m_tile * kConvTile + (r & 3) + 8 * (r >> 2) + 4 * kh;
+        const int co = m_tile * kGemmTile + (r & 3) + 8 * (r >> 2) + 4 * kh;
         if (co >= Cout) {
             continue;
         }
@@ -256,7 +258,7 @@ hipError_t launch_strided(const ConvPlan &plan, const ConvStridedParams &p, int 
 }  // namespace
 
 hipError_t raft_conv_strided_launch(const ConvPlan &plan, const ConvStridedParams &p, int kernel_size, int relu, hipStream_t stream) {
-    if (plan.refused != ConvRefusal::None || plan.block.x != (unsigned)kThreads || plan.wm * plan.wn != kConvWaves) {
+    if (plan.refused != ConvRefusal::None || plan.block.x != (unsigned)kThreads || plan.wm * plan.wn != kGemmWaves) {
         return hipErrorInvalidValue;
     }
     if (plan.stride == 1 && p.residual == nullptr && !p.normalise) {
@@ -273,7 +275,7 @@ hipError_t raft_conv_strided_launch(const ConvPlan &plan, const ConvStridedParam
 }
 
 hipError_t raft_conv_launch(const ConvPlan &plan, const ConvParams &p, int kernel_size, int relu, hipStream_t stream) {
-    if (plan.refused != ConvRefusal::None || plan.block.x != (unsigned)kThreads || plan.wm * plan.wn != kConvWaves || plan.stride != 1) {
+    if (plan.refused != ConvRefusal::None || plan.block.x != (unsigned)kThreads || plan.wm * plan.wn != kGemmWaves || plan.stride != 1) {
         return hipErrorInvalidValue;
     }
     switch (kernel_size) {

@@ -16,9 +16,7 @@ const char *gru_refusal_name(GruRefusal r) {
 }
 
 int64_t sep_conv_gru_packed_elements(int32_t out_channels, int32_t in_channels, int32_t kernel_size) {
-    const int64_t m_tiles = ((int64_t)out_channels + kGruTile - 1) / kGruTile;
-    const int64_t chunks = ((int64_t)in_channels + kGruChunk - 1) / kGruChunk;
-    return m_tiles * chunks * (kGruChunk * kernel_size / 2) * 64;
+    return gemm_packed_elements(out_channels, in_channels, kGruChunk, kGruChunk * kernel_size / 2);
 }
 
 SepConvGruPlan sep_conv_gru_plan(const SepConvGruPlanInput &in) {
@@ -38,29 +36,25 @@ SepConvGruPlan sep_conv_gru_plan(const SepConvGruPlanInput &in) {
     }
     const int pad = in.kernel_size / 2;
     p.out_channels = in.gates ? 2 * in.h_channels : in.h_channels;
-    p.m_tiles = (p.out_channels + kGruTile - 1) / kGruTile;
-    // Waves share the staged input: as many of them along the output channels as there are tiles (3 tiles: 4 waves, one idle in the
-    // matrix loop), the rest along the pixels.
-    p.wm = p.m_tiles >= 3 ? 4 : p.m_tiles;
-    p.wn = kGruWaves / p.wm;
-    p.m_groups = (p.m_tiles + p.wm - 1) / p.wm;
-    p.tile_w = in.vertical ? kGruTile : kGruTile * p.wn;
+    const GemmWaveSplit split = gemm_wave_split(p.out_channels);
+    p.m_tiles = split.m_tiles, p.wm = split.wm, p.wn = split.wn, p.m_groups = split.m_groups;
+    p.tile_w = in.vertical ? kGemmTile : kGemmTile * p.wn;
     p.tile_h = in.vertical ? p.wn : 1;
-    p.tiles_x = (in.W + p.tile_w - 1) / p.tile_w;
-    p.tiles_y = (in.H + p.tile_h - 1) / p.tile_h;
-    p.chunks = (in.in_channels + kGruChunk - 1) / kGruChunk;
+    p.tiles_x = gemm_tiles(in.W, p.tile_w);
+    p.tiles_y = gemm_tiles(in.H, p.tile_h);
+    p.chunks = gemm_chunks(in.in_channels, kGruChunk);
     p.steps_per_chunk = kGruChunk * in.kernel_size / 2;
     p.k_steps = p.chunks * p.steps_per_chunk;
-    p.pitch = in.vertical ? (p.wn + 2 * pad) * kGruTile : kGruTile * p.wn + 2 * pad;
+    p.pitch = in.vertical ? (p.wn + 2 * pad) * kGemmTile : kGemmTile * p.wn + 2 * pad;
     p.lds = (size_t)kGruChunk * p.pitch * sizeof(float);
-    const int64_t groups = (int64_t)p.tiles_x * p.tiles_y * in.B;
-    if (groups > 0x7fffffff) {
+    const int64_t groups = gemm_groups(p.tiles_x, p.tiles_y, in.B);
+    if (groups < 0) {
         p = SepConvGruPlan{};
         p.refused = GruRefusal::Grid;
         return p;
     }
     p.grid = dim3((unsigned)groups, (unsigned)p.m_groups);
-    p.block = dim3(64 * kGruWaves);
+    p.block = dim3(64 * kGemmWaves);
     p.mfma = "32x32x2_f32";
     return p;
 }

@@ -382,27 +382,18 @@ class SepConvGru:
         self._packed = self._pack(taken)
 
     def _pack(self, w) -> Dict[str, object]:
-        """include/ftk.h's layout: [M, K] (torch's own k = c * ks + t) padded to whole tiles and k-steps (rows +0, columns -0), as
-        [tiles][k_steps][64] with lane = 32 (k % 2) + row % 32.  Construction time: torch ops."""
+        """The packed matrices (``_pack_matrix`` of torch's own [M, K], k = c * ks + t) and biases, per pass.  Construction time: torch ops."""
         import torch
 
         K = (self.x_channels + self.h_channels) * self.kernel_size
         k_steps = N.sep_conv_gru_k_steps(self.x_channels + self.h_channels, self.kernel_size)
 
-        def pack(matrix):
-            M = matrix.size(0)
-            tiles = -(-M // 32)
-            full = torch.zeros((tiles * 32, 2 * k_steps), dtype=torch.float32, device=matrix.device)
-            full[:, K:] = -0.0
-            full[:M, :K] = matrix
-            return full.view(tiles, 32, k_steps, 2).permute(0, 2, 3, 1).contiguous().view(-1)
-
         packed = {}
         for d in ("horizontal", "vertical"):
             flat = {g: w[f"conv_{g}_{d}.weight"].reshape(self.h_channels, K) for g in "zrq"}
-            packed["zr_" + d] = pack(torch.cat([flat["z"], flat["r"]], 0))
+            packed["zr_" + d] = _pack_matrix(torch.cat([flat["z"], flat["r"]], 0), k_steps)
             packed["zr_bias_" + d] = torch.cat([w[f"conv_z_{d}.bias"], w[f"conv_r_{d}.bias"]], 0).contiguous()
-            packed["q_" + d] = pack(flat["q"])
+            packed["q_" + d] = _pack_matrix(flat["q"], k_steps)
             packed["q_bias_" + d] = w[f"conv_q_{d}.bias"].contiguous()
         return packed
 
@@ -461,18 +452,23 @@ def _state_tensor(state: Mapping, key: str, rank: int = None):
     return t
 
 
-def _pack_conv(weight):
-    """include/ftk.h's layout of a Conv2d weight [M, C_in, ks, ks]: torch's own [M, K] (k = (c * ks + ty) * ks + tx) padded to whole tiles
-    and k-steps (rows +0, columns -0), as [tiles][k_steps][64] with lane = 32 (k % 2) + row % 32.  Construction time: torch ops."""
+def _pack_matrix(matrix, k_steps: int):
+    """include/ftk.h's layout of a weight matrix [M, K] in torch's own k order: padded to whole tiles and k-steps (rows +0, columns -0), as
+    [tiles][k_steps][64] with lane = 32 (k % 2) + row % 32.  Construction time: torch ops."""
     import torch
 
-    M, Cin, ks, _ = (int(e) for e in weight.shape)
-    K, k_steps = Cin * ks * ks, N.conv2d_k_steps(Cin, ks)
+    M, K = (int(e) for e in matrix.shape)
     tiles = -(-M // 32)
-    full = torch.zeros((tiles * 32, 2 * k_steps), dtype=torch.float32, device=weight.device)
+    full = torch.zeros((tiles * 32, 2 * k_steps), dtype=torch.float32, device=matrix.device)
     full[:, K:] = -0.0
-    full[:M, :K] = weight.reshape(M, K)
+    full[:M, :K] = matrix
     return full.view(tiles, 32, k_steps, 2).permute(0, 2, 3, 1).contiguous().view(-1)
+
+
+def _pack_conv(weight):
+    """The packed matrix of a Conv2d weight [M, C_in, ks, ks]: ``_pack_matrix`` of torch's own [M, K], k = (c * ks + ty) * ks + tx."""
+    M, Cin, ks, _ = (int(e) for e in weight.shape)
+    return _pack_matrix(weight.reshape(M, Cin * ks * ks), N.conv2d_k_steps(Cin, ks))
 
 
 def _load_convs(state: Mapping, prefix: str, shapes: Mapping):

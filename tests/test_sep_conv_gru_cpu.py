@@ -454,3 +454,22 @@ def test_plan_refuses_limits_by_name():
              dict(base, B=2 ** 31 - 1, H=2 ** 31 - 1), dict(base, h_channels=1024, in_channels=4096), dict(base, h_channels=512, in_channels=1024)]
     got = [p["refused"] for p in plan(cases)]
     assert got == ["kernel_size", "kernel_size", "h_channels", "h_channels", "in_channels", "in_channels", "sizes", "sizes", "sizes", "grid", "none", "none"]
+
+
+def test_plan_counts_tiles_of_the_widest_row_exactly():
+    """W + tile_w - 1 passes 2^31 for a W near INT32_MAX: the tile counts are computed in 64 bits, for every wave split, and the grid is
+    refused only when the workgroup count itself passes 2^31 - 1."""
+    W = 2 ** 31 - 1
+    cases = [dict(h_channels=h, in_channels=h + 16, kernel_size=ks, vertical=vertical, gates=0, B=1, H=1, W=W)
+             for h in (16, 48, 100) for vertical in (0, 1) for ks in (3, 5)]
+    plans = plan(cases)
+    assert sorted({p.get("wn") for p in plans}) == [1, 2, 4]
+    for c, p in zip(cases, plans):
+        what = f"{c} -> {p}"
+        assert p["refused"] == "none", what
+        assert p["wn"] == {16: 4, 48: 2, 100: 1}[c["h_channels"]], what
+        assert p["tile_w"] == (32 if c["vertical"] else 32 * p["wn"]), what
+        assert p["tiles_x"] == cdiv(W, p["tile_w"]) and p["tiles_y"] == 1, what
+        assert p["grid"] == (cdiv(W, p["tile_w"]), p["m_groups"]), what
+    refused = plan([dict(c, B=2 ** 31 - 1, H=1, W=129) for c in cases])
+    assert [p["refused"] for p in refused] == ["grid"] * len(cases)
