@@ -46,6 +46,10 @@ FTK_KEYPOINT_DECODE_MAX_CHANNELS = 1024
 # the assignment head (include/ftk.h)
 FTK_MATCH_ASSIGNMENT_MAX_ROWS = 4096
 FTK_MATCH_ASSIGNMENT_MAX_DIM = 1024
+# the transformer layer (include/ftk.h)
+FTK_TRANSFORMER_MAX_ROWS = 4096
+FTK_TRANSFORMER_MAX_DIM = 1024
+FTK_TRANSFORMER_MAX_HEAD_DIM = 128
 # SepConvGru (include/ftk.h): the supported sizes and the packed weight layout
 FTK_SEP_CONV_GRU_MAX_PARTS = 3
 FTK_SEP_CONV_GRU_MAX_H_CHANNELS = 1024
@@ -85,6 +89,7 @@ EXPORTS = [
     "ftk_two_view_workspace_bytes", "ftk_two_view_ransac_device",
     "ftk_keypoint_decode_workspace_bytes", "ftk_keypoint_decode_device",
     "ftk_match_assignment_workspace_bytes", "ftk_match_assignment_device",
+    "ftk_transformer_layer_workspace_bytes", "ftk_attention_device", "ftk_linear_device", "ftk_transformer_layer_device",
 ]
 UNIQUE_ID_BYTES = 128
 
@@ -272,6 +277,10 @@ def lib() -> C.CDLL:
     l.ftk_keypoint_decode_device.argtypes = [vp, vp, vp, i32, i32, vp, i32, C.c_int64, C.c_int64, C.c_int64, i32, f32, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]
     l.ftk_match_assignment_workspace_bytes.argtypes = [i32, i32, i32, i32, i64p]
     l.ftk_match_assignment_device.argtypes = [vp, vp, vp, i32, vp, i32, i32, vp, vp, f32, vp, vp, vp, vp, C.c_int64]
+    l.ftk_transformer_layer_workspace_bytes.argtypes = [i32, i32, i32, i32, i64p]
+    l.ftk_attention_device.argtypes = [vp, vp, vp, i32, vp, vp, i32, i32, i32, vp, f32, f32, vp]
+    l.ftk_linear_device.argtypes = [vp, vp, vp, i32, i32, vp, vp, i32, vp]
+    l.ftk_transformer_layer_device.argtypes = [vp, vp, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     _lib = l
     return l
 
@@ -358,6 +367,38 @@ def match_assignment_workspace_bytes(rows0: int, rows1: int, dim: int, with_weig
     up16 = lambda v: (v + 15) & ~15  # noqa: E731
     own = up16(4 * m) + up16(4 * n)
     return own + (up16(4 * (m + n) * d) + up16(4 * (m + n)) + up16(8 * m) + up16(8 * n) if with_weights else 0)
+
+
+def transformer_layer_workspace_bytes(rows0: int, rows1: int, dim: int, heads: int = 4) -> int:
+    """Bytes of workspace ftk_transformer_layer_device needs, the value ftk_transformer_layer_workspace_bytes returns (pure Python;
+    csrc/transformer_plan.cpp): with R = rows0 + rows1 the q | k | v planes [3][R][D], the attention output, the message and the self
+    block's result [R][D] each, and the hidden rows [R][2 D].  ValueError for a shape the library refuses."""
+    m, n, d, h = int(rows0), int(rows1), int(dim), int(heads)
+    if not (1 <= m <= FTK_TRANSFORMER_MAX_ROWS and 1 <= n <= FTK_TRANSFORMER_MAX_ROWS):
+        raise ValueError(f"rows must be in 1 .. FTK_TRANSFORMER_MAX_ROWS = {FTK_TRANSFORMER_MAX_ROWS} per side (got {m} and {n})")
+    if not 1 <= d <= FTK_TRANSFORMER_MAX_DIM:
+        raise ValueError(f"dim must be in 1 .. FTK_TRANSFORMER_MAX_DIM = {FTK_TRANSFORMER_MAX_DIM} (got {d})")
+    if h < 1 or d % h != 0:
+        raise ValueError(f"heads = {h} must divide dim = {d}")
+    if (d // h) % 2 != 0 or not 2 <= d // h <= FTK_TRANSFORMER_MAX_HEAD_DIM:
+        raise ValueError(f"the head dimension must be even and in 2 .. FTK_TRANSFORMER_MAX_HEAD_DIM = {FTK_TRANSFORMER_MAX_HEAD_DIM} (got {d // h})")
+    r = m + n
+    up16 = lambda v: (v + 15) & ~15  # noqa: E731
+    return up16(12 * r * d) + 3 * up16(4 * r * d) + up16(8 * r * d)
+
+
+def transformer_layer_weight_offsets(dim: int):
+    """(float offsets of the self block's ten tensors, of the cross block's, the total) in ftk_transformer_layer_device's packed weights
+    (csrc/transformer_plan.cpp): per block the input Linear and bias, the output Linear and bias, ffn.0 and bias, LayerNorm's weight and
+    bias, ffn.3 and bias."""
+    d, at, blocks = int(dim), 0, []
+    for in_outs in (3 * d, 2 * d):
+        offsets = []
+        for size in (in_outs * d, in_outs, d * d, d, 4 * d * d, 2 * d, 2 * d, 2 * d, 2 * d * d, d):
+            offsets.append(at)
+            at += size
+        blocks.append(tuple(offsets))
+    return blocks[0], blocks[1], at
 
 
 def _gemm_k_steps(in_channels: int, chunk: int, taps: int) -> int:

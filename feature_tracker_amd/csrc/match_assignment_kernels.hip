@@ -15,72 +15,13 @@
 // Every float operation is written out (fmaf, __f*_rn); with -ffp-contract=off the results are bit-identical to the scalar restatement
 // tests/match_assignment_ref.c.  Out-of-range rows and columns of a tile read row 0 and are never stored.
 #include "match_assignment_plan.h"
+#include "mfma_tile_gemm.h"
 #include "raft_math.h"
 
 namespace ftk {
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int kColTiles = kAssignGemmTileCols / 32;
-
-// One wave's 32 x 128 tile: acc[t][r] += sum over c ascending of a[c] b_t[c], where this lane's `a` is row (lane & 31) of the 32 and
-// `b[t]` column 32 t + (lane & 31) of the 128, both as rows of `dim` floats.  Afterwards acc[t][r] belongs to row
-// (r & 3) + 8 (r >> 2) + 4 (lane >> 5) and column 32 t + (lane & 31).  k-step s feeds channel 2 s from lanes 0-31 and 2 s + 1 from lanes
-// 32-63; the matrix core adds them in that order with one rounding per product.  An odd dim pads the last step with (-0) * (+0) = -0,
-// which leaves every accumulator as it is.
-template <bool kVec>
-__device__ __forceinline__ void tile_gemm(const float *a, const float *(&b)[kColTiles], int dim, float scale, int kh, f32x16 (&acc)[kColTiles]) {
-    if (kVec) {
-        const int chunks = dim >> 2;
-        const float4 *a4 = reinterpret_cast<const float4 *>(a);
-        const float4 *b4[kColTiles];
-#pragma unroll
-        for (int t = 0; t < kColTiles; ++t) {
-            b4[t] = reinterpret_cast<const float4 *>(b[t]);
-        }
-        float4 a_cur = a4[0], b_cur[kColTiles];
-#pragma unroll
-        for (int t = 0; t < kColTiles; ++t) {
-            b_cur[t] = b4[t][0];
-        }
-        for (int u = 0; u < chunks; ++u) {
-            float4 a_nxt = a_cur, b_nxt[kColTiles];
-            const int un = u + 1 < chunks ? u + 1 : u;
-            a_nxt = a4[un];
-#pragma unroll
-            for (int t = 0; t < kColTiles; ++t) {
-                b_nxt[t] = b4[t][un];
-            }
-            const float a0 = __fmul_rn(kh ? a_cur.y : a_cur.x, scale), a1 = __fmul_rn(kh ? a_cur.w : a_cur.z, scale);
-#pragma unroll
-            for (int t = 0; t < kColTiles; ++t) {
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, __fmul_rn(kh ? b_cur[t].y : b_cur[t].x, scale), acc[t], 0, 0, 0);
-            }
-#pragma unroll
-            for (int t = 0; t < kColTiles; ++t) {
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, __fmul_rn(kh ? b_cur[t].w : b_cur[t].z, scale), acc[t], 0, 0, 0);
-            }
-            a_cur = a_nxt;
-#pragma unroll
-            for (int t = 0; t < kColTiles; ++t) {
-                b_cur[t] = b_nxt[t];
-            }
-        }
-    } else {
-        const int steps = (dim + 1) >> 1;
-        for (int s = 0; s < steps; ++s) {
-            const int c = 2 * s + kh;
-            const bool in = c < dim;
-            const float av = in ? __fmul_rn(a[c], scale) : -0.0f;
-#pragma unroll
-            for (int t = 0; t < kColTiles; ++t) {
-                const float bv = in ? __fmul_rn(b[t][c], scale) : 0.0f;
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[t], 0, 0, 0);
-            }
-        }
-    }
-}
+static_assert(kAssignGemmTileCols == 32 * kColTiles, "tile_gemm's 4 column tiles");
 
 template <bool kVec>
 __global__ void __launch_bounds__(64 * kAssignGemmWaves) match_project_kernel(const MatchAssignmentParams p) {
@@ -167,14 +108,6 @@ __global__ void __launch_bounds__(64 * kAssignGemmWaves) match_similarity_kernel
     }
 }
 
-__device__ __forceinline__ int valid_count(const int32_t *count, int extent) {
-    return count ? min(max(count[0], 0), extent) : extent;
-}
-
-// m of 5.23 step 3 from the first valid entry and the greatest entry that is no NaN: the scan `m = x_0; if (x > m) m = x` ends at x_0
-// when that is NaN and at the greatest comparable entry otherwise (which of two zeros it ends at changes no later bit).
-__device__ __forceinline__ float scan_maximum(float first, float greatest) { return first != first ? first : greatest; }
-
 __global__ void __launch_bounds__(kAssignNormThreads) match_normalise_kernel(const MatchAssignmentParams p, uint32_t row_blocks) {
     __shared__ float tile[64 * kAssignNormLdsStride];
     const int lane = threadIdx.x;
@@ -201,22 +134,13 @@ __global__ void __launch_bounds__(kAssignNormThreads) match_normalise_kernel(con
                 greatest = x;
             }
         }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            const float o = __shfl_xor(greatest, off);
-            if (o > greatest) {
-                greatest = o;
-            }
-        }
+        greatest = xor_greatest(greatest);
         const float m = scan_maximum(row[0], greatest);
         float sum = 0.0f;
         for (int c = lane; c < n1; c += 64) {
             sum = __fadd_rn(sum, exp_c(__fsub_rn(row[c], m)));
         }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            sum = __fadd_rn(sum, __shfl_xor(sum, off));
-        }
+        sum = xor_sum(sum);
         if (lane == 0) {
             p.lse_row[i] = __fadd_rn(m, log_c(sum));
         }
@@ -246,13 +170,7 @@ __global__ void __launch_bounds__(kAssignNormThreads) match_normalise_kernel(con
             greatest = x;
         }
     }
-#pragma unroll
-    for (int off = 32; off >= kAssignNormCols; off >>= 1) {
-        const float o = __shfl_xor(greatest, off);
-        if (o > greatest) {
-            greatest = o;
-        }
-    }
+    greatest = xor_greatest<32, kAssignNormCols>(greatest);
     const float m = scan_maximum(src[0], greatest);
     float sums[kAssignNormCols];  // of column c0 + k over the rows = lane (mod 64)
 #pragma unroll
@@ -280,10 +198,7 @@ __global__ void __launch_bounds__(kAssignNormThreads) match_normalise_kernel(con
     }
 #pragma unroll
     for (int k = 0; k < kAssignNormCols; ++k) {
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            sums[k] = __fadd_rn(sums[k], __shfl_xor(sums[k], off));
-        }
+        sums[k] = xor_sum(sums[k]);
     }
     float sum = sums[0];
 #pragma unroll

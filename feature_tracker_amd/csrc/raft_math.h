@@ -1,5 +1,5 @@
 // raft_math.h — the device functions the RAFT kernels share: exp_c and, built on it, sigmoid_c and tanh_c
-// (DESIGN.md 5.13).  Each is a stated sequence of correctly rounded float32 operations (the fused ones written as fmaf; the
+// (DESIGN.md 5.13), log_c (5.23) and erf_c (5.24).  Each is a stated sequence of correctly rounded float32 operations (the fused ones written as fmaf; the
 // library is compiled with -ffp-contract=off), so a kernel that uses them can be held bit-identical to a scalar restatement.
 #pragma once
 
@@ -65,6 +65,49 @@ __device__ __forceinline__ float log_c(float x) {
 // ls of DESIGN.md 5.23 (log sigmoid): min(z, 0) - log_c(1 + exp_c(-|z|)); NaN gives NaN.
 __device__ __forceinline__ float log_sigmoid_c(float z) {
     return __fsub_rn(fminf(z, 0.0f), log_c(__fadd_rn(1.0f, exp_c(-fabsf(z)))));
+}
+
+// erf_c of DESIGN.md 5.24; a = |x|.  a < 1: x P(x^2), P the Taylor coefficients 2 / sqrt(pi) (-1)^n / (n! (2 n + 1)) up to n = 12.
+// 1 <= a < 4: 1 - exp_c(-(a a)) Q(1 / a), Q a degree-9 fit of erfc(a) exp(a^2) on [1, 4], with the sign of x.  a >= 4: +-1.  Odd,
+// erf_c(+-0) = +-0, NaN gives NaN.
+__device__ __forceinline__ float erf_c(float x) {
+    if (x != x) {
+        return x;
+    }
+    const float a = fabsf(x);
+    if (a < 1.0f) {
+        const float s = __fmul_rn(x, x);
+        float p = 0x1.9e6ad6p-34f;
+        p = fmaf(p, s, -0x1.51d718p-30f);
+        p = fmaf(p, s, 0x1.fcc572p-27f);
+        p = fmaf(p, s, -0x1.5f742ep-23f);
+        p = fmaf(p, s, 0x1.b9e6cap-20f);
+        p = fmaf(p, s, -0x1.f4d25cp-17f);
+        p = fmaf(p, s, 0x1.f9a326p-14f);
+        p = fmaf(p, s, -0x1.c02db4p-11f);
+        p = fmaf(p, s, 0x1.565bcep-8f);
+        p = fmaf(p, s, -0x1.b82ce4p-6f);
+        p = fmaf(p, s, 0x1.ce2f22p-4f);
+        p = fmaf(p, s, -0x1.812746p-2f);
+        p = fmaf(p, s, 0x1.20dd76p+0f);
+        return __fmul_rn(x, p);
+    }
+    if (a >= 4.0f) {
+        return copysignf(1.0f, x);
+    }
+    const float t = __fdiv_rn(1.0f, a);
+    float q = 0x1.eb6cf6p-6f;
+    q = fmaf(q, t, -0x1.6687c8p-3f);
+    q = fmaf(q, t, 0x1.b39f5p-2f);
+    q = fmaf(q, t, -0x1.08bcdap-1f);
+    q = fmaf(q, t, 0x1.c0ff9ap-3f);
+    q = fmaf(q, t, 0x1.effe7ap-3f);
+    q = fmaf(q, t, -0x1.85acaap-2f);
+    q = fmaf(q, t, 0x1.634f56p-6f);
+    q = fmaf(q, t, 0x1.1f8b32p-1f);
+    q = fmaf(q, t, 0x1.11b274p-13f);
+    const float e = exp_c(-__fmul_rn(a, a));
+    return copysignf(__fsub_rn(1.0f, __fmul_rn(e, q)), x);
 }
 
 // sigmoid_c of DESIGN.md 5.13: 1 / (1 + e) for v >= 0 and e / (1 + e) otherwise, e = exp_c(-|v|); NaN gives NaN.

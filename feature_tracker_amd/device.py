@@ -487,6 +487,7 @@ from ._device_epipolar import epipolar_ransac_device  # noqa: E402,F401  (two-vi
 from ._device_two_view import two_view_ransac_device  # noqa: E402,F401  (the same with a choice of model)
 from ._device_keypoint_decode import keypoint_decode_device  # noqa: E402,F401  (the keypoint decoder; its own file, see there)
 from ._device_match_assignment import match_assignment_device  # noqa: E402,F401  (LightGlue's assignment head; its own file, see there)
+from ._device_transformer import attention_device, linear_device, transformer_layer_device  # noqa: E402,F401  (LightGlue's transformer layer; likewise)
 
 
 def _nn_stream(torch, device, stream):

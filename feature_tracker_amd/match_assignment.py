@@ -1,8 +1,8 @@
 """``MatchAssignment``: LightGlue's assignment head on the device.
 
 The last stage of LightGlue, and the producer of the tensor ``NNFeatureMatcher`` reads: two ``Linear`` layers, the M x N similarity, a
-log-softmax along both axes, the matchability terms and the dustbin row and column.  The transformer layers before it are not part of
-this package.  Without weights the same kernels are the dual-softmax matcher of LoFTR-style pipelines, which takes ``KeypointDecoder``'s
+log-softmax along both axes, the matchability terms and the dustbin row and column.  The transformer layers before it are
+``TransformerLayer`` (transformer.py); ``LightGlue`` composes them with this head.  Without weights the same kernels are the dual-softmax matcher of LoFTR-style pipelines, which takes ``KeypointDecoder``'s
 descriptors as they are.  4 launches (3 without weights) on one stream, on tensors that stay where they are: no copy to the host, no
 count read back, no synchronisation.
 """
@@ -24,7 +24,7 @@ class MatchAssignment:
     ``logsigmoid(-z)``, the corner 0; every entry of an invalid row or column is -inf.  Without weights there is no ``z``: the dustbins
     are -inf too.  The bits are those of DESIGN.md 5.23's contract, which the tests hold to a scalar restatement.
 
-    Limits: 1 <= M, N <= 4 096, 1 <= D <= 1 024, float32, one pair per call.  Out of scope: the transformer layers, a batch dimension,
+    Limits: 1 <= M, N <= 4 096, 1 <= D <= 1 024, float32, one pair per call.  Out of scope: a batch dimension,
     upstream's ``filter_matches`` threshold on ``exp(score)`` (``NNFeatureMatcher`` thresholds the log score).  The kernels run on torch's
     current stream (or on ``ctx``'s, from ``device.context_on_stream``); the object keeps one workspace per (device, M, N), so a call
     captured after one eager call at that size allocates nothing but its outputs.  There is no CPU fallback."""

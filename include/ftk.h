@@ -407,6 +407,37 @@ int ftk_match_assignment_device(ftk_context *ctx, void *stream, const float *d_d
                                 const float *d_weights, const float *d_bias, float scale, const int32_t *d_count0, const int32_t *d_count1,
                                 void *d_workspace, float *d_scores, int64_t row_stride);
 
+/*
+ * ftk_transformer_layer_device — one of LightGlue's transformer layers (TransformerLayer): the self block on each
+ * descriptor set, then the cross block in both directions, all in device memory.  ftk_attention_device and ftk_linear_device are two
+ * of its kernels alone.
+ *   d_desc0 [rows0][dim], d_desc1 [rows1][dim]: float32, dense rows; head a is columns a * dh .. a * dh + dh - 1, dh = dim / heads.
+ *   d_enc0 [2][rows0][dh], d_enc1 [2][rows1][dh]: the rotary encoding's cos and sin planes, repeat-interleaved as upstream caches them.
+ *   d_weights: the layer's tensors packed as DESIGN.md 5.24 states (TransformerLayer.from_state_dict packs them): per block the input
+ *   Linear (self: q | k | v rows, 3 dim; cross: to_qk | to_v, 2 dim) and its bias, the output Linear and its bias, ffn.0 [2 dim][2 dim]
+ *   and its bias, LayerNorm's weight and bias [2 dim], ffn.3 [dim][2 dim] and its bias; the self block first.
+ *   d_count0 / d_count1: int32 [1] device words or NULL: keys at or behind clamp(count, 0, rows) take part in no softmax (NULL: all).
+ *   d_out0 [rows0][dim], d_out1 [rows1][dim]: the layer's result; they may not overlap the inputs.
+ * ftk_attention_device: out [rows_q][heads * head_dim] = softmax((q pre)(k pre)^T post) v per head over the first clamp(count, 0,
+ * rows_k) keys; no valid key gives +0.  ftk_linear_device: out [rows][out_dim] = x [rows][in_dim] weight^T + bias.
+ * d_workspace: ftk_transformer_layer_workspace_bytes(rows0, rows1, dim, heads) bytes, 16-byte aligned, no initialisation needed.
+ * Limits: 1 <= rows <= FTK_TRANSFORMER_MAX_ROWS per side; 1 <= dim <= FTK_TRANSFORMER_MAX_DIM; heads divides dim; dh even and in
+ * 2 .. FTK_TRANSFORMER_MAX_HEAD_DIM; scales finite and > 0.  Everything is refused before any launch.  12 launches of fixed shape
+ * (attention, linear: 1) on `stream`; no host read, no synchronisation, no allocation: capturable.  The arithmetic is DESIGN.md 5.24's
+ * to the bit.  Non-finite values propagate; the inputs are never written.
+ */
+#define FTK_TRANSFORMER_MAX_ROWS 4096
+#define FTK_TRANSFORMER_MAX_DIM 1024
+#define FTK_TRANSFORMER_MAX_HEAD_DIM 128
+int ftk_transformer_layer_workspace_bytes(int32_t rows0, int32_t rows1, int32_t dim, int32_t heads, int64_t *bytes);
+int ftk_attention_device(ftk_context *ctx, void *stream, const float *d_q, int32_t rows_q, const float *d_k, const float *d_v, int32_t rows_k,
+                         int32_t heads, int32_t head_dim, const int32_t *d_count, float pre_scale, float post_scale, float *d_out);
+int ftk_linear_device(ftk_context *ctx, void *stream, const float *d_x, int32_t rows, int32_t in_dim, const float *d_weight, const float *d_bias,
+                      int32_t out_dim, float *d_out);
+int ftk_transformer_layer_device(ftk_context *ctx, void *stream, const float *d_desc0, int32_t rows0, const float *d_desc1, int32_t rows1, int32_t dim,
+                                 int32_t heads, const float *d_enc0, const float *d_enc1, const float *d_weights, const int32_t *d_count0,
+                                 const int32_t *d_count1, void *d_workspace, float *d_out0, float *d_out1);
+
 /* ---- diagnostics ---------------------------------------------------------------------------- */
 
 /*
