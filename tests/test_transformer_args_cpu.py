@@ -241,6 +241,26 @@ def _plan(m, n, d, h, aligned):
     return plan
 
 
+def test_the_shapes_of_the_non_vector_gpu_tests_plan_the_non_vector_kernels():
+    """What tests/test_transformer_gpu.py relies on: every LAYER_NARROW shape plans the non-vector Linear and attention whatever the
+    alignment; LAYER_SHAPES[2] plans them only for buffers that are not 16-byte aligned; D = 130 has the column tiles it is there for;
+    and the Linear's row tile is the header's kLinearTileRows, which LINEAR_ROWS brackets."""
+    from tests import transformer_ref as R
+    assert os.path.exists(PLAN_CLI), "host/build/transformer_plan_cli is missing: build() makes it"
+    tile = R.linear_tile_rows()
+    assert R.LINEAR_ROWS == (1, 31, 32, 33, tile - 1, tile, tile + 1)
+    cases = [s[:4] + (1,) for s in R.LAYER_NARROW] + [R.LAYER_SHAPES[2][:4] + (0,), R.LAYER_SHAPES[2][:4] + (1,), (tile - 1, 1, 8, 2, 1), (tile, 1, 8, 2, 1)]
+    text = "".join(" ".join(str(v) for v in c) + "\n" for c in cases)
+    out = subprocess.run([PLAN_CLI], input=text, capture_output=True, text=True, check=True).stdout.strip().split("\n")
+    plans = [dict(kv.split("=") for kv in line.split()) for line in out]
+    assert all(p["refused"] == "none" for p in plans)
+    k = len(R.LAYER_NARROW)
+    assert all(s[2] % 4 != 0 for s in R.LAYER_NARROW) and all((p["vec_linear"], p["vec_attn"]) == ("0", "0") for p in plans[:k])
+    assert R.LAYER_NARROW[4][2] == 130 and [plans[4][f"grid_y_{c}"] for c in ("d", "2d", "3d")] == ["2", "3", "4"]
+    assert (plans[k]["vec_linear"], plans[k]["vec_attn"]) == ("0", "0") and (plans[k + 1]["vec_linear"], plans[k + 1]["vec_attn"]) == ("1", "1")
+    assert plans[k + 2]["linear_grid_x"] == "1" and plans[k + 3]["linear_grid_x"] == "2" and int(plans[k]["linear_threads"]) == 2 * tile
+
+
 def test_plan_cli_equals_the_restated_plan():
     from feature_tracker_amd import _native as N
     assert os.path.exists(PLAN_CLI), "host/build/transformer_plan_cli is missing: build() makes it"

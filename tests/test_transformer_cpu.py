@@ -4,7 +4,12 @@ answers by hand, erf_c's error bound, upstream's formulas in torch float64, and 
 Measured here against float64 at the GPU tests' shapes (transformer_ref.LAYER_SHAPES, with and without counts): the worst absolute
 deviation of an output element is MEASURED_DEVIATION; the bound is 4 x that (DESIGN.md 5.23's margin).  erf_c's worst error against
 float64 erf over 2^20 + 1 points of [-6, 6] and every float32 of [2^-40, 2^-10] step 4099 is MEASURED_ERF_ULP; the bound is the next
-whole ulp above it."""
+whole ulp above it.
+
+Measured the same way at the shapes of the non-vector path (transformer_ref.LAYER_NARROW, with and without counts): MEASURED_DEVIATION_NARROW.
+With both blocks' LayerNorm weight times transformer_ref.GELU_WEIGHT_SCALE (the case that takes every branch of erf_c) the weight
+multiplies the error and the outputs are about 26 in magnitude instead of about 3: MEASURED_DEVIATION_SCALED, at LAYER_SHAPES[2].  Each
+has its own bound of 4 x its constant; every one of them measures the restatement against float64, never the device."""
 import functools
 import math
 import os
@@ -22,6 +27,10 @@ MEASURED_ERF_ULP = 2.3746
 ERF_ULP_BOUND = 3.0
 MEASURED_DEVIATION = 4.063e-6  # at (130, 65, 256, 4) with counts
 DEVIATION_BOUND = 4 * MEASURED_DEVIATION
+MEASURED_DEVIATION_NARROW = 2.673e-6  # at (35, 33, 130, 5) with counts
+DEVIATION_BOUND_NARROW = 4 * MEASURED_DEVIATION_NARROW
+MEASURED_DEVIATION_SCALED = 5.208e-5  # at (65, 130, 64, 4) with counts, LayerNorm weights x 6
+DEVIATION_BOUND_SCALED = 4 * MEASURED_DEVIATION_SCALED
 
 
 # ---- known answers -----------------------------------------------------------------------------------------------------------------------
@@ -175,6 +184,82 @@ def test_the_restatement_against_upstreams_formulas_in_float64(shape, counted):
     worst = _deviation(shape, counted)
     print(f"{shape[:4]} counted={counted}: worst absolute deviation {worst:.3e}")
     assert worst <= DEVIATION_BOUND
+
+
+@pytest.mark.parametrize("counted", [False, True], ids=["all_rows", "with_counts"])
+@pytest.mark.parametrize("shape", R.LAYER_NARROW, ids=["x".join(str(v) for v in s[:4]) for s in R.LAYER_NARROW])
+def test_the_restatement_against_float64_at_the_shapes_of_the_non_vector_path(shape, counted):
+    assert shape[2] % 4 != 0
+    worst = _deviation(shape, counted)
+    print(f"{shape[:4]} counted={counted}: worst absolute deviation {worst:.3e}")
+    assert worst <= DEVIATION_BOUND_NARROW
+
+
+@pytest.mark.parametrize("counted", [False, True], ids=["all_rows", "with_counts"])
+def test_the_scaled_layernorm_weight_takes_every_branch_of_erf_c_and_stays_at_float64(counted):
+    """The inputs of the GPU test of the same case: every branch of erf_c holds at least 1 % of the self block's pre-GELU values of
+    either set (a condition on the inputs; about 19 % / 47 % / 34 % here, against 84 % / 16 % / 0 with the weights as they are), the
+    restatement's outputs are finite, and they stay at upstream's formulas in float64."""
+    shape = R.LAYER_SHAPES[2]
+    h = shape[3]
+    a, b, e0, e1, sd = R.scaled_gelu_case(shape)
+    c0, c1 = _counts(shape, counted)
+    for x, enc, count in ((a, e0, c0), (b, e1, c1)):
+        shares = R.erf_branch_shares(R.self_block_pre_gelu(x, h, enc, sd, count))
+        print(f"counted={counted}: shares of a < 1, 1 <= a < 4, a >= 4: " + " / ".join(f"{100 * s:.1f} %" for s in shares))
+        assert min(shares) >= 0.01
+    plain = R.layer_case(shape)
+    assert R.erf_branch_shares(R.self_block_pre_gelu(plain[0], h, plain[2], plain[4]))[2] == 0  # what the other layer tests leave out
+    got = R.layer(a, b, h, e0, e1, sd, count0=c0, count1=c1)
+    want = layer64(a, b, h, e0, e1, sd, count0=c0, count1=c1)
+    assert np.isfinite(got[0]).all() and np.isfinite(got[1]).all()
+    worst = max(np.abs(got[0] - want[0]).max(), np.abs(got[1] - want[1]).max())
+    print(f"counted={counted}: worst absolute deviation {worst:.3e}")
+    assert worst <= DEVIATION_BOUND_SCALED
+
+
+def test_the_hostile_layer_case_spoils_only_its_own_rows_and_overflows_a_variance():
+    """The inputs of the GPU test of the same case, on the restatement alone: the rows that hold a NaN or an inf, and the row of 3e38,
+    whose Linears overflow, come out all NaN; every other row is finite, the row of zeros (variance 0) and the subnormal row among them; and the
+    row of 1e30 reaches LayerNorm finite, its sum of squares overflows, rstd is 0 and the row leaves the layer finite."""
+    shape = R.LAYER_SHAPES[2]
+    h = shape[3]
+    a, b, e0, e1, sd = R.hostile_layer_case(shape)
+    c0, c1 = R.HOSTILE_COUNTS
+    out0, out1 = R.layer(a, b, h, e0, e1, sd, count0=c0, count1=c1)
+    assert np.flatnonzero(~np.isfinite(out0).all(1)).tolist() == [3] and np.flatnonzero(~np.isfinite(out1).all(1)).tolist() == [8, 9]
+    assert np.isnan(out0[3]).all() and np.isnan(out1[8]).all() and np.isnan(out1[9]).all()
+    assert np.isfinite(b[8]).all() and not np.isfinite(b[9]).all() and not np.isfinite(a[3]).all()  # row 8 entered finite
+    hid = R.self_block_hidden(b, h, e1, sd, c1)
+    assert np.isfinite(hid[7]).all() and not np.isfinite(hid[8]).any()
+    with np.errstate(over="ignore"):
+        dev = hid[7] - np.float32(hid[7].astype(np.float64).mean())
+        assert np.isfinite(dev).all() and np.isinf((dev * dev).sum(dtype=np.float32))
+    gamma_beta = [sd[f"transformers.0.self_attn.ffn.1.{part}"] for part in ("weight", "bias")]
+    normed = R.layernorm_gelu(hid[7:8], *gamma_beta)
+    assert R.same(normed, R.layernorm_gelu(np.zeros((1, hid.shape[1]), np.float32), np.zeros_like(gamma_beta[0]), gamma_beta[1]))  # y = beta: rstd was 0
+
+
+@pytest.mark.parametrize("case", R.LINEAR_HOSTILE, ids=lambda c: f"{c[0]}x{c[1]}to{c[2]}")
+def test_the_hostile_linear_case_holds_nan_finite_values_and_a_negative_zero(case):
+    x, w, bias = R.hostile_linear_case(*case)
+    for a in (x, w, bias):
+        assert np.isnan(a).any() and np.isinf(a).any() and ((a == 0) & np.signbit(a)).any() and ((a != 0) & (np.abs(a) < 1.1754944e-38)).any()
+    assert not x[2].any() and not np.signbit(x[2]).any() and np.signbit(bias[1]) and np.signbit(bias[4])
+    want = R.linear(x, w, bias)
+    assert np.isnan(want).any() and np.isinf(want).any() and np.isfinite(want).sum() > want.size // 2
+    assert want[2, 1] == 0 and np.signbit(want[2, 1])      # -0 + (+0)(w < 0) ... stays -0
+    assert want[2, 4] == 0 and not np.signbit(want[2, 4])  # -0 + (+0)(w > 0) is +0
+    for k in range(1, case[1] + 1):  # the chain cut anywhere (a k-step padded with a product of -0 adds nothing to either)
+        part = R.linear(x[2:3, :k], w[:, :k], bias)
+        assert np.signbit(part[0, 1]) and not np.signbit(part[0, 4])
+
+
+def test_the_linear_cases_cover_every_edge_named():
+    assert len(R.LINEAR_CASES) < 40 and (33, 1024, 129) in R.LINEAR_CASES and (1, 1, 1) in R.LINEAR_CASES
+    for axis, values in enumerate((R.LINEAR_ROWS, R.LINEAR_INS, R.LINEAR_OUTS)):
+        assert {c[axis] for c in R.LINEAR_CASES} == set(values)
+    assert R.LINEAR_HOSTILE == ((33, 5, 33), (33, 8, 33))
 
 
 @pytest.mark.parametrize("mutant", sorted(R.MUTANTS))

@@ -10,6 +10,7 @@ from tests import transformer_ref as R
 pytestmark = pytest.mark.gpu
 
 LAYER_IDS = ["x".join(str(v) for v in s[:4]) for s in R.LAYER_SHAPES]
+NARROW_IDS = ["x".join(str(v) for v in s[:4]) for s in R.LAYER_NARROW]
 
 
 def _cuda(a):
@@ -117,8 +118,9 @@ def _run_layer(layer, a, b, e0, e1, c0=None, c1=None):
 
 
 @pytest.mark.parametrize("counted", [False, True], ids=["all_rows", "with_counts"])
-@pytest.mark.parametrize("shape", R.LAYER_SHAPES, ids=LAYER_IDS)
+@pytest.mark.parametrize("shape", R.LAYER_SHAPES + R.LAYER_NARROW, ids=LAYER_IDS + NARROW_IDS)
 def test_the_layer_is_the_restatement_bit_for_bit(ftk, shape, counted):
+    """LAYER_NARROW: D % 4 != 0, so all eight Linears of the layer run linear_kernel<false> and attention its scalar loads."""
     a, b, e0, e1, sd = R.layer_case(shape)
     c0, c1 = _given(shape) if counted else (None, None)
     got0, got1 = _run_layer(_layer_of(ftk, sd, shape[3]), a, b, e0, e1, c0, c1)
@@ -148,9 +150,8 @@ def test_a_repeated_call_with_another_size_in_between_gives_the_same_bits(ftk):
     assert all(R.same(x, y) for x, y in zip(first, second)) and all(R.same(x, y) for x, y in zip(first, want))
 
 
-def test_a_captured_graph_replayed_on_changed_descriptors_and_counts_equals_the_restatement(ftk):
+def _replayed_graph_equals_the_restatement(ftk, shape, replay_counts):
     import torch
-    shape = R.LAYER_SHAPES[2]
     m, n, d, h, seed = shape
     a, b, e0, e1, sd = R.layer_case(shape)
     a2, b2 = R.inputs(m, n, d, h, seed + 50)[:2]
@@ -164,12 +165,108 @@ def test_a_captured_graph_replayed_on_changed_descriptors_and_counts_equals_the_
         out0, out1 = layer(d_a, d_b, d_e0, d_e1, c0, c1)
     d_a.copy_(torch.from_numpy(a2.copy()))
     d_b.copy_(torch.from_numpy(b2.copy()))
-    c0.fill_(40)
-    c1.fill_(101)
+    c0.fill_(replay_counts[0])
+    c1.fill_(replay_counts[1])
     graph.replay()
     torch.cuda.synchronize()
-    want0, want1 = R.layer(a2, b2, h, e0, e1, sd, count0=40, count1=101)
+    want0, want1 = R.layer(a2, b2, h, e0, e1, sd, count0=replay_counts[0], count1=replay_counts[1])
     assert R.same(out0.cpu().numpy(), want0) and R.same(out1.cpu().numpy(), want1)
+
+
+def test_a_captured_graph_replayed_on_changed_descriptors_and_counts_equals_the_restatement(ftk):
+    _replayed_graph_equals_the_restatement(ftk, R.LAYER_SHAPES[2], (40, 101))
+
+
+def test_a_captured_graph_of_the_non_vector_path_replayed_equals_the_restatement(ftk):
+    shape = R.LAYER_NARROW[3]
+    assert shape[:4] == (40, 70, 18, 3)
+    _replayed_graph_equals_the_restatement(ftk, shape, (25, 43))
+
+
+def _offset_by_one_float(array_or_shape):
+    """A contiguous CUDA view one float into a larger tensor, so only 4-byte aligned; the tensor it lies in."""
+    import torch
+    given = isinstance(array_or_shape, np.ndarray)
+    shape = array_or_shape.shape if given else tuple(array_or_shape)
+    big = torch.full((int(np.prod(shape)) + 1,), 7.0, dtype=torch.float32, device="cuda")
+    view = big[1:].view(shape)
+    if given:
+        view.copy_(torch.from_numpy(np.array(array_or_shape, copy=True)))
+    assert view.is_contiguous() and view.data_ptr() % 16 == 4
+    return view, big
+
+
+@pytest.mark.parametrize("offset", ["desc0", "desc1", "weights", "out0", "out1", "all_five"])
+def test_the_layer_on_buffers_that_are_only_4_byte_aligned(ftk, offset):
+    """D % 4 == 0, so the alignment alone selects linear_kernel<false> and attention's scalar loads: each of the five buffers the entry
+    looks at, and then all of them, one float into a larger tensor.  The torch entry takes such views; the bits are the restatement's,
+    which are the aligned run's, with and without counts, and the float in front of each view keeps its value."""
+    import torch
+    from feature_tracker_amd import _native as N
+    from feature_tracker_amd import device as D
+    shape = R.LAYER_SHAPES[2]
+    m, n, d, h, _ = shape
+    a, b, e0, e1, sd = R.layer_case(shape)
+    packed = next(iter(_layer_of(ftk, sd, h)._packed.values())).numpy()
+    moved = ("desc0", "desc1", "weights", "out0", "out1") if offset == "all_five" else (offset,)
+    for counted in (False, True):
+        given = dict(desc0=a, desc1=b, weights=packed, out0=(m, d), out1=(n, d))
+        t, fronts = {}, []
+        for name, value in given.items():
+            if name in moved:
+                t[name], big = _offset_by_one_float(value)
+                fronts.append(big)
+            else:
+                t[name] = _cuda(value) if isinstance(value, np.ndarray) else torch.empty(value, dtype=torch.float32, device="cuda")
+                assert t[name].data_ptr() % 16 == 0
+        enc0, enc1 = _cuda(e0), _cuda(e1)
+        c0, c1 = _given(shape) if counted else (None, None)
+        workspace = torch.empty(-(-N.transformer_layer_workspace_bytes(m, n, d, h) // 8), dtype=torch.int64, device="cuda")
+        D.transformer_layer_device(ftk.default_context(), t["desc0"], t["desc1"], h, enc0, enc1, t["weights"], _count(c0), _count(c1), workspace,
+                                   t["out0"], t["out1"])
+        torch.cuda.synchronize()
+        want0, want1 = _want(shape, counted)
+        assert R.same(t["out0"].cpu().numpy(), want0) and R.same(t["out1"].cpu().numpy(), want1), (offset, counted)
+        assert R.same(t["desc0"].cpu().numpy(), a) and R.same(t["desc1"].cpu().numpy(), b) and R.same(t["weights"].cpu().numpy(), packed)
+        assert all(float(big[0]) == 7.0 for big in fronts)
+
+
+@functools.lru_cache(maxsize=None)
+def _want_scaled(counted):
+    shape = R.LAYER_SHAPES[2]
+    a, b, e0, e1, sd = R.scaled_gelu_case(shape)
+    c0, c1 = _given(shape) if counted else (None, None)
+    return R.layer(a, b, shape[3], e0, e1, sd, count0=c0, count1=c1)
+
+
+@pytest.mark.parametrize("counted", [False, True], ids=["all_rows", "with_counts"])
+def test_the_layer_with_every_branch_of_erf_c_taken(ftk, counted):
+    """Both blocks' LayerNorm weight times 6: about 19 % / 47 % / 34 % of the self block's pre-GELU values fall in erf_c's branches
+    a < 1, 1 <= a < 4 and a >= 4 (at least 1 % each is asserted here and, with the float64 pin, in tests/test_transformer_cpu.py); with
+    the weights as they are the last branch is never taken."""
+    shape = R.LAYER_SHAPES[2]
+    a, b, e0, e1, sd = R.scaled_gelu_case(shape)
+    c0, c1 = _given(shape) if counted else (None, None)
+    assert min(R.erf_branch_shares(R.self_block_pre_gelu(a, shape[3], e0, sd, c0))) >= 0.01
+    want0, want1 = _want_scaled(counted)
+    assert np.isfinite(want0).all() and np.isfinite(want1).all()
+    got0, got1 = _run_layer(_layer_of(ftk, sd, shape[3]), a, b, e0, e1, c0, c1)
+    assert R.same(got0, want0) and R.same(got1, want1)
+
+
+def test_the_layer_with_hostile_rows_behind_the_counts(ftk):
+    """NaN, inf, zeros, subnormals, 1e30 and 3e38 rows behind the counts (transformer_ref.hostile_layer_case): attention masks them as
+    keys, so they spoil only themselves.  On the restatement: NaN rows and finite rows in both sets, one NaN row that entered finite
+    (3e38: its Linears overflow), and the 1e30 row, whose LayerNorm variance overflows to inf (rstd = 0), finite.  Then the device, bit for bit."""
+    shape = R.LAYER_SHAPES[2]
+    a, b, e0, e1, sd = R.hostile_layer_case(shape)
+    c0, c1 = R.HOSTILE_COUNTS
+    want0, want1 = R.layer(a, b, shape[3], e0, e1, sd, count0=c0, count1=c1)
+    nan0, nan1 = np.isnan(want0).all(1), np.isnan(want1).all(1)
+    assert nan0.sum() == 1 and nan1.sum() == 2 and np.isfinite(want0[~nan0]).all() and np.isfinite(want1[~nan1]).all()
+    assert nan1[8] and np.isfinite(b[8]).all() and np.isfinite(want1[7]).all() and (b[7] == np.float32(1e30)).all()
+    got0, got1 = _run_layer(_layer_of(ftk, sd, shape[3]), a, b, e0, e1, c0, c1)
+    assert R.same(got0, want0) and R.same(got1, want1)
 
 
 def test_lightglue_is_the_restatements_composed_and_feeds_the_two_view_filter_without_a_host_read(ftk):

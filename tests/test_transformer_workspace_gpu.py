@@ -40,7 +40,10 @@ def _run(ftk, shape, counts, fill):
     return arena["out0"].cpu().numpy(), arena["out1"].cpu().numpy()
 
 
-@pytest.mark.parametrize("shape", R.LAYER_SHAPES[:4], ids=["x".join(str(v) for v in s[:4]) for s in R.LAYER_SHAPES[:4]])
+GUARDED_SHAPES = R.LAYER_SHAPES[:4] + R.LAYER_NARROW  # the latter: D % 4 != 0, the non-vector Linear and attention
+
+
+@pytest.mark.parametrize("shape", GUARDED_SHAPES, ids=["x".join(str(v) for v in s[:4]) for s in GUARDED_SHAPES])
 def test_the_layer_in_its_declared_bytes(ftk, shape):
     import ctypes as C
     from feature_tracker_amd import _native as N

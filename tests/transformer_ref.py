@@ -225,6 +225,102 @@ ATTENTION_WIDE = ((1024, 130, 8, 64), (1024, 130, 8, 128), (1024, 70, 8, 66), (1
 LAYER_WIDE = (1024, 33, 144, 4, 206)
 
 
+# (M, N, D, h, seed) with D % 4 != 0: every Linear of the layer runs its non-vector body and attention its scalar loads.  One lane and
+# dh = 2; partial row tiles; dh = 10 in one head; dh = 6 and the key tile crossed in the cross block; D = 130: 3 D = 390 outputs are 4
+# column tiles, the rotary boundary 2 D = 260 lies inside the third, and the second column tile of the D outputs holds 2 live columns
+LAYER_NARROW = ((1, 1, 6, 3, 207), (33, 31, 6, 3, 208), (65, 34, 10, 1, 209), (40, 70, 18, 3, 210), (35, 33, 130, 5, 211))
+# the Linear entry alone, (rows, in_dim, out_dim): a wave's 32 rows and a workgroup's 128 (transformer_plan.h's kLinearTileRows), the
+# 32-column MFMA tiles and the 128-column tile of a workgroup, in_dim 1, odd and at the limit; every value of each list at least once
+LINEAR_ROWS = (1, 31, 32, 33, 127, 128, 129)
+LINEAR_INS = (1, 2, 3, 5, 8, 33, 100, 1024)
+LINEAR_OUTS = (1, 31, 32, 33, 127, 128, 129, 1024)
+LINEAR_CASES = ((1, 1, 1), (33, 1024, 129), (31, 2, 31), (32, 3, 32), (33, 5, 33), (127, 8, 127), (128, 33, 128), (129, 100, 129), (129, 1, 1024),
+                (1, 1024, 1024), (32, 100, 1), (127, 33, 129), (128, 5, 127), (129, 3, 33), (31, 8, 128), (33, 2, 32))
+LINEAR_HOSTILE = ((33, 5, 33), (33, 8, 33))
+GELU_WEIGHT_SCALE = 6.0  # of both blocks' ffn.1.weight: |y / sqrt 2| reaches every branch of erf_c
+HOSTILE_COUNTS = (3, 7)  # of hostile_layer_case: its bad rows lie behind them
+
+
+def linear_tile_rows() -> int:
+    """kLinearTileRows as csrc/transformer_plan.h states it (the text of the header; tests/test_transformer_args_cpu.py holds the plan's
+    row tiles to it through the plan CLI)."""
+    import re
+    header = open(os.path.join(os.path.dirname(os.path.dirname(_SRC)), "feature_tracker_amd", "csrc", "transformer_plan.h")).read()
+    waves = int(re.search(r"constexpr int kLinearWaves = (\d+);", header).group(1))
+    assert re.search(r"constexpr int kLinearTileRows = 32 \* kLinearWaves;", header)
+    return 32 * waves
+
+
+@functools.lru_cache(maxsize=None)
+def linear_case(rows, ins, outs):
+    """(x, weight, bias) of a Linear shape, seeded by the shape."""
+    rng = np.random.default_rng(5000 + 1031 * rows + 17 * ins + outs)
+    return _frozen(rng.standard_normal((rows, ins)).astype(np.float32), *_linear_weights(rng, outs, ins))
+
+
+@functools.lru_cache(maxsize=None)
+def hostile_linear_case(rows, ins, outs):
+    """``linear_case`` with NaN, +-inf, -0 and subnormals scattered through x, weight and bias, and row 2 of x all +0 against a bias
+    that is -0 at outputs 1 and 4: fmaf(+0, w, -0) is -0 for w < 0 and +0 for w > 0, and a k-step that added a +0 of its own would
+    turn every such -0 into +0."""
+    x, w, b = (np.array(a, copy=True) for a in linear_case(rows, ins, outs))
+    x[0, 0], x[1, ins - 1], x[4, 1], x[5, 0], x[6, 2] = np.nan, np.inf, -np.inf, -0.0, 1e-40
+    x[7] = -1e-41
+    x[2] = 0.0
+    w[0, 0], w[3, ins - 1], w[5, 1], w[6, 0], w[7] = np.inf, np.nan, -0.0, 1e-39, 3e-40
+    w[1], w[4, :ins - 1], w[4, ins - 1] = -np.abs(w[1]), np.abs(w[4, :ins - 1]), -0.0  # row 2 of x: every product -0; +0 ... +0, -0
+    b[1], b[4], b[8], b[9], b[10], b[11] = -0.0, -0.0, np.nan, np.inf, -np.inf, 1e-42
+    return _frozen(x, w, b)
+
+
+def scaled_gelu_case(shape, scale=GELU_WEIGHT_SCALE):
+    """``layer_case`` with both blocks' LayerNorm weight times ``scale`` (a copy of the frozen state dict)."""
+    a, b, e0, e1, sd = layer_case(shape)
+    sd = dict(sd)
+    for block in ("self_attn", "cross_attn"):
+        key = f"transformers.0.{block}.ffn.1.weight"
+        sd[key] = _frozen((sd[key] * np.float32(scale)).astype(np.float32))[0]
+    return a, b, e0, e1, sd
+
+
+def hostile_layer_case(shape):
+    """``layer_case`` with bad rows behind HOSTILE_COUNTS, where attention masks them as keys and they spoil only themselves: a NaN, a
+    row of zeros (variance 0) and a subnormal row in set 0; in set 1 a row of 1e30 (LayerNorm's sum of squares overflows: rstd = 0), a row
+    of 3e38 (finite on input; the Linears' chains overflow and inf meets -inf: NaN) and a row that holds an inf."""
+    a, b, e0, e1, sd = layer_case(shape)
+    a, b = np.array(a, copy=True), np.array(b, copy=True)
+    a[3, 5], a[11], a[12] = np.nan, 0.0, 1e-40
+    b[7], b[8], b[9, 0] = 1e30, 3e38, np.inf
+    assert min(3, 11, 12) >= HOSTILE_COUNTS[0] and min(7, 8, 9) >= HOSTILE_COUNTS[1]
+    return _frozen(a, b) + (e0, e1, sd)
+
+
+def self_block_hidden(x, heads, enc, sd, count=None, prefix="transformers.0.self_attn."):
+    """The self block's rows in front of LayerNorm, ``ffn.0([x | message])``, composed from this module's exports: float32 [rows, 2 D]."""
+    rows, d = x.shape
+    dh = d // heads
+    raw = linear(x, sd[prefix + "Wqkv.weight"], sd[prefix + "Wqkv.bias"]).reshape(rows, heads, dh, 3)  # upstream's (head, channel, q | k | v)
+    q, k, v = (np.ascontiguousarray(raw[..., t]).reshape(rows, d) for t in range(3))
+    q, k = rotary(q, heads, enc), rotary(k, heads, enc)
+    ctx = attention(q.reshape(rows, heads, dh), k.reshape(rows, heads, dh), v.reshape(rows, heads, dh), count).reshape(rows, d)
+    msg = linear(ctx, sd[prefix + "out_proj.weight"], sd[prefix + "out_proj.bias"])
+    return linear(x, sd[prefix + "ffn.0.weight"], sd[prefix + "ffn.0.bias"], xb=msg)
+
+
+def self_block_pre_gelu(x, heads, enc, sd, count=None, prefix="transformers.0.self_attn."):
+    """The self block's values in front of GELU, ``LN(ffn.0([x | message])) gamma + beta``, with the LayerNorm in float64: float64
+    [rows, 2 D].  For statements about the inputs of a test (which branch of erf_c a value takes), not for bit comparisons."""
+    hid = self_block_hidden(x, heads, enc, sd, count, prefix).astype(np.float64)
+    norm = (hid - hid.mean(1, keepdims=True)) / np.sqrt(hid.var(1, keepdims=True) + 1e-5)
+    return norm * sd[prefix + "ffn.1.weight"].astype(np.float64) + sd[prefix + "ffn.1.bias"].astype(np.float64)
+
+
+def erf_branch_shares(y):
+    """The shares of a = |(float)y sqrt(1 / 2)| in erf_c's three branches: a < 1, 1 <= a < 4, a >= 4."""
+    a = np.abs(np.asarray(y, np.float32) * np.float32(float.fromhex("0x1.6a09e6p-1"))).ravel()  # the kernel's product, in float32
+    return float((a < 1).mean()), float(((a >= 1) & (a < 4)).mean()), float((a >= 4).mean())
+
+
 @functools.lru_cache(maxsize=None)
 def qkv(m, n, h, dh, seed):
     rng = np.random.default_rng(seed)
