@@ -1,6 +1,8 @@
 """``device.conv2d_device``: the torch device entry of the stock layers of RAFT's UpdateBlock (ftk_conv2d_device), and
 ``device.conv2d_strided_device``, the same layer with a stride, a residual and the image normalisation for RAFT's encoders
-(ftk_conv2d_strided_device; its walk and refusals are tests/test_raft_encoder_cpu.py).
+(ftk_conv2d_strided_device; its walk and refusals are tests/test_raft_encoder_cpu.py), ``device.conv2d_pool_device``, the
+layer with a 2 x 2 max-pool in its epilogue, and ``device.channel_normalise_device``, both for SuperPoint (ftk_conv2d_pool_device and
+ftk_channel_normalise_device; their walk and refusals are tests/test_superpoint_cpu.py).
 
 It is re-exported by device.py and held to that module's rule: no ``data_ptr()`` of a tensor that did not pass ``device._check``.
 It lives in a file of its own for the reason _device_sep_conv_gru.py gives; this entry's walk (the same recording stand-ins) and its
@@ -14,8 +16,10 @@ import math
 from . import _native as N
 
 
-def _conv2d(ctx, parts, packed_weights, bias, kernel_size, relu, out_scale, out, stream, *, strided: bool, stride=1, residual=None, normalise=False) -> None:
-    """The checks and the marshalling of both entries; ``strided`` says which of them calls, and so which ABI entry is called."""
+def _conv2d(ctx, parts, packed_weights, bias, kernel_size, relu, out_scale, out, stream, *, strided: bool, stride=1, residual=None, normalise=False,
+            pool: bool = False) -> None:
+    """The checks and the marshalling of the three conv entries; ``strided`` and ``pool`` say which of them calls, and so which ABI entry is
+    called."""
     from . import device as D
 
     ks, st = int(kernel_size), int(stride)
@@ -23,6 +27,8 @@ def _conv2d(ctx, parts, packed_weights, bias, kernel_size, relu, out_scale, out,
         raise ValueError(f"kernel_size {kernel_size} is not supported: 1, 3 and 7 are")
     if strided and (st not in N.FTK_CONV2D_STRIDES or ks not in N.FTK_CONV2D_STRIDES[st]):
         raise ValueError(f"stride {stride} with kernel_size {ks} is not supported: stride 1, and stride 2 with kernel sizes 1 and 3, are")
+    if pool and ks not in N.FTK_CONV2D_POOL_KERNEL_SIZES:
+        raise ValueError(f"kernel_size {ks} is not supported with the max-pool: 1 and 3 are")
     if not math.isfinite(float(out_scale)):
         raise ValueError(f"out_scale must be finite (got {out_scale})")
     parts = N.part_list(parts, "the input", N.FTK_CONV2D_MAX_PARTS)
@@ -34,10 +40,13 @@ def _conv2d(ctx, parts, packed_weights, bias, kernel_size, relu, out_scale, out,
     if Cout > N.FTK_CONV2D_MAX_OUT_CHANNELS:
         raise ValueError(f"out_channels {Cout} above FTK_CONV2D_MAX_OUT_CHANNELS = {N.FTK_CONV2D_MAX_OUT_CHANNELS}")
     H, W = OH, OW
-    if strided:  # the input's sizes are parts[0]'s
+    if strided or pool:  # the input's sizes are parts[0]'s
         D._check("parts[0]", parts[0], D._F32, (B, None, None, None), dev)
         H, W = int(parts[0].shape[2]), int(parts[0].shape[3])
-        if (-(-H // st), -(-W // st)) != (OH, OW):
+        if pool and (H // 2, W // 2) != (OH, OW):
+            raise ValueError(f"out must be [B, out_channels, {H // 2}, {W // 2}] for parts[0] {list(parts[0].shape)} under a 2 x 2 max-pool (got "
+                             f"{list(out.shape)})")
+        if not pool and (-(-H // st), -(-W // st)) != (OH, OW):
             raise ValueError(f"out must be [B, out_channels, {-(-H // st)}, {-(-W // st)}] for parts[0] {list(parts[0].shape)} at stride {st} (got "
                              f"{list(out.shape)})")
     Cin = N.checked_channels("parts", parts, B, H, W, dev)
@@ -50,7 +59,9 @@ def _conv2d(ctx, parts, packed_weights, bias, kernel_size, relu, out_scale, out,
     s = D._torch().cuda.current_stream(out.device) if stream is None else stream
     layer = (ctx.handle, C.c_void_p(s.cuda_stream), N.part_array(parts), len(parts), C.c_void_p(packed_weights.data_ptr()), C.c_void_p(bias.data_ptr()), Cout, ks)
     sizes = (B, H, W, C.c_void_p(out.data_ptr()))
-    if strided:
+    if pool:
+        rc = N.lib().ftk_conv2d_pool_device(*layer, 1 if relu else 0, *sizes)
+    elif strided:
         rc = N.lib().ftk_conv2d_strided_device(*layer, st, 1 if relu else 0, float(out_scale), None if residual is None else C.c_void_p(residual.data_ptr()),
                                                1 if normalise else 0, *sizes)
     else:
@@ -75,3 +86,31 @@ def conv2d_strided_device(ctx, parts, packed_weights, bias, kernel_size: int, st
     weights are BatchNorm-folded by the caller and packed as for ``conv2d_device``.  One launch, no synchronisation, no allocation:
     capturable.  Every argument is checked before the device is touched."""
     _conv2d(ctx, parts, packed_weights, bias, kernel_size, relu, out_scale, out, stream, strided=True, stride=stride, residual=residual, normalise=normalise)
+
+
+def conv2d_pool_device(ctx, parts, packed_weights, bias, kernel_size: int, relu: bool, out, stream=None) -> None:
+    """One layer of SuperPoint's VGG with the pool after it: ``conv2d_device`` (kernel size 1 or 3; there is no ``out_scale``) followed by
+    ``max_pool2d(2, 2)``, in one launch that never stores the tensor before the pool.  ``parts``: [B, C_i, H, W] with H, W >= 2; ``out``:
+    [B, out_channels, H // 2, W // 2]: a last odd row or column is dropped.  A NaN propagates and the first of equal maxima wins, as in
+    torch.  No synchronisation, no allocation: capturable.  Every argument is checked before the device is touched."""
+    _conv2d(ctx, parts, packed_weights, bias, kernel_size, relu, 1.0, out, stream, strided=False, pool=True)
+
+
+def channel_normalise_device(ctx, x, out, stream=None) -> None:
+    """The L2 normalisation of a dense descriptor map over its channels (``torch.nn.functional.normalize(dim=1)`` with the summation order
+    of DESIGN.md 5.25), written channel-last: ``x`` contiguous float32 CUDA [D, Hc, Wc], ``out`` [Hc, Wc, D]; ``out.permute(2, 0, 1)`` is
+    the view ``KeypointDecoder.decode`` reads with coalesced loads.  One launch on ``stream`` (default: torch's current stream), no
+    synchronisation, no allocation: capturable.  Every argument is checked before the device is touched."""
+    from . import device as D
+
+    dev = D._call_device(ctx, x)
+    D._check("x", x, D._F32, (None, None, None), dev)
+    d, hc, wc = (int(e) for e in x.shape)
+    if not 1 <= d <= N.FTK_KEYPOINT_DECODE_MAX_CHANNELS:
+        raise ValueError(f"x must have 1 .. FTK_KEYPOINT_DECODE_MAX_CHANNELS = {N.FTK_KEYPOINT_DECODE_MAX_CHANNELS} channels (got {d})")
+    if min(hc, wc) < 1:
+        raise ValueError(f"x must be a non-empty [D, Hc, Wc] tensor (got {list(x.shape)})")
+    D._check("out", out, D._F32, (hc, wc, d), dev)
+    s = D._torch().cuda.current_stream(x.device) if stream is None else stream
+    N.check(N.lib().ftk_channel_normalise_device(ctx.handle, C.c_void_p(s.cuda_stream), C.c_void_p(x.data_ptr()), d, hc, wc, C.c_void_p(out.data_ptr())),
+            ctx.handle)

@@ -63,6 +63,7 @@ FTK_CONV2D_MAX_IN_CHANNELS = 4096
 FTK_CONV2D_CHUNK = {1: 32, 3: 8, 7: 2}  # FTK_CONV2D_CHUNK_1 / _3 / _7
 FTK_CONV2D_KERNEL_SIZES = (1, 3, 7)
 FTK_CONV2D_STRIDES = {1: (1, 3, 7), 2: (1, 3)}  # ftk_conv2d_strided_device: the kernel sizes of each stride
+FTK_CONV2D_POOL_KERNEL_SIZES = (1, 3)  # ftk_conv2d_pool_device
 ERROR_NAMES = {0: "FTK_OK", -1: "FTK_E_INVALID_ARGUMENT", -2: "FTK_E_NO_DEVICE", -3: "FTK_E_HIP", -4: "FTK_E_UNSUPPORTED",
                -5: "FTK_E_OUT_OF_MEMORY"}
 
@@ -82,7 +83,7 @@ EXPORTS = [
     "ftk_corr_pyramid_layout", "ftk_corr_pyramid_build_device", "ftk_corr_pyramid_lookup_device", "ftk_flow_upsample_device", "ftk_flow_track_points_device", "ftk_flow_warm_splits", "ftk_flow_warm_device",
     "ftk_corr_ondemand_layout", "ftk_corr_ondemand_prepare_device", "ftk_corr_ondemand_lookup_device",
     "ftk_sep_conv_gru_packed_elements", "ftk_sep_conv_gru_gates_device", "ftk_sep_conv_gru_blend_device",
-    "ftk_conv2d_packed_elements", "ftk_conv2d_device", "ftk_conv2d_strided_device",
+    "ftk_conv2d_packed_elements", "ftk_conv2d_device", "ftk_conv2d_strided_device", "ftk_conv2d_pool_device", "ftk_channel_normalise_device",
     "ftk_nn_match_scores_device", "ftk_nn_match_scores", "ftk_nn_match_list_device", "ftk_nn_match_list", "ftk_nn_fill_pixels_device",
     "ftk_harris_detect_device", "ftk_track_table_retire_device", "ftk_track_table_fill_device",
     "ftk_epipolar_workspace_bytes", "ftk_epipolar_ransac_device",
@@ -261,6 +262,8 @@ def lib() -> C.CDLL:
     l.ftk_conv2d_packed_elements.argtypes = [i32, i32, i32, i64p]
     l.ftk_conv2d_device.argtypes = [vp, vp, parts, i32, vp, vp, i32, i32, i32, f32, i32, i32, i32, vp]
     l.ftk_conv2d_strided_device.argtypes = [vp, vp, parts, i32, vp, vp, i32, i32, i32, i32, f32, vp, i32, i32, i32, i32, vp]
+    l.ftk_conv2d_pool_device.argtypes = [vp, vp, parts, i32, vp, vp, i32, i32, i32, i32, i32, i32, vp]
+    l.ftk_channel_normalise_device.argtypes = [vp, vp, vp, i32, i32, i32, vp]
     l.ftk_nn_match_scores_device.argtypes = [vp, vp, vp, i32, i32, i32, i64, i64, f32, vp, vp]
     l.ftk_nn_match_scores.argtypes = [vp, vp, i32, i32, i32, i64, i64, f32, vp, vp, C.POINTER(C.c_int)]
     l.ftk_nn_match_list_device.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]

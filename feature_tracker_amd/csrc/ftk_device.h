@@ -527,6 +527,9 @@ struct ConvParams {
 };
 struct ConvPlan;
 hipError_t raft_conv_launch(const ConvPlan &plan, const ConvParams &p, int kernel_size, int relu, hipStream_t stream);
+// SuperPoint's VGG: the same layer (kernel sizes 1 and 3) with a 2 x 2 max-pool in its epilogue; p.out is [B][out_channels]
+// [H / 2][W / 2], p.out_scale is not read.  `plan` is a plan of pool = 1.
+hipError_t raft_conv_pool_launch(const ConvPlan &plan, const ConvParams &p, int kernel_size, int relu, hipStream_t stream);
 // RAFT's encoders (encoder.py:4-68): the same layer with a stride of 1 or 2 (base.H, base.W the input's sizes), a residual
 // added before the ReLU and the image normalisation of model.py:70-71 at the fetch.  Stride 1 with neither is raft_conv_launch itself.
 struct ConvStridedParams {
@@ -536,6 +539,11 @@ struct ConvStridedParams {
     int32_t normalise;      // != 0: an in-image input value x is read as 2 (x / 255) - 1
 };
 hipError_t raft_conv_strided_launch(const ConvPlan &plan, const ConvStridedParams &p, int kernel_size, int relu, hipStream_t stream);
+
+// SuperPoint's dense descriptor map (superpoint_kernels.hip): x [D][cells] to y [cells][D], every cell divided by
+// fmaxf(sqrtf(sum of squares over ascending c, an fmaf chain from +0), 1e-12f).  hipErrorInvalidValue when D or cells is not positive or
+// the grid (64 cells per workgroup) would not fit in 2^31 - 1 workgroups.
+hipError_t channel_normalise_launch(const float *x, float *y, int32_t D, int64_t cells, hipStream_t stream);
 
 // NNFeatureMatcher's post-processing (nn_match_kernels.hip): mutual-best matching of a score matrix, or a match list.
 // Keys (unsigned 64-bit, merged with atomicMax, 0 = empty): score mode (order-preserving map of the score << 32 | ~index), so the

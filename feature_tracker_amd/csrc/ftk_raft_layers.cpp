@@ -1,7 +1,7 @@
 // ftk_raft_layers.cpp — the layers of RAFT's update block and encoders of the C ABI (include/ftk.h), all launches of raft_gemm_core.h's
 // implicit GEMM over an input given as parts: the separable ConvGRU (SepConvGru.forward, gru.py:59-76), the nine stock
-// convolutions of update_block.py:4-67 and the same layer with a stride, a residual and the image normalisation for the
-// encoders (encoder.py:4-68).
+// convolutions of update_block.py:4-67, the same layer with a stride, a residual and the image normalisation for the
+// encoders (encoder.py:4-68) and with a 2 x 2 max-pool in its epilogue for SuperPoint's VGG.
 #include <cmath>
 
 #include "ftk_internal.h"
@@ -88,11 +88,11 @@ int gru_prepare(ftk_context *ctx, const char *what, const ftk_gru_part *x_parts,
     return FTK_OK;
 }
 
-// The checks, the plan and the launch of both conv entries; `what` names the caller.  stride 1 with no residual and no normalisation is
-// conv2d_kernel's plain form, whichever entry asks.
+// The checks, the plan and the launch of the three conv entries; `what` names the caller.  stride 1 with no residual and no normalisation is
+// conv2d_kernel's plain form, whichever entry asks; `pool` (the pooled entry alone: stride 1, no scale, no residual) is its pooled form.
 int conv2d_entry(const char *what, ftk_context *ctx, void *stream, const ftk_gru_part *parts, int32_t n_parts, const float *d_weights, const float *d_bias,
                  int32_t out_channels, int32_t kernel_size, int32_t stride, int32_t relu, float out_scale, const float *d_residual, int32_t normalise,
-                 int32_t B, int32_t H, int32_t W, float *d_out) {
+                 int32_t pool, int32_t B, int32_t H, int32_t W, float *d_out) {
     if (!ctx) {
         return ftk_fail(nullptr, FTK_E_INVALID_ARGUMENT, "%s: null context", what);
     }
@@ -111,6 +111,12 @@ int conv2d_entry(const char *what, ftk_context *ctx, void *stream, const ftk_gru
     if (kernel_size != 1 && kernel_size != 3 && kernel_size != 7) {
         return ftk_fail(ctx, FTK_E_UNSUPPORTED, "%s: kernel_size %d is not supported (1, 3 and 7 are)", what, kernel_size);
     }
+    if (pool && kernel_size == 7) {
+        return ftk_fail(ctx, FTK_E_UNSUPPORTED, "%s: kernel_size 7 is not supported with the max-pool (1 and 3 are)", what);
+    }
+    if (pool && (H < 2 || W < 2)) {
+        return ftk_fail(ctx, FTK_E_INVALID_ARGUMENT, "%s: H %d, W %d must be at least 2: the output is floor(H / 2) x floor(W / 2)", what, H, W);
+    }
     if ((stride != 1 && stride != 2) || (stride == 2 && kernel_size == 7)) {
         return ftk_fail(ctx, FTK_E_UNSUPPORTED, "%s: stride %d with kernel_size %d is not supported (stride 1, and stride 2 with kernel sizes 1 and 3, are)",
                         what, stride, kernel_size);
@@ -128,6 +134,7 @@ int conv2d_entry(const char *what, ftk_context *ctx, void *stream, const ftk_gru
     }
     ftk::ConvPlanInput in{};
     in.out_channels = out_channels, in.in_channels = (int32_t)in_channels, in.kernel_size = kernel_size, in.B = B, in.H = H, in.W = W, in.stride = stride;
+    in.pool = pool ? 1 : 0;
     const ftk::ConvPlan plan = ftk::raft_conv_plan(in);
     if (plan.refused != ftk::ConvRefusal::None) {
         return ftk_fail(ctx, FTK_E_UNSUPPORTED, "%s: B %d, %d x %d does not fit a launch (%s)", what, B, H, W, ftk::conv_refusal_name(plan.refused));
@@ -139,6 +146,10 @@ int conv2d_entry(const char *what, ftk_context *ctx, void *stream, const ftk_gru
     p.out_channels = out_channels, p.in_channels = (int32_t)in_channels, p.B = B, p.H = H, p.W = W;
     sp.residual = d_residual, sp.OH = plan.out_h, sp.OW = plan.out_w, sp.normalise = normalise != 0;
     FTK_HIP(ctx, hipSetDevice(ctx->device));
+    if (pool) {
+        FTK_HIP(ctx, ftk::raft_conv_pool_launch(plan, p, kernel_size, relu != 0, static_cast<hipStream_t>(stream)));
+        return FTK_OK;
+    }
     FTK_HIP(ctx, ftk::raft_conv_strided_launch(plan, sp, kernel_size, relu != 0, static_cast<hipStream_t>(stream)));
     return FTK_OK;
 }
@@ -221,8 +232,8 @@ int ftk_conv2d_packed_elements(int32_t out_channels, int32_t in_channels, int32_
 // out_conv.0), :57-59 with :66 (the mask head; :66's 0.25 is out_scale of its last layer)
 int ftk_conv2d_device(ftk_context *ctx, void *stream, const ftk_gru_part *parts, int32_t n_parts, const float *d_weights, const float *d_bias,
                       int32_t out_channels, int32_t kernel_size, int32_t relu, float out_scale, int32_t B, int32_t H, int32_t W, float *d_out) {
-    return conv2d_entry("conv2d_device", ctx, stream, parts, n_parts, d_weights, d_bias, out_channels, kernel_size, 1, relu, out_scale, nullptr, 0, B, H, W,
-                        d_out);
+    return conv2d_entry("conv2d_device", ctx, stream, parts, n_parts, d_weights, d_bias, out_channels, kernel_size, 1, relu, out_scale, nullptr, 0, 0, B, H,
+                        W, d_out);
 }
 
 // encoder.py:7-13 with :16-22 (ResNetBlock: conv1 + bn1 + ReLU; shortcut + its BatchNorm; conv2 + bn2 + the add + ReLU), :30-31 and :46-47
@@ -231,7 +242,14 @@ int ftk_conv2d_strided_device(ftk_context *ctx, void *stream, const ftk_gru_part
                               int32_t out_channels, int32_t kernel_size, int32_t stride, int32_t relu, float out_scale, const float *d_residual,
                               int32_t normalise, int32_t B, int32_t H, int32_t W, float *d_out) {
     return conv2d_entry("conv2d_strided_device", ctx, stream, parts, n_parts, d_weights, d_bias, out_channels, kernel_size, stride, relu, out_scale,
-                        d_residual, normalise, B, H, W, d_out);
+                        d_residual, normalise, 0, B, H, W, d_out);
+}
+
+// SuperPoint's VGG: conv1b, conv2b and conv3b, each with the ReLU and the 2 x 2 max-pool after it
+int ftk_conv2d_pool_device(ftk_context *ctx, void *stream, const ftk_gru_part *parts, int32_t n_parts, const float *d_weights, const float *d_bias,
+                           int32_t out_channels, int32_t kernel_size, int32_t relu, int32_t B, int32_t H, int32_t W, float *d_out) {
+    return conv2d_entry("conv2d_pool_device", ctx, stream, parts, n_parts, d_weights, d_bias, out_channels, kernel_size, 1, relu, 1.0f, nullptr, 0, 1, B, H, W,
+                        d_out);
 }
 
 }  // extern "C"

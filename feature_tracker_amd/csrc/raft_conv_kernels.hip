@@ -31,6 +31,14 @@
 // float j + tx / 2 of plane tx % 2, lane j's bank is (base + j) % 32, 32 different banks.  Lanes 32-63 hold another tap and are
 // another half.  The strip of KS 3 is 2 (wn - 1) + 3 rows of 2 x 33 floats per channel (the 66th input column is never read); KS 1
 // reads even rows and columns only and stages just those, wn rows of 32.
+//
+// SuperPoint's VGG adds, behind POOL (default off: the instantiations above are the code they were), a 2 x 2 max-pool in
+// the epilogue of stride 1, KS 1 and 3: the output is [B][Cout][H / 2][W / 2] (floored: a last odd row or column is computed and dropped),
+// v = relu(acc) as above, pick(m, x) = (x > m || x != x) ? x : m, out = pick(pick(v00, v01), pick(v10, v11)); no out_scale.  x0 is a
+// multiple of 32, so a horizontal pair is lanes j, j ^ 1 of one wave (one cross-lane move per accumulator); the plan of this form makes
+// wn even (raft_conv_plan.h), so y0 is even and a vertical pair is waves wni, wni ^ 1 of one wmi: the wave of the odd row hands its 16
+// horizontally reduced accumulators of its even lanes to the wave of the even row through s_in, free after the loop's last barrier
+// (2 pairs x 16 x 32 floats), whose even lanes store.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -47,10 +55,14 @@ constexpr int kThreads = 64 * kGemmWaves;
 inline __device__ const ConvParams &conv_base(const ConvParams &p) { return p; }
 inline __device__ const ConvParams &conv_base(const ConvStridedParams &p) { return p.base; }
 
-template <int KS, bool RELU, int S = 1, bool EX = false, typename P = ConvParams>
+// torch's max-pool scan step: a NaN wins, and among equals (+-0 included) the one met first stays
+inline __device__ float pool_pick(float m, float x) { return (x > m || x != x) ? x : m; }
+
+template <int KS, bool RELU, int S = 1, bool EX = false, typename P = ConvParams, bool POOL = false>
 __global__ __launch_bounds__(kThreads) void conv2d_kernel(P launch, int wm, int tiles_x, int tiles_y, int chunks, int m_tiles) {
     static_assert(S == 1 || (S == 2 && KS != 7), "stride 2 is built for kernel sizes 1 and 3");
     static_assert(EX || S == 1, "the strided forms take the extended parameters");
+    static_assert(!POOL || (S == 1 && !EX && KS != 7), "the pooled form is stride 1, kernel sizes 1 and 3, plain parameters");
     const ConvParams &prm = conv_base(launch);
     constexpr int PAD = KS / 2;
     constexpr int CC = conv_chunk(KS);     // input channels of a chunk
@@ -199,6 +211,44 @@ __global__ __launch_bounds__(kThreads) void conv2d_kernel(P launch, int wm, int 
         }
     }
 
+    if constexpr (POOL) {
+        // the pooled epilogue: every wave meets the barrier; lanes j, j ^ 1 are columns 2 ox, 2 ox + 1, waves wni, wni ^ 1 rows 2 oy, 2 oy + 1
+        constexpr int kHandOff = 16 * 32;  // floats one odd-row wave hands on: 16 accumulators of its 32 even lanes (j even, both kh)
+        static_assert(2 * kHandOff <= CC * PITCH_MAX, "the hand-off of both row pairs fits the staging array");
+        const int slot = (wmi + wm * (wni >> 1)) * kHandOff + kh * 16 + (j >> 1);
+        float hv[16];
+        if (active) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                float v = acc[r];
+                if (RELU) {
+                    v = (v < 0.0f) ? 0.0f : v;
+                }
+                hv[r] = pool_pick(v, __shfl_xor(v, 1));  // an even lane: pick(v(y, 2 ox), v(y, 2 ox + 1)); an odd lane's is not used
+            }
+            if ((wni & 1) && !(j & 1)) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    s_in[slot + 32 * r] = hv[r];
+                }
+            }
+        }
+        __syncthreads();
+        const int PH = H >> 1, PW = W >> 1;
+        const int64_t oy = (y0 + wni) >> 1, ox = (x0 + j) >> 1;
+        if (!active || (wni & 1) || (j & 1) || oy >= PH || ox >= PW) {
+            return;
+        }
+        const int64_t PHW = (int64_t)PH * PW;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int co = m_tile * kGemmTile + (r & 3) + 8 * (r >> 2) + 4 * kh;
+            if (co < Cout) {
+                prm.out[(b * Cout + co) * PHW + oy * PW + ox] = pool_pick(hv[r], s_in[slot + 32 * r]);
+            }
+        }
+        return;
+    }
     // epilogue
     const int64_t py = y0 + wni;
     const int64_t px = x0 + j;
@@ -238,6 +288,21 @@ hipError_t launch_ks(const ConvPlan &plan, const ConvParams &p, int relu, hipStr
     return hipGetLastError();
 }
 
+template <int KS>
+hipError_t launch_pool(const ConvPlan &plan, const ConvParams &p, int relu, hipStream_t stream) {
+    if ((size_t)plan.chunk * plan.pitch > (size_t)conv_lds_floats(KS) || plan.chunk != conv_chunk(KS)) {
+        return hipErrorInvalidValue;
+    }
+    if (relu) {
+        hipLaunchKernelGGL((conv2d_kernel<KS, true, 1, false, ConvParams, true>), plan.grid, plan.block, 0, stream, p, plan.wm, plan.tiles_x, plan.tiles_y,
+                           plan.chunks, plan.m_tiles);
+    } else {
+        hipLaunchKernelGGL((conv2d_kernel<KS, false, 1, false, ConvParams, true>), plan.grid, plan.block, 0, stream, p, plan.wm, plan.tiles_x, plan.tiles_y,
+                           plan.chunks, plan.m_tiles);
+    }
+    return hipGetLastError();
+}
+
 template <int KS, int S>
 hipError_t launch_strided(const ConvPlan &plan, const ConvStridedParams &p, int relu, hipStream_t stream) {
     constexpr int kLds = S == 1 ? conv_lds_floats(KS) : conv_s2_lds_floats(KS);
@@ -257,8 +322,21 @@ hipError_t launch_strided(const ConvPlan &plan, const ConvStridedParams &p, int 
 
 }  // namespace
 
+hipError_t raft_conv_pool_launch(const ConvPlan &plan, const ConvParams &p, int kernel_size, int relu, hipStream_t stream) {
+    // the kernel pairs waves wni, wni ^ 1 and rows y0 + wni: wn must be even; the output is the plan's floored sizes
+    if (plan.refused != ConvRefusal::None || plan.block.x != (unsigned)kThreads || plan.wm * plan.wn != kGemmWaves || plan.pool != 1 || plan.stride != 1 ||
+        plan.wn % 2 != 0 || plan.out_h != p.H / 2 || plan.out_w != p.W / 2 || plan.out_h < 1 || plan.out_w < 1) {
+        return hipErrorInvalidValue;
+    }
+    switch (kernel_size) {
+    case 1: return launch_pool<1>(plan, p, relu, stream);
+    case 3: return launch_pool<3>(plan, p, relu, stream);
+    }
+    return hipErrorInvalidValue;
+}
+
 hipError_t raft_conv_strided_launch(const ConvPlan &plan, const ConvStridedParams &p, int kernel_size, int relu, hipStream_t stream) {
-    if (plan.refused != ConvRefusal::None || plan.block.x != (unsigned)kThreads || plan.wm * plan.wn != kGemmWaves) {
+    if (plan.refused != ConvRefusal::None || plan.block.x != (unsigned)kThreads || plan.wm * plan.wn != kGemmWaves || plan.pool != 0) {
         return hipErrorInvalidValue;
     }
     if (plan.stride == 1 && p.residual == nullptr && !p.normalise) {
@@ -275,7 +353,7 @@ hipError_t raft_conv_strided_launch(const ConvPlan &plan, const ConvStridedParam
 }
 
 hipError_t raft_conv_launch(const ConvPlan &plan, const ConvParams &p, int kernel_size, int relu, hipStream_t stream) {
-    if (plan.refused != ConvRefusal::None || plan.block.x != (unsigned)kThreads || plan.wm * plan.wn != kGemmWaves || plan.stride != 1) {
+    if (plan.refused != ConvRefusal::None || plan.block.x != (unsigned)kThreads || plan.wm * plan.wn != kGemmWaves || plan.stride != 1 || plan.pool != 0) {
         return hipErrorInvalidValue;
     }
     switch (kernel_size) {

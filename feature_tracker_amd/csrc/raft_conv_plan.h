@@ -35,15 +35,18 @@ struct ConvPlanInput {
     int32_t out_channels, in_channels, kernel_size;
     int32_t B, H, W;     // of the input
     int32_t stride = 1;  // 1 or 2 (2: kernel sizes 1 and 3); the output is ceil(H / stride) x ceil(W / stride)
+    int32_t pool = 0;    // 1: a 2 x 2 max-pool in the epilogue (stride 1, kernel sizes 1 and 3, H, W >= 2); the output is
+                         // floor(H / 2) x floor(W / 2).  0: every field of the plan is what it was without this member
 };
-enum class ConvRefusal { None, KernelSize, OutChannels, InChannels, Sizes, Grid, Stride };
+enum class ConvRefusal { None, KernelSize, OutChannels, InChannels, Sizes, Grid, Stride, Pool };
 struct ConvPlan {
     ConvRefusal refused;  // not None: nothing else is set
     int32_t m_tiles;      // 32-row tiles of the weight matrix
     int32_t wm, wn;       // wm * wn = kGemmWaves; a workgroup owns wm tiles of output channels and wn rows of 32 pixels
     int32_t m_groups;     // grid.y: ceil(m_tiles / wm)
     int32_t stride, out_h, out_w;  // the input's; the output's sizes, which the tiles partition
-    int32_t tile_w, tile_h;    // output pixels of a workgroup: 32 x wn
+    int32_t pool;              // the input's.  1: wm = min(m_tiles, 2), so wn and with it a workgroup's first row ty * wn are even
+    int32_t tile_w, tile_h;    // output pixels of a workgroup: 32 x wn (pool 1: convolution pixels, 16 x wn / 2 outputs)
     int32_t tiles_x, tiles_y;  // grid.x = tiles_x * tiles_y * B, x fastest
     int32_t chunk, chunks, steps_per_chunk, k_steps;  // conv_chunk; ceil(in_channels / chunk); conv_steps; chunks * steps_per_chunk
     int32_t pitch;        // LDS floats per staged channel: the strip and its halo on all four sides (rows * row)

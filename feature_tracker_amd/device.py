@@ -480,7 +480,7 @@ from ._device_flow_upsample import flow_upsample_device  # noqa: E402,F401  (RAF
 from ._device_flow_points import flow_track_points_device  # noqa: E402,F401  (sparse tracking from RAFT's coarse flow; its own file, see there)
 from ._device_flow_warm import flow_warm_device  # noqa: E402,F401  (the warm start of RAFT on video; its own file, see there)
 from ._device_sep_conv_gru import sep_conv_gru_device  # noqa: E402,F401  (RAFT's SepConvGru; its own file, see there)
-from ._device_raft_conv import conv2d_device, conv2d_strided_device  # noqa: E402,F401  (the stock layers of RAFT's UpdateBlock; its own file, see there)
+from ._device_raft_conv import channel_normalise_device, conv2d_device, conv2d_pool_device, conv2d_strided_device  # noqa: E402,F401  (the stock layers of RAFT's UpdateBlock and SuperPoint's; its own file, see there)
 from ._device_corr_ondemand import corr_ondemand_lookup_device, corr_ondemand_prepare_device  # noqa: E402,F401  (RAFT's on-demand correlation; its own file, see there)
 from ._device_klt_video import _check_bound, harris_detect_device, track_table_fill_device, track_table_retire_device  # noqa: E402,F401  (masked Harris detection and KltVideoTracker's table; its own file, see there)
 from ._device_epipolar import epipolar_ransac_device  # noqa: E402,F401  (two-view outlier rejection; its own file, see there)

@@ -1,6 +1,7 @@
 // raft_conv_plan_cli — prints the launch plan of conv2d_kernel (csrc/raft_conv_plan.h) without a device.  One case per line on stdin:
-//   out_channels in_channels kernel_size B H W [stride]
-// (a line of six fields is stride 1 and is answered with the fields of stride 1 alone; a seventh adds the strided plan's) one line of key=value pairs per case on stdout.  tests/test_update_block_cpu.py drives it.
+//   out_channels in_channels kernel_size B H W [stride [pool]]
+// (a line of six fields is stride 1 and is answered with the fields of stride 1 alone; a seventh adds the strided plan's; an eighth is the
+// pool flag of DESIGN.md 5.25 and adds pool=) one line of key=value pairs per case on stdout.  tests/test_update_block_cpu.py drives it.
 #include <cstdio>
 #include <iostream>
 #include <sstream>
@@ -19,10 +20,13 @@ int main() {
         long long seventh = 0;
         const bool strided = (bool)(line >> seventh);  // a failed read would store 0
         stride = strided ? seventh : 1;
+        long long eighth = 0;
+        const bool pooled = strided && (bool)(line >> eighth);
         ftk::ConvPlanInput in{};
         in.out_channels = (int32_t)v[0], in.in_channels = (int32_t)v[1], in.kernel_size = (int32_t)v[2];
         in.B = (int32_t)v[3], in.H = (int32_t)v[4], in.W = (int32_t)v[5];
         in.stride = (int32_t)stride;
+        in.pool = pooled ? (int32_t)eighth : 0;
         const ftk::ConvPlan p = ftk::raft_conv_plan(in);
         printf("refused=%s", ftk::conv_refusal_name(p.refused));
         if (p.refused == ftk::ConvRefusal::None) {
@@ -38,6 +42,9 @@ int main() {
                        p.strip_h, p.strip_w,
                        sizeof(float) * (p.stride == 1 ? (ks == 1 ? ftk::conv_lds_floats(1) : ks == 3 ? ftk::conv_lds_floats(3) : ftk::conv_lds_floats(7))
                                                       : (ks == 1 ? ftk::conv_s2_lds_floats(1) : ftk::conv_s2_lds_floats(3))));
+            }
+            if (pooled) {
+                printf(" pool=%d", p.pool);
             }
         }
         printf("\n");

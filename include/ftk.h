@@ -753,6 +753,30 @@ int ftk_conv2d_strided_device(ftk_context *ctx, void *stream, const ftk_gru_part
                               int32_t out_channels, int32_t kernel_size, int32_t stride, int32_t relu, float out_scale, const float *d_residual,
                               int32_t normalise, int32_t B, int32_t H, int32_t W, float *d_out);
 
+/* ---- SuperPoint's VGG and descriptor head --------------------------------------------------------------------- */
+
+/*
+ * ftk_conv2d_device's layer (kernel_size 1 or 3) with a 2 x 2 max-pool of stride 2 in its epilogue: SuperPoint's conv1b, conv2b and conv3b
+ * with the ReLU and the pool after them, in one launch that never stores the tensor before the pool.  d_out: [B][out_channels][H / 2][W / 2]
+ * (floored: a last odd row or column is computed and dropped, as by torch's max_pool2d(2, 2)).  Per output element, with acc the chain of
+ * ftk_conv2d_device: v = (acc < 0) ? +0 : acc if relu, else acc; pick(m, x) = (x > m || x != x) ? x : m; out = pick(pick(v00, v01),
+ * pick(v10, v11)) over the window's (row, column) offsets: torch's scan, a NaN propagates and among equal maxima (+-0 included) the first
+ * of (0,0), (0,1), (1,0), (1,1) wins.  There is no out_scale.  Packed weights, parts and limits as ftk_conv2d_device, and H, W >= 2
+ * (FTK_E_INVALID_ARGUMENT); kernel_size 7 is FTK_E_UNSUPPORTED; neither launches anything.  One launch on `stream`, no allocation, no
+ * synchronisation: capturable.
+ */
+int ftk_conv2d_pool_device(ftk_context *ctx, void *stream, const ftk_gru_part *parts, int32_t n_parts, const float *d_weights, const float *d_bias,
+                           int32_t out_channels, int32_t kernel_size, int32_t relu, int32_t B, int32_t H, int32_t W, float *d_out);
+/*
+ * The L2 normalisation of a dense descriptor map over its channels, with the change of layout ftk_keypoint_decode_device reads fastest:
+ * d_in [channels][cell_rows][cell_cols] to d_out [cell_rows][cell_cols][channels] (strides 1, cell_cols * channels, channels there).  Per
+ * cell: n2 = fmaf(x_c, x_c, n2) over ascending c from +0; den = fmaxf(sqrtf(n2), 1e-12f); y_c = x_c / den (torch's F.normalize(dim = 1)
+ * with this summation order; square root and division correctly rounded).  1 <= channels <= FTK_KEYPOINT_DECODE_MAX_CHANNELS,
+ * cell_rows, cell_cols >= 1 (FTK_E_INVALID_ARGUMENT).  d_out must not alias d_in.  One launch on `stream`, no allocation, no
+ * synchronisation: capturable.
+ */
+int ftk_channel_normalise_device(ftk_context *ctx, void *stream, const float *d_in, int32_t channels, int32_t cell_rows, int32_t cell_cols, float *d_out);
+
 /* ---- features sharded over the GPUs of one node ------------------------ */
 
 /*
