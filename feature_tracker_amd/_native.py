@@ -50,6 +50,9 @@ FTK_MATCH_ASSIGNMENT_MAX_DIM = 1024
 FTK_TRANSFORMER_MAX_ROWS = 4096
 FTK_TRANSFORMER_MAX_DIM = 1024
 FTK_TRANSFORMER_MAX_HEAD_DIM = 128
+# the adaptive pass (include/ftk.h)
+FTK_LIGHTGLUE_MAX_LAYERS = 64
+FTK_LIGHTGLUE_STATE_WORDS = 4  # live0, live1, stopped, stop_layer
 # SepConvGru (include/ftk.h): the supported sizes and the packed weight layout
 FTK_SEP_CONV_GRU_MAX_PARTS = 3
 FTK_SEP_CONV_GRU_MAX_H_CHANNELS = 1024
@@ -91,6 +94,8 @@ EXPORTS = [
     "ftk_keypoint_decode_workspace_bytes", "ftk_keypoint_decode_device",
     "ftk_match_assignment_workspace_bytes", "ftk_match_assignment_device",
     "ftk_transformer_layer_workspace_bytes", "ftk_attention_device", "ftk_linear_device", "ftk_transformer_layer_device",
+    "ftk_lightglue_adaptive_workspace_bytes", "ftk_transformer_layer_adaptive_device", "ftk_lightglue_confidence_device",
+    "ftk_lightglue_adapt_step_device", "ftk_lightglue_finish_device",
 ]
 UNIQUE_ID_BYTES = 128
 
@@ -284,6 +289,11 @@ def lib() -> C.CDLL:
     l.ftk_attention_device.argtypes = [vp, vp, vp, i32, vp, vp, i32, i32, i32, vp, f32, f32, vp]
     l.ftk_linear_device.argtypes = [vp, vp, vp, i32, i32, vp, vp, i32, vp]
     l.ftk_transformer_layer_device.argtypes = [vp, vp, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    l.ftk_lightglue_adaptive_workspace_bytes.argtypes = [i32, i32, i32, i32, i64p]
+    l.ftk_transformer_layer_adaptive_device.argtypes = [vp, vp, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+    l.ftk_lightglue_confidence_device.argtypes = [vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    l.ftk_lightglue_adapt_step_device.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, f32, f32, f32, i32] + [vp] * 15
+    l.ftk_lightglue_finish_device.argtypes = [vp, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp]
     _lib = l
     return l
 
@@ -388,6 +398,16 @@ def transformer_layer_workspace_bytes(rows0: int, rows1: int, dim: int, heads: i
     r = m + n
     up16 = lambda v: (v + 15) & ~15  # noqa: E731
     return up16(12 * r * d) + 3 * up16(4 * r * d) + up16(8 * r * d)
+
+
+def lightglue_adaptive_workspace_bytes(rows0: int, rows1: int, dim: int, heads: int = 4) -> int:
+    """Bytes of workspace the adaptive pass needs, the value ftk_lightglue_adaptive_workspace_bytes returns (pure Python;
+    csrc/lightglue_adaptive_plan.cpp): the layer's workspace, the assignment head's, the selected head [D + 1][D] and [D + 1], the gather
+    maps [M] and [N], and the matcher's index and status [M].  ValueError for a shape the library refuses."""
+    m, n, d = int(rows0), int(rows1), int(dim)
+    up16 = lambda v: (v + 15) & ~15  # noqa: E731
+    return (up16(transformer_layer_workspace_bytes(m, n, d, heads)) + up16(match_assignment_workspace_bytes(m, n, d, True)) + up16(4 * (d + 1) * d)
+            + up16(4 * (d + 1)) + 2 * up16(4 * m) + up16(4 * n) + up16(m))
 
 
 def transformer_layer_weight_offsets(dim: int):

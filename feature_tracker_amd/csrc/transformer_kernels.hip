@@ -26,6 +26,13 @@ static_assert(kLinearTileCols == 32 * kColTiles && kAttnKeyTile == 32 * kColTile
 
 constexpr float kSqrtHalf = 0x1.6a09e6p-1f;  // (float)M_SQRT1_2
 
+// Whether any of the rows [begin, end) of the two sets laid one behind the other (the second from rows0) is in front of its set's
+// live count.
+__device__ __forceinline__ bool any_live_row(int begin, int end, int rows0, int live0, int live1) {
+    const int begin1 = (begin > rows0 ? begin : rows0) - rows0;
+    return begin < live0 || (end > rows0 && begin1 < live1);
+}
+
 template <bool kVec>
 __global__ void __launch_bounds__(64 * kLinearWaves) linear_kernel(const LinearParams p) {
     const int lane = threadIdx.x & 63, j = lane & 31, kh = lane >> 5;
@@ -33,6 +40,11 @@ __global__ void __launch_bounds__(64 * kLinearWaves) linear_kernel(const LinearP
     const int r0 = (blockIdx.x * kLinearWaves + (threadIdx.x >> 6)) * 32;  // wave-uniform
     if (r0 >= rows) {
         return;
+    }
+    if (p.gate) {  // the adaptive pass: a stopped layer, or 32 rows that are all pruned (wave-uniform; this kernel has no barrier)
+        if (p.gate[0] != 0 || !any_live_row(r0, r0 + 32 < rows ? r0 + 32 : rows, rows0, valid_count(p.live0, rows0), valid_count(p.live1, rows - rows0))) {
+            return;
+        }
     }
     const int o0 = blockIdx.y * kLinearTileCols;
     const bool rotary = p.epilogue == kLinearRotary;
@@ -133,6 +145,11 @@ __global__ void __launch_bounds__(kAttnThreads) attention_kernel(const Attention
     const int i0 = blockIdx.x * 32;  // block-uniform, as all control flow below
     if (i0 >= rows_q) {
         return;
+    }
+    if (p.gate) {  // the adaptive pass: a stopped layer, or 32 queries that are all pruned (before the first load and the first barrier)
+        if (p.gate[0] != 0 || i0 >= valid_count(z ? p.prob[1].live_q : p.prob[0].live_q, rows_q)) {
+            return;
+        }
     }
     const float *q = z ? p.prob[1].q : p.prob[0].q, *k = z ? p.prob[1].k : p.prob[0].k, *v = z ? p.prob[1].v : p.prob[0].v;
     float *out = z ? p.prob[1].out : p.prob[0].out;
@@ -269,6 +286,12 @@ __global__ void __launch_bounds__(kAttnThreads) attention_kernel(const Attention
 
 __global__ void __launch_bounds__(kNormThreads) layernorm_gelu_kernel(const NormParams p) {
     const int lane = threadIdx.x, cols = p.cols;
+    if (p.gate) {  // the adaptive pass: a stopped layer or a pruned row
+        const int row = blockIdx.x;
+        if (p.gate[0] != 0 || !any_live_row(row, row + 1, p.rows0, valid_count(p.live0, p.rows0), valid_count(p.live1, p.n_rows - p.rows0))) {
+            return;
+        }
+    }
     float *x = p.rows + (size_t)blockIdx.x * cols;
     const float n = (float)cols;
     float s1 = 0.0f;

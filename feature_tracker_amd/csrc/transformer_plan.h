@@ -73,6 +73,9 @@ struct LinearParams {
     float *out0, *out1;        // rows below rows0, the others; plane o / plane_cols at plane_stride floats, plane_cols floats a row
     int32_t plane_cols;
     int64_t plane_stride;
+    // the adaptive pass, all null otherwise: a wave returns before its first load when *gate != 0 or when all of its
+    // rows lie at or behind their set's live count
+    const int32_t *gate, *live0, *live1;
 };
 // One launch on the plan's grid (grid_y: the 128-column tiles of p.outs).
 hipError_t linear_launch(const LinearParams &p, bool vec, uint32_t grid_x, uint32_t grid_y, hipStream_t stream);
@@ -83,11 +86,13 @@ struct AttentionProblem {
     float *out;                // [rows_q][dim]
     int32_t rows_q, rows_k;
     const int32_t *count;      // of the keys; device word or null
+    const int32_t *live_q;     // of the queries, read only with a gate; device word or null
 };
 struct AttentionParams {
     AttentionProblem prob[2];
     int32_t dim, head_dim;
     float pre, post;
+    const int32_t *gate;       // the adaptive pass or null: a workgroup returns when *gate != 0 or its queries lie at or behind live_q
 };
 hipError_t attention_launch(const TransformerPlan &plan, const AttentionParams &p, hipStream_t stream);
 
@@ -95,6 +100,8 @@ struct NormParams {
     float *rows;               // [n_rows][cols], in place
     int32_t n_rows, cols;
     const float *gamma, *beta;
+    const int32_t *gate, *live0, *live1;  // the adaptive pass or null, as LinearParams'; rows below rows0 belong to the first set
+    int32_t rows0;
 };
 hipError_t layernorm_gelu_launch(const NormParams &p, uint32_t blocks, hipStream_t stream);
 

@@ -10,6 +10,8 @@ from __future__ import annotations
 import math
 
 from . import _native as N
+from ._device_lightglue_adaptive import (check_confidence, check_min_keypoints, lightglue_adapt_step_args, lightglue_confidence_args,
+                                         lightglue_finish_args, stop_threshold, transformer_layer_adaptive_args)
 from ._device_transformer import attention_args, check_heads, check_rows, linear_args, transformer_layer_args
 
 _SELF = ("self_attn.Wqkv", "self_attn.out_proj", "self_attn.ffn.0", "self_attn.ffn.1", "self_attn.ffn.3")
@@ -233,12 +235,18 @@ class LightGlue:
 
     ``kpts0`` [M, 2], ``kpts1`` [N, 2]: float32 CUDA pixel coordinates; ``desc0`` [M, D_in], ``desc1`` [N, D_in]; ``size0`` / ``size1``:
     (width, height) of the images; ``count0`` / ``count1``: optional int32 [1] device tensors.  Everything runs on one stream and nothing
-    is read on the host; the layers share one workspace per (device, M, N).  Out of scope: early stopping (``token_confidence``), point pruning, a batch dimension, a C++ class, and the
-    SuperPoint network that produces the inputs."""
+    is read on the host; the layers share one workspace per (device, M, N).  ``match_adaptive`` is upstream's forward pass with
+    ``depth_confidence`` (early stopping) and ``width_confidence`` (point pruning), DESIGN.md 5.26.  Out of scope: a host-synchronising
+    mode that skips the launches of a stopped layer, a batch dimension, a C++ class."""
 
-    def __init__(self, layers, head, Wr, input_proj=None, ctx=None):
+    def __init__(self, layers, head, Wr, input_proj=None, ctx=None, adaptive=None):
         _check_ctx(ctx)
         self.layers, self.head, self.Wr, self.input_proj, self._ctx = list(layers), head, Wr, input_proj, ctx
+        # (depth_confidence, width_confidence, pruning_min_keypoints, token_w [L, D], token_b [L], head_w [L, D + 1, D], head_b [L, D + 1])
+        self._adaptive = adaptive
+        self._adaptive_moved = {}
+        self._adaptive_buffers = {}  # (device, M, N) -> the pass's buffers
+        self._adaptive_sizes = {}    # (device, width, height) -> the image size on the device
         self.dim, self.num_heads = self.layers[0].dim, self.layers[0].num_heads
         self._moved = {}
         # the layers run one after another on one stream: one workspace per (device, M, N) serves them all
@@ -247,12 +255,19 @@ class LightGlue:
             layer._workspace = self._workspace
 
     @classmethod
-    def from_state_dict(cls, sd, num_heads: int = 4, n_layers=None, ctx=None) -> "LightGlue":
+    def from_state_dict(cls, sd, num_heads: int = 4, n_layers=None, ctx=None, depth_confidence=-1, width_confidence=-1,
+                        pruning_min_keypoints: int = 1024) -> "LightGlue":
         """Upstream's state dict: ``posenc.Wr.weight``, ``transformers.{i}.*``, ``log_assignment.{n_layers - 1}.*`` and, where the input
-        dimension differs, ``input_proj.{weight, bias}``.  ``n_layers`` None: every layer the state dict holds."""
+        dimension differs, ``input_proj.{weight, bias}``.  ``n_layers`` None: every layer the state dict holds.  With
+        ``depth_confidence`` or ``width_confidence`` > 0 (upstream: 0.95 and 0.99; ``pruning_min_keypoints``: upstream's CUDA default)
+        also ``token_confidence.{i}.token.0.{weight, bias}`` and ``log_assignment.{i}.*`` of every layer, for ``match_adaptive``."""
         import torch
 
         from .match_assignment import MatchAssignment
+
+        depth = check_confidence("depth_confidence", depth_confidence)
+        width = check_confidence("width_confidence", width_confidence)
+        check_min_keypoints(pruning_min_keypoints)
 
         if n_layers is None:
             n_layers = 0
@@ -277,7 +292,30 @@ class LightGlue:
                 raise ValueError(f"input_proj.weight must be [{layers[0].dim}, 1 .. {N.FTK_TRANSFORMER_MAX_DIM}] (got {list(w.shape)})")
             _shaped("input_proj.bias", b, (layers[0].dim,))
             input_proj = (w.contiguous(), b.contiguous())
-        return cls(layers, head, Wr.detach(), input_proj, ctx)
+        adaptive = None
+        if depth > 0 or width > 0:
+            if n_layers > N.FTK_LIGHTGLUE_MAX_LAYERS:
+                raise ValueError(f"the adaptive pass takes at most FTK_LIGHTGLUE_MAX_LAYERS = {N.FTK_LIGHTGLUE_MAX_LAYERS} layers (got {n_layers})")
+            d = layers[0].dim
+            wanted = [f"token_confidence.{i}.token.0.{part}" for i in range(n_layers - 1) for part in ("weight", "bias")]
+            wanted += [f"log_assignment.{i}.{k}" for i in range(n_layers) for k in ("final_proj.weight", "final_proj.bias", "matchability.weight",
+                                                                                     "matchability.bias")]
+            missing = [k for k in wanted if k not in sd]
+            if missing:
+                raise ValueError(f"depth_confidence / width_confidence need tensors the state dict lacks: {missing}")
+            device = head._packed[next(iter(head._packed))][0].device
+            token_w, token_b = torch.zeros((n_layers, d), dtype=torch.float32, device=device), torch.zeros((n_layers,), dtype=torch.float32, device=device)
+            for i in range(n_layers - 1):
+                w, b = _linear_pair(sd, f"token_confidence.{i}.token.0")
+                token_w[i] = _shaped(f"token_confidence.{i}.token.0.weight", w, (1, d)).to(device)[0]
+                token_b[i] = _shaped(f"token_confidence.{i}.token.0.bias", b, (1,)).to(device)[0]
+            heads = [MatchAssignment.from_state_dict(sd, f"log_assignment.{i}.", ctx) for i in range(n_layers)]
+            if any(h.dim != d for h in heads):
+                raise ValueError("the layers and every assignment head must share one D")
+            head_w = torch.stack([next(iter(h._packed.values()))[0].to(device) for h in heads]).contiguous()
+            head_b = torch.stack([next(iter(h._packed.values()))[1].to(device) for h in heads]).contiguous()
+            adaptive = (depth, width, pruning_min_keypoints, token_w, token_b, head_w, head_b)
+        return cls(layers, head, Wr.detach(), input_proj, ctx, adaptive)
 
     def _validate(self, kpts0, kpts1, desc0, desc1, size0, size1, count0, count1, min_score=None):
         from . import device as D
@@ -299,7 +337,8 @@ class LightGlue:
         _complain(tensors)
         return m, n
 
-    def _descriptors(self, on, kpts0, kpts1, desc0, desc1, size0, size1, count0, count1, m, n):
+    def _inputs(self, on, kpts0, kpts1, desc0, desc1, size0, size1):
+        """The projected descriptors and the rotary encodings: what the first layer reads."""
         torch, device = on.torch, desc0.device
         if device not in self._moved:
             proj = None if self.input_proj is None else tuple(t.to(device) for t in self.input_proj)
@@ -314,7 +353,10 @@ class LightGlue:
                     N.check(rc, on.ctx.handle)
                 projected.append(out)
             desc0, desc1 = projected
-        enc0, enc1 = rotary_encoding(kpts0, size0, Wr), rotary_encoding(kpts1, size1, Wr)
+        return desc0, desc1, rotary_encoding(kpts0, size0, Wr), rotary_encoding(kpts1, size1, Wr)
+
+    def _descriptors(self, on, kpts0, kpts1, desc0, desc1, size0, size1, count0, count1, m, n):
+        desc0, desc1, enc0, enc1 = self._inputs(on, kpts0, kpts1, desc0, desc1, size0, size1)
         for layer in self.layers:
             desc0, desc1 = layer._run(on, desc0, desc1, enc0, enc1, count0, count1, m, n)
         return desc0, desc1
@@ -334,3 +376,96 @@ class LightGlue:
             desc0, desc1 = self._descriptors(on, kpts0, kpts1, desc0, desc1, size0, size1, count0, count1, m, n)
             result = self.head.match(desc0, desc1, count0, count1, min_score=min_score)
         return result
+
+    # ---- the adaptive pass ----
+
+    def _adaptive_state(self, on, device, m, n):
+        """The packed heads on ``device`` and the pass's buffers of this size, made on the first call."""
+        torch = on.torch
+        if device not in self._adaptive_moved:
+            self._adaptive_moved[device] = tuple(t.to(device) for t in self._adaptive[3:])
+        key = (device, m, n)
+        b = self._adaptive_buffers.get(key)
+        if b is None:
+            dh, L = self.layers[0].head_dim, len(self.layers)
+            f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=device)  # noqa: E731
+            i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=device)  # noqa: E731
+            b = dict(halves=[(f32(m, self.dim), f32(n, self.dim), f32(2, m, dh), f32(2, n, dh), i32(m), i32(n)) for _ in range(2)],
+                     conf=f32(m + n), mt=f32(m + n), scores=f32(m + 1, n + 1), match_index=i32(m),
+                     status=torch.empty((m,), dtype=torch.uint8, device=device), state=i32(N.FTK_LIGHTGLUE_STATE_WORDS), layers=i32(m + n),
+                     identity=torch.arange(max(m, n), dtype=torch.int32, device=device),
+                     start=torch.tensor([m, n, 0, L - 1], dtype=torch.int32, device=device),
+                     workspace=torch.empty(-(-N.lightglue_adaptive_workspace_bytes(m, n, self.dim, self.num_heads) // 8), dtype=torch.int64, device=device))
+            self._adaptive_buffers[key] = b
+        return self._adaptive_moved[device], b
+
+    def match_adaptive(self, kpts0, kpts1, desc0, desc1, size0, size1, count0=None, count1=None, min_score: float = -1.0e30):
+        """Upstream's forward pass with early stopping and point pruning, entirely on the stream.  Returns an
+        ``AdaptiveMatches`` of device tensors: ``match_index`` int32 [M] and ``status`` uint8 [M] in original indices; ``scores``
+        float32 [M + 1, N + 1] in compacted layout, of which rows below ``live0`` [1] and columns below ``live1`` [1] are valid, row r
+        being original row ``ind0[r]`` and column c ``ind1[c]``; ``stop_layer`` int32 [1]; ``layers0`` [M] and ``layers1`` [N], the
+        number of layers each original row took part in.  Every returned tensor is a buffer kept per (device, M, N): a later
+        call of that size overwrites what an earlier one returned (clone what must outlive it).  Per call only the optional input
+        projection and the rotary encodings are allocated, as in ``match``.  Needs ``depth_confidence`` or ``width_confidence`` > 0 at ``from_state_dict``."""
+        if self._adaptive is None:
+            raise ValueError("match_adaptive needs LightGlue.from_state_dict(..., depth_confidence=..., width_confidence=...) with one of them > 0")
+        m, n = self._validate(kpts0, kpts1, desc0, desc1, size0, size1, count0, count1, min_score)
+        depth, width, min_keypoints = self._adaptive[:3]
+        L = len(self.layers)
+        with _OnStream(self._ctx, desc0) as on:
+            torch, device = on.torch, desc0.device
+            (token_w, token_b, head_w, head_b), b = self._adaptive_state(on, device, m, n)
+            # the image sizes as device tensors, made once: rotary_encoding then uploads nothing, and the pass can be captured
+            sizes = []
+            for size in (size0, size1):
+                size_key = (device, float(size[0]), float(size[1]))
+                if size_key not in self._adaptive_sizes:
+                    self._adaptive_sizes[size_key] = torch.as_tensor(size, dtype=torch.float32, device=device)
+                sizes.append(self._adaptive_sizes[size_key])
+            x0, x1, enc0, enc1 = self._inputs(on, kpts0, kpts1, desc0, desc1, sizes[0], sizes[1])
+            halves, state, layers, ws = b["halves"], b["state"], b["layers"], b["workspace"]
+            for dst, src in zip(halves[0], (x0, x1, enc0, enc1, b["identity"][:m], b["identity"][:n])):
+                dst.copy_(src)
+            state.copy_(b["start"])
+            if count0 is not None:
+                torch.clamp(count0, 0, m, out=state[0:1])
+            if count1 is not None:
+                torch.clamp(count1, 0, n, out=state[1:2])
+            layers.zero_()
+            live0, live1, gate = state[0:1], state[1:2], state[2:3]
+            layers0, layers1 = layers[:m], layers[m:]
+            lib, d = N.lib(), self.dim
+            for i, layer in enumerate(self.layers):
+                cur, nxt = halves[i % 2], halves[(i + 1) % 2]
+                if device not in layer._packed:
+                    layer._packed[device] = next(iter(layer._packed.values())).to(device)
+                rc = lib.ftk_transformer_layer_adaptive_device(*transformer_layer_adaptive_args(
+                    on.ctx, cur[0], cur[1], self.num_heads, cur[2], cur[3], layer._packed[device], live0, live1, gate, ws, on.stream))
+                if rc == 0 and i < L - 1:
+                    rc = lib.ftk_lightglue_confidence_device(*lightglue_confidence_args(
+                        on.ctx, cur[0], cur[1], token_w[i], token_b[i:i + 1], head_w[i, d], head_b[i, d:d + 1], live0, live1, gate, b["conf"], b["mt"],
+                        on.stream))
+                if rc == 0 and i < L - 1:
+                    rc = lib.ftk_lightglue_adapt_step_device(*lightglue_adapt_step_args(
+                        on.ctx, self.num_heads, i, b["conf"], b["mt"], count0, count1, state, stop_threshold(i, L), depth, width, min_keypoints, cur, nxt,
+                        layers0, layers1, ws, on.stream))
+                if rc != 0:
+                    N.check(rc, on.ctx.handle)
+            last = halves[(L - 1) % 2]
+            scores, match_index, status = b["scores"], b["match_index"], b["status"]
+            rc = lib.ftk_lightglue_finish_device(*lightglue_finish_args(
+                on.ctx, last[0], last[1], self.num_heads, head_w, head_b, state, last[4], last[5], float(min_score), ws, scores, match_index, status,
+                layers0, layers1, on.stream))
+            if rc != 0:
+                N.check(rc, on.ctx.handle)
+        return AdaptiveMatches(match_index, status, scores, last[4], last[5], live0, live1, state[3:4], layers0, layers1)
+
+
+class AdaptiveMatches:
+    """What ``LightGlue.match_adaptive`` returns; every field is a device tensor (see there)."""
+
+    __slots__ = ("match_index", "status", "scores", "ind0", "ind1", "live0", "live1", "stop_layer", "layers0", "layers1")
+
+    def __init__(self, *fields):
+        for name, value in zip(self.__slots__, fields):
+            setattr(self, name, value)

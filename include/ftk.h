@@ -438,6 +438,48 @@ int ftk_transformer_layer_device(ftk_context *ctx, void *stream, const float *d_
                                  int32_t heads, const float *d_enc0, const float *d_enc1, const float *d_weights, const int32_t *d_count0,
                                  const int32_t *d_count1, void *d_workspace, float *d_out0, float *d_out1);
 
+/*
+ * LightGlue's adaptive depth and width (LightGlue.match_adaptive): the steps that stop the network once enough points
+ * are confident and that remove points which are confidently unmatchable, all in device memory.  A pass owns two halves of a
+ * ping-pong pair of descriptors [rows][dim], rotary encodings [2][rows][dh] and index maps int32 [rows] per side, conf and mt
+ * float32 [rows0 + rows1], layers int32 [rows] per side (zeroed by the caller) and d_state, int32 [FTK_LIGHTGLUE_STATE_WORDS]:
+ * the live counts of both sides, the sticky stop flag, the stop layer (initialised by the caller to clamp(count), 0, L - 1).
+ *   ftk_transformer_layer_adaptive_device: ftk_transformer_layer_device in place on d_desc0 / d_desc1, with the live counts (required)
+ *   as the counts; every workgroup returns before its first load when *d_gate != 0 or when all of its rows lie at or behind their
+ *   set's live count.  Rows at or behind the live count are unspecified afterwards.
+ *   ftk_lightglue_confidence_device: conf = sigmoid_c(token(x)) and mt = sigmoid_c(matchability(x)) of every live row, each the fmaf
+ *   chain over the columns ascending from its bias (d_live0 / d_live1 / d_gate may be NULL: all rows, never gated).  1 launch.
+ *   ftk_lightglue_adapt_step_device: layer i's stop test and pruning (5.26 steps 3 and 4), then the stable gather of the kept rows of
+ *   the `in` half to the front of the `out` half (the identity when stopped or not pruning).  d_count0 / d_count1: the pass's input
+ *   counts or NULL.  threshold: t_i; depth_confidence / width_confidence <= 0: off.  2 launches.
+ *   ftk_lightglue_finish_device: selects log_assignment.{stop layer} out of d_head_w [L][dim + 1][dim] and d_head_b [L][dim + 1], runs
+ *   ftk_match_assignment_device and ftk_nn_match_scores_device on the compacted sets with the live counts (d_scores: [rows0 + 1][rows1
+ *   + 1], compacted layout) and maps the result back: d_match_index [rows0] and d_status [rows0] in original indices, -1 and
+ *   FTK_STATUS_LARGE_RESIDUAL for every row without a match; d_layers0 / d_layers1 receive stop layer + 1 for the rows that stayed.
+ * d_workspace: ftk_lightglue_adaptive_workspace_bytes(rows0, rows1, dim, heads) bytes, 16-byte aligned, no initialisation needed; it
+ * contains the layer's and the head's workspaces.  Limits: ftk_transformer_layer_device's, and at most FTK_LIGHTGLUE_MAX_LAYERS
+ * layers.  Everything is refused before any launch; launches of fixed shape on `stream`; no host read, no synchronisation.
+ */
+#define FTK_LIGHTGLUE_MAX_LAYERS 64
+#define FTK_LIGHTGLUE_STATE_WORDS 4
+int ftk_lightglue_adaptive_workspace_bytes(int32_t rows0, int32_t rows1, int32_t dim, int32_t heads, int64_t *bytes);
+int ftk_transformer_layer_adaptive_device(ftk_context *ctx, void *stream, float *d_desc0, int32_t rows0, float *d_desc1, int32_t rows1, int32_t dim,
+                                          int32_t heads, const float *d_enc0, const float *d_enc1, const float *d_weights, const int32_t *d_live0,
+                                          const int32_t *d_live1, const int32_t *d_gate, void *d_workspace);
+int ftk_lightglue_confidence_device(ftk_context *ctx, void *stream, const float *d_desc0, int32_t rows0, const float *d_desc1, int32_t rows1, int32_t dim,
+                                    const float *d_token_w, const float *d_token_b, const float *d_match_w, const float *d_match_b,
+                                    const int32_t *d_live0, const int32_t *d_live1, const int32_t *d_gate, float *d_conf, float *d_mt);
+int ftk_lightglue_adapt_step_device(ftk_context *ctx, void *stream, int32_t rows0, int32_t rows1, int32_t dim, int32_t heads, int32_t layer,
+                                    const float *d_conf, const float *d_mt, const int32_t *d_count0, const int32_t *d_count1, int32_t *d_state,
+                                    float threshold, float depth_confidence, float width_confidence, int32_t min_keypoints, const float *d_desc_in0,
+                                    const float *d_desc_in1, const float *d_enc_in0, const float *d_enc_in1, const int32_t *d_ind_in0,
+                                    const int32_t *d_ind_in1, float *d_desc_out0, float *d_desc_out1, float *d_enc_out0, float *d_enc_out1,
+                                    int32_t *d_ind_out0, int32_t *d_ind_out1, int32_t *d_layers0, int32_t *d_layers1, void *d_workspace);
+int ftk_lightglue_finish_device(ftk_context *ctx, void *stream, const float *d_desc0, int32_t rows0, const float *d_desc1, int32_t rows1, int32_t dim,
+                                int32_t heads, int32_t n_layers, const float *d_head_w, const float *d_head_b, const int32_t *d_state,
+                                const int32_t *d_ind0, const int32_t *d_ind1, float min_score, void *d_workspace, float *d_scores,
+                                int32_t *d_match_index, uint8_t *d_status, int32_t *d_layers0, int32_t *d_layers1);
+
 /* ---- diagnostics ---------------------------------------------------------------------------- */
 
 /*

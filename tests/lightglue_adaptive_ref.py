@@ -1,0 +1,209 @@
+"""ctypes binding of tests/lightglue_adaptive_ref.c — the scalar CPU restatement of LightGlue's adaptive depth and width
+— with the steered weights and inputs the CPU and GPU tests share.  The C file composes tests/transformer_ref.c's and
+tests/match_assignment_ref.c's functions, which this binding hands in as function pointers taken from their own bindings.
+
+TEST INFRASTRUCTURE ONLY: compiled on first use (gcc -O3 -ffp-contract=off) into a temporary directory; nothing under
+feature_tracker_amd/ may import it, and it imports nothing from there.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import functools
+import math
+import os
+import subprocess
+import tempfile
+from types import SimpleNamespace
+
+import numpy as np
+
+from tests import match_assignment_ref as MA
+from tests import nn_match_ref
+from tests import transformer_ref as T
+
+_SRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lightglue_adaptive_ref.c")
+_lib = None
+_tmpdir = None
+
+CONTRACT = 0
+MUTANTS = {"stop_ratio_over_the_live_count": 1, "keep_rule_with_less_than": 2, "pruning_at_the_stopping_layer": 3, "last_head_after_an_early_stop": 4,
+           "unstable_compaction": 5, "indices_left_in_compacted_space": 6}
+UNMATCHED = 2
+_HEAD = ("final_proj.weight", "final_proj.bias", "matchability.weight", "matchability.bias")
+
+
+def lib():
+    global _lib, _tmpdir
+    if _lib is None:
+        _tmpdir = tempfile.TemporaryDirectory(prefix="lightglue_adaptive_ref_")
+        path = os.path.join(_tmpdir.name, "liblightglue_adaptive_ref.so")
+        flags = ["-O3", "-std=c99", "-ffp-contract=off", "-fno-fast-math"]
+        subprocess.run(["gcc"] + flags + ["-shared", "-fPIC", "-o", path, _SRC, "-lm"], check=True, capture_output=True)
+        l = C.CDLL(path)
+        vp, i32, f32 = C.c_void_p, C.c_int32, C.c_float
+        l.lga_sigmoid_c.argtypes = [vp, f32]
+        l.lga_sigmoid_c.restype = f32
+        l.lga_confidence.argtypes = [vp, vp, i32, i32, vp, f32, vp]
+        l.lga_confidence.restype = None
+        l.lga_pass.argtypes = [vp, vp, vp, vp, i32, vp, i32, i32, i32, vp, vp, i32, vp, C.c_int64, vp, vp, vp, vp, vp, f32, f32, i32, vp, vp, i32] + [vp] * 8
+        l.lga_pass.restype = i32
+        l.lga_remap.argtypes = [vp, vp, i32, i32, i32, vp, vp, i32, vp, vp]
+        l.lga_remap.restype = None
+        _lib = l
+    return _lib
+
+
+def _fn(function):
+    return C.cast(function, C.c_void_p)
+
+
+def _p(a):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _word(c):
+    return None if c is None else np.array([c], np.int32)
+
+
+def thresholds(n_layers: int) -> np.ndarray:
+    """t_i = (float)clip(0.8 + 0.1 exp(-4 i / L), 0, 1), in float64."""
+    return np.array([min(max(0.8 + 0.1 * math.exp(-4.0 * i / n_layers), 0.0), 1.0) for i in range(n_layers)], np.float64).astype(np.float32)
+
+
+def confidence(x, w, bias) -> np.ndarray:
+    """sigmoid_c of the fmaf chain from ``bias`` over the columns of each row of ``x`` with ``w``."""
+    x, w = np.ascontiguousarray(x, np.float32), np.ascontiguousarray(w, np.float32).ravel()
+    out = np.empty(x.shape[0], np.float32)
+    lib().lga_confidence(_fn(T.lib().tr_exp_c), _p(x), x.shape[0], x.shape[1], _p(w), float(np.float32(bias)), _p(out))
+    return out
+
+
+def sigmoid_c(z) -> np.float32:
+    return np.float32(lib().lga_sigmoid_c(_fn(T.lib().tr_exp_c), float(np.float32(z))))
+
+
+def bias_hitting(t) -> float:
+    """A float32 z with sigmoid_c(z) == t exactly, found among the floats next to logit(t) (the sigmoid's values there lie closer
+    together than float32's, so every float32 near t is some z's)."""
+    t = np.float32(t)
+    z = np.float32(math.log(float(t) / (1.0 - float(t))))
+    for _ in range(400):
+        z = np.nextafter(z, np.float32(-100))
+    for _ in range(800):
+        if sigmoid_c(z) == t:
+            return float(z)
+        z = np.nextafter(z, np.float32(100))
+    raise AssertionError(f"no float32 z with sigmoid_c(z) == {t}")
+
+
+def packed_heads(sd, n_layers):
+    packs = [MA.pack(*(sd[f"log_assignment.{i}.{k}"] for k in _HEAD)) for i in range(n_layers)]
+    return np.ascontiguousarray(np.stack([p[0] for p in packs])), np.ascontiguousarray(np.stack([p[1] for p in packs]))
+
+
+def run(desc0, desc1, heads, enc0, enc1, sd, n_layers, depth, width, min_keypoints=0, count0=None, count1=None, min_score=-1.0e30, variant=CONTRACT):
+    """The whole pass: a namespace of match_index, status, scores (compacted), ind0, ind1, live0, live1, stopped, stop_layer, layers0,
+    layers1, conf and mt ([L, M + N], NaN where step 2 did not run), desc0 and desc1 (the final descriptors, live rows valid)."""
+    d0, d1 = np.array(desc0, np.float32, copy=True, order="C"), np.array(desc1, np.float32, copy=True, order="C")
+    e0, e1 = np.array(enc0, np.float32, copy=True, order="C"), np.array(enc1, np.float32, copy=True, order="C")
+    (m, d), n, L = d0.shape, d1.shape[0], n_layers
+    layer_w = np.ascontiguousarray(np.stack([T.flat_weights(sd, f"transformers.{i}.") for i in range(L)]))
+    token_w, token_b = np.zeros((L, d), np.float32), np.zeros(L, np.float32)
+    for i in range(L - 1):
+        token_w[i], token_b[i] = sd[f"token_confidence.{i}.token.0.weight"].reshape(d), sd[f"token_confidence.{i}.token.0.bias"].reshape(())
+    head_w, head_b = packed_heads(sd, L)
+    th = thresholds(L)
+    ind0, ind1, state = np.empty(m, np.int32), np.empty(n, np.int32), np.empty(4, np.int32)
+    layers0, layers1 = np.empty(m, np.int32), np.empty(n, np.int32)
+    conf, mt = np.full((L, m + n), np.nan, np.float32), np.full((L, m + n), np.nan, np.float32)
+    scores = np.empty((m + 1, n + 1), np.float32)
+    w0, w1 = _word(count0), _word(count1)
+    in_pass = variant if variant in (1, 2, 3, 4, 5) else 0
+    rc = lib().lga_pass(_fn(T.lib().tr_exp_c), _fn(T.lib().tr_layer), _fn(MA.lib().mar_assign), _p(d0), m, _p(d1), n, d, heads, _p(e0), _p(e1), L, _p(layer_w),
+                        layer_w.shape[1], _p(token_w), _p(token_b), _p(head_w), _p(head_b), _p(th), float(np.float32(depth)), float(np.float32(width)),
+                        int(min_keypoints), _p(w0), _p(w1), in_pass, _p(ind0), _p(ind1), _p(state), _p(layers0), _p(layers1), _p(conf), _p(mt), _p(scores))
+    assert rc == 0
+    live0, live1 = int(state[0]), int(state[1])
+    m_c, st_c = nn_match_ref.match_scores(scores[:m, :n], min_score)
+    match_index, status = np.empty(m, np.int32), np.empty(m, np.uint8)
+    lib().lga_remap(_p(m_c), _p(st_c), m, live0, live1, _p(ind0), _p(ind1), 6 if variant == 6 else 0, _p(match_index), _p(status))
+    return SimpleNamespace(match_index=match_index, status=status, scores=scores, ind0=ind0, ind1=ind1, live0=live0, live1=live1, stopped=int(state[2]),
+                           stop_layer=int(state[3]), layers0=layers0, layers1=layers1, conf=conf, mt=mt, desc0=d0, desc1=d1)
+
+
+def outputs(r):
+    """What a comparison of two runs looks at: every specified output (the compacted arrays only in front of the live counts)."""
+    return (r.match_index, r.status, r.scores[:r.live0, :r.live1], r.scores[:r.live0, -1], r.scores[-1, :r.live1], r.ind0[:r.live0], r.ind1[:r.live1],
+            np.array([r.live0, r.live1, r.stop_layer]), r.layers0, r.layers1)
+
+
+def same_outputs(a, b) -> bool:
+    return all(x.shape == y.shape and (T.same(x, y) if x.dtype == np.float32 else np.array_equal(x, y)) for x, y in zip(outputs(a), outputs(b)))
+
+
+# ---- inputs --------------------------------------------------------------------------------------------------------------------------
+
+N_LAYERS = 3
+
+
+@functools.lru_cache(maxsize=None)
+def state_dict(d, heads, seed, token_bias=(0.0, 0.0), match_bias=(0.0, 0.0), token_scale=1.0, match_scale=1.0, n_layers=N_LAYERS):
+    """``transformer_ref.state_dict`` with ``token_confidence.{i}`` and ``log_assignment.{i}`` of every layer: seeded weights times the
+    scales, and the biases the tests steer the pass with (per layer in front of the last)."""
+    rng = np.random.default_rng(seed + 77)
+    sd = dict(T.state_dict(d, heads, n_layers, seed))
+    for i in range(n_layers):
+        head = f"log_assignment.{i}."
+        if i < n_layers - 1:
+            sd[head + "final_proj.weight"] = (np.eye(d) + rng.standard_normal((d, d)) / np.sqrt(d) * 0.5).astype(np.float32)
+            sd[head + "final_proj.bias"] = (0.1 * rng.standard_normal(d)).astype(np.float32)
+            sd[head + "matchability.weight"] = (match_scale * rng.standard_normal((1, d)) / np.sqrt(d)).astype(np.float32)
+            sd[head + "matchability.bias"] = np.array([match_bias[i]], np.float32)
+            sd[f"token_confidence.{i}.token.0.weight"] = (token_scale * rng.standard_normal((1, d)) / np.sqrt(d)).astype(np.float32)
+            sd[f"token_confidence.{i}.token.0.bias"] = np.array([token_bias[i]], np.float32)
+    for v in sd.values():
+        v.setflags(write=False)
+    return sd
+
+
+def case(shape, **steer):
+    """(desc0, desc1, enc0, enc1, sd) of (M, N, D, h, seed)."""
+    m, n, d, h, seed = shape
+    sd = state_dict(d, h, seed + 1000, **steer)
+    a, b, kp0, kp1, size = T.inputs(m, n, d, h, seed)
+    return a, b, T.encoding(kp0, size, sd["posenc.Wr.weight"]), T.encoding(kp1, size, sd["posenc.Wr.weight"]), sd
+
+
+# (M, N, D, h, seed): the shapes of the GPU tests
+SHAPES = ((1, 1, 4, 2, 301), (33, 31, 8, 2, 302), (65, 130, 64, 4, 303), (130, 65, 256, 4, 304), (40, 70, 18, 3, 305))
+# how the tests steer the pass: keyword arguments of state_dict, then (depth_confidence, width_confidence)
+STOP_AT_0 = (dict(token_bias=(30.0, 30.0)), 0.95, -1)
+STOP_AT_1 = (dict(token_bias=(-30.0, 30.0)), 0.95, -1)
+NEVER = (dict(token_bias=(-30.0, -30.0)), 0.95, 0.99)   # unsure tokens: no stop, and every row is kept
+DEPTH_ONLY = (dict(token_bias=(-30.0, 30.0)), 0.95, -1)
+STEER_SCALE = 24.0
+
+
+@functools.lru_cache(maxsize=None)
+def _medians(shape):
+    """The medians over all rows of the two heads' z after layers 0 and 1 of a pass that neither stops nor prunes, with the weights
+    at scale 1 and no bias (z = logit of the traced values, in float64: this only steers)."""
+    a, b, e0, e1, sd = case(shape)
+    r = run(a, b, shape[3], e0, e1, sd, N_LAYERS, -1, -1)
+    logit = lambda p: np.log(p.astype(np.float64)) - np.log1p(-p.astype(np.float64))  # noqa: E731
+    return (tuple(float(np.median(logit(r.conf[i]))) for i in range(2)), tuple(float(np.median(logit(r.mt[i]))) for i in range(2)))
+
+
+def split_steer(shape, token=True):
+    """state_dict arguments that put about half of the rows on either side of each threshold: the heads' weights times STEER_SCALE and
+    biases that move the median z to logit(t_i) = 1.7 (token) and logit(0.1) = -2.2 (matchability)."""
+    zt, zm = _medians(shape)
+    steer = dict(match_scale=STEER_SCALE, match_bias=tuple(round(-2.2 - STEER_SCALE * z, 3) for z in zm))
+    if token:
+        steer.update(token_scale=STEER_SCALE, token_bias=tuple(round(1.7 - STEER_SCALE * z, 3) for z in zt))
+    return steer
+
+
+def prune_case(shape, depth_on=True):
+    """(case, depth_confidence, width_confidence) of a pass that prunes some rows of each side at each step and never stops."""
+    return case(shape, **split_steer(shape, depth_on)), (0.9999 if depth_on else -1), 0.9
