@@ -10,6 +10,7 @@ from __future__ import annotations
 import ctypes as C
 
 from . import _native as N
+from ._torch_call import stream_or_current
 
 
 def corr_ondemand_prepare_device(ctx, fmap0, fmap1, levels: int, workspace, stream=None) -> None:
@@ -18,7 +19,7 @@ def corr_ondemand_prepare_device(ctx, fmap0, fmap1, levels: int, workspace, stre
     torch.cuda.Stream; default: torch's current stream).  No synchronisation, no allocation: capturable."""
     from . import device as D
 
-    torch = D._torch()
+    D._torch()  # (no HIP device: that refusal comes first)
     D._corr_check("fmap0", fmap0, 4)
     D._corr_check("fmap1", fmap1, 4)
     if tuple(fmap0.shape) != tuple(fmap1.shape) or fmap0.device != fmap1.device:
@@ -28,7 +29,7 @@ def corr_ondemand_prepare_device(ctx, fmap0, fmap1, levels: int, workspace, stre
     D._corr_check("workspace", workspace, workspace.dim())
     if workspace.numel() != elements or workspace.device != fmap0.device:
         raise ValueError(f"workspace must hold {elements} floats on {fmap0.device} (got {workspace.numel()} on {workspace.device})")
-    s = torch.cuda.current_stream(fmap0.device) if stream is None else stream
+    s = stream_or_current(fmap0, stream)
     rc = N.lib().ftk_corr_ondemand_prepare_device(ctx.handle, C.c_void_p(s.cuda_stream), C.c_void_p(fmap0.data_ptr()), C.c_void_p(fmap1.data_ptr()),
                                                   B, Cc, H, W, int(levels), C.c_void_p(workspace.data_ptr()))
     N.check(rc, ctx.handle)
@@ -41,7 +42,7 @@ def corr_ondemand_lookup_device(ctx, workspace, channels: int, levels: int, radi
     [B, H, W, K] blocks (K = (2r+1)^2)."""
     from . import device as D
 
-    torch = D._torch()
+    D._torch()  # (no HIP device: that refusal comes first)
     D._corr_check("coords", coords, 4)
     B, two, H, W = coords.shape
     if two != 2:
@@ -56,7 +57,7 @@ def corr_ondemand_lookup_device(ctx, workspace, channels: int, levels: int, radi
     D._corr_check("out", out, out.dim())
     if out.numel() != B * levels * K * H * W or out.device != coords.device:
         raise ValueError(f"out must hold {B * levels * K * H * W} floats on {coords.device}")
-    s = torch.cuda.current_stream(coords.device) if stream is None else stream
+    s = stream_or_current(coords, stream)
     rc = N.lib().ftk_corr_ondemand_lookup_device(ctx.handle, C.c_void_p(s.cuda_stream), C.c_void_p(workspace.data_ptr()), B, int(channels), H, W,
                                                  int(levels), int(radius), C.c_void_p(coords.data_ptr()), C.c_void_p(out.data_ptr()),
                                                  int(bool(per_level)))

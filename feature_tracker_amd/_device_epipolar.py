@@ -1,6 +1,6 @@
 """``device.epipolar_ransac_device``: the torch device entry of two-view outlier rejection (ftk_epipolar_ransac_device).
 
-It is re-exported by device.py and held to that module's rule: no ``data_ptr()`` of a tensor that did not pass ``device._check``.
+It is re-exported by device.py and held to that module's rule: no ``datapointer()`` of a tensor that did not pass ``device._check``.
 It lives in a file of its own because tests/test_device_args_cpu.py walks the entries DEFINED in device.py against a closed table;
 this entry's walk (the same recording stand-ins) and its refusals are tests/test_epipolar_args_cpu.py.
 """
@@ -9,6 +9,7 @@ from __future__ import annotations
 import ctypes as C
 
 from . import _native as N
+from ._torch_call import pointer, stream_or_current
 
 SEED_ARG = 10  # where the seed sits in the marshalled arguments (KltVideoTracker replaces it per frame)
 
@@ -32,10 +33,6 @@ def check_sizes(image_size, threshold, hypotheses, seed):
     return rows, cols, t, k, int(seed)
 
 
-def _ptr(x):
-    return None if x is None else C.c_void_p(x.data_ptr())
-
-
 def ransac_inputs(ctx, ref_uv, cur_uv, status, sizes, stream):
     """What the checks of ftk_epipolar_ransac_device and ftk_two_view_ransac_device share after ``sizes = check_sizes(...)``: the three input
     tensors, the limit of n and the choice of stream.  Returns (device.py, the device the other tensors must be on, n, hypotheses, the
@@ -50,8 +47,8 @@ def ransac_inputs(ctx, ref_uv, cur_uv, status, sizes, stream):
         raise ValueError(f"ref_uv must have 1 .. FTK_TRACK_TABLE_MAX_SLOTS = {N.FTK_TRACK_TABLE_MAX_SLOTS} points (got {n})")
     D._check("cur_uv", cur_uv, D._F32, (n, 2), dev)
     D._check("status", status, D._U8, (n,), dev)
-    s = D._torch().cuda.current_stream(ref_uv.device) if stream is None else stream
-    head = (ctx.handle, C.c_void_p(s.cuda_stream), _ptr(ref_uv), _ptr(cur_uv), _ptr(status), n, rows, cols, C.c_float(t), k, C.c_uint32(seed))
+    s = stream_or_current(ref_uv, stream)
+    head = (ctx.handle, C.c_void_p(s.cuda_stream), pointer(ref_uv), pointer(cur_uv), pointer(status), n, rows, cols, C.c_float(t), k, C.c_uint32(seed))
     return D, dev, n, k, head
 
 
@@ -67,7 +64,7 @@ def epipolar_ransac_args(ctx, ref_uv, cur_uv, status, image_size, threshold: flo
         D._check("counts", counts, D._I32, (k,), dev)
     if models is not None:
         D._check("models", models, D._F32, (k, 9), dev)
-    return head + (_ptr(workspace), _ptr(best), _ptr(n_inliers), _ptr(F), _ptr(counts), _ptr(models))
+    return head + (pointer(workspace), pointer(best), pointer(n_inliers), pointer(F), pointer(counts), pointer(models))
 
 
 def epipolar_ransac_device(ctx, ref_uv, cur_uv, status, image_size, threshold: float, hypotheses: int, seed: int, workspace, best, n_inliers, F,

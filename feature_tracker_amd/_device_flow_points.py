@@ -11,6 +11,7 @@ import ctypes as C
 import math
 
 from . import _native as N
+from ._torch_call import pointer, stream_or_current
 
 
 def flow_track_points_device(ctx, flow, mask, points, image_rows: int, image_cols: int, cur_points, status, fb_error2=None, mask_scale: float = 1.0,
@@ -49,8 +50,7 @@ def flow_track_points_device(ctx, flow, mask, points, image_rows: int, image_col
     if flow_back is not None:
         D._check("flow_back", flow_back, D._F32, (B, 2, H, W), dev)
         D._check("mask_back", mask_back, D._F32, (B, 576, H, W), dev)
-    s = D._torch().cuda.current_stream(flow.device) if stream is None else stream
-    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-    rc = N.lib().ftk_flow_track_points_device(ctx.handle, C.c_void_p(s.cuda_stream), ptr(flow), ptr(mask), ptr(flow_back), ptr(mask_back), B, H, W, n,
-                                              rows, cols, scale, threshold, ptr(points), ptr(cur_points), ptr(status), ptr(fb_error2))
+    s = stream_or_current(flow, stream)
+    rc = N.lib().ftk_flow_track_points_device(ctx.handle, C.c_void_p(s.cuda_stream), pointer(flow), pointer(mask), pointer(flow_back), pointer(mask_back), B, H, W, n,
+                                              rows, cols, scale, threshold, pointer(points), pointer(cur_points), pointer(status), pointer(fb_error2))
     N.check(rc, ctx.handle)

@@ -10,6 +10,7 @@ import ctypes as C
 import math
 
 from . import _native as N
+from ._torch_call import stream_or_current
 
 
 def flow_upsample_device(ctx, flow, mask, out, mask_scale: float = 1.0, stream=None) -> None:
@@ -29,7 +30,7 @@ def flow_upsample_device(ctx, flow, mask, out, mask_scale: float = 1.0, stream=N
         raise ValueError(f"flow must be a non-empty [B, 2, H, W] tensor (got {list(flow.shape)})")
     D._check("mask", mask, D._F32, (B, 576, H, W), dev)
     D._check("out", out, D._F32, (B, 2, 8 * H, 8 * W), dev)
-    s = D._torch().cuda.current_stream(flow.device) if stream is None else stream
+    s = stream_or_current(flow, stream)
     rc = N.lib().ftk_flow_upsample_device(ctx.handle, C.c_void_p(s.cuda_stream), C.c_void_p(flow.data_ptr()), C.c_void_p(mask.data_ptr()),
                                           B, H, W, scale, C.c_void_p(out.data_ptr()))
     N.check(rc, ctx.handle)

@@ -9,6 +9,7 @@ from __future__ import annotations
 import ctypes as C
 
 from . import _native as N
+from ._torch_call import stream_or_current
 
 
 def flow_warm_device(ctx, flow, out, splits: int = 1, workspace=None, stream=None) -> None:
@@ -35,7 +36,7 @@ def flow_warm_device(ctx, flow, out, splits: int = 1, workspace=None, stream=Non
     D._check("out", out, D._F32, (B, 2, H, W), dev)
     if workspace is not None:
         D._check("workspace", workspace, D._KEYS, (None,), dev, min_numel=k * B * H * W)
-    s = D._torch().cuda.current_stream(flow.device) if stream is None else stream
+    s = stream_or_current(flow, stream)
     rc = N.lib().ftk_flow_warm_device(ctx.handle, C.c_void_p(s.cuda_stream), C.c_void_p(flow.data_ptr()), B, H, W, k,
                                       None if workspace is None else C.c_void_p(workspace.data_ptr()), C.c_void_p(out.data_ptr()))
     N.check(rc, ctx.handle)

@@ -9,6 +9,7 @@ import ctypes as C
 import math
 
 from . import _native as N
+from ._torch_call import pointer, stream_or_current
 
 LAYOUTS = ("chw", "hwc")
 MAX_CELLS = 65536 // N.FTK_KEYPOINT_DECODE_CELL
@@ -77,8 +78,8 @@ def keypoint_decode_args(ctx, semi, desc, max_keypoints: int, min_score: float, 
     D._check("count", count, D._I32, (1,), dev)
     if heatmap is not None:
         D._check("heatmap", heatmap, D._F32, (8 * hc, 8 * wc), dev)
-    st = D._torch().cuda.current_stream(semi.device) if stream is None else stream
-    p = lambda x: None if x is None else C.c_void_p(x.data_ptr())  # noqa: E731
+    st = stream_or_current(semi, stream)
+    p = pointer
     return (ctx.handle, C.c_void_p(st.cuda_stream), p(semi), hc, wc, p(desc), d, strides[0], strides[1], strides[2], k, C.c_float(s), distance, border,
             p(occupied), p(occupied_mask) if n > 0 else None, n, p(workspace), p(uv), p(scores), p(descriptors), p(count), p(heatmap))
 

@@ -9,6 +9,7 @@ from __future__ import annotations
 import ctypes as C
 
 from . import _native as N
+from ._torch_call import pointer
 
 _I64 = ("int64",)
 
@@ -55,9 +56,7 @@ def harris_detect_device(ctx, pyramid, max_count: int, min_distance: int, min_re
         if occupied_mask is not None:
             D._check("occupied_mask", occupied_mask, D._U8, (n,), dev)
     rc = N.lib().ftk_harris_detect_device(ctx.handle, pyramid.handle, int(level), k, int(min_distance), float(min_response),
-                                          None if occupied is None else C.c_void_p(occupied.data_ptr()),
-                                          None if occupied_mask is None else C.c_void_p(occupied_mask.data_ptr()), n,
-                                          C.c_void_p(uv_out.data_ptr()), C.c_void_p(count_out.data_ptr()))
+                                          pointer(occupied), pointer(occupied_mask), n, pointer(uv_out), pointer(count_out))
     N.check(rc, ctx.handle)
 
 
@@ -93,7 +92,7 @@ def track_table_retire_args(ctx, ids, points, prev_points, status, age, n_live, 
         D._check("back_status", back_status, D._U8, (n,), dev)
     D._check("free_slots", free_slots, D._I32, (n,), dev)
     D._check("n_free", n_free, D._I32, (1,), dev)
-    p = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+    p = pointer
     return (ctx.handle, n, p(ids), p(points), p(prev_points), p(status), p(age), p(n_live), p(tracked_uv), p(tracked_status), p(back_uv), p(back_status),
             C.c_float(float(fb_threshold)), p(free_slots), p(n_free))
 
@@ -120,7 +119,7 @@ def track_table_fill_args(ctx, pyramid, min_distance: int, min_response: float, 
     D._check("next_id", next_id, _I64, (1,), dev)
     D._check("free_slots", free_slots, D._I32, (n,), dev)
     D._check("n_free", n_free, D._I32, (1,), dev)
-    p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    p = pointer
     return (ctx.handle, pyramid.handle, int(level), int(min_distance), C.c_float(float(min_response)), n, p(ids), p(points), p(prev_points), p(status), p(age),
             p(n_live), p(next_id), p(free_slots), p(n_free))
 

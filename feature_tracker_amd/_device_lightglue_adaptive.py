@@ -11,6 +11,7 @@ import math
 
 from . import _native as N
 from ._device_transformer import check_heads, check_rows
+from ._torch_call import pointer, stream_or_current
 
 
 def stop_threshold(layer: int, n_layers: int) -> float:
@@ -37,14 +38,6 @@ def check_min_keypoints(value) -> int:
     if isinstance(value, bool) or not isinstance(value, int) or not 0 <= value < 2 ** 31:
         raise ValueError(f"pruning_min_keypoints must be an integer >= 0 (got {value!r})")
     return value
-
-
-def _pointer(x):
-    return None if x is None else C.c_void_p(x.data_ptr())
-
-
-def _stream(D, tensor, stream):
-    return D._torch().cuda.current_stream(tensor.device) if stream is None else stream
 
 
 def _workspace(D, workspace, m, n, d, heads, dev):
@@ -79,9 +72,9 @@ def lightglue_confidence_args(ctx, desc0, desc1, token_w, token_b, match_w, matc
             D._check(name, word, D._I32, (1,), dev)
     D._check("conf", conf, D._F32, (m + n,), dev)
     D._check("mt", mt, D._F32, (m + n,), dev)
-    st = _stream(D, desc0, stream)
-    return (ctx.handle, C.c_void_p(st.cuda_stream), _pointer(desc0), m, _pointer(desc1), n, d, _pointer(token_w), _pointer(token_b), _pointer(match_w),
-            _pointer(match_b), _pointer(live0), _pointer(live1), _pointer(gate), _pointer(conf), _pointer(mt))
+    st = stream_or_current(desc0, stream)
+    return (ctx.handle, C.c_void_p(st.cuda_stream), pointer(desc0), m, pointer(desc1), n, d, pointer(token_w), pointer(token_b), pointer(match_w),
+            pointer(match_b), pointer(live0), pointer(live1), pointer(gate), pointer(conf), pointer(mt))
 
 
 def lightglue_confidence_device(ctx, desc0, desc1, token_w, token_b, match_w, match_b, live0, live1, gate, conf, mt, stream=None) -> None:
@@ -104,9 +97,9 @@ def transformer_layer_adaptive_args(ctx, desc0, desc1, heads, enc0, enc1, weight
     for name, word in (("live0", live0), ("live1", live1), ("gate", gate)):
         D._check(name, word, D._I32, (1,), dev)
     D._check("workspace", workspace, D._KEYS, (None,), dev, min_numel=-(-N.transformer_layer_workspace_bytes(m, n, d, heads) // 8))
-    st = _stream(D, desc0, stream)
-    return (ctx.handle, C.c_void_p(st.cuda_stream), _pointer(desc0), m, _pointer(desc1), n, d, heads, _pointer(enc0), _pointer(enc1), _pointer(weights),
-            _pointer(live0), _pointer(live1), _pointer(gate), _pointer(workspace))
+    st = stream_or_current(desc0, stream)
+    return (ctx.handle, C.c_void_p(st.cuda_stream), pointer(desc0), m, pointer(desc1), n, d, heads, pointer(enc0), pointer(enc1), pointer(weights),
+            pointer(live0), pointer(live1), pointer(gate), pointer(workspace))
 
 
 def transformer_layer_adaptive_device(ctx, desc0, desc1, heads, enc0, enc1, weights, live0, live1, gate, workspace, stream=None) -> None:
@@ -150,10 +143,10 @@ def lightglue_adapt_step_args(ctx, heads, layer, conf, mt, count0, count1, state
     D._check("layers0", layers0, D._I32, (m,), dev)
     D._check("layers1", layers1, D._I32, (n,), dev)
     _workspace(D, workspace, m, n, d, heads, dev)
-    st = _stream(D, src[0], stream)
-    return ((ctx.handle, C.c_void_p(st.cuda_stream), m, n, d, heads, layer, _pointer(conf), _pointer(mt), _pointer(count0), _pointer(count1), _pointer(state),
-             C.c_float(threshold), C.c_float(depth), C.c_float(width), min_keypoints) + tuple(_pointer(t) for t in src) + tuple(_pointer(t) for t in dst)
-            + (_pointer(layers0), _pointer(layers1), _pointer(workspace)))
+    st = stream_or_current(src[0], stream)
+    return ((ctx.handle, C.c_void_p(st.cuda_stream), m, n, d, heads, layer, pointer(conf), pointer(mt), pointer(count0), pointer(count1), pointer(state),
+             C.c_float(threshold), C.c_float(depth), C.c_float(width), min_keypoints) + tuple(pointer(t) for t in src) + tuple(pointer(t) for t in dst)
+            + (pointer(layers0), pointer(layers1), pointer(workspace)))
 
 
 def lightglue_adapt_step_device(ctx, heads, layer, conf, mt, count0, count1, state, threshold, depth_confidence, width_confidence, min_keypoints, src, dst,
@@ -187,10 +180,10 @@ def lightglue_finish_args(ctx, desc0, desc1, heads, head_w, head_b, state, ind0,
     D._check("status", status, D._U8, (m,), dev)
     D._check("layers0", layers0, D._I32, (m,), dev)
     D._check("layers1", layers1, D._I32, (n,), dev)
-    st = _stream(D, desc0, stream)
-    return (ctx.handle, C.c_void_p(st.cuda_stream), _pointer(desc0), m, _pointer(desc1), n, d, heads, n_layers, _pointer(head_w), _pointer(head_b),
-            _pointer(state), _pointer(ind0), _pointer(ind1), C.c_float(min_score), _pointer(workspace), _pointer(scores), _pointer(match_index),
-            _pointer(status), _pointer(layers0), _pointer(layers1))
+    st = stream_or_current(desc0, stream)
+    return (ctx.handle, C.c_void_p(st.cuda_stream), pointer(desc0), m, pointer(desc1), n, d, heads, n_layers, pointer(head_w), pointer(head_b),
+            pointer(state), pointer(ind0), pointer(ind1), C.c_float(min_score), pointer(workspace), pointer(scores), pointer(match_index),
+            pointer(status), pointer(layers0), pointer(layers1))
 
 
 def lightglue_finish_device(ctx, desc0, desc1, heads, head_w, head_b, state, ind0, ind1, min_score, workspace, scores, match_index, status, layers0,

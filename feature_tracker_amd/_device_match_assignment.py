@@ -9,6 +9,7 @@ import ctypes as C
 import math
 
 from . import _native as N
+from ._torch_call import pointer, stream_or_current
 
 
 def check_scale(scale) -> float:
@@ -64,8 +65,8 @@ def match_assignment_args(ctx, desc0, desc1, weights, bias, scale, count0, count
     stride = check_row_stride(row_stride, n)
     D._check("workspace", workspace, D._KEYS, (None,), dev, min_numel=-(-N.match_assignment_workspace_bytes(m, n, d, weights is not None) // 8))
     D._check("scores", scores, D._F32, (None,), dev, min_numel=m * stride + n + 1)
-    st = D._torch().cuda.current_stream(desc0.device) if stream is None else stream
-    p = lambda x: None if x is None else C.c_void_p(x.data_ptr())  # noqa: E731
+    st = stream_or_current(desc0, stream)
+    p = pointer
     return (ctx.handle, C.c_void_p(st.cuda_stream), p(desc0), m, p(desc1), n, d, p(weights), p(bias), C.c_float(s), p(count0), p(count1), p(workspace),
             p(scores), stride)
 

@@ -14,6 +14,7 @@ import ctypes as C
 import math
 
 from . import _native as N
+from ._torch_call import stream_or_current
 
 
 def _conv2d(ctx, parts, packed_weights, bias, kernel_size, relu, out_scale, out, stream, *, strided: bool, stride=1, residual=None, normalise=False,
@@ -56,7 +57,7 @@ def _conv2d(ctx, parts, packed_weights, bias, kernel_size, relu, out_scale, out,
     D._check("bias", bias, D._F32, (Cout,), dev)
     if residual is not None:
         D._check("residual", residual, D._F32, (B, Cout, OH, OW), dev)
-    s = D._torch().cuda.current_stream(out.device) if stream is None else stream
+    s = stream_or_current(out, stream)
     layer = (ctx.handle, C.c_void_p(s.cuda_stream), N.part_array(parts), len(parts), C.c_void_p(packed_weights.data_ptr()), C.c_void_p(bias.data_ptr()), Cout, ks)
     sizes = (B, H, W, C.c_void_p(out.data_ptr()))
     if pool:
@@ -111,6 +112,6 @@ def channel_normalise_device(ctx, x, out, stream=None) -> None:
     if min(hc, wc) < 1:
         raise ValueError(f"x must be a non-empty [D, Hc, Wc] tensor (got {list(x.shape)})")
     D._check("out", out, D._F32, (hc, wc, d), dev)
-    s = D._torch().cuda.current_stream(x.device) if stream is None else stream
+    s = stream_or_current(x, stream)
     N.check(N.lib().ftk_channel_normalise_device(ctx.handle, C.c_void_p(s.cuda_stream), C.c_void_p(x.data_ptr()), d, hc, wc, C.c_void_p(out.data_ptr())),
             ctx.handle)

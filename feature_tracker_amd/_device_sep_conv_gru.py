@@ -9,6 +9,7 @@ from __future__ import annotations
 import ctypes as C
 
 from . import _native as N
+from ._torch_call import stream_or_current
 
 # the packed tensors a call needs, per pass: the stacked z | r matrix and bias, the q matrix and bias
 PACKED_KEYS = ("zr_horizontal", "zr_bias_horizontal", "q_horizontal", "q_bias_horizontal",
@@ -45,7 +46,7 @@ def sep_conv_gru_device(ctx, x_parts, h, packed, kernel_size: int, z, rh, mid, o
         rows = Ch if key.startswith("q") else 2 * Ch
         want = rows if "bias" in key else N.sep_conv_gru_packed_elements(rows, Cin, ks)
         D._check(f"packed[{key!r}]", packed[key], D._F32, (want,), dev)
-    s = D._torch().cuda.current_stream(h.device) if stream is None else stream
+    s = stream_or_current(h, stream)
     parts = N.part_array(x_parts)
     ptr = {key: C.c_void_p(packed[key].data_ptr()) for key in PACKED_KEYS}
     h_p, z_p, rh_p, mid_p, out_p = (C.c_void_p(t.data_ptr()) for t in (h, z, rh, mid, out))

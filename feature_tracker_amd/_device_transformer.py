@@ -10,6 +10,7 @@ import ctypes as C
 import math
 
 from . import _native as N
+from ._torch_call import pointer, stream_or_current
 
 
 def check_scale(name: str, scale) -> float:
@@ -42,14 +43,6 @@ def check_heads(dim: int, heads) -> int:
     return dh
 
 
-def _pointer(x):
-    return None if x is None else C.c_void_p(x.data_ptr())
-
-
-def _stream(D, tensor, stream):
-    return D._torch().cuda.current_stream(tensor.device) if stream is None else stream
-
-
 def attention_args(ctx, q, k, v, count, pre_scale, post_scale, out, stream=None):
     """Checks one ftk_attention_device call and returns its marshalled arguments."""
     from . import device as D
@@ -69,9 +62,9 @@ def attention_args(ctx, q, k, v, count, pre_scale, post_scale, out, stream=None)
     if count is not None:
         D._check("count", count, D._I32, (1,), dev)
     D._check("out", out, D._F32, (m, h, dh), dev)
-    st = _stream(D, q, stream)
-    return (ctx.handle, C.c_void_p(st.cuda_stream), _pointer(q), m, _pointer(k), _pointer(v), n, h, dh, _pointer(count), C.c_float(pre), C.c_float(post),
-            _pointer(out))
+    st = stream_or_current(q, stream)
+    return (ctx.handle, C.c_void_p(st.cuda_stream), pointer(q), m, pointer(k), pointer(v), n, h, dh, pointer(count), C.c_float(pre), C.c_float(post),
+            pointer(out))
 
 
 def attention_device(ctx, q, k, v, count, pre_scale, post_scale, out, stream=None) -> None:
@@ -97,8 +90,8 @@ def linear_args(ctx, x, weight, bias, out, stream=None):
     if not (1 <= k <= N.FTK_TRANSFORMER_MAX_DIM and 1 <= outs <= N.FTK_TRANSFORMER_MAX_DIM):
         raise ValueError(f"weight must be [1 .. FTK_TRANSFORMER_MAX_DIM, 1 .. FTK_TRANSFORMER_MAX_DIM = {N.FTK_TRANSFORMER_MAX_DIM}] (got {[outs, k]})")
     D._check("out", out, D._F32, (rows, outs), dev)
-    st = _stream(D, x, stream)
-    return (ctx.handle, C.c_void_p(st.cuda_stream), _pointer(x), rows, k, _pointer(weight), _pointer(bias), outs, _pointer(out))
+    st = stream_or_current(x, stream)
+    return (ctx.handle, C.c_void_p(st.cuda_stream), pointer(x), rows, k, pointer(weight), pointer(bias), outs, pointer(out))
 
 
 def linear_device(ctx, x, weight, bias, out, stream=None) -> None:
@@ -129,9 +122,9 @@ def transformer_layer_args(ctx, desc0, desc1, heads, enc0, enc1, weights, count0
     D._check("workspace", workspace, D._KEYS, (None,), dev, min_numel=-(-N.transformer_layer_workspace_bytes(m, n, d, heads) // 8))
     D._check("out0", out0, D._F32, (m, d), dev)
     D._check("out1", out1, D._F32, (n, d), dev)
-    st = _stream(D, desc0, stream)
-    return (ctx.handle, C.c_void_p(st.cuda_stream), _pointer(desc0), m, _pointer(desc1), n, d, heads, _pointer(enc0), _pointer(enc1), _pointer(weights),
-            _pointer(count0), _pointer(count1), _pointer(workspace), _pointer(out0), _pointer(out1))
+    st = stream_or_current(desc0, stream)
+    return (ctx.handle, C.c_void_p(st.cuda_stream), pointer(desc0), m, pointer(desc1), n, d, heads, pointer(enc0), pointer(enc1), pointer(weights),
+            pointer(count0), pointer(count1), pointer(workspace), pointer(out0), pointer(out1))
 
 
 def transformer_layer_device(ctx, desc0, desc1, heads, enc0, enc1, weights, count0, count1, workspace, out0, out1, stream=None) -> None:

@@ -1,7 +1,7 @@
 """``device.two_view_ransac_device``: the torch device entry of two-view outlier rejection with a choice of model
 (ftk_two_view_ransac_device).
 
-It is re-exported by device.py and held to that module's rule: no ``data_ptr()`` of a tensor that did not pass ``device._check``.  It lives
+It is re-exported by device.py and held to that module's rule: no ``datapointer()`` of a tensor that did not pass ``device._check``.  It lives
 in a file of its own for _device_epipolar.py's reason; its walk and its refusals are tests/test_two_view_args_cpu.py.
 """
 from __future__ import annotations
@@ -9,7 +9,8 @@ from __future__ import annotations
 import math
 
 from . import _native as N
-from ._device_epipolar import SEED_ARG, _ptr, check_sizes, ransac_inputs  # noqa: F401  (SEED_ARG: both entries share the arguments up to the seed)
+from ._torch_call import pointer
+from ._device_epipolar import SEED_ARG, check_sizes, ransac_inputs  # noqa: F401  (SEED_ARG: both entries share the arguments up to the seed)
 
 
 def check_mode(model) -> int:
@@ -54,7 +55,7 @@ def two_view_ransac_args(ctx, ref_uv, cur_uv, status, image_size, threshold: flo
         D._check("counts", counts, D._I32, (2, k), dev)
     if models is not None:
         D._check("models", models, D._F32, (2, k, 9), dev)
-    return head + (mode, permille, _ptr(workspace), _ptr(model_out), _ptr(best), _ptr(n_inliers), _ptr(F), _ptr(H), _ptr(counts), _ptr(models))
+    return head + (mode, permille, pointer(workspace), pointer(model_out), pointer(best), pointer(n_inliers), pointer(F), pointer(H), pointer(counts), pointer(models))
 
 
 def two_view_ransac_device(ctx, ref_uv, cur_uv, status, image_size, threshold: float, hypotheses: int, seed: int, model, prefer_homography_permille: int,

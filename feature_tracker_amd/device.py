@@ -12,6 +12,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _native as N
+from ._torch_call import stream_or_current
 from .tracker import Context, ImagePyramid, OpticalFlowOptions
 
 
@@ -438,7 +439,7 @@ def corr_pyramid_build_device(ctx: Context, fmap0, fmap1, levels: int, volume, s
     """ftk_corr_pyramid_build_device: the correlation pyramid of ``fmap0`` / ``fmap1`` (contiguous float32 CUDA [B, C, H, W]) into
     ``volume`` (contiguous float32 CUDA, ftk_corr_pyramid_layout's element count), enqueued on ``stream`` (a torch.cuda.Stream; default:
     torch's current stream).  No synchronisation, no allocation: capturable."""
-    torch = _torch()
+    _torch()  # (no HIP device: that refusal comes first)
     _corr_check("fmap0", fmap0, 4)
     _corr_check("fmap1", fmap1, 4)
     if tuple(fmap0.shape) != tuple(fmap1.shape) or fmap0.device != fmap1.device:
@@ -448,7 +449,7 @@ def corr_pyramid_build_device(ctx: Context, fmap0, fmap1, levels: int, volume, s
     _corr_check("volume", volume, volume.dim())
     if volume.numel() != elements or volume.device != fmap0.device:
         raise ValueError(f"volume must hold {elements} floats on {fmap0.device} (got {volume.numel()} on {volume.device})")
-    s = torch.cuda.current_stream(fmap0.device) if stream is None else stream
+    s = stream_or_current(fmap0, stream)
     rc = N.lib().ftk_corr_pyramid_build_device(ctx.handle, C.c_void_p(s.cuda_stream), C.c_void_p(fmap0.data_ptr()), C.c_void_p(fmap1.data_ptr()),
                                                B, Cc, H, W, int(levels), C.c_void_p(volume.data_ptr()))
     N.check(rc, ctx.handle)
@@ -457,7 +458,7 @@ def corr_pyramid_build_device(ctx: Context, fmap0, fmap1, levels: int, volume, s
 def corr_pyramid_lookup_device(ctx: Context, volume, levels: int, radius: int, coords, out, per_level: bool = False, stream=None) -> None:
     """ftk_corr_pyramid_lookup_device: the (2r+1)^2 windows of every level around ``coords`` (contiguous float32 CUDA [B, 2, H, W], x then y)
     into ``out``: [B, levels * K, H, W], or with ``per_level`` ``levels`` consecutive [B, H, W, K] blocks (K = (2r+1)^2)."""
-    torch = _torch()
+    _torch()  # (no HIP device: that refusal comes first)
     _corr_check("coords", coords, 4)
     B, two, H, W = coords.shape
     if two != 2:
@@ -470,7 +471,7 @@ def corr_pyramid_lookup_device(ctx: Context, volume, levels: int, radius: int, c
     _corr_check("out", out, out.dim())
     if out.numel() != B * levels * K * H * W or out.device != coords.device:
         raise ValueError(f"out must hold {B * levels * K * H * W} floats on {coords.device}")
-    s = torch.cuda.current_stream(coords.device) if stream is None else stream
+    s = stream_or_current(coords, stream)
     rc = N.lib().ftk_corr_pyramid_lookup_device(ctx.handle, C.c_void_p(s.cuda_stream), C.c_void_p(volume.data_ptr()), B, H, W, int(levels),
                                                 int(radius), C.c_void_p(coords.data_ptr()), C.c_void_p(out.data_ptr()), int(bool(per_level)))
     N.check(rc, ctx.handle)
@@ -492,9 +493,8 @@ from ._device_lightglue_adaptive import (lightglue_adapt_step_device, lightglue_
                                          transformer_layer_adaptive_device)  # (LightGlue's adaptive depth and width; likewise)
 
 
-def _nn_stream(torch, device, stream):
-    s = torch.cuda.current_stream(device) if stream is None else stream
-    return C.c_void_p(s.cuda_stream)
+def _nn_stream(tensor, stream):
+    return C.c_void_p(stream_or_current(tensor, stream).cuda_stream)
 
 
 def nn_match_scores_device(ctx: Context, scores, min_score: float, match_index, status, stream=None) -> None:
@@ -513,7 +513,7 @@ def nn_match_scores_device(ctx: Context, scores, min_score: float, match_index, 
     # a size-1 dimension's stride is arbitrary in torch: give the extent the library validates against
     row_stride = scores.stride(1) if n_ref > 1 else max(n_cur, 1)
     batch_stride = scores.stride(0) if B > 1 else 0
-    rc = N.lib().ftk_nn_match_scores_device(ctx.handle, _nn_stream(torch, scores.device, stream), C.c_void_p(scores.data_ptr()), B, n_ref, n_cur,
+    rc = N.lib().ftk_nn_match_scores_device(ctx.handle, _nn_stream(scores, stream), C.c_void_p(scores.data_ptr()), B, n_ref, n_cur,
                                             row_stride, batch_stride, float(min_score), C.c_void_p(match_index.data_ptr()),
                                             C.c_void_p(status.data_ptr()))
     N.check(rc, ctx.handle)
@@ -529,7 +529,7 @@ def nn_match_list_device(ctx: Context, matches, n_ref: int, n_cur: int, match_in
     for name, t, dt in (("match_index", match_index, torch.int32), ("status", status, torch.uint8)):
         if t.dtype != dt or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != (int(n_ref),) or t.device != matches.device:
             raise ValueError(f"{name} must be a contiguous {dt} tensor of shape ({n_ref},) on {matches.device}")
-    rc = N.lib().ftk_nn_match_list_device(ctx.handle, _nn_stream(torch, matches.device, stream), C.c_void_p(matches.data_ptr()), matches.size(0),
+    rc = N.lib().ftk_nn_match_list_device(ctx.handle, _nn_stream(matches, stream), C.c_void_p(matches.data_ptr()), matches.size(0),
                                           int(n_ref), int(n_cur), C.c_void_p(match_index.data_ptr()), C.c_void_p(status.data_ptr()))
     N.check(rc, ctx.handle)
 
@@ -544,6 +544,6 @@ def nn_fill_pixels_device(ctx: Context, match_index, cur_uv, matched_uv, stream=
     for name, t in (("cur_uv", cur_uv), ("matched_uv", matched_uv)):
         if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != (n_cur, 2) or t.device != match_index.device:
             raise ValueError(f"{name} must be a contiguous float32 tensor of shape ({n_cur}, 2) on {match_index.device}")
-    rc = N.lib().ftk_nn_fill_pixels_device(ctx.handle, _nn_stream(torch, match_index.device, stream), C.c_void_p(match_index.data_ptr()), n_ref,
+    rc = N.lib().ftk_nn_fill_pixels_device(ctx.handle, _nn_stream(match_index, stream), C.c_void_p(match_index.data_ptr()), n_ref,
                                            C.c_void_p(cur_uv.data_ptr()), n_cur, C.c_void_p(matched_uv.data_ptr()))
     N.check(rc, ctx.handle)

@@ -10,6 +10,7 @@ from typing import Optional
 
 from . import _native as N
 from ._device_epipolar import check_sizes, epipolar_ransac_args
+from ._torch_call import OnStream, PerDevice, call, check_ctx, complain
 
 
 def ransac_filter(ransac, ref_uv, cur_uv, status, image_size, seed, return_hypotheses):
@@ -21,37 +22,14 @@ def ransac_filter(ransac, ref_uv, cur_uv, status, image_size, seed, return_hypot
     from . import device as D
 
     tensors = (("ref_uv", ref_uv, D._F32, (None, 2)), ("cur_uv", cur_uv, D._F32, (None, 2)), ("status", status, D._U8, (None,)))
-    for name, t, dtypes, shape in tensors:
-        complaint = D._tensor_complaint(name, t, dtypes, shape)
-        if complaint:
-            raise ValueError(complaint)
-    for name, t, _, _ in tensors:
-        if not t.is_cuda:
-            raise ValueError(f"{name} must be a CUDA tensor (got one on {t.device}): there is no CPU fallback")
-    torch = D._torch()
-    ctx = ransac._ctx
-    if ctx is None:
-        from .raft import _device_context
-
-        ctx = _device_context(ref_uv)
-    device = ref_uv.device
-    caller = torch.cuda.current_stream(device)
-    stream = getattr(ctx, "stream", None) or caller
-    n = int(ref_uv.shape[0])
-    if stream != caller:
-        stream.wait_stream(caller)
-    with torch.cuda.stream(stream):
-        workspace = ransac._workspace.get(device)
+    complain(tensors)
+    device, n = ref_uv.device, int(ref_uv.shape[0])
+    with OnStream(ransac._ctx, ref_uv) as on:
+        workspace = ransac._workspace.get(device)  # (of an n outside the limits: whatever there is, and the entry's refusal)
         if 1 <= n <= N.FTK_TRACK_TABLE_MAX_SLOTS:
-            words = -(-ransac._workspace_bytes(n, k) // 8)
-            if workspace is None or workspace.numel() < words:  # (the old block, if any, goes back to torch's allocator in stream order)
-                workspace = ransac._workspace[device] = torch.empty(words + words // 4, dtype=torch.int64, device=device)
-        out = ransac._result(torch, device, k, return_hypotheses)
-        rc = getattr(N.lib(), ransac._entry)(*ransac._args(ctx, ref_uv, cur_uv, status, (rows, cols), k, seed, workspace, out, stream))
-        if rc != 0:
-            N.check(rc, ctx.handle)
-    if stream != caller:
-        caller.wait_stream(stream)
+            workspace = ransac._workspace.of(on.torch, device, ransac._workspace_bytes(n, k))
+        out = ransac._result(on.torch, device, k, return_hypotheses)
+        call(ransac._entry, ransac._args(on.ctx, ref_uv, cur_uv, status, (rows, cols), k, seed, workspace, out, on.stream), on.ctx)
     return out
 
 
@@ -87,11 +65,9 @@ class EpipolarRansac:
 
     def __init__(self, hypotheses: int = 512, threshold: float = 1.0, seed: int = 0, ctx=None):
         _, _, self.threshold, self.hypotheses, self.seed = check_sizes((1, 1), threshold, hypotheses, seed)
-        if ctx is not None and getattr(ctx, "stream", None) is None:
-            raise ValueError("ctx must come from device.context_on_stream(stream): torch must know the stream the kernels run on (None: torch's "
-                             "current stream)")
+        check_ctx(ctx)
         self._ctx = ctx
-        self._workspace = {}  # device -> the one workspace of this object on it, grown to the largest call so far
+        self._workspace = PerDevice()  # device -> the one workspace of this object on it, grown to the largest call so far
 
     def filter(self, ref_uv, cur_uv, status, image_size, seed: Optional[int] = None, return_hypotheses: bool = False) -> EpipolarResult:
         """One pass of outlier rejection; ``seed``: this call's seed instead of the object's; ``return_hypotheses``: also ``counts`` and

@@ -9,6 +9,7 @@ from __future__ import annotations
 
 from . import _native as N
 from ._device_keypoint_decode import check_grid, check_options, keypoint_decode_args
+from ._torch_call import OnStream, PerDevice, call, check_ctx, complain, complain_cuda
 
 
 class KeypointResult:
@@ -40,11 +41,9 @@ class KeypointDecoder:
 
     def __init__(self, max_keypoints: int = 300, min_score: float = 0.1, min_distance: int = 20, border: int = 4, ctx=None):
         self.max_keypoints, self.min_score, self.min_distance, self.border = check_options(max_keypoints, min_score, min_distance, border)
-        if ctx is not None and getattr(ctx, "stream", None) is None:
-            raise ValueError("ctx must come from device.context_on_stream(stream): torch must know the stream the kernels run on (None: torch's "
-                             "current stream)")
+        check_ctx(ctx)
         self._ctx = ctx
-        self._workspace = {}  # device -> the one workspace of this object on it, grown to the largest call so far
+        self._workspace = PerDevice()  # device -> the one workspace of this object on it, grown to the largest call so far
 
     def decode(self, semi, desc, occupied=None, occupied_mask=None, return_heatmap: bool = False) -> KeypointResult:
         """One image's heads to keypoints.  Everything is enqueued; the returned tensors are valid in stream order."""
@@ -57,10 +56,7 @@ class KeypointDecoder:
             tensors.append(("occupied", occupied, D._F32, (None, 2)))
         if occupied_mask is not None:
             tensors.append(("occupied_mask", occupied_mask, D._U8, (None,)))
-        for name, t, dtypes, shape in tensors:
-            complaint = D._tensor_complaint(name, t, dtypes, shape)
-            if complaint:
-                raise ValueError(complaint)
+        complain(tensors, cuda=False)
         hc, wc = int(semi.shape[1]), int(semi.shape[2])
         check_grid(hc, wc, self.min_distance)
         # desc is [D, Hc, Wc] by its shape; its memory is that order or channel-last
@@ -74,42 +70,22 @@ class KeypointDecoder:
         else:
             raise ValueError(f"desc must be a contiguous [D, Hc, Wc] tensor or a permute(2, 0, 1) view of a contiguous [Hc, Wc, D] one (got strides "
                              f"{list(desc.stride())}); nothing is copied here")
-        complaint = D._tensor_complaint("desc", base, D._F32, (None, hc, wc) if layout == "chw" else (hc, wc, None))
-        if complaint:
-            raise ValueError(complaint)
-        for name, t in [(n, t) for n, t, _, _ in tensors] + [("desc", desc)]:
-            if not t.is_cuda:
-                raise ValueError(f"{name} must be a CUDA tensor (got one on {t.device}): there is no CPU fallback")
-        torch = D._torch()
-        ctx = self._ctx
-        if ctx is None:
-            from .raft import _device_context
-
-            ctx = _device_context(semi)
+        complain([("desc", base, D._F32, (None, hc, wc) if layout == "chw" else (hc, wc, None))], cuda=False)
+        complain_cuda([(n, t) for n, t, _, _ in tensors] + [("desc", desc)])
         device = semi.device
-        caller = torch.cuda.current_stream(device)
-        stream = getattr(ctx, "stream", None) or caller
         k, d = self.max_keypoints, int(desc.shape[0])
         n = 0 if occupied is None else int(occupied.shape[0])
-        if stream != caller:
-            stream.wait_stream(caller)
-        with torch.cuda.stream(stream):
-            words = -(-N.keypoint_decode_workspace_bytes(hc, wc, self.min_distance, n) // 8)
-            workspace = self._workspace.get(device)
-            if workspace is None or workspace.numel() < words:  # (the old block, if any, goes back to torch's allocator in stream order)
-                workspace = self._workspace[device] = torch.empty(words + words // 4, dtype=torch.int64, device=device)
+        with OnStream(self._ctx, semi) as on:
+            torch, ctx = on.torch, on.ctx
+            workspace = self._workspace.of(torch, device, N.keypoint_decode_workspace_bytes(hc, wc, self.min_distance, n))
             f32 = dict(dtype=torch.float32, device=device)
             out = KeypointResult(torch.empty((k, 2), **f32), torch.empty(k, **f32), torch.empty((k, d), **f32),
                                  torch.empty(1, dtype=torch.int32, device=device))
             if return_heatmap:
                 out.heatmap = torch.empty((8 * hc, 8 * wc), **f32)
             args = keypoint_decode_args(ctx, semi, base, k, self.min_score, self.min_distance, self.border, workspace, out.uv, out.scores, out.descriptors,
-                                        out.count, out.heatmap, occupied, occupied_mask, layout, stream)
-            rc = N.lib().ftk_keypoint_decode_device(*args)
-            if rc != 0:
-                N.check(rc, ctx.handle)
-        if stream != caller:
-            caller.wait_stream(stream)
+                                        out.count, out.heatmap, occupied, occupied_mask, layout, on.stream)
+            call("ftk_keypoint_decode_device", args, ctx)
         return out
 
     @staticmethod

@@ -15,6 +15,7 @@ from . import _native as N
 from ._device_epipolar import SEED_ARG, check_sizes, epipolar_ransac_args
 from ._device_two_view import check_mode, prefer_to_permille, two_view_ransac_args
 from ._device_klt_video import harris_survivor_bound, track_table_fill_args, track_table_retire_args
+from ._torch_call import OnStream, call, check_ctx
 from .tracker import OUTSIDE, ImagePyramid, OpticalFlow
 
 _MIN_SIDE = 23  # 2 * Harris border + 1: a smaller image has no valid centre
@@ -81,9 +82,7 @@ class KltVideoTracker:
             self._epipolar_permille = prefer_to_permille(epipolar_prefer_homography)
             _, _, self.epipolar_threshold, self.epipolar_hypotheses, self.epipolar_seed = check_sizes((1, 1), epipolar_threshold, epipolar_hypotheses,
                                                                                                       epipolar_seed)
-        if ctx is not None and getattr(ctx, "stream", None) is None:
-            raise ValueError("ctx must come from device.context_on_stream(stream): the table's tensors are torch's, and torch must know the stream "
-                             "the kernels run on (None: the tracker makes its own)")
+        check_ctx(ctx, none_means="the tracker makes its own", because="the table's tensors are torch's, and ")
         self.flow, self.max_features, self.levels = flow, n, int(levels)
         self.min_distance, self.min_response = int(min_distance), float(min_response)
         self.forward_backward = None if forward_backward is None else float(forward_backward)
@@ -106,12 +105,8 @@ class KltVideoTracker:
         self._pyramids = None
         self._image = None
         if self.ids is not None:
-            torch = self._torch
-            caller = torch.cuda.current_stream(self.ids.device)
-            self._ctx.stream.wait_stream(caller)
-            with torch.cuda.stream(self._ctx.stream):
+            with OnStream(self._ctx, self.ids):
                 self._empty_table()
-            caller.wait_stream(self._ctx.stream)
         return self
 
     def live(self):
@@ -138,9 +133,7 @@ class KltVideoTracker:
         device = torch.device("cuda", ctx.device_index)
         if not host and image.device != device:
             raise ValueError(f"image must be on {device}, the context's device (got one on {image.device})")
-        caller = torch.cuda.current_stream(device)
-        ctx.stream.wait_stream(caller)
-        with torch.cuda.stream(ctx.stream):
+        with OnStream(ctx, device):
             if self.ids is None:
                 self._allocate(device)
             if self._pyramids is None:
@@ -161,10 +154,7 @@ class KltVideoTracker:
                 fill = self._bound[("fill", self._spare)] = track_table_fill_args(
                     ctx, cur, self.min_distance, self.min_response, self.ids, self.points, self.prev_points, self.status, self.age, self.n_live, self.next_id,
                     self._free, self._n_free)
-            rc = N.lib().ftk_track_table_fill_device(*fill)
-            if rc != 0:
-                N.check(rc, ctx.handle)
-        caller.wait_stream(ctx.stream)
+            call("ftk_track_table_fill_device", fill, ctx)
         self._spare = 1 - self._spare
         self._frames += 1
         return self
@@ -263,9 +253,7 @@ class KltVideoTracker:
             retire = self._bound["retire"] = track_table_retire_args(
                 ctx, self.ids, self.points, self.prev_points, self.status, self.age, self.n_live, self._uv[0], self._st[0], self._free, self._n_free,
                 self._uv[1] if fb else None, self._st[1] if fb else None, self.forward_backward if fb else 0.0)
-        rc = N.lib().ftk_track_table_retire_device(*retire)
-        if rc != 0:
-            N.check(rc, ctx.handle)
+        call("ftk_track_table_retire_device", retire, ctx)
 
     def _reject_outliers(self):
         """The forward results against the best fundamental matrix (or the chosen model): ``_st[0]`` of a tracked slot that disagrees becomes LARGE_RESIDUAL."""
@@ -276,9 +264,7 @@ class KltVideoTracker:
             args = self._bound[key] = list(marshal(ctx, self.points, self._uv[0], self._st[0], self._shape, self.epipolar_threshold, self.epipolar_hypotheses, 0,
                                                    *rest, stream=ctx.stream))
         args[SEED_ARG] = C.c_uint32((self.epipolar_seed + self._frames) & 0xFFFFFFFF)
-        rc = getattr(N.lib(), entry)(*args)
-        if rc != 0:
-            N.check(rc, ctx.handle)
+        call(entry, args, ctx)
 
 
 _MODEL_NAMES = {v: k for k, v in N.MODELS.items()}

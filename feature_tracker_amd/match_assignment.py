@@ -10,6 +10,7 @@ from __future__ import annotations
 
 from . import _native as N
 from ._device_match_assignment import check_row_stride, check_scale, check_sizes, match_assignment_args
+from ._torch_call import OnStream, PerKey, call, check_ctx, complain, complain_cuda, words
 
 _KEYS = ("final_proj.weight", "final_proj.bias", "matchability.weight", "matchability.bias")
 
@@ -32,15 +33,13 @@ class MatchAssignment:
     def __init__(self, dim: int, packed_weights=None, packed_bias=None, scale=None, ctx=None):
         if isinstance(dim, bool) or not isinstance(dim, int) or not 1 <= dim <= N.FTK_MATCH_ASSIGNMENT_MAX_DIM:
             raise ValueError(f"dim must be an integer in 1 .. FTK_MATCH_ASSIGNMENT_MAX_DIM = {N.FTK_MATCH_ASSIGNMENT_MAX_DIM} (got {dim!r})")
-        if ctx is not None and getattr(ctx, "stream", None) is None:
-            raise ValueError("ctx must come from device.context_on_stream(stream): torch must know the stream the kernels run on (None: torch's "
-                             "current stream)")
+        check_ctx(ctx)
         self.dim = dim
         self.with_weights = packed_weights is not None
         self.scale = 1.0 if self.with_weights else check_scale(dim ** -0.25 if scale is None else scale)
         self._packed = {} if packed_weights is None else {packed_weights.device: (packed_weights, packed_bias)}
         self._ctx = ctx
-        self._workspace = {}  # (device, M, N) -> the workspace of that size
+        self._workspace = PerKey()  # (device, M, N) -> the workspace of that size
 
     @classmethod
     def from_state_dict(cls, sd, prefix: str = "log_assignment.8.", ctx=None) -> "MatchAssignment":
@@ -83,10 +82,7 @@ class MatchAssignment:
             tensors.append(("count0", count0, D._I32, (1,)))
         if count1 is not None:
             tensors.append(("count1", count1, D._I32, (1,)))
-        for name, t, dtypes, shape in tensors:
-            complaint = D._tensor_complaint(name, t, dtypes, shape)
-            if complaint:
-                raise ValueError(complaint)
+        complain(tensors, cuda=False)
         m, n = int(desc0.shape[0]), int(desc1.shape[0])
         check_sizes(m, n, self.dim)
         if out is not None:
@@ -98,9 +94,7 @@ class MatchAssignment:
             row_stride = int(out.stride(0))
             tensors.append(("out", out, None, None))
         stride = check_row_stride(row_stride, n)
-        for name, t, _, _ in tensors:
-            if not t.is_cuda:
-                raise ValueError(f"{name} must be a CUDA tensor (got one on {t.device}): there is no CPU fallback")
+        complain_cuda((name, t) for name, t, _, _ in tensors)
         return m, n, stride
 
     def assign(self, desc0, desc1, count0=None, count1=None, out=None, row_stride=None):
@@ -122,45 +116,28 @@ class MatchAssignment:
     def _run(self, desc0, desc1, count0, count1, out, m, n, stride, min_score):
         from . import device as D
 
-        torch = D._torch()
-        ctx = self._ctx
-        if ctx is None:
-            from .raft import _device_context
-
-            ctx = _device_context(desc0)
         device = desc0.device
-        caller = torch.cuda.current_stream(device)
-        stream = getattr(ctx, "stream", None) or caller
-        if stream != caller:
-            stream.wait_stream(caller)
-        with torch.cuda.stream(stream):
+        with OnStream(self._ctx, desc0) as on:
+            torch, ctx, stream = on.torch, on.ctx, on.stream
             weights = bias = None
             if self.with_weights:
                 if device not in self._packed:
                     w, b = next(iter(self._packed.values()))
                     self._packed[device] = (w.to(device), b.to(device))
                 weights, bias = self._packed[device]
-            key = (device, m, n)
-            workspace = self._workspace.get(key)
-            if workspace is None:
-                words = -(-N.match_assignment_workspace_bytes(m, n, self.dim, self.with_weights) // 8)
-                workspace = self._workspace[key] = torch.empty(words, dtype=torch.int64, device=device)
+            workspace = self._workspace.of((device, m, n), lambda: words(torch, N.match_assignment_workspace_bytes(m, n, self.dim, self.with_weights), device))
             if out is None:
                 flat = torch.empty((m + 1) * stride, dtype=torch.float32, device=device)
                 scores = flat.as_strided((m + 1, n + 1), (stride, 1))
             else:
                 scores = out
                 flat = out.as_strided((m * stride + n + 1,), (1,))
-            args = match_assignment_args(ctx, desc0, desc1, weights, bias, self.scale, count0, count1, workspace, flat, stride, stream)
-            rc = N.lib().ftk_match_assignment_device(*args)
-            if rc != 0:
-                N.check(rc, ctx.handle)
+            call("ftk_match_assignment_device", match_assignment_args(ctx, desc0, desc1, weights, bias, self.scale, count0, count1, workspace, flat, stride, stream),
+                 ctx)
             result = scores
             if min_score is not None:
                 match_index = torch.empty((1, m), dtype=torch.int32, device=device)
                 status = torch.empty((1, m), dtype=torch.uint8, device=device)
                 D.nn_match_scores_device(ctx, scores[:m, :n].unsqueeze(0), min_score, match_index, status, stream)
                 result = (scores, match_index[0], status[0])
-        if stream != caller:
-            caller.wait_stream(stream)
         return result

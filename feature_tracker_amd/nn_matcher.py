@@ -23,6 +23,7 @@ import numpy as np
 
 from . import _native as N
 from . import device as D
+from ._torch_call import context_of_index
 from .tracker import Context, _ptr, default_context
 
 
@@ -71,8 +72,7 @@ class NNFeatureMatcher:
             return self._ctx
         if device_index is None:
             return default_context()
-        from .raft import _context  # one library context per torch device
-        return _context(device_index)
+        return context_of_index(device_index)  # one library context per torch device
 
     # ---- score-matrix models ----
 

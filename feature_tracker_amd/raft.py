@@ -28,21 +28,12 @@ Inference only, float32 only, and no CPU fallback.
 from __future__ import annotations
 
 import math
-from typing import Dict, List, Mapping
+from typing import List, Mapping
 
 from . import _native as N
 from . import device as D
-from .tracker import Context
-
-_contexts: Dict[int, Context] = {}
-
-
-def _context(index: int) -> Context:
-    """One library context per device: it selects the device and records errors; the launches go to torch's current stream."""
-    ctx = _contexts.get(index)
-    if ctx is None:
-        ctx = _contexts[index] = Context(index)
-    return ctx
+from ._torch_call import context_of as _device_context
+from ._torch_call import context_of_index as _context  # noqa: F401  (the name tests and scripts ask this module for)
 
 
 def _check_no_grad(torch, *tensors, what: str = "CorrelationPyramid") -> None:
@@ -75,7 +66,7 @@ class CorrelationPyramid:
         self.radius = int(radius)
         self._shape = (B, H, W)
         self._device = fmap0.device
-        self._ctx = _context(fmap0.device.index if fmap0.device.index is not None else torch.cuda.current_device())
+        self._ctx = _device_context(fmap0)
         self._volume = torch.empty(elements, dtype=torch.float32, device=fmap0.device)
         D.corr_pyramid_build_device(self._ctx, fmap0.contiguous(), fmap1.contiguous(), self.num_levels, self._volume)
         n = B * H * W
@@ -150,7 +141,7 @@ class OnDemandCorrelation:
         self._shape = (B, H, W)
         self._channels = int(C)
         self._device = fmap0.device
-        self._ctx = _context(fmap0.device.index if fmap0.device.index is not None else torch.cuda.current_device())
+        self._ctx = _device_context(fmap0)
         self._workspace = torch.empty(elements, dtype=torch.float32, device=fmap0.device)
         D.corr_ondemand_prepare_device(self._ctx, fmap0.contiguous(), fmap1.contiguous(), self.num_levels, self._workspace)
 
@@ -207,7 +198,7 @@ def upsample_flow(flow, mask, mask_scale: float = 1.0):
         raise ValueError(f"flow and mask must be CUDA tensors (got them on {flow.device}): there is no CPU fallback")
     _check_no_grad(torch, flow, mask, what="upsample_flow")
     torch = D._torch()
-    ctx = _context(flow.device.index if flow.device.index is not None else torch.cuda.current_device())
+    ctx = _device_context(flow)
     out = torch.empty((B, 2, 8 * H, 8 * W), dtype=torch.float32, device=flow.device)
     D.flow_upsample_device(ctx, flow.contiguous(), mask.contiguous(), out, mask_scale)
     return out
@@ -430,7 +421,7 @@ class SepConvGru:
         if self._packed["q_horizontal"].device != h.device:
             raise ValueError(f"the weights are on {self._packed['q_horizontal'].device}, x and h on {h.device}")
         torch = D._torch()
-        ctx = _context(h.device.index if h.device.index is not None else torch.cuda.current_device())
+        ctx = _device_context(h)
         z, rh, mid, out = (torch.empty((B, Ch, H, W), dtype=torch.float32, device=h.device) for _ in range(4))
         D.sep_conv_gru_device(ctx, [p.contiguous() for p in parts], h.contiguous(), self._packed, self.kernel_size, z, rh, mid, out)
         return out
@@ -531,8 +522,6 @@ def _conv(ctx, parts, layer, relu: bool, out_scale: float = 1.0):
     return out
 
 
-def _device_context(t):
-    return _context(t.device.index if t.device.index is not None else D._torch().cuda.current_device())
 
 
 class MotionEncoder:

@@ -13,7 +13,8 @@ from typing import Dict, Mapping
 
 from . import _native as N
 from . import device as D
-from .raft import _check_no_grad, _device_context, _pack_conv, _state_tensor
+from ._torch_call import OnStream, PerKey, check_ctx
+from .raft import _check_no_grad, _pack_conv, _state_tensor
 
 # upstream's layer names in forward order: (name, kernel size)
 TRUNK = (("conv1a", 3), ("conv1b", 3), ("conv2a", 3), ("conv2b", 3), ("conv3a", 3), ("conv3b", 3), ("conv4a", 3), ("conv4b", 3))
@@ -40,9 +41,7 @@ class SuperPoint:
     def __init__(self, state: Mapping, prefix: str = "", ctx=None):
         import torch
 
-        if ctx is not None and getattr(ctx, "stream", None) is None:
-            raise ValueError("ctx must come from device.context_on_stream(stream): torch must know the stream the kernels run on (None: torch's "
-                             "current stream)")
+        check_ctx(ctx)
         self._ctx = ctx
         taken, device, previous = {}, None, 1  # the image is one channel
         trunk_out = None
@@ -87,7 +86,7 @@ class SuperPoint:
         self._layers["convPa+convDa"] = (_pack_conv(stacked), torch.cat([taken["convPa.bias"], taken["convDa.bias"]], 0).contiguous(), 3,
                                          self.detector_hidden + self.descriptor_hidden)
         self._device = device
-        self._buffers = {}  # (device, H, W) -> the tensors of a pass at that size
+        self._buffers = PerKey()  # (device, H, W) -> the tensors of a pass at that size
 
     @classmethod
     def from_state_dict(cls, state: Mapping, prefix: str = "", ctx=None):
@@ -153,20 +152,10 @@ class SuperPoint:
     def heads(self, image):
         """One image to the two head tensors ``KeypointDecoder.decode`` takes.  Everything is enqueued; nothing is read on the host."""
         H, W = self._check_image(image)
-        torch = D._torch()
-        ctx = self._ctx if self._ctx is not None else _device_context(image)
         device = image.device
-        caller = torch.cuda.current_stream(device)
-        stream = getattr(ctx, "stream", None) or caller
-        if stream != caller:
-            stream.wait_stream(caller)
-        with torch.cuda.stream(stream):
-            bufs = self._buffers.get((device, H, W))
-            if bufs is None:
-                bufs = self._buffers[(device, H, W)] = self._allocate(H, W, device)
-            self._forward(ctx, image.view(1, 1, H, W), bufs, stream)
-        if stream != caller:
-            caller.wait_stream(stream)
+        with OnStream(self._ctx, image) as on:
+            bufs = self._buffers.of((device, H, W), lambda: self._allocate(H, W, device))
+            self._forward(on.ctx, image.view(1, 1, H, W), bufs, on.stream)
         return bufs["convPb"][0], bufs["desc"].permute(2, 0, 1)
 
     def detect(self, image, decoder, occupied=None, occupied_mask=None, return_heatmap: bool = False):

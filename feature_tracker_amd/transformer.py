@@ -13,58 +13,10 @@ from . import _native as N
 from ._device_lightglue_adaptive import (check_confidence, check_min_keypoints, lightglue_adapt_step_args, lightglue_confidence_args,
                                          lightglue_finish_args, stop_threshold, transformer_layer_adaptive_args)
 from ._device_transformer import attention_args, check_heads, check_rows, linear_args, transformer_layer_args
+from ._torch_call import OnStream, PerKey, call, check_ctx, complain, words
 
 _SELF = ("self_attn.Wqkv", "self_attn.out_proj", "self_attn.ffn.0", "self_attn.ffn.1", "self_attn.ffn.3")
 _CROSS = ("cross_attn.to_qk", "cross_attn.to_v", "cross_attn.to_out", "cross_attn.ffn.0", "cross_attn.ffn.1", "cross_attn.ffn.3")
-
-
-def _check_ctx(ctx):
-    if ctx is not None and getattr(ctx, "stream", None) is None:
-        raise ValueError("ctx must come from device.context_on_stream(stream): torch must know the stream the kernels run on (None: torch's "
-                         "current stream)")
-
-
-class _OnStream:
-    """The context and stream of a call: ``ctx``'s stream where it has one, else torch's current stream; the caller's stream waits for the
-    work on the way out."""
-
-    def __init__(self, ctx, tensor):
-        from . import device as D
-
-        self.torch = D._torch()
-        if ctx is None:
-            from .raft import _device_context
-
-            ctx = _device_context(tensor)
-        self.ctx = ctx
-        self.caller = self.torch.cuda.current_stream(tensor.device)
-        self.stream = getattr(ctx, "stream", None) or self.caller
-
-    def __enter__(self):
-        if self.stream != self.caller:
-            self.stream.wait_stream(self.caller)
-        self._guard = self.torch.cuda.stream(self.stream)
-        self._guard.__enter__()
-        return self
-
-    def __exit__(self, *exc):
-        self._guard.__exit__(*exc)
-        if self.stream != self.caller and exc[0] is None:
-            self.caller.wait_stream(self.stream)
-        return False
-
-
-def _complain(tensors, cuda=True):
-    """``device._tensor_complaint`` of (name, tensor, dtypes, shape) in turn, then (``cuda``) that each is a CUDA tensor."""
-    from . import device as D
-
-    for name, t, dtypes, shape in tensors:
-        complaint = D._tensor_complaint(name, t, dtypes, shape)
-        if complaint:
-            raise ValueError(complaint)
-    for name, t, _, _ in tensors if cuda else ():
-        if not t.is_cuda:
-            raise ValueError(f"{name} must be a CUDA tensor (got one on {t.device}): there is no CPU fallback")
 
 
 def attention(q, k, v, count=None, pre_scale=1.0, post_scale=None, ctx=None):
@@ -74,22 +26,19 @@ def attention(q, k, v, count=None, pre_scale=1.0, post_scale=None, ctx=None):
     launch, nothing read back."""
     from . import device as D
 
-    _check_ctx(ctx)
+    check_ctx(ctx)
     tensors = [("q", q, D._F32, (None, None, None))]
-    _complain(tensors[:1], cuda=False)
+    complain(tensors[:1], cuda=False)
     m, h, dh = (int(e) for e in q.shape)
     tensors += [("k", k, D._F32, (None, h, dh))]
-    _complain(tensors[1:], cuda=False)
+    complain(tensors[1:], cuda=False)
     tensors += [("v", v, D._F32, (int(k.shape[0]), h, dh))]
     if count is not None:
         tensors.append(("count", count, D._I32, (1,)))
-    _complain(tensors)
-    with _OnStream(ctx, q) as on:
+    complain(tensors)
+    with OnStream(ctx, q) as on:
         out = on.torch.empty_like(q)
-        args = attention_args(on.ctx, q, k, v, count, pre_scale, post_scale, out, on.stream)
-        rc = N.lib().ftk_attention_device(*args)
-        if rc != 0:
-            N.check(rc, on.ctx.handle)
+        call("ftk_attention_device", attention_args(on.ctx, q, k, v, count, pre_scale, post_scale, out, on.stream), on.ctx)
     return out
 
 
@@ -152,11 +101,11 @@ class TransformerLayer:
 
     def __init__(self, dim: int, num_heads: int, packed, ctx=None):
         self.head_dim = check_heads(dim, num_heads)
-        _check_ctx(ctx)
+        check_ctx(ctx)
         self.dim, self.num_heads = dim, num_heads
         self._packed = {packed.device: packed}
         self._ctx = ctx
-        self._workspace = {}  # (device, M, N) -> the workspace of that size
+        self._workspace = PerKey()  # (device, M, N) -> the workspace of that size
 
     @classmethod
     def from_state_dict(cls, sd, prefix: str = "transformers.0.", num_heads: int = 4, ctx=None) -> "TransformerLayer":
@@ -193,7 +142,7 @@ class TransformerLayer:
         from . import device as D
 
         tensors = [("desc0", desc0, D._F32, (None, self.dim)), ("desc1", desc1, D._F32, (None, self.dim))]
-        _complain(tensors, cuda=False)
+        complain(tensors, cuda=False)
         m, n = int(desc0.shape[0]), int(desc1.shape[0])
         check_rows("desc0 and desc1", m, n)
         tensors += [("enc0", enc0, D._F32, (2, m, self.head_dim)), ("enc1", enc1, D._F32, (2, n, self.head_dim))]
@@ -201,12 +150,12 @@ class TransformerLayer:
             tensors.append(("count0", count0, D._I32, (1,)))
         if count1 is not None:
             tensors.append(("count1", count1, D._I32, (1,)))
-        _complain(tensors)
+        complain(tensors)
         return m, n
 
     def __call__(self, desc0, desc1, enc0, enc1, count0=None, count1=None):
         m, n = self._validate(desc0, desc1, enc0, enc1, count0, count1)
-        with _OnStream(self._ctx, desc0) as on:
+        with OnStream(self._ctx, desc0) as on:
             out = self._run(on, desc0, desc1, enc0, enc1, count0, count1, m, n)
         return out
 
@@ -214,17 +163,10 @@ class TransformerLayer:
         torch, device = on.torch, desc0.device
         if device not in self._packed:
             self._packed[device] = next(iter(self._packed.values())).to(device)
-        key = (device, m, n)
-        workspace = self._workspace.get(key)
-        if workspace is None:
-            words = -(-N.transformer_layer_workspace_bytes(m, n, self.dim, self.num_heads) // 8)
-            workspace = self._workspace[key] = torch.empty(words, dtype=torch.int64, device=device)
+        workspace = self._workspace.of((device, m, n), lambda: words(torch, N.transformer_layer_workspace_bytes(m, n, self.dim, self.num_heads), device))
         out0, out1 = torch.empty_like(desc0), torch.empty_like(desc1)
-        args = transformer_layer_args(on.ctx, desc0, desc1, self.num_heads, enc0, enc1, self._packed[device], count0, count1, workspace, out0, out1,
-                                      on.stream)
-        rc = N.lib().ftk_transformer_layer_device(*args)
-        if rc != 0:
-            N.check(rc, on.ctx.handle)
+        call("ftk_transformer_layer_device", transformer_layer_args(on.ctx, desc0, desc1, self.num_heads, enc0, enc1, self._packed[device], count0, count1,
+                                                                    workspace, out0, out1, on.stream), on.ctx)
         return out0, out1
 
 
@@ -240,17 +182,17 @@ class LightGlue:
     mode that skips the launches of a stopped layer, a batch dimension, a C++ class."""
 
     def __init__(self, layers, head, Wr, input_proj=None, ctx=None, adaptive=None):
-        _check_ctx(ctx)
+        check_ctx(ctx)
         self.layers, self.head, self.Wr, self.input_proj, self._ctx = list(layers), head, Wr, input_proj, ctx
         # (depth_confidence, width_confidence, pruning_min_keypoints, token_w [L, D], token_b [L], head_w [L, D + 1, D], head_b [L, D + 1])
         self._adaptive = adaptive
         self._adaptive_moved = {}
-        self._adaptive_buffers = {}  # (device, M, N) -> the pass's buffers
+        self._adaptive_buffers = PerKey()  # (device, M, N) -> the pass's buffers
         self._adaptive_sizes = {}    # (device, width, height) -> the image size on the device
         self.dim, self.num_heads = self.layers[0].dim, self.layers[0].num_heads
         self._moved = {}
         # the layers run one after another on one stream: one workspace per (device, M, N) serves them all
-        self._workspace = {}
+        self._workspace = PerKey()
         for layer in self.layers:
             layer._workspace = self._workspace
 
@@ -326,7 +268,7 @@ class LightGlue:
             raise ValueError(f"min_score must be a number (got {min_score!r})")
         d_in = self.dim if self.input_proj is None else int(self.input_proj[0].shape[1])
         tensors = [("desc0", desc0, D._F32, (None, d_in)), ("desc1", desc1, D._F32, (None, d_in))]
-        _complain(tensors, cuda=False)
+        complain(tensors, cuda=False)
         m, n = int(desc0.shape[0]), int(desc1.shape[0])
         check_rows("desc0 and desc1", m, n)
         tensors += [("kpts0", kpts0, D._F32, (m, 2)), ("kpts1", kpts1, D._F32, (n, 2))]
@@ -334,7 +276,7 @@ class LightGlue:
             tensors.append(("count0", count0, D._I32, (1,)))
         if count1 is not None:
             tensors.append(("count1", count1, D._I32, (1,)))
-        _complain(tensors)
+        complain(tensors)
         return m, n
 
     def _inputs(self, on, kpts0, kpts1, desc0, desc1, size0, size1):
@@ -348,9 +290,7 @@ class LightGlue:
             projected = []
             for x in (desc0, desc1):
                 out = torch.empty((int(x.shape[0]), self.dim), dtype=torch.float32, device=device)
-                rc = N.lib().ftk_linear_device(*linear_args(on.ctx, x, proj[0], proj[1], out, on.stream))
-                if rc != 0:
-                    N.check(rc, on.ctx.handle)
+                call("ftk_linear_device", linear_args(on.ctx, x, proj[0], proj[1], out, on.stream), on.ctx)
                 projected.append(out)
             desc0, desc1 = projected
         return desc0, desc1, rotary_encoding(kpts0, size0, Wr), rotary_encoding(kpts1, size1, Wr)
@@ -364,7 +304,7 @@ class LightGlue:
     def scores(self, kpts0, kpts1, desc0, desc1, size0, size1, count0=None, count1=None):
         """``scores`` float32 [M + 1, N + 1], as ``MatchAssignment.assign`` lays it out."""
         m, n = self._validate(kpts0, kpts1, desc0, desc1, size0, size1, count0, count1)
-        with _OnStream(self._ctx, desc0) as on:
+        with OnStream(self._ctx, desc0) as on:
             desc0, desc1 = self._descriptors(on, kpts0, kpts1, desc0, desc1, size0, size1, count0, count1, m, n)
             result = self.head.assign(desc0, desc1, count0, count1)
         return result
@@ -372,7 +312,7 @@ class LightGlue:
     def match(self, kpts0, kpts1, desc0, desc1, size0, size1, count0=None, count1=None, min_score: float = -1.0e30):
         """``(scores, match_index int32 [M], status uint8 [M])``, as ``MatchAssignment.match`` returns them."""
         m, n = self._validate(kpts0, kpts1, desc0, desc1, size0, size1, count0, count1, min_score)
-        with _OnStream(self._ctx, desc0) as on:
+        with OnStream(self._ctx, desc0) as on:
             desc0, desc1 = self._descriptors(on, kpts0, kpts1, desc0, desc1, size0, size1, count0, count1, m, n)
             result = self.head.match(desc0, desc1, count0, count1, min_score=min_score)
         return result
@@ -384,20 +324,18 @@ class LightGlue:
         torch = on.torch
         if device not in self._adaptive_moved:
             self._adaptive_moved[device] = tuple(t.to(device) for t in self._adaptive[3:])
-        key = (device, m, n)
-        b = self._adaptive_buffers.get(key)
-        if b is None:
-            dh, L = self.layers[0].head_dim, len(self.layers)
-            f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=device)  # noqa: E731
-            i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=device)  # noqa: E731
-            b = dict(halves=[(f32(m, self.dim), f32(n, self.dim), f32(2, m, dh), f32(2, n, dh), i32(m), i32(n)) for _ in range(2)],
-                     conf=f32(m + n), mt=f32(m + n), scores=f32(m + 1, n + 1), match_index=i32(m),
-                     status=torch.empty((m,), dtype=torch.uint8, device=device), state=i32(N.FTK_LIGHTGLUE_STATE_WORDS), layers=i32(m + n),
-                     identity=torch.arange(max(m, n), dtype=torch.int32, device=device),
-                     start=torch.tensor([m, n, 0, L - 1], dtype=torch.int32, device=device),
-                     workspace=torch.empty(-(-N.lightglue_adaptive_workspace_bytes(m, n, self.dim, self.num_heads) // 8), dtype=torch.int64, device=device))
-            self._adaptive_buffers[key] = b
-        return self._adaptive_moved[device], b
+        return self._adaptive_moved[device], self._adaptive_buffers.of((device, m, n), lambda: self._adaptive_allocate(torch, device, m, n))
+
+    def _adaptive_allocate(self, torch, device, m, n):
+        dh, L = self.layers[0].head_dim, len(self.layers)
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=device)  # noqa: E731
+        i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=device)  # noqa: E731
+        return dict(halves=[(f32(m, self.dim), f32(n, self.dim), f32(2, m, dh), f32(2, n, dh), i32(m), i32(n)) for _ in range(2)],
+                    conf=f32(m + n), mt=f32(m + n), scores=f32(m + 1, n + 1), match_index=i32(m),
+                    status=torch.empty((m,), dtype=torch.uint8, device=device), state=i32(N.FTK_LIGHTGLUE_STATE_WORDS), layers=i32(m + n),
+                    identity=torch.arange(max(m, n), dtype=torch.int32, device=device),
+                    start=torch.tensor([m, n, 0, L - 1], dtype=torch.int32, device=device),
+                    workspace=words(torch, N.lightglue_adaptive_workspace_bytes(m, n, self.dim, self.num_heads), device))
 
     def match_adaptive(self, kpts0, kpts1, desc0, desc1, size0, size1, count0=None, count1=None, min_score: float = -1.0e30):
         """Upstream's forward pass with early stopping and point pruning, entirely on the stream.  Returns an
@@ -412,7 +350,7 @@ class LightGlue:
         m, n = self._validate(kpts0, kpts1, desc0, desc1, size0, size1, count0, count1, min_score)
         depth, width, min_keypoints = self._adaptive[:3]
         L = len(self.layers)
-        with _OnStream(self._ctx, desc0) as on:
+        with OnStream(self._ctx, desc0) as on:
             torch, device = on.torch, desc0.device
             (token_w, token_b, head_w, head_b), b = self._adaptive_state(on, device, m, n)
             # the image sizes as device tensors, made once: rotary_encoding then uploads nothing, and the pass can be captured
@@ -434,30 +372,25 @@ class LightGlue:
             layers.zero_()
             live0, live1, gate = state[0:1], state[1:2], state[2:3]
             layers0, layers1 = layers[:m], layers[m:]
-            lib, d = N.lib(), self.dim
+            d = self.dim
             for i, layer in enumerate(self.layers):
                 cur, nxt = halves[i % 2], halves[(i + 1) % 2]
                 if device not in layer._packed:
                     layer._packed[device] = next(iter(layer._packed.values())).to(device)
-                rc = lib.ftk_transformer_layer_adaptive_device(*transformer_layer_adaptive_args(
-                    on.ctx, cur[0], cur[1], self.num_heads, cur[2], cur[3], layer._packed[device], live0, live1, gate, ws, on.stream))
-                if rc == 0 and i < L - 1:
-                    rc = lib.ftk_lightglue_confidence_device(*lightglue_confidence_args(
+                call("ftk_transformer_layer_adaptive_device", transformer_layer_adaptive_args(
+                    on.ctx, cur[0], cur[1], self.num_heads, cur[2], cur[3], layer._packed[device], live0, live1, gate, ws, on.stream), on.ctx)
+                if i < L - 1:
+                    call("ftk_lightglue_confidence_device", lightglue_confidence_args(
                         on.ctx, cur[0], cur[1], token_w[i], token_b[i:i + 1], head_w[i, d], head_b[i, d:d + 1], live0, live1, gate, b["conf"], b["mt"],
-                        on.stream))
-                if rc == 0 and i < L - 1:
-                    rc = lib.ftk_lightglue_adapt_step_device(*lightglue_adapt_step_args(
+                        on.stream), on.ctx)
+                    call("ftk_lightglue_adapt_step_device", lightglue_adapt_step_args(
                         on.ctx, self.num_heads, i, b["conf"], b["mt"], count0, count1, state, stop_threshold(i, L), depth, width, min_keypoints, cur, nxt,
-                        layers0, layers1, ws, on.stream))
-                if rc != 0:
-                    N.check(rc, on.ctx.handle)
+                        layers0, layers1, ws, on.stream), on.ctx)
             last = halves[(L - 1) % 2]
             scores, match_index, status = b["scores"], b["match_index"], b["status"]
-            rc = lib.ftk_lightglue_finish_device(*lightglue_finish_args(
+            call("ftk_lightglue_finish_device", lightglue_finish_args(
                 on.ctx, last[0], last[1], self.num_heads, head_w, head_b, state, last[4], last[5], float(min_score), ws, scores, match_index, status,
-                layers0, layers1, on.stream))
-            if rc != 0:
-                N.check(rc, on.ctx.handle)
+                layers0, layers1, on.stream), on.ctx)
         return AdaptiveMatches(match_index, status, scores, last[4], last[5], live0, live1, state[3:4], layers0, layers1)
 
 

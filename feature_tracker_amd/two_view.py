@@ -12,6 +12,7 @@ from typing import Optional
 from . import _native as N
 from ._device_epipolar import check_sizes
 from ._device_two_view import check_mode, prefer_to_permille, two_view_ransac_args
+from ._torch_call import PerDevice, check_ctx
 from .epipolar import ransac_filter
 
 
@@ -48,11 +49,9 @@ class TwoViewRansac:
         self.model = model
         self.prefer_homography_permille = prefer_to_permille(prefer_homography)
         _, _, self.threshold, self.hypotheses, self.seed = check_sizes((1, 1), threshold, hypotheses, seed)
-        if ctx is not None and getattr(ctx, "stream", None) is None:
-            raise ValueError("ctx must come from device.context_on_stream(stream): torch must know the stream the kernels run on (None: torch's "
-                             "current stream)")
+        check_ctx(ctx)
         self._ctx = ctx
-        self._workspace = {}  # device -> the one workspace of this object on it, grown to the largest call so far
+        self._workspace = PerDevice()  # device -> the one workspace of this object on it, grown to the largest call so far
 
     def filter(self, ref_uv, cur_uv, status, image_size, seed: Optional[int] = None, return_hypotheses: bool = False) -> TwoViewResult:
         """One pass of outlier rejection; ``seed``: this call's seed instead of the object's; ``return_hypotheses``: also ``counts`` and
