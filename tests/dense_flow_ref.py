@@ -9,15 +9,14 @@ restatement stage by stage and end to end; tests/test_dense_ref64_gpu.py compare
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 
+from tests.ref_build import compile_ref
+
 _SRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "dense_flow_ref.c")
-_lib = None
-_tmpdir = None
 
 
 class Options(C.Structure):
@@ -29,27 +28,21 @@ def options(max_iteration=10, half_patch=2, max_converge_step=1e-6, max_delta_fl
     return Options(int(max_iteration), int(half_patch), float(max_converge_step), float(max_delta_flow_step))
 
 
+@functools.lru_cache(maxsize=None)
 def lib():
-    global _lib, _tmpdir
-    if _lib is None:
-        _tmpdir = tempfile.TemporaryDirectory(prefix="dense_flow_ref_")
-        path = os.path.join(_tmpdir.name, "libdense_flow_ref.so")
-        subprocess.run(["gcc", "-O3", "-std=c99", "-ffp-contract=off", "-fno-fast-math", "-shared", "-fPIC", "-o", path, _SRC, "-lm"],
-                       check=True, capture_output=True)
-        l = C.CDLL(path)
-        vp, i32, f32 = C.c_void_p, C.c_int32, C.c_float
-        l.dfr_interpolate.argtypes = [vp, i32, i32, f32, f32]
-        l.dfr_interpolate.restype = f32
-        l.dfr_median9.argtypes = [vp]
-        l.dfr_median9.restype = f32
-        l.dfr_gaussian.argtypes = [i32, vp, vp]
-        l.dfr_moments_f32.argtypes = [vp, i32, i32, i32, vp, vp]
-        l.dfr_moments_u8.argtypes = [vp, i32, i32, i32, vp, vp]
-        l.dfr_coefficients.argtypes = [vp, vp, vp, vp]
-        l.dfr_track_image.argtypes = [vp, i32, i32, vp, i32, i32, C.POINTER(Options), vp, vp, vp, i32]
-        l.dfr_track_pyramid.argtypes = [vp, vp, vp, vp, vp, vp, i32, C.POINTER(Options), vp, vp, vp]
-        _lib = l
-    return _lib
+    l = compile_ref("dense_flow_ref", [_SRC])
+    vp, i32, f32 = C.c_void_p, C.c_int32, C.c_float
+    l.dfr_interpolate.argtypes = [vp, i32, i32, f32, f32]
+    l.dfr_interpolate.restype = f32
+    l.dfr_median9.argtypes = [vp]
+    l.dfr_median9.restype = f32
+    l.dfr_gaussian.argtypes = [i32, vp, vp]
+    l.dfr_moments_f32.argtypes = [vp, i32, i32, i32, vp, vp]
+    l.dfr_moments_u8.argtypes = [vp, i32, i32, i32, vp, vp]
+    l.dfr_coefficients.argtypes = [vp, vp, vp, vp]
+    l.dfr_track_image.argtypes = [vp, i32, i32, vp, i32, i32, C.POINTER(Options), vp, vp, vp, i32]
+    l.dfr_track_pyramid.argtypes = [vp, vp, vp, vp, vp, vp, i32, C.POINTER(Options), vp, vp, vp]
+    return l
 
 
 def _p(a):

@@ -9,14 +9,12 @@ from __future__ import annotations
 import ctypes as C
 import functools
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 
+from tests.ref_build import compile_ref
+
 _SRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "epipolar_ref.c")
-_lib = None
-_tmpdir = None
 
 NOT_TRACKED, TRACKED, LARGE_RESIDUAL, OUTSIDE, NUMERIC_ERROR = range(5)
 CONTRACT = 0
@@ -24,21 +22,15 @@ MUTANTS = {"highest_h_on_a_tie": 1, "f_applied_transposed": 2, "sampler_allows_d
 SAMPLE, ATTEMPTS = 8, 16
 
 
+@functools.lru_cache(maxsize=None)
 def lib():
-    global _lib, _tmpdir
-    if _lib is None:
-        _tmpdir = tempfile.TemporaryDirectory(prefix="epipolar_ref_")
-        path = os.path.join(_tmpdir.name, "libepipolar_ref.so")
-        flags = ["-O3", "-std=c99", "-ffp-contract=off", "-fno-fast-math"]
-        subprocess.run(["gcc"] + flags + ["-shared", "-fPIC", "-o", path, _SRC, "-lm"], check=True, capture_output=True)
-        l = C.CDLL(path)
-        vp, i32, u32 = C.c_void_p, C.c_int32, C.c_uint32
-        l.epr_mix32.argtypes = [u32, u32, u32, u32]
-        l.epr_mix32.restype = u32
-        l.epr_ransac.argtypes = [vp, vp, vp, i32, i32, i32, C.c_float, i32, u32, i32, vp, vp, vp, vp, vp, vp]
-        l.epr_ransac.restype = i32
-        _lib = l
-    return _lib
+    l = compile_ref("epipolar_ref", [_SRC])
+    vp, i32, u32 = C.c_void_p, C.c_int32, C.c_uint32
+    l.epr_mix32.argtypes = [u32, u32, u32, u32]
+    l.epr_mix32.restype = u32
+    l.epr_ransac.argtypes = [vp, vp, vp, i32, i32, i32, C.c_float, i32, u32, i32, vp, vp, vp, vp, vp, vp]
+    l.epr_ransac.restype = i32
+    return l
 
 
 class Result:

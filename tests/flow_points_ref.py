@@ -7,47 +7,32 @@ feature_tracker_amd/ may import it, and it imports nothing from there.
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 
+from tests.ref_build import FMA, STRICT, compile_ref
+
 _SRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "flow_points_ref.c")
-_lib = None
-_tmpdir = None
 
 CONTRACT, MUTANT_SWAPPED_UV, MUTANT_WRAPPED_NEIGHBOUR = 0, 1, 2
 NOT_TRACKED, TRACKED, LARGE_RESIDUAL, OUTSIDE, NUMERIC_ERROR = 0, 1, 2, 3, 4  # include/ftk.h's TrackStatus
 
 
-def _cpu_has_fma() -> bool:
-    try:
-        with open("/proc/cpuinfo") as f:
-            return any(line.startswith("flags") and " fma " in line + " " for line in f)
-    except OSError:
-        return False
-
-
+@functools.lru_cache(maxsize=None)
 def lib():
-    global _lib, _tmpdir
-    if _lib is None:
-        _tmpdir = tempfile.TemporaryDirectory(prefix="flow_points_ref_")
-        path = os.path.join(_tmpdir.name, "libflow_points_ref.so")
-        flags = ["-O3", "-std=c99", "-ffp-contract=off", "-fno-fast-math"] + (["-mfma"] if _cpu_has_fma() else [])
-        subprocess.run(["gcc"] + flags + ["-shared", "-fPIC", "-o", path, _SRC, "-lm"], check=True, capture_output=True)
-        l = C.CDLL(path)
-        vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
-        l.fpr_bilinear.argtypes = [f32] * 6
-        l.fpr_bilinear.restype = f32
-        l.fpr_bilinear_array.argtypes = [vp] * 6 + [i64, vp]
-        l.fpr_bilinear_array.restype = None
-        l.fpr_track.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, f32, i32, vp, vp, vp, vp]
-        l.fpr_track.restype = i32
-        l.fpr_track_dense.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, f32, i32, vp, vp, vp, vp]
-        l.fpr_track_dense.restype = i32
-        _lib = l
-    return _lib
+    l = compile_ref("flow_points_ref", [_SRC], flags=STRICT + FMA)  # -mfma where the CPU has it: fmaf as one instruction (see above)
+    vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
+    l.fpr_bilinear.argtypes = [f32] * 6
+    l.fpr_bilinear.restype = f32
+    l.fpr_bilinear_array.argtypes = [vp] * 6 + [i64, vp]
+    l.fpr_bilinear_array.restype = None
+    l.fpr_track.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, f32, i32, vp, vp, vp, vp]
+    l.fpr_track.restype = i32
+    l.fpr_track_dense.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, f32, i32, vp, vp, vp, vp]
+    l.fpr_track_dense.restype = i32
+    return l
 
 
 def _f32(a):

@@ -7,46 +7,31 @@ feature_tracker_amd/ may import it.
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 
+from tests.ref_build import FMA, STRICT, compile_ref
+
 _SRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "flow_upsample_ref.c")
-_lib = None
-_tmpdir = None
 
 CONTRACT, MUTANT_TRANSPOSED_WINDOW, MUTANT_DEGREE_3 = 0, 1, 2
 
 
-def _cpu_has_fma() -> bool:
-    try:
-        with open("/proc/cpuinfo") as f:
-            return any(line.startswith("flags") and " fma " in line + " " for line in f)
-    except OSError:
-        return False
-
-
+@functools.lru_cache(maxsize=None)
 def lib():
-    global _lib, _tmpdir
-    if _lib is None:
-        _tmpdir = tempfile.TemporaryDirectory(prefix="flow_upsample_ref_")
-        path = os.path.join(_tmpdir.name, "libflow_upsample_ref.so")
-        flags = ["-O3", "-std=c99", "-ffp-contract=off", "-fno-fast-math"] + (["-mfma"] if _cpu_has_fma() else [])
-        subprocess.run(["gcc"] + flags + ["-shared", "-fPIC", "-o", path, _SRC, "-lm"], check=True, capture_output=True)
-        l = C.CDLL(path)
-        vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
-        l.fur_exp_c.argtypes = [f32]
-        l.fur_exp_c.restype = f32
-        l.fur_exp_c_array.argtypes = [vp, i64, vp]
-        l.fur_exp_c_array.restype = None
-        l.fur_cutoff.argtypes = []
-        l.fur_cutoff.restype = f32
-        l.fur_upsample.argtypes = [vp, vp, i32, i32, i32, f32, i32, vp]
-        l.fur_upsample.restype = i32
-        _lib = l
-    return _lib
+    l = compile_ref("flow_upsample_ref", [_SRC], flags=STRICT + FMA)  # -mfma where the CPU has it: fmaf as one instruction (see above)
+    vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
+    l.fur_exp_c.argtypes = [f32]
+    l.fur_exp_c.restype = f32
+    l.fur_exp_c_array.argtypes = [vp, i64, vp]
+    l.fur_exp_c_array.restype = None
+    l.fur_cutoff.argtypes = []
+    l.fur_cutoff.restype = f32
+    l.fur_upsample.argtypes = [vp, vp, i32, i32, i32, f32, i32, vp]
+    l.fur_upsample.restype = i32
+    return l
 
 
 def _p(a):

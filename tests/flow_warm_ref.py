@@ -7,34 +7,26 @@ feature_tracker_amd/ may import it, and it imports nothing from there.
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 
-from tests.flow_points_ref import _cpu_has_fma, same  # noqa: F401  (same: bit-identical arrays, any NaN equals any NaN)
+from tests.flow_points_ref import same  # noqa: F401  (same: bit-identical arrays, any NaN equals any NaN)
+from tests.ref_build import FMA, STRICT, compile_ref
 
 _SRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "flow_warm_ref.c")
-_lib = None
-_tmpdir = None
 
 CONTRACT, MUTANT_HIGHEST_INDEX, MUTANT_CLOSED_BOUNDS, MUTANT_SWAPPED_XY = 0, 1, 2, 3
 
 
+@functools.lru_cache(maxsize=None)
 def lib():
-    global _lib, _tmpdir
-    if _lib is None:
-        _tmpdir = tempfile.TemporaryDirectory(prefix="flow_warm_ref_")
-        path = os.path.join(_tmpdir.name, "libflow_warm_ref.so")
-        flags = ["-O3", "-std=c99", "-ffp-contract=off", "-fno-fast-math"] + (["-mfma"] if _cpu_has_fma() else [])
-        subprocess.run(["gcc"] + flags + ["-shared", "-fPIC", "-o", path, _SRC, "-lm"], check=True, capture_output=True)
-        l = C.CDLL(path)
-        vp, i32 = C.c_void_p, C.c_int32
-        l.fwr_warm.argtypes = [vp, i32, i32, i32, i32, vp, vp]
-        l.fwr_warm.restype = i32
-        _lib = l
-    return _lib
+    l = compile_ref("flow_warm_ref", [_SRC], flags=STRICT + FMA)  # -mfma where the CPU has it: fmaf as one instruction (see above)
+    vp, i32 = C.c_void_p, C.c_int32
+    l.fwr_warm.argtypes = [vp, i32, i32, i32, i32, vp, vp]
+    l.fwr_warm.restype = i32
+    return l
 
 
 def warm(flow, variant: int = CONTRACT, with_chosen: bool = False):

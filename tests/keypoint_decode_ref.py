@@ -9,14 +9,12 @@ from __future__ import annotations
 import ctypes as C
 import functools
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 
+from tests.ref_build import compile_ref
+
 _SRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "keypoint_decode_ref.c")
-_lib = None
-_tmpdir = None
 
 CONTRACT = 0
 MUTANTS = {"dustbin_left_out_of_the_denominator": 1, "k_div_8_and_k_mod_8_exchanged": 2, "no_cell_centre_shift": 3, "higher_pixel_index_first_on_a_tie": 4,
@@ -24,19 +22,13 @@ MUTANTS = {"dustbin_left_out_of_the_denominator": 1, "k_div_8_and_k_mod_8_exchan
 LAYOUTS = ("chw", "hwc")
 
 
+@functools.lru_cache(maxsize=None)
 def lib():
-    global _lib, _tmpdir
-    if _lib is None:
-        _tmpdir = tempfile.TemporaryDirectory(prefix="keypoint_decode_ref_")
-        path = os.path.join(_tmpdir.name, "libkeypoint_decode_ref.so")
-        flags = ["-O3", "-std=c99", "-ffp-contract=off", "-fno-fast-math"]
-        subprocess.run(["gcc"] + flags + ["-shared", "-fPIC", "-o", path, _SRC, "-lm"], check=True, capture_output=True)
-        l = C.CDLL(path)
-        vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
-        l.kdr_decode.argtypes = [vp, i32, i32, vp, i32, i64, i64, i64, i32, C.c_float, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
-        l.kdr_decode.restype = i32
-        _lib = l
-    return _lib
+    l = compile_ref("keypoint_decode_ref", [_SRC])
+    vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
+    l.kdr_decode.argtypes = [vp, i32, i32, vp, i32, i64, i64, i64, i32, C.c_float, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
+    l.kdr_decode.restype = i32
+    return l
 
 
 class Result:

@@ -11,8 +11,6 @@ import ctypes as C
 import functools
 import math
 import os
-import subprocess
-import tempfile
 from types import SimpleNamespace
 
 import numpy as np
@@ -20,10 +18,9 @@ import numpy as np
 from tests import match_assignment_ref as MA
 from tests import nn_match_ref
 from tests import transformer_ref as T
+from tests.ref_build import compile_ref
 
 _SRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lightglue_adaptive_ref.c")
-_lib = None
-_tmpdir = None
 
 CONTRACT = 0
 MUTANTS = {"stop_ratio_over_the_live_count": 1, "keep_rule_with_less_than": 2, "pruning_at_the_stopping_layer": 3, "last_head_after_an_early_stop": 4,
@@ -32,25 +29,19 @@ UNMATCHED = 2
 _HEAD = ("final_proj.weight", "final_proj.bias", "matchability.weight", "matchability.bias")
 
 
+@functools.lru_cache(maxsize=None)
 def lib():
-    global _lib, _tmpdir
-    if _lib is None:
-        _tmpdir = tempfile.TemporaryDirectory(prefix="lightglue_adaptive_ref_")
-        path = os.path.join(_tmpdir.name, "liblightglue_adaptive_ref.so")
-        flags = ["-O3", "-std=c99", "-ffp-contract=off", "-fno-fast-math"]
-        subprocess.run(["gcc"] + flags + ["-shared", "-fPIC", "-o", path, _SRC, "-lm"], check=True, capture_output=True)
-        l = C.CDLL(path)
-        vp, i32, f32 = C.c_void_p, C.c_int32, C.c_float
-        l.lga_sigmoid_c.argtypes = [vp, f32]
-        l.lga_sigmoid_c.restype = f32
-        l.lga_confidence.argtypes = [vp, vp, i32, i32, vp, f32, vp]
-        l.lga_confidence.restype = None
-        l.lga_pass.argtypes = [vp, vp, vp, vp, i32, vp, i32, i32, i32, vp, vp, i32, vp, C.c_int64, vp, vp, vp, vp, vp, f32, f32, i32, vp, vp, i32] + [vp] * 8
-        l.lga_pass.restype = i32
-        l.lga_remap.argtypes = [vp, vp, i32, i32, i32, vp, vp, i32, vp, vp]
-        l.lga_remap.restype = None
-        _lib = l
-    return _lib
+    l = compile_ref("lightglue_adaptive_ref", [_SRC])
+    vp, i32, f32 = C.c_void_p, C.c_int32, C.c_float
+    l.lga_sigmoid_c.argtypes = [vp, f32]
+    l.lga_sigmoid_c.restype = f32
+    l.lga_confidence.argtypes = [vp, vp, i32, i32, vp, f32, vp]
+    l.lga_confidence.restype = None
+    l.lga_pass.argtypes = [vp, vp, vp, vp, i32, vp, i32, i32, i32, vp, vp, i32, vp, C.c_int64, vp, vp, vp, vp, vp, f32, f32, i32, vp, vp, i32] + [vp] * 8
+    l.lga_pass.restype = i32
+    l.lga_remap.argtypes = [vp, vp, i32, i32, i32, vp, vp, i32, vp, vp]
+    l.lga_remap.restype = None
+    return l
 
 
 def _fn(function):

@@ -9,14 +9,12 @@ from __future__ import annotations
 import ctypes as C
 import functools
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 
+from tests.ref_build import compile_ref
+
 _SRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "match_assignment_ref.c")
-_lib = None
-_tmpdir = None
 
 CONTRACT = 0
 MUTANTS = {"column_softmax_left_out": 1, "scale_on_one_side_only": 2, "dustbin_from_ls_z": 3, "invalid_columns_in_a_rows_normaliser": 4,
@@ -24,22 +22,16 @@ MUTANTS = {"column_softmax_left_out": 1, "scale_on_one_side_only": 2, "dustbin_f
 SENTINEL = np.float32(-12345.0)  # what a strided output holds behind each row before the call, and must hold after it
 
 
+@functools.lru_cache(maxsize=None)
 def lib():
-    global _lib, _tmpdir
-    if _lib is None:
-        _tmpdir = tempfile.TemporaryDirectory(prefix="match_assignment_ref_")
-        path = os.path.join(_tmpdir.name, "libmatch_assignment_ref.so")
-        flags = ["-O3", "-std=c99", "-ffp-contract=off", "-fno-fast-math"]
-        subprocess.run(["gcc"] + flags + ["-shared", "-fPIC", "-o", path, _SRC, "-lm"], check=True, capture_output=True)
-        l = C.CDLL(path)
-        vp, i32, f32 = C.c_void_p, C.c_int32, C.c_float
-        l.mar_assign.argtypes = [vp, i32, vp, i32, i32, vp, vp, f32, vp, vp, i32, vp, C.c_int64]
-        l.mar_assign.restype = i32
-        for name in ("mar_exp_c", "mar_log_c", "mar_ls"):
-            getattr(l, name).argtypes = [f32]
-            getattr(l, name).restype = f32
-        _lib = l
-    return _lib
+    l = compile_ref("match_assignment_ref", [_SRC])
+    vp, i32, f32 = C.c_void_p, C.c_int32, C.c_float
+    l.mar_assign.argtypes = [vp, i32, vp, i32, i32, vp, vp, f32, vp, vp, i32, vp, C.c_int64]
+    l.mar_assign.restype = i32
+    for name in ("mar_exp_c", "mar_log_c", "mar_ls"):
+        getattr(l, name).argtypes = [f32]
+        getattr(l, name).restype = f32
+    return l
 
 
 def default_scale(dim: int) -> float:

@@ -6,35 +6,30 @@ temporary directory; nothing under feature_tracker_amd/ may import it.
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 
+from tests.ref_build import compile_ref
+
 _SRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "nn_match_ref.c")
-_lib = None
-_tmpdir = None
 
 TRACKED, LARGE_RESIDUAL = 1, 2
 
 
+@functools.lru_cache(maxsize=None)
 def lib():
-    global _lib, _tmpdir
-    if _lib is None:
-        _tmpdir = tempfile.TemporaryDirectory(prefix="nn_match_ref_")
-        path = os.path.join(_tmpdir.name, "libnn_match_ref.so")
-        subprocess.run(["gcc", "-O2", "-std=c99", "-fno-fast-math", "-shared", "-fPIC", "-o", path, _SRC], check=True, capture_output=True)
-        l = C.CDLL(path)
-        vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
-        l.nmr_scores.argtypes = [vp, i32, i32, i64, f32, vp, vp, vp, C.c_int]
-        l.nmr_scores.restype = None
-        l.nmr_list.argtypes = [vp, i32, i32, i32, vp, vp]
-        l.nmr_list.restype = None
-        l.nmr_fill.argtypes = [vp, i32, vp, i32, vp]
-        l.nmr_fill.restype = None
-        _lib = l
-    return _lib
+    # not STRICT: -O2, no -ffp-contract=off, no -lm; the source compares and copies floats and has no arithmetic on them to contract
+    l = compile_ref("nn_match_ref", [_SRC], flags=["-O2", "-std=c99", "-fno-fast-math"], libs=())
+    vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
+    l.nmr_scores.argtypes = [vp, i32, i32, i64, f32, vp, vp, vp, C.c_int]
+    l.nmr_scores.restype = None
+    l.nmr_list.argtypes = [vp, i32, i32, i32, vp, vp]
+    l.nmr_list.restype = None
+    l.nmr_fill.argtypes = [vp, i32, vp, i32, vp]
+    l.nmr_fill.restype = None
+    return l
 
 
 def _p(a):

@@ -7,19 +7,17 @@ CPU has it) into a temporary directory; nothing under feature_tracker_amd/ may i
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 
-from tests.flow_upsample_ref import _cpu_has_fma, same  # noqa: F401  (same: bit-identical, any NaN equals any NaN)
+from tests.flow_upsample_ref import same  # noqa: F401  (same: bit-identical, any NaN equals any NaN)
 from tests.sep_conv_gru_ref import GATES
+from tests.ref_build import FMA, STRICT, compile_ref
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SRCS = [os.path.join(_HERE, "raft_conv_ref.c"), os.path.join(_HERE, "sep_conv_gru_ref.c")]
-_lib = None
-_tmpdir = None
 
 (CONTRACT, MUTANT_TAPS_FLIPPED, MUTANT_TAPS_TRANSPOSED, MUTANT_CLAMPED_PADDING, MUTANT_RELU_DROPPED, MUTANT_OUT_CONV_PARTS_EXCHANGED,
  MUTANT_FLOW_HEAD_ON_OLD_NET) = range(7)
@@ -31,21 +29,15 @@ LAYERS = ("motion_encoder.correlation_conv.0", "motion_encoder.correlation_conv.
           "motion_encoder.out_conv.0", "flow_head.conv1", "flow_head.conv2", "mask.0", "mask.2")
 
 
+@functools.lru_cache(maxsize=None)
 def lib():
-    global _lib, _tmpdir
-    if _lib is None:
-        _tmpdir = tempfile.TemporaryDirectory(prefix="raft_conv_ref_")
-        path = os.path.join(_tmpdir.name, "libraft_conv_ref.so")
-        flags = ["-O3", "-std=c99", "-ffp-contract=off", "-fno-fast-math"] + (["-mfma"] if _cpu_has_fma() else [])
-        subprocess.run(["gcc"] + flags + ["-shared", "-fPIC", "-o", path] + _SRCS + ["-lm"], check=True, capture_output=True)
-        l = C.CDLL(path)
-        vp, i32, f32 = C.c_void_p, C.c_int32, C.c_float
-        l.rc_conv2d.argtypes = [vp, vp, i32, vp, vp, i32, i32, i32, f32, i32, i32, i32, i32, vp]
-        l.rc_conv2d.restype = i32
-        l.rc_update_block.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
-        l.rc_update_block.restype = i32
-        _lib = l
-    return _lib
+    l = compile_ref("raft_conv_ref", _SRCS, flags=STRICT + FMA)  # -mfma where the CPU has it: fmaf as one instruction (see above)
+    vp, i32, f32 = C.c_void_p, C.c_int32, C.c_float
+    l.rc_conv2d.argtypes = [vp, vp, i32, vp, vp, i32, i32, i32, f32, i32, i32, i32, i32, vp]
+    l.rc_conv2d.restype = i32
+    l.rc_update_block.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
+    l.rc_update_block.restype = i32
+    return l
 
 
 def _p(a):

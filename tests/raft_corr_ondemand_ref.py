@@ -6,35 +6,27 @@ has it) into a temporary directory; nothing under feature_tracker_amd/ may impor
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 
-from tests.raft_corr_ref import _cpu_has_fma, layout, same  # noqa: F401  (same: bit-identical, any NaN equals any NaN)
+from tests.raft_corr_ref import layout, same  # noqa: F401  (same: bit-identical, any NaN equals any NaN)
+from tests.ref_build import FMA, STRICT, compile_ref
 
 _SRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "raft_corr_ondemand_ref.c")
-_lib = None
-_tmpdir = None
 
 
+@functools.lru_cache(maxsize=None)
 def lib():
-    global _lib, _tmpdir
-    if _lib is None:
-        _tmpdir = tempfile.TemporaryDirectory(prefix="raft_corr_ondemand_ref_")
-        path = os.path.join(_tmpdir.name, "libraft_corr_ondemand_ref.so")
-        flags = ["-O3", "-std=c99", "-ffp-contract=off", "-fno-fast-math"] + (["-mfma"] if _cpu_has_fma() else [])
-        subprocess.run(["gcc"] + flags + ["-shared", "-fPIC", "-o", path, _SRC, "-lm"], check=True, capture_output=True)
-        l = C.CDLL(path)
-        vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
-        l.rco_pool.argtypes, l.rco_pool.restype = [vp, i64, i32, i32, vp], None
-        l.rco_row.argtypes, l.rco_row.restype = [vp, vp, i32, i64, i64, i32, i64, vp], None
-        l.rco_sample.argtypes, l.rco_sample.restype = [vp, i32, i32, i32, f32, f32, i32, i32], f32
-        l.rco_floor_ix.argtypes, l.rco_floor_ix.restype = [i32, i32, vp, i64, i32, vp], None
-        l.rco_lookup.argtypes, l.rco_lookup.restype = [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp], i32
-        _lib = l
-    return _lib
+    l = compile_ref("raft_corr_ondemand_ref", [_SRC], flags=STRICT + FMA)  # -mfma where the CPU has it: fmaf as one instruction (see above)
+    vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
+    l.rco_pool.argtypes, l.rco_pool.restype = [vp, i64, i32, i32, vp], None
+    l.rco_row.argtypes, l.rco_row.restype = [vp, vp, i32, i64, i64, i32, i64, vp], None
+    l.rco_sample.argtypes, l.rco_sample.restype = [vp, i32, i32, i32, f32, f32, i32, i32], f32
+    l.rco_floor_ix.argtypes, l.rco_floor_ix.restype = [i32, i32, vp, i64, i32, vp], None
+    l.rco_lookup.argtypes, l.rco_lookup.restype = [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp], i32
+    return l
 
 
 def _p(a):

@@ -7,46 +7,31 @@ feature_tracker_amd/ may import it.
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 
+from tests.ref_build import FMA, STRICT, compile_ref
+
 _SRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "raft_corr_ref.c")
-_lib = None
-_tmpdir = None
 
 
-def _cpu_has_fma() -> bool:
-    try:
-        with open("/proc/cpuinfo") as f:
-            return any(line.startswith("flags") and " fma " in line + " " for line in f)
-    except OSError:
-        return False
-
-
+@functools.lru_cache(maxsize=None)
 def lib():
-    global _lib, _tmpdir
-    if _lib is None:
-        _tmpdir = tempfile.TemporaryDirectory(prefix="raft_corr_ref_")
-        path = os.path.join(_tmpdir.name, "libraft_corr_ref.so")
-        flags = ["-O3", "-std=c99", "-ffp-contract=off", "-fno-fast-math"] + (["-mfma"] if _cpu_has_fma() else [])
-        subprocess.run(["gcc"] + flags + ["-shared", "-fPIC", "-o", path, _SRC, "-lm"], check=True, capture_output=True)
-        l = C.CDLL(path)
-        vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
-        l.rcr_row.argtypes = [vp, vp, i32, i32, i32, i32, i64, vp]
-        l.rcr_row.restype = None
-        l.rcr_pool.argtypes = [vp, i64, i32, i32, vp]
-        l.rcr_pool.restype = None
-        l.rcr_build.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp]
-        l.rcr_build.restype = i32
-        l.rcr_sample.argtypes = [vp, i32, i32, i32, f32, f32, i32, i32]
-        l.rcr_sample.restype = f32
-        l.rcr_lookup.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp]
-        l.rcr_lookup.restype = i32
-        _lib = l
-    return _lib
+    l = compile_ref("raft_corr_ref", [_SRC], flags=STRICT + FMA)  # -mfma where the CPU has it: fmaf as one instruction (see above)
+    vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
+    l.rcr_row.argtypes = [vp, vp, i32, i32, i32, i32, i64, vp]
+    l.rcr_row.restype = None
+    l.rcr_pool.argtypes = [vp, i64, i32, i32, vp]
+    l.rcr_pool.restype = None
+    l.rcr_build.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp]
+    l.rcr_build.restype = i32
+    l.rcr_sample.argtypes = [vp, i32, i32, i32, f32, f32, i32, i32]
+    l.rcr_sample.restype = f32
+    l.rcr_lookup.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp]
+    l.rcr_lookup.restype = i32
+    return l
 
 
 def _p(a):

@@ -10,19 +10,17 @@ import it.
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 
 from tests import flow_upsample_ref, raft_conv_ref, raft_corr_ref
-from tests.flow_upsample_ref import _cpu_has_fma, same  # noqa: F401  (same: bit-identical, any NaN equals any NaN)
+from tests.flow_upsample_ref import same  # noqa: F401  (same: bit-identical, any NaN equals any NaN)
+from tests.ref_build import FMA, STRICT, compile_ref
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SRCS = [os.path.join(_HERE, f) for f in ("raft_encoder_ref.c", "raft_conv_ref.c", "sep_conv_gru_ref.c")]
-_lib = None
-_tmpdir = None
 
 BN_EPS = np.float32(1e-5)
 (CONTRACT, MUTANT_STRIDE_TAP_WITHOUT_PAD, MUTANT_OUTPUT_SIZE_FLOOR, MUTANT_FOLD_WITHOUT_SQRT, MUTANT_FOLD_WITHOUT_EPS, MUTANT_RESIDUAL_AFTER_RELU,
@@ -36,20 +34,14 @@ BLOCKS = tuple((f"resnet_{k}.{i}", 1 + i) for k in (1, 2, 3) for i in (0, 1))  #
 BN_KINDS = ("weight", "bias", "running_mean", "running_var", "num_batches_tracked")
 
 
+@functools.lru_cache(maxsize=None)
 def lib():
-    global _lib, _tmpdir
-    if _lib is None:
-        _tmpdir = tempfile.TemporaryDirectory(prefix="raft_encoder_ref_")
-        path = os.path.join(_tmpdir.name, "libraft_encoder_ref.so")
-        flags = ["-O3", "-std=c99", "-ffp-contract=off", "-fno-fast-math"] + (["-mfma"] if _cpu_has_fma() else [])
-        subprocess.run(["gcc"] + flags + ["-shared", "-fPIC", "-o", path] + _SRCS + ["-lm"], check=True, capture_output=True)
-        l = C.CDLL(path)
-        vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
-        l.re_normalise.argtypes, l.re_normalise.restype = [f32], f32
-        l.re_fold.argtypes, l.re_fold.restype = [vp, vp, vp, vp, vp, f32, i32, i64, i32, vp, vp], i32
-        l.re_conv2d.argtypes, l.re_conv2d.restype = [vp, i32, vp, vp, i32, i32, i32, vp, i32, f32, i32, i32, i32, i32, i32, vp], i32
-        _lib = l
-    return _lib
+    l = compile_ref("raft_encoder_ref", _SRCS, flags=STRICT + FMA)  # -mfma where the CPU has it: fmaf as one instruction (see above)
+    vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
+    l.re_normalise.argtypes, l.re_normalise.restype = [f32], f32
+    l.re_fold.argtypes, l.re_fold.restype = [vp, vp, vp, vp, vp, f32, i32, i64, i32, vp, vp], i32
+    l.re_conv2d.argtypes, l.re_conv2d.restype = [vp, i32, vp, vp, i32, i32, i32, vp, i32, f32, i32, i32, i32, i32, i32, vp], i32
+    return l
 
 
 def _p(a):

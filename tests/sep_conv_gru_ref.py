@@ -7,17 +7,15 @@ feature_tracker_amd/ may import it.
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 
-from tests.flow_upsample_ref import _cpu_has_fma, same  # noqa: F401  (same: bit-identical, any NaN equals any NaN)
+from tests.flow_upsample_ref import same  # noqa: F401  (same: bit-identical, any NaN equals any NaN)
+from tests.ref_build import FMA, STRICT, compile_ref
 
 _SRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "sep_conv_gru_ref.c")
-_lib = None
-_tmpdir = None
 
 CONTRACT, MUTANT_TAPS_REVERSED, MUTANT_Z_R_EXCHANGED, MUTANT_VERTICAL_FIRST, MUTANT_BLEND_EXCHANGED, MUTANT_CLAMPED_PADDING = range(6)
 MUTANTS = {"taps reversed": MUTANT_TAPS_REVERSED, "z and r weights exchanged": MUTANT_Z_R_EXCHANGED, "vertical pass first": MUTANT_VERTICAL_FIRST,
@@ -26,26 +24,20 @@ MUTANTS = {"taps reversed": MUTANT_TAPS_REVERSED, "z and r weights exchanged": M
 GATES = ("z_horizontal", "r_horizontal", "q_horizontal", "z_vertical", "r_vertical", "q_vertical")
 
 
+@functools.lru_cache(maxsize=None)
 def lib():
-    global _lib, _tmpdir
-    if _lib is None:
-        _tmpdir = tempfile.TemporaryDirectory(prefix="sep_conv_gru_ref_")
-        path = os.path.join(_tmpdir.name, "libsep_conv_gru_ref.so")
-        flags = ["-O3", "-std=c99", "-ffp-contract=off", "-fno-fast-math"] + (["-mfma"] if _cpu_has_fma() else [])
-        subprocess.run(["gcc"] + flags + ["-shared", "-fPIC", "-o", path, _SRC, "-lm"], check=True, capture_output=True)
-        l = C.CDLL(path)
-        vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
-        for name in ("scg_sigmoid_c", "scg_tanh_c"):
-            getattr(l, name).argtypes = [f32]
-            getattr(l, name).restype = f32
-            getattr(l, name + "_array").argtypes = [vp, i64, vp]
-            getattr(l, name + "_array").restype = None
-        l.scg_tanh_small.argtypes = []
-        l.scg_tanh_small.restype = f32
-        l.scg_forward.argtypes = [vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
-        l.scg_forward.restype = i32
-        _lib = l
-    return _lib
+    l = compile_ref("sep_conv_gru_ref", [_SRC], flags=STRICT + FMA)  # -mfma where the CPU has it: fmaf as one instruction (see above)
+    vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
+    for name in ("scg_sigmoid_c", "scg_tanh_c"):
+        getattr(l, name).argtypes = [f32]
+        getattr(l, name).restype = f32
+        getattr(l, name + "_array").argtypes = [vp, i64, vp]
+        getattr(l, name + "_array").restype = None
+    l.scg_tanh_small.argtypes = []
+    l.scg_tanh_small.restype = f32
+    l.scg_forward.argtypes = [vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
+    l.scg_forward.restype = i32
+    return l
 
 
 def _p(a):

@@ -8,19 +8,17 @@ has it) together with raft_conv_ref.c and sep_conv_gru_ref.c, into a temporary d
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 
 from tests import raft_conv_ref
-from tests.flow_upsample_ref import _cpu_has_fma, same  # noqa: F401  (same: bit-identical, any NaN equals any NaN)
+from tests.flow_upsample_ref import same  # noqa: F401  (same: bit-identical, any NaN equals any NaN)
+from tests.ref_build import FMA, STRICT, compile_ref
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SRCS = [os.path.join(_HERE, f) for f in ("superpoint_ref.c", "raft_conv_ref.c", "sep_conv_gru_ref.c")]
-_lib = None
-_tmpdir = None
 
 CONTRACT, MUTANT_POOL_SHIFTED, MUTANT_POOL_FMAXF, MUTANT_NO_FLOOR, MUTANT_HEADS_EXCHANGED = range(5)
 MUTANTS = {"pooling window shifted by one pixel": MUTANT_POOL_SHIFTED, "pool as fmaxf of the four": MUTANT_POOL_FMAXF,
@@ -29,20 +27,14 @@ LAYERS = ("conv1a", "conv1b", "conv2a", "conv2b", "conv3a", "conv3b", "conv4a", 
 POOLED = ("conv1b", "conv2b", "conv3b")
 
 
+@functools.lru_cache(maxsize=None)
 def lib():
-    global _lib, _tmpdir
-    if _lib is None:
-        _tmpdir = tempfile.TemporaryDirectory(prefix="superpoint_ref_")
-        path = os.path.join(_tmpdir.name, "libsuperpoint_ref.so")
-        flags = ["-O3", "-std=c99", "-ffp-contract=off", "-fno-fast-math"] + (["-mfma"] if _cpu_has_fma() else [])
-        subprocess.run(["gcc"] + flags + ["-shared", "-fPIC", "-o", path] + _SRCS + ["-lm"], check=True, capture_output=True)
-        l = C.CDLL(path)
-        vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
-        l.sp_max_pool.argtypes, l.sp_max_pool.restype = [vp, i64, i32, i32, i32, vp], i32
-        l.sp_conv2d_pool.argtypes, l.sp_conv2d_pool.restype = [vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp], i32
-        l.sp_channel_normalise.argtypes, l.sp_channel_normalise.restype = [vp, i32, i64, i32, vp], i32
-        _lib = l
-    return _lib
+    l = compile_ref("superpoint_ref", _SRCS, flags=STRICT + FMA)  # -mfma where the CPU has it: fmaf as one instruction (see above)
+    vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
+    l.sp_max_pool.argtypes, l.sp_max_pool.restype = [vp, i64, i32, i32, i32, vp], i32
+    l.sp_conv2d_pool.argtypes, l.sp_conv2d_pool.restype = [vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp], i32
+    l.sp_channel_normalise.argtypes, l.sp_channel_normalise.restype = [vp, i32, i64, i32, vp], i32
+    return l
 
 
 def _p(a):

@@ -10,7 +10,6 @@ what the kernel reads agree only if the Python layer holds every tensor to the A
   guard that keeps the next entry from being added unchecked.  (The GPU half, refusals with the native entry stubbed and bit parity of
   what stays legal, is tests/test_device_args_gpu.py.)"""
 import inspect
-import types
 
 import pytest
 import torch
@@ -18,7 +17,7 @@ import torch
 import feature_tracker_amd as F
 from feature_tracker_amd import _native as N
 from feature_tracker_amd import device as D
-from feature_tracker_amd import dist as FD
+from tests.args_walk import Fake, FakeDevice, Walk
 
 F32, U8, I32, WORDS = ("float32",), ("uint8",), ("int32",), ("int32", "uint32")
 
@@ -108,146 +107,13 @@ def test_the_check_raises_the_complaint_and_refuses_host_tensors():
         D._check("ref_uv", good.double(), F32, (None, 2), None)
     with pytest.raises(ValueError, match=r"pass ref_desc\.contiguous\(\)"):
         D._check("ref_desc", _t(16, 8).t(), F32, (None, 16), None)
-    fake = _Fake("x", "float32", (8, 2), set(), [], device=_FakeDevice(1))
+    fake = Fake("x", "float32", (8, 2), set(), [], device=FakeDevice(1))
     assert D._device_complaint("x", fake, None) is None
     assert D._device_complaint("x", fake, 1) is None
     assert "must be on cuda:0" in D._device_complaint("x", fake, 0)
 
 
-# ---- the walk ------------------------------------------------------------------------------------------------------------------
-
-
-class _FakeDtype:
-    def __init__(self, name):
-        self.name = name
-
-    def __repr__(self):
-        return "torch." + self.name
-
-
-_DTYPES = {n: _FakeDtype(n) for n in ("float32", "uint8", "int32", "uint32", "int64")}
-
-
-class _FakeDevice:
-    type = "cuda"
-
-    def __init__(self, index=0):
-        self.index = index
-
-    def __eq__(self, other):
-        return isinstance(other, _FakeDevice) and other.index == self.index
-
-    def __repr__(self):
-        return f"cuda:{self.index}"
-
-
-class _Fake:
-    """What device.py may ask of a tensor, and a ``data_ptr()`` that tells on a caller who did not have the tensor checked first."""
-    is_cuda = True
-
-    def __init__(self, name, dtype, shape, checked, unchecked_reads, device=None):
-        self.name, self.dtype, self.shape, self.device = name, _DTYPES[dtype], tuple(shape), device or _FakeDevice(0)
-        self._checked, self._unchecked_reads, self.reads = checked, unchecked_reads, 0
-
-    def stride(self, k=None):
-        s, run = [], 1
-        for e in reversed(self.shape):
-            s.append(run)
-            run *= e
-        s = tuple(reversed(s))
-        return s if k is None else s[k]
-
-    def size(self, k=None):
-        return self.shape if k is None else self.shape[k]
-
-    def dim(self):
-        return len(self.shape)
-
-    def numel(self):
-        n = 1
-        for e in self.shape:
-            n *= e
-        return n
-
-    def is_contiguous(self):
-        return True
-
-    def data_ptr(self):
-        self.reads += 1
-        if id(self) not in self._checked:
-            self._unchecked_reads.append(self.name)
-        return 0x10000
-
-
-class _RecorderLib:
-    """Stands where the loaded library stands: every entry point is recorded and answers FTK_OK; nothing is launched."""
-
-    def __init__(self):
-        self.calls = []
-
-    def ftk_klt_shard_bytes(self, n, world):
-        return FD.packed_bytes(FD.shard_capacity(n, world)) if n > 0 and world > 0 else 0
-
-    def __getattr__(self, name):
-        if not name.startswith("ftk_"):
-            raise AttributeError(name)
-
-        def entry(*args):
-            self.calls.append(name)
-            return 0
-
-        return entry
-
-
-class _FakePyramid:
-    handle = None
-
-    def level_desc(self, i):
-        return 0, 12, 16
-
-    @classmethod
-    def from_device_levels(cls, desc, ctx, keepalive=None):
-        N.lib().ftk_pyramid_wrap_device(desc)
-        return cls()
-
-
-class _Walk:
-    def __init__(self, monkeypatch):
-        self.checked, self.unchecked_reads, self.made = set(), [], []
-        self.lib = _RecorderLib()
-        real_check = D._check
-
-        def recording_check(name, t, *args, **kwargs):
-            real_check(name, t, *args, **kwargs)
-            self.checked.add(id(t))
-
-        stream = types.SimpleNamespace(cuda_stream=0)
-        fake_torch = types.SimpleNamespace(cuda=types.SimpleNamespace(current_stream=lambda device=None: stream))
-        monkeypatch.setattr(D, "_check", recording_check)
-        monkeypatch.setattr(D, "_torch", lambda: fake_torch)
-        monkeypatch.setattr(D, "ImagePyramid", _FakePyramid)
-        monkeypatch.setattr(N, "lib", lambda: self.lib)
-        monkeypatch.setattr(N, "corr_pyramid_layout", lambda B, H, W, levels: (B * H * W * H * W * levels, [], []))
-        self.ctx = types.SimpleNamespace(handle=None, device_index=0)
-        self.comm = types.SimpleNamespace(handle=None)
-        self.pyr = _FakePyramid()
-
-    def t(self, name, dtype, *shape):
-        fake = _Fake(name, dtype, shape, self.checked, self.unchecked_reads)
-        self.made.append(fake)
-        return fake
-
-    def klt(self):
-        return D.DeviceKlt("basic", F.OpticalFlowOptions(), self.pyr, self.pyr, self.ctx)
-
-    def klt_in(self, n=8):
-        return self.t("ref_uv", "float32", n, 2), self.t("cur_uv_in", "float32", n, 2), self.t("status_in", "uint8", n)
-
-    def klt_out(self, n=8):
-        return self.t("cur_uv_out", "float32", n, 2), self.t("status_out", "uint8", n)
-
-    def nearby(self, n_ref=8, n_cur=9):
-        return dict(pred_uv=self.t("pred_uv", "float32", n_ref, 2), cur_uv=self.t("cur_uv", "float32", n_cur, 2))
+# ---- the walk (its duck-typed tensors and recording library: tests/args_walk.py) ----------------------------------------------------
 
 
 def _direct_problem(w, k):
@@ -315,7 +181,7 @@ def test_no_entry_takes_a_pointer_of_an_unchecked_argument(entry, monkeypatch):
     """With every argument right the entry reaches its native function, has taken ``data_ptr()`` of every tensor it was given, and of
     none before that tensor passed ``_check``."""
     call, native = RECIPES[entry]
-    w = _Walk(monkeypatch)
+    w = Walk(monkeypatch)
     call(w)
     assert w.unchecked_reads == [], f"{entry}: data_ptr() of {w.unchecked_reads} taken without a check"
     assert native in w.lib.calls, f"{entry}: the walk's call was refused before {native} ({w.lib.calls})"
@@ -325,7 +191,7 @@ def test_no_entry_takes_a_pointer_of_an_unchecked_argument(entry, monkeypatch):
 
 def test_the_walk_notices_an_unchecked_pointer(monkeypatch):
     """The guard itself: an entry written the old way (pointer first, no check) is reported."""
-    w = _Walk(monkeypatch)
+    w = Walk(monkeypatch)
 
     def old_style_entry(ctx, uv, status):
         D._check("uv", uv, F32, (None, 2), 0)
@@ -339,20 +205,10 @@ def test_the_walk_notices_an_unchecked_pointer(monkeypatch):
 def test_a_refused_argument_stops_the_entry_before_the_library(entry, monkeypatch):
     """Each tensor argument of each entry in turn made float64 / int64: ValueError, and the recording library saw no launch."""
     call, native = RECIPES[entry]
-    probe = _Walk(monkeypatch)
+    probe = Walk(monkeypatch)
     call(probe)
     for k in range(len(probe.made)):
-        w = _Walk(monkeypatch)
-        real_t, count = w.t, [0]
-
-        def t(name, dtype, *shape):
-            fake = real_t(name, dtype, *shape)
-            if count[0] == k:
-                fake.dtype = _FakeDtype("float64")
-            count[0] += 1
-            return fake
-
-        w.t = t
+        w = Walk(monkeypatch, spoil=(k, "dtype", "float64"))
         with pytest.raises(ValueError, match=probe.made[k].name.rstrip("01")):
             call(w)
         assert [c for c in w.lib.calls if c.endswith("_device")] == [], (entry, probe.made[k].name, w.lib.calls)

@@ -17,6 +17,8 @@ from tests.test_flow_upsample_cpu import inputs, torch_upsample
 
 torch = pytest.importorskip("torch")
 
+from tests import args_walk as A  # noqa: E402
+
 GRIDS = [(1, 1, 1), (2, 3, 5), (1, 2, 33)]  # (B, H, W)
 MASK_SCALES = (1.0, 0.25, 0.3)
 LOGIT_SCALES = (1.0, 30.0)
@@ -349,11 +351,10 @@ def test_raft_track_points_refuses_bad_arguments_without_a_device(monkeypatch):
     """The checks of Raft.__call__ and those of the points, every one before the first launch: the recording library sees none."""
     import feature_tracker_amd as F
     from feature_tracker_amd import _native as N
-    from tests.test_device_args_cpu import _RecorderLib
     from tests.test_raft_encoder_cpu import RAFT_CASES, make_image, make_raft_state
     c = RAFT_CASES[0]
     model = F.Raft.from_state_dict(make_raft_state(c, 1), c[3], c[4], max_iterations=2)
-    recorder = _RecorderLib()
+    recorder = A.RecorderLib()
     monkeypatch.setattr(N, "lib", lambda: recorder)
     ref, cur, pts = make_image(1, 1, 16, 24, 1), make_image(1, 1, 16, 24, 2), torch.zeros(1, 5, 2)
     for match, args, kwargs in (
@@ -392,7 +393,7 @@ def test_device_entry_refuses_bad_arguments_without_a_device():
         D.flow_track_points_device(ctx, flow, mask, pts, 24, 40, cur, status, flow_back=flow)
 
 
-# the walk of tests/test_device_args_cpu.py (duck-typed tensors, a recording stand-in for the native library) over this entry
+# the walk of tests/args_walk.py (duck-typed tensors, a recording stand-in for the native library) over this entry
 def _walk_call(w, rows=24, cols=40):
     from feature_tracker_amd import device as D
     return D.flow_track_points_device(w.ctx, w.t("flow", "float32", 2, 2, 3, 5), w.t("mask", "float32", 2, 576, 3, 5), w.t("points", "float32", 2, 9, 2), rows,
@@ -401,11 +402,7 @@ def _walk_call(w, rows=24, cols=40):
 
 
 def test_device_entry_takes_no_pointer_of_an_unchecked_argument(monkeypatch):
-    from tests.test_device_args_cpu import _Walk
-    w = _Walk(monkeypatch)
-    _walk_call(w)
-    assert w.unchecked_reads == [] and w.lib.calls == ["ftk_flow_track_points_device"]
-    assert [f.name for f in w.made if f.reads != 1] == []
+    A.walk_call(monkeypatch, _walk_call, ["ftk_flow_track_points_device"])
 
 
 @pytest.mark.parametrize("which,change,match", [
@@ -419,33 +416,12 @@ def test_device_entry_takes_no_pointer_of_an_unchecked_argument(monkeypatch):
     (2, ("device", 1), "points must be on cuda:0"), (4, ("device", 1), "status must be on cuda:0"),
 ])
 def test_device_entry_stops_before_the_library(monkeypatch, which, change, match):
-    from tests.test_device_args_cpu import _FakeDevice, _FakeDtype, _Walk
-    w = _Walk(monkeypatch)
-    real_t, count = w.t, [0]
-
-    def t(name, dtype, *shape):
-        fake = real_t(name, dtype, *shape)
-        if count[0] == which:
-            kind, value = change
-            if kind == "dtype":
-                fake.dtype = _FakeDtype(value)
-            elif kind == "shape":
-                fake.shape = tuple(value)
-            else:
-                fake.device = _FakeDevice(value)
-        count[0] += 1
-        return fake
-
-    w.t = t
-    with pytest.raises(ValueError, match=match):
-        _walk_call(w)
-    assert w.lib.calls == [] and w.unchecked_reads == []
+    A.refused_call(monkeypatch, _walk_call, (which, *change), match)
 
 
 @pytest.mark.parametrize("rows,cols", [(25, 40), (24, 41), (0, 40), (24, -1)])
 def test_device_entry_refuses_an_image_outside_the_grid(monkeypatch, rows, cols):
-    from tests.test_device_args_cpu import _Walk
-    w = _Walk(monkeypatch)
+    w = A.Walk(monkeypatch)
     with pytest.raises(ValueError, match="image_rows x image_cols"):
         _walk_call(w, rows, cols)
     assert w.lib.calls == [] and w.unchecked_reads == []

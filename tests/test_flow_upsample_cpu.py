@@ -18,6 +18,8 @@ from tests import flow_upsample_ref as R
 
 torch = pytest.importorskip("torch")
 
+from tests import args_walk as A  # noqa: E402
+
 # |out - ref64| <= UNITS * u, u = 2^-24 * max|8 flow| (one rounding is at most 1 u relative).  Derived, not tuned, every
 # error with the same sign and exp_c at 2 ulp = 4 u: the nine numerators carry exp_c's 4 u plus the rounded subtraction's
 # |x_k - m| e^(x_k - m) u, at most 0.75 u over the nine weights; the sum s inherits both (4.75 u) and adds 8 roundings; the division 1;
@@ -297,18 +299,14 @@ def test_device_entry_refuses_bad_arguments_without_a_device():
         D.flow_upsample_device(ctx, flow, mask, out, mask_scale=NAN)
 
 
-# the walk of tests/test_device_args_cpu.py (duck-typed tensors, a recording stand-in for the native library) over this entry
+# the walk of tests/args_walk.py (duck-typed tensors, a recording stand-in for the native library) over this entry
 def _walk_call(w):
     from feature_tracker_amd import device as D
     return D.flow_upsample_device(w.ctx, w.t("flow", "float32", 2, 2, 3, 5), w.t("mask", "float32", 2, 576, 3, 5), w.t("out", "float32", 2, 2, 24, 40), 0.25)
 
 
 def test_device_entry_takes_no_pointer_of_an_unchecked_argument(monkeypatch):
-    from tests.test_device_args_cpu import _Walk
-    w = _Walk(monkeypatch)
-    _walk_call(w)
-    assert w.unchecked_reads == [] and w.lib.calls == ["ftk_flow_upsample_device"]
-    assert [f.name for f in w.made if f.reads != 1] == []
+    A.walk_call(monkeypatch, _walk_call, ["ftk_flow_upsample_device"])
 
 
 @pytest.mark.parametrize("which,change,match", [
@@ -319,24 +317,4 @@ def test_device_entry_takes_no_pointer_of_an_unchecked_argument(monkeypatch):
     (2, ("device", 1), "out must be on cuda:0"),
 ])
 def test_device_entry_stops_before_the_library(monkeypatch, which, change, match):
-    from tests.test_device_args_cpu import _FakeDevice, _FakeDtype, _Walk
-    w = _Walk(monkeypatch)
-    real_t, count = w.t, [0]
-
-    def t(name, dtype, *shape):
-        fake = real_t(name, dtype, *shape)
-        if count[0] == which:
-            kind, value = change
-            if kind == "dtype":
-                fake.dtype = _FakeDtype(value)
-            elif kind == "shape":
-                fake.shape = tuple(value)
-            else:
-                fake.device = _FakeDevice(value)
-        count[0] += 1
-        return fake
-
-    w.t = t
-    with pytest.raises(ValueError, match=match):
-        _walk_call(w)
-    assert w.lib.calls == [] and w.unchecked_reads == []
+    A.refused_call(monkeypatch, _walk_call, (which, *change), match)

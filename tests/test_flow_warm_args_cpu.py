@@ -1,14 +1,15 @@
 """The loud failures of the warm start's entries, of ``flow_init`` and of ``RaftVideoTracker`` before any device is touched (DESIGN.md
 5.18): what tests/test_flow_warm_gpu.py and tests/test_raft_video_gpu.py check on a device, as far as it can be checked without one;
-the walk of tests/test_device_args_cpu.py (duck-typed tensors, a recording stand-in for the native library) over
+the walk of tests/args_walk.py (duck-typed tensors, a recording stand-in for the native library) over
 ``device.flow_warm_device``; and the agreement of header, library and binding."""
-import os
 import re
 import types
 
 import pytest
 
 torch = pytest.importorskip("torch")
+
+from tests import args_walk as A  # noqa: E402
 
 
 def test_warm_start_flow_refuses_bad_arguments_without_a_device():
@@ -48,15 +49,10 @@ def _walk_call(w, splits=3, words=3 * 2 * 3 * 5):
 
 
 def test_device_entry_takes_no_pointer_of_an_unchecked_argument(monkeypatch):
-    from tests.test_device_args_cpu import _Walk
-    w = _Walk(monkeypatch)
-    _walk_call(w)
-    assert w.unchecked_reads == [] and w.lib.calls == ["ftk_flow_warm_device"]
-    assert [f.name for f in w.made if f.reads != 1] == []
-    w = _Walk(monkeypatch)
     from feature_tracker_amd import device as D
-    D.flow_warm_device(w.ctx, w.t("flow", "float32", 2, 2, 3, 5), w.t("out", "float32", 2, 2, 3, 5))  # one split: no workspace
-    assert w.unchecked_reads == [] and w.lib.calls == ["ftk_flow_warm_device"]
+    A.walk_call(monkeypatch, _walk_call, ["ftk_flow_warm_device"])
+    one_split = lambda w: D.flow_warm_device(w.ctx, w.t("flow", "float32", 2, 2, 3, 5), w.t("out", "float32", 2, 2, 3, 5))  # noqa: E731  (no workspace)
+    A.walk_call(monkeypatch, one_split, ["ftk_flow_warm_device"])
 
 
 @pytest.mark.parametrize("which,change,match", [
@@ -68,36 +64,13 @@ def test_device_entry_takes_no_pointer_of_an_unchecked_argument(monkeypatch):
     (1, ("device", 1), "out must be on cuda:0"), (2, ("device", 1), "workspace must be on cuda:0"),
 ])
 def test_device_entry_stops_before_the_library(monkeypatch, which, change, match):
-    from tests.test_device_args_cpu import _FakeDevice, _FakeDtype, _Walk
-    w = _Walk(monkeypatch)
-    real_t, count = w.t, [0]
-
-    def t(name, dtype, *shape):
-        fake = real_t(name, dtype, *shape)
-        if count[0] == which:
-            kind, value = change
-            if kind == "dtype":
-                fake.dtype = _FakeDtype(value)
-            elif kind == "shape":
-                fake.shape = tuple(value)
-            else:
-                fake.device = _FakeDevice(value)
-        count[0] += 1
-        return fake
-
-    w.t = t
-    with pytest.raises(ValueError, match=match):
-        _walk_call(w)
-    assert w.lib.calls == [] and w.unchecked_reads == []
+    A.refused_call(monkeypatch, _walk_call, (which, *change), match)
 
 
 def test_header_library_and_binding_agree():
     from feature_tracker_amd import _native as N
-    header = open(os.path.join(os.path.dirname(N.CSRC_DIR), "..", "include", "ftk.h")).read()
-    assert int(re.search(r"#define FTK_FLOW_WARM_TILE (\d+)", header).group(1)) == N.FTK_FLOW_WARM_TILE
-    assert int(re.search(r"#define FTK_FLOW_WARM_MAX_SPLITS (\d+)", header).group(1)) == N.FTK_FLOW_WARM_MAX_SPLITS
+    header = A.header_library_and_binding_agree(("FTK_FLOW_WARM_TILE", "FTK_FLOW_WARM_MAX_SPLITS"), {"ftk_flow_warm_splits", "ftk_flow_warm_device"})
     assert re.search(r"#define FTK_FLOW_WARM_MAX_PIXELS \(1 << (\d+)\)", header).group(1) == "20" and N.FTK_FLOW_WARM_MAX_PIXELS == 1 << 20
-    assert {"ftk_flow_warm_splits", "ftk_flow_warm_device"} <= set(N.EXPORTS)
 
 
 def test_split_rule_and_native_refusals_need_no_device():
@@ -122,11 +95,10 @@ def test_raft_flow_init_refused_without_a_device(monkeypatch):
     none."""
     import feature_tracker_amd as F
     from feature_tracker_amd import _native as N
-    from tests.test_device_args_cpu import _RecorderLib
     from tests.test_raft_encoder_cpu import RAFT_CASES, make_image, make_raft_state
     c = RAFT_CASES[0]
     model = F.Raft.from_state_dict(make_raft_state(c, 1), c[3], c[4], max_iterations=2)
-    recorder = _RecorderLib()
+    recorder = A.RecorderLib()
     monkeypatch.setattr(N, "lib", lambda: recorder)
     ref, cur, pts = make_image(1, 1, 16, 24, 1), make_image(1, 1, 16, 24, 2), torch.zeros(1, 5, 2)
     good = torch.zeros(1, 2, 2, 3)  # 16 x 24 images give 2 x 3 feature maps
@@ -152,7 +124,6 @@ def test_raft_flow_init_refused_without_a_device(monkeypatch):
 def test_video_tracker_refuses_bad_arguments_without_a_device(monkeypatch):
     import feature_tracker_amd as F
     from feature_tracker_amd import _native as N
-    from tests.test_device_args_cpu import _RecorderLib
     from tests.test_raft_encoder_cpu import RAFT_CASES, make_image, make_raft_state
     c = RAFT_CASES[0]
     model = F.Raft.from_state_dict(make_raft_state(c, 1), c[3], c[4], max_iterations=2)
@@ -160,7 +131,7 @@ def test_video_tracker_refuses_bad_arguments_without_a_device(monkeypatch):
                                 ("forward_backward", (model,), {"forward_backward": -1.0}), ("forward_backward", (model,), {"forward_backward": float("nan")})):
         with pytest.raises(ValueError, match=match):
             F.RaftVideoTracker(*args, **kwargs)
-    recorder = _RecorderLib()
+    recorder = A.RecorderLib()
     monkeypatch.setattr(N, "lib", lambda: recorder)
     tracker = F.RaftVideoTracker(model)
     assert tracker.last_flow is None and tracker.iterations == 2 and tracker.warm_start and tracker.forward_backward is None

@@ -1,17 +1,15 @@
-"""The loud failures of the keypoint decoder before any device is touched: the walk of tests/test_device_args_cpu.py over
+"""The loud failures of the keypoint decoder before any device is touched: the walk of tests/args_walk.py over
 ``device.keypoint_decode_device``; the refusals of ``KeypointDecoder``; the agreement of header, library and binding; and the launch plan
 through host/build/keypoint_decode_plan_cli."""
-import os
-import re
-import subprocess
 import types
 
 import pytest
 
 torch = pytest.importorskip("torch")
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PLAN_CLI = os.path.join(ROOT, "feature_tracker_amd", "host", "build", "keypoint_decode_plan_cli")
+from tests import args_walk as A  # noqa: E402
+
+PLAN_CLI = A.plan_cli("keypoint_decode_plan_cli")
 
 
 def _call(w, hc=3, wc=5, d=16, k=10, min_score=0.1, min_distance=4, border=4, n_occ=6, layout="chw", mask=True, heatmap=True):
@@ -28,47 +26,20 @@ def _call(w, hc=3, wc=5, d=16, k=10, min_score=0.1, min_distance=4, border=4, n_
 
 
 def test_entry_takes_no_pointer_of_an_unchecked_argument(monkeypatch):
-    from tests.test_device_args_cpu import _Walk
     for layout in ("chw", "hwc"):
-        w = _Walk(monkeypatch)
-        _call(w, layout=layout)
-        assert w.unchecked_reads == [] and w.lib.calls == ["ftk_keypoint_decode_device"]
-        assert [f.name for f in w.made if f.reads != 1] == []
+        A.walk_call(monkeypatch, lambda w: _call(w, layout=layout), ["ftk_keypoint_decode_device"])
 
 
 @pytest.mark.parametrize("kind", ["dtype", "shape", "device"])
 def test_each_refused_tensor_stops_the_entry_before_the_library(monkeypatch, kind):
-    from tests.test_device_args_cpu import _FakeDevice, _FakeDtype, _Walk
-    probe = _Walk(monkeypatch)
-    _call(probe)
-    for k, made in enumerate(probe.made):
-        w = _Walk(monkeypatch)
-        real_t, count = w.t, [0]
-
-        def t(name, dtype, *shape):
-            fake = real_t(name, dtype, *shape)
-            if count[0] == k:
-                if kind == "dtype":
-                    fake.dtype = _FakeDtype("float64")
-                elif kind == "shape":
-                    fake.shape = (fake.shape[0] - 1,) + fake.shape[1:]
-                else:
-                    fake.device = _FakeDevice(1)
-            count[0] += 1
-            return fake
-
-        w.t = t
-        # (one channel or one occupied point fewer is a valid tensor: the next tensor sized by it is the one refused)
-        with pytest.raises(ValueError, match="must be" if kind == "shape" and made.name in ("desc", "occupied", "workspace") else f"^{made.name} must be"):
-            _call(w)
-        assert w.lib.calls == [] and w.unchecked_reads == []
+    # (one channel or one occupied point fewer is a valid tensor: the next tensor sized by it is the one refused)
+    A.refusal_sweep(monkeypatch, _call, kind, loose=("desc", "occupied", "workspace"))
 
 
 def test_other_refusals(monkeypatch):
     import feature_tracker_amd as F
     from feature_tracker_amd import _native as N
-    from tests.test_device_args_cpu import _RecorderLib, _Walk
-    w = _Walk(monkeypatch)
+    w = A.Walk(monkeypatch)
     for match, kw in (("max_keypoints must be in 1 .. FTK_KEYPOINT_DECODE_MAX_KEYPOINTS", dict(k=0)), ("max_keypoints must be in", dict(k=65537)),
                       ("min_score must be a finite", dict(min_score=float("nan"))), ("min_score must be a finite", dict(min_score=float("inf"))),
                       ("min_score must be a finite", dict(min_score="high")), ("border must not be negative", dict(border=-1)),
@@ -85,7 +56,7 @@ def test_other_refusals(monkeypatch):
                dict(hc=1, wc=1, border=0), dict(hc=32, wc=32, min_distance=1)):
         _call(w, **kw)
     assert len(w.lib.calls) == 11
-    recorder = _RecorderLib()
+    recorder = A.RecorderLib()
     monkeypatch.setattr(N, "lib", lambda: recorder)
     for match, kw in (("max_keypoints", dict(max_keypoints=0)), ("max_keypoints", dict(max_keypoints=1.5)), ("min_score", dict(min_score=float("nan"))),
                       ("min_distance", dict(min_distance="far")), ("border", dict(border=-4)), ("context_on_stream", dict(ctx=types.SimpleNamespace(handle=None)))):
@@ -114,12 +85,8 @@ def test_header_library_and_binding_agree():
     import feature_tracker_amd as F
     from feature_tracker_amd import _native as N
     from feature_tracker_amd import device as D
-    header = open(os.path.join(ROOT, "include", "ftk.h")).read()
-    for name in ("FTK_KEYPOINT_DECODE_CELL", "FTK_KEYPOINT_DECODE_MAX_KEYPOINTS", "FTK_KEYPOINT_DECODE_MAX_CHANNELS"):
-        assert int(re.search(rf"#define {name} (\d+)", header).group(1)) == getattr(N, name)
-    assert int(re.search(r"#define FTK_ABI_VERSION (\d+)", header).group(1)) == 1
-    new = {"ftk_keypoint_decode_workspace_bytes", "ftk_keypoint_decode_device"}
-    assert new <= set(N.EXPORTS) and all(re.search(rf"\bint {s}\(", header) for s in new)
+    A.header_library_and_binding_agree(("FTK_KEYPOINT_DECODE_CELL", "FTK_KEYPOINT_DECODE_MAX_KEYPOINTS", "FTK_KEYPOINT_DECODE_MAX_CHANNELS"),
+                                       {"ftk_keypoint_decode_workspace_bytes", "ftk_keypoint_decode_device"})
     assert {"KeypointDecoder", "KeypointResult"} <= set(F.__all__) and callable(D.keypoint_decode_device)
     lib, out = N.lib(), C.c_int64()
     for hc, wc in ((1, 1), (3, 5), (2, 65), (9, 17), (60, 94), (60, 80)):
@@ -136,11 +103,7 @@ def test_header_library_and_binding_agree():
 
 
 def test_nothing_in_the_package_imports_the_restatement():
-    pkg = os.path.join(ROOT, "feature_tracker_amd")
-    for folder, _, files in os.walk(pkg):
-        for f in files:
-            if f.endswith(".py"):
-                assert "keypoint_decode_ref" not in open(os.path.join(folder, f)).read(), f
+    A.nothing_in_the_package_imports("keypoint_decode_ref")
 
 
 def _plan(hc, wc, d, k, distance, border, n_occ):
@@ -172,17 +135,13 @@ def _plan(hc, wc, d, k, distance, border, n_occ):
 
 def test_plan_cli_equals_the_restated_plan():
     from feature_tracker_amd import _native as N
-    assert os.path.exists(PLAN_CLI), "host/build/keypoint_decode_plan_cli is missing: build() makes it"
     cases = [(hc, wc, d, k, distance, 4, n_occ) for hc, wc in ((1, 1), (3, 5), (2, 65), (9, 17), (60, 94), (60, 80), (8192, 8192), (0, 5), (3, 8193), (-1, -1))
              for d, k in ((1, 1), (64, 300), (65, 3), (256, 2000), (1024, 65536), (0, 300), (1025, 300), (256, 0), (256, 65537))
              for distance in (-2, 0, 1, 4, 9, 20, 256) for n_occ in (0, 1, 256, 257)]
     cases += [(3, 5, 64, 300, 4, -1, 0), (3, 5, 64, 300, 4, 0, -1), (3, 5, 64, 300, 4, 1000, 0)]
-    text = "".join(" ".join(str(v) for v in c) + "\n" for c in cases)
-    out = subprocess.run([PLAN_CLI], input=text, capture_output=True, text=True, check=True).stdout.strip().split("\n")
-    assert len(out) == len(cases)
+    plans = A.run_plan_tool(PLAN_CLI, cases)
     seen = set()
-    for case, line in zip(cases, out):
-        got = dict(kv.split("=") for kv in line.split())
+    for case, got in zip(cases, plans):
         want = _plan(*case)
         assert got == {k: str(v) for k, v in want.items()}, (case, got, want)
         seen.add(want["refused"])

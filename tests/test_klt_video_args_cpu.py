@@ -1,9 +1,7 @@
 """The loud failures of masked Harris detection, the track-table entries and ``KltVideoTracker`` before any device is touched (DESIGN.md
-5.19): the walk of tests/test_device_args_cpu.py (duck-typed tensors, a recording stand-in for the native library) over the new entries of
+5.19): the walk of tests/args_walk.py (duck-typed tensors, a recording stand-in for the native library) over the new entries of
 device.py; the agreement of header, library and binding; and the launch plan through host/build/track_table_plan_cli."""
-import os
 import re
-import subprocess
 import types
 
 import numpy as np
@@ -11,8 +9,9 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PLAN_CLI = os.path.join(ROOT, "feature_tracker_amd", "host", "build", "track_table_plan_cli")
+from tests import args_walk as A  # noqa: E402
+
+PLAN_CLI = A.plan_cli("track_table_plan_cli")
 
 
 class _Pyramid:
@@ -53,50 +52,20 @@ CALLS = {"ftk_harris_detect_device": _detect, "ftk_track_table_retire_device": _
 
 @pytest.mark.parametrize("native", sorted(CALLS))
 def test_entries_take_no_pointer_of_an_unchecked_argument(monkeypatch, native):
-    from tests.test_device_args_cpu import _Walk
-    w = _Walk(monkeypatch)
-    CALLS[native](w)
-    assert w.unchecked_reads == [] and w.lib.calls == [native]
-    assert [f.name for f in w.made if f.reads != 1] == []
+    A.walk_call(monkeypatch, CALLS[native], [native])
 
 
 @pytest.mark.parametrize("native", sorted(CALLS))
 @pytest.mark.parametrize("kind", ["dtype", "shape", "device"])
 def test_each_refused_tensor_stops_the_entry_before_the_library(monkeypatch, native, kind):
     """Every tensor argument of every entry in turn with another dtype, one element too many in its first dimension, or on another device."""
-    from tests.test_device_args_cpu import _FakeDevice, _FakeDtype, _Walk
-    probe = _Walk(monkeypatch)
-    CALLS[native](probe)
-    for k, made in enumerate(probe.made):
-        w = _Walk(monkeypatch)
-        real_t, count = w.t, [0]
-
-        def t(name, dtype, *shape):
-            fake = real_t(name, dtype, *shape)
-            if count[0] == k:
-                if kind == "dtype":
-                    fake.dtype = _FakeDtype("float64")
-                elif kind == "shape":
-                    fake.shape = (fake.shape[0] + 1,) + fake.shape[1:]
-                else:
-                    fake.device = _FakeDevice(1)
-            count[0] += 1
-            return fake
-
-        w.t = t
-        if kind == "shape" and made.name in ("ids", "occupied"):  # the tensors the others are sized by: the NEXT one is refused
-            with pytest.raises(ValueError, match="must be"):
-                CALLS[native](w)
-        else:
-            with pytest.raises(ValueError, match=f"^{made.name} must be"):
-                CALLS[native](w)
-        assert w.lib.calls == [] and w.unchecked_reads == []
+    # (ids and occupied are the tensors the others are sized by: the NEXT one is refused)
+    A.refusal_sweep(monkeypatch, CALLS[native], kind, loose=("ids", "occupied"), reshape=A.one_row_more)
 
 
 def test_other_refusals_of_the_entries(monkeypatch):
     from feature_tracker_amd import device as D
-    from tests.test_device_args_cpu import _Walk
-    w = _Walk(monkeypatch)
+    w = A.Walk(monkeypatch)
     with pytest.raises(ValueError, match="FTK_HARRIS_DEVICE_MAX_SURVIVORS"):
         _detect(w, _Pyramid(257, 256), distance=1)  # 65 792 cells
     with pytest.raises(ValueError, match="FTK_HARRIS_DEVICE_MAX_SURVIVORS"):
@@ -127,8 +96,7 @@ def test_other_refusals_of_the_entries(monkeypatch):
 def test_detect_device_of_the_detector_refuses_before_the_library(monkeypatch):
     import feature_tracker_amd as F
     from feature_tracker_amd import _native as N
-    from tests.test_device_args_cpu import _RecorderLib
-    recorder = _RecorderLib()
+    recorder = A.RecorderLib()
     monkeypatch.setattr(N, "lib", lambda: recorder)
     det = F.FeaturePointHarrisDetector(types.SimpleNamespace(handle=None))
     det.options().kMinFeatureDistance = 1
@@ -148,7 +116,6 @@ def test_detect_device_of_the_detector_refuses_before_the_library(monkeypatch):
 def test_video_tracker_refuses_bad_arguments_without_a_device(monkeypatch):
     import feature_tracker_amd as F
     from feature_tracker_amd import _native as N
-    from tests.test_device_args_cpu import _RecorderLib
     flow = F.OpticalFlowBasicKlt()
     for match, args, kwargs in (("flow must be", (None, 8), {}), ("flow must be", (F.OpticalFlow(), 8), {}), ("max_features must be in 1 .. 65536", (flow, 0), {}),
                                 ("max_features must be in 1 .. 65536", (flow, 65537), {}), ("exceeds flow.options\\(\\).kMaxTrackPointsNumber = 500", (flow, 501), {}),
@@ -157,7 +124,7 @@ def test_video_tracker_refuses_bad_arguments_without_a_device(monkeypatch):
                                 ("context_on_stream", (flow, 8), {"ctx": types.SimpleNamespace(handle=None)})):
         with pytest.raises(ValueError, match=match):
             F.KltVideoTracker(*args, **kwargs)
-    recorder = _RecorderLib()
+    recorder = A.RecorderLib()
     monkeypatch.setattr(N, "lib", lambda: recorder)
     tracker = F.KltVideoTracker(flow, 8, min_distance=1)
     assert tracker.ids is None and tracker.forward_backward is None and tracker.reset() is tracker
@@ -182,11 +149,8 @@ def test_video_tracker_refuses_bad_arguments_without_a_device(monkeypatch):
 
 def test_header_library_and_binding_agree():
     from feature_tracker_amd import _native as N
-    header = open(os.path.join(ROOT, "include", "ftk.h")).read()
-    for name in ("FTK_HARRIS_DEVICE_MAX_SURVIVORS", "FTK_HARRIS_RANK_TILE", "FTK_TRACK_TABLE_MAX_SLOTS", "FTK_TRACK_TABLE_BLOCK"):
-        assert int(re.search(rf"#define {name} (\d+)", header).group(1)) == getattr(N, name)
-    new = {"ftk_harris_detect_device", "ftk_track_table_retire_device", "ftk_track_table_fill_device"}
-    assert new <= set(N.EXPORTS) and all(re.search(rf"\bint {s}\(", header) for s in new)
+    header = A.header_library_and_binding_agree(("FTK_HARRIS_DEVICE_MAX_SURVIVORS", "FTK_HARRIS_RANK_TILE", "FTK_TRACK_TABLE_MAX_SLOTS", "FTK_TRACK_TABLE_BLOCK"),
+                                                {"ftk_harris_detect_device", "ftk_track_table_retire_device", "ftk_track_table_fill_device"})
     assert re.search(r"#define FTK_ABI_VERSION 1\b", header) and N.lib().ftk_abi_version() == 1
     lib = N.lib()  # null-context calls
     assert lib.ftk_harris_detect_device(None, None, 0, 0, 0, 0.0, None, None, 0, None, None) == -1
@@ -195,11 +159,7 @@ def test_header_library_and_binding_agree():
 
 
 def test_nothing_in_the_package_imports_the_restatement():
-    pkg = os.path.join(ROOT, "feature_tracker_amd")
-    for folder, _, files in os.walk(pkg):
-        for f in files:
-            if f.endswith(".py"):
-                assert "track_table_ref" not in open(os.path.join(folder, f)).read(), f
+    A.nothing_in_the_package_imports("track_table_ref")
 
 
 def _plan(rows, cols, distance, slots, occupied):
@@ -220,7 +180,6 @@ def _plan(rows, cols, distance, slots, occupied):
 
 
 def test_plan_cli_equals_the_restated_plan():
-    assert os.path.exists(PLAN_CLI), "host/build/track_table_plan_cli is missing: build() makes it"
     cases = []
     # survivor capacity 0, 1, tile, tile + 1, 65 536 (and one above); slots 1, 1 024, 1 025, 65 536 (and out of range)
     for rows, cols, d in ((22, 40, 3), (23, 23, 25), (32, 32, 2), (23, 6425, 25), (256, 256, 1), (257, 256, 1), (480, 752, 25), (480, 640, 8), (333, 251, 0),
@@ -228,12 +187,9 @@ def test_plan_cli_equals_the_restated_plan():
         for slots in (0, 1, 1024, 1025, 65536, 65537, -1):
             cases.append((rows, cols, d, slots, max(slots, 0)))
     cases.append((120, 160, 9, 8, -1))
-    text = "".join(" ".join(str(v) for v in c) + "\n" for c in cases)
-    out = subprocess.run([PLAN_CLI], input=text, capture_output=True, text=True, check=True).stdout.strip().split("\n")
-    assert len(out) == len(cases)
+    plans = A.run_plan_tool(PLAN_CLI, cases)
     seen = set()
-    for case, line in zip(cases, out):
-        got = dict(kv.split("=") for kv in line.split())
+    for case, got in zip(cases, plans):
         want = _plan(*case)
         assert got == {k: str(v) for k, v in want.items()}, (case, got, want)
         seen.add((want["refused"], want.get("capacity")))

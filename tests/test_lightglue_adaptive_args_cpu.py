@@ -3,15 +3,14 @@ host/build/lightglue_adaptive_plan_cli at the limit edges; header, library and b
 import ctypes as C
 import os
 import re
-import subprocess
-import types
 
 import pytest
 
 torch = pytest.importorskip("torch")
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PLAN_CLI = os.path.join(ROOT, "feature_tracker_amd", "host", "build", "lightglue_adaptive_plan_cli")
+from tests import args_walk as A  # noqa: E402
+
+PLAN_CLI = A.plan_cli("lightglue_adaptive_plan_cli")
 ENTRIES = ("ftk_lightglue_adaptive_workspace_bytes", "ftk_transformer_layer_adaptive_device", "ftk_lightglue_confidence_device",
            "ftk_lightglue_adapt_step_device", "ftk_lightglue_finish_device")
 
@@ -40,15 +39,11 @@ def _restated(m, n, d, h):
 
 def test_plan_cli_equals_the_restated_plan_at_every_limit_edge():
     from feature_tracker_amd import _native as N
-    assert os.path.exists(PLAN_CLI), "host/build/lightglue_adaptive_plan_cli is missing: build() makes it"
     cases = [(m, n, d, h) for m, n in ((1, 1), (33, 31), (65, 130), (255, 257), (300, 300), (4096, 4096), (4097, 1), (1, 4097), (0, 5), (-1, -1))
              for d, h in ((4, 2), (8, 2), (18, 3), (64, 4), (256, 4), (1024, 8), (1024, 16), (6, 2), (256, 3), (0, 1), (1025, 5), (4, 0))]
-    text = "".join(" ".join(str(v) for v in c) + "\n" for c in cases)
-    out = subprocess.run([PLAN_CLI], input=text, capture_output=True, text=True, check=True).stdout.strip().split("\n")
-    assert len(out) == len(cases)
+    plans = A.run_plan_tool(PLAN_CLI, cases)
     refused = 0
-    for case, line in zip(cases, out):
-        plan = dict(kv.split("=") for kv in line.split())
+    for case, plan in zip(cases, plans):
         want = _restated(*case)
         got_bytes = C.c_int64(-1)
         rc = N.lib().ftk_lightglue_adaptive_workspace_bytes(*case, C.byref(got_bytes))
@@ -64,12 +59,9 @@ def test_plan_cli_equals_the_restated_plan_at_every_limit_edge():
 
 def test_header_library_and_binding_agree():
     from feature_tracker_amd import _native as N
-    header = open(os.path.join(ROOT, "include", "ftk.h")).read()
-    plan = open(os.path.join(ROOT, "feature_tracker_amd", "csrc", "lightglue_adaptive_plan.h")).read()
-    for name in ENTRIES:
-        assert re.search(rf"\bint {name}\(", header) and name in N.EXPORTS and getattr(N.lib(), name).argtypes is not None, name
-    assert int(re.search(r"#define FTK_LIGHTGLUE_MAX_LAYERS (\d+)", header).group(1)) == N.FTK_LIGHTGLUE_MAX_LAYERS
-    assert int(re.search(r"#define FTK_LIGHTGLUE_STATE_WORDS (\d+)", header).group(1)) == N.FTK_LIGHTGLUE_STATE_WORDS
+    header = A.header_library_and_binding_agree(("FTK_LIGHTGLUE_MAX_LAYERS", "FTK_LIGHTGLUE_STATE_WORDS"), ENTRIES)
+    plan = open(os.path.join(A.ROOT, "feature_tracker_amd", "csrc", "lightglue_adaptive_plan.h")).read()
+    assert all(getattr(N.lib(), name).argtypes is not None for name in ENTRIES)
     assert re.search(r"kAdaptiveMaxLayers = %d;" % N.FTK_LIGHTGLUE_MAX_LAYERS, plan) and re.search(r"kAdaptiveStateWords = %d " % N.FTK_LIGHTGLUE_STATE_WORDS, plan)
     # the argument counts of the prototypes and of the bindings
     for name in ENTRIES:
@@ -133,49 +125,21 @@ CALLS = {"ftk_lightglue_confidence_device": _confidence, "ftk_transformer_layer_
 
 @pytest.mark.parametrize("native", sorted(CALLS))
 def test_entry_takes_no_pointer_of_an_unchecked_argument(monkeypatch, native):
-    from tests.test_device_args_cpu import _Walk
-    w = _Walk(monkeypatch)
-    CALLS[native](w)
-    assert w.unchecked_reads == [] and w.lib.calls == [native]
-    assert [f.name for f in w.made if f.reads != 1] == []
+    A.walk_call(monkeypatch, CALLS[native], [native])
 
 
 @pytest.mark.parametrize("kind", ["dtype", "device", "shape"])
 @pytest.mark.parametrize("native", sorted(CALLS))
 def test_each_refused_tensor_stops_the_entry_before_the_library(monkeypatch, native, kind):
     """Every tensor argument of every entry in turn with a wrong dtype, on another device, and one element longer in its last dimension."""
-    from tests.test_device_args_cpu import _FakeDevice, _FakeDtype, _Walk
-    probe = _Walk(monkeypatch)
-    CALLS[native](probe)
-    assert len(probe.made) == {"ftk_lightglue_confidence_device": 11, "ftk_transformer_layer_adaptive_device": 9, "ftk_lightglue_adapt_step_device": 20,
-                               "ftk_lightglue_finish_device": 13}[native]
-    for k, made in enumerate(probe.made):
-        if kind == "shape" and made.name in ("desc0", "src desc0", "workspace"):
-            continue  # (desc0 gives the call its sizes; the workspace has a least size, tested below)
-        w = _Walk(monkeypatch)
-        real_t, count = w.t, [0]
-
-        def t(name, dtype, *shape):
-            fake = real_t(name, dtype, *shape)
-            if count[0] == k:
-                if kind == "dtype":
-                    fake.dtype = _FakeDtype("float64")
-                elif kind == "device":
-                    fake.device = _FakeDevice(1)
-                else:
-                    fake.shape = fake.shape[:-1] + (fake.shape[-1] + 1,)
-            count[0] += 1
-            return fake
-
-        w.t = t
-        with pytest.raises(ValueError, match=f"^{made.name} must be"):
-            CALLS[native](w)
-        assert w.lib.calls == [] and w.unchecked_reads == []
+    # (desc0 gives the call its sizes; the workspace has a least size, tested below)
+    names = A.refusal_sweep(monkeypatch, CALLS[native], kind, reshape=A.one_column_more, skip=("desc0", "src desc0", "workspace"))
+    assert len(names) == {"ftk_lightglue_confidence_device": 11, "ftk_transformer_layer_adaptive_device": 9, "ftk_lightglue_adapt_step_device": 20,
+                          "ftk_lightglue_finish_device": 13}[native]
 
 
 def test_other_refusals(monkeypatch):
-    from tests.test_device_args_cpu import _Walk
-    w = _Walk(monkeypatch)
+    w = A.Walk(monkeypatch)
     for match, call, kw in (("FTK_TRANSFORMER_MAX_ROWS", _layer, dict(m=4097)), ("FTK_TRANSFORMER_MAX_ROWS", _layer, dict(n=0)),
                             ("must divide D", _layer, dict(h=3)), ("FTK_TRANSFORMER_MAX_HEAD_DIM", _layer, dict(d=6, h=2)),
                             ("num_heads must be", _layer, dict(h=0)), ("layer must be", _step, dict(layer=-1)), ("layer must be", _step, dict(layer=64)),
@@ -186,7 +150,7 @@ def test_other_refusals(monkeypatch):
         with pytest.raises(ValueError, match=match):
             call(w, **kw)
     assert w.lib.calls == [] and w.unchecked_reads == []
-    short = _Walk(monkeypatch)
+    short = A.Walk(monkeypatch)
     real_t = short.t
     short.t = lambda name, dtype, *shape: real_t(name, dtype, *((8,) if name == "workspace" else shape))
     for call in (_layer, _step, _finish):

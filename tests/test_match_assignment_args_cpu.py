@@ -1,17 +1,15 @@
-"""The loud failures of the assignment head before any device is touched: the walk of tests/test_device_args_cpu.py over
+"""The loud failures of the assignment head before any device is touched: the walk of tests/args_walk.py over
 ``device.match_assignment_device``; the refusals of ``MatchAssignment``; the agreement of header, library and binding; and the launch
 plan through host/build/match_assignment_plan_cli."""
-import os
-import re
-import subprocess
 import types
 
 import pytest
 
 torch = pytest.importorskip("torch")
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PLAN_CLI = os.path.join(ROOT, "feature_tracker_amd", "host", "build", "match_assignment_plan_cli")
+from tests import args_walk as A  # noqa: E402
+
+PLAN_CLI = A.plan_cli("match_assignment_plan_cli")
 
 
 def _call(w, m=6, n=7, d=16, weights=True, counts=True, scale=0.5, row_stride=None):
@@ -30,50 +28,24 @@ def _call(w, m=6, n=7, d=16, weights=True, counts=True, scale=0.5, row_stride=No
 
 
 def test_entry_takes_no_pointer_of_an_unchecked_argument(monkeypatch):
-    from tests.test_device_args_cpu import _Walk
     for kw in (dict(), dict(weights=False), dict(counts=False), dict(row_stride=12)):
-        w = _Walk(monkeypatch)
-        _call(w, **kw)
-        assert w.unchecked_reads == [] and w.lib.calls == ["ftk_match_assignment_device"]
-        assert [f.name for f in w.made if f.reads != 1] == []
+        A.walk_call(monkeypatch, lambda w: _call(w, **kw), ["ftk_match_assignment_device"])
 
 
 @pytest.mark.parametrize("kind", ["dtype", "shape", "device"])
 def test_each_refused_tensor_stops_the_entry_before_the_library(monkeypatch, kind):
-    from tests.test_device_args_cpu import _FakeDevice, _FakeDtype, _Walk
-    probe = _Walk(monkeypatch)
-    _call(probe)
-    for k, made in enumerate(probe.made):
-        w = _Walk(monkeypatch)
-        real_t, count = w.t, [0]
+    def reshape(fake):  # (a row fewer is a valid call: a column fewer is not)
+        return (fake.shape[0], fake.shape[1] - 1) if fake.name in ("desc0", "desc1") else A.one_row_fewer(fake)
 
-        def t(name, dtype, *shape):
-            fake = real_t(name, dtype, *shape)
-            if count[0] == k:
-                if kind == "dtype":
-                    fake.dtype = _FakeDtype("float64")
-                elif kind == "shape" and name in ("desc0", "desc1"):  # (a row fewer is a valid call: a column fewer is not)
-                    fake.shape = (fake.shape[0], fake.shape[1] - 1)
-                elif kind == "shape":
-                    fake.shape = (fake.shape[0] - 1,) + fake.shape[1:]
-                else:
-                    fake.device = _FakeDevice(1)
-            count[0] += 1
-            return fake
-
-        w.t = t
-        # (desc0 with a column fewer is a valid tensor: desc1, sized by it, is the one refused)
-        with pytest.raises(ValueError, match="must be" if kind == "shape" and made.name in ("desc0", "desc1") else f"^{made.name} must be"):
-            _call(w)
-        assert w.lib.calls == [] and w.unchecked_reads == []
+    # (desc0 with a column fewer is a valid tensor: desc1, sized by it, is the one refused)
+    A.refusal_sweep(monkeypatch, _call, kind, loose=("desc0", "desc1"), reshape=reshape)
 
 
 def test_other_refusals(monkeypatch):
     import feature_tracker_amd as F
     from feature_tracker_amd import _native as N
     from feature_tracker_amd import device as D
-    from tests.test_device_args_cpu import _RecorderLib, _Walk
-    w = _Walk(monkeypatch)
+    w = A.Walk(monkeypatch)
     for match, kw in (("FTK_MATCH_ASSIGNMENT_MAX_ROWS", dict(m=4097)), ("FTK_MATCH_ASSIGNMENT_MAX_ROWS", dict(n=4097)), ("FTK_MATCH_ASSIGNMENT_MAX_ROWS", dict(m=0)),
                       ("FTK_MATCH_ASSIGNMENT_MAX_DIM", dict(d=1025)), ("FTK_MATCH_ASSIGNMENT_MAX_DIM", dict(d=0, weights=False)),
                       ("scale must be a finite number > 0", dict(weights=False, scale=0.0)), ("scale must be", dict(weights=False, scale=float("nan"))),
@@ -89,7 +61,7 @@ def test_other_refusals(monkeypatch):
                dict(row_stride=1 << 24, m=1), dict(scale=float("nan"))):  # (scale is ignored with weights)
         _call(w, **kw)
     assert len(w.lib.calls) == 9
-    recorder = _RecorderLib()
+    recorder = A.RecorderLib()
     monkeypatch.setattr(N, "lib", lambda: recorder)
     for match, call in (("dim must be an integer in 1", lambda: F.MatchAssignment.without_weights(0)), ("dim must be", lambda: F.MatchAssignment.without_weights(1025)),
                         ("dim must be", lambda: F.MatchAssignment.without_weights(64.0)), ("scale must be", lambda: F.MatchAssignment.without_weights(64, scale=0)),
@@ -135,12 +107,8 @@ def test_header_library_and_binding_agree():
     import feature_tracker_amd as F
     from feature_tracker_amd import _native as N
     from feature_tracker_amd import device as D
-    header = open(os.path.join(ROOT, "include", "ftk.h")).read()
-    for name in ("FTK_MATCH_ASSIGNMENT_MAX_ROWS", "FTK_MATCH_ASSIGNMENT_MAX_DIM"):
-        assert int(re.search(rf"#define {name} (\d+)", header).group(1)) == getattr(N, name)
-    assert int(re.search(r"#define FTK_ABI_VERSION (\d+)", header).group(1)) == 1
-    new = {"ftk_match_assignment_workspace_bytes", "ftk_match_assignment_device"}
-    assert new <= set(N.EXPORTS) and all(re.search(rf"\bint {s}\(", header) for s in new)
+    header = A.header_library_and_binding_agree(("FTK_MATCH_ASSIGNMENT_MAX_ROWS", "FTK_MATCH_ASSIGNMENT_MAX_DIM"),
+                                                {"ftk_match_assignment_workspace_bytes", "ftk_match_assignment_device"})
     assert "nn_feature_matcher.cpp:130-131" in header
     assert "MatchAssignment" in F.__all__ and callable(D.match_assignment_device)
     lib, out = N.lib(), C.c_int64()
@@ -156,11 +124,7 @@ def test_header_library_and_binding_agree():
 
 
 def test_nothing_in_the_package_imports_the_restatement():
-    pkg = os.path.join(ROOT, "feature_tracker_amd")
-    for folder, _, files in os.walk(pkg):
-        for f in files:
-            if f.endswith(".py"):
-                assert "match_assignment_ref" not in open(os.path.join(folder, f)).read(), f
+    A.nothing_in_the_package_imports("match_assignment_ref")
 
 
 def _plan(m, n, d, weights, stride, aligned):
@@ -188,15 +152,11 @@ def _plan(m, n, d, weights, stride, aligned):
 
 def test_plan_cli_equals_the_restated_plan():
     from feature_tracker_amd import _native as N
-    assert os.path.exists(PLAN_CLI), "host/build/match_assignment_plan_cli is missing: build() makes it"
     cases = [(m, n, d, weights, stride, aligned) for m, n in ((1, 1), (31, 33), (64, 65), (128, 129), (130, 130), (300, 2048), (4096, 4096), (0, 5), (3, 4097), (-1, -1))
              for d in (1, 2, 3, 64, 65, 256, 1024, 0, 1025) for weights in (0, 1) for stride in (0, n + 1, n + 5, n, 1 << 24, (1 << 24) + 1) for aligned in (0, 1)]
-    text = "".join(" ".join(str(v) for v in c) + "\n" for c in cases)
-    out = subprocess.run([PLAN_CLI], input=text, capture_output=True, text=True, check=True).stdout.strip().split("\n")
-    assert len(out) == len(cases)
+    plans = A.run_plan_tool(PLAN_CLI, cases)
     seen = set()
-    for case, line in zip(cases, out):
-        got = dict(kv.split("=") for kv in line.split())
+    for case, got in zip(cases, plans):
         want = _plan(*case)
         assert got == {k: str(v) for k, v in want.items()}, (case, got, want)
         seen.add(want["refused"])

@@ -15,6 +15,7 @@ from tests import raft_corr_ref as R
 
 torch = pytest.importorskip("torch")
 
+from tests import args_walk as A  # noqa: E402
 from tests.test_raft_corr_cpu import random_coords, torch_pyramid  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -278,13 +279,12 @@ def test_on_demand_raft_checks_the_levels_without_sizing_a_volume(monkeypatch):
         model(make_image(1, 1, 16, 24, 1), make_image(1, 1, 16, 24, 2))
 
 
-# the walk of tests/test_device_args_cpu.py (duck-typed tensors, a recording stand-in for the native library) over the two entries
+# the walk of tests/args_walk.py (duck-typed tensors, a recording stand-in for the native library) over the two entries
 
 
-def _walk(monkeypatch):
+def _walk(monkeypatch, spoil=None):
     from feature_tracker_amd import _native as N
-    from tests.test_device_args_cpu import _Walk
-    w = _Walk(monkeypatch)
+    w = A.Walk(monkeypatch, spoil=spoil)
     monkeypatch.setattr(N, "corr_ondemand_layout", lambda B, C, H, W, levels: (B * C * 2 * H * W, [], []))
     return w
 
@@ -311,21 +311,7 @@ def test_device_entries_take_no_pointer_of_an_unchecked_argument(monkeypatch, en
 @pytest.mark.parametrize("kind", ["dtype", "shape"])
 def test_device_entries_stop_before_the_library(monkeypatch, entry, which, kind):
     """Each tensor of the call in turn made float64, or one element longer in its last dimension."""
-    from tests.test_device_args_cpu import _FakeDtype
-    w = _walk(monkeypatch)
-    real_t, count = w.t, [0]
-
-    def t(n, dtype, *shape):
-        fake = real_t(n, dtype, *shape)
-        if count[0] == which:
-            if kind == "dtype":
-                fake.dtype = _FakeDtype("float64")
-            else:
-                fake.shape = fake.shape[:-1] + (fake.shape[-1] + 1,)
-        count[0] += 1
-        return fake
-
-    w.t = t
+    w = _walk(monkeypatch, spoil=(which, kind, A.one_column_more if kind == "shape" else None))
     with pytest.raises(ValueError):
         _calls(w)[entry]()
     assert w.lib.calls == [] and w.unchecked_reads == []

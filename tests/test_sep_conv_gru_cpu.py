@@ -18,6 +18,8 @@ from tests import sep_conv_gru_ref as R
 
 torch = pytest.importorskip("torch")
 
+from tests import args_walk as A  # noqa: E402
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PLAN_CLI = os.path.join(ROOT, "feature_tracker_amd", "host", "build", "sep_conv_gru_plan_cli")
 
@@ -331,7 +333,7 @@ def test_device_entry_refuses_bad_arguments_without_a_device():
         D.sep_conv_gru_device(ctx, [x] * 4, h, gru._packed, 5, *bufs)
 
 
-# the walk of tests/test_device_args_cpu.py (duck-typed tensors, a recording stand-in for the native library) over this entry
+# the walk of tests/args_walk.py (duck-typed tensors, a recording stand-in for the native library) over this entry
 WALK_TENSORS = 2 + 1 + 4 + 8  # two x parts, h, z / rh / mid / out, the packed eight
 
 
@@ -351,40 +353,20 @@ def _walk_call(w):
 
 
 def test_device_entry_takes_no_pointer_of_an_unchecked_argument(monkeypatch):
-    from tests.test_device_args_cpu import _Walk
-    w = _Walk(monkeypatch)
-    _walk_call(w)
-    assert w.unchecked_reads == []
-    assert w.lib.calls == ["ftk_sep_conv_gru_gates_device", "ftk_sep_conv_gru_blend_device"] * 2
-    assert len(w.made) == WALK_TENSORS and [f.name for f in w.made if f.reads != 1] == []
+    w = A.walk_call(monkeypatch, _walk_call, ["ftk_sep_conv_gru_gates_device", "ftk_sep_conv_gru_blend_device"] * 2)
+    assert len(w.made) == WALK_TENSORS
 
 
 @pytest.mark.parametrize("which", range(WALK_TENSORS))
 @pytest.mark.parametrize("kind", ["dtype", "shape", "device"])
 def test_device_entry_stops_before_the_library(monkeypatch, which, kind):
     """Each tensor of the call in turn made float64, one element longer in its last dimension, or moved to another device."""
-    from tests.test_device_args_cpu import _FakeDevice, _FakeDtype, _Walk
-    w = _Walk(monkeypatch)
-    real_t, count, name = w.t, [0], [None]
-
-    def t(n, dtype, *shape):
-        fake = real_t(n, dtype, *shape)
-        if count[0] == which:
-            name[0] = n
-            if kind == "dtype":
-                fake.dtype = _FakeDtype("float64")
-            elif kind == "shape":
-                fake.shape = fake.shape[:-1] + (fake.shape[-1] + 1,)
-            else:
-                fake.device = _FakeDevice(1)
-        count[0] += 1
-        return fake
-
-    w.t = t
+    w = A.Walk(monkeypatch, spoil=(which, kind, A.one_column_more if kind == "shape" else None))
     with pytest.raises(ValueError) as e:
         _walk_call(w)
-    if not (kind == "shape" and name[0] == "h"):  # a longer h is a legal h: the first x part is then the one refused
-        assert name[0].replace("'", "") in str(e.value).replace("'", ""), (name[0], str(e.value))
+    name = w.spoiled.name
+    if not (kind == "shape" and name == "h"):  # a longer h is a legal h: the first x part is then the one refused
+        assert name.replace("'", "") in str(e.value).replace("'", ""), (name, str(e.value))
     assert w.lib.calls == [] and w.unchecked_reads == []
 
 

@@ -17,6 +17,8 @@ from tests import superpoint_ref as R
 
 torch = pytest.importorskip("torch")
 
+from tests import args_walk as A  # noqa: E402
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PLAN_CLI = os.path.join(ROOT, "feature_tracker_amd", "host", "build", "raft_conv_plan_cli")
 RECORDED = os.path.join(ROOT, "tests", "golden", "superpoint", "raft_conv_plan_recorded.txt")
@@ -273,37 +275,18 @@ def _normalise_call(w, d=65, hc=3, wc=5, out_shape=None):
 
 @pytest.mark.parametrize("call,native,tensors", [(_pool_call, "ftk_conv2d_pool_device", 6), (_normalise_call, "ftk_channel_normalise_device", 2)])
 def test_device_entries_take_no_pointer_of_an_unchecked_argument(monkeypatch, call, native, tensors):
-    from tests.test_device_args_cpu import _FakeDevice, _FakeDtype, _Walk
-    w = _Walk(monkeypatch)
-    call(w)
-    assert w.unchecked_reads == [] and w.lib.calls == [native]
-    assert len(w.made) == tensors and [f.name for f in w.made if f.reads != 1] == []
+    w = A.walk_call(monkeypatch, call, [native])
+    assert len(w.made) == tensors
     for which in range(tensors):
         for kind in ("dtype", "shape", "device"):
-            w = _Walk(monkeypatch)
-            real_t, count = w.t, [0]
-
-            def t(n, dtype, *shape):
-                fake = real_t(n, dtype, *shape)
-                if count[0] == which:
-                    if kind == "dtype":
-                        fake.dtype = _FakeDtype("float64")
-                    elif kind == "shape":
-                        fake.shape = fake.shape[:-1] + (fake.shape[-1] + 1,)
-                    else:
-                        fake.device = _FakeDevice(1)
-                count[0] += 1
-                return fake
-
-            w.t = t
+            w = A.Walk(monkeypatch, spoil=(which, kind, A.one_column_more if kind == "shape" else None))
             with pytest.raises(ValueError):
                 call(w)
             assert w.lib.calls == [] and w.unchecked_reads == [], (which, kind)
 
 
 def test_device_entries_refuse_before_the_library(monkeypatch):
-    from tests.test_device_args_cpu import _Walk
-    w = _Walk(monkeypatch)
+    w = A.Walk(monkeypatch)
     for match, call, kw in (("kernel_size 7 is not supported with the max-pool", _pool_call, dict(ks=7)), ("kernel_size 5", _pool_call, dict(ks=5)),
                             ("out must be .*0, 3", _pool_call, dict(H=1)), ("FTK_KEYPOINT_DECODE_MAX_CHANNELS", _normalise_call, dict(d=1025)),
                             ("non-empty", _normalise_call, dict(hc=0)), ("out must be", _normalise_call, dict(out_shape=(65, 3, 5)))):
@@ -314,7 +297,6 @@ def test_device_entries_refuse_before_the_library(monkeypatch):
 
 def test_a_forward_pass_is_twelve_calls_in_order(monkeypatch):
     import feature_tracker_amd as F
-    from tests.test_device_args_cpu import _Walk
     sp = F.SuperPoint.from_state_dict(R.make_state(NARROW, 1))
     assert sp.widths == dict(zip(R.LAYERS, (4, 4, 4, 4, 8, 8, 8, 8, 8, 65, 8, 16))) and (sp.detector_hidden, sp.descriptor_hidden, sp.descriptor_channels) == (8, 8, 16)
     assert set(sp.weights) == {f"{layer}.{kind}" for layer in R.LAYERS for kind in ("weight", "bias")}
@@ -332,7 +314,7 @@ def test_a_forward_pass_is_twelve_calls_in_order(monkeypatch):
     assert shapes["conv1a"] == (1, 4, 16, 24) and shapes["conv1b"] == (1, 4, 8, 12) and shapes["conv3b"] == shapes["conv4b"] == (1, 8, 2, 3)
     assert shapes["convPa+convDa"] == (1, 16, 2, 3) and shapes["convPb"] == (1, 65, 2, 3) and shapes["convDb"] == (1, 16, 2, 3) and shapes["desc"] == (2, 3, 16)
     # the pass itself, over stand-ins of every tensor it touches
-    w = _Walk(monkeypatch)
+    w = A.Walk(monkeypatch)
     sp._layers = {name: (w.t(name + ".packed", "float32", int(layer[0].numel())), w.t(name + ".bias", "float32", layer[3]), layer[2], layer[3])
                   for name, layer in sp._layers.items()}
     bufs = {name: w.t(name, "float32", *shape) for name, shape in shapes.items()}
@@ -346,8 +328,7 @@ def test_a_forward_pass_is_twelve_calls_in_order(monkeypatch):
 def test_superpoint_refuses_by_key_and_before_any_call(monkeypatch):
     import feature_tracker_amd as F
     from feature_tracker_amd import _native as N
-    from tests.test_device_args_cpu import _RecorderLib
-    recorder = _RecorderLib()
+    recorder = A.RecorderLib()
     monkeypatch.setattr(N, "lib", lambda: recorder)
     state = R.make_state(NARROW, 1)
     assert F.SuperPoint.from_state_dict({"net." + k: v for k, v in state.items()}, prefix="net.").widths["convDb"] == 16

@@ -1,18 +1,16 @@
-"""The loud failures of the transformer layer before any device is touched: the walk of tests/test_device_args_cpu.py over
+"""The loud failures of the transformer layer before any device is touched: the walk of tests/args_walk.py over
 ``device.attention_device``, ``device.linear_device`` and ``device.transformer_layer_device``; the refusals of ``attention``,
 ``TransformerLayer`` and ``LightGlue``; the agreement of header, library and binding; and the launch plan through
 host/build/transformer_plan_cli."""
-import os
-import re
-import subprocess
 import types
 
 import pytest
 
 torch = pytest.importorskip("torch")
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PLAN_CLI = os.path.join(ROOT, "feature_tracker_amd", "host", "build", "transformer_plan_cli")
+from tests import args_walk as A  # noqa: E402
+
+PLAN_CLI = A.plan_cli("transformer_plan_cli")
 
 
 def _layer(w, m=6, n=7, d=16, h=4, counts=True):
@@ -43,44 +41,19 @@ CALLS = {"ftk_transformer_layer_device": _layer, "ftk_attention_device": _attent
 
 @pytest.mark.parametrize("native", sorted(CALLS))
 def test_entry_takes_no_pointer_of_an_unchecked_argument(monkeypatch, native):
-    from tests.test_device_args_cpu import _Walk
-    w = _Walk(monkeypatch)
-    CALLS[native](w)
-    assert w.unchecked_reads == [] and w.lib.calls == [native]
-    assert [f.name for f in w.made if f.reads != 1] == []
+    A.walk_call(monkeypatch, CALLS[native], [native])
 
 
 @pytest.mark.parametrize("kind", ["dtype", "device"])
 @pytest.mark.parametrize("native", sorted(CALLS))
 def test_each_refused_tensor_stops_the_entry_before_the_library(monkeypatch, native, kind):
-    from tests.test_device_args_cpu import _FakeDevice, _FakeDtype, _Walk
-    probe = _Walk(monkeypatch)
-    CALLS[native](probe)
-    for k, made in enumerate(probe.made):
-        w = _Walk(monkeypatch)
-        real_t, count = w.t, [0]
-
-        def t(name, dtype, *shape):
-            fake = real_t(name, dtype, *shape)
-            if count[0] == k:
-                if kind == "dtype":
-                    fake.dtype = _FakeDtype("float64")
-                else:
-                    fake.device = _FakeDevice(1)
-            count[0] += 1
-            return fake
-
-        w.t = t
-        with pytest.raises(ValueError, match=f"^{made.name} must be"):
-            CALLS[native](w)
-        assert w.lib.calls == [] and w.unchecked_reads == []
+    A.refusal_sweep(monkeypatch, CALLS[native], kind)
 
 
 def test_other_refusals(monkeypatch):
     import feature_tracker_amd as F
     from feature_tracker_amd import _native as N
-    from tests.test_device_args_cpu import _RecorderLib, _Walk
-    w = _Walk(monkeypatch)
+    w = A.Walk(monkeypatch)
     for match, call, kw in (("FTK_TRANSFORMER_MAX_ROWS", _layer, dict(m=4097)), ("FTK_TRANSFORMER_MAX_ROWS", _layer, dict(n=0)),
                             ("FTK_TRANSFORMER_MAX_DIM", _layer, dict(d=1028, h=257)), ("must divide D", _layer, dict(d=16, h=3)),
                             ("FTK_TRANSFORMER_MAX_HEAD_DIM", _layer, dict(d=6, h=2)), ("FTK_TRANSFORMER_MAX_HEAD_DIM", _layer, dict(d=260, h=2)),
@@ -97,7 +70,7 @@ def test_other_refusals(monkeypatch):
                      (_layer, dict(d=1024, h=8)), (_attention, dict(count=False)), (_attention, dict(dh=128, post=0.25)), (_linear, dict(k=1024, o=1024))):
         call(w, **kw)
     assert len(w.lib.calls) == 8
-    recorder = _RecorderLib()
+    recorder = A.RecorderLib()
     monkeypatch.setattr(N, "lib", lambda: recorder)
     d, h = 16, 4
     sd = {}
@@ -179,11 +152,8 @@ def test_header_library_and_binding_agree():
     import feature_tracker_amd as F
     from feature_tracker_amd import _native as N
     from feature_tracker_amd import device as D
-    header = open(os.path.join(ROOT, "include", "ftk.h")).read()
-    for name in ("FTK_TRANSFORMER_MAX_ROWS", "FTK_TRANSFORMER_MAX_DIM", "FTK_TRANSFORMER_MAX_HEAD_DIM"):
-        assert int(re.search(rf"#define {name} (\d+)", header).group(1)) == getattr(N, name)
-    new = {"ftk_transformer_layer_workspace_bytes", "ftk_attention_device", "ftk_linear_device", "ftk_transformer_layer_device"}
-    assert new <= set(N.EXPORTS) and all(re.search(rf"\bint {s}\(", header) for s in new)
+    A.header_library_and_binding_agree(("FTK_TRANSFORMER_MAX_ROWS", "FTK_TRANSFORMER_MAX_DIM", "FTK_TRANSFORMER_MAX_HEAD_DIM"),
+                                       {"ftk_transformer_layer_workspace_bytes", "ftk_attention_device", "ftk_linear_device", "ftk_transformer_layer_device"})
     assert {"TransformerLayer", "LightGlue", "attention", "rotary_encoding"} <= set(F.__all__)
     assert callable(D.attention_device) and callable(D.linear_device) and callable(D.transformer_layer_device)
     lib, out = N.lib(), C.c_int64()
@@ -201,11 +171,7 @@ def test_header_library_and_binding_agree():
 
 
 def test_nothing_in_the_package_imports_the_restatement():
-    pkg = os.path.join(ROOT, "feature_tracker_amd")
-    for folder, _, files in os.walk(pkg):
-        for f in files:
-            if f.endswith(".py"):
-                assert "transformer_ref" not in open(os.path.join(folder, f)).read(), f
+    A.nothing_in_the_package_imports("transformer_ref")
 
 
 def _plan(m, n, d, h, aligned):
@@ -246,13 +212,10 @@ def test_the_shapes_of_the_non_vector_gpu_tests_plan_the_non_vector_kernels():
     alignment; LAYER_SHAPES[2] plans them only for buffers that are not 16-byte aligned; D = 130 has the column tiles it is there for;
     and the Linear's row tile is the header's kLinearTileRows, which LINEAR_ROWS brackets."""
     from tests import transformer_ref as R
-    assert os.path.exists(PLAN_CLI), "host/build/transformer_plan_cli is missing: build() makes it"
     tile = R.linear_tile_rows()
     assert R.LINEAR_ROWS == (1, 31, 32, 33, tile - 1, tile, tile + 1)
     cases = [s[:4] + (1,) for s in R.LAYER_NARROW] + [R.LAYER_SHAPES[2][:4] + (0,), R.LAYER_SHAPES[2][:4] + (1,), (tile - 1, 1, 8, 2, 1), (tile, 1, 8, 2, 1)]
-    text = "".join(" ".join(str(v) for v in c) + "\n" for c in cases)
-    out = subprocess.run([PLAN_CLI], input=text, capture_output=True, text=True, check=True).stdout.strip().split("\n")
-    plans = [dict(kv.split("=") for kv in line.split()) for line in out]
+    plans = A.run_plan_tool(PLAN_CLI, cases)
     assert all(p["refused"] == "none" for p in plans)
     k = len(R.LAYER_NARROW)
     assert all(s[2] % 4 != 0 for s in R.LAYER_NARROW) and all((p["vec_linear"], p["vec_attn"]) == ("0", "0") for p in plans[:k])
@@ -263,16 +226,12 @@ def test_the_shapes_of_the_non_vector_gpu_tests_plan_the_non_vector_kernels():
 
 def test_plan_cli_equals_the_restated_plan():
     from feature_tracker_amd import _native as N
-    assert os.path.exists(PLAN_CLI), "host/build/transformer_plan_cli is missing: build() makes it"
     cases = [(m, n, d, h, aligned) for m, n in ((1, 1), (31, 33), (65, 130), (300, 300), (1024, 1000), (2048, 2048), (4096, 4096), (4097, 1), (1, 4097), (0, 5), (-1, -1))
              for d, h in ((4, 2), (6, 1), (6, 3), (8, 2), (64, 4), (256, 4), (256, 2), (1024, 8), (1024, 16), (6, 2), (260, 2), (7, 2), (256, 3), (0, 1), (1025, 5), (4, 0), (8, 8))
              for aligned in (0, 1)]
-    text = "".join(" ".join(str(v) for v in c) + "\n" for c in cases)
-    out = subprocess.run([PLAN_CLI], input=text, capture_output=True, text=True, check=True).stdout.strip().split("\n")
-    assert len(out) == len(cases)
+    plans = A.run_plan_tool(PLAN_CLI, cases)
     seen = set()
-    for case, line in zip(cases, out):
-        got = dict(kv.split("=") for kv in line.split())
+    for case, got in zip(cases, plans):
         want = _plan(*case)
         assert got == {k: str(v) for k, v in want.items()}, (case, got, want)
         seen.add(want["refused"])

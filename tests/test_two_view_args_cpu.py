@@ -1,17 +1,15 @@
 """The loud failures of two-view outlier rejection with a choice of model before any device is touched: the walk of
-tests/test_device_args_cpu.py over ``device.two_view_ransac_device``; the refusals of ``TwoViewRansac`` and of ``KltVideoTracker``'s new
+tests/args_walk.py over ``device.two_view_ransac_device``; the refusals of ``TwoViewRansac`` and of ``KltVideoTracker``'s new
 arguments; the agreement of header, library and binding; the launch plan through host/build/two_view_plan_cli; and the restated video runs."""
-import os
-import re
-import subprocess
 import types
 
 import pytest
 
 torch = pytest.importorskip("torch")
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PLAN_CLI = os.path.join(ROOT, "feature_tracker_amd", "host", "build", "two_view_plan_cli")
+from tests import args_walk as A  # noqa: E402
+
+PLAN_CLI = A.plan_cli("two_view_plan_cli")
 
 
 def _call(w, n=40, k=64, image=(120, 160), threshold=1.0, seed=0, model="auto", permille=750):
@@ -24,45 +22,19 @@ def _call(w, n=40, k=64, image=(120, 160), threshold=1.0, seed=0, model="auto", 
 
 
 def test_entry_takes_no_pointer_of_an_unchecked_argument(monkeypatch):
-    from tests.test_device_args_cpu import _Walk
-    w = _Walk(monkeypatch)
-    _call(w)
-    assert w.unchecked_reads == [] and w.lib.calls == ["ftk_two_view_ransac_device"]
-    assert [f.name for f in w.made if f.reads != 1] == []
+    A.walk_call(monkeypatch, _call, ["ftk_two_view_ransac_device"])
 
 
 @pytest.mark.parametrize("kind", ["dtype", "shape", "device"])
 def test_each_refused_tensor_stops_the_entry_before_the_library(monkeypatch, kind):
-    from tests.test_device_args_cpu import _FakeDevice, _FakeDtype, _Walk
-    probe = _Walk(monkeypatch)
-    _call(probe)
-    for k, made in enumerate(probe.made):
-        w = _Walk(monkeypatch)
-        real_t, count = w.t, [0]
-
-        def t(name, dtype, *shape):
-            fake = real_t(name, dtype, *shape)
-            if count[0] == k:
-                if kind == "dtype":
-                    fake.dtype = _FakeDtype("float64")
-                elif kind == "shape":
-                    fake.shape = (fake.shape[0] - 1,) + fake.shape[1:]
-                else:
-                    fake.device = _FakeDevice(1)
-            count[0] += 1
-            return fake
-
-        w.t = t
-        with pytest.raises(ValueError, match="must be" if kind == "shape" and made.name == "ref_uv" else f"^{made.name} must be"):
-            _call(w)
-        assert w.lib.calls == [] and w.unchecked_reads == []
+    # (ref_uv with a row fewer is a valid tensor: cur_uv, sized by it, is the one refused)
+    A.refusal_sweep(monkeypatch, _call, kind, loose=("ref_uv",))
 
 
 def test_other_refusals(monkeypatch):
     import feature_tracker_amd as F
     from feature_tracker_amd import _native as N
-    from tests.test_device_args_cpu import _RecorderLib, _Walk
-    w = _Walk(monkeypatch)
+    w = A.Walk(monkeypatch)
     for match, kw in (("hypotheses must be in 1 .. FTK_EPIPOLAR_MAX_HYPOTHESES", dict(k=4097)), ("threshold", dict(threshold=-1.0)),
                       ("image_size", dict(image=(0, 160))), ("seed must be a uint32", dict(seed=-1)), ("FTK_TRACK_TABLE_MAX_SLOTS", dict(n=65537)),
                       ("model must be one of", dict(model="affine")), ("model must be one of", dict(model=3)), ("model must be one of", dict(model=None)),
@@ -74,7 +46,7 @@ def test_other_refusals(monkeypatch):
     for model in ("fundamental", "homography", "auto", 0, 1, 2):
         _call(w, model=model)
     assert len(w.lib.calls) == 6
-    recorder = _RecorderLib()
+    recorder = A.RecorderLib()
     monkeypatch.setattr(N, "lib", lambda: recorder)
     for match, kw in (("model must be one of", dict(model="essential")), ("model must be one of", dict(model=None)), ("hypotheses", dict(hypotheses=0)),
                       ("threshold", dict(threshold=-0.5)), ("seed", dict(seed=-3)), ("prefer_homography", dict(prefer_homography=1.001)),
@@ -111,13 +83,9 @@ def test_header_library_and_binding_agree():
     import ctypes as C
     import feature_tracker_amd as F
     from feature_tracker_amd import _native as N
-    header = open(os.path.join(ROOT, "include", "ftk.h")).read()
-    for name in ("FTK_TWO_VIEW_FUNDAMENTAL", "FTK_TWO_VIEW_HOMOGRAPHY", "FTK_TWO_VIEW_AUTO", "FTK_TWO_VIEW_HOMOGRAPHY_SAMPLE"):
-        assert int(re.search(rf"#define {name} (\d+)", header).group(1)) == getattr(N, name)
+    A.header_library_and_binding_agree(("FTK_TWO_VIEW_FUNDAMENTAL", "FTK_TWO_VIEW_HOMOGRAPHY", "FTK_TWO_VIEW_AUTO", "FTK_TWO_VIEW_HOMOGRAPHY_SAMPLE"),
+                                       {"ftk_two_view_workspace_bytes", "ftk_two_view_ransac_device"})
     assert N.TWO_VIEW_MODES == {"fundamental": N.FTK_TWO_VIEW_FUNDAMENTAL, "homography": N.FTK_TWO_VIEW_HOMOGRAPHY, "auto": N.FTK_TWO_VIEW_AUTO}
-    assert int(re.search(r"#define FTK_ABI_VERSION (\d+)", header).group(1)) == 1
-    new = {"ftk_two_view_workspace_bytes", "ftk_two_view_ransac_device"}
-    assert new <= set(N.EXPORTS) and all(re.search(rf"\bint {s}\(", header) for s in new)
     assert {"TwoViewRansac", "TwoViewResult"} <= set(F.__all__)
     lib, out = N.lib(), C.c_int64()
     for n, k in ((1, 1), (7, 3), (300, 512), (1025, 1000), (65536, 4096)):
@@ -131,11 +99,7 @@ def test_header_library_and_binding_agree():
 
 
 def test_nothing_in_the_package_imports_the_restatement():
-    pkg = os.path.join(ROOT, "feature_tracker_amd")
-    for folder, _, files in os.walk(pkg):
-        for f in files:
-            if f.endswith(".py"):
-                assert "two_view_ref" not in open(os.path.join(folder, f)).read(), f
+    A.nothing_in_the_package_imports("two_view_ref")
 
 
 def _plan(n, k, rows, cols, mode, permille):
@@ -165,17 +129,13 @@ def _plan(n, k, rows, cols, mode, permille):
 
 def test_plan_cli_equals_the_restated_plan():
     from feature_tracker_amd import _native as N
-    assert os.path.exists(PLAN_CLI), "host/build/two_view_plan_cli is missing: build() makes it"
     cases = [(n, k, 480, 640, mode, 750) for n in (0, 1, 3, 4, 7, 8, 256, 257, 1024, 1025, 65536, 65537, -1) for k in (0, 1, 16, 17, 64, 65, 1024, 1025, 4096, 4097)
              for mode in (0, 1, 2)]
     cases += [(8, 8, 0, 640, 2, 750), (8, 8, 480, 65537, 2, 750), (8, 8, 65536, 65536, 2, 750), (8, 8, 480, 640, 3, 750), (8, 8, 480, 640, -1, 750),
               (8, 8, 480, 640, 2, -1), (8, 8, 480, 640, 2, 1001), (8, 8, 480, 640, 2, 0), (8, 8, 480, 640, 2, 1000)]
-    text = "".join(" ".join(str(v) for v in c) + "\n" for c in cases)
-    out = subprocess.run([PLAN_CLI], input=text, capture_output=True, text=True, check=True).stdout.strip().split("\n")
-    assert len(out) == len(cases)
+    plans = A.run_plan_tool(PLAN_CLI, cases)
     seen = set()
-    for case, line in zip(cases, out):
-        got = dict(kv.split("=") for kv in line.split())
+    for case, got in zip(cases, plans):
         want = _plan(*case)
         assert got == {k: str(v) for k, v in want.items()}, (case, got, want)
         seen.add(want["refused"])

@@ -20,6 +20,7 @@ from tests import raft_conv_ref as R
 
 torch = pytest.importorskip("torch")
 
+from tests import args_walk as A  # noqa: E402
 from tests.test_sep_conv_gru_cpu import make_state as make_gru_state  # noqa: E402
 from tests.test_sep_conv_gru_cpu import torch_forward as gru_torch_forward  # noqa: E402
 
@@ -335,7 +336,7 @@ def test_device_entry_refuses_bad_arguments_without_a_device():
         D.conv2d_device(ctx, [x], w, b, 3, True, float("nan"), out)
 
 
-# the walk of tests/test_device_args_cpu.py (duck-typed tensors, a recording stand-in for the native library) over this entry
+# the walk of tests/args_walk.py (duck-typed tensors, a recording stand-in for the native library) over this entry
 WALK_TENSORS = 1 + 3 + 2  # out, three parts, the packed weights and the bias
 
 
@@ -351,40 +352,20 @@ def _walk_call(w):
 
 
 def test_device_entry_takes_no_pointer_of_an_unchecked_argument(monkeypatch):
-    from tests.test_device_args_cpu import _Walk
-    w = _Walk(monkeypatch)
-    _walk_call(w)
-    assert w.unchecked_reads == []
-    assert w.lib.calls == ["ftk_conv2d_device"]
-    assert len(w.made) == WALK_TENSORS and [f.name for f in w.made if f.reads != 1] == []
+    w = A.walk_call(monkeypatch, _walk_call, ["ftk_conv2d_device"])
+    assert len(w.made) == WALK_TENSORS
 
 
 @pytest.mark.parametrize("which", range(WALK_TENSORS))
 @pytest.mark.parametrize("kind", ["dtype", "shape", "device"])
 def test_device_entry_stops_before_the_library(monkeypatch, which, kind):
     """Each tensor of the call in turn made float64, one element longer in its last dimension, or moved to another device."""
-    from tests.test_device_args_cpu import _FakeDevice, _FakeDtype, _Walk
-    w = _Walk(monkeypatch)
-    real_t, count, name = w.t, [0], [None]
-
-    def t(n, dtype, *shape):
-        fake = real_t(n, dtype, *shape)
-        if count[0] == which:
-            name[0] = n
-            if kind == "dtype":
-                fake.dtype = _FakeDtype("float64")
-            elif kind == "shape":
-                fake.shape = fake.shape[:-1] + (fake.shape[-1] + 1,)
-            else:
-                fake.device = _FakeDevice(1)
-        count[0] += 1
-        return fake
-
-    w.t = t
+    w = A.Walk(monkeypatch, spoil=(which, kind, A.one_column_more if kind == "shape" else None))
     with pytest.raises(ValueError) as e:
         _walk_call(w)
-    if not (kind == "shape" and name[0] == "out"):  # a wider out is a legal out: the first part is then the one refused
-        assert name[0] in str(e.value), (name[0], str(e.value))
+    name = w.spoiled.name
+    if not (kind == "shape" and name == "out"):  # a wider out is a legal out: the first part is then the one refused
+        assert name in str(e.value), (name, str(e.value))
     assert w.lib.calls == [] and w.unchecked_reads == []
 
 

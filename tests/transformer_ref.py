@@ -9,14 +9,12 @@ from __future__ import annotations
 import ctypes as C
 import functools
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 
+from tests.ref_build import compile_ref
+
 _SRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "transformer_ref.c")
-_lib = None
-_tmpdir = None
 
 CONTRACT = 0
 MUTANTS = {"rotary_pairs_as_halves": 1, "qkv_columns_as_3_h_dh": 2, "reverse_cross_softmax_along_the_wrong_axis": 3, "invalid_keys_inside_a_softmax": 4,
@@ -26,32 +24,26 @@ LAYER_TENSORS = ("self_attn.Wqkv", "self_attn.out_proj", "self_attn.ffn.0", "sel
                  "cross_attn.to_out", "cross_attn.ffn.0", "cross_attn.ffn.1", "cross_attn.ffn.3")
 
 
+@functools.lru_cache(maxsize=None)
 def lib():
-    global _lib, _tmpdir
-    if _lib is None:
-        _tmpdir = tempfile.TemporaryDirectory(prefix="transformer_ref_")
-        path = os.path.join(_tmpdir.name, "libtransformer_ref.so")
-        flags = ["-O3", "-std=c99", "-ffp-contract=off", "-fno-fast-math"]
-        subprocess.run(["gcc"] + flags + ["-shared", "-fPIC", "-o", path, _SRC, "-lm"], check=True, capture_output=True)
-        l = C.CDLL(path)
-        vp, i32, f32 = C.c_void_p, C.c_int32, C.c_float
-        for name in ("tr_exp_c", "tr_erf_c"):
-            getattr(l, name).argtypes = [f32]
-            getattr(l, name).restype = f32
-        l.tr_linear.argtypes = [vp, vp, i32, i32, i32, vp, vp, i32, vp, vp]
-        l.tr_linear.restype = None
-        l.tr_rotary.argtypes = [vp, i32, i32, i32, vp, i32]
-        l.tr_rotary.restype = None
-        l.tr_attention.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, f32, f32, vp]
-        l.tr_attention.restype = None
-        l.tr_layernorm_gelu.argtypes = [vp, i32, i32, vp, vp, i32]
-        l.tr_layernorm_gelu.restype = None
-        l.tr_layer_weight_floats.argtypes = [i32]
-        l.tr_layer_weight_floats.restype = C.c_int64
-        l.tr_layer.argtypes = [vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp]
-        l.tr_layer.restype = i32
-        _lib = l
-    return _lib
+    l = compile_ref("transformer_ref", [_SRC])
+    vp, i32, f32 = C.c_void_p, C.c_int32, C.c_float
+    for name in ("tr_exp_c", "tr_erf_c"):
+        getattr(l, name).argtypes = [f32]
+        getattr(l, name).restype = f32
+    l.tr_linear.argtypes = [vp, vp, i32, i32, i32, vp, vp, i32, vp, vp]
+    l.tr_linear.restype = None
+    l.tr_rotary.argtypes = [vp, i32, i32, i32, vp, i32]
+    l.tr_rotary.restype = None
+    l.tr_attention.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, f32, f32, vp]
+    l.tr_attention.restype = None
+    l.tr_layernorm_gelu.argtypes = [vp, i32, i32, vp, vp, i32]
+    l.tr_layernorm_gelu.restype = None
+    l.tr_layer_weight_floats.argtypes = [i32]
+    l.tr_layer_weight_floats.restype = C.c_int64
+    l.tr_layer.argtypes = [vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp]
+    l.tr_layer.restype = i32
+    return l
 
 
 def _p(a):

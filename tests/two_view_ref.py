@@ -9,16 +9,13 @@ from __future__ import annotations
 import ctypes as C
 import functools
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 
 from tests import epipolar_ref as E
+from tests.ref_build import compile_ref
 
 _SRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "two_view_ref.c")
-_lib = None
-_tmpdir = None
 
 TRACKED, LARGE_RESIDUAL = E.TRACKED, E.LARGE_RESIDUAL
 FUNDAMENTAL, HOMOGRAPHY, AUTO = 0, 1, 2
@@ -30,21 +27,15 @@ F_SAMPLE, H_SAMPLE, ATTEMPTS = 8, 4, 16
 IMAGE = E.IMAGE
 
 
+@functools.lru_cache(maxsize=None)
 def lib():
-    global _lib, _tmpdir
-    if _lib is None:
-        _tmpdir = tempfile.TemporaryDirectory(prefix="two_view_ref_")
-        path = os.path.join(_tmpdir.name, "libtwo_view_ref.so")
-        flags = ["-O3", "-std=c99", "-ffp-contract=off", "-fno-fast-math"]
-        subprocess.run(["gcc"] + flags + ["-shared", "-fPIC", "-o", path, _SRC, "-lm"], check=True, capture_output=True)
-        l = C.CDLL(path)
-        vp, i32, u32 = C.c_void_p, C.c_int32, C.c_uint32
-        l.tvr_choose.argtypes = [i32] * 6
-        l.tvr_choose.restype = i32
-        l.tvr_ransac.argtypes = [vp, vp, vp, i32, i32, i32, C.c_float, i32, u32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-        l.tvr_ransac.restype = i32
-        _lib = l
-    return _lib
+    l = compile_ref("two_view_ref", [_SRC])
+    vp, i32, u32 = C.c_void_p, C.c_int32, C.c_uint32
+    l.tvr_choose.argtypes = [i32] * 6
+    l.tvr_choose.restype = i32
+    l.tvr_ransac.argtypes = [vp, vp, vp, i32, i32, i32, C.c_float, i32, u32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    l.tvr_ransac.restype = i32
+    return l
 
 
 class Result:
