@@ -96,6 +96,8 @@ struct KltParams {
     uint32_t spill_stride_floats;
     int32_t tree;                        // 0: sums in the reference's order (the contract); 1: throughput mode — the same per-pixel products, summed
                                          // by per-lane partials + a cross-lane butterfly (ftk_set_reduction_mode; reported, never the default)
+    int32_t scale_recip;                 // 1: n_levels - 1 <= 30, so the coarsest level's 2^-(n_levels - 1) is a normal float and a kernel may multiply by
+                                         // it where it would divide by 2^(n_levels - 1) (klt_basic_kernels.hip; set by klt_plan_call)
 };
 
 // ceil(2^32 / d): row = umulhi(index, magic)

@@ -75,6 +75,7 @@ int klt_plan_call(ftk_context *ctx, int model, const ftk_klt_options *opt, const
     ftk::KltPlanInput in = {};
     p.n_levels = single_level ? 1 : ref->n_levels;
     p.single_level = single_level ? 1 : 0;
+    p.scale_recip = (p.n_levels - 1 <= 30) ? 1 : 0;  // (always, while FTK_MAX_LEVELS <= 31: the kernels take it from here, not from that)
     for (int i = 0; i < p.n_levels; ++i) {
         p.ref[i] = ref->levels[i];
         p.cur[i] = cur->levels[i];

@@ -290,6 +290,12 @@ __device__ __forceinline__ uint32_t magic20(int d) {
 
 constexpr int kWavesPerEu = 4;
 
+// window_inside() of klt_common.h for a wave-uniform origin: r_lo + wrows <= rows written as r_lo <= rows - wrows has no sum that
+// could overflow, so the four tests are 32-bit scalar compares (the 64-bit form costs vector moves and two vector compares per call).
+__device__ __forceinline__ bool pb_window_inside(const DevImage &im, int r_lo, int c_lo, int wrows, int wcols) {
+    return r_lo >= 0 && c_lo >= 0 && r_lo <= im.rows - wrows && c_lo <= im.cols - wcols - 4;
+}
+
 // Workgroup barrier — or, for one-wave features packed several to a workgroup (solo), only a compiler fence: LDS operations of
 // one wave execute in program order, and the other waves of the group work on other features.
 __device__ __forceinline__ void pb_sync(bool solo) {
@@ -418,25 +424,46 @@ __global__ void __attribute__((amdgpu_waves_per_eu(kWavesPerEu))) __launch_bound
     // basic_klt.cpp:10,18-19 (pyramid) / :59-86 (single level)
     const float full_ref_u = full_ref.x, full_ref_v = full_ref.y;
     const float scale = p.single_level ? 1.0f : (float)(1 << (p.n_levels - 1));
-    float ref_u = p.single_level ? full_ref_u : full_ref_u / scale;
-    float ref_v = p.single_level ? full_ref_v : full_ref_v / scale;
-    float cur_u = p.single_level ? in_u : in_u / scale;
-    float cur_v = p.single_level ? in_v : in_v / scale;
+    float ref_u = full_ref_u, ref_v = full_ref_v, cur_u = in_u, cur_v = in_v;
+    if (!p.single_level) {
+        // scale = 2^k: x * 2^-k is the correctly rounded x / 2^k, four multiplications instead of four ~11-instruction divisions in
+        // every wave.  Taken only when the host has checked k <= 30 (p.scale_recip, klt_plan_call) and all four quotients are normal
+        // numbers (|x| >= 2^(k - 126); a NaN fails the test) — the same answer in every lane of the wave; everything else divides.
+        const uint32_t k = (uint32_t)(p.n_levels - 1);
+        const float inv_scale = __uint_as_float((127u - k) << 23), least = __uint_as_float((1u + k) << 23);
+        const bool normal = fabsf(full_ref_u) >= least && fabsf(full_ref_v) >= least && fabsf(in_u) >= least && fabsf(in_v) >= least;
+        if (p.scale_recip && wave_ballot(!normal) == 0ull) {
+            ref_u = full_ref_u * inv_scale;
+            ref_v = full_ref_v * inv_scale;
+            cur_u = in_u * inv_scale;
+            cur_v = in_v * inv_scale;
+        } else {
+            ref_u = full_ref_u / scale;
+            ref_v = full_ref_v / scale;
+            cur_u = in_u / scale;
+            cur_v = in_v / scale;
+        }
+    }
 
     const int rrows = p.pb_rwin_rows, rcols = p.pb_rwin_cols;
     const int ref_quads_total = rrows * (rcols >> 2), cur_quads_total = p.cwin_rows * (p.cwin_cols >> 2);
     const bool ref_fits = ref_quads_total <= kRefQuads * b.nt, cur_fits = cur_quads_total <= kCurQuads * b.nt;
 
     int buf = 0;
+    // origin of this level's reference window: computed once per level, as the NEXT level's origin while the level before it is entered
+    int ref_r_lo, ref_c_lo;
     {
         // the coarsest level's reference window: nothing to overlap it with yet
         const DevImage ref = p_arg.ref[p.n_levels - 1];
-        int r_lo, c_lo;
-        footprint_origin(p, ref_u, ref_v, r_lo, c_lo);
-        stage_any(opaque_blk(b), ref, c.ref_win, r_lo, c_lo, rrows, rcols, p.pb_magic_rwc, p.pb_magic_rwq);
+        footprint_origin(p, ref_u, ref_v, ref_r_lo, ref_c_lo);
+        stage_any(opaque_blk(b), ref, c.ref_win, ref_r_lo, ref_c_lo, rrows, rcols, p.pb_magic_rwc, p.pb_magic_rwq);
     }
     uint32_t iters = 0;
     float out_u = in_u, out_v = in_v;
+    // the column axis has patch_cols + 2 nodes on every level but those with an extra node: that divisor's magic once (a constant
+    // in the compile-time geometries), not a float division and a correction loop per level in every thread
+    const int base_n_c = p.patch_cols + 2;
+    const uint32_t base_magic = (HC > 0) ? (uint32_t)((1048576 + base_n_c - 1) / base_n_c) : magic20(base_n_c);
     for (int level = p.n_levels - 1; level > -1; --level) {
         const DevImage ref = p_arg.ref[level];
         const DevImage cur = p_arg.cur[level];
@@ -446,7 +473,8 @@ __global__ void __attribute__((amdgpu_waves_per_eu(kWavesPerEu))) __launch_bound
         rw.data = c.ref_win + buf * c.ref_win_stride;
         rw.rows = rrows;
         rw.cols = rcols;
-        footprint_origin(p, ref_u, ref_v, rw.r_lo, rw.c_lo);
+        rw.r_lo = ref_r_lo;
+        rw.c_lo = ref_c_lo;
         int need_r, need_c;
         footprint_origin(p, cur_u, cur_v, need_r, need_c);
         cw.data = c.cur_win;
@@ -459,8 +487,8 @@ __global__ void __attribute__((amdgpu_waves_per_eu(kWavesPerEu))) __launch_bound
         if (level > 0) {
             footprint_origin(p, ref_u * 2.0f, ref_v * 2.0f, nr_lo, nc_lo);
         }
-        const bool cur_async = cur_fits && window_inside(cur, cw.r_lo, cw.c_lo, cw.rows, cw.cols);
-        const bool next_async = level > 0 && ref_fits && window_inside(p_arg.ref[level > 0 ? level - 1 : 0], nr_lo, nc_lo, rrows, rcols);
+        const bool cur_async = cur_fits && pb_window_inside(cur, cw.r_lo, cw.c_lo, cw.rows, cw.cols);
+        const bool next_async = level > 0 && ref_fits && pb_window_inside(p_arg.ref[level > 0 ? level - 1 : 0], nr_lo, nc_lo, rrows, rcols);
         // the window loads are issued FIRST (they depend on the footprints only) and fly while the node tables and
         // the lattice are built: at one wave per feature the level entry is a chain of dependent latencies
         RawQuads<kCurQuads> qc;
@@ -487,10 +515,10 @@ __global__ void __attribute__((amdgpu_waves_per_eu(kWavesPerEu))) __launch_bound
         }
         pb_sync(solo);  // B1: node tables (and this level's reference window) visible
         // ---- lattice: one bilinear per node pair ----
-        const int n_r = (int)c.slots[0], n_c = (int)c.slots[1];
+        const int n_r = __builtin_amdgcn_readfirstlane((int)c.slots[0]), n_c = __builtin_amdgcn_readfirstlane((int)c.slots[1]);  // one value per feature
         {
             const int total = n_r * n_c;
-            const uint32_t m = magic20(n_c);
+            const uint32_t m = (n_c == base_n_c) ? base_magic : magic20(n_c);
             for (int idx = opaque(b.tid); idx < total; idx += b.nt) {
                 const int r = (int)(__umul24((uint32_t)idx, m) >> 20);  // idx < 4096 and m <= 2^20: the 24-bit multiplier is exact here
                 const int cc = idx - imul(r, n_c);
@@ -660,6 +688,8 @@ __global__ void __attribute__((amdgpu_waves_per_eu(kWavesPerEu))) __launch_bound
         ref_v *= 2.0f;
         cur_u *= 2.0f;
         cur_v *= 2.0f;
+        ref_r_lo = nr_lo;  // footprint_origin of the doubled position: what the level below would compute again
+        ref_c_lo = nc_lo;
         buf ^= 1;
     }
 
