@@ -39,6 +39,29 @@ namespace ftk {
 namespace {
 
 constexpr int kChunk = 64;  // pixels per chunk = one producer wave round
+// What a chunk is.  LINEAR: pixels [64 k, 64 k + 64) of the row-major patch — every lane divides its pixel number by the patch width in
+// every chunk.  ROW chunks: kChunk / patch_cols WHOLE patch rows, the lanes behind them idle (exact zeros in the ring) — a lane's column
+// and its row within the chunk are then the same in every chunk, on every level and in every iteration.  Row chunks are taken where
+// they do not add a chunk (each one is a barrier and 64 chain adds): 21 x 21 has 7 chunks either way (3 rows = 63 pixels); 13 x 13
+// would go from 3 to 4 and 11 x 11 from 2 to 3, so they stay linear, as does the run-time geometry (patch_rows = 0 here).
+constexpr bool pb_row_chunks(int patch_rows, int patch_cols) {
+    if (patch_rows < 1 || patch_cols < 1 || patch_cols > kChunk) {
+        return false;
+    }
+    const int rows_per_chunk = kChunk / patch_cols;
+    return (patch_rows + rows_per_chunk - 1) / rows_per_chunk == (patch_rows * patch_cols + kChunk - 1) / kChunk;
+}
+// The chunk geometry of an instantiation <HR, HC> (0 / 0: run-time geometry).
+template <int HR, int HC>
+struct PbChunks {
+    static constexpr int kRows = HR > 0 && HC > 0 ? 2 * HR + 1 : 0, kCols = HR > 0 && HC > 0 ? 2 * HC + 1 : 0;
+    static constexpr bool kByRows = pb_row_chunks(kRows, kCols);
+    static constexpr int kRowsPerChunk = kByRows ? kChunk / kCols : 1;
+    static constexpr int kCount = kByRows ? (kRows + kRowsPerChunk - 1) / kRowsPerChunk : 0;  // chunks per patch (row chunks only)
+    static constexpr bool kLastRowsShort = kCount * kRowsPerChunk > kRows;                    // the last chunk has rows beyond the patch
+};
+static_assert(PbChunks<10, 10>::kByRows && PbChunks<10, 10>::kCount == 7 && !PbChunks<10, 10>::kLastRowsShort, "21 x 21: seven chunks of three rows");
+static_assert(!PbChunks<6, 6>::kByRows && !PbChunks<5, 5>::kByRows && !PbChunks<0, 0>::kByRows, "13 x 13, 11 x 11 and the run-time geometry stay linear");
 // Ring rows are kChunk + 4 floats apart: the consumer's lanes read 16 bytes each from DIFFERENT rows
 // at the same column, and a row pitch of 256 B would put all of them on the same four banks.
 // (round 5: the quad chain reads 16 bytes per lane, the four lanes of a quad 64 consecutive bytes of ONE row; a pitch of 80 floats puts
@@ -225,16 +248,64 @@ __device__ __forceinline__ void cur_tables(int lane, const KltParams &p, const P
     }
 }
 
+// Row chunks (PbChunks): what a lane keeps across chunks.  Its place, once per kernel; its column's two table entries, once per iteration
+// (behind cur_tables): they are the same in every chunk, so a chunk reads only its row entries, at the lane's row + a wave-uniform offset.
+struct PbLane {
+    int row, col;  // row within the chunk, patch column; an idle lane sits on (0, 0), which is always in the tables
+    bool in;       // the lane is a pixel of its chunk (lane < rows per chunk * patch_cols)
+};
+struct PbCols {
+    float4 c0, c1;
+};
+template <class G>
+__device__ __forceinline__ PbLane pb_lane(int lane) {
+    PbLane l = {0, 0, false};
+    if constexpr (G::kByRows) {
+        constexpr uint32_t kMagic = (1048576 + G::kCols - 1) / G::kCols;  // lane < 64: exact (magic20)
+        const int row = (int)(__umul24((uint32_t)lane, kMagic) >> 20);
+        l.in = lane < G::kRowsPerChunk * G::kCols;
+        l.row = l.in ? row : 0;
+        l.col = l.in ? lane - row * G::kCols : 0;
+    }
+    return l;
+}
+template <class G>
+__device__ __forceinline__ void pb_read_cols(const PbLane &l, const KltParams &p, const float4 *tab, PbCols &cols) {
+    if constexpr (G::kByRows) {
+        cols.c0 = tab[p.patch_rows + l.col];
+        cols.c1 = tab[2 * p.patch_rows + p.patch_cols + l.col];
+    }
+}
+
 // The five per-pixel products of one 64-pixel chunk (basic_klt.cpp:135-144); returns the lane's validity.
-__device__ __forceinline__ bool chunk_products(int lane, int chunk, const KltParams &p, const PbLds &c, const float4 *tab, const Win &cw, float (&prod)[kTerms]) {
-    const int pxi = chunk * kChunk + lane;
-    const bool in = pxi < p.P;
-    const int pp = in ? pxi : 0;
-    int prow, pcol;
-    pixel_rc(p, pp, prow, pcol);
+template <class G>
+__device__ __forceinline__ bool chunk_products(int lane, int chunk, const KltParams &p, const PbLds &c, const float4 *tab, const Win &cw, const PbLane &l,
+                                               const PbCols &cols, float (&prod)[kTerms]) {
     const int tab_total = p.patch_rows + p.patch_cols;
-    const float4 r0 = tab[prow], r1 = tab[tab_total + prow];
-    const float4 c0 = tab[p.patch_rows + pcol], c1 = tab[tab_total + p.patch_rows + pcol];
+    bool in;
+    float4 r0, r1, c0, c1;
+    if constexpr (G::kByRows) {
+        int prow = wadd(l.row, imul(chunk, G::kRowsPerChunk));  // (an unsigned sum and the 24-bit multiplier: a 32-bit LDS address, not a 64-bit multiply-add)
+        in = l.in;
+        if constexpr (G::kLastRowsShort) {  // (not at 21 x 21: 7 x 3 rows are the patch)
+            in = in && prow < p.patch_rows;
+            prow = in ? prow : 0;
+        }
+        r0 = tab[prow];
+        r1 = tab[tab_total + prow];
+        c0 = cols.c0;
+        c1 = cols.c1;
+    } else {
+        const int pxi = chunk * kChunk + lane;
+        in = pxi < p.P;
+        const int pp = in ? pxi : 0;
+        int prow, pcol;
+        pixel_rc(p, pp, prow, pcol);
+        r0 = tab[prow];
+        r1 = tab[tab_total + prow];
+        c0 = tab[p.patch_rows + pcol];
+        c1 = tab[tab_total + p.patch_rows + pcol];
+    }
     const float i_cur = node_tap(cw.data, cw.cols, r0, c0);
     const float *lat = c.lattice;
     const int rc = __float_as_int(r1.x), rm = __float_as_int(r1.y), rp = __float_as_int(r1.z);
@@ -258,9 +329,11 @@ __device__ __forceinline__ bool chunk_products(int lane, int chunk, const KltPar
 }
 
 // ... -> ring slot (the exact mode: the consumer wave adds them in pixel order).
-__device__ __forceinline__ bool produce_chunk(int lane, int chunk, const KltParams &p, const PbLds &c, const float4 *tab, const Win &cw, float *slot) {
+template <class G>
+__device__ __forceinline__ bool produce_chunk(int lane, int chunk, const KltParams &p, const PbLds &c, const float4 *tab, const Win &cw, const PbLane &l,
+                                              const PbCols &cols, float *slot) {
     float prod[kTerms];
-    const bool ok = chunk_products(lane, chunk, p, c, tab, cw, prod);
+    const bool ok = chunk_products<G>(lane, chunk, p, c, tab, cw, l, cols, prod);
 #pragma unroll
     for (int k = 0; k < kTerms; ++k) {
         slot[k * kRingRow + lane] = prod[k];
@@ -415,10 +488,13 @@ __global__ void __attribute__((amdgpu_waves_per_eu(kWavesPerEu))) __launch_bound
     const bool consumer = b.wave == 0;
     const int pw = (b.nwaves == 1) ? 0 : b.wave - 1;  // producer index
     float4 *const my_tab = c.ctab + (TREE ? b.wave : pw) * 2 * (p.patch_rows + p.patch_cols);
-    const int n_chunks = (p.P + kChunk - 1) / kChunk;
+    using G = PbChunks<HR, HC>;
+    const PbLane my_px = pb_lane<G>(b.lane);
+    const int n_chunks = G::kByRows ? G::kCount : (p.P + kChunk - 1) / kChunk;
     const int n_steps = (n_chunks + np - 1) / np;
     const int ring_mask = pb_ring_slots(b.nwaves) - 1;
-    const bool last_chunk_short = p.P - (n_chunks - 1) * kChunk <= 48;  // (a last chunk of 49 .. 64 terms is a full one: its row is zero beyond P)
+    // (a last chunk of 49 .. 64 terms is a full one: its row is zero beyond P; so is every row chunk: its rows' terms, then zeros)
+    const bool last_chunk_short = !G::kByRows && p.P - (n_chunks - 1) * kChunk <= 48;
     const float *const quad_rows = c.ring + min(b.lane >> 2, kTerms - 1) * kRingRow + 4 * (b.lane & 3);  // this lane's quad's sum, its 4 of every 16 terms
 
     // basic_klt.cpp:10,18-19 (pyramid) / :59-86 (single level)
@@ -559,14 +635,16 @@ __global__ void __attribute__((amdgpu_waves_per_eu(kWavesPerEu))) __launch_bound
             }
             uint32_t wave_valid = 0;
             float acc = 0.0f;
+            PbCols my_cols = {};  // row chunks: this lane's column entries, the same for every chunk of the iteration
             if constexpr (TREE) {
                 // throughput mode: no ring, no chain — every wave samples chunks wave, wave + W, ... into five per-lane partial sums
                 float part[kTerms] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
                 cur_tables(b.lane, p, c, my_tab, cur, cw, cur_u, cur_v, n_c);
                 __builtin_amdgcn_wave_barrier();
+                pb_read_cols<G>(my_px, p, my_tab, my_cols);
                 for (int chunk = b.wave; chunk < n_chunks; chunk += b.nwaves) {
                     float prod[kTerms];
-                    const bool ok = chunk_products(b.lane, chunk, p, c, my_tab, cw, prod);
+                    const bool ok = chunk_products<G>(b.lane, chunk, p, c, my_tab, cw, my_px, my_cols, prod);
 #pragma unroll
                     for (int k = 0; k < kTerms; ++k) {
                         part[k] += prod[k];
@@ -609,12 +687,13 @@ __global__ void __attribute__((amdgpu_waves_per_eu(kWavesPerEu))) __launch_bound
                 if (producer) {
                     cur_tables(b.lane, p, c, my_tab, cur, cw, cur_u, cur_v, n_c);
                     __builtin_amdgcn_wave_barrier();  // same-wave LDS traffic is ordered; keep the compiler from reordering across
+                    pb_read_cols<G>(my_px, p, my_tab, my_cols);
                 }
                 for (int s = 0; s < n_steps; ++s) {
                     if (producer) {
                         const int chunk = s * np + pw;
                         if (chunk < n_chunks) {
-                            const bool ok = produce_chunk(b.lane, chunk, p, c, my_tab, cw, c.ring + ((s & ring_mask) * np + pw) * kTerms * kRingRow);
+                            const bool ok = produce_chunk<G>(b.lane, chunk, p, c, my_tab, cw, my_px, my_cols, c.ring + ((s & ring_mask) * np + pw) * kTerms * kRingRow);
                             wave_valid += (uint32_t)__popcll(wave_ballot(ok));
                         }
                         if (s == n_steps - 1 && b.lane == 0) {
@@ -723,7 +802,7 @@ KltKernel pick_kernel(bool solo, bool tree) {
     } else {
         entry = solo ? klt_basic_inverse_pipelined_kernel<true, HR, HC, false> : klt_basic_inverse_pipelined_kernel<false, HR, HC, false>;
     }
-    return {entry, "pipelined", HR, solo, tree, false, false};
+    return {entry, "pipelined", HR, solo, tree, false, false, PbChunks<HR, HC>::kByRows};
 }
 }  // namespace
 

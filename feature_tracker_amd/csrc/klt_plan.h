@@ -59,6 +59,7 @@ struct KltKernel {
     int half;            // compile-time half patch size (0: run-time geometry)
     bool solo;           // one wave per feature
     bool tree, lum, spill;
+    bool row_chunks = false;  // the pipelined kernel's chunks are whole patch rows (klt_basic_kernels.hip pb_row_chunks)
 };
 KltKernel klt_pipelined_pick(const KltParams &p);
 KltKernel klt_fast_pick(int model, const KltParams &p);

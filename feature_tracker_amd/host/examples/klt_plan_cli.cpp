@@ -29,8 +29,8 @@ int main() {
         const bool stable = rc_again == rc && memcmp(&p, &again, sizeof(p)) == 0 && plan.form == plan_again.form && plan.lds_bytes == plan_again.lds_bytes &&
                             plan.grid == plan_again.grid && plan.block == plan_again.block;
         const ftk::KltKernel k = ftk::klt_pick(plan, in.model, in.method, p);
-        printf("rc=0 stable=%d form=%s lds_bytes=%zu grid=%u block=%u kernel=%d family=%s half=%d solo=%d k_tree=%d k_lum=%d k_spill=%d", stable ? 1 : 0,
-               forms[(int)plan.form], plan.lds_bytes, plan.grid, plan.block, k.entry != nullptr, k.family ? k.family : "-", k.half, k.solo, k.tree, k.lum, k.spill);
+        printf("rc=0 stable=%d form=%s lds_bytes=%zu grid=%u block=%u kernel=%d family=%s half=%d solo=%d k_tree=%d k_lum=%d k_spill=%d k_row_chunks=%d", stable ? 1 : 0,
+               forms[(int)plan.form], plan.lds_bytes, plan.grid, plan.block, k.entry != nullptr, k.family ? k.family : "-", k.half, k.solo, k.tree, k.lum, k.spill, k.row_chunks);
         printf(" waves_per_feature=%d features_per_group=%d group_lds_stride=%d px_floats=%d terms_floats=%d a0_floats=%d lssd_chunked=%d quad_chain=%d"
                " pb_enabled=%d fk_enabled=%d spill=%d tree=%d long_tail=%d spill_stride_floats=%u rwin_rows=%d rwin_cols=%d cwin_rows=%d cwin_cols=%d P=%d\n",
                p.waves_per_feature, p.features_per_group, p.group_lds_stride, p.px_floats, p.terms_floats, p.a0_floats, p.lssd_chunked, p.quad_chain, p.pb_enabled,
