@@ -53,6 +53,9 @@ FTK_TRANSFORMER_MAX_HEAD_DIM = 128
 # the adaptive pass (include/ftk.h)
 FTK_LIGHTGLUE_MAX_LAYERS = 64
 FTK_LIGHTGLUE_STATE_WORDS = 4  # live0, live1, stopped, stop_layer
+# the landmark table (include/ftk.h)
+FTK_MATCH_TABLE_MAX_SLOTS = 4096
+FTK_MATCH_TABLE_MAX_DIM = 1024
 # SepConvGru (include/ftk.h): the supported sizes and the packed weight layout
 FTK_SEP_CONV_GRU_MAX_PARTS = 3
 FTK_SEP_CONV_GRU_MAX_H_CHANNELS = 1024
@@ -96,6 +99,7 @@ EXPORTS = [
     "ftk_transformer_layer_workspace_bytes", "ftk_attention_device", "ftk_linear_device", "ftk_transformer_layer_device",
     "ftk_lightglue_adaptive_workspace_bytes", "ftk_transformer_layer_adaptive_device", "ftk_lightglue_confidence_device",
     "ftk_lightglue_adapt_step_device", "ftk_lightglue_finish_device",
+    "ftk_match_table_workspace_bytes", "ftk_match_table_query_device", "ftk_match_table_update_device",
 ]
 UNIQUE_ID_BYTES = 128
 
@@ -294,6 +298,9 @@ def lib() -> C.CDLL:
     l.ftk_lightglue_confidence_device.argtypes = [vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     l.ftk_lightglue_adapt_step_device.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, f32, f32, f32, i32] + [vp] * 15
     l.ftk_lightglue_finish_device.argtypes = [vp, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp]
+    l.ftk_match_table_workspace_bytes.argtypes = [i32, i32, i32, i64p]
+    l.ftk_match_table_query_device.argtypes = [vp, vp, i32, i32] + [vp] * 7
+    l.ftk_match_table_update_device.argtypes = [vp, vp, i32, i32] + [vp] * 15 + [i32, vp, i32, vp, vp]
     _lib = l
     return l
 
@@ -408,6 +415,12 @@ def lightglue_adaptive_workspace_bytes(rows0: int, rows1: int, dim: int, heads: 
     up16 = lambda v: (v + 15) & ~15  # noqa: E731
     return (up16(transformer_layer_workspace_bytes(m, n, d, heads)) + up16(match_assignment_workspace_bytes(m, n, d, True)) + up16(4 * (d + 1) * d)
             + up16(4 * (d + 1)) + 2 * up16(4 * m) + up16(4 * n) + up16(m))
+
+
+def match_table_workspace_bytes(n_slots: int, rows_cur: int, dim: int) -> int:
+    """Bytes of workspace ftk_match_table_update_device needs, the value ftk_match_table_workspace_bytes returns (pure Python;
+    csrc/match_table_plan.h): the current rows' slots, int32 [rows_cur], rounded up to 16 bytes."""
+    return (4 * int(rows_cur) + 15) & ~15
 
 
 def transformer_layer_weight_offsets(dim: int):

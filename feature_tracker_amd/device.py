@@ -488,6 +488,7 @@ from ._device_epipolar import epipolar_ransac_device  # noqa: E402,F401  (two-vi
 from ._device_two_view import two_view_ransac_device  # noqa: E402,F401  (the same with a choice of model)
 from ._device_keypoint_decode import keypoint_decode_device  # noqa: E402,F401  (the keypoint decoder; its own file, see there)
 from ._device_match_assignment import match_assignment_device  # noqa: E402,F401  (LightGlue's assignment head; its own file, see there)
+from ._device_match_table import match_table_query_device, match_table_update_device  # noqa: E402,F401  (MatchVideoTracker's landmark table; its own file, see there)
 from ._device_transformer import attention_device, linear_device, transformer_layer_device  # noqa: E402,F401  (LightGlue's transformer layer; likewise)
 from ._device_lightglue_adaptive import (lightglue_adapt_step_device, lightglue_confidence_device, lightglue_finish_device,  # noqa: E402,F401
                                          transformer_layer_adaptive_device)  # (LightGlue's adaptive depth and width; likewise)

@@ -480,6 +480,53 @@ int ftk_lightglue_finish_device(ftk_context *ctx, void *stream, const float *d_d
                                 const int32_t *d_ind0, const int32_t *d_ind1, float min_score, void *d_workspace, float *d_scores,
                                 int32_t *d_match_index, uint8_t *d_status, int32_t *d_layers0, int32_t *d_layers1);
 
+/* ---- the landmark table (MatchVideoTracker) -------------------------------------- */
+
+/*
+ * A fixed-capacity table of landmarks in device memory for tracking with learned features over a frame sequence.  It extends the step at
+ * nn_feature_matcher.cpp:187-215 (the mutual-best matches of one pair) to a sequence: the matcher is asked about the TABLE, the last
+ * seen position and descriptor of every live track, not about the previous frame's detections, so a landmark hidden for a few frames
+ * is found again under its identity.  n_slots = 1 .. FTK_MATCH_TABLE_MAX_SLOTS slots that never move (the matchers' row limit):
+ * d_ids int64 [n] (-1 = empty), d_points / d_prev_points float32 [n][2] (8-byte aligned), d_descriptors float32 [n][dim], dim = 1 ..
+ * FTK_MATCH_TABLE_MAX_DIM, d_status uint8 [n], d_age int32 [n] (frames matched since admission), d_lost int32 [n] (frames since the slot
+ * was last matched), d_n_live int32 [1], d_next_id int64 [1].
+ *
+ * ftk_match_table_query_device — the table as a matcher's reference set.  The live slots (id >= 0) in ASCENDING slot order (a scan, not
+ * an atomic append) become rows 0 .. nq - 1 of d_q_uv [n][2] (8-byte aligned), d_q_desc [n][dim] and d_q_slot int32 [n] (the row's
+ * slot); d_q_count [1] = nq.  Rows at or behind nq are +0 in d_q_uv and d_q_desc and -1 in d_q_slot.  The table is not written.
+ *
+ * ftk_match_table_update_device — one frame's results into the table.  d_q_slot / d_q_count as the query wrote them; d_match_index
+ * int32 [n] and d_match_status uint8 [n] as ftk_nn_match_scores_device or ftk_lightglue_finish_device wrote them for the query rows
+ * against the current set d_cur_uv [rows_cur][2] (8-byte aligned), d_cur_desc [rows_cur][dim], rows_cur = 1 .. FTK_MATCH_TABLE_MAX_SLOTS;
+ * d_cur_count int32 [1] or NULL (all rows); max_lost >= 0.  With nq = clamp(q_count, 0, n) and nk = clamp(cur_count, 0, rows_cur):
+ *   1. row r < nq NAMES j = match_index[r] iff 0 <= j < nk; it is a HIT iff it names j, match_status[r] == FTK_TRACKED and no lower hit
+ *      row names the same j (an integer atomicMin per j: a pure function of the inputs).  A current row named by any row is CLAIMED,
+ *      hit or not: a match the geometric filter rejected does not come back as a new track on the same keypoint.
+ *   2. for r < nq and s = q_slot[r], a slot live before the call: a hit gets prev_points[s] <- points[s], points[s] <- cur_uv[j],
+ *      descriptors[s] <- cur_desc[j] (replaced, not averaged), age += 1, lost <- 0, status FTK_TRACKED; any other gets lost += 1, status
+ *      FTK_LARGE_RESIDUAL and, if lost > max_lost, id <- -1 (its other fields stay).  A slot that was empty before the call is not touched.
+ *   3. the unclaimed current rows j < nk in ascending j and the empty slots after step 2 (the ones just retired included) in ascending
+ *      slot order: for rank r < min(#unclaimed, #empty) the r-th row goes to the r-th slot with id next_id + r, points = prev_points =
+ *      cur_uv[j], its descriptor, age 0, lost 0, status FTK_NOT_TRACKED; then next_id grows by the number admitted and n_live is the
+ *      live count.
+ * d_cur_slot int32 [rows_cur], or NULL: the slot each current row now belongs to (hit or admitted), else -1.
+ * d_workspace: ftk_match_table_workspace_bytes(n_slots, rows_cur, dim) bytes, 16-byte aligned, no initialisation needed.  No argument may
+ * alias another: equal pointers are refused.  Everything is refused (FTK_E_INVALID_ARGUMENT) before any launch.  2 launches each of
+ * fixed shape on `stream` (one workgroup of FTK_TRACK_TABLE_BLOCK threads scans up to four flags per thread, then one wave per
+ * descriptor row moves it, 16 bytes per lane when dim % 4 == 0 and the descriptor bases are 16-byte aligned); no host read, no
+ * synchronisation, no allocation: capturable.  Integer logic and copies only.
+ */
+#define FTK_MATCH_TABLE_MAX_SLOTS 4096
+#define FTK_MATCH_TABLE_MAX_DIM 1024
+int ftk_match_table_workspace_bytes(int32_t n_slots, int32_t rows_cur, int32_t dim, int64_t *bytes);
+int ftk_match_table_query_device(ftk_context *ctx, void *stream, int32_t n_slots, int32_t dim, const int64_t *d_ids, const float *d_points,
+                                 const float *d_descriptors, float *d_q_uv, float *d_q_desc, int32_t *d_q_slot, int32_t *d_q_count);
+int ftk_match_table_update_device(ftk_context *ctx, void *stream, int32_t n_slots, int32_t dim, int64_t *d_ids, float *d_points, float *d_prev_points,
+                                  float *d_descriptors, uint8_t *d_status, int32_t *d_age, int32_t *d_lost, int32_t *d_n_live, int64_t *d_next_id,
+                                  const int32_t *d_q_slot, const int32_t *d_q_count, const int32_t *d_match_index, const uint8_t *d_match_status,
+                                  const float *d_cur_uv, const float *d_cur_desc, int32_t rows_cur, const int32_t *d_cur_count, int32_t max_lost,
+                                  void *d_workspace, int32_t *d_cur_slot);
+
 /* ---- diagnostics ---------------------------------------------------------------------------- */
 
 /*
