@@ -22,20 +22,41 @@
 //   4. cosine_recheck_kernel  8 lanes per ref row: exact d of every candidate in Eigen's order,
 //                             minimum with the lowest index on ties, strict threshold test, write.
 //
-// |d~ - d| <= eps for every "regular" pair (both norms in [2^-40, 2^40]): fp16 rounding of unit
-// vectors perturbs the cosine by at most 2^-10 * sum|x_k y_k| <= 2^-10 (Cauchy-Schwarz) plus
-// 256 * 2^-24 of subnormal fp16 components, fp32 accumulation adds < 4e-5, the exact side's own
-// rounding < 3e-5 — so eps < 5.5e-4 on the distance and margin = 2 * eps bounds the set {j : d(i, j)
-// can equal min_j d(i, j)}.  kMargin = 1.5e-3 leaves > 25 % slack.  Descriptors outside the regular
-// range (zero / non-finite / extreme norm) never enter the approximation: an irregular ref row, a
-// row whose candidate list overflowed, or more irregular cur rows than the side list holds sends
-// that row through the exact scan over every j in step 4 (same code, longer list).
+// The error budget, for every accepted width (1 <= dim <= 4096).  The lists keep every j whose approximate cosine lies
+// within 2 * margin of the row's approximate maximum (margin on the distance), so the deciding pair is listed if
+// |c~ - c| <= margin for every "regular" pair (both norms in [2^-40, 2^40]), c = 1 - 2 d being the cosine of the distance
+// as step 4 computes it, i.e. eps = |d~ - d| <= margin / 2.  With u = 2^-24, a = x / norm(x), b = y / norm(y) for the
+// computed norms (both sides divide by the same ones; |a|, |b| <= 1 + dn, dn = (dim / 16 + 5) u):
+//   fp16 copies    a component is off by r |a_k| at most (r = 2^-11 + 2^-22: the fp32 scaling, then the rounding) or,
+//                  below 2^-14, by s = 2^-25 + 2^-37 (half a subnormal step: the kernels run with fp16 denormals on, the
+//                  compiler's default, and CDNA3 / 4 matrix cores take subnormal fp16 inputs as they are); by Cauchy-Schwarz a copy is off by h = r (1 + dn) + s sqrt(dim) in length and the
+//                  cosine by 2 h (1 + dn) + h^2 — the subnormal part is 2 s sqrt(dim), NOT dim * 2^-24;
+//   accumulation   the MFMA's products are exact; how it rounds its sums is not specified, so every addend of every
+//                  instruction (16 products, the accumulator) is charged one unit in the last place of the running sum,
+//                  as if truncated: (17 / 16) dim_pad 2^-23 (1 + dn + h)^2;
+//   exact side     Eigen's order sends a product through at most dim / 8 + 7 roundings; two divisions, the final
+//                  subtraction: (dim / 8 + 10) u (1 + dn)^2;
+//   index bits     (single walk only, below) 31 * 2^-23.
+//                     dim    fp16 copies  accumulation  exact side     sum       margin   to spare
+//                     256     9.78e-4      3.2e-5        2.5e-6      1.017e-3   1.5e-3     32 %   (with the index bits)
+//                    1024     9.79e-4      1.30e-4       8.2e-6      1.117e-3   1.634e-3   32 %
+//                    4096     9.81e-4      5.19e-4       3.1e-5      1.532e-3   2.172e-3   29 %
+// The first term does not grow, the other two do, linearly: against a CONSTANT 1.5e-3 the sum keeps a quarter to spare up
+// to dim 1024, stays below it up to 3840 (0.2 % to spare) and exceeds it at 4096 (by 2 %) — under this worst-case model of
+// the matrix unit, which round-to-nearest sums would halve.  So the margin is a plan field (CosinePlan::margin,
+// match_plan.cpp): kCosineMargin = 1.5e-3 up to dim_pad 256, kCosineMarginPerK = 1.75e-7 more per component beyond, which
+// keeps more than a quarter of it to spare at every width (tests/test_cosine_widths_cpu.py evaluates the sum at every dim
+// against the plan's margin).  The chunked pair and the recheck read it from CosineParams; the single-walk kernel below
+// serves dim_pad <= 256 only and compiles the constant in.
+// Descriptors outside the regular range (zero / non-finite / extreme norm) never enter the approximation: an irregular ref
+// row, a row whose candidate list overflowed, or more irregular cur rows than the side list holds sends that row through
+// the exact scan over every j in step 4 (same code, longer list).
 //
 // For dim <= 256 steps 2 and 3 are ONE walk over the candidates (cosine_gemm_rr_kernel): a running row maximum replaces the known one, which only makes the list a
 // superset; entries carry their approximate score and step 4 keeps those within 2 * margin of the final
 // maximum.  The rr kernel also writes the accumulator element's index into the 5 low mantissa bits of the
-// score (so a maximum names its own element): a perturbation of at most 31 ulp < 2e-6 of the cosine, i.e.
-// 1e-6 on the distance — eps stays below 5.6e-4 and 2 * eps below kMargin with > 25 % to spare.
+// score (so a maximum names its own element): a perturbation of at most 31 ulp <= 31 * 2^-23 = 3.7e-6 of the cosine
+// (a score can round to just above 1) — the "index bits" term of the budget above, inside the 32 % to spare at 256.
 #include <limits.h>
 #include <stdlib.h>
 
@@ -50,7 +71,8 @@ typedef float float16v __attribute__((ext_vector_type(16)));
 constexpr int kTile = kCosineTile;
 constexpr int kChunkK = 64;    // K staged per LDS chunk
 constexpr int kPitch = kChunkK + 8;  // halfs; +16 B keeps the 128-bit fragment reads off one bank group
-constexpr float kMargin = 1.5e-3f;
+constexpr float kMargin = kCosineMargin;  // the register-stationary kernel's (dim_pad <= 256: the plan's margin IS this constant, launch_rr checks);
+                                          // the chunked pair and the recheck read CosineParams::margin
 constexpr float kNormLo = 9.094947017729282e-13f;  // 2^-40
 constexpr float kNormHi = 1.099511627776e12f;      // 2^40
 
@@ -318,7 +340,7 @@ __global__ void __launch_bounds__(256) cosine_gemm_kernel(const CosineParams p) 
         thr[nt] = pos_inf;
         if (kCollect && live[nt]) {
             const uint32_t key = p.row_max[i];
-            thr[nt] = (key == 0u) ? pos_inf : order_value(key) - 2.0f * kMargin;  // cosine domain: d = 0.5 - 0.5 c
+            thr[nt] = (key == 0u) ? pos_inf : order_value(key) - 2.0f * p.margin;  // cosine domain: d = 0.5 - 0.5 c
         }
     }
 
@@ -942,7 +964,7 @@ __global__ void __launch_bounds__(256) cosine_recheck_kernel(const CosineParams 
     const bool scan_all = p.ref_irregular[row] != 0 || cnt > (uint32_t)kCosineCandCap || n_irr > (uint32_t)kCosineIrregularCap;
     // single-walk lists were cut against the running maximum: keep what the final maximum admits
     const uint32_t max_key = p.cand_score ? p.row_max[row] : 0u;
-    const float admit = max_key ? order_value(max_key) - 2.0f * kMargin : __uint_as_float(0xFF800000u);
+    const float admit = max_key ? order_value(max_key) - 2.0f * p.margin : __uint_as_float(0xFF800000u);
     const float pu = nearby ? p.pred_uv[2 * row] : 0.0f, pv = nearby ? p.pred_uv[2 * row + 1] : 0.0f;
     float best_d = __uint_as_float(0x7F800000u);
     int best_j = -1;
@@ -1140,6 +1162,9 @@ __global__ void __launch_bounds__(256) cosine_match_small_kernel(const CosinePar
 
 template <int kKSteps>
 hipError_t launch_rr(const CosinePlan &plan, const CosineParams &p, hipStream_t stream) {
+    if (p.margin != kMargin) {
+        return hipErrorInvalidValue;  // the kernel cuts against the compiled-in margin
+    }
     void (*kern)(const CosineParams) = p.pred_uv ? cosine_gemm_rr_kernel<kKSteps, true> : cosine_gemm_rr_kernel<kKSteps, false>;
     const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds);
     if (e != hipSuccess) {

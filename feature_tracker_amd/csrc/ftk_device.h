@@ -199,6 +199,11 @@ constexpr int kRrRows = 512;      // ref rows per workgroup of the register-stat
 constexpr int kCosineSmallCurNearby = 2048;  // 300 x 300 x 256 NearbyMatch 48.7 -> 10.7 us, 1 000 x 1 000 47.4 -> 21.3, 2 000 x 2 000 54.6 -> 40.3 (3 000 candidates: even)
 constexpr int kCosineSmallCurForce = 384;    // ForceMatch computes every pair exactly: 100 x 100 x 256 35.4 -> 14.8 us, 300 x 300 40.3 -> 32.1, 600 x 600 41.6 -> 59.2 (not taken)
 constexpr int kCosineSmallRefMax = 4096;
+// Shortlist margin on the distance (band 2 * margin on the approximate cosine): the error budget in the header of
+// float_matcher_kernels.hip.  Constant up to dim_pad 256 (the register-stationary kernel compiles it in); cosine_plan lets it grow
+// with dim_pad above that, where the accumulation terms of the budget would otherwise use up the slack.
+constexpr float kCosineMargin = 1.5e-3f;
+constexpr float kCosineMarginPerK = 1.75e-7f;  // added per descriptor component beyond 256
 struct CosineParams {
     const float *ref, *cur;   // [n][dim] fp32 descriptors, row-major
     const float *pred_uv;     // null => ForceMatch
@@ -223,6 +228,7 @@ struct CosineParams {
                               // n_cur_pad % 64 == 0, `splits` workgroups share the cur tiles evenly); 0: the chunked kernel
     int32_t splits;
     float max_distance, max_col, max_row;
+    float margin;             // CosinePlan::margin
 };
 size_t cosine_rr_lds_bytes(int dim_pad);
 struct CosinePlan;

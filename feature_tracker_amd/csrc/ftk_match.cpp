@@ -202,7 +202,7 @@ int ftk_cosine_match_device(ftk_context *ctx, const float *d_ref_desc, int32_t n
                                  (uint32_t *)at(plan.cand_count), (int32_t *)at(plan.cand), plan.ref_stationary ? (float *)at(plan.cand_score) : nullptr,
                                  (uint32_t *)at(plan.irregular_count), (int32_t *)at(plan.irregular_list), at(plan.row_max), plan.clear_end - plan.row_max,
                                  n_ref, n_cur, dim, plan.n_ref_pad, plan.n_cur_pad, plan.dim_pad, plan.tiles_per_split, plan.ref_stationary, plan.splits,
-                                 max_distance, (float)max_col_distance, (float)max_row_distance};
+                                 max_distance, (float)max_col_distance, (float)max_row_distance, plan.margin};
     FTK_HIP(ctx, ftk::cosine_match_launch(plan, p, ctx->stream));
     return FTK_OK;
 }

@@ -94,6 +94,7 @@ CosinePlan cosine_plan(const CosinePlanInput &in) {
     CosinePlan pl = {};
     pl.prep_grid = pl.box_grid = pl.recheck_grid = dim3(0);
     pl.dim_pad = (int32_t)align_up((size_t)in.dim, 64);
+    pl.margin = pl.dim_pad <= 256 ? kCosineMargin : kCosineMargin + kCosineMarginPerK * (float)(pl.dim_pad - 256);
     // dim <= 256 (SuperPoint, DISK): the ref fragments stay in registers for the whole walk over cur (cosine_gemm_rr_kernel,
     // kRrRows ref rows per workgroup).  Longer descriptors, or FTK_COSINE_CHUNKED=1, use the chunked kernel.
     const bool rs = pl.dim_pad <= 256 && in.chunked != 1;

@@ -44,6 +44,9 @@ enum class CosineForm { Small, RegisterStationary, Chunked };
 struct CosinePlan {
     CosineForm form;
     int32_t dim_pad, n_ref_pad, n_cur_pad, splits, tiles_per_split;
+    // shortlist margin on the distance: kCosineMargin up to dim_pad 256, + kCosineMarginPerK per component beyond (the error budget in
+    // float_matcher_kernels.hip, which grows with the width); both contraction forms and the recheck's admission cut use it
+    float margin;
     // workspace: byte offsets of the regions (256-byte aligned); [row_max, clear_end) is zeroed by one memset per call
     size_t ref_h, cur_h, ref_norm, cur_norm, cur_bias, cur_info, tile_box, ref_irregular, row_max, cand_count, irregular_count, clear_end,
         cand, cand_score, irregular_list, ws_bytes;

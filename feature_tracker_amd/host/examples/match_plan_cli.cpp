@@ -49,6 +49,7 @@ int main() {
                    " irregular_count=%zu clear_end=%zu cand=%zu cand_score=%zu irregular_list=%zu ws_bytes=%zu",
                    p.ref_h, p.cur_h, p.ref_norm, p.cur_norm, p.cur_bias, p.cur_info, p.tile_box, p.ref_irregular, p.row_max, p.cand_count, p.irregular_count,
                    p.clear_end, p.cand, p.cand_score, p.irregular_list, p.ws_bytes);
+            printf(" margin=%.9g", (double)p.margin);
             grid("prep_grid", p.prep_grid), grid("box_grid", p.box_grid), grid("grid", p.grid), grid("block", p.block), grid("recheck_grid", p.recheck_grid);
         } else if (kind == "direct") {
             ftk::DirectPlanInput in;

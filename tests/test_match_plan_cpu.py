@@ -181,6 +181,15 @@ def region_bytes(p):
                 irregular_list=4 * 64)
 
 
+COSINE_MARGIN = 0.00150000001  # 1.5e-3f as the CLI prints it (%.9g)
+
+
+def cosine_margin(dim_pad):
+    """kCosineMargin + kCosineMarginPerK * (dim_pad - 256) in fp32, as the CLI prints it."""
+    import numpy as np
+    return float("%.9g" % (np.float32(1.5e-3) + np.float32(1.75e-7) * np.float32(dim_pad - 256)))
+
+
 def test_cosine_plan_properties():
     cases = cosine_cases()
     seen = set()
@@ -212,6 +221,9 @@ def test_cosine_plan_properties():
         assert p["cand_count"] == p["row_max"] + cdiv(sizes["row_max"], 256) * 256 and p["irregular_count"] == p["cand_count"] + cdiv(sizes["cand_count"], 256) * 256, what
         assert p["clear_end"] == p["irregular_count"] + 256, what
         assert p["use_tile_box"] == int(c["nearby"] == 1 and p["n_cur_pad"] // 64 >= 32), what
+        # the shortlist margin: today's constant wherever the register-stationary kernel (which compiles it in) can run, growing with
+        # dim_pad beyond, whatever the form, the sizes and the switches
+        assert float(p["margin"]) == (COSINE_MARGIN if p["dim_pad"] <= 256 else cosine_margin(p["dim_pad"])), what
         if p["form"] == "small":
             assert p["grid"] == (cdiv(n_ref, 4), 1) and p["block"] == (256, 1) and p["lds"] == 0, what
             assert p["prep_grid"][0] == p["box_grid"][0] == p["recheck_grid"][0] == 0, what
@@ -261,6 +273,9 @@ def test_cosine_pinned():
     expect(p[11], form="register_stationary", dim_pad=128, packet_prep=0)
     expect(p[12], form="register_stationary", ref_stationary=1, dim_pad=256, splits=16, tiles_per_split=2, grid=(64, 1), block=(512, 1), lds=80032)
     expect(p[13], form="chunked", ref_stationary=0, dim_pad=320, splits=16, tiles_per_split=1, grid=(16, 16), block=(256, 1), lds=0)
+    # the margin: 1.5e-3 up to dim_pad 256 (also under the chunked pair, case 8), 1.75e-7 more per component beyond
+    assert [q["margin"] for k, q in enumerate(p) if k not in (9, 13)] == ["0.00150000001"] * 12
+    assert abs(float(p[9]["margin"]) - (1.5e-3 + 256 * 1.75e-7)) < 1e-9 and abs(float(p[13]["margin"]) - (1.5e-3 + 64 * 1.75e-7)) < 1e-9
 
 
 # ---- direct method ----
