@@ -84,7 +84,6 @@ struct KltParams {
     // pipelined Basic-KLT inverse kernel (klt_basic_kernels.hip); pb_enabled = 0 selects the generic kernel
     int32_t pb_enabled;
     int32_t pb_rwin_rows, pb_rwin_cols;  // reference window incl. the rounding row / column: 2h+5 (cols padded to 4)
-    uint32_t pb_magic_rwc, pb_magic_rwq;
     int32_t pb_cap_r, pb_cap_c;          // lattice node capacity per axis: len + 2 + provable maximum of extras
     int32_t fk_enabled;                  // the one-wave `fast` kernels (klt_fast_kernels.hip); 0 selects the generic kernel
     // Patches whose per-pixel arrays exceed a workgroup's 160 KB of LDS (the reference has no patch-size ceiling: optical_flow.h:24-25
@@ -98,10 +97,44 @@ struct KltParams {
                                          // by per-lane partials + a cross-lane butterfly (ftk_set_reduction_mode; reported, never the default)
     int32_t scale_recip;                 // 1: n_levels - 1 <= 30, so the coarsest level's 2^-(n_levels - 1) is a normal float and a kernel may multiply by
                                          // it where it would divide by 2^(n_levels - 1) (klt_basic_kernels.hip; set by klt_plan_call)
+    int32_t pb_rwin_pitch, pb_cwin_pitch;  // the pipelined kernel keeps its windows as plain BYTES: row pitch in bytes (klt_byte_pitch), a power of two
 };
 
 // ceil(2^32 / d): row = umulhi(index, magic)
 __host__ __device__ constexpr uint32_t klt_div_magic(int32_t d) { return d <= 1 ? 0u : (uint32_t)(((1ull << 32) + (uint64_t)d - 1) / (uint64_t)d); }
+
+// Byte windows of the pipelined Basic kernel (klt_basic_kernels.hip).  Byte (r, c) of a window is img[clamp(r_lo + r)][clamp(c_lo + c)];
+// the 2x2 neighbourhood of element (r, c), c < cols, is bytes c, c + 1 of rows r, r + 1, so a row holds cols + 1 bytes that are read.
+// The pitch is that rounded up to a multiple of 8 (a row is staged in 8-byte units) and then to a power of two (unit -> row and
+// position are a shift and a mask).  The windows live in the regions carved for 16-bit pairs, 2 * pad4(rows * cols) bytes.  The power of
+// two always fits them: cols is a multiple of 4 and >= 8, and with 2^k <= cols < 2^(k + 1) the pitch is at most 2^(k + 1) <= 2 * cols.
+// (klt_byte_windows_ok states it as a check: a static_assert of the compile-time geometries, a condition of the form in the plan.)
+__host__ __device__ constexpr int32_t klt_byte_window_room(int32_t rows, int32_t cols) { return 2 * ((rows * cols + 3) & ~3); }
+__host__ __device__ constexpr int32_t klt_byte_pitch(int32_t cols) {
+    const int32_t pitch8 = (cols + 1 + 7) & ~7;
+    int32_t pow2 = 8;
+    while (pow2 < pitch8) {
+        pow2 *= 2;
+    }
+    return pow2;
+}
+// Image byte offset of 8-byte unit idx of a window relative to the window's origin: row idx >> shift, position idx & mask, with
+// shift = log2(pitch / 8).  The one place that says where a unit comes from (klt_common.h issue_octets; klt_plan_cli prints it).
+__host__ __device__ constexpr uint32_t klt_byte_unit_offset(uint32_t idx, int shift, uint32_t im_cols) {
+    return (idx >> shift) * im_cols + 8u * (idx & ((1u << shift) - 1u));
+}
+__host__ __device__ constexpr int klt_byte_units_shift(int32_t pitch) {
+    int shift = 0;
+    while ((8 << shift) < pitch) {
+        ++shift;
+    }
+    return shift;
+}
+// The staging rule of a byte window: every 8-byte unit of every row — bytes [c_lo, c_lo + pitch) of image rows [r_lo, r_lo + wrows) —
+// lies inside the level's rows * cols bytes AND inside its own image row.  (r_lo <= rows - wrows has no sum that could overflow.)
+__host__ __device__ constexpr bool klt_byte_window_inside(int32_t im_rows, int32_t im_cols, int32_t r_lo, int32_t c_lo, int32_t wrows, int32_t pitch) {
+    return r_lo >= 0 && c_lo >= 0 && r_lo <= im_rows - wrows && c_lo <= im_cols - pitch;
+}
 
 // Everything in KltParams that follows from (half_rows, half_cols) ALONE.  One definition for the host (klt_plan) and
 // for the kernels' compile-time specialisations (klt_basic_kernels.hip instantiates the pipelined kernel for the common patch
@@ -132,8 +165,8 @@ __host__ __device__ constexpr void klt_fill_geometry(KltParams &p) {
     p.magic_cwq = klt_div_magic(p.cwin_cols / 4);
     p.pb_rwin_rows = p.patch_rows + 4;
     p.pb_rwin_cols = (p.patch_cols + 4 + 3) & ~3;
-    p.pb_magic_rwc = klt_div_magic(p.pb_rwin_cols);
-    p.pb_magic_rwq = klt_div_magic(p.pb_rwin_cols / 4);
+    p.pb_rwin_pitch = klt_byte_pitch(p.pb_rwin_cols);
+    p.pb_cwin_pitch = klt_byte_pitch(p.cwin_cols);
     // lattice extras per axis: a unit step crosses at most log2(len + 2) + 3 binade boundaries, two nodes each
     int bits_r = 0, bits_c = 0;
     while ((1 << bits_r) < p.patch_rows + 2) {
@@ -144,6 +177,14 @@ __host__ __device__ constexpr void klt_fill_geometry(KltParams &p) {
     }
     p.pb_cap_r = p.patch_rows + 2 + 2 * (bits_r + 3);
     p.pb_cap_c = p.patch_cols + 2 + 2 * (bits_c + 3);
+}
+
+// What the pipelined kernel needs of its byte windows: a power-of-two pitch that covers cols + 1 bytes, inside the carved region.
+__host__ __device__ constexpr bool klt_byte_window_ok(int32_t rows, int32_t cols, int32_t pitch) {
+    return pitch >= cols + 1 && (pitch & (pitch - 1)) == 0 && pitch % 8 == 0 && rows * pitch <= klt_byte_window_room(rows, cols);
+}
+__host__ __device__ constexpr bool klt_byte_windows_ok(const KltParams &p) {
+    return klt_byte_window_ok(p.pb_rwin_rows, p.pb_rwin_cols, p.pb_rwin_pitch) && klt_byte_window_ok(p.cwin_rows, p.cwin_cols, p.pb_cwin_pitch);
 }
 
 // (the trackers' launch plan, per-form LDS sizes, kernel pickers and klt_launch: klt_plan.h)

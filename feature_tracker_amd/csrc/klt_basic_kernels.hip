@@ -17,12 +17,19 @@
 //     5 * len^2.  Per patch row / column an index triple (centre, minus, plus) says which nodes
 //     its taps use; gx, gy and i_ref are read back from the lattice each iteration.
 //
-//  2. Windows prefetched.  At level entry the global loads of the current-image window and of the
-//     NEXT level's reference window are issued into registers, the node tables and the lattice of
-//     this level are built meanwhile, and only then are the loads consumed (LDS stores).  The
-//     reference window is one row / column larger than the generic kernel's so that a valid tap
-//     is always covered (a coordinate sum may round up to the next integer), hence no
-//     global-memory fallback sampler exists here.
+//  2. Windows prefetched, as plain bytes.  At level entry the global loads of the current-image window
+//     and of the NEXT level's reference window are issued into registers, the node tables and the
+//     lattice of this level are built meanwhile, and only then are the loads consumed (LDS stores).
+//     A window row is `pitch` bytes (a power of two, ftk_device.h klt_byte_pitch: 32 at 21x21), staged
+//     in 8-byte units that go to LDS as they came from memory — unit -> (row, position) is a shift
+//     and a mask, one unit per thread and window at 21x21 on two waves — and a tap reads the two
+//     aligned dwords around its pixel in each of its two rows and shifts them into place (node_tap:
+//     as many LDS reads as with pairs; four single-byte reads measured 6 % slower than pairs, and a
+//     16-bit read at an odd address 22 %, docs/LAB_NOTES.md).  The generic and the one-wave kernels
+//     keep 16-bit pixel pairs (klt_common.h Win), whose staging is four times the work.  The
+//     reference window is one row / column larger than the generic kernel's so that a valid tap is
+//     always covered (a coordinate sum may round up to the next integer), hence no global-memory
+//     fallback sampler exists here.
 //
 //  3. Producer / consumer waves.  Wave 0 runs the five exact-order chains (one lane each) over
 //     64-pixel chunks while the other wave(s) compute the next chunk's per-pixel products; chunks
@@ -68,8 +75,14 @@ static_assert(!PbChunks<6, 6>::kByRows && !PbChunks<5, 5>::kByRows && !PbChunks<
 // the rows of the two quads of an 8-lane group on the two halves of the banks.  Its quads follow klt_common.h chain_quads_left.)
 constexpr int kRingRow = kChunk + 16;
 constexpr int kTerms = 5;   // 0 H00, 1 H11, 2 H01, 3 -fx*ft, 4 -fy*ft (basic_klt.cpp:139-144)
-constexpr int kCurQuads = 4;  // 8-byte window loads a thread may hold in flight (current window)
-constexpr int kRefQuads = 3;  // ... (next level's reference window)
+// 8-byte window loads a thread holds in flight per window: what the instantiation's windows need on its fewest threads (one wave
+// solo, two otherwise).  The run-time geometry (rows = 0) holds kRunTimeRefOctets / kRunTimeCurOctets, the slot counts of the pair
+// staging this replaced: a unit carries twice the pixels of a quad and a pitch is less than twice the columns, so every window
+// those covered is covered (up to 33 x 33 on two waves); a window with more units is staged after the lattice instead.
+constexpr int kRunTimeRefOctets = 3, kRunTimeCurOctets = 4;
+constexpr int pb_octets(int rows, int pitch, bool solo, int run_time) {
+    return rows > 0 ? (rows * (pitch / 8) + (solo ? 64 : 128) - 1) / (solo ? 64 : 128) : run_time;
+}
 
 __host__ __device__ inline int pb_pad4(int x) { return (x + 3) & ~3; }
 __host__ __device__ inline int pb_producers(int waves) { return waves > 1 ? waves - 1 : 1; }
@@ -87,9 +100,11 @@ struct PbLds {
     float *lattice;           // [n_r][n_c] reference bilinear values
     float *sol;               // 4 floats: published solution
     uint32_t *slots;          // 16: node counts (0, 1), valid-pixel counts by iteration parity (4 + 4 * parity + wave)
-    uint16_t *ref_win;        // two reference windows (this level, next level), ref_win_stride apart
+    // Byte windows (klt_common.h "Byte windows"), rows pb_rwin_pitch / pb_cwin_pitch bytes apart, inside regions that are still sized
+    // for 16-bit pixel pairs (pb_lds_bytes: 2 * pad4(rows * cols) bytes each; klt_byte_windows_ok holds the pitch to that room).
+    uint8_t *ref_win;         // two reference windows (this level, next level), ref_win_stride BYTES apart
     int ref_win_stride;
-    uint16_t *cur_win;
+    uint8_t *cur_win;
 };
 
 // Current-tap tables: one per producer wave; in the throughput mode (p.tree) every wave samples, so one per wave.
@@ -120,8 +135,8 @@ __device__ __forceinline__ PbLds pb_carve(float4 *base, const KltParams &p, int 
     c.lattice = c.ring + pb_ring_slots(waves) * np * kTerms * kRingRow;
     c.sol = c.lattice + pb_pad4(p.pb_cap_r * p.pb_cap_c);
     c.slots = reinterpret_cast<uint32_t *>(c.sol + 4);
-    c.ref_win = reinterpret_cast<uint16_t *>(c.slots + 16);
-    c.ref_win_stride = pb_pad4(p.pb_rwin_rows * p.pb_rwin_cols);
+    c.ref_win = reinterpret_cast<uint8_t *>(c.slots + 16);
+    c.ref_win_stride = 2 * pb_pad4(p.pb_rwin_rows * p.pb_rwin_cols);
     c.cur_win = c.ref_win + 2 * c.ref_win_stride;
     return c;
 }
@@ -213,23 +228,36 @@ __device__ __forceinline__ void build_nodes_pass(int lane, const AxisSpec &A, co
     }
 }
 
-// Bilinear value of a node pair from an LDS window: tap_table() of the generic kernel.
-__device__ __forceinline__ float node_tap(const uint16_t *win, int wcols, const float4 &nr, const float4 &nc) {
+// A window of this kernel: bytes, `pitch` apart (a power of two >= cols + 1: element (r, c < cols) reads bytes c, c + 1 of rows r, r + 1).
+struct PbWin {
+    const uint8_t *data;
+    int r_lo, c_lo;
+    int rows, cols, pitch;  // wave-uniform
+    float cover[4];         // as Win::cover (win_set_cover)
+};
+
+// Bilinear value of a node pair from an LDS window: tap_table() of the generic kernel.  No 16-bit read of the two neighbours: idx is
+// odd half of the time, and single-byte reads double the LDS instructions of the kernel's most frequent read.
+__device__ __forceinline__ float node_tap(const uint8_t *win, int pitch, const float4 &nr, const float4 &nc) {
     const int idx = __float_as_int(nr.x) + __float_as_int(nc.x);
-    const unsigned a = win[idx];
-    const unsigned bb = win[idx + wcols];
+    // two aligned dwords per row and an alignbyte: pixel idx, idx + 1 in bytes 0, 1 (the second dword is inside the row: pitch >= cols + 4)
+    const uint32_t *const w = reinterpret_cast<const uint32_t *>(win) + (idx >> 2);
+    const uint32_t top = __builtin_amdgcn_alignbyte(w[1], w[0], (uint32_t)idx & 3u);
+    const uint32_t bot = __builtin_amdgcn_alignbyte(w[(pitch >> 2) + 1], w[pitch >> 2], (uint32_t)idx & 3u);
+    const unsigned tl = top & 0xFFu, tr = (top >> 8) & 0xFFu;
+    const unsigned bl = bot & 0xFFu, br = (bot >> 8) & 0xFFu;
     const float w_tl = nr.z * nc.z;
     const float w_tr = nr.z * nc.y;
     const float w_bl = nr.y * nc.z;
     const float w_br = nr.y * nc.y;
-    return w_tl * (float)(a & 0xFFu) + w_tr * (float)(a >> 8) + w_bl * (float)(bb & 0xFFu) + w_br * (float)(bb >> 8);
+    return w_tl * (float)tl + w_tr * (float)tr + w_bl * (float)bl + w_br * (float)br;
 }
 
 // Per-iteration tables of the current-image taps, private to one producer wave (so no barrier):
 // entry t         = node_entry of the current coordinate of patch row / column t, w = valid AND the
 //                   reference-side validity of that row / column
 // entry total + t = lattice offsets {centre, minus, plus} of that row (pre-multiplied by n_c) / column
-__device__ __forceinline__ void cur_tables(int lane, const KltParams &p, const PbLds &c, float4 *tab, const DevImage &cur, const Win &cw, float cur_u,
+__device__ __forceinline__ void cur_tables(int lane, const KltParams &p, const PbLds &c, float4 *tab, const DevImage &cur, const PbWin &cw, float cur_u,
                                            float cur_v, int n_c) {
     const int total = p.patch_rows + p.patch_cols;
     for (int t = lane; t < total; t += kWave) {
@@ -237,7 +265,7 @@ __device__ __forceinline__ void cur_tables(int lane, const KltParams &p, const P
         const int d = is_row ? t : t - p.patch_rows;
         const float x = (float)(d - (is_row ? p.half_rows : p.half_cols)) + (is_row ? cur_v : cur_u);
         float4 e = node_entry(x, (is_row ? cur.rows : cur.cols) - 1, is_row ? cw.r_lo : cw.c_lo, is_row ? cw.rows - 1 : cw.cols,
-                              is_row ? cw.cols : 1);
+                              is_row ? cw.pitch : 1);
         const uint4 id = is_row ? c.ridx[d] : c.cidx[d];
         e.w = __int_as_float(__float_as_int(e.w) & (int)id.w);
         const int mul = is_row ? n_c : 1;
@@ -279,7 +307,7 @@ __device__ __forceinline__ void pb_read_cols(const PbLane &l, const KltParams &p
 
 // The five per-pixel products of one 64-pixel chunk (basic_klt.cpp:135-144); returns the lane's validity.
 template <class G>
-__device__ __forceinline__ bool chunk_products(int lane, int chunk, const KltParams &p, const PbLds &c, const float4 *tab, const Win &cw, const PbLane &l,
+__device__ __forceinline__ bool chunk_products(int lane, int chunk, const KltParams &p, const PbLds &c, const float4 *tab, const PbWin &cw, const PbLane &l,
                                                const PbCols &cols, float (&prod)[kTerms]) {
     const int tab_total = p.patch_rows + p.patch_cols;
     bool in;
@@ -306,7 +334,7 @@ __device__ __forceinline__ bool chunk_products(int lane, int chunk, const KltPar
         c0 = tab[p.patch_rows + pcol];
         c1 = tab[tab_total + p.patch_rows + pcol];
     }
-    const float i_cur = node_tap(cw.data, cw.cols, r0, c0);
+    const float i_cur = node_tap(cw.data, cw.pitch, r0, c0);
     const float *lat = c.lattice;
     const int rc = __float_as_int(r1.x), rm = __float_as_int(r1.y), rp = __float_as_int(r1.z);
     const int cc = __float_as_int(c1.x), cm = __float_as_int(c1.y), cp = __float_as_int(c1.z);
@@ -330,7 +358,7 @@ __device__ __forceinline__ bool chunk_products(int lane, int chunk, const KltPar
 
 // ... -> ring slot (the exact mode: the consumer wave adds them in pixel order).
 template <class G>
-__device__ __forceinline__ bool produce_chunk(int lane, int chunk, const KltParams &p, const PbLds &c, const float4 *tab, const Win &cw, const PbLane &l,
+__device__ __forceinline__ bool produce_chunk(int lane, int chunk, const KltParams &p, const PbLds &c, const float4 *tab, const PbWin &cw, const PbLane &l,
                                               const PbCols &cols, float *slot) {
     float prod[kTerms];
     const bool ok = chunk_products<G>(lane, chunk, p, c, tab, cw, l, cols, prod);
@@ -363,10 +391,17 @@ __device__ __forceinline__ uint32_t magic20(int d) {
 
 constexpr int kWavesPerEu = 4;
 
-// window_inside() of klt_common.h for a wave-uniform origin: r_lo + wrows <= rows written as r_lo <= rows - wrows has no sum that
-// could overflow, so the four tests are 32-bit scalar compares (the 64-bit form costs vector moves and two vector compares per call).
-__device__ __forceinline__ bool pb_window_inside(const DevImage &im, int r_lo, int c_lo, int wrows, int wcols) {
-    return r_lo >= 0 && c_lo >= 0 && r_lo <= im.rows - wrows && c_lo <= im.cols - wcols - 4;
+constexpr KltParams pb_geometry(int hr, int hc) {
+    KltParams g = {};
+    g.half_rows = hr;
+    g.half_cols = hc;
+    klt_fill_geometry(g);
+    return g;
+}
+
+// The byte windows' staging rule (ftk_device.h klt_byte_window_inside) for a wave-uniform origin: four 32-bit scalar compares.
+__device__ __forceinline__ bool pb_window_inside(const DevImage &im, int r_lo, int c_lo, int wrows, int pitch) {
+    return klt_byte_window_inside(im.rows, im.cols, r_lo, c_lo, wrows, pitch);
 }
 
 // Workgroup barrier — or, for one-wave features packed several to a workgroup (solo), only a compiler fence: LDS operations of
@@ -400,6 +435,10 @@ __global__ void __attribute__((amdgpu_waves_per_eu(kWavesPerEu))) __launch_bound
         p.half_cols = HC;
         klt_fill_geometry(p);  // the same function the host filled p_arg with: identical values, now compile-time
     }
+    constexpr KltParams kGeo = pb_geometry(HR, HC);
+    static_assert(HR == 0 || klt_byte_windows_ok(kGeo), "byte windows: power-of-two pitch inside the carved regions");
+    constexpr int kCurOctets = pb_octets(HR > 0 ? kGeo.cwin_rows : 0, kGeo.pb_cwin_pitch, SOLO, kRunTimeCurOctets);
+    constexpr int kRefOctets = pb_octets(HR > 0 ? kGeo.pb_rwin_rows : 0, kGeo.pb_rwin_pitch, SOLO, kRunTimeRefOctets);
     extern __shared__ float4 lds_raw[];
     Blk b;
     uint32_t id;
@@ -521,9 +560,8 @@ __global__ void __attribute__((amdgpu_waves_per_eu(kWavesPerEu))) __launch_bound
         }
     }
 
-    const int rrows = p.pb_rwin_rows, rcols = p.pb_rwin_cols;
-    const int ref_quads_total = rrows * (rcols >> 2), cur_quads_total = p.cwin_rows * (p.cwin_cols >> 2);
-    const bool ref_fits = ref_quads_total <= kRefQuads * b.nt, cur_fits = cur_quads_total <= kCurQuads * b.nt;
+    const int rrows = p.pb_rwin_rows, rcols = p.pb_rwin_cols, rpitch = p.pb_rwin_pitch, cpitch = p.pb_cwin_pitch;
+    const bool ref_fits = rrows * (rpitch >> 3) <= kRefOctets * b.nt, cur_fits = p.cwin_rows * (cpitch >> 3) <= kCurOctets * b.nt;
 
     int buf = 0;
     // origin of this level's reference window: computed once per level, as the NEXT level's origin while the level before it is entered
@@ -532,7 +570,7 @@ __global__ void __attribute__((amdgpu_waves_per_eu(kWavesPerEu))) __launch_bound
         // the coarsest level's reference window: nothing to overlap it with yet
         const DevImage ref = p_arg.ref[p.n_levels - 1];
         footprint_origin(p, ref_u, ref_v, ref_r_lo, ref_c_lo);
-        stage_any(opaque_blk(b), ref, c.ref_win, ref_r_lo, ref_c_lo, rrows, rcols, p.pb_magic_rwc, p.pb_magic_rwq);
+        stage_bytes_any(opaque_blk(b), ref, c.ref_win, ref_r_lo, ref_c_lo, rrows, rpitch);
     }
     uint32_t iters = 0;
     float out_u = in_u, out_v = in_v;
@@ -545,10 +583,11 @@ __global__ void __attribute__((amdgpu_waves_per_eu(kWavesPerEu))) __launch_bound
         const DevImage cur = p_arg.cur[level];
         set_level_priority(level, younger);
         // ---- level entry: issue the window loads, build the node tables meanwhile ----
-        Win rw, cw;
+        PbWin rw, cw;
         rw.data = c.ref_win + buf * c.ref_win_stride;
         rw.rows = rrows;
         rw.cols = rcols;
+        rw.pitch = rpitch;
         rw.r_lo = ref_r_lo;
         rw.c_lo = ref_c_lo;
         int need_r, need_c;
@@ -558,26 +597,27 @@ __global__ void __attribute__((amdgpu_waves_per_eu(kWavesPerEu))) __launch_bound
         cw.c_lo = wadd(need_c, -p.cwin_margin);
         cw.rows = p.cwin_rows;
         cw.cols = p.cwin_cols;
+        cw.pitch = cpitch;
         win_set_cover(p, cw);
         int nr_lo = 0, nc_lo = 0;
         if (level > 0) {
             footprint_origin(p, ref_u * 2.0f, ref_v * 2.0f, nr_lo, nc_lo);
         }
-        const bool cur_async = cur_fits && pb_window_inside(cur, cw.r_lo, cw.c_lo, cw.rows, cw.cols);
-        const bool next_async = level > 0 && ref_fits && pb_window_inside(p_arg.ref[level > 0 ? level - 1 : 0], nr_lo, nc_lo, rrows, rcols);
+        const bool cur_async = cur_fits && pb_window_inside(cur, cw.r_lo, cw.c_lo, cw.rows, cpitch);
+        const bool next_async = level > 0 && ref_fits && pb_window_inside(p_arg.ref[level > 0 ? level - 1 : 0], nr_lo, nc_lo, rrows, rpitch);
         // the window loads are issued FIRST (they depend on the footprints only) and fly while the node tables and
         // the lattice are built: at one wave per feature the level entry is a chain of dependent latencies
-        RawQuads<kCurQuads> qc;
-        RawQuads<kRefQuads> qn;
+        RawOctets<kCurOctets> qc;
+        RawOctets<kRefOctets> qn;
         if (cur_async) {
-            issue_quads(qc, b, cur, cw.r_lo, cw.c_lo, cw.rows, cw.cols, p.magic_cwq);
+            issue_octets(qc, b, cur, cw.r_lo, cw.c_lo, cw.rows, cpitch);
         }
         if (next_async) {
-            issue_quads(qn, b, p_arg.ref[level - 1], nr_lo, nc_lo, rrows, rcols, p.pb_magic_rwq);
+            issue_octets(qn, b, p_arg.ref[level - 1], nr_lo, nc_lo, rrows, rpitch);
         }
         if (b.wave == 0) {
             // both axes' node tables in one pass of wave 0 (two passes when the patch has more than 64 rows + columns)
-            AxisSpec ar = {p.patch_rows, p.half_rows, ref.rows - 1, rw.r_lo, rw.rows - 1, rw.cols, p.pb_cap_r, ref_v, c.rnodes, c.ridx, &c.slots[0]};
+            AxisSpec ar = {p.patch_rows, p.half_rows, ref.rows - 1, rw.r_lo, rw.rows - 1, rw.pitch, p.pb_cap_r, ref_v, c.rnodes, c.ridx, &c.slots[0]};
             AxisSpec ac = {p.patch_cols, p.half_cols, ref.cols - 1, rw.c_lo, rw.cols, 1, p.pb_cap_c, ref_u, c.cnodes, c.cidx, &c.slots[1]};
             const int lane = opaque(b.lane);
             if (p.patch_rows + p.patch_cols <= kWave) {
@@ -598,20 +638,20 @@ __global__ void __attribute__((amdgpu_waves_per_eu(kWavesPerEu))) __launch_bound
             for (int idx = opaque(b.tid); idx < total; idx += b.nt) {
                 const int r = (int)(__umul24((uint32_t)idx, m) >> 20);  // idx < 4096 and m <= 2^20: the 24-bit multiplier is exact here
                 const int cc = idx - imul(r, n_c);
-                c.lattice[idx] = node_tap(rw.data, rw.cols, c.rnodes[r], c.cnodes[cc]);
+                c.lattice[idx] = node_tap(rw.data, rw.pitch, c.rnodes[r], c.cnodes[cc]);
             }
         }
         // ---- consume the prefetched loads ----
         if (cur_async) {
-            store_quads(qc, b, c.cur_win, cw.rows, cw.cols, p.magic_cwq);
+            store_octets(qc, b, c.cur_win, cw.rows, cpitch);
         } else {
-            stage_any(opaque_blk(b), cur, c.cur_win, cw.r_lo, cw.c_lo, cw.rows, cw.cols, p.magic_cwc, p.magic_cwq);
+            stage_bytes_any(opaque_blk(b), cur, c.cur_win, cw.r_lo, cw.c_lo, cw.rows, cpitch);
         }
         if (level > 0) {
             if (next_async) {
-                store_quads(qn, b, c.ref_win + (buf ^ 1) * c.ref_win_stride, rrows, rcols, p.pb_magic_rwq);
+                store_octets(qn, b, c.ref_win + (buf ^ 1) * c.ref_win_stride, rrows, rpitch);
             } else {
-                stage_any(opaque_blk(b), p_arg.ref[level - 1], c.ref_win + (buf ^ 1) * c.ref_win_stride, nr_lo, nc_lo, rrows, rcols, p.pb_magic_rwc, p.pb_magic_rwq);
+                stage_bytes_any(opaque_blk(b), p_arg.ref[level - 1], c.ref_win + (buf ^ 1) * c.ref_win_stride, nr_lo, nc_lo, rrows, rpitch);
             }
         }
         pb_sync(solo);  // B2: lattice and windows visible
@@ -629,7 +669,7 @@ __global__ void __attribute__((amdgpu_waves_per_eu(kWavesPerEu))) __launch_bound
                     cw.r_lo = wadd(need_r, -p.cwin_margin);
                     cw.c_lo = wadd(need_c, -p.cwin_margin);
                     win_set_cover(p, cw);
-                    stage_any(opaque_blk(b), cur, c.cur_win, cw.r_lo, cw.c_lo, cw.rows, cw.cols, p.magic_cwc, p.magic_cwq);
+                    stage_bytes_any(opaque_blk(b), cur, c.cur_win, cw.r_lo, cw.c_lo, cw.rows, cpitch);
                     pb_sync(solo);
                 }
             }
@@ -802,7 +842,9 @@ KltKernel pick_kernel(bool solo, bool tree) {
     } else {
         entry = solo ? klt_basic_inverse_pipelined_kernel<true, HR, HC, false> : klt_basic_inverse_pipelined_kernel<false, HR, HC, false>;
     }
-    return {entry, "pipelined", HR, solo, tree, false, false, PbChunks<HR, HC>::kByRows};
+    return {entry, "pipelined", HR, solo, tree, false, false, PbChunks<HR, HC>::kByRows,
+            pb_octets(HR > 0 ? pb_geometry(HR, HC).cwin_rows : 0, pb_geometry(HR, HC).pb_cwin_pitch, solo, kRunTimeCurOctets),
+            pb_octets(HR > 0 ? pb_geometry(HR, HC).pb_rwin_rows : 0, pb_geometry(HR, HC).pb_rwin_pitch, solo, kRunTimeRefOctets)};
 }
 }  // namespace
 
@@ -815,7 +857,8 @@ KltKernel klt_pipelined_pick(const KltParams &p) {
     if (p.half_rows == p.half_cols) {
         KltParams check = p;
         klt_fill_geometry(check);  // the specialised kernels recompute exactly this: refuse them if the caller's geometry differs
-        const bool same = check.pb_cap_r == p.pb_cap_r && check.pb_cap_c == p.pb_cap_c && check.cwin_rows == p.cwin_rows && check.cwin_cols == p.cwin_cols;
+        const bool same = check.pb_cap_r == p.pb_cap_r && check.pb_cap_c == p.pb_cap_c && check.cwin_rows == p.cwin_rows && check.cwin_cols == p.cwin_cols &&
+                          check.pb_rwin_pitch == p.pb_rwin_pitch && check.pb_cwin_pitch == p.pb_cwin_pitch;
         if (same) {
             switch (p.half_rows) {
                 case 5: return pick_kernel<5, 5>(solo, p.tree != 0);

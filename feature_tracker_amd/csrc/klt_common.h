@@ -1175,7 +1175,8 @@ __device__ __forceinline__ void footprint_origin(const KltParams &p, float u, fl
 // need = floor(x) - (half + 1) the integer test need >= lo && need + 2 half + 4 <= lo + extent (+ 1 for columns, whose last pair
 // reaches one pixel further) is floor(x) in [lo + half + 1, lo + extent - half - 3 (+ 1)] — exact in fp32 while the bounds are small
 // integers; for a window whose origin is not (a feature far outside the image) the interval is empty and the integer test decides.
-__device__ __forceinline__ void win_set_cover(const KltParams &p, Win &w) {
+template <class W>  // Win, or the pipelined kernel's byte window: the same origin and extents
+__device__ __forceinline__ void win_set_cover(const KltParams &p, W &w) {
     const bool small = (unsigned)(w.r_lo + (1 << 22)) < (1u << 23) && (unsigned)(w.c_lo + (1 << 22)) < (1u << 23);
     w.cover[0] = small ? (float)(w.r_lo + p.half_rows + 1) : 1.0f;
     w.cover[1] = small ? (float)(w.r_lo + w.rows - p.half_rows - 3) : 0.0f;
@@ -1183,7 +1184,8 @@ __device__ __forceinline__ void win_set_cover(const KltParams &p, Win &w) {
     w.cover[3] = small ? (float)(w.c_lo + w.cols - p.half_cols - 2) : 0.0f;
 }
 
-__device__ __forceinline__ bool win_covers(const Win &w, float u, float v) {
+template <class W>
+__device__ __forceinline__ bool win_covers(const W &w, float u, float v) {
     const float fu = floorf(u), fv = floorf(v);
     return fv >= w.cover[0] && fv <= w.cover[1] && fu >= w.cover[2] && fu <= w.cover[3];  // NaN and huge coordinates fail
 }
@@ -1342,6 +1344,114 @@ __device__ __forceinline__ void store_quads(const RawQuads<N> &q, const Blk &b, 
             const uint32_t p3 = __builtin_amdgcn_alignbyte(y, x, 3) & 0xFFFFu;
             *reinterpret_cast<uint2 *>(dst + imul(r, wcols) + 4 * qq) = make_uint2(p0 | (p1 << 16), p2 | (p3 << 16));
         }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Byte windows (the pipelined Basic kernel): byte (r, c) of a window is img[clamp(r_lo + r)][clamp(c_lo + c)], rows `pitch` bytes
+// apart, pitch a power of two (ftk_device.h klt_byte_pitch).  A row is pitch / 8 units of 8 consecutive image bytes; unit idx sits
+// at row idx >> log2(units per row), position idx & (units per row - 1), and at LDS byte 8 * idx: no pair building, no division.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ int byte_units_shift(int pitch) { return 28 - __builtin_clz((unsigned)pitch); }  // log2(pitch / 8)
+
+// Image byte offset of unit idx relative to the window's origin: klt_byte_unit_offset (ftk_device.h) on the 24-bit multiplier (rows and
+// columns of a level are < 2^24 and the product < 2^32, as in px(): the same value).
+__device__ __forceinline__ unsigned byte_unit_offset(int idx, int shift, const DevImage &im) {
+    const unsigned r = (unsigned)idx >> shift, u = (unsigned)idx & ((1u << shift) - 1u);
+    return __umul24(r, (unsigned)im.cols) + 8u * u;
+}
+
+template <int N>
+struct RawOctets {
+    uint32_t x[N], y[N];
+};
+
+// For windows that pass klt_byte_window_inside: the raw 8-byte loads, issued early ...
+template <int N>
+__device__ __forceinline__ void issue_octets(RawOctets<N> &q, const Blk &b, const DevImage &im, int r_lo, int c_lo, int wrows, int pitch) {
+    const int shift = byte_units_shift(pitch);
+    const int total = wrows << shift;
+    const int tid = opaque(b.tid);
+    const uint8_t *base = im.data + (long long)r_lo * im.cols + c_lo;  // wave-uniform: scalar base + 32-bit lane offset
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        int idx = tid + k * b.nt;
+        idx = idx < total ? idx : 0;
+        const uint8_t *src = base + (size_t)byte_unit_offset(idx, shift, im);
+        __builtin_memcpy(&q.x[k], src, 4);  // image columns are not aligned: two dword loads, as the quads
+        __builtin_memcpy(&q.y[k], src + 4, 4);
+    }
+}
+
+// ... and stored late, as they came: one ds_write_b64 per unit.
+template <int N>
+__device__ __forceinline__ void store_octets(const RawOctets<N> &q, const Blk &b, uint8_t *dst, int wrows, int pitch) {
+    const int total = wrows << byte_units_shift(pitch);
+    const int tid = opaque(b.tid);
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        const int idx = tid + k * b.nt;
+        if (idx < total) {
+            *reinterpret_cast<uint2 *>(dst + 8 * idx) = make_uint2(q.x[k], q.y[k]);
+        }
+    }
+}
+
+// Both at once (the coarsest level's reference window, a restaged current window, windows with more units than a thread prefetches).
+__device__ __forceinline__ void stage_bytes_inside(const Blk &b, const DevImage &im, uint8_t *dst, int r_lo, int c_lo, int wrows, int pitch) {
+    const int shift = byte_units_shift(pitch);
+    const int total = wrows << shift;
+    const uint8_t *base = im.data + (long long)r_lo * im.cols + c_lo;
+    for (int idx = b.tid; idx < total; idx += b.nt) {
+        const uint8_t *src = base + (size_t)byte_unit_offset(idx, shift, im);
+        uint32_t x, y;
+        __builtin_memcpy(&x, src, 4);
+        __builtin_memcpy(&y, src + 4, 4);
+        *reinterpret_cast<uint2 *>(dst + 8 * idx) = make_uint2(x, y);
+    }
+}
+
+// Windows that leave the image: four clamped pixels per 32-bit word (what stage_elements puts into the low bytes of its pairs; the
+// high byte of pair c is byte c + 1 here, clamped the same way), kStageBatch words per thread in flight.
+__device__ __forceinline__ uint32_t byte_window_word(const DevImage &im, int r_lo, int c_lo, int word, int pitch_shift) {
+    const int r = word >> (pitch_shift - 2), c = (word & ((1 << (pitch_shift - 2)) - 1)) << 2;
+    const int ir = clampi(wadd(r_lo, r), 0, im.rows - 1);
+    const unsigned row_off = __umul24((unsigned)ir, (unsigned)im.cols);  // 32-bit offsets, as in px()
+    uint32_t w = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int ic = clampi(wadd(c_lo, c + k), 0, im.cols - 1);
+        w |= (uint32_t)im.data[row_off + (unsigned)ic] << (8 * k);
+    }
+    return w;
+}
+
+__device__ __forceinline__ void stage_bytes_elements(const Blk &b, const DevImage &im, uint8_t *dst, int r_lo, int c_lo, int wrows, int pitch) {
+    const int pitch_shift = byte_units_shift(pitch) + 3;
+    const int total = wrows << (pitch_shift - 2);
+    uint32_t *const words = reinterpret_cast<uint32_t *>(dst);
+    for (int base = 0; base < total; base += b.nt * kStageBatch) {
+        uint32_t v[kStageBatch];
+#pragma unroll
+        for (int k = 0; k < kStageBatch; ++k) {
+            const int idx = base + k * b.nt + b.tid;
+            v[k] = byte_window_word(im, r_lo, c_lo, idx < total ? idx : 0, pitch_shift);
+        }
+#pragma unroll
+        for (int k = 0; k < kStageBatch; ++k) {
+            const int idx = base + k * b.nt + b.tid;
+            if (idx < total) {
+                words[idx] = v[k];
+            }
+        }
+    }
+}
+
+__device__ __forceinline__ void stage_bytes_any(const Blk &b, const DevImage &im, uint8_t *dst, int r_lo, int c_lo, int wrows, int pitch) {
+    if (klt_byte_window_inside(im.rows, im.cols, r_lo, c_lo, wrows, pitch)) {
+        stage_bytes_inside(b, im, dst, r_lo, c_lo, wrows, pitch);
+    } else {
+        stage_bytes_elements(b, im, dst, r_lo, c_lo, wrows, pitch);
     }
 }
 

@@ -60,6 +60,8 @@ struct KltKernel {
     bool solo;           // one wave per feature
     bool tree, lum, spill;
     bool row_chunks = false;  // the pipelined kernel's chunks are whole patch rows (klt_basic_kernels.hip pb_row_chunks)
+    // the pipelined kernel: 8-byte units of the current / next reference byte window a thread prefetches at level entry (pb_octets)
+    int cur_units = 0, ref_units = 0;
 };
 KltKernel klt_pipelined_pick(const KltParams &p);
 KltKernel klt_fast_pick(int model, const KltParams &p);
