@@ -39,6 +39,9 @@ FTK_TWO_VIEW_HOMOGRAPHY = 1
 FTK_TWO_VIEW_AUTO = 2
 FTK_TWO_VIEW_HOMOGRAPHY_SAMPLE = 4
 TWO_VIEW_MODES = {"fundamental": 0, "homography": 1, "auto": 2}
+# relative pose and landmarks from two-view inliers (include/ftk.h)
+FTK_POSE_JACOBI_SWEEPS = 7
+FTK_POSE_TILE = 256
 # the keypoint decoder (include/ftk.h)
 FTK_KEYPOINT_DECODE_CELL = 8
 FTK_KEYPOINT_DECODE_MAX_KEYPOINTS = 65536
@@ -94,6 +97,7 @@ EXPORTS = [
     "ftk_harris_detect_device", "ftk_track_table_retire_device", "ftk_track_table_fill_device",
     "ftk_epipolar_workspace_bytes", "ftk_epipolar_ransac_device",
     "ftk_two_view_workspace_bytes", "ftk_two_view_ransac_device",
+    "ftk_two_view_pose_workspace_bytes", "ftk_two_view_pose_device",
     "ftk_keypoint_decode_workspace_bytes", "ftk_keypoint_decode_device",
     "ftk_match_assignment_workspace_bytes", "ftk_match_assignment_device",
     "ftk_transformer_layer_workspace_bytes", "ftk_attention_device", "ftk_linear_device", "ftk_transformer_layer_device",
@@ -285,6 +289,8 @@ def lib() -> C.CDLL:
     l.ftk_epipolar_ransac_device.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, C.c_uint32, vp, vp, vp, vp, vp, vp]
     l.ftk_two_view_workspace_bytes.argtypes = [i32, i32, i32, i64p]
     l.ftk_two_view_ransac_device.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, C.c_uint32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    l.ftk_two_view_pose_workspace_bytes.argtypes = [i32, i64p]
+    l.ftk_two_view_pose_device.argtypes = [vp, vp, vp, vp, vp, i32] + [f32] * 10 + [vp] * 7
     l.ftk_keypoint_decode_workspace_bytes.argtypes = [i32, i32, i32, i32, i64p]
     l.ftk_keypoint_decode_device.argtypes = [vp, vp, vp, i32, i32, vp, i32, C.c_int64, C.c_int64, C.c_int64, i32, f32, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]
     l.ftk_match_assignment_workspace_bytes.argtypes = [i32, i32, i32, i32, i64p]
@@ -303,6 +309,12 @@ def lib() -> C.CDLL:
     l.ftk_match_table_update_device.argtypes = [vp, vp, i32, i32] + [vp] * 15 + [i32, vp, i32, vp, vp]
     _lib = l
     return l
+
+
+def loaded():
+    """The library if it has been loaded, else None: what a destructor frees a handle through.  A destructor runs whenever the collector
+    decides, so it must neither load a library nor talk to whatever stands in for ``lib`` at that moment (a test's recording stand-in)."""
+    return _lib
 
 
 def build_info() -> dict:
@@ -367,6 +379,14 @@ def two_view_workspace_bytes(n: int, hypotheses: int, mode: int = FTK_TWO_VIEW_A
     """Bytes of workspace ftk_two_view_ransac_device needs, the value ftk_two_view_workspace_bytes returns (pure Python): the plan's layout
     with the slots of two models, the same for every mode."""
     return _ransac_workspace_bytes(n, hypotheses, 2)
+
+
+def two_view_pose_workspace_bytes(n: int) -> int:
+    """Bytes of workspace ftk_two_view_pose_device needs, the value ftk_two_view_pose_workspace_bytes returns (pure Python;
+    csrc/two_view_pose_plan.cpp): M, the participants' calibrated coordinates, 45 totals per tile of FTK_POSE_TILE points, the model block."""
+    n = int(n)
+    up16 = lambda v: (v + 15) & ~15  # noqa: E731
+    return 16 + up16(16 * n) + up16(4 * 45 * -(-n // FTK_POSE_TILE)) + 128
 
 
 def keypoint_decode_workspace_bytes(cell_rows: int, cell_cols: int, min_distance: int, n_occupied: int = 0) -> int:

@@ -11,6 +11,43 @@ namespace ftk {
 
 __device__ __forceinline__ bool ep_finite(float v) { return (__float_as_uint(v) & 0x7F800000u) != 0x7F800000u; }
 
+// The participants' scan of ONE workgroup of kEpipolarScanBlock threads (two_view_scan_kernel, pose_scan_kernel): the points with
+// status == FTK_TRACKED in ascending index order, by a block scan of per-thread counts (no atomic append).  A thread owns per_thread
+// (<= 64) consecutive points, its participants one 64-bit mask; store(at, i) places participant `at` of the list, the point i; m[0]
+// receives their number.  scan: kEpipolarScanBlock ints of LDS.
+template <class Store>
+__device__ __forceinline__ void ep_scan_participants(int32_t *const scan, const uint8_t *const status, const int n, const int per_thread, int32_t *const m,
+                                                     Store store) {
+    const int tid = threadIdx.x;
+    const int begin = min(tid * per_thread, n), end = min(begin + per_thread, n);
+    unsigned long long mask = 0ull;
+    int32_t mine = 0;
+    for (int i = begin; i < end; ++i) {
+        if (status[i] == FTK_TRACKED) {
+            mask |= 1ull << (i - begin);
+            ++mine;
+        }
+    }
+    scan[tid] = mine;
+    __syncthreads();
+    for (int step = 1; step < kEpipolarScanBlock; step <<= 1) {  // inclusive Hillis-Steele scan
+        const int32_t add = tid >= step ? scan[tid - step] : 0;
+        __syncthreads();
+        scan[tid] += add;
+        __syncthreads();
+    }
+    int32_t at = scan[tid] - mine;
+    for (int i = begin; i < end; ++i) {
+        if ((mask >> (i - begin)) & 1ull) {
+            store(at, i);
+            ++at;
+        }
+    }
+    if (tid == kEpipolarScanBlock - 1) {
+        m[0] = scan[tid];
+    }
+}
+
 __device__ __forceinline__ uint32_t ep_fmix32(uint32_t x) {  // murmur3's finaliser
     x ^= x >> 16;
     x *= 0x85EBCA6Bu;

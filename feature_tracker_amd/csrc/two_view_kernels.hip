@@ -25,38 +25,12 @@ namespace {
 
 __global__ void __launch_bounds__(kEpipolarScanBlock) two_view_scan_kernel(const TwoViewParams p) {
     __shared__ int32_t scan[kEpipolarScanBlock];
-    const int tid = threadIdx.x;
-    const int n = p.n;
-    const int begin = min(tid * p.scan_per_thread, n), end = min(begin + p.scan_per_thread, n);
-    unsigned long long mask = 0ull;
-    int32_t mine = 0;
-    for (int i = begin; i < end; ++i) {
-        if (p.status[i] == FTK_TRACKED) {
-            mask |= 1ull << (i - begin);
-            ++mine;
-        }
-    }
-    scan[tid] = mine;
-    __syncthreads();
-    for (int step = 1; step < kEpipolarScanBlock; step <<= 1) {  // inclusive Hillis-Steele scan
-        const int32_t add = tid >= step ? scan[tid - step] : 0;
-        __syncthreads();
-        scan[tid] += add;
-        __syncthreads();
-    }
-    int32_t at = scan[tid] - mine;
-    for (int i = begin; i < end; ++i) {
-        if ((mask >> (i - begin)) & 1ull) {
-            const float2 r = reinterpret_cast<const float2 *>(p.ref_uv)[i];
-            const float2 c = reinterpret_cast<const float2 *>(p.cur_uv)[i];
-            p.list[at] = i;
-            p.points[at] = make_float4((r.x - p.cx) * p.s, (r.y - p.cy) * p.s, (c.x - p.cx) * p.s, (c.y - p.cy) * p.s);
-            ++at;
-        }
-    }
-    if (tid == kEpipolarScanBlock - 1) {
-        p.m[0] = scan[tid];
-    }
+    ep_scan_participants(scan, p.status, p.n, p.scan_per_thread, p.m, [&](const int at, const int i) {
+        const float2 r = reinterpret_cast<const float2 *>(p.ref_uv)[i];
+        const float2 c = reinterpret_cast<const float2 *>(p.cur_uv)[i];
+        p.list[at] = i;
+        p.points[at] = make_float4((r.x - p.cx) * p.s, (r.y - p.cy) * p.s, (c.x - p.cx) * p.s, (c.y - p.cy) * p.s);
+    });
 }
 
 template <class Model>

@@ -281,7 +281,9 @@ class Comm:
 
     def close(self):
         if self._handle:
-            N.lib().ftk_comm_destroy(self._handle)
+            library = N.loaded()  # (as Context.close)
+            if library is not None:
+                library.ftk_comm_destroy(self._handle)
             self._handle = None
 
     def __del__(self):
@@ -486,6 +488,7 @@ from ._device_corr_ondemand import corr_ondemand_lookup_device, corr_ondemand_pr
 from ._device_klt_video import _check_bound, harris_detect_device, track_table_fill_device, track_table_retire_device  # noqa: E402,F401  (masked Harris detection and KltVideoTracker's table; its own file, see there)
 from ._device_epipolar import epipolar_ransac_device  # noqa: E402,F401  (two-view outlier rejection; its own file, see there)
 from ._device_two_view import two_view_ransac_device  # noqa: E402,F401  (the same with a choice of model)
+from ._device_two_view_pose import two_view_pose_device  # noqa: E402,F401  (the pose and the landmarks of the inliers; its own file, see there)
 from ._device_keypoint_decode import keypoint_decode_device  # noqa: E402,F401  (the keypoint decoder; its own file, see there)
 from ._device_match_assignment import match_assignment_device  # noqa: E402,F401  (LightGlue's assignment head; its own file, see there)
 from ._device_match_table import match_table_query_device, match_table_update_device  # noqa: E402,F401  (MatchVideoTracker's landmark table; its own file, see there)

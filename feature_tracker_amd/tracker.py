@@ -72,7 +72,9 @@ class Context:
 
     def close(self):
         if self._h:
-            N.lib().ftk_context_destroy(self._h)
+            library = N.loaded()  # (the library that made the handle; never a stand-in for N.lib: __del__ comes here at any time)
+            if library is not None:
+                library.ftk_context_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
@@ -186,7 +188,9 @@ class ImagePyramid:
 
     def close(self):
         if self._h:
-            N.lib().ftk_pyramid_destroy(self._h)
+            library = N.loaded()  # (the library that made the handle; never a stand-in for N.lib: __del__ comes here at any time)
+            if library is not None:
+                library.ftk_pyramid_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

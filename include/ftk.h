@@ -311,7 +311,8 @@ int ftk_track_table_fill_device(ftk_context *ctx, const ftk_pyramid *image, int3
  * d_workspace: ftk_epipolar_workspace_bytes(n, hypotheses) bytes, 16-byte aligned, no initialisation needed.  n = 1 .. FTK_TRACK_TABLE_MAX_SLOTS
  * and hypotheses = 1 .. FTK_EPIPOLAR_MAX_HYPOTHESES, anything beyond is FTK_E_UNSUPPORTED before any launch.  Four launches on `stream` (a
  * hipStream_t; NULL is the null stream) of fixed shape; no host read, no synchronisation, no allocation: capturable at any time.  Integer
- * counts and integer atomics only: the result does not depend on the schedule.
+ * counts and integer atomics only: the result does not depend on the schedule.  The pose and the landmarks of the points this leaves TRACKED:
+ * ftk_two_view_pose_device below.
  */
 #define FTK_EPIPOLAR_MAX_HYPOTHESES 4096
 #define FTK_EPIPOLAR_SAMPLE 8
@@ -339,6 +340,7 @@ int ftk_epipolar_ransac_device(ftk_context *ctx, void *stream, const float *d_re
  * d_workspace: ftk_two_view_workspace_bytes(n, hypotheses, mode) bytes, 16-byte aligned, no initialisation needed.  The limits are the
  * fundamental route's; a mode outside 0 .. 2 or prefer_homography_permille outside 0 .. 1000 is FTK_E_INVALID_ARGUMENT before any launch.
  * Four launches (six with FTK_TWO_VIEW_AUTO) of fixed shape on `stream`; no host read, no synchronisation, no allocation: capturable.
+ * F and H are for rejecting outliers; the pose and the landmarks of the points this leaves TRACKED: ftk_two_view_pose_device below.
  */
 #define FTK_TWO_VIEW_FUNDAMENTAL 0
 #define FTK_TWO_VIEW_HOMOGRAPHY 1
@@ -349,6 +351,42 @@ int ftk_two_view_ransac_device(ftk_context *ctx, void *stream, const float *d_re
                                int32_t image_rows, int32_t image_cols, float threshold, int32_t hypotheses, uint32_t seed, int32_t mode,
                                int32_t prefer_homography_permille, void *d_workspace, int32_t *d_model, int32_t *d_best, int32_t *d_n_inliers,
                                float *d_F, float *d_H, int32_t *d_counts, float *d_models);
+
+/* ---- relative pose and landmarks from two-view inliers (TwoViewPose) ------------ */
+
+/*
+ * What follows the two filters above: the refit of the essential matrix on ALL participants (d_status[i] == FTK_TRACKED, ascending index
+ * order, the scan of the filters), its decomposition, the cheirality vote and the triangulation, all on the device.  DESIGN.md 5.29 states
+ * every float operation and its order; in short, all in float32 without contraction, `/` and sqrtf correctly rounded:
+ *   calibrated coordinates x = (u - cx) / fx, y = (v - cy) / fy, each view with its own camera (fx, fy, cx, cy); a participant with a
+ *   non-finite calibrated coordinate contributes nothing to any sum and ends as FTK_LARGE_RESIDUAL;
+ *   the 45 distinct entries of A = sum r r^T, r = [x2 x1, x2 y1, x2, y2 x1, y2 y1, y2, x1, y1, 1], are summed in a fixed tree: tiles of
+ *   FTK_POSE_TILE participants (a position beyond M is +0), within a tile p[j] += p[j + stride] for stride 128 .. 1, tile totals in ascending
+ *   order from +0.  No float atomics: the bits do not depend on the schedule;
+ *   the null vector of A by cyclic Jacobi (pairs in row-major order, FTK_POSE_JACOBI_SWEEPS sweeps, no early exit), smallest eigenvalue,
+ *   ties to the lowest column; the same Jacobi on E^T E gives U, V; Ehat = u1 v1^T + u2 v2^T; candidates c = 0 .. 3:
+ *   R = U W V^T (c < 2) or U W^T V^T, t = u3 (c even) or -u3, with u3 = u1 x u2, v3 = v1 x v2 (det R > 0 by construction);
+ *   n_front[c] counts the participants whose two-ray (midpoint) depths z1, z2 of z2 x2 = z1 R x1 + t are finite and > 0; the greatest
+ *   count wins, the lowest c among equals.
+ * Outputs: d_pose float32 [7] = q_rc (w, x, y, z), p_rc in ftk_direct_track's convention (x_cur ~ q_rc^-1 (X_ref - p_rc)), |p_rc| = baseline;
+ * d_points float32 [n][3], z1 (x1, y1, 1) scaled to the baseline for a participant with z1, z2 > 0 and a reprojection error in the current
+ * image of at most `threshold` pixels ((fx (X - x2 Z))^2 + (fy (Y - y2 Z))^2 <= threshold^2 Z^2, both sides finite), zeros elsewhere;
+ * d_E float32 [9] Ehat; d_n_front int32 [4]; d_valid int32 [1] (1 / -1); d_n_points int32 [1]; d_status rewritten in place: every other
+ * participant becomes FTK_LARGE_RESIDUAL.  INVALID (M < 8, a second-smallest eigenvalue of A not above 2^-20 of the largest: the points do not determine
+ * E, a non-finite entry of Ehat, R, t or the pose, a winning count of 0): no
+ * status changes, valid = -1, pose = (1, 0, 0, 0, 0, 0, 0), E = 0, points = 0, n_points = 0.
+ * d_workspace: ftk_two_view_pose_workspace_bytes(n) bytes, 16-byte aligned, no initialisation needed.  n = 1 .. FTK_TRACK_TABLE_MAX_SLOTS
+ * (beyond: FTK_E_UNSUPPORTED); fx, fy finite and > 0, cx, cy finite, threshold >= 0 with threshold^2 finite in float32 (up to about 1.8e19),
+ * baseline finite and > 0, else
+ * FTK_E_INVALID_ARGUMENT, all before any launch.  Five launches of fixed shape on `stream`; no host read, no synchronisation, no
+ * allocation: capturable.
+ */
+#define FTK_POSE_JACOBI_SWEEPS 7
+#define FTK_POSE_TILE 256
+int ftk_two_view_pose_workspace_bytes(int32_t n, int64_t *bytes);
+int ftk_two_view_pose_device(ftk_context *ctx, void *stream, const float *d_ref_uv, const float *d_cur_uv, uint8_t *d_status, int32_t n, float fx,
+                             float fy, float cx, float cy, float fx_cur, float fy_cur, float cx_cur, float cy_cur, float threshold, float baseline,
+                             void *d_workspace, float *d_pose, float *d_points, float *d_E, int32_t *d_n_front, int32_t *d_valid, int32_t *d_n_points);
 
 /*
  * ftk_keypoint_decode_device — a SuperPoint-style network's head tensors to keypoints, scores and descriptors, all in device memory

@@ -1,0 +1,352 @@
+"""The restatement of TwoViewPose (tests/two_view_pose_ref.c) pinned without a device: the seeded two-view scenes of
+tests/test_epipolar_cpu.py, an independent float64 composition (numpy eigh, svd, the same four candidates and cheirality), ground truth,
+DirectMethod's own projection (tests/direct_ref64.py), the summation tree restated apart in numpy, the edge cases of the contract, the
+rule that fixed the sweep count, and six mutants that the same checks must each catch.  tests/test_two_view_pose_gpu.py then holds the
+kernels to the restatement bit for bit."""
+import functools
+
+import numpy as np
+import pytest
+
+from tests import direct_ref64 as D64
+from tests import epipolar_ref as E
+from tests import two_view_pose_ref as P
+
+SEEDS = (1, 2, 3)
+S = P.SWEEPS - 1                # the smallest sweep count whose E, pose and n_front equal those of two sweeps more on every scene below
+# against the float64 composition, 4 x the worst deviation measured over the twelve scenes
+MEASURED = (1.04e-5, 7.36e-5, 1.52e-4)  # radians between the two R, radians between the two translation directions, relative depth error
+ROTATION_TOLERANCE, DIRECTION_TOLERANCE, DEPTH_TOLERANCE = (4 * v for v in MEASURED)
+EIGEN_RATIO_CAP = 0.1           # a scene whose two smallest float64 eigenvalues of A have a greater ratio is left out: none may be
+# A point may differ in cheirality or status from float64 only within this multiple of the measured deviations of its margin: a depth by
+# its relative deviation; a reprojection error by fx (d_rotation + d_direction) pixels, which bounds what the two angles move a projection
+# by (a direction's share is further divided by depth / baseline > 1).
+MARGIN_MULTIPLE = 2.0
+# against ground truth on the noise-free scenes, 4 x the worst error measured
+MEASURED_TRUTH = (1.04e-5, 7.35e-5)
+TRUTH_ROTATION_TOLERANCE, TRUTH_DIRECTION_TOLERANCE = (4 * v for v in MEASURED_TRUTH)
+
+
+@functools.lru_cache(maxsize=None)
+def scenes():
+    """The twelve scenes: seeds 1 .. 3, noise-free and with 0.3 px noise, inliers only and after the filter's restatement has marked 30 %
+    outliers: (name, ref_uv, cur_uv, status)."""
+    out = []
+    for seed in SEEDS:
+        for noise in (0.0, 0.3):
+            ref, cur, _, _ = E.scene(300, seed, outlier_share=0.0, noise=noise)
+            out.append(((seed, noise, "inliers"), ref, cur, np.full(300, P.TRACKED, np.uint8)))
+            ref, cur, _, _ = E.scene(300, seed, outlier_share=0.3, noise=noise)
+            filtered = E.ransac(ref, cur, np.full(300, P.TRACKED, np.uint8), E.IMAGE, 1.0, 512, seed)
+            assert 190 <= (filtered.status == P.TRACKED).sum() <= 215
+            out.append(((seed, noise, "filtered"), ref, cur, filtered.status))
+    return tuple(out)
+
+
+def _contract(variant=P.CONTRACT, sweeps=P.SWEEPS):
+    return functools.partial(P.solve, variant=variant, sweeps=sweeps)
+
+
+# ---- the independent float64 composition ------------------------------------------------------------------------------------------------
+
+def _calibrated(uv, K):
+    fx, fy, cx, cy = (np.float64(np.float32(k)) for k in K)
+    uv = uv.astype(np.float64)
+    return np.c_[(uv[:, 0] - cx) / fx, (uv[:, 1] - cy) / fy, np.ones(len(uv))]
+
+
+def _depths64(R, t, x1, x2):
+    a = x1 @ R.T
+    aa, bb, ab, at, bt = (a * a).sum(1), (x2 * x2).sum(1), (a * x2).sum(1), a @ t, x2 @ t
+    det = aa * bb - ab * ab
+    with np.errstate(all="ignore"):
+        return (ab * bt - bb * at) / det, (aa * bt - ab * at) / det, a
+
+
+def compose64(ref, cur, status, K=P.K, K_cur=None, threshold=1.0):
+    """(R, t, z1 [M], margin [M], front margins [4, M], eigenvalue ratio, participants) in float64 with numpy's eigh and svd."""
+    part = np.flatnonzero(status == P.TRACKED)
+    x1, x2 = _calibrated(ref[part], K), _calibrated(cur[part], K if K_cur is None else K_cur)
+    rows = np.stack([x2[:, 0] * x1[:, 0], x2[:, 0] * x1[:, 1], x2[:, 0], x2[:, 1] * x1[:, 0], x2[:, 1] * x1[:, 1], x2[:, 1], x1[:, 0], x1[:, 1],
+                     np.ones(len(part))], 1)
+    lam, vec = np.linalg.eigh(rows.T @ rows)
+    U, _, Vt = np.linalg.svd(vec[:, 0].reshape(3, 3))
+    if np.linalg.det(U) < 0:
+        U = -U
+    if np.linalg.det(Vt) < 0:
+        Vt = -Vt
+    W = np.array([[0.0, -1.0, 0.0], [1.0, 0.0, 0.0], [0.0, 0.0, 1.0]])
+    best = None
+    fronts = []
+    for R in (U @ W @ Vt, U @ W.T @ Vt):
+        for t in (U[:, 2], -U[:, 2]):
+            z1, z2, a = _depths64(R, t, x1, x2)
+            fronts.append(np.minimum(z1, z2))
+            count = int(((z1 > 0) & (z2 > 0)).sum())
+            if best is None or count > best[0]:
+                best = (count, R, t, z1, z2, a)
+    _, R, t, z1, z2, a = best
+    X = z1[:, None] * a + t
+    fx, fy = (np.float64(np.float32(k)) for k in (K if K_cur is None else K_cur)[:2])
+    err = np.hypot(fx * (X[:, 0] - x2[:, 0] * X[:, 2]), fy * (X[:, 1] - x2[:, 1] * X[:, 2])) / np.abs(X[:, 2])  # pixels
+    return R, t, z1, z2, err - threshold, np.array(fronts), lam[0] / lam[1], part
+
+
+def _angle(Ra, Rb):
+    return float(np.arccos(np.clip((np.trace(Ra.T @ Rb) - 1.0) / 2.0, -1.0, 1.0)))
+
+
+def _between(a, b):
+    return float(np.arccos(np.clip(a @ b / (np.linalg.norm(a) * np.linalg.norm(b)), -1.0, 1.0)))
+
+
+def _pose64(r):
+    """(R, t) with X_cur = R X_ref + t of a result's pose, float64: R = R_rc^T, t = -R p_rc."""
+    R = D64.q_matrix(r.pose[:4].astype(np.float64)).T
+    return R, -R @ r.pose[4:].astype(np.float64)
+
+
+# ---- the checks, each over a way to call the restatement (the contract, or a mutant) ---------------------------------------------------
+
+def check_float64(solve, threshold=0.5):
+    """R, the direction of t and the landmarks' depths against the float64 composition on all twelve scenes (none may be left out), and
+    n_front and the rewritten status different from float64 only on points near a boundary.  threshold 0.5 px: at 0.3 px noise some
+    participants fail the reprojection test.  Returns the worst deviations."""
+    worst = np.zeros(3)
+    for name, ref, cur, status in scenes():
+        R64, t64, z1, z2, margin, fronts, ratio, part = compose64(ref, cur, status, threshold=threshold)
+        assert ratio <= EIGEN_RATIO_CAP, (name, ratio)  # the cap on scenes left out is 0: float64 itself is well conditioned on every one
+        r = solve(ref, cur, status, threshold=threshold)
+        assert int(r.valid[0]) == 1, name
+        R, t = _pose64(r)
+        kept = r.status[part] == P.TRACKED
+        depth = np.abs(r.points[part, 2].astype(np.float64)[kept] / z1[kept] - 1.0).max()
+        dev = np.array([_angle(R, R64), _between(t, t64), depth])
+        worst = np.maximum(worst, dev)
+        assert dev[0] <= ROTATION_TOLERANCE and dev[1] <= DIRECTION_TOLERANCE and dev[2] <= DEPTH_TOLERANCE, (name, dev)
+        assert abs(np.linalg.norm(r.pose[4:].astype(np.float64)) - 1.0) <= 1e-6 and abs(np.linalg.norm(r.pose[:4].astype(np.float64)) - 1.0) <= 1e-6
+        # the winner's count: sure points in front, plus at most those whose smaller float64 depth is within the depth deviation of zero
+        front64 = np.minimum(z1, z2)
+        band = MARGIN_MULTIPLE * MEASURED[2] * np.abs(front64).max()
+        sure, near = int((front64 > band).sum()), int((np.abs(front64) <= band).sum())
+        assert sure <= r.n_front.max() <= sure + near, (name, sure, near, r.n_front)
+        assert np.sort(r.n_front)[-2] <= (np.sort((fronts > -band).sum(1))[-2]), (name, r.n_front)
+        # the status: float64's verdict except within the band of the threshold
+        pixel_band = MARGIN_MULTIPLE * float(np.float32(P.K[0])) * (MEASURED[0] + MEASURED[1])
+        want = (front64 > 0) & (margin <= 0)
+        differ = kept != want
+        assert ((np.abs(margin[differ]) <= pixel_band) | (np.abs(front64[differ]) <= band)).all(), (name, margin[differ])
+        assert int(r.n_points[0]) == int(kept.sum()) and (r.status[part][~kept] == P.LARGE_RESIDUAL).all() and not r.points[part][~kept].any()
+        assert 0.5 * len(part) <= kept.sum()
+        if name[1] > 0:
+            assert kept.sum() < len(part) or threshold >= 1.0, name  # noise: the reprojection test does reject
+    return worst
+
+
+def check_ground_truth(solve):
+    """Noise-free: R and the direction of t against the scene's own pose, the landmarks through DirectMethod's projection onto cur_uv."""
+    Rt, tt = P.scene_truth()
+    worst = np.zeros(2)
+    for name, ref, cur, status in scenes():
+        if name[1] > 0:
+            continue
+        r = solve(ref, cur, status)
+        assert int(r.valid[0]) == 1
+        R, t = _pose64(r)
+        err = np.array([_angle(R, Rt), _between(t, tt)])
+        worst = np.maximum(worst, err)
+        assert err[0] <= TRUTH_ROTATION_TOLERANCE and err[1] <= TRUTH_DIRECTION_TOLERANCE, (name, err)
+    return worst
+
+
+def check_direct_projection(solve, threshold=1.0):
+    """pose and points pushed through DirectMethod's own projection (tests/direct_ref64.py: K (q_rc^-1 (X - p_rc))) land on cur_uv within
+    the threshold, in front of the camera: this fixes the convention of q_rc and p_rc."""
+    for name, ref, cur, status in scenes():
+        r = solve(ref, cur, status, threshold=threshold)
+        kept = (status == P.TRACKED) & (r.status == P.TRACKED)
+        assert kept.sum() >= 150
+        uv, z = D64.project(P.K, r.pose[:4], r.pose[4:], r.points[kept])
+        assert (z > 0).all() and np.hypot(*(uv - cur[kept].astype(np.float64)).T).max() <= threshold * (1.0 + 1e-3), name
+        assert (r.points[kept, 2] > 0).all()
+
+
+def _tree_sums(ref, cur, status, K=P.K):
+    """The 45 sums by the stated tree, restated apart in numpy float32: halve a [45, 256] array of a tile seven times, add the tiles."""
+    part = np.flatnonzero(status == P.TRACKED)
+    k = np.array(K, np.float32)
+    x1, y1 = (ref[part, 0] - k[2]) / k[0], (ref[part, 1] - k[3]) / k[1]
+    x2, y2 = (cur[part, 0] - k[2]) / k[0], (cur[part, 1] - k[3]) / k[1]
+    rows = np.stack([x2 * x1, x2 * y1, x2, y2 * x1, y2 * y1, y2, x1, y1, np.ones(len(part), np.float32)]).astype(np.float32)
+    prods = np.stack([rows[a] * rows[b] for a in range(9) for b in range(a, 9)])
+    assert prods.dtype == np.float32
+    total = np.zeros(45, np.float32)
+    for base in range(0, len(part), 256):
+        tile = np.zeros((45, 256), np.float32)
+        chunk = prods[:, base:base + 256]
+        tile[:, :chunk.shape[1]] = chunk
+        stride = 128
+        while stride >= 1:
+            tile[:, :stride] = tile[:, :stride] + tile[:, stride:2 * stride]
+            stride //= 2
+        total = total + tile[:, 0]
+    return total
+
+
+def check_tree(solve):
+    """The sums are the stated tree's, bit for bit, at M <= 256, one tile and a bit, and five tiles."""
+    for name in ("n9", "n256", "n257", "n1025"):
+        ref, cur, status = P.case(name)
+        assert E.same(solve(ref, cur, status).A, _tree_sums(ref, cur, status)), name
+
+
+def check_sweep_rule(solve_with_sweeps, sweeps):
+    """E, pose and n_front with `sweeps` sweeps and with two more are equal bit for bit on every scene of these tests."""
+    cases = [(ref, cur, status, {}) for _, ref, cur, status in scenes()]
+    cases += [P.case(name) + ({},) for name in ("n8", "n9", "n64_half", "n255", "n256", "n257", "n1025", "hostile_finite", "interleaved")]
+    cases += [(cases[2][0], cases[2][1], cases[2][2], dict(K_cur=P.K_OTHER))]
+    for ref, cur, status, kw in cases:
+        a, b = solve_with_sweeps(ref, cur, status, sweeps=sweeps, **kw), solve_with_sweeps(ref, cur, status, sweeps=sweeps + 2, **kw)
+        assert P.same_results(a, b, ("E", "pose", "n_front")) == []
+
+
+CHECKS = {"twisted_pair_chosen": check_ground_truth, "t_with_the_wrong_sign": check_direct_projection, "e_transposed": check_float64,
+          "sequential_sum": check_tree, "reprojection_unscaled_by_fx": check_float64}
+
+
+@pytest.mark.parametrize("check", [check_float64, check_ground_truth, check_direct_projection, check_tree], ids=lambda c: c.__name__)
+def test_the_restatement_passes(check):
+    check(_contract())
+
+
+@pytest.mark.parametrize("mutant", sorted(P.MUTANTS))
+def test_each_mutant_is_caught(mutant):
+    with pytest.raises(AssertionError):
+        CHECKS[mutant](_contract(P.MUTANTS[mutant]))
+
+
+def test_the_sweep_rule_and_its_mutant():
+    """S is the smallest count that meets the rule (S - 1 does not), FTK_POSE_JACOBI_SWEEPS is S + 1, and a restatement that runs one sweep
+    fewer than S - 1 is caught by the rule."""
+    solve = functools.partial(P.solve, variant=P.CONTRACT)
+    check_sweep_rule(solve, S)
+    for fewer in (S - 1, S - 2):
+        with pytest.raises(AssertionError):
+            check_sweep_rule(solve, fewer)
+    header = open(P._SRC.replace("tests/two_view_pose_ref.c", "include/ftk.h")).read()
+    assert f"#define FTK_POSE_JACOBI_SWEEPS {S + 1}\n" in header
+
+
+def test_the_tolerances_are_the_measured_deviations_with_their_margin():
+    worst = check_float64(_contract())
+    truth = check_ground_truth(_contract())
+    print(f"against float64: rotation {worst[0]:.3e} rad, direction {worst[1]:.3e} rad, depth {worst[2]:.3e}; against truth: rotation {truth[0]:.3e}, "
+          f"direction {truth[1]:.3e}")
+    for tolerance, measured in ((ROTATION_TOLERANCE, worst[0]), (DIRECTION_TOLERANCE, worst[1]), (DEPTH_TOLERANCE, worst[2]),
+                                (TRUTH_ROTATION_TOLERANCE, truth[0]), (TRUTH_DIRECTION_TOLERANCE, truth[1])):
+        assert tolerance / 8 <= measured <= tolerance  # no more than 8 x what is measured: it was not set loose
+
+
+# ---- edges --------------------------------------------------------------------------------------------------------------------------------
+
+def _invalid(r, status):
+    return (int(r.valid[0]) == -1 and np.array_equal(r.pose, np.array([1, 0, 0, 0, 0, 0, 0], np.float32)) and not r.E.any() and not r.points.any()
+            and int(r.n_points[0]) == 0 and np.array_equal(r.status, status) and not r.n_front.any())
+
+
+@pytest.mark.parametrize("m", [7, 8, 9])
+def test_few_participants(m):
+    ref, cur, status = P.case(f"n{m}")
+    r = P.solve(ref, cur, status)
+    if m < 8:
+        assert _invalid(r, status)
+    else:
+        Rt, tt = P.scene_truth()
+        R, t = _pose64(r)
+        assert int(r.valid[0]) == 1 and r.n_front.max() == m == int(r.n_points[0]) and _angle(R, Rt) <= 1e-2 and _between(t, tt) <= 5e-2
+
+
+@pytest.mark.parametrize("name", ["identical", "collinear"])
+def test_degenerate_points_are_invalid(name):
+    """All points identical, or on one image line in both views: A has a null space of more than one dimension, which the rank test refuses."""
+    ref, cur, status = P.case(name)
+    assert _invalid(P.solve(ref, cur, status), status)
+
+
+def test_the_rank_test_switches_at_its_floor():
+    """A 40-point scene squeezed towards one image line in both views by a factor s: float64's second-smallest eigenvalue of A over the
+    largest crosses 2^-20 between s = 0.1 and s = 0.2.  The call is invalid where that ratio is below the floor by more than 4 float32
+    epsilons (what a float32 eigenvalue of A may be off by, relative to the largest), valid where it is above by more, and either within."""
+    ref0, cur0, _, _ = E.scene(40, 7, outlier_share=0.0)
+    status = np.full(40, P.TRACKED, np.uint8)
+    floor, band = 2.0 ** -20, 4 * 2.0 ** -23
+    verdicts = []
+    for s in (0.0, 0.05, 0.1, 0.15, 0.2, 0.3, 1.0):
+        ref, cur = ref0.copy(), cur0.copy()
+        ref[:, 1], cur[:, 1] = 100 + s * (ref0[:, 1] - 100), 120 + s * (cur0[:, 1] - 120)
+        x1, x2 = _calibrated(ref, P.K), _calibrated(cur, P.K)
+        rows = (x2[:, :, None] * x1[:, None, :]).reshape(-1, 9)
+        lam = np.linalg.eigvalsh(rows.T @ rows)
+        ratio = lam[1] / lam[-1]
+        r = P.solve(ref, cur, status)
+        if ratio < floor - band:
+            assert _invalid(r, status), (s, ratio)
+        elif ratio > floor + band:
+            assert int(r.valid[0]) == 1 and np.isfinite(r.pose).all() and np.isfinite(r.points).all(), (s, ratio)
+        verdicts.append((ratio, int(r.valid[0])))
+    assert sum(1 for _, v in verdicts if v == 1) >= 3 and sum(1 for _, v in verdicts if v == -1) >= 3
+    assert any(floor / 2 <= ratio <= 2 * floor for ratio, _ in verdicts)  # a case sits within a factor of two of the floor
+
+
+def test_non_participants_are_not_read_and_not_touched():
+    ref, cur, status = P.case("interleaved")
+    r = P.solve(ref, cur, status)
+    out = status != P.TRACKED
+    assert int(r.valid[0]) == 1 and np.array_equal(r.status[out], status[out]) and not r.points[out].any() and int(r.n_points[0]) == (~out).sum()
+    ref2 = ref.copy()
+    ref2[out] = 12345.0
+    assert P.same_results(r, P.solve(ref2, cur, status)) == []
+
+
+def test_hostile_participants():
+    """NaN and inf among the participants contribute nothing and end as LARGE_RESIDUAL with a zero point; the pose is that of the others.  A
+    finite 1e30 is a participant like any other: the products of its row overflow float32, the sums are not finite and the call is invalid."""
+    ref, cur, status = P.case("hostile_finite")
+    r = P.solve(ref, cur, status)
+    bad = ~(np.isfinite(ref).all(axis=1) & np.isfinite(cur).all(axis=1))
+    assert bad.sum() == 4 and int(r.valid[0]) == 1 and (r.status[bad] == P.LARGE_RESIDUAL).all() and not r.points[bad].any()
+    assert (r.status[~bad] == P.TRACKED).all() and int(r.n_points[0]) == 36 == r.n_front.max() and np.isfinite(r.points).all()
+    status2 = status.copy()
+    status2[bad] = E.OUTSIDE  # the same call without them: the same addends at other places of the tree, the same pose to rounding
+    clean = P.solve(ref, cur, status2)
+    (Ra, ta), (Rb, tb) = _pose64(r), _pose64(clean)
+    assert E.same(r.n_front, clean.n_front) and _angle(Ra, Rb) <= ROTATION_TOLERANCE and _between(ta, tb) <= DIRECTION_TOLERANCE
+    ref, cur, status = P.case("hostile")
+    assert _invalid(P.solve(ref, cur, status), status)
+
+
+def test_the_baseline_scales_p_rc_and_the_points_and_nothing_else():
+    _, ref, cur, status = scenes()[3]
+    a, b = P.solve(ref, cur, status), P.solve(ref, cur, status, baseline=0.12)
+    assert P.same_results(a, b, ("E", "n_front", "valid", "n_points", "status")) == [] and E.same(a.pose[:4], b.pose[:4])
+    assert abs(np.linalg.norm(b.pose[4:].astype(np.float64)) - 0.12) <= 1e-7
+    assert np.allclose(b.pose[4:], 0.12 * a.pose[4:].astype(np.float64), rtol=1e-6, atol=0) and np.allclose(b.points, 0.12 * a.points.astype(np.float64), rtol=1e-6, atol=0)
+
+
+def test_a_second_camera():
+    """The current view through another camera: cur_uv mapped by K_OTHER K^-1 gives the pose of the one-camera call."""
+    _, ref, cur, status = scenes()[0]
+    fx, fy, cx, cy = P.K
+    gx, gy, hx, hy = P.K_OTHER
+    cur2 = np.c_[(cur[:, 0].astype(np.float64) - cx) / fx * gx + hx, (cur[:, 1].astype(np.float64) - cy) / fy * gy + hy].astype(np.float32)
+    a, b = P.solve(ref, cur, status), P.solve(ref, cur2, status, K_cur=P.K_OTHER)
+    (Ra, ta), (Rb, tb) = _pose64(a), _pose64(b)
+    assert int(b.valid[0]) == 1 and _angle(Ra, Rb) <= ROTATION_TOLERANCE and _between(ta, tb) <= DIRECTION_TOLERANCE
+    assert P.same_results(a, P.solve(ref, cur, status, K_cur=P.K)) == []  # K_cur = K is K_cur = None
+    wrong = P.solve(ref, cur2, status)  # the second camera ignored: another pose
+    assert _angle(Ra, _pose64(wrong)[0]) > 10 * ROTATION_TOLERANCE
+
+
+def test_two_calls_give_equal_bits():
+    for _, ref, cur, status in scenes()[:4]:
+        assert P.same_results(P.solve(ref, cur, status), P.solve(ref, cur, status)) == []
