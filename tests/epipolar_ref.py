@@ -109,31 +109,63 @@ def sample_indices(status, hypotheses, seed):
 IMAGE = (480, 640)  # (H, W)
 
 
-@functools.lru_cache(maxsize=None)
-def scene(n, seed, outlier_share=0.3, noise=0.0, image=IMAGE, min_outlier_distance=4.0):
+SCENE_CENTRE = (0.0, 0.0, 6.0)  # scenes with a given pose: points in a cube of half-width SCENE_HALF_WIDTH about this point of the reference frame
+SCENE_HALF_WIDTH = 1.5
+SCENE_MIN_DEPTH = 0.5           # ... kept when at least this deep in both views and 5 px inside both images
+
+
+def pose_key(pose):
+    """(R, t) -> a hashable key of its float64 values (None stays None): what the cached scene functions take."""
+    if pose is None:
+        return None
+    R, t = pose
+    return tuple(float(v) for v in np.asarray(R, np.float64).reshape(9)), tuple(float(v) for v in np.asarray(t, np.float64).reshape(3))
+
+
+def scene(n, seed, outlier_share=0.3, noise=0.0, image=IMAGE, min_outlier_distance=4.0, pose=None):
     """Seeded 3-D points seen by two pinhole poses with real translation: (ref_uv, cur_uv, is_inlier, F64).  The first
     round(n * outlier_share) indices of a seeded permutation are gross outliers: cur is redrawn until it lies at least
-    ``min_outlier_distance`` pixels from the true epipolar line of ref.  ``noise``: Gaussian sigma in pixels on the inliers' cur."""
+    ``min_outlier_distance`` pixels from the true epipolar line of ref.  ``noise``: Gaussian sigma in pixels on the inliers' cur.
+    ``pose`` = (R, t) with X_cur = R X_ref + t: None is the one small motion these scenes began with (points by pixel and depth 2-10); a
+    given pose sees points of the cube about SCENE_CENTRE."""
+    return _scene(n, seed, outlier_share, noise, image, min_outlier_distance, pose_key(pose))
+
+
+@functools.lru_cache(maxsize=None)
+def _scene(n, seed, outlier_share, noise, image, min_outlier_distance, pose):
     rng = np.random.default_rng(seed)
     H, W = image
     f = 0.8 * W
     Kc = np.array([[f, 0, 0.5 * (W - 1)], [0, f, 0.5 * (H - 1)], [0, 0, 1.0]])
-    ang = np.array([0.03, -0.05, 0.02])
-    Rx = np.array([[1, 0, 0], [0, np.cos(ang[0]), -np.sin(ang[0])], [0, np.sin(ang[0]), np.cos(ang[0])]])
-    Ry = np.array([[np.cos(ang[1]), 0, np.sin(ang[1])], [0, 1, 0], [-np.sin(ang[1]), 0, np.cos(ang[1])]])
-    Rz = np.array([[np.cos(ang[2]), -np.sin(ang[2]), 0], [np.sin(ang[2]), np.cos(ang[2]), 0], [0, 0, 1]])
-    R, t = Rz @ Ry @ Rx, np.array([0.5, 0.1, 0.15])
     ref, cur = np.zeros((n, 2)), np.zeros((n, 2))
     k = 0
-    while k < n:
-        uv = rng.uniform([10, 10], [W - 10, H - 10])
-        depth = rng.uniform(2.0, 10.0)
-        X = np.linalg.inv(Kc) @ np.array([uv[0], uv[1], 1.0]) * depth
-        x2 = Kc @ (R @ X + t)
-        x2 = x2[:2] / x2[2]
-        if 5 <= x2[0] <= W - 5 and 5 <= x2[1] <= H - 5:
-            ref[k], cur[k] = uv, x2
-            k += 1
+    if pose is None:
+        ang = np.array([0.03, -0.05, 0.02])
+        Rx = np.array([[1, 0, 0], [0, np.cos(ang[0]), -np.sin(ang[0])], [0, np.sin(ang[0]), np.cos(ang[0])]])
+        Ry = np.array([[np.cos(ang[1]), 0, np.sin(ang[1])], [0, 1, 0], [-np.sin(ang[1]), 0, np.cos(ang[1])]])
+        Rz = np.array([[np.cos(ang[2]), -np.sin(ang[2]), 0], [np.sin(ang[2]), np.cos(ang[2]), 0], [0, 0, 1]])
+        R, t = Rz @ Ry @ Rx, np.array([0.5, 0.1, 0.15])
+        while k < n:
+            uv = rng.uniform([10, 10], [W - 10, H - 10])
+            depth = rng.uniform(2.0, 10.0)
+            X = np.linalg.inv(Kc) @ np.array([uv[0], uv[1], 1.0]) * depth
+            x2 = Kc @ (R @ X + t)
+            x2 = x2[:2] / x2[2]
+            if 5 <= x2[0] <= W - 5 and 5 <= x2[1] <= H - 5:
+                ref[k], cur[k] = uv, x2
+                k += 1
+    else:
+        R, t = np.array(pose[0]).reshape(3, 3), np.array(pose[1])
+        while k < n:
+            X = np.array(SCENE_CENTRE) + rng.uniform(-SCENE_HALF_WIDTH, SCENE_HALF_WIDTH, 3)
+            Y = R @ X + t
+            if X[2] < SCENE_MIN_DEPTH or Y[2] < SCENE_MIN_DEPTH:
+                continue
+            x1, x2 = Kc @ X, Kc @ Y
+            x1, x2 = x1[:2] / x1[2], x2[:2] / x2[2]
+            if all(5 <= x[0] <= W - 5 and 5 <= x[1] <= H - 5 for x in (x1, x2)):
+                ref[k], cur[k] = x1, x2
+                k += 1
     tx = np.array([[0, -t[2], t[1]], [t[2], 0, -t[0]], [-t[1], t[0], 0]])
     F = np.linalg.inv(Kc).T @ tx @ R @ np.linalg.inv(Kc)
     F /= np.linalg.norm(F)

@@ -212,3 +212,79 @@ def test_pixel_F_is_the_denormalised_model():
     s, cx, cy = 2.0 / (W + H), 0.5 * (W - 1), 0.5 * (H - 1)
     T = np.array([[s, 0, -cx * s], [0, s, -cy * s], [0, 0, 1]])
     assert np.abs(T.T @ r.models[r.best].astype(np.float64).reshape(3, 3) @ T - F).max() <= 1e-6 * np.abs(F).max()
+
+
+# ---- more than one camera motion: the pose family of tests/two_view_pose_ref.py -----------------------------------------
+
+EPIPOLE_RADIUS = 20.0  # pixels
+
+
+def near_the_epipole(pose, ref, cur):
+    """Points within EPIPOLE_RADIUS of the epipole in either image (K t / t_z in the current one, K (-R^T t) / (.)_z in the reference)."""
+    from tests import two_view_pose_ref as P
+    R, t = P.family_pose(pose)
+    fx, fy, cx, cy = P.K
+    e_cur, e_ref = t, -R.T @ t
+    near = np.zeros(len(ref), bool)
+    for uv, e in ((cur, e_cur), (ref, e_ref)):
+        if abs(e[2]) > 1e-9:
+            near |= np.hypot(uv[:, 0] - (fx * e[0] / e[2] + cx), uv[:, 1] - (fy * e[1] / e[2] + cy)) <= EPIPOLE_RADIUS
+    return near
+
+
+def _sampson_pixels(f, ref, cur, image=E.IMAGE, of_pixels=False):
+    """The contract's residual of every point under a model of the normalised coordinates (or of pixels), float64, in pixels."""
+    H, W = image
+    centre, s = (np.zeros(2), 1.0) if of_pixels else (np.array([0.5 * (W - 1), 0.5 * (H - 1)]), 2.0 / (W + H))
+    x1, x2 = np.c_[(ref.astype(np.float64) - centre) * s, np.ones(len(ref))], np.c_[(cur.astype(np.float64) - centre) * s, np.ones(len(ref))]
+    F = np.asarray(f, np.float64).reshape(3, 3)
+    a, b = x1 @ F.T, x2 @ F
+    return np.abs((x2 * a).sum(axis=1)) / np.sqrt(a[:, 0] ** 2 + a[:, 1] ** 2 + b[:, 0] ** 2 + b[:, 1] ** 2) / s
+
+
+KEPT_OUTLIERS = {"small/forward": 1, "z-150/side": 1, "z90/forward": 3}  # at seed 1, 512 hypotheses; every other pose of the family: none
+
+
+def family_filter_runs():
+    """(pose, ref_uv, cur_uv, is_inlier, the restatement's result, float64's eigenvalue ratio of the inliers' A) over the whole family at 300
+    points, 30 % outliers, seed 1, 512 hypotheses."""
+    from tests import two_view_pose_ref as P
+    from tests.test_two_view_pose_cpu import _rank_ratio64
+    for pose in P.FAMILY:
+        ref, cur, is_inlier, _ = P.family_scene(pose, 300, 1, outlier_share=0.3)
+        r = E.ransac(ref, cur, _all_tracked(300), E.IMAGE, 1.0, 512, 1)
+        yield pose, ref, cur, is_inlier, r, _rank_ratio64(ref, cur, np.where(is_inlier, E.TRACKED, E.OUTSIDE).astype(np.uint8))
+
+
+def test_the_pose_family_is_cleaned_as_far_as_its_scenes_determine_one_model():
+    """The whole pose family.  No inlier is ever rejected, those within 20 px of an epipole included.  check_noise_free_scenes' other half,
+    every outlier rejected, holds where the scene determines one fundamental matrix: float64's ratio of the second-smallest to the largest
+    eigenvalue of the inliers' A at or above P.FILTER_WELL_CONDITIONED (14 poses).  Below it (the small turns and the turns about z of a
+    shallow cube: 1.6e-6 ... 6.6e-6) the second eigenvector fits the inliers to 0.9 ... 4.6 px rms, a mix of the two still fits all of them
+    within the pixel, and a sample of seven inliers and an outlier picks the mix through that outlier: it counts one more than any clean
+    sample and wins, as the greatest count must.  On three poses that happens; it is shown to be the scene and not the arithmetic: the winning
+    sample holds the kept outlier, the float64 null vector of the same sample keeps it too (at 0.0 px) with every inlier, and under the true F
+    it lies 19 px (small/forward), 4.1 px (z-150/side) and 1.4 ... 2.8 px (z90/forward) away.  A refit on the inliers is not part of 5.20."""
+    from tests import two_view_pose_ref as P
+    seen, near_total = {}, 0
+    for pose, ref, cur, is_inlier, r, ratio in family_filter_runs():
+        kept = r.status == E.TRACKED
+        wrong = kept & ~is_inlier
+        assert r.best >= 0 and kept[is_inlier].all(), (pose, int((~kept & is_inlier).sum()))
+        assert r.n_inliers == int(kept.sum()) == r.counts[r.best] and (r.status[~kept] == E.LARGE_RESIDUAL).all()
+        if pose.endswith("/forward"):
+            near = near_the_epipole(pose, ref, cur) & is_inlier
+            near_total += int(near.sum())
+            assert kept[near].all(), pose
+        if ratio >= P.FILTER_WELL_CONDITIONED:
+            assert not wrong.any(), (pose, ratio, np.flatnonzero(wrong))
+        if wrong.any():
+            seen[pose] = int(wrong.sum())
+            models, _, _ = _f64_models(ref, cur, r, E.IMAGE)
+            f64 = next(f for h, f, _ in models if h == r.best)
+            distance = _sampson_pixels(f64, ref, cur)
+            assert set(np.flatnonzero(wrong)) & set(r.samples[r.best].tolist()), pose       # the winning sample holds a kept outlier
+            assert (distance[kept] <= 1.0).all() and (distance[~kept] > 1.0).all(), pose      # float64 on that sample: the same verdict
+            assert (_sampson_pixels(P.family_scene(pose, 300, 1, outlier_share=0.3)[3], ref, cur, of_pixels=True)[wrong] > 1.0).all(), pose
+    assert seen == KEPT_OUTLIERS, seen
+    assert near_total >= 3  # x170/forward, y170/forward and z90/forward have inliers about the epipole

@@ -102,3 +102,12 @@ def test_the_context_stream_and_the_refusals_of_the_library(ftk):
     assert call(0, 8) == -1 and call(16, 0) == -1 and call(16, 8, rows=0) == -1
     torch.cuda.synchronize()
     assert st.cpu().numpy().tolist() == [1] * 16
+
+
+def test_bit_identity_on_the_pose_family(ftk):
+    """A pose per branch of TwoViewPose's quaternion and forward motion (tests/two_view_pose_ref.py), 30 % outliers."""
+    from tests import two_view_pose_ref as P
+    for pose in P.FILTER_POSES:
+        ref, cur, _, _ = P.family_scene(pose, 300, 1, outlier_share=0.3)
+        status = np.full(300, E.TRACKED, np.uint8)
+        _equal(_device(ftk, ref, cur, status, E.IMAGE, 1.0, 512, 1), E.ransac(ref, cur, status, E.IMAGE, 1.0, 512, 1), pose)

@@ -302,3 +302,25 @@ def test_repeat_and_seed():
     a, b, c = (T.ransac(ref, cur, _all_tracked(300), T.IMAGE, 1.0, 64, seed, T.AUTO) for seed in (7, 7, 8))
     assert T.same_results(a, b) == [] and E.same(a.samples_h, b.samples_h) and E.same(a.samples_f, b.samples_f)
     assert not np.array_equal(a.samples_h, c.samples_h)
+
+
+# ---- more than one camera motion: the pose family of tests/two_view_pose_ref.py -----------------------------------------
+
+def test_the_pose_family_is_cleaned_as_far_as_its_scenes_determine_one_model():
+    """The whole pose family.  Mode "fundamental" is tests/epipolar_ref.c's result bit for bit at every pose, so the bound that
+    tests/test_epipolar_cpu.py asserts there holds here: no inlier rejected anywhere, no outlier kept where the scene determines one
+    fundamental matrix, and the kept outliers of the three shallow scenes named there (KEPT_OUTLIERS) are these.  The homography on the plane
+    (a pose per branch of TwoViewPose's quaternion, and forward motion) has check_scene_a's noise-free bound: every patch point rejected and
+    no background point."""
+    from tests import two_view_pose_ref as P
+    from tests.test_epipolar_cpu import KEPT_OUTLIERS, family_filter_runs
+    for pose, ref, cur, is_inlier, want, _ in family_filter_runs():
+        r = T.ransac(ref, cur, _all_tracked(300), T.IMAGE, 1.0, 512, 1, "fundamental")
+        assert r.model == 0 and E.same(r.status, want.status) and E.same(r.F, want.F) and E.same(r.counts[0], want.counts), pose
+        assert int(((r.status == T.TRACKED) & ~is_inlier).sum()) == KEPT_OUTLIERS.get(pose, 0) and (r.status == T.TRACKED)[is_inlier].all(), pose
+    for pose in P.FILTER_POSES:
+        ref, cur, on_patch, _ = T.planar_scene(300, 1, "moving", 0.0, pose=P.family_pose(pose))
+        r = T.ransac(ref, cur, _all_tracked(300), T.IMAGE, 1.0, 512, 1, "homography")
+        rejected = r.status == T.LARGE_RESIDUAL
+        assert int((rejected & on_patch).sum()) == int(on_patch.sum()) == 45 and not (rejected & ~on_patch).any(), pose
+        assert r.model == 1 and r.n_inliers[1] == 255 == int((r.status == T.TRACKED).sum()), pose

@@ -125,3 +125,17 @@ def test_the_context_stream_and_the_refusals_of_the_library(ftk):
     assert call(16, 8, mode=3) == -1 and call(16, 8, mode=-1) == -1 and call(16, 8, p=1001) == -1 and call(16, 8, p=-1) == -1
     torch.cuda.synchronize()
     assert st.cpu().numpy().tolist() == [1] * 16
+
+
+def test_bit_identity_on_the_pose_family(ftk):
+    """A pose per branch of TwoViewPose's quaternion and forward motion (tests/two_view_pose_ref.py): the fundamental
+    matrix on the depth scene with 30 % outliers, the homography on the plane with its patch."""
+    from tests import two_view_pose_ref as P
+    status = np.full(300, T.TRACKED, np.uint8)
+    for pose in P.FILTER_POSES:
+        ref, cur, _, _ = P.family_scene(pose, 300, 1, outlier_share=0.3)
+        want = T.ransac(ref, cur, status, T.IMAGE, 1.0, 512, 1, "fundamental")
+        assert T.same_results(_device(ftk, ref, cur, status, T.IMAGE, 1.0, 512, 1, "fundamental"), want) == [], pose
+        ref, cur, _, _ = T.planar_scene(300, 1, "moving", 0.0, pose=P.family_pose(pose))
+        want = T.ransac(ref, cur, status, T.IMAGE, 1.0, 512, 1, "homography")
+        assert T.same_results(_device(ftk, ref, cur, status, T.IMAGE, 1.0, 512, 1, "homography"), want) == [], pose

@@ -1,8 +1,9 @@
 """The restatement of TwoViewPose (tests/two_view_pose_ref.c) pinned without a device: the seeded two-view scenes of
 tests/test_epipolar_cpu.py, an independent float64 composition (numpy eigh, svd, the same four candidates and cheirality), ground truth,
 DirectMethod's own projection (tests/direct_ref64.py), the summation tree restated apart in numpy, the edge cases of the contract, the
-rule that fixed the sweep count, and six mutants that the same checks must each catch.  tests/test_two_view_pose_gpu.py then holds the
-kernels to the restatement bit for bit."""
+rule that fixed the sweep count, and six mutants that the same checks must each catch; then the same over a family of camera motions that
+reaches every branch of the quaternion, every cheirality winner and every Jacobi path, with four mutants only the family catches.
+tests/test_two_view_pose_gpu.py then holds the kernels to the restatement bit for bit."""
 import functools
 
 import numpy as np
@@ -159,10 +160,10 @@ def check_ground_truth(solve):
     return worst
 
 
-def check_direct_projection(solve, threshold=1.0):
+def check_direct_projection(solve, threshold=1.0, over=scenes):
     """pose and points pushed through DirectMethod's own projection (tests/direct_ref64.py: K (q_rc^-1 (X - p_rc))) land on cur_uv within
     the threshold, in front of the camera: this fixes the convention of q_rc and p_rc."""
-    for name, ref, cur, status in scenes():
+    for name, ref, cur, status in over():
         r = solve(ref, cur, status, threshold=threshold)
         kept = (status == P.TRACKED) & (r.status == P.TRACKED)
         assert kept.sum() >= 150
@@ -200,9 +201,9 @@ def check_tree(solve):
         assert E.same(solve(ref, cur, status).A, _tree_sums(ref, cur, status)), name
 
 
-def check_sweep_rule(solve_with_sweeps, sweeps):
+def check_sweep_rule(solve_with_sweeps, sweeps, over=scenes):
     """E, pose and n_front with `sweeps` sweeps and with two more are equal bit for bit on every scene of these tests."""
-    cases = [(ref, cur, status, {}) for _, ref, cur, status in scenes()]
+    cases = [(ref, cur, status, {}) for _, ref, cur, status in over()]
     cases += [P.case(name) + ({},) for name in ("n8", "n9", "n64_half", "n255", "n256", "n257", "n1025", "hostile_finite", "interleaved")]
     cases += [(cases[2][0], cases[2][1], cases[2][2], dict(K_cur=P.K_OTHER))]
     for ref, cur, status, kw in cases:
@@ -350,3 +351,204 @@ def test_a_second_camera():
 def test_two_calls_give_equal_bits():
     for _, ref, cur, status in scenes()[:4]:
         assert P.same_results(P.solve(ref, cur, status), P.solve(ref, cur, status)) == []
+
+
+# ---- the pose family: more than one camera motion ----------------------------------------------------------------------
+
+FAMILY_SEEDS = (1, 2)
+# against the float64 composition over the family, 4 x the worst deviation measured: radians between the two R (by _rotation_angle),
+# radians between the two translation directions, relative depth error
+FAMILY_MEASURED = (4.36e-5, 6.69e-4, 7.03e-3)
+FAMILY_TOLERANCES = tuple(4 * v for v in FAMILY_MEASURED)
+# against the family's own (R, t) on the noise-free scenes, the depths being float64's two-ray depths under that pose, 4 x the worst measured
+FAMILY_MEASURED_TRUTH = (3.76e-5, 5.80e-4, 6.26e-3)
+FAMILY_TRUTH_TOLERANCES = tuple(4 * v for v in FAMILY_MEASURED_TRUTH)
+# A depth is compared where the point's two rays meet at PARALLAX_FLOOR radians or more: the relative error of a two-ray depth is the
+# error of the rays' directions over that angle, so towards the epipole (forward motion puts it inside the image) it measures the point's
+# place, not the code: on z90/forward the worst point is off by 0.30 with a median of 1.3e-4.  Under forward motion the parallax of a
+# point at the angle w from the epipole is (baseline / depth) sin w = 0.13 w: the floor is a disc of 0.038 rad, 20 px at fx = 512, about the
+# epipole, and nothing at the sideways poses (0.11 ... 0.13 rad).  At least WIDE_SHARE of a scene's landmarks must stand above it.
+PARALLAX_FLOOR = 0.005
+WIDE_SHARE = 0.9
+RANK_FLOOR = 2.0 ** -20        # kPoseRankFloor: the second-smallest eigenvalue of A over the largest must exceed it
+NAMED_CASES = ("n8", "n9", "n64_half", "n255", "n256", "n257", "n1025") + P.HOSTILE_CASES
+
+
+@functools.lru_cache(maxsize=None)
+def family_scenes():
+    """Every pose of the family at 300 points, seeds 1 and 2, noise-free and with 0.3 px noise: ((pose, seed, noise), ref_uv, cur_uv, status)."""
+    status = np.full(300, P.TRACKED, np.uint8)
+    status.setflags(write=False)
+    return tuple(((pose, seed, noise),) + P.family_scene(pose, 300, seed, noise)[:2] + (status,)
+                 for pose in P.FAMILY for seed in FAMILY_SEEDS for noise in (0.0, 0.3))
+
+
+def _rotation_angle(Ra, Rb):
+    """The angle of Ra^T Rb by atan2 of the sine (half the norm of the vee of its antisymmetric part) and the cosine: unlike _angle's arccos
+    it resolves an angle far below the square root of float32's epsilon."""
+    D = Ra.T @ Rb
+    A = D - D.T
+    return float(np.arctan2(0.5 * np.linalg.norm([A[2, 1], A[0, 2], A[1, 0]]), 0.5 * (np.trace(D) - 1.0)))
+
+
+def _rank_ratio64(ref, cur, status, K=P.K):
+    part = status == P.TRACKED
+    x1, x2 = _calibrated(ref[part], K), _calibrated(cur[part], K)
+    rows = (x2[:, :, None] * x1[:, None, :]).reshape(-1, 9)
+    lam = np.linalg.eigvalsh(rows.T @ rows)
+    return float(lam[1] / lam[-1])
+
+
+def check_family_float64(solve, threshold=0.5):
+    """check_float64 over the family, none left out, with the angle that resolves small rotations and the family's own measured deviations;
+    on the noise-free scenes also against the pose the scene was made with.  Returns the worst deviations from float64 and from the truth."""
+    worst, worst_truth = np.zeros(3), np.zeros(3)
+    for name, ref, cur, status in family_scenes():
+        R64, t64, z1, z2, margin, fronts, ratio, part = compose64(ref, cur, status, threshold=threshold)
+        assert ratio <= EIGEN_RATIO_CAP, (name, ratio)
+        r = solve(ref, cur, status, threshold=threshold)
+        assert int(r.valid[0]) == 1, name
+        R, t = _pose64(r)
+        kept = r.status[part] == P.TRACKED
+        z = r.points[part, 2].astype(np.float64)
+        x1, x2 = _calibrated(ref[part], P.K), _calibrated(cur[part], P.K)
+        a = x1 @ R64.T
+        parallax = np.arcsin(np.linalg.norm(np.cross(a, x2), axis=1) / (np.linalg.norm(a, axis=1) * np.linalg.norm(x2, axis=1)))
+        wide = kept & (parallax >= PARALLAX_FLOOR)
+        assert wide.sum() >= WIDE_SHARE * kept.sum(), (name, int(wide.sum()), int(kept.sum()))
+        dev = np.array([_rotation_angle(R, R64), _between(t, t64), np.abs(z[wide] / z1[wide] - 1.0).max()])
+        worst = np.maximum(worst, dev)
+        assert (dev <= FAMILY_TOLERANCES).all(), (name, dev)
+        assert abs(np.linalg.norm(r.pose[4:].astype(np.float64)) - 1.0) <= 1e-6 and abs(np.linalg.norm(r.pose[:4].astype(np.float64)) - 1.0) <= 1e-6
+        assert r.pose[0] >= 0, (name, r.pose)  # the contract's sign of q_rc
+        front64 = np.minimum(z1, z2)
+        band = MARGIN_MULTIPLE * FAMILY_MEASURED[2] * np.abs(front64).max()
+        sure, near = int((front64 > band).sum()), int((np.abs(front64) <= band).sum())
+        assert sure <= r.n_front.max() <= sure + near, (name, sure, near, r.n_front)
+        assert np.sort(r.n_front)[-2] <= (np.sort((fronts > -band).sum(1))[-2]), (name, r.n_front)
+        pixel_band = MARGIN_MULTIPLE * float(np.float32(P.K[0])) * (FAMILY_MEASURED[0] + FAMILY_MEASURED[1])
+        want = (front64 > 0) & (margin <= 0)
+        differ = kept != want
+        assert ((np.abs(margin[differ]) <= pixel_band) | (np.abs(front64[differ]) <= band)).all(), (name, margin[differ])
+        assert int(r.n_points[0]) == int(kept.sum()) and (r.status[part][~kept] == P.LARGE_RESIDUAL).all() and not r.points[part][~kept].any()
+        if name[2] > 0:
+            # noise: the reprojection test does reject.  How many is the scene's matter (the eight-point pose of noisy points is off by up
+            # to 6e-3 rad, 3 px, in float64 as here); that they are float64's is asserted above.
+            assert 8 <= kept.sum() < len(part), name
+            continue
+        assert kept.all(), name  # exact correspondences: every point is a landmark
+        Rt, tt = P.family_pose(name[0])
+        zt, _, _ = _depths64(Rt, tt / np.linalg.norm(tt), x1, x2)
+        err = np.array([_rotation_angle(R, Rt), _between(t, tt), np.abs(z[wide] / zt[wide] - 1.0).max()])
+        worst_truth = np.maximum(worst_truth, err)
+        assert (err <= FAMILY_TRUTH_TOLERANCES).all(), (name, err)
+    return worst, worst_truth
+
+
+def check_family_direct_projection(solve):
+    """check_direct_projection at every pose of the family: a quaternion that is not the candidate's rotation sends the points elsewhere."""
+    check_direct_projection(solve, over=family_scenes)
+
+
+def family_traces():
+    """The restatement's trace on every family scene and named case: [cases, 17]."""
+    cases = [(ref, cur, status) for _, ref, cur, status in family_scenes()] + [P.case(name) for name in NAMED_CASES]
+    return np.array([P.solve(*c).trace for c in cases])
+
+
+FAMILY_CHECKS = {"shepperd_x_branch_sign": check_family_direct_projection, "shepperd_y_branch_sign": check_family_direct_projection,
+                 "shepperd_z_branch_sign": check_family_direct_projection, "negation_to_w_positive_omitted": check_family_float64}
+
+
+@pytest.mark.parametrize("check", [check_family_float64, check_family_direct_projection], ids=lambda c: c.__name__)
+def test_the_restatement_passes_on_the_family(check):
+    check(_contract())
+
+
+def test_the_family_reaches_every_branch():
+    """A condition on the inputs, not a measurement: without it the checks above prove nothing about the paths they are there for."""
+    traces = family_traces()
+    taken = traces[traces[:, P.TRACE_WINNER] >= 0]
+    assert set(taken[:, P.TRACE_SHEPPERD]) == {0, 1, 2, 3} and set(taken[:, P.TRACE_NEGATED]) == {0, 1}
+    assert set(taken[:, P.TRACE_WINNER]) == {0, 1, 2, 3} and set(taken[:, P.TRACE_I1]) == {0, 1, 2}
+    paths = dict(zip(P.JACOBI_PATHS, traces[:, P.TRACE_JACOBI9].sum(0)))
+    print(paths, dict(zip(P.JACOBI_PATHS, traces[:, P.TRACE_JACOBI3].sum(0))))
+    assert all(count > 0 for count in paths.values()), paths
+    for (name, *_), trace in zip(family_scenes(), traces):  # the branch of every pose is the one the GPU and the filters' tests take it for
+        assert trace[P.TRACE_SHEPPERD] == P.SHEPPERD_BRANCH[name[0].split("/")[0]], name
+    assert [P.SHEPPERD_BRANCH[name.split("/")[0]] for name in P.SHEPPERD_POSES] == [0, 1, 2, 3]
+
+
+@pytest.mark.parametrize("mutant", sorted(P.FAMILY_MUTANTS))
+def test_each_family_mutant_is_caught_by_the_family_alone(mutant):
+    """A sign error in a branch of the quaternion, or w left negative: on the scenes of the one small motion the results are the contract's
+    bit for bit (the gap the family closes); on the family the named check fails."""
+    for _, ref, cur, status in scenes():
+        assert P.same_results(P.solve(ref, cur, status), P.solve(ref, cur, status, variant=P.FAMILY_MUTANTS[mutant])) == []
+    for check in (check_float64, check_ground_truth, check_direct_projection, check_tree):
+        check(_contract(P.FAMILY_MUTANTS[mutant]))
+    with pytest.raises(AssertionError):
+        FAMILY_CHECKS[mutant](_contract(P.FAMILY_MUTANTS[mutant]))
+
+
+def test_the_sweep_rule_on_the_family():
+    solve = functools.partial(P.solve, variant=P.CONTRACT)
+    check_sweep_rule(solve, S, over=family_scenes)
+    with pytest.raises(AssertionError):
+        check_sweep_rule(solve, S - 1, over=family_scenes)
+    # the family's scenes alone (the rule above also runs the named cases): how many differ from two sweeps more, by sweep count
+    differ = {sweeps: sum(P.same_results(solve(ref, cur, status, sweeps=sweeps), solve(ref, cur, status, sweeps=sweeps + 2), ("E", "pose", "n_front")) != []
+                          for _, ref, cur, status in family_scenes()) for sweeps in (S - 2, S - 1, S, S + 1)}
+    assert differ == {S - 2: 96, S - 1: 29, S: 0, S + 1: 0}, differ
+
+
+REFUSED_AT_NINE = ("small/side", "small/back", "small/forward", "z170/side", "z170/back", "z170/forward", "z-150/side", "z90/side", "z90/back",
+                   "z90/forward")
+
+
+def test_nine_point_cuts_below_the_floor_are_refused_though_float64_solves_them():
+    """A known limit of the float32 rank floor, asserted.  Ten of the family's 24 nine-point cuts have a float64 ratio below the floor (1.4e-7
+    ... 3.6e-7) and are refused, yet on each of them float64 recovers the pose the scene was made with, far inside the family's tolerances:
+    by DESIGN.md 5.29's own definition they are well-posed.  The floor cannot move below them: the squeezed scene at a factor 0.1, which is
+    to be refused as degenerate, has a ratio (2.2e-7) above the smallest of theirs, so no value separates the two kinds."""
+    refused = {}
+    for pose in P.FAMILY:
+        ref, cur, status = P.family_case(pose, 9)
+        ratio, r = _rank_ratio64(ref, cur, status), P.solve(ref, cur, status)
+        band = 4 * 2.0 ** -23  # as in test_the_rank_test_switches_at_its_floor; z-150/forward (1.27e-6) lies within it, and is valid
+        if ratio < RANK_FLOOR - band:
+            assert _invalid(r, status), (pose, ratio)
+            refused[pose] = ratio
+            R64, t64 = compose64(ref, cur, status)[:2]
+            Rt, tt = P.family_pose(pose)
+            assert _rotation_angle(R64, Rt) <= FAMILY_TRUTH_TOLERANCES[0] / 10 and _between(t64, tt) <= FAMILY_TRUTH_TOLERANCES[1] / 10, pose
+        else:
+            assert int(r.valid[0]) == 1 and int(r.n_points[0]) == 9 and (ratio > RANK_FLOOR + band or pose == "z-150/forward"), (pose, ratio)
+    assert tuple(refused) == REFUSED_AT_NINE and 1.3e-7 <= min(refused.values()) and max(refused.values()) <= 3.7e-7, refused
+    degenerate = _rank_ratio64(*P.case("squeezed10"))
+    assert _invalid(P.solve(*P.case("squeezed10")), P.case("squeezed10")[2]) and min(refused.values()) < degenerate < RANK_FLOOR, degenerate
+
+
+def test_big_scene_with_a_pose_is_a_scene_of_that_pose():
+    pose = P.family_pose("z170/side")
+    ref, cur = P.big_scene(1000, 400, pose=pose)
+    for uv in (ref, cur):
+        assert uv.shape == (1000, 2) and (uv >= 5).all() and (uv[:, 0] <= P.IMAGE[1] - 5).all() and (uv[:, 1] <= P.IMAGE[0] - 5).all()
+    r = P.solve(ref, cur, np.full(1000, P.TRACKED, np.uint8))
+    R, t = _pose64(r)
+    assert int(r.n_points[0]) == 1000 and _rotation_angle(R, pose[0]) <= FAMILY_TRUTH_TOLERANCES[0] and _between(t, pose[1]) <= FAMILY_TRUTH_TOLERANCES[1]
+    assert r.points[:, 2].min() >= P.E.SCENE_MIN_DEPTH / np.linalg.norm(pose[1])  # depths in units of the baseline
+
+
+def test_the_family_stands_above_the_rank_floor():
+    ratios = {name: _rank_ratio64(ref, cur, status) for name, ref, cur, status in family_scenes()}
+    lowest = min(ratios, key=ratios.get)
+    print(f"smallest second eigenvalue over the largest: {ratios[lowest]:.3e} on {lowest}, the floor {RANK_FLOOR:.3e}")
+    assert ratios[lowest] > RANK_FLOOR, (lowest, ratios[lowest])
+
+
+def test_the_family_tolerances_are_the_measured_deviations_with_their_margin():
+    worst, truth = check_family_float64(_contract())
+    print("against float64: " + " ".join(f"{v:.3e}" for v in worst) + "; against truth: " + " ".join(f"{v:.3e}" for v in truth))
+    for tolerance, measured in zip(FAMILY_TOLERANCES + FAMILY_TRUTH_TOLERANCES, tuple(worst) + tuple(truth)):
+        assert tolerance / 8 <= measured <= tolerance

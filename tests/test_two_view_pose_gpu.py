@@ -38,6 +38,41 @@ def test_bit_identity_with_the_restatement(ftk, name):
     assert P.same_results(_device(ftk, ref, cur, status), want) == [], name
 
 
+# The pose family: every pose at 300 points (two tiles); a pose per branch of the quaternion at 9 and 257 points, through a
+# second camera, and with 0.3 px noise at a 0.5 px threshold.  (pose, points, noise, arguments of the call)
+FAMILY_CASES = ([(pose, 300, 0.0, {}) for pose in P.FAMILY] + [(pose, 9, 0.0, {}) for pose in P.SHEPPERD_POSES_N9]
+                + [(pose, 257, 0.0, {}) for pose in P.SHEPPERD_POSES]
+                + [(pose, 300, 0.0, dict(K_cur=P.K_OTHER)) for pose in P.SHEPPERD_POSES]
+                + [(pose, 300, 0.3, dict(threshold=0.5)) for pose in P.SHEPPERD_POSES])
+
+
+REFUSED = ("small/side", 9)  # by the rank test (tests/two_view_pose_ref.py); branch 0 at nine points is the case n9 above
+
+
+def _family_id(case):
+    pose, n, noise, kw = case
+    return f"{pose}-n{n}" + ("-noise" if noise else "") + "".join(f"-{k}" for k in kw)
+
+
+@pytest.mark.parametrize("case", FAMILY_CASES, ids=_family_id)
+def test_bit_identity_on_the_pose_family(ftk, case):
+    pose, n, noise, kw = case
+    ref, cur, status = P.family_case(pose, n, noise)
+    want = P.solve(ref, cur, status, **kw)
+    assert int(want.valid[0]) == (-1 if (pose, n) == REFUSED else 1)
+    assert P.same_results(_device(ftk, ref, cur, status, **kw), want) == [], case
+
+
+def test_the_family_cases_reach_every_branch_of_the_quaternion_and_every_winner():
+    """By the restatement's trace: a list pruned of a branch, of either outcome of the negation or of a winner fails here.  Each of the
+    poses taken for a branch is on that branch at every size and in every call it is taken with."""
+    traces = {_family_id(c): P.solve(*P.family_case(*c[:3]), **c[3]).trace for c in FAMILY_CASES}
+    seen = np.array([t for t in traces.values() if t[P.TRACE_WINNER] >= 0])
+    assert set(seen[:, P.TRACE_SHEPPERD]) == {0, 1, 2, 3} and set(seen[:, P.TRACE_NEGATED]) == {0, 1} and set(seen[:, P.TRACE_WINNER]) == {0, 1, 2, 3}
+    for c in FAMILY_CASES:
+        assert traces[_family_id(c)][P.TRACE_SHEPPERD] == (-1 if c[:2] == REFUSED else P.SHEPPERD_BRANCH[c[0].split("/")[0]]), c
+
+
 @pytest.mark.parametrize("name", P.HOSTILE_CASES)
 def test_hostile_and_degenerate_inputs(ftk, name):
     ref, cur, status = P.case(name)
@@ -99,6 +134,21 @@ def test_filter_then_solve_equals_the_two_restatements_composed(ftk):
     filtered = T.ransac(ref, cur, status, E.IMAGE, 1.0, 512, 1, "fundamental")
     want = P.solve(ref, cur, filtered.status)
     assert int(fit.model.item()) == 0 and int(want.valid[0]) == 1 and int(want.n_points[0]) >= 150
+    assert P.same_results(_host(d_status, out), want) == []
+
+
+def test_filter_then_solve_on_a_half_turn_equals_the_two_restatements_composed(ftk):
+    """The same composition at x170/side: the filter in front and the quaternion's x branch behind it, 30 % outliers, 0.3 px noise."""
+    import torch
+    ref, cur, _, _ = P.family_scene("x170/side", 300, 1, noise=0.3, outlier_share=0.3)
+    status = np.full(300, P.TRACKED, np.uint8)
+    d_ref, d_cur, d_status = torch.from_numpy(ref).cuda(), torch.from_numpy(cur).cuda(), torch.from_numpy(status).cuda()
+    fit = ftk.TwoViewRansac("fundamental", hypotheses=512, threshold=1.0, seed=1).filter(d_ref, d_cur, d_status, E.IMAGE)
+    out = ftk.TwoViewPose(P.K, threshold=1.0).solve(d_ref, d_cur, d_status)
+    torch.cuda.synchronize()
+    filtered = T.ransac(ref, cur, status, E.IMAGE, 1.0, 512, 1, "fundamental")
+    want = P.solve(ref, cur, filtered.status)
+    assert int(fit.model.item()) == 0 and int(want.valid[0]) == 1 and int(want.n_points[0]) >= 150 and want.trace[P.TRACE_SHEPPERD] == 1
     assert P.same_results(_host(d_status, out), want) == []
 
 

@@ -4,7 +4,8 @@
  * contraction (tests/ref_build.py's STRICT flags); `/` and sqrtf are correctly rounded.  The device (csrc/two_view_pose_kernels.hip) is held
  * to this file bit for bit by tests/test_two_view_pose_gpu.py; tests/test_two_view_pose_cpu.py pins this file to an independent float64
  * composition, to ground truth and to the projection of DirectMethod.  `variant` 0 is the contract; the others are the mutants that the CPU
- * tests must catch.  `sweeps` is a parameter so that the rule which fixed FTK_POSE_JACOBI_SWEEPS can be asserted.
+ * tests must catch.  `sweeps` is a parameter so that the rule which fixed FTK_POSE_JACOBI_SWEEPS can be asserted.  `trace` (may be NULL)
+ * records which way every data-dependent choice went; it reads values the contract computes and changes none of them.
  */
 #include <math.h>
 #include <stdint.h>
@@ -14,7 +15,12 @@
 #define LARGE_RESIDUAL 2
 #define TILE 256
 
-enum { CONTRACT = 0, TWISTED_PAIR = 1, T_WRONG_SIGN = 2, E_TRANSPOSED = 3, SEQUENTIAL_SUM = 4, REPROJECTION_UNSCALED = 5 };
+enum { CONTRACT = 0, TWISTED_PAIR = 1, T_WRONG_SIGN = 2, E_TRANSPOSED = 3, SEQUENTIAL_SUM = 4, REPROJECTION_UNSCALED = 5,
+       SHEPPERD_X_SIGN = 6, SHEPPERD_Y_SIGN = 7, SHEPPERD_Z_SIGN = 8, NO_NEGATION = 9 };
+
+/* The trace: 7 choices (-1 where the call ended before making them), then the pairs of the 9 x 9 and of the 3 x 3 Jacobi by the path taken. */
+enum { TR_K = 0, TR_K2, TR_I1, TR_I2, TR_WINNER, TR_SHEPPERD, TR_NEGATED, TR_JACOBI9, TR_JACOBI3 = TR_JACOBI9 + 5, TR_LENGTH = TR_JACOBI3 + 5 };
+enum { J_ZERO = 0, J_NEGLIGIBLE, J_APQ_OVER_H, J_THETA_POSITIVE, J_THETA_NEGATIVE };
 
 static int finite32(float v) {
     uint32_t u;
@@ -23,29 +29,36 @@ static int finite32(float v) {
 }
 
 /* Cyclic Jacobi on the symmetric n x n matrix a (full storage, row-major, destroyed; its diagonal ends as the eigenvalues), eigenvectors
- * accumulated in the columns of v.  Pairs (p, q), p < q, in row-major order; `sweeps` sweeps, all of them. */
-static void jacobi_eigen(int n, float *a, float *v, int sweeps) {
+ * accumulated in the columns of v.  Pairs (p, q), p < q, in row-major order; `sweeps` sweeps, all of them.  paths (may be NULL) counts the
+ * pairs by the path they took. */
+static void jacobi_eigen(int n, float *a, float *v, int sweeps, int32_t *paths) {
     for (int i = 0; i < n; ++i)
         for (int j = 0; j < n; ++j) v[i * n + j] = i == j ? 1.0f : 0.0f;
     for (int sweep = 0; sweep < sweeps; ++sweep) {
         for (int p = 0; p < n - 1; ++p) {
             for (int q = p + 1; q < n; ++q) {
                 const float apq = a[p * n + q], app = a[p * n + p], aqq = a[q * n + q];
-                if (apq == 0.0f) continue;
+                if (apq == 0.0f) {
+                    if (paths) ++paths[J_ZERO];
+                    continue;
+                }
                 const float g = 100.0f * fabsf(apq);
                 if (fabsf(app) + g == fabsf(app) && fabsf(aqq) + g == fabsf(aqq)) { /* negligible: set to zero, no rotation */
                     a[p * n + q] = 0.0f;
                     a[q * n + p] = 0.0f;
+                    if (paths) ++paths[J_NEGLIGIBLE];
                     continue;
                 }
                 const float h = aqq - app;
                 float t;
                 if (fabsf(h) + g == fabsf(h)) {
                     t = apq / h;
+                    if (paths) ++paths[J_APQ_OVER_H];
                 } else {
                     const float theta = h / (2.0f * apq);
                     t = 1.0f / (fabsf(theta) + sqrtf(theta * theta + 1.0f));
                     if (theta < 0.0f) t = -t;
+                    if (paths) ++paths[theta < 0.0f ? J_THETA_NEGATIVE : J_THETA_POSITIVE];
                 }
                 const float c = 1.0f / sqrtf(t * t + 1.0f);
                 const float s = t * c;
@@ -103,9 +116,11 @@ static int in_front(const float R[9], const float t[3], const float q[4], float 
     return finite32(*z1) && finite32(*z2) && *z1 > 0.0f && *z2 > 0.0f;
 }
 
-/* K8 = (fx, fy, cx, cy) of the reference view, then of the current view.  a45 (may be NULL) receives the 45 sums. */
+/* K8 = (fx, fy, cx, cy) of the reference view, then of the current view.  a45 (may be NULL) receives the 45 sums, trace (may be NULL) the
+ * TR_LENGTH entries of the trace. */
 int tvp_solve(const float *ref_uv, const float *cur_uv, uint8_t *status, int32_t n, const float *K8, float threshold, float baseline, int32_t sweeps,
-              int32_t variant, float *pose, float *points, float *E_out, int32_t *n_front, int32_t *valid, int32_t *n_points, float *a45) {
+              int32_t variant, float *pose, float *points, float *E_out, int32_t *n_front, int32_t *valid, int32_t *n_points, float *a45,
+              int32_t *trace) {
     if (n < 1 || n > 65536 || sweeps < 0) return -1;
     static float pts[65536][4];
     const float fx1 = K8[0], fy1 = K8[1], cx1 = K8[2], cy1 = K8[3], fx2 = K8[4], fy2 = K8[5], cx2 = K8[6], cy2 = K8[7];
@@ -130,6 +145,10 @@ int tvp_solve(const float *ref_uv, const float *cur_uv, uint8_t *status, int32_t
     *valid = -1;
     *n_points = 0;
     if (a45) memset(a45, 0, sizeof(float) * 45);
+    if (trace) {
+        for (int i = 0; i < TR_JACOBI9; ++i) trace[i] = -1;
+        for (int i = TR_JACOBI9; i < TR_LENGTH; ++i) trace[i] = 0;
+    }
     if (m < 8) return 0;
     /* 2. the 45 sums: tiles of 256 positions, a tree within the tile, tile totals in ascending order from +0 */
     float sums[45];
@@ -170,7 +189,7 @@ int tvp_solve(const float *ref_uv, const float *cur_uv, uint8_t *status, int32_t
         for (int a = 0; a < 9; ++a)
             for (int b = a; b < 9; ++b, ++e) A[a * 9 + b] = A[b * 9 + a] = sums[e];
     }
-    jacobi_eigen(9, A, V, sweeps);
+    jacobi_eigen(9, A, V, sweeps, trace ? trace + TR_JACOBI9 : 0);
     int k = 0;
     for (int j = 1; j < 9; ++j)
         if (A[j * 9 + j] < A[k * 9 + k]) k = j;
@@ -195,13 +214,14 @@ int tvp_solve(const float *ref_uv, const float *cur_uv, uint8_t *status, int32_t
     float G[9], W[9];
     for (int i = 0; i < 3; ++i)
         for (int j = 0; j < 3; ++j) G[i * 3 + j] = (E[i] * E[j] + E[3 + i] * E[3 + j]) + E[6 + i] * E[6 + j];
-    jacobi_eigen(3, G, W, sweeps);
+    jacobi_eigen(3, G, W, sweeps, trace ? trace + TR_JACOBI3 : 0);
     const float l0 = G[0], l1 = G[4], l2 = G[8];
     int i1 = 0;
     if (l1 > l0) i1 = 1;
     if (l2 > (i1 == 0 ? l0 : l1)) i1 = 2;
     const int ia = i1 == 0 ? 1 : 0, ib = i1 == 2 ? 1 : 2; /* the other two, ascending */
     const int i2 = G[ib * 4] > G[ia * 4] ? ib : ia;
+    if (trace) trace[TR_K] = k, trace[TR_K2] = k2, trace[TR_I1] = i1, trace[TR_I2] = i2;
     const float s1 = sqrtf(G[i1 * 4]), s2 = sqrtf(G[i2 * 4]);
     float v1[3], v2[3], v3[3], u1[3], u2[3], u3[3];
     for (int i = 0; i < 3; ++i) v1[i] = W[i * 3 + i1], v2[i] = W[i * 3 + i2];
@@ -235,6 +255,7 @@ int tvp_solve(const float *ref_uv, const float *cur_uv, uint8_t *status, int32_t
     for (int c = 1; c < 4; ++c)
         if (n_front[c] > n_front[win]) win = c;
     if (n_front[win] <= 0) return 0;
+    if (trace) trace[TR_WINNER] = win;
     /* 6. the pose in DirectMethod's convention: R_rc = R^T, p_rc = -R^T t scaled to the baseline */
     int out = win;
     if (variant == TWISTED_PAIR) out = win ^ 2;
@@ -249,20 +270,29 @@ int tvp_solve(const float *ref_uv, const float *cur_uv, uint8_t *status, int32_t
     const float m00 = R[0], m01 = R[3], m02 = R[6], m10 = R[1], m11 = R[4], m12 = R[7], m20 = R[2], m21 = R[5], m22 = R[8];
     const float tr = (m00 + m11) + m22;
     float qw, qx, qy, qz;
+    int branch = 0;
     if (tr > 0.0f) {
         const float s = sqrtf(tr + 1.0f) * 2.0f;
         qw = 0.25f * s, qx = (m21 - m12) / s, qy = (m02 - m20) / s, qz = (m10 - m01) / s;
     } else if (m00 > m11 && m00 > m22) {
         const float s = sqrtf(((1.0f + m00) - m11) - m22) * 2.0f;
         qw = (m21 - m12) / s, qx = 0.25f * s, qy = (m01 + m10) / s, qz = (m02 + m20) / s;
+        if (variant == SHEPPERD_X_SIGN) qy = (m01 - m10) / s;
+        branch = 1;
     } else if (m11 > m22) {
         const float s = sqrtf(((1.0f + m11) - m00) - m22) * 2.0f;
         qw = (m02 - m20) / s, qx = (m01 + m10) / s, qy = 0.25f * s, qz = (m12 + m21) / s;
+        if (variant == SHEPPERD_Y_SIGN) qz = (m12 - m21) / s;
+        branch = 2;
     } else {
         const float s = sqrtf(((1.0f + m22) - m00) - m11) * 2.0f;
         qw = (m10 - m01) / s, qx = (m02 + m20) / s, qy = (m12 + m21) / s, qz = 0.25f * s;
+        if (variant == SHEPPERD_Z_SIGN) qx = (m02 - m20) / s;
+        branch = 3;
     }
-    if (qw < 0.0f) qw = -qw, qx = -qx, qy = -qy, qz = -qz;
+    const int negate = qw < 0.0f;
+    if (negate && variant != NO_NEGATION) qw = -qw, qx = -qx, qy = -qy, qz = -qz;
+    if (trace) trace[TR_SHEPPERD] = branch, trace[TR_NEGATED] = negate;
     const float qn = sqrtf(((qw * qw + qx * qx) + qy * qy) + qz * qz);
     ps[0] = qw / qn, ps[1] = qx / qn, ps[2] = qy / qn, ps[3] = qz / qn;
     for (int i = 0; i < 7; ++i) ok = ok && finite32(ps[i]);

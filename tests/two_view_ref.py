@@ -105,16 +105,38 @@ PATCH_BOX = (380.0, 150.0, 520.0, 290.0)  # (u0, v0, u1, v1) of the patch in the
 PATCH_SHIFT = (5.6, -4.2)                 # 7 px on top of the background's motion
 
 
-@functools.lru_cache(maxsize=None)
-def planar_scene(n, seed, camera="moving", noise=0.0, patch_share=0.15, image=IMAGE):
+def planar_scene(n, seed, camera="moving", noise=0.0, patch_share=0.15, image=IMAGE, pose=None):
     """Scene A: one plane seen by a camera that translates and rolls ("moving") or does not move at all ("static"): (ref_uv, cur_uv,
     on_patch, H64).  The first round(n * patch_share) points lie in PATCH_BOX and move a further PATCH_SHIFT; the others lie outside it.
-    ``noise``: Gaussian sigma in pixels on every cur."""
+    ``noise``: Gaussian sigma in pixels on every cur.  ``pose`` = (R, t) with X_cur = R X_ref + t replaces the moving camera's motion; the
+    plane then passes through tests/epipolar_ref.py's SCENE_CENTRE, and a point is kept when it is SCENE_MIN_DEPTH deep in both views and
+    5 px inside the current image (a patch point: with its shift)."""
+    return _planar_scene(n, seed, camera, noise, patch_share, image, E.pose_key(pose))
+
+
+@functools.lru_cache(maxsize=None)
+def _planar_scene(n, seed, camera, noise, patch_share, image, pose):
     rng = np.random.default_rng(seed)
     Hh, W = image
     f = 0.8 * W
     Kc = np.array([[f, 0, 0.5 * (W - 1)], [0, f, 0.5 * (Hh - 1)], [0, 0, 1.0]])
-    if camera == "moving":
+    seen = lambda uv, patch: True  # noqa: E731
+    if pose is not None:
+        assert camera == "moving"
+        R, t = np.array(pose[0]).reshape(3, 3), np.array(pose[1])
+        normal = np.array([0.1, -0.2, 1.0]) / np.linalg.norm([0.1, -0.2, 1.0])
+        d = float(normal @ np.array(E.SCENE_CENTRE))
+        H = Kc @ (R + np.outer(t, normal) / d) @ np.linalg.inv(Kc)
+
+        def seen(uv, patch):
+            ray = np.linalg.inv(Kc) @ np.array([uv[0], uv[1], 1.0])
+            X = ray * (d / (normal @ ray))
+            Y = R @ X + t
+            if X[2] < E.SCENE_MIN_DEPTH or Y[2] < E.SCENE_MIN_DEPTH:
+                return False
+            x2 = (Kc @ Y)[:2] / Y[2] + (np.array(PATCH_SHIFT) if patch else 0.0)
+            return 5 <= x2[0] <= W - 5 and 5 <= x2[1] <= Hh - 5
+    elif camera == "moving":
         roll = 0.02
         R = np.array([[np.cos(roll), -np.sin(roll), 0], [np.sin(roll), np.cos(roll), 0], [0, 0, 1.0]])
         t, normal, d = np.array([0.3, 0.05, 0.1]), np.array([0.1, -0.2, 1.0]), 5.0
@@ -126,14 +148,18 @@ def planar_scene(n, seed, camera="moving", noise=0.0, patch_share=0.15, image=IM
     n_patch = int(round(n * patch_share))
     u0, v0, u1, v1 = PATCH_BOX
     ref = np.zeros((n, 2))
-    k = 0
+    k = draws = 0
     while k < n:
+        draws += 1
+        assert draws <= 1000 * n, "the pose leaves too little of the plane in view"
         if k < n_patch:
             uv = rng.uniform([u0, v0], [u1, v1])
         else:
             uv = rng.uniform([10, 10], [W - 10, Hh - 10])
             if u0 - 2 <= uv[0] <= u1 + 2 and v0 - 2 <= uv[1] <= v1 + 2:
                 continue
+        if not seen(uv, k < n_patch):
+            continue
         ref[k] = uv
         k += 1
     x = (H @ np.c_[ref, np.ones(n)].T).T
