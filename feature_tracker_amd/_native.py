@@ -361,12 +361,16 @@ def flow_warm_splits(B: int, H: int, W: int) -> int:
     return splits.value
 
 
+def _up16(v: int) -> int:
+    """v rounded up to a multiple of 16: what a block of v bytes occupies in a caller-owned workspace (csrc/ftk_layout.h's 16-byte slots)."""
+    return (v + 15) & ~15
+
+
 def _ransac_workspace_bytes(n: int, hypotheses: int, slots: int) -> int:
     """csrc/two_view_plan.cpp's workspace: M, then the participants' normalised coordinates, their indices, and per slot counts, models and
     validity flags, each block rounded up to 16 bytes."""
     n, k = int(n), slots * int(hypotheses)
-    up16 = lambda v: (v + 15) & ~15  # noqa: E731
-    return 16 + up16(16 * n) + up16(4 * n) + up16(4 * k) + up16(36 * k) + up16(k)
+    return 16 + _up16(16 * n) + _up16(4 * n) + _up16(4 * k) + _up16(36 * k) + _up16(k)
 
 
 def epipolar_workspace_bytes(n: int, hypotheses: int) -> int:
@@ -385,8 +389,7 @@ def two_view_pose_workspace_bytes(n: int) -> int:
     """Bytes of workspace ftk_two_view_pose_device needs, the value ftk_two_view_pose_workspace_bytes returns (pure Python;
     csrc/two_view_pose_plan.cpp): M, the participants' calibrated coordinates, 45 totals per tile of FTK_POSE_TILE points, the model block."""
     n = int(n)
-    up16 = lambda v: (v + 15) & ~15  # noqa: E731
-    return 16 + up16(16 * n) + up16(4 * 45 * -(-n // FTK_POSE_TILE)) + 128
+    return 16 + _up16(16 * n) + _up16(4 * 45 * -(-n // FTK_POSE_TILE)) + 128
 
 
 def keypoint_decode_workspace_bytes(cell_rows: int, cell_cols: int, min_distance: int, n_occupied: int = 0) -> int:
@@ -396,17 +399,15 @@ def keypoint_decode_workspace_bytes(cell_rows: int, cell_cols: int, min_distance
     px = 64 * int(cell_rows) * int(cell_cols)
     d = max(int(min_distance), 1)
     capacity = -(-8 * int(cell_rows) // d) * -(-8 * int(cell_cols) // d)
-    up16 = lambda v: (v + 15) & ~15  # noqa: E731
-    return 3 * up16(8 * px) + up16(8 * capacity) + 16 + (2 * up16(px) if int(n_occupied) > 0 else 0)
+    return 3 * _up16(8 * px) + _up16(8 * capacity) + 16 + (2 * _up16(px) if int(n_occupied) > 0 else 0)
 
 
 def match_assignment_workspace_bytes(rows0: int, rows1: int, dim: int, with_weights: bool) -> int:
     """Bytes of workspace ftk_match_assignment_device needs, the value ftk_match_assignment_workspace_bytes returns (pure Python;
     csrc/match_assignment_plan.cpp): the two normalisers, and with weights the projected descriptors, z and ls(z), ls(-z) of both sides."""
     m, n, d = int(rows0), int(rows1), int(dim)
-    up16 = lambda v: (v + 15) & ~15  # noqa: E731
-    own = up16(4 * m) + up16(4 * n)
-    return own + (up16(4 * (m + n) * d) + up16(4 * (m + n)) + up16(8 * m) + up16(8 * n) if with_weights else 0)
+    own = _up16(4 * m) + _up16(4 * n)
+    return own + (_up16(4 * (m + n) * d) + _up16(4 * (m + n)) + _up16(8 * m) + _up16(8 * n) if with_weights else 0)
 
 
 def transformer_layer_workspace_bytes(rows0: int, rows1: int, dim: int, heads: int = 4) -> int:
@@ -423,8 +424,7 @@ def transformer_layer_workspace_bytes(rows0: int, rows1: int, dim: int, heads: i
     if (d // h) % 2 != 0 or not 2 <= d // h <= FTK_TRANSFORMER_MAX_HEAD_DIM:
         raise ValueError(f"the head dimension must be even and in 2 .. FTK_TRANSFORMER_MAX_HEAD_DIM = {FTK_TRANSFORMER_MAX_HEAD_DIM} (got {d // h})")
     r = m + n
-    up16 = lambda v: (v + 15) & ~15  # noqa: E731
-    return up16(12 * r * d) + 3 * up16(4 * r * d) + up16(8 * r * d)
+    return _up16(12 * r * d) + 3 * _up16(4 * r * d) + _up16(8 * r * d)
 
 
 def lightglue_adaptive_workspace_bytes(rows0: int, rows1: int, dim: int, heads: int = 4) -> int:
@@ -432,9 +432,8 @@ def lightglue_adaptive_workspace_bytes(rows0: int, rows1: int, dim: int, heads: 
     csrc/lightglue_adaptive_plan.cpp): the layer's workspace, the assignment head's, the selected head [D + 1][D] and [D + 1], the gather
     maps [M] and [N], and the matcher's index and status [M].  ValueError for a shape the library refuses."""
     m, n, d = int(rows0), int(rows1), int(dim)
-    up16 = lambda v: (v + 15) & ~15  # noqa: E731
-    return (up16(transformer_layer_workspace_bytes(m, n, d, heads)) + up16(match_assignment_workspace_bytes(m, n, d, True)) + up16(4 * (d + 1) * d)
-            + up16(4 * (d + 1)) + 2 * up16(4 * m) + up16(4 * n) + up16(m))
+    return (_up16(transformer_layer_workspace_bytes(m, n, d, heads)) + _up16(match_assignment_workspace_bytes(m, n, d, True)) + _up16(4 * (d + 1) * d)
+            + _up16(4 * (d + 1)) + 2 * _up16(4 * m) + _up16(4 * n) + _up16(m))
 
 
 def match_table_workspace_bytes(n_slots: int, rows_cur: int, dim: int) -> int:

@@ -136,6 +136,25 @@ struct ftk_pyramid {
 // Records the message on the context (or, with ctx == nullptr, for ftk_last_error(NULL)) and returns `code`.
 int ftk_fail(ftk_context *ctx, int code, const char *fmt, ...);
 
+// The argument checks the entries share.  A null pointer is aligned: "may be null" and "must be aligned" are separate questions.
+inline bool ftk_aligned(const void *p, uintptr_t to) { return (reinterpret_cast<uintptr_t>(p) & (to - 1)) == 0; }
+inline bool ftk_finite(float v) { return v - v == 0.0f; }  // false for NaN and the infinities alone
+inline bool ftk_positive(float v) { return v > 0.0f && ftk_finite(v); }
+
+// The body of every ftk_*_workspace_bytes entry: `plan_call(&plan)` plans the call and answers FTK_OK or the refusal it has recorded.
+template <class Plan, class PlanCall>
+int ftk_workspace_bytes(const char *who, int64_t *bytes, PlanCall plan_call) {
+    if (!bytes) {
+        return ftk_fail(nullptr, FTK_E_INVALID_ARGUMENT, "%s: null argument", who);
+    }
+    Plan plan;
+    const int rc = plan_call(&plan);
+    if (rc == FTK_OK) {
+        *bytes = (int64_t)plan.bytes;
+    }
+    return rc;
+}
+
 #define FTK_HIP(ctx, expr)                                                                                   \
     do {                                                                                                     \
         hipError_t e_ = (expr);                                                                              \

@@ -39,23 +39,14 @@ int plan_call(ftk_context *ctx, const char *who, int32_t cell_rows, int32_t cell
     }
 }
 
-bool aligned(const void *p, uintptr_t to) { return (reinterpret_cast<uintptr_t>(p) & (to - 1)) == 0; }
-
 }  // namespace
 
 extern "C" {
 
 int ftk_keypoint_decode_workspace_bytes(int32_t cell_rows, int32_t cell_cols, int32_t min_distance, int32_t n_occupied, int64_t *bytes) {
-    if (!bytes) {
-        return ftk_fail(nullptr, FTK_E_INVALID_ARGUMENT, "keypoint_decode_workspace_bytes: null argument");
-    }
-    ftk::KeypointDecodePlan plan;
-    const int rc = plan_call(nullptr, "keypoint_decode_workspace_bytes", cell_rows, cell_cols, 1, 1, min_distance, 0, n_occupied, &plan);
-    if (rc != FTK_OK) {
-        return rc;
-    }
-    *bytes = (int64_t)plan.bytes;
-    return FTK_OK;
+    const char *who = "keypoint_decode_workspace_bytes";
+    return ftk_workspace_bytes<ftk::KeypointDecodePlan>(
+        who, bytes, [&](ftk::KeypointDecodePlan *plan) { return plan_call(nullptr, who, cell_rows, cell_cols, 1, 1, min_distance, 0, n_occupied, plan); });
 }
 
 int ftk_keypoint_decode_device(ftk_context *ctx, void *stream, const float *d_semi, int32_t cell_rows, int32_t cell_cols, const float *d_desc,
@@ -82,33 +73,32 @@ int ftk_keypoint_decode_device(ftk_context *ctx, void *stream, const float *d_se
         return ftk_fail(ctx, FTK_E_INVALID_ARGUMENT, "keypoint_decode_device: the descriptor strides (%lld, %lld, %lld) must not be negative",
                         (long long)desc_stride_c, (long long)desc_stride_y, (long long)desc_stride_x);
     }
-    if (!aligned(d_workspace, 16) || !aligned(d_uv, 8) || !aligned(d_semi, 4) || !aligned(d_desc, 4) || !aligned(d_scores, 4) ||
-        !aligned(d_descriptors, 4) || !aligned(d_count, 4) || !aligned(d_heatmap, 4)) {
+    if (!ftk_aligned(d_workspace, 16) || !ftk_aligned(d_uv, 8) || !ftk_aligned(d_semi, 4) || !ftk_aligned(d_desc, 4) || !ftk_aligned(d_scores, 4) ||
+        !ftk_aligned(d_descriptors, 4) || !ftk_aligned(d_count, 4) || !ftk_aligned(d_heatmap, 4)) {
         return ftk_fail(ctx, FTK_E_INVALID_ARGUMENT, "keypoint_decode_device: the workspace must be 16-byte aligned, d_uv 8-byte, the others 4-byte");
     }
-    uint8_t *ws = static_cast<uint8_t *>(d_workspace);
     ftk::KeypointDecodeParams p{};
     p.score.semi = d_semi;
     p.score.cell_rows = cell_rows;
     p.score.cell_cols = cell_cols;
     p.score.min_score = min_score;
     p.score.border = border;
-    p.score.key = reinterpret_cast<unsigned long long *>(ws);
+    p.score.key = plan.key.in(d_workspace);
     p.score.heatmap = d_heatmap;
     p.select.rows = plan.rows;
     p.select.cols = plan.cols;
     p.select.reach = plan.reach;
     p.select.key = p.score.key;
-    p.select.tmp = reinterpret_cast<unsigned long long *>(ws + plan.off_tmp);
-    p.select.wmax = reinterpret_cast<unsigned long long *>(ws + plan.off_wmax);
-    p.select.list = reinterpret_cast<unsigned long long *>(ws + plan.off_list);
-    p.select.count = reinterpret_cast<unsigned *>(ws + plan.off_count);
+    p.select.tmp = plan.tmp.in(d_workspace);
+    p.select.wmax = plan.wmax.in(d_workspace);
+    p.select.list = plan.list.in(d_workspace);
+    p.select.count = plan.count.in(d_workspace);
     p.select.capacity = (unsigned)plan.capacity;
     p.occupied.uv = d_occupied_uv;
     p.occupied.flags = d_occupied_flags;
     p.occupied.n = n_occupied;
-    p.occupied.plane = n_occupied > 0 ? ws + plan.off_plane : nullptr;
-    p.occupied.dilated = n_occupied > 0 ? ws + plan.off_dilated : nullptr;
+    p.occupied.plane = n_occupied > 0 ? plan.plane.in(d_workspace) : nullptr;
+    p.occupied.dilated = n_occupied > 0 ? plan.dilated.in(d_workspace) : nullptr;
     p.rank.list = p.select.list;
     p.rank.count = p.select.count;
     p.rank.capacity = p.select.capacity;

@@ -23,8 +23,7 @@ int plan_call(ftk_context *ctx, const char *who, int32_t rows0, int32_t rows1, i
     return FTK_OK;
 }
 
-bool aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
-bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+bool aligned4(const void *p) { return ftk_aligned(p, 4); }
 bool unit_interval(float v) { return v >= 0.0f && v <= 1.0f; }
 
 }  // namespace
@@ -32,16 +31,8 @@ bool unit_interval(float v) { return v >= 0.0f && v <= 1.0f; }
 extern "C" {
 
 int ftk_lightglue_adaptive_workspace_bytes(int32_t rows0, int32_t rows1, int32_t dim, int32_t heads, int64_t *bytes) {
-    if (!bytes) {
-        return ftk_fail(nullptr, FTK_E_INVALID_ARGUMENT, "lightglue_adaptive_workspace_bytes: null argument");
-    }
-    ftk::LightglueAdaptivePlan plan;
-    const int rc = plan_call(nullptr, "lightglue_adaptive_workspace_bytes", rows0, rows1, dim, heads, &plan);
-    if (rc != FTK_OK) {
-        return rc;
-    }
-    *bytes = (int64_t)plan.bytes;
-    return FTK_OK;
+    const char *who = "lightglue_adaptive_workspace_bytes";
+    return ftk_workspace_bytes<ftk::LightglueAdaptivePlan>(who, bytes, [&](ftk::LightglueAdaptivePlan *plan) { return plan_call(nullptr, who, rows0, rows1, dim, heads, plan); });
 }
 
 int ftk_lightglue_confidence_device(ftk_context *ctx, void *stream, const float *d_desc0, int32_t rows0, const float *d_desc1, int32_t rows1, int32_t dim,
@@ -103,14 +94,13 @@ int ftk_lightglue_adapt_step_device(ftk_context *ctx, void *stream, int32_t rows
             return ftk_fail(ctx, FTK_E_INVALID_ARGUMENT, "lightglue_adapt_step_device: null or misaligned buffer (4 bytes; the workspace 16)");
         }
     }
-    if (!aligned16(d_workspace) || !aligned4(d_count0) || !aligned4(d_count1)) {
+    if (!ftk_aligned(d_workspace, 16) || !aligned4(d_count0) || !aligned4(d_count1)) {
         return ftk_fail(ctx, FTK_E_INVALID_ARGUMENT, "lightglue_adapt_step_device: null or misaligned buffer (4 bytes; the workspace 16)");
     }
     if (d_desc_in0 == d_desc_out0 || d_desc_in1 == d_desc_out1 || d_enc_in0 == d_enc_out0 || d_enc_in1 == d_enc_out1 || d_ind_in0 == d_ind_out0 ||
         d_ind_in1 == d_ind_out1) {
         return ftk_fail(ctx, FTK_E_INVALID_ARGUMENT, "lightglue_adapt_step_device: the gather is not in place: the outputs are the other half of a pair");
     }
-    uint8_t *ws = static_cast<uint8_t *>(d_workspace);
     ftk::AdaptStepParams p{};
     p.conf = d_conf, p.mt = d_mt;
     p.rows0 = rows0, p.rows1 = rows1, p.dim = dim, p.head_dim = dim / heads;
@@ -121,7 +111,7 @@ int ftk_lightglue_adapt_step_device(ftk_context *ctx, void *stream, int32_t rows
     p.threshold = threshold, p.depth = depth_confidence;
     p.width = (float)(1.0 - (double)width_confidence);
     p.min_keypoints = min_keypoints;
-    p.src0 = reinterpret_cast<int32_t *>(ws + plan.off_src0), p.src1 = reinterpret_cast<int32_t *>(ws + plan.off_src1);
+    p.src0 = plan.src0.in(d_workspace), p.src1 = plan.src1.in(d_workspace);
     p.desc_in0 = d_desc_in0, p.desc_in1 = d_desc_in1, p.enc_in0 = d_enc_in0, p.enc_in1 = d_enc_in1, p.ind_in0 = d_ind_in0, p.ind_in1 = d_ind_in1;
     p.desc_out0 = d_desc_out0, p.desc_out1 = d_desc_out1, p.enc_out0 = d_enc_out0, p.enc_out1 = d_enc_out1;
     p.ind_out0 = d_ind_out0, p.ind_out1 = d_ind_out1;
@@ -156,19 +146,18 @@ int ftk_lightglue_finish_device(ftk_context *ctx, void *stream, const float *d_d
             return ftk_fail(ctx, FTK_E_INVALID_ARGUMENT, "lightglue_finish_device: null buffer");
         }
     }
-    if (!aligned16(d_workspace) || !aligned4(d_desc0) || !aligned4(d_desc1) || !aligned4(d_head_w) || !aligned4(d_head_b) || !aligned4(d_state) ||
+    if (!ftk_aligned(d_workspace, 16) || !aligned4(d_desc0) || !aligned4(d_desc1) || !aligned4(d_head_w) || !aligned4(d_head_b) || !aligned4(d_state) ||
         !aligned4(d_ind0) || !aligned4(d_ind1) || !aligned4(d_scores) || !aligned4(d_match_index) || !aligned4(d_layers0) || !aligned4(d_layers1)) {
         return ftk_fail(ctx, FTK_E_INVALID_ARGUMENT, "lightglue_finish_device: the workspace must be 16-byte aligned, the others 4-byte");
     }
-    uint8_t *ws = static_cast<uint8_t *>(d_workspace);
     ftk::FinishParams p{};
     p.rows0 = rows0, p.rows1 = rows1, p.dim = dim, p.n_layers = n_layers;
     p.head_w = d_head_w, p.head_b = d_head_b;
-    p.sel_w = reinterpret_cast<float *>(ws + plan.off_head_w), p.sel_b = reinterpret_cast<float *>(ws + plan.off_head_b);
+    p.sel_w = plan.head_w.in(d_workspace), p.sel_b = plan.head_b.in(d_workspace);
     p.state = d_state;
     p.ind0 = d_ind0, p.ind1 = d_ind1;
-    int32_t *match = reinterpret_cast<int32_t *>(ws + plan.off_match);
-    uint8_t *status_in = ws + plan.off_status;
+    int32_t *match = plan.match.in(d_workspace);
+    uint8_t *status_in = plan.status.in(d_workspace);
     p.match = match, p.status_in = status_in;
     p.match_index = d_match_index, p.status = d_status;
     p.layers0 = d_layers0, p.layers1 = d_layers1;
@@ -177,7 +166,7 @@ int ftk_lightglue_finish_device(ftk_context *ctx, void *stream, const float *d_d
     FTK_HIP(ctx, ftk::head_select_launch(plan, p, s));
     // the head and the matcher as they are, on the compacted sets with the live counts: rows and columns behind them are -inf
     int rc2 = ftk_match_assignment_device(ctx, stream, d_desc0, rows0, d_desc1, rows1, dim, p.sel_w, p.sel_b, 1.0f, d_state + ftk::kStateLive0,
-                                          d_state + ftk::kStateLive1, ws + plan.off_assign, d_scores, 0);
+                                          d_state + ftk::kStateLive1, plan.assign.in(d_workspace), d_scores, 0);
     if (rc2 != FTK_OK) {
         return rc2;
     }

@@ -195,7 +195,7 @@ int ftk_cosine_match_device(ftk_context *ctx, const float *d_ref_desc, int32_t n
         return rc;
     }
     uint8_t *ws = ctx->cosine_ws.as<uint8_t>();
-    auto at = [ws](size_t offset) { return reinterpret_cast<void *>(ws + offset); };
+    auto at = [ws](size_t offset) -> void * { return ws + offset; };
     const ftk::CosineParams p = {d_ref_desc, d_cur_desc, d_pred_uv, d_cur_uv, d_index_pairs, (_Float16 *)at(plan.ref_h), (_Float16 *)at(plan.cur_h),
                                  (float *)at(plan.ref_norm), (float *)at(plan.cur_norm), (float *)at(plan.cur_bias), (float4 *)at(plan.cur_info),
                                  plan.use_tile_box ? (float4 *)at(plan.tile_box) : nullptr, ws + plan.ref_irregular, (uint32_t *)at(plan.row_max),

@@ -35,23 +35,14 @@ int plan_call(ftk_context *ctx, const char *who, int32_t rows0, int32_t rows1, i
     }
 }
 
-bool aligned(const void *p, uintptr_t to) { return (reinterpret_cast<uintptr_t>(p) & (to - 1)) == 0; }
-
 }  // namespace
 
 extern "C" {
 
 int ftk_match_assignment_workspace_bytes(int32_t rows0, int32_t rows1, int32_t dim, int32_t with_weights, int64_t *bytes) {
-    if (!bytes) {
-        return ftk_fail(nullptr, FTK_E_INVALID_ARGUMENT, "match_assignment_workspace_bytes: null argument");
-    }
-    ftk::MatchAssignmentPlan plan;
-    const int rc = plan_call(nullptr, "match_assignment_workspace_bytes", rows0, rows1, dim, with_weights, 0, false, &plan);
-    if (rc != FTK_OK) {
-        return rc;
-    }
-    *bytes = (int64_t)plan.bytes;
-    return FTK_OK;
+    const char *who = "match_assignment_workspace_bytes";
+    return ftk_workspace_bytes<ftk::MatchAssignmentPlan>(
+        who, bytes, [&](ftk::MatchAssignmentPlan *plan) { return plan_call(nullptr, who, rows0, rows1, dim, with_weights, 0, false, plan); });
 }
 
 int ftk_match_assignment_device(ftk_context *ctx, void *stream, const float *d_desc0, int32_t rows0, const float *d_desc1, int32_t rows1, int32_t dim,
@@ -62,7 +53,7 @@ int ftk_match_assignment_device(ftk_context *ctx, void *stream, const float *d_d
     }
     FTK_LOCK(ctx);
     const bool with_weights = d_weights != nullptr;
-    const bool aligned16 = aligned(d_desc0, 16) && aligned(d_desc1, 16) && aligned(d_weights, 16);
+    const bool aligned16 = ftk_aligned(d_desc0, 16) && ftk_aligned(d_desc1, 16) && ftk_aligned(d_weights, 16);
     ftk::MatchAssignmentPlan plan;
     const int rc = plan_call(ctx, "match_assignment_device", rows0, rows1, dim, with_weights ? 1 : 0, row_stride, aligned16, &plan);
     if (rc != FTK_OK) {
@@ -74,11 +65,10 @@ int ftk_match_assignment_device(ftk_context *ctx, void *stream, const float *d_d
     if (!with_weights && (!(scale > 0.0f) || !(scale <= 3.0e38f))) {
         return ftk_fail(ctx, FTK_E_INVALID_ARGUMENT, "match_assignment_device: scale %g must be finite and positive", (double)scale);
     }
-    if (!aligned(d_workspace, 16) || !aligned(d_desc0, 4) || !aligned(d_desc1, 4) || !aligned(d_weights, 4) || !aligned(d_bias, 4) ||
-        !aligned(d_count0, 4) || !aligned(d_count1, 4) || !aligned(d_scores, 4)) {
+    if (!ftk_aligned(d_workspace, 16) || !ftk_aligned(d_desc0, 4) || !ftk_aligned(d_desc1, 4) || !ftk_aligned(d_weights, 4) || !ftk_aligned(d_bias, 4) ||
+        !ftk_aligned(d_count0, 4) || !ftk_aligned(d_count1, 4) || !ftk_aligned(d_scores, 4)) {
         return ftk_fail(ctx, FTK_E_INVALID_ARGUMENT, "match_assignment_device: the workspace must be 16-byte aligned, the others 4-byte");
     }
-    uint8_t *ws = static_cast<uint8_t *>(d_workspace);
     ftk::MatchAssignmentParams p{};
     p.desc0 = d_desc0;
     p.desc1 = d_desc1;
@@ -91,12 +81,12 @@ int ftk_match_assignment_device(ftk_context *ctx, void *stream, const float *d_d
     p.scale = with_weights ? 1.0f : scale;
     p.count0 = d_count0;
     p.count1 = d_count1;
-    p.md = with_weights ? reinterpret_cast<float *>(ws + plan.off_md) : nullptr;
-    p.z = with_weights ? reinterpret_cast<float *>(ws + plan.off_z) : nullptr;
-    p.lse_row = reinterpret_cast<float *>(ws + plan.off_lse_row);
-    p.lse_col = reinterpret_cast<float *>(ws + plan.off_lse_col);
-    p.ls0 = with_weights ? reinterpret_cast<float *>(ws + plan.off_ls0) : nullptr;
-    p.ls1 = with_weights ? reinterpret_cast<float *>(ws + plan.off_ls1) : nullptr;
+    p.md = with_weights ? plan.md.in(d_workspace) : nullptr;
+    p.z = with_weights ? plan.z.in(d_workspace) : nullptr;
+    p.lse_row = plan.lse_row.in(d_workspace);
+    p.lse_col = plan.lse_col.in(d_workspace);
+    p.ls0 = with_weights ? plan.ls0.in(d_workspace) : nullptr;
+    p.ls1 = with_weights ? plan.ls1.in(d_workspace) : nullptr;
     p.scores = d_scores;
     p.row_stride = plan.row_stride;
     FTK_HIP(ctx, hipSetDevice(ctx->device));

@@ -32,8 +32,6 @@ int plan_call(ftk_context *ctx, const char *who, int32_t n_slots, int32_t rows_c
     }
 }
 
-bool aligned(const void *p, uintptr_t to) { return (reinterpret_cast<uintptr_t>(p) & (to - 1)) == 0; }
-
 // Two of the call's arrays at one address (null pointers aside).
 bool any_equal(const void *const *ptrs, int count) {
     for (int a = 0; a < count; ++a) {
@@ -68,16 +66,8 @@ ftk::MatchTable table_of(int32_t n_slots, int32_t dim, int64_t *d_ids, float *d_
 extern "C" {
 
 int ftk_match_table_workspace_bytes(int32_t n_slots, int32_t rows_cur, int32_t dim, int64_t *bytes) {
-    if (!bytes) {
-        return ftk_fail(nullptr, FTK_E_INVALID_ARGUMENT, "match_table_workspace_bytes: null argument");
-    }
-    ftk::MatchTablePlan plan;
-    const int rc = plan_call(nullptr, "match_table_workspace_bytes", n_slots, rows_cur, dim, false, &plan);
-    if (rc != FTK_OK) {
-        return rc;
-    }
-    *bytes = (int64_t)plan.bytes;
-    return FTK_OK;
+    const char *who = "match_table_workspace_bytes";
+    return ftk_workspace_bytes<ftk::MatchTablePlan>(who, bytes, [&](ftk::MatchTablePlan *plan) { return plan_call(nullptr, who, n_slots, rows_cur, dim, false, plan); });
 }
 
 int ftk_match_table_query_device(ftk_context *ctx, void *stream, int32_t n_slots, int32_t dim, const int64_t *d_ids, const float *d_points,
@@ -87,15 +77,15 @@ int ftk_match_table_query_device(ftk_context *ctx, void *stream, int32_t n_slots
     }
     FTK_LOCK(ctx);
     ftk::MatchTablePlan plan;
-    const int rc = plan_call(ctx, "match_table_query_device", n_slots, 1, dim, aligned(d_descriptors, 16) && aligned(d_q_desc, 16), &plan);
+    const int rc = plan_call(ctx, "match_table_query_device", n_slots, 1, dim, ftk_aligned(d_descriptors, 16) && ftk_aligned(d_q_desc, 16), &plan);
     if (rc != FTK_OK) {
         return rc;
     }
     if (!d_ids || !d_points || !d_descriptors || !d_q_uv || !d_q_desc || !d_q_slot || !d_q_count) {
         return ftk_fail(ctx, FTK_E_INVALID_ARGUMENT, "match_table_query_device: null buffer");
     }
-    if (!aligned(d_ids, 8) || !aligned(d_points, 8) || !aligned(d_q_uv, 8) || !aligned(d_descriptors, 4) || !aligned(d_q_desc, 4) ||
-        !aligned(d_q_slot, 4) || !aligned(d_q_count, 4)) {
+    if (!ftk_aligned(d_ids, 8) || !ftk_aligned(d_points, 8) || !ftk_aligned(d_q_uv, 8) || !ftk_aligned(d_descriptors, 4) || !ftk_aligned(d_q_desc, 4) ||
+        !ftk_aligned(d_q_slot, 4) || !ftk_aligned(d_q_count, 4)) {
         return ftk_fail(ctx, FTK_E_INVALID_ARGUMENT, "match_table_query_device: ids and the (u, v) arrays must be 8-byte aligned, the others 4-byte");
     }
     const void *const ptrs[] = {d_ids, d_points, d_descriptors, d_q_uv, d_q_desc, d_q_slot, d_q_count};
@@ -124,7 +114,7 @@ int ftk_match_table_update_device(ftk_context *ctx, void *stream, int32_t n_slot
     }
     FTK_LOCK(ctx);
     ftk::MatchTablePlan plan;
-    const int rc = plan_call(ctx, "match_table_update_device", n_slots, rows_cur, dim, aligned(d_descriptors, 16) && aligned(d_cur_desc, 16), &plan);
+    const int rc = plan_call(ctx, "match_table_update_device", n_slots, rows_cur, dim, ftk_aligned(d_descriptors, 16) && ftk_aligned(d_cur_desc, 16), &plan);
     if (rc != FTK_OK) {
         return rc;
     }
@@ -135,10 +125,10 @@ int ftk_match_table_update_device(ftk_context *ctx, void *stream, int32_t n_slot
         !d_match_index || !d_match_status || !d_cur_uv || !d_cur_desc || !d_workspace) {
         return ftk_fail(ctx, FTK_E_INVALID_ARGUMENT, "match_table_update_device: null buffer");
     }
-    if (!aligned(d_workspace, 16) || !aligned(d_ids, 8) || !aligned(d_next_id, 8) || !aligned(d_points, 8) || !aligned(d_prev_points, 8) ||
-        !aligned(d_cur_uv, 8) || !aligned(d_descriptors, 4) || !aligned(d_cur_desc, 4) || !aligned(d_age, 4) || !aligned(d_lost, 4) ||
-        !aligned(d_n_live, 4) || !aligned(d_q_slot, 4) || !aligned(d_q_count, 4) || !aligned(d_match_index, 4) || !aligned(d_cur_count, 4) ||
-        !aligned(d_cur_slot, 4)) {
+    if (!ftk_aligned(d_workspace, 16) || !ftk_aligned(d_ids, 8) || !ftk_aligned(d_next_id, 8) || !ftk_aligned(d_points, 8) || !ftk_aligned(d_prev_points, 8) ||
+        !ftk_aligned(d_cur_uv, 8) || !ftk_aligned(d_descriptors, 4) || !ftk_aligned(d_cur_desc, 4) || !ftk_aligned(d_age, 4) || !ftk_aligned(d_lost, 4) ||
+        !ftk_aligned(d_n_live, 4) || !ftk_aligned(d_q_slot, 4) || !ftk_aligned(d_q_count, 4) || !ftk_aligned(d_match_index, 4) || !ftk_aligned(d_cur_count, 4) ||
+        !ftk_aligned(d_cur_slot, 4)) {
         return ftk_fail(ctx, FTK_E_INVALID_ARGUMENT,
                         "match_table_update_device: the workspace must be 16-byte aligned, the int64 and (u, v) arrays 8-byte, the others 4-byte");
     }
@@ -158,7 +148,7 @@ int ftk_match_table_update_device(ftk_context *ctx, void *stream, int32_t n_slot
     p.cur_count = d_cur_count;
     p.rows_cur = rows_cur;
     p.max_lost = max_lost;
-    p.cur_slot = d_cur_slot ? d_cur_slot : reinterpret_cast<int32_t *>(static_cast<uint8_t *>(d_workspace) + plan.off_cur_slot);
+    p.cur_slot = d_cur_slot ? d_cur_slot : plan.cur_slot.in(d_workspace);
     FTK_HIP(ctx, hipSetDevice(ctx->device));
     FTK_HIP(ctx, ftk::match_table_update_launch(plan, p, static_cast<hipStream_t>(stream)));
     return FTK_OK;

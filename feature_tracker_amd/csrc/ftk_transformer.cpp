@@ -29,8 +29,6 @@ int refusal(ftk_context *ctx, const char *who, const ftk::TransformerPlan &plan,
     }
 }
 
-bool aligned(const void *p, uintptr_t to) { return (reinterpret_cast<uintptr_t>(p) & (to - 1)) == 0; }
-
 bool usable_scale(float s) { return s > 0.0f && s <= 3.0e38f; }
 
 // The layer's 12 launches.  `gate` null: ftk_transformer_layer_device.  Otherwise the adaptive pass: the counts are the
@@ -39,10 +37,8 @@ bool usable_scale(float s) { return s > 0.0f && s <= 3.0e38f; }
 int run_layer(ftk_context *ctx, const ftk::TransformerPlan &plan, const float *d_desc0, int32_t rows0, const float *d_desc1, int32_t rows1, int32_t dim,
               const float *d_enc0, const float *d_enc1, const float *d_weights, const int32_t *d_count0, const int32_t *d_count1, const int32_t *gate,
               void *d_workspace, float *d_out0, float *d_out1, hipStream_t s) {
-    uint8_t *ws = static_cast<uint8_t *>(d_workspace);
-    float *qkv = reinterpret_cast<float *>(ws + plan.off_qkv), *att = reinterpret_cast<float *>(ws + plan.off_ctx);
-    float *msg = reinterpret_cast<float *>(ws + plan.off_msg), *hidden = reinterpret_cast<float *>(ws + plan.off_hidden);
-    float *x1 = reinterpret_cast<float *>(ws + plan.off_x1);
+    float *qkv = plan.qkv.in(d_workspace), *att = plan.ctx.in(d_workspace), *msg = plan.msg.in(d_workspace), *hidden = plan.hidden.in(d_workspace);
+    float *x1 = plan.x1.in(d_workspace);
     const int32_t rows = rows0 + rows1, dh = plan.head_dim;
     const size_t d = (size_t)dim, plane = (size_t)rows * d, second = (size_t)rows0 * d;
     const bool vec = plan.vec_linear != 0;
@@ -118,16 +114,11 @@ int run_layer(ftk_context *ctx, const ftk::TransformerPlan &plan, const float *d
 extern "C" {
 
 int ftk_transformer_layer_workspace_bytes(int32_t rows0, int32_t rows1, int32_t dim, int32_t heads, int64_t *bytes) {
-    if (!bytes) {
-        return ftk_fail(nullptr, FTK_E_INVALID_ARGUMENT, "transformer_layer_workspace_bytes: null argument");
-    }
-    const ftk::TransformerPlan plan = ftk::transformer_plan(ftk::TransformerPlanInput{rows0, rows1, dim, heads, 0});
-    const int rc = refusal(nullptr, "transformer_layer_workspace_bytes", plan, rows0, rows1, dim, heads);
-    if (rc != FTK_OK) {
-        return rc;
-    }
-    *bytes = (int64_t)plan.bytes;
-    return FTK_OK;
+    const char *who = "transformer_layer_workspace_bytes";
+    return ftk_workspace_bytes<ftk::TransformerPlan>(who, bytes, [&](ftk::TransformerPlan *plan) {
+        *plan = ftk::transformer_plan(ftk::TransformerPlanInput{rows0, rows1, dim, heads, 0});
+        return refusal(nullptr, who, *plan, rows0, rows1, dim, heads);
+    });
 }
 
 int ftk_attention_device(ftk_context *ctx, void *stream, const float *d_q, int32_t rows_q, const float *d_k, const float *d_v, int32_t rows_k,
@@ -136,7 +127,7 @@ int ftk_attention_device(ftk_context *ctx, void *stream, const float *d_q, int32
         return ftk_fail(nullptr, FTK_E_INVALID_ARGUMENT, "attention_device: null context");
     }
     FTK_LOCK(ctx);
-    const bool aligned16 = aligned(d_q, 16) && aligned(d_k, 16) && aligned(d_v, 16);
+    const bool aligned16 = ftk_aligned(d_q, 16) && ftk_aligned(d_k, 16) && ftk_aligned(d_v, 16);
     const ftk::TransformerPlan plan = ftk::attention_plan(rows_q, rows_k, heads, head_dim, aligned16 ? 1 : 0);
     const bool sized = heads >= 1 && heads <= FTK_TRANSFORMER_MAX_DIM && head_dim >= 1 && head_dim <= FTK_TRANSFORMER_MAX_DIM;
     const int rc = refusal(ctx, "attention_device", plan, rows_q, rows_k, sized ? heads * head_dim : head_dim, sized ? heads : 1);
@@ -149,7 +140,7 @@ int ftk_attention_device(ftk_context *ctx, void *stream, const float *d_q, int32
     if (!usable_scale(pre_scale) || !usable_scale(post_scale)) {
         return ftk_fail(ctx, FTK_E_INVALID_ARGUMENT, "attention_device: scales %g, %g must be finite and positive", (double)pre_scale, (double)post_scale);
     }
-    if (!aligned(d_q, 4) || !aligned(d_k, 4) || !aligned(d_v, 4) || !aligned(d_out, 4) || !aligned(d_count, 4)) {
+    if (!ftk_aligned(d_q, 4) || !ftk_aligned(d_k, 4) || !ftk_aligned(d_v, 4) || !ftk_aligned(d_out, 4) || !ftk_aligned(d_count, 4)) {
         return ftk_fail(ctx, FTK_E_INVALID_ARGUMENT, "attention_device: every buffer must be 4-byte aligned");
     }
     ftk::AttentionParams p{};
@@ -170,7 +161,7 @@ int ftk_linear_device(ftk_context *ctx, void *stream, const float *d_x, int32_t 
         return ftk_fail(nullptr, FTK_E_INVALID_ARGUMENT, "linear_device: null context");
     }
     FTK_LOCK(ctx);
-    const ftk::LinearPlan plan = ftk::linear_plan(rows, in_dim, out_dim, aligned(d_x, 16) && aligned(d_weight, 16) ? 1 : 0);
+    const ftk::LinearPlan plan = ftk::linear_plan(rows, in_dim, out_dim, ftk_aligned(d_x, 16) && ftk_aligned(d_weight, 16) ? 1 : 0);
     if (plan.refused == ftk::TransformerRefusal::Rows) {
         return ftk_fail(ctx, FTK_E_INVALID_ARGUMENT, "linear_device: %d rows outside 1 .. %d", rows, FTK_TRANSFORMER_MAX_ROWS);
     }
@@ -180,7 +171,7 @@ int ftk_linear_device(ftk_context *ctx, void *stream, const float *d_x, int32_t 
     if (!d_x || !d_weight || !d_bias || !d_out) {
         return ftk_fail(ctx, FTK_E_INVALID_ARGUMENT, "linear_device: null buffer");
     }
-    if (!aligned(d_x, 4) || !aligned(d_weight, 4) || !aligned(d_bias, 4) || !aligned(d_out, 4)) {
+    if (!ftk_aligned(d_x, 4) || !ftk_aligned(d_weight, 4) || !ftk_aligned(d_bias, 4) || !ftk_aligned(d_out, 4)) {
         return ftk_fail(ctx, FTK_E_INVALID_ARGUMENT, "linear_device: every buffer must be 4-byte aligned");
     }
     ftk::LinearParams p{};
@@ -205,7 +196,7 @@ int ftk_transformer_layer_device(ftk_context *ctx, void *stream, const float *d_
         return ftk_fail(nullptr, FTK_E_INVALID_ARGUMENT, "transformer_layer_device: null context");
     }
     FTK_LOCK(ctx);
-    const bool aligned16 = aligned(d_desc0, 16) && aligned(d_desc1, 16) && aligned(d_weights, 16) && aligned(d_out0, 16) && aligned(d_out1, 16);
+    const bool aligned16 = ftk_aligned(d_desc0, 16) && ftk_aligned(d_desc1, 16) && ftk_aligned(d_weights, 16) && ftk_aligned(d_out0, 16) && ftk_aligned(d_out1, 16);
     const ftk::TransformerPlan plan = ftk::transformer_plan(ftk::TransformerPlanInput{rows0, rows1, dim, heads, aligned16 ? 1 : 0});
     const int rc = refusal(ctx, "transformer_layer_device", plan, rows0, rows1, dim, heads);
     if (rc != FTK_OK) {
@@ -214,8 +205,8 @@ int ftk_transformer_layer_device(ftk_context *ctx, void *stream, const float *d_
     if (!d_desc0 || !d_desc1 || !d_enc0 || !d_enc1 || !d_weights || !d_workspace || !d_out0 || !d_out1) {
         return ftk_fail(ctx, FTK_E_INVALID_ARGUMENT, "transformer_layer_device: null buffer");
     }
-    if (!aligned(d_workspace, 16) || !aligned(d_desc0, 4) || !aligned(d_desc1, 4) || !aligned(d_enc0, 4) || !aligned(d_enc1, 4) || !aligned(d_weights, 4) ||
-        !aligned(d_count0, 4) || !aligned(d_count1, 4) || !aligned(d_out0, 4) || !aligned(d_out1, 4)) {
+    if (!ftk_aligned(d_workspace, 16) || !ftk_aligned(d_desc0, 4) || !ftk_aligned(d_desc1, 4) || !ftk_aligned(d_enc0, 4) || !ftk_aligned(d_enc1, 4) || !ftk_aligned(d_weights, 4) ||
+        !ftk_aligned(d_count0, 4) || !ftk_aligned(d_count1, 4) || !ftk_aligned(d_out0, 4) || !ftk_aligned(d_out1, 4)) {
         return ftk_fail(ctx, FTK_E_INVALID_ARGUMENT, "transformer_layer_device: the workspace must be 16-byte aligned, the others 4-byte");
     }
     FTK_HIP(ctx, hipSetDevice(ctx->device));
@@ -230,7 +221,7 @@ int ftk_transformer_layer_adaptive_device(ftk_context *ctx, void *stream, float 
         return ftk_fail(nullptr, FTK_E_INVALID_ARGUMENT, "transformer_layer_adaptive_device: null context");
     }
     FTK_LOCK(ctx);
-    const bool aligned16 = aligned(d_desc0, 16) && aligned(d_desc1, 16) && aligned(d_weights, 16);
+    const bool aligned16 = ftk_aligned(d_desc0, 16) && ftk_aligned(d_desc1, 16) && ftk_aligned(d_weights, 16);
     const ftk::TransformerPlan plan = ftk::transformer_plan(ftk::TransformerPlanInput{rows0, rows1, dim, heads, aligned16 ? 1 : 0});
     const int rc = refusal(ctx, "transformer_layer_adaptive_device", plan, rows0, rows1, dim, heads);
     if (rc != FTK_OK) {
@@ -239,8 +230,8 @@ int ftk_transformer_layer_adaptive_device(ftk_context *ctx, void *stream, float 
     if (!d_desc0 || !d_desc1 || !d_enc0 || !d_enc1 || !d_weights || !d_workspace || !d_live0 || !d_live1 || !d_gate) {
         return ftk_fail(ctx, FTK_E_INVALID_ARGUMENT, "transformer_layer_adaptive_device: null buffer (the live counts and the gate are required)");
     }
-    if (!aligned(d_workspace, 16) || !aligned(d_desc0, 4) || !aligned(d_desc1, 4) || !aligned(d_enc0, 4) || !aligned(d_enc1, 4) || !aligned(d_weights, 4) ||
-        !aligned(d_live0, 4) || !aligned(d_live1, 4) || !aligned(d_gate, 4)) {
+    if (!ftk_aligned(d_workspace, 16) || !ftk_aligned(d_desc0, 4) || !ftk_aligned(d_desc1, 4) || !ftk_aligned(d_enc0, 4) || !ftk_aligned(d_enc1, 4) || !ftk_aligned(d_weights, 4) ||
+        !ftk_aligned(d_live0, 4) || !ftk_aligned(d_live1, 4) || !ftk_aligned(d_gate, 4)) {
         return ftk_fail(ctx, FTK_E_INVALID_ARGUMENT, "transformer_layer_adaptive_device: the workspace must be 16-byte aligned, the others 4-byte");
     }
     FTK_HIP(ctx, hipSetDevice(ctx->device));

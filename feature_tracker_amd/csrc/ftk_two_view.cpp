@@ -46,19 +46,9 @@ int plan_call(ftk_context *ctx, const char *who, int32_t slots, int32_t n, int32
 }
 
 int workspace_bytes(const char *who, int32_t slots, int32_t n, int32_t hypotheses, int32_t mode, int64_t *bytes) {
-    if (!bytes) {
-        return ftk_fail(nullptr, FTK_E_INVALID_ARGUMENT, "%s: null argument", who);
-    }
-    ftk::TwoViewPlan plan;
-    const int rc = plan_call(nullptr, who, slots, n, hypotheses, 1, 1, mode, 0, &plan);
-    if (rc != FTK_OK) {
-        return rc;
-    }
-    *bytes = (int64_t)plan.bytes;
-    return FTK_OK;
+    return ftk_workspace_bytes<ftk::TwoViewPlan>(
+        who, bytes, [&](ftk::TwoViewPlan *plan) { return plan_call(nullptr, who, slots, n, hypotheses, 1, 1, mode, 0, plan); });
 }
-
-bool aligned(const void *p, uintptr_t to) { return (reinterpret_cast<uintptr_t>(p) & (to - 1)) == 0; }
 
 // Both device entries.  One slot: d_model and d_H are not part of the entry (null), d_best / d_n_inliers hold one element.
 int ransac_device(const char *who, int32_t slots, ftk_context *ctx, void *stream, const float *d_ref_uv, const float *d_cur_uv, uint8_t *d_status,
@@ -80,14 +70,13 @@ int ransac_device(const char *who, int32_t slots, ftk_context *ctx, void *stream
     if (!(threshold >= 0.0f) || !(threshold <= 3.0e38f)) {
         return ftk_fail(ctx, FTK_E_INVALID_ARGUMENT, "%s: the threshold %g must be finite and >= 0", who, (double)threshold);
     }
-    if (!aligned(d_ref_uv, 8) || !aligned(d_cur_uv, 8)) {
+    if (!ftk_aligned(d_ref_uv, 8) || !ftk_aligned(d_cur_uv, 8)) {
         return ftk_fail(ctx, FTK_E_INVALID_ARGUMENT, "%s: the (u, v) arrays must be 8-byte aligned", who);
     }
-    if (!aligned(d_workspace, 16) || !aligned(d_model, 4) || !aligned(d_best, 4) || !aligned(d_n_inliers, 4) || !aligned(d_F, 4) || !aligned(d_H, 4) ||
-        !aligned(d_counts, 4) || !aligned(d_models, 4)) {
+    if (!ftk_aligned(d_workspace, 16) || !ftk_aligned(d_model, 4) || !ftk_aligned(d_best, 4) || !ftk_aligned(d_n_inliers, 4) || !ftk_aligned(d_F, 4) ||
+        !ftk_aligned(d_H, 4) || !ftk_aligned(d_counts, 4) || !ftk_aligned(d_models, 4)) {
         return ftk_fail(ctx, FTK_E_INVALID_ARGUMENT, "%s: the workspace must be 16-byte aligned, the outputs 4-byte aligned", who);
     }
-    uint8_t *ws = static_cast<uint8_t *>(d_workspace);
     const size_t K = (size_t)hypotheses;
     ftk::TwoViewParams p{};
     p.ref_uv = d_ref_uv;
@@ -102,15 +91,15 @@ int ransac_device(const char *who, int32_t slots, ftk_context *ctx, void *stream
     const float tn = threshold * p.s;
     p.tn2 = tn * tn;
     p.seed = seed;
-    p.m = reinterpret_cast<int32_t *>(ws);
-    p.points = reinterpret_cast<float4 *>(ws + plan.off_points);
-    p.list = reinterpret_cast<int32_t *>(ws + plan.off_list);
-    int32_t *const counts = d_counts ? d_counts : reinterpret_cast<int32_t *>(ws + plan.off_counts);
-    float *const models = d_models ? d_models : reinterpret_cast<float *>(ws + plan.off_models);
+    p.m = plan.m.in(d_workspace);
+    p.points = plan.points.in(d_workspace);
+    p.list = plan.list.in(d_workspace);
+    int32_t *const counts = d_counts ? d_counts : plan.counts.in(d_workspace);
+    float *const models = d_models ? d_models : plan.models.in(d_workspace);
     for (int32_t s = 0; s < slots; ++s) {
         p.slot[s].counts = counts + (size_t)s * K;
         p.slot[s].models = models + (size_t)s * 9 * K;
-        p.slot[s].valid = ws + plan.off_valid + (size_t)s * K;
+        p.slot[s].valid = plan.valid.in(d_workspace) + (size_t)s * K;
     }
     p.prefer_permille = permille;
     p.model = d_model;

@@ -23,26 +23,13 @@ int plan_call(ftk_context *ctx, const char *who, int32_t n, ftk::TwoViewPosePlan
     }
 }
 
-bool aligned(const void *p, uintptr_t to) { return (reinterpret_cast<uintptr_t>(p) & (to - 1)) == 0; }
-bool finite(float v) { return v - v == 0.0f; }  // false for NaN and the infinities alone
-bool positive(float v) { return v > 0.0f && finite(v); }
-
 }  // namespace
 
 extern "C" {
 
 int ftk_two_view_pose_workspace_bytes(int32_t n, int64_t *bytes) {
     const char *who = "two_view_pose_workspace_bytes";
-    if (!bytes) {
-        return ftk_fail(nullptr, FTK_E_INVALID_ARGUMENT, "%s: null argument", who);
-    }
-    ftk::TwoViewPosePlan plan;
-    const int rc = plan_call(nullptr, who, n, &plan);
-    if (rc != FTK_OK) {
-        return rc;
-    }
-    *bytes = (int64_t)plan.bytes;
-    return FTK_OK;
+    return ftk_workspace_bytes<ftk::TwoViewPosePlan>(who, bytes, [&](ftk::TwoViewPosePlan *plan) { return plan_call(nullptr, who, n, plan); });
 }
 
 int ftk_two_view_pose_device(ftk_context *ctx, void *stream, const float *d_ref_uv, const float *d_cur_uv, uint8_t *d_status, int32_t n, float fx,
@@ -61,24 +48,23 @@ int ftk_two_view_pose_device(ftk_context *ctx, void *stream, const float *d_ref_
     if (!d_ref_uv || !d_cur_uv || !d_status || !d_workspace || !d_pose || !d_points || !d_E || !d_n_front || !d_valid || !d_n_points) {
         return ftk_fail(ctx, FTK_E_INVALID_ARGUMENT, "%s: null buffer", who);
     }
-    if (!positive(fx) || !positive(fy) || !positive(fx_cur) || !positive(fy_cur) || !finite(cx) || !finite(cy) || !finite(cx_cur) || !finite(cy_cur)) {
+    if (!ftk_positive(fx) || !ftk_positive(fy) || !ftk_positive(fx_cur) || !ftk_positive(fy_cur) || !ftk_finite(cx) || !ftk_finite(cy) || !ftk_finite(cx_cur) || !ftk_finite(cy_cur)) {
         return ftk_fail(ctx, FTK_E_INVALID_ARGUMENT, "%s: a camera needs finite fx, fy > 0 and finite cx, cy (got %g %g %g %g and %g %g %g %g)", who,
                         (double)fx, (double)fy, (double)cx, (double)cy, (double)fx_cur, (double)fy_cur, (double)cx_cur, (double)cy_cur);
     }
-    if (!(threshold >= 0.0f) || !finite(threshold * threshold)) {  // the kernels compare against threshold^2
+    if (!(threshold >= 0.0f) || !ftk_finite(threshold * threshold)) {  // the kernels compare against threshold^2
         return ftk_fail(ctx, FTK_E_INVALID_ARGUMENT, "%s: the threshold %g must be >= 0 and its square finite in float32", who, (double)threshold);
     }
-    if (!positive(baseline)) {
+    if (!ftk_positive(baseline)) {
         return ftk_fail(ctx, FTK_E_INVALID_ARGUMENT, "%s: the baseline %g must be finite and > 0", who, (double)baseline);
     }
-    if (!aligned(d_ref_uv, 8) || !aligned(d_cur_uv, 8)) {
+    if (!ftk_aligned(d_ref_uv, 8) || !ftk_aligned(d_cur_uv, 8)) {
         return ftk_fail(ctx, FTK_E_INVALID_ARGUMENT, "%s: the (u, v) arrays must be 8-byte aligned", who);
     }
-    if (!aligned(d_workspace, 16) || !aligned(d_pose, 4) || !aligned(d_points, 4) || !aligned(d_E, 4) || !aligned(d_n_front, 4) || !aligned(d_valid, 4) ||
-        !aligned(d_n_points, 4)) {
+    if (!ftk_aligned(d_workspace, 16) || !ftk_aligned(d_pose, 4) || !ftk_aligned(d_points, 4) || !ftk_aligned(d_E, 4) || !ftk_aligned(d_n_front, 4) || !ftk_aligned(d_valid, 4) ||
+        !ftk_aligned(d_n_points, 4)) {
         return ftk_fail(ctx, FTK_E_INVALID_ARGUMENT, "%s: the workspace must be 16-byte aligned, the outputs 4-byte aligned", who);
     }
-    uint8_t *ws = static_cast<uint8_t *>(d_workspace);
     ftk::TwoViewPoseParams p{};
     p.ref_uv = d_ref_uv;
     p.cur_uv = d_cur_uv;
@@ -88,10 +74,10 @@ int ftk_two_view_pose_device(ftk_context *ctx, void *stream, const float *d_ref_
     p.fx2 = fx_cur, p.fy2 = fy_cur, p.cx2 = cx_cur, p.cy2 = cy_cur;
     p.t2 = threshold * threshold;
     p.baseline = baseline;
-    p.m = reinterpret_cast<int32_t *>(ws);
-    p.points = reinterpret_cast<float4 *>(ws + plan.off_points);
-    p.totals = reinterpret_cast<float *>(ws + plan.off_totals);
-    p.model = reinterpret_cast<float *>(ws + plan.off_model);
+    p.m = plan.m.in(d_workspace);
+    p.points = plan.points.in(d_workspace);
+    p.totals = plan.totals.in(d_workspace);
+    p.model = plan.model.in(d_workspace);
     p.pose = d_pose;
     p.landmarks = d_points;
     p.E = d_E;

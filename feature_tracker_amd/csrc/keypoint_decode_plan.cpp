@@ -37,7 +37,6 @@ KeypointDecodePlan keypoint_decode_plan(const KeypointDecodePlanInput &in) {
         p.refused = KeypointDecodeRefusal::Survivors;
         return p;
     }
-    const auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
     const size_t px = (size_t)rows * cols;
     p.refused = KeypointDecodeRefusal::None;
     p.rows = rows;
@@ -54,13 +53,16 @@ KeypointDecodePlan keypoint_decode_plan(const KeypointDecodePlanInput &in) {
     p.describe_blocks = (uint32_t)((in.max_keypoints + kKeypointDescribeWaves - 1) / kKeypointDescribeWaves);
     p.launches = in.n_occupied > 0 ? 10 : 7;
     p.memsets = in.n_occupied > 0 ? 4 : 3;
-    p.off_tmp = up16(8 * px);
-    p.off_wmax = p.off_tmp + up16(8 * px);
-    p.off_list = p.off_wmax + up16(8 * px);
-    p.off_count = p.off_list + up16(8 * (size_t)p.capacity);
-    p.off_plane = p.off_count + 16;
-    p.off_dilated = p.off_plane + (in.n_occupied > 0 ? up16(px) : 0);
-    p.bytes = p.off_dilated + (in.n_occupied > 0 ? up16(px) : 0);
+    const size_t occupied_px = in.n_occupied > 0 ? px : 0;
+    ftk_layout16 ws;  // cannot wrap: px <= 2^32
+    p.key = ws.take<unsigned long long>(px);
+    p.tmp = ws.take<unsigned long long>(px);
+    p.wmax = ws.take<unsigned long long>(px);
+    p.list = ws.take<unsigned long long>((size_t)p.capacity);
+    p.count = ws.take<unsigned>(1);
+    p.plane = ws.take<uint8_t>(occupied_px);
+    p.dilated = ws.take<uint8_t>(occupied_px);
+    p.bytes = ws.bytes();
     return p;
 }
 

@@ -5,6 +5,7 @@
 #pragma once
 
 #include "ftk_device.h"
+#include "ftk_layout.h"
 
 namespace ftk {
 
@@ -43,9 +44,12 @@ struct KeypointDecodePlan {
     uint32_t describe_blocks;       // workgroups of kKeypointDescribeWaves waves: one wave per output row
     int32_t launches;               // kernels: score, [stamp, dilate, block], 2 window maxima, collect, rank, describe: 7 or 10
     int32_t memsets;                // uv, scores, the survivor count, [the stamp plane]: 3 or 4
-    // the workspace, byte offsets (16-byte aligned): the key plane at 0, the two window-maximum planes, the survivor list, its count,
-    // and with occupied points the stamp plane and its row dilation
-    size_t off_tmp, off_wmax, off_list, off_count, off_plane, off_dilated, bytes;
+    // the workspace (ftk_layout.h), in this order: the key plane and the two window-maximum planes [H][W], the survivor list [capacity], its
+    // count, and with occupied points (count 0 without) the stamp plane and its row dilation [H][W]
+    ftk_slot16<unsigned long long> key, tmp, wmax, list;
+    ftk_slot16<unsigned> count;
+    ftk_slot16<uint8_t> plane, dilated;
+    size_t bytes;
 };
 const char *keypoint_decode_refusal_name(KeypointDecodeRefusal r);
 KeypointDecodePlan keypoint_decode_plan(const KeypointDecodePlanInput &in);

@@ -32,7 +32,6 @@ LightglueAdaptivePlan lightglue_adaptive_plan(const LightglueAdaptivePlanInput &
         return p;
     }
     p.refused = LightglueAdaptiveRefusal::None;
-    const auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
     const auto tiles = [](size_t n, size_t per) { return (uint32_t)((n + per - 1) / per); };
     const size_t m = (size_t)in.rows0, n = (size_t)in.rows1, r = m + n, d = (size_t)in.dim;
     p.conf_blocks = lightglue_confidence_blocks((int64_t)r);
@@ -43,15 +42,16 @@ LightglueAdaptivePlan lightglue_adaptive_plan(const LightglueAdaptivePlanInput &
     p.remap_blocks = tiles(r, kAdaptiveCopyThreads);
     p.step_launches = 3;
     p.finish_launches = 2;
-    p.off_layer = 0;
-    p.off_assign = p.off_layer + up16(layer.bytes);
-    p.off_head_w = p.off_assign + up16(assign.bytes);
-    p.off_head_b = p.off_head_w + up16(4 * (d + 1) * d);
-    p.off_src0 = p.off_head_b + up16(4 * (d + 1));
-    p.off_src1 = p.off_src0 + up16(4 * m);
-    p.off_match = p.off_src1 + up16(4 * n);
-    p.off_status = p.off_match + up16(4 * m);
-    p.bytes = p.off_status + up16(m);
+    ftk_layout16 ws;  // cannot wrap: the two plans accepted these sizes, and theirs are the largest blocks
+    p.layer = ws.take<uint8_t>(layer.bytes);
+    p.assign = ws.take<uint8_t>(assign.bytes);
+    p.head_w = ws.take<float>((d + 1) * d);
+    p.head_b = ws.take<float>(d + 1);
+    p.src0 = ws.take<int32_t>(m);
+    p.src1 = ws.take<int32_t>(n);
+    p.match = ws.take<int32_t>(m);
+    p.status = ws.take<uint8_t>(m);
+    p.bytes = ws.bytes();
     return p;
 }
 

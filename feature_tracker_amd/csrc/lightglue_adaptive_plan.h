@@ -5,6 +5,7 @@
 #pragma once
 
 #include "ftk_device.h"
+#include "ftk_layout.h"
 
 namespace ftk {
 
@@ -32,9 +33,12 @@ struct LightglueAdaptivePlan {
     uint32_t select_blocks, remap_blocks;  // grid-stride over the head's (D + 1) D + D + 1 floats and M indices; over M + N rows
     int32_t step_launches;             // 3 per layer in front of the last: confidence, decide, gather
     int32_t finish_launches;           // 2 on top of the head's and the matcher's: head select, remap
-    // the workspace, byte offsets (16-byte aligned): the layer's workspace, the assignment head's (with weights), the selected head
-    // [D + 1][D] and [D + 1], the gather maps [M], [N], the matcher's index [M] and status [M]
-    size_t off_layer, off_assign, off_head_w, off_head_b, off_src0, off_src1, off_match, off_status, bytes;
+    // the workspace (ftk_layout.h), in this order: the layer's workspace and the assignment head's (with weights) as the bytes of their
+    // own plans, the selected head [D + 1][D] and [D + 1], the gather maps [M], [N], the matcher's index [M] and status [M]
+    ftk_slot16<uint8_t> layer, assign, status;
+    ftk_slot16<float> head_w, head_b;
+    ftk_slot16<int32_t> src0, src1, match;
+    size_t bytes;
 };
 const char *lightglue_adaptive_refusal_name(LightglueAdaptiveRefusal r);
 // confidence_kernel's grid for `rows` rows of both sets: the plan's conf_blocks, and the grid of the confidence entry alone.

@@ -28,7 +28,6 @@ MatchAssignmentPlan match_assignment_plan(const MatchAssignmentPlanInput &in) {
         p.refused = MatchAssignmentRefusal::Stride;
         return p;
     }
-    const auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
     const auto tiles = [](int64_t n, int64_t per) { return (uint32_t)((n + per - 1) / per); };
     const size_t m = (size_t)in.rows0, n = (size_t)in.rows1, d = (size_t)in.dim;
     const bool w = in.with_weights != 0;
@@ -45,13 +44,14 @@ MatchAssignmentPlan match_assignment_plan(const MatchAssignmentPlanInput &in) {
     p.finish_grid_x = tiles(in.rows1 + 1, kAssignFinishThreads);
     p.finish_grid_y = tiles(in.rows0 + 1, kAssignFinishRows);
     p.launches = w ? 4 : 3;
-    p.off_md = 0;
-    p.off_z = p.off_md + (w ? up16(4 * (m + n) * d) : 0);
-    p.off_lse_row = p.off_z + (w ? up16(4 * (m + n)) : 0);
-    p.off_lse_col = p.off_lse_row + up16(4 * m);
-    p.off_ls0 = p.off_lse_col + up16(4 * n);
-    p.off_ls1 = p.off_ls0 + (w ? up16(8 * m) : 0);
-    p.bytes = p.off_ls1 + (w ? up16(8 * n) : 0);
+    ftk_layout16 ws;  // cannot wrap: (M + N) D <= 2^23
+    p.md = ws.take<float>(w ? (m + n) * d : 0);
+    p.z = ws.take<float>(w ? m + n : 0);
+    p.lse_row = ws.take<float>(m);
+    p.lse_col = ws.take<float>(n);
+    p.ls0 = ws.take<float>(w ? 2 * m : 0);
+    p.ls1 = ws.take<float>(w ? 2 * n : 0);
+    p.bytes = ws.bytes();
     return p;
 }
 

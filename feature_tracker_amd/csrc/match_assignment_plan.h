@@ -5,6 +5,7 @@
 #pragma once
 
 #include "ftk_device.h"
+#include "ftk_layout.h"
 
 namespace ftk {
 
@@ -38,9 +39,10 @@ struct MatchAssignmentPlan {
     size_t norm_lds;
     uint32_t finish_grid_x, finish_grid_y;    // kAssignFinishThreads columns of N + 1, kAssignFinishRows rows of M + 1
     int32_t launches;                // projection (with weights), similarity, normalisers, finish: 4 or 3
-    // the workspace, byte offsets (16-byte aligned): projected descriptors [M + N][D] and z [M + N] (with weights), the row and column
-    // normalisers [M], [N], and (with weights) ls(z), ls(-z) per row [2][M] and per column [2][N]
-    size_t off_md, off_z, off_lse_row, off_lse_col, off_ls0, off_ls1, bytes;
+    // the workspace (ftk_layout.h), in this order: projected descriptors [M + N][D] and z [M + N] (with weights, count 0 without), the row
+    // and column normalisers [M], [N], and (with weights) ls(z), ls(-z) per row [2][M] and per column [2][N]
+    ftk_slot16<float> md, z, lse_row, lse_col, ls0, ls1;
+    size_t bytes;
 };
 const char *match_assignment_refusal_name(MatchAssignmentRefusal r);
 MatchAssignmentPlan match_assignment_plan(const MatchAssignmentPlanInput &in);

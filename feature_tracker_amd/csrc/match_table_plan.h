@@ -4,6 +4,7 @@
 #pragma once
 
 #include "ftk_device.h"
+#include "ftk_layout.h"
 #include "track_table_plan.h"
 
 namespace ftk {
@@ -31,7 +32,7 @@ struct MatchTablePlan {
     uint32_t query_move_blocks;   // workgroups of kMatchTableMoveWaves waves: one wave per query row
     uint32_t update_move_blocks;  // one wave per current row
     int32_t query_launches, update_launches;  // 2 and 2: the scan workgroup, then the row mover
-    size_t off_cur_slot;        // the workspace, byte offsets (16-byte aligned): the current rows' slots int32 [K]
+    ftk_slot16<int32_t> cur_slot;  // the workspace (ftk_layout.h): the current rows' slots [K]
     size_t bytes;
 };
 
@@ -67,8 +68,9 @@ inline MatchTablePlan match_table_plan(const MatchTablePlanInput &in) {
     p.update_move_blocks = (uint32_t)((in.rows_cur + kMatchTableMoveWaves - 1) / kMatchTableMoveWaves);
     p.query_launches = 2;
     p.update_launches = 2;
-    p.off_cur_slot = 0;
-    p.bytes = (sizeof(int32_t) * (size_t)in.rows_cur + 15) & ~(size_t)15;
+    ftk_layout16 ws;  // cannot wrap: K <= 2^12
+    p.cur_slot = ws.take<int32_t>((size_t)in.rows_cur);
+    p.bytes = ws.bytes();
     return p;
 }
 

@@ -89,7 +89,6 @@ TransformerPlan transformer_plan(const TransformerPlanInput &in) {
     if (p.refused != TransformerRefusal::None) {
         return p;
     }
-    const auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
     const size_t r = (size_t)in.rows0 + (size_t)in.rows1, d = (size_t)in.dim;
     p.linear_grid_x = tiles((int64_t)r, kLinearTileRows);
     p.grid_y_d = tiles(in.dim, kLinearTileCols);
@@ -97,12 +96,13 @@ TransformerPlan transformer_plan(const TransformerPlanInput &in) {
     p.grid_y_3d = tiles(3 * in.dim, kLinearTileCols);
     p.norm_blocks = (uint32_t)r;
     p.launches = 12;
-    p.off_qkv = 0;
-    p.off_ctx = p.off_qkv + up16(4 * 3 * r * d);
-    p.off_msg = p.off_ctx + up16(4 * r * d);
-    p.off_hidden = p.off_msg + up16(4 * r * d);
-    p.off_x1 = p.off_hidden + up16(4 * 2 * r * d);
-    p.bytes = p.off_x1 + up16(4 * r * d);
+    ftk_layout16 ws;  // cannot wrap: R D <= 2^23
+    p.qkv = ws.take<float>(3 * r * d);
+    p.ctx = ws.take<float>(r * d);
+    p.msg = ws.take<float>(r * d);
+    p.hidden = ws.take<float>(2 * r * d);
+    p.x1 = ws.take<float>(r * d);
+    p.bytes = ws.bytes();
     size_t at = 0;
     for (int block = 0; block < 2; ++block) {
         size_t *w = block == 0 ? p.w_self : p.w_cross;

@@ -5,6 +5,7 @@
 #pragma once
 
 #include "ftk_device.h"
+#include "ftk_layout.h"
 
 namespace ftk {
 
@@ -38,9 +39,10 @@ struct TransformerPlan {
     uint32_t attn_grid_x, attn_grid_y, attn_grid_z;  // 32-row tiles of max(M, N); heads x column splits; the two sets or directions
     uint32_t norm_blocks;        // M + N
     int32_t launches;            // 12: per block qkv, attention, out, ffn.0, LayerNorm + GELU, ffn.3
-    // the workspace, byte offsets (16-byte aligned), R = M + N: the q | k | v planes [3][R][D], the attention output [R][D], the message
+    // the workspace (ftk_layout.h), in this order, R = M + N: the q | k | v planes [3][R][D], the attention output [R][D], the message
     // [R][D], the hidden rows [R][2 D], the self block's result [R][D]
-    size_t off_qkv, off_ctx, off_msg, off_hidden, off_x1, bytes;
+    ftk_slot16<float> qkv, ctx, msg, hidden, x1;
+    size_t bytes;
     // the packed weights, float offsets: per block w_in, b_in, w_out, b_out, w_ffn0, b_ffn0, gamma, beta, w_ffn3, b_ffn3
     size_t w_self[10], w_cross[10], weight_floats;
 };

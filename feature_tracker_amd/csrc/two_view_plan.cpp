@@ -38,8 +38,7 @@ TwoViewPlan two_view_plan(const TwoViewPlanInput &in) {
         p.refused = TwoViewRefusal::Hypotheses;
         return p;
     }
-    const auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    const size_t slots = (size_t)in.slots;
+    const size_t n = (size_t)in.n, k = (size_t)in.slots * (size_t)in.hypotheses;
     p.refused = TwoViewRefusal::None;
     p.slots = in.slots;
     p.run_fundamental = in.mode != kTwoViewHomography;
@@ -53,12 +52,14 @@ TwoViewPlan two_view_plan(const TwoViewPlanInput &in) {
     p.score_groups = (uint32_t)((in.hypotheses + kEpipolarScoreGroup - 1) / kEpipolarScoreGroup);
     p.score_lds = sizeof(float) * 4 * kEpipolarScoreTile;
     p.select_per_thread = (in.hypotheses + kEpipolarScanBlock - 1) / kEpipolarScanBlock;
-    p.off_points = 16;
-    p.off_list = p.off_points + up16(sizeof(float) * 4 * (size_t)in.n);
-    p.off_counts = p.off_list + up16(sizeof(int32_t) * (size_t)in.n);
-    p.off_models = p.off_counts + up16(sizeof(int32_t) * slots * (size_t)in.hypotheses);
-    p.off_valid = p.off_models + up16(sizeof(float) * 9 * slots * (size_t)in.hypotheses);
-    p.bytes = p.off_valid + up16(slots * (size_t)in.hypotheses);
+    ftk_layout16 ws;  // cannot wrap: the limits hold every count below 2^17
+    p.m = ws.take<int32_t>(1);
+    p.points = ws.take<float4>(n);
+    p.list = ws.take<int32_t>(n);
+    p.counts = ws.take<int32_t>(k);
+    p.models = ws.take<float>(9 * k);
+    p.valid = ws.take<uint8_t>(k);
+    p.bytes = ws.bytes();
     return p;
 }
 

@@ -6,6 +6,7 @@
 #pragma once
 
 #include "ftk_device.h"
+#include "ftk_layout.h"
 
 namespace ftk {
 
@@ -49,9 +50,13 @@ struct TwoViewPlan {
     uint32_t score_groups;      // grid.y: groups of kEpipolarScoreGroup hypotheses
     size_t score_lds;           // bytes of a tile of normalised coordinates
     int32_t select_per_thread;  // hypotheses of ONE model a thread of the select workgroup reduces
-    // the workspace, byte offsets (16-byte aligned): M (one int32, padded), the participants' normalised (x1, y1, x2, y2), their indices,
-    // counts [slots][K], models [slots][K][9], validity flags [slots][K]; the same for every mode
-    size_t off_points, off_list, off_counts, off_models, off_valid, bytes;
+    // the workspace (ftk_layout.h), in this order: M, the participants' normalised (x1, y1, x2, y2) [n], their indices [n], counts [slots][K],
+    // models [slots][K][9], validity flags [slots][K]; the same for every mode
+    ftk_slot16<int32_t> m, list, counts;
+    ftk_slot16<float4> points;
+    ftk_slot16<float> models;
+    ftk_slot16<uint8_t> valid;
+    size_t bytes;
 };
 const char *two_view_refusal_name(TwoViewRefusal r);
 TwoViewPlan two_view_plan(const TwoViewPlanInput &in);

@@ -22,16 +22,17 @@ TwoViewPosePlan two_view_pose_plan(const TwoViewPosePlanInput &in) {
         p.refused = TwoViewPoseRefusal::Points;
         return p;
     }
-    const auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
     p.refused = TwoViewPoseRefusal::None;
     p.launches = 5;
     p.scan_per_thread = (in.n + kEpipolarScanBlock - 1) / kEpipolarScanBlock;
     p.tiles = (uint32_t)((in.n + kPoseTile - 1) / kPoseTile);
     p.moment_lds = sizeof(float) * kPoseMoments * kPoseTile;
-    p.off_points = 16;
-    p.off_totals = p.off_points + up16(sizeof(float) * 4 * (size_t)in.n);
-    p.off_model = p.off_totals + up16(sizeof(float) * kPoseMoments * (size_t)p.tiles);
-    p.bytes = p.off_model + sizeof(float) * kPoseModelFloats;
+    ftk_layout16 ws;  // cannot wrap: n <= 2^16
+    p.m = ws.take<int32_t>(1);
+    p.points = ws.take<float4>((size_t)in.n);
+    p.totals = ws.take<float>(kPoseMoments * (size_t)p.tiles);
+    p.model = ws.take<float>(kPoseModelFloats);
+    p.bytes = ws.bytes();
     return p;
 }
 

@@ -24,9 +24,12 @@ struct TwoViewPosePlan {
     int32_t scan_per_thread;     // consecutive points a thread of the scan workgroup owns (<= 64)
     uint32_t tiles;              // grid of the moment, count and finish kernels: tiles of kPoseTile, sized for n (M is on the device)
     size_t moment_lds;           // bytes of a tile's 45 x 256 tree
-    // the workspace, byte offsets (16-byte aligned): M (one int32, padded), the participants' calibrated (x1, y1, x2, y2), the tile totals
-    // [tiles][45], the model block [kPoseModelFloats]
-    size_t off_points, off_totals, off_model, bytes;
+    // the workspace (ftk_layout.h), in this order: M, the participants' calibrated (x1, y1, x2, y2) [n], the tile totals [tiles][45], the
+    // model block [kPoseModelFloats]
+    ftk_slot16<int32_t> m;
+    ftk_slot16<float4> points;
+    ftk_slot16<float> totals, model;
+    size_t bytes;
 };
 const char *two_view_pose_refusal_name(TwoViewPoseRefusal r);
 TwoViewPosePlan two_view_pose_plan(const TwoViewPosePlanInput &in);

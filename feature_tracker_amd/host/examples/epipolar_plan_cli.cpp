@@ -26,8 +26,8 @@ int main() {
             printf(" scan_block=%d scan_per_thread=%d scan_lds=%zu hyp_block=%d hyp_blocks=%u hyp_lds=%zu score_tile=%d score_group=%d score_tiles=%u"
                    " score_groups=%u score_lds=%zu select_per_thread=%d off_points=%zu off_list=%zu off_counts=%zu off_models=%zu off_valid=%zu bytes=%zu",
                    ftk::kEpipolarScanBlock, p.scan_per_thread, p.scan_lds, ftk::kEpipolarHypBlock, p.hyp_blocks, p.hyp_lds, ftk::kEpipolarScoreTile,
-                   ftk::kEpipolarScoreGroup, p.score_tiles, p.score_groups, p.score_lds, p.select_per_thread, p.off_points, p.off_list, p.off_counts,
-                   p.off_models, p.off_valid, p.bytes);
+                   ftk::kEpipolarScoreGroup, p.score_tiles, p.score_groups, p.score_lds, p.select_per_thread, p.points.offset, p.list.offset, p.counts.offset,
+                   p.models.offset, p.valid.offset, p.bytes);
         }
         printf("\n");
     }

@@ -28,7 +28,7 @@ int main() {
                    " off_list=%zu off_count=%zu off_plane=%zu off_dilated=%zu bytes=%zu",
                    p.rows, p.cols, p.distance, p.reach, p.capacity, ftk::kKeypointScoreTile, p.score_grid_x, p.score_grid_y, p.score_lds, p.image_blocks,
                    p.stamp_blocks, ftk::kKeypointRankTile, p.rank_blocks, ftk::kKeypointDescribeWaves, p.describe_blocks, p.launches, p.memsets,
-                   p.off_tmp, p.off_wmax, p.off_list, p.off_count, p.off_plane, p.off_dilated, p.bytes);
+                   p.tmp.offset, p.wmax.offset, p.list.offset, p.count.offset, p.plane.offset, p.dilated.offset, p.bytes);
         }
         printf("\n");
     }

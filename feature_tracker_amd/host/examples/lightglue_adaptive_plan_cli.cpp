@@ -25,8 +25,8 @@ int main() {
                    " select_blocks=%u remap_blocks=%u step_launches=%d finish_launches=%d off_layer=%zu off_assign=%zu off_head_w=%zu off_head_b=%zu"
                    " off_src0=%zu off_src1=%zu off_match=%zu off_status=%zu bytes=%zu",
                    ftk::kAdaptiveConfThreads, p.conf_blocks, ftk::kAdaptiveDecideThreads, p.decide_blocks, ftk::kAdaptiveGatherThreads, p.gather_blocks,
-                   ftk::kAdaptiveCopyThreads, p.select_blocks, p.remap_blocks, p.step_launches, p.finish_launches, p.off_layer, p.off_assign,
-                   p.off_head_w, p.off_head_b, p.off_src0, p.off_src1, p.off_match, p.off_status, p.bytes);
+                   ftk::kAdaptiveCopyThreads, p.select_blocks, p.remap_blocks, p.step_launches, p.finish_launches, p.layer.offset, p.assign.offset,
+                   p.head_w.offset, p.head_b.offset, p.src0.offset, p.src1.offset, p.match.offset, p.status.offset, p.bytes);
         }
         printf("\n");
     }

@@ -28,7 +28,7 @@ int main() {
                    " off_z=%zu off_lse_row=%zu off_lse_col=%zu off_ls0=%zu off_ls1=%zu bytes=%zu",
                    (long long)p.row_stride, p.vec, 64 * ftk::kAssignGemmWaves, p.project_grid_x, p.project_grid_y, p.sim_grid_x, p.sim_grid_y,
                    ftk::kAssignNormThreads, p.norm_row_blocks, p.norm_col_blocks, p.norm_lds, ftk::kAssignFinishThreads, p.finish_grid_x,
-                   p.finish_grid_y, p.launches, p.off_md, p.off_z, p.off_lse_row, p.off_lse_col, p.off_ls0, p.off_ls1, p.bytes);
+                   p.finish_grid_y, p.launches, p.md.offset, p.z.offset, p.lse_row.offset, p.lse_col.offset, p.ls0.offset, p.ls1.offset, p.bytes);
         }
         printf("\n");
     }

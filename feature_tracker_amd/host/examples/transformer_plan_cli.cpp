@@ -26,7 +26,7 @@ int main() {
                    " off_qkv=%zu off_ctx=%zu off_msg=%zu off_hidden=%zu off_x1=%zu bytes=%zu weight_floats=%zu",
                    p.head_dim, p.vec_linear, p.vec_attn, 64 * ftk::kLinearWaves, p.linear_grid_x, p.grid_y_d, p.grid_y_2d, p.grid_y_3d,
                    ftk::kAttnThreads, p.attn_out_tiles, p.attn_grid_x, p.attn_grid_y, p.attn_grid_z, ftk::kNormThreads, p.norm_blocks,
-                   p.launches, p.off_qkv, p.off_ctx, p.off_msg, p.off_hidden, p.off_x1, p.bytes, p.weight_floats);
+                   p.launches, p.qkv.offset, p.ctx.offset, p.msg.offset, p.hidden.offset, p.x1.offset, p.bytes, p.weight_floats);
             for (int k = 0; k < 10; ++k) {
                 printf(" w_self%d=%zu w_cross%d=%zu", k, p.w_self[k], k, p.w_cross[k]);
             }

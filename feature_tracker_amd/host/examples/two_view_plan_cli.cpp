@@ -28,7 +28,7 @@ int main() {
                    " off_models=%zu off_valid=%zu bytes=%zu",
                    p.run_fundamental, p.run_homography, p.launches, ftk::kEpipolarScanBlock, p.scan_per_thread, ftk::kEpipolarHypBlock, p.hyp_blocks,
                    p.hyp_lds, ftk::kEpipolarScoreTile, ftk::kEpipolarScoreGroup, p.score_tiles, p.score_groups, p.score_lds, p.select_per_thread,
-                   p.off_points, p.off_list, p.off_counts, p.off_models, p.off_valid, p.bytes);
+                   p.points.offset, p.list.offset, p.counts.offset, p.models.offset, p.valid.offset, p.bytes);
         }
         printf("\n");
     }

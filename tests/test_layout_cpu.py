@@ -1,7 +1,9 @@
 """The staging layouts of the host-buffer entry points (csrc/ftk_layout.h) on the CPU, through host/build/layout_cli: for the sequence
 of take() calls every entry makes, each offset, each copy span and the total equal the formulas the entries spelled out by hand
 before the layout type existed (restated below from that source: columns of align_up(..., 256) and sums of them).  Three tails were
-irregular there (a bare `+ 256`, an unpadded status array); as slots of their own they may only grow, by at most 256 bytes."""
+irregular there (a bare `+ 256`, an unpadded status array); as slots of their own they may only grow, by at most 256 bytes.
+The 16-byte flavour of the same class, which lays out the caller-owned workspaces (csrc/*_plan.h), is held to the take rule itself at
+the end of the file; the workspaces' own byte formulas are restated in the *_args_cpu.py tests."""
 import os
 import subprocess
 
@@ -25,7 +27,7 @@ def cli(lines):
     r = subprocess.run([EXE], input="\n".join(lines) + "\n", capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stderr
     out = [{k: int(v) for k, v in (kv.split("=") for kv in line.split())} for line in r.stdout.splitlines()]
-    assert len(out) == sum(1 for l in lines if l != "new")
+    assert len(out) == sum(1 for l in lines if l not in ("new", "new16"))
     return out
 
 
@@ -133,3 +135,44 @@ def test_a_wrapping_count_voids_the_layout():
                   ["new", f"take 16 {SIZE_MAX // 16 + 1}", "take 1 1", "total"]):  # and nothing taken later revives it
         out = cli(lines)
         assert out[-2]["ok"] == 0 and out[-1] == {"total": SIZE_MAX, "ok": 0}, lines
+
+
+def up16(x):
+    return (x + 15) // 16 * 16
+
+
+def test_sixteen_byte_slots_in_call_order():
+    """Every slot on the next 16-byte boundary, in call order; the payload unpadded, the padded size the payload rounded up to 16 bytes,
+    for byte sizes that are multiples of 16 (0 aside), one below, one above, and far from one."""
+    takes = [(4, 1), (16, 7), (4, 4), (4, 5), (1, 15), (1, 16), (1, 17), (8, 2), (8, 3), (2, 8), (2, 9), (4, 45 * 257), (1, 4096 + 1), (4, 32)]
+    out = cli(["new16"] + [f"take {e} {c}" for e, c in takes] + ["span 1 3", "span 0 13", "total"])
+    end = 0
+    for (e, c), s in zip(takes, out):
+        assert s == {"offset": end, "size": e * c, "padded": up16(e * c), "ok": 1}, (e, c)
+        assert s["offset"] % 16 == 0 and 0 <= s["padded"] - s["size"] < 16
+        end += up16(e * c)
+    assert out[-3] == {"span": up16(16 * 7) + 16 + up16(4 * 5)} and out[-2] == {"span": end}
+    assert out[-1] == {"total": end, "ok": 1}
+    assert sum(1 for e, c in takes if e * c % 16 == 0) >= 4 and sum(1 for e, c in takes if e * c % 16 != 0) >= 4
+
+
+def test_a_sixteen_byte_slot_of_count_zero_occupies_nothing():
+    out = cli(["new16", "take 4 0", "take 8 3", "take 1 0", "take 16 0", "take 4 1", "take 8 0", "total"])
+    assert [s["offset"] for s in out[:-1]] == [0, 0, 32, 32, 32, 48]  # an empty slot reports the running end
+    assert [s["padded"] for s in out[:-1]] == [0, 32, 0, 0, 16, 0] and [s["size"] for s in out[:-1]] == [0, 24, 0, 0, 4, 0]
+    assert all(s["ok"] == 1 for s in out) and out[-1]["total"] == 48
+
+
+def test_a_wrapping_count_voids_the_sixteen_byte_layout():
+    last_good = (SIZE_MAX - 15) // 4  # 4 * count == 2^64 - 16: its padded end is still a size_t
+    out = cli(["new16", f"take 4 {last_good}", "total"])
+    assert out[0]["ok"] == 1 and out[1] == {"total": 4 * last_good, "ok": 1}
+    for lines in (["new16", f"take 4 {last_good + 1}", "total"],                     # 2^64 - 12 bytes: only the padding wraps
+                  ["new16", f"take 4 {SIZE_MAX // 4 + 2}", "total"],                 # the product itself wraps to 4
+                  ["new16", "take 4 5", f"take 8 {SIZE_MAX // 8 - 3}", "total"],     # fits alone, not behind the first slot
+                  ["new16", f"take 16 {SIZE_MAX // 16 + 1}", "take 1 1", "total"]):  # and nothing taken later revives it
+        out = cli(lines)
+        assert out[-2]["ok"] == 0 and out[-1] == {"total": SIZE_MAX, "ok": 0}, lines
+    # a 256-byte layout made after a 16-byte one is a 256-byte layout again
+    out = cli(["new16", "take 1 1", "new", "take 1 1", "take 1 1", "total"])
+    assert [s["offset"] for s in out[:3]] == [0, 0, 256] and out[-1] == {"total": 512, "ok": 1}
