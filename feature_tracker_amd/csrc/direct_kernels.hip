@@ -17,7 +17,7 @@
 //   * wave 0 is the CONSUMER: lane k < 27 adds row k of every chunk in stream order (the exact-order
 //     chain of the KLT kernels, klt_basic_kernels.hip);
 //   * one barrier per round of 7 chunks; after the last round wave 0 solves the 6 x 6 system with
-//     the lane-parallel Eigen-compatible LDLT (klt_common.h: rows on lanes 0..5), publishes dx in
+//     the lane-parallel Eigen-compatible LDLT (klt_ldlt.h: rows on lanes 0..5), publishes dx in
 //     LDS, and every thread applies the same pose update, so the pose lives in registers.
 //
 // Projection of the features (cur_pixel_uv, :141-142) happens once per iteration in a prologue pass
@@ -25,7 +25,8 @@
 // on the reference-frame point only and is recomputed per lane (12 products).
 // fp32 throughout, no contraction; quaternion arithmetic as defined in oracle/oracle_direct_method.c.
 #define FTK_CHAIN_ROUND 8  // 32 terms per prefetch round (four: +2 % on the spread kernel, whose consumer does nothing but chain; the one-workgroup kernel does not care)
-#include "klt_common.h"
+#include "klt_chain.h"
+#include "klt_ldlt.h"
 #include "match_plan.h"
 
 namespace ftk {
@@ -92,7 +93,7 @@ __device__ __forceinline__ void q_rotate(const Quat &q, float vx, float vy, floa
 // and the images stay in L2), in two halves so that the SIX taps of a term have all their 24 byte loads in flight before the
 // first value is formed: the producers were bound by six dependent round trips per term (sample() returns early on an invalid
 // coordinate, and the compiler keeps the taps behind one another).  An invalid tap reads pixel (0, 0) and is not used.  Same
-// validity rule, fractions, weight products and sum order as sample() (klt_common.h).
+// validity rule, fractions, weight products and sum order as sample() (klt_window.h).
 struct DmTap {
     bool valid;
     float w_tl, w_tr, w_bl, w_br;
@@ -137,7 +138,7 @@ __device__ __forceinline__ float dm_chain_chunk(float acc, const float *row) {
     return acc;
 }
 
-// The spread kernel's chain: a QUAD of lanes per sum (klt_common.h, chain_quad_step16 — the same left-to-right sum, 16 terms per
+// The spread kernel's chain: a QUAD of lanes per sum (klt_chain.h, chain_quad_step16 — the same left-to-right sum, 16 terms per
 // ds_read_b128 and 4.84 cycles per term instead of one lane's ~7).  `t`: this lane's first float4 of the round's first chunk (row of
 // its sum, floats 4 (lane & 3) ..); a chunk's 64 terms are four steps of 16, the chunks of a round lie kDmTerms rows apart.  The
 // reads of chunk w + 1 are issued before chunk w's 64 adds; with kChunks a constant the loop unrolls and every address is an
@@ -276,7 +277,7 @@ __device__ __forceinline__ void dm_term(const float4 *feat, const DirectParams &
     }
 }
 
-// wave 0: the 27 sums (lane k < 27 holds sum k) -> full symmetric H in LDS -> lane-parallel LDLT (klt_common.h) -> dx at sums[68..74)
+// wave 0: the 27 sums (lane k < 27 holds sum k) -> full symmetric H in LDS -> lane-parallel LDLT (klt_ldlt.h) -> dx at sums[68..74)
 // (kPublish = false: the sums already lie in sums[0 .. 27), written behind a barrier by the waves that chained them)
 template <bool kPublish = true>
 __device__ __forceinline__ void dm_solve(float *sums, float acc, int lane) {

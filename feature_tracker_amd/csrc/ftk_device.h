@@ -36,19 +36,19 @@ struct KltParams {
     uint32_t *iters;       // may be null
     const int32_t *order;  // may be null: launch slot -> feature index (a permutation of [0, n) made by an earlier launch's sort block)
     uint32_t *sched_iters; // may be null: iteration counts kept by the context for the launch order of later calls
-    // Position-keyed slot swaps (klt_common.h klt_resolve_feature), all null / 0 when off: a coarse grid over the level-0 image in
+    // Position-keyed slot swaps (klt_order.h klt_resolve_feature), all null / 0 when off: a coarse grid over the level-0 image in
     // which every feature leaves its iteration count, tagged with the call number; one claim word per launch slot; this call's number
     uint32_t *sched_grid;
     uint32_t *sched_claim;
     uint32_t *sched_flags;  // [2]: (call number << 1 | "the counts that call sorted had no tail"), written by the sort block of a launch
     uint32_t sched_call;
-    // the call's longest feature, reported for the next call's wave policy (klt_common.h tail_report; null: not reported)
+    // the call's longest feature, reported for the next call's wave policy (klt_order.h tail_report; null: not reported)
     uint32_t *tail_dev;
     uint32_t *tail_host;
     uint32_t tail_call;
     int32_t long_tail;          // host-side note: this variant's recent calls had a feature of many iterations (klt_plan.cpp; nothing reads it back)
     const uint32_t *sort_iters;  // may be null: the previous call's counts; one extra workgroup (block 0) sorts them ...
-    int32_t *sort_order_out;     // ... into this permutation, longest first (klt_common.h, klt_order_block)
+    int32_t *sort_order_out;     // ... into this permutation, longest first (klt_order.h, klt_order_block)
     const float *sort_ref_uv;    // reference positions the sort block may use for the spatial (tile) order: ref_uv, or null when this
                                  // launch's outputs overwrite them (in-place position buffer: the two passes of the sort would disagree)
     int32_t n;             // features in the buffers
@@ -73,7 +73,7 @@ struct KltParams {
     uint32_t magic_rwq, magic_cwq;  // division by window cols / 4
     int32_t waves_per_feature;  // workgroup = 64 * waves_per_feature lanes
     int32_t px_floats;          // per-pixel floats behind a0 in the generic kernel's LDS carve: 3, 4 (one float4 record: non-fast affine) or 6 (chunked LSSD)
-    int32_t quad_chain;         // chunked one-wave LSSD levels: 1 = the exact-order sums through the DPP network (klt_common.h "quad chain": fewer
+    int32_t quad_chain;         // chunked one-wave LSSD levels: 1 = the exact-order sums through the DPP network (klt_chain.h "quad chain": fewer
                                 // instructions on a lone feature's critical path), 0 = one lane per sum (fewer LDS bytes and plain adds: better when
                                 // the launch oversubscribes the chip — config 4: 136 against 141 us, with luminance 255 against 285)
     int32_t terms_floats;       // floats of the generic kernel's `terms` LDS region: K * Ppad, or the 64-pixel ring of a chunked variant
@@ -119,7 +119,7 @@ __host__ __device__ constexpr int32_t klt_byte_pitch(int32_t cols) {
     return pow2;
 }
 // Image byte offset of 8-byte unit idx of a window relative to the window's origin: row idx >> shift, position idx & mask, with
-// shift = log2(pitch / 8).  The one place that says where a unit comes from (klt_common.h issue_octets; klt_plan_cli prints it).
+// shift = log2(pitch / 8).  The one place that says where a unit comes from (klt_stage.h issue_octets; klt_plan_cli prints it).
 __host__ __device__ constexpr uint32_t klt_byte_unit_offset(uint32_t idx, int shift, uint32_t im_cols) {
     return (idx >> shift) * im_cols + 8u * (idx & ((1u << shift) - 1u));
 }
@@ -143,7 +143,7 @@ __host__ __device__ constexpr void klt_fill_geometry(KltParams &p) {
     p.patch_rows = 2 * p.half_rows + 1;
     p.patch_cols = 2 * p.half_cols + 1;
     p.P = p.patch_rows * p.patch_cols;
-    p.Ppad = (p.P + 15) & ~15;  // (a multiple of 16 since round 5: the quad chains add 16 terms per step, klt_common.h; the padding holds exact zeros)
+    p.Ppad = (p.P + 15) & ~15;  // (a multiple of 16 since round 5: the quad chains add 16 terms per step, klt_chain.h; the padding holds exact zeros)
     p.ex_rows = p.patch_rows + 2;
     p.ex_cols = p.patch_cols + 2;
     p.E = p.ex_rows * p.ex_cols;
@@ -192,7 +192,7 @@ __host__ __device__ constexpr bool klt_byte_windows_ok(const KltParams &p) {
 // first.  last_table: 2^16 words; pred: n bytes; hist_and_cursor: kSchedOrderWords (klt_sched.h) words (zeroed here).
 hipError_t klt_position_order_launch(const float *ref_uv, int32_t n, const uint32_t *last_table, uint32_t last_call, uint8_t *pred, uint32_t *hist_and_cursor,
                                      int32_t *order, hipStream_t stream);
-// Lane-parallel 6x6 LDLT (klt_common.h) on n systems, one wave each: the test hook behind ftk_ldlt6_solve.
+// Lane-parallel 6x6 LDLT (klt_ldlt.h) on n systems, one wave each: the test hook behind ftk_ldlt6_solve.
 hipError_t ldlt6_launch(const float *d_a, const float *d_b, float *d_x, int n, hipStream_t stream);
 
 // Reference descriptors a thread of the register-tiled Hamming scan keeps in registers (a 256-thread workgroup covers

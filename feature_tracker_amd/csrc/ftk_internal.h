@@ -82,7 +82,7 @@ struct ftk_context {
     // sort block of the tracker launches makes from them, double-buffered
     ftk_buffer sched_iters[2];  // uint32_t
     ftk_buffer sched_order[2];  // int32_t
-    // position-keyed slot swaps (klt_common.h sched_resolve_slot): iteration counts by position (two hash tables), one claim word per launch slot
+    // position-keyed slot swaps (klt_order.h sched_resolve_slot): iteration counts by position (two hash tables), one claim word per launch slot
     ftk_buffer sched_grid, sched_claim;  // uint32_t
     ftk_buffer sched_pred;            // uint8_t: predicted iteration count of every feature of the call in hand (position-keyed launch order)
     ftk::KltSchedState sched;         // which order the next call gets (klt_sched.h klt_sched_step)

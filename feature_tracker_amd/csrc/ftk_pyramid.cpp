@@ -20,7 +20,7 @@ int make_pyramid(ftk_context *ctx, ftk_pyramid **out) {
     return FTK_OK;
 }
 
-// The trackers index a level with 32-bit pixel offsets formed on the 24-bit multiplier (klt_common.h px()).
+// The trackers index a level with 32-bit pixel offsets formed on the 24-bit multiplier (klt_scalar.h px()).
 bool level_addressable(int32_t rows, int32_t cols) { return rows < (1 << 24) && cols < (1 << 24) && (long long)rows * cols < (1ll << 32); }
 
 int check_levels(ftk_context *ctx, const ftk_image *levels, int32_t n_levels) {

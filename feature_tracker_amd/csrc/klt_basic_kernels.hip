@@ -26,7 +26,7 @@
 //     aligned dwords around its pixel in each of its two rows and shifts them into place (node_tap:
 //     as many LDS reads as with pairs; four single-byte reads measured 6 % slower than pairs, and a
 //     16-bit read at an odd address 22 %, docs/LAB_NOTES.md).  The generic and the one-wave kernels
-//     keep 16-bit pixel pairs (klt_common.h Win), whose staging is four times the work.  The
+//     keep 16-bit pixel pairs (klt_window.h Win), whose staging is four times the work.  The
 //     reference window is one row / column larger than the generic kernel's so that a valid tap is
 //     always covered (a coordinate sum may round up to the next integer), hence no global-memory
 //     fallback sampler exists here.
@@ -39,8 +39,13 @@
 //
 // Arithmetic contract as in klt_kernels.hip: IEEE fp32, no contraction, correctly rounded division.
 #define FTK_CHAIN_ROUND 4  // 16 terms per round: the consumer wave holds 32 VGPRs of prefetched terms
-#include "klt_common.h"
+#include "klt_chain.h"
+#include "klt_ldlt.h"
+#include "klt_order.h"
 #include "klt_plan.h"
+#include "klt_scalar.h"
+#include "klt_stage.h"
+#include "klt_window.h"
 
 namespace ftk {
 namespace {
@@ -72,7 +77,7 @@ static_assert(!PbChunks<6, 6>::kByRows && !PbChunks<5, 5>::kByRows && !PbChunks<
 // Ring rows are kChunk + 4 floats apart: the consumer's lanes read 16 bytes each from DIFFERENT rows
 // at the same column, and a row pitch of 256 B would put all of them on the same four banks.
 // (round 5: the quad chain reads 16 bytes per lane, the four lanes of a quad 64 consecutive bytes of ONE row; a pitch of 80 floats puts
-// the rows of the two quads of an 8-lane group on the two halves of the banks.  Its quads follow klt_common.h chain_quads_left.)
+// the rows of the two quads of an 8-lane group on the two halves of the banks.  Its quads follow klt_chain.h chain_quads_left.)
 constexpr int kRingRow = kChunk + 16;
 constexpr int kTerms = 5;   // 0 H00, 1 H11, 2 H01, 3 -fx*ft, 4 -fy*ft (basic_klt.cpp:139-144)
 // 8-byte window loads a thread holds in flight per window: what the instantiation's windows need on its fewest threads (one wave
@@ -100,7 +105,7 @@ struct PbLds {
     float *lattice;           // [n_r][n_c] reference bilinear values
     float *sol;               // 4 floats: published solution
     uint32_t *slots;          // 16: node counts (0, 1), valid-pixel counts by iteration parity (4 + 4 * parity + wave)
-    // Byte windows (klt_common.h "Byte windows"), rows pb_rwin_pitch / pb_cwin_pitch bytes apart, inside regions that are still sized
+    // Byte windows (klt_stage.h "Byte windows"), rows pb_rwin_pitch / pb_cwin_pitch bytes apart, inside regions that are still sized
     // for 16-bit pixel pairs (pb_lds_bytes: 2 * pad4(rows * cols) bytes each; klt_byte_windows_ok holds the pitch to that room).
     uint8_t *ref_win;         // two reference windows (this level, next level), ref_win_stride BYTES apart
     int ref_win_stride;
@@ -428,7 +433,7 @@ template <bool SOLO, int HR, int HC, bool TREE>
 __global__ void __attribute__((amdgpu_waves_per_eu(kWavesPerEu))) __launch_bounds__(256) klt_basic_inverse_pipelined_kernel(const KltParams p_arg) {
     // `p` carries everything but the level tables, which stay in the kernel argument (p_arg.ref / p_arg.cur): a local copy whose
     // arrays are indexed with a run-time level would be placed in scratch memory (measured: the kernel twice as slow).
-    klt_touch_kernarg<sizeof(KltParams)>();  // every line of the argument block requested up front (klt_common.h)
+    klt_touch_kernarg<sizeof(KltParams)>();  // every line of the argument block requested up front (klt_scalar.h)
     KltParams p = p_arg;
     if constexpr (HR > 0 && HC > 0) {
         p.half_rows = HR;
@@ -444,7 +449,7 @@ __global__ void __attribute__((amdgpu_waves_per_eu(kWavesPerEu))) __launch_bound
     uint32_t id;
     float4 *lds_mine = lds_raw;
     // block 0 of a launch that carries the previous call's iteration counts sorts them into a later call's launch order
-    // (klt_common.h) beside the feature workgroups; the feature blocks follow it
+    // (klt_order.h) beside the feature workgroups; the feature blocks follow it
     uint32_t block = blockIdx.x;
     if (p.sort_iters) {
         if (block == 0) {
@@ -480,7 +485,7 @@ __global__ void __attribute__((amdgpu_waves_per_eu(kWavesPerEu))) __launch_bound
     }
     const bool younger = 2u * id >= (uint32_t)p.n;  // launch slot in the later-dispatched half (set_level_priority)
     if (p.sched_claim != nullptr) {
-        // a trade of places between an early slot and a late one whose POSITION predicts many iterations (klt_common.h
+        // a trade of places between an early slot and a late one whose POSITION predicts many iterations (klt_order.h
         // sched_resolve_slot; one wave decides for the workgroup)
         bool swapped_in = false;
         if (SOLO) {
@@ -659,7 +664,7 @@ __global__ void __attribute__((amdgpu_waves_per_eu(kWavesPerEu))) __launch_bound
         // ---- Gauss-Newton iterations (TrackOneFeature, basic_klt.cpp:88-116) ----
         for (uint32_t iter = 0; iter < p.max_iteration; ++iter) {
             ++iters;
-            if (iter > 0 && !win_covers(cw, cur_u, cur_v)) {  // four float compares in the usual case (klt_common.h win_set_cover)
+            if (iter > 0 && !win_covers(cw, cur_u, cur_v)) {  // four float compares in the usual case (klt_window.h win_set_cover)
                 // restage the current window when the patch has left it (wave-uniform)
                 footprint_origin(p, cur_u, cur_v, need_r, need_c);
                 const long long nr = need_r, nc = need_c;
@@ -742,7 +747,7 @@ __global__ void __attribute__((amdgpu_waves_per_eu(kWavesPerEu))) __launch_bound
                     }
                     pb_sync(solo);
                     if (consumer) {
-                        // the whole wave: quad k = lanes 4 k .. 4 k + 3 carries sum k (klt_common.h, "quad chain"); the quads behind the
+                        // the whole wave: quad k = lanes 4 k .. 4 k + 3 carries sum k (klt_chain.h, "quad chain"); the quads behind the
                         // fifth follow its rows and are ignored
                         // the step's chunks are all in the ring: the full ones in one go (the next chunk's reads under this one's adds),
                         // then the patch's last chunk if it has fewer than 49 terms

@@ -26,8 +26,13 @@
 // Arithmetic contract as in klt_kernels.hip: IEEE fp32, no contraction, correctly rounded division, every sum strictly in
 // row-major pixel order on one lane.  Results are bit-identical to the generic kernel and to the oracle (tests/test_klt_gpu.py).
 #define FTK_CHAIN_ROUND 4
-#include "klt_common.h"
+#include "klt_chain.h"
+#include "klt_ldlt.h"
+#include "klt_order.h"
 #include "klt_plan.h"
+#include "klt_scalar.h"
+#include "klt_stage.h"
+#include "klt_window.h"
 
 namespace ftk {
 namespace {
@@ -169,7 +174,7 @@ __device__ __forceinline__ void fk_ex_from_rows(const RefRows<N> &q, int lane, c
     }
 }
 
-// Eigen's LDLT of the 2 x 2 Hessian (ldlt_solve<2>, klt_common.h) split in two: the factorisation is a function of H alone, H is
+// Eigen's LDLT of the 2 x 2 Hessian (ldlt_solve<2>, klt_ldlt.h) split in two: the factorisation is a function of H alone, H is
 // fixed for a level (basic_klt_fast.cpp:64-99), so it is done once per level and every iteration only runs the substitution — the
 // same operations on the same operands in the same order as ldlt_solve<2>, hence the same bits.
 struct Ldlt2 {
@@ -205,8 +210,8 @@ __device__ __forceinline__ void ldlt2_apply(const Ldlt2 &f, float b0, float b1, 
     y1 -= f.l10 * y0;
     const float num = lane == 0 ? y0 : y1, den = lane == 0 ? f.d0 : f.d1;
     const float quot = (fabsf(den) > 1.17549435e-38f) ? num / den : 0.0f;
-    y0 = uniform_lane(quot, 0);
-    y1 = uniform_lane(quot, 1);
+    y0 = bcast_lane(quot, 0);
+    y1 = bcast_lane(quot, 1);
     y0 -= f.l10 * y1;
     x0 = f.swapped ? y1 : y0;
     x1 = f.swapped ? y0 : y1;
@@ -313,7 +318,7 @@ __global__ void __attribute__((amdgpu_waves_per_eu(kWavesPerEu))) __launch_bound
         cw.c_lo = wadd(need_c, -p.cwin_margin);
         win_set_cover(p, cw);
         if (cur_fits && window_inside(cur, cw.r_lo, cw.c_lo, cw.rows, cw.cols)) {
-            RawQuads<kFkCurQuads> qc;
+            RawOctets<kFkCurQuads> qc;
             issue_quads(qc, b, cur, cw.r_lo, cw.c_lo, cw.rows, cw.cols, p.magic_cwq);
             // the zero padding of the term rows (pixels P .. pitch - 1 are never written again) while the loads fly
             // (the affine ring has none: every sweep writes all 64 columns of the rows it chains)
@@ -382,7 +387,7 @@ __global__ void __attribute__((amdgpu_waves_per_eu(kWavesPerEu))) __launch_bound
         const bool all_ref_valid = ref_interior;
         fk_fence();
         // ---- the next level's inputs are requested now and arrive while this level runs ----
-        RawQuads<kFkCurQuads> qcn;
+        RawOctets<kFkCurQuads> qcn;
         int nr_lo = 0, nc_lo = 0, ncr_lo = 0, ncc_lo = 0;
         bool next_interior = false, next_cur_async = false;
         if (level > 0) {
@@ -514,7 +519,7 @@ __global__ void __attribute__((amdgpu_waves_per_eu(kWavesPerEu))) __launch_bound
                     // the exact-order sums: lanes 0 / 1 the bias, and in the level's first iteration lanes 2 - 4 the Hessian
                     const int chains = iter == 0 ? kFkTerms : 2;
                     float acc = 0.0f;
-                    // every lane: quad q carries sum q (klt_common.h "quad chain"); the quads behind the last sum follow its row, ignored
+                    // every lane: quad q carries sum q (klt_chain.h "quad chain"); the quads behind the last sum follow its row, ignored
                     constexpr int kSumLanes = 4;
                     acc = chain_quads_row<true>(0.0f, c.terms + min(lane >> 2, chains - 1) * pitch + 4 * (lane & 3), p.Ppad >> 4);
                     const int acc_bits = __float_as_int(acc);

@@ -36,8 +36,15 @@
 // LDS latency; the default of 8 costs 32 more VGPRs in every variant (basic 104 -> 72, lssd fast 111 -> 85, affine
 // inverse 134 -> 122, which then fits 4 waves per SIMD instead of 3).
 #define FTK_CHAIN_ROUND 4
-#include "klt_common.h"
+#include "klt_chain.h"
+#include "klt_ldlt.h"
+#include "klt_order.h"
 #include "klt_plan.h"
+#include "klt_scalar.h"
+#include "klt_stage.h"
+#include "klt_window.h"
+
+#include <type_traits>
 
 namespace ftk {
 namespace {
@@ -714,7 +721,7 @@ __device__ __forceinline__ void basic_level_fast(const Blk &b, const KltParams &
 }
 
 // ---------------------------------------------------------------------------------------------
-// Affine KLT (6x6).  The chain indices A_* of its 18 + 6 sums, affine_dense_slots and kAffineDiagLane live in klt_common.h
+// Affine KLT (6x6).  The chain indices A_* of its 18 + 6 sums, affine_dense_slots and kAffineDiagLane live in klt_ldlt.h
 // (shared with the one-wave fast kernel, klt_fast_kernels.hip).
 // ---------------------------------------------------------------------------------------------
 struct AffineState {
@@ -1095,10 +1102,10 @@ __device__ __forceinline__ void se2_update(LssdState &s, const float (&v)[3], in
     const float norm = sqrtf(n00 * n00 + n10 * n10);
     if (kLanes) {
         const float q = (lane == 0 ? n00 : (lane == 1 ? n01 : (lane == 2 ? n10 : n11))) / norm;
-        s.r00 = uniform_lane(q, 0);
-        s.r01 = uniform_lane(q, 1);
-        s.r10 = uniform_lane(q, 2);
-        s.r11 = uniform_lane(q, 3);
+        s.r00 = bcast_lane(q, 0);
+        s.r01 = bcast_lane(q, 1);
+        s.r10 = bcast_lane(q, 2);
+        s.r11 = bcast_lane(q, 3);
     } else {
         s.r00 = n00 / norm;
         s.r01 = n01 / norm;
@@ -1222,7 +1229,7 @@ __device__ __forceinline__ void lssd_ring_products(float *ring, int lane, bool o
 }
 
 // Advances the kSums exact-order sums (9: the products; 1: the luminance form's mean, in ring row 0) over chunk `chunk` of the ring.
-// quad chain: every lane works, quad q carries sum q (klt_common.h "quad chain"); the quads behind the last sum follow its row and
+// quad chain: every lane works, quad q carries sum q (klt_chain.h "quad chain"); the quads behind the last sum follow its row and
 // are ignored.  A launch that oversubscribes the chip keeps one lane per sum (KltParams::quad_chain): there the instruction COUNT
 // decides.  Either way sum k ends in lane k * sum_lanes(p).
 template <int kSums>
@@ -1316,7 +1323,7 @@ __device__ __forceinline__ bool lssd_chunked_entry(const Blk &b, const KltParams
         if (b.lane == 0) {
             ref_sum = chain_lane(row, p.Ppad);
         }
-        ref_average = uniform_lane(ref_sum, 0) / (float)ref_valid_num;
+        ref_average = bcast_lane(ref_sum, 0) / (float)ref_valid_num;
         blk_sync(b);
     }
     for (int pxi = b.tid; pxi < p.P; pxi += b.nt) {
@@ -1710,7 +1717,7 @@ __device__ __forceinline__ void lssd_level_fast_chunked_lum(const Blk &b, const 
         if (cur_valid_num == 0) {
             break;  // :60-63
         }
-        const float cur_average = uniform_lane(mean_acc, 0) / (float)cur_valid_num;
+        const float cur_average = bcast_lane(mean_acc, 0) / (float)cur_valid_num;
         // ---- pass 2: the scaled patch (:72-78) and ComputeHessianAndBias (:197-229) ----
         bool seen_valid = false;
         float acc = 0.0f;
@@ -1784,7 +1791,7 @@ template <int MODEL, int METHOD, bool SOLO, int H, bool TREE = false, bool LUM =
 __global__ void FTK_EU_ATTR __launch_bounds__(kWave *kMaxWaves) klt_track_kernel(const KltParams p_arg) {
     // `p` carries everything but the level tables, which stay in the kernel argument: a local copy whose arrays are indexed
     // with a run-time level would live in scratch memory
-    klt_touch_kernarg<sizeof(KltParams)>();  // every line of the argument block requested up front (klt_common.h)
+    klt_touch_kernarg<sizeof(KltParams)>();  // every line of the argument block requested up front (klt_scalar.h)
     KltParams p = p_arg;
     if constexpr (H > 0) {
         p.half_rows = H;
@@ -1803,7 +1810,7 @@ __global__ void FTK_EU_ATTR __launch_bounds__(kWave *kMaxWaves) klt_track_kernel
     b.nwaves = SOLO ? 1 : b.nt >> 6;
     // SOLO: p.features_per_group one-wave features share a workgroup without ever meeting (own LDS carve, no barrier)
     // block 0 of a launch that carries the previous call's iteration counts sorts them into a later call's launch order
-    // (klt_common.h) beside the feature workgroups; the feature blocks follow it
+    // (klt_order.h) beside the feature workgroups; the feature blocks follow it
     uint32_t block = blockIdx.x;
     if (p.sort_iters) {
         if (block == 0) {
@@ -1819,7 +1826,7 @@ __global__ void FTK_EU_ATTR __launch_bounds__(kWave *kMaxWaves) klt_track_kernel
         return;
     }
     // ... and, for callers whose list changes between frames, a trade of places between an early slot and a late one whose
-    // POSITION predicts many iterations (klt_common.h sched_resolve_slot; one wave decides for the workgroup)
+    // POSITION predicts many iterations (klt_order.h sched_resolve_slot; one wave decides for the workgroup)
     uint32_t list_slot = slot_id;
     bool swapped_in = false;
     if (p.sched_claim != nullptr) {

@@ -20,7 +20,7 @@ bool klt_sched_applies(const KltSchedInput &in) {
 // and the grid drains while they finish.  Trackers are called frame after frame on (nearly) the same feature list
 // and a feature that needed many iterations tends to need many again, so the launch slots go through a permutation:
 // longest first by an EARLIER call's iteration counts.  No launch of its own: call k's tracker launch carries one
-// extra workgroup (block 0, klt_common.h klt_order_block) that sorts call k - 1's counts while the features of call k
+// extra workgroup (block 0, klt_order.h klt_order_block) that sorts call k - 1's counts while the features of call k
 // run, and call k + 1 uses the result — so from the third call with the same feature count on, with a predictor two
 // calls old.  Which slot runs a feature changes nothing in its arithmetic.  Only for calls with more features than
 // fit the chip at once; FTK_KLT_SCHED=0 keeps list order.

@@ -1,7 +1,7 @@
 // klt_sched.h — what the host and the kernels of the trackers share about launch order and tail class: the geometry of the position
 // tables, the formats of the four words both sides read and write, and the two state machines of a context (which launch order a
 // call gets, which tail class a variant is in) as pure step functions (klt_sched.cpp: no context, no environment, no HIP call;
-// tests/test_klt_sched_cpu.py walks them without a device through host/build/klt_sched_cli).  Plain C++: klt_common.h includes
+// tests/test_klt_sched_cpu.py walks them without a device through host/build/klt_sched_cli).  Plain C++: klt_order.h includes
 // this for the device side, ftk_klt.cpp for the host side.
 #pragma once
 
@@ -20,7 +20,7 @@ constexpr int klt_method_class(int method) { return method == FTK_METHOD_INVERSE
 // The helpers are inlined before anything is optimised, like the kernels' own __forceinline__ helpers.
 #define FTK_WORD_FN constexpr __attribute__((always_inline))
 
-// ---- position tables and launch slots (klt_common.h "Position-keyed slot swaps") ----
+// ---- position tables and launch slots (klt_order.h "Position-keyed slot swaps") ----
 constexpr int kSchedTableBits = 16;
 constexpr int kSchedTableSize = 1 << kSchedTableBits;  // entries per table; two tables (written by this call / read from the last)
 constexpr int kSchedHeadFirst = 256;   // the heads are the slots [kSchedHeadFirst, kSchedHeadFirst + kSchedHeadSlots): resident from the
@@ -29,7 +29,7 @@ constexpr int kSchedLateSlot = 1024;   // longest features, which must not start
 constexpr uint32_t kSchedLongCount = 12;   // a late slot is a candidate from this predicted count on ...
 constexpr uint32_t kSchedSwapMargin = 8;   // ... and a head trades with it if that is this much above its own feature's prediction
 constexpr uint32_t kSchedSelf = 0x1FFu;    // claim code "the slot runs its own feature"; 0 .. kSchedHeadSlots - 1: the head (by number) it trades with
-constexpr uint32_t kTailReportFrom = 12;   // a feature reports its iteration count from here on (klt_common.h tail_report)
+constexpr uint32_t kTailReportFrom = 12;   // a feature reports its iteration count from here on (klt_order.h tail_report)
 // trades need more features than this: a late slot beyond the heads' own
 constexpr int32_t kSchedTradeMin = kSchedLateSlot + kSchedHeadFirst + kSchedHeadSlots;
 

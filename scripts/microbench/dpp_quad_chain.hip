@@ -1,6 +1,6 @@
 // Micro-benchmark (experiment, not product): the exact-order chain with the terms handed to the accumulator through the DPP network.
 //
-// Today (klt_common.h chain_chunk): lane k of the chain wave reads 4 terms of ITS sum per ds_read_b128 and adds them — one read
+// Today (klt_chain.h chain_chunk): lane k of the chain wave reads 4 terms of ITS sum per ds_read_b128 and adds them — one read
 // instruction per 4 terms, 8 - 9 cycles per term for a lone wave (one instruction of any kind per 4 cycles + LDS waits).
 // Here: the 4 lanes of a QUAD all carry the same sum.  Lane i of quad q reads the float4 at term 16 j + 4 i of sum q, so ONE
 // ds_read_b128 brings 16 consecutive terms of up to 16 sums into the wave, and 16 `v_add_f32_dpp acc, T, acc quad_perm:[i,i,i,i]`

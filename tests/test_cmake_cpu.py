@@ -32,6 +32,17 @@ def test_every_kernel_source_is_in_the_makefile():
     assert sorted(objs) == sorted([os.path.splitext(s)[0] + ".o" for s in srcs] + ["ftk_build_info.o"])
 
 
+def test_every_header_is_in_the_makefile():
+    """HDRS drives the rebuilds and the source hash of ftk_build_info(): a header missing from it goes stale silently."""
+    csrc = os.path.join(ROOT, "feature_tracker_amd", "csrc")
+    mk = open(os.path.join(csrc, "Makefile")).read()
+    hdrs = re.search(r"^HDRS\s*:=\s*(.*)$", mk, flags=re.M).group(1).split()
+    for h in hdrs:
+        assert os.path.isfile(os.path.join(csrc, h)), h + " is in HDRS and not on disk"
+    on_disk = sorted(f for f in os.listdir(csrc) if f.endswith((".h", ".inc")) and f != "ftk_build_info.inc")
+    assert sorted(h for h in hdrs if "/" not in h) == on_disk
+
+
 @pytest.mark.skipif(shutil.which("cmake") is None or shutil.which("make") is None, reason="cmake / make not installed")
 def test_cmake_configures_builds_and_links_a_caller(tmp_path):
     build = str(tmp_path / "cm")

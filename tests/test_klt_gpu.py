@@ -584,7 +584,7 @@ def test_lssd_fast_chunked_equals_the_unchunked_level(ftk, oracle, switch):
 @pytest.mark.parametrize("model,method", [("affine", "inverse"), ("lssd", "fast"), ("basic", "inverse")])
 def test_launch_order_from_the_previous_call_changes_nothing(ftk, oracle, model, method, switch):
     """From the third call with the same feature count on, the device entry launches the features longest-first by an earlier
-    call's iteration counts (ftk_klt.cpp; the sort runs in an extra workgroup of the launch in between, klt_common.h
+    call's iteration counts (ftk_klt.cpp; the sort runs in an extra workgroup of the launch in between, klt_order.h
     klt_order_block; calls of >= 4096 features).  Every call must return what the first one did — the oracle's answer — also
     when the history comes from DIFFERENT inputs (a stale predictor) and when some features are passed through (incoming
     status, kMaxTrackPointsNumber)."""
@@ -669,7 +669,7 @@ def test_position_keyed_launch_order_when_the_feature_count_changes(ftk, oracle,
 
 @pytest.mark.parametrize("n", [4603, 8192])
 def test_flat_iteration_counts_give_a_spatial_xcd_major_launch_order(ftk, oracle, n, switch, tmp_path):
-    """Without a tail in the iteration counts the launch order is by image region, dealt XCD-major (klt_common.h klt_order_block,
+    """Without a tail in the iteration counts the launch order is by image region, dealt XCD-major (klt_order.h klt_order_block,
     xcd_major_slot): it must be a permutation for feature counts that do and do not fill the last workgroup, the slots of one XCD
     (workgroup index mod 8) must come in runs that each cover a compact part of the image, and the results stay the oracle's."""
     import torch
@@ -817,7 +817,7 @@ def test_host_images_reach_the_pyramid_launch_through_the_pinned_slots(ftk, orac
 
 def test_position_keyed_trades_of_launch_slots_process_every_feature_once(ftk, oracle, switch, tmp_path):
     """A list that is reshuffled between calls: the launch order (by list index) is stale, and early launch slots trade places with
-    late ones whose POSITION predicts many iterations (klt_common.h sched_resolve_slot; multi-wave trackers, >= 4096 features).
+    late ones whose POSITION predicts many iterations (klt_order.h sched_resolve_slot; multi-wave trackers, >= 4096 features).
     Trades must happen here, and every feature must come out exactly as the oracle has it — whichever slot ran it."""
     import torch
     from feature_tracker_amd import device as D

@@ -1,4 +1,4 @@
-"""GPU unit test of the lane-parallel 6x6 LDLT (csrc/klt_common.h: ldlt6_factor / ldlt6_solve) against the oracle's
+"""GPU unit test of the lane-parallel 6x6 LDLT (csrc/klt_ldlt.h: ldlt6_factor / ldlt6_solve) against the oracle's
 restatement of Eigen's pivoted LDLT, bit for bit — including the matrices a tracker rarely produces."""
 import ctypes as C
 
