@@ -80,12 +80,18 @@ def test_nan_and_inf_features(ftk):
     check(ftk, f0, f1, 3, 2, coords_for(32, 1, 16, 20))
 
 
-def test_hostile_coordinates(ftk):
+def hostile_case():
+    """(fmap0, fmap1, coords) of 1 x 8 x 16 x 24 with NaN, +-inf, huge, 2^31 and edge coordinates over the first 600 of them."""
     f0, f1 = features(41, 1, 8, 16, 24)
     c = coords_for(42, 1, 16, 24)
     flat = c.view(-1)
     specials = torch.tensor([float("nan"), float("inf"), float("-inf"), 1e30, -1e30, 3e9, -3e9, 2.0 ** 31, -0.0, 23.0, 15.0, -1.0])
     flat[: specials.numel() * 50] = specials.repeat(50)
+    return f0, f1, c
+
+
+def test_hostile_coordinates(ftk):
+    f0, f1, c = hostile_case()
     check(ftk, f0, f1, 3, 3, c)
 
 
