@@ -42,6 +42,10 @@ TWO_VIEW_MODES = {"fundamental": 0, "homography": 1, "auto": 2}
 # relative pose and landmarks from two-view inliers (include/ftk.h)
 FTK_POSE_JACOBI_SWEEPS = 7
 FTK_POSE_TILE = 256
+# PnpRansac (include/ftk.h)
+FTK_PNP_SAMPLE = 6
+FTK_PNP_MODEL_FLOATS = 12
+FTK_PNP_MAX_REFINE_ITERATIONS = 16
 # the keypoint decoder (include/ftk.h)
 FTK_KEYPOINT_DECODE_CELL = 8
 FTK_KEYPOINT_DECODE_MAX_KEYPOINTS = 65536
@@ -98,6 +102,7 @@ EXPORTS = [
     "ftk_epipolar_workspace_bytes", "ftk_epipolar_ransac_device",
     "ftk_two_view_workspace_bytes", "ftk_two_view_ransac_device",
     "ftk_two_view_pose_workspace_bytes", "ftk_two_view_pose_device",
+    "ftk_pnp_ransac_workspace_bytes", "ftk_pnp_ransac_device",
     "ftk_keypoint_decode_workspace_bytes", "ftk_keypoint_decode_device",
     "ftk_match_assignment_workspace_bytes", "ftk_match_assignment_device",
     "ftk_transformer_layer_workspace_bytes", "ftk_attention_device", "ftk_linear_device", "ftk_transformer_layer_device",
@@ -291,6 +296,8 @@ def lib() -> C.CDLL:
     l.ftk_two_view_ransac_device.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, C.c_uint32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     l.ftk_two_view_pose_workspace_bytes.argtypes = [i32, i64p]
     l.ftk_two_view_pose_device.argtypes = [vp, vp, vp, vp, vp, i32] + [f32] * 10 + [vp] * 7
+    l.ftk_pnp_ransac_workspace_bytes.argtypes = [i32, i32, i32, i64p]
+    l.ftk_pnp_ransac_device.argtypes = [vp, vp, vp, vp, vp, i32] + [f32] * 5 + [i32, i32, C.c_uint32] + [vp] * 7
     l.ftk_keypoint_decode_workspace_bytes.argtypes = [i32, i32, i32, i32, i64p]
     l.ftk_keypoint_decode_device.argtypes = [vp, vp, vp, i32, i32, vp, i32, C.c_int64, C.c_int64, C.c_int64, i32, f32, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]
     l.ftk_match_assignment_workspace_bytes.argtypes = [i32, i32, i32, i32, i64p]
@@ -390,6 +397,15 @@ def two_view_pose_workspace_bytes(n: int) -> int:
     csrc/two_view_pose_plan.cpp): M, the participants' calibrated coordinates, 45 totals per tile of FTK_POSE_TILE points, the model block."""
     n = int(n)
     return 16 + _up16(16 * n) + _up16(4 * 45 * -(-n // FTK_POSE_TILE)) + 128
+
+
+def pnp_ransac_workspace_bytes(n: int, hypotheses: int, refine_iterations: int = 0) -> int:
+    """Bytes of workspace ftk_pnp_ransac_device needs, the value ftk_pnp_ransac_workspace_bytes returns (pure Python; csrc/pnp_plan.cpp): M,
+    the participants' (x, y, X, Y), Z and indices, per hypothesis a count, a model of 12 floats and a validity flag, per tile of
+    FTK_POSE_TILE points 27 totals and an inlier count, the pose and the flags.  The same for every refine_iterations."""
+    n, k = int(n), int(hypotheses)
+    tiles = -(-n // FTK_POSE_TILE)
+    return 16 + _up16(16 * n) + 2 * _up16(4 * n) + _up16(4 * k) + _up16(4 * FTK_PNP_MODEL_FLOATS * k) + _up16(k) + _up16(4 * 27 * tiles) + _up16(4 * tiles) + 32 + 16
 
 
 def keypoint_decode_workspace_bytes(cell_rows: int, cell_cols: int, min_distance: int, n_occupied: int = 0) -> int:

@@ -1,6 +1,6 @@
 // epipolar_device.h — the device functions of the two-view kernels (two_view_kernels.hip): "finite", the hash, the
-// sampler, the null vector of an 8 x 9 system by Gaussian elimination with complete pivoting, the two inlier tests, and the two models
-// as compile-time traits of the hypothesis, score and select kernels.  Every float operation is stated in DESIGN.md 5.20 and 5.21 and
+// sampler, the null vector of an R x (R + 1) system by Gaussian elimination with complete pivoting (8 x 9 here, 11 x 12 in
+// pnp_kernels.hip), the two inlier tests, and the two models as compile-time traits of the hypothesis, score and select kernels.  Every float operation is stated in DESIGN.md 5.20 and 5.21 and
 // restated in tests/epipolar_ref.c and tests/two_view_ref.c; the build has no contraction (-ffp-contract=off) and correctly rounded
 // division and square root.
 #pragma once
@@ -15,15 +15,15 @@ __device__ __forceinline__ bool ep_finite(float v) { return (__float_as_uint(v) 
 // status == FTK_TRACKED in ascending index order, by a block scan of per-thread counts (no atomic append).  A thread owns per_thread
 // (<= 64) consecutive points, its participants one 64-bit mask; store(at, i) places participant `at` of the list, the point i; m[0]
 // receives their number.  scan: kEpipolarScanBlock ints of LDS.
-template <class Store>
-__device__ __forceinline__ void ep_scan_participants(int32_t *const scan, const uint8_t *const status, const int n, const int per_thread, int32_t *const m,
-                                                     Store store) {
+// ep_scan_participants_if: the same with the test of a participant given, takes(i).
+template <class Takes, class Store>
+__device__ __forceinline__ void ep_scan_participants_if(int32_t *const scan, const int n, const int per_thread, int32_t *const m, Takes takes, Store store) {
     const int tid = threadIdx.x;
     const int begin = min(tid * per_thread, n), end = min(begin + per_thread, n);
     unsigned long long mask = 0ull;
     int32_t mine = 0;
     for (int i = begin; i < end; ++i) {
-        if (status[i] == FTK_TRACKED) {
+        if (takes(i)) {
             mask |= 1ull << (i - begin);
             ++mine;
         }
@@ -46,6 +46,12 @@ __device__ __forceinline__ void ep_scan_participants(int32_t *const scan, const 
     if (tid == kEpipolarScanBlock - 1) {
         m[0] = scan[tid];
     }
+}
+
+template <class Store>
+__device__ __forceinline__ void ep_scan_participants(int32_t *const scan, const uint8_t *const status, const int n, const int per_thread, int32_t *const m,
+                                                     Store store) {
+    ep_scan_participants_if(scan, n, per_thread, m, [&](const int i) { return status[i] == FTK_TRACKED; }, store);
 }
 
 __device__ __forceinline__ uint32_t ep_fmix32(uint32_t x) {  // murmur3's finaliser
@@ -168,20 +174,22 @@ struct HomographyModel {
     static __device__ __forceinline__ bool inlier(const float (&g)[9], const float4 q, float tn2) { return tv_inlier(g, q, tn2); }
 };
 
-// The unit null vector of the 8 x 9 matrix a (LDS, a[(r * 9 + c) * L] of this lane; destroyed), by Gaussian elimination with complete
-// pivoting, back substitution with the free unknown 1 and scaling to unit norm.  perm (9 ints) and fv (9 floats) are this lane's LDS
-// scratch, strided by L as a is.  `ok`: the matrix was filled from finite coordinates.  Returns the validity of f; f is zero when invalid.
-template <int L>
-__device__ __forceinline__ bool ep_null_vector(float *const a, int *const perm, float *const fv, bool ok, float (&f)[9]) {
-    for (int c = 0; c < 9; ++c) {
+// The unit null vector of the R x (R + 1) matrix a (LDS, a[(r * C + c) * L] of this lane, C = R + 1; destroyed), by Gaussian elimination
+// with complete pivoting, back substitution with the free unknown 1 and scaling to unit norm.  perm (C ints) and fv (C floats) are this
+// lane's LDS scratch, strided by L as a is.  `ok`: the matrix was filled from finite coordinates.  Returns the validity of f; f is zero
+// when invalid.  R = 8: the two-view filters' 8 x 9 system; R = 11: the six-point DLT of a projection (pnp_kernels.hip).
+template <int R, int L>
+__device__ __forceinline__ bool ep_null_vector_of(float *const a, int *const perm, float *const fv, bool ok, float (&f)[R + 1]) {
+    constexpr int C = R + 1;
+    for (int c = 0; c < C; ++c) {
         perm[c * L] = c;
     }
-    for (int s = 0; ok && s < 8; ++s) {
+    for (int s = 0; ok && s < R; ++s) {
         float best = -1.0f;
         int br = s, bc = s;
-        for (int r = s; r < 8; ++r) {
-            for (int c = s; c < 9; ++c) {
-                const float v = fabsf(a[(r * 9 + c) * L]);
+        for (int r = s; r < R; ++r) {
+            for (int c = s; c < C; ++c) {
+                const float v = fabsf(a[(r * C + c) * L]);
                 if (v > best) {
                     best = v;
                     br = r;
@@ -189,72 +197,78 @@ __device__ __forceinline__ bool ep_null_vector(float *const a, int *const perm, 
                 }
             }
         }
-        const float piv = a[(br * 9 + bc) * L];
+        const float piv = a[(br * C + bc) * L];
         if (!ep_finite(piv) || piv == 0.0f) {
             ok = false;
             break;
         }
         if (br != s) {
-            for (int c = s; c < 9; ++c) {
-                const float t = a[(s * 9 + c) * L];
-                a[(s * 9 + c) * L] = a[(br * 9 + c) * L];
-                a[(br * 9 + c) * L] = t;
+            for (int c = s; c < C; ++c) {
+                const float t = a[(s * C + c) * L];
+                a[(s * C + c) * L] = a[(br * C + c) * L];
+                a[(br * C + c) * L] = t;
             }
         }
         if (bc != s) {
-            for (int r = 0; r < 8; ++r) {
-                const float t = a[(r * 9 + s) * L];
-                a[(r * 9 + s) * L] = a[(r * 9 + bc) * L];
-                a[(r * 9 + bc) * L] = t;
+            for (int r = 0; r < R; ++r) {
+                const float t = a[(r * C + s) * L];
+                a[(r * C + s) * L] = a[(r * C + bc) * L];
+                a[(r * C + bc) * L] = t;
             }
             const int t = perm[s * L];
             perm[s * L] = perm[bc * L];
             perm[bc * L] = t;
         }
-        for (int r = s + 1; r < 8; ++r) {
-            const float mult = a[(r * 9 + s) * L] / piv;
-            for (int c = s + 1; c < 9; ++c) {
-                a[(r * 9 + c) * L] = a[(r * 9 + c) * L] - mult * a[(s * 9 + c) * L];
+        for (int r = s + 1; r < R; ++r) {
+            const float mult = a[(r * C + s) * L] / piv;
+            for (int c = s + 1; c < C; ++c) {
+                a[(r * C + c) * L] = a[(r * C + c) * L] - mult * a[(s * C + c) * L];
             }
         }
     }
 #pragma unroll
-    for (int i = 0; i < 9; ++i) {
+    for (int i = 0; i < C; ++i) {
         f[i] = 0.0f;
     }
     if (ok) {
-        // the null vector: the free (ninth) column's unknown is 1, the others by back substitution
-        float z[9];
-        z[8] = 1.0f;
+        // the null vector: the free (last) column's unknown is 1, the others by back substitution
+        float z[C];
+        z[R] = 1.0f;
 #pragma unroll
-        for (int s = 7; s >= 0; --s) {
-            float acc = a[(s * 9 + 8) * L];
+        for (int s = R - 1; s >= 0; --s) {
+            float acc = a[(s * C + R) * L];
 #pragma unroll
-            for (int q = s + 1; q < 8; ++q) {
-                acc = acc + a[(s * 9 + q) * L] * z[q];
+            for (int q = s + 1; q < R; ++q) {
+                acc = acc + a[(s * C + q) * L] * z[q];
             }
-            z[s] = -acc / a[(s * 9 + s) * L];
+            z[s] = -acc / a[(s * C + s) * L];
         }
 #pragma unroll
-        for (int q = 0; q < 9; ++q) {
+        for (int q = 0; q < C; ++q) {
             fv[perm[q * L] * L] = z[q];
         }
         float n2 = fv[0] * fv[0];
 #pragma unroll
-        for (int i = 1; i < 9; ++i) {
+        for (int i = 1; i < C; ++i) {
             n2 = n2 + fv[i * L] * fv[i * L];
         }
         ok = ep_finite(n2) && n2 > 0.0f;
         if (ok) {
             const float inv = 1.0f / sqrtf(n2);
 #pragma unroll
-            for (int i = 0; i < 9; ++i) {
+            for (int i = 0; i < C; ++i) {
                 f[i] = fv[i * L] * inv;
                 ok = ok && ep_finite(f[i]);
             }
         }
     }
     return ok;
+}
+
+// The 8 x 9 form of the two filters.
+template <int L>
+__device__ __forceinline__ bool ep_null_vector(float *const a, int *const perm, float *const fv, bool ok, float (&f)[9]) {
+    return ep_null_vector_of<8, L>(a, perm, fv, ok, f);
 }
 
 }  // namespace ftk

@@ -1,0 +1,690 @@
+// pnp_kernels.hip — PnpRansac on gfx950: the camera pose from landmarks and the pixels where they are seen, RANSAC over the
+// six-point DLT and a Gauss-Newton refit of the reprojection error on the inliers, everything on the device, 5 + 2 refine_iterations
+// launches of fixed shape.
+//
+//  * pnp_scan_kernel: the filters' scan (epipolar_device.h: ONE workgroup lists the participants in ascending index order) with this
+//    stage's test of a participant: status TRACKED, five finite numbers, a landmark other than (0, 0, 0).  It stores the calibrated pixel
+//    and the landmark.
+//  * pnp_hypothesis_kernel: one lane = one hypothesis, as two_view_hypothesis_kernel.  The six landmarks are conditioned from the sample
+//    alone; the 11 x 12 DLT system lives in LDS, [entry][lane] (156 floats per lane, 39 KB per workgroup: complete pivoting indexes rows
+//    and columns at run time), and the elimination is epipolar_device.h's ep_null_vector_of<11>, the two filters' at another size.
+//  * pnp_score_kernel: two_view_score_kernel's tiling (a tile of 256 participants in LDS, 4 hypotheses per wave, ballot and popcount, ONE
+//    integer atomicAdd per workgroup and hypothesis) on a participant record of five floats and a model of twelve, which is why it is a
+//    kernel of its own and no third Model of that family: the family's record is one float4 and its models are nine floats.
+//  * pnp_select_kernel: ONE workgroup takes the maximum of (count + 1) << 32 | ~h; thread 0 turns the winner's [A | b] into a pose: the
+//    nearest rotation by TwoViewPose's cyclic Jacobi on A^T A (its statements, run by one thread on LDS arrays: jacobi_eigen<3> itself
+//    needs the solve kernel's wave), Shepperd's quaternion.
+//  * pnp_sums_kernel / pnp_step_kernel, once per refit step: a tile of 256 participants reduces its 27 terms by pose_moment_kernel's tree
+//    (the first step over the inliers of the model that won, the later ones over the current pose's);
+//    one wave adds the tile totals in tile order, solves the 6 x 6 system by an LDL^T and moves the pose, or ends the refit.
+//  * pnp_finish_kernel: a thread per participant applies the status rule under the final pose; block 0 writes the outputs.
+// Every float operation below is stated in DESIGN.md 5.30 and restated in tests/pnp_ref.c; the build has no contraction (-ffp-contract=off)
+// and correctly rounded division and square root.
+#include "epipolar_device.h"
+#include "pnp_plan.h"
+
+namespace ftk {
+namespace {
+
+constexpr int kFlagOk = 0, kFlagDone = 1, kFlagWinner = 2;
+
+// The inlier rule on the camera coordinates c of a landmark seen at the calibrated (x, y).
+__device__ __forceinline__ bool pnp_inlier(const float (&c)[3], const float x, const float y, const float ry, const float tn2) {
+    const float ex = c[0] - x * c[2];
+    const float ey = (c[1] - y * c[2]) * ry;
+    const float lhs = ex * ex + ey * ey, rhs = tn2 * (c[2] * c[2]);
+    return c[2] > 0.0f && ep_finite(lhs) && ep_finite(rhs) && lhs <= rhs;
+}
+
+// R_rc of a unit quaternion, row-major.
+__device__ __forceinline__ void pnp_rotation(const float (&q)[7], float (&R)[9]) {
+    const float w = q[0], x = q[1], y = q[2], z = q[3];
+    R[0] = 1.0f - 2.0f * (y * y + z * z), R[1] = 2.0f * (x * y - w * z), R[2] = 2.0f * (x * z + w * y);
+    R[3] = 2.0f * (x * y + w * z), R[4] = 1.0f - 2.0f * (x * x + z * z), R[5] = 2.0f * (y * z - w * x);
+    R[6] = 2.0f * (x * z - w * y), R[7] = 2.0f * (y * z + w * x), R[8] = 1.0f - 2.0f * (x * x + y * y);
+}
+
+// c = R_rc^T (X - p_rc)
+__device__ __forceinline__ void pnp_camera(const float (&R)[9], const float (&ps)[7], const float X, const float Y, const float Z, float (&c)[3]) {
+    const float d0 = X - ps[4], d1 = Y - ps[5], d2 = Z - ps[6];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        c[j] = (R[j] * d0 + R[3 + j] * d1) + R[6 + j] * d2;
+    }
+}
+
+__global__ void __launch_bounds__(kEpipolarScanBlock) pnp_scan_kernel(const PnpParams p) {
+    __shared__ int32_t scan[kEpipolarScanBlock];
+    ep_scan_participants_if(
+        scan, p.n, p.scan_per_thread, p.m,
+        [&](const int i) {
+            if (p.status[i] != FTK_TRACKED) {
+                return false;  // (nothing else of a point that is not TRACKED is read)
+            }
+            const float X = p.landmarks[3 * (size_t)i], Y = p.landmarks[3 * (size_t)i + 1], Z = p.landmarks[3 * (size_t)i + 2];
+            const float2 c = reinterpret_cast<const float2 *>(p.uv)[i];
+            return ep_finite(X) && ep_finite(Y) && ep_finite(Z) && ep_finite(c.x) && ep_finite(c.y) && !(X == 0.0f && Y == 0.0f && Z == 0.0f);
+        },
+        [&](const int at, const int i) {
+            const float X = p.landmarks[3 * (size_t)i], Y = p.landmarks[3 * (size_t)i + 1], Z = p.landmarks[3 * (size_t)i + 2];
+            const float2 c = reinterpret_cast<const float2 *>(p.uv)[i];
+            p.points[at] = make_float4((c.x - p.cx) / p.fx, (c.y - p.cy) / p.fy, X, Y);
+            p.depth[at] = Z;
+            p.list[at] = i;
+        });
+}
+
+__global__ void __launch_bounds__(kEpipolarHypBlock) pnp_hypothesis_kernel(const PnpParams p) {
+    __shared__ float lds[kPnpHypLdsFloats * kEpipolarHypBlock];
+    const int lane = threadIdx.x;
+    const int h = blockIdx.x * kEpipolarHypBlock + lane;
+    if (h >= p.hypotheses) {
+        return;  // (no barrier below)
+    }
+    constexpr int L = kEpipolarHypBlock, C = kPnpRows + 1;
+    float *const a = lds + lane;                                                // a[(r * 12 + c) * 64]
+    int *const perm = reinterpret_cast<int *>(lds + kPnpRows * C * L) + lane;   // perm[c * 64]
+    float *const fv = lds + (kPnpRows * C + C) * L + lane;                      // fv[c * 64]
+    const uint32_t m = (uint32_t)max(min(p.m[0], p.n), 0);
+    uint32_t idx[kPnpSample];
+    bool ok = ep_draw<kPnpSample>(p.seed, (uint32_t)h, m, idx);
+    float x[kPnpSample], y[kPnpSample], X[kPnpSample], Y[kPnpSample], Z[kPnpSample];
+#pragma unroll
+    for (int k = 0; k < kPnpSample; ++k) {
+        const float4 q = ok ? p.points[idx[k]] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        x[k] = q.x, y[k] = q.y, X[k] = q.z, Y[k] = q.w;
+        Z[k] = ok ? p.depth[idx[k]] : 0.0f;
+    }
+    // conditioning from the sample alone: the mean in index order, the mean absolute deviation over the 18 coordinates
+    const float mx = (((((X[0] + X[1]) + X[2]) + X[3]) + X[4]) + X[5]) / 6.0f;
+    const float my = (((((Y[0] + Y[1]) + Y[2]) + Y[3]) + Y[4]) + Y[5]) / 6.0f;
+    const float mz = (((((Z[0] + Z[1]) + Z[2]) + Z[3]) + Z[4]) + Z[5]) / 6.0f;
+    float dev = 0.0f;
+#pragma unroll
+    for (int k = 0; k < kPnpSample; ++k) {
+        X[k] = X[k] - mx, Y[k] = Y[k] - my, Z[k] = Z[k] - mz;
+        const float d = (fabsf(X[k]) + fabsf(Y[k])) + fabsf(Z[k]);
+        dev = k == 0 ? d : dev + d;
+    }
+    const float s = dev / 18.0f;
+    ok = ok && ep_finite(s) && s > 0.0f;
+    if (ok) {
+#pragma unroll
+        for (int k = 0; k < kPnpSample; ++k) {
+            const float Xn = X[k] / s, Yn = Y[k] / s, Zn = Z[k] / s;
+            const int r0 = 2 * k * C, r1 = (2 * k + 1) * C;
+            a[(r0 + 0) * L] = Xn;
+            a[(r0 + 1) * L] = Yn;
+            a[(r0 + 2) * L] = Zn;
+            a[(r0 + 3) * L] = 1.0f;
+            a[(r0 + 4) * L] = 0.0f;
+            a[(r0 + 5) * L] = 0.0f;
+            a[(r0 + 6) * L] = 0.0f;
+            a[(r0 + 7) * L] = 0.0f;
+            a[(r0 + 8) * L] = -(x[k] * Xn);
+            a[(r0 + 9) * L] = -(x[k] * Yn);
+            a[(r0 + 10) * L] = -(x[k] * Zn);
+            a[(r0 + 11) * L] = -x[k];
+            if (2 * k + 1 < kPnpRows) {  // (the twelfth row is not used)
+                a[(r1 + 0) * L] = 0.0f;
+                a[(r1 + 1) * L] = 0.0f;
+                a[(r1 + 2) * L] = 0.0f;
+                a[(r1 + 3) * L] = 0.0f;
+                a[(r1 + 4) * L] = Xn;
+                a[(r1 + 5) * L] = Yn;
+                a[(r1 + 6) * L] = Zn;
+                a[(r1 + 7) * L] = 1.0f;
+                a[(r1 + 8) * L] = -(y[k] * Xn);
+                a[(r1 + 9) * L] = -(y[k] * Yn);
+                a[(r1 + 10) * L] = -(y[k] * Zn);
+                a[(r1 + 11) * L] = -y[k];
+            }
+        }
+    }
+    float f[C];
+    ok = ep_null_vector_of<kPnpRows, L>(a, perm, fv, ok, f);
+    float P[12];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) {
+        P[i] = 0.0f;
+    }
+    if (ok) {
+        // the conditioning folded back, times s: A = the normalised A, b = s b_n - A mean
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            P[r * 4] = f[r * 4], P[r * 4 + 1] = f[r * 4 + 1], P[r * 4 + 2] = f[r * 4 + 2];
+            P[r * 4 + 3] = s * f[r * 4 + 3] - ((f[r * 4] * mx + f[r * 4 + 1] * my) + f[r * 4 + 2] * mz);
+        }
+        // the sign: the sample's depths positive (X, Y, Z hold the centred landmarks: the sample is read again)
+        int front = 0, behind = 0;
+#pragma unroll
+        for (int k = 0; k < kPnpSample; ++k) {
+            const float4 q = p.points[idx[k]];
+            const float w = ((P[8] * q.z + P[9] * q.w) + P[10] * p.depth[idx[k]]) + P[11];
+            front += w > 0.0f ? 1 : 0;
+            behind += w < 0.0f ? 1 : 0;
+        }
+        ok = front == kPnpSample || behind == kPnpSample;
+        if (behind == kPnpSample) {
+#pragma unroll
+            for (int i = 0; i < 12; ++i) {
+                P[i] = -P[i];
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 12; ++i) {
+            ok = ok && ep_finite(P[i]);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 12; ++i) {
+        p.models[(size_t)h * 12 + i] = ok ? P[i] : 0.0f;
+    }
+    p.valid[h] = ok ? 1 : 0;
+    p.counts[h] = ok ? 0 : -1;
+}
+
+__global__ void __launch_bounds__(kEpipolarScoreTile) pnp_score_kernel(const PnpParams p) {
+    __shared__ float4 tile[kEpipolarScoreTile];
+    __shared__ float tile_z[kEpipolarScoreTile];
+    const int m = min(p.m[0], p.n);
+    const int base = blockIdx.x * kEpipolarScoreTile;
+    if (m < kPnpSample || base >= m) {
+        return;  // the whole workgroup: the grid covers n
+    }
+    const int tid = threadIdx.x;
+    tile[tid] = base + tid < m ? p.points[base + tid] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    tile_z[tid] = base + tid < m ? p.depth[base + tid] : 0.0f;
+    __syncthreads();
+    const int wave = tid >> 6, lane = tid & 63;
+    constexpr int kPerWave = kEpipolarScoreGroup / (kEpipolarScoreTile / 64);
+    for (int i = 0; i < kPerWave; ++i) {
+        const int h = __builtin_amdgcn_readfirstlane((int)blockIdx.y * kEpipolarScoreGroup + wave * kPerWave + i);
+        if (h >= p.hypotheses) {
+            break;
+        }
+        if (!p.valid[h]) {
+            continue;
+        }
+        float P[12];
+#pragma unroll
+        for (int e = 0; e < 12; ++e) {
+            P[e] = p.models[(size_t)h * 12 + e];
+        }
+        int32_t count = 0;
+#pragma unroll
+        for (int r = 0; r < kEpipolarScoreTile / 64; ++r) {
+            const int j = r * 64 + lane;
+            const float4 q = tile[j];
+            const float Z = tile_z[j];
+            float c[3];
+#pragma unroll
+            for (int e = 0; e < 3; ++e) {
+                c[e] = ((P[e * 4] * q.z + P[e * 4 + 1] * q.w) + P[e * 4 + 2] * Z) + P[e * 4 + 3];
+            }
+            const bool in = base + j < m && pnp_inlier(c, q.x, q.y, p.ry, p.tn2);
+            count += (int32_t)__popcll(__ballot(in));
+        }
+        if (lane == 0 && count > 0) {
+            atomicAdd(&p.counts[h], count);
+        }
+    }
+}
+
+// TwoViewPose's cyclic Jacobi (two_view_pose_kernels.hip's jacobi_eigen) at N = 3, every statement in its order, run by ONE thread on
+// arrays in LDS (run-time indices: no scratch).
+__device__ __forceinline__ void pnp_jacobi3(float *const a, float *const v) {
+    constexpr int N = 3;
+    for (int idx = 0; idx < N * N; ++idx) {
+        v[idx] = idx / N == idx % N ? 1.0f : 0.0f;
+    }
+    for (int sweep = 0; sweep < kPoseJacobiSweeps; ++sweep) {
+        for (int p = 0; p < N - 1; ++p) {
+            for (int q = p + 1; q < N; ++q) {
+                const float apq = a[p * N + q], app = a[p * N + p], aqq = a[q * N + q];
+                if (apq == 0.0f) {
+                    continue;
+                }
+                const float g = 100.0f * fabsf(apq);
+                if (fabsf(app) + g == fabsf(app) && fabsf(aqq) + g == fabsf(aqq)) {  // negligible: set to zero, no rotation
+                    a[p * N + q] = 0.0f;
+                    a[q * N + p] = 0.0f;
+                    continue;
+                }
+                const float h = aqq - app;
+                float t;
+                if (fabsf(h) + g == fabsf(h)) {
+                    t = apq / h;
+                } else {
+                    const float theta = h / (2.0f * apq);
+                    t = 1.0f / (fabsf(theta) + sqrtf(theta * theta + 1.0f));
+                    if (theta < 0.0f) {
+                        t = -t;
+                    }
+                }
+                const float c = 1.0f / sqrtf(t * t + 1.0f);
+                const float s = t * c;
+                const float tau = s / (1.0f + c);
+                const float hh = t * apq;
+                a[p * N + p] = app - hh;
+                a[q * N + q] = aqq + hh;
+                a[p * N + q] = 0.0f;
+                a[q * N + p] = 0.0f;
+                for (int r = 0; r < N; ++r) {
+                    if (r != p && r != q) {
+                        const float x = a[r * N + p], y = a[r * N + q];
+                        const float xn = x - s * (y + x * tau), yn = y + s * (x - y * tau);
+                        a[r * N + p] = xn;
+                        a[p * N + r] = xn;
+                        a[r * N + q] = yn;
+                        a[q * N + r] = yn;
+                    }
+                    const float x = v[r * N + p], y = v[r * N + q];
+                    v[r * N + p] = x - s * (y + x * tau);
+                    v[r * N + q] = y + s * (x - y * tau);
+                }
+            }
+        }
+    }
+}
+
+// The winner's P = [A | b] as a pose (q_rc, p_rc): R the nearest rotation to A, t = b / s with s the mean singular value; R_rc = R^T,
+// p_rc = -R^T t.  M, V: 9 floats of LDS each.  false: singular or not finite.
+__device__ __forceinline__ bool pnp_pose_of_model(const float (&P)[12], float *const M, float *const V, float (&ps)[7]) {
+    float A[9];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            A[r * 3 + c] = P[r * 4 + c];
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            M[i * 3 + j] = (A[i] * A[j] + A[3 + i] * A[3 + j]) + A[6 + i] * A[6 + j];
+        }
+    }
+    pnp_jacobi3(M, V);
+    const float l0 = M[0], l1 = M[4], l2 = M[8];
+    if (!(l0 > 0.0f && l1 > 0.0f && l2 > 0.0f)) {
+        return false;
+    }
+    const float sg0 = sqrtf(l0), sg1 = sqrtf(l1), sg2 = sqrtf(l2);
+    const float det = (A[0] * (A[4] * A[8] - A[5] * A[7]) - A[1] * (A[3] * A[8] - A[5] * A[6])) + A[2] * (A[3] * A[7] - A[4] * A[6]);
+    if (!ep_finite(det) || det == 0.0f) {
+        return false;
+    }
+    // det < 0: the term of the smallest eigenvalue (the lowest index among equals) enters with the other sign
+    int small = 0;
+    if (l1 < l0) {
+        small = 1;
+    }
+    if (l2 < (small == 0 ? l0 : l1)) {
+        small = 2;
+    }
+    float w0 = 1.0f / sg0, w1 = 1.0f / sg1, w2 = 1.0f / sg2;
+    if (det < 0.0f) {
+        w0 = small == 0 ? -w0 : w0, w1 = small == 1 ? -w1 : w1, w2 = small == 2 ? -w2 : w2;
+    }
+    // R = A W, W = V diag(w) V^T
+    float W[9], R[9];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            W[i * 3 + j] = ((V[i * 3] * w0) * V[j * 3] + (V[i * 3 + 1] * w1) * V[j * 3 + 1]) + (V[i * 3 + 2] * w2) * V[j * 3 + 2];
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            R[i * 3 + j] = (A[i * 3] * W[j] + A[i * 3 + 1] * W[3 + j]) + A[i * 3 + 2] * W[6 + j];
+        }
+    }
+    const float sc = ((sg0 + sg1) + sg2) / 3.0f;
+    const float t0 = P[3] / sc, t1 = P[7] / sc, t2 = P[11] / sc;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        ps[4 + j] = -((R[j] * t0 + R[3 + j] * t1) + R[6 + j] * t2);
+    }
+    // Shepperd on R_rc = R^T: m(i, j) = R[j * 3 + i], as pose_finish_kernel
+    const float m00 = R[0], m01 = R[3], m02 = R[6], m10 = R[1], m11 = R[4], m12 = R[7], m20 = R[2], m21 = R[5], m22 = R[8];
+    const float tr = (m00 + m11) + m22;
+    float qw, qx, qy, qz;
+    if (tr > 0.0f) {
+        const float s = sqrtf(tr + 1.0f) * 2.0f;
+        qw = 0.25f * s, qx = (m21 - m12) / s, qy = (m02 - m20) / s, qz = (m10 - m01) / s;
+    } else if (m00 > m11 && m00 > m22) {
+        const float s = sqrtf(((1.0f + m00) - m11) - m22) * 2.0f;
+        qw = (m21 - m12) / s, qx = 0.25f * s, qy = (m01 + m10) / s, qz = (m02 + m20) / s;
+    } else if (m11 > m22) {
+        const float s = sqrtf(((1.0f + m11) - m00) - m22) * 2.0f;
+        qw = (m02 - m20) / s, qx = (m01 + m10) / s, qy = 0.25f * s, qz = (m12 + m21) / s;
+    } else {
+        const float s = sqrtf(((1.0f + m22) - m00) - m11) * 2.0f;
+        qw = (m10 - m01) / s, qx = (m02 + m20) / s, qy = (m12 + m21) / s, qz = 0.25f * s;
+    }
+    if (qw < 0.0f) {
+        qw = -qw, qx = -qx, qy = -qy, qz = -qz;
+    }
+    const float qn = sqrtf(((qw * qw + qx * qx) + qy * qy) + qz * qz);
+    ps[0] = qw / qn, ps[1] = qx / qn, ps[2] = qy / qn, ps[3] = qz / qn;
+    bool ok = true;
+#pragma unroll
+    for (int e = 0; e < 7; ++e) {
+        ok = ok && ep_finite(ps[e]);
+    }
+    return ok;
+}
+
+__global__ void __launch_bounds__(kEpipolarScanBlock) pnp_select_kernel(const PnpParams p) {
+    __shared__ unsigned long long red[kEpipolarScanBlock];
+    __shared__ float M[9], V[9];
+    const int tid = threadIdx.x;
+    unsigned long long key = 0ull;
+    for (int i = 0; i < p.select_per_thread; ++i) {
+        const int h = tid * p.select_per_thread + i;
+        if (h < p.hypotheses) {
+            const unsigned long long k = ((unsigned long long)(uint32_t)(p.counts[h] + 1) << 32) | (unsigned long long)(~(uint32_t)h);
+            key = k > key ? k : key;
+        }
+    }
+    red[tid] = key;
+    __syncthreads();
+    for (int step = kEpipolarScanBlock / 2; step > 0; step >>= 1) {
+        if (tid < step) {
+            const unsigned long long other = red[tid + step];
+            if (other > red[tid]) {
+                red[tid] = other;
+            }
+        }
+        __syncthreads();
+    }
+    if (tid != 0) {
+        return;
+    }
+    key = red[0];
+    const int m = min(p.m[0], p.n);
+    bool ok = m >= kPnpSample && (key >> 32) != 0ull;  // (with M < 6 no hypothesis was formed)
+    const int h = ok ? (int)(~(uint32_t)(key & 0xFFFFFFFFull)) : -1;
+    float ps[7] = {1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    if (ok) {
+        float P[12];
+#pragma unroll
+        for (int e = 0; e < 12; ++e) {
+            P[e] = p.models[(size_t)h * 12 + e];
+        }
+        ok = pnp_pose_of_model(P, M, V, ps);
+    }
+#pragma unroll
+    for (int e = 0; e < 7; ++e) {
+        p.state[e] = ps[e];
+    }
+    p.state[7] = 0.0f;
+    p.flags[kFlagOk] = ok ? 1 : 0;
+    p.flags[kFlagDone] = ok ? 0 : 1;
+    p.flags[kFlagWinner] = ok ? h : -1;
+    p.flags[3] = 0;
+    p.n_inliers[0] = 0;
+}
+
+__global__ void __launch_bounds__(kPoseTile) pnp_sums_kernel(const PnpParams p) {
+    __shared__ float tree[kPnpSums][kPoseTile];
+    __shared__ int32_t counts[kPoseTile / 64];
+    const int m = min(p.m[0], p.n);
+    const int base = blockIdx.x * kPoseTile;
+    if (p.flags[kFlagOk] == 0 || p.flags[kFlagDone] != 0 || base >= m) {
+        return;  // the whole workgroup: the grid covers n, the step kernel reads the tiles below M alone
+    }
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    float ps[7], R[9];
+#pragma unroll
+    for (int e = 0; e < 7; ++e) {
+        ps[e] = p.state[e];
+    }
+    pnp_rotation(ps, R);
+    bool in = false;
+    float term[kPnpSums];
+#pragma unroll
+    for (int e = 0; e < kPnpSums; ++e) {
+        term[e] = 0.0f;
+    }
+    if (base + tid < m) {
+        const float4 q = p.points[base + tid];
+        float c[3];
+        const float Z = p.depth[base + tid];
+        pnp_camera(R, ps, q.z, q.w, Z, c);
+        if (p.step == 0) {  // the first step refits on the inliers of the model that won, those in front of the camera under the pose
+            const float *const P = p.models + (size_t)p.flags[kFlagWinner] * 12;
+            float cp[3];
+#pragma unroll
+            for (int e = 0; e < 3; ++e) {
+                cp[e] = ((P[e * 4] * q.z + P[e * 4 + 1] * q.w) + P[e * 4 + 2] * Z) + P[e * 4 + 3];
+            }
+            in = pnp_inlier(cp, q.x, q.y, p.ry, p.tn2) && c[2] > 0.0f;
+        } else {
+            in = pnp_inlier(c, q.x, q.y, p.ry, p.tn2);
+        }
+        if (in) {
+            const float ry = p.ry;
+            const float iz = 1.0f / c[2];
+            const float a = c[0] * iz, b = c[1] * iz;
+            const float j1[6] = {a * b, -(1.0f + a * a), b, -iz, 0.0f, a * iz};
+            const float j2[6] = {ry * (1.0f + b * b), ry * -(a * b), ry * -a, 0.0f, ry * -iz, ry * (b * iz)};
+            const float r1 = a - q.x, r2 = (b - q.y) * ry;
+            int e = 0;
+#pragma unroll
+            for (int i = 0; i < 6; ++i) {
+#pragma unroll
+                for (int j = i; j < 6; ++j, ++e) {
+                    term[e] = j1[i] * j1[j] + j2[i] * j2[j];
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < 6; ++i, ++e) {
+                term[e] = j1[i] * r1 + j2[i] * r2;
+            }
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < kPnpSums; ++e) {
+        tree[e][tid] = term[e];
+    }
+    const int32_t count = (int32_t)__popcll(__ballot(in));
+    if (lane == 0) {
+        counts[wave] = count;
+    }
+    __syncthreads();
+    for (int stride = kPoseTile / 2, shift = 7; stride >= 1; stride >>= 1, --shift) {
+        const int jobs = kPnpSums * stride;
+        for (int job = tid; job < jobs; job += kPoseTile) {
+            const int e = job >> shift, j = job & (stride - 1);
+            tree[e][j] = tree[e][j] + tree[e][j + stride];
+        }
+        __syncthreads();
+    }
+    if (tid < kPnpSums) {
+        p.totals[(size_t)blockIdx.x * kPnpSums + tid] = tree[tid][0];
+    }
+    if (tid == 0) {
+        int32_t sum = 0;
+#pragma unroll
+        for (int w = 0; w < kPoseTile / 64; ++w) {
+            sum += counts[w];
+        }
+        p.tile_counts[blockIdx.x] = sum;
+    }
+}
+
+__global__ void __launch_bounds__(kPoseSolveBlock) pnp_step_kernel(const PnpParams p) {
+    __shared__ float sums[kPnpSums];
+    __shared__ float H[36], Lm[36], d[6], y[6], dx[6];
+    const int tid = threadIdx.x;
+    if (p.flags[kFlagOk] == 0 || p.flags[kFlagDone] != 0) {
+        return;  // the whole workgroup
+    }
+    const int m = min(p.m[0], p.n);
+    const int tiles = (m + kPoseTile - 1) / kPoseTile;
+    if (tid < kPnpSums) {  // the tile totals in ascending tile order from +0
+        float acc = 0.0f;
+        for (int t = 0; t < tiles; ++t) {
+            acc = acc + p.totals[(size_t)t * kPnpSums + tid];
+        }
+        sums[tid] = acc;
+    }
+    __syncthreads();
+    if (tid != 0) {
+        return;
+    }
+    int32_t count = 0;
+    for (int t = 0; t < tiles; ++t) {
+        count += p.tile_counts[t];
+    }
+    bool take = count >= kPnpSample;
+    if (take) {  // H x = -g by an LDL^T without pivoting, column by column
+        int e = 0;
+        for (int i = 0; i < 6; ++i) {
+            for (int j = i; j < 6; ++j, ++e) {
+                H[i * 6 + j] = sums[e];
+                H[j * 6 + i] = sums[e];
+            }
+        }
+        for (int j = 0; take && j < 6; ++j) {
+            float acc = H[j * 6 + j];
+            for (int k = 0; k < j; ++k) {
+                acc = acc - (Lm[j * 6 + k] * Lm[j * 6 + k]) * d[k];
+            }
+            take = ep_finite(acc) && acc > 0.0f;
+            d[j] = acc;
+            for (int i = j + 1; take && i < 6; ++i) {
+                float v = H[i * 6 + j];
+                for (int k = 0; k < j; ++k) {
+                    v = v - (Lm[i * 6 + k] * Lm[j * 6 + k]) * d[k];
+                }
+                Lm[i * 6 + j] = v / acc;
+            }
+        }
+    }
+    if (take) {
+        for (int i = 0; i < 6; ++i) {
+            float v = -sums[21 + i];
+            for (int k = 0; k < i; ++k) {
+                v = v - Lm[i * 6 + k] * y[k];
+            }
+            y[i] = v;
+        }
+        for (int i = 0; i < 6; ++i) {
+            y[i] = y[i] / d[i];
+        }
+        for (int i = 5; i >= 0; --i) {
+            float v = y[i];
+            for (int k = i + 1; k < 6; ++k) {
+                v = v - Lm[k * 6 + i] * dx[k];
+            }
+            dx[i] = v;
+        }
+        // q <- q (1, dtheta / 2), renormalised; p <- p + R_rc dt
+        float ps[7], R[9];
+#pragma unroll
+        for (int e = 0; e < 7; ++e) {
+            ps[e] = p.state[e];
+        }
+        pnp_rotation(ps, R);
+        const float w = ps[0], x = ps[1], yq = ps[2], z = ps[3], hx = 0.5f * dx[0], hy = 0.5f * dx[1], hz = 0.5f * dx[2];
+        float nq0 = ((w - x * hx) - yq * hy) - z * hz;
+        float nq1 = ((x + w * hx) + yq * hz) - z * hy;
+        float nq2 = ((yq + w * hy) + z * hx) - x * hz;
+        float nq3 = ((z + w * hz) + x * hy) - yq * hx;
+        const float qn = sqrtf(((nq0 * nq0 + nq1 * nq1) + nq2 * nq2) + nq3 * nq3);
+        nq0 = nq0 / qn, nq1 = nq1 / qn, nq2 = nq2 / qn, nq3 = nq3 / qn;
+        const float d3 = dx[3], d4 = dx[4], d5 = dx[5];
+        const float np0 = ps[4] + ((R[0] * d3 + R[1] * d4) + R[2] * d5);
+        const float np1 = ps[5] + ((R[3] * d3 + R[4] * d4) + R[5] * d5);
+        const float np2 = ps[6] + ((R[6] * d3 + R[7] * d4) + R[8] * d5);
+        take = ep_finite(nq0) && ep_finite(nq1) && ep_finite(nq2) && ep_finite(nq3) && ep_finite(np0) && ep_finite(np1) && ep_finite(np2);
+        if (take) {
+            p.state[0] = nq0, p.state[1] = nq1, p.state[2] = nq2, p.state[3] = nq3;
+            p.state[4] = np0, p.state[5] = np1, p.state[6] = np2;
+        }
+    }
+    if (!take) {
+        p.flags[kFlagDone] = 1;  // the pose before this step stands
+    }
+}
+
+__global__ void __launch_bounds__(kPoseTile) pnp_finish_kernel(const PnpParams p) {
+    __shared__ int32_t kept[kPoseTile / 64];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int j = blockIdx.x * kPoseTile + tid;
+    const int m = min(p.m[0], p.n);
+    const bool ok = p.flags[kFlagOk] != 0;
+    float ps[7], R[9];
+#pragma unroll
+    for (int e = 0; e < 7; ++e) {
+        ps[e] = p.state[e];
+    }
+    if (ps[0] < 0.0f) {
+        ps[0] = -ps[0], ps[1] = -ps[1], ps[2] = -ps[2], ps[3] = -ps[3];
+    }
+    pnp_rotation(ps, R);
+    if (blockIdx.x == 0 && tid == 0) {
+#pragma unroll
+        for (int e = 0; e < 7; ++e) {
+            p.pose[e] = ok ? ps[e] : (e == 0 ? 1.0f : 0.0f);
+        }
+        p.out_valid[0] = ok ? 1 : -1;
+        p.best[0] = ok ? p.flags[kFlagWinner] : -1;
+    }
+    bool keep = false;
+    if (ok && j < m) {
+        const float4 q = p.points[j];
+        float c[3];
+        pnp_camera(R, ps, q.z, q.w, p.depth[j], c);
+        keep = pnp_inlier(c, q.x, q.y, p.ry, p.tn2);
+        if (!keep) {
+            const int32_t i = p.list[j];
+            if (i >= 0 && i < p.n) {
+                p.status[i] = FTK_LARGE_RESIDUAL;
+            }
+        }
+    }
+    const int32_t count = (int32_t)__popcll(__ballot(keep));
+    if (lane == 0) {
+        kept[wave] = count;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int32_t sum = 0;
+#pragma unroll
+        for (int w = 0; w < kPoseTile / 64; ++w) {
+            sum += kept[w];
+        }
+        if (sum > 0) {
+            atomicAdd(&p.n_inliers[0], sum);
+        }
+    }
+}
+
+}  // namespace
+
+hipError_t pnp_launch(const PnpPlan &plan, const PnpParams &p, hipStream_t stream) {
+    PnpParams q = p;
+    q.scan_per_thread = plan.scan_per_thread;
+    q.select_per_thread = plan.select_per_thread;
+    hipLaunchKernelGGL(pnp_scan_kernel, dim3(1), dim3(kEpipolarScanBlock), 0, stream, q);
+    hipLaunchKernelGGL(pnp_hypothesis_kernel, dim3(plan.hyp_blocks), dim3(kEpipolarHypBlock), 0, stream, q);
+    hipLaunchKernelGGL(pnp_score_kernel, dim3(plan.score_tiles, plan.score_groups), dim3(kEpipolarScoreTile), 0, stream, q);
+    hipLaunchKernelGGL(pnp_select_kernel, dim3(1), dim3(kEpipolarScanBlock), 0, stream, q);
+    for (int32_t step = 0; step < plan.refine_iterations; ++step) {
+        q.step = step;
+        hipLaunchKernelGGL(pnp_sums_kernel, dim3(plan.tiles), dim3(kPoseTile), 0, stream, q);
+        hipLaunchKernelGGL(pnp_step_kernel, dim3(1), dim3(kPoseSolveBlock), 0, stream, q);
+    }
+    hipLaunchKernelGGL(pnp_finish_kernel, dim3(plan.tiles), dim3(kPoseTile), 0, stream, q);
+    return hipGetLastError();
+}
+
+}  // namespace ftk

@@ -388,6 +388,53 @@ int ftk_two_view_pose_device(ftk_context *ctx, void *stream, const float *d_ref_
                              float fy, float cx, float cy, float fx_cur, float fy_cur, float cx_cur, float cy_cur, float threshold, float baseline,
                              void *d_workspace, float *d_pose, float *d_points, float *d_E, int32_t *d_n_front, int32_t *d_valid, int32_t *d_n_points);
 
+/* ---- camera pose from landmarks and their pixels (PnpRansac) --------------------- */
+
+/*
+ * What every frame after the second asks: given landmarks d_landmarks float32 [n][3] (in the frame the points of TwoViewPose are in) and
+ * the pixels d_uv float32 [n][2] where they are seen now, the pose of the camera, all on the device.  DESIGN.md 5.30 states every float
+ * operation and its order (float32, no contraction, `/` and sqrtf correctly rounded); the result is a pure function of the inputs and
+ * the seed.  In short:
+ *   a point takes part iff d_status[i] == FTK_TRACKED, its five numbers are finite and its landmark is not exactly (0, 0, 0) (how
+ *   TwoViewPose writes "no landmark"); nothing else of a point that is not TRACKED is read.  The participants are listed in ascending
+ *   index order with x = (u - cx) / fx, y = (v - cy) / fy;
+ *   hypothesis h draws FTK_PNP_SAMPLE = 6 distinct participants by the filters' sampler (same generator, seed mixing and
+ *   FTK_EPIPOLAR_MAX_ATTEMPTS), centres their landmarks on the sample mean and divides by the mean absolute deviation, builds the DLT
+ *   system of the 3 x 4 projection (two rows per point, the twelfth row dropped: 11 x 12) and takes its null vector by the filters'
+ *   elimination with complete pivoting.  The conditioning is folded back, the sign fixed so that the six depths are positive.  Invalid:
+ *   a zero pivot, anything non-finite, depths of both signs.  A model is P = [A | b], FTK_PNP_MODEL_FLOATS = 12 floats row-major;
+ *   a participant is an inlier of camera coordinates (c0, c1, c2) iff c2 > 0 and (c0 - x c2)^2 + ((c1 - y c2) fy / fx)^2 <=
+ *   (threshold / fx)^2 c2^2, both sides finite: a reprojection error of at most `threshold` pixels, without the division.  Integer counts;
+ *   the highest count wins, the lowest h among equals;
+ *   the winner's pose: R the nearest rotation to A through the cyclic Jacobi of A^T A (FTK_POSE_JACOBI_SWEEPS sweeps; det A < 0: the term
+ *   of the smallest eigenvalue changes sign; det A = 0 or an eigenvalue <= 0: invalid), t = b / s with s the mean singular value;
+ *   refine_iterations Gauss-Newton steps on the reprojection error.  The first step is taken over the inliers of the model that won (those
+ *   in front of the camera under the pose: the nearest rotation of a six-point model of noisy pixels can be pixels away from the model
+ *   itself), every later step over the inliers of the current pose.  Each step: the 21 + 6 sums in TwoViewPose's tree
+ *   (tiles of FTK_POSE_TILE, then the tile totals in order), an LDL^T without pivoting, a first-order quaternion step with
+ *   renormalisation.  A step with fewer than 6 inliers, a pivot that is not > 0, or a non-finite update ends the refit; the pose before
+ *   it stands.
+ * Outputs: d_pose float32 [7] = q_rc (w >= 0, x, y, z), p_rc in ftk_direct_track's convention (x_cur ~ q_rc^-1 (X - p_rc)); d_n_inliers,
+ * d_best (the winning hypothesis), d_valid (1 / -1) int32 [1] each; d_counts int32 [hypotheses] (-1: invalid) and d_models float32
+ * [hypotheses][12] when not null.  d_status is rewritten in place: a participant that is no inlier of the final pose becomes
+ * FTK_LARGE_RESIDUAL; no other point is touched.  INVALID (fewer than 6 participants, no valid hypothesis, a singular or non-finite
+ * pose; in particular landmarks of one plane, for which the six-point DLT has no unique solution): no status changes, valid = -1,
+ * best = -1, n_inliers = 0, pose = (1, 0, 0, 0, 0, 0, 0).
+ * d_workspace: ftk_pnp_ransac_workspace_bytes(n, hypotheses, refine_iterations) bytes, 16-byte aligned, no initialisation needed.
+ * n = 1 .. FTK_TRACK_TABLE_MAX_SLOTS, hypotheses = 1 .. FTK_EPIPOLAR_MAX_HYPOTHESES, refine_iterations = 0 ..
+ * FTK_PNP_MAX_REFINE_ITERATIONS (beyond: FTK_E_UNSUPPORTED); fx, fy finite and > 0, cx, cy finite, threshold >= 0 with threshold^2
+ * finite in float32, else FTK_E_INVALID_ARGUMENT, all before any launch.  5 + 2 refine_iterations launches of fixed shape on `stream`;
+ * no host read, no synchronisation, no allocation: capturable.
+ */
+#define FTK_PNP_SAMPLE 6
+#define FTK_PNP_MODEL_FLOATS 12
+#define FTK_PNP_MAX_REFINE_ITERATIONS 16
+int ftk_pnp_ransac_workspace_bytes(int32_t n, int32_t hypotheses, int32_t refine_iterations, int64_t *bytes);
+int ftk_pnp_ransac_device(ftk_context *ctx, void *stream, const float *d_landmarks, const float *d_uv, uint8_t *d_status, int32_t n, float fx,
+                          float fy, float cx, float cy, float threshold, int32_t hypotheses, int32_t refine_iterations, uint32_t seed,
+                          void *d_workspace, float *d_pose, int32_t *d_n_inliers, int32_t *d_best, int32_t *d_valid, int32_t *d_counts,
+                          float *d_models);
+
 /*
  * ftk_keypoint_decode_device — a SuperPoint-style network's head tensors to keypoints, scores and descriptors, all in device memory
  * (KeypointDecoder).  The networks are not part of this library; this is the weight-free arithmetic behind them.
