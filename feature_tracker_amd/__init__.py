@@ -20,6 +20,7 @@ from .transformer import LightGlue, TransformerLayer, attention, rotary_encoding
 from .two_view import TwoViewRansac, TwoViewResult  # noqa: F401
 from .two_view_pose import TwoViewPose, TwoViewPoseResult  # noqa: F401
 from .pnp import PnpRansac, PnpResult  # noqa: F401
+from .track_odometry import TrackOdometry  # noqa: F401
 from .tracker import (  # noqa: F401
     BriefDescriptor, BriefMatcher, CosineMatcher, DenseOpticalFlow, DenseOpticalFlowOptions, DirectMethod, DirectMethodOptions, DiskMatcher, SuperpointMatcher, Context, FeaturePointHarrisDetector, DescriptorMatcherOptions, ImagePyramid, OpticalFlow, OpticalFlowAffineKlt, OpticalFlowBasicKlt,
     OpticalFlowLssdKlt, OpticalFlowOptions, default_context, pack_brief, unpack_brief, refresh_env_switches,
@@ -27,7 +28,7 @@ from .tracker import (  # noqa: F401
 )
 
 __all__ = [
-    "CorrelationPyramid", "OnDemandCorrelation", "MotionEncoder", "SepConvGru", "UpdateBlock", "upsample_flow", "track_points_from_flow", "warm_start_flow", "FeatureEncoder", "ContextEncoder", "Raft", "RaftVideoTracker", "KltVideoTracker", "MatchVideoTracker", "EpipolarRansac", "EpipolarResult", "TwoViewRansac", "TwoViewResult", "TwoViewPose", "TwoViewPoseResult", "PnpRansac", "PnpResult", "KeypointDecoder", "KeypointResult", "SuperPoint", "MatchAssignment", "TransformerLayer", "LightGlue", "attention", "rotary_encoding", "NNFeatureMatcher", "NNFeatureMatcherOptions", "BriefDescriptor", "BriefMatcher", "CosineMatcher", "DenseOpticalFlow", "DenseOpticalFlowOptions", "DirectMethod", "DirectMethodOptions", "DiskMatcher", "SuperpointMatcher", "Context", "FeaturePointHarrisDetector", "DescriptorMatcherOptions", "ImagePyramid", "OpticalFlow", "OpticalFlowAffineKlt", "OpticalFlowBasicKlt",
+    "CorrelationPyramid", "OnDemandCorrelation", "MotionEncoder", "SepConvGru", "UpdateBlock", "upsample_flow", "track_points_from_flow", "warm_start_flow", "FeatureEncoder", "ContextEncoder", "Raft", "RaftVideoTracker", "KltVideoTracker", "MatchVideoTracker", "EpipolarRansac", "EpipolarResult", "TwoViewRansac", "TwoViewResult", "TwoViewPose", "TwoViewPoseResult", "PnpRansac", "PnpResult", "TrackOdometry", "KeypointDecoder", "KeypointResult", "SuperPoint", "MatchAssignment", "TransformerLayer", "LightGlue", "attention", "rotary_encoding", "NNFeatureMatcher", "NNFeatureMatcherOptions", "BriefDescriptor", "BriefMatcher", "CosineMatcher", "DenseOpticalFlow", "DenseOpticalFlowOptions", "DirectMethod", "DirectMethodOptions", "DiskMatcher", "SuperpointMatcher", "Context", "FeaturePointHarrisDetector", "DescriptorMatcherOptions", "ImagePyramid", "OpticalFlow", "OpticalFlowAffineKlt", "OpticalFlowBasicKlt",
     "OpticalFlowLssdKlt", "OpticalFlowOptions", "default_context", "pack_brief", "unpack_brief", "refresh_env_switches", "synth",
     "NOT_TRACKED", "TRACKED", "LARGE_RESIDUAL", "OUTSIDE", "NUMERIC_ERROR",
 ]

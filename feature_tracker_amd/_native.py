@@ -63,6 +63,12 @@ FTK_LIGHTGLUE_STATE_WORDS = 4  # live0, live1, stopped, stop_layer
 # the landmark table (include/ftk.h)
 FTK_MATCH_TABLE_MAX_SLOTS = 4096
 FTK_MATCH_TABLE_MAX_DIM = 1024
+# TrackOdometry's landmark table (include/ftk.h): the counters' indices and the end entry's modes
+FTK_LANDMARK_TABLE_BLOCK = 256
+FTK_LANDMARK_TABLE_COUNTERS = 8
+FTK_LANDMARK_TABLE_VALID, FTK_LANDMARK_TABLE_N_NEW, FTK_LANDMARK_TABLE_N_ANCHORED = 0, 1, 2
+FTK_LANDMARK_TABLE_N_LANDMARKS, FTK_LANDMARK_TABLE_N_DROPPED, FTK_LANDMARK_TABLE_LOST = 3, 4, 5
+FTK_LANDMARK_TABLE_STEADY, FTK_LANDMARK_TABLE_BOOTSTRAP = 0, 1
 # SepConvGru (include/ftk.h): the supported sizes and the packed weight layout
 FTK_SEP_CONV_GRU_MAX_PARTS = 3
 FTK_SEP_CONV_GRU_MAX_H_CHANNELS = 1024
@@ -103,6 +109,7 @@ EXPORTS = [
     "ftk_two_view_workspace_bytes", "ftk_two_view_ransac_device",
     "ftk_two_view_pose_workspace_bytes", "ftk_two_view_pose_device",
     "ftk_pnp_ransac_workspace_bytes", "ftk_pnp_ransac_device",
+    "ftk_landmark_table_begin_device", "ftk_landmark_table_end_device",
     "ftk_keypoint_decode_workspace_bytes", "ftk_keypoint_decode_device",
     "ftk_match_assignment_workspace_bytes", "ftk_match_assignment_device",
     "ftk_transformer_layer_workspace_bytes", "ftk_attention_device", "ftk_linear_device", "ftk_transformer_layer_device",
@@ -298,6 +305,8 @@ def lib() -> C.CDLL:
     l.ftk_two_view_pose_device.argtypes = [vp, vp, vp, vp, vp, i32] + [f32] * 10 + [vp] * 7
     l.ftk_pnp_ransac_workspace_bytes.argtypes = [i32, i32, i32, i64p]
     l.ftk_pnp_ransac_device.argtypes = [vp, vp, vp, vp, vp, i32] + [f32] * 5 + [i32, i32, C.c_uint32] + [vp] * 7
+    l.ftk_landmark_table_begin_device.argtypes = [vp, vp, vp, i32] + [vp] * 6
+    l.ftk_landmark_table_end_device.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, i32] + [f32] * 6 + [vp] * 6
     l.ftk_keypoint_decode_workspace_bytes.argtypes = [i32, i32, i32, i32, i64p]
     l.ftk_keypoint_decode_device.argtypes = [vp, vp, vp, i32, i32, vp, i32, C.c_int64, C.c_int64, C.c_int64, i32, f32, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]
     l.ftk_match_assignment_workspace_bytes.argtypes = [i32, i32, i32, i32, i64p]

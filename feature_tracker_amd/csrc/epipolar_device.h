@@ -124,6 +124,49 @@ __device__ __forceinline__ bool tv_inlier(const float (&g)[9], const float4 q, f
     return w != 0.0f && ep_finite(lhs) && ep_finite(rhs) && lhs <= rhs;
 }
 
+// ---- what PnpRansac (pnp_kernels.hip) and the landmark table (landmark_table_kernels.hip) share ----
+
+// The inlier rule on the camera coordinates c of a landmark seen at the calibrated (x, y).
+__device__ __forceinline__ bool pnp_inlier(const float (&c)[3], const float x, const float y, const float ry, const float tn2) {
+    const float ex = c[0] - x * c[2];
+    const float ey = (c[1] - y * c[2]) * ry;
+    const float lhs = ex * ex + ey * ey, rhs = tn2 * (c[2] * c[2]);
+    return c[2] > 0.0f && ep_finite(lhs) && ep_finite(rhs) && lhs <= rhs;
+}
+
+// R_rc of a unit quaternion, row-major.
+__device__ __forceinline__ void pnp_rotation(const float (&q)[7], float (&R)[9]) {
+    const float w = q[0], x = q[1], y = q[2], z = q[3];
+    R[0] = 1.0f - 2.0f * (y * y + z * z), R[1] = 2.0f * (x * y - w * z), R[2] = 2.0f * (x * z + w * y);
+    R[3] = 2.0f * (x * y + w * z), R[4] = 1.0f - 2.0f * (x * x + z * z), R[5] = 2.0f * (y * z - w * x);
+    R[6] = 2.0f * (x * z - w * y), R[7] = 2.0f * (y * z + w * x), R[8] = 1.0f - 2.0f * (x * x + y * y);
+}
+
+// c = R_rc^T (X - p_rc)
+__device__ __forceinline__ void pnp_camera(const float (&R)[9], const float (&ps)[7], const float X, const float Y, const float Z, float (&c)[3]) {
+    const float d0 = X - ps[4], d1 = Y - ps[5], d2 = Z - ps[6];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        c[j] = (R[j] * d0 + R[3 + j] * d1) + R[6 + j] * d2;
+    }
+}
+
+// The two-ray depths z1, z2 of z2 b = z1 a + t by the 2 x 2 normal equations of the midpoint (TwoViewPose's cheirality test, DESIGN.md
+// 5.29; the landmark table's triangulation); aa, bb, ab: the rays' squared lengths and their product, for the caller's
+// parallax test.  true: both depths finite and > 0.
+__device__ __forceinline__ bool ep_two_ray_depths(const float (&a)[3], const float (&b)[3], const float (&t)[3], float &z1, float &z2, float &aa,
+                                                  float &bb, float &ab) {
+    aa = (a[0] * a[0] + a[1] * a[1]) + a[2] * a[2];
+    bb = (b[0] * b[0] + b[1] * b[1]) + b[2] * b[2];
+    ab = (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2];
+    const float at = (a[0] * t[0] + a[1] * t[1]) + a[2] * t[2];
+    const float bt = (b[0] * t[0] + b[1] * t[1]) + b[2] * t[2];
+    const float det = aa * bb - ab * ab;
+    z1 = (ab * bt - bb * at) / det;
+    z2 = (aa * bt - ab * at) / det;
+    return ep_finite(z1) && ep_finite(z2) && z1 > 0.0f && z2 > 0.0f;
+}
+
 // The models.  kSample: correspondences of a hypothesis; kSlot: the model's slot of TwoViewParams; fill: the rows that the k-th drawn
 // correspondence q contributes to the 8 x 9 system a (LDS, a[(r * 9 + c) * L] of this lane); inlier: the test of a participant.
 struct FundamentalModel {

@@ -28,31 +28,6 @@ namespace {
 
 constexpr int kFlagOk = 0, kFlagDone = 1, kFlagWinner = 2;
 
-// The inlier rule on the camera coordinates c of a landmark seen at the calibrated (x, y).
-__device__ __forceinline__ bool pnp_inlier(const float (&c)[3], const float x, const float y, const float ry, const float tn2) {
-    const float ex = c[0] - x * c[2];
-    const float ey = (c[1] - y * c[2]) * ry;
-    const float lhs = ex * ex + ey * ey, rhs = tn2 * (c[2] * c[2]);
-    return c[2] > 0.0f && ep_finite(lhs) && ep_finite(rhs) && lhs <= rhs;
-}
-
-// R_rc of a unit quaternion, row-major.
-__device__ __forceinline__ void pnp_rotation(const float (&q)[7], float (&R)[9]) {
-    const float w = q[0], x = q[1], y = q[2], z = q[3];
-    R[0] = 1.0f - 2.0f * (y * y + z * z), R[1] = 2.0f * (x * y - w * z), R[2] = 2.0f * (x * z + w * y);
-    R[3] = 2.0f * (x * y + w * z), R[4] = 1.0f - 2.0f * (x * x + z * z), R[5] = 2.0f * (y * z - w * x);
-    R[6] = 2.0f * (x * z - w * y), R[7] = 2.0f * (y * z + w * x), R[8] = 1.0f - 2.0f * (x * x + y * y);
-}
-
-// c = R_rc^T (X - p_rc)
-__device__ __forceinline__ void pnp_camera(const float (&R)[9], const float (&ps)[7], const float X, const float Y, const float Z, float (&c)[3]) {
-    const float d0 = X - ps[4], d1 = Y - ps[5], d2 = Z - ps[6];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        c[j] = (R[j] * d0 + R[3 + j] * d1) + R[6 + j] * d2;
-    }
-}
-
 __global__ void __launch_bounds__(kEpipolarScanBlock) pnp_scan_kernel(const PnpParams p) {
     __shared__ int32_t scan[kEpipolarScanBlock];
     ep_scan_participants_if(

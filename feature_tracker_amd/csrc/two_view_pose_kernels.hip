@@ -274,16 +274,9 @@ __device__ __forceinline__ bool pose_in_front(const float (&R)[9], const float (
     }
     float a[3];
     pose_rotate(R, q.x, q.y, a);
-    const float b0 = q.z, b1 = q.w, b2 = 1.0f;
-    const float aa = (a[0] * a[0] + a[1] * a[1]) + a[2] * a[2];
-    const float bb = (b0 * b0 + b1 * b1) + b2 * b2;
-    const float ab = (a[0] * b0 + a[1] * b1) + a[2] * b2;
-    const float at = (a[0] * t[0] + a[1] * t[1]) + a[2] * t[2];
-    const float bt = (b0 * t[0] + b1 * t[1]) + b2 * t[2];
-    const float det = aa * bb - ab * ab;
-    z1 = (ab * bt - bb * at) / det;
-    z2 = (aa * bt - ab * at) / det;
-    return ep_finite(z1) && ep_finite(z2) && z1 > 0.0f && z2 > 0.0f;
+    const float b[3] = {q.z, q.w, 1.0f};
+    float aa, bb, ab;
+    return ep_two_ray_depths(a, b, t, z1, z2, aa, bb, ab);
 }
 
 // Candidate c = 2 * (R is Rb) + (t is -u3), from the model block.

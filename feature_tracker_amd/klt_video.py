@@ -16,6 +16,7 @@ from ._device_epipolar import SEED_ARG, check_sizes, epipolar_ransac_args
 from ._device_two_view import check_mode, prefer_to_permille, two_view_ransac_args
 from ._device_klt_video import harris_survivor_bound, track_table_fill_args, track_table_retire_args
 from ._torch_call import OnStream, call, check_ctx
+from .track_odometry import TrackOdometry
 from .tracker import OUTSIDE, ImagePyramid, OpticalFlow
 
 _MIN_SIDE = 23  # 2 * Harris border + 1: a smaller image has no valid centre
@@ -46,7 +47,10 @@ class KltVideoTracker:
     routes the same step through ``TwoViewRansac`` (``epipolar_prefer_homography`` is its ``prefer_homography``):
     ``epipolar_F`` / ``epipolar_H`` float32 [3, 3], ``epipolar_n_inliers`` / ``epipolar_best`` int32 [2] (slot 0 the fundamental matrix,
     slot 1 the homography) and ``epipolar_model_chosen`` int32 [1] (-1 before the first fit) then hold the last fit; with the default
-    ``"fundamental"`` the tracker launches what it launches without the argument and the two new attributes stay None.  ``ctx``: a context made by
+    ``"fundamental"`` the tracker launches what it launches without the argument and the two new attributes stay None.
+    ``odometry``: a ``TrackOdometry`` built on the same ``ctx`` (anything else is a ValueError at construction); ``track()`` then ends with
+    ``odometry.update(self.ids, self.points, (H, W))``, after the fill; ``reset()`` of the tracker leaves it alone.  None: the
+    tracker launches exactly what it launches without the argument.  ``ctx``: a context made by
     ``device.context_on_stream`` (torch must know the stream the kernels run on); None: the tracker makes a stream and a context of its own.
 
     Limits: uint8 images of at least 23 x 23 and of one shape (``reset()`` before another), float32 points, the context's stream (the
@@ -55,7 +59,7 @@ class KltVideoTracker:
 
     def __init__(self, flow, max_features: int, levels: int = 4, min_distance: int = 25, min_response: float = 40.0,
                  forward_backward: Optional[float] = None, ctx=None, epipolar_threshold: Optional[float] = None, epipolar_hypotheses: int = 512,
-                 epipolar_seed: int = 0, epipolar_model: str = "fundamental", epipolar_prefer_homography: float = 0.75):
+                 epipolar_seed: int = 0, epipolar_model: str = "fundamental", epipolar_prefer_homography: float = 0.75, odometry=None):
         if not isinstance(flow, OpticalFlow) or flow._model is None:
             raise ValueError(f"flow must be an OpticalFlowBasicKlt, OpticalFlowAffineKlt or OpticalFlowLssdKlt (got {type(flow).__name__})")
         n = int(max_features)
@@ -83,6 +87,13 @@ class KltVideoTracker:
             _, _, self.epipolar_threshold, self.epipolar_hypotheses, self.epipolar_seed = check_sizes((1, 1), epipolar_threshold, epipolar_hypotheses,
                                                                                                       epipolar_seed)
         check_ctx(ctx, none_means="the tracker makes its own", because="the table's tensors are torch's, and ")
+        if odometry is not None:
+            if not isinstance(odometry, TrackOdometry):
+                raise ValueError(f"odometry must be a TrackOdometry or None (got {type(odometry).__name__})")
+            if ctx is None or odometry._ctx is not ctx:
+                raise ValueError("odometry must be a TrackOdometry built on this tracker's ctx (device.context_on_stream): its launches follow the "
+                                 "tracker's on one stream of one device")
+        self.odometry = odometry
         self.flow, self.max_features, self.levels = flow, n, int(levels)
         self.min_distance, self.min_response = int(min_distance), float(min_response)
         self.forward_backward = None if forward_backward is None else float(forward_backward)
@@ -155,6 +166,8 @@ class KltVideoTracker:
                     ctx, cur, self.min_distance, self.min_response, self.ids, self.points, self.prev_points, self.status, self.age, self.n_live, self.next_id,
                     self._free, self._n_free)
             call("ftk_track_table_fill_device", fill, ctx)
+            if self.odometry is not None:
+                self.odometry.update(self.ids, self.points, self._shape)
         self._spare = 1 - self._spare
         self._frames += 1
         return self

@@ -435,6 +435,60 @@ int ftk_pnp_ransac_device(ftk_context *ctx, void *stream, const float *d_landmar
                           void *d_workspace, float *d_pose, int32_t *d_n_inliers, int32_t *d_best, int32_t *d_valid, int32_t *d_counts,
                           float *d_models);
 
+/* ---- the landmark table beside a track table (TrackOdometry) --------------------- */
+
+/*
+ * What turns the single-shot pieces above into a per-frame front end: a table of n slots beside a track table (d_ids int64 [n], -1 = empty;
+ * d_points float32 [n][2]; KltVideoTracker's or MatchVideoTracker's) that says which slot's landmark belongs to which track and gives a
+ * landmark to a track born after the first pair.  The state is the caller's device arrays: d_owner int64 [n] (the id the slot's state
+ * belongs to, -1: none), d_landmarks float32 [n][3] (world frame, exactly (0, 0, 0): no landmark, which is ftk_pnp_ransac_device's own
+ * rule, so the array goes into it unchanged), d_anchor_uv float32 [n][2], d_anchor_pose float32 [n][7] (q_rc, p_rc of the anchor
+ * observation), d_anchor_frame int32 [n] (negative: no anchor), d_counters int32 [FTK_LANDMARK_TABLE_COUNTERS] (indices below) and d_pose
+ * float32 [7].  DESIGN.md 5.31 states every float operation and its order (float32, no contraction, `/` correctly rounded); every output
+ * is a pure function of the inputs.  A frame is begin, the pose (ftk_pnp_ransac_device in the steady state), end.
+ *
+ * ftk_landmark_table_begin_device, before the pose is known.  Per slot: if d_ids[s] != d_owner[s] the slot changed hands: owner <- id, the
+ * landmark zeroed, anchor_frame <- -1.  d_pnp_status[s] <- FTK_TRACKED iff id >= 0 and the landmark is not (0, 0, 0), d_anchor_status[s] <-
+ * FTK_TRACKED iff id >= 0 and anchor_frame >= 0 (the participants of a two-view bootstrap on d_anchor_uv), else FTK_NOT_TRACKED.
+ * The counters N_NEW, N_ANCHORED, N_LANDMARKS and N_DROPPED are zeroed: end adds to them, so end follows begin.
+ *
+ * ftk_landmark_table_end_device, after it.  d_pose_in float32 [7] / d_valid_in int32 [1]: the pose of this frame and its validity
+ * (ftk_pnp_ransac_device's outputs, or ftk_two_view_pose_device's in the bootstrap); d_model_in int32 [1] or null: ftk_two_view_ransac_device's
+ * chosen model, anything but 0 counts as invalid (a homography is no pose).  Invalid (valid_in != 1): VALID <- -1, LOST += 1 and no slot
+ * changes.  Otherwise VALID <- 1, LOST <- 0, d_pose <- pose_in, and for every live slot (id >= 0):
+ *   a (steady mode) d_status_in[s] == FTK_LARGE_RESIDUAL: the landmark is zeroed, the anchor dropped, N_DROPPED counts it; on to b;
+ *   b (steady mode) no landmark and no anchor: anchor_uv <- points[s], anchor_pose <- pose_in, anchor_frame <- frame;
+ *   c no landmark and an anchor that this call did not write: with x = (u - cx) / fx, y = (v - cy) / fy, the world rays a = R_a (x_a, y_a, 1),
+ *     b = R_c (x_c, y_c, 1) (R of a quaternion by ftk_pnp_ransac_device's nine expressions) and t = p_a - p_c, the depths of z2 b = z1 a + t
+ *     by ftk_two_view_pose_device's 2 x 2 normal equations.  Any non-finite input: the attempt fails.  (a.b)^2 > min_parallax_cos2
+ *     ((a.a) (b.b)): it WAITS, nothing changes.  A depth not finite or <= 0: it fails.  X = ((p_a + z1 a) + (p_c + z2 b)) * 0.5 per
+ *     component; not finite, exactly (0, 0, 0), or no inlier of both views by ftk_pnp_ransac_device's rule on R^T (X - p) with `threshold`:
+ *     it fails.  Success: the landmark is written, N_NEW counts it.  Failure in steady mode: the slot is anchored again by b's writes; in
+ *     bootstrap mode nothing changes.
+ * N_ANCHORED counts the live slots that had an anchor when the call began, N_LANDMARKS those that hold a landmark when it ends (both
+ * also when the pose is invalid).  Counts are ballots, one integer atomic add per workgroup of FTK_LANDMARK_TABLE_BLOCK slots and counter.
+ * n = 1 .. FTK_TRACK_TABLE_MAX_SLOTS (beyond: FTK_E_UNSUPPORTED); frame >= 0, mode one of the two, fx, fy finite and > 0, cx, cy finite,
+ * threshold >= 0 with threshold^2 finite in float32, min_parallax_cos2 in 0 .. 1 (the squared cosine of the parallax floor, computed by
+ * the caller: no trigonometry runs on the device), else FTK_E_INVALID_ARGUMENT, all before any launch.  One launch of fixed shape each on
+ * `stream`; no host read, no synchronisation, no allocation: capturable.
+ */
+#define FTK_LANDMARK_TABLE_BLOCK 256
+#define FTK_LANDMARK_TABLE_COUNTERS 8
+#define FTK_LANDMARK_TABLE_VALID 0
+#define FTK_LANDMARK_TABLE_N_NEW 1
+#define FTK_LANDMARK_TABLE_N_ANCHORED 2
+#define FTK_LANDMARK_TABLE_N_LANDMARKS 3
+#define FTK_LANDMARK_TABLE_N_DROPPED 4
+#define FTK_LANDMARK_TABLE_LOST 5
+#define FTK_LANDMARK_TABLE_STEADY 0
+#define FTK_LANDMARK_TABLE_BOOTSTRAP 1
+int ftk_landmark_table_begin_device(ftk_context *ctx, void *stream, const int64_t *d_ids, int32_t n, int64_t *d_owner, float *d_landmarks,
+                                    int32_t *d_anchor_frame, uint8_t *d_pnp_status, uint8_t *d_anchor_status, int32_t *d_counters);
+int ftk_landmark_table_end_device(ftk_context *ctx, void *stream, const int64_t *d_ids, const float *d_points, int32_t n, const uint8_t *d_status_in,
+                                  const float *d_pose_in, const int32_t *d_valid_in, const int32_t *d_model_in, int32_t frame, int32_t mode, float fx,
+                                  float fy, float cx, float cy, float threshold, float min_parallax_cos2, float *d_landmarks, float *d_anchor_uv,
+                                  float *d_anchor_pose, int32_t *d_anchor_frame, int32_t *d_counters, float *d_pose);
+
 /*
  * ftk_keypoint_decode_device — a SuperPoint-style network's head tensors to keypoints, scores and descriptors, all in device memory
  * (KeypointDecoder).  The networks are not part of this library; this is the weight-free arithmetic behind them.
