@@ -28,11 +28,22 @@ def check_counts(hypotheses, refine_iterations, seed):
     return k, r, s
 
 
+SAMPLES = {"dlt6": N.FTK_PNP_SAMPLE_DLT6, "p3p": N.FTK_PNP_SAMPLE_P3P}
+
+
+def check_sample(sample, name="sample") -> str:
+    """The sampler's name, or the ValueError: before anything touches a device."""
+    if not isinstance(sample, str) or sample not in SAMPLES:
+        raise ValueError(f"{name} must be one of {sorted(SAMPLES)} (got {sample!r})")
+    return sample
+
+
 def pnp_args(ctx, landmarks, uv, status, K, threshold: float, hypotheses: int, refine_iterations: int, seed: int, workspace, pose, n_inliers, best,
-             valid, counts=None, models=None, stream=None):
-    """Checks one ftk_pnp_ransac_device call and returns its marshalled arguments."""
+             valid, counts=None, models=None, stream=None, sample=None):
+    """Checks one ftk_pnp_ransac_device call (``sample`` None) or one ftk_pnp_ransac_sampled_device call and returns its marshalled arguments."""
     from . import device as D
 
+    code = None if sample is None else SAMPLES[check_sample(sample)]
     cam = check_camera("K", K)
     t, _ = check_scalars(threshold, 1.0)
     k, r, s = check_counts(hypotheses, refine_iterations, seed)
@@ -54,7 +65,7 @@ def pnp_args(ctx, landmarks, uv, status, K, threshold: float, hypotheses: int, r
         D._check("models", models, D._F32, (k, N.FTK_PNP_MODEL_FLOATS), dev)
     st = stream_or_current(landmarks, stream)
     return ((ctx.handle, C.c_void_p(st.cuda_stream), pointer(landmarks), pointer(uv), pointer(status), n) + tuple(C.c_float(e) for e in cam)
-            + (C.c_float(t), k, r, C.c_uint32(s), pointer(workspace), pointer(pose), pointer(n_inliers), pointer(best), pointer(valid), pointer(counts),
+            + (C.c_float(t), k, r, C.c_uint32(s)) + (() if code is None else (code,)) + (pointer(workspace), pointer(pose), pointer(n_inliers), pointer(best), pointer(valid), pointer(counts),
                pointer(models)))
 
 
@@ -73,3 +84,14 @@ def pnp_ransac_device(ctx, landmarks, uv, status, K, threshold: float, hypothese
     args = pnp_args(ctx, landmarks, uv, status, K, threshold, hypotheses, refine_iterations, seed, workspace, pose, n_inliers, best, valid, counts, models,
                     stream)
     N.check(N.lib().ftk_pnp_ransac_device(*args), ctx.handle)
+
+
+def pnp_ransac_sampled_device(ctx, landmarks, uv, status, K, threshold: float, hypotheses: int, refine_iterations: int, seed: int, sample: str,
+                              workspace, pose, n_inliers, best, valid, counts=None, models=None, stream=None) -> None:
+    """ftk_pnp_ransac_sampled_device: ``pnp_ransac_device`` with the minimal solver behind the hypotheses chosen by ``sample``: "dlt6" (that
+    call exactly) or "p3p" (four participants per hypothesis, three to a P3P solver and the fourth choosing among its
+    solutions; ``models`` then holds [R | t]; a call needs 4 participants, and landmarks of one plane give a pose).  Same workspace, same
+    launches, same checks; another ``sample`` is a ValueError before the device is touched."""
+    args = pnp_args(ctx, landmarks, uv, status, K, threshold, hypotheses, refine_iterations, seed, workspace, pose, n_inliers, best, valid, counts, models,
+                    stream, sample=check_sample(sample))
+    N.check(N.lib().ftk_pnp_ransac_sampled_device(*args), ctx.handle)

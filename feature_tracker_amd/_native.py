@@ -46,6 +46,9 @@ FTK_POSE_TILE = 256
 FTK_PNP_SAMPLE = 6
 FTK_PNP_MODEL_FLOATS = 12
 FTK_PNP_MAX_REFINE_ITERATIONS = 16
+FTK_PNP_SAMPLE_DLT6 = 0
+FTK_PNP_SAMPLE_P3P = 1
+FTK_PNP_P3P_SAMPLE = 4
 # the keypoint decoder (include/ftk.h)
 FTK_KEYPOINT_DECODE_CELL = 8
 FTK_KEYPOINT_DECODE_MAX_KEYPOINTS = 65536
@@ -108,7 +111,7 @@ EXPORTS = [
     "ftk_epipolar_workspace_bytes", "ftk_epipolar_ransac_device",
     "ftk_two_view_workspace_bytes", "ftk_two_view_ransac_device",
     "ftk_two_view_pose_workspace_bytes", "ftk_two_view_pose_device",
-    "ftk_pnp_ransac_workspace_bytes", "ftk_pnp_ransac_device",
+    "ftk_pnp_ransac_workspace_bytes", "ftk_pnp_ransac_device", "ftk_pnp_ransac_sampled_device",
     "ftk_landmark_table_begin_device", "ftk_landmark_table_end_device",
     "ftk_keypoint_decode_workspace_bytes", "ftk_keypoint_decode_device",
     "ftk_match_assignment_workspace_bytes", "ftk_match_assignment_device",
@@ -305,6 +308,7 @@ def lib() -> C.CDLL:
     l.ftk_two_view_pose_device.argtypes = [vp, vp, vp, vp, vp, i32] + [f32] * 10 + [vp] * 7
     l.ftk_pnp_ransac_workspace_bytes.argtypes = [i32, i32, i32, i64p]
     l.ftk_pnp_ransac_device.argtypes = [vp, vp, vp, vp, vp, i32] + [f32] * 5 + [i32, i32, C.c_uint32] + [vp] * 7
+    l.ftk_pnp_ransac_sampled_device.argtypes = [vp, vp, vp, vp, vp, i32] + [f32] * 5 + [i32, i32, C.c_uint32, i32] + [vp] * 7
     l.ftk_landmark_table_begin_device.argtypes = [vp, vp, vp, i32] + [vp] * 6
     l.ftk_landmark_table_end_device.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, i32] + [f32] * 6 + [vp] * 6
     l.ftk_keypoint_decode_workspace_bytes.argtypes = [i32, i32, i32, i32, i64p]

@@ -5,15 +5,18 @@
 
 static_assert(FTK_PNP_SAMPLE == ftk::kPnpSample && FTK_PNP_MODEL_FLOATS == ftk::kPnpModelFloats && FTK_PNP_MAX_REFINE_ITERATIONS == ftk::kPnpMaxRefine,
               "include/ftk.h states the constants");
+static_assert(FTK_PNP_SAMPLE_DLT6 == (int)ftk::PnpSample::Dlt6 && FTK_PNP_SAMPLE_P3P == (int)ftk::PnpSample::P3p && FTK_PNP_P3P_SAMPLE == ftk::kP3pSample,
+              "include/ftk.h states the samplers");
 
 namespace {
 
 // The plan of a call, or its refusal as the entry's return value.
-int plan_call(ftk_context *ctx, const char *who, int32_t n, int32_t hypotheses, int32_t refine_iterations, ftk::PnpPlan *plan) {
+int plan_call(ftk_context *ctx, const char *who, int32_t n, int32_t hypotheses, int32_t refine_iterations, int32_t sample, ftk::PnpPlan *plan) {
     ftk::PnpPlanInput in{};
     in.n = n;
     in.hypotheses = hypotheses;
     in.refine_iterations = refine_iterations;
+    in.sampler = static_cast<ftk::PnpSample>(sample);
     *plan = ftk::pnp_plan(in);
     switch (plan->refused) {
         case ftk::PnpRefusal::None:
@@ -26,6 +29,8 @@ int plan_call(ftk_context *ctx, const char *who, int32_t n, int32_t hypotheses, 
         case ftk::PnpRefusal::Refine:
             return ftk_fail(ctx, FTK_E_UNSUPPORTED, "%s: %d refit steps above FTK_PNP_MAX_REFINE_ITERATIONS = %d", who, refine_iterations,
                             FTK_PNP_MAX_REFINE_ITERATIONS);
+        case ftk::PnpRefusal::Sampler:
+            return ftk_fail(ctx, FTK_E_INVALID_ARGUMENT, "%s: sample %d is neither FTK_PNP_SAMPLE_DLT6 nor FTK_PNP_SAMPLE_P3P", who, sample);
         default:
             return ftk_fail(ctx, FTK_E_INVALID_ARGUMENT, "%s: bad sizes (%d points, %d hypotheses, %d refit steps)", who, n, hypotheses, refine_iterations);
     }
@@ -37,20 +42,28 @@ extern "C" {
 
 int ftk_pnp_ransac_workspace_bytes(int32_t n, int32_t hypotheses, int32_t refine_iterations, int64_t *bytes) {
     const char *who = "pnp_ransac_workspace_bytes";
-    return ftk_workspace_bytes<ftk::PnpPlan>(who, bytes, [&](ftk::PnpPlan *plan) { return plan_call(nullptr, who, n, hypotheses, refine_iterations, plan); });
+    return ftk_workspace_bytes<ftk::PnpPlan>(who, bytes, [&](ftk::PnpPlan *plan) { return plan_call(nullptr, who, n, hypotheses, refine_iterations, FTK_PNP_SAMPLE_DLT6, plan); });
 }
 
 int ftk_pnp_ransac_device(ftk_context *ctx, void *stream, const float *d_landmarks, const float *d_uv, uint8_t *d_status, int32_t n, float fx,
                           float fy, float cx, float cy, float threshold, int32_t hypotheses, int32_t refine_iterations, uint32_t seed,
                           void *d_workspace, float *d_pose, int32_t *d_n_inliers, int32_t *d_best, int32_t *d_valid, int32_t *d_counts,
                           float *d_models) {
-    const char *who = "pnp_ransac_device";
+    return ftk_pnp_ransac_sampled_device(ctx, stream, d_landmarks, d_uv, d_status, n, fx, fy, cx, cy, threshold, hypotheses, refine_iterations, seed,
+                                         FTK_PNP_SAMPLE_DLT6, d_workspace, d_pose, d_n_inliers, d_best, d_valid, d_counts, d_models);
+}
+
+int ftk_pnp_ransac_sampled_device(ftk_context *ctx, void *stream, const float *d_landmarks, const float *d_uv, uint8_t *d_status, int32_t n,
+                                  float fx, float fy, float cx, float cy, float threshold, int32_t hypotheses, int32_t refine_iterations,
+                                  uint32_t seed, int32_t sample, void *d_workspace, float *d_pose, int32_t *d_n_inliers, int32_t *d_best,
+                                  int32_t *d_valid, int32_t *d_counts, float *d_models) {
+    const char *who = sample == FTK_PNP_SAMPLE_DLT6 ? "pnp_ransac_device" : "pnp_ransac_sampled_device";
     if (!ctx) {
         return ftk_fail(nullptr, FTK_E_INVALID_ARGUMENT, "%s: null context", who);
     }
     FTK_LOCK(ctx);
     ftk::PnpPlan plan;
-    const int rc = plan_call(ctx, who, n, hypotheses, refine_iterations, &plan);
+    const int rc = plan_call(ctx, who, n, hypotheses, refine_iterations, sample, &plan);
     if (rc != FTK_OK) {
         return rc;
     }

@@ -8,6 +8,8 @@
 //  * pnp_hypothesis_kernel: one lane = one hypothesis, as two_view_hypothesis_kernel.  The six landmarks are conditioned from the sample
 //    alone; the 11 x 12 DLT system lives in LDS, [entry][lane] (156 floats per lane, 39 KB per workgroup: complete pivoting indexes rows
 //    and columns at run time), and the elimination is epipolar_device.h's ep_null_vector_of<11>, the two filters' at another size.
+//  * pnp_p3p_hypothesis_kernel: the "p3p" sampler's kernel in the place of pnp_hypothesis_kernel: four participants, Grunert's
+//    quartic by Ferrari's factorisation on the first three, the fourth chooses among the solutions; registers alone, no LDS.
 //  * pnp_score_kernel: two_view_score_kernel's tiling (a tile of 256 participants in LDS, 4 hypotheses per wave, ballot and popcount, ONE
 //    integer atomicAdd per workgroup and hypothesis) on a participant record of five floats and a model of twelve, which is why it is a
 //    kernel of its own and no third Model of that family: the family's record is one float4 and its models are nine floats.
@@ -159,12 +161,244 @@ __global__ void __launch_bounds__(kEpipolarHypBlock) pnp_hypothesis_kernel(const
     p.counts[h] = ok ? 0 : -1;
 }
 
+// ---- the "p3p" sampler (tests/pnp_p3p_ref.c states every operation below in the same order) ----
+
+__device__ __forceinline__ void p3p_cross(const float (&a)[3], const float (&b)[3], float (&r)[3]) {
+    r[0] = a[1] * b[2] - a[2] * b[1];
+    r[1] = a[2] * b[0] - a[0] * b[2];
+    r[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+__device__ __forceinline__ float p3p_dot(const float (&a)[3], const float (&b)[3]) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
+
+// One Newton step on y^3 + r2 y^2 + r1 y + r0; a step that is not finite is not taken.
+__device__ __forceinline__ float p3p_cubic_step(const float y, const float r2, const float r1, const float r0) {
+    const float val = ((y + r2) * y + r1) * y + r0;
+    const float der = (3.0f * y + 2.0f * r2) * y + r1;
+    const float step = val / der;
+    return ep_finite(step) ? y - step : y;
+}
+
+// What three participants fix before any root is known: the bearings f and their cosines, the landmarks' frame (d01, d02, n = d01 x d02,
+// nn = |n|^2), the squared sides a, b, c, u = N(w) / D(w), and the real roots w = s2 / s0 - 1 of Grunert's quartic in the slots of the two
+// quadratics of Ferrari's factorisation (slots 0, 1 when pair[0], slots 2, 3 when pair[1]).
+struct P3pSetup {
+    float f[3][3];
+    float c01, c02, c12;
+    float d01[3], d02[3], n[3], nn;
+    float a, b, c;
+    float N[3], D[2], alpha2;
+    float w[4];
+    bool pair[2];
+};
+
+// false: the degeneracy test fired (two equal bearings, coincident or collinear landmarks, a leading coefficient of zero, not finite).
+__device__ __forceinline__ bool p3p_setup(const float (&x)[4], const float (&y)[4], const float (&X)[4], const float (&Y)[4], const float (&Z)[4], P3pSetup &s) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float len = sqrtf((x[k] * x[k] + y[k] * y[k]) + 1.0f);
+        s.f[k][0] = x[k] / len, s.f[k][1] = y[k] / len, s.f[k][2] = 1.0f / len;
+    }
+    s.c01 = p3p_dot(s.f[0], s.f[1]), s.c02 = p3p_dot(s.f[0], s.f[2]), s.c12 = p3p_dot(s.f[1], s.f[2]);
+    float g1[3], g2[3], m[3], d12[3];
+#pragma unroll
+    for (int e = 0; e < 3; ++e) {
+        g1[e] = s.f[1][e] - s.f[0][e], g2[e] = s.f[2][e] - s.f[0][e];
+    }
+    p3p_cross(g1, g2, m);
+    const float mm = p3p_dot(m, m);
+    bool ok = ep_finite(mm) && mm > 0.0f;
+    s.d01[0] = X[1] - X[0], s.d01[1] = Y[1] - Y[0], s.d01[2] = Z[1] - Z[0];
+    s.d02[0] = X[2] - X[0], s.d02[1] = Y[2] - Y[0], s.d02[2] = Z[2] - Z[0];
+    d12[0] = X[2] - X[1], d12[1] = Y[2] - Y[1], d12[2] = Z[2] - Z[1];
+    s.c = p3p_dot(s.d01, s.d01), s.b = p3p_dot(s.d02, s.d02), s.a = p3p_dot(d12, d12);
+    p3p_cross(s.d01, s.d02, s.n);
+    s.nn = p3p_dot(s.n, s.n);
+    ok = ok && ep_finite(s.nn) && s.nn > 0.0f;
+    // v = 1 + w: alpha = 1 - c02 and delta = c12 - c01 from differences of bearings
+    const float alpha = 0.5f * p3p_dot(g2, g2), delta = p3p_dot(s.f[1], g2);
+    const float B = s.a / s.b, k = (s.c - s.a) / s.b;
+    const float n0 = 2.0f * (k * alpha), n1 = n0 + 2.0f, n2 = k + 1.0f;
+    const float e0 = 2.0f * delta, e1 = 2.0f * s.c12;
+    s.N[0] = n0, s.N[1] = n1, s.N[2] = n2, s.D[0] = e0, s.D[1] = e1, s.alpha2 = 2.0f * alpha;
+    const float a2 = s.alpha2, t12 = 2.0f * s.c12;
+    const float g0 = e0 * e0, g1c = 2.0f * (e0 * e1), g2c = e1 * e1;
+    const float h0 = n0 * e0, h1 = n0 * e1 + n1 * e0, h2 = n1 * e1 + n2 * e0, h3 = n2 * e1;
+    const float k4 = ((n2 * n2 + g2c) - t12 * h3) - B * g2c;
+    const float k3 = ((2.0f * (n1 * n2) + (2.0f * g2c + g1c)) - t12 * (h3 + h2)) - B * (a2 * g2c + g1c);
+    const float k2 = (((2.0f * (n0 * n2) + n1 * n1) + ((g2c + 2.0f * g1c) + g0)) - t12 * (h2 + h1)) - B * ((a2 * g2c + a2 * g1c) + g0);
+    const float k1 = ((2.0f * (n0 * n1) + (g1c + 2.0f * g0)) - t12 * (h1 + h0)) - B * (a2 * g1c + a2 * g0);
+    const float k0 = ((n0 * n0 + g0) - t12 * h0) - B * (a2 * g0);
+    ok = ok && ep_finite(k4) && k4 != 0.0f;
+    const float p3 = k3 / k4, p2 = k2 / k4, p1 = k1 / k4, p0 = k0 / k4;
+    // Ferrari: the largest real root of the resolvent cubic, kP3pCubicSteps Newton steps from Cauchy's bound on the convex (concave) side
+    const float r2 = -p2, r1 = p3 * p1 - 4.0f * p0, r0 = (4.0f * (p2 * p0) - (p3 * p3) * p0) - p1 * p1;
+    float bound = fabsf(r2);
+    if (fabsf(r1) > bound) {
+        bound = fabsf(r1);
+    }
+    if (fabsf(r0) > bound) {
+        bound = fabsf(r0);
+    }
+    const float xi = -r2 / 3.0f;
+    const float at_xi = ((xi + r2) * xi + r1) * xi + r0;
+    float yr = at_xi > 0.0f ? -(1.0f + bound) : 1.0f + bound;
+    for (int i = 0; i < kP3pCubicSteps; ++i) {  // (a fixed count: no test of a float ends this loop)
+        yr = p3p_cubic_step(yr, r2, r1, r0);
+    }
+    const float db = r2 + yr, dc = r1 + db * yr;
+    const float ddisc = db * db - 4.0f * dc;
+    if (ddisc >= 0.0f) {
+        const float other = (-db + sqrtf(ddisc)) * 0.5f;
+        if (other > yr) {
+            yr = other;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < kP3pCubicPolish; ++i) {
+        yr = p3p_cubic_step(yr, r2, r1, r0);
+    }
+    const float hp = 0.5f * p3, hy = 0.5f * yr;
+    const float R2 = (hp * hp - p2) + yr, S2 = hy * hy - p0, RS = 0.5f * (hp * yr - p1);
+    float R = 0.0f, S = 0.0f;
+    if (R2 >= S2 && R2 > 0.0f) {
+        R = sqrtf(R2), S = RS / R;
+    } else if (S2 > 0.0f) {
+        S = sqrtf(S2), R = RS / S;
+    }
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const float beta = j == 0 ? hp + R : hp - R, gamma = j == 0 ? hy + S : hy - S;
+        const float disc = beta * beta - 4.0f * gamma;
+        s.pair[j] = disc >= 0.0f;
+        const float sq = sqrtf(s.pair[j] ? disc : 0.0f);
+        s.w[2 * j] = (-beta + sq) * 0.5f;
+        s.w[2 * j + 1] = (-beta - sq) * 0.5f;
+    }
+    return ok;
+}
+
+// The pose [R | t] of root w: the distances, kP3pNewtonSteps Newton steps on the three distance equations, the residual test, the two
+// frames.  false: a distance is not positive, a residual is too large or an entry is not finite.
+__device__ __forceinline__ bool p3p_pose(const P3pSetup &s, const float w, const float X0, const float Y0w, const float Z0, float (&P)[12]) {
+    const float u = ((s.N[2] * w + s.N[1]) * w + s.N[0]) / (s.D[1] * w + s.D[0]);
+    const float v = 1.0f + w;
+    const float qv = (w * w + s.alpha2 * w) + s.alpha2;
+    float s0 = sqrtf(s.b / qv), s1 = u * s0, s2 = v * s0;
+#pragma unroll
+    for (int i = 0; i < kP3pNewtonSteps; ++i) {
+        const float q0 = ((s0 * s0 + s1 * s1) - (2.0f * s.c01) * (s0 * s1)) - s.c;
+        const float q1 = ((s0 * s0 + s2 * s2) - (2.0f * s.c02) * (s0 * s2)) - s.b;
+        const float q2 = ((s1 * s1 + s2 * s2) - (2.0f * s.c12) * (s1 * s2)) - s.a;
+        const float j00 = 2.0f * (s0 - s1 * s.c01), j01 = 2.0f * (s1 - s0 * s.c01);
+        const float j10 = 2.0f * (s0 - s2 * s.c02), j12 = 2.0f * (s2 - s0 * s.c02);
+        const float j21 = 2.0f * (s1 - s2 * s.c12), j22 = 2.0f * (s2 - s1 * s.c12);
+        const float det = -(j00 * (j12 * j21)) - j01 * (j10 * j22);
+        const float m12 = q1 * j22 - j12 * q2;
+        const float x0 = (-(q0 * (j12 * j21)) - j01 * m12) / det;
+        const float x1 = (j00 * m12 - q0 * (j10 * j22)) / det;
+        const float x2 = ((-(j00 * (q1 * j21)) - j01 * (j10 * q2)) + q0 * (j10 * j21)) / det;
+        s0 = s0 - x0, s1 = s1 - x1, s2 = s2 - x2;
+    }
+    bool ok = s0 > 0.0f && s1 > 0.0f && s2 > 0.0f;
+    {
+        const float t0 = s0 * s0, t1 = s1 * s1, t2 = s2 * s2;
+        const float q0 = ((t0 + t1) - (2.0f * s.c01) * (s0 * s1)) - s.c;
+        const float q1 = ((t0 + t2) - (2.0f * s.c02) * (s0 * s2)) - s.b;
+        const float q2 = ((t1 + t2) - (2.0f * s.c12) * (s1 * s2)) - s.a;
+        ok = ok && fabsf(q0) <= kP3pResidual * (t0 + t1) && fabsf(q1) <= kP3pResidual * (t0 + t2) && fabsf(q2) <= kP3pResidual * (t1 + t2);
+    }
+    float C0[3], e1[3], e2[3], e3[3], i1[3], i2[3];
+#pragma unroll
+    for (int e = 0; e < 3; ++e) {
+        C0[e] = s0 * s.f[0][e];
+        e1[e] = s1 * s.f[1][e] - C0[e];
+        e2[e] = s2 * s.f[2][e] - C0[e];
+    }
+    p3p_cross(e1, e2, e3);
+    p3p_cross(s.d02, s.n, i1);
+    p3p_cross(s.n, s.d01, i2);
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            P[r * 4 + c] = ((e1[r] * i1[c] + e2[r] * i2[c]) + e3[r] * s.n[c]) / s.nn;
+        }
+        P[r * 4 + 3] = C0[r] - ((P[r * 4] * X0 + P[r * 4 + 1] * Y0w) + P[r * 4 + 2] * Z0);
+    }
+#pragma unroll
+    for (int i = 0; i < 12; ++i) {
+        ok = ok && ep_finite(P[i]);
+    }
+    return ok;
+}
+
+// One lane = one hypothesis: four participants, the first three to the solver, the fourth chooses among its solutions, which are formed
+// and judged one at a time (one candidate and the best so far are live, never four poses).  No LDS.
+__global__ void __launch_bounds__(kEpipolarHypBlock) pnp_p3p_hypothesis_kernel(const PnpParams p) {
+    const int h = blockIdx.x * kEpipolarHypBlock + threadIdx.x;
+    if (h >= p.hypotheses) {
+        return;
+    }
+    const uint32_t m = (uint32_t)max(min(p.m[0], p.n), 0);
+    uint32_t idx[kP3pSample];
+    bool ok = ep_draw<kP3pSample>(p.seed, (uint32_t)h, m, idx);
+    float x[kP3pSample], y[kP3pSample], X[kP3pSample], Y[kP3pSample], Z[kP3pSample];
+#pragma unroll
+    for (int k = 0; k < kP3pSample; ++k) {
+        const float4 q = ok ? p.points[idx[k]] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        x[k] = q.x, y[k] = q.y, X[k] = q.z, Y[k] = q.w;
+        Z[k] = ok ? p.depth[idx[k]] : 0.0f;
+    }
+    P3pSetup s;
+    ok = p3p_setup(x, y, X, Y, Z, s) && ok;
+    float P[12];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) {
+        P[i] = 0.0f;
+    }
+    bool have = false;
+    float best = 0.0f;
+#pragma unroll 1
+    for (int i = 0; i < 4; ++i) {  // the solutions in the order they are produced: w+ and w- of the first quadratic, then of the second
+        const float w = i == 0 ? s.w[0] : i == 1 ? s.w[1] : i == 2 ? s.w[2] : s.w[3];
+        float Q[12];
+        bool take = ok && (i < 2 ? s.pair[0] : s.pair[1]) && p3p_pose(s, w, X[0], Y[0], Z[0], Q);
+        float c[3] = {0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int k = 0; k < kP3pSample; ++k) {  // every sample point in front; c ends as the fourth point's camera coordinates
+#pragma unroll
+            for (int e = 0; e < 3; ++e) {
+                c[e] = ((Q[e * 4] * X[k] + Q[e * 4 + 1] * Y[k]) + Q[e * 4 + 2] * Z[k]) + Q[e * 4 + 3];
+            }
+            take = take && c[2] > 0.0f;
+        }
+        const float ex = c[0] - x[3] * c[2];
+        const float ey = (c[1] - y[3] * c[2]) * p.ry;
+        const float err = ex * ex + ey * ey;
+        take = take && ep_finite(err) && (!have || err < best);
+        if (take) {
+#pragma unroll
+            for (int e = 0; e < 12; ++e) {
+                P[e] = Q[e];
+            }
+            best = err, have = true;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 12; ++i) {
+        p.models[(size_t)h * 12 + i] = have ? P[i] : 0.0f;
+    }
+    p.valid[h] = have ? 1 : 0;
+    p.counts[h] = have ? 0 : -1;
+}
+
 __global__ void __launch_bounds__(kEpipolarScoreTile) pnp_score_kernel(const PnpParams p) {
     __shared__ float4 tile[kEpipolarScoreTile];
     __shared__ float tile_z[kEpipolarScoreTile];
     const int m = min(p.m[0], p.n);
     const int base = blockIdx.x * kEpipolarScoreTile;
-    if (m < kPnpSample || base >= m) {
+    if (m < p.sample || base >= m) {
         return;  // the whole workgroup: the grid covers n
     }
     const int tid = threadIdx.x;
@@ -383,7 +617,7 @@ __global__ void __launch_bounds__(kEpipolarScanBlock) pnp_select_kernel(const Pn
     }
     key = red[0];
     const int m = min(p.m[0], p.n);
-    bool ok = m >= kPnpSample && (key >> 32) != 0ull;  // (with M < 6 no hypothesis was formed)
+    bool ok = m >= p.sample && (key >> 32) != 0ull;  // (with fewer participants than a sample no hypothesis was formed)
     const int h = ok ? (int)(~(uint32_t)(key & 0xFFFFFFFFull)) : -1;
     float ps[7] = {1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
     if (ok) {
@@ -518,7 +752,7 @@ __global__ void __launch_bounds__(kPoseSolveBlock) pnp_step_kernel(const PnpPara
     for (int t = 0; t < tiles; ++t) {
         count += p.tile_counts[t];
     }
-    bool take = count >= kPnpSample;
+    bool take = count >= kPnpRefitRows;
     if (take) {  // H x = -g by an LDL^T without pivoting, column by column
         int e = 0;
         for (int i = 0; i < 6; ++i) {
@@ -649,8 +883,13 @@ hipError_t pnp_launch(const PnpPlan &plan, const PnpParams &p, hipStream_t strea
     PnpParams q = p;
     q.scan_per_thread = plan.scan_per_thread;
     q.select_per_thread = plan.select_per_thread;
+    q.sample = plan.sample;
     hipLaunchKernelGGL(pnp_scan_kernel, dim3(1), dim3(kEpipolarScanBlock), 0, stream, q);
-    hipLaunchKernelGGL(pnp_hypothesis_kernel, dim3(plan.hyp_blocks), dim3(kEpipolarHypBlock), 0, stream, q);
+    if (plan.sampler == PnpSample::P3p) {
+        hipLaunchKernelGGL(pnp_p3p_hypothesis_kernel, dim3(plan.hyp_blocks), dim3(kEpipolarHypBlock), 0, stream, q);
+    } else {
+        hipLaunchKernelGGL(pnp_hypothesis_kernel, dim3(plan.hyp_blocks), dim3(kEpipolarHypBlock), 0, stream, q);
+    }
     hipLaunchKernelGGL(pnp_score_kernel, dim3(plan.score_tiles, plan.score_groups), dim3(kEpipolarScoreTile), 0, stream, q);
     hipLaunchKernelGGL(pnp_select_kernel, dim3(1), dim3(kEpipolarScanBlock), 0, stream, q);
     for (int32_t step = 0; step < plan.refine_iterations; ++step) {

@@ -10,6 +10,7 @@ const char *pnp_refusal_name(PnpRefusal r) {
         case PnpRefusal::Points: return "points";
         case PnpRefusal::Hypotheses: return "hypotheses";
         case PnpRefusal::Refine: return "refine";
+        case PnpRefusal::Sampler: return "sampler";
     }
     return "?";
 }
@@ -32,12 +33,18 @@ PnpPlan pnp_plan(const PnpPlanInput &in) {
         p.refused = PnpRefusal::Hypotheses;
         return p;
     }
+    if (in.sampler != PnpSample::Dlt6 && in.sampler != PnpSample::P3p) {
+        p.refused = PnpRefusal::Sampler;
+        return p;
+    }
     p.refused = PnpRefusal::None;
+    p.sampler = in.sampler;
+    p.sample = in.sampler == PnpSample::P3p ? kP3pSample : kPnpSample;
     p.refine_iterations = in.refine_iterations;
     p.launches = 5 + 2 * in.refine_iterations;
     p.scan_per_thread = (in.n + kEpipolarScanBlock - 1) / kEpipolarScanBlock;
     p.hyp_blocks = (uint32_t)((in.hypotheses + kEpipolarHypBlock - 1) / kEpipolarHypBlock);
-    p.hyp_lds = sizeof(float) * kPnpHypLdsFloats * kEpipolarHypBlock;
+    p.hyp_lds = in.sampler == PnpSample::P3p ? 0 : sizeof(float) * kPnpHypLdsFloats * kEpipolarHypBlock;
     p.score_tiles = (uint32_t)((in.n + kEpipolarScoreTile - 1) / kEpipolarScoreTile);
     p.score_groups = (uint32_t)((in.hypotheses + kEpipolarScoreGroup - 1) / kEpipolarScoreGroup);
     p.select_per_thread = (in.hypotheses + kEpipolarScanBlock - 1) / kEpipolarScanBlock;

@@ -8,6 +8,12 @@
 namespace ftk {
 
 constexpr int kPnpSample = 6;           // FTK_PNP_SAMPLE: participants of a hypothesis
+constexpr int kPnpRefitRows = 6;        // a refit step needs this many rows (the six-point sample's size, under either sampler)
+constexpr int kP3pSample = 4;           // participants of a "p3p" hypothesis: three to the solver, the fourth chooses
+constexpr int kP3pCubicSteps = 64;      // Newton steps on the resolvent cubic from Cauchy's bound
+constexpr int kP3pCubicPolish = 4;      // ... and after the deflation
+constexpr int kP3pNewtonSteps = 1;      // Newton steps on the three distance equations per root
+constexpr float kP3pResidual = 0.0000152587890625f;  // 2^-16: a solution's residuals against the sum of its two squared distances
 constexpr int kPnpRows = 11;            // rows of the DLT system that are eliminated (two per participant, the twelfth dropped)
 constexpr int kPnpModelFloats = 12;     // FTK_PNP_MODEL_FLOATS: a hypothesis, P = [A | b] row-major
 constexpr int kPnpHypLdsFloats = 156;   // per lane: the 11 x 12 matrix, the 12 column indices, the 12 entries of the null vector
@@ -16,19 +22,23 @@ constexpr int kPnpMaxRefine = 16;       // FTK_PNP_MAX_REFINE_ITERATIONS
 constexpr int kPnpStateFloats = 8;      // the pose between the kernels: q_rc (w, x, y, z), p_rc, one unused
 constexpr int kPnpFlags = 4;            // ok (the select kernel formed a pose), done (the refit has ended), the winner, one unused
 
+enum class PnpSample : int32_t { Dlt6 = 0, P3p = 1 };  // FTK_PNP_SAMPLE_DLT6, FTK_PNP_SAMPLE_P3P
 struct PnpPlanInput {
     int32_t n;  // landmarks
     int32_t hypotheses;
     int32_t refine_iterations;
+    PnpSample sampler = PnpSample::Dlt6;
 };
-enum class PnpRefusal { None, Sizes, Points, Hypotheses, Refine };
+enum class PnpRefusal { None, Sizes, Points, Hypotheses, Refine, Sampler };
 struct PnpPlan {
     PnpRefusal refused;        // not None: nothing else is set
     int32_t launches;          // scan, hypotheses, score, select, two per refit step (sums, step), finish: 5 + 2 refine_iterations
     int32_t refine_iterations;
+    PnpSample sampler;         // which hypothesis kernel is launched
+    int32_t sample;            // participants of a hypothesis, and the fewest a call needs: 6 (Dlt6) or 4 (P3p)
     int32_t scan_per_thread;   // consecutive points a thread of the scan workgroup owns (<= 64)
     uint32_t hyp_blocks;       // workgroups of kEpipolarHypBlock lanes of the hypothesis kernel
-    size_t hyp_lds;            // bytes of their matrices
+    size_t hyp_lds;            // bytes of their matrices (0 under P3p: its kernel holds none)
     uint32_t score_tiles;      // grid.x of the scoring kernel: tiles of kEpipolarScoreTile participants, sized for n (M is on the device)
     uint32_t score_groups;     // grid.y: groups of kEpipolarScoreGroup hypotheses
     int32_t select_per_thread; // hypotheses a thread of the select workgroup reduces
@@ -73,6 +83,7 @@ struct PnpParams {
     float *pose;             // [7]
     int32_t *n_inliers, *best, *out_valid;  // [1] each
     int32_t scan_per_thread, select_per_thread;
+    int32_t sample;          // the plan's (the launcher sets it): below it the score and select kernels form nothing
     int32_t step;            // the refit step a sums kernel belongs to (the launcher sets it)
 };
 hipError_t pnp_launch(const PnpPlan &plan, const PnpParams &p, hipStream_t stream);

@@ -489,7 +489,7 @@ from ._device_klt_video import _check_bound, harris_detect_device, track_table_f
 from ._device_epipolar import epipolar_ransac_device  # noqa: E402,F401  (two-view outlier rejection; its own file, see there)
 from ._device_two_view import two_view_ransac_device  # noqa: E402,F401  (the same with a choice of model)
 from ._device_two_view_pose import two_view_pose_device  # noqa: E402,F401  (the pose and the landmarks of the inliers; its own file, see there)
-from ._device_pnp import pnp_ransac_device  # noqa: E402,F401  (the pose from landmarks and their pixels; its own file, see there)
+from ._device_pnp import pnp_ransac_device, pnp_ransac_sampled_device  # noqa: E402,F401  (the pose from landmarks and their pixels; its own file, see there)
 from ._device_landmark_table import landmark_table_begin_device, landmark_table_end_device  # noqa: E402,F401  (the landmark table; its own file, see there)
 from ._device_keypoint_decode import keypoint_decode_device  # noqa: E402,F401  (the keypoint decoder; its own file, see there)
 from ._device_match_assignment import match_assignment_device  # noqa: E402,F401  (LightGlue's assignment head; its own file, see there)

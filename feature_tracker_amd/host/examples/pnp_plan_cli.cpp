@@ -1,6 +1,6 @@
 // pnp_plan_cli — prints the launch plan and workspace layout of PnpRansac (csrc/pnp_plan.h) without a device.  One case per line on stdin:
-//   n hypotheses refine_iterations
-// one line of key=value pairs per case on stdout.  tests/test_pnp_args_cpu.py drives it.
+//   n hypotheses refine_iterations [sampler]
+// one line of key=value pairs per case on stdout; with a sampler (0: dlt6, 1: p3p) the line also ends in sampler= and sample=.  tests/test_pnp_args_cpu.py drives it.
 #include <cstdio>
 #include <iostream>
 #include <sstream>
@@ -16,8 +16,11 @@ int main() {
         for (long long &e : v) {
             line >> e;
         }
+        long long sampler = 0;
+        const bool sampled = static_cast<bool>(line >> sampler);
         ftk::PnpPlanInput in{};
         in.n = (int32_t)v[0], in.hypotheses = (int32_t)v[1], in.refine_iterations = (int32_t)v[2];
+        in.sampler = static_cast<ftk::PnpSample>((int32_t)sampler);
         const ftk::PnpPlan p = ftk::pnp_plan(in);
         printf("refused=%s", ftk::pnp_refusal_name(p.refused));
         if (p.refused == ftk::PnpRefusal::None) {
@@ -28,6 +31,9 @@ int main() {
                    ftk::kEpipolarScoreGroup, p.score_tiles, p.score_groups, p.select_per_thread, ftk::kPoseTile, p.tiles, p.sums_lds, p.points.offset,
                    p.depth.offset, p.list.offset, p.counts.offset, p.models.offset, p.valid.offset, p.totals.offset, p.tile_counts.offset, p.state.offset,
                    p.flags.offset, p.bytes);
+            if (sampled) {
+                printf(" sampler=%d sample=%d", (int)p.sampler, p.sample);
+            }
         }
         printf("\n");
     }

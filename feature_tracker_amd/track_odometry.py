@@ -13,7 +13,7 @@ from . import _native as N
 from ._device_epipolar import check_sizes
 from ._device_landmark_table import (END_FRAME_ARG, END_MODE_ARG, END_MODEL_ARG, END_POSE_ARG, END_STATUS_ARG, END_VALID_ARG, STREAM_ARG, check_parallax,
                                      landmark_begin_args, landmark_end_args)
-from ._device_pnp import check_counts
+from ._device_pnp import check_counts, check_sample
 from ._device_two_view_pose import check_camera, check_scalars
 from ._torch_call import OnStream, call, check_ctx, complain, pointer
 from .pnp import PnpRansac
@@ -32,7 +32,7 @@ def check_min_landmarks(min_landmarks) -> int:
 
 class TrackOdometry:
     """``TrackOdometry(K, threshold=1.0, min_parallax_deg=1.0, min_landmarks=30, baseline=1.0, hypotheses=512, refine_iterations=4,
-    seed=0).update(ids, points, image_size)``, once per frame, on any track table: ``ids`` int64 CUDA [n] (-1 = empty; a slot index is
+    seed=0, ctx=None, pnp_sample="dlt6").update(ids, points, image_size)``, once per frame, on any track table: ``ids`` int64 CUDA [n] (-1 = empty; a slot index is
     stable for the life of a track, an id is never reused) and ``points`` float32 CUDA [n, 2], as ``KltVideoTracker`` and
     ``MatchVideoTracker`` keep them.  Afterwards, all on the device and valid until the next call:
 
@@ -56,7 +56,9 @@ class TrackOdometry:
     homography chosen by "auto" counts as not yet: DESIGN.md 5.29), and with fewer than ``min_landmarks`` anchored slots left the
     bootstrap starts again from the current frame.  The translation of two views has no scale: the map's is ``baseline``.
 
-    Steady state.  ``PnpRansac.solve(landmarks, points, status, seed=seed + frame)`` between the table's two kernels.  A landmark that
+    Steady state.  ``PnpRansac.solve(landmarks, points, status, seed=seed + frame)`` between the table's two kernels, with
+    ``PnpRansac``'s ``sample=pnp_sample`` ("dlt6", or "p3p": a pose also where the landmarks in view lie on one plane; the bootstrap
+    still cannot start on one plane).  A landmark that
     ``PnpRansac`` finds to be an outlier is dropped; a live slot without a landmark is anchored and, once its ray and the anchor's meet at
     ``min_parallax_deg`` or more, triangulated by the two-ray midpoint, kept iff it lies in front of both cameras within ``threshold``
     pixels in both, else anchored again.  A frame whose pose is invalid keeps the previous pose and raises ``lost``; there is no automatic
@@ -67,7 +69,8 @@ class TrackOdometry:
     ``PnpRansac``'s.  Limits: n in 1 .. 65 536 and fixed until ``reset()``, no CPU fallback."""
 
     def __init__(self, K, threshold: float = 1.0, min_parallax_deg: float = 1.0, min_landmarks: int = 30, baseline: float = 1.0, hypotheses: int = 512,
-                 refine_iterations: int = 4, seed: int = 0, ctx=None):
+                 refine_iterations: int = 4, seed: int = 0, ctx=None, pnp_sample: str = "dlt6"):
+        self.pnp_sample = check_sample(pnp_sample, "pnp_sample")
         self.K = check_camera("K", K)
         self.threshold, self.baseline = check_scalars(threshold, baseline)
         self._cos2 = check_parallax(min_parallax_deg)
@@ -76,7 +79,7 @@ class TrackOdometry:
         self.hypotheses, self.refine_iterations, self.seed = check_counts(hypotheses, refine_iterations, seed)
         check_ctx(ctx)
         self._ctx = ctx
-        self._pnp = PnpRansac(self.K, self.hypotheses, self.threshold, self.refine_iterations, self.seed, ctx=ctx)
+        self._pnp = PnpRansac(self.K, self.hypotheses, self.threshold, self.refine_iterations, self.seed, ctx=ctx, sample=self.pnp_sample)
         self._filter = TwoViewRansac("auto", self.hypotheses, self.threshold, seed=self.seed, ctx=ctx)
         self._two_view = TwoViewPose(self.K, threshold=self.threshold, baseline=self.baseline, ctx=ctx)
         self.initialised, self.frame = False, 0

@@ -435,6 +435,26 @@ int ftk_pnp_ransac_device(ftk_context *ctx, void *stream, const float *d_landmar
                           void *d_workspace, float *d_pose, int32_t *d_n_inliers, int32_t *d_best, int32_t *d_valid, int32_t *d_counts,
                           float *d_models);
 
+/* ftk_pnp_ransac_sampled_device: ftk_pnp_ransac_device with a choice of the minimal solver behind the hypotheses.
+ * sample = FTK_PNP_SAMPLE_DLT6: exactly ftk_pnp_ransac_device (which is this call with that value).  sample = FTK_PNP_SAMPLE_P3P:
+ * hypothesis h draws FTK_PNP_P3P_SAMPLE = 4 distinct participants by the same sampler; the first three go to a P3P solver (Grunert's
+ * quartic in s2 / s0 - 1, factored by Ferrari's resolvent cubic, whose root comes from a fixed number of Newton steps; one Newton step
+ * on the three distance equations per root; float32, `+ - * /` and sqrtf alone), which returns up to four poses (R, t), x_cam = R X + t;
+ * of those that put all four sample points in front of the camera, the one with the smallest (c0 - x c2)^2 + ((c1 - y c2) fy / fx)^2 at
+ * the fourth point wins, the first produced among equals.  The model is [R | t], row-major, in the slot of a DLT model; invalid: a draw
+ * that fails, coincident or collinear sample landmarks, two equal bearings, no solution with four positive depths, anything non-finite.
+ * Every other stage is ftk_pnp_ransac_device's; a call needs 4 participants instead of 6 (a refit step still needs 6 rows: with 4 or 5
+ * participants the pose is the winner's), and landmarks of one plane give a pose.  The workspace is ftk_pnp_ransac_workspace_bytes's,
+ * the launches are 5 + 2 refine_iterations.  Another value of sample: FTK_E_INVALID_ARGUMENT before any launch.
+ */
+#define FTK_PNP_SAMPLE_DLT6 0
+#define FTK_PNP_SAMPLE_P3P 1
+#define FTK_PNP_P3P_SAMPLE 4
+int ftk_pnp_ransac_sampled_device(ftk_context *ctx, void *stream, const float *d_landmarks, const float *d_uv, uint8_t *d_status, int32_t n,
+                                  float fx, float fy, float cx, float cy, float threshold, int32_t hypotheses, int32_t refine_iterations,
+                                  uint32_t seed, int32_t sample, void *d_workspace, float *d_pose, int32_t *d_n_inliers, int32_t *d_best,
+                                  int32_t *d_valid, int32_t *d_counts, float *d_models);
+
 /* ---- the landmark table beside a track table (TrackOdometry) --------------------- */
 
 /*

@@ -2,7 +2,8 @@
 torch.linalg.svd for the hypotheses, torch.linalg.solve for the refit) timed in the same run as the yardstick.
 The torch composition is a different algorithm at ties and rounds differently: a yardstick for time only.  Calls are interleaved in one
 process and the medians of device-synchronised wall times are reported, one JSON line per shape (appended to --out, default
-profiles/pnp_bench.jsonl).  No time is asserted anywhere."""
+profiles/pnp_bench.jsonl).  ``--sample dlt6,p3p`` times both samplers of DESIGN.md 5.30a in the same interleaved rounds and writes one line
+per shape and sampler, with a ``sample`` field.  No time is asserted anywhere."""
 from __future__ import annotations
 
 import argparse
@@ -103,7 +104,9 @@ def main():
     ap.add_argument("--repeats", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pnp_bench.jsonl"))
+    ap.add_argument("--sample", default="dlt6", help="the samplers to time in the same rounds, comma-separated: dlt6, p3p")
     args = ap.parse_args()
+    samples_timed = args.sample.split(",")
     import torch
 
     import feature_tracker_amd as F
@@ -114,11 +117,11 @@ def main():
         d_X, d_uv = torch.from_numpy(X).cuda(), torch.from_numpy(uv).cuda()
         fresh = torch.ones(n, dtype=torch.uint8, device="cuda")
         for hypotheses in (512, 2048):
-            pnp = F.PnpRansac(K, hypotheses=hypotheses, threshold=1.0, refine_iterations=4, seed=1)
+            pnps = {name: F.PnpRansac(K, hypotheses=hypotheses, threshold=1.0, refine_iterations=4, seed=1, sample=name) for name in samples_timed}
             status = fresh.clone()
             samples = torch.from_numpy(np.stack([np.random.default_rng(h).permutation(n)[:6] for h in range(hypotheses)])).cuda()
 
-            def solve():
+            def solve(pnp):
                 status.copy_(fresh)
                 return pnp.solve(d_X, d_uv, status)
 
@@ -126,18 +129,20 @@ def main():
                 status.copy_(fresh)
                 return torch_pnp(torch, d_X, d_uv, status, samples, 1.0, 4)
 
-            calls = {"solve": solve, "torch_solve": torch_solve}
+            calls = {name: (lambda pnp=pnp: solve(pnp)) for name, pnp in pnps.items()}
+            calls["torch_solve"] = torch_solve
             times = {name: [] for name in calls}
             for _ in range(3):  # interleaved rounds
                 for name, fn in calls.items():
                     times[name] += timed(torch, fn, args.repeats // 3, args.warmup)
-            fit = solve()
-            row = {"bench": "pnp", "points": n, "hypotheses": hypotheses, "refine_iterations": 4, "launches": 13, "n_inliers": int(fit.n_inliers.item()),
-                   "valid": int(fit.valid.item())}
-            for name in calls:
-                row[f"{name}_us_median"] = round(1e6 * float(np.median(times[name])), 1)
-                row[f"{name}_us_min"] = round(1e6 * float(np.min(times[name])), 1)
-            rows.append(row)
+            for sample, pnp in pnps.items():
+                fit = solve(pnp)
+                row = {"bench": "pnp", "sample": sample, "points": n, "hypotheses": hypotheses, "refine_iterations": 4, "launches": 13,
+                       "n_inliers": int(fit.n_inliers.item()), "valid": int(fit.valid.item())}
+                for name, key in ((sample, "solve"), ("torch_solve", "torch_solve")):
+                    row[f"{key}_us_median"] = round(1e6 * float(np.median(times[name])), 1)
+                    row[f"{key}_us_min"] = round(1e6 * float(np.min(times[name])), 1)
+                rows.append(row)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     for row in rows:
         row["device"] = torch.cuda.get_device_name(0)
