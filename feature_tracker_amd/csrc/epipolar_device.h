@@ -1,8 +1,18 @@
-// epipolar_device.h — the device functions of the two-view kernels (two_view_kernels.hip): "finite", the hash, the
-// sampler, the null vector of an R x (R + 1) system by Gaussian elimination with complete pivoting (8 x 9 here, 11 x 12 in
-// pnp_kernels.hip), the two inlier tests, and the two models as compile-time traits of the hypothesis, score and select kernels.  Every float operation is stated in DESIGN.md 5.20 and 5.21 and
-// restated in tests/epipolar_ref.c and tests/two_view_ref.c; the build has no contraction (-ffp-contract=off) and correctly rounded
-// division and square root.
+// epipolar_device.h — the RANSAC stages that the point-set kernels share.  Each is stated here once:
+//
+//  * ep_finite: every kernel of two_view_kernels.hip, two_view_pose_kernels.hip, pnp_kernels.hip and landmark_table_kernels.hip.
+//  * ep_scan_participants(_if): two_view_scan_kernel, pose_scan_kernel, pnp_scan_kernel.
+//  * ep_mix32, ep_draw<S> (the hash and the sampler): two_view_hypothesis_kernel<Model>, pnp_hypothesis_kernel, pnp_p3p_hypothesis_kernel.
+//  * ep_null_vector_of<R> (Gaussian elimination with complete pivoting): two_view_hypothesis_kernel<Model> (8 x 9), pnp_hypothesis_kernel
+//    (11 x 12).
+//  * ep_store_hypothesis<F>: the tail of the three hypothesis kernels.
+//  * ep_score_walk<F>: two_view_score_kernel<Model>, pnp_score_kernel.
+//  * ep_key and its parts, ep_winner_keys<SLOTS>: two_view_select_kernel<SLOTS>, pnp_select_kernel.
+//  * FundamentalModel, HomographyModel with ep_inlier, tv_inlier: the two-view filters' models as compile-time traits.
+//
+// The pose geometry and the reductions of the kernels that follow a RANSAC are pose_device.h's.  Every float operation is stated in
+// DESIGN.md 5.20 and 5.21 and restated in tests/epipolar_ref.c and tests/two_view_ref.c; the build has no contraction
+// (-ffp-contract=off) and correctly rounded division and square root.
 #pragma once
 
 #include "two_view_plan.h"
@@ -122,49 +132,6 @@ __device__ __forceinline__ bool tv_inlier(const float (&g)[9], const float4 q, f
     const float ey = py - y2 * w;
     const float lhs = ex * ex + ey * ey, rhs = tn2 * (w * w);
     return w != 0.0f && ep_finite(lhs) && ep_finite(rhs) && lhs <= rhs;
-}
-
-// ---- what PnpRansac (pnp_kernels.hip) and the landmark table (landmark_table_kernels.hip) share ----
-
-// The inlier rule on the camera coordinates c of a landmark seen at the calibrated (x, y).
-__device__ __forceinline__ bool pnp_inlier(const float (&c)[3], const float x, const float y, const float ry, const float tn2) {
-    const float ex = c[0] - x * c[2];
-    const float ey = (c[1] - y * c[2]) * ry;
-    const float lhs = ex * ex + ey * ey, rhs = tn2 * (c[2] * c[2]);
-    return c[2] > 0.0f && ep_finite(lhs) && ep_finite(rhs) && lhs <= rhs;
-}
-
-// R_rc of a unit quaternion, row-major.
-__device__ __forceinline__ void pnp_rotation(const float (&q)[7], float (&R)[9]) {
-    const float w = q[0], x = q[1], y = q[2], z = q[3];
-    R[0] = 1.0f - 2.0f * (y * y + z * z), R[1] = 2.0f * (x * y - w * z), R[2] = 2.0f * (x * z + w * y);
-    R[3] = 2.0f * (x * y + w * z), R[4] = 1.0f - 2.0f * (x * x + z * z), R[5] = 2.0f * (y * z - w * x);
-    R[6] = 2.0f * (x * z - w * y), R[7] = 2.0f * (y * z + w * x), R[8] = 1.0f - 2.0f * (x * x + y * y);
-}
-
-// c = R_rc^T (X - p_rc)
-__device__ __forceinline__ void pnp_camera(const float (&R)[9], const float (&ps)[7], const float X, const float Y, const float Z, float (&c)[3]) {
-    const float d0 = X - ps[4], d1 = Y - ps[5], d2 = Z - ps[6];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        c[j] = (R[j] * d0 + R[3 + j] * d1) + R[6 + j] * d2;
-    }
-}
-
-// The two-ray depths z1, z2 of z2 b = z1 a + t by the 2 x 2 normal equations of the midpoint (TwoViewPose's cheirality test, DESIGN.md
-// 5.29; the landmark table's triangulation); aa, bb, ab: the rays' squared lengths and their product, for the caller's
-// parallax test.  true: both depths finite and > 0.
-__device__ __forceinline__ bool ep_two_ray_depths(const float (&a)[3], const float (&b)[3], const float (&t)[3], float &z1, float &z2, float &aa,
-                                                  float &bb, float &ab) {
-    aa = (a[0] * a[0] + a[1] * a[1]) + a[2] * a[2];
-    bb = (b[0] * b[0] + b[1] * b[1]) + b[2] * b[2];
-    ab = (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2];
-    const float at = (a[0] * t[0] + a[1] * t[1]) + a[2] * t[2];
-    const float bt = (b[0] * t[0] + b[1] * t[1]) + b[2] * t[2];
-    const float det = aa * bb - ab * ab;
-    z1 = (ab * bt - bb * at) / det;
-    z2 = (aa * bt - ab * at) / det;
-    return ep_finite(z1) && ep_finite(z2) && z1 > 0.0f && z2 > 0.0f;
 }
 
 // The models.  kSample: correspondences of a hypothesis; kSlot: the model's slot of TwoViewParams; fill: the rows that the k-th drawn
@@ -312,6 +279,115 @@ __device__ __forceinline__ bool ep_null_vector_of(float *const a, int *const per
 template <int L>
 __device__ __forceinline__ bool ep_null_vector(float *const a, int *const perm, float *const fv, bool ok, float (&f)[9]) {
     return ep_null_vector_of<8, L>(a, perm, fv, ok, f);
+}
+
+// The tail of a hypothesis kernel: hypothesis h's model of F floats (zero when not ok), its validity flag, and its count, 0 for the
+// score kernel to add to or -1 for "no hypothesis".
+template <int F>
+__device__ __forceinline__ void ep_store_hypothesis(float *const models, uint8_t *const valid, int32_t *const counts, const int h, const bool ok,
+                                                    const float (&f)[F]) {
+#pragma unroll
+    for (int i = 0; i < F; ++i) {
+        models[(size_t)h * F + i] = ok ? f[i] : 0.0f;
+    }
+    valid[h] = ok ? 1 : 0;
+    counts[h] = ok ? 0 : -1;
+}
+
+// The score walk of ONE workgroup of kEpipolarScoreTile threads on tile blockIdx.x of the m participants and group blockIdx.y of the
+// hypotheses.  stage(tid, j, live) puts participant j (zeros when not live: past m) at place tid of the caller's tile in LDS; each wave
+// then walks the tile for its kEpipolarScoreGroup / 4 hypotheses, whose model of F floats is wave-uniform; inlier(f, place) is the
+// caller's test of the staged participant under the model f.  Inliers are counted by ballot and popcount and reach memory as ONE integer
+// atomicAdd per workgroup and hypothesis.  With m < sample no hypothesis was formed and nothing is done.
+template <int F, class Stage, class Inlier>
+__device__ __forceinline__ void ep_score_walk(const int m, const int sample, const int hypotheses, const float *const models, const uint8_t *const valid,
+                                              int32_t *const counts, Stage stage, Inlier inlier) {
+    const int base = blockIdx.x * kEpipolarScoreTile;
+    if (m < sample || base >= m) {
+        return;  // the whole workgroup: the grid covers n
+    }
+    const int tid = threadIdx.x;
+    stage(tid, base + tid, base + tid < m);
+    __syncthreads();
+    const int wave = tid >> 6, lane = tid & 63;
+    constexpr int kPerWave = kEpipolarScoreGroup / (kEpipolarScoreTile / 64);
+    for (int i = 0; i < kPerWave; ++i) {
+        const int h = __builtin_amdgcn_readfirstlane((int)blockIdx.y * kEpipolarScoreGroup + wave * kPerWave + i);
+        if (h >= hypotheses) {
+            break;
+        }
+        if (!valid[h]) {
+            continue;
+        }
+        float f[F];
+#pragma unroll
+        for (int e = 0; e < F; ++e) {
+            f[e] = models[(size_t)h * F + e];
+        }
+        int32_t count = 0;
+#pragma unroll
+        for (int r = 0; r < kEpipolarScoreTile / 64; ++r) {
+            const int j = r * 64 + lane;
+            const bool in = base + j < m && inlier(f, j);
+            count += (int32_t)__popcll(__ballot(in));
+        }
+        if (lane == 0 && count > 0) {
+            atomicAdd(&counts[h], count);
+        }
+    }
+}
+
+// The winner key of hypothesis h with `count` inliers: (count + 1) << 32 | ~h, so that the maximum is the greatest count and, among equals,
+// the lowest h.  count = -1 (no hypothesis) gives a key whose upper half is zero, as the key 0 that nothing was folded into.
+__device__ __forceinline__ unsigned long long ep_key(const int32_t count, const int h) {
+    return ((unsigned long long)(uint32_t)(count + 1) << 32) | (unsigned long long)(~(uint32_t)h);
+}
+__device__ __forceinline__ bool ep_key_has_winner(const unsigned long long key) { return (key >> 32) != 0ull; }
+__device__ __forceinline__ int ep_key_hypothesis(const unsigned long long key) { return (int)(~(uint32_t)(key & 0xFFFFFFFFull)); }
+__device__ __forceinline__ int32_t ep_key_count(const unsigned long long key) { return (int32_t)(key >> 32) - 1; }
+
+// key[s] = the maximum of ep_key(count_of(s, h), h) over the hypotheses, for every slot s, by ONE workgroup of kEpipolarScanBlock threads:
+// a thread folds its per_thread consecutive hypotheses, then the workgroup takes the maximum in LDS (red).  Every thread returns with
+// every key.
+template <int SLOTS, class CountOf>
+__device__ __forceinline__ void ep_winner_keys(unsigned long long (&red)[SLOTS][kEpipolarScanBlock], const int per_thread, const int hypotheses,
+                                               unsigned long long (&key)[SLOTS], CountOf count_of) {
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int s = 0; s < SLOTS; ++s) {
+        key[s] = 0ull;
+    }
+    for (int i = 0; i < per_thread; ++i) {
+        const int h = tid * per_thread + i;
+        if (h < hypotheses) {
+#pragma unroll
+            for (int s = 0; s < SLOTS; ++s) {
+                const unsigned long long k = ep_key(count_of(s, h), h);
+                key[s] = k > key[s] ? k : key[s];
+            }
+        }
+    }
+#pragma unroll
+    for (int s = 0; s < SLOTS; ++s) {
+        red[s][tid] = key[s];
+    }
+    __syncthreads();
+    for (int step = kEpipolarScanBlock / 2; step > 0; step >>= 1) {
+        if (tid < step) {
+#pragma unroll
+            for (int s = 0; s < SLOTS; ++s) {
+                const unsigned long long other = red[s][tid + step];
+                if (other > red[s][tid]) {
+                    red[s][tid] = other;
+                }
+            }
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int s = 0; s < SLOTS; ++s) {
+        key[s] = red[s][0];
+    }
 }
 
 }  // namespace ftk

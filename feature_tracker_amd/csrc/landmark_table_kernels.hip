@@ -10,9 +10,10 @@
 //    anchor and this frame (it waits below the parallax floor; a failure anchors it again).  The counts are ballots and popcounts, ONE
 //    integer atomicAdd per workgroup and counter: every output is a pure function of the inputs.
 // Every float operation below is stated in DESIGN.md 5.31 and restated in tests/landmark_table_ref.c; the build has no contraction
-// (-ffp-contract=off) and correctly rounded division.  The inlier rule, the rotation of a quaternion and the camera coordinates are
-// PnpRansac's, the two-ray depths TwoViewPose's (epipolar_device.h).
-#include "epipolar_device.h"
+// (-ffp-contract=off) and correctly rounded division.  The inlier rule, the rotation of a quaternion and the camera coordinates
+// (pnp_inlier, pnp_rotation, pnp_camera), the rays and their depths (pose_ray, ep_two_ray_depths) and the end kernel's four counts
+// (pose_block_counts_add) are pose_device.h's, shared with PnpRansac and TwoViewPose.
+#include "pose_device.h"
 #include "landmark_table_plan.h"
 
 namespace ftk {
@@ -35,8 +36,9 @@ __device__ __forceinline__ int landmark_triangulate(const LandmarkParams &p, con
     const float xc = (uc - p.cx) / p.fx, yc = (vc - p.cy) / p.fy;
     float Ra[9];
     pnp_rotation(pa, Ra);
-    const float a[3] = {(Ra[0] * xa + Ra[1] * ya) + Ra[2], (Ra[3] * xa + Ra[4] * ya) + Ra[5], (Ra[6] * xa + Ra[7] * ya) + Ra[8]};
-    const float b[3] = {(Rc[0] * xc + Rc[1] * yc) + Rc[2], (Rc[3] * xc + Rc[4] * yc) + Rc[5], (Rc[6] * xc + Rc[7] * yc) + Rc[8]};
+    float a[3], b[3];
+    pose_ray(Ra, xa, ya, a);
+    pose_ray(Rc, xc, yc, b);
     const float t[3] = {pa[4] - pc[4], pa[5] - pc[5], pa[6] - pc[6]};
     float z1, z2, aa, bb, ab;
     const bool front = ep_two_ray_depths(a, b, t, z1, z2, aa, bb, ab);
@@ -89,7 +91,7 @@ __global__ void __launch_bounds__(kLandmarkBlock) landmark_begin_kernel(const La
 __global__ void __launch_bounds__(kLandmarkBlock) landmark_end_kernel(const LandmarkParams p) {
     constexpr int kWaves = kLandmarkBlock / 64;
     __shared__ int32_t counts[4][kWaves];
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int tid = threadIdx.x;
     const int s = blockIdx.x * kLandmarkBlock + tid;
     const bool ok = p.valid_in[0] == 1 && (p.model_in == nullptr || p.model_in[0] == 0);
     float pc[7];
@@ -150,24 +152,7 @@ __global__ void __launch_bounds__(kLandmarkBlock) landmark_end_kernel(const Land
         }
     }
     const bool flags[4] = {is_new, anchored, holds, dropped};
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const int32_t count = (int32_t)__popcll(__ballot(flags[c]));
-        if (lane == 0) {
-            counts[c][wave] = count;
-        }
-    }
-    __syncthreads();
-    if (tid < 4) {
-        int32_t sum = 0;
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w) {
-            sum += counts[tid][w];
-        }
-        if (sum > 0) {
-            atomicAdd(&p.counters[kLandmarkNew + tid], sum);  // kLandmarkNew, kLandmarkAnchored, kLandmarkCount, kLandmarkDropped are consecutive
-        }
-    }
+    pose_block_counts_add(counts, flags, &p.counters[kLandmarkNew]);  // kLandmarkNew, kLandmarkAnchored, kLandmarkCount, kLandmarkDropped are consecutive
 }
 
 }  // namespace

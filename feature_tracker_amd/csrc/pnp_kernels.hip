@@ -2,28 +2,31 @@
 // six-point DLT and a Gauss-Newton refit of the reprojection error on the inliers, everything on the device, 5 + 2 refine_iterations
 // launches of fixed shape.
 //
-//  * pnp_scan_kernel: the filters' scan (epipolar_device.h: ONE workgroup lists the participants in ascending index order) with this
-//    stage's test of a participant: status TRACKED, five finite numbers, a landmark other than (0, 0, 0).  It stores the calibrated pixel
-//    and the landmark.
+//  * pnp_scan_kernel: the filters' scan (epipolar_device.h's ep_scan_participants_if: ONE workgroup lists the participants in ascending
+//    index order) with this stage's test of a participant: status TRACKED, five finite numbers, a landmark other than (0, 0, 0).  It
+//    stores the calibrated pixel and the landmark.
 //  * pnp_hypothesis_kernel: one lane = one hypothesis, as two_view_hypothesis_kernel.  The six landmarks are conditioned from the sample
 //    alone; the 11 x 12 DLT system lives in LDS, [entry][lane] (156 floats per lane, 39 KB per workgroup: complete pivoting indexes rows
 //    and columns at run time), and the elimination is epipolar_device.h's ep_null_vector_of<11>, the two filters' at another size.
-//  * pnp_p3p_hypothesis_kernel: the "p3p" sampler's kernel in the place of pnp_hypothesis_kernel: four participants, Grunert's
-//    quartic by Ferrari's factorisation on the first three, the fourth chooses among the solutions; registers alone, no LDS.
-//  * pnp_score_kernel: two_view_score_kernel's tiling (a tile of 256 participants in LDS, 4 hypotheses per wave, ballot and popcount, ONE
-//    integer atomicAdd per workgroup and hypothesis) on a participant record of five floats and a model of twelve, which is why it is a
-//    kernel of its own and no third Model of that family: the family's record is one float4 and its models are nine floats.
-//  * pnp_select_kernel: ONE workgroup takes the maximum of (count + 1) << 32 | ~h; thread 0 turns the winner's [A | b] into a pose: the
-//    nearest rotation by TwoViewPose's cyclic Jacobi on A^T A (its statements, run by one thread on LDS arrays: jacobi_eigen<3> itself
-//    needs the solve kernel's wave), Shepperd's quaternion.
-//  * pnp_sums_kernel / pnp_step_kernel, once per refit step: a tile of 256 participants reduces its 27 terms by pose_moment_kernel's tree
-//    (the first step over the inliers of the model that won, the later ones over the current pose's);
-//    one wave adds the tile totals in tile order, solves the 6 x 6 system by an LDL^T and moves the pose, or ends the refit.
-//  * pnp_finish_kernel: a thread per participant applies the status rule under the final pose; block 0 writes the outputs.
+//  * pnp_p3p_hypothesis_kernel: the "p3p" sampler's kernel in the place of pnp_hypothesis_kernel: four participants,
+//    Grunert's quartic by Ferrari's factorisation on the first three, the fourth chooses among the solutions; registers alone, no LDS.
+//    Both hypothesis kernels begin with pnp_draw_sample and end with epipolar_device.h's ep_store_hypothesis.
+//  * pnp_score_kernel: epipolar_device.h's ep_score_walk (a tile of 256 participants in LDS, 4 hypotheses per wave, ballot and popcount,
+//    ONE integer atomicAdd per workgroup and hypothesis) on a participant record of five floats and a model of twelve, which is why it is
+//    a kernel of its own and no third Model of the two-view family: the family's record is one float4 and its models are nine floats.
+//  * pnp_select_kernel: ONE workgroup takes the winner key (epipolar_device.h's ep_winner_keys); thread 0 turns the winner's [A | b] into
+//    a pose: the nearest rotation by pose_device.h's jacobi_eigen<3, Jacobi::Thread> on A^T A (one thread on LDS arrays: the other
+//    threads have returned), the quaternion by pose_quaternion_of_transpose.
+//  * pnp_sums_kernel / pnp_step_kernel, once per refit step: a tile of 256 participants reduces its 27 terms by pose_device.h's
+//    pose_tree_sum (the first step over the inliers of the model that won, the later ones over the current pose's) and counts them by
+//    pose_block_counts; one wave adds the tile totals in tile order (pose_tile_total), solves the 6 x 6 system by an LDL^T and moves the
+//    pose, or ends the refit.
+//  * pnp_finish_kernel: a thread per participant applies the status rule under the final pose (pose_block_counts_add counts the
+//    inliers); block 0 writes the outputs.
 // Every float operation below is stated in DESIGN.md 5.30 and restated in tests/pnp_ref.c; the build has no contraction (-ffp-contract=off)
 // and correctly rounded division and square root.
-#include "epipolar_device.h"
 #include "pnp_plan.h"
+#include "pose_device.h"
 
 namespace ftk {
 namespace {
@@ -51,6 +54,21 @@ __global__ void __launch_bounds__(kEpipolarScanBlock) pnp_scan_kernel(const PnpP
         });
 }
 
+// The head of a hypothesis kernel: hypothesis h's draw of S participants and their (x, y, X, Y, Z), zeros when the draw failed.
+template <int S>
+__device__ __forceinline__ bool pnp_draw_sample(const PnpParams &p, const int h, uint32_t (&idx)[S], float (&x)[S], float (&y)[S], float (&X)[S],
+                                                float (&Y)[S], float (&Z)[S]) {
+    const uint32_t m = (uint32_t)max(min(p.m[0], p.n), 0);
+    const bool ok = ep_draw<S>(p.seed, (uint32_t)h, m, idx);
+#pragma unroll
+    for (int k = 0; k < S; ++k) {
+        const float4 q = ok ? p.points[idx[k]] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        x[k] = q.x, y[k] = q.y, X[k] = q.z, Y[k] = q.w;
+        Z[k] = ok ? p.depth[idx[k]] : 0.0f;
+    }
+    return ok;
+}
+
 __global__ void __launch_bounds__(kEpipolarHypBlock) pnp_hypothesis_kernel(const PnpParams p) {
     __shared__ float lds[kPnpHypLdsFloats * kEpipolarHypBlock];
     const int lane = threadIdx.x;
@@ -62,16 +80,9 @@ __global__ void __launch_bounds__(kEpipolarHypBlock) pnp_hypothesis_kernel(const
     float *const a = lds + lane;                                                // a[(r * 12 + c) * 64]
     int *const perm = reinterpret_cast<int *>(lds + kPnpRows * C * L) + lane;   // perm[c * 64]
     float *const fv = lds + (kPnpRows * C + C) * L + lane;                      // fv[c * 64]
-    const uint32_t m = (uint32_t)max(min(p.m[0], p.n), 0);
     uint32_t idx[kPnpSample];
-    bool ok = ep_draw<kPnpSample>(p.seed, (uint32_t)h, m, idx);
     float x[kPnpSample], y[kPnpSample], X[kPnpSample], Y[kPnpSample], Z[kPnpSample];
-#pragma unroll
-    for (int k = 0; k < kPnpSample; ++k) {
-        const float4 q = ok ? p.points[idx[k]] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        x[k] = q.x, y[k] = q.y, X[k] = q.z, Y[k] = q.w;
-        Z[k] = ok ? p.depth[idx[k]] : 0.0f;
-    }
+    bool ok = pnp_draw_sample(p, h, idx, x, y, X, Y, Z);
     // conditioning from the sample alone: the mean in index order, the mean absolute deviation over the 18 coordinates
     const float mx = (((((X[0] + X[1]) + X[2]) + X[3]) + X[4]) + X[5]) / 6.0f;
     const float my = (((((Y[0] + Y[1]) + Y[2]) + Y[3]) + Y[4]) + Y[5]) / 6.0f;
@@ -153,12 +164,7 @@ __global__ void __launch_bounds__(kEpipolarHypBlock) pnp_hypothesis_kernel(const
             ok = ok && ep_finite(P[i]);
         }
     }
-#pragma unroll
-    for (int i = 0; i < 12; ++i) {
-        p.models[(size_t)h * 12 + i] = ok ? P[i] : 0.0f;
-    }
-    p.valid[h] = ok ? 1 : 0;
-    p.counts[h] = ok ? 0 : -1;
+    ep_store_hypothesis(p.models, p.valid, p.counts, h, ok, P);
 }
 
 // ---- the "p3p" sampler (tests/pnp_p3p_ref.c states every operation below in the same order) ----
@@ -340,16 +346,9 @@ __global__ void __launch_bounds__(kEpipolarHypBlock) pnp_p3p_hypothesis_kernel(c
     if (h >= p.hypotheses) {
         return;
     }
-    const uint32_t m = (uint32_t)max(min(p.m[0], p.n), 0);
     uint32_t idx[kP3pSample];
-    bool ok = ep_draw<kP3pSample>(p.seed, (uint32_t)h, m, idx);
     float x[kP3pSample], y[kP3pSample], X[kP3pSample], Y[kP3pSample], Z[kP3pSample];
-#pragma unroll
-    for (int k = 0; k < kP3pSample; ++k) {
-        const float4 q = ok ? p.points[idx[k]] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        x[k] = q.x, y[k] = q.y, X[k] = q.z, Y[k] = q.w;
-        Z[k] = ok ? p.depth[idx[k]] : 0.0f;
-    }
+    bool ok = pnp_draw_sample(p, h, idx, x, y, X, Y, Z);
     P3pSetup s;
     ok = p3p_setup(x, y, X, Y, Z, s) && ok;
     float P[12];
@@ -385,116 +384,28 @@ __global__ void __launch_bounds__(kEpipolarHypBlock) pnp_p3p_hypothesis_kernel(c
             best = err, have = true;
         }
     }
-#pragma unroll
-    for (int i = 0; i < 12; ++i) {
-        p.models[(size_t)h * 12 + i] = have ? P[i] : 0.0f;
-    }
-    p.valid[h] = have ? 1 : 0;
-    p.counts[h] = have ? 0 : -1;
+    ep_store_hypothesis(p.models, p.valid, p.counts, h, have, P);
 }
 
 __global__ void __launch_bounds__(kEpipolarScoreTile) pnp_score_kernel(const PnpParams p) {
     __shared__ float4 tile[kEpipolarScoreTile];
     __shared__ float tile_z[kEpipolarScoreTile];
-    const int m = min(p.m[0], p.n);
-    const int base = blockIdx.x * kEpipolarScoreTile;
-    if (m < p.sample || base >= m) {
-        return;  // the whole workgroup: the grid covers n
-    }
-    const int tid = threadIdx.x;
-    tile[tid] = base + tid < m ? p.points[base + tid] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    tile_z[tid] = base + tid < m ? p.depth[base + tid] : 0.0f;
-    __syncthreads();
-    const int wave = tid >> 6, lane = tid & 63;
-    constexpr int kPerWave = kEpipolarScoreGroup / (kEpipolarScoreTile / 64);
-    for (int i = 0; i < kPerWave; ++i) {
-        const int h = __builtin_amdgcn_readfirstlane((int)blockIdx.y * kEpipolarScoreGroup + wave * kPerWave + i);
-        if (h >= p.hypotheses) {
-            break;
-        }
-        if (!p.valid[h]) {
-            continue;
-        }
-        float P[12];
-#pragma unroll
-        for (int e = 0; e < 12; ++e) {
-            P[e] = p.models[(size_t)h * 12 + e];
-        }
-        int32_t count = 0;
-#pragma unroll
-        for (int r = 0; r < kEpipolarScoreTile / 64; ++r) {
-            const int j = r * 64 + lane;
-            const float4 q = tile[j];
-            const float Z = tile_z[j];
+    ep_score_walk<12>(
+        min(p.m[0], p.n), p.sample, p.hypotheses, p.models, p.valid, p.counts,
+        [&](const int at, const int j, const bool live) {
+            tile[at] = live ? p.points[j] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            tile_z[at] = live ? p.depth[j] : 0.0f;
+        },
+        [&](const float (&P)[12], const int at) {
+            const float4 q = tile[at];
+            const float Z = tile_z[at];
             float c[3];
 #pragma unroll
             for (int e = 0; e < 3; ++e) {
                 c[e] = ((P[e * 4] * q.z + P[e * 4 + 1] * q.w) + P[e * 4 + 2] * Z) + P[e * 4 + 3];
             }
-            const bool in = base + j < m && pnp_inlier(c, q.x, q.y, p.ry, p.tn2);
-            count += (int32_t)__popcll(__ballot(in));
-        }
-        if (lane == 0 && count > 0) {
-            atomicAdd(&p.counts[h], count);
-        }
-    }
-}
-
-// TwoViewPose's cyclic Jacobi (two_view_pose_kernels.hip's jacobi_eigen) at N = 3, every statement in its order, run by ONE thread on
-// arrays in LDS (run-time indices: no scratch).
-__device__ __forceinline__ void pnp_jacobi3(float *const a, float *const v) {
-    constexpr int N = 3;
-    for (int idx = 0; idx < N * N; ++idx) {
-        v[idx] = idx / N == idx % N ? 1.0f : 0.0f;
-    }
-    for (int sweep = 0; sweep < kPoseJacobiSweeps; ++sweep) {
-        for (int p = 0; p < N - 1; ++p) {
-            for (int q = p + 1; q < N; ++q) {
-                const float apq = a[p * N + q], app = a[p * N + p], aqq = a[q * N + q];
-                if (apq == 0.0f) {
-                    continue;
-                }
-                const float g = 100.0f * fabsf(apq);
-                if (fabsf(app) + g == fabsf(app) && fabsf(aqq) + g == fabsf(aqq)) {  // negligible: set to zero, no rotation
-                    a[p * N + q] = 0.0f;
-                    a[q * N + p] = 0.0f;
-                    continue;
-                }
-                const float h = aqq - app;
-                float t;
-                if (fabsf(h) + g == fabsf(h)) {
-                    t = apq / h;
-                } else {
-                    const float theta = h / (2.0f * apq);
-                    t = 1.0f / (fabsf(theta) + sqrtf(theta * theta + 1.0f));
-                    if (theta < 0.0f) {
-                        t = -t;
-                    }
-                }
-                const float c = 1.0f / sqrtf(t * t + 1.0f);
-                const float s = t * c;
-                const float tau = s / (1.0f + c);
-                const float hh = t * apq;
-                a[p * N + p] = app - hh;
-                a[q * N + q] = aqq + hh;
-                a[p * N + q] = 0.0f;
-                a[q * N + p] = 0.0f;
-                for (int r = 0; r < N; ++r) {
-                    if (r != p && r != q) {
-                        const float x = a[r * N + p], y = a[r * N + q];
-                        const float xn = x - s * (y + x * tau), yn = y + s * (x - y * tau);
-                        a[r * N + p] = xn;
-                        a[p * N + r] = xn;
-                        a[r * N + q] = yn;
-                        a[q * N + r] = yn;
-                    }
-                    const float x = v[r * N + p], y = v[r * N + q];
-                    v[r * N + p] = x - s * (y + x * tau);
-                    v[r * N + q] = y + s * (x - y * tau);
-                }
-            }
-        }
-    }
+            return pnp_inlier(c, q.x, q.y, p.ry, p.tn2);
+        });
 }
 
 // The winner's P = [A | b] as a pose (q_rc, p_rc): R the nearest rotation to A, t = b / s with s the mean singular value; R_rc = R^T,
@@ -515,7 +426,7 @@ __device__ __forceinline__ bool pnp_pose_of_model(const float (&P)[12], float *c
             M[i * 3 + j] = (A[i] * A[j] + A[3 + i] * A[3 + j]) + A[6 + i] * A[6 + j];
         }
     }
-    pnp_jacobi3(M, V);
+    jacobi_eigen<3, Jacobi::Thread>(M, V, 0);
     const float l0 = M[0], l1 = M[4], l2 = M[8];
     if (!(l0 > 0.0f && l1 > 0.0f && l2 > 0.0f)) {
         return false;
@@ -559,28 +470,7 @@ __device__ __forceinline__ bool pnp_pose_of_model(const float (&P)[12], float *c
     for (int j = 0; j < 3; ++j) {
         ps[4 + j] = -((R[j] * t0 + R[3 + j] * t1) + R[6 + j] * t2);
     }
-    // Shepperd on R_rc = R^T: m(i, j) = R[j * 3 + i], as pose_finish_kernel
-    const float m00 = R[0], m01 = R[3], m02 = R[6], m10 = R[1], m11 = R[4], m12 = R[7], m20 = R[2], m21 = R[5], m22 = R[8];
-    const float tr = (m00 + m11) + m22;
-    float qw, qx, qy, qz;
-    if (tr > 0.0f) {
-        const float s = sqrtf(tr + 1.0f) * 2.0f;
-        qw = 0.25f * s, qx = (m21 - m12) / s, qy = (m02 - m20) / s, qz = (m10 - m01) / s;
-    } else if (m00 > m11 && m00 > m22) {
-        const float s = sqrtf(((1.0f + m00) - m11) - m22) * 2.0f;
-        qw = (m21 - m12) / s, qx = 0.25f * s, qy = (m01 + m10) / s, qz = (m02 + m20) / s;
-    } else if (m11 > m22) {
-        const float s = sqrtf(((1.0f + m11) - m00) - m22) * 2.0f;
-        qw = (m02 - m20) / s, qx = (m01 + m10) / s, qy = 0.25f * s, qz = (m12 + m21) / s;
-    } else {
-        const float s = sqrtf(((1.0f + m22) - m00) - m11) * 2.0f;
-        qw = (m10 - m01) / s, qx = (m02 + m20) / s, qy = (m12 + m21) / s, qz = 0.25f * s;
-    }
-    if (qw < 0.0f) {
-        qw = -qw, qx = -qx, qy = -qy, qz = -qz;
-    }
-    const float qn = sqrtf(((qw * qw + qx * qx) + qy * qy) + qz * qz);
-    ps[0] = qw / qn, ps[1] = qx / qn, ps[2] = qy / qn, ps[3] = qz / qn;
+    pose_quaternion_of_transpose(R, ps);  // R_rc = R^T
     bool ok = true;
 #pragma unroll
     for (int e = 0; e < 7; ++e) {
@@ -590,35 +480,17 @@ __device__ __forceinline__ bool pnp_pose_of_model(const float (&P)[12], float *c
 }
 
 __global__ void __launch_bounds__(kEpipolarScanBlock) pnp_select_kernel(const PnpParams p) {
-    __shared__ unsigned long long red[kEpipolarScanBlock];
+    __shared__ unsigned long long red[1][kEpipolarScanBlock];
     __shared__ float M[9], V[9];
-    const int tid = threadIdx.x;
-    unsigned long long key = 0ull;
-    for (int i = 0; i < p.select_per_thread; ++i) {
-        const int h = tid * p.select_per_thread + i;
-        if (h < p.hypotheses) {
-            const unsigned long long k = ((unsigned long long)(uint32_t)(p.counts[h] + 1) << 32) | (unsigned long long)(~(uint32_t)h);
-            key = k > key ? k : key;
-        }
-    }
-    red[tid] = key;
-    __syncthreads();
-    for (int step = kEpipolarScanBlock / 2; step > 0; step >>= 1) {
-        if (tid < step) {
-            const unsigned long long other = red[tid + step];
-            if (other > red[tid]) {
-                red[tid] = other;
-            }
-        }
-        __syncthreads();
-    }
-    if (tid != 0) {
+    unsigned long long best[1];
+    ep_winner_keys<1>(red, p.select_per_thread, p.hypotheses, best, [&](const int, const int h) { return p.counts[h]; });
+    if (threadIdx.x != 0) {
         return;
     }
-    key = red[0];
+    const unsigned long long key = best[0];
     const int m = min(p.m[0], p.n);
-    bool ok = m >= p.sample && (key >> 32) != 0ull;  // (with fewer participants than a sample no hypothesis was formed)
-    const int h = ok ? (int)(~(uint32_t)(key & 0xFFFFFFFFull)) : -1;
+    bool ok = m >= p.sample && ep_key_has_winner(key);  // (with fewer participants than a sample no hypothesis was formed)
+    const int h = ok ? ep_key_hypothesis(key) : -1;
     float ps[7] = {1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
     if (ok) {
         float P[12];
@@ -642,13 +514,13 @@ __global__ void __launch_bounds__(kEpipolarScanBlock) pnp_select_kernel(const Pn
 
 __global__ void __launch_bounds__(kPoseTile) pnp_sums_kernel(const PnpParams p) {
     __shared__ float tree[kPnpSums][kPoseTile];
-    __shared__ int32_t counts[kPoseTile / 64];
+    __shared__ int32_t counts[1][kPoseTile / 64];
     const int m = min(p.m[0], p.n);
     const int base = blockIdx.x * kPoseTile;
     if (p.flags[kFlagOk] == 0 || p.flags[kFlagDone] != 0 || base >= m) {
         return;  // the whole workgroup: the grid covers n, the step kernel reads the tiles below M alone
     }
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int tid = threadIdx.x;
     float ps[7], R[9];
 #pragma unroll
     for (int e = 0; e < 7; ++e) {
@@ -702,29 +574,11 @@ __global__ void __launch_bounds__(kPoseTile) pnp_sums_kernel(const PnpParams p) 
     for (int e = 0; e < kPnpSums; ++e) {
         tree[e][tid] = term[e];
     }
-    const int32_t count = (int32_t)__popcll(__ballot(in));
-    if (lane == 0) {
-        counts[wave] = count;
-    }
-    __syncthreads();
-    for (int stride = kPoseTile / 2, shift = 7; stride >= 1; stride >>= 1, --shift) {
-        const int jobs = kPnpSums * stride;
-        for (int job = tid; job < jobs; job += kPoseTile) {
-            const int e = job >> shift, j = job & (stride - 1);
-            tree[e][j] = tree[e][j] + tree[e][j + stride];
-        }
-        __syncthreads();
-    }
+    const bool flags[1] = {in};
+    pose_block_counts(counts, flags, [&](const int, const int32_t sum) { p.tile_counts[blockIdx.x] = sum; });  // (its barrier is the tree's)
+    pose_tree_sum(tree, tid);
     if (tid < kPnpSums) {
         p.totals[(size_t)blockIdx.x * kPnpSums + tid] = tree[tid][0];
-    }
-    if (tid == 0) {
-        int32_t sum = 0;
-#pragma unroll
-        for (int w = 0; w < kPoseTile / 64; ++w) {
-            sum += counts[w];
-        }
-        p.tile_counts[blockIdx.x] = sum;
     }
 }
 
@@ -737,12 +591,8 @@ __global__ void __launch_bounds__(kPoseSolveBlock) pnp_step_kernel(const PnpPara
     }
     const int m = min(p.m[0], p.n);
     const int tiles = (m + kPoseTile - 1) / kPoseTile;
-    if (tid < kPnpSums) {  // the tile totals in ascending tile order from +0
-        float acc = 0.0f;
-        for (int t = 0; t < tiles; ++t) {
-            acc = acc + p.totals[(size_t)t * kPnpSums + tid];
-        }
-        sums[tid] = acc;
+    if (tid < kPnpSums) {
+        sums[tid] = pose_tile_total(p.totals, tiles, kPnpSums, tid);
     }
     __syncthreads();
     if (tid != 0) {
@@ -825,8 +675,8 @@ __global__ void __launch_bounds__(kPoseSolveBlock) pnp_step_kernel(const PnpPara
 }
 
 __global__ void __launch_bounds__(kPoseTile) pnp_finish_kernel(const PnpParams p) {
-    __shared__ int32_t kept[kPoseTile / 64];
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    __shared__ int32_t kept[1][kPoseTile / 64];
+    const int tid = threadIdx.x;
     const int j = blockIdx.x * kPoseTile + tid;
     const int m = min(p.m[0], p.n);
     const bool ok = p.flags[kFlagOk] != 0;
@@ -860,21 +710,8 @@ __global__ void __launch_bounds__(kPoseTile) pnp_finish_kernel(const PnpParams p
             }
         }
     }
-    const int32_t count = (int32_t)__popcll(__ballot(keep));
-    if (lane == 0) {
-        kept[wave] = count;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        int32_t sum = 0;
-#pragma unroll
-        for (int w = 0; w < kPoseTile / 64; ++w) {
-            sum += kept[w];
-        }
-        if (sum > 0) {
-            atomicAdd(&p.n_inliers[0], sum);
-        }
-    }
+    const bool flags[1] = {keep};
+    pose_block_counts_add(kept, flags, p.n_inliers);
 }
 
 }  // namespace

@@ -9,13 +9,13 @@
 //  * two_view_hypothesis_kernel<Model>: one lane = one hypothesis.  The sampler is integer logic; the 8 x 9 constraint matrix lives in LDS,
 //    [entry][lane], because complete pivoting indexes rows and columns at run time and a register array indexed so goes to scratch;
 //    [entry][lane] makes every access of a wave one conflict-free row of 64 words.  The elimination, the null vector and its scaling are
-//    epipolar_device.h's ep_null_vector for both models.
-//  * two_view_score_kernel<Model>: a workgroup stages a tile of 256 participants in LDS and each of its waves walks the tile for 4
-//    hypotheses, whose model is wave-uniform; inliers are counted by ballot and popcount and reach memory as ONE integer atomicAdd per
-//    workgroup and hypothesis.  Integer sums: no result depends on the order.
-//  * two_view_select_kernel<SLOTS>: ONE workgroup takes the maximum of (count + 1) << 32 | ~h of each slot, denormalises the winner and
-//    rewrites the statuses of the participants that are not its inliers.  With two slots it first applies the rule on the two integer
-//    counts, and the statuses follow the CHOSEN model.
+//    epipolar_device.h's ep_null_vector for both models, the tail its ep_store_hypothesis.
+//  * two_view_score_kernel<Model>: epipolar_device.h's ep_score_walk (a workgroup stages a tile of 256 participants in LDS, each of its
+//    waves walks the tile for 4 hypotheses, ONE integer atomicAdd per workgroup and hypothesis) on a record of one float4 and a model of
+//    nine floats.  Integer sums: no result depends on the order.
+//  * two_view_select_kernel<SLOTS>: ONE workgroup takes each slot's winner key (epipolar_device.h's ep_winner_keys), denormalises the
+//    winner and rewrites the statuses of the participants that are not its inliers.  With two slots it first applies the rule on the two
+//    integer counts, and the statuses follow the CHOSEN model.
 // Every float operation below is stated in DESIGN.md 5.20 and 5.21 and restated in tests/epipolar_ref.c and tests/two_view_ref.c; the build
 // has no contraction (-ffp-contract=off) and correctly rounded division and square root.
 #include "epipolar_device.h"
@@ -61,81 +61,20 @@ __global__ void __launch_bounds__(kEpipolarHypBlock) two_view_hypothesis_kernel(
     float f[9];
     ok = ep_null_vector<L>(a, perm, fv, ok, f);
     const TwoViewSlot out = p.slot[Model::kSlot];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) {
-        out.models[(size_t)h * 9 + i] = ok ? f[i] : 0.0f;
-    }
-    out.valid[h] = ok ? 1 : 0;
-    out.counts[h] = ok ? 0 : -1;
+    ep_store_hypothesis(out.models, out.valid, out.counts, h, ok, f);
 }
 
 template <class Model>
 __global__ void __launch_bounds__(kEpipolarScoreTile) two_view_score_kernel(const TwoViewParams p) {
     __shared__ float4 tile[kEpipolarScoreTile];
-    const int m = min(p.m[0], p.n);
-    const int base = blockIdx.x * kEpipolarScoreTile;
-    if (m < Model::kSample || base >= m) {
-        return;  // the whole workgroup: the grid covers n
-    }
-    const int tid = threadIdx.x;
-    tile[tid] = base + tid < m ? p.points[base + tid] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    __syncthreads();
     const TwoViewSlot slot = p.slot[Model::kSlot];
-    const int wave = tid >> 6, lane = tid & 63;
-    constexpr int kPerWave = kEpipolarScoreGroup / (kEpipolarScoreTile / 64);
-    for (int i = 0; i < kPerWave; ++i) {
-        const int h = __builtin_amdgcn_readfirstlane((int)blockIdx.y * kEpipolarScoreGroup + wave * kPerWave + i);
-        if (h >= p.hypotheses) {
-            break;
-        }
-        if (!slot.valid[h]) {
-            continue;
-        }
-        float f[9];
-#pragma unroll
-        for (int e = 0; e < 9; ++e) {
-            f[e] = slot.models[(size_t)h * 9 + e];
-        }
-        int32_t count = 0;
-#pragma unroll
-        for (int r = 0; r < kEpipolarScoreTile / 64; ++r) {
-            const int j = r * 64 + lane;
-            const bool in = base + j < m && Model::inlier(f, tile[j], p.tn2);
-            count += (int32_t)__popcll(__ballot(in));
-        }
-        if (lane == 0 && count > 0) {
-            atomicAdd(&slot.counts[h], count);
-        }
-    }
+    ep_score_walk<9>(
+        min(p.m[0], p.n), Model::kSample, p.hypotheses, slot.models, slot.valid, slot.counts,
+        [&](const int at, const int j, const bool live) { tile[at] = live ? p.points[j] : make_float4(0.0f, 0.0f, 0.0f, 0.0f); },
+        [&](const float (&f)[9], const int at) { return Model::inlier(f, tile[at], p.tn2); });
 }
 
-// The select kernel's parts, each stated once for its two instances.
-
-// Every slot's maximum of (count + 1) << 32 | ~h over the workgroup: key[s] enters as this thread's maximum and leaves as the workgroup's.
-template <int SLOTS>
-__device__ __forceinline__ void sel_reduce(unsigned long long (&red)[SLOTS][kEpipolarScanBlock], unsigned long long (&key)[SLOTS], const int tid) {
-#pragma unroll
-    for (int s = 0; s < SLOTS; ++s) {
-        red[s][tid] = key[s];
-    }
-    __syncthreads();
-    for (int step = kEpipolarScanBlock / 2; step > 0; step >>= 1) {
-        if (tid < step) {
-#pragma unroll
-            for (int s = 0; s < SLOTS; ++s) {
-                const unsigned long long other = red[s][tid + step];
-                if (other > red[s][tid]) {
-                    red[s][tid] = other;
-                }
-            }
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int s = 0; s < SLOTS; ++s) {
-        key[s] = red[s][0];
-    }
-}
+// The select kernel's parts, each stated once for its two instances (the winner keys: epipolar_device.h's ep_winner_keys).
 
 // G = M T, T = [s 0 tx; 0 s ty; 0 0 1]: the first half of either denormalisation.
 __device__ __forceinline__ void sel_times_T(const float (&f)[9], const float s, const float tx, const float ty, float (&g)[9]) {
@@ -191,32 +130,20 @@ template <int SLOTS>
 __global__ void __launch_bounds__(kEpipolarScanBlock) two_view_select_kernel(const TwoViewParams p) {
     __shared__ unsigned long long red[SLOTS][kEpipolarScanBlock];
     const int tid = threadIdx.x;
-    unsigned long long key[SLOTS] = {};
-    for (int i = 0; i < p.select_per_thread; ++i) {
-        const int h = tid * p.select_per_thread + i;
-        if (h < p.hypotheses) {
-#pragma unroll
-            for (int s = 0; s < SLOTS; ++s) {
-                bool ran = true;  // one slot: the entry has no mode
-                if constexpr (SLOTS > 1) {
-                    ran = p.run[s] != 0;
-                }
-                if (ran) {
-                    const unsigned long long k = ((unsigned long long)(uint32_t)(p.slot[s].counts[h] + 1) << 32) | (unsigned long long)(~(uint32_t)h);
-                    key[s] = k > key[s] ? k : key[s];
-                } else {  // the slot of a model that did not run: no hypothesis
-                    p.slot[s].counts[h] = -1;
-                    for (int e = 0; e < 9; ++e) {
-                        p.slot[s].models[(size_t)h * 9 + e] = 0.0f;
-                    }
-                }
+    unsigned long long key[SLOTS];
+    ep_winner_keys<SLOTS>(red, p.select_per_thread, p.hypotheses, key, [&](const int s, const int h) -> int32_t {
+        if (SLOTS > 1 && p.run[s] == 0) {  // the slot of a model that did not run: no hypothesis (one slot: the entry has no mode)
+            p.slot[s].counts[h] = -1;
+            for (int e = 0; e < 9; ++e) {
+                p.slot[s].models[(size_t)h * 9 + e] = 0.0f;
             }
+            return -1;
         }
-    }
-    sel_reduce<SLOTS>(red, key, tid);
+        return p.slot[s].counts[h];
+    });
     const int m = min(p.m[0], p.n);
     if constexpr (SLOTS == 1) {
-        if ((key[0] >> 32) == 0ull) {  // no valid hypothesis (with M < 8: none was formed)
+        if (!ep_key_has_winner(key[0])) {  // no valid hypothesis (with M < 8: none was formed)
             if (tid == 0) {
                 p.best[0] = -1;
                 p.n_inliers[0] = m;
@@ -226,7 +153,7 @@ __global__ void __launch_bounds__(kEpipolarScanBlock) two_view_select_kernel(con
             }
             return;
         }
-        const int h = (int)(~(uint32_t)(key[0] & 0xFFFFFFFFull));
+        const int h = ep_key_hypothesis(key[0]);
         float f[9];
 #pragma unroll
         for (int e = 0; e < 9; ++e) {
@@ -234,7 +161,7 @@ __global__ void __launch_bounds__(kEpipolarScanBlock) two_view_select_kernel(con
         }
         if (tid == 0) {
             p.best[0] = h;
-            p.n_inliers[0] = (int32_t)(key[0] >> 32) - 1;
+            p.n_inliers[0] = ep_key_count(key[0]);
             float F[9];
             sel_pixel_F(p, f, F);
 #pragma unroll
@@ -244,9 +171,9 @@ __global__ void __launch_bounds__(kEpipolarScanBlock) two_view_select_kernel(con
         }
         sel_reject<FundamentalModel>(p, f, m, tid);
     } else {
-        const bool has_f = (key[0] >> 32) != 0ull, has_h = (key[1] >> 32) != 0ull;
-        const int32_t n_f = has_f ? (int32_t)(key[0] >> 32) - 1 : m, n_h = has_h ? (int32_t)(key[1] >> 32) - 1 : m;
-        const int h_f = has_f ? (int)(~(uint32_t)(key[0] & 0xFFFFFFFFull)) : -1, h_h = has_h ? (int)(~(uint32_t)(key[1] & 0xFFFFFFFFull)) : -1;
+        const bool has_f = ep_key_has_winner(key[0]), has_h = ep_key_has_winner(key[1]);
+        const int32_t n_f = has_f ? ep_key_count(key[0]) : m, n_h = has_h ? ep_key_count(key[1]) : m;
+        const int h_f = has_f ? ep_key_hypothesis(key[0]) : -1, h_h = has_h ? ep_key_hypothesis(key[1]) : -1;
         // the rule, on integers: the homography iff it has a winner and (the fundamental matrix has none or 1000 n_H >= p n_F)
         int model = -1;
         if (has_h && (!has_f || 1000ll * (long long)n_h >= (long long)p.prefer_permille * (long long)n_f)) {

@@ -4,21 +4,21 @@
 //  * pose_scan_kernel: the filters' scan (epipolar_device.h's ep_scan_participants: ONE workgroup lists the participants, status ==
 //    FTK_TRACKED, in ascending index order) storing the CALIBRATED coordinates x = (u - cx) / fx of each view's own camera.
 //  * pose_moment_kernel: the hot path.  A workgroup owns a tile of 256 participants; a thread forms its participant's epipolar row and the
-//    45 distinct products of r r^T, and the tile reduces them in LDS by the STATED tree (p[j] += p[j + stride], stride 128 .. 1).  The
-//    (entry, j) pairs of a step are dealt to all 256 threads, so a step costs ceil(45 stride / 256) adds per thread, not 45; the
-//    operands of every add are the tree's, so the bits are.  No float atomics: a tile's 45 totals go to the workspace.
-//  * pose_solve_kernel: ONE wave.  Lanes 0 .. 44 add the tile totals in ascending tile order; jacobi_eigen<9> finds the null vector,
-//    jacobi_eigen<3> on E^T E the projection onto the essential matrices; the four candidates go to the workspace.  The matrices live
-//    in LDS (run-time indices: no scratch); a rotation's row updates of A and of V run on lanes 0 .. N-1 and 16 .. 16+N-1, each the
-//    restatement's expression on the restatement's operands.
-//  * pose_count_kernel: per candidate the participants in front of both cameras, by ballot and popcount, ONE integer atomicAdd per
-//    workgroup and candidate.
-//  * pose_finish_kernel: a thread per point selects the winner, forms the pose (uniform arithmetic, every thread the same), triangulates
-//    its point, tests its reprojection and rewrites its status; block 0 writes the pose.
+//    45 distinct products of r r^T, and the tile reduces them in LDS by the STATED tree (pose_device.h's pose_tree_sum: p[j] += p[j +
+//    stride], stride 128 .. 1).  The (entry, j) pairs of a step are dealt to all 256 threads, so a step costs ceil(45 stride / 256) adds
+//    per thread, not 45; the operands of every add are the tree's, so the bits are.  No float atomics: a tile's 45 totals go to the
+//    workspace.
+//  * pose_solve_kernel: ONE wave.  Lanes 0 .. 44 add the tile totals in ascending tile order (pose_tile_total); pose_device.h's
+//    jacobi_eigen<9, Jacobi::Wave> finds the null vector, jacobi_eigen<3, Jacobi::Wave> on E^T E the projection onto the essential
+//    matrices; the four candidates go to the workspace.  The matrices live in LDS (run-time indices: no scratch); a rotation's row
+//    updates of A and of V run on lanes 0 .. N-1 and 16 .. 16+N-1, each the restatement's expression on the restatement's operands.
+//  * pose_count_kernel: per candidate the participants in front of both cameras (pose_ray, ep_two_ray_depths), counted by
+//    pose_block_counts_add: ballot and popcount, ONE integer atomicAdd per workgroup and candidate.
+//  * pose_finish_kernel: a thread per point selects the winner, forms the pose (uniform arithmetic, every thread the same; the quaternion
+//    is pose_quaternion_of_transpose), triangulates its point, tests its reprojection and rewrites its status; block 0 writes the pose.
 // Every float operation below is stated in DESIGN.md 5.29 and restated in tests/two_view_pose_ref.c; the build has no contraction
 // (-ffp-contract=off) and correctly rounded division and square root.
-#include "epipolar_device.h"
-#include "two_view_pose_plan.h"
+#include "pose_device.h"
 
 namespace ftk {
 namespace {
@@ -60,85 +60,9 @@ __global__ void __launch_bounds__(kPoseTile) pose_moment_kernel(const TwoViewPos
         }
     }
     __syncthreads();
-    for (int stride = kPoseTile / 2, shift = 7; stride >= 1; stride >>= 1, --shift) {
-        const int jobs = kPoseMoments * stride;
-        for (int job = tid; job < jobs; job += kPoseTile) {
-            const int e = job >> shift, j = job & (stride - 1);
-            tree[e][j] = tree[e][j] + tree[e][j + stride];
-        }
-        __syncthreads();
-    }
+    pose_tree_sum(tree, tid);
     if (tid < kPoseMoments) {
         p.totals[(size_t)blockIdx.x * kPoseMoments + tid] = tree[tid][0];
-    }
-}
-
-// Cyclic Jacobi on the symmetric N x N matrix a (LDS, full storage, row-major; its diagonal ends as the eigenvalues), eigenvectors
-// accumulated in the columns of v (LDS).  Called by the whole workgroup of kPoseSolveBlock threads; a is complete and visible on entry,
-// a and v are on return.  Pairs (p, q), p < q, in row-major order; kPoseJacobiSweeps sweeps, all of them.
-template <int N>
-__device__ __forceinline__ void jacobi_eigen(float *const a, float *const v, const int tid) {
-    static_assert(16 + N <= kPoseSolveBlock, "the lanes of a rotation");
-    for (int idx = tid; idx < N * N; idx += kPoseSolveBlock) {
-        v[idx] = idx / N == idx % N ? 1.0f : 0.0f;
-    }
-    __syncthreads();
-    for (int sweep = 0; sweep < kPoseJacobiSweeps; ++sweep) {
-        for (int p = 0; p < N - 1; ++p) {
-            for (int q = p + 1; q < N; ++q) {
-                const float apq = a[p * N + q], app = a[p * N + p], aqq = a[q * N + q];
-                __syncthreads();  // every lane has read the pair before any lane writes
-                if (apq == 0.0f) {
-                    continue;  // (wave-uniform, as every branch on the pair's three entries)
-                }
-                const float g = 100.0f * fabsf(apq);
-                if (fabsf(app) + g == fabsf(app) && fabsf(aqq) + g == fabsf(aqq)) {  // negligible: set to zero, no rotation
-                    if (tid == 0) {
-                        a[p * N + q] = 0.0f;
-                        a[q * N + p] = 0.0f;
-                    }
-                    __syncthreads();
-                    continue;
-                }
-                const float h = aqq - app;
-                float t;
-                if (fabsf(h) + g == fabsf(h)) {
-                    t = apq / h;
-                } else {
-                    const float theta = h / (2.0f * apq);
-                    t = 1.0f / (fabsf(theta) + sqrtf(theta * theta + 1.0f));
-                    if (theta < 0.0f) {
-                        t = -t;
-                    }
-                }
-                const float c = 1.0f / sqrtf(t * t + 1.0f);
-                const float s = t * c;
-                const float tau = s / (1.0f + c);
-                const float hh = t * apq;
-                if (tid < N) {
-                    const int r = tid;
-                    if (r == p) {
-                        a[p * N + p] = app - hh;
-                        a[q * N + q] = aqq + hh;
-                        a[p * N + q] = 0.0f;
-                        a[q * N + p] = 0.0f;
-                    } else if (r != q) {
-                        const float x = a[r * N + p], y = a[r * N + q];
-                        const float xn = x - s * (y + x * tau), yn = y + s * (x - y * tau);
-                        a[r * N + p] = xn;
-                        a[p * N + r] = xn;
-                        a[r * N + q] = yn;
-                        a[q * N + r] = yn;
-                    }
-                } else if (tid >= 16 && tid < 16 + N) {
-                    const int r = tid - 16;
-                    const float x = v[r * N + p], y = v[r * N + q];
-                    v[r * N + p] = x - s * (y + x * tau);
-                    v[r * N + q] = y + s * (x - y * tau);
-                }
-                __syncthreads();
-            }
-        }
     }
 }
 
@@ -160,11 +84,7 @@ __global__ void __launch_bounds__(kPoseSolveBlock) pose_solve_kernel(const TwoVi
     }
     // the 45 sums: tile totals in ascending tile order from +0
     if (tid < kPoseMoments) {
-        const int tiles = (m + kPoseTile - 1) / kPoseTile;
-        float acc = 0.0f;
-        for (int t = 0; t < tiles; ++t) {
-            acc = acc + p.totals[(size_t)t * kPoseMoments + tid];
-        }
+        const float acc = pose_tile_total(p.totals, (m + kPoseTile - 1) / kPoseTile, kPoseMoments, tid);
         int row = 0, rem = tid;
         while (rem >= 9 - row) {
             rem -= 9 - row;
@@ -176,7 +96,7 @@ __global__ void __launch_bounds__(kPoseSolveBlock) pose_solve_kernel(const TwoVi
     }
     __syncthreads();
     // the null vector: the eigenvector of the smallest eigenvalue, ties to the lowest column
-    jacobi_eigen<9>(a9, v9, tid);
+    jacobi_eigen<9, Jacobi::Wave>(a9, v9, tid);
     int k = 0;
     for (int j = 1; j < 9; ++j) {
         if (a9[j * 9 + j] < a9[k * 9 + k]) {
@@ -211,7 +131,7 @@ __global__ void __launch_bounds__(kPoseSolveBlock) pose_solve_kernel(const TwoVi
         }
     }
     __syncthreads();
-    jacobi_eigen<3>(a3, v3, tid);
+    jacobi_eigen<3, Jacobi::Wave>(a3, v3, tid);
     const float l0 = a3[0], l1 = a3[4], l2 = a3[8];
     int i1 = 0;
     if (l1 > l0) {
@@ -258,13 +178,6 @@ __global__ void __launch_bounds__(kPoseSolveBlock) pose_solve_kernel(const TwoVi
     }
 }
 
-// a = R (x, y, 1)
-__device__ __forceinline__ void pose_rotate(const float (&R)[9], const float x, const float y, float (&a)[3]) {
-    a[0] = (R[0] * x + R[1] * y) + R[2];
-    a[1] = (R[3] * x + R[4] * y) + R[5];
-    a[2] = (R[6] * x + R[7] * y) + R[8];
-}
-
 // The two-ray depths of z2 (x2, y2, 1) = z1 R (x1, y1, 1) + t by the 2 x 2 normal equations of the midpoint; true: both finite and > 0.
 __device__ __forceinline__ bool pose_in_front(const float (&R)[9], const float (&t)[3], const float4 q, float &z1, float &z2) {
     z1 = 0.0f;
@@ -273,7 +186,7 @@ __device__ __forceinline__ bool pose_in_front(const float (&R)[9], const float (
         return false;
     }
     float a[3];
-    pose_rotate(R, q.x, q.y, a);
+    pose_ray(R, q.x, q.y, a);
     const float b[3] = {q.z, q.w, 1.0f};
     float aa, bb, ab;
     return ep_two_ray_depths(a, b, t, z1, z2, aa, bb, ab);
@@ -299,35 +212,22 @@ __global__ void __launch_bounds__(kPoseTile) pose_count_kernel(const TwoViewPose
     if (m < kEpipolarSample || base >= m || p.model[kModelOk] == 0.0f) {
         return;  // the whole workgroup
     }
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int tid = threadIdx.x;
     const bool active = base + tid < m;
     const float4 q = active ? p.points[base + tid] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    bool in[4];
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
         float R[9], t[3], z1, z2;
         pose_candidate(p.model, c, R, t);
-        const bool in = active && pose_in_front(R, t, q, z1, z2);
-        const int32_t count = (int32_t)__popcll(__ballot(in));
-        if (lane == 0) {
-            counts[c][wave] = count;
-        }
+        in[c] = active && pose_in_front(R, t, q, z1, z2);
     }
-    __syncthreads();
-    if (tid < 4) {
-        int32_t sum = 0;
-#pragma unroll
-        for (int w = 0; w < kPoseTile / 64; ++w) {
-            sum += counts[tid][w];
-        }
-        if (sum > 0) {
-            atomicAdd(&p.n_front[tid], sum);
-        }
-    }
+    pose_block_counts_add(counts, in, p.n_front);
 }
 
 __global__ void __launch_bounds__(kPoseTile) pose_finish_kernel(const TwoViewPoseParams p) {
-    __shared__ int32_t kept[kPoseTile / 64];
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    __shared__ int32_t kept[1][kPoseTile / 64];
+    const int tid = threadIdx.x;
     const int i = blockIdx.x * kPoseTile + tid;
     const int m = min(p.m[0], p.n);
     bool ok = m >= kEpipolarSample && p.model[kModelOk] != 0.0f;
@@ -358,28 +258,7 @@ __global__ void __launch_bounds__(kPoseTile) pose_finish_kernel(const TwoViewPos
         for (int j = 0; j < 3; ++j) {
             ps[4 + j] = -((R[j] * ts0 + R[3 + j] * ts1) + R[6 + j] * ts2);
         }
-        // Shepperd on M = R^T: M(i, j) = R[j * 3 + i]
-        const float m00 = R[0], m01 = R[3], m02 = R[6], m10 = R[1], m11 = R[4], m12 = R[7], m20 = R[2], m21 = R[5], m22 = R[8];
-        const float tr = (m00 + m11) + m22;
-        float qw, qx, qy, qz;
-        if (tr > 0.0f) {
-            const float s = sqrtf(tr + 1.0f) * 2.0f;
-            qw = 0.25f * s, qx = (m21 - m12) / s, qy = (m02 - m20) / s, qz = (m10 - m01) / s;
-        } else if (m00 > m11 && m00 > m22) {
-            const float s = sqrtf(((1.0f + m00) - m11) - m22) * 2.0f;
-            qw = (m21 - m12) / s, qx = 0.25f * s, qy = (m01 + m10) / s, qz = (m02 + m20) / s;
-        } else if (m11 > m22) {
-            const float s = sqrtf(((1.0f + m11) - m00) - m22) * 2.0f;
-            qw = (m02 - m20) / s, qx = (m01 + m10) / s, qy = 0.25f * s, qz = (m12 + m21) / s;
-        } else {
-            const float s = sqrtf(((1.0f + m22) - m00) - m11) * 2.0f;
-            qw = (m10 - m01) / s, qx = (m02 + m20) / s, qy = (m12 + m21) / s, qz = 0.25f * s;
-        }
-        if (qw < 0.0f) {
-            qw = -qw, qx = -qx, qy = -qy, qz = -qz;
-        }
-        const float qn = sqrtf(((qw * qw + qx * qx) + qy * qy) + qz * qz);
-        ps[0] = qw / qn, ps[1] = qx / qn, ps[2] = qy / qn, ps[3] = qz / qn;
+        pose_quaternion_of_transpose(R, ps);
 #pragma unroll
         for (int e = 0; e < 7; ++e) {
             ok = ok && ep_finite(ps[e]);
@@ -409,7 +288,7 @@ __global__ void __launch_bounds__(kPoseTile) pose_finish_kernel(const TwoViewPos
             keep = pose_in_front(R, t, q, z1, z2);
             if (keep) {
                 float a[3];
-                pose_rotate(R, q.x, q.y, a);
+                pose_ray(R, q.x, q.y, a);
                 const float cX = z1 * a[0] + t[0], cY = z1 * a[1] + t[1], cZ = z1 * a[2] + t[2];
                 const float ex = p.fx2 * (cX - q.z * cZ), ey = p.fy2 * (cY - q.w * cZ);
                 const float lhs = ex * ex + ey * ey, rhs = p.t2 * (cZ * cZ);
@@ -426,21 +305,8 @@ __global__ void __launch_bounds__(kPoseTile) pose_finish_kernel(const TwoViewPos
         p.landmarks[3 * (size_t)i + 1] = Y;
         p.landmarks[3 * (size_t)i + 2] = Z;
     }
-    const int32_t count = (int32_t)__popcll(__ballot(keep));
-    if (lane == 0) {
-        kept[wave] = count;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        int32_t sum = 0;
-#pragma unroll
-        for (int w = 0; w < kPoseTile / 64; ++w) {
-            sum += kept[w];
-        }
-        if (sum > 0) {
-            atomicAdd(&p.n_points[0], sum);
-        }
-    }
+    const bool flags[1] = {keep};
+    pose_block_counts_add(kept, flags, p.n_points);
 }
 
 }  // namespace

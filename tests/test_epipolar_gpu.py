@@ -36,6 +36,16 @@ def test_bit_identity_with_the_restatement(ftk, name, K):
     _equal(_device(ftk, ref, cur, status, image, 1.0, K, 3), want, (name, K))
 
 
+def test_a_winner_beyond_the_first_hypothesis_of_every_select_thread(ftk):
+    """2048 hypotheses: a thread of the select kernel folds two.  The 300-point scene with 0.3 px of noise (without noise the first sample
+    of inliers alone wins, an early one); under this seed the winner (best = 1543) is a thread's second."""
+    ref, cur, _, _ = E.scene(300, 1, noise=0.3)
+    status = np.full(300, E.TRACKED, np.uint8)
+    want = E.ransac(ref, cur, status, E.IMAGE, 1.0, 2048, 4)
+    assert want.best >= 1024
+    _equal(_device(ftk, ref, cur, status, E.IMAGE, 1.0, 2048, 4), want, "fold")
+
+
 @pytest.mark.parametrize("name", E.HOSTILE_CASES)
 def test_hostile_and_degenerate_inputs(ftk, name):
     ref, cur, status, image = E.case(name)

@@ -49,6 +49,15 @@ def test_hypothesis_counts_across_the_workgroup(ftk, hypotheses):
     assert R.same_results(_device(ftk, X, uv, status, hypotheses=hypotheses, seed=5), want, ALL) == [], hypotheses
 
 
+def test_a_winner_beyond_the_first_hypothesis_of_every_select_thread(ftk):
+    """2048 hypotheses: a thread of the select kernel folds two, and under this seed the winner (best = 1950) is a thread's second."""
+    X, uv, _, _ = R.scene(300, 2, noise=0.3, outlier_share=0.3)
+    status = np.full(300, R.TRACKED, np.uint8)
+    want = Q.solve(X, uv, status, hypotheses=2048, seed=0)
+    assert int(want.valid[0]) == 1 and int(want.best[0]) >= 1024
+    assert R.same_results(_device(ftk, X, uv, status, hypotheses=2048, seed=0), want, ALL) == []
+
+
 @pytest.mark.parametrize("name", Q.NAMED_CASES)
 def test_hostile_degenerate_and_planar_inputs(ftk, name):
     X, uv, status = Q.case(name)

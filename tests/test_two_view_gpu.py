@@ -39,6 +39,17 @@ def test_bit_identity_with_the_restatement(ftk, name, K):
         assert T.same_results(_device(ftk, ref, cur, status, image, 1.0, K, 3, mode), want) == [], (name, K, mode)
 
 
+def test_winners_beyond_the_first_hypothesis_of_every_select_thread(ftk):
+    """2048 hypotheses: a thread of the select kernel folds two of each model.  The 300-point scene with 0.3 px of noise (without noise
+    the first sample of inliers alone wins, an early one); under this seed both winners (best = 1543, 1664) are a thread's second."""
+    ref, cur, _, _ = E.scene(300, 1, noise=0.3)
+    status = np.full(300, T.TRACKED, np.uint8)
+    for mode in MODES:
+        want = T.ransac(ref, cur, status, T.IMAGE, 1.0, 2048, 4, mode)
+        assert min(b for b in want.best if b >= 0) >= 1024
+        assert T.same_results(_device(ftk, ref, cur, status, T.IMAGE, 1.0, 2048, 4, mode), want) == [], mode
+
+
 @pytest.mark.parametrize("name", T.HOSTILE_CASES)
 def test_hostile_and_degenerate_inputs(ftk, name):
     ref, cur, status, image = T.case(name)
