@@ -17,8 +17,6 @@ Fields:
                      pixel); the bilinear taps of the iterations are re-reads served by the caches and are not counted.
   hbm_fraction       compulsory_bytes / device time over the 8 TB/s HBM peak (MI355X_MICROARCH.md) — a floor, not a bound.
 """
-import argparse
-import json
 import os
 import sys
 import time
@@ -30,6 +28,7 @@ sys.path.insert(0, ROOT)
 import feature_tracker_amd as F  # noqa: E402
 from feature_tracker_amd import _native, synth  # noqa: E402
 from feature_tracker_amd import device as D  # noqa: E402
+from scripts.benchlib import parser, percentiles, write_rows  # noqa: E402
 from tests import dense_flow_ref as R  # noqa: E402
 
 HBM_PEAK = 8.0e12
@@ -54,19 +53,7 @@ def compulsory_bytes(rl, cl):
     return b
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--calls", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--host-calls", type=int, default=30)
-    ap.add_argument("--cpu-calls", type=int, default=1)
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--workload", default="all", help="example | vga4 | all")
-    args = ap.parse_args()
-    import torch
-
-    assert torch.cuda.is_available(), "bench_dense_flow.py measures on a HIP device (no CPU fallback)"
-    lines = []
+def rows(args, torch):
     for name, ref, cur, levels, opts in workloads():
         if args.workload not in ("all", name):
             continue
@@ -110,22 +97,28 @@ def main():
             ok_c, fr_c, fc_c, _ = R.track_pyramid(rl, cl, ropt)
             cpu.append((time.perf_counter() - t0) * 1e3)
         identical = bool(ok and ok_c and R.same(fr, fr_c) and R.same(fc, fc_c) and R.same(dev_r, fr_c) and R.same(dev_c, fc_c))
-        dev_ms = float(np.median(times))
+        dev_ms, dev_p10, dev_p90 = percentiles(times)
         nbytes = compulsory_bytes(rl, cl)
         line = dict(workload=name, shape=[int(ref.shape[0]), int(ref.shape[1])], levels=levels, half_patch=o.kHalfPatchSize, max_iteration=o.kMaxIteration,
-                    device_ms_median=round(dev_ms, 4), device_ms_p10=round(float(np.percentile(times, 10)), 4), device_ms_p90=round(float(np.percentile(times, 90)), 4),
+                    device_ms_median=round(dev_ms, 4), device_ms_p10=round(dev_p10, 4), device_ms_p90=round(dev_p90, 4),
                     device_calls=len(times), host_call_ms=round(float(np.median(host)), 4), cpu_restatement_ms=round(float(np.median(cpu)), 2),
                     cpu_restatement_note="single-thread C restatement (tests/dense_flow_ref.c, gcc -O3), not the reference's time",
                     speedup_vs_cpu_restatement=round(float(np.median(cpu)) / dev_ms, 1), compulsory_bytes=nbytes,
                     hbm_fraction=round(nbytes / (dev_ms * 1e-3) / HBM_PEAK, 5), identical_to_restatement=identical,
                     build=_native.build_info().get("source_hash"))
-        print(json.dumps(line), flush=True)
-        lines.append(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            for line in lines:
-                f.write(json.dumps(line) + "\n")
+        yield line
+
+
+def main():
+    ap = parser("--calls", 200, 20)
+    ap.add_argument("--host-calls", type=int, default=30)
+    ap.add_argument("--cpu-calls", type=int, default=1)
+    ap.add_argument("--workload", default="all", help="example | vga4 | all")
+    args = ap.parse_args()
+    import torch
+
+    assert torch.cuda.is_available(), "bench_dense_flow.py measures on a HIP device (no CPU fallback)"
+    lines = write_rows(rows(args, torch), args.out, append=False)
     return 0 if all(l["identical_to_restatement"] for l in lines) else 1
 
 

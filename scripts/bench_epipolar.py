@@ -5,35 +5,14 @@ Sampson test as one [K, M] tensor expression, argmax, the status rewrite), and o
 medians of device-synchronised wall times are reported, one JSON line per configuration (appended to --out when given)."""
 from __future__ import annotations
 
-import argparse
-import json
 import os
 import sys
-import time
-
-import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-IMAGE = (480, 640)
-
-
-def scene(n, seed=1):
-    """Correspondences of a translating, slightly rotating camera over random depths, 30 % of them replaced by random points."""
-    rng = np.random.default_rng(seed)
-    H, W = IMAGE
-    f = 0.8 * W
-    ref = rng.uniform([10, 10], [W - 10, H - 10], (n, 2))
-    depth = rng.uniform(2.0, 10.0, n)
-    X = np.c_[(ref[:, 0] - 0.5 * (W - 1)) / f, (ref[:, 1] - 0.5 * (H - 1)) / f, np.ones(n)] * depth[:, None]
-    a = 0.03
-    R = np.array([[np.cos(a), 0, np.sin(a)], [0, 1, 0], [-np.sin(a), 0, np.cos(a)]])
-    Y = X @ R.T + np.array([0.5, 0.1, 0.15])
-    cur = np.c_[f * Y[:, 0] / Y[:, 2] + 0.5 * (W - 1), f * Y[:, 1] / Y[:, 2] + 0.5 * (H - 1)]
-    out = rng.permutation(n)[:int(0.3 * n)]
-    cur[out] = rng.uniform([5, 5], [W - 5, H - 5], (len(out), 2))
-    return ref.astype(np.float32), cur.astype(np.float32)
+from scripts.bench_scenes import IMAGE, VIDEO_SHAPES, sequence, two_view_scene  # noqa: E402
+from scripts.benchlib import interleaved, parser, us_fields, us_median, wall_time, write_rows  # noqa: E402
 
 
 def torch_filter(torch, ref_uv, cur_uv, status, image, threshold, K, seed):
@@ -82,33 +61,11 @@ def torch_filter(torch, ref_uv, cur_uv, status, image, threshold, K, seed):
     return best, counts[best]
 
 
-def timed(torch, fn, repeats, warmup):
-    times = []
-    for k in range(repeats + warmup):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        if k >= warmup:
-            times.append(time.perf_counter() - t0)
-    return times
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--repeats", type=int, default=30)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--frames", type=int, default=30)
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
-    import torch
-
+def rows(args, torch):
     import feature_tracker_amd as F
-    from scripts.bench_klt_video import SHAPES, sequence
 
-    rows = []
     for M in (300, 2000):
-        ref, cur = scene(M)
+        ref, cur = two_view_scene(M)
         d_ref, d_cur = torch.from_numpy(ref).cuda(), torch.from_numpy(cur).cuda()
         fresh = torch.ones(M, dtype=torch.uint8, device="cuda")
         for K in (512, 2048):
@@ -123,39 +80,33 @@ def main():
                 status_b.copy_(fresh)
                 return torch_filter(torch, d_ref, d_cur, status_b, IMAGE, 1.0, K, 1)
 
-            t_ours, t_stock = [], []
-            for _ in range(3):  # interleaved rounds
-                t_ours += timed(torch, ours, args.repeats // 3, args.warmup)
-                t_stock += timed(torch, stock, args.repeats // 3, args.warmup)
-            kept_a, kept_b = int((status_a == 1).sum().item()), int((status_b == 1).sum().item())
-            rows.append({"bench": "epipolar_filter", "participants": M, "hypotheses": K, "filter_us_median": round(1e6 * float(np.median(t_ours)), 1),
-                         "filter_us_min": round(1e6 * float(np.min(t_ours)), 1), "torch_ops_us_median": round(1e6 * float(np.median(t_stock)), 1),
-                         "torch_ops_us_min": round(1e6 * float(np.min(t_stock)), 1), "kept": kept_a, "torch_ops_kept": kept_b})
-    for name, (width, height, n, distance) in SHAPES.items():
+            times = interleaved(torch, {"filter": ours, "torch_ops": stock}, args.repeats, args.warmup)
+            row = {"bench": "epipolar_filter", "participants": M, "hypotheses": K}
+            for name in times:
+                us_fields(row, name, times[name])
+            row["kept"], row["torch_ops_kept"] = int((status_a == 1).sum().item()), int((status_b == 1).sum().item())
+            yield row
+    for name, (width, height, n, distance) in VIDEO_SHAPES.items():
         images = [torch.from_numpy(i).cuda() for i in sequence(width, height, args.frames + args.warmup)]
         medians = {}
         for label, kw in (("plain", {}), ("filtered", {"epipolar_threshold": 1.0, "epipolar_hypotheses": 512})):
             flow = F.OpticalFlowBasicKlt()
             flow.options().kMaxTrackPointsNumber = n
             tracker = F.KltVideoTracker(flow, n, levels=4, min_distance=distance, **kw)
-            times = []
-            for image in images:
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                tracker.track(image)
-                torch.cuda.synchronize()
-                times.append(time.perf_counter() - t0)
-            medians[label] = (round(1e6 * float(np.median(times[args.warmup:])), 1), int(tracker.n_live.item()))
-        rows.append({"bench": "klt_video_epipolar", "shape": name, "width": width, "height": height, "max_features": n, "hypotheses": 512,
-                     "frame_us_median": medians["plain"][0], "frame_with_filter_us_median": medians["filtered"][0],
-                     "filter_adds_us": round(medians["filtered"][0] - medians["plain"][0], 1), "live": medians["plain"][1], "live_with_filter": medians["filtered"][1]})
-    for row in rows:
-        row["device"] = torch.cuda.get_device_name(0)
-        line = json.dumps(row)
-        print(line, flush=True)
-        if args.out:
-            with open(args.out, "a") as f:
-                f.write(line + "\n")
+            times = [wall_time(torch, lambda: tracker.track(image)) for image in images]
+            medians[label] = (us_median(times[args.warmup:]), int(tracker.n_live.item()))
+        yield {"bench": "klt_video_epipolar", "shape": name, "width": width, "height": height, "max_features": n, "hypotheses": 512,
+               "frame_us_median": medians["plain"][0], "frame_with_filter_us_median": medians["filtered"][0],
+               "filter_adds_us": round(medians["filtered"][0] - medians["plain"][0], 1), "live": medians["plain"][1], "live_with_filter": medians["filtered"][1]}
+
+
+def main():
+    ap = parser("--repeats", 30, 5)
+    ap.add_argument("--frames", type=int, default=30)
+    args = ap.parse_args()
+    import torch
+
+    write_rows(rows(args, torch), args.out, append=True, extra={"device": torch.cuda.get_device_name(0)})
 
 
 if __name__ == "__main__":

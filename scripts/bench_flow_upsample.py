@@ -19,18 +19,15 @@ Fields (all times: one device-event pair per call, median over --calls after --w
   cpu_ms                               with --cpu: ONE call of the single-thread C restatement (tests/flow_upsample_ref.c) — labelled as
                                        such, not the reference's time.
 """
-import argparse
-import json
 import os
 import sys
 import time
-
-import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import feature_tracker_amd as F  # noqa: E402
 from feature_tracker_amd import _native  # noqa: E402
+from scripts.benchlib import event_times, ms_fields, parser, write_rows  # noqa: E402
 from tests import flow_upsample_ref as R  # noqa: E402
 from tests.test_flow_upsample_cpu import torch_upsample  # noqa: E402
 
@@ -38,35 +35,9 @@ COPY_GBPS = 6290.0  # MI355X_MICROARCH.md: HBM3E, 6.29 TB/s measured with a floa
 SHAPES = [("eighth_example", 1, 60, 94), ("raft_55x128", 1, 55, 128), ("eighth_example_12_iterations", 12, 60, 94)]
 
 
-def time_gpu(torch, fns, calls, warmup):
-    """Median / p10 / p90 of `calls` event-timed calls, call q running fns[q % len(fns)]."""
-    for q in range(max(warmup, len(fns))):
-        fns[q % len(fns)]()
-    torch.cuda.synchronize()
-    ms = []
-    for q in range(calls):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fns[q % len(fns)]()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return float(np.median(ms)), float(np.percentile(ms, 10)), float(np.percentile(ms, 90))
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--calls", type=int, default=100)
-    ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--footprint-mb", type=int, default=640, help="total size of the rotating input sets")
-    ap.add_argument("--cpu", action="store_true", help="also time one call of the single-thread C restatement")
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
-    import torch
-
+def rows(args, torch):
     dev = torch.device("cuda")
     build = _native.build_info().get("source_hash", "?")
-    rows = []
     for name, B, H, W in SHAPES:
         compulsory = 4 * B * H * W * (576 + 2 + 128)
         n_sets = max(2, -(-args.footprint_mb * 2 ** 20 // compulsory))
@@ -85,16 +56,15 @@ def main():
             }
             t = {}
             for key, fn in variants.items():
-                t[key] = time_gpu(torch, [lambda fn=fn: fn(flow, mask)], args.calls, args.warmup)
-                t[key + "_rotating"] = time_gpu(torch, [lambda fn=fn, f=f, m=m: fn(f, m) for f, m in sets], args.calls, args.warmup)
+                t[key] = event_times(torch, [lambda fn=fn: fn(flow, mask)], args.calls, args.warmup)
+                t[key + "_rotating"] = event_times(torch, [lambda fn=fn, f=f, m=m: fn(f, m) for f, m in sets], args.calls, args.warmup)
             out = F.upsample_flow(flow, mask, 0.25).cpu().numpy()
         identical = R.same(out, R.upsample(host[0].numpy(), host[1].numpy(), 0.25))
         row = {"shape": name, "B": B, "H": H, "W": W, "compulsory_bytes": compulsory, "input_sets": n_sets}
-        for key, (med, p10, p90) in t.items():
-            row[key + "_ms"] = round(med, 4)
+        for key in t:
+            ms_fields(row, key, t[key], spread=key.startswith("kernel"))
             if key.startswith("kernel"):
-                row[key + "_ms_p10"], row[key + "_ms_p90"] = round(p10, 4), round(p90, 4)
-                row[key + "_gbps"] = round(compulsory / (med * 1e-3) / 1e9, 1)
+                row[key + "_gbps"] = round(compulsory / (t[key][0] * 1e-3) / 1e9, 1)
         row["copy_gbps"] = COPY_GBPS
         for a, b in (("kernel", "torch"), ("kernel_scaled", "torch_scaled"), ("kernel_rotating", "torch_rotating"), ("kernel_scaled_rotating", "torch_scaled_rotating")):
             row[a + "_speedup_vs_torch"] = round(t[b][0] / t[a][0], 2)
@@ -105,14 +75,19 @@ def main():
             R.upsample(host[0].numpy(), host[1].numpy(), 0.25)
             row["cpu_ms"] = round((time.perf_counter() - t0) * 1e3, 1)
             row["cpu_note"] = "one call of the single-thread C restatement (tests/flow_upsample_ref.c, gcc -O3), not the reference's time"
-        print(json.dumps(row), flush=True)
-        rows.append(row)
+        yield row
         del sets, flow, mask
         torch.cuda.empty_cache()
-    if args.out:
-        with open(args.out, "w") as f:
-            for row in rows:
-                f.write(json.dumps(row) + "\n")
+
+
+def main():
+    ap = parser("--calls", 100, 10)
+    ap.add_argument("--footprint-mb", type=int, default=640, help="total size of the rotating input sets")
+    ap.add_argument("--cpu", action="store_true", help="also time one call of the single-thread C restatement")
+    args = ap.parse_args()
+    import torch
+
+    write_rows(rows(args, torch), args.out, append=False)
 
 
 if __name__ == "__main__":

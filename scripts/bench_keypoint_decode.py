@@ -7,30 +7,17 @@ blend in its own order.  Calls are interleaved in one process and the medians of
 per shape (appended to --out, default profiles/keypoint_decode_bench.jsonl).  No time is asserted anywhere."""
 from __future__ import annotations
 
-import argparse
-import json
 import os
 import sys
-import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+from scripts.benchlib import interleaved, parser, us_fields, write_rows  # noqa: E402
+
 SHAPES = {"euroc_752x480": (480, 752, 300, 256, 20), "vga_640x480": (480, 640, 2000, 256, 4)}  # H, W, K, D, min_distance
-
-
-def timed(torch, fn, repeats, warmup):
-    out = []
-    for i in range(repeats + warmup):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        if i >= warmup:
-            out.append(time.perf_counter() - t0)
-    return out
 
 
 def torch_composition(torch, semi, desc, K, min_score, min_distance, border):
@@ -49,17 +36,9 @@ def torch_composition(torch, semi, desc, K, min_score, min_distance, border):
     return uv, scores, F.normalize(sampled, dim=1)
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--repeats", type=int, default=30)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "keypoint_decode_bench.jsonl"))
-    args = ap.parse_args()
-    import torch
-
+def rows(args, torch):
     import feature_tracker_amd as F
 
-    rows = []
     for name, (H, W, K, D, distance) in SHAPES.items():
         hc, wc = H // 8, W // 8
         rng = np.random.default_rng(1)
@@ -69,23 +48,19 @@ def main():
         decoder = F.KeypointDecoder(max_keypoints=K, min_score=0.05, min_distance=distance, border=4)
         calls = {"chw": lambda: decoder.decode(semi, desc), "hwc": lambda: decoder.decode(semi, desc_last),
                  "torch_ops": lambda: torch_composition(torch, semi, desc, K, 0.05, distance, 4)}
-        times = {label: [] for label in calls}
-        for _ in range(3):  # interleaved rounds
-            for label, fn in calls.items():
-                times[label] += timed(torch, fn, args.repeats // 3, args.warmup)
+        times = interleaved(torch, calls, args.repeats, args.warmup)
         row = {"bench": "keypoint_decode", "shape": name, "height": H, "width": W, "max_keypoints": K, "channels": D, "min_distance": distance,
                "count": int(decoder.decode(semi, desc).count.item())}
         for label in calls:
-            row[f"{label}_us_median"] = round(1e6 * float(np.median(times[label])), 1)
-            row[f"{label}_us_min"] = round(1e6 * float(np.min(times[label])), 1)
-        rows.append(row)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    for row in rows:
-        row["device"] = torch.cuda.get_device_name(0)
-        line = json.dumps(row)
-        print(line, flush=True)
-        with open(args.out, "a") as f:
-            f.write(line + "\n")
+            us_fields(row, label, times[label])
+        yield row
+
+
+def main():
+    args = parser("--repeats", 30, 5, os.path.join(ROOT, "profiles", "keypoint_decode_bench.jsonl")).parse_args()
+    import torch
+
+    write_rows(rows(args, torch), args.out, append=True, extra={"device": torch.cuda.get_device_name(0)})
 
 
 if __name__ == "__main__":

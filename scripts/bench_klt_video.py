@@ -4,8 +4,6 @@ synthetic sequence at the reference's shape (752 x 480, 300 features, distance 2
 distance 8); medians of the timed frames, one JSON line per shape (appended to --out when given)."""
 from __future__ import annotations
 
-import argparse
-import json
 import os
 import sys
 import time
@@ -15,26 +13,16 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-SHAPES = {"reference": (752, 480, 300, 25), "headline": (640, 480, 2000, 8)}
-
-
-def sequence(width, height, frames):
-    from feature_tracker_amd import synth
-    big = synth.make_image_pair(width + 2 * frames, height + frames, (0.0, 0.0))[0]
-    return [np.ascontiguousarray(big[k:k + height, 2 * k:2 * k + width]) for k in range(frames)]  # the camera moves by (2, 1) pixels a frame
+from scripts.bench_scenes import VIDEO_SHAPES as SHAPES  # noqa: E402
+from scripts.bench_scenes import sequence  # noqa: E402
+from scripts.benchlib import parser, us_median, wall_time, write_rows  # noqa: E402
 
 
 def run_tracker(F, torch, images, n, distance, levels):
     flow = F.OpticalFlowBasicKlt()
     flow.options().kMaxTrackPointsNumber = n
     tracker = F.KltVideoTracker(flow, n, levels=levels, min_distance=distance)
-    times = []
-    for image in images:
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        tracker.track(image)
-        torch.cuda.synchronize()
-        times.append(time.perf_counter() - t0)
+    times = [wall_time(torch, lambda: tracker.track(image)) for image in images]
     return times, int(tracker.n_live.item())
 
 
@@ -73,15 +61,7 @@ def run_composition(F, torch, D, images_host, images, n, distance, levels):
     return times, len(points)
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--frames", type=int, default=30)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--levels", type=int, default=4)
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
-    import torch
-
+def rows(args, torch):
     import feature_tracker_amd as F
     from feature_tracker_amd import device as D
 
@@ -91,14 +71,19 @@ def main():
         t_new, live_new = run_tracker(F, torch, images, n, distance, args.levels)
         t_old, live_old = run_composition(F, torch, D, host, images, n, distance, args.levels)
         row = {"bench": "klt_video", "shape": name, "width": width, "height": height, "max_features": n, "min_distance": distance, "frames": args.frames,
-               "tracker_us_median": round(1e6 * float(np.median(t_new[args.warmup:])), 1), "composition_us_median": round(1e6 * float(np.median(t_old[args.warmup:])), 1),
+               "tracker_us_median": us_median(t_new[args.warmup:]), "composition_us_median": us_median(t_old[args.warmup:]),
                "tracker_live": live_new, "composition_live": live_old, "device": torch.cuda.get_device_name(0)}
         row["speedup"] = round(row["composition_us_median"] / row["tracker_us_median"], 2)
-        line = json.dumps(row)
-        print(line, flush=True)
-        if args.out:
-            with open(args.out, "a") as f:
-                f.write(line + "\n")
+        yield row
+
+
+def main():
+    ap = parser("--frames", 30, 5)
+    ap.add_argument("--levels", type=int, default=4)
+    args = ap.parse_args()
+    import torch
+
+    write_rows(rows(args, torch), args.out, append=True)
 
 
 if __name__ == "__main__":

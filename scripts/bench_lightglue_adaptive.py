@@ -13,8 +13,6 @@ profiles/lightglue_adaptive_bench.jsonl), with the stop layer and live counts ea
 random weights nothing is claimed about matching quality or typical stop layers."""
 from __future__ import annotations
 
-import argparse
-import json
 import os
 import sys
 
@@ -23,7 +21,8 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from scripts.bench_transformer_layer import DIM, HEADS, LAYERS, SIZES, state_dict, timed  # noqa: E402
+from scripts.bench_scenes import DIM, HEADS, LAYERS, SIZES, lightglue_inputs, state_dict  # noqa: E402
+from scripts.benchlib import interleaved, parser, us_fields, write_rows  # noqa: E402
 
 
 def adaptive_state_dict(torch, base, rng, token_bias, match_bias):
@@ -41,14 +40,7 @@ def adaptive_state_dict(torch, base, rng, token_bias, match_bias):
     return sd
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--repeats", type=int, default=30)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "lightglue_adaptive_bench.jsonl"))
-    args = ap.parse_args()
-    import torch
-
+def rows(args, torch):
     import feature_tracker_amd as F
     from feature_tracker_amd import _native as N
     from feature_tracker_amd import device as D
@@ -63,14 +55,8 @@ def main():
     lg_full = F.LightGlue.from_state_dict(sd_full, num_heads=HEADS, depth_confidence=0.95, width_confidence=0.99, pruning_min_keypoints=0)
     lg_stop = F.LightGlue.from_state_dict(sd_stop, num_heads=HEADS, depth_confidence=0.95, width_confidence=0.99, pruning_min_keypoints=0)
     size = (640.0, 480.0)
-    rows = []
     for n in SIZES:
-        x = rng.standard_normal((n, DIM))
-        y = x[rng.permutation(n)] + 0.3 * rng.standard_normal((n, DIM))
-        a = torch.from_numpy((x / np.linalg.norm(x, axis=1, keepdims=True)).astype(np.float32)).cuda()
-        b = torch.from_numpy((y / np.linalg.norm(y, axis=1, keepdims=True)).astype(np.float32)).cuda()
-        kp0 = torch.from_numpy((rng.random((n, 2)) * np.array(size)).astype(np.float32)).cuda()
-        kp1 = torch.from_numpy((rng.random((n, 2)) * np.array(size)).astype(np.float32)).cuda()
+        a, b, kp0, kp1 = lightglue_inputs(torch, rng, n, size)
         e0, e1 = F.rotary_encoding(kp0, size, base["posenc.Wr.weight"]), F.rotary_encoding(kp1, size, base["posenc.Wr.weight"])
         # the matchability z of the rows after layers 0 and 1: its median goes on the bar logit(1 - 0.9) = -2.2 at layer 1
         x0, x1 = a, b
@@ -93,10 +79,7 @@ def main():
                  "adaptive_stop3": lambda: lg_stop.match_adaptive(kp0, kp1, a, b, size, size),
                  "adaptive_prune_half": lambda: lg_prune.match_adaptive(kp0, kp1, a, b, size, size),
                  "layer_open": lambda: layer(gates["layer_open"]), "layer_gated": lambda: layer(gates["layer_gated"])}
-        times = {label: [] for label in calls}
-        for _ in range(3):  # interleaved rounds
-            for label, fn in calls.items():
-                times[label] += timed(torch, fn, args.repeats // 3, args.warmup)
+        times = interleaved(torch, calls, args.repeats, args.warmup)
         row = {"bench": "lightglue_adaptive", "rows": n, "dim": DIM, "heads": HEADS, "layers": LAYERS}
         for label, lg in (("adaptive_full", lg_full), ("adaptive_stop3", lg_stop), ("adaptive_prune_half", lg_prune)):
             r = lg.match_adaptive(kp0, kp1, a, b, size, size)
@@ -106,16 +89,15 @@ def main():
         plain = lg_plain.match(kp0, kp1, a, b, size, size)
         row["adaptive_full_equals_match"] = bool(torch.equal(full.match_index, plain[1]) and torch.equal(full.scores, plain[0]))
         for label in calls:
-            row[f"{label}_us_median"] = round(1e6 * float(np.median(times[label])), 1)
-            row[f"{label}_us_min"] = round(1e6 * float(np.min(times[label])), 1)
-        rows.append(row)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    for row in rows:
-        row["device"] = torch.cuda.get_device_name(0)
-        line = json.dumps(row)
-        print(line, flush=True)
-        with open(args.out, "a") as f:
-            f.write(line + "\n")
+            us_fields(row, label, times[label])
+        yield row
+
+
+def main():
+    args = parser("--repeats", 30, 5, os.path.join(ROOT, "profiles", "lightglue_adaptive_bench.jsonl")).parse_args()
+    import torch
+
+    write_rows(rows(args, torch), args.out, append=True, extra={"device": torch.cuda.get_device_name(0)})
 
 
 if __name__ == "__main__":

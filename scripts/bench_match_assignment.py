@@ -6,31 +6,18 @@ interleaved in one process and the medians of 30 device-synchronised wall times 
 to --out, default profiles/match_assignment_bench.jsonl).  No time is asserted anywhere."""
 from __future__ import annotations
 
-import argparse
-import json
 import os
 import sys
-import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+from scripts.benchlib import interleaved, parser, us_fields, write_rows  # noqa: E402
+
 SIZES = (300, 1024, 2048)
 DIM = 256
-
-
-def timed(torch, fn, repeats, warmup):
-    out = []
-    for i in range(repeats + warmup):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        if i >= warmup:
-            out.append(time.perf_counter() - t0)
-    return out
 
 
 def torch_assign(torch, a, b, weights, scale):
@@ -64,14 +51,7 @@ def torch_match(torch, scores, min_score):
     return torch.where(mutual, idx0, torch.full_like(idx0, -1)).int(), mutual.to(torch.uint8)
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--repeats", type=int, default=30)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "match_assignment_bench.jsonl"))
-    args = ap.parse_args()
-    import torch
-
+def rows(args, torch):
     import feature_tracker_amd as F
 
     rng = np.random.default_rng(1)
@@ -82,7 +62,6 @@ def main():
     sd = {"log_assignment.8.final_proj.weight": fw, "log_assignment.8.final_proj.bias": fb, "log_assignment.8.matchability.weight": mw,
           "log_assignment.8.matchability.bias": mb}
     heads = {True: F.MatchAssignment.from_state_dict(sd), False: F.MatchAssignment.without_weights(DIM)}
-    rows = []
     for size in SIZES:
         x = rng.standard_normal((size, DIM))
         y = x[rng.permutation(size)] + 0.3 * rng.standard_normal((size, DIM))
@@ -94,24 +73,20 @@ def main():
             calls = {"assign": lambda: head.assign(a, b), "match": lambda: head.match(a, b, min_score=-20.0),
                      "torch_assign": lambda: torch_assign(torch, a, b, weights, head.scale),
                      "torch_match": lambda: torch_match(torch, torch_assign(torch, a, b, weights, head.scale), -20.0)}
-            times = {label: [] for label in calls}
-            for _ in range(3):  # interleaved rounds
-                for label, fn in calls.items():
-                    times[label] += timed(torch, fn, args.repeats // 3, args.warmup)
+            times = interleaved(torch, calls, args.repeats, args.warmup)
             _, index, _ = head.match(a, b, min_score=-20.0)
             row = {"bench": "match_assignment", "rows": size, "dim": DIM, "with_weights": with_weights, "matches": int((index >= 0).sum().item()),
                    "max_abs_difference_to_torch": float((head.assign(a, b)[:size, :size] - torch_assign(torch, a, b, weights, head.scale)[:size, :size]).abs().max().item())}
             for label in calls:
-                row[f"{label}_us_median"] = round(1e6 * float(np.median(times[label])), 1)
-                row[f"{label}_us_min"] = round(1e6 * float(np.min(times[label])), 1)
-            rows.append(row)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    for row in rows:
-        row["device"] = torch.cuda.get_device_name(0)
-        line = json.dumps(row)
-        print(line, flush=True)
-        with open(args.out, "a") as f:
-            f.write(line + "\n")
+                us_fields(row, label, times[label])
+            yield row
+
+
+def main():
+    args = parser("--repeats", 30, 5, os.path.join(ROOT, "profiles", "match_assignment_bench.jsonl")).parse_args()
+    import torch
+
+    write_rows(rows(args, torch), args.out, append=True, extra={"device": torch.cuda.get_device_name(0)})
 
 
 if __name__ == "__main__":

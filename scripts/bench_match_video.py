@@ -11,38 +11,22 @@ Random weights give arbitrary matches: the rows compare the cost of the two loop
 shape (appended to --out when given)."""
 from __future__ import annotations
 
-import argparse
-import json
 import os
 import sys
-import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from scripts.bench_superpoint import WIDTHS, make_state  # noqa: E402
-from scripts.bench_transformer_layer import HEADS, state_dict  # noqa: E402
+from scripts.bench_scenes import HEADS, WIDTHS, make_state, sequence, state_dict  # noqa: E402
+from scripts.benchlib import parser, percentiles, wall_time, write_rows  # noqa: E402
 
 SHAPES = {"euroc_752x480": (752, 480, 300), "vga_640x480": (640, 480, 1024)}
 
 
-def sequence(torch, width, height, frames):
-    from feature_tracker_amd import synth
-    big = synth.make_image_pair(width + 2 * frames, height + frames, (0.0, 0.0))[0]  # the camera moves by (2, 1) pixels a frame
-    return [torch.from_numpy(np.ascontiguousarray(big[k:k + height, 2 * k:2 * k + width]).astype(np.float32) / np.float32(255.0)).cuda() for k in range(frames)]
-
-
 def timed_frames(torch, images, frame):
-    times = []
-    for k, image in enumerate(images):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        frame(k, image)
-        torch.cuda.synchronize()
-        times.append(time.perf_counter() - t0)
-    return times
+    return [wall_time(torch, lambda: frame(k, image)) for k, image in enumerate(images)]
 
 
 def composition(F, sp, decoder, lg, size, images):
@@ -76,18 +60,10 @@ def composition(F, sp, decoder, lg, size, images):
 
 
 def spread(times, warmup):
-    us = 1e6 * np.asarray(times[warmup:])
-    return {"median": round(float(np.median(us)), 1), "p10": round(float(np.percentile(us, 10)), 1), "p90": round(float(np.percentile(us, 90)), 1)}
+    return dict(zip(("median", "p10", "p90"), (round(v, 1) for v in percentiles(1e6 * np.asarray(times[warmup:])))))
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--frames", type=int, default=30)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "match_video_bench.jsonl"))
-    args = ap.parse_args()
-    import torch
-
+def rows(args, torch):
     import feature_tracker_amd as F
     from feature_tracker_amd._device_match_table import match_table_query_args, match_table_update_args
     from feature_tracker_amd._torch_call import call, context_of
@@ -95,7 +71,7 @@ def main():
     sp = F.SuperPoint.from_state_dict(make_state(torch, WIDTHS, 1))
     sd = state_dict(torch, np.random.default_rng(1))
     for name, (width, height, n) in SHAPES.items():
-        images = sequence(torch, width, height, args.frames + args.warmup)
+        images = [torch.from_numpy(i.astype(np.float32) / np.float32(255.0)).cuda() for i in sequence(width, height, args.frames + args.warmup)]
         decoder = F.KeypointDecoder(max_keypoints=n, min_score=0.0, min_distance=4, border=4)  # seeded weights: every score is near 1 / 65
         tracker = F.MatchVideoTracker(F.LightGlue.from_state_dict(sd, num_heads=HEADS), n, max_lost=2, detector=(sp, decoder))
         t_tracker = timed_frames(torch, images, lambda k, image: tracker.track(image))
@@ -119,12 +95,14 @@ def main():
                "tracker_us": spread(t_tracker, args.warmup), "composition_us": spread(t_composition, args.warmup), "table_us": spread(t_table, args.warmup),
                "tracker_live": int(tracker.n_live.item()), "composition_live": len(ids), "device": torch.cuda.get_device_name(0)}
         row["speedup"] = round(row["composition_us"]["median"] / row["tracker_us"]["median"], 2)
-        line = json.dumps(row)
-        print(line, flush=True)
-        if args.out:
-            os.makedirs(os.path.dirname(args.out), exist_ok=True)
-            with open(args.out, "a") as f:
-                f.write(line + "\n")
+        yield row
+
+
+def main():
+    args = parser("--frames", 30, 5, os.path.join(ROOT, "profiles", "match_video_bench.jsonl")).parse_args()
+    import torch
+
+    write_rows(rows(args, torch), args.out, append=True)
 
 
 if __name__ == "__main__":

@@ -15,8 +15,6 @@ Fields:
   torch_us           the same step with stock torch ops on the same device, same run: max over dim 1 and 0, gather, arange, two
                      compares, where (same results: checked).
 """
-import argparse
-import json
 import os
 import sys
 
@@ -28,6 +26,7 @@ import feature_tracker_amd as F  # noqa: E402
 from feature_tracker_amd import _native  # noqa: E402
 from feature_tracker_amd import device as D  # noqa: E402
 from feature_tracker_amd.raft import _context  # noqa: E402
+from scripts.benchlib import parser, write_rows  # noqa: E402
 
 HBM_PEAK = 8.0e12
 SHAPES = [("300", 300, 300, 0), ("1024", 1024, 1024, 0), ("2048", 2048, 2048, 0), ("4096", 4096, 4096, 0), ("2048_view_of_2049", 2048, 2048, 1)]
@@ -43,20 +42,11 @@ def torch_step(torch, s, min_score):
     return torch.where(ok, row_best, torch.full_like(row_best, -1))
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--calls", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--cold-calls", type=int, default=10)
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
-    import torch
-
+def rows(args, torch):
     dev = torch.device("cuda")
     build = _native.build_info().get("source_hash", "?")
     m = F.NNFeatureMatcher()
     flush = torch.empty(1 << 28, dtype=torch.float32, device=dev)  # 1 GiB: four times the Infinity Cache
-    rows = []
 
     def back_to_back(fn):
         for _ in range(args.warmup):
@@ -105,12 +95,16 @@ def main():
                "gbps": round(nbytes / us / 1e3, 1), "hbm_frac": round(nbytes / (us * 1e-6) / HBM_PEAK, 3),
                "cold_gbps": round(nbytes / c_us / 1e3, 1), "cold_hbm_frac": round(nbytes / (c_us * 1e-6) / HBM_PEAK, 3),
                "same_as_torch_on_distinct_scores": same, "build": build}
-        print(json.dumps(row), flush=True)
-        rows.append(row)
-    if args.out:
-        with open(args.out, "w") as f:
-            for row in rows:
-                f.write(json.dumps(row) + "\n")
+        yield row
+
+
+def main():
+    ap = parser("--calls", 200, 20)
+    ap.add_argument("--cold-calls", type=int, default=10)
+    args = ap.parse_args()
+    import torch
+
+    write_rows(rows(args, torch), args.out, append=False)
 
 
 if __name__ == "__main__":

@@ -6,8 +6,6 @@ profiles/pnp_bench.jsonl).  ``--sample dlt6,p3p`` times both samplers of DESIGN.
 per shape and sampler, with a ``sample`` field.  No time is asserted anywhere."""
 from __future__ import annotations
 
-import argparse
-import json
 import os
 import sys
 
@@ -16,25 +14,8 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-K = (512.0, 512.0, 319.5, 239.5)
-IMAGE = (480, 640)
-
-
-def scene(n, seed=1, outlier_share=0.3, noise=0.3):
-    """n landmarks 4.5 to 7.5 deep seen by a camera a small motion away, 0.3 px noise, 30 % of the pixels redrawn: (landmarks, uv)."""
-    rng = np.random.default_rng(seed)
-    fx, fy, cx, cy = K
-    a = np.array([0.03, -0.05, 0.02])
-    Rx = np.array([[1, 0, 0], [0, np.cos(a[0]), -np.sin(a[0])], [0, np.sin(a[0]), np.cos(a[0])]])
-    Ry = np.array([[np.cos(a[1]), 0, np.sin(a[1])], [0, 1, 0], [-np.sin(a[1]), 0, np.cos(a[1])]])
-    Rz = np.array([[np.cos(a[2]), -np.sin(a[2]), 0], [np.sin(a[2]), np.cos(a[2]), 0], [0, 0, 1]])
-    R, t = Rz @ Ry @ Rx, np.array([0.5, 0.1, 0.15])
-    X = np.array([0.0, 0.0, 6.0]) + rng.uniform(-1.5, 1.5, (n, 3))
-    Y = X @ R.T + t
-    uv = np.c_[fx * Y[:, 0] / Y[:, 2] + cx, fy * Y[:, 1] / Y[:, 2] + cy] + rng.normal(0.0, noise, (n, 2))
-    out = rng.permutation(n)[:int(round(n * outlier_share))]
-    uv[out] = rng.uniform([5, 5], [IMAGE[1] - 5, IMAGE[0] - 5], (len(out), 2))
-    return X.astype(np.float32), uv.astype(np.float32)
+from scripts.bench_scenes import K, landmark_scene  # noqa: E402
+from scripts.benchlib import interleaved, parser, us_fields, write_rows  # noqa: E402
 
 
 def torch_pnp(torch, X, uv, status, samples, threshold, refine):
@@ -85,39 +66,15 @@ def torch_pnp(torch, X, uv, status, samples, threshold, refine):
     return Rrc, p
 
 
-def timed(torch, fn, repeats, warmup):
-    import time
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(repeats):
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        out.append(time.perf_counter() - t0)
-    return out
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--repeats", type=int, default=30)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pnp_bench.jsonl"))
-    ap.add_argument("--sample", default="dlt6", help="the samplers to time in the same rounds, comma-separated: dlt6, p3p")
-    args = ap.parse_args()
-    samples_timed = args.sample.split(",")
-    import torch
-
+def rows(args, torch):
     import feature_tracker_amd as F
 
-    rows = []
     for n in (300, 2000):
-        X, uv = scene(n)
+        X, uv = landmark_scene(n)
         d_X, d_uv = torch.from_numpy(X).cuda(), torch.from_numpy(uv).cuda()
         fresh = torch.ones(n, dtype=torch.uint8, device="cuda")
         for hypotheses in (512, 2048):
-            pnps = {name: F.PnpRansac(K, hypotheses=hypotheses, threshold=1.0, refine_iterations=4, seed=1, sample=name) for name in samples_timed}
+            pnps = {name: F.PnpRansac(K, hypotheses=hypotheses, threshold=1.0, refine_iterations=4, seed=1, sample=name) for name in args.sample.split(",")}
             status = fresh.clone()
             samples = torch.from_numpy(np.stack([np.random.default_rng(h).permutation(n)[:6] for h in range(hypotheses)])).cuda()
 
@@ -131,25 +88,23 @@ def main():
 
             calls = {name: (lambda pnp=pnp: solve(pnp)) for name, pnp in pnps.items()}
             calls["torch_solve"] = torch_solve
-            times = {name: [] for name in calls}
-            for _ in range(3):  # interleaved rounds
-                for name, fn in calls.items():
-                    times[name] += timed(torch, fn, args.repeats // 3, args.warmup)
+            times = interleaved(torch, calls, args.repeats, args.warmup)
             for sample, pnp in pnps.items():
                 fit = solve(pnp)
                 row = {"bench": "pnp", "sample": sample, "points": n, "hypotheses": hypotheses, "refine_iterations": 4, "launches": 13,
                        "n_inliers": int(fit.n_inliers.item()), "valid": int(fit.valid.item())}
-                for name, key in ((sample, "solve"), ("torch_solve", "torch_solve")):
-                    row[f"{key}_us_median"] = round(1e6 * float(np.median(times[name])), 1)
-                    row[f"{key}_us_min"] = round(1e6 * float(np.min(times[name])), 1)
-                rows.append(row)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    for row in rows:
-        row["device"] = torch.cuda.get_device_name(0)
-        line = json.dumps(row)
-        print(line, flush=True)
-        with open(args.out, "a") as f:
-            f.write(line + "\n")
+                us_fields(row, "solve", times[sample])
+                us_fields(row, "torch_solve", times["torch_solve"])
+                yield row
+
+
+def main():
+    ap = parser("--repeats", 30, 5, os.path.join(ROOT, "profiles", "pnp_bench.jsonl"))
+    ap.add_argument("--sample", default="dlt6", help="the samplers to time in the same rounds, comma-separated: dlt6, p3p")
+    args = ap.parse_args()
+    import torch
+
+    write_rows(rows(args, torch), args.out, append=True, extra={"device": torch.cuda.get_device_name(0)})
 
 
 if __name__ == "__main__":

@@ -15,51 +15,19 @@ JSON line per row (`row`: "feature_encoder" over the two stacked images, or "for
   fused_speedup_vs_torch              torch over fused
   max_abs_vs_torch                    largest |difference| (the two sum in different orders)
 """
-import argparse
-import json
 import os
 import sys
-
-import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import feature_tracker_amd as F  # noqa: E402
 from feature_tracker_amd import _native  # noqa: E402
+from scripts.bench_scenes import RAFT_SHAPES as SHAPES  # noqa: E402
+from scripts.benchlib import event_times, ms_fields, parser, write_rows  # noqa: E402
 from tests.test_raft_encoder_cpu import make_image, make_raft_state, torch_encoder, torch_raft  # noqa: E402
 
-# (name, (hidden, feature, context, levels, radius, corr_hidden, corr_out, flow_hidden, flow_out, motion_out, mask_hidden), B, H, W, iterations)
-SHAPES = [("model_py_60x60", (64, 128, 128, 3, 3, 64, 32, 32, 16, 32, 64), 5, 60, 60, 5),
-          ("raft_440x1024", (128, 256, 128, 4, 4, 256, 192, 128, 64, 128, 256), 1, 440, 1024, 12)]
 
-
-def time_gpu(torch, fn, calls, warmup):
-    for _ in range(max(warmup, 1)):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(calls):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return float(np.median(ms)), float(np.percentile(ms, 10)), float(np.percentile(ms, 90))
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--calls", type=int, default=30)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--shapes", default=",".join(s[0] for s in SHAPES))
-    args = ap.parse_args()
-    import torch
-
-    assert torch.cuda.is_available(), "bench_raft.py needs a HIP device"
-    info = _native.build_info()
-    lines = []
+def rows(args, torch):
     for name, widths, B, H, W, iterations in SHAPES:
         if name not in args.shapes.split(","):
             continue
@@ -68,27 +36,31 @@ def main():
         model = F.Raft.from_state_dict(state, widths[3], widths[4], max_iterations=iterations)
         stacked = torch.cat([ref_image, cur_image], 0)
         normalised = 2.0 * (stacked / 255.0) - 1.0
-        rows = {
+        pairs = {
             "feature_encoder": (lambda: model.feature_encoder(stacked, normalise=True),
                                 lambda: torch_encoder(state, normalised, "feature_encoder.", torch.float32)),
             "forward": (lambda: model(ref_image, cur_image)[-1],
                         lambda: torch_raft(state, ref_image, cur_image, widths[3], widths[4], iterations, torch.float32)[-1]),
         }
         with torch.no_grad():
-            for row, (fused, stock) in rows.items():
-                f_ms = time_gpu(torch, fused, args.calls, args.warmup)
-                t_ms = time_gpu(torch, stock, args.calls, args.warmup)
-                line = dict(shape=name, row=row, B=B, H=H, W=W, iterations=iterations, widths=list(widths), calls=args.calls,
-                            fused_ms=f_ms[0], fused_ms_p10=f_ms[1], fused_ms_p90=f_ms[2], torch_ms=t_ms[0], torch_ms_p10=t_ms[1], torch_ms_p90=t_ms[2],
-                            fused_speedup_vs_torch=t_ms[0] / f_ms[0], max_abs_vs_torch=float((fused() - stock()).abs().max()),
-                            source_hash=info.get("source_hash"), device=torch.cuda.get_device_name(0))
-                lines.append(line)
-                print(json.dumps(line), flush=True)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "a") as f:
-            for line in lines:
-                f.write(json.dumps(line) + "\n")
+            for row, (fused, stock) in pairs.items():
+                f_ms = event_times(torch, [fused], args.calls, args.warmup)
+                t_ms = event_times(torch, [stock], args.calls, args.warmup)
+                line = dict(shape=name, row=row, B=B, H=H, W=W, iterations=iterations, widths=list(widths), calls=args.calls)
+                ms_fields(line, "fused", f_ms, spread=True, digits=None)
+                ms_fields(line, "torch", t_ms, spread=True, digits=None)
+                line.update(fused_speedup_vs_torch=t_ms[0] / f_ms[0], max_abs_vs_torch=float((fused() - stock()).abs().max()))
+                yield line
+
+
+def main():
+    ap = parser("--calls", 30, 5)
+    ap.add_argument("--shapes", default=",".join(s[0] for s in SHAPES))
+    args = ap.parse_args()
+    import torch
+
+    assert torch.cuda.is_available(), "bench_raft.py needs a HIP device"
+    write_rows(rows(args, torch), args.out, append=True, extra=dict(source_hash=_native.build_info().get("source_hash"), device=torch.cuda.get_device_name(0)))
 
 
 if __name__ == "__main__":

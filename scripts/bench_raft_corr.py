@@ -15,52 +15,25 @@ Fields:
   lookup_gbps                      (volume slabs touched are gathers served mostly by the caches, so this counts the compulsory
                                    bytes: coordinates read + output written) / lookup time.
 """
-import argparse
-import json
 import os
 import sys
 import time
-
-import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import feature_tracker_amd as F  # noqa: E402
 from feature_tracker_amd import _native  # noqa: E402
+from scripts.bench_scenes import CORR_SHAPES as SHAPES  # noqa: E402
+from scripts.benchlib import event_times, ms_fields, parser, write_rows  # noqa: E402
 from tests import raft_corr_ref as R  # noqa: E402
 from tests.test_raft_corr_cpu import torch_lookup, torch_pyramid  # noqa: E402
 
 F32_PEAK = 157.3e12
-SHAPES = [("eighth_example_c128", 128, 60, 94, 3, 3), ("eighth_example_c256", 256, 60, 94, 4, 4), ("raft_55x128_c256", 256, 55, 128, 4, 4)]
 
 
-def time_gpu(torch, fn, calls, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(calls):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return float(np.median(ms)), float(np.percentile(ms, 10)), float(np.percentile(ms, 90))
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--calls", type=int, default=100)
-    ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--cpu", action="store_true", help="also time the single-thread C restatement")
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
-    import torch
-
+def rows(args, torch):
     dev = torch.device("cuda")
     build = _native.build_info().get("source_hash", "?")
-    rows = []
     for name, C, H, W, L, r in SHAPES:
         g = torch.Generator().manual_seed(C * H)
         f0, f1 = torch.randn(1, C, H, W, generator=g), torch.randn(1, C, H, W, generator=g)
@@ -69,10 +42,10 @@ def main():
         with torch.no_grad():
             cp = F.CorrelationPyramid(a0, a1, L, r)
             ref = torch_pyramid(a0, a1, L)
-            b_ms = time_gpu(torch, lambda: F.CorrelationPyramid(a0, a1, L, r), args.calls, args.warmup)
-            l_ms = time_gpu(torch, lambda: cp.lookup(ac), args.calls, args.warmup)
-            tb_ms = time_gpu(torch, lambda: torch_pyramid(a0, a1, L), args.calls, args.warmup)
-            tl_ms = time_gpu(torch, lambda: torch_lookup(ref, ac, r), args.calls, args.warmup)
+            b_ms = event_times(torch, [lambda: F.CorrelationPyramid(a0, a1, L, r)], args.calls, args.warmup)
+            l_ms = event_times(torch, [lambda: cp.lookup(ac)], args.calls, args.warmup)
+            tb_ms = event_times(torch, [lambda: torch_pyramid(a0, a1, L)], args.calls, args.warmup)
+            tl_ms = event_times(torch, [lambda: torch_lookup(ref, ac, r)], args.calls, args.warmup)
             out = cp.lookup(ac)
         want = R.build(f0.numpy(), f1.numpy(), L)
         identical = all(R.same(cp.correlation_pyramid[l][:, 0].cpu().numpy(), want[l]) for l in range(L))
@@ -82,14 +55,15 @@ def main():
         K = (2 * r + 1) ** 2
         lookup_bytes = 4 * (2 * HW + L * K * HW)
         elements, _, _ = _native.corr_pyramid_layout(1, H, W, L)
-        row = {"shape": name, "B": 1, "C": C, "H": H, "W": W, "levels": L, "radius": r,
-               "build_ms": round(b_ms[0], 4), "build_ms_p10": round(b_ms[1], 4), "build_ms_p90": round(b_ms[2], 4),
-               "lookup_ms": round(l_ms[0], 4), "lookup_ms_p10": round(l_ms[1], 4), "lookup_ms_p90": round(l_ms[2], 4),
-               "torch_build_ms": round(tb_ms[0], 4), "torch_lookup_ms": round(tl_ms[0], 4),
-               "build_vs_torch": round(b_ms[0] / tb_ms[0], 3), "lookup_speedup_vs_torch": round(tl_ms[0] / l_ms[0], 2),
-               "build_tflops": round(flop / (b_ms[0] * 1e-3) / 1e12, 2), "floor_us": round(flop / F32_PEAK * 1e6, 1),
-               "volume_bytes": 4 * elements, "level0_bytes": 4 * HW * HW,
-               "lookup_gbps": round(lookup_bytes / (l_ms[0] * 1e-3) / 1e9, 1), "identical_to_restatement": bool(identical), "build": build}
+        row = {"shape": name, "B": 1, "C": C, "H": H, "W": W, "levels": L, "radius": r}
+        ms_fields(row, "build", b_ms, spread=True)
+        ms_fields(row, "lookup", l_ms, spread=True)
+        ms_fields(row, "torch_build", tb_ms)
+        ms_fields(row, "torch_lookup", tl_ms)
+        row.update({"build_vs_torch": round(b_ms[0] / tb_ms[0], 3), "lookup_speedup_vs_torch": round(tl_ms[0] / l_ms[0], 2),
+                    "build_tflops": round(flop / (b_ms[0] * 1e-3) / 1e12, 2), "floor_us": round(flop / F32_PEAK * 1e6, 1),
+                    "volume_bytes": 4 * elements, "level0_bytes": 4 * HW * HW,
+                    "lookup_gbps": round(lookup_bytes / (l_ms[0] * 1e-3) / 1e9, 1), "identical_to_restatement": bool(identical), "build": build})
         if args.cpu:
             t = time.perf_counter()
             R.build(f0.numpy(), f1.numpy(), L)
@@ -98,14 +72,18 @@ def main():
             R.lookup(want, coords.numpy(), r)
             row["cpu_lookup_ms"] = round((time.perf_counter() - t) * 1e3, 2)
             row["cpu_note"] = "single-thread C restatement (tests/raft_corr_ref.c, gcc -O3), not the reference's time"
-        print(json.dumps(row), flush=True)
-        rows.append(row)
+        yield row
         del cp, ref, out
         torch.cuda.empty_cache()
-    if args.out:
-        with open(args.out, "w") as f:
-            for row in rows:
-                f.write(json.dumps(row) + "\n")
+
+
+def main():
+    ap = parser("--calls", 100, 10)
+    ap.add_argument("--cpu", action="store_true", help="also time the single-thread C restatement")
+    args = ap.parse_args()
+    import torch
+
+    write_rows(rows(args, torch), args.out, append=False)
 
 
 if __name__ == "__main__":

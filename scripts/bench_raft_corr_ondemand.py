@@ -15,50 +15,23 @@ after --warmup.
   level0_identical                 the level-0 channels of the two lookups are bit-identical (where both ran)
 Model rows (`row`: "forward"): the whole Raft of scripts/bench_raft.py's two shapes, once per mode (`correlation`), `forward_ms`.
 """
-import argparse
-import json
 import os
 import sys
-
-import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import feature_tracker_amd as F  # noqa: E402
 from feature_tracker_amd import _native  # noqa: E402
-from scripts.bench_raft import SHAPES as MODEL_SHAPES  # noqa: E402
-from scripts.bench_raft_corr import SHAPES as CORR_SHAPES  # noqa: E402
-from scripts.bench_raft_corr import time_gpu  # noqa: E402
+from scripts.bench_scenes import CORR_SHAPES  # noqa: E402
+from scripts.bench_scenes import RAFT_SHAPES as MODEL_SHAPES  # noqa: E402
+from scripts.benchlib import event_times, ms_fields, parser, write_rows  # noqa: E402
 from tests.test_raft_encoder_cpu import make_image, make_raft_state  # noqa: E402
 
 SHAPES = CORR_SHAPES + [("features_of_1080p_c256", 256, 135, 240, 4, 4)]
 
 
-def stats(prefix, ms):
-    return {prefix: round(ms[0], 4), prefix + "_p10": round(ms[1], 4), prefix + "_p90": round(ms[2], 4)}
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--calls", type=int, default=50)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--iterations", type=int, default=12)
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--no-models", action="store_true", help="skip the whole-Raft rows")
-    args = ap.parse_args()
-    import torch
-
-    assert torch.cuda.is_available(), "bench_raft_corr_ondemand.py needs a HIP device"
+def rows(args, torch):
     dev = torch.device("cuda")
-    build = _native.build_info().get("source_hash", "?")
-    device_name = torch.cuda.get_device_name(0)
-    rows = []
-
-    def emit(row):
-        row.update(build=build, device=device_name, calls=args.calls)
-        print(json.dumps(row), flush=True)
-        rows.append(row)
-
     n = args.iterations
     for name, C, H, W, L, r in SHAPES:
         g = torch.Generator().manual_seed(C * H)
@@ -68,19 +41,19 @@ def main():
         row = {"row": "correlation", "shape": name, "B": 1, "C": C, "H": H, "W": W, "levels": L, "radius": r, "iterations": n}
         with torch.no_grad():
             od = F.OnDemandCorrelation(f0, f1, L, r)
-            p_ms = time_gpu(torch, lambda: F.OnDemandCorrelation(f0, f1, L, r), args.calls, args.warmup)
-            l_ms = time_gpu(torch, lambda: od.lookup(coords), args.calls, args.warmup)
-            row.update(stats("prepare_ms", p_ms))
-            row.update(stats("lookup_ms", l_ms))
+            p_ms = event_times(torch, [lambda: F.OnDemandCorrelation(f0, f1, L, r)], args.calls, args.warmup)
+            l_ms = event_times(torch, [lambda: od.lookup(coords)], args.calls, args.warmup)
+            ms_fields(row, "prepare", p_ms, spread=True)
+            ms_fields(row, "lookup", l_ms, spread=True)
             row.update(workspace_bytes=od.workspace_bytes, on_demand_total_ms=round(p_ms[0] + n * l_ms[0], 4))
             mine = od.lookup(coords)[:, :K].clone()
             row["volume_bytes"] = 4 * _native.corr_pyramid_layout(1, H, W, L)[0]
             try:
                 cp = F.CorrelationPyramid(f0, f1, L, r)
-                b_ms = time_gpu(torch, lambda: F.CorrelationPyramid(f0, f1, L, r), args.calls, args.warmup)
-                a_ms = time_gpu(torch, lambda: cp.lookup(coords), args.calls, args.warmup)
-                row.update(stats("build_ms", b_ms))
-                row.update(stats("all_pairs_lookup_ms", a_ms))
+                b_ms = event_times(torch, [lambda: F.CorrelationPyramid(f0, f1, L, r)], args.calls, args.warmup)
+                a_ms = event_times(torch, [lambda: cp.lookup(coords)], args.calls, args.warmup)
+                ms_fields(row, "build", b_ms, spread=True)
+                ms_fields(row, "all_pairs_lookup", a_ms, spread=True)
                 row["all_pairs_total_ms"] = round(b_ms[0] + n * a_ms[0], 4)
                 row["on_demand_over_all_pairs"] = round(row["on_demand_total_ms"] / row["all_pairs_total_ms"], 3)
                 row["level0_identical"] = bool(torch.equal(mine.view(torch.int32), cp.lookup(coords)[:, :K].view(torch.int32)))
@@ -89,7 +62,7 @@ def main():
                 row["all_pairs_error"] = str(e).splitlines()[0][:200]
             del od
         torch.cuda.empty_cache()
-        emit(row)
+        yield row
     if not args.no_models:
         for name, widths, B, H, W, iterations in MODEL_SHAPES:
             state = {k: v.to(dev) for k, v in make_raft_state(widths, 1).items()}
@@ -98,20 +71,27 @@ def main():
             for mode in ("all_pairs", "on_demand"):
                 model = F.Raft.from_state_dict(state, widths[3], widths[4], max_iterations=iterations, correlation=mode)
                 with torch.no_grad():
-                    ms = time_gpu(torch, lambda: model(ref_image, cur_image)[-1], max(args.calls // 2, 5), args.warmup)
+                    ms = event_times(torch, [lambda: model(ref_image, cur_image)[-1]], max(args.calls // 2, 5), args.warmup)
                     last[mode] = model(ref_image, cur_image)[-1]
                 row = {"row": "forward", "shape": name, "correlation": mode, "B": B, "H": H, "W": W, "iterations": iterations, "widths": list(widths)}
-                row.update(stats("forward_ms", ms))
+                ms_fields(row, "forward", ms, spread=True)
                 if mode == "on_demand":
                     row["max_abs_between_modes"] = float((last["on_demand"] - last["all_pairs"]).abs().max())
-                emit(row)
+                yield row
             del state, last
             torch.cuda.empty_cache()
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            for row in rows:
-                f.write(json.dumps(row) + "\n")
+
+
+def main():
+    ap = parser("--calls", 50, 5)
+    ap.add_argument("--iterations", type=int, default=12)
+    ap.add_argument("--no-models", action="store_true", help="skip the whole-Raft rows")
+    args = ap.parse_args()
+    import torch
+
+    assert torch.cuda.is_available(), "bench_raft_corr_ondemand.py needs a HIP device"
+    extra = dict(build=_native.build_info().get("source_hash", "?"), device=torch.cuda.get_device_name(0), calls=args.calls)
+    write_rows(rows(args, torch), args.out, append=False, extra=extra)
 
 
 if __name__ == "__main__":

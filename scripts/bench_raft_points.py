@@ -14,18 +14,15 @@ with a pair of events after a warm-up, median / p10 / p90 of `calls` calls; floa
 with new_ms, old_ms (and their p10 / p90), old_over_new, and max_abs_points: the largest distance between the two routes' tracked
 points (grid_sample's interpolation arithmetic is torch's own).
 """
-import argparse
-import json
 import os
 import sys
-
-import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import feature_tracker_amd as F  # noqa: E402
 from feature_tracker_amd import _native  # noqa: E402
-from scripts.bench_raft import SHAPES, time_gpu  # noqa: E402
+from scripts.bench_scenes import RAFT_SHAPES as SHAPES  # noqa: E402
+from scripts.benchlib import event_times, ms_fields, parser, write_rows  # noqa: E402
 from tests.test_raft_encoder_cpu import make_image, make_raft_state  # noqa: E402
 
 POINT_COUNTS = (300, 2000)
@@ -44,18 +41,7 @@ def torch_sample(torch, dense, points, H, W):
     return cur, inside(points) & inside(cur) & torch.isfinite(cur).all(-1)
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--calls", type=int, default=30)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--shapes", default=",".join(s[0] for s in SHAPES))
-    args = ap.parse_args()
-    import torch
-
-    assert torch.cuda.is_available(), "bench_raft_points.py needs a HIP device"
-    info = _native.build_info()
-    lines = []
+def rows(args, torch):
     for name, widths, B, H, W, iterations in SHAPES:
         if name not in args.shapes.split(","):
             continue
@@ -73,29 +59,33 @@ def main():
                 back, ok_back = torch_sample(torch, model(cur_image, ref_image)[-1], cur.clamp(min=0).minimum(points.new_tensor([W - 1.0, H - 1.0])), H, W)
                 return cur, ok & (((back - points) ** 2).sum(-1) <= 1.0)
 
-            rows = {
+            pairs = {
                 "track_points": (lambda: model.track_points(ref_image, cur_image, points), lambda: torch_sample(torch, model(ref_image, cur_image)[-1], points, H, W)),
                 "track_points_fb": (lambda: model.track_points(ref_image, cur_image, points, forward_backward=1.0), old_fb),
                 "kernel": (lambda: F.track_points_from_flow(flow, mask, points, (H, W)), lambda: torch_sample(torch, F.upsample_flow(flow, mask), points, H, W)),
             }
             with torch.no_grad():
-                for row, (new, old) in rows.items():
-                    n_ms = time_gpu(torch, new, args.calls, args.warmup)
-                    o_ms = time_gpu(torch, old, args.calls, args.warmup)
+                for row, (new, old) in pairs.items():
+                    n_ms = event_times(torch, [new], args.calls, args.warmup)
+                    o_ms = event_times(torch, [old], args.calls, args.warmup)
                     got, want = new(), old()
                     both = (got[1] == F.TRACKED) & want[1]
-                    line = dict(shape=name, row=row, points=count, B=B, H=H, W=W, iterations=iterations, widths=list(widths), calls=args.calls,
-                                new_ms=n_ms[0], new_ms_p10=n_ms[1], new_ms_p90=n_ms[2], old_ms=o_ms[0], old_ms_p10=o_ms[1], old_ms_p90=o_ms[2],
-                                old_over_new=o_ms[0] / n_ms[0], tracked=int((got[1] == F.TRACKED).sum()),
-                                max_abs_points=float((got[0] - want[0])[both].abs().max()) if bool(both.any()) else None,
-                                source_hash=info.get("source_hash"), device=torch.cuda.get_device_name(0))
-                    lines.append(line)
-                    print(json.dumps(line), flush=True)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "a") as f:
-            for line in lines:
-                f.write(json.dumps(line) + "\n")
+                    line = dict(shape=name, row=row, points=count, B=B, H=H, W=W, iterations=iterations, widths=list(widths), calls=args.calls)
+                    ms_fields(line, "new", n_ms, spread=True, digits=None)
+                    ms_fields(line, "old", o_ms, spread=True, digits=None)
+                    line.update(old_over_new=o_ms[0] / n_ms[0], tracked=int((got[1] == F.TRACKED).sum()),
+                                max_abs_points=float((got[0] - want[0])[both].abs().max()) if bool(both.any()) else None)
+                    yield line
+
+
+def main():
+    ap = parser("--calls", 30, 5)
+    ap.add_argument("--shapes", default=",".join(s[0] for s in SHAPES))
+    args = ap.parse_args()
+    import torch
+
+    assert torch.cuda.is_available(), "bench_raft_points.py needs a HIP device"
+    write_rows(rows(args, torch), args.out, append=True, extra=dict(source_hash=_native.build_info().get("source_hash"), device=torch.cuda.get_device_name(0)))
 
 
 if __name__ == "__main__":

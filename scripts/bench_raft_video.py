@@ -13,8 +13,6 @@ on its own with a pair of events after a warm-up, median / p10 / p90 of `calls` 
                              form (`splits`, `launches`), the one-launch form forced, and upstream's forward_interpolate per entry with the
                              copies to the host and back (host_ms; null without scipy)
 """
-import argparse
-import json
 import os
 import sys
 
@@ -26,7 +24,8 @@ import feature_tracker_amd as F  # noqa: E402
 from feature_tracker_amd import _native  # noqa: E402
 from feature_tracker_amd import device as D  # noqa: E402
 from feature_tracker_amd import raft as R  # noqa: E402
-from scripts.bench_raft import SHAPES, time_gpu  # noqa: E402
+from scripts.bench_scenes import RAFT_SHAPES as SHAPES  # noqa: E402
+from scripts.benchlib import event_times, ms_fields, parser, write_rows  # noqa: E402
 from tests.test_raft_encoder_cpu import make_image, make_raft_state  # noqa: E402
 
 POINTS = 300
@@ -50,26 +49,7 @@ def forward_interpolate(flow):
     return np.stack([flow_x, flow_y], axis=0).astype(np.float32)
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--calls", type=int, default=30)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--shapes", default=",".join(s[0] for s in SHAPES))
-    ap.add_argument("--no-warm-start-rows", action="store_true")
-    args = ap.parse_args()
-    import torch
-
-    assert torch.cuda.is_available(), "bench_raft_video.py needs a HIP device"
-    info = _native.build_info()
-    common = dict(calls=args.calls, source_hash=info.get("source_hash"), device=torch.cuda.get_device_name(0))
-    lines = []
-
-    def emit(**line):
-        line.update(common)
-        lines.append(line)
-        print(json.dumps(line), flush=True)
-
+def rows(args, torch):
     for name, widths, B, H, W, iterations in SHAPES:
         if name not in args.shapes.split(","):
             continue
@@ -92,20 +72,21 @@ def main():
 
         trackers = {"video_cold": F.RaftVideoTracker(model, warm_start=False), "video_warm": F.RaftVideoTracker(model),
                     "video_warm_fb": F.RaftVideoTracker(model, forward_backward=1.0)}
-        rows = {"pairwise": lambda: pairwise(), "pairwise_fb": lambda: pairwise(1.0)}
+        steps = {"pairwise": lambda: pairwise(), "pairwise_fb": lambda: pairwise(1.0)}
         with torch.no_grad():
             for row, tracker in trackers.items():
                 tracker.track(ring[0])
-                rows[row] = video(tracker)
+                steps[row] = video(tracker)
             # two passes, alternating the rows, so that a drift of the machine falls on all of them
-            timed = {row: [] for row in rows}
+            timed = {row: [] for row in steps}
             for _ in range(2):
-                for row, fn in rows.items():
-                    timed[row].append(time_gpu(torch, fn, args.calls, args.warmup))
+                for row, fn in steps.items():
+                    timed[row].append(event_times(torch, [fn], args.calls, args.warmup))
         for row, passes in timed.items():
             ms = min(passes)
-            emit(shape=name, row=row, points=POINTS, B=B, H=H, W=W, iterations=iterations, widths=list(widths), ms=ms[0], ms_p10=ms[1], ms_p90=ms[2],
-                 ms_passes=[p[0] for p in passes], over_pairwise=ms[0] / min(timed["pairwise_fb" if row.endswith("_fb") else "pairwise"])[0])
+            line = dict(shape=name, row=row, points=POINTS, B=B, H=H, W=W, iterations=iterations, widths=list(widths), ms=ms[0], ms_p10=ms[1], ms_p90=ms[2],
+                        ms_passes=[p[0] for p in passes], over_pairwise=ms[0] / min(timed["pairwise_fb" if row.endswith("_fb") else "pairwise"])[0])
+            yield line
 
     if not args.no_warm_start_rows:
         try:
@@ -125,18 +106,26 @@ def main():
                     return torch.from_numpy(np.stack([forward_interpolate(f[b]) for b in range(B)])).to("cuda")
 
                 with torch.no_grad():
-                    auto = time_gpu(torch, lambda: F.warm_start_flow(flow), args.calls, args.warmup)
-                    one = time_gpu(torch, lambda: D.flow_warm_device(ctx, flow, out, 1), args.calls, args.warmup)
-                    host_ms = time_gpu(torch, host, args.calls, 1) if have_scipy else None
+                    auto = event_times(torch, [lambda: F.warm_start_flow(flow)], args.calls, args.warmup)
+                    one = event_times(torch, [lambda: D.flow_warm_device(ctx, flow, out, 1)], args.calls, args.warmup)
+                    host_ms = event_times(torch, [host], args.calls, 1) if have_scipy else None
                     same = bool(torch.equal(F.warm_start_flow(flow), host())) if have_scipy else None
-                emit(row="warm_start", B=B, H=H, W=W, splits=splits, launches=1 if splits == 1 else 2, ms=auto[0], ms_p10=auto[1], ms_p90=auto[2],
-                     one_launch_ms=one[0], one_launch_ms_p10=one[1], one_launch_ms_p90=one[2], host_ms=None if host_ms is None else host_ms[0],
-                     host_over_device=None if host_ms is None else host_ms[0] / auto[0], equal_to_host=same)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "a") as f:
-            for line in lines:
-                f.write(json.dumps(line) + "\n")
+                line = dict(row="warm_start", B=B, H=H, W=W, splits=splits, launches=1 if splits == 1 else 2, ms=auto[0], ms_p10=auto[1], ms_p90=auto[2])
+                ms_fields(line, "one_launch", one, spread=True, digits=None)
+                line.update(host_ms=None if host_ms is None else host_ms[0], host_over_device=None if host_ms is None else host_ms[0] / auto[0], equal_to_host=same)
+                yield line
+
+
+def main():
+    ap = parser("--calls", 30, 5)
+    ap.add_argument("--shapes", default=",".join(s[0] for s in SHAPES))
+    ap.add_argument("--no-warm-start-rows", action="store_true")
+    args = ap.parse_args()
+    import torch
+
+    assert torch.cuda.is_available(), "bench_raft_video.py needs a HIP device"
+    common = dict(calls=args.calls, source_hash=_native.build_info().get("source_hash"), device=torch.cuda.get_device_name(0))
+    write_rows(rows(args, torch), args.out, append=True, extra=common)
 
 
 if __name__ == "__main__":

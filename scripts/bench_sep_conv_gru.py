@@ -15,49 +15,22 @@ on both sides.  One JSON line per shape:
   fused_speedup_vs_torch[_parts]      torch over fused
   max_abs_vs_torch                    largest |difference| of the two results (they differ in summation order)
 """
-import argparse
-import json
 import os
 import sys
-
-import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import feature_tracker_amd as F  # noqa: E402
 from feature_tracker_amd import _native  # noqa: E402
+from scripts.benchlib import event_times, ms_fields, parser, write_rows  # noqa: E402
 from tests.test_sep_conv_gru_cpu import make_state, torch_forward  # noqa: E402
 
 # (name, the channels of the parts of x, h_channels, B, H, W)
 SHAPES = [("model_py_60x60", (64, 96), 64, 5, 8, 8), ("raft_55x128", (128, 128), 128, 1, 55, 128)]
 
 
-def time_gpu(torch, fn, calls, warmup):
-    for _ in range(max(warmup, 1)):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(calls):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return float(np.median(ms)), float(np.percentile(ms, 10)), float(np.percentile(ms, 90))
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--calls", type=int, default=100)
-    ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
-    import torch
-
+def rows(args, torch):
     dev = torch.device("cuda")
-    build = _native.build_info().get("source_hash", "?")
-    rows = []
     for name, part_channels, Ch, B, H, W in SHAPES:
         Cx = sum(part_channels)
         state = {k: v.to(dev) for k, v in make_state(Cx, Ch, 5, 1).items()}
@@ -66,31 +39,27 @@ def main():
         parts = [torch.randn(B, c, H, W, generator=g).to(dev) for c in part_channels]
         h = torch.randn(B, Ch, H, W, generator=g).to(dev)
         x = torch.cat(parts, 1)
+        calls = {"fused": lambda: gru(x, h), "fused_parts": lambda: gru(parts, h), "torch": lambda: torch_forward(state, x, h),
+                 "torch_parts": lambda: torch_forward(state, torch.cat(parts, 1), h)}
         with torch.no_grad():
-            t = {
-                "fused": time_gpu(torch, lambda: gru(x, h), args.calls, args.warmup),
-                "fused_parts": time_gpu(torch, lambda: gru(parts, h), args.calls, args.warmup),
-                "torch": time_gpu(torch, lambda: torch_forward(state, x, h), args.calls, args.warmup),
-                "torch_parts": time_gpu(torch, lambda: torch_forward(state, torch.cat(parts, 1), h), args.calls, args.warmup),
-            }
+            t = {key: event_times(torch, [fn], args.calls, args.warmup) for key, fn in calls.items()}
             diff = float((gru(parts, h) - torch_forward(state, x, h)).abs().max())
         row = {"shape": name, "x_parts": list(part_channels), "h_channels": Ch, "kernel_size": 5, "B": B, "H": H, "W": W}
-        for key, (med, p10, p90) in t.items():
-            row[key + "_ms"] = round(med, 4)
-            if key == "fused":
-                row["fused_ms_p10"], row["fused_ms_p90"] = round(p10, 4), round(p90, 4)
+        for key in t:
+            ms_fields(row, key, t[key], spread=key == "fused")
         row["fused_speedup_vs_torch"] = round(t["torch"][0] / t["fused"][0], 2)
         row["fused_speedup_vs_torch_parts"] = round(t["torch_parts"][0] / t["fused_parts"][0], 2)
         row["max_abs_vs_torch"] = diff
         row["flop"] = 2 * 2 * 3 * Ch * (Cx + Ch) * 5 * B * H * W
         row["fused_tflops"] = round(row["flop"] / (t["fused"][0] * 1e-3) / 1e12, 2)
-        row["build"] = build
-        print(json.dumps(row), flush=True)
-        rows.append(row)
-    if args.out:
-        with open(args.out, "w") as f:
-            for row in rows:
-                f.write(json.dumps(row) + "\n")
+        yield row
+
+
+def main():
+    args = parser("--calls", 100, 10).parse_args()
+    import torch
+
+    write_rows(rows(args, torch), args.out, append=False, extra={"build": _native.build_info().get("source_hash", "?")})
 
 
 if __name__ == "__main__":

@@ -6,19 +6,16 @@ process and the medians of device-synchronised wall times are reported, one JSON
 profiles/track_odometry_bench.jsonl).  No time is asserted anywhere; the kernels' own times are not measured here."""
 from __future__ import annotations
 
-import argparse
-import json
 import os
 import sys
-import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-K = (512.0, 512.0, 319.5, 239.5)
-IMAGE = (480, 640)
+from scripts.bench_scenes import IMAGE, K  # noqa: E402
+from scripts.benchlib import parser, us_median, wall_time, write_rows  # noqa: E402
 
 
 def sequence(n, frames, seed=1, churn=0.05, outlier_share=0.2, noise=0.3, step=0.1):
@@ -111,47 +108,30 @@ class HandOdometry:
         self.frame += 1
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--repeats", type=int, default=30)
-    ap.add_argument("--warmup", type=int, default=8)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "track_odometry_bench.jsonl"))
-    args = ap.parse_args()
-    import torch
-
+def rows(args, torch):
     import feature_tracker_amd as F
     from feature_tracker_amd import device as D
     from feature_tracker_amd import synth
 
-    def timed(fn):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        return time.perf_counter() - t0
-
-    rows = []
     for n in (300, 2000):
         seq = [(torch.from_numpy(i).cuda(), torch.from_numpy(p).cuda()) for i, p in sequence(n, args.warmup + args.repeats)]
         odo, hand = F.TrackOdometry(K, seed=0), HandOdometry(F, torch, n)
         times = {"update": [], "hand": []}
         for f, (ids, points) in enumerate(seq):
-            t_odo = timed(lambda: odo.update(ids, points, IMAGE))
+            t_odo = wall_time(torch, lambda: odo.update(ids, points, IMAGE))
             if odo.initialised and f > 0 and hand.frame == 0:  # the yardstick starts from the class's map
                 hand.owner = odo.owner.cpu().numpy().copy()
                 hand.landmarks, hand.anchor_uv, hand.anchor_pose = odo.landmarks.clone(), odo.anchor_uv.clone(), odo.anchor_pose.clone()
                 hand.anchor_frame, hand.frame = odo.anchor_frame.clone(), odo.frame
                 continue
             if hand.frame > 0:
-                t_hand = timed(lambda: hand.update(ids, points))
+                t_hand = wall_time(torch, lambda: hand.update(ids, points))
                 if f >= args.warmup:
                     times["update"].append(t_odo)
                     times["hand"].append(t_hand)
-        row = {"what": "steady_update", "slots": n, "frames": len(times["update"]), "initialised": bool(odo.initialised), "valid": int(odo.valid[0]),
+        yield {"what": "steady_update", "slots": n, "frames": len(times["update"]), "initialised": bool(odo.initialised), "valid": int(odo.valid[0]),
                "n_landmarks": int(odo.n_landmarks[0]), "launches": 15,
-               "update_us_median": round(1e6 * float(np.median(times["update"])), 1), "hand_us_median": round(1e6 * float(np.median(times["hand"])), 1)}
-        rows.append(row)
-        print(json.dumps(row))
+               "update_us_median": us_median(times["update"]), "hand_us_median": us_median(times["hand"])}
     # a KltVideoTracker frame with and without odometry (the tracker's own synthetic frames: one plane, so the odometry stays in its bootstrap)
     frames = [np.ascontiguousarray(synth.make_image_pair(640, 480, (0.7 * k, -0.4 * k))[1]) for k in range(args.warmup + args.repeats)]
     times = {}
@@ -163,16 +143,16 @@ def main():
         odo = F.TrackOdometry(K, ctx=ctx) if name.endswith("odometry") else None
         tracker = F.KltVideoTracker(flow, 300, ctx=ctx, odometry=odo)
         images = [torch.from_numpy(f).cuda() for f in frames]
-        times[name] = [timed(lambda: tracker.track(image)) for image in images][args.warmup:]
-    row = {"what": "klt_video_frame", "slots": 300, "image": [480, 640], "frames": args.repeats, "odometry_state": "bootstrap (one plane: the homography is chosen)",
-           "tracker_us_median": round(1e6 * float(np.median(times["tracker"])), 1),
-           "tracker_with_odometry_us_median": round(1e6 * float(np.median(times["tracker_with_odometry"])), 1)}
-    rows.append(row)
-    print(json.dumps(row))
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "a") as f:
-        for row in rows:
-            f.write(json.dumps(row) + "\n")
+        times[name] = [wall_time(torch, lambda: tracker.track(image)) for image in images][args.warmup:]
+    yield {"what": "klt_video_frame", "slots": 300, "image": [480, 640], "frames": args.repeats, "odometry_state": "bootstrap (one plane: the homography is chosen)",
+           "tracker_us_median": us_median(times["tracker"]), "tracker_with_odometry_us_median": us_median(times["tracker_with_odometry"])}
+
+
+def main():
+    args = parser("--repeats", 30, 8, os.path.join(ROOT, "profiles", "track_odometry_bench.jsonl")).parse_args()
+    import torch
+
+    write_rows(rows(args, torch), args.out, append=True)
 
 
 if __name__ == "__main__":

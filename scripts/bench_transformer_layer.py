@@ -6,47 +6,16 @@ default profiles/transformer_layer_bench.jsonl).  No time is asserted anywhere. 
 count, other D or h."""
 from __future__ import annotations
 
-import argparse
-import json
 import os
 import sys
-import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-SIZES = (300, 1024, 2048)
-DIM, HEADS, LAYERS = 256, 4, 9
-
-
-def timed(torch, fn, repeats, warmup):
-    out = []
-    for i in range(repeats + warmup):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        if i >= warmup:
-            out.append(time.perf_counter() - t0)
-    return out
-
-
-def state_dict(torch, rng):
-    sd, d = {}, DIM
-    lin = lambda outs, ins: (torch.from_numpy((rng.standard_normal((outs, ins)) / np.sqrt(ins)).astype(np.float32)).cuda(),  # noqa: E731
-                             torch.from_numpy((0.1 * rng.standard_normal(outs)).astype(np.float32)).cuda())
-    for i in range(LAYERS):
-        for block, names in (("self_attn", (("Wqkv", 3 * d, d), ("out_proj", d, d))), ("cross_attn", (("to_qk", d, d), ("to_v", d, d), ("to_out", d, d)))):
-            for name, outs, ins in names + (("ffn.0", 2 * d, 2 * d), ("ffn.3", d, 2 * d)):
-                sd[f"transformers.{i}.{block}.{name}.weight"], sd[f"transformers.{i}.{block}.{name}.bias"] = lin(outs, ins)
-            sd[f"transformers.{i}.{block}.ffn.1.weight"], sd[f"transformers.{i}.{block}.ffn.1.bias"] = torch.ones(2 * d).cuda(), torch.zeros(2 * d).cuda()
-    sd["posenc.Wr.weight"] = torch.from_numpy(rng.standard_normal((d // HEADS // 2, 2)).astype(np.float32)).cuda()
-    head = f"log_assignment.{LAYERS - 1}."
-    sd[head + "final_proj.weight"], sd[head + "final_proj.bias"] = lin(d, d)
-    sd[head + "matchability.weight"], sd[head + "matchability.bias"] = lin(1, d)
-    return sd
+from scripts.bench_scenes import DIM, HEADS, LAYERS, SIZES, lightglue_inputs, state_dict  # noqa: E402
+from scripts.benchlib import interleaved, parser, us_fields, write_rows  # noqa: E402
 
 
 def torch_layer(torch, sd, i, x0, x1, e0, e1):
@@ -76,28 +45,15 @@ def torch_layer(torch, sd, i, x0, x1, e0, e1):
     return ffn("cross_attn", x0, lin("cross_attn.to_out", m0)), ffn("cross_attn", x1, lin("cross_attn.to_out", m1))
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--repeats", type=int, default=30)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "transformer_layer_bench.jsonl"))
-    args = ap.parse_args()
-    import torch
-
+def rows(args, torch):
     import feature_tracker_amd as F
 
     rng = np.random.default_rng(1)
     sd = state_dict(torch, rng)
     lg = F.LightGlue.from_state_dict(sd, num_heads=HEADS)
     size = (640.0, 480.0)
-    rows = []
     for n in SIZES:
-        x = rng.standard_normal((n, DIM))
-        y = x[rng.permutation(n)] + 0.3 * rng.standard_normal((n, DIM))
-        a = torch.from_numpy((x / np.linalg.norm(x, axis=1, keepdims=True)).astype(np.float32)).cuda()
-        b = torch.from_numpy((y / np.linalg.norm(y, axis=1, keepdims=True)).astype(np.float32)).cuda()
-        kp0 = torch.from_numpy((rng.random((n, 2)) * np.array(size)).astype(np.float32)).cuda()
-        kp1 = torch.from_numpy((rng.random((n, 2)) * np.array(size)).astype(np.float32)).cuda()
+        a, b, kp0, kp1 = lightglue_inputs(torch, rng, n, size)
         e0, e1 = F.rotary_encoding(kp0, size, sd["posenc.Wr.weight"]), F.rotary_encoding(kp1, size, sd["posenc.Wr.weight"])
 
         def torch_all():
@@ -108,24 +64,20 @@ def main():
 
         calls = {"layer": lambda: lg.layers[0](a, b, e0, e1), "torch_layer": lambda: torch_layer(torch, sd, 0, a, b, e0, e1),
                  "lightglue_scores": lambda: lg.scores(kp0, kp1, a, b, size, size), "torch_nine_layers": torch_all}
-        times = {label: [] for label in calls}
-        for _ in range(3):  # interleaved rounds
-            for label, fn in calls.items():
-                times[label] += timed(torch, fn, args.repeats // 3, args.warmup)
+        times = interleaved(torch, calls, args.repeats, args.warmup)
         got, want = lg.layers[0](a, b, e0, e1), torch_layer(torch, sd, 0, a, b, e0, e1)
         row = {"bench": "transformer_layer", "rows": n, "dim": DIM, "heads": HEADS, "layers": LAYERS,
                "max_abs_difference_to_torch": float(max((got[0] - want[0]).abs().max().item(), (got[1] - want[1]).abs().max().item()))}
         for label in calls:
-            row[f"{label}_us_median"] = round(1e6 * float(np.median(times[label])), 1)
-            row[f"{label}_us_min"] = round(1e6 * float(np.min(times[label])), 1)
-        rows.append(row)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    for row in rows:
-        row["device"] = torch.cuda.get_device_name(0)
-        line = json.dumps(row)
-        print(line, flush=True)
-        with open(args.out, "a") as f:
-            f.write(line + "\n")
+            us_fields(row, label, times[label])
+        yield row
+
+
+def main():
+    args = parser("--repeats", 30, 5, os.path.join(ROOT, "profiles", "transformer_layer_bench.jsonl")).parse_args()
+    import torch
+
+    write_rows(rows(args, torch), args.out, append=True, extra={"device": torch.cuda.get_device_name(0)})
 
 
 if __name__ == "__main__":

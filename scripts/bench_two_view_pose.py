@@ -5,17 +5,14 @@ medians of device-synchronised wall times are reported, one JSON line per shape 
 profiles/two_view_pose_bench.jsonl).  No time is asserted anywhere."""
 from __future__ import annotations
 
-import argparse
-import json
 import os
 import sys
-
-import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-K = (512.0, 512.0, 319.5, 239.5)  # the camera of scripts/bench_epipolar.py's scene
+from scripts.bench_scenes import IMAGE, K, two_view_scene  # noqa: E402
+from scripts.benchlib import interleaved, parser, us_fields, write_rows  # noqa: E402
 
 
 def torch_pose(torch, ref_uv, cur_uv, status, threshold, baseline):
@@ -48,21 +45,12 @@ def torch_pose(torch, ref_uv, cur_uv, status, threshold, baseline):
     return R.T, -(R.T @ t) * baseline, points
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--repeats", type=int, default=30)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "two_view_pose_bench.jsonl"))
-    args = ap.parse_args()
-    import torch
-
+def rows(args, torch):
     import feature_tracker_amd as F
-    from scripts.bench_epipolar import IMAGE, scene, timed
 
-    rows = []
     for M in (300, 2000):
         n = int(round(M / 0.7))  # 30 % of the scene are outliers: the filter leaves about M participants
-        ref, cur = scene(n)
+        ref, cur = two_view_scene(n)
         d_ref, d_cur = torch.from_numpy(ref).cuda(), torch.from_numpy(cur).cuda()
         fresh = torch.ones(n, dtype=torch.uint8, device="cuda")
         ransac = F.TwoViewRansac("fundamental", hypotheses=512, threshold=1.0, seed=1)
@@ -89,24 +77,20 @@ def main():
             return torch_pose(torch, d_ref, d_cur, status, 1.0, 1.0)
 
         calls = {"solve": solve_alone, "filter": filter_alone, "filter_solve": filter_then_solve, "torch_solve": torch_alone}
-        times = {name: [] for name in calls}
-        for _ in range(3):  # interleaved rounds
-            for name, fn in calls.items():
-                times[name] += timed(torch, fn, args.repeats // 3, args.warmup)
+        times = interleaved(torch, calls, args.repeats, args.warmup)
         fit = solve_alone()
         row = {"bench": "two_view_pose", "points": n, "participants": int((filtered == 1).sum().item()), "n_points": int(fit.n_points.item()),
                "valid": int(fit.valid.item())}
         for name in calls:
-            row[f"{name}_us_median"] = round(1e6 * float(np.median(times[name])), 1)
-            row[f"{name}_us_min"] = round(1e6 * float(np.min(times[name])), 1)
-        rows.append(row)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    for row in rows:
-        row["device"] = torch.cuda.get_device_name(0)
-        line = json.dumps(row)
-        print(line, flush=True)
-        with open(args.out, "a") as f:
-            f.write(line + "\n")
+            us_fields(row, name, times[name])
+        yield row
+
+
+def main():
+    args = parser("--repeats", 30, 5, os.path.join(ROOT, "profiles", "two_view_pose_bench.jsonl")).parse_args()
+    import torch
+
+    write_rows(rows(args, torch), args.out, append=True, extra={"device": torch.cuda.get_device_name(0)})
 
 
 if __name__ == "__main__":

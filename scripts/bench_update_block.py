@@ -17,17 +17,14 @@ float32 on both sides.  One JSON line per shape:
   flop, fused_tflops                  2 * M * K * pixels over the nine layers and the GRU's twelve
   layers                              per layer: its shape, fused_ms, torch_ms (conv2d + relu [+ the 0.25 pass]), speedup, tflops
 """
-import argparse
-import json
 import os
 import sys
-
-import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import feature_tracker_amd as F  # noqa: E402
 from feature_tracker_amd import _native, raft  # noqa: E402
+from scripts.benchlib import event_times, ms_fields, parser, write_rows  # noqa: E402
 from tests.test_update_block_cpu import GRU_KERNEL_SIZE, layer_shapes, make_inputs, make_state, torch_forward  # noqa: E402
 
 # (name, (net, inp, corr, corr_hidden, corr_out, flow_hidden, flow_out, motion_out, mask_hidden), B, H, W)
@@ -37,33 +34,9 @@ RELU = {"motion_encoder.correlation_conv.0", "motion_encoder.correlation_conv.2"
         "motion_encoder.out_conv.0", "flow_head.conv1", "mask.0"}
 
 
-def time_gpu(torch, fn, calls, warmup):
-    for _ in range(max(warmup, 1)):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(calls):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return float(np.median(ms)), float(np.percentile(ms, 10)), float(np.percentile(ms, 90))
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--calls", type=int, default=100)
-    ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
-    import torch
-
+def rows(args, torch):
     dev = torch.device("cuda")
     Fn = torch.nn.functional
-    build = _native.build_info().get("source_hash", "?")
-    rows = []
     for name, widths, B, H, W in SHAPES:
         state = {k: v.to(dev) for k, v in make_state(widths, 1).items()}
         block = F.UpdateBlock.from_state_dict(state, prefix="")
@@ -71,8 +44,8 @@ def main():
         ctx = raft._context(torch.cuda.current_device())
         pixels = B * H * W
         with torch.no_grad():
-            fused = time_gpu(torch, lambda: block(*inputs), args.calls, args.warmup)
-            stock = time_gpu(torch, lambda: torch_forward(state, *inputs), args.calls, args.warmup)
+            fused = event_times(torch, [lambda: block(*inputs)], args.calls, args.warmup)
+            stock = event_times(torch, [lambda: torch_forward(state, *inputs)], args.calls, args.warmup)
             diff = max(float((a - b).abs().max()) for a, b in zip(block(*inputs), torch_forward(state, *inputs)[:3]))
             layers, flop = [], 0
             g = torch.Generator().manual_seed(7)
@@ -90,25 +63,30 @@ def main():
                     y = Fn.relu(y) if relu else y
                     return .25 * y if scale != 1.0 else y
 
-                t_ours, t_theirs = time_gpu(torch, ours, args.calls, args.warmup), time_gpu(torch, theirs, args.calls, args.warmup)
+                t_ours, t_theirs = event_times(torch, [ours], args.calls, args.warmup), event_times(torch, [theirs], args.calls, args.warmup)
                 f = 2 * M * Cin * ks * ks * pixels
                 flop += f
-                layers.append({"layer": layer, "out_channels": M, "in_channels": Cin, "kernel_size": ks, "fused_ms": round(t_ours[0], 4),
-                               "torch_ms": round(t_theirs[0], 4), "speedup_vs_torch": round(t_theirs[0] / t_ours[0], 2),
-                               "fused_tflops": round(f / (t_ours[0] * 1e-3) / 1e12, 3), "max_abs_vs_torch": float((ours() - theirs()).abs().max())})
+                entry = {"layer": layer, "out_channels": M, "in_channels": Cin, "kernel_size": ks}
+                ms_fields(entry, "fused", t_ours)
+                ms_fields(entry, "torch", t_theirs)
+                entry.update({"speedup_vs_torch": round(t_theirs[0] / t_ours[0], 2), "fused_tflops": round(f / (t_ours[0] * 1e-3) / 1e12, 3),
+                              "max_abs_vs_torch": float((ours() - theirs()).abs().max())})
+                layers.append(entry)
         net, inp, motion_out = widths[0], widths[1], widths[7]
         flop += 2 * 2 * 3 * net * (inp + motion_out + net) * GRU_KERNEL_SIZE * pixels
-        row = {"shape": name, "widths": list(widths), "B": B, "H": H, "W": W,
-               "fused_ms": round(fused[0], 4), "fused_ms_p10": round(fused[1], 4), "fused_ms_p90": round(fused[2], 4),
-               "torch_ms": round(stock[0], 4), "torch_ms_p10": round(stock[1], 4), "torch_ms_p90": round(stock[2], 4),
-               "fused_speedup_vs_torch": round(stock[0] / fused[0], 2), "not_slower": bool(fused[0] <= stock[0] + (stock[2] - stock[1])),
-               "max_abs_vs_torch": diff, "flop": flop, "fused_tflops": round(flop / (fused[0] * 1e-3) / 1e12, 3), "layers": layers, "build": build}
-        print(json.dumps(row), flush=True)
-        rows.append(row)
-    if args.out:
-        with open(args.out, "w") as f:
-            for row in rows:
-                f.write(json.dumps(row) + "\n")
+        row = {"shape": name, "widths": list(widths), "B": B, "H": H, "W": W}
+        ms_fields(row, "fused", fused, spread=True)
+        ms_fields(row, "torch", stock, spread=True)
+        row.update({"fused_speedup_vs_torch": round(stock[0] / fused[0], 2), "not_slower": bool(fused[0] <= stock[0] + (stock[2] - stock[1])),
+                    "max_abs_vs_torch": diff, "flop": flop, "fused_tflops": round(flop / (fused[0] * 1e-3) / 1e12, 3), "layers": layers})
+        yield row
+
+
+def main():
+    args = parser("--calls", 100, 10).parse_args()
+    import torch
+
+    write_rows(rows(args, torch), args.out, append=False, extra={"build": _native.build_info().get("source_hash", "?")})
 
 
 if __name__ == "__main__":
