@@ -243,7 +243,9 @@ class DeviceKlt:
     def track(self, ref_uv, cur_uv_in, status_in, cur_uv_out, status_out, iters=None, max_track_points=None):
         """``max_track_points`` overrides the options' cap for this launch (a shard's share of the global cap).
         Tensors: ref_uv, cur_uv_in, cur_uv_out: contiguous float32 [n, 2]; status_in, status_out: uint8 [n]; iters: int32 [n] or None; the
-        out tensors may alias the in tensors.  A strided view, another dtype or a short buffer is a ValueError, never a copy."""
+        out tensors may alias the in tensors.  A strided view, another dtype or a short buffer is a ValueError, never a copy.
+        Every element of cur_uv_out, status_out and iters is written: a feature that arrives with a status above tracked, or lies beyond
+        the cap, gets its cur_uv_in and status_in copied and 0 iterations, so nothing depends on what the out tensors held."""
         n, dev = self._check_in(ref_uv, cur_uv_in, status_in, iters)
         self._check_out(n, dev, cur_uv_out, status_out)
         opt = self.opt

@@ -8,7 +8,8 @@ check fails as "native call reached" and no bad pointer ever reaches a kernel.
 
 Part B, what must keep working, bit for bit against the oracle: every tensor of a call a view into a larger allocation at a non-zero
 offset (with the bytes around every output left alone), int32 and uint32 words, out tensors aliasing in tensors, one-row inputs,
-empty inputs, and the caller's remedy for a refused view, ``.contiguous()``."""
+empty inputs, and the caller's remedy for a refused view, ``.contiguous()``.  The views here are misaligned and their tails short; exact
+sizes, whole-row overruns and what an output held before the call are tests/test_sparse_entries_guarded_gpu.py's, on 256-byte aligned payloads."""
 import types
 
 import numpy as np
